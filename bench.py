@@ -37,6 +37,10 @@ Besides the contract fields the JSON line carries
                   run carries config 3 and its N = 8 run config 4, with its OWN `roofline`
                   (dominant class, PMC traffic) and, at N = 1, its own `parity` / `cpu_baseline`
                   against the CPU oracle on 8 of its utterances.  Never mixed into `value`.
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step of each timed configuration returned:
+<prefix>logits.npy (B, 2) and <prefix>scores.npy, float32, prefix "" (headline), "contract_", "config3_", "config3_contract_".
+Weights and waveforms are seeded, so two builds run with the same arguments can be compared file by file.
 """
 import argparse
 import json
@@ -294,7 +298,11 @@ def main():
     ap.add_argument("--force-lanes", action="store_true", help="issue the two-lanes form (whole forwards on alternating streams) without the probe")
     ap.add_argument("--no-config3", action="store_true", help="skip the teacher (BASELINE configs[2]/[3]) side measurement")
     ap.add_argument("--allow-parity-miss", action="store_true", help="report, do not fail, when the parity sample misses 1e-3")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of every timed configuration returned (logits, scores; float32) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -334,9 +342,11 @@ def main():
 
         def step():
             if not overlapped:
-                scores = w["eng"].forward(w["wave"])[:, 1]
+                w["logits"] = w["eng"].forward(w["wave"])
+                scores = w["logits"][:, 1]
                 return all_gather_scores(idx, scores, world) if use_dist else (idx, scores)
-            scores = w["eng"].forward_overlapped(w["wave"])[:, 1]
+            w["logits"] = w["eng"].forward_overlapped(w["wave"])
+            scores = w["logits"][:, 1]
             if use_dist:  # the collective follows the logits on THEIR stream: the next trunk does not wait for it
                 with torch.cuda.stream(w["eng"].last_stream):
                     out = all_gather_scores(idx, scores, world)
@@ -376,7 +386,9 @@ def main():
     ISSUE = {"two_stream": "back-end of step i on a side stream under the trunk of step i+1 (the scoring loop's form)", "one_stream": "one stream",
              "two_lanes": "two steps in flight: whole forwards of consecutive steps on alternating streams (the scoring loop's form)"}
 
-    def measure(w, workload, dtype):
+    outputs = {}  # --dump-outputs: name -> what the last timed step of a configuration returned
+
+    def measure(w, workload, dtype, name):
         """Warm-up, K timed steps (barriers, max over ranks), then the instrumented roofline pass: the fields every
         timed configuration of this file carries."""
         ov, probe = pick_issue(w)  # (the form's name)
@@ -384,6 +396,9 @@ def main():
         el, dms, out = time_steps(st, args.steps, args.warmup, use_dist, dist, join=jn)
         if use_dist:
             assert out[0].numel() == world * w["B"]
+        if args.dump_outputs:  # (time_steps joined and synchronised: the K-th step is complete)
+            outputs[name + "logits"] = w["logits"].cpu()  # this rank's (B, 2) logits
+            outputs[name + "scores"] = out[1].cpu()  # bonafide scores, every rank's under a process group
         roof, brk = roofline_of(w, workload, dtype, args.steps)
         w["eng"].check_finite()  # (an operand overflow in any step above is an error, not a rate)
         val = world * w["B"] * args.steps / el
@@ -400,10 +415,10 @@ def main():
                      "holds whatever the checkpoint's top-k gaps (48 / 48 teacher utterances, 4096-trial student EER: tests/test_gpu_teacher.py, "
                      "tests/test_gpu_models.py); same protocol, same utterances, roofline against 2.5 PF / 3")
 
-    def contract_of(workload, sd, oracle):
+    def contract_of(workload, sd, oracle, name):
         """The same protocol in the contract-holding precision, on the same weights and utterances."""
         c = build(workload, "fp16x3", None, 4.0, rank, sd=sd)
-        r = measure(c, workload, "fp16x3")
+        r = measure(c, workload, "fp16x3", name)
         r["note"] = CONTRACT_NOTE
         if oracle is not None:
             r["parity"] = parity_of(c, oracle[1], oracle[2])
@@ -412,7 +427,7 @@ def main():
 
     default_run = args.workload == "conformer_student" and args.seconds == 4.0 and args.batch is None and args.dtype == "fp16"
     w = build(args.workload, args.dtype, args.batch, args.seconds, rank)
-    m = measure(w, args.workload, args.dtype)
+    m = measure(w, args.workload, args.dtype, "")
     eng, wave, B, L = w["eng"], w["wave"], w["B"], w["L"]
 
     result = {
@@ -476,7 +491,7 @@ def main():
     del eng, wave, w
     torch.cuda.empty_cache()
     if default_run:
-        result["contract"] = contract_of(args.workload, sd, oracle)
+        result["contract"] = contract_of(args.workload, sd, oracle, "contract_")
         torch.cuda.empty_cache()
 
     # ---- BASELINE configs[2] (N = 1) / configs[3] (N = 8): the XLS-R-24 + AASIST teacher at batch 16 per GPU, timed by
@@ -486,7 +501,7 @@ def main():
     # effect config 3's contract is about.  Head weights do not change any kernel's time.
     if args.workload == "conformer_student" and not args.no_config3 and args.seconds == 4.0 and args.batch is None:
         t = build("xlsr_aasist", args.dtype, None, 4.0, rank, head_scale=1.5)
-        c3 = measure(t, "xlsr_aasist", args.dtype)
+        c3 = measure(t, "xlsr_aasist", args.dtype, "config3_")
         c3["workload"] = (f"xlsr_aasist: XLSR_AASIST (24-layer XLS-R trunk), batch {t['B']} per GPU, 4 s clips @ 16 kHz, random-init weights, lively head (x 1.5)"
                           + (f", dp{world} (BASELINE configs[3] at N = 8)" if world > 1 else " (BASELINE configs[2])"))
         t_oracle = None
@@ -502,8 +517,14 @@ def main():
         del t
         torch.cuda.empty_cache()
         if args.dtype == "fp16":
-            c3["contract"] = contract_of("xlsr_aasist", t_sd, t_oracle)
+            c3["contract"] = contract_of("xlsr_aasist", t_sd, t_oracle, "config3_contract_")
         result["config3"] = c3
+    if rank == 0 and args.dump_outputs:
+        # seeded weights and waveforms: the same arguments give the same inputs on every run, so two builds compare file by file
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr.numpy().astype(np.float32))
     if rank == 0:
         print(json.dumps(result))
     if use_dist:

@@ -10,6 +10,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -50,8 +51,8 @@ def _check_probe(r):
     assert r["issue"].startswith(FORMS[p["issued"]])
 
 
-def test_bench_line_carries_the_contract():
-    d = _bench("--steps", "4", "--warmup", "2", "--cpu-sample", "2")
+def test_bench_line_carries_the_contract(tmp_path):
+    d = _bench("--steps", "4", "--warmup", "2", "--cpu-sample", "2", "--dump-outputs", str(tmp_path))
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
                 "dtype", "data", "config", "roofline", "cpu_baseline", "parity", "config3", "contract", "issue_probe"):
         assert key in d, key
@@ -83,6 +84,11 @@ def test_bench_line_carries_the_contract():
     assert all(kc["parity"]["same_topk"]) and kc["parity"]["max_abs_dlogit_vs_oracle"] <= 2e-5 and kc["parity"]["feature_rel_l2_max"] <= 2e-5
     _check_probe(c)
     _check_probe(kc)
+    # --dump-outputs: the last timed step of every timed configuration, finite float32, scores = column 1 of the logits
+    for prefix, B in (("", 64), ("contract_", 64), ("config3_", 16), ("config3_contract_", 16)):
+        logits, scores = np.load(tmp_path / f"{prefix}logits.npy"), np.load(tmp_path / f"{prefix}scores.npy")
+        assert logits.dtype == scores.dtype == np.float32 and logits.shape == (B, 2) and scores.shape == (B,)
+        assert np.isfinite(logits).all() and np.array_equal(scores, logits[:, 1])
 
 
 def test_bench_under_rccl_issues_the_faster_form():
