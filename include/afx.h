@@ -135,6 +135,16 @@ void afx_kv_destroy(afx_kv* kv);
 size_t afx_kv_state_bytes(const afx_kv* kv);
 size_t afx_kv_workspace_bytes(const afx_kv* kv, int n_frames);
 int afx_kv_step(afx_kv* kv, const float* feats6, int n_frames, float* logits, void* ws, size_t ws_bytes, void* stream);
+/* Per-stream sessions: every stream still brings one chunk per step, but streams start at different steps.
+ * afx_kv_reset makes the listed slots (distinct, 0 <= slot < n_streams) begin a new stream with the next step: their
+ * cached keys / values, positional-conv context and feature window are dropped.  afx_kv_step_ragged takes the chunks as
+ * (n_streams, n_max, 512) fp32 with stream b's n_frames[b] (host array, 1 <= n_frames[b] <= n_max <= 16) frames first;
+ * each stream's logits equal, bit for bit, those of the same stream stepped from its reset in a fresh afx_kv.  Once
+ * either is called, the state is per stream and afx_kv_step refuses it. */
+int afx_kv_reset(afx_kv* kv, const int* slots, int n_slots, void* stream);
+size_t afx_kv_ragged_workspace_bytes(const afx_kv* kv, int n_max);
+int afx_kv_step_ragged(afx_kv* kv, const float* feats6, int n_max, const int* n_frames, float* logits, void* ws, size_t ws_bytes,
+                       void* stream);
 /* back-end alone from given SSL features (B,T,1024) fp32 -> logits (B,2) */
 int afx_head_forward(afx_handle h, const float* feats, int B, int T, float* logits, void* ws, size_t ws_bytes,
                      void* stream);

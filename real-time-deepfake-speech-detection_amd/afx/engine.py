@@ -516,8 +516,9 @@ class KVState:
                 pass
             self._k = None
 
-    def step(self, feats6):
-        """feats6: (S, n, 512) fp32, the n (1..16) NEW frames of conv layer 6 -> logits (S, 2)."""
+    def step(self, feats6, n_frames=None):
+        """feats6: (S, n, 512) fp32, the n (1..16) NEW frames of conv layer 6 -> logits (S, 2).  n_frames (per-stream
+        sessions): S counts, stream b's n_frames[b] (1..n) new frames first in its n rows (afx_kv_step_ragged)."""
         eng = self.engine
         eng._on_device(feats6, "conv-layer-6 frames")
         f = feats6.to(torch.float32).contiguous()
@@ -526,8 +527,22 @@ class KVState:
         n = f.shape[1]
         l = lib()
         with torch.cuda.device(eng.device):
-            ws = eng._workspace(max(l.afx_kv_workspace_bytes(self._k, n), 256))
             out = torch.empty(self.S, 2, dtype=torch.float32, device=eng.device)
-            check(l.afx_kv_step(self._k, ptr(f), n, ptr(out), ptr(ws), ws.numel(), eng._stream()))
+            if n_frames is None:
+                ws = eng._workspace(max(l.afx_kv_workspace_bytes(self._k, n), 256))
+                check(l.afx_kv_step(self._k, ptr(f), n, ptr(out), ptr(ws), ws.numel(), eng._stream()))
+            else:
+                nf = [int(v) for v in n_frames]
+                if len(nf) != self.S:
+                    raise ValueError(f"n_frames: one count per stream ({self.S}), got {len(nf)}")
+                ws = eng._workspace(max(l.afx_kv_ragged_workspace_bytes(self._k, n), 256))
+                check(l.afx_kv_step_ragged(self._k, ptr(f), n, (C.c_int * self.S)(*nf), ptr(out), ptr(ws), ws.numel(), eng._stream()))
         return out
+
+    def reset(self, slots):
+        """The listed slots (distinct stream indices) begin a new stream with the next ``step`` (afx_kv_reset).  From the
+        first reset on, the state is per stream: continue with ``step(feats6, n_frames)``."""
+        idx = [int(v) for v in slots]
+        with torch.cuda.device(self.engine.device):
+            check(lib().afx_kv_reset(self._k, (C.c_int * max(len(idx), 1))(*idx), len(idx), self.engine._stream()))
 

@@ -27,6 +27,13 @@ Per stream the state is a sample ring (256 KB, used while the window fills and b
 (< 5 KB) and the layer-5 ring (399 x 512 halfs = 408 KB).  Streams are pinned to a GPU; nothing is exchanged between
 GPUs (tools/stream_bench.py --gpus N runs one process per GPU over its own streams).  Real-time factor = time per hop /
 hop duration.
+
+Sessions: every ``push`` brings one hop for EVERY slot (the server ticks at the hop rate; an idle slot is fed anything and
+its score ignored), and ``reset(slots)`` makes the named slots begin a new stream with their next push -- their history,
+conv carries and layer-5 frames are dropped, the other slots are untouched.  A slot reset before tick t0 emits at tick
+t0 + j, bit for bit, the score it would emit at tick j of a fresh scorer with the same number of slots fed the same audio
+from tick 0 (every kernel behind a score is row-wise and accumulates a row in one order whatever the batch: a slot's
+score does not depend on the other slots' audio or phase).  ``samples_seen`` counts each slot's samples since its reset.
 """
 import torch
 
@@ -46,27 +53,82 @@ class SlidingWindowScorer:
         self.model, self.S, self.window, self.hop = model, n_streams, window, hop
         self.ring = torch.zeros(n_streams, window, dtype=torch.float32, device=device)
         self.device = self.ring.device  # every launch of a push() goes to THIS GPU, whatever torch's current device is
-        self.total = 0  # samples received per stream (streams advance in lockstep)
+        self.total = 0  # samples pushed since construction (every slot receives one hop per push)
+        self._seen = torch.zeros(n_streams, dtype=torch.int64)  # samples per slot since its last reset (host)
+        self._uniform = True  # every slot at the same phase: the lockstep path
         self._offs = (torch.arange(n_streams + 1, dtype=torch.int64) * window).to(device)
         self._starts = torch.zeros(n_streams, dtype=torch.int64, device=device)
         self._batch = torch.empty(n_streams, window, dtype=torch.float32, device=device)
 
+    @property
+    def samples_seen(self):
+        """(S,) int64: the samples each slot received since its last ``reset`` (or since construction)."""
+        return self._seen.clone()
+
+    def _slot_list(self, slots):
+        """``slots``: slot indices or a bool mask of length S -> sorted list of distinct indices; bad input is a ValueError."""
+        t = torch.as_tensor(slots)
+        if t.numel() == 0 and t.ndim <= 1:
+            return []
+        if t.dtype == torch.bool:
+            if t.shape != (self.S,):
+                raise ValueError(f"a slot mask has {self.S} entries, got shape {tuple(t.shape)}")
+            return t.nonzero().flatten().tolist()
+        if t.is_floating_point() or t.is_complex() or t.ndim > 1:
+            raise ValueError("slots: a list of slot indices or a bool mask")
+        idx = [int(i) for i in t.reshape(-1).tolist()]
+        bad = [i for i in idx if not 0 <= i < self.S]
+        if bad:
+            raise ValueError(f"slot index {bad[0]} outside 0..{self.S - 1}")
+        if len(set(idx)) != len(idx):
+            raise ValueError("a slot is named twice")
+        return sorted(idx)
+
+    def reset(self, slots):
+        """The named slots (indices or a bool mask) begin a new stream with their next ``push``; the others are untouched."""
+        idx = self._slot_list(slots)
+        if idx:
+            self._reset_slots(idx)
+            self._uniform = bool((self._seen == self._seen[0]).all())
+
+    def _reset_slots(self, idx):
+        self._seen[idx] = 0
+
     def _store(self, chunk):
         if chunk.shape != (self.S, self.hop) or not chunk.is_cuda:
             raise ValueError(f"expected a CUDA tensor of shape {(self.S, self.hop)}")
-        pos = self.total % self.window
-        first = min(self.hop, self.window - pos)
-        self.ring[:, pos:pos + first] = chunk[:, :first]
-        if first < self.hop:
-            self.ring[:, : self.hop - first] = chunk[:, first:]
+        if self._uniform:
+            pos = int(self._seen[0]) % self.window
+            first = min(self.hop, self.window - pos)
+            self.ring[:, pos:pos + first] = chunk[:, :first]
+            if first < self.hop:
+                self.ring[:, : self.hop - first] = chunk[:, first:]
+        else:  # each slot writes at its own phase: a slot's history starts at ring column 0 from its reset on (phases never
+            # re-align once a slot has been reset, so this path stays for the scorer's life)
+            pos = (self._seen % self.window).to(self.ring.device, non_blocking=True)
+            col = (pos[:, None] + torch.arange(self.hop, device=self.ring.device)) % self.window
+            self.ring.scatter_(1, col, chunk.to(self.ring.dtype))
         self.total += self.hop
+        self._seen += self.hop
+
+    def _warm_windows(self, idx):
+        """The tiled history (reference pad policy) of the slots ``idx``, each shorter than the window."""
+        return harness.batch_adjust_duration([self.ring[s, : int(self._seen[s])] for s in idx], self.window, device=self.ring.device)
 
     def _window_batch(self):
-        if self.total < self.window:  # warm-up: the history so far, repeated (reference pad policy)
-            return harness.batch_adjust_duration([self.ring[s, : self.total] for s in range(self.S)], self.window)
-        self._starts.fill_(self.total % self.window)  # steady state: one batched ring read, oldest sample first
+        if self._uniform:
+            seen = int(self._seen[0])
+            if seen < self.window:  # warm-up: the history so far, repeated (reference pad policy)
+                return self._warm_windows(range(self.S))
+            self._starts.fill_(seen % self.window)  # steady state: one batched ring read, oldest sample first
+        else:
+            self._starts.copy_(self._seen % self.window)
         check(call_on(self.ring, lib().afx_k_tile_crop, ptr(self.ring), ptr(self._offs), ptr(self._starts), self.S, self.window,
                                     ptr(self._batch)))
+        if not self._uniform:
+            warm = (self._seen < self.window).nonzero().flatten().tolist()
+            if warm:  # slots whose session is younger than the window: their tiled history replaces the ring read
+                self._batch[warm] = self._warm_windows(warm)
         return self._batch
 
     def push(self, chunk):
@@ -144,11 +206,49 @@ class IncrementalScorer(SlidingWindowScorer):
 
     def _advance(self, chunk):
         """Feed `hop` new samples through conv layers 0-5; only frames that became computable are produced."""
-        x = torch.cat([self.carry[0], chunk], dim=1)
+        self._n5 = None  # layer-5 frames per slot when they differ (a first hop among steady slots), else None
+        if self._uniform:
+            return self._advance_rows(chunk, self.carry)
+        # mixed tick: slots on the first hop of a session start from empty carries, the others from theirs -- one
+        # sub-batch each; a first hop completes fewer layer-5 frames, which join the others right-aligned
+        first = (self._seen == self.hop).nonzero().flatten().tolist()  # (_store has counted this hop)
+        if not first:
+            return self._advance_rows(chunk, self.carry)
+        dev = chunk.device
+        rest = (self._seen != self.hop).nonzero().flatten().tolist()
+        ia, ib = torch.tensor(first, device=dev), torch.tensor(rest, device=dev)
+        ca = [c.new_empty(len(first), 0, *c.shape[2:]) for c in self.carry]
+        cb = [c.index_select(0, ib) for c in self.carry]
+        ya = self._advance_rows(chunk.index_select(0, ia), ca)
+        yb = self._advance_rows(chunk.index_select(0, ib), cb)
+        for i in range(6):
+            if ca[i].shape[1:] != cb[i].shape[1:]:
+                raise RuntimeError("conv carries of a new session differ from the steady state's: hop / stride mismatch")
+            c = cb[i].new_empty(self.S, *cb[i].shape[1:])
+            c[ia], c[ib] = ca[i], cb[i]
+            self.carry[i] = c
+        na = 0 if ya is None else ya.shape[1]
+        nb = 0 if yb is None else yb.shape[1]
+        if na > nb:
+            raise RuntimeError("a first hop completed more layer-5 frames than a steady one")
+        if nb == 0:
+            return None
+        y = yb.new_zeros(self.S, nb, yb.shape[2])
+        y[ib] = yb
+        if na:
+            y[ia, nb - na:] = ya
+        self._n5 = [nb] * self.S
+        for b in first:
+            self._n5[b] = na
+        return y
+
+    def _advance_rows(self, chunk, carry):
+        """_advance on the rows of ``chunk`` with their carries ``carry`` (a list, updated in place)."""
+        x = torch.cat([carry[0], chunk], dim=1)
         for i, (k, s) in enumerate(CONV_KS[:6]):
             n_in = x.shape[1]
             n_out = (n_in - k) // s + 1 if n_in >= k else 0
-            self.carry[i] = x[:, n_out * s:].contiguous()  # the unconsumed tail: k - s frames in steady state
+            carry[i] = x[:, n_out * s:].contiguous()  # the unconsumed tail: k - s frames in steady state
             if n_out == 0:
                 return None
             xin = x  # (the kernels derive n_out from the row count themselves and read nothing past the last window: no slice copy)
@@ -157,8 +257,13 @@ class IncrementalScorer(SlidingWindowScorer):
             else:
                 y = self._conv_ln_gelu(xin, self.cw[i], k, s, self.cb[i], self.lg[i], self.lb[i])
             if i < 5:
-                x = torch.cat([self.carry[i + 1], y], dim=1)
+                x = torch.cat([carry[i + 1], y], dim=1)
         return y
+
+    def _reset_slots(self, idx):
+        super()._reset_slots(idx)
+        if bool((self._seen == 0).all()):  # every slot starts afresh: the lockstep path from empty carries
+            self.carry = [c[:, :0].contiguous() for c in self.carry]
 
     def _conv_ln_gelu(self, xin, wp, k, s, bias, gamma, beta, fp32_out=False):
         """Conv1d(512 -> 512) + LayerNorm + GELU on (S, Tin, 512) frames: one fused kernel for the half-precision operand types;
@@ -175,11 +280,22 @@ class IncrementalScorer(SlidingWindowScorer):
         new5 = self._advance(chunk)
         if new5 is not None:
             self._l5_append(new5)
-        if self.total < self.window:  # the window is still filling: the reference would be given the tiled history
-            out = self.eng.forward(self._window_batch())
-        else:
-            assert self.l5.shape[1] == self.T5
-            out = self.eng.tail(self.l5)
+        warm = self._seen < self.window  # the window is still filling: the reference would be given the tiled history
+        if self._uniform or bool(warm.all()) or not bool(warm.any()):
+            if bool(warm[0]):
+                out = self.eng.forward(self._window_batch())
+            else:
+                assert self.l5.shape[1] == self.T5
+                out = self.eng.tail(self.l5)
+            return out[:, 1]
+        # mixed tick: the slots still warming up through the whole forward on their tiled windows, the others through the tail
+        iw, it = warm.nonzero().flatten().tolist(), (~warm).nonzero().flatten().tolist()
+        dev = self.eng.device
+        out = torch.empty(self.S, 2, dtype=torch.float32, device=dev)
+        out[torch.tensor(iw, device=dev)] = self.eng.forward(self._warm_windows(iw))
+        assert self.l5.shape[1] == self.T5
+        ti = torch.tensor(it, device=dev)
+        out[ti] = self.eng.tail(self.l5.index_select(0, ti))
         return out[:, 1]
 
 
@@ -196,7 +312,11 @@ class KVCachedScorer(IncrementalScorer):
     the cost: 12.5 new frames per hop through 24 layers instead of 199 (tools/stream_bench.py).
 
     Conv layers 0-5 advance exactly as in IncrementalScorer; layer 6 advances the same way (its stride-2 window over
-    the layer-5 frames carries 0 or 1 frame between hops), giving the 12 or 13 new frames a 250-ms chunk completes."""
+    the layer-5 frames carries 0 or 1 frame between hops), giving the 12 or 13 new frames a 250-ms chunk completes.
+
+    Sessions: after the first ``reset`` the conv-layer-6 carries are per slot (slots at different phases complete 12 or 13
+    frames in the same hop) and every hop goes through the library's per-stream step (afx_kv_step_ragged: per-stream
+    valid counts, base groups and windows)."""
 
     _exact_conv_ok = True  # dtype "fp16x3": every hop within 1e-3 of the offline restatement whatever the top-k gaps (round 4)
 
@@ -213,15 +333,61 @@ class KVCachedScorer(IncrementalScorer):
         # (this mode never re-scores a window: the sample ring and the layer-5 window of the exact-reuse scorer are not kept)
         self.ring = self._batch = self._l5_buf = None
         self.kv = engine.kv_state(n_streams)
-        self.frames = 0  # conv-layer-6 frames consumed so far (per stream)
+        self.frames = 0  # conv-layer-6 frames consumed so far (per stream, while the streams are lock-stepped)
+        self._sessions = False  # after the first reset: per-slot conv-layer-6 carries and the library's per-stream step
+        self._n5 = None
+
+    def _reset_slots(self, idx):
+        if not self._sessions:  # the lock-stepped carries become per-slot ones (width 0 or 1 frame each)
+            w = self.carry6.shape[1]
+            self._c6 = self.carry6.new_zeros(self.S, 1, 512)
+            if w:
+                self._c6[:, :w] = self.carry6
+            self._c6w = [w] * self.S
+            self._sessions = True
+        self.kv.reset(idx)
+        for b in idx:
+            self._c6w[b] = 0
+        super()._reset_slots(idx)
+
+    def _step_sessions(self, new5):
+        """Conv layer 6 per slot -- a slot's frames and carry depend on its own phase (12 or 13 frames per hop from its own
+        first sample) -- one sub-batch per (carry, new frames) pair, then the library's per-stream step."""
+        nb = new5.shape[1]
+        n5 = self._n5 if self._n5 is not None else [nb] * self.S
+        groups = {}
+        for b in range(self.S):
+            groups.setdefault((self._c6w[b], n5[b]), []).append(b)
+        outs, n6 = [], [0] * self.S
+        for (c, f), idx in groups.items():
+            n_out = (c + f - 2) // 2 + 1 if c + f >= 2 else 0
+            if n_out < 1:
+                raise RuntimeError("a hop completed no conv-layer-6 frame for some slot")
+            it = torch.tensor(idx, device=new5.device)
+            x = torch.cat([self._c6.index_select(0, it)[:, :c], new5.index_select(0, it)[:, nb - f:]], dim=1)
+            y = self._conv_ln_gelu(x, self.cw6, 2, 2, self.cb6, self.lg6, self.lb6, fp32_out=True)
+            rest = c + f - 2 * n_out
+            if rest:
+                self._c6[it, :rest] = x[:, 2 * n_out:]
+            for b in idx:
+                self._c6w[b], n6[b] = rest, n_out
+            outs.append((it, y))
+        n_max = max(n6)
+        f6 = torch.zeros(self.S, n_max, 512, dtype=torch.float32, device=new5.device)
+        for it, y in outs:
+            f6[it, :y.shape[1]] = y
+        return self.kv.step(f6, n_frames=n6)[:, 1]
 
     def _push(self, chunk):
         if chunk.shape != (self.S, self.hop) or not chunk.is_cuda:
             raise ValueError(f"expected a CUDA tensor of shape {(self.S, self.hop)}")
         self.total += self.hop
+        self._seen += self.hop
         new5 = self._advance(chunk)
         if new5 is None:
             return None
+        if self._sessions:
+            return self._step_sessions(new5)
         x = torch.cat([self.carry6, new5], dim=1)
         n_out = (x.shape[1] - 2) // 2 + 1 if x.shape[1] >= 2 else 0
         self.carry6 = x[:, n_out * 2:].contiguous()

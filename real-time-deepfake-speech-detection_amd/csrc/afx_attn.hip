@@ -37,10 +37,15 @@ struct MhsaRing {
   int q_tile;
   unsigned char cnt[16];
 };
+// RING == 2 (per-stream sessions, afx_kv_step_ragged): the valid counts come per stream from a device table instead of
+// ring.cnt -- `lens` then points at (S, 8) ints per stream: [0] = the stream's base group (the group of its first chunk),
+// ints [4, 8) = its 16 valid counts as bytes -- and the 256 slots are visited rotated by the base group: key i is slot
+// (((i >> 4) + base) & 15) * 16 + (i & 15).  Key and summation order are then those of a stream that started at group 0.
+__device__ __forceinline__ int ring_slot(int key, int base) { return ((((key >> 4) + base) & 15) << 4) | (key & 15); }
 // VTR (round 3): V stays ROW-major in LDS (staged exactly like K: one swizzled 16-byte write per loaded chunk, no transposing
 // scatter) and the V^T fragments of P.V come from `ds_read_b64_tr_b16` -- per 16-lane group a block of 4 keys x 16 dims delivered
 // column-major, i.e. lane (dim) gets its 4 consecutive keys, the same registers the V^T image gave.
-template <class HT, int KS, int NW, bool RING = false, bool VTR = false>  // KS = number of 32-key steps actually computed
+template <class HT, int KS, int NW, int RING = 0, bool VTR = false>  // KS = number of 32-key steps actually computed
 __global__ __launch_bounds__(64 * NW, NW > 4 ? 4 : 2) void mhsa_kernel(const typename HT::T* __restrict__ qkv,
                                                    typename HT::T* __restrict__ out, int T, int H, float scale,
                                                    const int* __restrict__ lens, MhsaRing ring) {
@@ -61,7 +66,9 @@ __global__ __launch_bounds__(64 * NW, NW > 4 ? 4 : 2) void mhsa_kernel(const typ
   // Ragged batch (key-padding mask): utterance b has lens[b] valid frames of the Trow rows it owns in memory; from
   // here on T is ITS length -- keys beyond it are staged as zeros and masked, queries beyond it are not computed.
   const int Trow = T;
-  if (lens) T = lens[b];
+  if (RING != 2 && lens) T = lens[b];
+  const unsigned char* scnt = RING == 2 ? (const unsigned char*)(lens + (long)b * 8 + 4) : nullptr;
+  const int sbase = RING == 2 ? lens[(long)b * 8] : 0;
   const Tt* base = qkv + (long)b * Trow * ld + h * 64;
   const Tt* kbase = base + (long)H * 64;
   const Tt* vbase = base + 2L * H * 64;
@@ -84,10 +91,11 @@ __global__ __launch_bounds__(64 * NW, NW > 4 ? 4 : 2) void mhsa_kernel(const typ
       kreg[it] = u32x4{0u, 0u, 0u, 0u};
 #pragma unroll
       for (int i = 0; i < 8; ++i) vreg[it][i] = (Tt)0.f;
-      const bool live = RING ? (key & 15) < ring.cnt[(key >> 4) & 15] : key < T;
+      const int slot = RING == 2 ? ring_slot(key, sbase) : key;
+      const bool live = RING == 2 ? (slot & 15) < scnt[slot >> 4] : RING ? (key & 15) < ring.cnt[(key >> 4) & 15] : key < T;
       if (live && !(MHSA_DBG & 1)) {
-        kreg[it] = *(const u32x4*)(kbase + (long)key * ld + c * 8);
-        vreg[it] = *(const V8*)(vbase + (long)key * ld + c * 8);
+        kreg[it] = *(const u32x4*)(kbase + (long)slot * ld + c * 8);
+        vreg[it] = *(const V8*)(vbase + (long)slot * ld + c * 8);
       }
     }
 #pragma unroll
@@ -120,7 +128,8 @@ __global__ __launch_bounds__(64 * NW, NW > 4 ? 4 : 2) void mhsa_kernel(const typ
       }
     }
   }
-  for (int i = tid; i < KEYS; i += 64 * NW) mask_lds[i] = (RING ? (i & 15) < ring.cnt[(i >> 4) & 15] : i < T) ? 0.f : -1e30f;
+  for (int i = tid; i < KEYS; i += 64 * NW)
+    mask_lds[i] = (RING == 2 ? (i & 15) < scnt[ring_slot(i, sbase) >> 4] : RING ? (i & 15) < ring.cnt[(i >> 4) & 15] : i < T) ? 0.f : -1e30f;
   __syncthreads();
   if (MHSA_DBG & 2) return;
 
@@ -302,7 +311,7 @@ __global__ __launch_bounds__(64 * NW, NW > 4 ? 4 : 2) void mhsa_kernel(const typ
 // ---------------------------------------------------------------------------------------
 // RING (round 4; the KV-cached streaming mode in dtype "fp16x3" -- NOT a reference function, see mhsa_kernel's RING): `qkv` is the
 // per-stream ring of 256 fp32 [q | k | v] slots in 16-slot groups; the ONE query tile ring.q_tile attends to every valid slot.
-template <int KS, int NW, bool RING = false>
+template <int KS, int NW, int RING = 0>
 __global__ __launch_bounds__(64 * NW, 2) void mhsa_split_kernel(const float* __restrict__ qkv, float* __restrict__ out, int T, int H,
                                                                  float scale, const int* __restrict__ lens, int out_pairs, float out_scale,
                                                                  MhsaRing ring) {
@@ -319,7 +328,9 @@ __global__ __launch_bounds__(64 * NW, 2) void mhsa_split_kernel(const float* __r
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long ld = 3L * H * 64;
   const int Trow = T;
-  if (lens) T = lens[b];
+  if (RING != 2 && lens) T = lens[b];
+  const unsigned char* scnt = RING == 2 ? (const unsigned char*)(lens + (long)b * 8 + 4) : nullptr;
+  const int sbase = RING == 2 ? lens[(long)b * 8] : 0;
   const float* base = qkv + (long)b * Trow * ld + h * 64;
   const float* kbase = base + (long)H * 64;
   const float* vbase = base + 2L * H * 64;
@@ -338,11 +349,12 @@ __global__ __launch_bounds__(64 * NW, 2) void mhsa_split_kernel(const float* __r
     for (int idx = tid; idx < KEYS * 8; idx += NT) {
       const int key = idx >> 3, c = idx & 7;
       f32x4 k0 = f32x4{0.f, 0.f, 0.f, 0.f}, k1 = k0, v0 = k0, v1 = k0;
-      if (RING ? (key & 15) < ring.cnt[(key >> 4) & 15] : key < T) {
-        k0 = *(const f32x4*)(kbase + (long)key * ld + c * 8);
-        k1 = *(const f32x4*)(kbase + (long)key * ld + c * 8 + 4);
-        v0 = *(const f32x4*)(vbase + (long)key * ld + c * 8);
-        v1 = *(const f32x4*)(vbase + (long)key * ld + c * 8 + 4);
+      const int slot = RING == 2 ? ring_slot(key, sbase) : key;
+      if (RING == 2 ? (slot & 15) < scnt[slot >> 4] : RING ? (key & 15) < ring.cnt[(key >> 4) & 15] : key < T) {
+        k0 = *(const f32x4*)(kbase + (long)slot * ld + c * 8);
+        k1 = *(const f32x4*)(kbase + (long)slot * ld + c * 8 + 4);
+        v0 = *(const f32x4*)(vbase + (long)slot * ld + c * 8);
+        v1 = *(const f32x4*)(vbase + (long)slot * ld + c * 8 + 4);
       }
       V8 kh, kl, vh, vl;
       split8(k0, k1, kh, kl);
@@ -355,7 +367,8 @@ __global__ __launch_bounds__(64 * NW, 2) void mhsa_split_kernel(const float* __r
       *(V8*)((char*)vt_lds[1] + voff) = vl;
     }
   }
-  for (int i = tid; i < KEYS; i += 64 * NW) mask_lds[i] = (RING ? (i & 15) < ring.cnt[(i >> 4) & 15] : i < T) ? 0.f : -1e30f;
+  for (int i = tid; i < KEYS; i += 64 * NW)
+    mask_lds[i] = (RING == 2 ? (i & 15) < scnt[ring_slot(i, sbase) >> 4] : RING ? (i & 15) < ring.cnt[(i >> 4) & 15] : i < T) ? 0.f : -1e30f;
   __syncthreads();
   const int ql = lane & 15, g = lane >> 4;
   const int nqt_all = (T + 15) >> 4;
@@ -705,6 +718,20 @@ const char* launch_mhsa_ring(const void* ring, void* out, int S, int H, int q_ti
   return e == hipSuccess ? nullptr : hipGetErrorString(e);
 }
 
+// the per-stream form (RING == 2): tab = (S, 8) ints per stream, [0] base group, bytes [16, 32) the 16 valid counts
+const char* launch_mhsa_ring_tab(const void* ring, void* out, int S, int H, int q_tile, const int* tab, int dtype, hipStream_t s) {
+  if (S <= 0 || S > 65535 || H <= 0 || q_tile < 0 || q_tile > 15 || !tab) return "mhsa_ring: bad shape";
+  if (dtype != DT_FP16 && dtype != DT_BF16) return "mhsa_ring: half-precision operands only";
+  MhsaRing r = {};
+  r.q_tile = q_tile;
+  if (dtype == DT_BF16)
+    hipLaunchKernelGGL((mhsa_kernel<BF16, 8, 4, 2, true>), dim3(H, S, 1), dim3(256), 0, s, (const BF16::T*)ring, (BF16::T*)out, 256, H, 0.125f, tab, r);
+  else
+    hipLaunchKernelGGL((mhsa_kernel<FP16, 8, 4, 2, true>), dim3(H, S, 1), dim3(256), 0, s, (const FP16::T*)ring, (FP16::T*)out, 256, H, 0.125f, tab, r);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
 // fp32 rows in / out, products in split precision on the fp16 matrix pipe (the engine's "fp16x3"); T <= 224
 const char* launch_mhsa_split(const float* qkv, float* out, int B, int T, int H, hipStream_t s, const int* lens, bool out_pairs, float out_scale) {
   if (T <= 0 || T > ATT_KEYS || B <= 0 || B > 65535 || H <= 0) return "mhsa_split: 1..224 frames";
@@ -746,6 +773,18 @@ const char* launch_mhsa(const void* qkv, void* out, int B, int T, int H, int dty
     launch_mhsa_t<BF16>(qkv, out, B, T, H, scale, lens, s);
   else
     launch_mhsa_t<FP16>(qkv, out, B, T, H, scale, lens, s);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+// the per-stream form of the split-precision ring (see launch_mhsa_ring_tab)
+const char* launch_mhsa_ring_split_tab(const float* ring, float* out, int S, int H, int q_tile, const int* tab, hipStream_t s, bool out_pairs,
+                                       float out_scale) {
+  if (S <= 0 || S > 65535 || H <= 0 || q_tile < 0 || q_tile > 15 || !tab) return "mhsa_ring: bad shape";
+  MhsaRing r = {};
+  r.q_tile = q_tile;
+  hipLaunchKernelGGL((mhsa_split_kernel<8, 4, 2>), dim3(H, S, 1), dim3(256), 0, s, ring, out, 256, H, 0.125f, tab, out_pairs ? 1 : 0,
+                     out_scale, r);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? nullptr : hipGetErrorString(e);
 }

@@ -1394,15 +1394,21 @@ struct afx_kv {
   void* rings = nullptr;   // (layers, S, 256, 3072) operand type
   void* hist = nullptr;    // (S, 64, 1024) operand type: the newest projected frames (positional conv's left context)
   float* feat[2] = {nullptr, nullptr};  // (S, 208, 1024) fp32, right-aligned window, ping-pong
+  // per-stream sessions (afx_kv_reset / afx_kv_step_ragged): once either is called, the state is per stream
+  bool per_stream = false;
+  int* tab = nullptr;    // device (S, 8) ints: [0] base group (the group of the stream's first chunk), bytes [16, 32) valid counts
+  int* meta = nullptr;   // device (4 S) ints, written per call: frame counts | 64 + frame counts | window lengths | slot lists
+  std::vector<int> nfeat_s, hmeta;
 };
 struct KvWs {
   void *feats_h, *xpad, *hbuf, *att, *ff;
   float *xp, *x;
+  float* fl = nullptr;  // per-stream step: the final LayerNorm's rows before they join each stream's window
   void* s3planes = nullptr;  // split precision: pair-form scratch of the chunk's products
   size_t s3bytes = 0;
   Ws head;
 };
-static size_t kv_carve(const afx_engine* e, int S, int n, int Th, void* base, KvWs* k) {
+static size_t kv_carve(const afx_engine* e, int S, int n, int Th, void* base, KvWs* k, bool per_stream = false) {
   Carver c(base);
   const size_t hs = dtype_size(e->dt), M = (size_t)S * n, Tp = kKvHist + n;
   k->feats_h = c.take(M * kC * hs);
@@ -1418,8 +1424,9 @@ static size_t kv_carve(const afx_engine* e, int S, int n, int Th, void* base, Kv
     k->s3bytes = c.largest + 4096;
     k->s3planes = c.take(k->s3bytes);
   }
+  k->fl = per_stream ? (float*)c.take(M * kD * 4) : nullptr;
   c.off = (c.off + 255) & ~(size_t)255;
-  const size_t head_bytes = carve(e, S, 0, Th, base ? (char*)base + c.off : nullptr, &k->head);
+  const size_t head_bytes = carve(e, S, 0, Th, base ? (char*)base + c.off : nullptr, &k->head, 0, per_stream);
   return c.off + head_bytes + 256;
 }
 extern "C" int afx_kv_create(afx_handle h, int n_streams, afx_kv** out) {
@@ -1434,13 +1441,16 @@ extern "C" int afx_kv_create(afx_handle h, int n_streams, afx_kv** out) {
   for (int i = 0; i < kKvGroups; ++i) k->cnt[i] = 0;
   const size_t hs = h->hsz, ring = (size_t)h->cfg.n_layers * n_streams * kKvSlots * 3 * kD * hs, hist = (size_t)n_streams * kKvHist * kD * hs,
                feat = (size_t)n_streams * kKvFeat * kD * 4;
-  bool ok = hipMalloc(&k->rings, ring) == hipSuccess && hipMalloc(&k->hist, hist) == hipSuccess &&
+  bool ok = hipMalloc((void**)&k->tab, (size_t)n_streams * 32) == hipSuccess && hipMalloc((void**)&k->meta, (size_t)n_streams * 16) == hipSuccess &&
+            hipMemset(k->tab, 0, (size_t)n_streams * 32) == hipSuccess &&
+            hipMalloc(&k->rings, ring) == hipSuccess && hipMalloc(&k->hist, hist) == hipSuccess &&
             hipMalloc((void**)&k->feat[0], feat) == hipSuccess && hipMalloc((void**)&k->feat[1], feat) == hipSuccess;
   // the history starts as silence-before-the-stream (zero left padding); ring slots are masked until written
   ok = ok && hipMemset(k->rings, 0, ring) == hipSuccess && hipMemset(k->hist, 0, hist) == hipSuccess &&
        hipMemset(k->feat[0], 0, feat) == hipSuccess && hipMemset(k->feat[1], 0, feat) == hipSuccess;
   if (!ok) {
     (void)hipFree(k->rings); (void)hipFree(k->hist); (void)hipFree(k->feat[0]); (void)hipFree(k->feat[1]);
+    (void)hipFree(k->tab); (void)hipFree(k->meta);
     delete k;
     return fail("afx_kv_create: device allocation failed (%zu bytes per stream)", (ring + hist + 2 * feat) / n_streams);
   }
@@ -1450,6 +1460,7 @@ extern "C" int afx_kv_create(afx_handle h, int n_streams, afx_kv** out) {
 extern "C" void afx_kv_destroy(afx_kv* k) {
   if (!k) return;
   (void)hipFree(k->rings); (void)hipFree(k->hist); (void)hipFree(k->feat[0]); (void)hipFree(k->feat[1]);
+  (void)hipFree(k->tab); (void)hipFree(k->meta);
   delete k;
 }
 extern "C" size_t afx_kv_state_bytes(const afx_kv* k) {
@@ -1466,6 +1477,7 @@ extern "C" size_t afx_kv_workspace_bytes(const afx_kv* k, int n_frames) {
 extern "C" int afx_kv_step(afx_kv* k, const float* feats6, int n, float* logits, void* ws, size_t ws_bytes, void* stream) {
   if (n < 1 || n > 16) return fail("afx_kv_step: a chunk brings 1..16 frames (got %d)", n);
   if (!k || !feats6 || !logits || !ws) return fail("afx_kv_step: null argument");
+  if (k->per_stream) return fail("afx_kv_step: this state holds per-stream sessions (afx_kv_reset / afx_kv_step_ragged): continue with afx_kv_step_ragged");
   afx_engine* e = k->e;
   const int S = k->S, dt = e->dt, M = S * n, Tp = kKvHist + n, group = (int)(k->hop % kKvGroups);
   const int Th = std::min(k->nfeat + n, kKvWindow);
@@ -1585,6 +1597,270 @@ extern "C" int afx_kv_step(afx_kv* k, const float* feats6, int n, float* logits,
   if (e->taps_on && tap(e, "ssl", w.head.ssl_f, (size_t)S * Th * kD, false, s)) return 1;
   begin_call(e, &w.head);  // (the back-end's products use the back-end workspace's own scratch and buffer list)
   return run_head(e, S, Th, w.head, logits, s);
+}
+
+
+// ---------------------------------------------------------------------------------
+// Per-stream sessions of the KV-cached mode: streams that start (afx_kv_reset) at different ticks.  Every stream still
+// brings one chunk per step and the ring group stays global (group = step % 16, the QKV epilogue unchanged), so a stream's
+// last 16 chunks are always the last 16 groups; what is per stream is its base group (where its first chunk sits), its
+// valid-count row, its frame count per step (12 or 13 from its own first sample: n_s <= n_max, rows padded to n_max) and
+// its window length.  The ring attention visits the slots rotated by the base group, so a stream's keys are summed in the
+// order of a stream that started at group 0: a session scores bit for bit as that stream alone from the start.
+// ---------------------------------------------------------------------------------
+__global__ void kv_reset_kernel(const int* __restrict__ slots, int* __restrict__ tab, int base_group, u32x4* __restrict__ hist,
+                                long hist_words, u32x4* __restrict__ f0, u32x4* __restrict__ f1, long feat_words) {
+  const long sl = slots[blockIdx.y];
+  if (blockIdx.x == 0 && threadIdx.x < 8) tab[sl * 8 + threadIdx.x] = threadIdx.x == 0 ? base_group : 0;
+  const u32x4 z = {0u, 0u, 0u, 0u};
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < hist_words; i += (long)gridDim.x * blockDim.x) hist[sl * hist_words + i] = z;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < feat_words; i += (long)gridDim.x * blockDim.x) {
+    f0[sl * feat_words + i] = z;
+    f1[sl * feat_words + i] = z;
+  }
+}
+__global__ void kv_count_kernel(int* __restrict__ tab, const int* __restrict__ n, int S, int group) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < S) ((unsigned char*)(tab + (long)b * 8 + 4))[group] = (unsigned char)n[b];
+}
+// hist[s] = rows [pad + n_s, pad + n_s + 64) of stream s's padded rows (the newest 64 projected frames); 16-byte words
+__global__ void kv_hist_kernel(u32x4* __restrict__ hist, const u32x4* __restrict__ xpad, const int* __restrict__ n, long row_words,
+                               long xpad_rows, int pad) {
+  const long b = blockIdx.y;
+  const long words = kKvHist * row_words;
+  const u32x4* src = xpad + (b * xpad_rows + pad + n[b]) * row_words;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (long)gridDim.x * blockDim.x) hist[b * words + i] = src[i];
+}
+// the window moves up by n_s rows and the stream's n_s new feature rows (dense (S, n_max, 1024) fp32) join it right-aligned
+__global__ void kv_feat_kernel(const f32x4* __restrict__ cur, f32x4* __restrict__ nxt, const f32x4* __restrict__ fl, const int* __restrict__ n, int n_max) {
+  const long b = blockIdx.y;
+  const int nb = n[b];
+  constexpr long RW = kD / 4;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < kKvFeat * RW; i += (long)gridDim.x * blockDim.x) {
+    const int r = (int)(i / RW), c = (int)(i % RW);
+    nxt[b * kKvFeat * RW + i] = r < kKvFeat - nb ? cur[(b * kKvFeat + r + nb) * RW + c] : fl[(b * n_max + r - (kKvFeat - nb)) * RW + c];
+  }
+}
+// out row i (pitch Tout rows) = the last th_i rows of the window of stream ids[i] (identity if null), LEFT-aligned, zeros after
+__global__ void kv_gather_kernel(const f32x4* __restrict__ win, const int* __restrict__ ids, const int* __restrict__ th, int th_const,
+                                 int Tout, f32x4* __restrict__ out) {
+  const long i = blockIdx.y;
+  const long b = ids ? ids[i] : i;
+  const int t = th ? th[i] : th_const;
+  constexpr long RW = kD / 4;
+  for (long j = (long)blockIdx.x * blockDim.x + threadIdx.x; j < Tout * RW; j += (long)gridDim.x * blockDim.x) {
+    const int r = (int)(j / RW), c = (int)(j % RW);
+    out[i * Tout * RW + j] = r < t ? win[(b * kKvFeat + kKvFeat - t + r) * RW + c] : f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+}
+__global__ void kv_scatter_logits_kernel(const float* __restrict__ in, const int* __restrict__ ids, int nb, float* __restrict__ logits) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nb * 2) logits[(long)ids[i >> 1] * 2 + (i & 1)] = in[i];
+}
+
+// the lock-stepped state becomes per-stream tables (base group 0, the shared valid counts, the shared window length)
+static int kv_to_per_stream(afx_kv* k, hipStream_t s) {
+  if (k->per_stream) return 0;
+  std::vector<int> t((size_t)k->S * 8, 0);
+  for (int b = 0; b < k->S; ++b)
+    for (int g = 0; g < kKvGroups; ++g) ((unsigned char*)&t[(size_t)b * 8 + 4])[g] = (unsigned char)k->cnt[g];
+  HIP_OK(hipMemcpyAsync(k->tab, t.data(), t.size() * 4, hipMemcpyHostToDevice, s));
+  HIP_OK(hipStreamSynchronize(s));  // (pageable host memory)
+  k->nfeat_s.assign(k->S, k->nfeat);
+  k->hmeta.assign((size_t)k->S * 4, 0);
+  k->per_stream = true;
+  return 0;
+}
+
+extern "C" int afx_kv_reset(afx_kv* k, const int* slots, int n_slots, void* stream) {
+  if (!k || (n_slots > 0 && !slots) || n_slots < 0) return fail("afx_kv_reset: bad argument");
+  std::vector<char> seen(k->S, 0);
+  for (int i = 0; i < n_slots; ++i) {
+    if (slots[i] < 0 || slots[i] >= k->S) return fail("afx_kv_reset: slot %d outside 0..%d", slots[i], k->S - 1);
+    if (seen[slots[i]]++) return fail("afx_kv_reset: slot %d named twice", slots[i]);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (kv_to_per_stream(k, s)) return 1;
+  if (n_slots == 0) return 0;
+  for (int i = 0; i < n_slots; ++i) {
+    k->nfeat_s[slots[i]] = 0;
+    k->hmeta[(size_t)3 * k->S + i] = slots[i];
+  }
+  int* dslots = k->meta + 3 * k->S;
+  HIP_OK(hipMemcpyAsync(dslots, k->hmeta.data() + 3 * k->S, (size_t)n_slots * 4, hipMemcpyHostToDevice, s));
+  HIP_OK(hipStreamSynchronize(s));
+  const size_t hs = k->e->hsz;
+  hipLaunchKernelGGL(kv_reset_kernel, dim3(64, n_slots), dim3(256), 0, s, dslots, k->tab, (int)(k->hop % kKvGroups), (u32x4*)k->hist,
+                     (long)(kKvHist * kD * hs / 16), (u32x4*)k->feat[0], (u32x4*)k->feat[1], (long)(kKvFeat * kD * 4 / 16));
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+extern "C" size_t afx_kv_ragged_workspace_bytes(const afx_kv* k, int n_max) {
+  if (!k || n_max <= 0 || n_max > 16) return 0;
+  KvWs w;
+  return kv_carve(k->e, k->S, n_max, kKvWindow, nullptr, &w, true);
+}
+
+// feats6: device (S, n_max, 512) fp32, stream b's n_frames[b] new frames first (rows past them are read but never score);
+// n_frames: host, S entries, 1 <= n_frames[b] <= n_max <= 16.  Same function per stream as afx_kv_step on that stream alone.
+extern "C" int afx_kv_step_ragged(afx_kv* k, const float* feats6, int n, const int* n_frames, float* logits, void* ws, size_t ws_bytes,
+                                  void* stream) {
+  if (n < 1 || n > 16) return fail("afx_kv_step_ragged: a chunk brings 1..16 frames (got n_max %d)", n);
+  if (!k || !feats6 || !n_frames || !logits || !ws) return fail("afx_kv_step_ragged: null argument");
+  afx_engine* e = k->e;
+  const int S = k->S, dt = e->dt, M = S * n, Tp = kKvHist + n, group = (int)(k->hop % kKvGroups);
+  for (int b = 0; b < S; ++b)
+    if (n_frames[b] < 1 || n_frames[b] > n) return fail("afx_kv_step_ragged: stream %d brings %d frames (1..%d)", b, n_frames[b], n);
+  hipStream_t s = (hipStream_t)stream;
+  if (kv_to_per_stream(k, s)) return 1;
+  int Thmax = 0;
+  std::vector<int>& hm = k->hmeta;
+  for (int b = 0; b < S; ++b) {
+    const int th = std::min(k->nfeat_s[b] + n_frames[b], kKvWindow);
+    if (e->cfg.arch == AFX_ARCH_XLSR_AASIST && th < 6) return fail("afx_kv_step_ragged: the AASIST head needs at least 6 frames in stream %d's window", b);
+    hm[b] = n_frames[b];
+    hm[S + b] = kKvHist + n_frames[b];
+    hm[2 * S + b] = th;
+    Thmax = std::max(Thmax, th);
+  }
+  KvWs w;
+  const size_t needb = kv_carve(e, S, n, Thmax, ws, &w, true);
+  if (ws_bytes < needb) return fail("afx_kv_step_ragged: workspace too small (%zu < %zu bytes)", ws_bytes, needb);
+  // AASIST: the streams grouped by window length (one uniform sub-batch each, as afx_forward_ragged does)
+  std::vector<std::pair<int, int>> buckets;  // (length, first index into the slot list)
+  if (e->cfg.arch == AFX_ARCH_XLSR_AASIST) {
+    std::vector<int> order(S);
+    for (int b = 0; b < S; ++b) order[b] = b;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int c) { return hm[2 * S + a] < hm[2 * S + c]; });
+    for (int i = 0; i < S; ++i) {
+      hm[3 * S + i] = order[i];
+      if (i == 0 || hm[2 * S + order[i]] != hm[2 * S + order[i - 1]]) buckets.push_back({hm[2 * S + order[i]], i});
+    }
+  }
+  const int* dn = k->meta;
+  HIP_OK(hipMemcpyAsync(k->meta, hm.data(), (size_t)S * 16, hipMemcpyHostToDevice, s));
+  HIP_OK(hipStreamSynchronize(s));  // (pageable host memory)
+  begin_call(e, nullptr);
+  if (e->s3) {
+    t_s3planes = w.s3planes;
+    t_s3bytes = w.s3bytes;
+    s3_begin({w.feats_h, w.hbuf, w.att, w.ff, w.xpad, (char*)w.xpad + (size_t)kKvHist * kD * e->hsz});
+  }
+  const size_t hs = e->hsz;
+  hipLaunchKernelGGL(kv_count_kernel, dim3((S + 255) / 256), dim3(256), 0, s, k->tab, dn, S, group);
+  HIP_OK(hipGetLastError());
+  {
+    RowNormArgs a = plain_norm(feats6, kC, M, kC, e->F("ssl.layer_norm.weight"), e->F("ssl.layer_norm.bias"));
+    a.out_h = w.feats_h; a.ldo_h = kC;
+    KOK(launch_rownorm(a, dt, s));
+  }
+  const size_t xrow = (size_t)kD * hs, xpad_pitch = (size_t)(Tp + kPosK) * xrow;
+  HIP_OK(hipMemcpy2DAsync((char*)w.xpad + kPosPad * xrow, xpad_pitch, k->hist, kKvHist * xrow, kKvHist * xrow, S, hipMemcpyDeviceToDevice, s));
+  {
+    GemmArgs g = plain_gemm(w.feats_h, kC, e->projw, kC, M, kD, kC);
+    g.rpb = n; g.a_batch = (long)n * kC; g.a_row = kC;
+    g.bias = e->F("ssl.post_extract_proj.bias");
+    g.out_f = w.x; g.ldo_f = kD; g.o_batch_rows = n;
+    g.out_h = w.xpad; g.ldo_h = kD; g.oh_batch_rows = Tp + kPosK; g.oh_row_off = kPosPad + kKvHist;
+    KOK(launch_gemm(g, dt, 1, s));
+    // a stream's chunk rows past its own n_s are zero, as beyond its chunk when it steps alone
+    KOK(timed(PC_MISC, 0, s, [&] { return launch_zero_pad_rows(w.xpad, S, Tp, kD, kPosPad, kPosK - kPosPad, dt, s, dn + S); }));
+  }
+  void* xchunk = (char*)w.xpad + (size_t)kKvHist * xrow;
+  if (!e->s3) {
+    PosConvArgs pc;
+    memset(&pc, 0, sizeof pc);
+    pc.xpad = xchunk; pc.xpad_batch = (long)(Tp + kPosK) * kD; pc.W = e->posw; pc.bias = e->F("ssl.encoder.pos_conv.0.bias");
+    pc.x = w.x; pc.B = S; pc.T = n;
+    KOK(timed(PC_POSCONV, 2.0 * S * n * kD * (kD / kPosG) * kPosK, s, [&] { return launch_posconv(pc, dt, s); }));
+  } else {
+    const int cpg = kD / kPosG;
+    s3_set(xchunk, kS3ScaleFree);
+    GemmArgs g = plain_gemm(xchunk, 0, e->posw, (long)cpg * kPosK, S * n, cpg, cpg * kPosK);
+    g.rpb = n; g.a_batch = (long)(Tp + kPosK) * kD; g.a_row = kD;
+    g.kchunk = cpg; g.kchunk_stride = kD;
+    g.g_a = cpg; g.g_w = (long)cpg * cpg * kPosK; g.g_n = cpg;
+    g.bias = e->F("ssl.encoder.pos_conv.0.bias");
+    g.act = ACT_GELU;
+    g.resid = w.x; g.ldr = kD;
+    g.out_f = w.x; g.ldo_f = kD; g.o_batch_rows = n; g.oh_batch_rows = n;
+    KOK(launch_gemm(g, dt, kPosG, s));
+  }
+  hipLaunchKernelGGL(kv_hist_kernel, dim3(32, S), dim3(256), 0, s, (u32x4*)k->hist, (const u32x4*)w.xpad, dn, (long)(xrow / 16),
+                     (long)(Tp + kPosK), kPosPad);
+  HIP_OK(hipGetLastError());
+  for (int l = 0; l < e->cfg.n_layers; ++l) {
+    const std::string P = "ssl.encoder.layers." + std::to_string(l) + ".";
+    void* ring = (char*)k->rings + (size_t)l * S * kKvSlots * 3 * kD * hs;
+    RowNormArgs n1 = plain_norm(w.x, kD, M, kD, e->F(P + "self_attn_layer_norm.weight"), e->F(P + "self_attn_layer_norm.bias"));
+    n1.out_h = w.hbuf; n1.ldo_h = kD;
+    KOK(launch_rownorm(n1, dt, s));
+    GemmArgs q = plain_gemm(w.hbuf, kD, e->wqkv[l], kD, M, 3 * kD, kD);
+    q.rpb = n; q.a_batch = (long)n * kD; q.a_row = kD;
+    q.bias = e->bqkv[l];
+    q.out_h = ring; q.ldo_h = 3 * kD; q.oh_batch_rows = kKvSlots; q.oh_row_off = group * 16;
+    KOK(launch_gemm(q, dt, 1, s));
+    KOK(timed(PC_MHSA, 4.0 * S * kH * 16.0 * kKvSlots * 64, s, [&] {
+      if (e->s3) {
+        const bool pairs = s3_ok(w.att);
+        s3_set(w.att, pairs ? kS3ScaleFree : 0.f);
+        return launch_mhsa_ring_split_tab((const float*)ring, (float*)w.att, S, kH, group, k->tab, s, pairs, kS3ScaleFree);
+      }
+      return launch_mhsa_ring_tab(ring, w.att, S, kH, group, k->tab, dt, s);
+    }));
+    GemmArgs o = plain_gemm(w.att, kD, e->wo[l], kD, M, kD, kD);
+    o.rpb = n; o.a_batch = 16L * kD; o.a_row = kD; o.o_batch_rows = n;
+    o.bias = e->F(P + "self_attn.out_proj.bias"); o.resid = w.x; o.ldr = kD; o.out_f = w.x; o.ldo_f = kD;
+    KOK(launch_gemm(o, dt, 1, s));
+    RowNormArgs n2 = plain_norm(w.x, kD, M, kD, e->F(P + "final_layer_norm.weight"), e->F(P + "final_layer_norm.bias"));
+    n2.out_h = w.hbuf; n2.ldo_h = kD;
+    KOK(launch_rownorm(n2, dt, s));
+    GemmArgs f1 = plain_gemm(w.hbuf, kD, e->w1[l], kD, M, kF, kD);
+    f1.bias = e->F(P + "fc1.bias"); f1.act = ACT_GELU; f1.out_h = w.ff; f1.ldo_h = kF;
+    KOK(launch_gemm(f1, dt, 1, s));
+    GemmArgs f2 = plain_gemm(w.ff, kF, e->w2[l], kF, M, kD, kF);
+    f2.bias = e->F(P + "fc2.bias"); f2.resid = w.x; f2.ldr = kD; f2.out_f = w.x; f2.ldo_f = kD;
+    KOK(launch_gemm(f2, dt, 1, s));
+  }
+  float *cur = k->feat[k->pp], *nxt = k->feat[k->pp ^ 1];
+  {
+    RowNormArgs nf = plain_norm(w.x, kD, M, kD, e->F("ssl.encoder.layer_norm.weight"), e->F("ssl.encoder.layer_norm.bias"));
+    nf.out_f = w.fl; nf.ldo_f = kD;
+    nf.nonfinite = e->nonfinite;
+    KOK(launch_rownorm(nf, dt, s));
+  }
+  hipLaunchKernelGGL(kv_feat_kernel, dim3(64, S), dim3(256), 0, s, (const f32x4*)cur, (f32x4*)nxt, (const f32x4*)w.fl, dn, n);
+  HIP_OK(hipGetLastError());
+  k->pp ^= 1;
+  for (int b = 0; b < S; ++b) k->nfeat_s[b] = std::min(k->nfeat_s[b] + n_frames[b], kKvFeat);
+  k->hop += 1;
+  const int* dth = dn + 2 * S;
+  if (e->cfg.arch == AFX_ARCH_CONFORMER) {  // every stream's window left-aligned, key-padding lengths (afx_forward_ragged's head)
+    hipLaunchKernelGGL(kv_gather_kernel, dim3(32, S), dim3(256), 0, s, (const f32x4*)nxt, (const int*)nullptr, dth, 0, Thmax, (f32x4*)w.head.ssl_f);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(w.head.lens, dth, (size_t)S * 4, hipMemcpyDeviceToDevice, s));
+    if (e->s3) {
+      HIP_OK(hipMemcpyAsync(w.head.ssl_h, w.head.ssl_f, (size_t)S * Thmax * kD * 4, hipMemcpyDeviceToDevice, s));
+    } else {
+      hipLaunchKernelGGL(f32_to_half_kernel, dim3(1024), dim3(256), 0, s, w.head.ssl_f, (uint16_t*)w.head.ssl_h, (size_t)S * Thmax * kD, dt == AFX_DT_BF16 ? 1 : 0);
+      HIP_OK(hipGetLastError());
+    }
+    begin_call(e, &w.head);
+    return run_head(e, S, Thmax, w.head, logits, s);
+  }
+  begin_call(e, &w.head);
+  for (size_t bi = 0; bi < buckets.size(); ++bi) {
+    const int t = buckets[bi].first, i0 = buckets[bi].second;
+    const int nb = (bi + 1 < buckets.size() ? buckets[bi + 1].second : S) - i0;
+    const int* ids = dn + 3 * S + i0;
+    hipLaunchKernelGGL(kv_gather_kernel, dim3(32, nb), dim3(256), 0, s, (const f32x4*)nxt, ids, (const int*)nullptr, t, t, (f32x4*)w.head.bucket_f);
+    HIP_OK(hipGetLastError());
+    if (const char* m = aasist_forward(e->aw, w.head.bucket_f, nb, t, w.head.aa, w.head.bucket_logits, s, e->nonfinite + 1)) return fail("%s", m);
+    hipLaunchKernelGGL(kv_scatter_logits_kernel, dim3((2 * nb + 255) / 256), dim3(256), 0, s, w.head.bucket_logits, ids, nb, logits);
+    HIP_OK(hipGetLastError());
+  }
+  return 0;
 }
 
 #undef launch_gemm

@@ -192,6 +192,11 @@ const char* launch_mhsa_ring(const void* ring, void* out, int S, int H, int q_ti
 // the same in split precision (dtype "fp16x3"): fp32 [q | k | v] slots in; fp32 rows or (out_pairs) pair-form rows out
 const char* launch_mhsa_ring_split(const float* ring, float* out, int S, int H, int q_tile, const int* cnt, hipStream_t s,
                                    bool out_pairs = false, float out_scale = 1.f);
+// per-stream sessions (afx_kv_step_ragged): tab = (S, 8) ints per stream -- [0] the stream's base group, bytes [16, 32) its
+// 16 valid counts; the slots are visited rotated by the base group (the key order of a stream that started at group 0)
+const char* launch_mhsa_ring_tab(const void* ring, void* out, int S, int H, int q_tile, const int* tab, int dtype, hipStream_t s);
+const char* launch_mhsa_ring_split_tab(const float* ring, float* out, int S, int H, int q_tile, const int* tab, hipStream_t s,
+                                       bool out_pairs, float out_scale);
 
 // ---- Conformer student head (afx_conformer.hip) ----------------------------------
 // y = selu(bn(x)) for rows 1..T of each utterance, row 0 = class token; x is the LL

@@ -6,6 +6,13 @@ and the labelled NON-reference mode config 5 names (a different, block-causal fu
   kv-cached    cached keys / values of the last 16 chunks, only the chunk's 12-13 new frames through the trunk.
 
     python tools/stream_bench.py [--workload conformer_student|xlsr_aasist] [--streams 1 64 512 2048]
+    python tools/stream_bench.py --staggered [--session-hops 120] --modes incremental ...
+
+--staggered measures every mode twice: lockstep (all streams started together, as above) and with per-slot sessions --
+before every hop, warm-up included, each slot restarts (``scorer.reset``) with probability 1 / session-hops, seeded, so
+that slots warming up and slots in the steady state share the ticks as they do on a server scoring live calls (the warm-up
+runs session-hops more ticks, so the timed hops see the stationary mix: ~1 - (1 - 1/120)^16 = 12.5 % of the slots still
+younger than the window at the default).
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/stream_bench.py --gpus N ...
 
 With --gpus N every rank pins its own S streams to its GPU (state lives there; nothing is exchanged on the data path);
@@ -31,6 +38,8 @@ def main():
     ap.add_argument("--streams", type=int, nargs="*", default=[1, 64, 512, 2048])
     ap.add_argument("--hops", type=int, default=10)
     ap.add_argument("--modes", nargs="*", default=["sliding", "incremental", "kv-cached"])
+    ap.add_argument("--staggered", action="store_true", help="also time per-slot sessions restarting at random ticks")
+    ap.add_argument("--session-hops", type=int, default=120, help="--staggered: mean session length in hops (120 = 30 s)")
     args = ap.parse_args()
     rank, local, world = (int(os.environ.get(k, d)) for k, d in (("RANK", 0), ("LOCAL_RANK", 0), ("WORLD_SIZE", 1)))
     if world != args.gpus:
@@ -49,29 +58,39 @@ def main():
     for S in args.streams:
         line = f"{args.workload}, {world} GPU(s) x {S} streams:"
         for name in args.modes:
-            try:
-                sc = {"sliding": lambda: SlidingWindowScorer(eng, S, window=W, hop=H), "incremental": lambda: IncrementalScorer(eng, sd, S, window=W, hop=H),
-                      "kv-cached": lambda: KVCachedScorer(eng, sd, S, window=W, hop=H)}[name]()
-            except Exception as exc:  # (the K / V rings of 24 layers are 38 MB per stream: 2 048 streams of the teacher do not fit beside the rest)
-                line += f"  {name} n/a ({str(exc)[:60]})"
-                continue
-            chunk = (0.1 * torch.randn(S, H, generator=torch.Generator().manual_seed(rank))).cuda()
-            for _ in range(W // H + 2):  # fill the window, reach the steady state
-                sc.push(chunk)
-            torch.cuda.synchronize()
-            if dist:
-                dist.barrier()
-            t0 = time.perf_counter()
-            for _ in range(args.hops):
-                sc.push(chunk)
-            torch.cuda.synchronize()
-            dt = (time.perf_counter() - t0) / args.hops
-            if dist:
-                t = torch.tensor([dt], dtype=torch.float64, device="cuda")
-                dist.all_reduce(t, op=dist.ReduceOp.MAX)
-                dt = t.item()
-            line += f"  {name} {dt * 1e3:8.2f} ms/hop RTF {dt / 0.25:6.3f} ({world * S / dt:8.0f} scores/s)"
-            del sc
+            for staggered in ((False, True) if args.staggered else (False,)):
+                label = name + (" staggered" if staggered else "")
+                try:
+                    sc = {"sliding": lambda: SlidingWindowScorer(eng, S, window=W, hop=H), "incremental": lambda: IncrementalScorer(eng, sd, S, window=W, hop=H),
+                          "kv-cached": lambda: KVCachedScorer(eng, sd, S, window=W, hop=H)}[name]()
+                    if staggered:
+                        sc.reset([0])  # (a no-op on a fresh scorer; a mode without sessions refuses it here)
+                except Exception as exc:  # (the K / V rings of 24 layers are 38 MB per stream: 2 048 streams of the teacher do not fit beside the rest)
+                    line += f"  {label} n/a ({str(exc)[:60]})"
+                    continue
+                chunk = (0.1 * torch.randn(S, H, generator=torch.Generator().manual_seed(rank))).cuda()
+                gen = torch.Generator().manual_seed(1000 + rank)
+
+                def tick():
+                    if staggered:
+                        sc.reset(torch.rand(S, generator=gen) < 1.0 / args.session_hops)
+                    sc.push(chunk)
+                for _ in range(W // H + 2 + (args.session_hops if staggered else 0)):  # fill the window, reach the steady state
+                    tick()
+                torch.cuda.synchronize()
+                if dist:
+                    dist.barrier()
+                t0 = time.perf_counter()
+                for _ in range(args.hops):
+                    tick()
+                torch.cuda.synchronize()
+                dt = (time.perf_counter() - t0) / args.hops
+                if dist:
+                    t = torch.tensor([dt], dtype=torch.float64, device="cuda")
+                    dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                    dt = t.item()
+                line += f"  {label} {dt * 1e3:8.2f} ms/hop RTF {dt / 0.25:6.3f} ({world * S / dt:8.0f} scores/s)"
+                del sc
         if rank == 0:
             print(line, flush=True)
     if dist:
