@@ -145,6 +145,18 @@ int afx_kv_reset(afx_kv* kv, const int* slots, int n_slots, void* stream);
 size_t afx_kv_ragged_workspace_bytes(const afx_kv* kv, int n_max);
 int afx_kv_step_ragged(afx_kv* kv, const float* feats6, int n_max, const int* n_frames, float* logits, void* ws, size_t ws_bytes,
                        void* stream);
+/* Non-paced streams: a step over a list of active streams.  slots: host, n_active distinct stream indices
+ * (0 <= slot < n_streams) in any order; feats6: device (n_active, n_max, 512) fp32, row i = the chunk of slots[i] with its
+ * n_frames[i] (host array, 1 <= n_frames[i] <= n_max <= 16) new frames first; logits: device (n_active, 2) in list order.
+ * Only the listed streams advance: every other stream's cached keys / values, positional-conv context, feature window and
+ * ring position stay as they are.  Each stream writes its chunks at its own ring group (its base group plus its own step
+ * count), so a stream's logits equal, bit for bit, those of the same stream stepped on every step of a fresh afx_kv.
+ * n_active == 0 launches nothing.  The workspace is carved for n_active streams (afx_kv_active_workspace_bytes).  The
+ * first call makes the state per stream; afx_kv_step and afx_kv_step_ragged then refuse it (afx_kv_reset still applies:
+ * a reset stream starts at its own next group). */
+size_t afx_kv_active_workspace_bytes(const afx_kv* kv, int n_active, int n_max);
+int afx_kv_step_active(afx_kv* kv, const int* slots, int n_active, const float* feats6, int n_max, const int* n_frames,
+                       float* logits, void* ws, size_t ws_bytes, void* stream);
 /* back-end alone from given SSL features (B,T,1024) fp32 -> logits (B,2) */
 int afx_head_forward(afx_handle h, const float* feats, int B, int T, float* logits, void* ws, size_t ws_bytes,
                      void* stream);

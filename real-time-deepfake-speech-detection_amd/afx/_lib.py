@@ -62,6 +62,8 @@ SIGNATURES = {
     "afx_kv_reset": (_I, [_P, _P, _I, _P]),
     "afx_kv_ragged_workspace_bytes": (_Z, [_P, _I]),
     "afx_kv_step_ragged": (_I, [_P, _P, _I, _P, _P, _P, _Z, _P]),
+    "afx_kv_active_workspace_bytes": (_Z, [_P, _I, _I]),
+    "afx_kv_step_active": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _Z, _P]),
     "afx_check_finite": (_I, [_P, _P]),
     "afx_enable_taps": (_I, [_P, _I]),
     "afx_tap": (_I, [_P, C.c_char_p, _P, _Z, C.POINTER(_Z), _P]),

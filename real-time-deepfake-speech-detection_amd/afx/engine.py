@@ -516,10 +516,15 @@ class KVState:
                 pass
             self._k = None
 
-    def step(self, feats6, n_frames=None):
+    def step(self, feats6, n_frames=None, slots=None):
         """feats6: (S, n, 512) fp32, the n (1..16) NEW frames of conv layer 6 -> logits (S, 2).  n_frames (per-stream
-        sessions): S counts, stream b's n_frames[b] (1..n) new frames first in its n rows (afx_kv_step_ragged)."""
+        sessions): S counts, stream b's n_frames[b] (1..n) new frames first in its n rows (afx_kv_step_ragged).
+        slots (non-paced streams): A distinct stream indices; feats6 is then (A, n, 512), row i stream slots[i]'s chunk,
+        only those streams advance and the logits are (A, 2) in list order (afx_kv_step_active; n_frames: A counts, or
+        None for n each).  From the first such step on, every step of this state names its streams."""
         eng = self.engine
+        if slots is not None:
+            return self._step_active(feats6, n_frames, slots)
         eng._on_device(feats6, "conv-layer-6 frames")
         f = feats6.to(torch.float32).contiguous()
         if f.ndim != 3 or f.shape[0] != self.S or f.shape[2] != 512:
@@ -537,6 +542,28 @@ class KVState:
                     raise ValueError(f"n_frames: one count per stream ({self.S}), got {len(nf)}")
                 ws = eng._workspace(max(l.afx_kv_ragged_workspace_bytes(self._k, n), 256))
                 check(l.afx_kv_step_ragged(self._k, ptr(f), n, (C.c_int * self.S)(*nf), ptr(out), ptr(ws), ws.numel(), eng._stream()))
+        return out
+
+    def _step_active(self, feats6, n_frames, slots):
+        eng = self.engine
+        idx = [int(v) for v in slots]
+        if not idx:
+            return torch.empty(0, 2, dtype=torch.float32, device=eng.device)
+        eng._on_device(feats6, "conv-layer-6 frames")
+        f = feats6.to(torch.float32).contiguous()
+        A = len(idx)
+        if f.ndim != 3 or f.shape[0] != A or f.shape[2] != 512:
+            raise ValueError(f"expected ({A}, n, 512) frames for {A} slots, got {tuple(f.shape)}")
+        n = f.shape[1]
+        nf = [n] * A if n_frames is None else [int(v) for v in n_frames]
+        if len(nf) != A:
+            raise ValueError(f"n_frames: one count per named slot ({A}), got {len(nf)}")
+        l = lib()
+        with torch.cuda.device(eng.device):
+            out = torch.empty(A, 2, dtype=torch.float32, device=eng.device)
+            ws = eng._workspace(max(l.afx_kv_active_workspace_bytes(self._k, A, n), 256))
+            check(l.afx_kv_step_active(self._k, (C.c_int * A)(*idx), A, ptr(f), n, (C.c_int * A)(*nf), ptr(out), ptr(ws), ws.numel(),
+                                       eng._stream()))
         return out
 
     def reset(self, slots):

@@ -34,6 +34,14 @@ conv carries and layer-5 frames are dropped, the other slots are untouched.  A s
 t0 + j, bit for bit, the score it would emit at tick j of a fresh scorer with the same number of slots fed the same audio
 from tick 0 (every kernel behind a score is row-wise and accumulates a row in one order whatever the batch: a slot's
 score does not depend on the other slots' audio or phase).  ``samples_seen`` counts each slot's samples since its reset.
+
+Non-paced streams: ``push(chunk, slots)`` brings one hop for the named slots only (indices in any order, or a bool mask =
+ascending order; chunk row i is slot slots[i]'s next hop) and returns their scores in that order.  Nothing of any other slot
+changes -- history, conv carries, layer-5 frames, K / V rings, positional-conv context, feature window, ``samples_seen`` --
+and a slot's j-th score equals, bit for bit, its score at tick j of a fresh lock-stepped scorer with the same S fed its hops
+back to back (the same row-wise argument: a sub-batch gives a row the bits the whole batch gives it).  The cost of a tick
+follows the number of named slots.  ``slots=None`` is the lock-stepped push; after the first push with slots, every push
+takes the per-slot path (with ``slots=None`` meaning every slot).
 """
 import torch
 
@@ -56,6 +64,7 @@ class SlidingWindowScorer:
         self.total = 0  # samples pushed since construction (every slot receives one hop per push)
         self._seen = torch.zeros(n_streams, dtype=torch.int64)  # samples per slot since its last reset (host)
         self._uniform = True  # every slot at the same phase: the lockstep path
+        self._per_slot = False  # after the first push with slots: every push names its slots (slots=None: all of them)
         self._offs = (torch.arange(n_streams + 1, dtype=torch.int64) * window).to(device)
         self._starts = torch.zeros(n_streams, dtype=torch.int64, device=device)
         self._batch = torch.empty(n_streams, window, dtype=torch.float32, device=device)
@@ -65,8 +74,9 @@ class SlidingWindowScorer:
         """(S,) int64: the samples each slot received since its last ``reset`` (or since construction)."""
         return self._seen.clone()
 
-    def _slot_list(self, slots):
-        """``slots``: slot indices or a bool mask of length S -> sorted list of distinct indices; bad input is a ValueError."""
+    def _slot_list(self, slots, ordered=False):
+        """``slots``: slot indices or a bool mask of length S -> sorted list of distinct indices (``ordered``: in the order
+        given; a mask counts as ascending); bad input is a ValueError."""
         t = torch.as_tensor(slots)
         if t.numel() == 0 and t.ndim <= 1:
             return []
@@ -82,7 +92,7 @@ class SlidingWindowScorer:
             raise ValueError(f"slot index {bad[0]} outside 0..{self.S - 1}")
         if len(set(idx)) != len(idx):
             raise ValueError("a slot is named twice")
-        return sorted(idx)
+        return idx if ordered else sorted(idx)
 
     def reset(self, slots):
         """The named slots (indices or a bool mask) begin a new stream with their next ``push``; the others are untouched."""
@@ -131,11 +141,52 @@ class SlidingWindowScorer:
                 self._batch[warm] = self._warm_windows(warm)
         return self._batch
 
-    def push(self, chunk):
+    def push(self, chunk, slots=None):
         """chunk: (S, hop) fp32 on the GPU, the newest `hop` samples of every stream.
-        Returns the (S,) bonafide scores of the current windows."""
+        Returns the (S,) bonafide scores of the current windows.
+        slots (non-paced streams): slot indices or a bool mask; chunk is then (len(slots), hop), row i the next hop of
+        slots[i], only those slots advance, and the (len(slots),) scores come in the same order."""
+        if slots is None and not self._per_slot:
+            with torch.cuda.device(self.device):
+                return self._push(chunk)
+        idx = list(range(self.S)) if slots is None else self._slot_list(slots, ordered=True)
+        if not isinstance(chunk, torch.Tensor) or not chunk.is_cuda or chunk.shape != (len(idx), self.hop):
+            raise ValueError(f"expected a CUDA tensor of shape {(len(idx), self.hop)} (one hop per named slot)")
+        if not idx:
+            return torch.empty(0, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            return self._push(chunk)
+            self._per_slot = True
+            return self._push_slots(chunk, idx)
+
+    def _store_slots(self, chunk, idx):
+        """Row i of ``chunk`` into slot idx[i]'s ring at that slot's own phase (the scatter path of a reset scorer)."""
+        dev = self.ring.device
+        rows = torch.tensor(idx, device=dev)
+        pos = (self._seen[idx] % self.window).to(dev, non_blocking=True)
+        col = (pos[:, None] + torch.arange(self.hop, device=dev)) % self.window
+        self.ring[rows[:, None], col] = chunk.to(self.ring.dtype)
+        self._uniform = False  # (phases differ from here on: the per-slot paths for the scorer's life)
+        self._seen[idx] += self.hop
+
+    def _windows_of(self, idx):
+        """The windows of the slots ``idx``: the tiled history of a slot younger than the window, else its ring from the oldest
+        sample on (the named rows of the ring, then one batched afx_k_tile_crop read)."""
+        A = len(idx)
+        rows = torch.tensor(idx, device=self.ring.device)
+        sub = self.ring.index_select(0, rows)
+        self._starts[:A].copy_(self._seen[idx] % self.window)
+        check(call_on(self.ring, lib().afx_k_tile_crop, ptr(sub), ptr(self._offs), ptr(self._starts), A, self.window, ptr(self._batch)))
+        batch = self._batch[:A]
+        warm = [i for i, s in enumerate(idx) if int(self._seen[s]) < self.window]
+        if warm:
+            batch[warm] = self._warm_windows([idx[i] for i in warm])
+        return batch
+
+    def _push_slots(self, chunk, idx):
+        self._store_slots(chunk, idx)
+        batch = self._windows_of(idx)
+        out = self.model.forward(batch) if hasattr(self.model, "forward") else self.model(batch)
+        return out[:, 1]
 
     def _push(self, chunk):
         self._store(chunk)
@@ -189,6 +240,7 @@ class IncrementalScorer(SlidingWindowScorer):
         # the newest T5 - 1 frames move to its front: one copy of the window every ~T5 / 25 hops instead of two per hop.
         self._l5_buf = torch.empty(n_streams, 2 * self.T5, 512, dtype=K.torch_dtype(self.dt), device=dev)
         self._l5_end = 0
+        self._l5_e = None  # per-slot ends (host int64, S) from the first push with slots on; `_l5_end` is the lock-stepped one
 
     @property
     def l5(self):
@@ -260,6 +312,91 @@ class IncrementalScorer(SlidingWindowScorer):
                 x = torch.cat([carry[i + 1], y], dim=1)
         return y
 
+    def _advance_slots(self, chunk, idx):
+        """Conv layers 0-5 on the named slots only (chunk row i = slot idx[i]), each from its own carries -- slots on the first
+        hop of a session from empty ones, one sub-batch each -- -> ((A, nb, 512) new layer-5 frames, right-aligned, or None;
+        the per-row frame counts).  The other slots' carries are untouched."""
+        dev = chunk.device
+        first = [i for i, s in enumerate(idx) if int(self._seen[s]) == self.hop]  # (_store_slots has counted this hop)
+        fs = set(first)
+        parts = []
+        for pos, fresh in ((first, True), ([i for i in range(len(idx)) if i not in fs], False)):
+            if not pos:
+                continue
+            pt, st = torch.tensor(pos, device=dev), torch.tensor([idx[i] for i in pos], device=dev)
+            c = [cr.new_empty(len(pos), 0, *cr.shape[2:]) for cr in self.carry] if fresh else [cr.index_select(0, st) for cr in self.carry]
+            parts.append((pt, st, c, self._advance_rows(chunk.index_select(0, pt), c)))
+        for i in range(6):
+            w = parts[0][2][i].shape[1:]
+            if any(p[2][i].shape[1:] != w for p in parts):
+                raise RuntimeError("conv carries of a new session differ from the steady state's: hop / stride mismatch")
+            if self.carry[i].shape[1:] != w:  # (the first hop of any slot: no slot holds a carry of another width)
+                self.carry[i] = self.carry[i].new_zeros(self.S, *w)
+            for pt, st, c, _ in parts:
+                self.carry[i][st] = c[i]
+        n5 = [0] * len(idx)
+        nb = max(0 if y is None else y.shape[1] for *_, y in parts)
+        if nb == 0:
+            return None, n5
+        ref = next(y for *_, y in parts if y is not None)
+        out = ref.new_zeros(len(idx), nb, ref.shape[2])
+        for pt, _, _, y in parts:
+            if y is not None and y.shape[1]:
+                out[pt, nb - y.shape[1]:] = y
+                for i in pt.tolist():
+                    n5[i] = y.shape[1]
+        return out, n5
+
+    def _l5_append_slots(self, idx, y, n5):
+        """Layer-5 frames of the named slots at each slot's own end of the buffer (per-slot ends from the first push with
+        slots on); a slot whose part is full keeps the frames its next window needs, at the front."""
+        if self._l5_e is None:
+            self._l5_e = torch.full((self.S,), self._l5_end, dtype=torch.int64)
+        if y is None:
+            return
+        dev, cap = y.device, self._l5_buf.shape[1]
+        nt = torch.tensor(n5, dtype=torch.int64)
+        ends = self._l5_e[idx]
+        full = (ends + nt > cap).nonzero().flatten().tolist()
+        for e in sorted({int(ends[i]) for i in full}):  # one copy per distinct end
+            rows = [idx[i] for i in full if int(ends[i]) == e]
+            keep = min(e, self.T5)
+            rt = torch.tensor(rows, device=dev)
+            self._l5_buf[rt, :keep] = self._l5_buf[rt, e - keep:e]
+            self._l5_e[rows] = keep
+        ends = self._l5_e[idx]
+        nb = y.shape[1]
+        j = torch.arange(nb)
+        valid = j[None, :] >= (nb - nt)[:, None]  # row i's n5[i] frames are its last ones (right-aligned)
+        ri, ji = valid.nonzero(as_tuple=True)
+        col = ends[ri] + ji - (nb - nt[ri])
+        slot = torch.tensor(idx, dtype=torch.int64)[ri]
+        self._l5_buf[slot.to(dev), col.to(dev)] = y[ri.to(dev), ji.to(dev)]
+        self._l5_e[idx] = ends + nt
+
+    def _l5_windows(self, slots):
+        """(len(slots), T5, 512): the newest T5 layer-5 frames of each slot, gathered into one dense operand."""
+        dev = self._l5_buf.device
+        ends = self._l5_e[slots]
+        if bool((ends < self.T5).any()):
+            raise RuntimeError("a steady slot holds fewer than T5 layer-5 frames")
+        cols = ends[:, None] - self.T5 + torch.arange(self.T5)
+        return self._l5_buf[torch.tensor(slots, device=dev)[:, None], cols.to(dev)]
+
+    def _push_slots(self, chunk, idx):
+        self._store_slots(chunk, idx)
+        y, n5 = self._advance_slots(chunk, idx)
+        self._l5_append_slots(idx, y, n5)
+        warm = [i for i, s in enumerate(idx) if int(self._seen[s]) < self.window]  # still filling: the tiled history
+        steady = [i for i in range(len(idx)) if int(self._seen[idx[i]]) >= self.window]
+        dev = self.eng.device
+        out = torch.empty(len(idx), 2, dtype=torch.float32, device=dev)
+        if warm:
+            out[torch.tensor(warm, device=dev)] = self.eng.forward(self._warm_windows([idx[i] for i in warm]))
+        if steady:
+            out[torch.tensor(steady, device=dev)] = self.eng.tail(self._l5_windows([idx[i] for i in steady]))
+        return out[:, 1]
+
     def _reset_slots(self, idx):
         super()._reset_slots(idx)
         if bool((self._seen == 0).all()):  # every slot starts afresh: the lockstep path from empty carries
@@ -316,7 +453,10 @@ class KVCachedScorer(IncrementalScorer):
 
     Sessions: after the first ``reset`` the conv-layer-6 carries are per slot (slots at different phases complete 12 or 13
     frames in the same hop) and every hop goes through the library's per-stream step (afx_kv_step_ragged: per-stream
-    valid counts, base groups and windows)."""
+    valid counts, base groups and windows).
+
+    Non-paced streams: ``push(chunk, slots)`` runs conv layers 0-6 on the named rows and one library step over the list
+    (afx_kv_step_active: each stream writes its own ring group); from then on every push goes through that step."""
 
     _exact_conv_ok = True  # dtype "fp16x3": every hop within 1e-3 of the offline restatement whatever the top-k gaps (round 4)
 
@@ -337,7 +477,7 @@ class KVCachedScorer(IncrementalScorer):
         self._sessions = False  # after the first reset: per-slot conv-layer-6 carries and the library's per-stream step
         self._n5 = None
 
-    def _reset_slots(self, idx):
+    def _per_slot_c6(self):
         if not self._sessions:  # the lock-stepped carries become per-slot ones (width 0 or 1 frame each)
             w = self.carry6.shape[1]
             self._c6 = self.carry6.new_zeros(self.S, 1, 512)
@@ -345,38 +485,61 @@ class KVCachedScorer(IncrementalScorer):
                 self._c6[:, :w] = self.carry6
             self._c6w = [w] * self.S
             self._sessions = True
+
+    def _reset_slots(self, idx):
+        self._per_slot_c6()
         self.kv.reset(idx)
         for b in idx:
             self._c6w[b] = 0
         super()._reset_slots(idx)
 
-    def _step_sessions(self, new5):
+    def _conv6_slots(self, new5, n5, idx):
         """Conv layer 6 per slot -- a slot's frames and carry depend on its own phase (12 or 13 frames per hop from its own
-        first sample) -- one sub-batch per (carry, new frames) pair, then the library's per-stream step."""
+        first sample) -- one sub-batch per (carry, new frames) pair.  new5 row i (its last n5[i] frames) is slot idx[i]'s;
+        -> ((A, n_max, 512) fp32 conv-layer-6 frames, first-aligned; the per-row counts)."""
         nb = new5.shape[1]
-        n5 = self._n5 if self._n5 is not None else [nb] * self.S
         groups = {}
-        for b in range(self.S):
-            groups.setdefault((self._c6w[b], n5[b]), []).append(b)
-        outs, n6 = [], [0] * self.S
-        for (c, f), idx in groups.items():
+        for i, b in enumerate(idx):
+            groups.setdefault((self._c6w[b], n5[i]), []).append(i)
+        outs, n6 = [], [0] * len(idx)
+        for (c, f), pos in groups.items():
             n_out = (c + f - 2) // 2 + 1 if c + f >= 2 else 0
             if n_out < 1:
                 raise RuntimeError("a hop completed no conv-layer-6 frame for some slot")
-            it = torch.tensor(idx, device=new5.device)
-            x = torch.cat([self._c6.index_select(0, it)[:, :c], new5.index_select(0, it)[:, nb - f:]], dim=1)
+            it = torch.tensor(pos, device=new5.device)
+            st = torch.tensor([idx[i] for i in pos], device=new5.device)
+            x = torch.cat([self._c6.index_select(0, st)[:, :c], new5.index_select(0, it)[:, nb - f:]], dim=1)
             y = self._conv_ln_gelu(x, self.cw6, 2, 2, self.cb6, self.lg6, self.lb6, fp32_out=True)
             rest = c + f - 2 * n_out
             if rest:
-                self._c6[it, :rest] = x[:, 2 * n_out:]
-            for b in idx:
-                self._c6w[b], n6[b] = rest, n_out
+                self._c6[st, :rest] = x[:, 2 * n_out:]
+            for i in pos:
+                self._c6w[idx[i]], n6[i] = rest, n_out
             outs.append((it, y))
         n_max = max(n6)
-        f6 = torch.zeros(self.S, n_max, 512, dtype=torch.float32, device=new5.device)
+        f6 = torch.zeros(len(idx), n_max, 512, dtype=torch.float32, device=new5.device)
         for it, y in outs:
             f6[it, :y.shape[1]] = y
+        return f6, n6
+
+    def _step_sessions(self, new5):
+        """Conv layer 6 per slot, then the library's per-stream step over every slot."""
+        nb = new5.shape[1]
+        n5 = self._n5 if self._n5 is not None else [nb] * self.S
+        f6, n6 = self._conv6_slots(new5, n5, range(self.S))
         return self.kv.step(f6, n_frames=n6)[:, 1]
+
+    def _push_slots(self, chunk, idx):
+        """Only the named slots: conv layers 0-5 and 6 on their rows, then one step of the library over the list
+        (afx_kv_step_active: each stream writes its own ring group; the other streams' state is not touched)."""
+        self._seen[idx] += self.hop
+        self._uniform = False
+        new5, n5 = self._advance_slots(chunk, idx)
+        if new5 is None:
+            return None
+        self._per_slot_c6()
+        f6, n6 = self._conv6_slots(new5, n5, idx)
+        return self.kv.step(f6, n_frames=n6, slots=idx)[:, 1]
 
     def _push(self, chunk):
         if chunk.shape != (self.S, self.hop) or not chunk.is_cuda:

@@ -41,6 +41,11 @@ struct MhsaRing {
 // ring.cnt -- `lens` then points at (S, 8) ints per stream: [0] = the stream's base group (the group of its first chunk),
 // ints [4, 8) = its 16 valid counts as bytes -- and the 256 slots are visited rotated by the base group: key i is slot
 // (((i >> 4) + base) & 15) * 16 + (i & 15).  Key and summation order are then those of a stream that started at group 0.
+// RING == 3 (a step over a list of active streams, afx_kv_step_active): as RING == 2, with `lens` a compact (A, 8) table
+// whose row b also names the stream -- [1] its newest group (the query tile), [2] its index among the S rings -- so
+// blockIdx.y walks the list and output row b is list entry b's.
+// (read where it is used, as ring.q_tile always was: the RING < 3 forms compile to the instructions they had)
+#define ring_qtile (RING == 3 ? lens[(long)b * 8 + 1] : ring.q_tile)
 __device__ __forceinline__ int ring_slot(int key, int base) { return ((((key >> 4) + base) & 15) << 4) | (key & 15); }
 // VTR (round 3): V stays ROW-major in LDS (staged exactly like K: one swizzled 16-byte write per loaded chunk, no transposing
 // scatter) and the V^T fragments of P.V come from `ds_read_b64_tr_b16` -- per 16-lane group a block of 4 keys x 16 dims delivered
@@ -66,10 +71,12 @@ __global__ __launch_bounds__(64 * NW, NW > 4 ? 4 : 2) void mhsa_kernel(const typ
   // Ragged batch (key-padding mask): utterance b has lens[b] valid frames of the Trow rows it owns in memory; from
   // here on T is ITS length -- keys beyond it are staged as zeros and masked, queries beyond it are not computed.
   const int Trow = T;
-  if (RING != 2 && lens) T = lens[b];
-  const unsigned char* scnt = RING == 2 ? (const unsigned char*)(lens + (long)b * 8 + 4) : nullptr;
-  const int sbase = RING == 2 ? lens[(long)b * 8] : 0;
-  const Tt* base = qkv + (long)b * Trow * ld + h * 64;
+  if (RING < 2 && lens) T = lens[b];
+  const unsigned char* scnt = RING >= 2 ? (const unsigned char*)(lens + (long)b * 8 + 4) : nullptr;
+  const int sbase = RING >= 2 ? lens[(long)b * 8] : 0;
+  // RING == 3 (afx_kv_step_active): row b of the table belongs to the active stream lens[8 b + 2], whose newest chunk
+  // sits in ITS OWN group lens[8 b + 1] (ring_qtile); the output stays row b
+  const Tt* base = qkv + (long)(RING == 3 ? lens[(long)b * 8 + 2] : b) * Trow * ld + h * 64;
   const Tt* kbase = base + (long)H * 64;
   const Tt* vbase = base + 2L * H * 64;
 
@@ -91,8 +98,8 @@ __global__ __launch_bounds__(64 * NW, NW > 4 ? 4 : 2) void mhsa_kernel(const typ
       kreg[it] = u32x4{0u, 0u, 0u, 0u};
 #pragma unroll
       for (int i = 0; i < 8; ++i) vreg[it][i] = (Tt)0.f;
-      const int slot = RING == 2 ? ring_slot(key, sbase) : key;
-      const bool live = RING == 2 ? (slot & 15) < scnt[slot >> 4] : RING ? (key & 15) < ring.cnt[(key >> 4) & 15] : key < T;
+      const int slot = RING >= 2 ? ring_slot(key, sbase) : key;
+      const bool live = RING >= 2 ? (slot & 15) < scnt[slot >> 4] : RING ? (key & 15) < ring.cnt[(key >> 4) & 15] : key < T;
       if (live && !(MHSA_DBG & 1)) {
         kreg[it] = *(const u32x4*)(kbase + (long)slot * ld + c * 8);
         vreg[it] = *(const V8*)(vbase + (long)slot * ld + c * 8);
@@ -129,7 +136,7 @@ __global__ __launch_bounds__(64 * NW, NW > 4 ? 4 : 2) void mhsa_kernel(const typ
     }
   }
   for (int i = tid; i < KEYS; i += 64 * NW)
-    mask_lds[i] = (RING == 2 ? (i & 15) < scnt[ring_slot(i, sbase) >> 4] : RING ? (i & 15) < ring.cnt[(i >> 4) & 15] : i < T) ? 0.f : -1e30f;
+    mask_lds[i] = (RING >= 2 ? (i & 15) < scnt[ring_slot(i, sbase) >> 4] : RING ? (i & 15) < ring.cnt[(i >> 4) & 15] : i < T) ? 0.f : -1e30f;
   __syncthreads();
   if (MHSA_DBG & 2) return;
 
@@ -138,8 +145,8 @@ __global__ __launch_bounds__(64 * NW, NW > 4 ? 4 : 2) void mhsa_kernel(const typ
   // at small batches B x H workgroups do not fill the chip (B = 16: 256 of them for 256 CUs x 2 slots)
   const int nqt_all = (T + 15) >> 4;
   const int per_z = (nqt_all + (int)gridDim.z - 1) / (int)gridDim.z;
-  const int qt_first = RING ? ring.q_tile : (int)blockIdx.z * per_z;
-  const int nqt = RING ? ring.q_tile + 1 : min(nqt_all, qt_first + per_z);
+  const int qt_first = RING ? ring_qtile : (int)blockIdx.z * per_z;
+  const int nqt = RING ? ring_qtile + 1 : min(nqt_all, qt_first + per_z);
   auto load_q = [&](int qt, V8 (&f)[2]) {
     int qrow = qt * 16 + ql;
     qrow = qrow < T ? qrow : T - 1;
@@ -294,7 +301,7 @@ __global__ __launch_bounds__(64 * NW, NW > 4 ? 4 : 2) void mhsa_kernel(const typ
           hv[r] = (Tt)va[r];
           hv[4 + r] = (Tt)vb[r];
         }
-        const long orow = RING ? (long)b * 16 + (q - 16 * ring.q_tile) : (long)b * Trow + q;
+        const long orow = RING ? (long)b * 16 + (q - 16 * ring_qtile) : (long)b * Trow + q;
         *(V8*)(out + orow * (H * 64) + h * 64 + np * 32 + cb) = hv;
       }
     }
@@ -328,10 +335,12 @@ __global__ __launch_bounds__(64 * NW, 2) void mhsa_split_kernel(const float* __r
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long ld = 3L * H * 64;
   const int Trow = T;
-  if (RING != 2 && lens) T = lens[b];
-  const unsigned char* scnt = RING == 2 ? (const unsigned char*)(lens + (long)b * 8 + 4) : nullptr;
-  const int sbase = RING == 2 ? lens[(long)b * 8] : 0;
-  const float* base = qkv + (long)b * Trow * ld + h * 64;
+  if (RING < 2 && lens) T = lens[b];
+  const unsigned char* scnt = RING >= 2 ? (const unsigned char*)(lens + (long)b * 8 + 4) : nullptr;
+  const int sbase = RING >= 2 ? lens[(long)b * 8] : 0;
+  // RING == 3 (afx_kv_step_active): row b of the table belongs to the active stream lens[8 b + 2], whose newest chunk
+  // sits in ITS OWN group lens[8 b + 1] (ring_qtile); the output stays row b
+  const float* base = qkv + (long)(RING == 3 ? lens[(long)b * 8 + 2] : b) * Trow * ld + h * 64;
   const float* kbase = base + (long)H * 64;
   const float* vbase = base + 2L * H * 64;
   auto split8 = [](const f32x4& a, const f32x4& c, V8& hi, V8& lo) {
@@ -349,8 +358,8 @@ __global__ __launch_bounds__(64 * NW, 2) void mhsa_split_kernel(const float* __r
     for (int idx = tid; idx < KEYS * 8; idx += NT) {
       const int key = idx >> 3, c = idx & 7;
       f32x4 k0 = f32x4{0.f, 0.f, 0.f, 0.f}, k1 = k0, v0 = k0, v1 = k0;
-      const int slot = RING == 2 ? ring_slot(key, sbase) : key;
-      if (RING == 2 ? (slot & 15) < scnt[slot >> 4] : RING ? (key & 15) < ring.cnt[(key >> 4) & 15] : key < T) {
+      const int slot = RING >= 2 ? ring_slot(key, sbase) : key;
+      if (RING >= 2 ? (slot & 15) < scnt[slot >> 4] : RING ? (key & 15) < ring.cnt[(key >> 4) & 15] : key < T) {
         k0 = *(const f32x4*)(kbase + (long)slot * ld + c * 8);
         k1 = *(const f32x4*)(kbase + (long)slot * ld + c * 8 + 4);
         v0 = *(const f32x4*)(vbase + (long)slot * ld + c * 8);
@@ -368,13 +377,13 @@ __global__ __launch_bounds__(64 * NW, 2) void mhsa_split_kernel(const float* __r
     }
   }
   for (int i = tid; i < KEYS; i += 64 * NW)
-    mask_lds[i] = (RING == 2 ? (i & 15) < scnt[ring_slot(i, sbase) >> 4] : RING ? (i & 15) < ring.cnt[(i >> 4) & 15] : i < T) ? 0.f : -1e30f;
+    mask_lds[i] = (RING >= 2 ? (i & 15) < scnt[ring_slot(i, sbase) >> 4] : RING ? (i & 15) < ring.cnt[(i >> 4) & 15] : i < T) ? 0.f : -1e30f;
   __syncthreads();
   const int ql = lane & 15, g = lane >> 4;
   const int nqt_all = (T + 15) >> 4;
   const int per_z = (nqt_all + (int)gridDim.z - 1) / (int)gridDim.z;
-  const int qt_first = RING ? ring.q_tile : (int)blockIdx.z * per_z;
-  const int nqt = RING ? ring.q_tile + 1 : min(nqt_all, qt_first + per_z);
+  const int qt_first = RING ? ring_qtile : (int)blockIdx.z * per_z;
+  const int nqt = RING ? ring_qtile + 1 : min(nqt_all, qt_first + per_z);
   for (int qt = qt_first + wave; qt < nqt; qt += NW) {
     const int q0 = qt * 16;
     int qrow = q0 + ql;
@@ -478,7 +487,7 @@ __global__ __launch_bounds__(64 * NW, 2) void mhsa_split_kernel(const float* __r
     }
     const int q = q0 + ql;
     if (q < T) {
-      const long eoff = (RING ? (long)b * 16 + (q - 16 * ring.q_tile) : (long)b * Trow + q) * (H * 64) + h * 64;
+      const long eoff = (RING ? (long)b * 16 + (q - 16 * ring_qtile) : (long)b * Trow + q) * (H * 64) + h * 64;
       if (out_pairs) {  // the output projection's A operand: the pair form of out_scale x value in place of the fp32 row
         _Float16* hp = (_Float16*)out + 2 * eoff;  // (eoff % 64 == 0: a head's 64 columns are two whole 32-element groups)
 #pragma unroll
@@ -701,6 +710,7 @@ static void launch_mhsa_t(const void* qkv, void* out, int B, int T, int H, float
 
 // KV-cached streaming attention (see MhsaRing): ring (S, 256 slots, 3 H 64) operand type, out (S, 16, H 64); cnt[16] = valid
 // frames per 16-slot group, q_tile = the group of the newest chunk.
+#undef ring_qtile
 const char* launch_mhsa_ring(const void* ring, void* out, int S, int H, int q_tile, const int* cnt, int dtype, hipStream_t s) {
   if (S <= 0 || S > 65535 || H <= 0 || q_tile < 0 || q_tile > 15) return "mhsa_ring: bad shape";
   if (dtype != DT_FP16 && dtype != DT_BF16) return "mhsa_ring: half-precision operands only";
@@ -728,6 +738,20 @@ const char* launch_mhsa_ring_tab(const void* ring, void* out, int S, int H, int 
     hipLaunchKernelGGL((mhsa_kernel<BF16, 8, 4, 2, true>), dim3(H, S, 1), dim3(256), 0, s, (const BF16::T*)ring, (BF16::T*)out, 256, H, 0.125f, tab, r);
   else
     hipLaunchKernelGGL((mhsa_kernel<FP16, 8, 4, 2, true>), dim3(H, S, 1), dim3(256), 0, s, (const FP16::T*)ring, (FP16::T*)out, 256, H, 0.125f, tab, r);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+// the active-list form (RING == 3): S = list length, tab = (S, 8) ints per list entry -- [0] base group, [1] the stream's newest
+// group, [2] its ring index, bytes [16, 32) its 16 valid counts
+const char* launch_mhsa_ring_active(const void* ring, void* out, int S, int H, const int* tab, int dtype, hipStream_t s) {
+  if (S <= 0 || S > 65535 || H <= 0 || !tab) return "mhsa_ring: bad shape";
+  if (dtype != DT_FP16 && dtype != DT_BF16) return "mhsa_ring: half-precision operands only";
+  MhsaRing r = {};
+  if (dtype == DT_BF16)
+    hipLaunchKernelGGL((mhsa_kernel<BF16, 8, 4, 3, true>), dim3(H, S, 1), dim3(256), 0, s, (const BF16::T*)ring, (BF16::T*)out, 256, H, 0.125f, tab, r);
+  else
+    hipLaunchKernelGGL((mhsa_kernel<FP16, 8, 4, 3, true>), dim3(H, S, 1), dim3(256), 0, s, (const FP16::T*)ring, (FP16::T*)out, 256, H, 0.125f, tab, r);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? nullptr : hipGetErrorString(e);
 }
@@ -784,6 +808,18 @@ const char* launch_mhsa_ring_split_tab(const float* ring, float* out, int S, int
   MhsaRing r = {};
   r.q_tile = q_tile;
   hipLaunchKernelGGL((mhsa_split_kernel<8, 4, 2>), dim3(H, S, 1), dim3(256), 0, s, ring, out, 256, H, 0.125f, tab, out_pairs ? 1 : 0,
+                     out_scale, r);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+
+// the active-list form of the split-precision ring (see launch_mhsa_ring_active)
+const char* launch_mhsa_ring_split_active(const float* ring, float* out, int S, int H, const int* tab, hipStream_t s, bool out_pairs,
+                                          float out_scale) {
+  if (S <= 0 || S > 65535 || H <= 0 || !tab) return "mhsa_ring: bad shape";
+  MhsaRing r = {};
+  hipLaunchKernelGGL((mhsa_split_kernel<8, 4, 3>), dim3(H, S, 1), dim3(256), 0, s, ring, out, 256, H, 0.125f, tab, out_pairs ? 1 : 0,
                      out_scale, r);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? nullptr : hipGetErrorString(e);

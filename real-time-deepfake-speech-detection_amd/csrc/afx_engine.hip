@@ -896,7 +896,8 @@ static const char* timed(int cls, double flops, hipStream_t s, F&& f) {
 // the workspace's scratch; ONE launch then walks the 2 K halfs of a row like a plain fp16 operand and issues three matrix
 // instructions per K-step on the fragments it reads anyway (round 3 walked K three times over separate hi / lo planes: 1.5x
 // the K-tiles, operand bytes and fragment reads for the same matrix-pipe work).
-static const char* P_gemm(const GemmArgs& g_in, int dt, int groups, hipStream_t s) {
+// rows: the product goes to launch_gemm_rows (GemmArgs::oh_rows holds its output row table)
+static const char* P_gemm(const GemmArgs& g_in, int dt, int groups, hipStream_t s, bool rows = false) {
   GemmArgs g = g_in;
   g.no_deep = t_no_deep;  // (the engine's "gemm_small_deep" switch)
   const double fl = 2.0 * g.M * g.N * (g.k_algo ? g.k_algo : g.K) * groups;
@@ -908,6 +909,7 @@ static const char* P_gemm(const GemmArgs& g_in, int dt, int groups, hipStream_t 
   if (dt == DT_FP32 && t_s3planes) {
     const bool groups32 = !(g.K % 32 || g.kchunk % 32 || g.a_row % 32 || g.a_batch % 32 || g.g_a % 32 || g.kchunk_stride % 32 || g.ldw % 32 || g.g_w % 32);
     if (!groups32 || ((size_t)g.A & 15)) {  // (rows the pair form cannot address in whole 32-element groups: the fp32 instruction)
+      if (rows) return "split-precision product with a row table: the operands must be pair-form addressable";
       if (g.out_h) s3_set(g.out_h, 0.f);
       return launch_gemm(g, DT_FP32, groups, s);
     }
@@ -945,9 +947,11 @@ static const char* P_gemm(const GemmArgs& g_in, int dt, int groups, hipStream_t 
       s3_set(g.out_h, pairs_out ? q.oh_scale : 0.f);
     }
     const int tile = gemm_tile_of(q, groups);
-    return timed(cls_of(tile), fl, s, [&] { return launch_gemm(q, DT_FP16X3, groups, s); });
+    return timed(cls_of(tile), fl, s, [&] { return rows ? launch_gemm_rows(q, DT_FP16X3, s) : launch_gemm(q, DT_FP16X3, groups, s); });
   }
-  return timed(dt == DT_FP32 ? PC_GEMM_F32 : cls_of(gemm_tile_of(g, groups)), fl, s, [&] { return launch_gemm(g, dt, groups, s); });
+  if (rows && (dt == DT_FP32 || groups != 1)) return "gemm with a row table: half- or split-precision operands, one group";
+  return timed(dt == DT_FP32 ? PC_GEMM_F32 : cls_of(gemm_tile_of(g, groups)), fl, s,
+               [&] { return rows ? launch_gemm_rows(g, dt, s) : launch_gemm(g, dt, groups, s); });
 }
 static const char* P_rownorm(const RowNormArgs& a_in, int dt, hipStream_t s) {
   RowNormArgs a = a_in;
@@ -1396,8 +1400,13 @@ struct afx_kv {
   float* feat[2] = {nullptr, nullptr};  // (S, 208, 1024) fp32, right-aligned window, ping-pong
   // per-stream sessions (afx_kv_reset / afx_kv_step_ragged): once either is called, the state is per stream
   bool per_stream = false;
-  int* tab = nullptr;    // device (S, 8) ints: [0] base group (the group of the stream's first chunk), bytes [16, 32) valid counts
-  int* meta = nullptr;   // device (4 S) ints, written per call: frame counts | 64 + frame counts | window lengths | slot lists
+  // steps over a list of streams (afx_kv_step_active): from the first one on, the ring group is per stream ([1] of tab) and
+  // each stream's window stays in feat[pp] (shifted in place); afx_kv_step_ragged then refuses the state
+  bool active = false;
+  int* tab = nullptr;    // device (S, 8) ints: [0] base group (the group of the stream's first chunk), [1] (active) its next group,
+                         // bytes [16, 32) valid counts
+  int* meta = nullptr;   // device (16 S) ints, written per call: frame counts | 64 + frame counts | window lengths | slot lists,
+                         // (active steps) + back-end order | its stream ids | QKV row table | (8 A) the list's attention table
   std::vector<int> nfeat_s, hmeta;
 };
 struct KvWs {
@@ -1441,7 +1450,7 @@ extern "C" int afx_kv_create(afx_handle h, int n_streams, afx_kv** out) {
   for (int i = 0; i < kKvGroups; ++i) k->cnt[i] = 0;
   const size_t hs = h->hsz, ring = (size_t)h->cfg.n_layers * n_streams * kKvSlots * 3 * kD * hs, hist = (size_t)n_streams * kKvHist * kD * hs,
                feat = (size_t)n_streams * kKvFeat * kD * 4;
-  bool ok = hipMalloc((void**)&k->tab, (size_t)n_streams * 32) == hipSuccess && hipMalloc((void**)&k->meta, (size_t)n_streams * 16) == hipSuccess &&
+  bool ok = hipMalloc((void**)&k->tab, (size_t)n_streams * 32) == hipSuccess && hipMalloc((void**)&k->meta, (size_t)n_streams * 64) == hipSuccess &&
             hipMemset(k->tab, 0, (size_t)n_streams * 32) == hipSuccess &&
             hipMalloc(&k->rings, ring) == hipSuccess && hipMalloc(&k->hist, hist) == hipSuccess &&
             hipMalloc((void**)&k->feat[0], feat) == hipSuccess && hipMalloc((void**)&k->feat[1], feat) == hipSuccess;
@@ -1477,6 +1486,7 @@ extern "C" size_t afx_kv_workspace_bytes(const afx_kv* k, int n_frames) {
 extern "C" int afx_kv_step(afx_kv* k, const float* feats6, int n, float* logits, void* ws, size_t ws_bytes, void* stream) {
   if (n < 1 || n > 16) return fail("afx_kv_step: a chunk brings 1..16 frames (got %d)", n);
   if (!k || !feats6 || !logits || !ws) return fail("afx_kv_step: null argument");
+  if (k->active) return fail("afx_kv_step: this state holds per-stream ring positions (afx_kv_step_active): continue with afx_kv_step_active");
   if (k->per_stream) return fail("afx_kv_step: this state holds per-stream sessions (afx_kv_reset / afx_kv_step_ragged): continue with afx_kv_step_ragged");
   afx_engine* e = k->e;
   const int S = k->S, dt = e->dt, M = S * n, Tp = kKvHist + n, group = (int)(k->hop % kKvGroups);
@@ -1611,7 +1621,10 @@ extern "C" int afx_kv_step(afx_kv* k, const float* feats6, int n, float* logits,
 __global__ void kv_reset_kernel(const int* __restrict__ slots, int* __restrict__ tab, int base_group, u32x4* __restrict__ hist,
                                 long hist_words, u32x4* __restrict__ f0, u32x4* __restrict__ f1, long feat_words) {
   const long sl = slots[blockIdx.y];
-  if (blockIdx.x == 0 && threadIdx.x < 8) tab[sl * 8 + threadIdx.x] = threadIdx.x == 0 ? base_group : 0;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {  // base_group < 0 (active steps): the new stream starts at the slot's own next group
+    const int g = base_group >= 0 ? base_group : tab[sl * 8 + 1];
+    for (int j = 0; j < 8; ++j) tab[sl * 8 + j] = j == 0 ? g : j == 1 && base_group < 0 ? g : 0;
+  }
   const u32x4 z = {0u, 0u, 0u, 0u};
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < hist_words; i += (long)gridDim.x * blockDim.x) hist[sl * hist_words + i] = z;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < feat_words; i += (long)gridDim.x * blockDim.x) {
@@ -1623,13 +1636,17 @@ __global__ void kv_count_kernel(int* __restrict__ tab, const int* __restrict__ n
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b < S) ((unsigned char*)(tab + (long)b * 8 + 4))[group] = (unsigned char)n[b];
 }
-// hist[s] = rows [pad + n_s, pad + n_s + 64) of stream s's padded rows (the newest 64 projected frames); 16-byte words
-__global__ void kv_hist_kernel(u32x4* __restrict__ hist, const u32x4* __restrict__ xpad, const int* __restrict__ n, long row_words,
-                               long xpad_rows, int pad) {
-  const long b = blockIdx.y;
+// hist[s] = rows [pad + n_s, pad + n_s + 64) of stream s's padded rows (the newest 64 projected frames); 16-byte words.
+// ids (active steps): padded-row block b is stream ids[b]'s; gather != 0 copies the other way, hist[ids[b]] -> rows [pad, pad + 64)
+__global__ void kv_hist_kernel(u32x4* __restrict__ hist, u32x4* __restrict__ xpad, const int* __restrict__ n, long row_words,
+                               long xpad_rows, int pad, const int* __restrict__ ids, int gather) {
+  const long b = blockIdx.y, sb = ids ? ids[b] : b;
   const long words = kKvHist * row_words;
-  const u32x4* src = xpad + (b * xpad_rows + pad + n[b]) * row_words;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (long)gridDim.x * blockDim.x) hist[b * words + i] = src[i];
+  u32x4* rows = xpad + (b * xpad_rows + pad + (gather ? 0 : n[b])) * row_words;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (long)gridDim.x * blockDim.x) {
+    if (gather) rows[i] = hist[sb * words + i];
+    else hist[sb * words + i] = rows[i];
+  }
 }
 // the window moves up by n_s rows and the stream's n_s new feature rows (dense (S, n_max, 1024) fp32) join it right-aligned
 __global__ void kv_feat_kernel(const f32x4* __restrict__ cur, f32x4* __restrict__ nxt, const f32x4* __restrict__ fl, const int* __restrict__ n, int n_max) {
@@ -1690,7 +1707,7 @@ extern "C" int afx_kv_reset(afx_kv* k, const int* slots, int n_slots, void* stre
   HIP_OK(hipMemcpyAsync(dslots, k->hmeta.data() + 3 * k->S, (size_t)n_slots * 4, hipMemcpyHostToDevice, s));
   HIP_OK(hipStreamSynchronize(s));
   const size_t hs = k->e->hsz;
-  hipLaunchKernelGGL(kv_reset_kernel, dim3(64, n_slots), dim3(256), 0, s, dslots, k->tab, (int)(k->hop % kKvGroups), (u32x4*)k->hist,
+  hipLaunchKernelGGL(kv_reset_kernel, dim3(64, n_slots), dim3(256), 0, s, dslots, k->tab, k->active ? -1 : (int)(k->hop % kKvGroups), (u32x4*)k->hist,
                      (long)(kKvHist * kD * hs / 16), (u32x4*)k->feat[0], (u32x4*)k->feat[1], (long)(kKvFeat * kD * 4 / 16));
   HIP_OK(hipGetLastError());
   return 0;
@@ -1708,6 +1725,7 @@ extern "C" int afx_kv_step_ragged(afx_kv* k, const float* feats6, int n, const i
                                   void* stream) {
   if (n < 1 || n > 16) return fail("afx_kv_step_ragged: a chunk brings 1..16 frames (got n_max %d)", n);
   if (!k || !feats6 || !n_frames || !logits || !ws) return fail("afx_kv_step_ragged: null argument");
+  if (k->active) return fail("afx_kv_step_ragged: this state holds per-stream ring positions (afx_kv_step_active): continue with afx_kv_step_active");
   afx_engine* e = k->e;
   const int S = k->S, dt = e->dt, M = S * n, Tp = kKvHist + n, group = (int)(k->hop % kKvGroups);
   for (int b = 0; b < S; ++b)
@@ -1787,8 +1805,8 @@ extern "C" int afx_kv_step_ragged(afx_kv* k, const float* feats6, int n, const i
     g.out_f = w.x; g.ldo_f = kD; g.o_batch_rows = n; g.oh_batch_rows = n;
     KOK(launch_gemm(g, dt, kPosG, s));
   }
-  hipLaunchKernelGGL(kv_hist_kernel, dim3(32, S), dim3(256), 0, s, (u32x4*)k->hist, (const u32x4*)w.xpad, dn, (long)(xrow / 16),
-                     (long)(Tp + kPosK), kPosPad);
+  hipLaunchKernelGGL(kv_hist_kernel, dim3(32, S), dim3(256), 0, s, (u32x4*)k->hist, (u32x4*)w.xpad, dn, (long)(xrow / 16),
+                     (long)(Tp + kPosK), kPosPad, (const int*)nullptr, 0);
   HIP_OK(hipGetLastError());
   for (int l = 0; l < e->cfg.n_layers; ++l) {
     const std::string P = "ssl.encoder.layers." + std::to_string(l) + ".";
@@ -1858,6 +1876,239 @@ extern "C" int afx_kv_step_ragged(afx_kv* k, const float* feats6, int n, const i
     HIP_OK(hipGetLastError());
     if (const char* m = aasist_forward(e->aw, w.head.bucket_f, nb, t, w.head.aa, w.head.bucket_logits, s, e->nonfinite + 1)) return fail("%s", m);
     hipLaunchKernelGGL(kv_scatter_logits_kernel, dim3((2 * nb + 255) / 256), dim3(256), 0, s, w.head.bucket_logits, ids, nb, logits);
+    HIP_OK(hipGetLastError());
+  }
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------
+// Steps over a list of active streams (afx_kv_step_active): only the listed streams advance, the others keep every byte of
+// their state.  The ring group is per stream from the first such step on -- tab[8 s + 1] is stream s's next group, its base
+// group plus its own step count mod 16 -- so a stream's chunks still fill consecutive groups from its base and the rotated
+// visit of the per-stream attention gives the key order of a fresh stream.  The list's QKV product writes entry b's chunk at
+// ring row 256 ids[b] + 16 group + r from the epilogue (launch_gemm_rows), the ring attention walks the list (RING == 3),
+// and the state kernels read and write by id: positional-conv context, the feature window (shifted in place per stream),
+// the back-end's windows.  Everything else runs on the A x n dense rows of the list.
+// ---------------------------------------------------------------------------------
+// every stream's next group = the lock-stepped group (the first active step of a state)
+__global__ void kv_activate_kernel(int* __restrict__ tab, int S, int group) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < S) tab[(long)b * 8 + 1] = group;
+}
+// list entry i (stream ids[i], n[i] new frames): its group's valid count, its attention-table row ([0] base, [1] group, [2] id,
+// [4, 8) counts), its QKV row offset; then the stream's next group moves on
+__global__ void kv_active_tab_kernel(int* __restrict__ tab, const int* __restrict__ ids, const int* __restrict__ n, int A,
+                                     int* __restrict__ atab, int* __restrict__ rows) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= A) return;
+  const long sl = ids[i];
+  int* t = tab + sl * 8;
+  const int g = t[1];
+  ((unsigned char*)(t + 4))[g] = (unsigned char)n[i];
+  for (int j = 0; j < 8; ++j) atab[(long)i * 8 + j] = j == 1 ? g : j == 2 ? (int)sl : t[j];
+  rows[i] = (int)(sl * kKvSlots + g * 16);
+  t[1] = (g + 1) % kKvGroups;
+}
+// stream ids[i]'s window moves up by n[i] rows IN PLACE and entry i's new rows (dense (A, n_max, 1024) fp32) join it at the
+// bottom.  Columns are independent: block x owns 32 16-byte columns of the stream and walks its rows downward-to-upward in
+// passes of 8 -- a pass reads rows [r0 + n, r0 + n + 8) into registers, waits for the whole block, then writes rows [r0, r0 + 8);
+// a later pass only reads rows below every row written so far, so no read meets a rewritten row.
+__global__ void kv_shift_kernel(f32x4* __restrict__ win, const f32x4* __restrict__ fl, const int* __restrict__ ids, const int* __restrict__ n,
+                                int n_max) {
+  constexpr int RW = kD / 4;
+  static_assert(kKvFeat % 8 == 0 && RW % 32 == 0, "pass shape");
+  const long i = blockIdx.y;
+  const int nb = n[i], c = blockIdx.x * 32 + (threadIdx.x & 31), rr = threadIdx.x >> 5;  // 256 threads = 8 rows x 32 columns
+  f32x4* w = win + (long)ids[i] * kKvFeat * RW;
+  for (int r0 = 0; r0 < kKvFeat; r0 += 8) {
+    const int r = r0 + rr;
+    const f32x4 v = r + nb < kKvFeat ? w[(long)(r + nb) * RW + c] : fl[(i * n_max + r + nb - kKvFeat) * RW + c];
+    __syncthreads();
+    w[(long)r * RW + c] = v;
+  }
+}
+
+extern "C" size_t afx_kv_active_workspace_bytes(const afx_kv* k, int n_active, int n_max) {
+  if (!k || n_active <= 0 || n_active > k->S || n_max <= 0 || n_max > 16) return 0;
+  KvWs w;
+  return kv_carve(k->e, n_active, n_max, kKvWindow, nullptr, &w, true);
+}
+
+// slots: host, A distinct stream indices (the list, in the caller's order); feats6: device (A, n_max, 512) fp32, entry i's
+// n_frames[i] (host, 1 <= n_frames[i] <= n_max <= 16) new frames first; logits: device (A, 2) in list order.
+extern "C" int afx_kv_step_active(afx_kv* k, const int* slots, int A, const float* feats6, int n, const int* n_frames, float* logits,
+                                  void* ws, size_t ws_bytes, void* stream) {
+  if (!k) return fail("afx_kv_step_active: null state");
+  if (A < 0 || A > k->S) return fail("afx_kv_step_active: %d active streams (0..%d)", A, k->S);
+  if (A == 0) return 0;  // nothing advances, nothing is launched
+  if (n < 1 || n > 16) return fail("afx_kv_step_active: a chunk brings 1..16 frames (got n_max %d)", n);
+  if (!slots || !feats6 || !n_frames || !logits || !ws) return fail("afx_kv_step_active: null argument");
+  afx_engine* e = k->e;
+  const int S = k->S, dt = e->dt, M = A * n, Tp = kKvHist + n;
+  {
+    std::vector<char> seen(S, 0);
+    for (int i = 0; i < A; ++i) {
+      if (slots[i] < 0 || slots[i] >= S) return fail("afx_kv_step_active: slot %d outside 0..%d", slots[i], S - 1);
+      if (seen[slots[i]]++) return fail("afx_kv_step_active: slot %d named twice", slots[i]);
+      if (n_frames[i] < 1 || n_frames[i] > n) return fail("afx_kv_step_active: slot %d brings %d frames (1..%d)", slots[i], n_frames[i], n);
+    }
+  }
+  int Thmax = 0;
+  std::vector<int> th(A);
+  for (int i = 0; i < A; ++i) {
+    th[i] = std::min((k->per_stream ? k->nfeat_s[slots[i]] : k->nfeat) + n_frames[i], kKvWindow);
+    if (e->cfg.arch == AFX_ARCH_XLSR_AASIST && th[i] < 6) return fail("afx_kv_step_active: the AASIST head needs at least 6 frames in slot %d's window", slots[i]);
+    Thmax = std::max(Thmax, th[i]);
+  }
+  KvWs w;
+  const size_t needb = kv_carve(e, A, n, Thmax, ws, &w, true);
+  if (ws_bytes < needb) return fail("afx_kv_step_active: workspace too small (%zu < %zu bytes)", ws_bytes, needb);
+  hipStream_t s = (hipStream_t)stream;
+  if (kv_to_per_stream(k, s)) return 1;
+  if (!k->active) {  // every stream's next group = the group a lock-stepped or ragged step would write now
+    hipLaunchKernelGGL(kv_activate_kernel, dim3((S + 255) / 256), dim3(256), 0, s, k->tab, S, (int)(k->hop % kKvGroups));
+    HIP_OK(hipGetLastError());
+    k->active = true;
+  }
+  // meta: n | 64 + n | window lengths | ids | back-end order (list entries) | their ids | QKV rows | (8 A) attention table
+  std::vector<int> hm((size_t)6 * A, 0);
+  for (int i = 0; i < A; ++i) {
+    hm[i] = n_frames[i];
+    hm[A + i] = kKvHist + n_frames[i];
+    hm[2 * A + i] = th[i];
+    hm[3 * A + i] = slots[i];
+  }
+  std::vector<std::pair<int, int>> buckets;  // AASIST: (window length, first position in the back-end order)
+  if (e->cfg.arch == AFX_ARCH_XLSR_AASIST) {
+    std::vector<int> order(A);
+    for (int i = 0; i < A; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int c) { return th[a] < th[c]; });
+    for (int i = 0; i < A; ++i) {
+      hm[4 * A + i] = order[i];
+      hm[5 * A + i] = slots[order[i]];
+      if (i == 0 || th[order[i]] != th[order[i - 1]]) buckets.push_back({th[order[i]], i});
+    }
+  }
+  int* dn = k->meta;
+  const int *dids = dn + 3 * A, *drows = dn + 6 * A, *datab = dn + 8 * A;
+  HIP_OK(hipMemcpyAsync(dn, hm.data(), (size_t)6 * A * 4, hipMemcpyHostToDevice, s));
+  HIP_OK(hipStreamSynchronize(s));  // (pageable host memory)
+  hipLaunchKernelGGL(kv_active_tab_kernel, dim3((A + 255) / 256), dim3(256), 0, s, k->tab, dids, dn, A, dn + 8 * A, dn + 6 * A);
+  HIP_OK(hipGetLastError());
+  begin_call(e, nullptr);
+  if (e->s3) {
+    t_s3planes = w.s3planes;
+    t_s3bytes = w.s3bytes;
+    s3_begin({w.feats_h, w.hbuf, w.att, w.ff, w.xpad, (char*)w.xpad + (size_t)kKvHist * kD * e->hsz});
+  }
+  const size_t hs = e->hsz;
+  {
+    RowNormArgs a = plain_norm(feats6, kC, M, kC, e->F("ssl.layer_norm.weight"), e->F("ssl.layer_norm.bias"));
+    a.out_h = w.feats_h; a.ldo_h = kC;
+    KOK(launch_rownorm(a, dt, s));
+  }
+  const size_t xrow = (size_t)kD * hs;
+  hipLaunchKernelGGL(kv_hist_kernel, dim3(32, A), dim3(256), 0, s, (u32x4*)k->hist, (u32x4*)w.xpad, dn, (long)(xrow / 16),
+                     (long)(Tp + kPosK), kPosPad, dids, 1);
+  HIP_OK(hipGetLastError());
+  {
+    GemmArgs g = plain_gemm(w.feats_h, kC, e->projw, kC, M, kD, kC);
+    g.rpb = n; g.a_batch = (long)n * kC; g.a_row = kC;
+    g.bias = e->F("ssl.post_extract_proj.bias");
+    g.out_f = w.x; g.ldo_f = kD; g.o_batch_rows = n;
+    g.out_h = w.xpad; g.ldo_h = kD; g.oh_batch_rows = Tp + kPosK; g.oh_row_off = kPosPad + kKvHist;
+    KOK(launch_gemm(g, dt, 1, s));
+    KOK(timed(PC_MISC, 0, s, [&] { return launch_zero_pad_rows(w.xpad, A, Tp, kD, kPosPad, kPosK - kPosPad, dt, s, dn + A); }));
+  }
+  void* xchunk = (char*)w.xpad + (size_t)kKvHist * xrow;
+  if (!e->s3) {
+    PosConvArgs pc;
+    memset(&pc, 0, sizeof pc);
+    pc.xpad = xchunk; pc.xpad_batch = (long)(Tp + kPosK) * kD; pc.W = e->posw; pc.bias = e->F("ssl.encoder.pos_conv.0.bias");
+    pc.x = w.x; pc.B = A; pc.T = n;
+    KOK(timed(PC_POSCONV, 2.0 * A * n * kD * (kD / kPosG) * kPosK, s, [&] { return launch_posconv(pc, dt, s); }));
+  } else {
+    const int cpg = kD / kPosG;
+    s3_set(xchunk, kS3ScaleFree);
+    GemmArgs g = plain_gemm(xchunk, 0, e->posw, (long)cpg * kPosK, A * n, cpg, cpg * kPosK);
+    g.rpb = n; g.a_batch = (long)(Tp + kPosK) * kD; g.a_row = kD;
+    g.kchunk = cpg; g.kchunk_stride = kD;
+    g.g_a = cpg; g.g_w = (long)cpg * cpg * kPosK; g.g_n = cpg;
+    g.bias = e->F("ssl.encoder.pos_conv.0.bias");
+    g.act = ACT_GELU;
+    g.resid = w.x; g.ldr = kD;
+    g.out_f = w.x; g.ldo_f = kD; g.o_batch_rows = n; g.oh_batch_rows = n;
+    KOK(launch_gemm(g, dt, kPosG, s));
+  }
+  hipLaunchKernelGGL(kv_hist_kernel, dim3(32, A), dim3(256), 0, s, (u32x4*)k->hist, (u32x4*)w.xpad, dn, (long)(xrow / 16),
+                     (long)(Tp + kPosK), kPosPad, dids, 0);
+  HIP_OK(hipGetLastError());
+  for (int l = 0; l < e->cfg.n_layers; ++l) {
+    const std::string P = "ssl.encoder.layers." + std::to_string(l) + ".";
+    void* ring = (char*)k->rings + (size_t)l * S * kKvSlots * 3 * kD * hs;
+    RowNormArgs n1 = plain_norm(w.x, kD, M, kD, e->F(P + "self_attn_layer_norm.weight"), e->F(P + "self_attn_layer_norm.bias"));
+    n1.out_h = w.hbuf; n1.ldo_h = kD;
+    KOK(launch_rownorm(n1, dt, s));
+    // entry b's q | k | v rows go to ring row 256 ids[b] + 16 group + r (the row table of the epilogue)
+    GemmArgs q = plain_gemm(w.hbuf, kD, e->wqkv[l], kD, M, 3 * kD, kD);
+    q.rpb = n; q.a_batch = (long)n * kD; q.a_row = kD;
+    q.bias = e->bqkv[l];
+    q.out_h = ring; q.ldo_h = 3 * kD; q.oh_rows = drows;
+    KOK(launch_gemm(q, dt, 1, s, true));
+    KOK(timed(PC_MHSA, 4.0 * A * kH * 16.0 * kKvSlots * 64, s, [&] {
+      if (e->s3) {
+        const bool pairs = s3_ok(w.att);
+        s3_set(w.att, pairs ? kS3ScaleFree : 0.f);
+        return launch_mhsa_ring_split_active((const float*)ring, (float*)w.att, A, kH, datab, s, pairs, kS3ScaleFree);
+      }
+      return launch_mhsa_ring_active(ring, w.att, A, kH, datab, dt, s);
+    }));
+    GemmArgs o = plain_gemm(w.att, kD, e->wo[l], kD, M, kD, kD);
+    o.rpb = n; o.a_batch = 16L * kD; o.a_row = kD; o.o_batch_rows = n;
+    o.bias = e->F(P + "self_attn.out_proj.bias"); o.resid = w.x; o.ldr = kD; o.out_f = w.x; o.ldo_f = kD;
+    KOK(launch_gemm(o, dt, 1, s));
+    RowNormArgs n2 = plain_norm(w.x, kD, M, kD, e->F(P + "final_layer_norm.weight"), e->F(P + "final_layer_norm.bias"));
+    n2.out_h = w.hbuf; n2.ldo_h = kD;
+    KOK(launch_rownorm(n2, dt, s));
+    GemmArgs f1 = plain_gemm(w.hbuf, kD, e->w1[l], kD, M, kF, kD);
+    f1.bias = e->F(P + "fc1.bias"); f1.act = ACT_GELU; f1.out_h = w.ff; f1.ldo_h = kF;
+    KOK(launch_gemm(f1, dt, 1, s));
+    GemmArgs f2 = plain_gemm(w.ff, kF, e->w2[l], kF, M, kD, kF);
+    f2.bias = e->F(P + "fc2.bias"); f2.resid = w.x; f2.ldr = kD; f2.out_f = w.x; f2.ldo_f = kD;
+    KOK(launch_gemm(f2, dt, 1, s));
+  }
+  float* win = k->feat[k->pp];  // (active steps: every window stays in this buffer)
+  {
+    RowNormArgs nf = plain_norm(w.x, kD, M, kD, e->F("ssl.encoder.layer_norm.weight"), e->F("ssl.encoder.layer_norm.bias"));
+    nf.out_f = w.fl; nf.ldo_f = kD;
+    nf.nonfinite = e->nonfinite;
+    KOK(launch_rownorm(nf, dt, s));
+  }
+  hipLaunchKernelGGL(kv_shift_kernel, dim3(kD / 4 / 32, A), dim3(256), 0, s, (f32x4*)win, (const f32x4*)w.fl, dids, dn, n);
+  HIP_OK(hipGetLastError());
+  for (int i = 0; i < A; ++i) k->nfeat_s[slots[i]] = std::min(k->nfeat_s[slots[i]] + n_frames[i], kKvFeat);
+  const int* dth = dn + 2 * A;
+  if (e->cfg.arch == AFX_ARCH_CONFORMER) {
+    hipLaunchKernelGGL(kv_gather_kernel, dim3(32, A), dim3(256), 0, s, (const f32x4*)win, dids, dth, 0, Thmax, (f32x4*)w.head.ssl_f);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(w.head.lens, dth, (size_t)A * 4, hipMemcpyDeviceToDevice, s));
+    if (e->s3) {
+      HIP_OK(hipMemcpyAsync(w.head.ssl_h, w.head.ssl_f, (size_t)A * Thmax * kD * 4, hipMemcpyDeviceToDevice, s));
+    } else {
+      hipLaunchKernelGGL(f32_to_half_kernel, dim3(1024), dim3(256), 0, s, w.head.ssl_f, (uint16_t*)w.head.ssl_h, (size_t)A * Thmax * kD, dt == AFX_DT_BF16 ? 1 : 0);
+      HIP_OK(hipGetLastError());
+    }
+    begin_call(e, &w.head);
+    return run_head(e, A, Thmax, w.head, logits, s);
+  }
+  begin_call(e, &w.head);
+  for (size_t bi = 0; bi < buckets.size(); ++bi) {
+    const int t = buckets[bi].first, i0 = buckets[bi].second;
+    const int nb = (bi + 1 < buckets.size() ? buckets[bi + 1].second : A) - i0;
+    hipLaunchKernelGGL(kv_gather_kernel, dim3(32, nb), dim3(256), 0, s, (const f32x4*)win, dn + 5 * A + i0, (const int*)nullptr, t, t, (f32x4*)w.head.bucket_f);
+    HIP_OK(hipGetLastError());
+    if (const char* m = aasist_forward(e->aw, w.head.bucket_f, nb, t, w.head.aa, w.head.bucket_logits, s, e->nonfinite + 1)) return fail("%s", m);
+    hipLaunchKernelGGL(kv_scatter_logits_kernel, dim3((2 * nb + 255) / 256), dim3(256), 0, s, w.head.bucket_logits, dn + 4 * A + i0, nb, logits);
     HIP_OK(hipGetLastError());
   }
   return 0;

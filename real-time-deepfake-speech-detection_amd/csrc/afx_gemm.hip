@@ -63,7 +63,9 @@ __device__ __forceinline__ void store_pairs8(void* out_h, long hrow, long ldo_h,
 // fallback: ~300 KB of code around a 12-KB K-loop, refetched through the instruction cache after every tile.
 // S3 (split precision, GemmArgs::k1): the accumulator of column n is multiplied by pre_scale[n] before the bias, and the
 // "operand type" output out_h is written as fp32 (the engine's operand buffers are fp32 in that mode).
-template <class HT, int BM, int BN, int WR, int WC, bool ROWLN, bool LEAN = false, bool S3 = false>
+// ROWTAB (launch_gemm_rows): operand-type row of A-row m = oh_rows[m / rpb] + m % rpb -- one output row offset per batch
+// from a device table (the KV-cached step over a list of streams writes each stream's chunk at that stream's own ring group).
+template <class HT, int BM, int BN, int WR, int WC, bool ROWLN, bool LEAN = false, bool S3 = false, bool ROWTAB = false>
 __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f32x4 (&acc)[BM / WR / 16][BN / WC / 16], char* smem,
                                               int m0, int n0, int g) {
   typedef typename HT::T T;
@@ -259,7 +261,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f32x4 (&acc)[BM
       const int mc = mok ? m : p.M - 1;
       const int bq = one_batch ? 0 : mc / p.rpb, br = one_batch ? mc : mc - bq * p.rpb;
       orow = (long)bq * p.o_batch_rows + br + p.o_row_off;
-      hrow = (long)bq * p.oh_batch_rows + br + p.oh_row_off;
+      if constexpr (ROWTAB) hrow = (long)p.oh_rows[bq] + br;
+      else hrow = (long)bq * p.oh_batch_rows + br + p.oh_row_off;
     };
     auto load_resid = [&](int step, f32x4 (&r)[2]) {
       const int i = step / (NT / 2), jp = step % (NT / 2);
@@ -452,8 +455,9 @@ __device__ __forceinline__ void wait_vmcnt() {
 // LayerNorm over the row (two-pass fp32 statistics, partial sums exchanged through LDS
 // between the WC waves of a row) followed by the activation -- the conv feature
 // extractor's "conv -> LayerNorm(512) -> GELU" in one kernel, no fp32 round trip.
-template <class HT, int BM, int BN, int WR, int WC, bool ROWLN = false, bool LEAN = false, bool S3 = false>
+template <class HT, int BM, int BN, int WR, int WC, bool ROWLN = false, bool LEAN = false, bool S3 = false, bool ROWTAB = false>
 __global__ __launch_bounds__(64 * WR * WC) void gemm_kernel(GemmArgs p) {
+  static_assert(!ROWTAB || (LEAN && !ROWLN), "per-batch output rows: wide-store epilogue only");
   typedef typename HT::T T;
   typedef typename HT::V8 V8;
   typedef typename HT::V4 V4;
@@ -619,7 +623,7 @@ __global__ __launch_bounds__(64 * WR * WC) void gemm_kernel(GemmArgs p) {
     }
   }
 
-  gemm_epilogue<HT, BM, BN, WR, WC, ROWLN, LEAN, S3>(p, acc, smem, m0, n0, g);
+  gemm_epilogue<HT, BM, BN, WR, WC, ROWLN, LEAN, S3, ROWTAB>(p, acc, smem, m0, n0, g);
 }
 
 
@@ -659,8 +663,9 @@ __global__ __launch_bounds__(64 * WR * WC) void gemm_kernel(GemmArgs p) {
 // TS (attribution build only): every wave stamps the shader clock at five points of each phase of the FIRST output tile
 // (start of the read part / DMA landed + reads retired / first barrier passed / MFMAs issued / second barrier passed) into
 // 16 KB of LDS behind the operand buffers; workgroup 0 dumps them over the head of out_h at the end (tools/kloop_timeline.py).
-template <class HT, int BM, int BN, bool ROWLN, int MF = BM / 32, int PH = 1, bool TS = false, bool S3 = false>
+template <class HT, int BM, int BN, bool ROWLN, int MF = BM / 32, int PH = 1, bool TS = false, bool S3 = false, bool ROWTAB = false>
 __global__ __launch_bounds__(512) void gemm8_kernel(GemmArgs p) {
+  static_assert(!ROWTAB || !ROWLN, "per-batch output rows: wide-store epilogue only");
   typedef typename HT::T T;
   typedef typename HT::V8 V8;
   // Two instances: 256x256 (A flows, both B halves stay in registers) and the row-complete
@@ -1118,7 +1123,7 @@ __global__ __launch_bounds__(512) void gemm8_kernel(GemmArgs p) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) asm volatile("" :: "v"(acc[i][j][r]));
     } else {
-      gemm_epilogue<HT, BMC, BN, 2, 4, ROWLN, true, S3>(p, acc, smem + BUF + (WIDE ? OFF_B1 : OFF_A1), m0c, n0c, g);
+      gemm_epilogue<HT, BMC, BN, 2, 4, ROWLN, true, S3, ROWTAB>(p, acc, smem + BUF + (WIDE ? OFF_B1 : OFF_A1), m0c, n0c, g);
     }
     ts_on = false;
     if (vn >= nwg) break;
@@ -1132,12 +1137,12 @@ __global__ __launch_bounds__(512) void gemm8_kernel(GemmArgs p) {
 #undef AFX_BAR
 }
 
-template <class HT, int BM, int BN, bool ROWLN, int MF = BM / 32, int PH = 1, bool TS = false, bool S3 = false>
+template <class HT, int BM, int BN, bool ROWLN, int MF = BM / 32, int PH = 1, bool TS = false, bool S3 = false, bool ROWTAB = false>
 static hipError_t launch_gemm8_t(const GemmArgs& p, int groups, hipStream_t s) {
   constexpr int lds = 2 * (BM + BN) * 128 + (TS ? 16384 : 0) + (PH == 3 ? BM * 128 : 0);  // ring3: a third buffer for A
   static_assert(lds <= 160 * 1024, "two K-tile buffers must fit the 160 KB LDS");
   static LdsLimit lim;
-  if (hipError_t e = lim.ensure((const void*)gemm8_kernel<HT, BM, BN, ROWLN, MF, PH, TS, S3>, lds); e != hipSuccess) return e;
+  if (hipError_t e = lim.ensure((const void*)gemm8_kernel<HT, BM, BN, ROWLN, MF, PH, TS, S3, ROWTAB>, lds); e != hipSuccess) return e;
   static int n_cu_of[kMaxDevices] = {0};  // (benign if two threads fill the same slot: same value)
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return hipErrorInvalidDevice;
@@ -1150,7 +1155,7 @@ static hipError_t launch_gemm8_t(const GemmArgs& p, int groups, hipStream_t s) {
   const int n_cu = n_cu_of[dev];
   const int tiles = ((p.N + BN - 1) / BN) * ((p.M - p.m_lo + MF * 32 - 1) / (MF * 32));
   dim3 grid(tiles < n_cu ? tiles : n_cu, 1, groups);  // persistent: at most one workgroup per CU
-  hipLaunchKernelGGL((gemm8_kernel<HT, BM, BN, ROWLN, MF, PH, TS, S3>), grid, dim3(512), lds, s, p);
+  hipLaunchKernelGGL((gemm8_kernel<HT, BM, BN, ROWLN, MF, PH, TS, S3, ROWTAB>), grid, dim3(512), lds, s, p);
   return hipGetLastError();
 }
 
@@ -1573,13 +1578,13 @@ static hipError_t launch_gemm5_t(const GemmArgs& p, int groups, hipStream_t s) {
 }
 #endif  // AFX_ATTR
 
-template <class HT, int BM, int BN, int WR, int WC, bool ROWLN = false, bool LEAN = false, bool S3 = false>
+template <class HT, int BM, int BN, int WR, int WC, bool ROWLN = false, bool LEAN = false, bool S3 = false, bool ROWTAB = false>
 static hipError_t launch_gemm_t(const GemmArgs& p, int groups, hipStream_t s) {
   constexpr int lds = 2 * (BM + BN) * 128;
   static LdsLimit lim;
-  if (hipError_t e = lim.ensure((const void*)gemm_kernel<HT, BM, BN, WR, WC, ROWLN, LEAN, S3>, lds); e != hipSuccess) return e;
+  if (hipError_t e = lim.ensure((const void*)gemm_kernel<HT, BM, BN, WR, WC, ROWLN, LEAN, S3, ROWTAB>, lds); e != hipSuccess) return e;
   dim3 grid(((p.N + BN - 1) / BN) * ((p.M + BM - 1) / BM), 1, groups);
-  hipLaunchKernelGGL((gemm_kernel<HT, BM, BN, WR, WC, ROWLN, LEAN, S3>), grid, dim3(64 * WR * WC), lds, s, p);
+  hipLaunchKernelGGL((gemm_kernel<HT, BM, BN, WR, WC, ROWLN, LEAN, S3, ROWTAB>), grid, dim3(64 * WR * WC), lds, s, p);
   return hipGetLastError();
 }
 
@@ -2003,6 +2008,35 @@ const char* launch_gemm(const GemmArgs& p_in, int dtype, int groups, hipStream_t
     }
   }
   const hipError_t err = AFX_DISPATCH_GEMM(p, tile);
+  return err == hipSuccess ? nullptr : hipGetErrorString(err);
+}
+
+// Per-batch output rows (GemmArgs::oh_rows, the ROWTAB instantiations): the same tiles as launch_gemm picks for this shape --
+// the 256-wide 8-phase kernel where launch_gemm takes it, the 128x128 2-stage tile otherwise -- with the operand-type row of
+// batch b read from the device table.  Same k order and epilogue arithmetic as every other tile: the rows' bits are those of
+// launch_gemm.  Only what the KV-cached step sends: plain K, one group, no LayerNorm / fp32 output / residual, lean epilogue.
+const char* launch_gemm_rows(const GemmArgs& p_in, int dtype, hipStream_t s) {
+  if (dtype == DT_FP32) return "gemm_rows: half- or split-precision operands only";
+  if ((dtype == DT_FP16X3) != (p_in.k1 != 0)) return "gemm: the split-precision fields (k1, planes, column scales) go with DT_FP16X3 and only with it";
+  if (const char* e = check_gemm(p_in, 1)) return e;
+  if (!p_in.oh_rows || !p_in.out_h || p_in.out_f || p_in.resid || p_in.ln_gamma || !plain_k(p_in) || (p_in.N & 7) ||
+      (p_in.act != ACT_NONE && p_in.act != ACT_GELU) || p_in.m_lo)
+    return "gemm_rows: operand-type output with a row table, plain K, N % 8 == 0, no LayerNorm / fp32 output / residual";
+  GemmArgs p = p_in;
+  p.map_mode = g_map_override >= 0 ? g_map_override : 2;
+  p.a_nt = g_ant_override >= 0 ? g_ant_override : 0;
+  p.dbg_nodma = g_nodma;
+  const bool wide = gemm_tile_of(p, 1) == 7;
+  hipError_t err;
+  if (p.k1)
+    err = wide ? launch_gemm8_t<FP16, 256, 256, false, 8, 3, false, true, true>(p, 1, s)
+               : launch_gemm_t<FP16, 128, 128, 2, 2, false, true, true, true>(p, 1, s);
+  else if (dtype == DT_BF16)
+    err = wide ? launch_gemm8_t<BF16, 256, 256, false, 8, 3, false, false, true>(p, 1, s)
+               : launch_gemm_t<BF16, 128, 128, 2, 2, false, true, false, true>(p, 1, s);
+  else
+    err = wide ? launch_gemm8_t<FP16, 256, 256, false, 8, 3, false, false, true>(p, 1, s)
+               : launch_gemm_t<FP16, 128, 128, 2, 2, false, true, false, true>(p, 1, s);
   return err == hipSuccess ? nullptr : hipGetErrorString(err);
 }
 

@@ -56,7 +56,14 @@ struct GemmArgs {
   // (out_f and resid use o_*, out_h uses oh_* -- e.g. the fp32 residual stream is
   // unpadded while the operand copy feeds the time-padded positional-conv buffer)
   int o_batch_rows, o_row_off;
-  int oh_batch_rows, oh_row_off;
+  union {
+    struct {
+      int oh_batch_rows, oh_row_off;
+    };
+    // launch_gemm_rows only, in place of the two above: out_h row of A-row m = oh_rows[m / rpb] + m % rpb (a device table
+    // of one row offset per batch; the size and layout of the struct, hence every other kernel's code, stay as they were)
+    const int* oh_rows;
+  };
   int map_mode;  // workgroup->tile order, set by launch_gemm (0 linear, 1 XCD-contiguous, 2 + grouped)
   // fused row LayerNorm epilogue (needs N == 512, one row-complete tile per M-tile):
   // out = act(LayerNorm(acc + bias) * ln_gamma + ln_beta); null ln_gamma = off
@@ -84,6 +91,7 @@ struct GemmArgs {
   int dbg_nodma;  // attribution build (-DAFX_ATTR) only, ignored otherwise: epilogue bits 8 no activation, 16 narrow stores, 32 no stores, 64 no epilogue
 };
 const char* launch_gemm(const GemmArgs& p, int dtype, int groups, hipStream_t s);
+const char* launch_gemm_rows(const GemmArgs& p, int dtype, hipStream_t s);  // out_h rows from GemmArgs::oh_rows (afx_gemm.hip)
 const char* launch_gemm_f32(const GemmArgs& p, int groups, hipStream_t s);  // afx_gemm_f32.hip (DT_FP32 operands)
 bool gemm_is_narrow(int N);  // true: the 128x64 tile instance serves this N
 int gemm_tile_of(const GemmArgs& p, int groups);  // tile instance id (afx_gemm.hip)
@@ -197,6 +205,11 @@ const char* launch_mhsa_ring_split(const float* ring, float* out, int S, int H, 
 const char* launch_mhsa_ring_tab(const void* ring, void* out, int S, int H, int q_tile, const int* tab, int dtype, hipStream_t s);
 const char* launch_mhsa_ring_split_tab(const float* ring, float* out, int S, int H, int q_tile, const int* tab, hipStream_t s,
                                        bool out_pairs, float out_scale);
+// a step over a list of active streams (afx_kv_step_active): tab = (A, 8) ints per list entry -- [0] base group, [1] the
+// stream's newest group (its query tile), [2] its ring index, bytes [16, 32) its valid counts; output row b = entry b's
+const char* launch_mhsa_ring_active(const void* ring, void* out, int A, int H, const int* tab, int dtype, hipStream_t s);
+const char* launch_mhsa_ring_split_active(const float* ring, float* out, int A, int H, const int* tab, hipStream_t s, bool out_pairs,
+                                          float out_scale);
 
 // ---- Conformer student head (afx_conformer.hip) ----------------------------------
 // y = selu(bn(x)) for rows 1..T of each utterance, row 0 = class token; x is the LL

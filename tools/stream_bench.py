@@ -13,6 +13,10 @@ before every hop, warm-up included, each slot restarts (``scorer.reset``) with p
 that slots warming up and slots in the steady state share the ticks as they do on a server scoring live calls (the warm-up
 runs session-hops more ticks, so the timed hops see the stationary mix: ~1 - (1 - 1/120)^16 = 12.5 % of the slots still
 younger than the window at the default).
+--active-frac F [F ...] measures non-paced streams (``push(chunk, slots)``): after the warm-up (every slot pushed until its
+window is full), before each timed hop each slot has audio with probability F, seeded, and only those slots are pushed.
+Reported per F: ms per hop, the RTF of the active streams (hop time / hop duration) and scores/s (active slots per second).
+    python tools/stream_bench.py --active-frac 0.25 0.5 1.0 --streams 2048 ...
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/stream_bench.py --gpus N ...
 
 With --gpus N every rank pins its own S streams to its GPU (state lives there; nothing is exchanged on the data path);
@@ -40,6 +44,8 @@ def main():
     ap.add_argument("--modes", nargs="*", default=["sliding", "incremental", "kv-cached"])
     ap.add_argument("--staggered", action="store_true", help="also time per-slot sessions restarting at random ticks")
     ap.add_argument("--session-hops", type=int, default=120, help="--staggered: mean session length in hops (120 = 30 s)")
+    ap.add_argument("--active-frac", type=float, nargs="*", default=[],
+                    help="also time non-paced streams: each slot has audio on a tick with this probability (seeded)")
     args = ap.parse_args()
     rank, local, world = (int(os.environ.get(k, d)) for k, d in (("RANK", 0), ("LOCAL_RANK", 0), ("WORLD_SIZE", 1)))
     if world != args.gpus:
@@ -58,8 +64,8 @@ def main():
     for S in args.streams:
         line = f"{args.workload}, {world} GPU(s) x {S} streams:"
         for name in args.modes:
-            for staggered in ((False, True) if args.staggered else (False,)):
-                label = name + (" staggered" if staggered else "")
+            for staggered, frac in [(False, None)] + ([(True, None)] if args.staggered else []) + [(False, f) for f in args.active_frac]:
+                label = name + (" staggered" if staggered else "") + (f" active {frac:.2f}" if frac is not None else "")
                 try:
                     sc = {"sliding": lambda: SlidingWindowScorer(eng, S, window=W, hop=H), "incremental": lambda: IncrementalScorer(eng, sd, S, window=W, hop=H),
                           "kv-cached": lambda: KVCachedScorer(eng, sd, S, window=W, hop=H)}[name]()
@@ -71,12 +77,21 @@ def main():
                 chunk = (0.1 * torch.randn(S, H, generator=torch.Generator().manual_seed(rank))).cuda()
                 gen = torch.Generator().manual_seed(1000 + rank)
 
-                def tick():
+                n_active = []
+
+                def tick(warm=False):
                     if staggered:
                         sc.reset(torch.rand(S, generator=gen) < 1.0 / args.session_hops)
-                    sc.push(chunk)
+                    if frac is None:
+                        sc.push(chunk)
+                    elif warm:
+                        sc.push(chunk, slots=range(S))
+                    else:
+                        on = (torch.rand(S, generator=gen) < frac).nonzero().flatten()
+                        n_active.append(on.numel())
+                        sc.push(chunk[on.cuda()], slots=on)
                 for _ in range(W // H + 2 + (args.session_hops if staggered else 0)):  # fill the window, reach the steady state
-                    tick()
+                    tick(warm=True)
                 torch.cuda.synchronize()
                 if dist:
                     dist.barrier()
@@ -89,7 +104,10 @@ def main():
                     t = torch.tensor([dt], dtype=torch.float64, device="cuda")
                     dist.all_reduce(t, op=dist.ReduceOp.MAX)
                     dt = t.item()
-                line += f"  {label} {dt * 1e3:8.2f} ms/hop RTF {dt / 0.25:6.3f} ({world * S / dt:8.0f} scores/s)"
+                per_hop = world * (sum(n_active) / len(n_active) if n_active else S)  # scores per hop
+                line += f"  {label} {dt * 1e3:8.2f} ms/hop RTF {dt / 0.25:6.3f} ({per_hop / dt:8.0f} scores/s)"
+                if n_active:
+                    line += f" [{per_hop:.0f} active]"
                 del sc
         if rank == 0:
             print(line, flush=True)
