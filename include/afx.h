@@ -157,6 +157,23 @@ int afx_kv_step_ragged(afx_kv* kv, const float* feats6, int n_max, const int* n_
 size_t afx_kv_active_workspace_bytes(const afx_kv* kv, int n_active, int n_max);
 int afx_kv_step_active(afx_kv* kv, const int* slots, int n_active, const float* feats6, int n_max, const int* n_frames,
                        float* logits, void* ws, size_t ws_bytes, void* stream);
+/* Moving sessions: a stream's state leaves one afx_kv and takes over a slot of another (another size, another GPU, the
+ * same afx_kv, after host memory).  afx_kv_export copies the listed streams (host slots, distinct, 0 <= slot < n_streams)
+ * into payload (device, 16-byte aligned, n x afx_kv_slot_bytes bytes: the k and v thirds of the stream's ring rows in
+ * every layer, 16 groups x 16 rows in the stream's own order from its first group on; the positional conv's 64-frame
+ * context; the 208-row feature window) and writes one host meta row of AFX_KV_META ints per stream: [0] the layout word
+ * (layers, dtype, element size, ring / context / window rows, format), [1] the stream's next group relative to its first,
+ * [2] its window length, [3] 0, ints [4, 8) its 16 valid counts as bytes in the payload's group order.  The state is read
+ * only: no byte of it changes and a lock-stepped state stays lock-stepped.  One stream synchronisation per call.
+ * afx_kv_import makes the listed slots of kv take over those streams (their own are dropped; the other slots keep every
+ * byte): it refuses a meta row whose layout word differs from kv's, or that is out of range, before anything changes.
+ * The imported stream's next chunk lands where kv writes next and its keys are visited in the order they had, so each
+ * stream's logits continue, bit for bit, as in the afx_kv it left.  The first import makes kv per stream (afx_kv_step then
+ * refuses it, as after afx_kv_reset).  n == 0 launches nothing. */
+#define AFX_KV_META 8
+size_t afx_kv_slot_bytes(const afx_kv* kv);
+int afx_kv_export(afx_kv* kv, const int* slots, int n, void* payload, int* meta, void* stream);
+int afx_kv_import(afx_kv* kv, const int* slots, int n, const void* payload, const int* meta, void* stream);
 /* back-end alone from given SSL features (B,T,1024) fp32 -> logits (B,2) */
 int afx_head_forward(afx_handle h, const float* feats, int B, int T, float* logits, void* ws, size_t ws_bytes,
                      void* stream);

@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("AFX_LIB") or os.path.join(os.path.dirname(_HERE), "li
 ARCH_SSL, ARCH_XLSR_AASIST, ARCH_CONFORMER, ARCH_CONFORMER_HEAD = 0, 1, 2, 3
 DT_BF16, DT_FP16, DT_FP32, DT_FP16X3 = 0, 1, 2, 3
 ACT_NONE, ACT_GELU, ACT_SWISH, ACT_SELU = 0, 1, 2, 3
+KV_META = 8  # AFX_KV_META: ints per stream of an afx_kv_export meta row
 
 
 class AfxError(RuntimeError):
@@ -64,6 +65,9 @@ SIGNATURES = {
     "afx_kv_step_ragged": (_I, [_P, _P, _I, _P, _P, _P, _Z, _P]),
     "afx_kv_active_workspace_bytes": (_Z, [_P, _I, _I]),
     "afx_kv_step_active": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _Z, _P]),
+    "afx_kv_slot_bytes": (_Z, [_P]),
+    "afx_kv_export": (_I, [_P, _P, _I, _P, _P, _P]),
+    "afx_kv_import": (_I, [_P, _P, _I, _P, _P, _P]),
     "afx_check_finite": (_I, [_P, _P]),
     "afx_enable_taps": (_I, [_P, _I]),
     "afx_tap": (_I, [_P, C.c_char_p, _P, _Z, C.POINTER(_Z), _P]),

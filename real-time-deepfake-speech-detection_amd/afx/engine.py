@@ -79,6 +79,7 @@ class Engine:
         if not torch.cuda.is_available():
             raise AfxError("no HIP device: the MI355X-native path has no CPU fallback")
         self.arch, self.dtype, self.n_layers = arch, dtype, n_layers
+        self.conf = dict(emb=conf_emb, heads=conf_heads, kernel=conf_kernel, blocks=conf_blocks)  # (the Conformer head's shape)
         self.pre_emphasis = bool(pre_emphasis)
         if extractor_mode not in EXTRACTORS:
             raise ValueError(f"extractor_mode must be one of {sorted(EXTRACTORS)}, got {extractor_mode!r}")
@@ -572,4 +573,36 @@ class KVState:
         idx = [int(v) for v in slots]
         with torch.cuda.device(self.engine.device):
             check(lib().afx_kv_reset(self._k, (C.c_int * max(len(idx), 1))(*idx), len(idx), self.engine._stream()))
+
+    @property
+    def slot_bytes(self):
+        """Device payload of one exported stream (afx_kv_slot_bytes): the k / v thirds of its ring rows, its positional-conv
+        context and its feature window."""
+        return int(lib().afx_kv_slot_bytes(self._k))
+
+    def export(self, slots):
+        """-> (payload (n, slot_bytes) uint8 on this state's GPU, meta (n, AFX_KV_META) int32 on the host): a copy of the
+        listed streams (afx_kv_export).  Reads the state only; one stream synchronisation."""
+        idx = [int(v) for v in slots]
+        dev = self.engine.device
+        with torch.cuda.device(dev):
+            payload = torch.empty(len(idx), self.slot_bytes, dtype=torch.uint8, device=dev)
+            meta = torch.zeros(len(idx), _lib.KV_META, dtype=torch.int32)
+            check(lib().afx_kv_export(self._k, (C.c_int * max(len(idx), 1))(*idx), len(idx), ptr(payload), ptr(meta), self.engine._stream()))
+        return payload, meta
+
+    def import_(self, slots, payload, meta):
+        """The listed slots take over the exported streams (afx_kv_import): row i of ``payload`` / ``meta`` (an ``export``
+        result, the payload on any device or the host) becomes slot slots[i].  A meta row of another layout raises
+        ``AfxError`` before anything changes."""
+        idx = [int(v) for v in slots]
+        n, dev = len(idx), self.engine.device
+        if payload.dtype != torch.uint8 or tuple(payload.shape) != (n, self.slot_bytes):
+            raise ValueError(f"expected a ({n}, {self.slot_bytes}) uint8 payload, got {tuple(payload.shape)} {payload.dtype}")
+        if tuple(meta.shape) != (n, _lib.KV_META):
+            raise ValueError(f"expected ({n}, {_lib.KV_META}) meta rows, got {tuple(meta.shape)}")
+        m = meta.to("cpu", torch.int32).contiguous()
+        with torch.cuda.device(dev):
+            p = payload.to(dev, non_blocking=True).contiguous()
+            check(lib().afx_kv_import(self._k, (C.c_int * max(n, 1))(*idx), n, ptr(p), ptr(m), self.engine._stream()))
 

@@ -42,7 +42,17 @@ and a slot's j-th score equals, bit for bit, its score at tick j of a fresh lock
 back to back (the same row-wise argument: a sub-batch gives a row the bits the whole batch gives it).  The cost of a tick
 follows the number of named slots.  ``slots=None`` is the lock-stepped push; after the first push with slots, every push
 takes the per-slot path (with ``slots=None`` meaning every slot).
+
+Moving sessions: ``export_slots(slots)`` returns a ``StreamState``, a copy of the named slots' sessions (the scorer is not
+changed); ``StreamState.to(device)`` moves it between GPUs and host memory, ``state_dict()`` / ``StreamState.from_state_dict``
+go through ``torch.save`` / ``torch.load``; ``import_slots(slots, state)`` makes the named slots of a scorer of the same kind,
+model, weights, window and hop take those sessions over (a reset of the slots, then a restore).  A moved session continues
+bit for bit as if it had never moved, whatever the destination's number of slots and whatever its other slots hold (the
+same row-wise argument), and the other slots of the destination are untouched.
 """
+import contextlib
+import hashlib
+
 import torch
 
 from . import harness
@@ -50,15 +60,93 @@ from . import kernels as K
 from ._lib import call_on, check, lib, ptr, stream_ptr
 
 CONV_KS = [(10, 5), (3, 2), (3, 2), (3, 2), (3, 2), (2, 2), (2, 2)]
+STATE_FORMAT = 1  # StreamState layout version: import_slots refuses any other
+_META_CHECKED = ("format", "kind", "arch", "head", "dtype", "n_layers", "extractor_mode", "window", "hop", "fingerprint")
+_HOST_KEYS = ("kv_meta", "c6w")  # StreamState tensors that stay on the host whatever ``to`` is given
+
+
+def weights_fingerprint(state_dict):
+    """Digest of a checkpoint's floating-point tensors (as fp32, "module." prefixes dropped) with their names and shapes,
+    in key order: two scorers with the same fingerprint were built with the same weights."""
+    h = hashlib.blake2b(digest_size=16)
+    items = {(k[7:] if k.startswith("module.") else k): v for k, v in (state_dict or {}).items()
+             if torch.is_tensor(v) and v.dtype.is_floating_point}
+    for k in sorted(items):
+        t = items[k].detach().to("cpu", torch.float32).contiguous()
+        h.update(f"{k}:{tuple(t.shape)};".encode())
+        h.update(memoryview(t.numpy()).cast("B"))
+    return h.hexdigest()
+
+
+def _frames5(n):
+    """Layer-5 frames the conv stack completes from the first n samples of a stream."""
+    for k, s in CONV_KS[:6]:
+        n = (n - k) // s + 1 if n >= k else 0
+    return n
+
+
+def _on(device):
+    return torch.cuda.device(device) if device.type == "cuda" else contextlib.nullcontext()
+
+
+class StreamState:
+    """A copy of some slots' streaming sessions (``export_slots``), in the order they were named: ``seen`` (n,) samples per
+    session, ``tensors`` the per-session state (row i = session i), ``meta`` what the sessions need of a scorer to continue
+    in it (format, scorer kind, engine arch and head, dtype, layers, extractor mode, window, hop, weights fingerprint) and
+    the library build id (for information)."""
+
+    def __init__(self, meta, seen, tensors):
+        self.meta = dict(meta)
+        self.seen = torch.as_tensor(seen, dtype=torch.int64).cpu().reshape(-1)
+        self.tensors = dict(tensors)
+        for k, t in self.tensors.items():
+            if t.shape[0] != len(self):
+                raise ValueError(f"state tensor {k!r} has {t.shape[0]} rows for {len(self)} sessions")
+
+    def __len__(self):
+        return int(self.seen.numel())
+
+    def to(self, device, pin_memory=False):
+        """A copy on ``device`` ("cpu", "cuda:1", ...); pin_memory: host tensors in page-locked memory (device-to-host
+        copies without staging, host-to-device copies that can overlap)."""
+        dev = torch.device(device)
+        out = {}
+        for k, t in self.tensors.items():
+            if k in _HOST_KEYS:
+                out[k] = t
+            elif dev.type == "cpu" and pin_memory:
+                out[k] = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+                out[k].copy_(t, non_blocking=True)
+            else:
+                out[k] = t.to(dev)
+        if dev.type == "cpu" and pin_memory:
+            for d in {t.device for t in self.tensors.values() if t.is_cuda}:
+                torch.cuda.current_stream(d).synchronize()
+        return StreamState(self.meta, self.seen, out)
+
+    def state_dict(self):
+        """Plain tensors, strings and ints (``torch.save`` / ``torch.load(weights_only=True)``)."""
+        return {"meta": dict(self.meta), "seen": self.seen.clone(), "tensors": dict(self.tensors)}
+
+    @classmethod
+    def from_state_dict(cls, d):
+        if not isinstance(d, dict) or set(d) != {"meta", "seen", "tensors"}:
+            raise ValueError("a StreamState state_dict has the keys 'meta', 'seen' and 'tensors'")
+        if d["meta"].get("format") != STATE_FORMAT:
+            raise ValueError(f"StreamState format {d['meta'].get('format')!r}, this build reads format {STATE_FORMAT}")
+        return cls(d["meta"], d["seen"], d["tensors"])
 
 
 class SlidingWindowScorer:
-    def __init__(self, model, n_streams, window=64000, hop=4000, device="cuda"):
+    def __init__(self, model, n_streams, window=64000, hop=4000, device="cuda", state_dict=None):
         """model: anything with ``forward(batch (S, window)) -> (S, 2)`` on the GPU (an afx Engine or
-        one of the drop-in ``models.*`` modules)."""
+        one of the drop-in ``models.*`` modules).  state_dict: the weights the model was built with, for the fingerprint
+        ``export_slots`` / ``import_slots`` compare (default: ``model.state_dict()`` when the model has one)."""
         if window <= 0 or hop <= 0 or n_streams <= 0:
             raise ValueError("window, hop and the number of streams must be positive")
         self.model, self.S, self.window, self.hop = model, n_streams, window, hop
+        # (a reference, not a copy: the digest is taken on the first export or import, from the caller's tensors)
+        self._weights, self._fingerprint = state_dict, None
         self.ring = torch.zeros(n_streams, window, dtype=torch.float32, device=device)
         self.device = self.ring.device  # every launch of a push() goes to THIS GPU, whatever torch's current device is
         self.total = 0  # samples pushed since construction (every slot receives one hop per push)
@@ -194,6 +282,93 @@ class SlidingWindowScorer:
         out = self.model.forward(batch) if hasattr(self.model, "forward") else self.model(batch)
         return out[:, 1]
 
+    # ---- moving sessions -------------------------------------------------------------
+    def _engine(self):
+        return self.model
+
+    def _weights_fingerprint(self):
+        if self._fingerprint is None:
+            sd = self._weights
+            if sd is None and self._engine() is not None:
+                if not hasattr(self._engine(), "state_dict"):
+                    raise ValueError("this scorer's model has no state_dict(): build the scorer with state_dict= (the weights "
+                                     "the model was loaded with) to move its sessions")
+                sd = self._engine().state_dict()
+            self._fingerprint = weights_fingerprint(sd)
+        return self._fingerprint
+
+    def state_meta(self):
+        """What a session of this scorer needs of a scorer to continue in it (``StreamState.meta``)."""
+        e = self._engine()
+        arch = getattr(e, "arch", None)
+        conf = getattr(e, "conf", None)
+        head = {"xlsr_aasist": "aasist", "conformer": "conformer"}.get(arch, arch)
+        if arch == "conformer" and conf:
+            head += " emb {emb} heads {heads} kernel {kernel} blocks {blocks}".format(**conf)
+        return dict(format=STATE_FORMAT, kind=type(self).__name__, arch=arch, head=head, dtype=getattr(e, "dtype", None),
+                    n_layers=getattr(e, "n_layers", None), extractor_mode=getattr(e, "extractor_mode", None),
+                    window=self.window, hop=self.hop, build_id=lib().afx_build_id().decode(), fingerprint=self._weights_fingerprint())
+
+    def export_slots(self, slots):
+        """-> ``StreamState``: a copy of the named slots' sessions (indices in the caller's order, or a bool mask = ascending
+        order), on this scorer's device.  No byte of the scorer changes."""
+        idx = self._slot_list(slots, ordered=True)
+        meta = self.state_meta()
+        with _on(self.device):
+            tensors = self._export(idx) if idx else {}
+        return StreamState(meta, self._seen[idx].clone(), tensors)
+
+    def import_slots(self, slots, state):
+        """The named slots take over the sessions of ``state`` (row i -> slots[i]; their own sessions are dropped, the other
+        slots are untouched): a reset of those slots followed by a restore.  A state of another scorer kind, model, dtype,
+        window, hop, format or weights, or of another number of sessions, is a ValueError before anything changes."""
+        idx = self._slot_list(slots, ordered=True)
+        if not isinstance(state, StreamState):
+            raise ValueError("import_slots takes a StreamState (export_slots / StreamState.from_state_dict)")
+        if len(state) != len(idx):
+            raise ValueError(f"the state holds {len(state)} sessions for {len(idx)} named slots")
+        mine = self.state_meta()
+        for key in _META_CHECKED:
+            if state.meta.get(key) != mine[key]:
+                raise ValueError(f"import_slots: the state's {key} {state.meta.get(key)!r} is not this scorer's {mine[key]!r}")
+        if not idx:
+            return
+        want = self._state_shapes(len(idx))
+        got = {k: tuple(t.shape) for k, t in state.tensors.items()}
+        if set(got) != set(want) or any(len(got[k]) != len(want[k]) or any(w is not None and w != g for w, g in zip(want[k], got[k]))
+                                         for k in want):
+            raise ValueError(f"import_slots: state tensors {got} do not fit this scorer ({want})")
+        if bool((state.seen < 0).any()) or bool((state.seen % self.hop != 0).any()):
+            raise ValueError("import_slots: a session's sample count is not a whole number of hops")
+        with _on(self.device):
+            self._import(idx, state)
+        self._uniform = bool((self._seen == self._seen[0]).all())
+
+    def _state_shapes(self, n):
+        return {"samples": (n, self.window)}
+
+    def _sample_cols(self, seen):
+        """(ring columns (n, window) of each session's last min(seen, window) samples, oldest first; their count (n, 1)),
+        on the ring's device: sample i since a session's start sits at ring column i % window."""
+        dev = self.ring.device
+        m = seen.clamp(max=self.window).to(dev)[:, None]
+        j = torch.arange(self.window, device=dev)
+        return (seen.to(dev)[:, None] - m + j) % self.window, m
+
+    def _export(self, idx):
+        """The last min(seen, window) samples of each slot, oldest first (left-aligned, zeros after)."""
+        cols, m = self._sample_cols(self._seen[idx])
+        out = self.ring[torch.tensor(idx, device=self.ring.device)[:, None], cols]
+        out.masked_fill_(torch.arange(self.window, device=out.device)[None, :] >= m, 0.0)
+        return {"samples": out}
+
+    def _import(self, idx, st):
+        """Sample i since a session's start to ring column i % window (the layout ``_store`` / ``_store_slots`` keep).  The
+        whole row is written: a session younger than the window never reads the columns past its samples before it writes them."""
+        cols, _ = self._sample_cols(st.seen)
+        self.ring[torch.tensor(idx, device=self.ring.device)[:, None], cols] = st.tensors["samples"].to(self.ring.device)
+        self._seen[idx] = st.seen
+
 
 class IncrementalScorer(SlidingWindowScorer):
     """Same scores as SlidingWindowScorer, bit for bit, with conv layers 0-5 computed once per frame (see the module
@@ -205,7 +380,7 @@ class IncrementalScorer(SlidingWindowScorer):
     _exact_conv_ok = False  # fp32 / fp16x3 engines: only the KV-cached subclass (it never calls the strided tail entry point)
 
     def __init__(self, engine, state_dict, n_streams, window=64000, hop=4000):
-        super().__init__(engine, n_streams, window, hop, device=engine.device)
+        super().__init__(engine, n_streams, window, hop, device=engine.device, state_dict=state_dict)
         if hop % 160 or window % hop:
             raise ValueError("exact reuse needs hop % 160 == 0 (the stride of conv layer 5) and window % hop == 0")
         if engine.dtype in ("fp32", "fp16x3") and not self._exact_conv_ok:
@@ -399,8 +574,82 @@ class IncrementalScorer(SlidingWindowScorer):
 
     def _reset_slots(self, idx):
         super()._reset_slots(idx)
+        self._drop_carries_if_fresh()
+
+    def _drop_carries_if_fresh(self):
         if bool((self._seen == 0).all()):  # every slot starts afresh: the lockstep path from empty carries
             self.carry = [c[:, :0].contiguous() for c in self.carry]
+
+    def _engine(self):
+        return self.eng
+
+    def _state_shapes(self, n):
+        shapes = {"l5": (n, self.T5, 512), "carry0": (n, None)}
+        shapes.update({f"carry{i}": (n, None, 512) for i in range(1, 6)})
+        if self.ring is not None:
+            shapes["samples"] = (n, self.window)
+        return shapes
+
+    def _export(self, idx):
+        """+ the conv carries and the last min(T5, produced) layer-5 frames of each slot (right-aligned, zeros before)."""
+        out = super()._export(idx)
+        dev = self._l5_buf.device
+        rows = torch.tensor(idx, device=dev)
+        out.update(self._export_carries(rows))
+        f = torch.tensor([min(self.T5, _frames5(int(s))) for s in self._seen[idx].tolist()], dtype=torch.int64)
+        ends = self._l5_e[idx] if self._l5_e is not None else torch.full((len(idx),), self._l5_end, dtype=torch.int64)
+        j = torch.arange(self.T5)
+        cols = (ends[:, None] - self.T5 + j).clamp(min=0)
+        l5 = self._l5_buf[rows[:, None], cols.to(dev)]
+        l5.masked_fill_((j[None, :] < (self.T5 - f)[:, None]).to(dev)[:, :, None], 0)
+        out["l5"] = l5
+        return out
+
+    def _export_carries(self, rows):
+        return {f"carry{i}": self.carry[i].index_select(0, rows) for i in range(6)}
+
+    def _carry_plan(self, idx, st):
+        """Checks the state's conv carries against this scorer's before anything changes -> the carries to write (None: every
+        session is before its first hop and starts from empty carries on it)."""
+        if not bool((st.seen > 0).any()):
+            return None
+        live = self._seen > 0
+        live[idx] = False
+        others = bool(live.any())  # (another slot holds live carries)
+        plan = [st.tensors[f"carry{i}"] for i in range(6)]
+        for i, c in enumerate(plan):
+            if others and self.carry[i].shape[1:] != c.shape[1:]:
+                raise RuntimeError("conv carries of the state differ from this scorer's: hop / stride mismatch")
+        return plan
+
+    def _import_carries(self, idx, plan):
+        """Each slot's conv carries; then, as a reset does, empty carries for the lock-stepped path when no slot holds samples."""
+        if plan is not None:
+            dev = self.eng.device
+            rows = torch.tensor(idx, device=dev)
+            for i, c in enumerate(plan):
+                if self.carry[i].shape[1:] != c.shape[1:]:  # (no live carry here: _carry_plan checked)
+                    self.carry[i] = self.carry[i].new_zeros(self.S, *c.shape[1:])
+                self.carry[i][rows] = c.to(dev, self.carry[i].dtype)
+        self._drop_carries_if_fresh()
+
+    def _import(self, idx, st):
+        plan = self._carry_plan(idx, st)
+        super()._import(idx, st)  # (the sample ring and samples_seen)
+        self._import_carries(idx, plan)
+        # The state's T5 frames per session (right-aligned, zeros before a young session's frames: never read, a session
+        # reads its last T5 frames only once it has produced them) go before the slot's end of the buffer.
+        dev = self._l5_buf.device
+        if self._l5_e is None:  # lock-stepped / sessions path: every slot's frames end at _l5_end
+            if self._l5_end < self.T5:  # room before the shared end: every slot's frames move right together
+                d = self.T5 - self._l5_end
+                self._l5_buf[:, d:d + self._l5_end] = self._l5_buf[:, :self._l5_end].clone()
+                self._l5_end = self.T5
+            end = self._l5_end
+        else:  # non-paced path: the slot's own end, at T5
+            end = self.T5
+            self._l5_e[idx] = self.T5
+        self._l5_buf[torch.tensor(idx, device=dev), end - self.T5:end] = st.tensors["l5"].to(dev)
 
     def _conv_ln_gelu(self, xin, wp, k, s, bias, gamma, beta, fp32_out=False):
         """Conv1d(512 -> 512) + LayerNorm + GELU on (S, Tin, 512) frames: one fused kernel for the half-precision operand types;
@@ -492,6 +741,37 @@ class KVCachedScorer(IncrementalScorer):
         for b in idx:
             self._c6w[b] = 0
         super()._reset_slots(idx)
+
+    def _state_shapes(self, n):
+        shapes = {"carry0": (n, None), "c6": (n, 1, 512), "c6w": (n,), "kv_payload": (n, self.kv.slot_bytes), "kv_meta": (n, None)}
+        shapes.update({f"carry{i}": (n, None, 512) for i in range(1, 6)})
+        return shapes
+
+    def _export(self, idx):
+        """The conv carries (layers 0-5 and 6) and the library's per-stream state (KVState.export)."""
+        dev = self.eng.device
+        rows = torch.tensor(idx, device=dev)
+        out = self._export_carries(rows)
+        if self._sessions:
+            out["c6"], w = self._c6.index_select(0, rows), [self._c6w[b] for b in idx]
+        else:
+            w = [self.carry6.shape[1]] * len(idx)
+            out["c6"] = self.carry6.new_zeros(len(idx), 1, 512)
+            if w[0]:
+                out["c6"][:, :w[0]] = self.carry6.index_select(0, rows)
+        out["c6w"] = torch.tensor(w, dtype=torch.int64)
+        out["kv_payload"], out["kv_meta"] = self.kv.export(idx)
+        return out
+
+    def _import(self, idx, st):
+        plan = self._carry_plan(idx, st)  # (every check before the library call, which refuses a foreign layout itself)
+        self.kv.import_(idx, st.tensors["kv_payload"], st.tensors["kv_meta"])
+        self._seen[idx] = st.seen
+        self._import_carries(idx, plan)
+        self._per_slot_c6()
+        self._c6[torch.tensor(idx, device=self.eng.device)] = st.tensors["c6"].to(self.eng.device, self._c6.dtype)
+        for b, w in zip(idx, st.tensors["c6w"].tolist()):
+            self._c6w[b] = int(w)
 
     def _conv6_slots(self, new5, n5, idx):
         """Conv layer 6 per slot -- a slot's frames and carry depend on its own phase (12 or 13 frames per hop from its own

@@ -2114,6 +2114,177 @@ extern "C" int afx_kv_step_active(afx_kv* k, const int* slots, int A, const floa
   return 0;
 }
 
+// ---------------------------------------------------------------------------------
+// Moving sessions (afx_kv_export / afx_kv_import): a stream's state leaves one afx_kv as a payload and enters a slot of
+// another (or of the same one, on another GPU, after host memory).  Payload per stream, 16-byte words:
+//   [n_layers x 256 ring rows x the k | v thirds (2 x 1024 operand-type elements)] [64 x 1024 operand type: the positional
+//   conv's context] [208 x 1024 fp32: the feature window of feat[pp]]
+// Ring rows go in the stream's own order: payload group j is ring group (base + j) & 15.  The host meta row (AFX_KV_META
+// ints) holds the layout word, the next group relative to the base, the window length and the 16 valid counts in the same
+// relative order.  Import picks the destination's base so that the stream's next chunk lands where the destination writes
+// next (its global group; an active-list state takes the same group as the stream's next one): the per-stream attention
+// forms visit the keys rotated by the base, so the summation order, and every bit, is the one the stream had.
+// Only k and v move.  The q third of a ring row is read by the ring attention for the query tile alone (RING == 1:
+// ring.q_tile, RING == 2: the step's group, RING == 3: the stream's own group, tab[1]) -- the group the same step's QKV
+// product has just written -- and for keys only the k / v thirds are loaded (afx_attn.hip, mhsa_kernel and
+// mhsa_split_kernel).  A q row of an older group is never read again, so the destination's q columns stay as they are.
+// ---------------------------------------------------------------------------------
+constexpr int kKvFormat = 1;
+static size_t kv_slot_bytes(const afx_engine* e) {
+  return (size_t)e->cfg.n_layers * kKvSlots * 2 * kD * e->hsz + (size_t)kKvHist * kD * e->hsz + (size_t)kKvFeat * kD * 4;
+}
+// n_layers | dtype << 8 | element size << 12 | 256 / 16 - 1 << 16 | 64 / 16 << 20 | 208 / 16 << 24 | format << 28
+static int kv_layout_word(const afx_engine* e) {
+  static_assert(kKvSlots % 16 == 0 && kKvSlots / 16 <= 16 && kKvHist % 16 == 0 && kKvHist / 16 < 16 && kKvFeat % 16 == 0 &&
+                kKvFeat / 16 < 16 && kKvFormat < 8, "layout word fields");
+  return (e->cfg.n_layers & 0xff) | (e->dt & 0xf) << 8 | ((int)e->hsz & 0xf) << 12 | (kKvSlots / 16 - 1) << 16 | (kKvHist / 16) << 20 |
+         (kKvFeat / 16) << 24 | kKvFormat << 28;
+}
+// One launch per call over the slot list: block row i moves stream ids[i] (ring group of payload group j = (base_i + j) & 15,
+// base_i = bases[i], or tab[8 ids[i]] when bases is null, or 0 when both are null: a lock-stepped state).  rs = log2 of the
+// k | v words of a ring row (256 or 512).  IMPORT: payload -> state, and tab row ids[i] = rows[8 i .. 8 i + 8).
+template <bool IMPORT>
+__global__ __launch_bounds__(256) void kv_move_kernel(u32x4* __restrict__ rings, u32x4* __restrict__ hist, u32x4* __restrict__ win,
+                                                      u32x4* __restrict__ payload, const int* __restrict__ ids, const int* __restrict__ bases,
+                                                      int* __restrict__ tab, const int* __restrict__ rows, int S, int n_layers, int rs,
+                                                      long hist_words, long win_words) {
+  const long i = blockIdx.y, sl = ids[i];
+  const int base = bases ? bases[i] : tab ? tab[sl * 8] : 0;
+  const long row_words = 1L << rs, ring_words = (long)n_layers * kKvSlots << rs;
+  u32x4* p = payload + i * (ring_words + hist_words + win_words);
+  const long stride = (long)gridDim.x * blockDim.x, t0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  // four independent words per thread and pass: the loads are issued before the stores
+  for (long w0 = t0; w0 < ring_words; w0 += 4 * stride) {
+    u32x4 v[4];
+    long at[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long w = w0 + u * stride;
+      const long r = w >> rs, l = r / kKvSlots;
+      const int rr = (int)(r % kKvSlots), g = ((rr >> 4) + base) & (kKvGroups - 1);
+      // [q | k | v] ring row = 3 / 2 row_words words; k | v start at its second third
+      at[u] = w < ring_words ? ((l * S + sl) * kKvSlots + g * 16 + (rr & 15)) * (3 * row_words / 2) + row_words / 2 + (w & (row_words - 1)) : -1;
+      if (at[u] >= 0) v[u] = IMPORT ? p[w] : rings[at[u]];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (at[u] < 0) continue;
+      if (IMPORT) rings[at[u]] = v[u];
+      else p[w0 + u * stride] = v[u];
+    }
+  }
+  u32x4 *ph = p + ring_words, *pw = ph + hist_words, *h = hist + sl * hist_words, *f = win + sl * win_words;
+  for (long w = t0; w < hist_words; w += stride) {
+    if (IMPORT) h[w] = ph[w];
+    else ph[w] = h[w];
+  }
+  for (long w = t0; w < win_words; w += stride) {
+    if (IMPORT) f[w] = pw[w];
+    else pw[w] = f[w];
+  }
+  if (IMPORT && blockIdx.x == 0 && threadIdx.x < 8) tab[sl * 8 + threadIdx.x] = rows[i * 8 + threadIdx.x];
+}
+
+static int kv_slot_list(const afx_kv* k, const int* slots, int n, const char* what) {
+  std::vector<char> seen(k->S, 0);
+  for (int i = 0; i < n; ++i) {
+    if (slots[i] < 0 || slots[i] >= k->S) return fail("%s: slot %d outside 0..%d", what, slots[i], k->S - 1);
+    if (seen[slots[i]]++) return fail("%s: slot %d named twice", what, slots[i]);
+  }
+  return 0;
+}
+static int kv_move_launch(afx_kv* k, bool import, int n, void* payload, const int* bases, hipStream_t s) {
+  const afx_engine* e = k->e;
+  if (n > 65535) return fail("afx_kv_%s: at most 65535 streams per call", import ? "import" : "export");
+  const int rs = e->hsz == 4 ? 9 : 8;  // 2 x 1024 elements of 2 or 4 bytes = 256 or 512 words
+  const int gx = std::max(8, std::min(256, 4096 / n));
+  u32x4* win = (u32x4*)k->feat[k->pp];
+  const long hw = (long)kKvHist * kD * e->hsz / 16, ww = (long)kKvFeat * kD * 4 / 16;
+  if (import)
+    hipLaunchKernelGGL(kv_move_kernel<true>, dim3(gx, n), dim3(256), 0, s, (u32x4*)k->rings, (u32x4*)k->hist, win, (u32x4*)payload, k->meta,
+                       bases, k->tab, k->meta + 2 * n, k->S, e->cfg.n_layers, rs, hw, ww);
+  else
+    hipLaunchKernelGGL(kv_move_kernel<false>, dim3(gx, n), dim3(256), 0, s, (u32x4*)k->rings, (u32x4*)k->hist, win, (u32x4*)payload, k->meta,
+                       (const int*)nullptr, k->per_stream ? k->tab : nullptr, (const int*)nullptr, k->S, e->cfg.n_layers, rs, hw, ww);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+extern "C" size_t afx_kv_slot_bytes(const afx_kv* k) { return k ? kv_slot_bytes(k->e) : 0; }
+
+extern "C" int afx_kv_export(afx_kv* k, const int* slots, int n, void* payload, int* meta, void* stream) {
+  if (!k) return fail("afx_kv_export: null state");
+  if (n < 0 || n > k->S) return fail("afx_kv_export: %d streams (0..%d)", n, k->S);
+  if (n == 0) return 0;
+  if (!slots || !payload || !meta) return fail("afx_kv_export: null argument");
+  if ((uintptr_t)payload & 15) return fail("afx_kv_export: the payload must be 16-byte aligned");
+  if (kv_slot_list(k, slots, n, "afx_kv_export")) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  // the state is read, never converted: a lock-stepped state exports base 0, its shared counts, group and window length
+  std::vector<int> t;
+  if (k->per_stream) {
+    t.resize((size_t)k->S * 8);
+    HIP_OK(hipMemcpyAsync(t.data(), k->tab, t.size() * 4, hipMemcpyDeviceToHost, s));
+  }
+  std::vector<int> ids(slots, slots + n);
+  HIP_OK(hipMemcpyAsync(k->meta, ids.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+  HIP_OK(hipStreamSynchronize(s));
+  const int layout = kv_layout_word(k->e), group = (int)(k->hop % kKvGroups);
+  for (int i = 0; i < n; ++i) {
+    const int* row = k->per_stream ? &t[(size_t)slots[i] * 8] : nullptr;
+    const int base = row ? row[0] & (kKvGroups - 1) : 0, next = row && k->active ? row[1] : group;
+    int* m = meta + (size_t)i * AFX_KV_META;
+    m[0] = layout;
+    m[1] = (next - base) & (kKvGroups - 1);
+    m[2] = k->per_stream ? k->nfeat_s[slots[i]] : k->nfeat;
+    m[3] = 0;
+    unsigned char* c = (unsigned char*)(m + 4);
+    for (int j = 0; j < kKvGroups; ++j)
+      c[j] = row ? ((const unsigned char*)(row + 4))[(base + j) & (kKvGroups - 1)] : (unsigned char)k->cnt[(base + j) & (kKvGroups - 1)];
+  }
+  return kv_move_launch(k, false, n, payload, nullptr, s);
+}
+
+extern "C" int afx_kv_import(afx_kv* k, const int* slots, int n, const void* payload, const int* meta, void* stream) {
+  if (!k) return fail("afx_kv_import: null state");
+  if (n < 0 || n > k->S) return fail("afx_kv_import: %d streams (0..%d)", n, k->S);
+  if (n == 0) return 0;
+  if (!slots || !payload || !meta) return fail("afx_kv_import: null argument");
+  if ((uintptr_t)payload & 15) return fail("afx_kv_import: the payload must be 16-byte aligned");
+  if (kv_slot_list(k, slots, n, "afx_kv_import")) return 1;
+  const int layout = kv_layout_word(k->e);
+  for (int i = 0; i < n; ++i) {  // every row is checked before anything changes
+    const int* m = meta + (size_t)i * AFX_KV_META;
+    if (m[0] != layout)
+      return fail("afx_kv_import: stream %d's layout word 0x%08x does not match this state's 0x%08x (layers, dtype, element size, "
+                  "ring / context / window rows, format)", i, (unsigned)m[0], (unsigned)layout);
+    if (m[1] < 0 || m[1] >= kKvGroups || m[2] < 0 || m[2] > kKvFeat || m[3] != 0) return fail("afx_kv_import: stream %d's meta row is corrupt", i);
+    for (int j = 0; j < kKvGroups; ++j)
+      if (((const unsigned char*)(m + 4))[j] > 16) return fail("afx_kv_import: stream %d holds a group of more than 16 frames", i);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (kv_to_per_stream(k, s)) return 1;  // (a never-reset lock-stepped state becomes per stream, as afx_kv_reset makes it)
+  // the stream's next chunk goes where this state writes next: the global group (an active-list state: the same group,
+  // set as the stream's own next one)
+  const int group = (int)(k->hop % kKvGroups);
+  std::vector<int> h((size_t)10 * n, 0);
+  for (int i = 0; i < n; ++i) {
+    const int* m = meta + (size_t)i * AFX_KV_META;
+    const int base = (group - m[1]) & (kKvGroups - 1);
+    h[i] = slots[i];
+    h[n + i] = base;
+    int* row = &h[(size_t)2 * n + 8 * i];
+    row[0] = base;
+    row[1] = group;
+    for (int j = 0; j < kKvGroups; ++j) ((unsigned char*)(row + 4))[(base + j) & (kKvGroups - 1)] = ((const unsigned char*)(m + 4))[j];
+  }
+  HIP_OK(hipMemcpyAsync(k->meta, h.data(), h.size() * 4, hipMemcpyHostToDevice, s));
+  HIP_OK(hipStreamSynchronize(s));  // (pageable host memory)
+  if (kv_move_launch(k, true, n, const_cast<void*>(payload), k->meta + n, s)) return 1;
+  for (int i = 0; i < n; ++i) k->nfeat_s[slots[i]] = meta[(size_t)i * AFX_KV_META + 2];
+  return 0;
+}
+
 #undef launch_gemm
 #undef launch_rownorm
 
