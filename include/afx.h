@@ -255,6 +255,24 @@ int afx_k_pre_emphasis(const float* x, int B, int L, float coef, float* y, void*
  * offsets (device, int64), starts[B] crop starts or NULL; out (B, duration): out[b][i] = x_b[(start_b + i) mod n_b]. */
 int afx_k_tile_crop(const float* x, const long long* offs, const long long* starts, int B, int duration, float* out,
                     void* stream);
+/* Polyphase resampling of an integer input rate r to 16 kHz (afx/resample.py builds the taps): g = gcd(16000, r),
+ * L = 16000/g up, M = r/g down, h = firwin(2*half_len + 1, 1/max(L, M), window=("kaiser", 5.0)) * L with
+ * half_len = 10*max(L, M) (scipy.signal.resample_poly's default design, float64); taps (L, T) fp32 with
+ * taps[p][j] = h[p + j*L] (0 past the end), T = ceil(len(h)/L).  Causal, zero history before the first sample:
+ *     y[n] = sum_{j<T} taps[p][j] * x[i0 - j],  i0 = floor(n*M/L),  p = n*M mod L,  x[<0] = 0
+ * = upfirdn(h, x, L, M)[:ceil(N*L/M)], fp32 with one fma chain per output in ascending j; it lags resample_poly by
+ * half_len/M output samples.  Offline: x = clips packed back to back (device), in_offs / out_offs[B+1] their input and
+ * output offsets (device, int64; out_offs[b+1] - out_offs[b] = ceil(n_b*L/M)), max_out = the longest output row.
+ * M/L <= 12. */
+int afx_k_resample(const float* x, const long long* in_offs, const long long* out_offs, int B, long long max_out,
+                   const float* taps, int L, int M, int T, float* out, void* stream);
+/* The same function streamed: row i of x (A, n_in) is the next chunk of the stream in slot slot[i] (int32, device,
+ * distinct); it is resampled as hist[slot[i]] ++ x[i] (hist (S, T-1) fp32: the stream's last T-1 samples, zeros for a
+ * new stream) into exactly n_in*L/M outputs (n_in*L % M == 0), then hist[slot[i]] takes the last T-1 samples of that
+ * concatenation.  Each output gets the offline form's inputs, taps and order: chunked output is bit-identical to the
+ * whole stream resampled by afx_k_resample.  Rows of slots not named are untouched. */
+int afx_k_resample_stream(const float* x, int A, int n_in, float* hist, const int* slot, const float* taps, int L, int M,
+                          int T, float* out, void* stream);
 int afx_k_rownorm(int dtype, const float* x, long ldx, int rows, int C, const float* gamma, const float* beta,
                   float eps, int act, float* out_f, long ldo_f, void* out_h, long ldo_h, void* stream);
 int afx_k_mhsa(int dtype, const void* qkv, void* out, int B, int T, int H, void* stream);

@@ -65,13 +65,19 @@ def adjust_duration(x, duration):
     return x[:duration]
 
 
-def batch_adjust_duration(clips, duration, starts=None, device="cuda"):
+def batch_adjust_duration(clips, duration, starts=None, device="cuda", sample_rate=16000):
     """The same policy for a whole ragged batch as ONE device op: ``clips`` is a list of 1-D waveforms
     of any lengths, the result a (B, duration) fp32 batch on the GPU.  ``starts`` (optional, one per
-    clip) are the crop starts of data/test_set.py:229-248 for clips longer than ``duration``."""
+    clip) are the crop starts of data/test_set.py:229-248 for clips longer than ``duration``.
+    ``sample_rate``: the clips' rate; other than 16 kHz, the clips are first resampled to 16 kHz on the
+    device (afx.resample, one launch), and ``duration`` / ``starts`` count 16 kHz samples -- the order of
+    the reference, which loads at 16 kHz and then pads or crops."""
     import ctypes as C
 
     from ._lib import call_on, check, lib, ptr, stream_ptr
+    if sample_rate != 16000:
+        from .resample import Resampler
+        clips = Resampler(sample_rate, device).clips(clips)
     lens = [int(c.numel()) for c in clips]
     if not clips or min(lens) <= 0:
         raise ValueError("every clip needs at least one sample")

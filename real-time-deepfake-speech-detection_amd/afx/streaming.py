@@ -840,3 +840,94 @@ class KVCachedScorer(IncrementalScorer):
         self.frames += n_out
         return self.kv.step(f6)[:, 1]
 
+
+
+class ResamplingScorer:
+    """Any of the three scorers fed audio at ``input_rate`` Hz: each hop is resampled to 16 kHz on the GPU
+    (``afx.resample``: causal polyphase filter, ``delay`` 16 kHz samples behind resample_poly's centred output) with
+    per-slot filter history, then pushed into ``scorer``.  A slot's scores are, bit for bit, those of ``scorer`` fed
+    ``Resampler(input_rate)(the slot's whole stream)`` hop by hop: resampling a stream hop by hop with carried history is
+    bit-identical to resampling it whole.  Sessions keep that through the inner scorer's contracts: ``reset(slots)`` also
+    zeroes the named slots' filter history, a non-paced ``push(chunk, slots)`` touches no other slot's history, and
+    ``export_slots`` / ``import_slots`` carry it (StreamState tensor ``resample_hist``, meta ``input_rate`` and
+    ``resampler``).  ``samples_seen`` counts the inner scorer's 16 kHz samples."""
+
+    def __init__(self, scorer, input_rate):
+        from .resample import TARGET_RATE, Resampler
+        self.rs = Resampler(input_rate, scorer.device)  # (a bad rate is a ValueError here)
+        if (scorer.hop * self.rs.rate) % TARGET_RATE:
+            raise ValueError(f"a hop of {scorer.hop} samples at 16 kHz is {scorer.hop * self.rs.rate / TARGET_RATE} samples at "
+                             f"{self.rs.rate} Hz: not a whole number")
+        self.scorer, self.input_rate, self.hop_in = scorer, self.rs.rate, scorer.hop * self.rs.rate // TARGET_RATE
+        self.hist = torch.zeros(scorer.S, self.rs.history, dtype=torch.float32, device=scorer.device)
+
+    @property
+    def S(self):
+        return self.scorer.S
+
+    @property
+    def device(self):
+        return self.scorer.device
+
+    @property
+    def delay(self):
+        """The resampled stream's lag behind resample_poly's centred output, in 16 kHz samples."""
+        return self.rs.delay
+
+    @property
+    def samples_seen(self):
+        """(S,) int64: the 16 kHz samples each slot's inner session received since its last ``reset``."""
+        return self.scorer.samples_seen
+
+    def push(self, chunk, slots=None):
+        """chunk: (S, hop_in) fp32 on the GPU at ``input_rate`` (or (len(slots), hop_in) with ``slots``: the non-paced push
+        of the inner scorer).  Returns the inner scorer's scores."""
+        idx = None if slots is None else self.scorer._slot_list(slots, ordered=True)
+        n = self.S if idx is None else len(idx)
+        if not isinstance(chunk, torch.Tensor) or not chunk.is_cuda or chunk.shape != (n, self.hop_in):
+            raise ValueError(f"expected a CUDA tensor of shape {(n, self.hop_in)} (one hop at {self.input_rate} Hz per slot)")
+        with torch.cuda.device(self.device):
+            y = self.rs.stream(chunk.to(self.device), self.hist, idx)
+            return self.scorer.push(y, idx)
+
+    def reset(self, slots):
+        """The named slots begin a new stream (inner session and filter history) with their next ``push``."""
+        idx = self.scorer._slot_list(slots)
+        self.scorer.reset(idx)
+        if idx:
+            self.hist[idx] = 0.0
+
+    def state_meta(self):
+        from .resample import FILTER_ID
+        return dict(self.scorer.state_meta(), input_rate=self.input_rate, resampler=FILTER_ID)
+
+    def export_slots(self, slots):
+        """The inner scorer's ``StreamState`` of the named slots plus their filter history."""
+        from .resample import FILTER_ID
+        idx = self.scorer._slot_list(slots, ordered=True)
+        st = self.scorer.export_slots(idx)
+        tensors = dict(st.tensors, resample_hist=self.hist[torch.tensor(idx, dtype=torch.long, device=self.device)].clone())
+        return StreamState(dict(st.meta, input_rate=self.input_rate, resampler=FILTER_ID), st.seen, tensors)
+
+    def import_slots(self, slots, state):
+        """The named slots take over the sessions of ``state``, a state of a ResamplingScorer at the same input rate and
+        filter; anything else is a ValueError before anything changes."""
+        from .resample import FILTER_ID
+        idx = self.scorer._slot_list(slots, ordered=True)
+        if not isinstance(state, StreamState):
+            raise ValueError("import_slots takes a StreamState (export_slots / StreamState.from_state_dict)")
+        if "resample_hist" not in state.tensors or "resampler" not in state.meta or "input_rate" not in state.meta:
+            raise ValueError("import_slots: the state has no resampler history (it was not exported by a ResamplingScorer)")
+        if state.meta["input_rate"] != self.input_rate:
+            raise ValueError(f"import_slots: the state's input rate {state.meta['input_rate']!r} is not this scorer's {self.input_rate}")
+        if state.meta["resampler"] != FILTER_ID:
+            raise ValueError(f"import_slots: the state's resampler {state.meta['resampler']!r} is not this scorer's {FILTER_ID!r}")
+        h = state.tensors["resample_hist"]
+        if tuple(h.shape) != (len(state), self.rs.history) or h.dtype != torch.float32:
+            raise ValueError(f"import_slots: resample_hist {tuple(h.shape)} {h.dtype} does not fit this scorer "
+                             f"({(len(state), self.rs.history)} float32)")
+        inner = StreamState({k: v for k, v in state.meta.items() if k not in ("input_rate", "resampler")}, state.seen,
+                            {k: t for k, t in state.tensors.items() if k != "resample_hist"})
+        self.scorer.import_slots(idx, inner)  # (refuses a foreign state before changing anything)
+        if idx:
+            self.hist[torch.tensor(idx, dtype=torch.long, device=self.device)] = h.to(self.device)

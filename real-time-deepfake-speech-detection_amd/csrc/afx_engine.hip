@@ -2734,6 +2734,14 @@ extern "C" int afx_k_tile_crop(const float* x, const long long* offs, const long
   if (!x || !offs || !out) return fail("afx_k_tile_crop: null argument");
   KRET(launch_tile_crop(x, offs, starts, B, duration, out, (hipStream_t)stream));
 }
+extern "C" int afx_k_resample(const float* x, const long long* in_offs, const long long* out_offs, int B,
+                              long long max_out, const float* taps, int L, int M, int T, float* out, void* stream) {
+  KRET(launch_resample(x, in_offs, out_offs, B, max_out, taps, L, M, T, out, (hipStream_t)stream));
+}
+extern "C" int afx_k_resample_stream(const float* x, int A, int n_in, float* hist, const int* slot, const float* taps,
+                                     int L, int M, int T, float* out, void* stream) {
+  KRET(launch_resample_stream(x, A, n_in, hist, slot, taps, L, M, T, out, (hipStream_t)stream));
+}
 extern "C" int afx_k_rownorm(int dtype, const float* x, long ldx, int rows, int C, const float* gamma,
                              const float* beta, float eps, int act, float* out_f, long ldo_f, void* out_h, long ldo_h,
                              void* stream) {

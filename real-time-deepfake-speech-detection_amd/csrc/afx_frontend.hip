@@ -636,6 +636,142 @@ const char* launch_tile_crop(const float* x, const long long* offs, const long l
 }
 
 // ---------------------------------------------------------------------------------
+// Polyphase resampling to 16 kHz (afx/resample.py; the function is stated in include/afx.h):
+//     y[n] = sum_{j<T} taps[p][j] * v[i0 - j],   i0 = floor(n*M/L),  p = n*M mod L
+// fp32 taps, one fmaf chain per output in ascending j.  v is the input with zeros before its first sample (offline form)
+// or a row's T-1 carried samples before it (streaming form).  Both forms give each output the same T inputs and taps in
+// the same order, so a stream resampled hop by hop is bit-identical to the whole signal resampled at once.
+// A workgroup owns `R` consecutive sub-tiles of 256 outputs of one row (one output per lane); per sub-tile it stages
+// its input span v[i0(n0) - (T-1) .. i0(n0 + 255)] in LDS.  The (L, T) tap table is staged in LDS too (row stride Tp,
+// odd, so lanes on different phases hit different banks) when it fits, else read from global memory.  Memory-bound: a
+// 48 kHz input is read once, the 16 kHz output written once.
+// ---------------------------------------------------------------------------------
+constexpr int RS_TILE = 256;          // outputs per sub-tile (one per lane)
+constexpr int RS_TAPS_LDS = 12288;    // largest L * Tp staged in LDS (48 KB)
+constexpr int RS_SPAN_MAX = 4096;     // largest staged input span (16 KB): (255 M + L - 1) / L + T for M / L <= 12
+
+struct ResampleArgs {
+  const float* x;                // offline: clips packed back to back; streaming: (A, n_in) rows
+  const long long* in_offs;      // offline: input offsets (B + 1)
+  const long long* out_offs;     // offline: output offsets (B + 1)
+  const float* hist;             // streaming: (S, T - 1) carried samples, oldest first
+  const int* slot;               // streaming: row -> hist row
+  const float* taps;             // (L, T)
+  int L, M, T, Tp, R, n_in;
+  float* out;
+};
+
+template <bool STREAM, bool LDS_TAPS>
+__global__ __launch_bounds__(256) void resample_kernel(ResampleArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float rs_lds[];
+  const int row = blockIdx.y, T = a.T;
+  long long in_base, out_base, n_out;
+  if (STREAM) {
+    n_out = (long long)a.n_in * a.L / a.M;
+    in_base = (long long)row * a.n_in;
+    out_base = (long long)row * n_out;
+  } else {
+    in_base = a.in_offs[row];
+    out_base = a.out_offs[row];
+    n_out = a.out_offs[row + 1] - out_base;
+  }
+  const float* hrow = STREAM ? a.hist + (long long)a.slot[row] * (T - 1) : nullptr;
+  const float* tp = a.taps;
+  int ts = T;
+  float* xs = rs_lds;
+  if (LDS_TAPS) {
+    for (int k = threadIdx.x; k < a.L * a.Tp; k += blockDim.x) {
+      const int p = k / a.Tp, j = k - p * a.Tp;
+      rs_lds[k] = j < T ? a.taps[p * T + j] : 0.f;
+    }
+    tp = rs_lds;
+    ts = a.Tp;
+    xs = rs_lds + a.L * a.Tp;
+  }
+  for (int r = 0; r < a.R; ++r) {
+    const long long n0 = ((long long)blockIdx.x * a.R + r) * RS_TILE;
+    if (n0 >= n_out) break;
+    const int cnt = (int)min((long long)RS_TILE, n_out - n0);
+    const long long q0 = n0 * a.M, b0 = q0 / a.L;
+    const int p0 = (int)(q0 - b0 * a.L);
+    // inputs b0 - (T-1) .. i0(n0 + cnt - 1); i0(n) < n_src for every n < n_out, so the span ends inside the row
+    const int span = (int)(((long long)(cnt - 1) * a.M + p0) / a.L) + T;
+    __syncthreads();  // the previous sub-tile is done with xs
+    for (int s = threadIdx.x; s < span; s += blockDim.x) {
+      const long long k = b0 - (T - 1) + s;
+      xs[s] = k >= 0 ? a.x[in_base + k] : (STREAM ? hrow[T - 1 + k] : 0.f);
+    }
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < cnt) {
+      const unsigned q = (unsigned)t * (unsigned)a.M + (unsigned)p0;
+      const int di = (int)(q / (unsigned)a.L), p = (int)(q - (unsigned)di * (unsigned)a.L);
+      const float* w = tp + (long)p * ts;
+      const float* xv = xs + di + T - 1;
+      float acc = 0.f;
+      for (int j = 0; j < T; ++j) acc = __builtin_fmaf(w[j], xv[-j], acc);
+      a.out[out_base + n0 + t] = acc;
+    }
+  }
+}
+
+// the carried samples of each streamed row after its chunk: the last T-1 of hist[slot[row]] ++ chunk[row].  One workgroup
+// per row (the slots are distinct): every lane reads its new value before any lane writes, so the in-place shift of a
+// chunk shorter than T-1 does not race.
+__global__ __launch_bounds__(256) void resample_hist_kernel(const float* __restrict__ x, int n_in, const int* __restrict__ slot,
+                                                            int H, float* hist) {
+  const int row = blockIdx.x, k = threadIdx.x;
+  float* h = hist + (long long)slot[row] * H;
+  float v = 0.f;
+  if (k < H) v = k + n_in < H ? h[k + n_in] : x[(long long)row * n_in + k + n_in - H];
+  __syncthreads();
+  if (k < H) h[k] = v;
+}
+
+static const char* launch_resample_any(bool stream, ResampleArgs a, int rows, long long max_out, hipStream_t s) {
+  if (a.L <= 0 || a.M <= 0 || a.T <= 0 || !a.taps || !a.x || !a.out) return "resample: bad arguments";
+  if (rows <= 0 || rows > 65535) return "resample: 1 to 65535 rows";
+  if (max_out <= 0) return nullptr;
+  const long long span = (255LL * a.M + a.L - 1) / a.L + a.T;
+  if (span > RS_SPAN_MAX) return "resample: input / output ratio above 12";
+  a.Tp = a.T | 1;
+  const bool lds_taps = (long long)a.L * a.Tp <= RS_TAPS_LDS;
+  a.R = lds_taps ? max(1, min(8, a.L * a.Tp / 1024)) : 1;  // amortise the tap staging of many-phase ratios
+  const long long gx = (max_out + (long long)RS_TILE * a.R - 1) / ((long long)RS_TILE * a.R);
+  if (gx > 0x7fffffffLL) return "resample: too many outputs per row";
+  const size_t lds = sizeof(float) * (size_t)((lds_taps ? a.L * a.Tp : 0) + span);
+  const dim3 grid((unsigned)gx, rows);
+  if (stream && lds_taps) hipLaunchKernelGGL((resample_kernel<true, true>), grid, dim3(256), lds, s, a);
+  else if (stream) hipLaunchKernelGGL((resample_kernel<true, false>), grid, dim3(256), lds, s, a);
+  else if (lds_taps) hipLaunchKernelGGL((resample_kernel<false, true>), grid, dim3(256), lds, s, a);
+  else hipLaunchKernelGGL((resample_kernel<false, false>), grid, dim3(256), lds, s, a);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+const char* launch_resample(const float* x, const long long* in_offs, const long long* out_offs, int B, long long max_out,
+                            const float* taps, int L, int M, int T, float* out, hipStream_t s) {
+  if (!in_offs || !out_offs) return "resample: null offsets";
+  ResampleArgs a{};
+  a.x = x; a.in_offs = in_offs; a.out_offs = out_offs; a.taps = taps; a.L = L; a.M = M; a.T = T; a.out = out;
+  return launch_resample_any(false, a, B, max_out, s);
+}
+
+const char* launch_resample_stream(const float* x, int A, int n_in, float* hist, const int* slot, const float* taps, int L,
+                                   int M, int T, float* out, hipStream_t s) {
+  if (!hist || !slot) return "resample_stream: null history or slot table";
+  if (n_in <= 0 || M <= 0 || ((long long)n_in * L) % M != 0) return "resample_stream: n_in * L must be a multiple of M";
+  if (T - 1 > 256) return "resample_stream: more than 256 carried samples";
+  ResampleArgs a{};
+  a.x = x; a.hist = hist; a.slot = slot; a.taps = taps; a.L = L; a.M = M; a.T = T; a.n_in = n_in; a.out = out;
+  const char* m = launch_resample_any(true, a, A, (long long)n_in * L / M, s);
+  if (m || T == 1) return m;
+  hipLaunchKernelGGL(resample_hist_kernel, dim3(A), dim3(256), 0, s, x, n_in, slot, T - 1, hist);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+// ---------------------------------------------------------------------------------
 // Row LayerNorm (+ activation): one wave per row, C <= 1024, C % 4 == 0.  The row
 // stays in registers (float4 per lane per 256-column slab), two-pass statistics in
 // fp32 like torch.  Used for the conv-stack LayerNorm+GELU, every transformer /

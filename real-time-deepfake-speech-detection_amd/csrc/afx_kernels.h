@@ -132,6 +132,12 @@ size_t conv0_groupnorm_stats_floats(int B, int T0);
 // ragged batch (packed, offs[B+1]) -> (B, duration): out[b][i] = x_b[(start_b + i) mod n_b]; starts may be null
 const char* launch_tile_crop(const float* x, const long long* offs, const long long* starts, int B, int duration,
                              float* out, hipStream_t s);
+// polyphase resampling (include/afx.h afx_k_resample / afx_k_resample_stream): offline over packed clips with int64 input
+// and output offsets (max_out = the longest output row), or streamed rows with per-slot carried samples hist (S, T-1)
+const char* launch_resample(const float* x, const long long* in_offs, const long long* out_offs, int B, long long max_out,
+                            const float* taps, int L, int M, int T, float* out, hipStream_t s);
+const char* launch_resample_stream(const float* x, int A, int n_in, float* hist, const int* slot, const float* taps, int L,
+                                   int M, int T, float* out, hipStream_t s);
 void conv0_set_mfma(int v);  // A/B knob: 1 (default) = matrix-core forms (split-precision fp16 when packed), 2 = fp32 MFMA form, 0 = VALU form
 // y[t] = x[t] - coef * x[t-1] with a reflect pad on the left; (B,L) fp32 -> (B,L) fp32
 const char* launch_pre_emphasis(const float* x, int B, int L, float coef, float* y, hipStream_t s);

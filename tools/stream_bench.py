@@ -23,6 +23,9 @@ bytes per session), then the hop time of a --migrate-hop-streams scorer that imp
 against one that does not.
     python tools/stream_bench.py --migrate [--workload xlsr_aasist] [--streams 1 64 512] ...
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/stream_bench.py --gpus N ...
+--input-rate R feeds every scorer audio at R Hz through ``ResamplingScorer`` (hops of 4000 * R / 16000 samples resampled to
+16 kHz on the GPU with per-slot filter history); the hop time then includes the resampling.
+    python tools/stream_bench.py --input-rate 48000 --modes kv-cached --streams 2048 ...
 
 With --gpus N every rank pins its own S streams to its GPU (state lives there; nothing is exchanged on the data path);
 the hop time reported is the max over ranks (one RCCL all-reduce of a scalar, outside the timed hops), the stream
@@ -37,7 +40,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "real-time-deepfake-speech-detection_amd")]
 from afx import engine, synth  # noqa: E402
-from afx.streaming import IncrementalScorer, KVCachedScorer, SlidingWindowScorer  # noqa: E402
+from afx.streaming import IncrementalScorer, KVCachedScorer, ResamplingScorer, SlidingWindowScorer  # noqa: E402
 
 
 def main():
@@ -53,6 +56,7 @@ def main():
                     help="also time non-paced streams: each slot has audio on a tick with this probability (seeded)")
     ap.add_argument("--migrate", action="store_true", help="time export_slots / import_slots instead of the hop (see above)")
     ap.add_argument("--migrate-hop-streams", type=int, default=2048, help="--migrate: streams of the scorer timed while it imports")
+    ap.add_argument("--input-rate", type=int, default=16000, help="audio rate fed to the scorers (resampled to 16 kHz on the GPU)")
     args = ap.parse_args()
     rank, local, world = (int(os.environ.get(k, d)) for k, d in (("RANK", 0), ("LOCAL_RANK", 0), ("WORLD_SIZE", 1)))
     if world != args.gpus:
@@ -68,22 +72,25 @@ def main():
     eng = engine.Engine(arch, n_layers=nl, dtype="fp16")
     eng.load_state_dict(sd)
     W, H = 64000, 4000
+    H_in = H * args.input_rate // 16000
     if args.migrate:
         return migrate(args, eng, sd, W, H)
     for S in args.streams:
-        line = f"{args.workload}, {world} GPU(s) x {S} streams:"
+        line = f"{args.workload}, {world} GPU(s) x {S} streams" + (f" at {args.input_rate} Hz" if args.input_rate != 16000 else "") + ":"
         for name in args.modes:
             for staggered, frac in [(False, None)] + ([(True, None)] if args.staggered else []) + [(False, f) for f in args.active_frac]:
                 label = name + (" staggered" if staggered else "") + (f" active {frac:.2f}" if frac is not None else "")
                 try:
                     sc = {"sliding": lambda: SlidingWindowScorer(eng, S, window=W, hop=H), "incremental": lambda: IncrementalScorer(eng, sd, S, window=W, hop=H),
                           "kv-cached": lambda: KVCachedScorer(eng, sd, S, window=W, hop=H)}[name]()
+                    if args.input_rate != 16000:
+                        sc = ResamplingScorer(sc, args.input_rate)
                     if staggered:
                         sc.reset([0])  # (a no-op on a fresh scorer; a mode without sessions refuses it here)
                 except Exception as exc:  # (the K / V rings of 24 layers are 38 MB per stream: 2 048 streams of the teacher do not fit beside the rest)
                     line += f"  {label} n/a ({str(exc)[:60]})"
                     continue
-                chunk = (0.1 * torch.randn(S, H, generator=torch.Generator().manual_seed(rank))).cuda()
+                chunk = (0.1 * torch.randn(S, H_in, generator=torch.Generator().manual_seed(rank))).cuda()
                 gen = torch.Generator().manual_seed(1000 + rank)
 
                 n_active = []
