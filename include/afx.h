@@ -120,6 +120,15 @@ int afx_tail_forward(afx_handle h, const void* conv5_h, int B, int T5, float* lo
  * passes a view, no copy per hop */
 int afx_tail_forward_strided(afx_handle h, const void* conv5_h, long batch_stride, int B, int T5, float* logits, void* ws,
                              size_t ws_bytes, void* stream);
+/* the same over B windows at arbitrary offsets of ONE layer-5 buffer (an offline timeline: the conv stack runs once over a
+ * whole recording, afx/timeline.py): window b is the T5 rows that start at element offs[b] of conv5_h, which holds
+ * total_elems elements.  Windows may overlap and may come from different recordings sharing the buffer.  offs: HOST
+ * long long[B], each a multiple of 8 with offs[b] + T5 * 512 <= total_elems -- checked before anything is launched.  A
+ * gather kernel packs the windows into the workspace (their offsets travel as kernel arguments: no upload, asynchronous),
+ * then the packed tail runs: window b's logits equal afx_tail_forward's on those rows copied contiguous, bit for bit. */
+size_t afx_tail_windows_workspace_bytes(afx_handle h, int B, int T5);
+int afx_tail_forward_windows(afx_handle h, const void* conv5_h, long long total_elems, const long long* offs, int B, int T5,
+                             float* logits, void* ws, size_t ws_bytes, void* stream);
 /* ---- KV-cached streaming mode (BASELINE config 5 as named: "250 ms chunks with cached SSL-encoder KV state") ----------
  * NOT A REFERENCE FUNCTION: the reference's trunk is bidirectional over the clip, an encoder that sees every frame once
  * -- when its chunk arrives -- is a different model (block-causal: a chunk's frames attend to the chunk and to the cached

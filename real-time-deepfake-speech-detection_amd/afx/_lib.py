@@ -53,6 +53,8 @@ SIGNATURES = {
     "afx_tail_workspace_bytes": (_Z, [_P, _I, _I]),
     "afx_tail_forward": (_I, [_P, _P, _I, _I, _P, _P, _Z, _P]),
     "afx_tail_forward_strided": (_I, [_P, _P, _L, _I, _I, _P, _P, _Z, _P]),
+    "afx_tail_windows_workspace_bytes": (_Z, [_P, _I, _I]),
+    "afx_tail_forward_windows": (_I, [_P, _P, C.c_longlong, C.POINTER(C.c_longlong), _I, _I, _P, _P, _Z, _P]),
     "afx_conformer_forward": (_I, [_P, _P, _I, _I, _P, _P, _P, _Z, _P]),
     "afx_engine_set": (_I, [_P, C.c_char_p, _I]),
     "afx_kv_create": (_I, [_P, _I, C.POINTER(_P)]),

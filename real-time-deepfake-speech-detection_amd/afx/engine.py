@@ -417,6 +417,28 @@ class Engine:
                                              self._stream()))
         return out
 
+    def tail_windows(self, conv5, offsets, T5=399):
+        """conv5: a contiguous buffer of layer-5 frames in the operand type ((F, 512), any shape of whole frames) shared by
+        several windows; offsets: window b is the T5 frames that start at ELEMENT offsets[b] of the buffer (a multiple of 8;
+        windows may overlap and come from different recordings) -> logits (B,2) (afx_tail_forward_windows).  Window b's row
+        equals ``tail`` on those frames copied contiguous; a misaligned or out-of-range offset is an AfxError before
+        anything is launched."""
+        self._on_device(conv5, "conv-layer-5 activations")
+        if conv5.dtype != torch_dtype(self.dtype) or not conv5.is_contiguous() or conv5.shape[-1] != 512:
+            raise ValueError(f"expected a contiguous (..., 512) {self.dtype} buffer, got {tuple(conv5.shape)} {conv5.dtype}")
+        offs = [int(o) for o in offsets]
+        B = len(offs)
+        if B == 0:
+            return torch.empty(0, 2, dtype=torch.float32, device=self.device)
+        arr = (C.c_longlong * B)(*offs)
+        l = lib()
+        with torch.cuda.device(self.device):
+            ws = self._workspace(l.afx_tail_windows_workspace_bytes(self._h, B, T5))
+            out = torch.empty(B, 2, dtype=torch.float32, device=self.device)
+            check(l.afx_tail_forward_windows(self._h, ptr(conv5), conv5.numel(), arr, B, T5, ptr(out), ptr(ws), ws.numel(),
+                                             self._stream()))
+        return out
+
     def kv_state(self, n_streams):
         """Per-stream state of the KV-cached streaming mode (afx_kv_create): see ``KVState``."""
         return KVState(self, n_streams)

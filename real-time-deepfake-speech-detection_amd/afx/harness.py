@@ -281,6 +281,41 @@ def produce_evaluation_file_ragged(dataset, model, device, save_path, batch_size
     return names, scores
 
 
+def write_timeline_file(save_path, utt_ids, timelines):
+    """One line per window: ``"{utt_id} {start_s:.3f} {end_s:.3f} {score}"`` (the score as the reference's writer prints it)."""
+    d = os.path.dirname(save_path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(save_path, "w") as fh:
+        for f, tl in zip(utt_ids, timelines):
+            for (s, e), cm in zip(tl.times().tolist(), tl.scores.tolist()):
+                fh.write("{} {:.3f} {:.3f} {}\n".format(f, s, e, cm))
+
+
+def produce_timeline_file(dataset, model, device, save_path, window=64000, hop=4000, batch_size=8, num_workers=4,
+                          state_dict=None):
+    """Per-hop timelines of UN-CROPPED clips (afx.timeline.score_timeline): ``model`` is a drop-in ``models.*`` module, or an
+    afx Engine with the ``state_dict`` it was loaded from; ``batch_size`` clips per loader batch; one line per window in
+    dataset order (``write_timeline_file``).  The per-utterance writer (``produce_evaluation_file*``) is untouched."""
+    from torch.utils import data
+
+    from .timeline import score_timeline
+    if hasattr(model, "eval"):
+        model.eval()
+    dev = _as_device(device)
+    names, timelines = [], []
+    loader = data.DataLoader(dataset, batch_size=batch_size, shuffle=False, drop_last=False, num_workers=num_workers,
+                             collate_fn=ragged_collate)
+    with torch.no_grad():
+        for utt_id, clips, _label in loader:
+            timelines.extend(score_timeline(model, [torch.as_tensor(c).to(dev) for c in clips], window=window, hop=hop,
+                                            state_dict=state_dict))
+            names.extend(utt_id)
+    _check_finite(model)
+    write_timeline_file(save_path, names, timelines)
+    return names, timelines
+
+
 def evaluate(model, loader, device, loss_fn=None, preprocessor=None):
     """trainer.py:85-132: (mean loss, accuracy %) over a loader."""
     model.eval()

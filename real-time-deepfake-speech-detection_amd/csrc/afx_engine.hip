@@ -2369,6 +2369,71 @@ extern "C" int afx_tail_forward(afx_handle h, const void* conv5_h, int B, int T5
   return afx_tail_forward_strided(h, conv5_h, 0, B, T5, logits, ws, ws_bytes, stream);
 }
 
+// The tail over windows at arbitrary frame offsets of one shared layer-5 buffer (afx/timeline.py: the conv stack runs
+// once over a whole recording, the windows of many recordings overlap in one buffer).  A gather kernel packs the B
+// windows into the workspace -- a plain 16-byte copy -- and the packed tail above runs on them unchanged.  The offsets
+// travel as kernel arguments, kGatherMax per launch: nothing is uploaded and the call stays asynchronous.
+constexpr int kGatherMax = 64;
+struct GatherArgs {
+  const uint4* src;
+  uint4* dst;
+  long long n16;                // 16-byte vectors per window
+  long long off16[kGatherMax];  // window starts in the source, in 16-byte vectors
+};
+__global__ __launch_bounds__(256) void gather_windows_kernel(GatherArgs a) {
+  const int b = blockIdx.y;
+  const uint4* __restrict__ src = a.src + a.off16[b];
+  uint4* __restrict__ dst = a.dst + (long long)b * a.n16;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n16; i += (long long)gridDim.x * blockDim.x)
+    dst[i] = src[i];
+}
+static size_t packed_windows_bytes(const afx_engine* e, int B, int T5) {
+  return ((size_t)B * T5 * kC * dtype_size(e->dt) + 255) & ~(size_t)255;
+}
+extern "C" size_t afx_tail_windows_workspace_bytes(afx_handle h, int B, int T5) {
+  if (!h || B <= 0 || T5 <= 0) return 0;
+  Ws w;
+  return packed_windows_bytes(h, B, T5) + carve(h, B, 0, 0, nullptr, &w, T5);
+}
+extern "C" int afx_tail_forward_windows(afx_handle h, const void* conv5_h, long long total_elems, const long long* offs, int B,
+                                        int T5, float* logits, void* ws, size_t ws_bytes, void* stream) {
+  if (check_call(h, conv5_h, B, T5, logits, ws)) return 1;
+  if (!offs) return fail("afx_tail_forward_windows: null offsets");
+  if (h->cfg.arch == AFX_ARCH_SSL || h->cfg.arch == AFX_ARCH_CONFORMER_HEAD) return fail("afx_tail_forward_windows: this handle has no trunk + back-end");
+  if ((uintptr_t)conv5_h & 15) return fail("afx_tail_forward_windows: the layer-5 buffer must be 16-byte aligned");
+  if ((uintptr_t)ws & 15) return fail("afx_tail_forward_windows: the workspace must be 16-byte aligned");
+  const long long win = (long long)T5 * kC;
+  for (int b = 0; b < B; ++b) {
+    if (offs[b] < 0 || offs[b] % 8)
+      return fail("afx_tail_forward_windows: offset %lld of window %d is not a non-negative multiple of 8 elements", offs[b], b);
+    if (offs[b] > total_elems - win)
+      return fail("afx_tail_forward_windows: window %d (%lld + %lld elements) reaches past the buffer's %lld", b, offs[b], win,
+                  total_elems);
+  }
+  const size_t hs = dtype_size(h->dt), packed = packed_windows_bytes(h, B, T5);
+  Ws w;
+  const size_t needb = packed + carve(h, B, 0, 0, (char*)ws + packed, &w, T5);
+  if (ws_bytes < needb) return fail("afx_tail_forward_windows: workspace too small (%zu < %zu bytes)", ws_bytes, needb);
+  if (w.T[6] < 1) return fail("afx_tail_forward_windows: %d conv-layer-5 frames are too few for one output frame", T5);
+  hipStream_t s = (hipStream_t)stream;
+  GatherArgs g;
+  g.src = (const uint4*)conv5_h;
+  g.n16 = win * (long long)hs / 16;
+  const long long per_row = (g.n16 + 255) / 256;
+  for (int b0 = 0; b0 < B; b0 += kGatherMax) {
+    const int nb = B - b0 < kGatherMax ? B - b0 : kGatherMax;
+    for (int i = 0; i < nb; ++i) g.off16[i] = offs[b0 + i] * (long long)hs / 16;
+    g.dst = (uint4*)ws + (long long)b0 * g.n16;
+    // about 2048 workgroups per launch whatever the batch: a few per CU, each lane a handful of 16-byte copies
+    const long long gx = std::max(1LL, std::min(per_row, 2048LL / nb));
+    hipLaunchKernelGGL(gather_windows_kernel, dim3((unsigned)gx, nb), dim3(256), 0, s, g);
+    HIP_OK(hipGetLastError());
+  }
+  begin_call(h, &w);
+  if (run_trunk(h, nullptr, B, 0, w, s, ws, 0)) return 1;
+  return run_head(h, B, w.T[6], w, logits, s);
+}
+
 // ---------------------------------------------------------------------------------
 // ragged batches: clips of different lengths in ONE forward, each scored exactly as if alone.
 // The conv stack is local and unpadded, so frame t of a clip depends on its first 400 + 320 t samples only: a clip
