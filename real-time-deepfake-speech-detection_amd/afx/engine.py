@@ -509,6 +509,17 @@ class Engine:
         self._taps = bool(on)
 
     def tap(self, name):
+        """fp32 copy of an intermediate of the last forward run with taps on (``enable_taps``), flat, in the buffer's own
+        row layout.  Operand buffers come back as the values their consumer reads (split precision: pair-form rows
+        decoded to (hi + lo) / scale).  Names:
+          trunk   c0 .. c5 (conv layers' operand outputs), conv (layer 6, fp32), feats (feature LayerNorm), proj, xpad
+                  (time-padded operand rows, pad rows included), pos, then per layer l: l{l}.ln1, l{l}.qkv, l{l}.att,
+                  l{l}.mid (x after the out-projection), l{l}.ln2, l{l}.ff, layer{l}; ssl (final LayerNorm, fp32)
+          head    tokens, then per block b: b{b}.xa, b{b}.qkv (after chain A / FF1 + QKV), b{b}.ao (attention output,
+                  padded rows), b{b}.xb, b{b}.glu (after chain B), b{b}.u (depthwise conv output, padded rows), block{b};
+                  the per-op path (``set("fuse_conformer", 0)``) also b{b}.{ff1,attn,conv,ff2}.hc (LayerNorm outputs),
+                  b{b}.{ff1,ff2}.hid (FF hidden), b{b}.xc (after the conv module), b{b}.xd (after FF2)
+          AASIST  e_S, e_T, hidden and the back-end's module taps"""
         n = C.c_size_t(0)
         with torch.cuda.device(self.device):
             check(lib().afx_tap(self._h, name.encode(), None, 0, C.byref(n), self._stream()))

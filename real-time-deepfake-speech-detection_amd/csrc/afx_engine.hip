@@ -764,6 +764,7 @@ extern "C" size_t afx_workspace_bytes(afx_handle h, int B, int L) {
   return carve(h, B, L, 0, nullptr, &w);
 }
 
+static float s3_pairs_in(const void* p);
 // ---------------------------------------------------------------------------------
 // taps (debug): engine-owned fp32 copies of intermediates
 // ---------------------------------------------------------------------------------
@@ -778,7 +779,21 @@ __global__ void half_to_f32_kernel(const uint16_t* in, float* out, size_t n, int
     }
   }
 }
-static int tap(afx_engine* e, const char* name, const void* src, size_t n, bool is_half, hipStream_t s) {
+// split precision: a buffer of pair-form rows (row stride ld fp32 elements) -> the fp32 values its consumer reads,
+// (hi + lo) / scale per element (afx_kernels.h::s3_pair_index), in the buffer's own row layout
+__global__ void pairs_to_f32_kernel(const uint16_t* in, float* out, size_t n, long ld, float inv_scale) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t r = i / ld;
+    const long k = (long)(i - r * ld);
+    const uint16_t* row = in + r * 2 * ld;
+    _Float16 hi, lo;
+    memcpy(&hi, &row[s3_pair_index(k)], 2);
+    memcpy(&lo, &row[s3_pair_index(k) + 32], 2);
+    out[i] = ((float)hi + (float)lo) * inv_scale;
+  }
+}
+// is_half: `src` is an operand buffer (operand type; split precision: fp32 rows or pair-form rows of stride ld elements)
+static int tap(afx_engine* e, const char* name, const void* src, size_t n, bool is_half, hipStream_t s, long ld = 0) {
   if (!e->taps_on) return 0;
   TapRec& t = e->taps[name];
   if (t.cap < n) {
@@ -787,7 +802,12 @@ static int tap(afx_engine* e, const char* name, const void* src, size_t n, bool 
     t.cap = n;
   }
   t.n = n;
-  if (is_half && e->dt != AFX_DT_FP32) {
+  const float pair_scale = is_half && e->s3 ? s3_pairs_in(src) : 0.f;
+  if (pair_scale != 0.f) {
+    if (ld <= 0 || ld % 32 || n % ld) return fail("tap '%s': pair-form rows need a row stride that is a multiple of 32", name);
+    hipLaunchKernelGGL(pairs_to_f32_kernel, dim3(1024), dim3(256), 0, s, (const uint16_t*)src, t.p, n, ld, 1.0f / pair_scale);
+    HIP_OK(hipGetLastError());
+  } else if (is_half && e->dt != AFX_DT_FP32) {
     hipLaunchKernelGGL(half_to_f32_kernel, dim3(1024), dim3(256), 0, s, (const uint16_t*)src, t.p, n,
                        e->dt == AFX_DT_BF16 ? 1 : 0);
     HIP_OK(hipGetLastError());
@@ -1032,6 +1052,11 @@ static RowNormArgs plain_norm(const float* x, long ldx, int rows, int C, const f
 
 #define launch_gemm P_gemm
 #define launch_rownorm P_rownorm
+// debug tap at a launch boundary (the name is only built while taps are on): op = an operand buffer of row stride ld
+#define TAP(nm, p, n, op, ld)                                                               \
+  do {                                                                                      \
+    if (e->taps_on && tap(e, std::string(nm).c_str(), (p), (n), (op), s, (ld))) return 1; \
+  } while (0)
 
 // l5: null = start from the waveform; else the output of conv layer 5, (B, T[5], 512) operand type (tail mode)
 // l5_batch: elements between two utterances of l5 (0 = packed, T[5] * 512): a streaming caller keeps its window inside a longer ring
@@ -1063,6 +1088,7 @@ static int run_trunk(afx_engine* e, const float* wave, int B, int L, Ws& w, hipS
       return launch_conv0(wave, B, L, T[0], cf(0, ".0.weight"), cf(0, ".0.bias"), cf(0, ".2.1.weight"),
                           cf(0, ".2.1.bias"), e->cfg.pre_emphasis, e->cfg.pre_emphasis_coef, w.bufA, dt, s, e->conv0pack);
     }));
+  if (!l5) TAP("c0", w.bufA, (size_t)B * T[0] * kC, true, kC);
   // layers 1..6: conv-as-GEMM on a row-complete tile, LayerNorm(512) + GELU fused into the
   // epilogue (the pre-norm fp32 activations never leave the registers)
   void* in = l5 ? const_cast<void*>(l5) : w.bufA;
@@ -1105,6 +1131,7 @@ static int run_trunk(afx_engine* e, const float* wave, int B, int L, Ws& w, hipS
       }
       KOK(launch_rownorm(n, dt, s));
     }
+    if (i < 6) TAP("c" + std::to_string(i), out, (size_t)M * kC, true, kC);
     void* t = in; in = out; out = t;
   }
   const int Tt = T[6], M = B * Tt;
@@ -1115,6 +1142,7 @@ static int run_trunk(afx_engine* e, const float* wave, int B, int L, Ws& w, hipS
     n.out_h = w.feats_h; n.ldo_h = kC;
     KOK(launch_rownorm(n, dt, s));
   }
+  TAP("feats", w.feats_h, (size_t)M * kC, true, kC);
   // post_extract_proj: fp32 residual stream x + operand copy into the time-padded buffer
   {
     GemmArgs g = plain_gemm(w.feats_h, kC, e->projw, kC, M, kD, kC);
@@ -1127,6 +1155,7 @@ static int run_trunk(afx_engine* e, const float* wave, int B, int L, Ws& w, hipS
     // see zero padding there)
     KOK(timed(PC_MISC, 0, s, [&] { return launch_zero_pad_rows(w.xpad, B, Tt, kD, kPosPad, kPosK - kPosPad, dt, s, w.lens); }));
   }
+  TAP("xpad", w.xpad, (size_t)B * (Tt + kPosK) * kD, true, kD);
   if (tap(e, "proj", w.x, (size_t)M * kD, false, s)) return 1;
   // positional conv (grouped, k=128) + GELU, added to x in place
   if (e->posconv_sliding && dt != DT_FP32 && Tt <= 224) {  // (reads the zero-padded operand copy: ragged batches need nothing more)
@@ -1159,10 +1188,13 @@ static int run_trunk(afx_engine* e, const float* wave, int B, int L, Ws& w, hipS
     RowNormArgs n1 = plain_norm(w.x, kD, M, kD, e->F(P + "self_attn_layer_norm.weight"), e->F(P + "self_attn_layer_norm.bias"));
     n1.out_h = w.hbuf; n1.ldo_h = kD;
     KOK(launch_rownorm(n1, dt, s));
+    const std::string lp = "l" + std::to_string(l) + ".";
+    TAP(lp + "ln1", w.hbuf, (size_t)M * kD, true, kD);
     GemmArgs q = plain_gemm(w.hbuf, kD, e->wqkv[l], kD, M, 3 * kD, kD);
     q.bias = e->bqkv[l];
     q.out_h = w.qkv; q.ldo_h = 3 * kD;
     KOK(launch_gemm(q, dt, 1, s));
+    TAP(lp + "qkv", w.qkv, (size_t)M * 3 * kD, true, 3 * kD);
     KOK(timed(PC_MHSA, 4.0 * B * kH * (double)Tt * Tt * 64, s, [&] {
       if (e->s3 && Tt <= 224) {  // split precision: the matrix-core form; its output goes out as the output projection's A planes
         const bool pairs = s3_ok(w.att);
@@ -1172,14 +1204,18 @@ static int run_trunk(afx_engine* e, const float* wave, int B, int L, Ws& w, hipS
       if (e->s3) s3_set(w.att, 0.f);
       return launch_mhsa(w.qkv, w.att, B, Tt, kH, dt, s, w.lens);
     }));
+    TAP(lp + "att", w.att, (size_t)M * kD, true, kD);
     KOK(resid_product(w.att, kD, e->wo[l], kD, e->F(P + "self_attn.out_proj.bias")));
+    TAP(lp + "mid", w.x, (size_t)M * kD, false, kD);
     RowNormArgs n2 = plain_norm(w.x, kD, M, kD, e->F(P + "final_layer_norm.weight"), e->F(P + "final_layer_norm.bias"));
     n2.out_h = w.hbuf; n2.ldo_h = kD;
     KOK(launch_rownorm(n2, dt, s));
+    TAP(lp + "ln2", w.hbuf, (size_t)M * kD, true, kD);
     GemmArgs f1 = plain_gemm(w.hbuf, kD, e->w1[l], kD, M, kF, kD);
     f1.bias = e->F(P + "fc1.bias"); f1.act = ACT_GELU;
     f1.out_h = w.ff; f1.ldo_h = kF;
     KOK(launch_gemm(f1, dt, 1, s));
+    TAP(lp + "ff", w.ff, (size_t)M * kF, true, kF);
     KOK(resid_product(w.ff, kF, e->w2[l], kF, e->F(P + "fc2.bias")));
     if (e->taps_on) {
       const std::string nm = "layer" + std::to_string(l);
@@ -1242,6 +1278,9 @@ static int run_conformer(afx_engine* e, int B, int T, Ws& w, float* logits, hipS
     c.w_a = K.wqkv; c.ld_w_a = Ep;
     c.out2 = w.qkv32; c.ld_out2 = 3 * e->inner;
     KOK(timed(PC_CONF_CHAIN, ff_fl + 2.0 * M * E * 3 * e->inner, s, [&] { return launch_conf_chain(c, 0, chain_dt, s); }));
+    const std::string bp = "b" + std::to_string(b) + ".";
+    TAP(bp + "xa", w.xc, (size_t)M * E, false, E);
+    TAP(bp + "qkv", w.qkv32, (size_t)M * 3 * e->inner, false, 3 * e->inner);
     KOK(timed(PC_CONF_ATTN, 6.0 * B * e->heads * (double)N * N * e->dh, s, [&] {
       if (e->conf_attn_mfma && dt != DT_FP32 && e->dh == 36)
         return launch_conf_attn_mfma(w.qkv32, 3 * e->inner, w.qkv32 + e->inner, 3 * e->inner, K.rel_h, 512, B, N, e->heads,
@@ -1252,17 +1291,21 @@ static int run_conformer(afx_engine* e, int B, int T, Ws& w, float* logits, hipS
       return launch_conf_attn(w.qkv32, 3 * e->inner, w.qkv32 + e->inner, 3 * e->inner,
                               e->F(P + "attn.fn.rel_pos_emb.weight"), 512, B, N, e->heads, e->dh, w.ao, Ep, dt, s, w.lens, 1);
     }));
+    TAP(bp + "ao", w.ao, (size_t)M * Ep, true, Ep);
     c.in_h = w.ao; c.ld_in_h = Ep;
     c.params = K.chain_prm[1];
     c.w_a = K.wout;
     c.w_b = K.pw1;
     c.out2 = w.glu32; c.ld_out2 = 2 * e->C2;
     KOK(timed(PC_CONF_CHAIN, 2.0 * M * E * (e->inner + 2 * e->C2), s, [&] { return launch_conf_chain(c, 1, chain_dt, s); }));
+    TAP(bp + "xb", w.xc, (size_t)M * E, false, E);
+    TAP(bp + "glu", w.glu32, (size_t)M * 2 * e->C2, false, 2 * e->C2);
     KOK(timed(PC_CONF_DWCONV, 2.0 * B * N * e->C2 * e->ck, s, [&] {
       return launch_conf_dwconv(w.glu32, 2 * e->C2, e->F(P + "conv.net.4.conv.weight"),
                                 e->F(P + "conv.net.4.conv.bias"), K.bn_scale, K.bn_shift, B, N, e->C2, e->ck, w.u,
                                 e->C2p, dt, s, w.lens, 1);
     }));
+    TAP(bp + "u", w.u, (size_t)M * e->C2p, true, e->C2p);
     c.in_h = w.u; c.ld_in_h = e->C2p;
     c.params = K.chain_prm[2];
     c.w_a = K.pw2; c.ld_w_a = e->C2p;
@@ -1277,31 +1320,38 @@ static int run_conformer(afx_engine* e, int B, int T, Ws& w, float* logits, hipS
   for (int b = 0; !fused && b < e->nblk; ++b) {
     const std::string P = "conformer.encoder_blocks." + std::to_string(b) + ".";
     ConfBlock& K = e->blk[b];
+    const std::string bp = "b" + std::to_string(b) + ".";
     auto norm_to_h = [&](const char* nm) -> const char* {
       RowNormArgs n = plain_norm(w.xc, E, M, E, e->F(P + nm + ".weight"), e->F(P + nm + ".bias"));
       n.out_h = w.hc; n.ldo_h = Ep;
       return launch_rownorm(n, dt, s);
     };
-    auto feed_forward = [&](const char* ff, void* w1, void* w2) -> const char* {
-      if (const char* m = norm_to_h((std::string(ff) + ".fn.norm").c_str())) return m;
+    auto feed_forward = [&](const char* ff, void* w1, void* w2) -> int {
+      KOK(norm_to_h((std::string(ff) + ".fn.norm").c_str()));
+      TAP(bp + ff + ".hc", w.hc, (size_t)M * Ep, true, Ep);
       GemmArgs a = plain_gemm(w.hc, Ep, w1, Ep, M, e->FF, Ep);
       a.k_algo = E;
       a.bias = e->F(P + ff + ".fn.fn.net.0.bias"); a.act = ACT_SWISH;
       a.out_h = w.hid; a.ldo_h = e->FFp;
-      if (const char* m = launch_gemm(a, dt, 1, s)) return m;
+      KOK(launch_gemm(a, dt, 1, s));
+      TAP(bp + ff + ".hid", w.hid, (size_t)M * e->FFp, true, e->FFp);
       GemmArgs c = plain_gemm(w.hid, e->FFp, w2, e->FFp, M, E, e->FFp);
       c.k_algo = e->FF;
       c.bias = e->F(P + ff + ".fn.fn.net.3.bias"); c.alpha = 0.5f;
       c.resid = w.xc; c.ldr = E; c.out_f = w.xc; c.ldo_f = E;
-      return launch_gemm(c, dt, 1, s);
+      KOK(launch_gemm(c, dt, 1, s));
+      return 0;
     };
-    KOK(feed_forward("ff1", K.ff1_w1, K.ff1_w2));
+    if (feed_forward("ff1", K.ff1_w1, K.ff1_w2)) return 1;
+    TAP(bp + "xa", w.xc, (size_t)M * E, false, E);
     // attention
     KOK(norm_to_h("attn.norm"));
+    TAP(bp + "attn.hc", w.hc, (size_t)M * Ep, true, Ep);
     GemmArgs q = plain_gemm(w.hc, Ep, K.wqkv, Ep, M, 3 * e->inner, Ep);
     q.k_algo = E;
     q.out_f = w.qkv32; q.ldo_f = 3 * e->inner;
     KOK(launch_gemm(q, dt, 1, s));
+    TAP(bp + "qkv", w.qkv32, (size_t)M * 3 * e->inner, false, 3 * e->inner);
     KOK(timed(PC_CONF_ATTN, 6.0 * B * e->heads * (double)N * N * e->dh, s, [&] {
       if (e->conf_attn_mfma && dt != DT_FP32 && e->dh == 36)
         return launch_conf_attn_mfma(w.qkv32, 3 * e->inner, w.qkv32 + e->inner, 3 * e->inner, K.rel_h, 512, B, N, e->heads,
@@ -1312,29 +1362,36 @@ static int run_conformer(afx_engine* e, int B, int T, Ws& w, float* logits, hipS
       return launch_conf_attn(w.qkv32, 3 * e->inner, w.qkv32 + e->inner, 3 * e->inner,
                               e->F(P + "attn.fn.rel_pos_emb.weight"), 512, B, N, e->heads, e->dh, w.ao, Ep, dt, s, w.lens, 1);
     }));
+    TAP(bp + "ao", w.ao, (size_t)M * Ep, true, Ep);
     GemmArgs o = plain_gemm(w.ao, Ep, K.wout, Ep, M, E, Ep);
     o.k_algo = e->inner;
     o.bias = e->F(P + "attn.fn.to_out.bias");
     o.resid = w.xc; o.ldr = E; o.out_f = w.xc; o.ldo_f = E;
     KOK(launch_gemm(o, dt, 1, s));
+    TAP(bp + "xb", w.xc, (size_t)M * E, false, E);
     // conv module
     KOK(norm_to_h("conv.net.0"));
+    TAP(bp + "conv.hc", w.hc, (size_t)M * Ep, true, Ep);
     GemmArgs p1 = plain_gemm(w.hc, Ep, K.pw1, Ep, M, 2 * e->C2, Ep);
     p1.k_algo = E;
     p1.bias = e->F(P + "conv.net.2.bias");
     p1.out_f = w.glu32; p1.ldo_f = 2 * e->C2;
     KOK(launch_gemm(p1, dt, 1, s));
+    TAP(bp + "glu", w.glu32, (size_t)M * 2 * e->C2, false, 2 * e->C2);
     KOK(timed(PC_CONF_DWCONV, 2.0 * B * N * e->C2 * e->ck, s, [&] {
       return launch_conf_dwconv(w.glu32, 2 * e->C2, e->F(P + "conv.net.4.conv.weight"),
                                 e->F(P + "conv.net.4.conv.bias"), K.bn_scale, K.bn_shift, B, N, e->C2, e->ck, w.u,
                                 e->C2p, dt, s, w.lens, 1);
     }));
+    TAP(bp + "u", w.u, (size_t)M * e->C2p, true, e->C2p);
     GemmArgs p2 = plain_gemm(w.u, e->C2p, K.pw2, e->C2p, M, E, e->C2p);
     p2.k_algo = e->C2;
     p2.bias = e->F(P + "conv.net.7.bias");
     p2.resid = w.xc; p2.ldr = E; p2.out_f = w.xc; p2.ldo_f = E;
     KOK(launch_gemm(p2, dt, 1, s));
-    KOK(feed_forward("ff2", K.ff2_w1, K.ff2_w2));
+    TAP(bp + "xc", w.xc, (size_t)M * E, false, E);
+    if (feed_forward("ff2", K.ff2_w1, K.ff2_w2)) return 1;
+    TAP(bp + "xd", w.xc, (size_t)M * E, false, E);
     RowNormArgs pn = plain_norm(w.xc, E, M, E, e->F(P + "post_norm.weight"), e->F(P + "post_norm.bias"));
     pn.out_f = w.xc; pn.ldo_f = E;
     KOK(launch_rownorm(pn, dt, s));
