@@ -282,6 +282,26 @@ int afx_k_resample(const float* x, const long long* in_offs, const long long* ou
  * whole stream resampled by afx_k_resample.  Rows of slots not named are untouched. */
 int afx_k_resample_stream(const float* x, int A, int n_in, float* hist, const int* slot, const float* taps, int L, int M,
                           int T, float* out, void* stream);
+/* Packet ingest (afx/ingest.py): bytes as a service receives them -> each slot's 16 kHz pending ring, in one launch for
+ * all packets of a feed.  stage (device, stage_bytes): the encoded payloads; hdr (device, rows x 8 int32), per row:
+ *     slot, byte offset of the row's first sample in stage (a multiple of the sample size), n_in samples, n_out outputs,
+ *     p0 = n_done*M mod L, d0 = floor(n_done*M/L) - N, wpos (where the ring takes the first output), 0
+ * for a slot that had received N input samples and made n_done = ceil(N*L/M) outputs; n_out = ceil((N+n_in)*L/M) - n_done
+ * (the host reduces these from its int64 counters; slots of one call are distinct).  encoding 0 pcm_f32le, 1 pcm_s16le
+ * (v / 32768), 2 G.711 mu-law, 3 G.711 A-law (ITU-T G.711 to the 16-bit linear value, / 32768): exact in fp32.  Output k
+ * of a row is output n_done + k of afx_k_resample over the slot's whole decoded stream,
+ *     y = sum_{j<T} taps[p][j] * v[i - j],  i = d0 + floor((k*M + p0)/L),  p = (k*M + p0) mod L,
+ * v = the decoded packet, and hist[slot] (S, T-1: the stream's T-1 samples before the packet, zeros for a new stream)
+ * at negative positions -- the same inputs, fp32 taps and ascending-j fma chain, so the bits do not depend on where the
+ * stream was cut.  It is written to ring[slot][(wpos + k) mod ring_len] (ring (S, ring_len) fp32; max_out = the largest
+ * n_out <= ring_len), then hist[slot] takes the last T-1 samples of hist[slot] ++ the decoded packet (rows with n_out = 0
+ * included).  taps NULL with L = M = T = 1: the identity, sample k decoded into the ring, no history.  A row whose header
+ * would leave stage, hist or ring is skipped whole.  M/L <= 12, T - 1 <= 256. */
+int afx_k_ingest(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_out, int encoding,
+                 const float* taps, int L, int M, int T, float* hist, float* ring, int S, int ring_len, void* stream);
+/* out (A, hop) fp32: out[i][k] = ring[slot_i][(head_i + k) mod ring_len], table (device, A x 2 int32) = (slot_i, head_i):
+ * the next hop of the named slots as the streaming scorers' push takes it.  The ring is only read. */
+int afx_k_ingest_pop(const float* ring, int S, int ring_len, const int* table, int A, int hop, float* out, void* stream);
 int afx_k_rownorm(int dtype, const float* x, long ldx, int rows, int C, const float* gamma, const float* beta,
                   float eps, int act, float* out_f, long ldo_f, void* out_h, long ldo_h, void* stream);
 int afx_k_mhsa(int dtype, const void* qkv, void* out, int B, int T, int H, void* stream);

@@ -2864,6 +2864,16 @@ extern "C" int afx_k_resample_stream(const float* x, int A, int n_in, float* his
                                      int L, int M, int T, float* out, void* stream) {
   KRET(launch_resample_stream(x, A, n_in, hist, slot, taps, L, M, T, out, (hipStream_t)stream));
 }
+extern "C" int afx_k_ingest(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_out, int encoding,
+                            const float* taps, int L, int M, int T, float* hist, float* ring, int S, int ring_len,
+                            void* stream) {
+  KRET(launch_ingest(stage, stage_bytes, hdr, rows, max_out, encoding, taps, L, M, T, hist, ring, S, ring_len,
+                     (hipStream_t)stream));
+}
+extern "C" int afx_k_ingest_pop(const float* ring, int S, int ring_len, const int* table, int A, int hop, float* out,
+                                void* stream) {
+  KRET(launch_ingest_pop(ring, S, ring_len, table, A, hop, out, (hipStream_t)stream));
+}
 extern "C" int afx_k_rownorm(int dtype, const float* x, long ldx, int rows, int C, const float* gamma,
                              const float* beta, float eps, int act, float* out_f, long ldo_f, void* out_h, long ldo_h,
                              void* stream) {

@@ -772,6 +772,195 @@ const char* launch_resample_stream(const float* x, int A, int n_in, float* hist,
 }
 
 // ---------------------------------------------------------------------------------
+// Packet ingest (afx/ingest.py; the function is stated in include/afx.h afx_k_ingest / afx_k_ingest_pop): each row is the
+// next n_in encoded samples of one slot's stream, of any length, starting at any filter phase.  The row's header carries
+// what the host reduced from the stream's absolute counters (N input samples received, n_done = ceil(N*L/M) outputs
+// made): p0 = n_done*M mod L and d0 = floor(n_done*M/L) - N >= 0, the position of output n_done's newest input from the
+// packet's first sample.  Output k of the row is output n_done + k of the stream:
+//     y = sum_{j<T} taps[p][j] * v[i - j],   i = d0 + floor((k*M + p0)/L),  p = (k*M + p0) mod L
+// with v = the packet decoded, and hist[slot] (the stream's T-1 samples before the packet) at negative positions: the
+// inputs, taps and order resample_kernel gives that output over the whole stream, so the bits are the same however the
+// stream was cut.  The outputs go into the slot's pending ring from wpos on (wrapping at ring_len); a second kernel then
+// makes hist[slot] the last T-1 decoded samples of hist ++ packet, as resample_hist_kernel does.  taps == nullptr: the
+// identity (16 kHz input), sample k decoded straight into the ring.  Same tiling and LDS staging as resample_kernel.
+// ---------------------------------------------------------------------------------
+constexpr int ING_HDR = 8;  // ints per row: slot, byte offset of the first sample, n_in, n_out, p0, d0, wpos, 0
+
+struct IngestArgs {
+  const unsigned char* stage;    // encoded payloads (each row's first sample at its header's byte offset)
+  long long stage_bytes;
+  const int* hdr;                // (rows, ING_HDR)
+  const float* taps;             // (L, T), nullptr = identity
+  float* hist;                   // (S, T - 1)
+  float* ring;                   // (S, ring_len)
+  int enc, L, M, T, Tp, R, S, ring_len;
+};
+
+// sample k of an encoded payload as fp32 (exact: 16-bit linear value / 32768; ITU-T G.711 expansion)
+__device__ __forceinline__ float ingest_sample(const unsigned char* p, int k, int enc) {
+  if (enc == 0) return ((const float*)p)[k];
+  int v;
+  if (enc == 1) {
+    v = ((const short*)p)[k];
+  } else if (enc == 2) {
+    const int u = ~(int)p[k] & 0xFF;
+    v = ((((u & 15) << 3) + 132) << ((u >> 4) & 7)) - 132;
+    if (u & 0x80) v = -v;
+  } else {
+    const int a = (int)p[k] ^ 0x55, e = (a >> 4) & 7, m = (a & 15) << 4;
+    v = e ? (m + 264) << (e - 1) : m + 8;
+    if (!(a & 0x80)) v = -v;
+  }
+  return (float)v * (1.0f / 32768.0f);
+}
+
+__device__ __forceinline__ int ingest_bytes_per_sample(int enc) { return enc == 0 ? 4 : enc == 1 ? 2 : 1; }
+
+// the row's header, or false for a row that would leave its buffers (the host plans every field; nothing is written then)
+__device__ __forceinline__ bool ingest_row(const IngestArgs& a, int row, int& slot, const unsigned char*& pay, int& n_in,
+                                           int& n_out, int& p0, int& d0, int& wpos) {
+  const int* h = a.hdr + (long long)row * ING_HDR;
+  slot = h[0]; n_in = h[2]; n_out = h[3]; p0 = h[4]; d0 = h[5]; wpos = h[6];
+  const long long off = h[1];
+  pay = a.stage + off;
+  const int bps = ingest_bytes_per_sample(a.enc);
+  return slot >= 0 && slot < a.S && n_in >= 0 && n_out >= 0 && n_out <= a.ring_len && wpos >= 0 && wpos < a.ring_len &&
+         p0 >= 0 && p0 < a.L && d0 >= 0 && off >= 0 && (off & (bps - 1)) == 0 && off + (long long)n_in * bps <= a.stage_bytes;
+}
+
+template <bool IDENT, bool LDS_TAPS>
+__global__ __launch_bounds__(256) void ingest_kernel(IngestArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float ing_lds[];
+  int slot, n_in, n_out, p0r, d0, wpos;
+  const unsigned char* pay;
+  if (!ingest_row(a, blockIdx.y, slot, pay, n_in, n_out, p0r, d0, wpos)) return;
+  float* out = a.ring + (long long)slot * a.ring_len;
+  if (IDENT) {
+    for (int r = 0; r < a.R; ++r) {
+      const int k = (blockIdx.x * a.R + r) * RS_TILE + threadIdx.x;
+      if (k >= n_out || k >= n_in) break;
+      const int w = wpos + k;
+      out[w < a.ring_len ? w : w - a.ring_len] = ingest_sample(pay, k, a.enc);
+    }
+    return;
+  }
+  const int T = a.T;
+  if ((long long)blockIdx.x * a.R * RS_TILE >= n_out) return;
+  const float* hrow = a.hist + (long long)slot * (T - 1);
+  const float* tp = a.taps;
+  int ts = T;
+  float* xs = ing_lds;
+  if (LDS_TAPS) {
+    for (int k = threadIdx.x; k < a.L * a.Tp; k += blockDim.x) {
+      const int p = k / a.Tp, j = k - p * a.Tp;
+      ing_lds[k] = j < T ? a.taps[p * T + j] : 0.f;
+    }
+    tp = ing_lds;
+    ts = a.Tp;
+    xs = ing_lds + a.L * a.Tp;
+  }
+  for (int r = 0; r < a.R; ++r) {
+    const int n0 = (blockIdx.x * a.R + r) * RS_TILE;
+    if (n0 >= n_out) break;
+    const int cnt = min(RS_TILE, n_out - n0);
+    const long long q0 = (long long)n0 * a.M + p0r, b0 = q0 / a.L;
+    const int p0 = (int)(q0 - b0 * a.L);
+    const int base = d0 + (int)b0;  // the packet position of output n0's newest input
+    const int span = (int)(((long long)(cnt - 1) * a.M + p0) / a.L) + T;
+    __syncthreads();  // the previous sub-tile is done with xs
+    for (int s = threadIdx.x; s < span; s += blockDim.x) {
+      const int k = base - (T - 1) + s;  // >= -(T-1); < n_in for every output the host counted
+      xs[s] = k >= 0 ? (k < n_in ? ingest_sample(pay, k, a.enc) : 0.f) : hrow[T - 1 + k];
+    }
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < cnt) {
+      const unsigned q = (unsigned)t * (unsigned)a.M + (unsigned)p0;
+      const int di = (int)(q / (unsigned)a.L), p = (int)(q - (unsigned)di * (unsigned)a.L);
+      const float* w = tp + (long)p * ts;
+      const float* xv = xs + di + T - 1;
+      float acc = 0.f;
+      for (int j = 0; j < T; ++j) acc = __builtin_fmaf(w[j], xv[-j], acc);
+      const int wp = wpos + n0 + t;
+      out[wp < a.ring_len ? wp : wp - a.ring_len] = acc;
+    }
+  }
+}
+
+// the carried samples of each row's slot after its packet: the last T-1 of hist[slot] ++ decoded packet.  One workgroup
+// per row (the slots of a launch are distinct): every lane reads its new value before any lane writes.
+__global__ __launch_bounds__(256) void ingest_hist_kernel(IngestArgs a) {
+  int slot, n_in, n_out, p0, d0, wpos;
+  const unsigned char* pay;
+  if (!ingest_row(a, blockIdx.x, slot, pay, n_in, n_out, p0, d0, wpos)) return;
+  const int H = a.T - 1, k = threadIdx.x;
+  float* h = a.hist + (long long)slot * H;
+  float v = 0.f;
+  if (k < H) v = (long long)k + n_in < H ? h[k + n_in] : ingest_sample(pay, k + n_in - H, a.enc);
+  __syncthreads();
+  if (k < H) h[k] = v;
+}
+
+const char* launch_ingest(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_out, int enc,
+                          const float* taps, int L, int M, int T, float* hist, float* ring, int S, int ring_len,
+                          hipStream_t s) {
+  if (!stage || !hdr || !ring || stage_bytes <= 0) return "ingest: null staging buffer, header table or ring";
+  if (enc < 0 || enc > 3) return "ingest: encoding 0 (pcm_f32le), 1 (pcm_s16le), 2 (mulaw) or 3 (alaw)";
+  if (rows <= 0 || rows > 65535) return "ingest: 1 to 65535 rows";
+  if (S <= 0 || ring_len <= 0 || max_out < 0 || max_out > ring_len) return "ingest: a row's outputs must fit its slot's ring";
+  if (L <= 0 || M <= 0 || T <= 0) return "ingest: bad filter shape";
+  const bool ident = taps == nullptr;
+  if (ident && (L != 1 || M != 1 || T != 1)) return "ingest: no taps is the identity (L = M = T = 1)";
+  if (!ident && T > 1 && !hist) return "ingest: null history";
+  if (T - 1 > 256) return "ingest: more than 256 carried samples";
+  IngestArgs a{};
+  a.stage = (const unsigned char*)stage; a.stage_bytes = stage_bytes; a.hdr = hdr; a.taps = taps; a.hist = hist; a.ring = ring;
+  a.enc = enc; a.L = L; a.M = M; a.T = T; a.S = S; a.ring_len = ring_len;
+  a.Tp = T | 1;
+  a.R = 1;
+  if (max_out > 0) {
+    const long long span = (255LL * M + L - 1) / L + T;
+    if (span > RS_SPAN_MAX) return "ingest: input / output ratio above 12";
+    const bool lds_taps = !ident && (long long)L * a.Tp <= RS_TAPS_LDS;
+    if (lds_taps) a.R = max(1, min(8, L * a.Tp / 1024));  // amortise the tap staging of many-phase ratios
+    const dim3 grid((unsigned)((max_out + RS_TILE * a.R - 1) / (RS_TILE * a.R)), rows);
+    const size_t lds = ident ? 0 : sizeof(float) * (size_t)((lds_taps ? L * a.Tp : 0) + span);
+    if (ident) hipLaunchKernelGGL((ingest_kernel<true, false>), grid, dim3(256), lds, s, a);
+    else if (lds_taps) hipLaunchKernelGGL((ingest_kernel<false, true>), grid, dim3(256), lds, s, a);
+    else hipLaunchKernelGGL((ingest_kernel<false, false>), grid, dim3(256), lds, s, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hipGetErrorString(e);
+  }
+  if (T == 1) return nullptr;
+  hipLaunchKernelGGL(ingest_hist_kernel, dim3(rows), dim3(256), 0, s, a);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+// the first `hop` pending samples of the named slots: out[i][k] = ring[slot_i][(head_i + k) mod ring_len], table (A, 2)
+// int32 = (slot_i, head_i).  The ring is only read: head and fill are the host's.
+__global__ __launch_bounds__(256) void ingest_pop_kernel(const float* __restrict__ ring, int S, int ring_len,
+                                                         const int* __restrict__ table, int hop, float* __restrict__ out) {
+  const int row = blockIdx.y, slot = table[2 * row], head = table[2 * row + 1];
+  const bool ok = slot >= 0 && slot < S && head >= 0 && head < ring_len;
+  const float* src = ring + (long long)(ok ? slot : 0) * ring_len;
+  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < hop; k += gridDim.x * blockDim.x) {
+    const int w = head + k;
+    out[(long long)row * hop + k] = ok ? src[w < ring_len ? w : w - ring_len] : 0.f;
+  }
+}
+
+const char* launch_ingest_pop(const float* ring, int S, int ring_len, const int* table, int A, int hop, float* out,
+                              hipStream_t s) {
+  if (!ring || !table || !out) return "ingest_pop: null argument";
+  if (S <= 0 || A <= 0 || A > 65535) return "ingest_pop: 1 to 65535 rows";
+  if (hop <= 0 || hop > ring_len) return "ingest_pop: a hop must fit the ring";
+  hipLaunchKernelGGL(ingest_pop_kernel, dim3(min((hop + 255) / 256, 64), A), dim3(256), 0, s, ring, S, ring_len, table, hop, out);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+// ---------------------------------------------------------------------------------
 // Row LayerNorm (+ activation): one wave per row, C <= 1024, C % 4 == 0.  The row
 // stays in registers (float4 per lane per 256-column slab), two-pass statistics in
 // fp32 like torch.  Used for the conv-stack LayerNorm+GELU, every transformer /

@@ -138,6 +138,13 @@ const char* launch_resample(const float* x, const long long* in_offs, const long
                             const float* taps, int L, int M, int T, float* out, hipStream_t s);
 const char* launch_resample_stream(const float* x, int A, int n_in, float* hist, const int* slot, const float* taps, int L,
                                    int M, int T, float* out, hipStream_t s);
+// packet ingest (include/afx.h afx_k_ingest / afx_k_ingest_pop): encoded packets of any length -> decoded, resampled at
+// each slot's carried phase into its pending ring, history advanced; and the first hop of named slots' rings -> (A, hop)
+const char* launch_ingest(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_out, int enc,
+                          const float* taps, int L, int M, int T, float* hist, float* ring, int S, int ring_len,
+                          hipStream_t s);
+const char* launch_ingest_pop(const float* ring, int S, int ring_len, const int* table, int A, int hop, float* out,
+                              hipStream_t s);
 void conv0_set_mfma(int v);  // A/B knob: 1 (default) = matrix-core forms (split-precision fp16 when packed), 2 = fp32 MFMA form, 0 = VALU form
 // y[t] = x[t] - coef * x[t-1] with a reflect pad on the left; (B,L) fp32 -> (B,L) fp32
 const char* launch_pre_emphasis(const float* x, int B, int L, float coef, float* y, hipStream_t s);
