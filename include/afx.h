@@ -302,6 +302,38 @@ int afx_k_ingest(const void* stage, long long stage_bytes, const int* hdr, int r
 /* out (A, hop) fp32: out[i][k] = ring[slot_i][(head_i + k) mod ring_len], table (device, A x 2 int32) = (slot_i, head_i):
  * the next hop of the named slots as the streaming scorers' push takes it.  The ring is only read. */
 int afx_k_ingest_pop(const float* ring, int S, int ring_len, const int* table, int A, int hop, float* out, void* stream);
+/* Jitter buffer (afx/jitter.py): per slot one DECODED reorder ring, jring (S, J) fp32; input-rate sample i of the slot's
+ * played-out stream E (indexed from the session's first accepted timestamp) lives at column i mod J.  All indices are the
+ * host's (playout point, received intervals, gaps); nothing is read back.  With lookback = max(T-1, P+F) the host keeps every
+ * launch of a round that has released E below `cur` inside the J consecutive indices [cur - lookback, cur + J - lookback).
+ * afx_k_jitter_place: one launch for all packet sub-ranges of a feed.  hdr (device, rows x 4 int32), per row: slot, byte
+ *     offset of the sub-range's first sample in stage (a multiple of the sample size), n samples, ring column c of the
+ *     first: jring[slot][(c + k) mod J] = decode(sample k), k < n, with afx_k_ingest's encodings and exact decode.  The rows
+ *     of one launch write disjoint ranges (the host splits packets at the playout point and at what was received before).
+ *     max_n = the largest n <= J.  A row whose header would leave stage or jring is skipped whole. */
+int afx_k_jitter_place(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n, int encoding,
+                       float* jring, int S, int J, void* stream);
+/* afx_k_jitter_conceal: a released gap of E that began at index a is written into the ring.  hdr (device, rows x 4 int32),
+ *     per row: slot, a mod J, d_lo, d_hi: for d in [d_lo, d_hi), E[a + d] = jring[slot][(a + d) mod J] =
+ *         mode 0 (zero):    0
+ *         mode 1 (repeat):  fade[d] * E[a - P + (d mod P)] for d < F, 0 for d >= F
+ *     one fp32 multiply of two stored fp32 values; fade (device, F fp32), P the repeat period, F the fade length.  The
+ *     source [a - P, a) is read from the ring as it stands (it may hold an earlier gap's concealed samples): gaps of one
+ *     slot go in successive launches, the rows of one launch are of distinct slots.  max_n = the largest d_hi - d_lo; a row
+ *     needs d_hi + P <= J (source and written columns disjoint), else it is skipped whole. */
+int afx_k_jitter_conceal(float* jring, int S, int J, const int* hdr, int rows, int max_n, const float* fade, int P, int F,
+                         int mode, void* stream);
+/* afx_k_jitter_release: afx_k_ingest with the ring as its input.  hdr (device, rows x 8 int32), per row: slot, a0 mod J,
+ *     n_in, n_out, p0, d0, wpos, 0 for a slot whose playout point a0 = N moves to N + n_in (p0, d0, n_out reduced from N as
+ *     for afx_k_ingest).  Output k of a row is output ceil(N*L/M) + k of afx_k_resample over all of E:
+ *         y = sum_{j<T} taps[p][j] * v[i - j],  i = d0 + floor((k*M + p0)/L),  p = (k*M + p0) mod L,
+ *     v[k] = jring[slot][(a0 + k) mod J] for k >= -(T-1) (the filter history is the ring's own earlier columns; zeros
+ *     after a reset) -- the same inputs, fp32 taps and ascending-j fma chain -- written to ring[slot][(wpos + k) mod
+ *     ring_len], the pending 16 kHz ring afx_k_ingest_pop reads.  taps NULL with L = M = T = 1: a copy.  Slots of one launch
+ *     are distinct; max_out = the largest n_out <= ring_len; n_in <= J, T - 1 <= J, M/L <= 12.  A row whose header would
+ *     leave a ring is skipped whole. */
+int afx_k_jitter_release(const float* jring, int S, int J, const int* hdr, int rows, int max_out, const float* taps, int L,
+                         int M, int T, float* ring, int ring_len, void* stream);
 int afx_k_rownorm(int dtype, const float* x, long ldx, int rows, int C, const float* gamma, const float* beta,
                   float eps, int act, float* out_f, long ldo_f, void* out_h, long ldo_h, void* stream);
 int afx_k_mhsa(int dtype, const void* qkv, void* out, int B, int T, int H, void* stream);

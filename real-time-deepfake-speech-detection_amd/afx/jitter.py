@@ -1,0 +1,721 @@
+"""Jitter buffer of the streaming scorers: timestamped packets from a lossy network in, scores out.
+
+``afx.ingest.PacketScorer`` takes each packet as the next bytes of its slot's stream.  Packets that crossed a network
+carry an RTP timestamp and arrive late, twice, out of order or not at all.  ``JitterScorer`` wraps any of the three
+streaming scorers and does per slot, on the GPU, what a telephony endpoint does: reorder, suppress duplicates, play out
+behind a fixed depth and conceal what is missing -- and states what a slot's scores are a function of.
+
+The contract.  Each slot has a played-out stream E, indexed in input-rate samples from the session's origin, the timestamp
+of the first packet accepted after ``reset``.  Per slot the host keeps ``hi`` (the largest end index received), ``next``
+(the playout point: everything below it has been released; it never moves back) and the received intervals in
+[next, hi) -- from timestamps and sizes alone, so nothing is read back from the device.
+
+  placement    a packet with timestamp t and n samples covers [t, t + n).  Samples below ``next`` are late: dropped and
+               counted.  Samples already covered are duplicates: the first arrival wins, per sample, the rest are counted.
+               All others are placed.  A packet may straddle any of these boundaries.
+  playout      after a ``feed`` each named slot releases [next, max(next, hi - depth)); ``flush`` releases up to ``hi``;
+               ``advance(slots, upto)`` up to a given index (clock-driven playout of a stream that went quiet).
+  concealment  a released index that was received has its exact fp32 decode.  A released gap [a, b) is, with d = i - a,
+               "zero":   E[i] = 0
+               "repeat": E[i] = fade[d] * E[a - P + (d mod P)] for d < F, 0 for d >= F, E[<0] = 0
+               with P the repeat period and F the fade length in input samples and fade[d] = fp32(1 - d/F) (computed in
+               float64).  The source [a - P, a) may itself hold concealed samples: E is a stream.  Received samples are
+               never modified.
+  scores       the slot's j-th score is, bit for bit, score j of a fresh inner scorer pushed ``Resampler(input_rate)(E)``
+               hop by hop, emitted by the call in which the last input sample it needs was released.
+
+So with no loss and every packet arriving before the playout point passes its start, E is the sent stream and the scores
+are an in-order lossless ``PacketScorer``'s whatever the permutation, the cuts and the duplicates; and ``depth = 0`` with
+in-order input is ``PacketScorer``, call by call.
+
+Device side (csrc/afx_frontend.hip): one decoded reorder ring per slot, (S, J) fp32, index i at column i mod J.
+``afx_k_jitter_place`` decodes all placed sub-ranges of a feed in one launch, ``afx_k_jitter_conceal`` writes released gaps
+into the ring (one launch per rank of gap within a slot, so a gap whose source overlaps an earlier gap reads concealed
+data), ``afx_k_jitter_release`` resamples released samples from the ring into the pending 16 kHz ring with the offline
+kernel's inputs, taps and fma order, and ``afx_k_ingest_pop`` hands whole hops to the inner scorer's non-paced ``push``.
+Sizing: with lookback = max(T - 1, P + F) (the filter history and a fading gap's source) and W = J - lookback >= depth,
+every launch of a round whose playout point is ``cur`` touches only indices in [cur - lookback, cur + W): J consecutive
+indices, no two on one column.  A forward jump or a packet longer than W is worked off in rounds (place what fits, conceal,
+release, pop), so device memory does not depend on it.  A call is one pinned upload (payloads, then every table).
+
+Sessions: ``export_slots`` adds ``jitter_pending`` / ``jitter_fill`` (pending 16 kHz samples), ``jitter_ring`` (the ring
+columns [next - lookback, hi) left-aligned), ``jitter_book`` (origin, started, next, hi, open gap, largest start, last
+sequence number, SSRC), ``jitter_stats`` and ``jitter_intervals`` ((n, K, 2), -1 padded) to the inner state, with meta
+``jitter`` (format), ``jitter_depth``, ``jitter_conceal``, ``jitter_period``, ``jitter_fade``, ``input_rate`` and ``resampler``.
+"""
+import numpy as np
+import torch
+
+from . import rtp
+from ._lib import AfxError, call_on, check, lib, ptr
+from .ingest import _SAMPLE, ENCODINGS, FeedResult, _at, _encoding, layout, pack, payload
+from .resample import FILTER_ID, Resampler
+from .streaming import StreamState, _on
+
+JITTER_FORMAT = 1  # layout of the jitter part of a StreamState: import_slots refuses any other
+CONCEAL = ("zero", "repeat")  # the library's mode numbers 0, 1
+PLACE_HDR, CONCEAL_HDR, RELEASE_HDR = 4, 4, 8  # int32 per row of the three tables (include/afx.h)
+STATS = ("received", "late", "duplicate", "concealed", "out_of_order")
+_STATE_KEYS = ("jitter_pending", "jitter_fill", "jitter_ring", "jitter_book", "jitter_stats", "jitter_intervals")
+_META_KEYS = ("input_rate", "resampler", "jitter", "jitter_depth", "jitter_conceal", "jitter_period", "jitter_fade")
+_BOOK = ("origin", "started", "next", "hi", "gap", "max_start", "max_seq", "ssrc")  # jitter_book columns
+_COUNTERS = ("received", "late", "dup", "concealed", "ooo")  # jitter_stats columns (STATS order)
+_MAX_SAMPLES = 1 << 30
+
+
+def _nonneg_int(v, name, least=0):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < least:
+        raise ValueError(f"{name}: an integer >= {least}, got {v!r}")
+    return int(v)
+
+
+class _Book:
+    """The host's bookkeeping of every slot (int64 arrays over S) and, for the slots that currently have holes, their
+    received intervals (``holes``: slot -> sorted disjoint [start, end) lists inside [next, hi)).  A slot that is not in
+    ``holes`` has received exactly [next, hi)."""
+
+    def __init__(self, S):
+        for f in _BOOK + _COUNTERS + ("head", "fill"):
+            setattr(self, f, np.zeros(S, dtype=np.int64))
+        for f in ("gap", "max_seq", "ssrc"):
+            getattr(self, f)[:] = -1
+        self.holey = np.zeros(S, dtype=bool)
+        self.holes = {}
+
+    def copy(self):
+        b = _Book.__new__(_Book)
+        for f in _BOOK + _COUNTERS + ("head", "fill", "holey"):
+            setattr(b, f, getattr(self, f).copy())
+        b.holes = dict(self.holes)  # (the lists are replaced, never edited in place)
+        return b
+
+    def clear(self, idx):
+        for f in _BOOK + _COUNTERS + ("head", "fill"):
+            getattr(self, f)[idx] = 0
+        for f in ("gap", "max_seq", "ssrc"):
+            getattr(self, f)[idx] = -1
+        self.holey[idx] = False
+        for s in idx:
+            self.holes.pop(s, None)
+
+    def intervals(self, s):
+        """The received intervals of slot s in [next, hi)."""
+        if self.holey[s]:
+            return self.holes[s]
+        return [[int(self.next[s]), int(self.hi[s])]] if self.hi[s] > self.next[s] else []
+
+    def set_intervals(self, s, ivs):
+        nxt, hi = int(self.next[s]), int(self.hi[s])
+        if (not ivs and nxt == hi) or (len(ivs) == 1 and ivs[0][0] == nxt and ivs[0][1] == hi):
+            self.holey[s] = False
+            self.holes.pop(s, None)
+        else:
+            self.holey[s] = True
+            self.holes[s] = ivs
+
+
+def _subtract(lo, hi, ivs):
+    """[lo, hi) minus the sorted disjoint intervals ``ivs`` -> list of [start, end)."""
+    out = []
+    for a, b in ivs:
+        if b <= lo:
+            continue
+        if a >= hi:
+            break
+        if a > lo:
+            out.append([lo, a])
+        lo = max(lo, b)
+        if lo >= hi:
+            break
+    if lo < hi:
+        out.append([lo, hi])
+    return out
+
+
+def _merge(ivs, new):
+    """Sorted disjoint ``ivs`` plus the intervals ``new`` (disjoint from them), touching intervals joined."""
+    out = []
+    for a, b in sorted(ivs + new):
+        if out and a <= out[-1][1]:
+            out[-1][1] = max(out[-1][1], b)
+        else:
+            out.append([a, b])
+    return out
+
+
+class Plan:
+    """What a call will do: ``ops`` (the launches, in order: ("place" | "conceal" | "release", int32 rows, largest row) and
+    ("pop", (A, 2) table, slots)), ``counts`` (hops per named row) and ``book`` (the bookkeeping after it)."""
+
+    def __init__(self, ops, slots, counts, book):
+        self.ops, self.slots, self.counts, self.book = ops, slots, counts, book
+
+
+class JitterScorer:
+    """``scorer`` (a SlidingWindowScorer, IncrementalScorer or KVCachedScorer) fed timestamped packets at ``input_rate`` Hz
+    in ``encoding`` (``afx.ingest.ENCODINGS``); see the module docstring for the contract.
+
+    ``depth``: the playout delay in input samples (60 ms is common; 0 is legal).  ``conceal``: "repeat" or "zero".
+    ``period``: the repeat period P in input samples, default 10 ms (input_rate // 100).  ``fade``: the fade length F in
+    input samples, default 3 P (30 ms).  ``max_pending``: the whole hops a slot may buffer between ``feed(..., score=False)``
+    and ``drain``.  ``ts_bits``: 32 (default) unwraps each timestamp to the value nearest the slot's ``hi``, so a stream
+    crossing 2**32 is seamless; None takes absolute indices."""
+
+    def __init__(self, scorer, input_rate, encoding, depth, conceal="repeat", period=None, fade=None, max_pending=4, ts_bits=32):
+        self.encoding = _encoding(encoding)
+        self.depth = _nonneg_int(depth, "depth")
+        if conceal not in CONCEAL:
+            raise ValueError(f"conceal {conceal!r}: one of {CONCEAL}")
+        self.max_pending = _nonneg_int(max_pending, "max_pending", 1)
+        if ts_bits is not None and (isinstance(ts_bits, bool) or not isinstance(ts_bits, (int, np.integer)) or not 8 <= ts_bits <= 48):
+            raise ValueError("ts_bits: None (absolute indices) or the width of the timestamp counter, 8..48")
+        self.ts_bits = None if ts_bits is None else int(ts_bits)
+        self.rs = Resampler(input_rate, scorer.device)  # (a bad rate is a ValueError here)
+        self.scorer, self.input_rate, self.hop = scorer, self.rs.rate, scorer.hop
+        self.L, self.M = self.rs.L, self.rs.M
+        self.conceal = conceal
+        if conceal == "repeat":
+            self.period = _nonneg_int(self.input_rate // 100 if period is None else period, "period", 1)
+            self.fade_len = _nonneg_int(3 * self.period if fade is None else fade, "fade")
+        else:
+            self.period = self.fade_len = 0  # (no part of the "zero" function: not recorded in a state either)
+        T = 1 if self.rs.identity else self.rs.T
+        # the sizing invariant (module docstring): J = lookback + W, W >= depth; the slack beyond depth is what a round can
+        # place and release at once (one hop of input: an ordinary packet never takes a second round)
+        self.lookback = max(T - 1, self.period + self.fade_len)
+        self.W = self.depth + -(-self.hop * self.M // self.L) + 1
+        self.J = self.lookback + self.W
+        if self.J >= _MAX_SAMPLES:
+            raise ValueError("depth + period + fade: less than 2**30 samples")
+        dev = scorer.device
+        self.ring_len = (self.max_pending + 1) * self.hop  # as PacketScorer: a scoring call always finds room
+        self.ring = torch.zeros(scorer.S, self.ring_len, dtype=torch.float32, device=dev)
+        self.jring = torch.zeros(scorer.S, self.J, dtype=torch.float32, device=dev)
+        F = self.fade_len
+        table = (1.0 - np.arange(max(F, 1), dtype=np.float64) / max(F, 1)).astype(np.float32)
+        self.fade = torch.from_numpy(table).to(dev)
+        self._b = _Book(scorer.S)
+
+    # ---- properties ----------------------------------------------------------------------------------------------------
+    @property
+    def S(self):
+        return self.scorer.S
+
+    @property
+    def device(self):
+        return self.scorer.device
+
+    @property
+    def delay(self):
+        """The resampled stream's lag behind resample_poly's centred output, in 16 kHz samples (the playout ``depth``, in
+        input samples, comes on top of it)."""
+        return self.rs.delay
+
+    @property
+    def samples_seen(self):
+        """(S,) int64: the 16 kHz samples each slot's inner session has been pushed since its last ``reset``."""
+        return self.scorer.samples_seen
+
+    @property
+    def pending(self):
+        """(S,) int64: the 16 kHz samples waiting in each slot's buffer."""
+        return torch.from_numpy(self._b.fill.copy())
+
+    @property
+    def samples_in(self):
+        """(S,) int64: each slot's playout point ``next``: the input-rate samples of E released since its last ``reset``."""
+        return torch.from_numpy(self._b.next.copy())
+
+    @property
+    def buffered(self):
+        """(S,) int64: hi - next, the span of input samples each slot's reorder ring holds back."""
+        return torch.from_numpy(self._b.hi - self._b.next)
+
+    def stats(self):
+        """Per-slot int64 counters since each slot's reset: ``received`` (samples placed), ``late`` (samples below the
+        playout point on arrival), ``duplicate`` (samples already covered), ``concealed`` (released gap samples) and
+        ``out_of_order`` (packets that arrived behind an earlier one: by sequence number in ``feed_rtp``, by timestamp in
+        ``feed``)."""
+        return {k: torch.from_numpy(getattr(self._b, f).copy()) for k, f in zip(STATS, _COUNTERS)}
+
+    # ---- planning (host arithmetic only) -----------------------------------------------------------------------------
+    def _unwrap(self, t, ref):
+        """Timestamp t as the absolute value nearest ref (ts_bits), or as it is."""
+        if self.ts_bits is None:
+            return t
+        mod = 1 << self.ts_bits
+        return ref + ((t - ref + mod // 2) % mod) - mod // 2
+
+    def _place_rows(self, b, slot, size, ts, offs, seqs):
+        """Phase 1 of a feed: the bookkeeping of every row, in order -> placements (int64 arrays: slot, first index, n, byte
+        offset).  Rows that continue a hole-free slot at its ``hi`` (the common case) are handled for all slots at once;
+        the others one by one."""
+        bps = _SAMPLE[self.encoding].itemsize
+        once = np.bincount(slot, minlength=self.S)[slot] == 1
+        ref = b.origin[slot] + b.hi[slot]
+        rel = self._unwrap(ts, ref) - b.origin[slot]
+        fast = once & (b.started[slot] == 1) & ~b.holey[slot] & (rel == b.hi[slot])
+        place = []
+        if fast.any():
+            s, n, r = slot[fast], size[fast], rel[fast]
+            if seqs is not None:
+                q, last = seqs[fast], b.max_seq[s]
+                behind = (last >= 0) & (((q - last) & 0xFFFF) >= 0x8000)
+                b.ooo[s] += behind
+                b.max_seq[s] = np.where(behind, last, q)
+            b.max_start[s] = np.maximum(b.max_start[s], r)  # (r = hi >= every earlier start: never out of order)
+            b.hi[s] += n
+            b.received[s] += n
+            keep = n > 0
+            place.append(np.stack([s[keep], r[keep], n[keep], offs[fast][keep]]))
+        slow = []
+        rest = np.flatnonzero(~fast)
+        if rest.size:  # plain Python ints over the slots these rows name: read once, written back once
+            ss = np.unique(slot[rest])
+            keys = ("started", "origin", "next", "hi", "max_start", "max_seq", "ooo", "late", "dup", "received")
+            started, origin, nxt_, hi_, max_start, max_seq, ooo, late, dup, received = (
+                dict(zip(ss.tolist(), getattr(b, f)[ss].tolist())) for f in keys)
+            ivs_of = {}
+            seq_rest = [None] * rest.size if seqs is None else seqs[rest].tolist()
+            for s, n, t, off, q in zip(slot[rest].tolist(), size[rest].tolist(), ts[rest].tolist(), offs[rest].tolist(), seq_rest):
+                first = not started[s]
+                if first:
+                    started[s], origin[s], r = 1, t, 0
+                else:
+                    r = self._unwrap(t, origin[s] + hi_[s]) - origin[s]
+                if q is not None:
+                    last = max_seq[s]
+                    if last >= 0 and ((q - last) & 0xFFFF) >= 0x8000:
+                        ooo[s] += 1
+                    else:
+                        max_seq[s] = q
+                elif not first and r < max_start[s]:
+                    ooo[s] += 1
+                max_start[s] = r if first else max(max_start[s], r)
+                lo, hi, nxt = r, r + n, nxt_[s]
+                if lo < nxt:
+                    late[s] += min(hi, nxt) - lo
+                    lo = min(hi, nxt)
+                if lo >= hi:
+                    continue
+                ivs = ivs_of[s] if s in ivs_of else b.intervals(s)
+                new = _subtract(lo, hi, ivs)
+                got = sum(e - a for a, e in new)
+                dup[s] += hi - lo - got
+                received[s] += got
+                for a, e in new:
+                    slow.append((s, a, e - a, off + (a - r) * bps))
+                hi_[s] = max(hi_[s], hi)
+                ivs_of[s] = _merge([list(v) for v in ivs], new)
+            order = ss.tolist()
+            for f, d in zip(keys, (started, origin, nxt_, hi_, max_start, max_seq, ooo, late, dup, received)):
+                getattr(b, f)[ss] = [d[s] for s in order]
+            for s, ivs in ivs_of.items():
+                b.set_intervals(s, ivs)
+        if slow:
+            place.append(np.array(slow, dtype=np.int64).T)
+        return np.concatenate(place, axis=1) if place else np.zeros((4, 0), dtype=np.int64)
+
+    def _take_gaps(self, b, U, tgt):
+        """Phase 2: the named slots U release [next, tgt) -> {position in U: [[origin, lo, hi], ...]} (the gaps of that
+        range, in order), and the bookkeeping moves to next = tgt.  Per-slot work only for slots with holes."""
+        nxt = b.next[U].copy()
+        gaps = {}
+        moved = tgt > nxt
+        plain = moved & ~b.holey[U]
+        b.gap[U[plain]] = -1
+        b.next[U[plain]] = tgt[plain]
+        for u in np.flatnonzero(moved & b.holey[U]).tolist():
+            s, lo, hi = int(U[u]), int(nxt[u]), int(tgt[u])
+            ivs = b.holes[s]
+            g = _subtract(lo, hi, ivs)
+            if g:
+                opened = int(b.gap[s])
+                gaps[u] = [[opened if k == 0 and a == lo and opened >= 0 else a, a, e] for k, (a, e) in enumerate(g)]
+                b.concealed[s] += sum(e - a for a, e in g)
+            b.gap[s] = gaps[u][-1][0] if g and g[-1][1] == hi else -1
+            b.next[s] = hi
+            b.set_intervals(s, [[max(a, hi), e] for a, e in ivs if e > hi])
+        return gaps
+
+    def _plan(self, slots, sizes=None, ts=None, offs=None, seqs=None, mode="feed", upto=None, score=True):
+        """The launches of a call over the rows ``slots`` (feed: sizes[i] samples with timestamp ts[i] and payload at byte
+        offs[i] for slots[i], a slot possibly named more than once; flush / advance / drain: distinct slots) -> Plan.  No
+        state changes here: ``_commit(plan.book)`` (or ``_run``) makes it so."""
+        b = self._b.copy()
+        L, M, R, hop, J, W, F = self.L, self.M, self.ring_len, self.hop, self.J, self.W, self.fade_len
+        bps = _SAMPLE[self.encoding].itemsize
+        slot = np.asarray(slots, dtype=np.int64).reshape(-1)
+        if mode == "feed":
+            pl = self._place_rows(b, slot, np.asarray(sizes, dtype=np.int64).reshape(-1), np.asarray(ts, dtype=np.int64).reshape(-1),
+                                  np.asarray(offs, dtype=np.int64).reshape(-1), None if seqs is None else np.asarray(seqs, dtype=np.int64))
+        else:
+            pl = np.zeros((4, 0), dtype=np.int64)
+        _, first = np.unique(slot, return_index=True)
+        first.sort()
+        U = slot[first]  # the named slots, once each, in the order they were first named
+        cur = b.next[U].copy()
+        if mode == "feed":
+            tgt = np.maximum(cur, b.hi[U] - self.depth)
+        elif mode == "flush":
+            tgt = b.hi[U].copy()
+        elif mode == "advance":
+            tgt = np.maximum(cur, np.broadcast_to(np.asarray(upto, dtype=np.int64), U.shape))
+            for u in np.flatnonzero(tgt > b.hi[U]).tolist():  # playout beyond everything received: a gap up to there
+                s = int(U[u])
+                ivs = b.intervals(s)
+                b.hi[s] = tgt[u]
+                b.set_intervals(s, [list(v) for v in ivs])
+        else:
+            tgt = cur.copy()
+        if not score:
+            after = b.fill[U] - (-tgt * L // M) + (-cur * L // M)
+            over = np.flatnonzero(after > self.max_pending * hop)
+            if over.size:
+                raise ValueError(f"slot {U[over[0]]} would hold {after[over[0]]} pending samples, more than max_pending = "
+                                 f"{self.max_pending} hops of {hop}: drain it first")
+        gaps = self._take_gaps(b, U, tgt)
+        pos = np.full(self.S, -1, dtype=np.int64)
+        pos[U] = np.arange(U.size)
+        pu, pstart, pn, poff = pos[pl[0]], pl[1], pl[2], pl[3]
+        pdone = np.zeros_like(pn)
+        head, fill = b.head[U].copy(), b.fill[U].copy()
+        counts = np.zeros(U.size, dtype=np.int64)
+        ops = []
+        while True:
+            progress = False
+            # place what the window [cur, cur + W) of each slot takes
+            take = np.clip(cur[pu] + W - (pstart + pdone), 0, pn - pdone)
+            k = np.flatnonzero(take > 0)
+            if k.size:
+                rows = np.stack([U[pu[k]], poff[k] + pdone[k] * bps, take[k], (pstart[k] + pdone[k]) % J], axis=1).astype(np.int32)
+                ops.append(("place", rows, int(take[k].max())))
+                pdone[k] += take[k]
+                progress = True
+            # release what is due, the window holds and the pending ring has room for
+            made = -(-cur * L // M)
+            m = np.maximum(np.minimum(np.minimum(tgt - cur, W), (made + R - fill) * M // L - cur), 0)
+            ranks = []
+            for u, gl in gaps.items():  # the gaps inside [cur, cur + m) of the slots that have any, by rank within the slot
+                c0, c1, s, rank = int(cur[u]), int(cur[u] + m[u]), int(U[u]), 0
+                for a, lo, hi in gl:
+                    lo, hi = max(lo, c0), min(hi, c1)
+                    if lo >= hi:
+                        continue
+                    d_lo, d_hi = lo - a, hi - a
+                    if d_lo >= F:  # all zeros from here on: the same row counted from a + d_lo - F (d stays small)
+                        a, d_lo, d_hi = a + d_lo - F, F, F + d_hi - d_lo
+                    if rank == len(ranks):
+                        ranks.append([])
+                    ranks[rank].append((s, a % J, d_lo, d_hi))
+                    rank += 1
+            for rows in ranks:
+                rows = np.array(rows, dtype=np.int32)
+                ops.append(("conceal", rows, int((rows[:, 3] - rows[:, 2]).max())))
+            k = np.flatnonzero(m > 0)
+            if k.size:
+                n_out = -(-(cur[k] + m[k]) * L // M) - made[k]
+                rows = np.zeros((k.size, RELEASE_HDR), dtype=np.int32)
+                for c, v in enumerate((U[k], cur[k] % J, m[k], n_out, made[k] * M % L, made[k] * M // L - cur[k], (head[k] + fill[k]) % R)):
+                    rows[:, c] = v
+                ops.append(("release", rows, int(n_out.max())))
+                cur[k] += m[k]
+                fill[k] += n_out
+                progress = True
+            while score:
+                ready = fill >= hop
+                if not ready.any():
+                    break
+                s = U[ready]
+                ops.append(("pop", np.stack([s, head[ready]], axis=1).astype(np.int32), s.tolist()))
+                head[ready] = (head[ready] + hop) % R
+                fill[ready] -= hop
+                counts += ready
+                progress = True
+            if (pdone == pn).all() and (cur == tgt).all():
+                break
+            if not progress:
+                raise RuntimeError("the jitter plan made no progress")  # (validated before planning: not reached)
+        b.head[U], b.fill[U] = head, fill
+        per_row = np.zeros(slot.size, dtype=np.int64)
+        per_row[first] = counts  # a slot named twice: its hops are counted at its first row
+        return Plan(ops, U.tolist(), per_row, b)
+
+    def _commit(self, book):
+        self._b = book
+
+    # ---- the public calls --------------------------------------------------------------------------------------------
+    def _rows(self, slots, repeats=False):
+        """``slots`` -> list of slot indices in the order given (a bool mask: ascending); repeats: a slot may be named more
+        than once."""
+        if not repeats:
+            return self.scorer._slot_list(slots, ordered=True)
+        t = torch.as_tensor(slots)
+        if t.numel() == 0 and t.ndim <= 1:
+            return []
+        if t.dtype == torch.bool or t.is_floating_point() or t.is_complex() or t.ndim > 1:
+            raise ValueError("slots: a list of slot indices (a slot may be named more than once)")
+        idx = t.reshape(-1).cpu().numpy()
+        bad = idx[(idx < 0) | (idx >= self.S)]
+        if bad.size:
+            raise ValueError(f"slot index {bad[0]} outside 0..{self.S - 1}")
+        return idx.tolist()
+
+    def _timestamps(self, timestamps, n):
+        if isinstance(timestamps, torch.Tensor):
+            timestamps = timestamps.detach().cpu().numpy()
+        try:
+            vals = np.asarray(timestamps)
+        except (OverflowError, ValueError):
+            vals = np.zeros(0, dtype=object)
+        if vals.ndim != 1 or (vals.size and vals.dtype.kind not in "iu"):
+            raise ValueError("timestamps: a list of ints or a 1-D integer array, in input-rate samples")
+        if vals.size != n:
+            raise ValueError(f"{vals.size} timestamps for {n} named slots")
+        lim = 1 << (self.ts_bits if self.ts_bits is not None else 62)
+        low = 0 if self.ts_bits is not None else -lim
+        if vals.size and (vals.dtype == np.uint64 and int(vals.max()) >= lim or int(vals.min()) < low or int(vals.max()) >= lim):
+            raise ValueError(f"a timestamp outside {low}..{lim - 1}" + (f" (ts_bits = {self.ts_bits})" if self.ts_bits else ""))
+        return vals.astype(np.int64)
+
+    def feed(self, packets, slots, timestamps, score=True, _seqs=None):
+        """packets[i]: a packet of slot slots[i] whose first sample has timestamp timestamps[i] (Python ints or an int64
+        array, in input-rate samples), any length, in any order; a slot may be named more than once (its rows are taken in
+        the order given).  Afterwards each named slot has released [next, max(next, hi - depth)).  score=True: every hop a
+        named slot completes is scored; score=False: buffered only (``drain`` scores them; a slot whose buffer would hold
+        more than ``max_pending`` hops is a ValueError).  Everything is checked before anything changes.  -> FeedResult
+        with one count per row of ``slots`` (a slot named twice has its hops at its first row)."""
+        return self._run(*self._plan_feed(packets, slots, timestamps, score, _seqs))
+
+    def _plan_feed(self, packets, slots, timestamps, score=True, seqs=None):
+        """The checks and the plan of a ``feed`` -> (Plan, payload blocks).  No state changes."""
+        idx = self._rows(slots, repeats=True)
+        if isinstance(packets, (bytes, bytearray, memoryview, np.ndarray, torch.Tensor)):
+            raise ValueError("packets: a list with one packet per named slot")
+        packets = list(packets)
+        if len(packets) != len(idx):
+            raise ValueError(f"{len(packets)} packets for {len(idx)} named slots")
+        ts = self._timestamps(timestamps, len(idx))
+        bps = _SAMPLE[self.encoding].itemsize
+        pay = [p if type(p) is bytes else payload(p, self.encoding) for p in packets]
+        nbytes = np.fromiter(map(len, pay), dtype=np.int64, count=len(pay))
+        for i in np.flatnonzero((nbytes % bps != 0) | (nbytes // bps >= _MAX_SAMPLES)):
+            payload(pay[i], self.encoding)  # (raises, with the message)
+        offs, total = layout(nbytes)
+        if total >= 1 << 31:
+            raise ValueError("a feed carries less than 2 GiB")
+        return self._plan(idx, nbytes // bps, ts, offs, seqs, "feed", score=score), pay
+
+    def feed_rtp(self, datagrams, slots, payload_types=None, score=True):
+        """datagrams[i]: one RTP datagram (RFC 3550) of slot slots[i].  Its payload type must name this scorer's encoding:
+        0 is mulaw and 8 alaw (RFC 3551), ``payload_types`` ({number: encoding}) adds the dynamic ones; its SSRC must be the
+        session's (the first datagram after ``reset`` sets it).  Placement uses the timestamps; the sequence numbers only
+        count packets out of order for ``stats()``.  Anything else is a ValueError before anything changes."""
+        idx = self._rows(slots, repeats=True)
+        if isinstance(datagrams, (bytes, bytearray, memoryview)):
+            raise ValueError("datagrams: a list with one datagram per named slot")
+        pk = [rtp.parse(d) for d in datagrams]
+        if len(pk) != len(idx):
+            raise ValueError(f"{len(pk)} datagrams for {len(idx)} named slots")
+        if self.ts_bits != 32:
+            raise ValueError("feed_rtp: RTP timestamps are 32 bits wide (ts_bits = 32)")
+        types = {**rtp.STATIC_PAYLOAD_TYPES, **(payload_types or {})}
+        ssrc = {}
+        for s, p in zip(idx, pk):
+            if types.get(p.payload_type) != self.encoding:
+                raise ValueError(f"slot {s}: RTP payload type {p.payload_type} is not this scorer's {self.encoding}")
+            mine = ssrc.setdefault(s, int(self._b.ssrc[s]) if self._b.ssrc[s] >= 0 else p.ssrc)
+            if p.ssrc != mine:
+                raise ValueError(f"slot {s}: SSRC {p.ssrc:#010x} is not the session's {mine:#010x}")
+        res = self.feed([p.payload for p in pk], idx, [p.timestamp for p in pk], score=score, _seqs=[p.seq for p in pk])
+        for s, v in ssrc.items():
+            self._b.ssrc[s] = v
+        return res
+
+    def flush(self, slots=None, score=True):
+        """The named (default: all) slots release everything received, up to ``hi`` -> FeedResult."""
+        idx = list(range(self.S)) if slots is None else self._rows(slots)
+        return self._run(self._plan(idx, mode="flush", score=score), [])
+
+    def advance(self, slots, upto, score=True):
+        """The named slots release up to index ``upto`` of their streams (one int, or one per slot; input-rate samples from
+        the session's origin): clock-driven playout of a stream that has gone quiet.  A slot already beyond it is left
+        alone; beyond ``hi`` the stream is a gap, and ``hi`` moves there -> FeedResult."""
+        idx = self._rows(slots)
+        up = np.asarray(upto)
+        if up.dtype.kind not in "iu" or up.ndim > 1 or (up.ndim == 1 and up.size != len(idx)) or (up.size and (up.min() < 0 or up.max() >= 1 << 62)):
+            raise ValueError("advance: upto is one non-negative integer, or one per named slot")
+        up = np.broadcast_to(up.astype(np.int64), (len(idx),))
+        cold = [s for s, v in zip(idx, up.tolist()) if not self._b.started[s] and v > 0]
+        if cold:
+            raise ValueError(f"slot {cold[0]} has no session yet: its origin is its first packet's timestamp")
+        return self._run(self._plan(idx, mode="advance", upto=up, score=score), [])
+
+    def drain(self, slots=None):
+        """Score every completed hop of the named (default: all) slots -> FeedResult.  Nothing is released."""
+        idx = list(range(self.S)) if slots is None else self._rows(slots)
+        return self._run(self._plan(idx, mode="drain"), [])
+
+    def _run(self, plan, pay):
+        ops, dev = plan.ops, self.device
+        counts = torch.from_numpy(plan.counts)
+        if not ops:
+            self._commit(plan.book)
+            return FeedResult(counts, torch.empty(0, dtype=torch.float32, device=dev))
+        if dev.type != "cuda":
+            raise AfxError("packets are decoded, concealed, resampled and scored on the GPU; there is no CPU fallback")
+        # where each score of the result sits in the concatenation of the pop rounds' outputs (a table when it is not in order)
+        pos, base = {s: [] for s in plan.slots}, 0
+        for op in ops:
+            if op[0] == "pop":
+                for k, s in enumerate(op[2]):
+                    pos[s].append(base + k)
+                base += len(op[2])
+        perm = [p for s in plan.slots for p in pos[s]]
+        tables = [op[1] for op in ops]
+        if perm != list(range(base)):
+            tables.append(np.array(perm, dtype=np.int64))
+        buf, _, toffs = pack(pay, tables, pinned=True)
+        enc, taps = ENCODINGS.index(self.encoding), (None if self.rs.identity else ptr(self.rs.taps))
+        T = 1 if self.rs.identity else self.rs.T
+        l, S, J = lib(), self.S, self.J
+        outs = []
+        with torch.cuda.device(dev):
+            d = buf.to(dev, non_blocking=True)  # the one upload
+            for op, off in zip(ops, toffs):
+                if op[0] == "place":
+                    check(call_on(self.jring, l.afx_k_jitter_place, _at(d, 0), d.numel(), _at(d, off), len(op[1]), op[2], enc,
+                                  ptr(self.jring), S, J))
+                elif op[0] == "conceal":
+                    check(call_on(self.jring, l.afx_k_jitter_conceal, ptr(self.jring), S, J, _at(d, off), len(op[1]), op[2],
+                                  ptr(self.fade), self.period, self.fade_len, CONCEAL.index(self.conceal)))
+                elif op[0] == "release":
+                    check(call_on(self.jring, l.afx_k_jitter_release, ptr(self.jring), S, J, _at(d, off), len(op[1]), op[2], taps,
+                                  self.L, self.M, T, ptr(self.ring), self.ring_len))
+                else:
+                    chunk = torch.empty(len(op[2]), self.hop, dtype=torch.float32, device=dev)
+                    check(call_on(self.ring, l.afx_k_ingest_pop, ptr(self.ring), S, self.ring_len, _at(d, off), len(op[2]),
+                                  self.hop, ptr(chunk)))
+                    sc = self.scorer.push(chunk, op[2])
+                    if sc is None:
+                        raise RuntimeError("the inner scorer emitted no score for a hop")
+                    outs.append(sc)
+            self._commit(plan.book)  # (the bookkeeping follows the device state: set once every launch has been issued)
+            scores = torch.cat(outs) if outs else torch.empty(0, dtype=torch.float32, device=dev)
+            if len(tables) > len(ops):
+                scores = scores.index_select(0, d[toffs[-1]:toffs[-1] + 8 * base].view(torch.int64))
+        return FeedResult(counts, scores)
+
+    # ---- sessions ----------------------------------------------------------------------------------------------------
+    def reset(self, slots):
+        """The named slots begin a new stream: inner session, reorder ring, pending samples, origin and counters are dropped."""
+        idx = self.scorer._slot_list(slots)
+        self.scorer.reset(idx)
+        if idx:
+            self._b.clear(idx)
+            self.jring[idx] = 0.0
+
+    def _meta(self):
+        return dict(input_rate=self.input_rate, resampler=FILTER_ID, jitter=JITTER_FORMAT, jitter_depth=self.depth,
+                    jitter_conceal=self.conceal, jitter_period=self.period, jitter_fade=self.fade_len)
+
+    def state_meta(self):
+        return dict(self.scorer.state_meta(), **self._meta())
+
+    def export_slots(self, slots):
+        """The inner scorer's ``StreamState`` of the named slots plus their jitter-buffer sessions (module docstring).  What is
+        stored is decoded.  No byte of the scorer changes."""
+        idx = self.scorer._slot_list(slots, ordered=True)
+        st = self.scorer.export_slots(idx)
+        dev, b = self.device, self._b
+        width = self.lookback + self.depth
+        with _on(dev):
+            rows = torch.tensor(idx, dtype=torch.long, device=dev)
+            fill = torch.from_numpy(b.fill[idx])
+            j = torch.arange(self.max_pending * self.hop)
+            cols = (torch.from_numpy(b.head[idx])[:, None] + j) % self.ring_len
+            pend = self.ring[rows[:, None], cols.to(dev)]
+            pend.masked_fill_((j[None, :] >= fill[:, None]).to(dev), 0.0)
+            nxt, held = torch.from_numpy(b.next[idx]), torch.from_numpy(b.hi[idx] - b.next[idx])
+            k = torch.arange(width)
+            jr = self.jring[rows[:, None], ((nxt[:, None] - self.lookback + k) % self.J).to(dev)]
+            jr.masked_fill_((k[None, :] >= self.lookback + held[:, None]).to(dev), 0.0)
+        ivs = [b.intervals(s) for s in idx]
+        K = max([len(v) for v in ivs] + [1])
+        table = np.full((len(idx), K, 2), -1, dtype=np.int64)
+        for i, v in enumerate(ivs):
+            if v:
+                table[i, :len(v)] = v
+        book = np.stack([getattr(b, f)[idx] for f in _BOOK], axis=1).reshape(len(idx), len(_BOOK))
+        stats = np.stack([getattr(b, f)[idx] for f in _COUNTERS], axis=1).reshape(len(idx), len(_COUNTERS))
+        tensors = dict(st.tensors, jitter_pending=pend, jitter_fill=fill.clone(), jitter_ring=jr, jitter_book=torch.from_numpy(book),
+                       jitter_stats=torch.from_numpy(stats), jitter_intervals=torch.from_numpy(table))
+        return StreamState(dict(st.meta, **self._meta()), st.seen, tensors)
+
+    def import_slots(self, slots, state):
+        """The named slots take over the sessions of ``state``, a state of a JitterScorer with the same input rate, filter,
+        depth, concealment mode, period and fade whose pending samples fit this scorer's ``max_pending``; anything else,
+        or a state whose counters contradict each other, is a ValueError before anything changes."""
+        idx = self.scorer._slot_list(slots, ordered=True)
+        if not isinstance(state, StreamState):
+            raise ValueError("import_slots takes a StreamState (export_slots / StreamState.from_state_dict)")
+        if any(k not in state.tensors for k in _STATE_KEYS) or any(k not in state.meta for k in _META_KEYS):
+            raise ValueError("import_slots: the state has no jitter-buffer part (it was not exported by a JitterScorer)")
+        mine = self._meta()
+        for k in _META_KEYS:
+            if state.meta[k] != mine[k]:
+                raise ValueError(f"import_slots: the state's {k} {state.meta[k]!r} is not this scorer's {mine[k]!r}")
+        n = len(state)
+        pend, jr = state.tensors["jitter_pending"], state.tensors["jitter_ring"]
+        ints = [state.tensors[k].cpu() for k in ("jitter_fill", "jitter_book", "jitter_stats", "jitter_intervals")]
+        if any(t.dtype != torch.int64 for t in ints):
+            raise ValueError("import_slots: jitter_fill, jitter_book, jitter_stats and jitter_intervals are int64")
+        fill, book, stats, table = (t.numpy() for t in ints)
+        fill = fill.reshape(-1)
+        if fill.size != n or book.shape != (n, len(_BOOK)) or stats.shape != (n, len(_COUNTERS)) or table.ndim != 3 or table.shape[2] != 2:
+            raise ValueError("import_slots: jitter_fill (n,), jitter_book (n, 8), jitter_stats (n, 5), jitter_intervals (n, K, 2)")
+        if pend.ndim != 2 or pend.shape[0] != n or pend.dtype != torch.float32:
+            raise ValueError(f"import_slots: jitter_pending {tuple(pend.shape)} {pend.dtype} is not (n, pending) float32")
+        width = self.lookback + self.depth
+        if tuple(jr.shape) != (n, width) or jr.dtype != torch.float32:
+            raise ValueError(f"import_slots: jitter_ring {tuple(jr.shape)} {jr.dtype} does not fit this scorer ({(n, width)} float32)")
+        if (fill < 0).any() or (fill > pend.shape[1]).any() or (fill > self.max_pending * self.hop).any():
+            raise ValueError(f"import_slots: a session holds more pending samples than max_pending = {self.max_pending} hops "
+                             f"of {self.hop} (or than its own buffer)")
+        col = {f: book[:, c] for c, f in enumerate(_BOOK)}
+        nxt, hi, gap = col["next"], col["hi"], col["gap"]
+        made = np.array([-(-int(v) * self.L // self.M) for v in nxt.tolist()], dtype=np.int64)
+        bad = ((nxt < 0) | (hi < nxt) | (hi - nxt > self.depth) | ((col["started"] != 0) & (col["started"] != 1)) |
+               ((col["started"] == 0) & (hi != 0)) | (gap < -1) | (gap >= nxt) | (stats < 0).any(axis=1) |
+               (stats[:, 3] > nxt) | (col["max_seq"] < -1) | (col["max_seq"] > 0xFFFF) | (col["ssrc"] < -1) | (col["ssrc"] >= 1 << 32))
+        if bad.any() or not np.array_equal(made, state.seen.numpy() + fill):
+            raise ValueError("import_slots: a session's counters contradict each other")
+        lists = []
+        for i in range(n):
+            v = [r for r in table[i].tolist() if r != [-1, -1]]
+            ok = all(a < e for a, e in v) and all(p[1] < q[0] for p, q in zip(v, v[1:])) and (not v or (v[0][0] >= nxt[i] and v[-1][1] == hi[i]))
+            if not ok or (not v and hi[i] != nxt[i]) or sum(e - a for a, e in v) > stats[i, 0]:
+                raise ValueError("import_slots: a session's received intervals contradict its counters")
+            lists.append(v)
+        inner = StreamState({k: v for k, v in state.meta.items() if k not in _META_KEYS}, state.seen,
+                            {k: t for k, t in state.tensors.items() if k not in _STATE_KEYS})
+        self.scorer.import_slots(idx, inner)  # (refuses a foreign state before changing anything)
+        if not idx:
+            return
+        dev, b = self.device, self._b
+        with _on(dev):
+            rows = torch.tensor(idx, dtype=torch.long, device=dev)
+            w = min(pend.shape[1], self.ring_len)
+            self.ring[rows, :w] = pend[:, :w].to(dev)
+            self.jring[rows] = 0.0
+            k = torch.arange(width)
+            cols = (torch.from_numpy(nxt.copy())[:, None] - self.lookback + k) % self.J
+            self.jring[rows[:, None], cols.to(dev)] = jr.to(dev)
+        b.clear(idx)
+        for f in _BOOK:
+            getattr(b, f)[idx] = col[f]
+        for c, f in enumerate(_COUNTERS):
+            getattr(b, f)[idx] = stats[:, c]
+        b.fill[idx] = fill
+        for s, v in zip(idx, lists):
+            b.set_intervals(s, v)

@@ -2874,6 +2874,18 @@ extern "C" int afx_k_ingest_pop(const float* ring, int S, int ring_len, const in
                                 void* stream) {
   KRET(launch_ingest_pop(ring, S, ring_len, table, A, hop, out, (hipStream_t)stream));
 }
+extern "C" int afx_k_jitter_place(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n, int encoding,
+                                  float* jring, int S, int J, void* stream) {
+  KRET(launch_jitter_place(stage, stage_bytes, hdr, rows, max_n, encoding, jring, S, J, (hipStream_t)stream));
+}
+extern "C" int afx_k_jitter_conceal(float* jring, int S, int J, const int* hdr, int rows, int max_n, const float* fade, int P,
+                                    int F, int mode, void* stream) {
+  KRET(launch_jitter_conceal(jring, S, J, hdr, rows, max_n, fade, P, F, mode, (hipStream_t)stream));
+}
+extern "C" int afx_k_jitter_release(const float* jring, int S, int J, const int* hdr, int rows, int max_out, const float* taps,
+                                    int L, int M, int T, float* ring, int ring_len, void* stream) {
+  KRET(launch_jitter_release(jring, S, J, hdr, rows, max_out, taps, L, M, T, ring, ring_len, (hipStream_t)stream));
+}
 extern "C" int afx_k_rownorm(int dtype, const float* x, long ldx, int rows, int C, const float* gamma,
                              const float* beta, float eps, int act, float* out_f, long ldo_f, void* out_h, long ldo_h,
                              void* stream) {

@@ -961,6 +961,192 @@ const char* launch_ingest_pop(const float* ring, int S, int ring_len, const int*
 }
 
 // ---------------------------------------------------------------------------------
+// Jitter buffer (afx/jitter.py; the functions are stated in include/afx.h afx_k_jitter_place / _conceal / _release): one
+// DECODED reorder ring per slot, jring (S, J) fp32, input-rate sample i of the slot's played-out stream E at column i mod J.
+// The host keeps every index (playout point `next`, received intervals, gaps) and plans rounds so that, with
+// lookback = max(T - 1, P + F) and W = J - lookback, every launch of a round that has released E up to `cur` touches only
+// indices in [cur - lookback, cur + W): a window of J consecutive indices, so no two of them share a column.  That is the
+// sizing invariant: what place writes at i >= cur destroys only i - J < cur - lookback, which neither the filter (T - 1
+// samples back) nor a fading gap (source [a - P, a), read until a + F) will read again.
+//   place:   decodes sub-ranges of packets into their columns (the rows of one launch are disjoint: the host splits a packet
+//            at the playout point and at what was received before; first arrival wins).
+//   conceal: writes a released gap's samples INTO the ring (zeros, or the faded repetition of the P samples before the
+//            gap), so that a later gap, and the filter, read them as they read received samples.  Gaps of one slot are
+//            ordered by the host: one launch per rank of gap within the slot.
+//   release: ingest_kernel's body with the ring in place of a decoded payload: outputs n_done .. of the stream from
+//            ring[(a0 + k) mod J], k >= -(T-1), into the slot's pending 16 kHz ring.  Same sub-tiles, tap staging, fp32
+//            taps and ascending-j fmaf chain, so output n has the bits afx_k_resample gives it over all of E.
+// ---------------------------------------------------------------------------------
+constexpr int JIT_PLACE_HDR = 4;    // ints per row: slot, byte offset of the first sample, n, ring column of the first sample
+constexpr int JIT_CONCEAL_HDR = 4;  // ints per row: slot, ring column of the gap origin a, d_lo, d_hi
+constexpr int JIT_RELEASE_HDR = 8;  // ints per row: slot, ring column of a0, n_in, n_out, p0, d0, wpos, 0
+
+__global__ __launch_bounds__(256) void jitter_place_kernel(const unsigned char* __restrict__ stage, long long stage_bytes,
+                                                           const int* __restrict__ hdr, int enc, float* __restrict__ jring,
+                                                           int S, int J) {
+  const int* h = hdr + (long long)blockIdx.y * JIT_PLACE_HDR;
+  const int slot = h[0], n = h[2], col = h[3];
+  const long long off = h[1];
+  const int bps = ingest_bytes_per_sample(enc);
+  if (!(slot >= 0 && slot < S && n >= 0 && n <= J && col >= 0 && col < J && off >= 0 && (off & (bps - 1)) == 0 &&
+        off + (long long)n * bps <= stage_bytes))
+    return;
+  const unsigned char* pay = stage + off;
+  float* row = jring + (long long)slot * J;
+  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += gridDim.x * blockDim.x) {
+    const int w = col + k;
+    row[w < J ? w : w - J] = ingest_sample(pay, k, enc);
+  }
+}
+
+const char* launch_jitter_place(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n, int enc,
+                                float* jring, int S, int J, hipStream_t s) {
+  if (!stage || !hdr || !jring || stage_bytes <= 0) return "jitter_place: null staging buffer, header table or ring";
+  if (enc < 0 || enc > 3) return "jitter_place: encoding 0 (pcm_f32le), 1 (pcm_s16le), 2 (mulaw) or 3 (alaw)";
+  if (rows <= 0 || rows > 65535) return "jitter_place: 1 to 65535 rows";
+  if (S <= 0 || J <= 0 || max_n < 0 || max_n > J) return "jitter_place: a row's samples must fit its slot's ring";
+  if (max_n == 0) return nullptr;
+  hipLaunchKernelGGL(jitter_place_kernel, dim3(min((max_n + 255) / 256, 64), rows), dim3(256), 0, s,
+                     (const unsigned char*)stage, stage_bytes, hdr, enc, jring, S, J);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+// E[a + d] for d in [d_lo, d_hi): 0 (mode 0, or d >= F), else fade[d] * E[a - P + d mod P] (one fp32 multiply of two stored
+// values).  The source columns [a - P, a) and the written ones [a + d_lo, a + d_hi) are disjoint for d_hi + P <= J.
+__global__ __launch_bounds__(256) void jitter_conceal_kernel(float* __restrict__ jring, int S, int J, const int* __restrict__ hdr,
+                                                             const float* __restrict__ fade, int P, int F, int mode) {
+  const int* h = hdr + (long long)blockIdx.y * JIT_CONCEAL_HDR;
+  const int slot = h[0], ac = h[1], lo = h[2], hi = h[3];
+  if (!(slot >= 0 && slot < S && ac >= 0 && ac < J && lo >= 0 && hi >= lo && (long long)hi + P <= J)) return;
+  float* row = jring + (long long)slot * J;
+  const int src0 = ac >= P ? ac - P : ac - P + J;
+  for (int d = lo + blockIdx.x * blockDim.x + threadIdx.x; d < hi; d += gridDim.x * blockDim.x) {
+    float v = 0.f;
+    if (mode == 1 && d < F) {
+      const int c = src0 + d % P;
+      v = fade[d] * row[c < J ? c : c - J];
+    }
+    const int w = ac + d;  // < 2 J
+    row[w < J ? w : w - J] = v;
+  }
+}
+
+const char* launch_jitter_conceal(float* jring, int S, int J, const int* hdr, int rows, int max_n, const float* fade, int P,
+                                  int F, int mode, hipStream_t s) {
+  if (!jring || !hdr) return "jitter_conceal: null ring or header table";
+  if (mode != 0 && mode != 1) return "jitter_conceal: mode 0 (zero) or 1 (repeat)";
+  if (mode == 1 && (!fade || P <= 0 || F < 0)) return "jitter_conceal: repeat needs a fade table, a period and a fade length";
+  if (rows <= 0 || rows > 65535) return "jitter_conceal: 1 to 65535 rows";
+  if (mode == 0) { P = 0; F = 0; }
+  if (S <= 0 || J <= 0 || max_n < 0 || (long long)max_n + P > J) return "jitter_conceal: a row's samples and its source must fit the ring";
+  if (max_n == 0) return nullptr;
+  hipLaunchKernelGGL(jitter_conceal_kernel, dim3(min((max_n + 255) / 256, 64), rows), dim3(256), 0, s, jring, S, J, hdr, fade,
+                     P, F, mode);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+struct JitterReleaseArgs {
+  const float* jring;            // (S, J) decoded input-rate samples
+  const int* hdr;                // (rows, JIT_RELEASE_HDR)
+  const float* taps;             // (L, T), nullptr = identity
+  float* ring;                   // (S, ring_len) pending 16 kHz samples
+  int J, L, M, T, Tp, R, S, ring_len;
+};
+
+template <bool IDENT, bool LDS_TAPS>
+__global__ __launch_bounds__(256) void jitter_release_kernel(JitterReleaseArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float jit_lds[];
+  const int* h = a.hdr + (long long)blockIdx.y * JIT_RELEASE_HDR;
+  const int slot = h[0], col0 = h[1], n_in = h[2], n_out = h[3], p0r = h[4], d0 = h[5], wpos = h[6];
+  if (!(slot >= 0 && slot < a.S && col0 >= 0 && col0 < a.J && n_in >= 0 && n_in <= a.J && n_out >= 0 && n_out <= a.ring_len &&
+        wpos >= 0 && wpos < a.ring_len && p0r >= 0 && p0r < a.L && d0 >= 0))
+    return;
+  const float* src = a.jring + (long long)slot * a.J;
+  float* out = a.ring + (long long)slot * a.ring_len;
+  if (IDENT) {
+    for (int r = 0; r < a.R; ++r) {
+      const int k = (blockIdx.x * a.R + r) * RS_TILE + threadIdx.x;
+      if (k >= n_out || k >= n_in) break;
+      const int c = col0 + k, w = wpos + k;
+      out[w < a.ring_len ? w : w - a.ring_len] = src[c < a.J ? c : c - a.J];
+    }
+    return;
+  }
+  const int T = a.T;
+  if ((long long)blockIdx.x * a.R * RS_TILE >= n_out) return;
+  const float* tp = a.taps;
+  int ts = T;
+  float* xs = jit_lds;
+  if (LDS_TAPS) {
+    for (int k = threadIdx.x; k < a.L * a.Tp; k += blockDim.x) {
+      const int p = k / a.Tp, j = k - p * a.Tp;
+      jit_lds[k] = j < T ? a.taps[p * T + j] : 0.f;
+    }
+    tp = jit_lds;
+    ts = a.Tp;
+    xs = jit_lds + a.L * a.Tp;
+  }
+  for (int r = 0; r < a.R; ++r) {
+    const int n0 = (blockIdx.x * a.R + r) * RS_TILE;
+    if (n0 >= n_out) break;
+    const int cnt = min(RS_TILE, n_out - n0);
+    const long long q0 = (long long)n0 * a.M + p0r, b0 = q0 / a.L;
+    const int p0 = (int)(q0 - b0 * a.L);
+    const int base = d0 + (int)b0;  // the position from a0 of output n0's newest input
+    const int span = (int)(((long long)(cnt - 1) * a.M + p0) / a.L) + T;
+    __syncthreads();  // the previous sub-tile is done with xs
+    for (int s = threadIdx.x; s < span; s += blockDim.x) {
+      const int k = base - (T - 1) + s;  // >= -(T-1) >= -J; < n_in <= J for every output the host counted
+      int c = col0 + k;
+      c = c < 0 ? c + a.J : (c < a.J ? c : c - a.J);
+      xs[s] = k < n_in ? src[c] : 0.f;
+    }
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < cnt) {
+      const unsigned q = (unsigned)t * (unsigned)a.M + (unsigned)p0;
+      const int di = (int)(q / (unsigned)a.L), p = (int)(q - (unsigned)di * (unsigned)a.L);
+      const float* w = tp + (long)p * ts;
+      const float* xv = xs + di + T - 1;
+      float acc = 0.f;
+      for (int j = 0; j < T; ++j) acc = __builtin_fmaf(w[j], xv[-j], acc);
+      const int wp = wpos + n0 + t;
+      out[wp < a.ring_len ? wp : wp - a.ring_len] = acc;
+    }
+  }
+}
+
+const char* launch_jitter_release(const float* jring, int S, int J, const int* hdr, int rows, int max_out, const float* taps,
+                                  int L, int M, int T, float* ring, int ring_len, hipStream_t s) {
+  if (!jring || !hdr || !ring) return "jitter_release: null ring or header table";
+  if (rows <= 0 || rows > 65535) return "jitter_release: 1 to 65535 rows";
+  if (S <= 0 || J <= 0 || ring_len <= 0 || max_out < 0 || max_out > ring_len) return "jitter_release: a row's outputs must fit its slot's ring";
+  if (L <= 0 || M <= 0 || T <= 0) return "jitter_release: bad filter shape";
+  const bool ident = taps == nullptr;
+  if (ident && (L != 1 || M != 1 || T != 1)) return "jitter_release: no taps is the identity (L = M = T = 1)";
+  if (T - 1 > J) return "jitter_release: the filter history must fit the ring";
+  if (max_out == 0) return nullptr;
+  const long long span = (255LL * M + L - 1) / L + T;
+  if (span > RS_SPAN_MAX) return "jitter_release: input / output ratio above 12";
+  JitterReleaseArgs a{};
+  a.jring = jring; a.hdr = hdr; a.taps = taps; a.ring = ring;
+  a.J = J; a.L = L; a.M = M; a.T = T; a.S = S; a.ring_len = ring_len;
+  a.Tp = T | 1;
+  a.R = 1;
+  const bool lds_taps = !ident && (long long)L * a.Tp <= RS_TAPS_LDS;
+  if (lds_taps) a.R = max(1, min(8, L * a.Tp / 1024));  // amortise the tap staging of many-phase ratios
+  const dim3 grid((unsigned)((max_out + RS_TILE * a.R - 1) / (RS_TILE * a.R)), rows);
+  const size_t lds = ident ? 0 : sizeof(float) * (size_t)((lds_taps ? L * a.Tp : 0) + span);
+  if (ident) hipLaunchKernelGGL((jitter_release_kernel<true, false>), grid, dim3(256), lds, s, a);
+  else if (lds_taps) hipLaunchKernelGGL((jitter_release_kernel<false, true>), grid, dim3(256), lds, s, a);
+  else hipLaunchKernelGGL((jitter_release_kernel<false, false>), grid, dim3(256), lds, s, a);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+// ---------------------------------------------------------------------------------
 // Row LayerNorm (+ activation): one wave per row, C <= 1024, C % 4 == 0.  The row
 // stays in registers (float4 per lane per 256-column slab), two-pass statistics in
 // fp32 like torch.  Used for the conv-stack LayerNorm+GELU, every transformer /

@@ -145,6 +145,14 @@ const char* launch_ingest(const void* stage, long long stage_bytes, const int* h
                           hipStream_t s);
 const char* launch_ingest_pop(const float* ring, int S, int ring_len, const int* table, int A, int hop, float* out,
                               hipStream_t s);
+// jitter buffer (include/afx.h afx_k_jitter_place / _conceal / _release): packet sub-ranges decoded into each slot's reorder
+// ring at their timestamps' columns; released gaps concealed in the ring; released samples resampled into the pending ring
+const char* launch_jitter_place(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n, int enc,
+                                float* jring, int S, int J, hipStream_t s);
+const char* launch_jitter_conceal(float* jring, int S, int J, const int* hdr, int rows, int max_n, const float* fade, int P,
+                                  int F, int mode, hipStream_t s);
+const char* launch_jitter_release(const float* jring, int S, int J, const int* hdr, int rows, int max_out, const float* taps,
+                                  int L, int M, int T, float* ring, int ring_len, hipStream_t s);
 void conv0_set_mfma(int v);  // A/B knob: 1 (default) = matrix-core forms (split-precision fp16 when packed), 2 = fp32 MFMA form, 0 = VALU form
 // y[t] = x[t] - coef * x[t-1] with a reflect pad on the left; (B,L) fp32 -> (B,L) fp32
 const char* launch_pre_emphasis(const float* x, int B, int L, float coef, float* y, hipStream_t s);
