@@ -47,20 +47,18 @@ import numpy as np
 import torch
 
 from . import rtp
-from ._lib import AfxError, call_on, check, lib, ptr
-from .ingest import _SAMPLE, ENCODINGS, FeedResult, _at, _encoding, layout, pack, payload
-from .resample import FILTER_ID, Resampler
-from .streaming import StreamState, _on
+from ._lib import call_on, check, lib, ptr
+from .ingest import _MAX_SAMPLES, _SAMPLE, ENCODINGS, _at, _encoding, layout
+from .resample import FILTER_ID
+from .streaming import _Front, _on
 
 JITTER_FORMAT = 1  # layout of the jitter part of a StreamState: import_slots refuses any other
 CONCEAL = ("zero", "repeat")  # the library's mode numbers 0, 1
 PLACE_HDR, CONCEAL_HDR, RELEASE_HDR = 4, 4, 8  # int32 per row of the three tables (include/afx.h)
 STATS = ("received", "late", "duplicate", "concealed", "out_of_order")
 _STATE_KEYS = ("jitter_pending", "jitter_fill", "jitter_ring", "jitter_book", "jitter_stats", "jitter_intervals")
-_META_KEYS = ("input_rate", "resampler", "jitter", "jitter_depth", "jitter_conceal", "jitter_period", "jitter_fade")
 _BOOK = ("origin", "started", "next", "hi", "gap", "max_start", "max_seq", "ssrc")  # jitter_book columns
 _COUNTERS = ("received", "late", "dup", "concealed", "ooo")  # jitter_stats columns (STATS order)
-_MAX_SAMPLES = 1 << 30
 
 
 def _nonneg_int(v, name, least=0):
@@ -151,27 +149,28 @@ class Plan:
         self.ops, self.slots, self.counts, self.book = ops, slots, counts, book
 
 
-class JitterScorer:
+class JitterScorer(_Front):
     """``scorer`` (a SlidingWindowScorer, IncrementalScorer or KVCachedScorer) fed timestamped packets at ``input_rate`` Hz
     in ``encoding`` (``afx.ingest.ENCODINGS``); see the module docstring for the contract.
 
-    ``depth``: the playout delay in input samples (60 ms is common; 0 is legal).  ``conceal``: "repeat" or "zero".
-    ``period``: the repeat period P in input samples, default 10 ms (input_rate // 100).  ``fade``: the fade length F in
+    ``depth``: the playout delay in input samples (60 ms is common; 0 is legal; the filter's ``delay`` comes on top of it).
+    ``conceal``: "repeat" or "zero".  ``period``: the repeat period P in input samples, default 10 ms (input_rate // 100).  ``fade``: the fade length F in
     input samples, default 3 P (30 ms).  ``max_pending``: the whole hops a slot may buffer between ``feed(..., score=False)``
     and ``drain``.  ``ts_bits``: 32 (default) unwraps each timestamp to the value nearest the slot's ``hi``, so a stream
     crossing 2**32 is seamless; None takes absolute indices."""
+
+    _WORK = "decoded, concealed, resampled"
 
     def __init__(self, scorer, input_rate, encoding, depth, conceal="repeat", period=None, fade=None, max_pending=4, ts_bits=32):
         self.encoding = _encoding(encoding)
         self.depth = _nonneg_int(depth, "depth")
         if conceal not in CONCEAL:
             raise ValueError(f"conceal {conceal!r}: one of {CONCEAL}")
-        self.max_pending = _nonneg_int(max_pending, "max_pending", 1)
+        max_pending = _nonneg_int(max_pending, "max_pending", 1)
         if ts_bits is not None and (isinstance(ts_bits, bool) or not isinstance(ts_bits, (int, np.integer)) or not 8 <= ts_bits <= 48):
             raise ValueError("ts_bits: None (absolute indices) or the width of the timestamp counter, 8..48")
         self.ts_bits = None if ts_bits is None else int(ts_bits)
-        self.rs = Resampler(input_rate, scorer.device)  # (a bad rate is a ValueError here)
-        self.scorer, self.input_rate, self.hop = scorer, self.rs.rate, scorer.hop
+        super().__init__(scorer, input_rate)
         self.L, self.M = self.rs.L, self.rs.M
         self.conceal = conceal
         if conceal == "repeat":
@@ -179,47 +178,24 @@ class JitterScorer:
             self.fade_len = _nonneg_int(3 * self.period if fade is None else fade, "fade")
         else:
             self.period = self.fade_len = 0  # (no part of the "zero" function: not recorded in a state either)
-        T = 1 if self.rs.identity else self.rs.T
         # the sizing invariant (module docstring): J = lookback + W, W >= depth; the slack beyond depth is what a round can
         # place and release at once (one hop of input: an ordinary packet never takes a second round)
-        self.lookback = max(T - 1, self.period + self.fade_len)
-        self.W = self.depth + -(-self.hop * self.M // self.L) + 1
+        self.lookback = max(0 if self.rs.identity else self.rs.T - 1, self.period + self.fade_len)
+        self.W = self.depth + -(-scorer.hop * self.M // self.L) + 1
         self.J = self.lookback + self.W
         if self.J >= _MAX_SAMPLES:
             raise ValueError("depth + period + fade: less than 2**30 samples")
-        dev = scorer.device
-        self.ring_len = (self.max_pending + 1) * self.hop  # as PacketScorer: a scoring call always finds room
-        self.ring = torch.zeros(scorer.S, self.ring_len, dtype=torch.float32, device=dev)
-        self.jring = torch.zeros(scorer.S, self.J, dtype=torch.float32, device=dev)
+        self._new_ring(max_pending)
+        self.jring = torch.zeros(scorer.S, self.J, dtype=torch.float32, device=scorer.device)
         F = self.fade_len
         table = (1.0 - np.arange(max(F, 1), dtype=np.float64) / max(F, 1)).astype(np.float32)
-        self.fade = torch.from_numpy(table).to(dev)
+        self.fade = torch.from_numpy(table).to(scorer.device)
         self._b = _Book(scorer.S)
 
     # ---- properties ----------------------------------------------------------------------------------------------------
     @property
-    def S(self):
-        return self.scorer.S
-
-    @property
-    def device(self):
-        return self.scorer.device
-
-    @property
-    def delay(self):
-        """The resampled stream's lag behind resample_poly's centred output, in 16 kHz samples (the playout ``depth``, in
-        input samples, comes on top of it)."""
-        return self.rs.delay
-
-    @property
-    def samples_seen(self):
-        """(S,) int64: the 16 kHz samples each slot's inner session has been pushed since its last ``reset``."""
-        return self.scorer.samples_seen
-
-    @property
-    def pending(self):
-        """(S,) int64: the 16 kHz samples waiting in each slot's buffer."""
-        return torch.from_numpy(self._b.fill.copy())
+    def _fill(self):
+        return self._b.fill
 
     @property
     def samples_in(self):
@@ -422,15 +398,7 @@ class JitterScorer:
                 cur[k] += m[k]
                 fill[k] += n_out
                 progress = True
-            while score:
-                ready = fill >= hop
-                if not ready.any():
-                    break
-                s = U[ready]
-                ops.append(("pop", np.stack([s, head[ready]], axis=1).astype(np.int32), s.tolist()))
-                head[ready] = (head[ready] + hop) % R
-                fill[ready] -= hop
-                counts += ready
+            if score and self._pop_rounds(ops, U, head, fill, counts):
                 progress = True
             if (pdone == pn).all() and (cur == tgt).all():
                 break
@@ -490,17 +458,9 @@ class JitterScorer:
     def _plan_feed(self, packets, slots, timestamps, score=True, seqs=None):
         """The checks and the plan of a ``feed`` -> (Plan, payload blocks).  No state changes."""
         idx = self._rows(slots, repeats=True)
-        if isinstance(packets, (bytes, bytearray, memoryview, np.ndarray, torch.Tensor)):
-            raise ValueError("packets: a list with one packet per named slot")
-        packets = list(packets)
-        if len(packets) != len(idx):
-            raise ValueError(f"{len(packets)} packets for {len(idx)} named slots")
+        pay, nbytes = self._packets(packets, len(idx), self.encoding)
         ts = self._timestamps(timestamps, len(idx))
         bps = _SAMPLE[self.encoding].itemsize
-        pay = [p if type(p) is bytes else payload(p, self.encoding) for p in packets]
-        nbytes = np.fromiter(map(len, pay), dtype=np.int64, count=len(pay))
-        for i in np.flatnonzero((nbytes % bps != 0) | (nbytes // bps >= _MAX_SAMPLES)):
-            payload(pay[i], self.encoding)  # (raises, with the message)
         offs, total = layout(nbytes)
         if total >= 1 << 31:
             raise ValueError("a feed carries less than 2 GiB")
@@ -557,54 +517,23 @@ class JitterScorer:
         return self._run(self._plan(idx, mode="drain"), [])
 
     def _run(self, plan, pay):
-        ops, dev = plan.ops, self.device
-        counts = torch.from_numpy(plan.counts)
-        if not ops:
-            self._commit(plan.book)
-            return FeedResult(counts, torch.empty(0, dtype=torch.float32, device=dev))
-        if dev.type != "cuda":
-            raise AfxError("packets are decoded, concealed, resampled and scored on the GPU; there is no CPU fallback")
-        # where each score of the result sits in the concatenation of the pop rounds' outputs (a table when it is not in order)
-        pos, base = {s: [] for s in plan.slots}, 0
-        for op in ops:
-            if op[0] == "pop":
-                for k, s in enumerate(op[2]):
-                    pos[s].append(base + k)
-                base += len(op[2])
-        perm = [p for s in plan.slots for p in pos[s]]
-        tables = [op[1] for op in ops]
-        if perm != list(range(base)):
-            tables.append(np.array(perm, dtype=np.int64))
-        buf, _, toffs = pack(pay, tables, pinned=True)
-        enc, taps = ENCODINGS.index(self.encoding), (None if self.rs.identity else ptr(self.rs.taps))
-        T = 1 if self.rs.identity else self.rs.T
+        enc, (taps, L, M, T) = ENCODINGS.index(self.encoding), self._filter()
         l, S, J = lib(), self.S, self.J
-        outs = []
-        with torch.cuda.device(dev):
-            d = buf.to(dev, non_blocking=True)  # the one upload
-            for op, off in zip(ops, toffs):
-                if op[0] == "place":
-                    check(call_on(self.jring, l.afx_k_jitter_place, _at(d, 0), d.numel(), _at(d, off), len(op[1]), op[2], enc,
-                                  ptr(self.jring), S, J))
-                elif op[0] == "conceal":
-                    check(call_on(self.jring, l.afx_k_jitter_conceal, ptr(self.jring), S, J, _at(d, off), len(op[1]), op[2],
-                                  ptr(self.fade), self.period, self.fade_len, CONCEAL.index(self.conceal)))
-                elif op[0] == "release":
-                    check(call_on(self.jring, l.afx_k_jitter_release, ptr(self.jring), S, J, _at(d, off), len(op[1]), op[2], taps,
-                                  self.L, self.M, T, ptr(self.ring), self.ring_len))
-                else:
-                    chunk = torch.empty(len(op[2]), self.hop, dtype=torch.float32, device=dev)
-                    check(call_on(self.ring, l.afx_k_ingest_pop, ptr(self.ring), S, self.ring_len, _at(d, off), len(op[2]),
-                                  self.hop, ptr(chunk)))
-                    sc = self.scorer.push(chunk, op[2])
-                    if sc is None:
-                        raise RuntimeError("the inner scorer emitted no score for a hop")
-                    outs.append(sc)
-            self._commit(plan.book)  # (the bookkeeping follows the device state: set once every launch has been issued)
-            scores = torch.cat(outs) if outs else torch.empty(0, dtype=torch.float32, device=dev)
-            if len(tables) > len(ops):
-                scores = scores.index_select(0, d[toffs[-1]:toffs[-1] + 8 * base].view(torch.int64))
-        return FeedResult(counts, scores)
+
+        def place(d, off, op):
+            check(call_on(self.jring, l.afx_k_jitter_place, _at(d, 0), d.numel(), _at(d, off), len(op[1]), op[2], enc, ptr(self.jring),
+                          S, J))
+
+        def conceal(d, off, op):
+            check(call_on(self.jring, l.afx_k_jitter_conceal, ptr(self.jring), S, J, _at(d, off), len(op[1]), op[2], ptr(self.fade),
+                          self.period, self.fade_len, CONCEAL.index(self.conceal)))
+
+        def release(d, off, op):
+            check(call_on(self.jring, l.afx_k_jitter_release, ptr(self.jring), S, J, _at(d, off), len(op[1]), op[2], taps, L, M, T,
+                          ptr(self.ring), self.ring_len))
+
+        return self._execute(plan.ops, plan.slots, plan.counts, pay, {"place": place, "conceal": conceal, "release": release},
+                             lambda: self._commit(plan.book))
 
     # ---- sessions ----------------------------------------------------------------------------------------------------
     def reset(self, slots):
@@ -619,9 +548,6 @@ class JitterScorer:
         return dict(input_rate=self.input_rate, resampler=FILTER_ID, jitter=JITTER_FORMAT, jitter_depth=self.depth,
                     jitter_conceal=self.conceal, jitter_period=self.period, jitter_fade=self.fade_len)
 
-    def state_meta(self):
-        return dict(self.scorer.state_meta(), **self._meta())
-
     def export_slots(self, slots):
         """The inner scorer's ``StreamState`` of the named slots plus their jitter-buffer sessions (module docstring).  What is
         stored is decoded.  No byte of the scorer changes."""
@@ -630,15 +556,9 @@ class JitterScorer:
         dev, b = self.device, self._b
         width = self.lookback + self.depth
         with _on(dev):
-            rows = torch.tensor(idx, dtype=torch.long, device=dev)
-            fill = torch.from_numpy(b.fill[idx])
-            j = torch.arange(self.max_pending * self.hop)
-            cols = (torch.from_numpy(b.head[idx])[:, None] + j) % self.ring_len
-            pend = self.ring[rows[:, None], cols.to(dev)]
-            pend.masked_fill_((j[None, :] >= fill[:, None]).to(dev), 0.0)
             nxt, held = torch.from_numpy(b.next[idx]), torch.from_numpy(b.hi[idx] - b.next[idx])
             k = torch.arange(width)
-            jr = self.jring[rows[:, None], ((nxt[:, None] - self.lookback + k) % self.J).to(dev)]
+            jr = self.jring[self._dev_rows(idx)[:, None], ((nxt[:, None] - self.lookback + k) % self.J).to(dev)]
             jr.masked_fill_((k[None, :] >= self.lookback + held[:, None]).to(dev), 0.0)
         ivs = [b.intervals(s) for s in idx]
         K = max([len(v) for v in ivs] + [1])
@@ -648,23 +568,16 @@ class JitterScorer:
                 table[i, :len(v)] = v
         book = np.stack([getattr(b, f)[idx] for f in _BOOK], axis=1).reshape(len(idx), len(_BOOK))
         stats = np.stack([getattr(b, f)[idx] for f in _COUNTERS], axis=1).reshape(len(idx), len(_COUNTERS))
-        tensors = dict(st.tensors, jitter_pending=pend, jitter_fill=fill.clone(), jitter_ring=jr, jitter_book=torch.from_numpy(book),
-                       jitter_stats=torch.from_numpy(stats), jitter_intervals=torch.from_numpy(table))
-        return StreamState(dict(st.meta, **self._meta()), st.seen, tensors)
+        return self._wrap(st, jitter_pending=self._export_pending(idx, b.head[idx], b.fill[idx]), jitter_fill=torch.from_numpy(b.fill[idx]),
+                          jitter_ring=jr, jitter_book=torch.from_numpy(book), jitter_stats=torch.from_numpy(stats),
+                          jitter_intervals=torch.from_numpy(table))
 
     def import_slots(self, slots, state):
         """The named slots take over the sessions of ``state``, a state of a JitterScorer with the same input rate, filter,
         depth, concealment mode, period and fade whose pending samples fit this scorer's ``max_pending``; anything else,
         or a state whose counters contradict each other, is a ValueError before anything changes."""
         idx = self.scorer._slot_list(slots, ordered=True)
-        if not isinstance(state, StreamState):
-            raise ValueError("import_slots takes a StreamState (export_slots / StreamState.from_state_dict)")
-        if any(k not in state.tensors for k in _STATE_KEYS) or any(k not in state.meta for k in _META_KEYS):
-            raise ValueError("import_slots: the state has no jitter-buffer part (it was not exported by a JitterScorer)")
-        mine = self._meta()
-        for k in _META_KEYS:
-            if state.meta[k] != mine[k]:
-                raise ValueError(f"import_slots: the state's {k} {state.meta[k]!r} is not this scorer's {mine[k]!r}")
+        inner = self._peel(state, _STATE_KEYS, self._meta(), "jitter-buffer part (it was not exported by a JitterScorer)")
         n = len(state)
         pend, jr = state.tensors["jitter_pending"], state.tensors["jitter_ring"]
         ints = [state.tensors[k].cpu() for k in ("jitter_fill", "jitter_book", "jitter_stats", "jitter_intervals")]
@@ -674,14 +587,10 @@ class JitterScorer:
         fill = fill.reshape(-1)
         if fill.size != n or book.shape != (n, len(_BOOK)) or stats.shape != (n, len(_COUNTERS)) or table.ndim != 3 or table.shape[2] != 2:
             raise ValueError("import_slots: jitter_fill (n,), jitter_book (n, 8), jitter_stats (n, 5), jitter_intervals (n, K, 2)")
-        if pend.ndim != 2 or pend.shape[0] != n or pend.dtype != torch.float32:
-            raise ValueError(f"import_slots: jitter_pending {tuple(pend.shape)} {pend.dtype} is not (n, pending) float32")
         width = self.lookback + self.depth
         if tuple(jr.shape) != (n, width) or jr.dtype != torch.float32:
             raise ValueError(f"import_slots: jitter_ring {tuple(jr.shape)} {jr.dtype} does not fit this scorer ({(n, width)} float32)")
-        if (fill < 0).any() or (fill > pend.shape[1]).any() or (fill > self.max_pending * self.hop).any():
-            raise ValueError(f"import_slots: a session holds more pending samples than max_pending = {self.max_pending} hops "
-                             f"of {self.hop} (or than its own buffer)")
+        self._check_pending("jitter_pending", pend, fill, n)
         col = {f: book[:, c] for c, f in enumerate(_BOOK)}
         nxt, hi, gap = col["next"], col["hi"], col["gap"]
         made = np.array([-(-int(v) * self.L // self.M) for v in nxt.tolist()], dtype=np.int64)
@@ -697,16 +606,13 @@ class JitterScorer:
             if not ok or (not v and hi[i] != nxt[i]) or sum(e - a for a, e in v) > stats[i, 0]:
                 raise ValueError("import_slots: a session's received intervals contradict its counters")
             lists.append(v)
-        inner = StreamState({k: v for k, v in state.meta.items() if k not in _META_KEYS}, state.seen,
-                            {k: t for k, t in state.tensors.items() if k not in _STATE_KEYS})
         self.scorer.import_slots(idx, inner)  # (refuses a foreign state before changing anything)
         if not idx:
             return
         dev, b = self.device, self._b
+        self._import_pending(idx, pend)
         with _on(dev):
-            rows = torch.tensor(idx, dtype=torch.long, device=dev)
-            w = min(pend.shape[1], self.ring_len)
-            self.ring[rows, :w] = pend[:, :w].to(dev)
+            rows = self._dev_rows(idx)
             self.jring[rows] = 0.0
             k = torch.arange(width)
             cols = (torch.from_numpy(nxt.copy())[:, None] - self.lookback + k) % self.J

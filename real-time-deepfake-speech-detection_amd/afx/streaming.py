@@ -53,11 +53,13 @@ same row-wise argument), and the other slots of the destination are untouched.
 import contextlib
 import hashlib
 
+import numpy as np
 import torch
 
 from . import harness
 from . import kernels as K
-from ._lib import call_on, check, lib, ptr, stream_ptr
+from ._lib import AfxError, call_on, check, lib, ptr, stream_ptr
+from .resample import FILTER_ID, TARGET_RATE, Resampler
 
 CONV_KS = [(10, 5), (3, 2), (3, 2), (3, 2), (3, 2), (2, 2), (2, 2)]
 STATE_FORMAT = 1  # StreamState layout version: import_slots refuses any other
@@ -135,6 +137,197 @@ class StreamState:
         if d["meta"].get("format") != STATE_FORMAT:
             raise ValueError(f"StreamState format {d['meta'].get('format')!r}, this build reads format {STATE_FORMAT}")
         return cls(d["meta"], d["seen"], d["tensors"])
+
+
+class FeedResult:
+    """What a ``feed`` / ``drain`` completed: ``counts`` (len(slots),) int64 on the host, the hops each named slot
+    completed; ``scores`` (counts.sum(),) fp32 on the scorer's device, the first named slot's scores in hop order, then the
+    second's, ...; ``split()``: the per-slot score tensors (views)."""
+
+    def __init__(self, counts, scores):
+        self.counts, self.scores = counts, scores
+
+    def split(self):
+        return list(self.scores.split(self.counts.tolist()))
+
+
+class _Front:
+    """What the wrappers that stand in front of a streaming scorer share (``ResamplingScorer``, ``afx.ingest.PacketScorer``,
+    ``afx.jitter.JitterScorer``): the inner ``scorer``, the ``Resampler`` of their input rate, and, for the two that take
+    packets, the pending ring ((S, ring_len) fp32 of 16 kHz samples per slot, its head and fill kept on the host), the
+    pop rounds that hand its whole hops to the inner scorer, the execution of a planned call and the session moves."""
+
+    _WORK = "resampled"  # what the device does for this front (the refusal of a scorer that has no GPU behind it)
+
+    def __init__(self, scorer, input_rate):
+        self.rs = Resampler(input_rate, scorer.device)  # (a bad rate is a ValueError here)
+        self.scorer, self.input_rate = scorer, self.rs.rate
+
+    @property
+    def S(self):
+        return self.scorer.S
+
+    @property
+    def device(self):
+        return self.scorer.device
+
+    @property
+    def delay(self):
+        """The resampled stream's lag behind resample_poly's centred output, in 16 kHz samples."""
+        return self.rs.delay
+
+    @property
+    def samples_seen(self):
+        """(S,) int64: the 16 kHz samples each slot's inner session has been pushed since its last ``reset``."""
+        return self.scorer.samples_seen
+
+    @property
+    def pending(self):
+        """(S,) int64: the 16 kHz samples waiting in each slot's buffer."""
+        return torch.from_numpy(self._fill.copy())
+
+    def state_meta(self):
+        return dict(self.scorer.state_meta(), **self._meta())
+
+    def _filter(self):
+        """(taps, L, M, T) as the library takes a filter: no taps and T = 1 for the identity."""
+        ident = self.rs.identity
+        return None if ident else ptr(self.rs.taps), self.rs.L, self.rs.M, 1 if ident else self.rs.T
+
+    # ---- a call of a packet front: validation, planning step, execution ---------------------------------------------
+    def _new_ring(self, max_pending):
+        # one hop beyond max_pending: a scoring call always finds room for a packet's next samples after it has popped the
+        # whole hops (a slot then holds < hop samples, and one input sample makes at most ceil(L/M) = 2)
+        self.hop, self.max_pending, self.ring_len = self.scorer.hop, max_pending, (max_pending + 1) * self.scorer.hop
+        self.ring = torch.zeros(self.S, self.ring_len, dtype=torch.float32, device=self.device)
+
+    @staticmethod
+    def _packets(packets, n, encoding):
+        """-> (one block of whole samples per named slot: bytes as they are, anything else through ``payload``; their byte
+        counts)."""
+        from .ingest import _MAX_SAMPLES, _SAMPLE, payload
+        if isinstance(packets, (bytes, bytearray, memoryview, np.ndarray, torch.Tensor)):
+            raise ValueError("packets: a list with one packet per named slot")
+        packets = list(packets)
+        if len(packets) != n:
+            raise ValueError(f"{len(packets)} packets for {n} named slots")
+        bps = _SAMPLE[encoding].itemsize
+        out = [p if type(p) is bytes else payload(p, encoding) for p in packets]
+        nbytes = np.fromiter(map(len, out), dtype=np.int64, count=len(out))
+        for i in np.flatnonzero((nbytes % bps != 0) | (nbytes // bps >= _MAX_SAMPLES)):
+            payload(out[i], encoding)  # (raises, with the message)
+        return out, nbytes
+
+    def _pop_rounds(self, ops, slots, head, fill, counts):
+        """Planning: one ("pop", (A, 2) table of slot and ring head, the slots) op per round in which some of ``slots`` hold
+        a whole hop; ``head``, ``fill`` and ``counts`` (int64 arrays over ``slots``) move with them -> rounds made."""
+        rounds = 0
+        while (fill >= self.hop).any():
+            ready = fill >= self.hop
+            s = slots[ready]
+            ops.append(("pop", np.stack([s, head[ready]], axis=1).astype(np.int32), s.tolist()))
+            head[ready] = (head[ready] + self.hop) % self.ring_len
+            fill[ready] -= self.hop
+            counts += ready
+            rounds += 1
+        return rounds
+
+    def _execute(self, ops, slots, counts, pay, launch, commit):
+        """Issue a planned call: one pinned upload (the payload blocks ``pay``, then every op's table), then the ops in
+        order.  ``launch[kind](d, off, op)`` issues an op of the subclass's (d: the uploaded buffer, off: the byte offset of
+        the op's table in it); a "pop" hands a round of whole hops to the inner scorer.  ``commit()`` makes the planned
+        bookkeeping the scorer's once every launch has been issued.  ``slots``: the named slots, once each, in the order
+        the result lists their scores; ``counts``: hops per named row -> FeedResult."""
+        from .ingest import _at, pack
+        dev = self.device
+        counts = torch.from_numpy(np.asarray(counts, dtype=np.int64))
+        if not ops:
+            commit()
+            return FeedResult(counts, torch.empty(0, dtype=torch.float32, device=dev))
+        if dev.type != "cuda":
+            raise AfxError(f"packets are {self._WORK} and scored on the GPU; there is no CPU fallback")
+        # where each score of the result sits in the concatenation of the pop rounds' outputs (a table when it is not in order)
+        pos, base = {s: [] for s in slots}, 0
+        for op in ops:
+            if op[0] == "pop":
+                for k, s in enumerate(op[2]):
+                    pos[s].append(base + k)
+                base += len(op[2])
+        perm = [p for s in slots for p in pos[s]]
+        tables = [op[1] for op in ops]
+        if perm != list(range(base)):
+            tables.append(np.array(perm, dtype=np.int64))
+        buf, _, toffs = pack(pay, tables, pinned=True)
+        outs = []
+        with torch.cuda.device(dev):
+            d = buf.to(dev, non_blocking=True)  # the one upload
+            for op, off in zip(ops, toffs):
+                if op[0] != "pop":
+                    launch[op[0]](d, off, op)
+                    continue
+                chunk = torch.empty(len(op[2]), self.hop, dtype=torch.float32, device=dev)
+                check(call_on(self.ring, lib().afx_k_ingest_pop, ptr(self.ring), self.S, self.ring_len, _at(d, off), len(op[2]),
+                              self.hop, ptr(chunk)))
+                sc = self.scorer.push(chunk, op[2])
+                if sc is None:
+                    raise RuntimeError("the inner scorer emitted no score for a hop")
+                outs.append(sc)
+            commit()  # (the bookkeeping follows the device state: set once every launch of the plan has been issued)
+            scores = torch.cat(outs) if outs else torch.empty(0, dtype=torch.float32, device=dev)
+            if len(tables) > len(ops):
+                scores = scores.index_select(0, d[toffs[-1]:toffs[-1] + 8 * base].view(torch.int64))
+        return FeedResult(counts, scores)
+
+    # ---- session moves -------------------------------------------------------------------------------------------------
+    def _dev_rows(self, idx):
+        return torch.tensor(idx, dtype=torch.long, device=self.device)
+
+    def _wrap(self, st, **tensors):
+        """The inner state ``st`` with this front's tensors and meta added."""
+        return StreamState(dict(st.meta, **self._meta()), st.seen, dict(st.tensors, **tensors))
+
+    @staticmethod
+    def _peel(state, state_keys, mine, what, names=None):
+        """``state`` must be a StreamState that has the tensors ``state_keys`` and the meta of ``mine`` (this front's own,
+        equal value by value; ``names``: how a message calls a key), else a ValueError -> the inner scorer's StreamState,
+        without them."""
+        if not isinstance(state, StreamState):
+            raise ValueError("import_slots takes a StreamState (export_slots / StreamState.from_state_dict)")
+        if any(k not in state.tensors for k in state_keys) or any(k not in state.meta for k in mine):
+            raise ValueError(f"import_slots: the state has no {what}")
+        for k, v in mine.items():
+            if state.meta[k] != v:
+                raise ValueError(f"import_slots: the state's {(names or {}).get(k, k)} {state.meta[k]!r} is not this scorer's {v!r}")
+        return StreamState({k: v for k, v in state.meta.items() if k not in mine}, state.seen,
+                           {k: t for k, t in state.tensors.items() if k not in state_keys})
+
+    def _export_pending(self, idx, head, fill):
+        """-> (n, max_pending * hop) fp32: the pending samples of the slots ``idx`` (ring heads ``head``, ``fill`` samples
+        each; int64 arrays over idx), left-aligned, zeros after."""
+        with _on(self.device):
+            j = torch.arange(self.max_pending * self.hop)
+            cols = (torch.from_numpy(head)[:, None] + j) % self.ring_len
+            pend = self.ring[self._dev_rows(idx)[:, None], cols.to(self.device)]
+            return pend.masked_fill_((j[None, :] >= torch.from_numpy(fill)[:, None]).to(self.device), 0.0)
+
+    def _check_pending(self, key, pend, fill, n):
+        """The checks of an exported pending ring ``pend`` (state tensor ``key``) with ``fill`` (n,) samples per session."""
+        if pend.ndim != 2 or pend.shape[0] != n or pend.dtype != torch.float32:
+            raise ValueError(f"import_slots: {key} {tuple(pend.shape)} {pend.dtype} is not (n, pending) float32")
+        if (fill < 0).any() or (fill > pend.shape[1]).any() or (fill > self.max_pending * self.hop).any():
+            raise ValueError(f"import_slots: a session holds more pending samples than max_pending = {self.max_pending} hops "
+                             f"of {self.hop} (or than its own buffer)")
+
+    def _import_pending(self, idx, pend):
+        """The slots ``idx`` take the pending samples ``pend`` (checked), at ring head 0."""
+        with _on(self.device):
+            w = min(pend.shape[1], self.ring_len)
+            self.ring[self._dev_rows(idx), :w] = pend[:, :w].to(self.device)
+
+    def _check_hist(self, h, n):
+        if tuple(h.shape) != (n, self.rs.history) or h.dtype != torch.float32:
+            raise ValueError(f"import_slots: resample_hist {tuple(h.shape)} {h.dtype} does not fit this scorer "
+                             f"({(n, self.rs.history)} float32)")
 
 
 class SlidingWindowScorer:
@@ -842,7 +1035,7 @@ class KVCachedScorer(IncrementalScorer):
 
 
 
-class ResamplingScorer:
+class ResamplingScorer(_Front):
     """Any of the three scorers fed audio at ``input_rate`` Hz: each hop is resampled to 16 kHz on the GPU
     (``afx.resample``: causal polyphase filter, ``delay`` 16 kHz samples behind resample_poly's centred output) with
     per-slot filter history, then pushed into ``scorer``.  A slot's scores are, bit for bit, those of ``scorer`` fed
@@ -853,31 +1046,12 @@ class ResamplingScorer:
     ``resampler``).  ``samples_seen`` counts the inner scorer's 16 kHz samples."""
 
     def __init__(self, scorer, input_rate):
-        from .resample import TARGET_RATE, Resampler
-        self.rs = Resampler(input_rate, scorer.device)  # (a bad rate is a ValueError here)
+        super().__init__(scorer, input_rate)
         if (scorer.hop * self.rs.rate) % TARGET_RATE:
             raise ValueError(f"a hop of {scorer.hop} samples at 16 kHz is {scorer.hop * self.rs.rate / TARGET_RATE} samples at "
                              f"{self.rs.rate} Hz: not a whole number")
-        self.scorer, self.input_rate, self.hop_in = scorer, self.rs.rate, scorer.hop * self.rs.rate // TARGET_RATE
+        self.hop_in = scorer.hop * self.rs.rate // TARGET_RATE
         self.hist = torch.zeros(scorer.S, self.rs.history, dtype=torch.float32, device=scorer.device)
-
-    @property
-    def S(self):
-        return self.scorer.S
-
-    @property
-    def device(self):
-        return self.scorer.device
-
-    @property
-    def delay(self):
-        """The resampled stream's lag behind resample_poly's centred output, in 16 kHz samples."""
-        return self.rs.delay
-
-    @property
-    def samples_seen(self):
-        """(S,) int64: the 16 kHz samples each slot's inner session received since its last ``reset``."""
-        return self.scorer.samples_seen
 
     def push(self, chunk, slots=None):
         """chunk: (S, hop_in) fp32 on the GPU at ``input_rate`` (or (len(slots), hop_in) with ``slots``: the non-paced push
@@ -897,37 +1071,22 @@ class ResamplingScorer:
         if idx:
             self.hist[idx] = 0.0
 
-    def state_meta(self):
-        from .resample import FILTER_ID
-        return dict(self.scorer.state_meta(), input_rate=self.input_rate, resampler=FILTER_ID)
+    def _meta(self):
+        return dict(input_rate=self.input_rate, resampler=FILTER_ID)
 
     def export_slots(self, slots):
         """The inner scorer's ``StreamState`` of the named slots plus their filter history."""
-        from .resample import FILTER_ID
         idx = self.scorer._slot_list(slots, ordered=True)
-        st = self.scorer.export_slots(idx)
-        tensors = dict(st.tensors, resample_hist=self.hist[torch.tensor(idx, dtype=torch.long, device=self.device)].clone())
-        return StreamState(dict(st.meta, input_rate=self.input_rate, resampler=FILTER_ID), st.seen, tensors)
+        return self._wrap(self.scorer.export_slots(idx), resample_hist=self.hist[self._dev_rows(idx)].clone())
 
     def import_slots(self, slots, state):
         """The named slots take over the sessions of ``state``, a state of a ResamplingScorer at the same input rate and
         filter; anything else is a ValueError before anything changes."""
-        from .resample import FILTER_ID
         idx = self.scorer._slot_list(slots, ordered=True)
-        if not isinstance(state, StreamState):
-            raise ValueError("import_slots takes a StreamState (export_slots / StreamState.from_state_dict)")
-        if "resample_hist" not in state.tensors or "resampler" not in state.meta or "input_rate" not in state.meta:
-            raise ValueError("import_slots: the state has no resampler history (it was not exported by a ResamplingScorer)")
-        if state.meta["input_rate"] != self.input_rate:
-            raise ValueError(f"import_slots: the state's input rate {state.meta['input_rate']!r} is not this scorer's {self.input_rate}")
-        if state.meta["resampler"] != FILTER_ID:
-            raise ValueError(f"import_slots: the state's resampler {state.meta['resampler']!r} is not this scorer's {FILTER_ID!r}")
+        inner = self._peel(state, ("resample_hist",), self._meta(), "resampler history (it was not exported by a ResamplingScorer)",
+                           names={"input_rate": "input rate"})
         h = state.tensors["resample_hist"]
-        if tuple(h.shape) != (len(state), self.rs.history) or h.dtype != torch.float32:
-            raise ValueError(f"import_slots: resample_hist {tuple(h.shape)} {h.dtype} does not fit this scorer "
-                             f"({(len(state), self.rs.history)} float32)")
-        inner = StreamState({k: v for k, v in state.meta.items() if k not in ("input_rate", "resampler")}, state.seen,
-                            {k: t for k, t in state.tensors.items() if k != "resample_hist"})
+        self._check_hist(h, len(state))
         self.scorer.import_slots(idx, inner)  # (refuses a foreign state before changing anything)
         if idx:
-            self.hist[torch.tensor(idx, dtype=torch.long, device=self.device)] = h.to(self.device)
+            self.hist[self._dev_rows(idx)] = h.to(self.device)

@@ -638,11 +638,20 @@ const char* launch_tile_crop(const float* x, const long long* offs, const long l
 // ---------------------------------------------------------------------------------
 // Polyphase resampling to 16 kHz (afx/resample.py; the function is stated in include/afx.h):
 //     y[n] = sum_{j<T} taps[p][j] * v[i0 - j],   i0 = floor(n*M/L),  p = n*M mod L
-// fp32 taps, one fmaf chain per output in ascending j.  v is the input with zeros before its first sample (offline form)
-// or a row's T-1 carried samples before it (streaming form).  Both forms give each output the same T inputs and taps in
-// the same order, so a stream resampled hop by hop is bit-identical to the whole signal resampled at once.
-// A workgroup owns `R` consecutive sub-tiles of 256 outputs of one row (one output per lane); per sub-tile it stages
-// its input span v[i0(n0) - (T-1) .. i0(n0 + 255)] in LDS.  The (L, T) tap table is staged in LDS too (row stride Tp,
+// fp32 taps, one fmaf chain per output in ascending j.  ONE tile body, polyphase_tiles, computes it for the three kernels
+// that resample: resample_kernel (whole clips, or rows of a stream hop by hop), ingest_kernel (encoded packets of any
+// length) and jitter_release_kernel (a jitter buffer's reorder ring).  A kernel decodes and validates its own row, then
+// hands the body the row's n_out outputs, a SOURCE (sample k of the row, k >= -(T-1) counted from the row's first new
+// sample: before it come zeros, the slot's T-1 carried samples, or the ring itself) and a SINK (where output n of the row
+// goes: linear, or a position of the slot's pending ring).  A row that continues a stream with N inputs received and
+// n_done = ceil(N*L/M) outputs made passes p0 = n_done*M mod L and d0 = floor(n_done*M/L) - N >= 0 (p0 = d0 = 0: the
+// stream's start, or a whole number of filter periods into it); output n of the row is output n_done + n of the stream:
+//     y = sum_{j<T} taps[p][j] * v[i - j],   i = d0 + floor((n*M + p0)/L),  p = (n*M + p0) mod L
+// Every output gets the same T inputs and taps in the same order whichever kernel makes it and however the stream was
+// cut, so a stream resampled hop by hop, packet by packet or out of a jitter buffer is bit-identical to the whole signal
+// resampled at once; with one body that holds by construction.
+// Tiling: a workgroup owns `R` consecutive sub-tiles of 256 outputs of one row (one output per lane); per sub-tile it
+// stages its input span v[i(n0) - (T-1) .. i(n0 + 255)] in LDS.  The (L, T) tap table is staged in LDS too (row stride Tp,
 // odd, so lanes on different phases hit different banks) when it fits, else read from global memory.  Memory-bound: a
 // 48 kHz input is read once, the 16 kHz output written once.
 // ---------------------------------------------------------------------------------
@@ -650,24 +659,119 @@ constexpr int RS_TILE = 256;          // outputs per sub-tile (one per lane)
 constexpr int RS_TAPS_LDS = 12288;    // largest L * Tp staged in LDS (48 KB)
 constexpr int RS_SPAN_MAX = 4096;     // largest staged input span (16 KB): (255 M + L - 1) / L + T for M / L <= 12
 
+struct PolyFilter {
+  const float* taps;             // (L, T); nullptr = identity (ingest / jitter release)
+  int L, M, T, Tp, R;            // Tp, R: set by poly_grid
+};
+
+// Idx: the type of a row's sample and output indices (long long where a row can pass 2^31, as the offline offsets can)
+template <bool LDS_TAPS, class Idx, class Src, class Sink>
+__device__ __forceinline__ void polyphase_tiles(const PolyFilter& f, Idx n_out, int p0r, Idx d0, Src src, Sink sink) {
+  extern __shared__ __attribute__((aligned(16))) float rs_lds[];
+  const int T = f.T;
+  const float* tp = f.taps;
+  int ts = T;
+  float* xs = rs_lds;
+  if (LDS_TAPS) {
+    for (int k = threadIdx.x; k < f.L * f.Tp; k += blockDim.x) {
+      const int p = k / f.Tp, j = k - p * f.Tp;
+      rs_lds[k] = j < T ? f.taps[p * T + j] : 0.f;
+    }
+    tp = rs_lds;
+    ts = f.Tp;
+    xs = rs_lds + f.L * f.Tp;
+  }
+  for (int r = 0; r < f.R; ++r) {
+    const Idx n0 = ((Idx)blockIdx.x * f.R + r) * RS_TILE;
+    if (n0 >= n_out) break;
+    const int cnt = (int)min((Idx)RS_TILE, n_out - n0);
+    const long long q0 = (long long)n0 * f.M + p0r, b0 = q0 / f.L;
+    const int p0 = (int)(q0 - b0 * f.L);
+    const Idx base = d0 + (Idx)b0;  // the row position of output n0's newest input
+    // inputs base - (T-1) .. i(n0 + cnt - 1), which is inside the row for every output the host counted
+    const int span = (int)(((long long)(cnt - 1) * f.M + p0) / f.L) + T;
+    __syncthreads();  // the previous sub-tile is done with xs
+    for (int s = threadIdx.x; s < span; s += blockDim.x) xs[s] = src(base - (T - 1) + s);
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < cnt) {
+      const unsigned q = (unsigned)t * (unsigned)f.M + (unsigned)p0;
+      const int di = (int)(q / (unsigned)f.L), p = (int)(q - (unsigned)di * (unsigned)f.L);
+      const float* w = tp + (long)p * ts;
+      const float* xv = xs + di + T - 1;
+      float acc = 0.f;
+      for (int j = 0; j < T; ++j) acc = __builtin_fmaf(w[j], xv[-j], acc);
+      sink(n0 + t, acc);
+    }
+  }
+}
+
+// the carried samples of a row's slot after the row: the last H = T-1 of h ++ the row's n_in samples.  One workgroup per
+// row (the slots of a launch are distinct): every lane reads its new value before any lane writes, so the in-place shift
+// of a row shorter than H does not race.
+template <class Src>
+__device__ __forceinline__ void hist_shift(float* h, int H, int n_in, Src src) {
+  const int k = threadIdx.x;
+  float v = 0.f;
+  if (k < H) v = (long long)k + n_in < H ? h[k + n_in] : src(k + n_in - H);
+  __syncthreads();
+  if (k < H) h[k] = v;
+}
+
+// the launch shape of polyphase_tiles for rows of up to max_out > 0 outputs: f.Tp, f.R and the grid's x, LDS bytes and
+// tap placement; false for a ratio whose input span does not fit
+struct PolyGrid { bool lds_taps; size_t lds; long long gx; };
+static bool poly_grid(PolyFilter& f, bool ident, long long max_out, PolyGrid& g) {
+  const long long span = (255LL * f.M + f.L - 1) / f.L + f.T;
+  if (span > RS_SPAN_MAX) return false;
+  f.Tp = f.T | 1;
+  g.lds_taps = !ident && (long long)f.L * f.Tp <= RS_TAPS_LDS;
+  f.R = g.lds_taps ? max(1, min(8, f.L * f.Tp / 1024)) : 1;  // amortise the tap staging of many-phase ratios
+  g.gx = (max_out + (long long)RS_TILE * f.R - 1) / ((long long)RS_TILE * f.R);
+  g.lds = ident ? 0 : sizeof(float) * (size_t)((g.lds_taps ? f.L * f.Tp : 0) + span);
+  return true;
+}
+
+// sample k of a dense fp32 row, with the slot's carried samples (HIST: the H before it, oldest first) or zeros before it
+template <bool HIST>
+struct DenseSource {
+  const float* x;
+  const float* hrow;
+  int H;
+  __device__ __forceinline__ float operator()(long long k) const { return k >= 0 ? x[k] : (HIST ? hrow[H + k] : 0.f); }
+};
+struct LinearSink {
+  float* out;
+  __device__ __forceinline__ void operator()(long long n, float v) const { out[n] = v; }
+};
+// output n of a row at position (wpos + n) mod len of the slot's pending ring (n < len)
+struct RingSink {
+  float* out;
+  int wpos, len;
+  __device__ __forceinline__ void operator()(int n, float v) const {
+    const int w = wpos + n;
+    out[w < len ? w : w - len] = v;
+  }
+};
+
 struct ResampleArgs {
   const float* x;                // offline: clips packed back to back; streaming: (A, n_in) rows
   const long long* in_offs;      // offline: input offsets (B + 1)
   const long long* out_offs;     // offline: output offsets (B + 1)
   const float* hist;             // streaming: (S, T - 1) carried samples, oldest first
   const int* slot;               // streaming: row -> hist row
-  const float* taps;             // (L, T)
-  int L, M, T, Tp, R, n_in;
+  PolyFilter f;
+  int n_in;
   float* out;
 };
 
+// offline (zeros before a clip) and streamed (hist[slot[row]] before a row): p0 = d0 = 0
 template <bool STREAM, bool LDS_TAPS>
 __global__ __launch_bounds__(256) void resample_kernel(ResampleArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float rs_lds[];
-  const int row = blockIdx.y, T = a.T;
+  const int row = blockIdx.y, H = a.f.T - 1;
   long long in_base, out_base, n_out;
   if (STREAM) {
-    n_out = (long long)a.n_in * a.L / a.M;
+    n_out = (long long)a.n_in * a.f.L / a.f.M;
     in_base = (long long)row * a.n_in;
     out_base = (long long)row * n_out;
   } else {
@@ -675,76 +779,28 @@ __global__ __launch_bounds__(256) void resample_kernel(ResampleArgs a) {
     out_base = a.out_offs[row];
     n_out = a.out_offs[row + 1] - out_base;
   }
-  const float* hrow = STREAM ? a.hist + (long long)a.slot[row] * (T - 1) : nullptr;
-  const float* tp = a.taps;
-  int ts = T;
-  float* xs = rs_lds;
-  if (LDS_TAPS) {
-    for (int k = threadIdx.x; k < a.L * a.Tp; k += blockDim.x) {
-      const int p = k / a.Tp, j = k - p * a.Tp;
-      rs_lds[k] = j < T ? a.taps[p * T + j] : 0.f;
-    }
-    tp = rs_lds;
-    ts = a.Tp;
-    xs = rs_lds + a.L * a.Tp;
-  }
-  for (int r = 0; r < a.R; ++r) {
-    const long long n0 = ((long long)blockIdx.x * a.R + r) * RS_TILE;
-    if (n0 >= n_out) break;
-    const int cnt = (int)min((long long)RS_TILE, n_out - n0);
-    const long long q0 = n0 * a.M, b0 = q0 / a.L;
-    const int p0 = (int)(q0 - b0 * a.L);
-    // inputs b0 - (T-1) .. i0(n0 + cnt - 1); i0(n) < n_src for every n < n_out, so the span ends inside the row
-    const int span = (int)(((long long)(cnt - 1) * a.M + p0) / a.L) + T;
-    __syncthreads();  // the previous sub-tile is done with xs
-    for (int s = threadIdx.x; s < span; s += blockDim.x) {
-      const long long k = b0 - (T - 1) + s;
-      xs[s] = k >= 0 ? a.x[in_base + k] : (STREAM ? hrow[T - 1 + k] : 0.f);
-    }
-    __syncthreads();
-    const int t = threadIdx.x;
-    if (t < cnt) {
-      const unsigned q = (unsigned)t * (unsigned)a.M + (unsigned)p0;
-      const int di = (int)(q / (unsigned)a.L), p = (int)(q - (unsigned)di * (unsigned)a.L);
-      const float* w = tp + (long)p * ts;
-      const float* xv = xs + di + T - 1;
-      float acc = 0.f;
-      for (int j = 0; j < T; ++j) acc = __builtin_fmaf(w[j], xv[-j], acc);
-      a.out[out_base + n0 + t] = acc;
-    }
-  }
+  const DenseSource<STREAM> src{a.x + in_base, STREAM ? a.hist + (long long)a.slot[row] * H : nullptr, H};
+  polyphase_tiles<LDS_TAPS>(a.f, n_out, 0, 0LL, src, LinearSink{a.out + out_base});
 }
 
-// the carried samples of each streamed row after its chunk: the last T-1 of hist[slot[row]] ++ chunk[row].  One workgroup
-// per row (the slots are distinct): every lane reads its new value before any lane writes, so the in-place shift of a
-// chunk shorter than T-1 does not race.
 __global__ __launch_bounds__(256) void resample_hist_kernel(const float* __restrict__ x, int n_in, const int* __restrict__ slot,
                                                             int H, float* hist) {
-  const int row = blockIdx.x, k = threadIdx.x;
-  float* h = hist + (long long)slot[row] * H;
-  float v = 0.f;
-  if (k < H) v = k + n_in < H ? h[k + n_in] : x[(long long)row * n_in + k + n_in - H];
-  __syncthreads();
-  if (k < H) h[k] = v;
+  const int row = blockIdx.x;
+  hist_shift(hist + (long long)slot[row] * H, H, n_in, DenseSource<false>{x + (long long)row * n_in, nullptr, 0});
 }
 
 static const char* launch_resample_any(bool stream, ResampleArgs a, int rows, long long max_out, hipStream_t s) {
-  if (a.L <= 0 || a.M <= 0 || a.T <= 0 || !a.taps || !a.x || !a.out) return "resample: bad arguments";
+  if (a.f.L <= 0 || a.f.M <= 0 || a.f.T <= 0 || !a.f.taps || !a.x || !a.out) return "resample: bad arguments";
   if (rows <= 0 || rows > 65535) return "resample: 1 to 65535 rows";
   if (max_out <= 0) return nullptr;
-  const long long span = (255LL * a.M + a.L - 1) / a.L + a.T;
-  if (span > RS_SPAN_MAX) return "resample: input / output ratio above 12";
-  a.Tp = a.T | 1;
-  const bool lds_taps = (long long)a.L * a.Tp <= RS_TAPS_LDS;
-  a.R = lds_taps ? max(1, min(8, a.L * a.Tp / 1024)) : 1;  // amortise the tap staging of many-phase ratios
-  const long long gx = (max_out + (long long)RS_TILE * a.R - 1) / ((long long)RS_TILE * a.R);
-  if (gx > 0x7fffffffLL) return "resample: too many outputs per row";
-  const size_t lds = sizeof(float) * (size_t)((lds_taps ? a.L * a.Tp : 0) + span);
-  const dim3 grid((unsigned)gx, rows);
-  if (stream && lds_taps) hipLaunchKernelGGL((resample_kernel<true, true>), grid, dim3(256), lds, s, a);
-  else if (stream) hipLaunchKernelGGL((resample_kernel<true, false>), grid, dim3(256), lds, s, a);
-  else if (lds_taps) hipLaunchKernelGGL((resample_kernel<false, true>), grid, dim3(256), lds, s, a);
-  else hipLaunchKernelGGL((resample_kernel<false, false>), grid, dim3(256), lds, s, a);
+  PolyGrid g;
+  if (!poly_grid(a.f, false, max_out, g)) return "resample: input / output ratio above 12";
+  if (g.gx > 0x7fffffffLL) return "resample: too many outputs per row";
+  const dim3 grid((unsigned)g.gx, rows);
+  if (stream && g.lds_taps) hipLaunchKernelGGL((resample_kernel<true, true>), grid, dim3(256), g.lds, s, a);
+  else if (stream) hipLaunchKernelGGL((resample_kernel<true, false>), grid, dim3(256), g.lds, s, a);
+  else if (g.lds_taps) hipLaunchKernelGGL((resample_kernel<false, true>), grid, dim3(256), g.lds, s, a);
+  else hipLaunchKernelGGL((resample_kernel<false, false>), grid, dim3(256), g.lds, s, a);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? nullptr : hipGetErrorString(e);
 }
@@ -753,7 +809,7 @@ const char* launch_resample(const float* x, const long long* in_offs, const long
                             const float* taps, int L, int M, int T, float* out, hipStream_t s) {
   if (!in_offs || !out_offs) return "resample: null offsets";
   ResampleArgs a{};
-  a.x = x; a.in_offs = in_offs; a.out_offs = out_offs; a.taps = taps; a.L = L; a.M = M; a.T = T; a.out = out;
+  a.x = x; a.in_offs = in_offs; a.out_offs = out_offs; a.f = PolyFilter{taps, L, M, T, 0, 0}; a.out = out;
   return launch_resample_any(false, a, B, max_out, s);
 }
 
@@ -763,7 +819,7 @@ const char* launch_resample_stream(const float* x, int A, int n_in, float* hist,
   if (n_in <= 0 || M <= 0 || ((long long)n_in * L) % M != 0) return "resample_stream: n_in * L must be a multiple of M";
   if (T - 1 > 256) return "resample_stream: more than 256 carried samples";
   ResampleArgs a{};
-  a.x = x; a.hist = hist; a.slot = slot; a.taps = taps; a.L = L; a.M = M; a.T = T; a.n_in = n_in; a.out = out;
+  a.x = x; a.hist = hist; a.slot = slot; a.f = PolyFilter{taps, L, M, T, 0, 0}; a.n_in = n_in; a.out = out;
   const char* m = launch_resample_any(true, a, A, (long long)n_in * L / M, s);
   if (m || T == 1) return m;
   hipLaunchKernelGGL(resample_hist_kernel, dim3(A), dim3(256), 0, s, x, n_in, slot, T - 1, hist);
@@ -774,15 +830,10 @@ const char* launch_resample_stream(const float* x, int A, int n_in, float* hist,
 // ---------------------------------------------------------------------------------
 // Packet ingest (afx/ingest.py; the function is stated in include/afx.h afx_k_ingest / afx_k_ingest_pop): each row is the
 // next n_in encoded samples of one slot's stream, of any length, starting at any filter phase.  The row's header carries
-// what the host reduced from the stream's absolute counters (N input samples received, n_done = ceil(N*L/M) outputs
-// made): p0 = n_done*M mod L and d0 = floor(n_done*M/L) - N >= 0, the position of output n_done's newest input from the
-// packet's first sample.  Output k of the row is output n_done + k of the stream:
-//     y = sum_{j<T} taps[p][j] * v[i - j],   i = d0 + floor((k*M + p0)/L),  p = (k*M + p0) mod L
-// with v = the packet decoded, and hist[slot] (the stream's T-1 samples before the packet) at negative positions: the
-// inputs, taps and order resample_kernel gives that output over the whole stream, so the bits are the same however the
-// stream was cut.  The outputs go into the slot's pending ring from wpos on (wrapping at ring_len); a second kernel then
-// makes hist[slot] the last T-1 decoded samples of hist ++ packet, as resample_hist_kernel does.  taps == nullptr: the
-// identity (16 kHz input), sample k decoded straight into the ring.  Same tiling and LDS staging as resample_kernel.
+// n_out, p0 and d0 as the host reduced them from the stream's absolute counters; ingest_kernel is polyphase_tiles (above)
+// with the source = the packet decoded (exact in fp32), hist[slot] at negative positions, and the sink = the slot's
+// pending ring from wpos on.  A second kernel then makes hist[slot] the last T-1 decoded samples of hist ++ packet.
+// taps == nullptr: the identity (16 kHz input), sample k decoded straight into the ring.
 // ---------------------------------------------------------------------------------
 constexpr int ING_HDR = 8;  // ints per row: slot, byte offset of the first sample, n_in, n_out, p0, d0, wpos, 0
 
@@ -790,10 +841,10 @@ struct IngestArgs {
   const unsigned char* stage;    // encoded payloads (each row's first sample at its header's byte offset)
   long long stage_bytes;
   const int* hdr;                // (rows, ING_HDR)
-  const float* taps;             // (L, T), nullptr = identity
+  PolyFilter f;
   float* hist;                   // (S, T - 1)
   float* ring;                   // (S, ring_len)
-  int enc, L, M, T, Tp, R, S, ring_len;
+  int enc, S, ring_len;
 };
 
 // sample k of an encoded payload as fp32 (exact: 16-bit linear value / 32768; ITU-T G.711 expansion)
@@ -825,80 +876,48 @@ __device__ __forceinline__ bool ingest_row(const IngestArgs& a, int row, int& sl
   pay = a.stage + off;
   const int bps = ingest_bytes_per_sample(a.enc);
   return slot >= 0 && slot < a.S && n_in >= 0 && n_out >= 0 && n_out <= a.ring_len && wpos >= 0 && wpos < a.ring_len &&
-         p0 >= 0 && p0 < a.L && d0 >= 0 && off >= 0 && (off & (bps - 1)) == 0 && off + (long long)n_in * bps <= a.stage_bytes;
+         p0 >= 0 && p0 < a.f.L && d0 >= 0 && off >= 0 && (off & (bps - 1)) == 0 && off + (long long)n_in * bps <= a.stage_bytes;
 }
+
+// sample k of a packet decoded (zeros past its end: never reached by an output the host counted), the slot's carried
+// samples before it
+struct PacketSource {
+  const unsigned char* pay;
+  int enc, n_in;
+  const float* hrow;
+  int H;
+  __device__ __forceinline__ float operator()(int k) const {
+    return k >= 0 ? (k < n_in ? ingest_sample(pay, k, enc) : 0.f) : hrow[H + k];
+  }
+};
 
 template <bool IDENT, bool LDS_TAPS>
 __global__ __launch_bounds__(256) void ingest_kernel(IngestArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float ing_lds[];
-  int slot, n_in, n_out, p0r, d0, wpos;
+  int slot, n_in, n_out, p0, d0, wpos;
   const unsigned char* pay;
-  if (!ingest_row(a, blockIdx.y, slot, pay, n_in, n_out, p0r, d0, wpos)) return;
+  if (!ingest_row(a, blockIdx.y, slot, pay, n_in, n_out, p0, d0, wpos)) return;
   float* out = a.ring + (long long)slot * a.ring_len;
   if (IDENT) {
-    for (int r = 0; r < a.R; ++r) {
-      const int k = (blockIdx.x * a.R + r) * RS_TILE + threadIdx.x;
+    for (int r = 0; r < a.f.R; ++r) {
+      const int k = (blockIdx.x * a.f.R + r) * RS_TILE + threadIdx.x;
       if (k >= n_out || k >= n_in) break;
       const int w = wpos + k;
       out[w < a.ring_len ? w : w - a.ring_len] = ingest_sample(pay, k, a.enc);
     }
     return;
   }
-  const int T = a.T;
-  if ((long long)blockIdx.x * a.R * RS_TILE >= n_out) return;
-  const float* hrow = a.hist + (long long)slot * (T - 1);
-  const float* tp = a.taps;
-  int ts = T;
-  float* xs = ing_lds;
-  if (LDS_TAPS) {
-    for (int k = threadIdx.x; k < a.L * a.Tp; k += blockDim.x) {
-      const int p = k / a.Tp, j = k - p * a.Tp;
-      ing_lds[k] = j < T ? a.taps[p * T + j] : 0.f;
-    }
-    tp = ing_lds;
-    ts = a.Tp;
-    xs = ing_lds + a.L * a.Tp;
-  }
-  for (int r = 0; r < a.R; ++r) {
-    const int n0 = (blockIdx.x * a.R + r) * RS_TILE;
-    if (n0 >= n_out) break;
-    const int cnt = min(RS_TILE, n_out - n0);
-    const long long q0 = (long long)n0 * a.M + p0r, b0 = q0 / a.L;
-    const int p0 = (int)(q0 - b0 * a.L);
-    const int base = d0 + (int)b0;  // the packet position of output n0's newest input
-    const int span = (int)(((long long)(cnt - 1) * a.M + p0) / a.L) + T;
-    __syncthreads();  // the previous sub-tile is done with xs
-    for (int s = threadIdx.x; s < span; s += blockDim.x) {
-      const int k = base - (T - 1) + s;  // >= -(T-1); < n_in for every output the host counted
-      xs[s] = k >= 0 ? (k < n_in ? ingest_sample(pay, k, a.enc) : 0.f) : hrow[T - 1 + k];
-    }
-    __syncthreads();
-    const int t = threadIdx.x;
-    if (t < cnt) {
-      const unsigned q = (unsigned)t * (unsigned)a.M + (unsigned)p0;
-      const int di = (int)(q / (unsigned)a.L), p = (int)(q - (unsigned)di * (unsigned)a.L);
-      const float* w = tp + (long)p * ts;
-      const float* xv = xs + di + T - 1;
-      float acc = 0.f;
-      for (int j = 0; j < T; ++j) acc = __builtin_fmaf(w[j], xv[-j], acc);
-      const int wp = wpos + n0 + t;
-      out[wp < a.ring_len ? wp : wp - a.ring_len] = acc;
-    }
-  }
+  if ((long long)blockIdx.x * a.f.R * RS_TILE >= n_out) return;  // (a short row of a ragged launch: no taps staged for it)
+  const int H = a.f.T - 1;
+  polyphase_tiles<LDS_TAPS>(a.f, n_out, p0, d0, PacketSource{pay, a.enc, n_in, a.hist + (long long)slot * H, H},
+                            RingSink{out, wpos, a.ring_len});
 }
 
-// the carried samples of each row's slot after its packet: the last T-1 of hist[slot] ++ decoded packet.  One workgroup
-// per row (the slots of a launch are distinct): every lane reads its new value before any lane writes.
 __global__ __launch_bounds__(256) void ingest_hist_kernel(IngestArgs a) {
   int slot, n_in, n_out, p0, d0, wpos;
   const unsigned char* pay;
   if (!ingest_row(a, blockIdx.x, slot, pay, n_in, n_out, p0, d0, wpos)) return;
-  const int H = a.T - 1, k = threadIdx.x;
-  float* h = a.hist + (long long)slot * H;
-  float v = 0.f;
-  if (k < H) v = (long long)k + n_in < H ? h[k + n_in] : ingest_sample(pay, k + n_in - H, a.enc);
-  __syncthreads();
-  if (k < H) h[k] = v;
+  const int H = a.f.T - 1;
+  hist_shift(a.hist + (long long)slot * H, H, n_in, PacketSource{pay, a.enc, n_in, nullptr, 0});
 }
 
 const char* launch_ingest(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_out, int enc,
@@ -914,20 +933,15 @@ const char* launch_ingest(const void* stage, long long stage_bytes, const int* h
   if (!ident && T > 1 && !hist) return "ingest: null history";
   if (T - 1 > 256) return "ingest: more than 256 carried samples";
   IngestArgs a{};
-  a.stage = (const unsigned char*)stage; a.stage_bytes = stage_bytes; a.hdr = hdr; a.taps = taps; a.hist = hist; a.ring = ring;
-  a.enc = enc; a.L = L; a.M = M; a.T = T; a.S = S; a.ring_len = ring_len;
-  a.Tp = T | 1;
-  a.R = 1;
+  a.stage = (const unsigned char*)stage; a.stage_bytes = stage_bytes; a.hdr = hdr; a.hist = hist; a.ring = ring;
+  a.f = PolyFilter{taps, L, M, T, 0, 0}; a.enc = enc; a.S = S; a.ring_len = ring_len;
   if (max_out > 0) {
-    const long long span = (255LL * M + L - 1) / L + T;
-    if (span > RS_SPAN_MAX) return "ingest: input / output ratio above 12";
-    const bool lds_taps = !ident && (long long)L * a.Tp <= RS_TAPS_LDS;
-    if (lds_taps) a.R = max(1, min(8, L * a.Tp / 1024));  // amortise the tap staging of many-phase ratios
-    const dim3 grid((unsigned)((max_out + RS_TILE * a.R - 1) / (RS_TILE * a.R)), rows);
-    const size_t lds = ident ? 0 : sizeof(float) * (size_t)((lds_taps ? L * a.Tp : 0) + span);
-    if (ident) hipLaunchKernelGGL((ingest_kernel<true, false>), grid, dim3(256), lds, s, a);
-    else if (lds_taps) hipLaunchKernelGGL((ingest_kernel<false, true>), grid, dim3(256), lds, s, a);
-    else hipLaunchKernelGGL((ingest_kernel<false, false>), grid, dim3(256), lds, s, a);
+    PolyGrid g;
+    if (!poly_grid(a.f, ident, max_out, g)) return "ingest: input / output ratio above 12";
+    const dim3 grid((unsigned)g.gx, rows);
+    if (ident) hipLaunchKernelGGL((ingest_kernel<true, false>), grid, dim3(256), g.lds, s, a);
+    else if (g.lds_taps) hipLaunchKernelGGL((ingest_kernel<false, true>), grid, dim3(256), g.lds, s, a);
+    else hipLaunchKernelGGL((ingest_kernel<false, false>), grid, dim3(256), g.lds, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hipGetErrorString(e);
   }
@@ -973,9 +987,8 @@ const char* launch_ingest_pop(const float* ring, int S, int ring_len, const int*
 //   conceal: writes a released gap's samples INTO the ring (zeros, or the faded repetition of the P samples before the
 //            gap), so that a later gap, and the filter, read them as they read received samples.  Gaps of one slot are
 //            ordered by the host: one launch per rank of gap within the slot.
-//   release: ingest_kernel's body with the ring in place of a decoded payload: outputs n_done .. of the stream from
-//            ring[(a0 + k) mod J], k >= -(T-1), into the slot's pending 16 kHz ring.  Same sub-tiles, tap staging, fp32
-//            taps and ascending-j fmaf chain, so output n has the bits afx_k_resample gives it over all of E.
+//   release: polyphase_tiles (above) with the source = ring[(a0 + k) mod J], k >= -(T-1), and the sink = the slot's pending
+//            16 kHz ring: outputs n_done .. of the stream, each with the bits afx_k_resample gives it over all of E.
 // ---------------------------------------------------------------------------------
 constexpr int JIT_PLACE_HDR = 4;    // ints per row: slot, byte offset of the first sample, n, ring column of the first sample
 constexpr int JIT_CONCEAL_HDR = 4;  // ints per row: slot, ring column of the gap origin a, d_lo, d_hi
@@ -1050,72 +1063,43 @@ const char* launch_jitter_conceal(float* jring, int S, int J, const int* hdr, in
 struct JitterReleaseArgs {
   const float* jring;            // (S, J) decoded input-rate samples
   const int* hdr;                // (rows, JIT_RELEASE_HDR)
-  const float* taps;             // (L, T), nullptr = identity
+  PolyFilter f;
   float* ring;                   // (S, ring_len) pending 16 kHz samples
-  int J, L, M, T, Tp, R, S, ring_len;
+  int J, S, ring_len;
+};
+
+// sample k of the released range that starts at ring column col0 (zeros past its end: never reached by an output the host
+// counted); k >= -(T-1) >= -J and k < n_in <= J, so one wrap either way
+struct RingSource {
+  const float* src;
+  int col0, J, n_in;
+  __device__ __forceinline__ float operator()(int k) const {
+    int c = col0 + k;
+    c = c < 0 ? c + J : (c < J ? c : c - J);
+    return k < n_in ? src[c] : 0.f;
+  }
 };
 
 template <bool IDENT, bool LDS_TAPS>
 __global__ __launch_bounds__(256) void jitter_release_kernel(JitterReleaseArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float jit_lds[];
   const int* h = a.hdr + (long long)blockIdx.y * JIT_RELEASE_HDR;
-  const int slot = h[0], col0 = h[1], n_in = h[2], n_out = h[3], p0r = h[4], d0 = h[5], wpos = h[6];
+  const int slot = h[0], col0 = h[1], n_in = h[2], n_out = h[3], p0 = h[4], d0 = h[5], wpos = h[6];
   if (!(slot >= 0 && slot < a.S && col0 >= 0 && col0 < a.J && n_in >= 0 && n_in <= a.J && n_out >= 0 && n_out <= a.ring_len &&
-        wpos >= 0 && wpos < a.ring_len && p0r >= 0 && p0r < a.L && d0 >= 0))
+        wpos >= 0 && wpos < a.ring_len && p0 >= 0 && p0 < a.f.L && d0 >= 0))
     return;
   const float* src = a.jring + (long long)slot * a.J;
   float* out = a.ring + (long long)slot * a.ring_len;
   if (IDENT) {
-    for (int r = 0; r < a.R; ++r) {
-      const int k = (blockIdx.x * a.R + r) * RS_TILE + threadIdx.x;
+    for (int r = 0; r < a.f.R; ++r) {
+      const int k = (blockIdx.x * a.f.R + r) * RS_TILE + threadIdx.x;
       if (k >= n_out || k >= n_in) break;
       const int c = col0 + k, w = wpos + k;
       out[w < a.ring_len ? w : w - a.ring_len] = src[c < a.J ? c : c - a.J];
     }
     return;
   }
-  const int T = a.T;
-  if ((long long)blockIdx.x * a.R * RS_TILE >= n_out) return;
-  const float* tp = a.taps;
-  int ts = T;
-  float* xs = jit_lds;
-  if (LDS_TAPS) {
-    for (int k = threadIdx.x; k < a.L * a.Tp; k += blockDim.x) {
-      const int p = k / a.Tp, j = k - p * a.Tp;
-      jit_lds[k] = j < T ? a.taps[p * T + j] : 0.f;
-    }
-    tp = jit_lds;
-    ts = a.Tp;
-    xs = jit_lds + a.L * a.Tp;
-  }
-  for (int r = 0; r < a.R; ++r) {
-    const int n0 = (blockIdx.x * a.R + r) * RS_TILE;
-    if (n0 >= n_out) break;
-    const int cnt = min(RS_TILE, n_out - n0);
-    const long long q0 = (long long)n0 * a.M + p0r, b0 = q0 / a.L;
-    const int p0 = (int)(q0 - b0 * a.L);
-    const int base = d0 + (int)b0;  // the position from a0 of output n0's newest input
-    const int span = (int)(((long long)(cnt - 1) * a.M + p0) / a.L) + T;
-    __syncthreads();  // the previous sub-tile is done with xs
-    for (int s = threadIdx.x; s < span; s += blockDim.x) {
-      const int k = base - (T - 1) + s;  // >= -(T-1) >= -J; < n_in <= J for every output the host counted
-      int c = col0 + k;
-      c = c < 0 ? c + a.J : (c < a.J ? c : c - a.J);
-      xs[s] = k < n_in ? src[c] : 0.f;
-    }
-    __syncthreads();
-    const int t = threadIdx.x;
-    if (t < cnt) {
-      const unsigned q = (unsigned)t * (unsigned)a.M + (unsigned)p0;
-      const int di = (int)(q / (unsigned)a.L), p = (int)(q - (unsigned)di * (unsigned)a.L);
-      const float* w = tp + (long)p * ts;
-      const float* xv = xs + di + T - 1;
-      float acc = 0.f;
-      for (int j = 0; j < T; ++j) acc = __builtin_fmaf(w[j], xv[-j], acc);
-      const int wp = wpos + n0 + t;
-      out[wp < a.ring_len ? wp : wp - a.ring_len] = acc;
-    }
-  }
+  if ((long long)blockIdx.x * a.f.R * RS_TILE >= n_out) return;
+  polyphase_tiles<LDS_TAPS>(a.f, n_out, p0, d0, RingSource{src, col0, a.J, n_in}, RingSink{out, wpos, a.ring_len});
 }
 
 const char* launch_jitter_release(const float* jring, int S, int J, const int* hdr, int rows, int max_out, const float* taps,
@@ -1128,20 +1112,15 @@ const char* launch_jitter_release(const float* jring, int S, int J, const int* h
   if (ident && (L != 1 || M != 1 || T != 1)) return "jitter_release: no taps is the identity (L = M = T = 1)";
   if (T - 1 > J) return "jitter_release: the filter history must fit the ring";
   if (max_out == 0) return nullptr;
-  const long long span = (255LL * M + L - 1) / L + T;
-  if (span > RS_SPAN_MAX) return "jitter_release: input / output ratio above 12";
   JitterReleaseArgs a{};
-  a.jring = jring; a.hdr = hdr; a.taps = taps; a.ring = ring;
-  a.J = J; a.L = L; a.M = M; a.T = T; a.S = S; a.ring_len = ring_len;
-  a.Tp = T | 1;
-  a.R = 1;
-  const bool lds_taps = !ident && (long long)L * a.Tp <= RS_TAPS_LDS;
-  if (lds_taps) a.R = max(1, min(8, L * a.Tp / 1024));  // amortise the tap staging of many-phase ratios
-  const dim3 grid((unsigned)((max_out + RS_TILE * a.R - 1) / (RS_TILE * a.R)), rows);
-  const size_t lds = ident ? 0 : sizeof(float) * (size_t)((lds_taps ? L * a.Tp : 0) + span);
-  if (ident) hipLaunchKernelGGL((jitter_release_kernel<true, false>), grid, dim3(256), lds, s, a);
-  else if (lds_taps) hipLaunchKernelGGL((jitter_release_kernel<false, true>), grid, dim3(256), lds, s, a);
-  else hipLaunchKernelGGL((jitter_release_kernel<false, false>), grid, dim3(256), lds, s, a);
+  a.jring = jring; a.hdr = hdr; a.f = PolyFilter{taps, L, M, T, 0, 0}; a.ring = ring;
+  a.J = J; a.S = S; a.ring_len = ring_len;
+  PolyGrid g;
+  if (!poly_grid(a.f, ident, max_out, g)) return "jitter_release: input / output ratio above 12";
+  const dim3 grid((unsigned)g.gx, rows);
+  if (ident) hipLaunchKernelGGL((jitter_release_kernel<true, false>), grid, dim3(256), g.lds, s, a);
+  else if (g.lds_taps) hipLaunchKernelGGL((jitter_release_kernel<false, true>), grid, dim3(256), g.lds, s, a);
+  else hipLaunchKernelGGL((jitter_release_kernel<false, false>), grid, dim3(256), g.lds, s, a);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? nullptr : hipGetErrorString(e);
 }

@@ -14,7 +14,7 @@ from scipy import signal
 
 pytestmark = pytest.mark.gpu
 
-RATES = [8000, 11025, 22050, 24000, 32000, 44100, 48000, 96000]
+RATES = [8000, 11025, 22050, 24000, 32000, 44100, 48000, 96000, 192000]  # 192 kHz: the largest staged input span
 H = 4000
 
 
@@ -52,10 +52,12 @@ def test_identity_rate_launches_nothing():
     assert Resampler(16000)(x) is x
 
 
-@pytest.mark.parametrize("rate,n_in", [(8000, 2000), (44100, 11025), (48000, 12000), (96000, 24000), (48000, 30)])
+@pytest.mark.parametrize("rate,n_in", [(8000, 2000), (44100, 11025), (48000, 12000), (96000, 24000), (48000, 30),
+                                       (11025, 2205), (22050, 4410)])
 def test_streaming_equals_offline(rate, n_in):
     """Named subsets of slots in shuffled order, one chunk each per tick; n_in = 30 at 48 kHz: chunks shorter than the
-    T - 1 = 60 carried samples."""
+    T - 1 = 60 carried samples; 11 025 Hz: the tap table stays in global memory (640 phases); 22 050 Hz: 8 sub-tiles per
+    workgroup, so a chunk's 3 200 outputs span two workgroups."""
     from afx.resample import Resampler
     rs = Resampler(rate)
     S, ticks = 5, 7
