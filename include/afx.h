@@ -81,8 +81,8 @@ int afx_finalize(afx_handle h, void* stream);
 int afx_num_frames(int n_samples);                       /* T after the 7 conv layers */
 size_t afx_workspace_bytes(afx_handle h, int B, int L);  /* scratch needed by one call */
 /* wave: device (B,L) fp32.  logits: device (B,2) fp32.  L is free (test_duration_sec, config.py:75): at least
- * 400 samples (one SSL frame); the AASIST head needs >= 6 frames and holds at most 630 temporal graph nodes
- * (clips up to about 37 s); beyond either bound the call fails with a message, it never truncates. */
+ * 400 samples (one SSL frame); the AASIST head needs >= 6 frames and holds at most 629 temporal graph nodes
+ * (T <= 1889 SSL frames, clips up to about 37 s); beyond either bound the call fails with a message, it never truncates. */
 int afx_forward(afx_handle h, const float* wave, int B, int L, float* logits, void* ws, size_t ws_bytes,
                 void* stream);
 /* The same forward in two calls, for scoring loops that overlap the back-end of one batch with the trunk of the next
@@ -226,6 +226,8 @@ int afx_engine_set(afx_handle h, const char* key, int value);
  * "gemm_map": workgroup->tile order of the MFMA GEMM, -1 default, 0 linear, 1 XCD-
  * contiguous, 2 XCD-contiguous + grouped.  "gemm_tile": -1 auto, 0 128x128, 1 256x256.
  * "fuse_conv_ln": 1 (default) conv layers 1-6 use the fused LayerNorm epilogue, 0 two kernels.
+ * "aasist_conv_slots": 0 automatic, n > 0 caps the grid of the AASIST back-end's persistent conv kernel at n workgroups
+ * (a test knob: a small problem then walks many tiles per workgroup).
  * None of these changes WHAT is computed; the timing-only switches that do ("gemm_nodma") exist only in the
  * attribution build (make attr), the product library refuses them. */
 int afx_debug_set(const char* key, int value);

@@ -61,7 +61,9 @@ def graph_pool(sd, p, h, k, taps=None):
     _, idx = torch.topk(s, n, dim=1)
     if taps is not None:
         v, _ = torch.sort(s.squeeze(-1), dim=1, descending=True)
-        gap = (v[:, :n] - v[:, 1:n + 1]).min(dim=1)[0] if v.shape[1] > n else (v[:, :n - 1] - v[:, 1:n]).min(dim=1)[0]
+        gaps = v[:, :n] - v[:, 1:n + 1] if v.shape[1] > n else v[:, :n - 1] - v[:, 1:n]
+        # (a one-node graph keeps its node: nothing to compare, no gap a perturbation could close)
+        gap = gaps.min(dim=1)[0] if gaps.shape[1] else torch.full_like(v[:, 0], float("inf"))
         taps.setdefault("pool_idx", {})[p] = idx.squeeze(-1)
         taps.setdefault("pool_margin", {})[p] = gap
     return torch.gather(h * s, 1, idx.expand(-1, -1, h.shape[2]))

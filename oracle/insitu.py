@@ -31,6 +31,31 @@ the worst ratio |got - ref| / bound):
   C_FLIP 3 one-ulp flips per row at an internal rounding point (and per output column for the posconv weights, whose
          weight norm the device computes in fp32 before it rounds them).
   Bias   fp16 / bf16 operand outputs measured within +-0.015 ulp (BIAS_MAX 0.05).
+
+The AASIST back-end (``aasist_walk`` and the functions above it) is fp32 throughout, so its bounds carry no operand ulp:
+
+  * products and convs (LL, conv1 / conv2 / downsample as chunked-K products over the padded image, the two 1x1 maps):
+    activations exact fp32, weights exact (dtype fp32) or ``Wh + 2^-11 Wl`` rebuilt as ``split_f16_kernel`` builds the
+    pair (every other dtype); ``C_ACC["fp32"]`` / ``C_ACC["fp16x3"]`` times ``S``, pushed through the epilogue (bias ->
+    residual -> post 1 = BN -> SELU / post 2 = SELU -> BN -> validity mask).  Invalid virtual pixels have reference 0 and
+    bound 0, and ``aas_border`` counts every nonzero float in an image's head and at its invalid pixels: it must be 0;
+  * VALU kernels (pool_bn_selu, first_block, att_pool, rowlin, gat, readout): ``C_ACC["fp32"]`` times the magnitude sum,
+    pushed through the derivative of tanh / softmax / SELU, plus ``C_FN`` fp32 ulps of the OUTPUT of expf / tanhf / the
+    sigmoid (for SELU's negative side: lambda alpha C_FN ulp(e^z));
+  * GraphPool (``pool_check``) is tie-tolerant and leaves no pool out: each output row is mapped to its nearest
+    ``h_j s64_j``, which must be within the product's bound and distinct, and order and membership must agree with the
+    fp64 scores up to delta = ``C_ACC["fp32"] (sum |h||w| + |b|) / 4 + C_FN ulps`` of the two scores compared.
+
+  C_FN   2 ulps.  Measured where a device function's output is visible: pool_bn_selu computes u = fmaf(max, sc, sh) and
+         lambda alpha (expf(u) - 1), and for e^u in [0.5, 1) the subtraction is exact, so |got - lambda alpha expm1(u)| /
+         (lambda alpha ulp32(e^u)) is expf's error plus one rounding of the product: worst 0.780 ulps over the 2 402 such
+         elements of five shapes (mean 0.26); twice that, rounded up to a power of two.  tanhf and the sigmoid feed sums
+         before anything is stored, so no tap shows them alone; |got - ref| / ulp32(ref) of whole outputs is cancellation
+         and accumulation (up to 84 ulps at elements within 1 / 16 of the largest, 1e5 at outputs near 0), not a property
+         of the functions.  With C_FN = 0 every launch of the back-end still passes (worst 0.34 of its bound).
+         Worst measured ratio per class (fp16 / bf16 / fp32 / fp16x3): aas_conv 0.354 / 0.350 / 0.355 / 0.350, aas_prod
+         0.337 / 0.337 / 0.369 / 0.337, aas_valu 0.381 / 0.111 / 0.164 / 0.111, gat 0.139 / 0.080 / 0.126 / 0.080, pool
+         0.078 / 0.078 / 0.093 / 0.078, readout 0.091 / 0.034 / 0.042 / 0.034 (fp16 and fp32 ran the larger shapes).
 """
 import math
 
@@ -348,6 +373,392 @@ def glu_dwconv(sd, p, glu, B, N, dt):
     e = (dswish(zz) * C_ACC["fp16x3"] * 16 * (s * sc.abs()[None, :, None] + zz.abs() + sh.abs()[None, :, None] + 1) +
          C_POLY * (1 + zz.abs())).transpose(1, 2).reshape(B * N, -1)
     return y, e + ulp(y, dt)
+
+
+# ---- AASIST back-end --------------------------------------------------------------------------------------------------
+# Everything after the trunk is fp32.  Images are channel-last and zero-padded, tapped whole: wd = T // 3 frames, wp = wd + 2
+# pixels per padded row, img = 46 wp pixels per utterance, (B img + wp + 1) pixel rows; a conv computes every "virtual
+# pixel" m < M = B img (pix = m % img, h = pix // wp, w = pix % wp, valid iff h < hout and w < wd), reads input pixels
+# a_off + m + ch wp + tap and stores row m + wp + 1, zeros where m is invalid: that re-creates the border.
+AAS_F, AAS_HP = 42, 46
+SELU_L, SELU_A = 1.0507009873554804934193349852946, 1.6732632423543772848170429916717
+C_FN = 2.0
+F32 = C_ACC["fp32"]
+
+
+def aas_dims(T):
+    wd = T // 3
+    return wd, wd + 2, AAS_HP * (wd + 2)
+
+
+def aas_valid(m, T, hout):
+    wd, wp, img = aas_dims(T)
+    pix = m % img
+    return (pix // wp < hout) & (pix % wp < wd)
+
+
+def aas_rows(B, T, full=8192):
+    """Virtual pixels a large image launch is checked on (all of them up to `full`): the first and last 64 of the first
+    and the last utterance, every m with m mod 64 in {0, 15, 16, 63} (the corners of the 64-pixel tiles and of their
+    16-row fragments), the first valid and the first invalid pixel of every image row, every 61st."""
+    wd, wp, img = aas_dims(T)
+    M = B * img
+    m = torch.arange(M)
+    if M <= full:
+        return m
+    pix = m % img
+    k = ((m < img) | (m >= M - img)) & ((pix < 64) | (pix >= img - 64))
+    k |= (pix % wp == 0) | (pix % wp == wd) | (m % 61 == 0)
+    for r in (0, 15, 16, 63):
+        k |= m % 64 == r
+    return m[k]
+
+
+def aas_border(image, B, T, hout, C):
+    """Number of nonzero floats where an image must hold exact zeros: its head (the first padded row + 1 pixel) and every
+    invalid virtual pixel."""
+    wd, wp, img = aas_dims(T)
+    x = image.reshape(-1, C)
+    M = B * img
+    bad = x[:wp + 1] != 0
+    inv = ~aas_valid(torch.arange(M), T, hout)
+    return int(bad.sum()) + int((x[wp + 1:wp + 1 + M][inv] != 0).sum())
+
+
+def aas_weight(w, split):
+    """The fp32 weights as a launch reads them: exact, or Wh + 2^-11 Wl rebuilt as split_f16_kernel builds the pair."""
+    w32 = w.detach().to("cpu", torch.float32)
+    if not split:
+        return w32.double()
+    hi = w32.half()
+    lo = ((w32 - hi.float()) * 2048.0).half()
+    return hi.double() + lo.double() / 2048.0
+
+
+def pack_conv(w):
+    """(cout, cin, kh, kw) -> tap-major (cout, (dh kw + dw) cin + c), the K order of the chunked products."""
+    return w.permute(0, 2, 3, 1).reshape(w.shape[0], -1)
+
+
+def bn_fold(sd, p):
+    sc = d(sd[p + "weight"]) / torch.sqrt(d(sd[p + "running_var"]) + BN_EPS)
+    return sc, d(sd[p + "bias"]) - d(sd[p + "running_mean"]) * sc
+
+
+def selu(z):
+    return SELU_L * torch.where(z > 0, z, SELU_A * torch.expm1(z))
+
+
+def selu_err(z, ez):
+    """Error of the device's SELU given the error ez of its argument: the derivative (the larger one within ez of the
+    kink), C_FN ulps of expf's output e^z <= 1 plus the rounding of the subtraction on the negative side, two roundings
+    of the result."""
+    dz = SELU_L * torch.where(z > ez, torch.ones_like(z), SELU_A * torch.exp((z + ez).clamp(max=0)))
+    fn = torch.where(z > ez, torch.zeros_like(z), SELU_L * SELU_A * ((C_FN + 1) * ulp(torch.exp(z.clamp(max=0)), "fp32")))
+    return dz * ez + fn + 2 * ulp(selu(z), "fp32")
+
+
+def aas_gather(image, C, T, rows, a_off, nch, taps):
+    """(R, nch taps C): what virtual pixels `rows` read of the tapped input image (chunk ch = image row + ch)."""
+    wd, wp, img = aas_dims(T)
+    x = image.reshape(-1, C)
+    idx = a_off + rows[:, None, None] + wp * torch.arange(nch)[None, :, None] + torch.arange(taps)[None, None, :]
+    idx = idx.clamp(max=x.shape[0] - 1)  # (only invalid pixels read past the tapped rows; their reference is 0)
+    return x[idx.reshape(len(rows), -1)].reshape(len(rows), -1)
+
+
+def aas_product(a, w, bias, split, resid=None, bn=None, post=0, valid=None):
+    """One product launch of the back-end: a (R, K) exact fp32 activations, w (N, K) fp32 weights (split: the hi / lo
+    pair form), epilogue bias -> residual -> post 1 (BN -> SELU) / post 2 (SELU -> BN) -> validity mask."""
+    w = aas_weight(w, split)
+    ca = C_ACC["fp16x3" if split else "fp32"]
+    z = a @ w.t()
+    s = (a.abs().float() @ w.abs().float().t()).double()
+    if bias is not None:
+        z, s = z + d(bias), s + d(bias).abs()
+    if resid is not None:
+        z, s = z + resid, s + resid.abs()
+    e = ca * s
+    if post:
+        sc, sh = bn
+    if post == 1:
+        u = z * sc + sh
+        z, e = selu(u), selu_err(u, e * sc.abs() + F32 * ((z * sc).abs() + sh.abs()))
+    elif post == 2:
+        v, ev = selu(z), selu_err(z, e)
+        z, e = v * sc + sh, ev * sc.abs() + F32 * ((v * sc).abs() + sh.abs())
+    if valid is not None:
+        z, e = z * valid[:, None], e * valid[:, None]
+    return z, e
+
+
+def aas_conv(image, w, bias, split, B, T, rows, kh, a_off, hout, resid=None, bn=None, post=0):
+    """A (kh, 3) conv launch over the padded image for the virtual pixels `rows`; compare with out[rows + wp + 1]
+    (`resid` is indexed like the output).  w: the reference's (cout, cin, kh, 3) weight."""
+    cin = w.shape[1]
+    a = aas_gather(image, cin, T, rows, a_off, kh, 3)
+    return aas_product(a, pack_conv(d(w)), bias, split, resid, bn, post, aas_valid(rows, T, hout).double())
+
+
+def pool_bn_selu(sd, ll, B, T):
+    """ll (B T, 128) -> the one-channel padded image (B img + 3 wp + 16,): max_pool2d(3, 3) of the (128, T) map -> BN ->
+    SELU at (f + 1, t + 1), exact zeros everywhere else."""
+    wd, wp, img = aas_dims(T)
+    m = F.max_pool2d(ll.reshape(B, T, 128).transpose(1, 2)[:, None], (3, 3))[:, 0]  # (B, 42, wd)
+    sc, sh = bn_fold(sd, "first_bn.")
+    u = m * sc + sh
+    y, e = selu(u), selu_err(u, F32 * ((m * sc).abs() + sh.abs()))
+    ref = torch.zeros(B * img + 3 * wp + 16, dtype=torch.float64)
+    bnd = torch.zeros_like(ref)
+    ref[:B * img].reshape(B, AAS_HP, wp)[:, 1:AAS_F + 1, 1:wd + 1] = y
+    bnd[:B * img].reshape(B, AAS_HP, wp)[:, 1:AAS_F + 1, 1:wd + 1] = e
+    return ref.reshape(-1, 1), bnd.reshape(-1, 1)
+
+
+def first_block(sd, x1, B, T, rows):
+    """Block 0's VALU kernel on the one-channel image: (Y, D) = (SELU(BN(conv1)), downsample) for virtual pixels `rows`."""
+    p = "encoder.0.0."
+    a = aas_gather(x1, 1, T, rows, 0, 2, 3)
+    y = aas_product(a, pack_conv(d(sd[p + "conv1.weight"])), sd[p + "conv1.bias"], False, bn=bn_fold(sd, p + "bn2."), post=1,
+                    valid=aas_valid(rows, T, AAS_F + 1).double())
+    dn = aas_product(a[:, 3:], pack_conv(d(sd[p + "conv_downsample.weight"])), sd[p + "conv_downsample.bias"], False,
+                     valid=aas_valid(rows, T, AAS_F).double())
+    return y, dn
+
+
+def _softmax_sum(w, x, dim, ew=0.0):
+    """sum softmax(w) x over `dim` as the VALU kernels compute it (expf(w - max), a division by the sum) and its bound:
+    each weight carries the relative error of expf (C_FN + 1 ulps), of the rounded difference w - max and of the logits'
+    own error ew; |d out| <= 2 max(rel) sum p (|x| + |out|)."""
+    p = torch.softmax(w, dim)
+    out = (p * x).sum(dim, keepdim=True)
+    rel = (C_FN + 1) * 2.0 ** -23 + 2.0 ** -24 * (w.amax(dim, keepdim=True) - w.amin(dim, keepdim=True)) + 2 * ew
+    mag = (p * x.abs()).sum(dim, keepdim=True)
+    return out.squeeze(dim), (2 * rel * (mag + out.abs()) + F32 * mag).squeeze(dim)
+
+
+def att_pool(sd, x, wm, B, T):
+    """x (>= B img, 64) encoder output image, wm (B img, 64) attention logits over the padded pixels ->
+    (e_S (B, 42, 64) = softmax over time + pos_S, e_T (B, wd, 64) = softmax over frequency)."""
+    wd, wp, img = aas_dims(T)
+    v = lambda t: t.reshape(-1, 64)[:B * img].reshape(B, AAS_HP, wp, 64)[:, 1:AAS_F + 1, 1:wd + 1]
+    x, wm = v(x), v(wm)
+    pos = d(sd["pos_S"]).reshape(1, AAS_F, 64)
+    s, es = _softmax_sum(wm, x, 2)
+    t, et = _softmax_sum(wm, x, 1)
+    return (s + pos, es + F32 * pos.abs()), (t, et)
+
+
+def rowlin(x, w, b):
+    """y = W x + b, fp32 fma chain per output."""
+    return aas_product(x, d(w), b, False)
+
+
+def gat(sd, p, x, n1, temp, master=None, hetero=True):
+    """One graph of a gat_kernel launch.  x (B, N, DIN) the (type-projected) nodes, the first n1 of type 1;
+    att[i, j] = softmax_j(tanh(W_att (x_i x_j) + b) . v_blk(i, j) / temp) with v11 / v22 inside a type and v12 across;
+    y_i = SELU(BN(W1 sum_j att[i, j] x_j + b1 + W2 x_i + b2)).  With `master` ((B or 1, DIN), heterogeneous layers): also
+    the master update from the SAME (pre-update) nodes, att_projM / att_weightM, no BN.  -> (y, ey)[, (m, em)]."""
+    B, N, DIN = x.shape
+    g = lambda k: d(sd[p + k])
+    aw, ab = g("att_proj.weight"), g("att_proj.bias")
+    if hetero:
+        v11, v22, v12 = g("att_weight11")[:, 0], g("att_weight22")[:, 0], g("att_weight12")[:, 0]
+    else:
+        v11 = v22 = v12 = g("att_weight")[:, 0]
+    t1 = torch.arange(N) < n1
+    same = t1[:, None] == t1[None, :]
+    vsel = torch.where(same[:, :, None], torch.where(t1[:, None, None], v11[None, None], v22[None, None]), v12[None, None])  # (N, N, O)
+
+    def attend(ctr, aw, ab, v, w1, b1, w2, b2):
+        """ctr (B, I, DIN) centre vectors, v (I, N, O) -> pre-activation (B, I, O) and its bound."""
+        wi = ctr[:, :, None, :] * aw[None, None]  # (B, I, O, D)
+        h = torch.einsum("biod,bjd->bijo", wi, x) + ab
+        sh = torch.einsum("biod,bjd->bijo", wi.abs().float(), x.abs().float()).double() + ab.abs()
+        th = torch.tanh(h)
+        sc = (th * v).sum(-1) / temp  # (B, I, N)
+        esc = (v.abs() * ((1 - th * th) * F32 * sh + C_FN * ulp(th, "fp32")) + F32 * (th * v).abs()).sum(-1) / temp
+        xj = x[:, None]  # (B, 1, N, D)
+        agg, ea = _softmax_sum(sc[..., None], xj, 2, esc.amax(-1)[..., None, None])  # (B, I, D)
+        pre = agg @ w1.t() + b1 + ctr @ w2.t() + b2
+        e = ea @ w1.abs().t() + F32 * (agg.abs() @ w1.abs().t() + b1.abs() + ctr.abs() @ w2.abs().t() + b2.abs())
+        return pre, e
+
+    w1, b1, w2, b2 = g("proj_with_att.weight"), g("proj_with_att.bias"), g("proj_without_att.weight"), g("proj_without_att.bias")
+    pre, e = [], []
+    for i0 in range(0, N, 64):  # (chunks of centre nodes: the (I, N, O, D) products stay small)
+        a, b = attend(x[:, i0:i0 + 64], aw, ab, vsel[i0:i0 + 64], w1, b1, w2, b2)
+        pre.append(a)
+        e.append(b)
+    pre, e = torch.cat(pre, 1), torch.cat(e, 1)
+    sc, sh = bn_fold(sd, p + "bn.")
+    u = pre * sc + sh
+    node = (selu(u), selu_err(u, e * sc.abs() + F32 * ((pre * sc).abs() + sh.abs())))
+    if master is None:
+        return node
+    m = master.reshape(-1, 1, DIN).expand(B, 1, DIN)
+    vM = g("att_weightM")[:, 0][None, None].expand(1, N, -1)
+    mo, em = attend(m, g("att_projM.weight"), g("att_projM.bias"), vM, g("proj_with_attM.weight"), g("proj_with_attM.bias"),
+                    g("proj_without_attM.weight"), g("proj_without_attM.bias"))
+    return node, (mo[:, 0], em[:, 0])
+
+
+def pool_check(h, w, b, out, keep):
+    """GraphPool launch, tie-tolerant: h (B, N, D) tapped input, out (B, keep, D) tapped output.  s64 = sigmoid(w.h + b);
+    delta = the derived error bound of a score.  Every output row is mapped to the node j whose h_j s64_j is nearest;
+    required: that distance within the product's bound, distinct j, and order and membership consistent with s64 up to
+    the deltas of the two nodes compared.  -> check()-style dict (ratio = the worst of those requirements; margin = the
+    smallest fp64 gap that decides order or membership, per launch)."""
+    B, N, D = h.shape
+    w, b = d(w).reshape(-1), d(b).reshape(-1)
+    x = h @ w + b
+    s = torch.sigmoid(x)
+    delta = F32 * (h.abs() @ w.abs() + b.abs()) / 4 + C_FN * ulp(s, "fp32")  # (B, N)
+    prod = h * s[..., None]
+    pb = h.abs() * delta[..., None] + ulp(prod, "fp32")
+    worst = dict(ratio=0.0, row=0, col=0, got=0.0, ref=0.0, bound=0.0, bias=None, n=out.numel(), margin=float("inf"))
+
+    def note(r, row, col, got, ref, bound):
+        if not r <= worst["ratio"]:
+            worst.update(ratio=float(r), row=row, col=col, got=float(got), ref=float(ref), bound=float(bound))
+
+    for u in range(B):
+        dist = (out[u][:, None, :] - prod[u][None]).abs()  # (keep, N, D)
+        j = dist.amax(-1).argmin(1)  # (keep,)
+        r = dist[torch.arange(keep), j] / pb[u][j]  # (keep, D)
+        k = int(r.argmax())
+        note(r.reshape(-1)[k], u * keep + k // D, k % D, out[u].reshape(-1)[k], prod[u][j].reshape(-1)[k], pb[u][j].reshape(-1)[k])
+        if len(set(j.tolist())) != keep:
+            note(float("inf"), u * keep, 0, 0.0, 0.0, 0.0)
+            continue
+        sj, dj = s[u][j], delta[u][j]
+        if keep > 1:  # order: s64[j_r] >= s64[j_{r+1}] - delta
+            r = (sj[1:] - sj[:-1]) / (dj[1:] + dj[:-1])
+            k = int(r.argmax())
+            note(r[k], u * keep + k, -1, sj[k + 1], sj[k], dj[k] + dj[k + 1])
+            worst["margin"] = min(worst["margin"], float((sj[:-1] - sj[1:]).abs().min()))
+        drop = torch.ones(N, dtype=torch.bool)
+        drop[j] = False
+        if bool(drop.any()):  # membership: min kept >= max dropped - delta
+            kmin, dmax = int(sj.argmin()), int(torch.where(drop, s[u], torch.full_like(s[u], -1.0)).argmax())
+            note((s[u][dmax] - sj[kmin]) / (delta[u][dmax] + dj[kmin]), u * keep + kmin, -2, s[u][dmax], sj[kmin], delta[u][dmax] + dj[kmin])
+            worst["margin"] = min(worst["margin"], float((sj[kmin] - s[u][dmax]).abs()))
+    return worst
+
+
+def readout(sd, t1, ta1, s1, m1, ma1, t2, ta2, s2, sa2, m2, ma2, hidden):
+    """readout_kernel: the residual adds (branch 1's spectral nodes get the literal + 1, not their second layer), the
+    branch maximum, hidden = [max |T|, mean T, max |S|, mean S, master] and the logits, which the kernel computes from
+    the hidden vector it stores (`hidden`: the tapped one).  Node inputs (B, n, 32), masters (B, 32)."""
+    def pair(a, b, c, e):
+        return torch.maximum(a + b, c + e), F32 * torch.maximum(a.abs() + b.abs(), c.abs() + e.abs())
+
+    vt, et = pair(t1, ta1, t2, ta2)
+    vs, es = pair(s1, torch.ones_like(s1), s2, sa2)
+    vm, em = pair(m1, ma1, m2, ma2)
+    hid = torch.cat([vt.abs().amax(1), vt.mean(1), vs.abs().amax(1), vs.mean(1), vm], 1)
+    eh = torch.cat([et.amax(1), et.mean(1) + F32 * vt.abs().mean(1), es.amax(1), es.mean(1) + F32 * vs.abs().mean(1), em], 1)
+    return (hid, eh), aas_product(hidden, d(sd["out_layer.weight"]), sd["out_layer.bias"], False)
+
+
+AAS_FILT = [(1, 32), (32, 32), (32, 64), (64, 64), (64, 64), (64, 64)]
+
+
+def aasist_walk(sd, feats, tap, split):
+    """Every launch of ONE back-end forward against its reference, each built from the launch's own tapped inputs.
+    feats (B, T, 1024) the forward's input, tap(name) -> the tapped buffer (flat, float64), split: the engine runs the
+    split-precision products (every dtype but fp32).  -> (results, zeros): results = [(class, tap name, check() dict)],
+    zeros = [(tap name, count of nonzero floats where the image must be exactly 0)].  Pools are never left out."""
+    B, T, _ = feats.shape
+    wd, wp, img = aas_dims(T)
+    M = B * img
+    res, zeros = [], []
+    rows = aas_rows(B, T)
+    o = rows + wp + 1
+
+    def put(cls, name, got, rb, r=None):
+        res.append((cls, name, check(got, rb[0], rb[1], None, r)))
+
+    def image(name, C, hout):
+        x = tap(name).reshape(-1, C)
+        zeros.append((name, aas_border(x, B, T, hout, C)))
+        return x
+
+    ll = tap("aa.ll").reshape(B * T, 128)
+    put("aas_prod", "aa.ll", ll, aas_product(d(feats).reshape(B * T, 1024), sd["LL.weight"], sd["LL.bias"], split))
+    x1 = tap("aa.x1").reshape(-1, 1)
+    put("aas_valu", "aa.x1", x1, pool_bn_selu(sd, ll, B, T))
+    Y, D = image("aa.b0.y", 32, AAS_F + 1), image("aa.b0.d", 32, AAS_F)
+    ry, rd = first_block(sd, x1, B, T, rows)
+    put("aas_valu", "aa.b0.y", Y[o], ry, rows)
+    put("aas_valu", "aa.b0.d", D[o], rd, rows)
+    p = "encoder.0.0."
+    X = image("aa.b0", 32, AAS_F)
+    put("aas_conv", "aa.b0", X[o], aas_conv(Y, sd[p + "conv2.weight"], sd[p + "conv2.bias"], split, B, T, rows, 2, wp, AAS_F, D[o]), rows)
+    for i in range(1, 6):
+        p, (cin, cout) = f"encoder.{i}.0.", AAS_FILT[i]
+        Y = image(f"aa.b{i}.y", cout, AAS_F + 1)
+        put("aas_conv", f"aa.b{i}.y", Y[o], aas_conv(X, sd[p + "conv1.weight"], sd[p + "conv1.bias"], split, B, T, rows, 2, 0, AAS_F + 1,
+                                                   bn=bn_fold(sd, p + "bn2."), post=1), rows)
+        resid = X[o]
+        if cin != cout:
+            D = image(f"aa.b{i}.d", cout, AAS_F)
+            put("aas_conv", f"aa.b{i}.d", D[o], aas_conv(X, sd[p + "conv_downsample.weight"], sd[p + "conv_downsample.bias"], split, B, T,
+                                                       rows, 1, wp, AAS_F), rows)
+            resid = D[o]
+        Xn = image(f"aa.b{i}", cout, AAS_F)
+        last = dict(bn=bn_fold(sd, "first_bn1."), post=1) if i == 5 else {}
+        put("aas_conv", f"aa.b{i}", Xn[o], aas_conv(Y, sd[p + "conv2.weight"], sd[p + "conv2.bias"], split, B, T, rows, 2, wp, AAS_F,
+                                                  resid, **last), rows)
+        X = Xn
+    w1, w2 = tap("aa.w1").reshape(M, 128), tap("aa.w2").reshape(M, 64)
+    put("aas_prod", "aa.w1", w1[rows], aas_product(X[rows], sd["attention.0.weight"][:, :, 0, 0], sd["attention.0.bias"], split,
+                                                   bn=bn_fold(sd, "attention.2."), post=2), rows)
+    put("aas_prod", "aa.w2", w2[rows], aas_product(w1[rows], sd["attention.3.weight"][:, :, 0, 0], sd["attention.3.bias"], split), rows)
+    eS, eT = tap("e_S").reshape(B, AAS_F, 64), tap("e_T").reshape(B, wd, 64)
+    rs, rt = att_pool(sd, X, w2, B, T)
+    put("aas_valu", "e_S", eS, rs)
+    put("aas_valu", "e_T", eT, rt)
+    gS, gT = tap("gat_S").reshape(B, AAS_F, 64), tap("gat_T").reshape(B, wd, 64)
+    put("gat", "gat_S", gS, gat(sd, "GAT_layer_S.", eS, AAS_F, 2.0, hetero=False))
+    put("gat", "gat_T", gT, gat(sd, "GAT_layer_T.", eT, wd, 2.0, hetero=False))
+    nS, nT = AAS_F // 2, max(wd // 2, 1)
+    nS1, nT1 = max(nS // 2, 1), max(nT // 2, 1)
+
+    def pool(name, pre, h, keep):
+        out = tap(name).reshape(B, keep, h.shape[2])
+        res.append(("pool", name, pool_check(h, sd[pre + "proj.weight"], sd[pre + "proj.bias"], out, keep)))
+        return out
+
+    oS, oT = pool("out_S", "pool_S.", gS, nS), pool("out_T", "pool_T.", gT, nT)
+    br = []
+    for k in (1, 2):
+        h1, h2 = f"HtrgGAT_layer_ST{k}1.", f"HtrgGAT_layer_ST{k}2."
+        n = f"b{k}_"
+        xp = tap(n + "xp").reshape(B, nT + nS, 64)
+        put("aas_valu", n + "xp.T", xp[:, :nT].reshape(B * nT, 64), rowlin(oT.reshape(B * nT, 64), sd[h1 + "proj_type1.weight"], sd[h1 + "proj_type1.bias"]))
+        put("aas_valu", n + "xp.S", xp[:, nT:].reshape(B * nS, 64), rowlin(oS.reshape(B * nS, 64), sd[h1 + "proj_type2.weight"], sd[h1 + "proj_type2.bias"]))
+        (y, ey), rm = gat(sd, h1, xp, nT, 100.0, master=d(sd[f"master{k}"]))
+        T1, S1, m1 = tap(n + "T1").reshape(B, nT, 32), tap(n + "S1").reshape(B, nS, 32), tap(n + "m1").reshape(B, 32)
+        put("gat", n + "T1", T1, (y[:, :nT], ey[:, :nT]))
+        put("gat", n + "S1", S1, (y[:, nT:], ey[:, nT:]))
+        put("gat", n + "m1", m1, rm)
+        S1p, T1p = pool(n + "S1p", f"pool_hS{k}.", S1, nS1), pool(n + "T1p", f"pool_hT{k}.", T1, nT1)
+        xp2 = tap(n + "xp2").reshape(B, nT1 + nS1, 32)
+        put("aas_valu", n + "xp2.T", xp2[:, :nT1].reshape(B * nT1, 32), rowlin(T1p.reshape(B * nT1, 32), sd[h2 + "proj_type1.weight"], sd[h2 + "proj_type1.bias"]))
+        put("aas_valu", n + "xp2.S", xp2[:, nT1:].reshape(B * nS1, 32), rowlin(S1p.reshape(B * nS1, 32), sd[h2 + "proj_type2.weight"], sd[h2 + "proj_type2.bias"]))
+        (y, ey), rm = gat(sd, h2, xp2, nT1, 100.0, master=m1)
+        Ta, Sa, ma = tap(n + "Ta").reshape(B, nT1, 32), tap(n + "Sa").reshape(B, nS1, 32), tap(n + "ma").reshape(B, 32)
+        put("gat", n + "Ta", Ta, (y[:, :nT1], ey[:, :nT1]))
+        put("gat", n + "Sa", Sa, (y[:, nT1:], ey[:, nT1:]))
+        put("gat", n + "ma", ma, rm)
+        br.append((T1p, Ta, S1p, Sa, m1, ma))
+    hidden, logits = tap("hidden").reshape(B, 160), tap("logits").reshape(B, 2)
+    (a, b) = br
+    rh, rl = readout(sd, a[0], a[1], a[2], a[4], a[5], b[0], b[1], b[2], b[3], b[4], b[5], hidden)
+    put("readout", "hidden", hidden, rh)
+    put("readout", "logits", logits, rl)
+    return res, zeros
 
 
 # ---- the check ---------------------------------------------------------------------------------------------------------

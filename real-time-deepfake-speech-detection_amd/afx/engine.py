@@ -519,7 +519,14 @@ class Engine:
                   padded rows), b{b}.xb, b{b}.glu (after chain B), b{b}.u (depthwise conv output, padded rows), block{b};
                   the per-op path (``set("fuse_conformer", 0)``) also b{b}.{ff1,attn,conv,ff2}.hc (LayerNorm outputs),
                   b{b}.{ff1,ff2}.hid (FF hidden), b{b}.xc (after the conv module), b{b}.xd (after FF2)
-          AASIST  e_S, e_T, hidden and the back-end's module taps"""
+          AASIST  every launch boundary of the back-end.  aa.ll (B T, 128); aa.x1 (the pooled one-channel image, B img +
+                  3 wp + 16 pixels); images whole in their padded channel-last layout, (B img + wp + 1) pixel rows x C with
+                  wd = T // 3, wp = wd + 2, img = 46 wp, virtual pixel m stored at row m + wp + 1: aa.b{i}.y (conv1 -> BN ->
+                  SELU), aa.b{i}.d (the downsample conv, blocks 0, 2) and aa.b{i} (conv2 + residual) for the blocks i =
+                  0 .. 5; aa.w1 (B img, 128), aa.w2 (B img, 64) the two attention maps over the padded pixels; e_S, e_T;
+                  gat_S, gat_T, out_S, out_T; per branch k = 1, 2: b{k}_xp (type-projected nodes, temporal first),
+                  b{k}_T1, b{k}_S1, b{k}_m1, b{k}_T1p, b{k}_S1p (pooled), b{k}_xp2, b{k}_Ta, b{k}_Sa, b{k}_ma; hidden;
+                  logits"""
         n = C.c_size_t(0)
         with torch.cuda.device(self.device):
             check(lib().afx_tap(self._h, name.encode(), None, 0, C.byref(n), self._stream()))

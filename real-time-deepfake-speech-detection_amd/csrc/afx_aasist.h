@@ -13,6 +13,8 @@ namespace afx {
 // (B, AAS_HP, AAS_WP, C): logical pixel (h, w) sits at (h+1, w+1).
 constexpr int AAS_F = 42;       // spectral bins after max_pool2d(3,3): 128 // 3
 constexpr int AAS_HP = 46;      // padded rows (43 conv1 rows + 1 top + slack)
+// most nodes of one graph: gat_kernel keeps (64 N + 64 + N + 8) floats in the 160 KB of LDS (N = 630 needs 164 088 B)
+constexpr int AAS_MAX_NODES = 629;  // T <= 1889 SSL frames, about 37 s
 
 struct AasistWeights {
   bool ready = false;
@@ -66,10 +68,15 @@ struct AasistWs {
   float *br;                 // per-branch scratch
   float *hidden;             // (B,160)
   // debug views of the last forward (names/pointers into the workspace)
-  const char* dbg_name[16];
-  const float* dbg_ptr[16];
-  size_t dbg_n[16];
+  const char* dbg_name[32];
+  const float* dbg_ptr[32];
+  size_t dbg_n[32];
   int dbg_count = 0;
+  // test hook (null = off, the only cost is the null check on the host): called after a launch whose output a later
+  // launch overwrites, with the tap's name, the output buffer and its length in floats; the callee makes a
+  // stream-ordered copy.  A nonzero return aborts the forward.  Names: Engine.tap (afx/engine.py).
+  int (*tap)(void* ctx, const char* name, const float* p, size_t n) = nullptr;
+  void* tap_ctx = nullptr;
 };
 
 using GetF = std::function<const float*(const std::string&)>;
@@ -78,6 +85,7 @@ using Alloc = std::function<void*(size_t)>;
 // prepare derived tensors (BN folds, tap-major conv weights); nullptr or error text
 const char* aasist_finalize(AasistWeights& w, const GetF& get, const Alloc& alloc, hipStream_t s);
 void aasist_set_stop(int v);  // diagnostic knob: return after that many stages of the back-end (0 = all)
+void aasist_set_conv_slots(int v);  // test knob: cap the persistent conv kernel's grid at v workgroups (0 = automatic)
 void aasist_carve(int B, int T, const Alloc& take, AasistWs* ws);
 // feats (B,T,1024) fp32 -> logits (B,2); nonfinite (device counter or null): += 1 for every logit that is not finite
 const char* aasist_forward(const AasistWeights& w, const float* feats, int B, int T, AasistWs& ws, float* logits,

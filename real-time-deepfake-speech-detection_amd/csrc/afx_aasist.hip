@@ -403,6 +403,11 @@ __global__ __launch_bounds__(512) void aas_conv_kernel(F32GemmArgs p, int C, int
   }
 }
 
+// test knob (afx_debug_set "aasist_conv_slots"): > 0 caps the grid at that many workgroups, so that a small problem
+// walks many tiles per workgroup (the prefetch of the next tile and its clamp at last_pix); 0 = automatic
+static int g_aas_conv_slots = 0;
+void aasist_set_conv_slots(int v) { g_aas_conv_slots = v > 0 ? v : 0; }
+
 // launch the LDS-staged form when the shape allows it; false = not applicable (caller falls back)
 static bool try_launch_aas_conv(const F32GemmArgs& p, hipStream_t s, hipError_t* err) {
   *err = hipSuccess;
@@ -417,7 +422,8 @@ static bool try_launch_aas_conv(const F32GemmArgs& p, hipStream_t s, hipError_t*
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) { *err = hipErrorInvalidDevice; return true; }
   if (!n_cu_of[dev] && hipDeviceGetAttribute(&n_cu_of[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { *err = hipErrorUnknown; return true; }
   const int per_cu = (int)((160 * 1024) / lds) > 2 ? 2 : (int)((160 * 1024) / lds);  // 512-thread workgroups
-  const int slots = n_cu_of[dev] * (per_cu < 1 ? 1 : per_cu);
+  int slots = n_cu_of[dev] * (per_cu < 1 ? 1 : per_cu);
+  if (g_aas_conv_slots > 0 && g_aas_conv_slots < slots) slots = g_aas_conv_slots;
   dim3 grid(ntiles < slots ? ntiles : slots);
   static LdsLimit lim[3];
 #define AFX_ACV(IDX, NTv)                                                                                 \
@@ -754,7 +760,8 @@ __global__ __launch_bounds__(256) void gat_kernel(GatMulti pp) {
 // one or two graphs of the same layer dims in one launch (a1 may be null)
 static const char* launch_gat(const GatArgs& a, int B, int din, int dout, hipStream_t s, const GatArgs* a1 = nullptr) {
   // one workgroup per node keeps the whole graph's features in LDS: 4-s clips have <= 66 nodes (17 KB); the
-  // 160 KB of a CU hold 630 nodes = clips of about 37 s (test_duration_sec is a free config value)
+  // 160 KB of a CU hold AAS_MAX_NODES = 629 nodes of 64 features ((65 N + 72) floats <= 40 960) = clips of about
+  // 37 s (test_duration_sec is a free config value); aasist_forward refuses longer clips before anything is launched
   const int nmax = a1 && a1->N > a.N ? a1->N : a.N;
   const int lds = (int)(((long)nmax * din + 64 + nmax + 8) * sizeof(float));
   if (a.N < 1 || (a1 && a1->N < 1) || lds > 160 * 1024) return "aasist: graph has too many nodes for the LDS slab (clip longer than ~37 s)";
@@ -1050,8 +1057,15 @@ const char* aasist_forward(const AasistWeights& w, const float* feats, int B, in
   int wd, wp, img;
   dims(T, &wd, &wp, &img);
   if (wd < 2) return "aasist: clip too short (need at least 6 SSL frames)";
-  if (wd > 630) return "aasist: clip too long for the graph kernels (about 37 s: T <= 1890 frames)";
+  if (wd > AAS_MAX_NODES) return "aasist: clip too long for the graph kernels (about 37 s: T <= 1889 frames)";
   const int M = B * img;
+  // test hook: nothing but this null check when taps are off; images are handed over whole in their padded layout
+  // ((M + wp + 1) pixel rows), so that their borders can be checked
+#define ATAP(nm, ptr, cnt)                                                                              \
+  do {                                                                                                  \
+    if (ws.tap && ws.tap(ws.tap_ctx, std::string(nm).c_str(), (ptr), (size_t)(cnt))) return "aasist: tap failed"; \
+  } while (0)
+  const size_t ipix = (size_t)M + wp + 1;
   // ---- LL: (B*T,1024) x [128][1024] on the fp32 matrix cores ------------------------
   {
     F32GemmArgs g;
@@ -1060,6 +1074,7 @@ const char* aasist_forward(const AasistWeights& w, const float* feats, int B, in
     g.bias = w.LLb; g.out = ws.ll; g.ldo = 128;
     AOK(launch_f32_gemm(g, s));
   }
+  ATAP("aa.ll", ws.ll, (size_t)B * T * 128);
   AAS_STAGE();  // 1: LL
   // ---- max-pool + BN + SELU into a 1-channel padded image ---------------------------
   float *X = ws.imgA, *Y = ws.imgB, *D = ws.imgC;
@@ -1071,6 +1086,7 @@ const char* aasist_forward(const AasistWeights& w, const float* feats, int B, in
   float* x1 = ws.wmap2;  // 1-channel image borrowed from a later buffer
   hipLaunchKernelGGL(pool_bn_selu_kernel, dim3((img + 255) / 256, B + 1), dim3(256), 0, s, ws.ll, T, wd, wp, img,
                      w.bn0_scale, w.bn0_shift, x1, B, 3 * wp + 16, ws.imgA, ws.imgB, ws.imgC, head);
+  ATAP("aa.x1", x1, (size_t)M + 3 * wp + 16);
   AAS_STAGE();  // 2: pooling
   // ---- residual encoder ----------------------------------------------------------------
   {  // block 0 (Cin = 1): conv1+bn2+selu -> Y, downsample -> D, conv2(Y) + D -> X
@@ -1078,12 +1094,15 @@ const char* aasist_forward(const AasistWeights& w, const float* feats, int B, in
     const long n = (long)M * K.cout;
     hipLaunchKernelGGL(first_block_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x1, M, img, wp, wd, K.w1,
                        K.b1, K.bn2_scale, K.bn2_shift, K.wd, K.bd, Y, D, K.cout, AAS_F);
+    ATAP("aa.b0.y", Y, ipix * K.cout);
+    ATAP("aa.b0.d", D, ipix * K.cout);
     F32GemmArgs g;
     memset(&g, 0, sizeof g);
     g.A = Y + (long)wp * K.cout; g.lda = K.cout; g.nch = 2; g.kc = 3 * K.cout; g.chunk_stride = (long)wp * K.cout;
     g.W = K.w2; g.Wh = K.s2.hi; g.Wl = K.s2.lo; g.M = M; g.N = K.cout; g.bias = K.b2; g.resid = D;
     g.img = img; g.wp = wp; g.hout = AAS_F; g.wd = wd; g.out = X; g.ldo = K.cout; g.o_off = wp + 1;
     AOK(launch_f32_gemm(g, s));
+    ATAP("aa.b0", X, ipix * K.cout);
   }
   AAS_STAGE();  // 3: residual block 0
   for (int i = 1; i < 6; ++i) {
@@ -1106,6 +1125,11 @@ const char* aasist_forward(const AasistWeights& w, const float* feats, int B, in
       // data; X's may go only now that both convs have read it
       if (K.cin != K.cout) hipLaunchKernelGGL(zero3_kernel, dim3((head + 255) / 256), dim3(256), 0, s, X, Y, D, head);
     }
+    if (ws.tap) {  // (after the heads are cleared: what conv2 reads)
+      const std::string nm = "aa.b" + std::to_string(i);
+      ATAP(nm + ".y", Y, ipix * K.cout);
+      if (K.wd) ATAP(nm + ".d", D, ipix * K.cout);
+    }
     // conv2 (pad (0,1)) on Y + residual, written over X (each element is read, as the
     // residual, by the same thread that then overwrites it)
     memset(&g, 0, sizeof g);
@@ -1116,6 +1140,7 @@ const char* aasist_forward(const AasistWeights& w, const float* feats, int B, in
     }
     g.img = img; g.wp = wp; g.hout = AAS_F; g.wd = wd; g.out = X; g.ldo = K.cout; g.o_off = wp + 1;
     AOK(launch_f32_gemm(g, s));
+    if (ws.tap) ATAP("aa.b" + std::to_string(i), X, ipix * K.cout);
     AAS_STAGE();  // 4..8: residual blocks 1..5
   }
   // ---- attention maps: 1x1 convs over the padded image --------------------------------
@@ -1125,10 +1150,12 @@ const char* aasist_forward(const AasistWeights& w, const float* feats, int B, in
     g.A = X; g.lda = 64; g.nch = 1; g.kc = 64; g.W = w.att_w0; g.Wh = w.att_s0.hi; g.Wl = w.att_s0.lo; g.M = M; g.N = 128; g.bias = w.att_b0;
     g.bn_scale = w.att_bn_scale; g.bn_shift = w.att_bn_shift; g.post = 2; g.out = ws.wmap1; g.ldo = 128;
     AOK(launch_f32_gemm(g, s));
+    ATAP("aa.w1", ws.wmap1, (size_t)M * 128);
     memset(&g, 0, sizeof g);
     g.A = ws.wmap1; g.lda = 128; g.nch = 1; g.kc = 128; g.W = w.att_w3; g.Wh = w.att_s3.hi; g.Wl = w.att_s3.lo; g.M = M; g.N = 64; g.bias = w.att_b3;
     g.out = ws.wmap2; g.ldo = 64;
     AOK(launch_f32_gemm(g, s));
+    ATAP("aa.w2", ws.wmap2, (size_t)M * 64);
   }
   hipLaunchKernelGGL(att_pool_kernel, dim3(AAS_F + wd, B), dim3(64), 0, s, X, ws.wmap2, img, wp, wd, w.pos_S, ws.eS,
                      ws.eT);
@@ -1225,6 +1252,11 @@ const char* aasist_forward(const AasistWeights& w, const float* feats, int B, in
     dbg("b1_T1", br[0].T1, (size_t)B * nT * 32); dbg("b1_S1", br[0].S1, (size_t)B * nS * 32); dbg("b1_m1", br[0].m1, (size_t)B * 32);
     dbg("b1_T1p", br[0].T1p, (size_t)B * nT1 * 32); dbg("b1_S1p", br[0].S1p, (size_t)B * nS1 * 32);
     dbg("b1_Ta", br[0].Ta, (size_t)B * nT1 * 32); dbg("b1_Sa", br[0].Sa, (size_t)B * nS1 * 32); dbg("b1_ma", br[0].ma, (size_t)B * 32);
+    dbg("b2_T1", br[1].T1, (size_t)B * nT * 32); dbg("b2_S1", br[1].S1, (size_t)B * nS * 32); dbg("b2_m1", br[1].m1, (size_t)B * 32);
+    dbg("b2_T1p", br[1].T1p, (size_t)B * nT1 * 32); dbg("b2_S1p", br[1].S1p, (size_t)B * nS1 * 32);
+    dbg("b2_Ta", br[1].Ta, (size_t)B * nT1 * 32); dbg("b2_Sa", br[1].Sa, (size_t)B * nS1 * 32); dbg("b2_ma", br[1].ma, (size_t)B * 32);
+    dbg("b1_xp", br[0].xp, (size_t)B * (nT + nS) * 64); dbg("b1_xp2", br[0].xp2, (size_t)B * (nT1 + nS1) * 32);
+    dbg("b2_xp", br[1].xp, (size_t)B * (nT + nS) * 64); dbg("b2_xp2", br[1].xp2, (size_t)B * (nT1 + nS1) * 32);
     ws.dbg_count = n;
   }
   hipLaunchKernelGGL(readout_kernel, dim3(B), dim3(32), 0, s, br[0].T1p, br[0].Ta, br[0].S1p, br[0].m1, br[0].ma,
@@ -1232,6 +1264,7 @@ const char* aasist_forward(const AasistWeights& w, const float* feats, int B, in
                      ws.hidden, logits, nonfinite);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? nullptr : hipGetErrorString(e);
+#undef ATAP
 }
 
 }  // namespace afx

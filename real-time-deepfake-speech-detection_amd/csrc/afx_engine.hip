@@ -1412,9 +1412,18 @@ static int run_conformer(afx_engine* e, int B, int T, Ws& w, float* logits, hipS
 static int run_head(afx_engine* e, int B, int T, Ws& w, float* logits, hipStream_t s) {
   if (e->cfg.arch == AFX_ARCH_CONFORMER) return run_conformer(e, B, T, w, logits, s);
   if (e->cfg.arch == AFX_ARCH_XLSR_AASIST) {
-    if (const char* m = timed(PC_AASIST, 2.0 * B * 1.399e9 / 2, s, [&] { return aasist_forward(e->aw, w.ssl_f, B, T, w.aa, logits, s, e->nonfinite + 1); }))
-      return fail("%s", m);
+    // taps on: the back-end hands every launch's output to tap() before a later launch overwrites it
+    struct TapCtx { afx_engine* e; hipStream_t s; } tc{e, s};
+    w.aa.tap = e->taps_on ? +[](void* c, const char* nm, const float* p, size_t n) {
+      return tap(((TapCtx*)c)->e, nm, p, n, false, ((TapCtx*)c)->s);
+    } : nullptr;
+    w.aa.tap_ctx = e->taps_on ? &tc : nullptr;
+    const char* m = timed(PC_AASIST, 2.0 * B * 1.399e9 / 2, s, [&] { return aasist_forward(e->aw, w.ssl_f, B, T, w.aa, logits, s, e->nonfinite + 1); });
+    w.aa.tap = nullptr;
+    w.aa.tap_ctx = nullptr;
+    if (m) return fail("%s", m);
     if (e->taps_on) {
+      if (tap(e, "logits", logits, (size_t)B * 2, false, s)) return 1;
       if (tap(e, "e_S", w.aa.eS, (size_t)B * 42 * 64, false, s)) return 1;
       if (tap(e, "e_T", w.aa.eT, (size_t)B * (T / 3) * 64, false, s)) return 1;
       if (tap(e, "hidden", w.aa.hidden, (size_t)B * 160, false, s)) return 1;
@@ -2761,6 +2770,10 @@ extern "C" int afx_debug_set(const char* key, int value) {
   }
   if (!strcmp(key, "aasist_stop")) {
     aasist_set_stop(value);
+    return 0;
+  }
+  if (!strcmp(key, "aasist_conv_slots")) {
+    aasist_set_conv_slots(value);
     return 0;
   }
   if (!strcmp(key, "gemm_tile")) {

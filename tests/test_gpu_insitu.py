@@ -1,5 +1,5 @@
-"""Per-launch parity inside real forwards on an MI355X: every tapped launch of the SSL trunk and of the Conformer head
-against its fp64 reference (oracle/insitu.py) built from the launch's own tapped inputs, element by element within the
+"""Per-launch parity inside real forwards on an MI355X: every tapped launch of the SSL trunk, of the Conformer head and
+of the AASIST back-end against its fp64 reference (oracle/insitu.py) built from the launch's own tapped inputs, element by element within the
 bounds stated there.  Large products are checked on a deterministic subset of rows (``check_rows``).  The module's
 summary line gives, per launch class and dtype, the worst |got - ref| / bound and the rounding-bias statistic."""
 import pytest
@@ -249,6 +249,88 @@ def test_head_launches_even_kernel(mods):
     head_checks(mods, eng, sd, _feats(3, 124, 7), "fp16", 1)
 
 
+# ---- AASIST back-end ---------------------------------------------------------------------------------------------------------
+_AAS = {}
+
+
+def _aasist(mods, dt):
+    """One xlsr_aasist engine per dtype (one-layer trunk, the lively head), shared by the tests of this module."""
+    engine, synth, I, ST = mods
+    if "sd" not in _AAS:
+        _AAS["sd"] = synth.model_state_dict("XLSR_AASIST", n_layers=1, head_scale=1.5)
+    if dt not in _AAS:
+        _AAS[dt] = engine.Engine("xlsr_aasist", n_layers=1, dtype=dt)
+        _AAS[dt].load_state_dict(_AAS["sd"])
+    return _AAS[dt], _AAS["sd"]
+
+
+AAS_TAPS = ["aa.ll", "aa.x1", "aa.b0.y", "aa.b0.d", "aa.b0", "aa.b1.y", "aa.b1", "aa.b2.y", "aa.b2.d", "aa.b2", "aa.b3.y", "aa.b3",
+            "aa.b4.y", "aa.b4", "aa.b5.y", "aa.b5", "aa.w1", "aa.w2", "e_S", "e_T", "gat_S", "gat_T", "out_S", "out_T"] + \
+           [f"b{k}_{t}" for k in (1, 2) for t in ("xp", "T1", "S1", "m1", "T1p", "S1p", "xp2", "Ta", "Sa", "ma")] + ["hidden", "logits"]
+
+
+def aasist_checks(mods, eng, sd, feats, dt):
+    """One taps-on forward of the back-end; every launch against its reference (oracle/insitu.py::aasist_walk)."""
+    engine, synth, I, ST = mods
+    eng.enable_taps()
+    eng.head(feats.cuda())
+    torch.cuda.synchronize()
+    res, zeros = I.aasist_walk(sd, feats, lambda n: eng.tap(n).cpu().double(), dt != "fp32")
+    eng.enable_taps(False)
+    fails = []
+    for cls, name, r in res:
+        gate(cls, dt, name, r, I, fails)
+    fails += [f"{name} [{dt}]: {n} nonzero floats in the image head / at invalid virtual pixels" for name, n in zeros if n]
+    assert sum(1 for cls, _, _ in res if cls == "pool") == 6  # (every pool is checked: near ties are tolerated, not skipped)
+    assert not fails, "\n".join(fails)
+
+
+@pytest.mark.parametrize("dt", ["fp16", "bf16", "fp32", "fp16x3"])
+def test_aasist_launches_ragged_last_tile(mods, dt):
+    eng, sd = _aasist(mods, dt)
+    aasist_checks(mods, eng, sd, _feats(2, 49, 2049), dt)
+
+
+def test_aasist_conv_many_tiles_per_workgroup(mods):
+    """Three workgroups walk the 26 tiles of (2, 49): nine tiles each, the prefetch of the next tile and its clamp at the
+    last pixel; every tap equals the automatic grid's bit for bit."""
+    from afx._lib import lib, check
+    eng, sd = _aasist(mods, "fp16")
+    feats = _feats(2, 49, 2049)
+    eng.enable_taps()
+    eng.head(feats.cuda())
+    auto = _all_taps(eng, AAS_TAPS)
+    eng.enable_taps(False)
+    check(lib().afx_debug_set(b"aasist_conv_slots", 3))
+    try:
+        aasist_checks(mods, eng, sd, feats, "fp16")
+        capped = _all_taps(eng, AAS_TAPS)
+    finally:
+        check(lib().afx_debug_set(b"aasist_conv_slots", 0))
+    for n in AAS_TAPS:
+        assert torch.equal(auto[n], capped[n]), f"tap {n} depends on the conv kernel's grid"
+
+
+@pytest.mark.parametrize("B,T,dt", [(3, 200, "fp16"), (3, 200, "fp32"), (1, 6, "fp16"), (2, 10, "fp16"), (2, 17, "fp16"), (16, 199, "fp16"),
+                                    (1, 573, "fp16"), (1, 1887, "fp16")])
+def test_aasist_launches_edge_shapes(mods, B, T, dt):
+    eng, sd = _aasist(mods, dt)
+    aasist_checks(mods, eng, sd, _feats(B, T, B * 1000 + T), dt)
+
+
+def test_aasist_documented_maximum(mods):
+    """629 temporal nodes (T <= 1889) is what the graph kernel's LDS slab holds: T = 1889 scores, T = 1890 is refused by
+    aasist_forward's own message before anything is launched."""
+    from afx._lib import AfxError
+    eng, sd = _aasist(mods, "fp16")
+    assert bool(torch.isfinite(eng.head(_feats(1, 1889, 2889).cuda())).all())
+    try:
+        out = eng.head(_feats(1, 1890, 2890).cuda())
+        assert bool(torch.isfinite(out).all())
+    except AfxError as e:
+        assert "clip too long for the graph kernels" in str(e), str(e)
+
+
 # ---- taps change nothing; a stale workspace changes nothing ----------------------------------------------------------------
 @pytest.mark.parametrize("dt", ["fp16", "bf16", "fp32", "fp16x3"])
 def test_taps_do_not_change_the_forward(mods, dt):
@@ -262,6 +344,12 @@ def test_taps_do_not_change_the_forward(mods, dt):
     on = eng.forward(wave).cpu()
     eng.enable_taps(False)
     assert torch.equal(on, off), f"[{dt}] taps moved the logits by {(on - off).abs().max().item():.3e}"
+    eng, _ = _aasist(mods, dt)
+    off = eng.forward(wave).cpu()
+    eng.enable_taps()
+    on = eng.forward(wave).cpu()
+    eng.enable_taps(False)
+    assert torch.equal(on, off), f"[{dt}] xlsr_aasist: taps moved the logits by {(on - off).abs().max().item():.3e}"
 
 
 def _all_taps(eng, names):
@@ -304,3 +392,10 @@ def test_stale_workspace_head_fp16x3_unfused(mods):
             ["block0", "block1"]
     other, feats = _feats(5, 230, 3).cuda(), _feats(3, 124, 4).cuda()
     _stale_vs_fresh(eng, lambda: eng.head(other), lambda: eng.head(feats), names, False)
+
+
+@pytest.mark.parametrize("dt", ["fp16", "fp32"])
+def test_stale_workspace_aasist(mods, dt):
+    eng, sd = _aasist(mods, dt)
+    other, feats = _feats(5, 230, 5230).cuda(), _feats(3, 124, 3124).cuda()
+    _stale_vs_fresh(eng, lambda: eng.head(other), lambda: eng.head(feats), AAS_TAPS, False)
