@@ -336,6 +336,29 @@ int afx_k_jitter_conceal(float* jring, int S, int J, const int* hdr, int rows, i
  *     leave a ring is skipped whole. */
 int afx_k_jitter_release(const float* jring, int S, int J, const int* hdr, int rows, int max_out, const float* taps, int L,
                          int M, int T, float* ring, int ring_len, void* stream);
+/* Speech gate (afx/vad.py): an energy gate with noise-floor tracking and hangover over frames of `frame` 16 kHz samples
+ * (160 = 10 ms), per slot.  Constants, fp32: e_floor (the mean-square floor times frame), ratio > 1, rise >= 1, and
+ * nf_min = e_floor / ratio (one fp32 division); hang >= 0 frames.  State per slot: nf (S,) fp32, +inf for a new stream, and
+ * h (S,) int32, 0 for a new stream.  The energy e of a frame x[0..frame) is a sum of squares in ONE order, every operation
+ * a single correctly rounded fp32 multiply or add (no fma):
+ *     sq[i] = x[i]*x[i];  p[l] = sq[l] + sq[l + 64] + sq[l + 128] + ... for l < 64, ascending, only indices < frame (a lane
+ *     with none holds 0);  for w = 32, 16, 8, 4, 2, 1: p[l] = p[l] + p[l + w], l < w;  e = p[0]
+ * Per frame, in stream order:
+ *     speech = e < inf && e > max(e_floor, ratio * nf)           (nf = inf: not speech)
+ *     if (e < inf) nf = max(nf_min, min(e, nf * rise))           (a non-finite e leaves nf alone)
+ *     if (speech) h = hang;   keep = speech || h > 0;   if (!speech && h > 0) h -= 1
+ * so exactly `hang` frames after the last speech frame are kept, and none before an onset.
+ * afx_k_gate: x (A, n) fp32 on the device, n a positive multiple of frame; row i is the next n samples of the stream in
+ * slot hdr[i][0] (hdr: device, A x 2 int32 = slot, wpos; the slots of one call are distinct).  The kept frames of row i
+ * are copied bit for bit, in order, to ring[slot][(wpos + k) mod ring_len] (ring (S, ring_len) fp32, the layout
+ * afx_k_ingest_pop reads); kept[i] (A,) int32 on the device receives the number of samples kept; nf[slot] and h[slot] take
+ * the state after the row; mask, (A, n / frame) bytes on the device or NULL, receives every frame's keep flag (0 / 1).
+ * Rows of slots not named are untouched.  A row whose header would leave the state or the ring (slot outside [0, S), wpos
+ * outside [0, ring_len)), or whose n exceeds ring_len, is skipped whole with kept[i] = 0 (its mask row is not written).
+ * One launch takes at most 512 frames of every row (its per-frame tables live in LDS); a longer row goes in successive
+ * launches on the same stream that carry nf, h and kept through device memory: the result does not depend on the split. */
+int afx_k_gate(const float* x, int A, int n, const int* hdr, int frame, float e_floor, float ratio, float rise, int hang,
+               float* nf, int* h, float* ring, int S, int ring_len, int* kept, unsigned char* mask, void* stream);
 int afx_k_rownorm(int dtype, const float* x, long ldx, int rows, int C, const float* gamma, const float* beta,
                   float eps, int act, float* out_f, long ldo_f, void* out_h, long ldo_h, void* stream);
 int afx_k_mhsa(int dtype, const void* qkv, void* out, int B, int T, int H, void* stream);

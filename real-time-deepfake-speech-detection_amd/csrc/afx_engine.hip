@@ -2899,6 +2899,12 @@ extern "C" int afx_k_jitter_release(const float* jring, int S, int J, const int*
                                     int L, int M, int T, float* ring, int ring_len, void* stream) {
   KRET(launch_jitter_release(jring, S, J, hdr, rows, max_out, taps, L, M, T, ring, ring_len, (hipStream_t)stream));
 }
+extern "C" int afx_k_gate(const float* x, int A, int n, const int* hdr, int frame, float e_floor, float ratio, float rise,
+                          int hang, float* nf, int* h, float* ring, int S, int ring_len, int* kept, unsigned char* mask,
+                          void* stream) {
+  KRET(launch_gate(x, A, n, hdr, frame, e_floor, ratio, rise, hang, nf, h, ring, S, ring_len, kept, mask,
+                   (hipStream_t)stream));
+}
 extern "C" int afx_k_rownorm(int dtype, const float* x, long ldx, int rows, int C, const float* gamma,
                              const float* beta, float eps, int act, float* out_f, long ldo_f, void* out_h, long ldo_h,
                              void* stream) {

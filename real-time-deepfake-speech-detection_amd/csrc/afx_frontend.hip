@@ -1126,6 +1126,126 @@ const char* launch_jitter_release(const float* jring, int S, int J, const int* h
 }
 
 // ---------------------------------------------------------------------------------
+// Speech gate (afx/vad.py; the function is stated in include/afx.h afx_k_gate): a per-slot energy gate over frames of
+// `frame` 16 kHz samples with a tracked noise floor and a hangover; the kept frames of a row are compacted, bit for bit, into
+// the slot's pending ring (the layout ingest_pop_kernel reads).  One workgroup per row, three phases:
+//   1. the four waves compute the frame energies into LDS: lane l sums sq[l], sq[l + 64], ... in ascending order, then a
+//      shuffle-down tree folds the 64 partials (w = 32 .. 1).  Every operation is one correctly rounded fp32 multiply or
+//      add (contraction is off in gate_frame_energy: p + v * v must not become an fma), so numpy float32 restates it;
+//   2. thread 0 runs the state machine over the frames in stream order (a serial recurrence of a few ops per frame),
+//      writes each frame's offset among the kept samples (or -1: dropped) to LDS and stores nf, h and kept;
+//   3. the four waves copy the kept frames, 64 consecutive samples per step.
+// A launch takes at most GATE_MAX_FRAMES frames of a row (what its LDS tables hold); launch_gate splits a longer row into
+// successive launches that find nf, h and the samples kept so far in device memory.
+// ---------------------------------------------------------------------------------
+constexpr int GATE_MAX_FRAMES = 512;  // frames of a row per launch: 2 x 512 x 4 bytes of LDS (include/afx.h states it)
+
+struct GateArgs {
+  const float* x;    // (A, n) samples, row i = the next n samples of slot hdr[i][0]
+  const int* hdr;    // (A, 2): slot, wpos
+  float* nf;         // (S,) noise floor per slot
+  int* h;            // (S,) hangover frames left per slot
+  float* ring;       // (S, ring_len)
+  int* kept;         // (A,) samples kept of each row
+  unsigned char* mask;  // (A, n / frame) keep flag of every frame, or nullptr
+  int n, frame, f0, nframes;  // this launch: frames [f0, f0 + nframes) of the n / frame of a row
+  int S, ring_len, hang;
+  float e_floor, ratio, rise, nf_min;
+};
+
+// the energy of one frame as lane `lane` of a wave sees it (lane 0 holds the result)
+__device__ __forceinline__ float gate_frame_energy(const float* __restrict__ x, int frame, int lane) {
+#pragma clang fp contract(off)
+  float p = 0.f;
+  if (lane < frame) {
+    const float v = x[lane];
+    p = v * v;
+  }
+  for (int i = lane + 64; i < frame; i += 64) {
+    const float v = x[i];
+    const float sq = v * v;
+    p = p + sq;
+  }
+  for (int w = 32; w >= 1; w >>= 1) {
+    const float q = __shfl_down(p, w);  // lanes l < w take p[l + w]: the lanes the next step reads
+    p = p + q;
+  }
+  return p;
+}
+
+__global__ __launch_bounds__(256) void gate_kernel(GateArgs a) {
+  __shared__ float s_e[GATE_MAX_FRAMES];
+  __shared__ int s_off[GATE_MAX_FRAMES];  // offset of the frame among this launch's kept samples, -1: dropped
+  __shared__ int s_base;                  // samples of the row kept by the launches before this one
+  const int row = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int slot = a.hdr[2 * row], wpos = a.hdr[2 * row + 1];
+  if (!(slot >= 0 && slot < a.S && wpos >= 0 && wpos < a.ring_len && a.n <= a.ring_len)) {
+    if (tid == 0 && a.f0 == 0) a.kept[row] = 0;
+    return;
+  }
+  const float* x = a.x + (long long)row * a.n + (long long)a.f0 * a.frame;
+  for (int f = wave; f < a.nframes; f += 4) {
+    const float e = gate_frame_energy(x + (long long)f * a.frame, a.frame, lane);
+    if (lane == 0) s_e[f] = e;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    float nf = a.nf[slot];
+    int h = a.h[slot], off = 0;
+    for (int f = 0; f < a.nframes; ++f) {
+      const float e = s_e[f];
+      const bool fin = e < INFINITY;  // (false for a NaN too)
+      const bool speech = fin && e > fmaxf(a.e_floor, a.ratio * nf);
+      if (fin) nf = fmaxf(a.nf_min, fminf(e, nf * a.rise));
+      if (speech) h = a.hang;
+      const bool keep = speech || h > 0;
+      if (!speech && h > 0) --h;
+      s_off[f] = keep ? off : -1;
+      if (keep) off += a.frame;
+      if (a.mask) a.mask[(long long)row * (a.n / a.frame) + a.f0 + f] = keep;
+    }
+    const int base = a.f0 ? a.kept[row] : 0;
+    a.nf[slot] = nf;
+    a.h[slot] = h;
+    a.kept[row] = base + off;
+    s_base = base;
+  }
+  __syncthreads();
+  float* out = a.ring + (long long)slot * a.ring_len;
+  const long long w0 = (long long)wpos + s_base;  // base + off + k < n <= ring_len: one wrap
+  for (int f = wave; f < a.nframes; f += 4) {
+    const int off = s_off[f];
+    if (off < 0) continue;
+    const float* src = x + (long long)f * a.frame;
+    for (int k = lane; k < a.frame; k += 64) {
+      const long long w = w0 + off + k;
+      out[w < a.ring_len ? w : w - a.ring_len] = src[k];
+    }
+  }
+}
+
+const char* launch_gate(const float* x, int A, int n, const int* hdr, int frame, float e_floor, float ratio, float rise, int hang,
+                        float* nf, int* h, float* ring, int S, int ring_len, int* kept, unsigned char* mask, hipStream_t s) {
+  if (!x || !hdr || !nf || !h || !ring || !kept) return "gate: null argument";
+  if (A <= 0 || A > 65535) return "gate: 1 to 65535 rows";
+  if (frame <= 0 || n <= 0 || n % frame) return "gate: a row is a positive whole number of frames";
+  if (S <= 0 || ring_len <= 0) return "gate: no slots or no ring";
+  if (!(e_floor > 0.f && e_floor < INFINITY && ratio > 1.f && ratio < INFINITY && rise >= 1.f && rise < INFINITY) || hang < 0)
+    return "gate: floor > 0, ratio > 1, rise >= 1 (all finite) and hang >= 0";
+  GateArgs a{};
+  a.x = x; a.hdr = hdr; a.nf = nf; a.h = h; a.ring = ring; a.kept = kept; a.mask = mask;
+  a.n = n; a.frame = frame; a.S = S; a.ring_len = ring_len; a.hang = hang;
+  a.e_floor = e_floor; a.ratio = ratio; a.rise = rise; a.nf_min = e_floor / ratio;  // (one IEEE fp32 division, on the host)
+  const int frames = n / frame;
+  for (a.f0 = 0; a.f0 < frames; a.f0 += GATE_MAX_FRAMES) {
+    a.nframes = min(GATE_MAX_FRAMES, frames - a.f0);
+    hipLaunchKernelGGL(gate_kernel, dim3(A), dim3(256), 0, s, a);
+  }
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+// ---------------------------------------------------------------------------------
 // Row LayerNorm (+ activation): one wave per row, C <= 1024, C % 4 == 0.  The row
 // stays in registers (float4 per lane per 256-column slab), two-pass statistics in
 // fp32 like torch.  Used for the conv-stack LayerNorm+GELU, every transformer /

@@ -153,6 +153,11 @@ const char* launch_jitter_conceal(float* jring, int S, int J, const int* hdr, in
                                   int F, int mode, hipStream_t s);
 const char* launch_jitter_release(const float* jring, int S, int J, const int* hdr, int rows, int max_out, const float* taps,
                                   int L, int M, int T, float* ring, int ring_len, hipStream_t s);
+// speech gate (include/afx.h afx_k_gate): per-slot energy gate with noise-floor tracking and hangover over the frames of each
+// row; the kept frames are compacted into the slot's pending ring, kept[i] = the samples kept of row i,
+// mask (optional) the keep flag of every frame
+const char* launch_gate(const float* x, int A, int n, const int* hdr, int frame, float e_floor, float ratio, float rise, int hang,
+                        float* nf, int* h, float* ring, int S, int ring_len, int* kept, unsigned char* mask, hipStream_t s);
 void conv0_set_mfma(int v);  // A/B knob: 1 (default) = matrix-core forms (split-precision fp16 when packed), 2 = fp32 MFMA form, 0 = VALU form
 // y[t] = x[t] - coef * x[t-1] with a reflect pad on the left; (B,L) fp32 -> (B,L) fp32
 const char* launch_pre_emphasis(const float* x, int B, int L, float coef, float* y, hipStream_t s);

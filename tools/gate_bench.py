@@ -1,0 +1,127 @@
+"""The speech gate measured against the bare scorer on the same build: S live streams of seeded synthetic talk-spurt audio
+(alternating exponential talk / silence spells, --activity of the time in talk on average; talk = a 180 Hz tone under a 4 Hz
+tremolo at -14 dBFS, silence = noise at -54 dBFS), the student scores them in KV-cached mode.  Two ways, timed per 250-ms hop:
+
+  gated     afx.vad.GatedScorer around the KV-cached scorer: every hop one ``push`` of all S slots (one afx_k_gate launch,
+            one read-back of S int32, one pop and one inner push over the slots that completed a hop of kept audio);
+  bare      the KV-cached scorer alone pushed the same hops lock-stepped: every slot scored every hop, what the parent of
+            the gate could do.
+
+    python tools/gate_bench.py [--streams 2048] [--activity 0.4] [--hops 8] [--reps 3]
+    rocprofv3 --kernel-trace --stats ... -- python tools/gate_bench.py --profile   (gated path only, 4 hops: kernel times)
+
+The two paths score different audio by design (the gate drops frames), so their scores are not compared; the gate's own
+contract is pinned by tests/test_gpu_vad.py.  Printed with the times: the share of slot-pushes that emitted a score and the
+share of samples kept.  Times are the median over --reps timed passes after one warm-up pass (min and max given), wall
+clock around a pass that ends in a device synchronise.  The streams come from a bank of --bank distinct seeded streams, each
+slot reading one of them from its own whole-hop offset.  Stamped with afx_build_id()."""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "real-time-deepfake-speech-detection_amd")]
+from afx import engine, synth  # noqa: E402
+from afx._lib import lib  # noqa: E402
+from afx.streaming import KVCachedScorer  # noqa: E402
+from afx.vad import GatedScorer, SpeechGate, emitted  # noqa: E402
+
+W, H = 64000, 4000
+
+
+def talk_spurts(n, activity, g, talk_s=1.0):
+    """n samples at 16 kHz: alternating talk / silence spells with exponential lengths (mean talk_s seconds of talk)."""
+    x = (0.002 * g.standard_normal(n)).astype(np.float32)
+    t = np.arange(n) / 16000
+    voice = (0.2 * np.sin(2 * np.pi * 180 * t) * (1 + 0.5 * np.sin(2 * np.pi * 4 * t))).astype(np.float32)
+    quiet_s = talk_s * (1 - activity) / activity
+    pos, talking = 0, g.random() < activity
+    while pos < n:
+        m = int(16000 * g.exponential(talk_s if talking else quiet_s)) + 160
+        if talking:
+            x[pos:pos + m] += voice[pos:pos + m]
+        pos, talking = pos + m, not talking
+    return x
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--streams", type=int, default=2048)
+    ap.add_argument("--activity", type=float, default=0.4)
+    ap.add_argument("--bank", type=int, default=64, help="distinct synthetic streams the slots draw from")
+    ap.add_argument("--hops", type=int, default=8, help="hops per timed pass")
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--profile", action="store_true", help="the gated path only, a short pass (for a rocprofv3 run)")
+    args = ap.parse_args()
+    S = args.streams
+    torch.cuda.set_device(0)
+    sd = synth.model_state_dict("ConformerModel", n_layers=6)
+    eng = engine.Engine("conformer", n_layers=6, dtype="fp16")
+    eng.load_state_dict(sd)
+    passes = 1 if args.profile else 1 + args.reps
+    hops = 4 if args.profile else args.hops
+    warm = W // H + 2
+    n_hops = warm + passes * hops
+    g = np.random.default_rng(11)
+    bank_hops = 4 * n_hops
+    bank = torch.from_numpy(np.stack([talk_spurts(bank_hops * H, args.activity, g) for _ in range(args.bank)])).cuda()
+    bank = bank.reshape(args.bank, bank_hops, H)
+    which = torch.from_numpy(g.integers(0, args.bank, S)).cuda()
+    start = torch.from_numpy(g.integers(0, bank_hops, S)).cuda()
+
+    def hop(t):
+        return bank[which, (start + t) % bank_hops].contiguous()
+
+    print(f"gate_bench: build {lib().afx_build_id().decode()}; student fp16 (6 layers), KV-cached, {S} streams of synthetic "
+          f"talk spurts ({args.activity:.0%} talk), gate {SpeechGate().params()}; {hops} hops per pass, {args.reps} timed passes "
+          f"per path after a warm-up pass of {warm} hops", flush=True)
+    results = {}
+    for name in (["gated"] if args.profile else ["gated", "bare"]):
+        inner = KVCachedScorer(eng, sd, S, window=W, hop=H)
+        front = GatedScorer(inner) if name == "gated" else inner
+        pushes = scores = 0
+
+        def run(t0, n):
+            nonlocal pushes, scores
+            chunks = [hop(t) for t in range(t0, t0 + n)]
+            outs = []
+            torch.cuda.synchronize()
+            begin = time.perf_counter()
+            for c in chunks:
+                outs.append(front.push(c))
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - begin
+            if name == "gated":
+                pushes += n * S
+                scores += int(sum(emitted(o).sum() for o in outs))
+            return dt
+
+        run(0, warm)
+        times = []
+        for rep in range(passes):
+            dt = run(warm + rep * hops, hops)
+            if rep > 0 or args.profile:
+                times.append(dt / hops)
+        times.sort()
+        med = times[len(times) // 2]
+        results[name] = (med, times)
+        extra = ""
+        if name == "gated":
+            kept = float(front.samples_kept.sum()) / float(front.samples_seen.sum())
+            extra = f"; {scores / pushes:.1%} of {pushes} slot-pushes emitted a score, {kept:.1%} of the samples kept"
+        print(f"  {name:6s} {med * 1e3:8.2f} ms per hop (min {times[0] * 1e3:.2f}, max {times[-1] * 1e3:.2f}); RTF {med / 0.25:.3f}{extra}",
+              flush=True)
+        del front, inner
+        torch.cuda.empty_cache()
+    if not args.profile:
+        (mg, tg), (mb, tb) = results["gated"], results["bare"]
+        print(f"  gated / bare {mg / mb:.2f}x (spread of bare: {(tb[-1] - tb[0]) / mb * 100:.1f} % of its median, of gated: "
+              f"{(tg[-1] - tg[0]) / mg * 100:.1f} %)", flush=True)
+
+
+if __name__ == "__main__":
+    main()
