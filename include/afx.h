@@ -359,6 +359,42 @@ int afx_k_jitter_release(const float* jring, int S, int J, const int* hdr, int r
  * launches on the same stream that carry nf, h and kept through device memory: the result does not depend on the split. */
 int afx_k_gate(const float* x, int A, int n, const int* hdr, int frame, float e_floor, float ratio, float rise, int hang,
                float* nf, int* h, float* ring, int S, int ring_len, int* kept, unsigned char* mask, void* stream);
+/* Cascade (afx/cascade.py): a cheap screen scores every slot at every hop; the windows of the slots whose score looks
+ * suspicious are gathered for a second model, under a per-push budget and a per-slot cooldown.  Every index comes from a
+ * host-built header (device int32), nothing is allocated, all three run on `stream`.  State: hist (S, window) fp32, the
+ * retained audio, sample t of a session at column t mod window; wait (S,) int32, 0 for a new stream.
+ * The selection.  A push names rows i = 0..A-1: slot b_i (distinct), score s_i (fp32), elig_i.  With fp32 compares,
+ *     cand_i       = elig_i && wait[b_i] == 0 && s_i < threshold      (a NaN score: never; threshold = +inf: every finite or -inf score)
+ *     before(j, i) = s_j < s_i || (!(s_i < s_j) && b_j < b_i)         (ties, -0.0 / +0.0 included, go to the lower slot)
+ *     rank_i       = the number of candidates j with before(j, i)
+ *     chosen_i     = cand_i && rank_i < budget
+ *     wait[b_i]    = chosen_i ? cooldown : max(wait[b_i] - 1, 0)      (named slots only)
+ * There is no ageing: a candidate the budget passed over keeps wait == 0 and competes again at its next hop.
+ * afx_k_cascade_store: x (A, hop) fp32; hdr (A x 2 int32) = slot, wpos: hist[slot][(wpos + k) mod window] = x[i][k], k < hop
+ *     (hop <= window).  Four samples per lane where wpos, hop and window are multiples of 4 and both rows are 16-byte
+ *     aligned, one per lane otherwise: any wpos in [0, window), any hop and window.  Rows of slots not named are untouched;
+ *     a row with its slot outside [0, S) or its wpos outside [0, window) is skipped whole.
+ * afx_k_cascade_select: scores (A,) fp32 on the device, s_i = scores[i * stride] (stride >= 1: a column of a logits matrix is
+ *     read in place); hdr (A x 2 int32) = slot, elig (0 / non-zero); 1 <= A <= 8192 (one
+ *     workgroup ranks the rows, 8-byte keys in 64 KB of LDS; a larger A is an error and launches nothing); budget >= 1,
+ *     cooldown >= 0, threshold not NaN.  sel, int32 (1 + budget): sel[0] = n = min(candidates, budget), sel[1..n] = the
+ *     chosen ROW POSITIONS i in ascending rank; entries after n are not written.  wait is advanced as above.  counts, (S x 2) int32 or
+ *     NULL: counts[b_i][0] += cand_i, counts[b_i][1] += cand_i && !chosen_i (the candidates the budget passed over).  A row
+ *     with its slot outside [0, S) is skipped whole (no candidate, no wait or counts written).
+ * afx_k_cascade_windows: hdr (A x 3 int32) = slot, n, start, with n = min(samples the session has seen, window) and
+ *     start = seen mod window when seen >= window, else 0.  For r < min(sel[0], budget) and i = sel[1 + r]:
+ *         out[r][j] = hist[slot_i][(start_i + j) mod n_i],  j < window       (out (budget, window) fp32)
+ *     -- the window oldest sample first; while n < window the history tiled, afx_k_tile_crop's function with start 0.  sel
+ *     is read on the device (no read-back between select and gather); the grid covers budget rows, and rows at or past
+ *     sel[0] write nothing.  Steady rows (n = window) copy four samples per lane where start and window are multiples of 4
+ *     and both rows 16-byte aligned.  A row whose sel entry is outside [0, A), whose slot is outside [0, S), whose n is
+ *     outside [1, window] or whose start is outside [0, n) is skipped whole.
+ * A NULL pointer or a size that is not positive: non-zero, afx_last_error set, nothing launched. */
+int afx_k_cascade_store(const float* x, int A, int hop, const int* hdr, float* hist, int S, int window, void* stream);
+int afx_k_cascade_select(const float* scores, int stride, const int* hdr, int A, int* wait, int* counts, int S,
+                         float threshold, int budget, int cooldown, int* sel, void* stream);
+int afx_k_cascade_windows(const float* hist, int S, int window, const int* hdr, int A, const int* sel, int budget,
+                          float* out, void* stream);
 int afx_k_rownorm(int dtype, const float* x, long ldx, int rows, int C, const float* gamma, const float* beta,
                   float eps, int act, float* out_f, long ldo_f, void* out_h, long ldo_h, void* stream);
 int afx_k_mhsa(int dtype, const void* qkv, void* out, int B, int T, int H, void* stream);

@@ -53,6 +53,7 @@ import numpy as np
 import torch
 
 from ._lib import AfxError, call_on, check, lib, ptr
+from .cascade import CascadeScorer
 from .streaming import SlidingWindowScorer, StreamState, _Front, _on
 
 GATE_FORMAT = 1  # layout of the gate part of a StreamState: import_slots refuses any other
@@ -198,8 +199,8 @@ def emitted(scores):
 
 
 class GatedScorer:
-    """``scorer`` (a SlidingWindowScorer, IncrementalScorer or KVCachedScorer) behind a ``SpeechGate`` (default: the default
-    gate); see the module docstring for the contract.  It presents the surface the fronts drive an inner scorer through, so
+    """``scorer`` (a SlidingWindowScorer, IncrementalScorer or KVCachedScorer, or an ``afx.cascade.CascadeScorer`` around
+    one: screen and verifier then see the same gated stream) behind a ``SpeechGate`` (default: the default gate); see the module docstring for the contract.  It presents the surface the fronts drive an inner scorer through, so
     it goes INSIDE them: ``PacketScorer(GatedScorer(inner), 8000, "mulaw")``.
 
     Per slot a ring of 2 hops of kept samples on the device: a slot holds less than one hop before a push and gains at most
@@ -209,8 +210,8 @@ class GatedScorer:
     def __init__(self, scorer, gate=None):
         if isinstance(scorer, (_Front, GatedScorer)):
             raise ValueError("the gate goes inside the fronts: PacketScorer(GatedScorer(scorer), ...), not around them")
-        if not isinstance(scorer, SlidingWindowScorer):
-            raise ValueError("GatedScorer wraps a SlidingWindowScorer, IncrementalScorer or KVCachedScorer")
+        if not isinstance(scorer, (SlidingWindowScorer, CascadeScorer)):
+            raise ValueError("GatedScorer wraps a SlidingWindowScorer, IncrementalScorer or KVCachedScorer (or a CascadeScorer around one)")
         gate = SpeechGate() if gate is None else gate
         if not isinstance(gate, SpeechGate):
             raise ValueError("gate: a SpeechGate")

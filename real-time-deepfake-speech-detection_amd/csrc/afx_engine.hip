@@ -2905,6 +2905,18 @@ extern "C" int afx_k_gate(const float* x, int A, int n, const int* hdr, int fram
   KRET(launch_gate(x, A, n, hdr, frame, e_floor, ratio, rise, hang, nf, h, ring, S, ring_len, kept, mask,
                    (hipStream_t)stream));
 }
+extern "C" int afx_k_cascade_store(const float* x, int A, int hop, const int* hdr, float* hist, int S, int window,
+                                   void* stream) {
+  KRET(launch_cascade_store(x, A, hop, hdr, hist, S, window, (hipStream_t)stream));
+}
+extern "C" int afx_k_cascade_select(const float* scores, int stride, const int* hdr, int A, int* wait, int* counts, int S,
+                                    float threshold, int budget, int cooldown, int* sel, void* stream) {
+  KRET(launch_cascade_select(scores, stride, hdr, A, wait, counts, S, threshold, budget, cooldown, sel, (hipStream_t)stream));
+}
+extern "C" int afx_k_cascade_windows(const float* hist, int S, int window, const int* hdr, int A, const int* sel, int budget,
+                                     float* out, void* stream) {
+  KRET(launch_cascade_windows(hist, S, window, hdr, A, sel, budget, out, (hipStream_t)stream));
+}
 extern "C" int afx_k_rownorm(int dtype, const float* x, long ldx, int rows, int C, const float* gamma,
                              const float* beta, float eps, int act, float* out_f, long ldo_f, void* out_h, long ldo_h,
                              void* stream) {

@@ -1246,6 +1246,205 @@ const char* launch_gate(const float* x, int A, int n, const int* hdr, int frame,
 }
 
 // ---------------------------------------------------------------------------------
+// Cascade (afx/cascade.py; the functions are stated in include/afx.h afx_k_cascade_store / _select / _windows): a cheap
+// screen scores every slot at every hop, and the windows of the slots whose score looks suspicious are gathered for a
+// second model.  Three launches per push, every index from a host-built header:
+//   store:   the hop of each named slot into its row of the retained-audio ring hist (S, window), sample t of a session
+//            at column t mod window (the layout of SlidingWindowScorer.ring);
+//   select:  ONE workgroup ranks the candidates (eligible, not cooling down, score < threshold) by (score, slot), writes
+//            the `budget` first row positions to sel and advances every named slot's cooldown counter;
+//   windows: reads sel from device memory and gathers the chosen slots' windows, oldest sample first, tiled while the
+//            session is younger than the window (afx_k_tile_crop's function), into a dense batch.
+// ---------------------------------------------------------------------------------
+constexpr int CASCADE_MAX_ROWS = 8192;     // rows of one select launch: 8-byte keys in 64 KB of LDS (include/afx.h states it)
+constexpr int CASCADE_SELECT_THREADS = 1024;
+constexpr int CASCADE_PER_THREAD = CASCADE_MAX_ROWS / CASCADE_SELECT_THREADS;
+
+__device__ __forceinline__ bool aligned16(const void* p) { return ((unsigned long long)p & 15ull) == 0; }
+
+// hist[slot_i][(wpos_i + k) mod window] = x[i][k], k < hop.  hdr (A, 2): slot, wpos.  Four samples per lane where the row's
+// source and destination are 16-byte aligned and no group of four straddles the wrap (wpos, hop and window multiples of
+// 4); one sample per lane otherwise.
+__global__ __launch_bounds__(256) void cascade_store_kernel(const float* __restrict__ x, const int* __restrict__ hdr,
+                                                            float* __restrict__ hist, int S, int window, int hop) {
+  const int row = blockIdx.y, slot = hdr[2 * row], wpos = hdr[2 * row + 1];
+  if (!(slot >= 0 && slot < S && wpos >= 0 && wpos < window)) return;
+  const float* src = x + (long long)row * hop;
+  float* dst = hist + (long long)slot * window;
+  const int t0 = blockIdx.x * blockDim.x + threadIdx.x, step = gridDim.x * blockDim.x;
+  if (((wpos | hop | window) & 3) == 0 && aligned16(src) && aligned16(dst)) {
+    for (int q = t0; q < hop / 4; q += step) {
+      const int w = wpos + 4 * q;
+      *reinterpret_cast<float4*>(dst + (w < window ? w : w - window)) = *reinterpret_cast<const float4*>(src + 4 * q);
+    }
+    return;
+  }
+  for (int k = t0; k < hop; k += step) {
+    const int w = wpos + k;  // hop <= window: one wrap
+    dst[w < window ? w : w - window] = src[k];
+  }
+}
+
+const char* launch_cascade_store(const float* x, int A, int hop, const int* hdr, float* hist, int S, int window,
+                                 hipStream_t s) {
+  if (!x || !hdr || !hist) return "cascade_store: null argument";
+  if (A <= 0 || A > 65535) return "cascade_store: 1 to 65535 rows";
+  if (S <= 0 || window <= 0 || hop <= 0 || hop > window) return "cascade_store: a hop must be positive and fit the window";
+  hipLaunchKernelGGL(cascade_store_kernel, dim3(min((hop + 1023) / 1024, 64), A), dim3(256), 0, s, x, hdr, hist, S, window, hop);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+// (score, slot) -> a 64-bit key whose unsigned order is before(): scores ascending with -0.0 and +0.0 equal, then the lower
+// slot.  Never called for a NaN (a NaN is no candidate).  The slots of a launch are distinct, so the keys are too.
+__device__ __forceinline__ unsigned long long cascade_key(float score, int slot) {
+  unsigned int u = __float_as_uint(score);
+  if (u == 0x80000000u) u = 0u;                              // -0.0 ties with +0.0
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);            // monotone: -inf lowest, +inf highest
+  return ((unsigned long long)u << 32) | (unsigned int)slot;
+}
+
+// One workgroup of 16 waves; thread t owns rows t, t + 1024, ... (at most CASCADE_PER_THREAD) and keeps their keys in
+// registers.  Candidates are compacted into LDS (wave ballot + popcount prefix, wave bases from a 16-entry table that the
+// keys then overwrite), then each owner counts the keys below its own: that count is the rank, all keys being distinct.
+__global__ __launch_bounds__(CASCADE_SELECT_THREADS) void cascade_select_kernel(const float* __restrict__ scores, int stride,
+                                                                                const int* __restrict__ hdr, int A,
+                                                                                int* __restrict__ wait, int* __restrict__ counts,
+                                                                                int S, float threshold, int budget, int cooldown,
+                                                                                int* __restrict__ sel) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char cascade_lds[];
+  unsigned long long* keys = reinterpret_cast<unsigned long long*>(cascade_lds);
+  int* wave_total = reinterpret_cast<int*>(cascade_lds);
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  unsigned long long key[CASCADE_PER_THREAD];
+  int w_old[CASCADE_PER_THREAD];
+  unsigned int named = 0, cand = 0;  // bit k: row tid + 1024 k has a slot inside the state / is a candidate
+  int mine = 0;                      // candidates of this wave
+#pragma unroll
+  for (int k = 0; k < CASCADE_PER_THREAD; ++k) {
+    const int i = tid + k * CASCADE_SELECT_THREADS;
+    bool c = false;
+    key[k] = 0ull;
+    w_old[k] = 0;
+    if (i < A) {
+      const int slot = hdr[2 * i];
+      if (slot >= 0 && slot < S) {
+        named |= 1u << k;
+        const float sc = scores[(long long)i * stride];
+        w_old[k] = wait[slot];
+        c = hdr[2 * i + 1] != 0 && w_old[k] == 0 && sc < threshold;  // (false for a NaN score)
+        if (c) {
+          cand |= 1u << k;
+          key[k] = cascade_key(sc, slot);
+        }
+      }
+    }
+    mine += __popcll(__ballot(c));
+  }
+  if (lane == 0) wave_total[wave] = mine;
+  __syncthreads();
+  int base = 0, total = 0;
+#pragma unroll
+  for (int w = 0; w < CASCADE_SELECT_THREADS / 64; ++w) {
+    const int t = wave_total[w];
+    base += w < wave ? t : 0;
+    total += t;
+  }
+  __syncthreads();  // every wave has read the table: the keys may take its place
+#pragma unroll
+  for (int k = 0; k < CASCADE_PER_THREAD; ++k) {
+    const bool c = (cand >> k) & 1u;
+    const unsigned long long b = __ballot(c);
+    if (c) keys[base + __popcll(b & below)] = key[k];
+    base += __popcll(b);
+  }
+  __syncthreads();
+  if (tid == 0) sel[0] = min(total, budget);
+  int rank[CASCADE_PER_THREAD];
+#pragma unroll
+  for (int k = 0; k < CASCADE_PER_THREAD; ++k) rank[k] = 0;
+  if (cand) {
+    for (int c = 0; c < total; ++c) {
+      const unsigned long long o = keys[c];  // one address for the whole wave: a broadcast read
+#pragma unroll
+      for (int k = 0; k < CASCADE_PER_THREAD; ++k) rank[k] += o < key[k] ? 1 : 0;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < CASCADE_PER_THREAD; ++k) {
+    if (!((named >> k) & 1u)) continue;
+    const int i = tid + k * CASCADE_SELECT_THREADS;
+    const bool chosen = ((cand >> k) & 1u) && rank[k] < budget;
+    const int slot = hdr[2 * i];
+    if (chosen) sel[1 + rank[k]] = i;
+    wait[slot] = chosen ? cooldown : max(w_old[k] - 1, 0);
+    if (counts && ((cand >> k) & 1u)) {  // (the slot is this thread's alone: plain adds)
+      counts[2 * slot] += 1;
+      counts[2 * slot + 1] += chosen ? 0 : 1;
+    }
+  }
+}
+
+const char* launch_cascade_select(const float* scores, int stride, const int* hdr, int A, int* wait, int* counts, int S,
+                                  float threshold, int budget, int cooldown, int* sel, hipStream_t s) {
+  if (!scores || !hdr || !wait || !sel) return "cascade_select: null argument";
+  if (stride < 1) return "cascade_select: a score stride of at least 1";
+  if (A <= 0 || A > CASCADE_MAX_ROWS) return "cascade_select: 1 to 8192 rows";
+  if (S <= 0) return "cascade_select: no slots";
+  if (threshold != threshold) return "cascade_select: the threshold is NaN";
+  if (budget < 1 || cooldown < 0) return "cascade_select: budget >= 1 and cooldown >= 0";
+  const size_t lds = (size_t)max(A, 16) * sizeof(unsigned long long);
+  hipLaunchKernelGGL(cascade_select_kernel, dim3(1), dim3(CASCADE_SELECT_THREADS), lds, s, scores, stride, hdr, A, wait, counts,
+                     S, threshold, budget, cooldown, sel);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+// out[r][j] = hist[slot_i][(start_i + j) mod n_i], j < window, for r < sel[0] and i = sel[1 + r].  hdr (A, 3): slot, n,
+// start.  A steady row (n = window) copies four samples per lane where start and window are multiples of 4 and both rows
+// 16-byte aligned; a warm row (n < window, the history tiled) and every other steady row take one sample per lane.
+__global__ __launch_bounds__(256) void cascade_windows_kernel(const float* __restrict__ hist, int S, int window,
+                                                              const int* __restrict__ hdr, int A, const int* __restrict__ sel,
+                                                              int budget, float* __restrict__ out) {
+  const int r = blockIdx.y;
+  if (r >= min(sel[0], budget)) return;
+  const int i = sel[1 + r];
+  if (i < 0 || i >= A) return;
+  const int slot = hdr[3 * i], n = hdr[3 * i + 1], start = hdr[3 * i + 2];
+  if (!(slot >= 0 && slot < S && n >= 1 && n <= window && start >= 0 && start < n)) return;
+  const float* src = hist + (long long)slot * window;
+  float* dst = out + (long long)r * window;
+  const int t0 = blockIdx.x * blockDim.x + threadIdx.x, step = gridDim.x * blockDim.x;
+  if (n == window) {
+    if (((start | window) & 3) == 0 && aligned16(src) && aligned16(dst)) {
+      for (int q = t0; q < window / 4; q += step) {
+        const int c = start + 4 * q;
+        *reinterpret_cast<float4*>(dst + 4 * q) = *reinterpret_cast<const float4*>(src + (c < window ? c : c - window));
+      }
+      return;
+    }
+    for (int j = t0; j < window; j += step) {
+      const int c = start + j;
+      dst[j] = src[c < window ? c : c - window];
+    }
+    return;
+  }
+  for (int j = t0; j < window; j += step) dst[j] = src[(int)(((long long)start + j) % n)];
+}
+
+const char* launch_cascade_windows(const float* hist, int S, int window, const int* hdr, int A, const int* sel, int budget,
+                                   float* out, hipStream_t s) {
+  if (!hist || !hdr || !sel || !out) return "cascade_windows: null argument";
+  if (S <= 0 || window <= 0 || A <= 0) return "cascade_windows: no slots, no window or no rows";
+  if (budget < 1 || budget > 65535) return "cascade_windows: a budget of 1 to 65535 rows";
+  hipLaunchKernelGGL(cascade_windows_kernel, dim3(min((window + 1023) / 1024, 64), budget), dim3(256), 0, s, hist, S, window,
+                     hdr, A, sel, budget, out);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+// ---------------------------------------------------------------------------------
 // Row LayerNorm (+ activation): one wave per row, C <= 1024, C % 4 == 0.  The row
 // stays in registers (float4 per lane per 256-column slab), two-pass statistics in
 // fp32 like torch.  Used for the conv-stack LayerNorm+GELU, every transformer /

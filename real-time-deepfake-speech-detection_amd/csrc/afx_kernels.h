@@ -158,6 +158,15 @@ const char* launch_jitter_release(const float* jring, int S, int J, const int* h
 // mask (optional) the keep flag of every frame
 const char* launch_gate(const float* x, int A, int n, const int* hdr, int frame, float e_floor, float ratio, float rise, int hang,
                         float* nf, int* h, float* ring, int S, int ring_len, int* kept, unsigned char* mask, hipStream_t s);
+// cascade (include/afx.h afx_k_cascade_store / _select / _windows): the named slots' hops into the retained-audio ring; the
+// candidates among the rows ranked by (score, slot), the first `budget` row positions into sel, the cooldown counters
+// advanced; the windows of the rows sel names gathered from the ring (sel is read on the device)
+const char* launch_cascade_store(const float* x, int A, int hop, const int* hdr, float* hist, int S, int window,
+                                 hipStream_t s);
+const char* launch_cascade_select(const float* scores, int stride, const int* hdr, int A, int* wait, int* counts, int S,
+                                  float threshold, int budget, int cooldown, int* sel, hipStream_t s);
+const char* launch_cascade_windows(const float* hist, int S, int window, const int* hdr, int A, const int* sel, int budget,
+                                   float* out, hipStream_t s);
 void conv0_set_mfma(int v);  // A/B knob: 1 (default) = matrix-core forms (split-precision fp16 when packed), 2 = fp32 MFMA form, 0 = VALU form
 // y[t] = x[t] - coef * x[t-1] with a reflect pad on the left; (B,L) fp32 -> (B,L) fp32
 const char* launch_pre_emphasis(const float* x, int B, int L, float coef, float* y, hipStream_t s);
