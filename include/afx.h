@@ -395,6 +395,45 @@ int afx_k_cascade_select(const float* scores, int stride, const int* hdr, int A,
                          float threshold, int budget, int cooldown, int* sel, void* stream);
 int afx_k_cascade_windows(const float* hist, int S, int window, const int* hdr, int A, const int* sel, int budget,
                           float* out, void* stream);
+/* Verdicts (afx/verdict.py): the per-stream decision over the scores of the streaming scorers -- exponential smoothing, a
+ * two-threshold hysteresis with confirm / release run lengths, and a device log of the raise / clear events.
+ * Policy, all fp32 / int32: alpha in (0, 1]; enter <= exit_ and verifier_enter, none NaN; confirm, release, min_scores >= 1;
+ * latch 0 / 1.  State per slot: m (S,) fp32, the smoothed score, NaN for a new stream; st (S, 4) int32 = (n, run, on, since),
+ * (0, 0, 0, -1) for a new stream: n the scores taken (saturating at 2^31 - 1), run the current run length, on 0 clear / 1
+ * alarm, since the hop index at which the current alarm was raised, -1 while clear.
+ * An update names rows i = 0..A-1: slot b_i = hdr[i][0] (distinct), hop index k_i = hdr[i][1] (hdr: device, A x 2 int32),
+ * score s_i = scores[i * stride] (fp32 bonafide score, low = spoof; stride >= 1: a column of a logits matrix is read in
+ * place) and v_i = vscores[i] (the verifier's score of the slot in this push, NaN if none; vscores NULL: every v_i is NaN).
+ * All compares are fp32, every arithmetic operation is a single correctly rounded fp32 operation (no fma):
+ *     if (isnan(s_i)) the row changes nothing and logs nothing           (a gate's "no hop completed")
+ *     n1 = n == 2^31-1 ? n : n + 1
+ *     m1 = n == 0 ? s_i : m + alpha * (s_i - m)                          (sub, mul, add: three roundings)
+ *     kind = 0
+ *     if (on == 0) {
+ *         if (!isnan(v_i) && v_i < verifier_enter) on, run, since, kind = 1, 0, k_i, 2    (raised by the verifier)
+ *         else if (!isnan(v_i))                    run = 0       (the verifier cleared this window: the run starts over)
+ *         else if (n1 >= min_scores && m1 < enter) { run += 1; if (run >= confirm) on, run, since, kind = 1, 0, k_i, 1 }
+ *         else                                     run = 0
+ *     } else if (!latch) {
+ *         if (m1 >= exit_) { run += 1; if (run >= release) on, run, since, kind = 0, 0, -1, 3 }
+ *         else             run = 0
+ *     }
+ *     m = m1; n = n1
+ * Infinite scores follow IEEE; a NaN m1 is neither < enter nor >= exit_.  While an alarm is on the verifier plays no part:
+ * its veto acts before the alarm, by restarting the confirm run.
+ * The log, int32 (1 + 4 cap): a row with kind != 0 appends the event (b_i, kind, k_i, bits of m1); the events of one launch
+ * in ascending row position, launches in stream order.  log[0] is the number of events since the log was last cleared
+ * (the caller zeroes it), event e sits at log[1 + 4e ..]; events at or past cap are not stored but still counted in log[0],
+ * and the state always advances.
+ * afx_k_verdict: 1 <= A <= 8192, ONE workgroup of 1024 threads takes the rows in chunks of 1024 in row order (event slots
+ * from a wave ballot + popcount prefix, wave totals prefixed through LDS onto a running base that starts at log[0]: no
+ * atomics, no second launch).  A row whose slot is outside [0, S) is skipped whole (no state change, no event); the state
+ * rows of slots not named are untouched.  A NULL scores / hdr / m / st / log, stride < 1, A outside 1..8192, S < 1, alpha
+ * outside (0, 1], a NaN threshold, exit_ < enter, confirm / release / min_scores < 1, latch outside {0, 1} or cap < 0:
+ * non-zero, afx_last_error names `verdict`, nothing launched. */
+int afx_k_verdict(const float* scores, int stride, const float* vscores, const int* hdr, int A, float* m, int* st, int S,
+                  float alpha, float enter, float exit_, float verifier_enter, int confirm, int release, int min_scores,
+                  int latch, int* log, int cap, void* stream);
 int afx_k_rownorm(int dtype, const float* x, long ldx, int rows, int C, const float* gamma, const float* beta,
                   float eps, int act, float* out_f, long ldo_f, void* out_h, long ldo_h, void* stream);
 int afx_k_mhsa(int dtype, const void* qkv, void* out, int B, int T, int H, void* stream);

@@ -174,6 +174,7 @@ class CascadeScorer:
         self._batch = torch.empty(B, screen.window, dtype=torch.float32, device=dev)
         self._sel_host = None  # (pinned, on the first push: a scorer on the host can be built and moved, not pushed)
         self._events = []
+        self._last = None  # (slots, verifier scores) of the newest push, None when it verified nothing
 
     # ---- the surface the fronts and the gate use -------------------------------------------------------------------------
     @property
@@ -216,6 +217,7 @@ class CascadeScorer:
         if (not isinstance(chunk, torch.Tensor) or not chunk.is_cuda or chunk.device != dev or chunk.dtype != torch.float32
                 or chunk.shape != (A, hop)):
             raise ValueError(f"expected a CUDA fp32 tensor of shape {(A, hop)} on {dev} (one hop per named slot)")
+        self._last = None
         scores = scr.push(chunk, None if slots is None else idx)
         if not A:
             return scores
@@ -262,7 +264,14 @@ class CascadeScorer:
                 self.verified_at[chosen] = at
                 self._verifications[slot[rows]] += 1
                 self._events.append((chosen, at, s32.index_select(0, self._sel[1:1 + k].long()), v))
+                self._last = (chosen, v)
         return scores
+
+    def last_verified(self):
+        """What the newest ``push`` verified: ``(slots (n,) int64 host, verifier_scores (n,) fp32 device)`` in rank order,
+        or None when it verified nothing.  The event log is not touched: a layer above reads this and leaves
+        ``take_events()`` to the caller."""
+        return self._last
 
     def take_events(self):
         """One entry per push since the last call that verified something: ``(slots (n,) int64 host, at (n,) int64 host,

@@ -74,6 +74,21 @@ class Timeline:
             i = j + 1
         return out
 
+    def alarms(self, policy):
+        """The alarms a ``VerdictPolicy`` raises over this timeline (``policy.run_reference`` over ``scores``: what a one-slot
+        ``afx.verdict.VerdictScorer`` logs when pushed the recording hop by hop): a list of ``(raised_s, cleared_s or None,
+        kind)`` -- the ends, in seconds, of the windows at which the alarm was raised and cleared (None: still on at the
+        end), and the raise's kind (1: by the smoothed score)."""
+        events, _ = policy.run_reference(self.scores.numpy(), hop_index=range(len(self)))
+        ends = (self.ends / self.sample_rate).tolist()
+        out = []
+        for _slot, kind, j, _bits in events:
+            if kind == 3:
+                out[-1] = (out[-1][0], ends[j], out[-1][2])
+            else:
+                out.append((ends[j], None, kind))
+        return out
+
     def summary(self, threshold):
         """min, mean and the fraction of windows scoring below ``threshold`` (flagged as spoof)."""
         n = len(self)

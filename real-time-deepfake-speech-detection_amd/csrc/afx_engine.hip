@@ -2917,6 +2917,12 @@ extern "C" int afx_k_cascade_windows(const float* hist, int S, int window, const
                                      float* out, void* stream) {
   KRET(launch_cascade_windows(hist, S, window, hdr, A, sel, budget, out, (hipStream_t)stream));
 }
+extern "C" int afx_k_verdict(const float* scores, int stride, const float* vscores, const int* hdr, int A, float* m, int* st,
+                             int S, float alpha, float enter, float exit_, float verifier_enter, int confirm, int release,
+                             int min_scores, int latch, int* log, int cap, void* stream) {
+  KRET(launch_verdict(scores, stride, vscores, hdr, A, m, st, S, alpha, enter, exit_, verifier_enter, confirm, release, min_scores,
+                      latch, log, cap, (hipStream_t)stream));
+}
 extern "C" int afx_k_rownorm(int dtype, const float* x, long ldx, int rows, int C, const float* gamma,
                              const float* beta, float eps, int act, float* out_f, long ldo_f, void* out_h, long ldo_h,
                              void* stream) {

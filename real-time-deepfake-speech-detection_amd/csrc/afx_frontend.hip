@@ -1445,6 +1445,118 @@ const char* launch_cascade_windows(const float* hist, int S, int window, const i
 }
 
 // ---------------------------------------------------------------------------------
+// Verdicts (afx/verdict.py; the function is stated in include/afx.h afx_k_verdict): per-slot smoothing, hysteresis and an
+// event log over the scores of one push.  ONE workgroup of 16 waves takes the rows in chunks of 1024, in row order; thread t
+// of a chunk runs its row's state machine (the slots of a launch are distinct: the state row is the thread's alone).  The
+// events of a chunk get their log positions from a wave ballot + popcount prefix, the 16 wave totals are prefixed through
+// LDS onto a running base that starts at log[0]: ascending row position within a launch, launches in stream order, no
+// atomics.  Events at or past cap are counted, not stored.
+// ---------------------------------------------------------------------------------
+constexpr int VERDICT_MAX_ROWS = 8192;
+constexpr int VERDICT_THREADS = 1024;
+constexpr int VERDICT_N_MAX = 0x7fffffff;
+
+__global__ __launch_bounds__(VERDICT_THREADS) void verdict_kernel(const float* __restrict__ scores, int stride,
+                                                                  const float* __restrict__ vscores, const int* __restrict__ hdr,
+                                                                  int A, float* __restrict__ m, int* __restrict__ st, int S,
+                                                                  float alpha, float enter, float exit_, float verifier_enter,
+                                                                  int confirm, int release, int min_scores, int latch,
+                                                                  int* __restrict__ log, int cap) {
+  __shared__ int wave_total[VERDICT_THREADS / 64];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  long long base = log[0];  // (every thread reads it before the first barrier; thread 0 stores the new count after the last)
+  for (int row0 = 0; row0 < A; row0 += VERDICT_THREADS) {
+    const int i = row0 + tid;
+    int kind = 0, slot = -1, k = 0;
+    float m1 = 0.f;
+    if (i < A) {
+      slot = hdr[2 * i];
+      k = hdr[2 * i + 1];
+      const float s = scores[(long long)i * stride];
+      if (slot >= 0 && slot < S && !(s != s)) {  // a NaN score: "no hop completed", the row changes nothing
+#pragma clang fp contract(off)
+        const float v = vscores ? vscores[i] : __builtin_nanf("");
+        const bool has_v = !(v != v);
+        int* q = st + 4ll * slot;
+        const int n = q[0];
+        int run = q[1], on = q[2], since = q[3];
+        const int n1 = n == VERDICT_N_MAX ? n : n + 1;
+        if (n == 0) {
+          m1 = s;
+        } else {
+          const float mo = m[slot];
+          const float d = s - mo;
+          const float p = alpha * d;
+          m1 = mo + p;
+        }
+        if (on == 0) {
+          if (has_v && v < verifier_enter) {
+            on = 1, run = 0, since = k, kind = 2;
+          } else if (has_v) {
+            run = 0;
+          } else if (n1 >= min_scores && m1 < enter) {
+            run += 1;
+            if (run >= confirm) on = 1, run = 0, since = k, kind = 1;
+          } else {
+            run = 0;
+          }
+        } else if (!latch) {
+          if (m1 >= exit_) {
+            run += 1;
+            if (run >= release) on = 0, run = 0, since = -1, kind = 3;
+          } else {
+            run = 0;
+          }
+        }
+        m[slot] = m1;
+        q[0] = n1, q[1] = run, q[2] = on, q[3] = since;
+      }
+    }
+    const unsigned long long b = __ballot(kind != 0);
+    if (lane == 0) wave_total[wave] = __popcll(b);
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < VERDICT_THREADS / 64; ++w) {
+      const int t = wave_total[w];
+      before += w < wave ? t : 0;
+      total += t;
+    }
+    if (kind != 0) {
+      const long long e = base + before + __popcll(b & below);
+      if (e >= 0 && e < cap) {
+        int* dst = log + 1 + 4 * e;
+        dst[0] = slot, dst[1] = kind, dst[2] = k, dst[3] = __float_as_int(m1);
+      }
+    }
+    base += total;
+    __syncthreads();  // every wave has read the table: the next chunk may overwrite it
+  }
+  if (tid == 0) log[0] = (int)min(base, (long long)VERDICT_N_MAX);
+}
+
+const char* launch_verdict(const float* scores, int stride, const float* vscores, const int* hdr, int A, float* m, int* st,
+                           int S, float alpha, float enter, float exit_, float verifier_enter, int confirm, int release,
+                           int min_scores, int latch, int* log, int cap, hipStream_t s) {
+  if (!scores || !hdr || !m || !st || !log) return "verdict: null argument";
+  if (stride < 1) return "verdict: a score stride of at least 1";
+  if (A <= 0 || A > VERDICT_MAX_ROWS) return "verdict: 1 to 8192 rows";
+  if (S <= 0) return "verdict: no slots";
+  if (!(alpha > 0.f && alpha <= 1.f)) return "verdict: alpha in (0, 1]";
+  if (enter != enter || exit_ != exit_) return "verdict: a threshold is NaN";
+  if (verifier_enter != verifier_enter) return "verdict: the verifier threshold is NaN";
+  if (exit_ < enter) return "verdict: exit below enter";
+  if (confirm < 1 || release < 1 || min_scores < 1) return "verdict: confirm, release and min_scores of at least 1";
+  if (latch != 0 && latch != 1) return "verdict: latch is 0 or 1";
+  if (cap < 0) return "verdict: a negative log capacity";
+  hipLaunchKernelGGL(verdict_kernel, dim3(1), dim3(VERDICT_THREADS), 0, s, scores, stride, vscores, hdr, A, m, st, S, alpha, enter,
+                     exit_, verifier_enter, confirm, release, min_scores, latch, log, cap);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+// ---------------------------------------------------------------------------------
 // Row LayerNorm (+ activation): one wave per row, C <= 1024, C % 4 == 0.  The row
 // stays in registers (float4 per lane per 256-column slab), two-pass statistics in
 // fp32 like torch.  Used for the conv-stack LayerNorm+GELU, every transformer /

@@ -167,6 +167,11 @@ const char* launch_cascade_select(const float* scores, int stride, const int* hd
                                   float threshold, int budget, int cooldown, int* sel, hipStream_t s);
 const char* launch_cascade_windows(const float* hist, int S, int window, const int* hdr, int A, const int* sel, int budget,
                                    float* out, hipStream_t s);
+// verdicts (include/afx.h afx_k_verdict): the scores of one push smoothed per slot, the hysteresis state machine advanced, the
+// raise / clear events appended to the device log in row order; one workgroup, no atomics
+const char* launch_verdict(const float* scores, int stride, const float* vscores, const int* hdr, int A, float* m, int* st,
+                           int S, float alpha, float enter, float exit_, float verifier_enter, int confirm, int release,
+                           int min_scores, int latch, int* log, int cap, hipStream_t s);
 void conv0_set_mfma(int v);  // A/B knob: 1 (default) = matrix-core forms (split-precision fp16 when packed), 2 = fp32 MFMA form, 0 = VALU form
 // y[t] = x[t] - coef * x[t-1] with a reflect pad on the left; (B,L) fp32 -> (B,L) fp32
 const char* launch_pre_emphasis(const float* x, int B, int L, float coef, float* y, hipStream_t s);
