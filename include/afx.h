@@ -434,6 +434,54 @@ int afx_k_cascade_windows(const float* hist, int S, int window, const int* hdr, 
 int afx_k_verdict(const float* scores, int stride, const float* vscores, const int* hdr, int A, float* m, int* st, int S,
                   float alpha, float enter, float exit_, float verifier_enter, int confirm, int release, int min_scores,
                   int latch, int* log, int cap, void* stream);
+/* Evidence clips (afx/evidence.py): the audio and the scores around each alarm, kept on the device.  Policy: pre >= 0 hops
+ * kept before the raising hop, post >= 0 hops after it, `clips` pool entries, encoding 0 = fp32 (bit for bit) / 1 = pcm16.
+ * P = pre + 1, a clip holds L = P + post hops.
+ * State per slot: hist (S, P hop) fp32, the audio ring; sring (S, P) fp32, the score ring; rec (S,) int32, the pool entry
+ * being recorded or -1; left (S,) int32, post-roll hops still to append.  Pool: pool (clips, 6) int32 headers = (status,
+ * slot, raised_at, first_hop, hops, seq), status 0 FREE / 1 RECORDING / 2 COMPLETE / 3 TRUNCATED (3 is set by the host's
+ * reset alone); audio (clips, L hop) fp32 or int16; cscores (clips, L) fp32; counters (4,) int32 = raised, recorded,
+ * dropped, merged.  Entries become FREE only between updates (the host's take_clips).
+ * An update names rows i = 0..A-1: slot b_i = hdr[i][0] (distinct), the 1-based hop number k_i = hdr[i][1] (the host's
+ * samples_seen / hop after this hop), the hop x[i][0..hop), the score s_i = scores[i * stride] (NaN if this push produced
+ * none; scores NULL: every s_i is NaN) and the verdict state row vst[b_i] = (n, run, on, since), read after this push's
+ * verdict update.  The update behaves as if the rows were processed in ascending row position:
+ *     store:  hist[b][((k-1) mod P) hop + j] = x[i][j], j < hop;  sring[b][(k-1) mod P] = s_i
+ *     raise = on == 1 && since == k                                       (raised by this very push)
+ *     if (rec[b] >= 0) {                                                  (recording)
+ *         merged += raise
+ *         e = rec[b]; the hop, encoded, and s_i go to position hops_e of clip e; hops_e += 1; left[b] -= 1
+ *         if (left[b] == 0) status_e = COMPLETE, rec[b] = -1
+ *     } else if (raise) {
+ *         raised += 1
+ *         e = the FREE entry of lowest index not yet taken by an earlier row of this update; none: dropped += 1, and that is all
+ *         f = max(1, k - pre); header_e = (post == 0 ? COMPLETE : RECORDING, b, k, f, k - f + 1, recorded); recorded += 1
+ *         hops f..k (hop h from ring position (h-1) mod P, which already holds hop k), encoded, and their scores go to
+ *         positions 0..k-f of clip e;  if (post > 0) rec[b] = e, left[b] = post
+ *     }
+ * The free set is fixed during an update, so the entry of a raising row is the (number of raising, not recording rows before
+ * it)-th FREE entry in ascending index, whatever the launch geometry.  f >= 1: a ring is never read further back than the
+ * session's first hop.  pcm16 of a sample x: q = x * 32768 (one fp32 multiply), NaN -> 0, q clamped to [-32768, 32767] and
+ * rounded half to even, stored as int16.
+ * A row with a slot outside [0, S) or k < 1 is skipped whole (nothing stored, no state change); of the rows naming one slot
+ * the one at the lowest row position is taken and the others are skipped whole.
+ * afx_k_evidence_mark: 1 <= A <= 8192, 1 <= clips <= 8192, ONE workgroup of 1024 threads: the FREE entries are listed in
+ * LDS (ballot + popcount prefix), the rows are taken in chunks of 1024 in row order (rank of a raising row from a wave ballot
+ * + popcount prefix, wave totals through LDS onto a running base).  Updates rec, left, the headers and the counters, and
+ * writes work (A, 4) int32 = (op, entry, a, b): op -1 the row is skipped, 0 store only, 1 append at position a of `entry`,
+ * 2 open `entry` with first hop a and b hops.  claim: (S,) int32 scratch, every word 2^31 - 1 before the first launch (the
+ * kernel leaves it so): rows naming one slot settle their owner through an atomic min.
+ * afx_k_evidence_copy: a grid over rows x hop tiles carries the work items out on the rings, the clips' audio and scores;
+ * 128-bit accesses where hop % 4 == 0 and the rows are 16-byte aligned, one sample per lane otherwise.  A work item whose
+ * entry, position or hops leave the pool (or do not end at k) is skipped whole.
+ * A NULL pointer (scores excepted), A outside 1..8192, S < 1, hop < 1, pre < 0, post < 0, a ring or a clip of 2^31 samples
+ * or more, clips outside 1..8192, stride < 1 with scores, encoding outside {0, 1}: non-zero, afx_last_error names
+ * `evidence_mark` / `evidence_copy`, nothing launched. */
+int afx_k_evidence_mark(const int* hdr, int A, const int* vst, int S, int pre, int post, int* rec, int* left, int* claim,
+                        int* pool, int clips, int* counters, int* work, void* stream);
+int afx_k_evidence_copy(const float* x, const float* scores, int stride, const int* hdr, const int* work, int A, int hop,
+                        int pre, int post, float* hist, float* sring, int S, void* audio, float* cscores, int clips,
+                        int encoding, void* stream);
 int afx_k_rownorm(int dtype, const float* x, long ldx, int rows, int C, const float* gamma, const float* beta,
                   float eps, int act, float* out_f, long ldo_f, void* out_h, long ldo_h, void* stream);
 int afx_k_mhsa(int dtype, const void* qkv, void* out, int B, int T, int H, void* stream);

@@ -101,6 +101,8 @@ SIGNATURES = {
     "afx_k_cascade_select": (_I, [_P, _I, _P, _I, _P, _P, _I, _F, _I, _I, _P, _P]),
     "afx_k_cascade_windows": (_I, [_P, _I, _I, _P, _I, _P, _I, _P, _P]),
     "afx_k_verdict": (_I, [_P, _I, _P, _P, _I, _P, _P, _I, _F, _F, _F, _F, _I, _I, _I, _I, _P, _I, _P]),
+    "afx_k_evidence_mark": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P]),
+    "afx_k_evidence_copy": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _P]),
     "afx_k_rownorm": (_I, [_I, _P, _L, _I, _I, _P, _P, _F, _I, _P, _L, _P, _L, _P]),
     "afx_k_mhsa": (_I, [_I, _P, _P, _I, _I, _I, _P]),
     "afx_k_conf_attn": (_I, [_I, _P, _L, _P, _L, _P, _I, _I, _I, _I, _I, _P, _L, _P]),

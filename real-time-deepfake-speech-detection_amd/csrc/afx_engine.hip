@@ -2923,6 +2923,16 @@ extern "C" int afx_k_verdict(const float* scores, int stride, const float* vscor
   KRET(launch_verdict(scores, stride, vscores, hdr, A, m, st, S, alpha, enter, exit_, verifier_enter, confirm, release, min_scores,
                       latch, log, cap, (hipStream_t)stream));
 }
+extern "C" int afx_k_evidence_mark(const int* hdr, int A, const int* vst, int S, int pre, int post, int* rec, int* left, int* claim,
+                                   int* pool, int clips, int* counters, int* work, void* stream) {
+  KRET(launch_evidence_mark(hdr, A, vst, S, pre, post, rec, left, claim, pool, clips, counters, work, (hipStream_t)stream));
+}
+extern "C" int afx_k_evidence_copy(const float* x, const float* scores, int stride, const int* hdr, const int* work, int A, int hop,
+                                   int pre, int post, float* hist, float* sring, int S, void* audio, float* cscores, int clips,
+                                   int encoding, void* stream) {
+  KRET(launch_evidence_copy(x, scores, stride, hdr, work, A, hop, pre, post, hist, sring, S, audio, cscores, clips, encoding,
+                            (hipStream_t)stream));
+}
 extern "C" int afx_k_rownorm(int dtype, const float* x, long ldx, int rows, int C, const float* gamma,
                              const float* beta, float eps, int act, float* out_f, long ldo_f, void* out_h, long ldo_h,
                              void* stream) {

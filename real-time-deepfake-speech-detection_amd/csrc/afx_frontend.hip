@@ -1557,6 +1557,252 @@ const char* launch_verdict(const float* scores, int stride, const float* vscores
 }
 
 // ---------------------------------------------------------------------------------
+// Evidence clips (afx/evidence.py; the function is stated in include/afx.h afx_k_evidence_mark / _copy): a pre-roll ring of
+// audio and scores per slot, and a pool of clips that an alarm raised by this push fills with the pre-roll, the raising hop
+// and a post-roll.  Two launches per update, every index from a host-built header and the verdict state on the device:
+//   mark:  ONE workgroup of 16 waves.  It lists the free pool entries in ascending index (ballot + popcount prefix into
+//          LDS), settles which row owns a slot named twice (the lowest row position, through an atomic min on a scratch
+//          word per slot), then takes the rows in chunks of 1024 in row order: a recording slot appends, a raising slot
+//          takes the free entry of its rank among the raising rows.  It updates rec, left, the clip headers and the four
+//          counters and leaves one work item per row;
+//   copy:  a grid over rows x hop tiles carries the work items out: the hop into the ring, into its clip, and for an
+//          opened clip the pre-roll out of the ring, fp32 bit for bit or as pcm16.
+// ---------------------------------------------------------------------------------
+constexpr int EVIDENCE_MAX_ROWS = 8192;
+constexpr int EVIDENCE_MAX_CLIPS = 8192;  // the free list: 32 KB of LDS (include/afx.h states it)
+constexpr int EVIDENCE_THREADS = 1024;
+constexpr int EVIDENCE_FREE = 0, EVIDENCE_RECORDING = 1, EVIDENCE_COMPLETE = 2;
+constexpr int EVIDENCE_UNCLAIMED = 0x7fffffff;
+
+__global__ __launch_bounds__(EVIDENCE_THREADS) void evidence_mark_kernel(const int* __restrict__ hdr, int A,
+                                                                         const int* __restrict__ vst, int S, int pre, int post,
+                                                                         int* __restrict__ rec, int* __restrict__ left, int* claim,
+                                                                         int* __restrict__ pool, int clips,
+                                                                         int* __restrict__ counters, int* __restrict__ work) {
+  __shared__ int s_free[EVIDENCE_MAX_CLIPS];
+  __shared__ int wave_total[EVIDENCE_THREADS / 64];
+  __shared__ int s_merged;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  const int recorded0 = counters[1];  // (every thread reads it before the first barrier; thread 0 stores after the last)
+  const int L = pre + 1 + post;
+  if (tid == 0) s_merged = 0;
+  // the free entries in ascending index
+  int nfree = 0;
+  for (int e0 = 0; e0 < clips; e0 += EVIDENCE_THREADS) {
+    const int e = e0 + tid;
+    const bool fr = e < clips && pool[6 * e] == EVIDENCE_FREE;
+    const unsigned long long b = __ballot(fr);
+    if (lane == 0) wave_total[wave] = __popcll(b);
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < EVIDENCE_THREADS / 64; ++w) {
+      const int t = wave_total[w];
+      before += w < wave ? t : 0;
+      total += t;
+    }
+    if (fr) s_free[nfree + before + __popcll(b & below)] = e;
+    nfree += total;
+    __syncthreads();
+  }
+  // a slot named twice belongs to the lowest row position that names it
+  for (int i = tid; i < A; i += EVIDENCE_THREADS) {
+    const int slot = hdr[2 * i], k = hdr[2 * i + 1];
+    if (slot >= 0 && slot < S && k >= 1) atomicMin(&claim[slot], i);
+  }
+  __threadfence();  // the claims have reached memory before any wave reads one
+  __syncthreads();
+  int base = 0;  // raising rows before this chunk
+  for (int row0 = 0; row0 < A; row0 += EVIDENCE_THREADS) {
+    const int i = row0 + tid;
+    int op = -1, entry = 0, wa = 0, wb = 0, slot = -1, k = 0;
+    bool opens = false, merges = false;
+    if (i < A) {
+      slot = hdr[2 * i];
+      k = hdr[2 * i + 1];
+      if (slot >= 0 && slot < S && k >= 1 && __hip_atomic_load(&claim[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == i) {
+        const bool raise = vst[4ll * slot + 2] == 1 && vst[4ll * slot + 3] == k;
+        const int r = rec[slot];
+        op = 0;
+        if (r >= 0 && r < clips && pool[6 * r + 4] < L) {  // recording: the hop is appended
+          int* h = pool + 6 * r;
+          merges = raise;
+          op = 1, entry = r, wa = h[4];
+          h[4] = wa + 1;
+          const int l = left[slot] - 1;
+          if (l <= 0) h[0] = EVIDENCE_COMPLETE, rec[slot] = -1;
+          left[slot] = max(l, 0);
+        } else {
+          opens = raise;
+        }
+      }
+    }
+    const unsigned long long bm = __ballot(merges);
+    if (lane == 0 && bm) atomicAdd(&s_merged, __popcll(bm));
+    const unsigned long long b = __ballot(opens);
+    if (lane == 0) wave_total[wave] = __popcll(b);
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < EVIDENCE_THREADS / 64; ++w) {
+      const int t = wave_total[w];
+      before += w < wave ? t : 0;
+      total += t;
+    }
+    if (opens) {
+      const int rank = base + before + __popcll(b & below);
+      if (rank < nfree) {  // else dropped: the hop is stored in the ring and nothing more
+        const int e = s_free[rank], f = max(1, k - pre);
+        int* h = pool + 6 * e;
+        h[0] = post == 0 ? EVIDENCE_COMPLETE : EVIDENCE_RECORDING;
+        h[1] = slot, h[2] = k, h[3] = f, h[4] = k - f + 1, h[5] = recorded0 + rank;
+        if (post > 0) rec[slot] = e, left[slot] = post;
+        op = 2, entry = e, wa = f, wb = k - f + 1;
+      }
+    }
+    if (i < A) {
+      int* w = work + 4ll * i;
+      w[0] = op, w[1] = entry, w[2] = wa, w[3] = wb;
+    }
+    base += total;
+    __syncthreads();  // every wave has read the table: the next chunk may overwrite it
+  }
+  // the scratch words go back to "unclaimed" for the next launch (every claim was read before the last barrier)
+  for (int i = tid; i < A; i += EVIDENCE_THREADS) {
+    const int slot = hdr[2 * i], k = hdr[2 * i + 1];
+    if (slot >= 0 && slot < S && k >= 1) __hip_atomic_store(&claim[slot], EVIDENCE_UNCLAIMED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  if (tid == 0) {
+    const int got = min(base, nfree);
+    counters[0] += base;
+    counters[1] = recorded0 + got;
+    counters[2] += base - got;
+    counters[3] += s_merged;
+  }
+}
+
+const char* launch_evidence_mark(const int* hdr, int A, const int* vst, int S, int pre, int post, int* rec, int* left, int* claim,
+                                 int* pool, int clips, int* counters, int* work, hipStream_t s) {
+  if (!hdr || !vst || !rec || !left || !claim || !pool || !counters || !work) return "evidence_mark: null argument";
+  if (A <= 0 || A > EVIDENCE_MAX_ROWS) return "evidence_mark: 1 to 8192 rows";
+  if (S <= 0) return "evidence_mark: no slots";
+  if (pre < 0 || post < 0 || (long long)pre + post + 1 > 0x7fffffffll) return "evidence_mark: pre and post of 0 or more hops";
+  if (clips < 1 || clips > EVIDENCE_MAX_CLIPS) return "evidence_mark: 1 to 8192 clips";
+  hipLaunchKernelGGL(evidence_mark_kernel, dim3(1), dim3(EVIDENCE_THREADS), 0, s, hdr, A, vst, S, pre, post, rec, left, claim, pool,
+                     clips, counters, work);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+// q = x * 32768 (one fp32 multiply), NaN -> 0, clamped to [-32768, 32767], rounded half to even
+__device__ __forceinline__ short evidence_pcm16(float x) {
+  float q = x * 32768.f;
+  q = (q != q) ? 0.f : q;
+  q = fminf(fmaxf(q, -32768.f), 32767.f);
+  return (short)(int)__builtin_rintf(q);
+}
+
+// one hop from src to dst_f (fp32, bit for bit) or dst_h (pcm16): four samples per lane where the hop is a multiple of 4
+// and both rows are aligned for it (16 bytes of fp32, 8 of int16), one sample per lane otherwise
+__device__ __forceinline__ void evidence_put(const float* __restrict__ src, float* __restrict__ dst_f, short* __restrict__ dst_h,
+                                             int hop, int t0, int step) {
+  if (dst_f) {
+    if ((hop & 3) == 0 && aligned16(src) && aligned16(dst_f)) {
+      for (int q = t0; q < hop / 4; q += step)
+        *reinterpret_cast<uint4*>(dst_f + 4 * q) = *reinterpret_cast<const uint4*>(src + 4 * q);
+      return;
+    }
+    const unsigned int* s = reinterpret_cast<const unsigned int*>(src);
+    unsigned int* d = reinterpret_cast<unsigned int*>(dst_f);
+    for (int j = t0; j < hop; j += step) d[j] = s[j];
+    return;
+  }
+  if ((hop & 3) == 0 && aligned16(src) && ((unsigned long long)dst_h & 7ull) == 0) {
+    for (int q = t0; q < hop / 4; q += step) {
+      const float4 v = *reinterpret_cast<const float4*>(src + 4 * q);
+      short4 o;
+      o.x = evidence_pcm16(v.x), o.y = evidence_pcm16(v.y), o.z = evidence_pcm16(v.z), o.w = evidence_pcm16(v.w);
+      *reinterpret_cast<short4*>(dst_h + 4 * q) = o;
+    }
+    return;
+  }
+  for (int j = t0; j < hop; j += step) dst_h[j] = evidence_pcm16(src[j]);
+}
+
+struct EvidenceCopyArgs {
+  const float* x;       // (A, hop) the hops of this update
+  const float* scores;  // score of row i at scores[i * stride], or nullptr: every score is NaN
+  const int* hdr;       // (A, 2): slot, k
+  const int* work;      // (A, 4): what evidence_mark left
+  float* hist;          // (S, (pre + 1) hop)
+  float* sring;         // (S, pre + 1)
+  void* audio;          // (clips, L hop) fp32 or int16
+  float* cscores;       // (clips, L)
+  int stride, A, hop, pre, post, S, clips, pcm16;
+};
+
+__global__ __launch_bounds__(256) void evidence_copy_kernel(EvidenceCopyArgs a) {
+  const int row = blockIdx.y;
+  const int slot = a.hdr[2 * row], k = a.hdr[2 * row + 1];
+  const int op = a.work[4 * row], entry = a.work[4 * row + 1], wa = a.work[4 * row + 2], wb = a.work[4 * row + 3];
+  const int P = a.pre + 1, L = P + a.post;
+  if (!(slot >= 0 && slot < a.S && k >= 1 && op >= 0 && op <= 2)) return;
+  if (op == 1 && !(entry >= 0 && entry < a.clips && wa >= 0 && wa < L)) return;
+  if (op == 2 && !(entry >= 0 && entry < a.clips && wa >= 1 && wb >= 1 && wb <= P && wa + (wb - 1) == k)) return;
+  const int t0 = blockIdx.x * blockDim.x + threadIdx.x, step = gridDim.x * blockDim.x;
+  const int c = (k - 1) % P;
+  const float* src = a.x + (long long)row * a.hop;
+  float* ring = a.hist + (long long)slot * P * a.hop;
+  evidence_put(src, ring + (long long)c * a.hop, nullptr, a.hop, t0, step);
+  const long long clip0 = (long long)entry * L * a.hop;
+  float* clip_f = a.pcm16 ? nullptr : static_cast<float*>(a.audio) + clip0;
+  short* clip_h = a.pcm16 ? static_cast<short*>(a.audio) + clip0 : nullptr;
+  if (op >= 1) {  // this hop, from the update's own rows: position wa of a clip being recorded, the last of an opened one
+    const long long at = (long long)(op == 1 ? wa : wb - 1) * a.hop;
+    evidence_put(src, clip_f ? clip_f + at : nullptr, clip_h ? clip_h + at : nullptr, a.hop, t0, step);
+  }
+  if (op == 2) {  // the pre-roll: hops wa .. k - 1 out of the ring (none of them is written by this launch)
+    for (int j = 0; j < wb - 1; ++j) {
+      const float* from = ring + (long long)((wa - 1 + j) % P) * a.hop;
+      const long long at = (long long)j * a.hop;
+      evidence_put(from, clip_f ? clip_f + at : nullptr, clip_h ? clip_h + at : nullptr, a.hop, t0, step);
+    }
+  }
+  if (blockIdx.x == 0) {  // the scores beside the audio
+    const float s = a.scores ? a.scores[(long long)row * a.stride] : __builtin_nanf("");
+    float* sr = a.sring + (long long)slot * P;
+    float* cs = a.cscores + (long long)entry * L;
+    if (threadIdx.x == 0) {
+      sr[c] = s;
+      if (op == 1) cs[wa] = s;
+      if (op == 2) cs[wb - 1] = s;
+    }
+    if (op == 2)
+      for (int j = threadIdx.x; j < wb - 1; j += blockDim.x) cs[j] = sr[(wa - 1 + j) % P];
+  }
+}
+
+const char* launch_evidence_copy(const float* x, const float* scores, int stride, const int* hdr, const int* work, int A, int hop,
+                                 int pre, int post, float* hist, float* sring, int S, void* audio, float* cscores, int clips,
+                                 int encoding, hipStream_t s) {
+  if (!x || !hdr || !work || !hist || !sring || !audio || !cscores) return "evidence_copy: null argument";
+  if (scores && stride < 1) return "evidence_copy: a score stride of at least 1";
+  if (A <= 0 || A > EVIDENCE_MAX_ROWS) return "evidence_copy: 1 to 8192 rows";
+  if (S <= 0 || hop <= 0) return "evidence_copy: no slots or no hop";
+  if (pre < 0 || post < 0 || ((long long)pre + 1) * hop > 0x7fffffffll || ((long long)pre + 1 + post) * hop > 0x7fffffffll)
+    return "evidence_copy: pre and post of 0 or more hops, a ring and a clip below 2^31 samples";
+  if (clips < 1 || clips > EVIDENCE_MAX_CLIPS) return "evidence_copy: 1 to 8192 clips";
+  if (encoding != 0 && encoding != 1) return "evidence_copy: encoding 0 (fp32) or 1 (pcm16)";
+  EvidenceCopyArgs a{};
+  a.x = x; a.scores = scores; a.hdr = hdr; a.work = work; a.hist = hist; a.sring = sring; a.audio = audio; a.cscores = cscores;
+  a.stride = scores ? stride : 0; a.A = A; a.hop = hop; a.pre = pre; a.post = post; a.S = S; a.clips = clips; a.pcm16 = encoding;
+  hipLaunchKernelGGL(evidence_copy_kernel, dim3(min((hop + 1023) / 1024, 64), A), dim3(256), 0, s, a);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+// ---------------------------------------------------------------------------------
 // Row LayerNorm (+ activation): one wave per row, C <= 1024, C % 4 == 0.  The row
 // stays in registers (float4 per lane per 256-column slab), two-pass statistics in
 // fp32 like torch.  Used for the conv-stack LayerNorm+GELU, every transformer /

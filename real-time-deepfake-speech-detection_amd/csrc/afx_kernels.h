@@ -172,6 +172,13 @@ const char* launch_cascade_windows(const float* hist, int S, int window, const i
 const char* launch_verdict(const float* scores, int stride, const float* vscores, const int* hdr, int A, float* m, int* st,
                            int S, float alpha, float enter, float exit_, float verifier_enter, int confirm, int release,
                            int min_scores, int latch, int* log, int cap, hipStream_t s);
+// evidence clips (include/afx.h afx_k_evidence_mark / _copy): mark decides, in one workgroup and in row order, which rows append
+// to a clip and which open one (rec, left, clip headers, counters, one work item per row); copy moves the samples and scores
+const char* launch_evidence_mark(const int* hdr, int A, const int* vst, int S, int pre, int post, int* rec, int* left, int* claim,
+                                 int* pool, int clips, int* counters, int* work, hipStream_t s);
+const char* launch_evidence_copy(const float* x, const float* scores, int stride, const int* hdr, const int* work, int A, int hop,
+                                 int pre, int post, float* hist, float* sring, int S, void* audio, float* cscores, int clips,
+                                 int encoding, hipStream_t s);
 void conv0_set_mfma(int v);  // A/B knob: 1 (default) = matrix-core forms (split-precision fp16 when packed), 2 = fp32 MFMA form, 0 = VALU form
 // y[t] = x[t] - coef * x[t-1] with a reflect pad on the left; (B,L) fp32 -> (B,L) fp32
 const char* launch_pre_emphasis(const float* x, int B, int L, float coef, float* y, hipStream_t s);
