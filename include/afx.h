@@ -482,6 +482,47 @@ int afx_k_evidence_mark(const int* hdr, int A, const int* vst, int S, int pre, i
 int afx_k_evidence_copy(const float* x, const float* scores, int stride, const int* hdr, const int* work, int A, int hop,
                         int pre, int post, float* hist, float* sring, int S, void* audio, float* cscores, int clips,
                         int encoding, void* stream);
+/* Input quality (afx/quality.py): what the hop behind each score looked like, measured on the device, and a score that is
+ * passed on or replaced by NaN ("cannot judge").  Policy, fp32 / int32: clip > 0, clip_count >= 1, flat_run >= 2, e_quiet >= 0
+ * (the host's fp32(quiet * hop), product in double, rounded once), dc >= 0 (fp32(dc * hop) likewise), mask in 0..31,
+ * max_bad >= 0, abstain 0 / 1; 1 <= W <= 1024 hops of window.
+ * State per slot: ring (S, W) uint8, the flags of hop j at (j - 1) mod W; state (S, 3) int32 = (last, run, bad): the bits of
+ * the newest sample, the length of the run of identical samples it ends, the flagged hops of the window -- (0, 0, 0) for a
+ * new stream; totals (S, 6) int32, saturating at 2^31 - 1: hops seen, hops with flag 1, 2, 4, 8, 16.
+ * An update names rows i = 0..A-1: slot b_i = hdr[i][0] (distinct), hop index k_i = hdr[i][1] >= 1 (the host's samples_seen /
+ * hop after this hop; hdr: device, A x 2 int32), the hop x[i * stride + 0 .. hop) (fp32, stride >= hop in floats: a chunk may
+ * be a view) and s_i = scores[i * sstride] (scores NULL: no scores, no out).  Every arithmetic operation is one correctly
+ * rounded fp32 operation (no fma):
+ *     nonfinite = #{ j : (bits(x_j) & 0x7f800000) == 0x7f800000 }
+ *     clipped   = #{ j : |x_j| >= clip }                                   (fp32 compare: a NaN is not counted)
+ *     peak      = max |x_j| over the x_j that are not NaN, +0.0 if none
+ *     e, s      = the sum of x_j * x_j and the sum of x_j, both in this order: the hop padded with +0.0 to a multiple of 1024
+ *                 and viewed as y[tile][t][c], t < 256, c < 4 (element 1024 tile + 4 t + c);
+ *                 q[t][c] = y[0][t][c], then + y[1][t][c], ... in ascending tile order;
+ *                 r[t] = (q[t][0] + q[t][1]) + (q[t][2] + q[t][3]);
+ *                 for w = 128, 64, .., 1: r[t] = r[t] + r[t + w], t < w;  the result is r[0].
+ *                 Non-finite values follow IEEE; a NaN result is recorded as 0x7fc00000 (IEEE fixes no payload)
+ *     longest   = max of r_j over the hop, r_j = 1 if bits(x_j) != bits of the sample before it in the STREAM, else that
+ *                 sample's r + 1 (saturating at 2^31 - 1); (last, run) carry across hops and run = 0 before a session's first
+ *                 sample, so its r is 1.  The compare is bitwise: +0 and -0 differ, two NaNs of equal bits are equal
+ *     flags     = 1 NONFINITE (nonfinite > 0) | 2 CLIPPED (clipped >= clip_count) | 4 FLAT (longest >= flat_run)
+ *               | 8 QUIET (e < e_quiet) | 16 DC (|s| > dc);   a NaN e or s sets neither 8 nor 16
+ *     ring[b][(k - 1) mod W] = flags
+ *     bad       = #{ j in [max(1, k - W + 1), k] : ring[b][(j - 1) mod W] & mask }   (never before the session's first hop)
+ *     state[b]  = (bits of the hop's last sample, r of it, bad);  totals[b][0] += 1, totals[b][1 + n] += (flags >> n) & 1
+ *     meas[i]   = (flags, nonfinite, clipped, longest, bits(e), bits(s), bits(peak), bad)          8 int32
+ *     out[i]    = s_i, bit for bit, if bad <= max_bad or abstain == 0, else the quiet NaN 0x7fc00000
+ * A row with a slot outside [0, S) or k < 1 is skipped whole: no state change, meas[i] all -1, out[i] = s_i.
+ * afx_k_quality: one workgroup of 256 threads per row, thread t owns y[.][t][0..3] (dwordx4 loads where x and stride are
+ * 16-byte aligned and the four elements are inside the hop, element loads otherwise, the same order); the tree's w = 128 and
+ * 64 steps go through LDS, w <= 32 through the wave; counts and peak are integer reductions; the run is a reduction, in stream
+ * order, over an associative summary (length, first and last bits, leading run, trailing run, longest run).  No atomics.
+ * A NULL x / hdr / ring / state / totals / meas, scores without out or with sstride < 1, A outside 1..8192, hop outside
+ * 1..2^24, stride < hop, S < 1, W outside 1..1024 or a policy value outside the ranges above (NaN included): non-zero,
+ * afx_last_error names `quality`, nothing launched. */
+int afx_k_quality(const float* x, long long stride, int A, int hop, const int* hdr, const float* scores, int sstride,
+                  float clip, int clip_count, int flat_run, float e_quiet, float dc, int mask, int max_bad, int abstain,
+                  unsigned char* ring, int W, int* state, int* totals, int S, int* meas, float* out, void* stream);
 int afx_k_rownorm(int dtype, const float* x, long ldx, int rows, int C, const float* gamma, const float* beta,
                   float eps, int act, float* out_f, long ldo_f, void* out_h, long ldo_h, void* stream);
 int afx_k_mhsa(int dtype, const void* qkv, void* out, int B, int T, int H, void* stream);

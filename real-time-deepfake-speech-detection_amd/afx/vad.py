@@ -56,6 +56,7 @@ from ._lib import AfxError, call_on, check, lib, ptr
 from .cascade import CascadeScorer
 from .verdict import VerdictScorer
 from .evidence import EvidenceScorer
+from .quality import QualityScorer
 from .streaming import SlidingWindowScorer, StreamState, _Front, _on
 
 GATE_FORMAT = 1  # layout of the gate part of a StreamState: import_slots refuses any other
@@ -212,7 +213,7 @@ class GatedScorer:
     def __init__(self, scorer, gate=None):
         if isinstance(scorer, (_Front, GatedScorer)):
             raise ValueError("the gate goes inside the fronts: PacketScorer(GatedScorer(scorer), ...), not around them")
-        if not isinstance(scorer, (SlidingWindowScorer, CascadeScorer, VerdictScorer, EvidenceScorer)):
+        if not isinstance(scorer, (SlidingWindowScorer, CascadeScorer, QualityScorer, VerdictScorer, EvidenceScorer)):
             raise ValueError("GatedScorer wraps a SlidingWindowScorer, IncrementalScorer or KVCachedScorer (or a CascadeScorer around one)")
         gate = SpeechGate() if gate is None else gate
         if not isinstance(gate, SpeechGate):

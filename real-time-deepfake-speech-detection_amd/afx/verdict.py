@@ -368,7 +368,8 @@ class Verdicts:
 
 
 class VerdictScorer:
-    """``scorer`` (a SlidingWindowScorer, IncrementalScorer or KVCachedScorer, or a ``CascadeScorer`` around one) with the
+    """``scorer`` (a SlidingWindowScorer, IncrementalScorer or KVCachedScorer, or a ``CascadeScorer`` around one, or an
+    ``afx.quality.QualityScorer`` around either: its withheld scores are NaN rows, which change nothing) with the
     verdict layer behind it under ``policy``; see the module docstring.  It presents the surface the fronts and the gate
     drive an inner scorer through and goes where the cascade goes:
     ``JitterScorer(GatedScorer(VerdictScorer(CascadeScorer(...), policy)), 8000, "mulaw", depth)``.
@@ -383,19 +384,22 @@ class VerdictScorer:
     moves leave it."""
 
     def __init__(self, scorer, policy):
+        from .quality import QualityScorer
         from .vad import GatedScorer
         if isinstance(scorer, (_Front, GatedScorer, VerdictScorer)):
             raise ValueError("the verdict layer goes inside the gate and the fronts: GatedScorer(VerdictScorer(scorer, policy)), "
                              "PacketScorer(VerdictScorer(...), ...)")
-        if not isinstance(scorer, (SlidingWindowScorer, CascadeScorer)):
-            raise ValueError("VerdictScorer wraps a SlidingWindowScorer, IncrementalScorer or KVCachedScorer (or a CascadeScorer around one)")
+        if not isinstance(scorer, (SlidingWindowScorer, CascadeScorer, QualityScorer)):
+            raise ValueError("VerdictScorer wraps a SlidingWindowScorer, IncrementalScorer or KVCachedScorer (or a CascadeScorer around one, "
+                             "or a QualityScorer around either)")
         if not isinstance(policy, VerdictPolicy):
             raise ValueError("policy: a VerdictPolicy")
         if scorer.S > MAX_ROWS:
             raise ValueError(f"a scorer of {scorer.S} slots: one update takes at most {MAX_ROWS} rows")
         self.scorer, self.policy = scorer, policy
         self.verdicts = Verdicts(scorer.S, policy, scorer.device)
-        self._verified = isinstance(scorer, CascadeScorer) and policy.verifier_enter is not None
+        cascade = scorer.scorer if isinstance(scorer, QualityScorer) else scorer  # (the quality layer hands the verifier scores on)
+        self._verified = isinstance(cascade, CascadeScorer) and policy.verifier_enter is not None
 
     # ---- the surface the fronts and the gate use -------------------------------------------------------------------------
     @property

@@ -2933,6 +2933,13 @@ extern "C" int afx_k_evidence_copy(const float* x, const float* scores, int stri
   KRET(launch_evidence_copy(x, scores, stride, hdr, work, A, hop, pre, post, hist, sring, S, audio, cscores, clips, encoding,
                             (hipStream_t)stream));
 }
+extern "C" int afx_k_quality(const float* x, long long stride, int A, int hop, const int* hdr, const float* scores, int sstride,
+                             float clip, int clip_count, int flat_run, float e_quiet, float dc, int mask, int max_bad,
+                             int abstain, unsigned char* ring, int W, int* state, int* totals, int S, int* meas, float* out,
+                             void* stream) {
+  KRET(launch_quality(x, stride, A, hop, hdr, scores, sstride, clip, clip_count, flat_run, e_quiet, dc, mask, max_bad, abstain, ring,
+                      W, state, totals, S, meas, out, (hipStream_t)stream));
+}
 extern "C" int afx_k_rownorm(int dtype, const float* x, long ldx, int rows, int C, const float* gamma,
                              const float* beta, float eps, int act, float* out_f, long ldo_f, void* out_h, long ldo_h,
                              void* stream) {

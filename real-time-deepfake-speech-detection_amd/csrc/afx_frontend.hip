@@ -1803,6 +1803,239 @@ const char* launch_evidence_copy(const float* x, const float* scores, int stride
 }
 
 // ---------------------------------------------------------------------------------
+// Input quality (afx/quality.py; the function is stated in include/afx.h afx_k_quality): what the hop behind each score
+// looked like -- non-finite and clipped samples, peak, energy, sum, the longest run of identical samples -- five flags, a
+// ring of the last W hops' flags per slot and the count of flagged hops in it, and the score passed on or replaced by NaN.
+// One workgroup of 256 threads per row, one launch per push, rows independent, no atomics:
+//   1. thread t owns elements 1024 tile + 4 t + c of every tile (one dwordx4 load where the row is 16-byte aligned and the
+//      four are inside the hop, element loads otherwise; past the hop the element is +0.0).  It accumulates q_e[c] += x * x
+//      and q_s[c] += x in ascending tile order, counts non-finite and clipped samples, takes the peak as an integer max over
+//      the bits of |x|, and folds its elements in stream order into a run summary (QRun).  Per tile the summaries are joined
+//      across the wave (shuffle-down over ADJACENT segments: w = 1, 2, .. 32, the join is not commutative) and the four
+//      wave summaries through LDS onto thread 0's running summary of the hop;
+//   2. r = (q0 + q1) + (q2 + q3); the tree's w = 128 and w = 64 steps through LDS, w <= 32 by shuffle-down in wave 0.
+//      Contraction is off in this kernel: every sum is one correctly rounded fp32 add of one correctly rounded product;
+//   3. thread 0 joins the hop's summary to the carried (last, run), sets the flags and stores the ring entry; the 256
+//      threads count the flagged entries of hops max(1, k - W + 1)..k; thread 0 writes state, totals, meas and out.
+// ---------------------------------------------------------------------------------
+constexpr int QUALITY_MAX_ROWS = 8192;
+constexpr int QUALITY_MAX_W = 1024;         // ring entries per slot (include/afx.h states it)
+constexpr int QUALITY_MAX_HOP = 1 << 24;    // samples of a hop: element indices and run lengths inside a hop stay far below 2^31
+constexpr int QUALITY_N_MAX = 0x7fffffff;
+constexpr int QUALITY_QNAN = 0x7fc00000;
+
+struct QualityArgs {
+  const float* x;        // (A, hop) samples at a row stride of `stride` floats
+  long long stride;
+  const int* hdr;        // (A, 2): slot, hop index k
+  const int* scores;     // the bits of the inner scores at a stride of `sstride` words, or nullptr
+  int sstride;
+  unsigned char* ring;   // (S, W) flags of hop j at (j - 1) mod W
+  int* state;            // (S, 3): bits of the newest sample, run, bad
+  int* totals;           // (S, 6): hops, hops with each flag
+  int* meas;             // (A, 8)
+  int* out;              // (A,) bits of the scores passed on, or nullptr
+  int A, hop, S, W, vec;
+  float clip, e_quiet, dc;
+  int clip_count, flat_run, mask, max_bad, abstain;
+};
+
+// the runs of identical words of a segment of the stream: its length, first and last word, the lengths of the run it
+// starts with and of the run it ends with, and the longest run inside it.  len == 0: the empty segment.
+struct QRun {
+  int len;
+  unsigned first, last;
+  int pre, suf, best;
+};
+
+// segment a followed by segment b (associative, not commutative)
+__device__ __forceinline__ QRun qrun_join(const QRun& a, const QRun& b) {
+  if (a.len == 0) return b;
+  if (b.len == 0) return a;
+  const bool j = a.last == b.first;
+  QRun r;
+  r.len = a.len + b.len;
+  r.first = a.first;
+  r.last = b.last;
+  r.pre = j && a.pre == a.len ? a.len + b.pre : a.pre;
+  r.suf = j && b.suf == b.len ? b.len + a.suf : b.suf;
+  r.best = max(max(a.best, b.best), j ? a.suf + b.pre : 0);
+  return r;
+}
+
+__device__ __forceinline__ int quality_sat_inc(int v, int by) { return v > QUALITY_N_MAX - by ? QUALITY_N_MAX : v + by; }
+
+__global__ __launch_bounds__(256) void quality_kernel(QualityArgs a) {
+#pragma clang fp contract(off)
+  __shared__ float s_e[256], s_s[256];
+  __shared__ int s_cnt[4][3];
+  __shared__ int s_run[2][4][6];
+  __shared__ int s_flags, s_bad[4];
+  const int row = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int slot = a.hdr[2 * row], k = a.hdr[2 * row + 1];
+  const int sbits = a.scores ? a.scores[(long long)row * a.sstride] : 0;
+  if (!(slot >= 0 && slot < a.S && k >= 1)) {  // (the same for every thread of the workgroup: no barrier is passed by some)
+    if (tid < 8) a.meas[8ll * row + tid] = -1;
+    if (tid == 0 && a.out) a.out[row] = sbits;
+    return;
+  }
+  const float* x = a.x + (long long)row * a.stride;
+  const int tiles = (a.hop + 1023) >> 10;
+  float qe[4], qs[4];
+  int nonfinite = 0, clipped = 0, peak = 0;  // (peak: the bits of the largest |x| that is not a NaN; they order as integers)
+  QRun acc{0, 0u, 0u, 0, 0, 0};              // thread 0: the tiles taken so far
+  for (int t = 0; t < tiles; ++t) {
+    const int i0 = (t << 10) + 4 * tid;
+    const int n = min(max(a.hop - i0, 0), 4);
+    float v[4];
+    if (a.vec && n == 4) {
+      const float4 f = *reinterpret_cast<const float4*>(x + i0);
+      v[0] = f.x, v[1] = f.y, v[2] = f.z, v[3] = f.w;
+    } else {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) v[c] = c < n ? x[i0 + c] : 0.f;
+    }
+    QRun r{0, 0u, 0u, 0, 0, 0};
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const float sq = v[c] * v[c];
+      if (t == 0) {
+        qe[c] = sq;
+        qs[c] = v[c];
+      } else {
+        qe[c] = qe[c] + sq;
+        qs[c] = qs[c] + v[c];
+      }
+      if (c < n) {
+        const unsigned b = __float_as_uint(v[c]), ab = b & 0x7fffffffu;
+        nonfinite += (b & 0x7f800000u) == 0x7f800000u;
+        clipped += fabsf(v[c]) >= a.clip;
+        if (ab <= 0x7f800000u) peak = max(peak, (int)ab);
+        r = qrun_join(r, QRun{1, b, b, 1, 1, 1});
+      }
+    }
+    for (int w = 1; w < 64; w <<= 1) {  // lane l (a multiple of 2 w) holds lanes l .. l + w - 1 and takes l + w .. l + 2 w - 1
+      QRun o;
+      o.len = __shfl_down(r.len, w);
+      o.first = __shfl_down(r.first, w);
+      o.last = __shfl_down(r.last, w);
+      o.pre = __shfl_down(r.pre, w);
+      o.suf = __shfl_down(r.suf, w);
+      o.best = __shfl_down(r.best, w);
+      r = qrun_join(r, o);
+    }
+    int* sr = s_run[t & 1][wave];
+    if (lane == 0) sr[0] = r.len, sr[1] = (int)r.first, sr[2] = (int)r.last, sr[3] = r.pre, sr[4] = r.suf, sr[5] = r.best;
+    __syncthreads();  // (one barrier per tile: tile t + 1 writes the other half, tile t + 2 comes after thread 0 passed t + 1's)
+    if (tid == 0) {
+      for (int w = 0; w < 4; ++w) {
+        const int* p = s_run[t & 1][w];
+        acc = qrun_join(acc, QRun{p[0], (unsigned)p[1], (unsigned)p[2], p[3], p[4], p[5]});
+      }
+    }
+  }
+  float re = (qe[0] + qe[1]) + (qe[2] + qe[3]);
+  float rs = (qs[0] + qs[1]) + (qs[2] + qs[3]);
+  for (int w = 32; w >= 1; w >>= 1) {
+    nonfinite += __shfl_down(nonfinite, w);
+    clipped += __shfl_down(clipped, w);
+    peak = max(peak, __shfl_down(peak, w));
+  }
+  if (lane == 0) s_cnt[wave][0] = nonfinite, s_cnt[wave][1] = clipped, s_cnt[wave][2] = peak;
+  s_e[tid] = re;
+  s_s[tid] = rs;
+  __syncthreads();
+  if (tid < 128) {
+    re = re + s_e[tid + 128];
+    rs = rs + s_s[tid + 128];
+    if (tid >= 64) s_e[tid] = re, s_s[tid] = rs;  // (entries 64..127 were read by nobody in this step)
+  }
+  __syncthreads();
+  if (tid < 64) {
+    re = re + s_e[tid + 64];
+    rs = rs + s_s[tid + 64];
+    for (int w = 32; w >= 1; w >>= 1) {  // lanes l < w take r[l + w]: the lanes the next step reads
+      const float oe = __shfl_down(re, w), os = __shfl_down(rs, w);
+      re = re + oe;
+      rs = rs + os;
+    }
+  }
+  int flags = 0, longest = 0, run1 = 0;
+  if (tid == 0) {
+    nonfinite = s_cnt[0][0] + s_cnt[1][0] + s_cnt[2][0] + s_cnt[3][0];
+    clipped = s_cnt[0][1] + s_cnt[1][1] + s_cnt[2][1] + s_cnt[3][1];
+    peak = max(max(s_cnt[0][2], s_cnt[1][2]), max(s_cnt[2][2], s_cnt[3][2]));
+    const int* st = a.state + 3ll * slot;
+    const unsigned last = (unsigned)st[0];
+    const long long run = st[1];  // (0 for a new stream: joining it to the first sample adds nothing)
+    const bool j = acc.first == last;
+    longest = max(acc.best, j ? (int)min(run + acc.pre, (long long)QUALITY_N_MAX) : 0);
+    run1 = j && acc.pre == acc.len ? (int)min(run + acc.len, (long long)QUALITY_N_MAX) : acc.suf;
+    flags = (nonfinite > 0 ? 1 : 0) | (clipped >= a.clip_count ? 2 : 0) | (longest >= a.flat_run ? 4 : 0) |
+            (re < a.e_quiet ? 8 : 0) | (fabsf(rs) > a.dc ? 16 : 0);
+    a.ring[(long long)slot * a.W + (k - 1) % a.W] = (unsigned char)flags;
+    s_flags = flags;
+  }
+  __syncthreads();
+  {
+    const int newest = s_flags, n = min(k, a.W);  // hops k, k - 1, .., k - n + 1: never before the session's first
+    const unsigned char* rg = a.ring + (long long)slot * a.W;
+    int bad = 0;
+    for (int i = tid; i < n; i += 256) {
+      const int f = i == 0 ? newest : rg[(k - 1 - i) % a.W];
+      bad += (f & a.mask) != 0;
+    }
+    for (int w = 32; w >= 1; w >>= 1) bad += __shfl_down(bad, w);
+    if (lane == 0) s_bad[wave] = bad;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const int bad = s_bad[0] + s_bad[1] + s_bad[2] + s_bad[3];
+    int* st = a.state + 3ll * slot;
+    st[0] = (int)acc.last, st[1] = run1, st[2] = bad;
+    int* tot = a.totals + 6ll * slot;
+    tot[0] = quality_sat_inc(tot[0], 1);
+#pragma unroll
+    for (int b = 0; b < 5; ++b) tot[1 + b] = quality_sat_inc(tot[1 + b], (flags >> b) & 1);
+    int* m = a.meas + 8ll * row;
+    m[0] = flags, m[1] = nonfinite, m[2] = clipped, m[3] = longest;
+    m[4] = re != re ? QUALITY_QNAN : __float_as_int(re);  // (a NaN sum is recorded as THE quiet NaN: IEEE fixes no payload)
+    m[5] = rs != rs ? QUALITY_QNAN : __float_as_int(rs);
+    m[6] = peak, m[7] = bad;
+    if (a.out) a.out[row] = bad <= a.max_bad || !a.abstain ? sbits : QUALITY_QNAN;
+  }
+}
+
+const char* launch_quality(const float* x, long long stride, int A, int hop, const int* hdr, const float* scores, int sstride,
+                           float clip, int clip_count, int flat_run, float e_quiet, float dc, int mask, int max_bad, int abstain,
+                           unsigned char* ring, int W, int* state, int* totals, int S, int* meas, float* out, hipStream_t s) {
+  if (!x || !hdr || !ring || !state || !totals || !meas) return "quality: null argument";
+  if (scores && (!out || sstride < 1)) return "quality: scores need an output and a stride of at least 1";
+  if (A <= 0 || A > QUALITY_MAX_ROWS) return "quality: 1 to 8192 rows";
+  if (hop <= 0 || hop > QUALITY_MAX_HOP) return "quality: a hop of 1 to 2^24 samples";
+  if (stride < hop) return "quality: a row stride of at least the hop";
+  if (S <= 0) return "quality: no slots";
+  if (W < 1 || W > QUALITY_MAX_W) return "quality: a window of 1 to 1024 hops";
+  if (!(clip > 0.f)) return "quality: clip above 0";
+  if (clip_count < 1) return "quality: clip_count of at least 1";
+  if (flat_run < 2) return "quality: flat_run of at least 2";
+  if (!(e_quiet >= 0.f) || !(dc >= 0.f)) return "quality: the quiet and dc bounds are 0 or more";
+  if (mask < 0 || mask > 31) return "quality: mask is 0 to 31";
+  if (max_bad < 0) return "quality: max_bad of 0 or more";
+  if (abstain != 0 && abstain != 1) return "quality: abstain is 0 or 1";
+  QualityArgs a{};
+  a.x = x; a.stride = stride; a.hdr = hdr; a.scores = reinterpret_cast<const int*>(scores); a.sstride = scores ? sstride : 0;
+  a.ring = ring; a.state = state; a.totals = totals; a.meas = meas; a.out = scores ? reinterpret_cast<int*>(out) : nullptr;
+  a.A = A; a.hop = hop; a.S = S; a.W = W;
+  a.vec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && stride % 4 == 0;
+  a.clip = clip; a.e_quiet = e_quiet; a.dc = dc;
+  a.clip_count = clip_count; a.flat_run = flat_run; a.mask = mask; a.max_bad = max_bad; a.abstain = abstain;
+  hipLaunchKernelGGL(quality_kernel, dim3(A), dim3(256), 0, s, a);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+// ---------------------------------------------------------------------------------
 // Row LayerNorm (+ activation): one wave per row, C <= 1024, C % 4 == 0.  The row
 // stays in registers (float4 per lane per 256-column slab), two-pass statistics in
 // fp32 like torch.  Used for the conv-stack LayerNorm+GELU, every transformer /

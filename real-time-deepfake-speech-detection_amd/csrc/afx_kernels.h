@@ -179,6 +179,12 @@ const char* launch_evidence_mark(const int* hdr, int A, const int* vst, int S, i
 const char* launch_evidence_copy(const float* x, const float* scores, int stride, const int* hdr, const int* work, int A, int hop,
                                  int pre, int post, float* hist, float* sring, int S, void* audio, float* cscores, int clips,
                                  int encoding, hipStream_t s);
+// input quality (include/afx.h afx_k_quality): per row the hop's non-finite / clipped counts, peak, energy, sum and longest run
+// of identical samples, the five flags into the slot's ring, the flagged hops of the last W, the score passed on or made NaN;
+// one workgroup per row, no atomics
+const char* launch_quality(const float* x, long long stride, int A, int hop, const int* hdr, const float* scores, int sstride,
+                           float clip, int clip_count, int flat_run, float e_quiet, float dc, int mask, int max_bad, int abstain,
+                           unsigned char* ring, int W, int* state, int* totals, int S, int* meas, float* out, hipStream_t s);
 void conv0_set_mfma(int v);  // A/B knob: 1 (default) = matrix-core forms (split-precision fp16 when packed), 2 = fp32 MFMA form, 0 = VALU form
 // y[t] = x[t] - coef * x[t-1] with a reflect pad on the left; (B,L) fp32 -> (B,L) fp32
 const char* launch_pre_emphasis(const float* x, int B, int L, float coef, float* y, hipStream_t s);
