@@ -35,26 +35,18 @@ The one read-back.  How many windows the verifier is given depends on the scores
 int32: the count, then the chosen rows) to pinned host memory and waits for it, once.  A push whose screen emitted no score
 (a KV-cached hop that completed no frame) stores the audio and selects nothing: no ``wait`` moves.
 """
-import math
-
 import numpy as np
 import torch
 
-from ._lib import AfxError, call_on, check, lib, ptr
-from .streaming import SlidingWindowScorer, StreamState, _Front, _on, weights_fingerprint
+from ._layer import Layer, _on, fp32, integer, need_gpu, rows_on, sample_cols, slot_count
+from ._lib import call_on, check, lib, ptr
+from .streaming import weights_fingerprint
 
 CASCADE_FORMAT = 1  # layout of the cascade part of a StreamState: import_slots refuses any other
-MAX_ROWS = 8192     # rows of one afx_k_cascade_select launch (its keys live in LDS)
 MAX_BUDGET = 1024
 MIN_CLIP = 400      # the shortest clip the engines take (one SSL frame)
 _STATE_KEYS = ("cascade_wait", "cascade_verified", "cascade_verified_at")
 _RING_KEY = "cascade_samples"
-
-
-def _integer(name, v):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-        raise ValueError(f"{name}: an integer, got {v!r}")
-    return int(v)
 
 
 class CascadePolicy:
@@ -66,24 +58,12 @@ class CascadePolicy:
     window; 400..window): a slot is eligible once it has seen this many samples."""
 
     def __init__(self, threshold, budget, cooldown=0, min_samples=None):
-        if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)):
-            raise ValueError(f"threshold: a number, got {threshold!r}")
-        if math.isnan(threshold) or threshold == -math.inf:
+        self.threshold32 = fp32("threshold", threshold)
+        if self.threshold32 == -np.inf:
             raise ValueError(f"threshold {threshold!r}: an fp32 number or +inf")
-        with np.errstate(over="ignore"):
-            t32 = np.float32(threshold)
-        if np.isinf(t32) and not math.isinf(threshold):
-            raise ValueError(f"threshold {threshold!r} is not an fp32 number")
-        self.threshold32 = t32
-        self.threshold = float(t32)
-        self.budget, self.cooldown = _integer("budget", budget), _integer("cooldown", cooldown)
-        if not 1 <= self.budget <= MAX_BUDGET:
-            raise ValueError(f"budget {budget!r}: 1 to {MAX_BUDGET} windows per push")
-        if self.cooldown < 0 or self.cooldown >= 1 << 31:
-            raise ValueError(f"cooldown {cooldown!r}: a number of hops, 0 or more")
-        self.min_samples = None if min_samples is None else _integer("min_samples", min_samples)
-        if self.min_samples is not None and self.min_samples < MIN_CLIP:
-            raise ValueError(f"min_samples {min_samples!r}: at least {MIN_CLIP}, the shortest clip the engines take")
+        self.threshold = float(self.threshold32)
+        self.budget, self.cooldown = integer("budget", budget, 1, MAX_BUDGET), integer("cooldown", cooldown, 0)
+        self.min_samples = None if min_samples is None else integer("min_samples", min_samples, MIN_CLIP)  # (the shortest clip the engines take)
 
     def params(self):
         """What identifies this policy (plain ints and floats; min_samples None = the scorer's window)."""
@@ -124,11 +104,11 @@ def _verifier_device(v):
     return None if d is None else torch.device(d)
 
 
-class CascadeScorer:
-    """``screen`` (a SlidingWindowScorer, IncrementalScorer or KVCachedScorer) with ``verifier`` (an Engine, or a drop-in
-    model, with ``forward((B, window)) -> (B, 2)`` on the screen's device) behind it under ``policy``; see the module
-    docstring for the contract.  ``state_dict``: the verifier's weights, for the fingerprint session moves compare
-    (default: ``verifier.state_dict()`` when it has one).
+class CascadeScorer(Layer):
+    """``screen`` (a SlidingWindowScorer, IncrementalScorer or KVCachedScorer: the cascade is the first layer of the stack
+    order of ``afx._layer``) with ``verifier`` (an Engine, or a drop-in model, with ``forward((B, window)) -> (B, 2)`` on
+    the screen's device) behind it under ``policy``; see the module docstring for the contract.  ``state_dict``: the
+    verifier's weights, for the fingerprint session moves compare (default: ``verifier.state_dict()`` when it has one).
 
     It presents the surface the fronts and the gate drive an inner scorer through and goes innermost:
     ``JitterScorer(GatedScorer(CascadeScorer(screen, teacher, policy)), 8000, "mulaw", depth)``; both models then see the
@@ -136,20 +116,21 @@ class CascadeScorer:
 
     Results: ``verified`` ((S,) fp32 on the device: the latest verifier score of each slot since its reset, NaN if none),
     ``verified_at`` ((S,) int64 on the host: the slot's ``samples_seen`` at that verification, -1 if none),
-    ``take_events()`` and ``stats()``."""
+    ``take_events()`` and ``stats()``.
+
+    Sessions: the part of a ``StreamState`` is ``cascade_wait`` ((n,) int64, 0..cooldown), ``cascade_verified`` ((n,) fp32),
+    ``cascade_verified_at`` ((n,) int64, at most the session's samples) and, when the cascade owns the ring,
+    ``cascade_samples`` ((n, window) fp32: the last min(seen, window) samples, oldest first, zeros after, the layout of the
+    sliding scorer's ``samples``); meta ``cascade`` (format), ``cascade_policy`` and ``cascade_verifier``."""
+
+    layer = "cascade"
+    _part = "cascade part (it was not exported by a CascadeScorer of this kind)"
 
     def __init__(self, screen, verifier, policy, state_dict=None):
-        from .vad import GatedScorer
-        if isinstance(screen, (_Front, GatedScorer, CascadeScorer)):
-            raise ValueError("the cascade goes innermost: GatedScorer(CascadeScorer(screen, ...)), PacketScorer(CascadeScorer(...), ...)")
-        if not isinstance(screen, SlidingWindowScorer):
-            raise ValueError("CascadeScorer screens with a SlidingWindowScorer, IncrementalScorer or KVCachedScorer")
-        if not isinstance(policy, CascadePolicy):
-            raise ValueError("policy: a CascadePolicy")
+        super().__init__(screen)
+        slot_count(screen.S, policy, CascadePolicy)
         if not (hasattr(verifier, "forward") or callable(verifier)):
             raise ValueError("verifier: an Engine or a model with forward((B, window)) -> (B, 2)")
-        if screen.S > MAX_ROWS:
-            raise ValueError(f"a screen of {screen.S} slots: one selection ranks at most {MAX_ROWS}")
         if policy.budget > screen.S:
             raise ValueError(f"a budget of {policy.budget} windows per push for {screen.S} slots")
         self.min_samples = screen.window if policy.min_samples is None else policy.min_samples
@@ -159,11 +140,12 @@ class CascadeScorer:
         if vd is not None and (vd.type != screen.device.type or (vd.index is not None and screen.device.index is not None
                                                                   and vd.index != screen.device.index)):
             raise ValueError(f"the verifier is on {vd}, the screen on {screen.device}")
-        self.screen, self.verifier, self.policy = screen, verifier, policy
+        self.verifier, self.policy = verifier, policy
         self._weights, self._fingerprint = state_dict, None
         dev, S, B = screen.device, screen.S, policy.budget
         # the retained audio: the screen's own sample ring where it keeps one (same layout, read in place), else a second ring
         self.hist = None if screen.ring is not None else torch.zeros(S, screen.window, dtype=torch.float32, device=dev)
+        self._keys = _STATE_KEYS + ((_RING_KEY,) if self.hist is not None else ())
         self.wait = torch.zeros(S, dtype=torch.int32, device=dev)
         self.verified = torch.full((S,), float("nan"), dtype=torch.float32, device=dev)
         self.verified_at = torch.full((S,), -1, dtype=torch.int64)
@@ -176,30 +158,10 @@ class CascadeScorer:
         self._events = []
         self._last = None  # (slots, verifier scores) of the newest push, None when it verified nothing
 
-    # ---- the surface the fronts and the gate use -------------------------------------------------------------------------
     @property
-    def S(self):
-        return self.screen.S
-
-    @property
-    def device(self):
-        return self.screen.device
-
-    @property
-    def hop(self):
-        return self.screen.hop
-
-    @property
-    def window(self):
-        return self.screen.window
-
-    @property
-    def samples_seen(self):
-        """(S,) int64: the samples each slot's session has seen since its last ``reset`` (the screen's count)."""
-        return self.screen.samples_seen
-
-    def _slot_list(self, slots, ordered=False):
-        return self.screen._slot_list(slots, ordered=ordered)
+    def screen(self):
+        """The inner scorer, by the name this layer has for it."""
+        return self.scorer
 
     def _ring(self):
         return self.hist if self.hist is not None else self.screen.ring
@@ -210,10 +172,9 @@ class CascadeScorer:
         ``afx_k_cascade_select``, ``afx_k_cascade_windows``, ONE read-back of ``sel`` and, when it names n > 0 rows,
         ``verifier.forward`` on the n windows; the results go to ``verified``, ``verified_at`` and the event log."""
         scr = self.screen
-        idx = list(range(self.S)) if slots is None else self._slot_list(slots, ordered=True)
+        idx = self._named(slots)
         dev, hop, window, A = self.device, self.hop, self.window, len(idx)
-        if dev.type != "cuda":
-            raise AfxError("hops are screened, selected and verified on the GPU; there is no CPU fallback")
+        need_gpu(dev, "hops are screened, selected and verified")
         if (not isinstance(chunk, torch.Tensor) or not chunk.is_cuda or chunk.device != dev or chunk.dtype != torch.float32
                 or chunk.shape != (A, hop)):
             raise ValueError(f"expected a CUDA fp32 tensor of shape {(A, hop)} on {dev} (one hop per named slot)")
@@ -288,14 +249,11 @@ class CascadeScorer:
         return dict(screened=torch.from_numpy(self._screened.copy()), candidates=c[:, 0].clone(),
                     verified=torch.from_numpy(self._verifications.copy()), passed_over=c[:, 1].clone())
 
-    def reset(self, slots):
-        """The named slots begin a new stream: the screen's session, ``wait = 0``, ``verified = NaN``, ``verified_at = -1``;
-        the retained audio starts over with the session's sample count."""
-        idx = self._slot_list(slots)
-        self.screen.reset(idx)
+    def _reset(self, idx):
+        """``wait = 0``, ``verified = NaN``, ``verified_at = -1``; the retained audio starts over with the session's sample count."""
         if idx:
             with _on(self.device):
-                rows = torch.tensor(idx, dtype=torch.long, device=self.device)
+                rows = rows_on(idx, self.device)
                 self.wait[rows] = 0
                 self.verified[rows] = float("nan")
             self.verified_at[idx] = -1
@@ -319,54 +277,20 @@ class CascadeScorer:
                     cascade_verifier=dict(arch=getattr(v, "arch", type(v).__name__), dtype=dt if dt is None or isinstance(dt, str) else str(dt),
                                           fingerprint=self._verifier_fingerprint()))
 
-    def state_meta(self):
-        return dict(self.screen.state_meta(), **self._meta())
-
-    def _sample_cols(self, seen):
-        """Ring columns (n, window) of each session's last min(seen, window) samples, oldest first, and their count (n, 1)
-        (``SlidingWindowScorer._sample_cols`` for the cascade's own ring)."""
-        dev = self.device
-        m = seen.clamp(max=self.window).to(dev)[:, None]
-        j = torch.arange(self.window, device=dev)
-        return (seen.to(dev)[:, None] - m + j) % self.window, m
-
-    def export_slots(self, slots):
-        """The screen's ``StreamState`` of the named slots plus the cascade's: ``cascade_wait`` ((n,) int64),
-        ``cascade_verified`` ((n,) fp32), ``cascade_verified_at`` ((n,) int64) and, when the cascade owns the ring,
-        ``cascade_samples`` ((n, window) fp32: the last min(seen, window) samples, oldest first, zeros after, the layout
-        of the sliding scorer's ``samples``); meta ``cascade``, ``cascade_policy`` and ``cascade_verifier``.  No byte of
-        the scorer changes."""
-        idx = self._slot_list(slots, ordered=True)
-        meta = self._meta()
-        st = self.screen.export_slots(idx)
+    def _export(self, idx, st):
         with _on(self.device):
-            rows = torch.tensor(idx, dtype=torch.long, device=self.device)
-            tensors = dict(st.tensors, cascade_wait=self.wait[rows].to("cpu", torch.int64), cascade_verified=self.verified[rows].clone(),
+            rows = rows_on(idx, self.device)
+            tensors = dict(cascade_wait=self.wait[rows].to("cpu", torch.int64), cascade_verified=self.verified[rows].clone(),
                            cascade_verified_at=self.verified_at[idx].clone())
             if self.hist is not None:
-                cols, m = self._sample_cols(st.seen)
+                cols, m = sample_cols(st.seen, self.window, self.device)
                 smp = self.hist[rows[:, None], cols]
                 smp.masked_fill_(torch.arange(self.window, device=self.device)[None, :] >= m, 0.0)
                 tensors[_RING_KEY] = smp
-        return StreamState(dict(st.meta, **meta), st.seen, tensors)
+        return tensors
 
-    def import_slots(self, slots, state):
-        """The named slots take over the sessions of ``state``, a state of a CascadeScorer with the same format, policy and
-        verifier around the same kind of screen; anything else, a state with no cascade part, or a ``wait`` outside
-        0..cooldown, is a ValueError before anything changes."""
-        idx = self._slot_list(slots, ordered=True)
-        if not isinstance(state, StreamState):
-            raise ValueError("import_slots takes a StreamState (export_slots / StreamState.from_state_dict)")
-        mine = self._meta()
-        keys = _STATE_KEYS + ((_RING_KEY,) if self.hist is not None else ())
-        if any(k not in state.tensors for k in keys) or any(k not in state.meta for k in mine):
-            raise ValueError("import_slots: the state has no cascade part (it was not exported by a CascadeScorer of this kind)")
-        for k, v in mine.items():
-            if state.meta[k] != v:
-                raise ValueError(f"import_slots: the state's {k} {state.meta[k]!r} is not this scorer's {v!r}")
-        n, t = len(state), state.tensors
-        if n != len(idx):
-            raise ValueError(f"the state holds {n} sessions for {len(idx)} named slots")
+    def _check(self, state, n):
+        t = state.tensors
         for k in ("cascade_wait", "cascade_verified_at"):
             if t[k].dtype != torch.int64 or tuple(t[k].shape) != (n,):
                 raise ValueError(f"import_slots: {k} is (n,) int64")
@@ -380,15 +304,16 @@ class CascadeScorer:
             raise ValueError("import_slots: a session was verified at a sample count it has not seen")
         if self.hist is not None and (t[_RING_KEY].dtype != torch.float32 or tuple(t[_RING_KEY].shape) != (n, self.window)):
             raise ValueError(f"import_slots: {_RING_KEY} {tuple(t[_RING_KEY].shape)} {t[_RING_KEY].dtype} is not {(n, self.window)} float32")
-        inner = StreamState({k: v for k, v in state.meta.items() if k not in mine}, state.seen,
-                            {k: v for k, v in t.items() if k not in _STATE_KEYS and k != _RING_KEY})
-        self.screen.import_slots(idx, inner)  # (refuses a foreign state before changing anything)
+        return wait, ver, at, state.seen, t.get(_RING_KEY)
+
+    def _import(self, idx, rows):
+        wait, ver, at, seen, smp = rows
         if idx:
             with _on(self.device):
-                rows = torch.tensor(idx, dtype=torch.long, device=self.device)
-                self.wait[rows] = wait.to(self.device, torch.int32)
-                self.verified[rows] = ver.to(self.device)
+                dev_rows = rows_on(idx, self.device)
+                self.wait[dev_rows] = wait.to(self.device, torch.int32)
+                self.verified[dev_rows] = ver.to(self.device)
                 if self.hist is not None:  # sample i of a session to column i % window: the whole row, as the sliding scorer
-                    cols, _ = self._sample_cols(state.seen)
-                    self.hist[rows[:, None], cols] = t[_RING_KEY].to(self.device)
+                    cols, _ = sample_cols(seen, self.window, self.device)
+                    self.hist[dev_rows[:, None], cols] = smp.to(self.device)
             self.verified_at[idx] = at

@@ -52,26 +52,14 @@ import wave
 import numpy as np
 import torch
 
-from ._lib import AfxError, call_on, check, lib, ptr
-from .streaming import StreamState, _on
-from .verdict import N_MAX, VerdictScorer, _slots
+from ._layer import N_MAX, Layer, _on, hop_indices, integer, need_gpu, slot_count, slots_of, upload_pairs
+from ._lib import call_on, check, lib, ptr
 
 EVIDENCE_FORMAT = 1  # layout of the evidence part of a StreamState: import_slots refuses any other
-MAX_ROWS = 8192      # rows of one update
 MAX_CLIPS = 8192     # pool entries (the free list of afx_k_evidence_mark lives in LDS)
 MAX_HOPS = 65535     # pre and post
 FREE, RECORDING, COMPLETE, TRUNCATED = 0, 1, 2, 3
 ENCODINGS = ("fp32", "pcm16")
-_STATE_KEYS = ("evidence_hist", "evidence_scores")
-
-
-def _integer(name, v, lo, hi):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-        raise ValueError(f"{name}: an integer, got {v!r}")
-    v = int(v)
-    if not lo <= v <= hi:
-        raise ValueError(f"{name} {v!r}: {lo} to {hi}")
-    return v
 
 
 def pcm16_reference(x):
@@ -132,9 +120,9 @@ class EvidencePolicy:
     none is free is counted ``dropped``.  encoding: "fp32" stores the samples bit for bit, "pcm16" as int16."""
 
     def __init__(self, pre=None, post=8, clips=64, encoding="fp32"):
-        self.pre = None if pre is None else _integer("pre", pre, 0, MAX_HOPS)
-        self.post = _integer("post", post, 0, MAX_HOPS)
-        self.clips = _integer("clips", clips, 1, MAX_CLIPS)
+        self.pre = None if pre is None else integer("pre", pre, 0, MAX_HOPS)
+        self.post = integer("post", post, 0, MAX_HOPS)
+        self.clips = integer("clips", clips, 1, MAX_CLIPS)
         if not isinstance(encoding, str) or encoding not in ENCODINGS:
             raise ValueError(f"encoding {encoding!r}: one of {ENCODINGS}")
         self.encoding = encoding
@@ -145,13 +133,13 @@ class EvidencePolicy:
 
     def pre_for(self, hop, window=None):
         """``pre`` for a scorer of this ``hop`` and ``window``; the ring and a clip stay below 2^31 samples."""
-        hop = _integer("hop", hop, 1, N_MAX)
+        hop = integer("hop", hop, 1, N_MAX)
         if self.pre is not None:
             pre = self.pre
         else:
             if window is None:
                 raise ValueError("pre=None takes window // hop - 1: give the window")
-            pre = _integer("window // hop - 1", _integer("window", window, 1, N_MAX) // hop - 1, 0, MAX_HOPS)
+            pre = integer("window // hop - 1", integer("window", window, 1, N_MAX) // hop - 1, 0, MAX_HOPS)
         if (pre + 1 + self.post) * hop > N_MAX:
             raise ValueError(f"a clip of {pre + 1 + self.post} hops of {hop} samples: below 2^31 samples")
         return pre
@@ -180,7 +168,7 @@ class EvidencePolicy:
         hop, pre, L = hist.shape[1] // P, P - 1, cscores.shape[1]
         if L != P + self.post or pool.shape != (self.clips, 6) or audio.shape != (self.clips, L * hop):
             raise ValueError("the state was not made by this policy's new_state")
-        b = _slots(slots, S)
+        b = slots_of(slots, S)
         A = b.size
         x = np.asarray(hops)
         if x.dtype != np.float32 or x.shape != (A, hop):
@@ -232,7 +220,7 @@ class EvidencePolicy:
     @staticmethod
     def reset_reference(state, slots):
         """``Evidence.reset`` on the mirrors: a clip being recorded by a named slot is TRUNCATED, ``rec = -1``, ``left = 0``."""
-        for slot in _slots(slots, state["rec"].size):
+        for slot in slots_of(slots, state["rec"].size):
             if state["rec"][slot] >= 0:
                 state["pool"][state["rec"][slot], 0] = TRUNCATED
             state["rec"][slot], state["left"][slot] = -1, 0
@@ -268,13 +256,7 @@ class Evidence:
     for a policy with ``pre=None``."""
 
     def __init__(self, S, policy, hop, device="cuda", window=None):
-        if isinstance(S, bool) or not isinstance(S, (int, np.integer)) or S < 1:
-            raise ValueError(f"S {S!r}: a positive number of slots")
-        if S > MAX_ROWS:
-            raise ValueError(f"{S} slots: one update takes at most {MAX_ROWS} rows")
-        if not isinstance(policy, EvidencePolicy):
-            raise ValueError("policy: an EvidencePolicy")
-        self.S, self.policy = int(S), policy
+        self.S, self.policy = slot_count(S, policy, EvidencePolicy), policy
         self.pre = policy.pre_for(hop, window)
         self.hop, self.post, self.clips = int(hop), policy.post, policy.clips
         self.P, self.L = self.pre + 1, self.pre + 1 + self.post
@@ -303,7 +285,7 @@ class Evidence:
         distinct); hop_index: an int or (A,) ints on the host, 1 or more; scores: (A,) fp32 on the device (any stride) or
         None: every score is NaN; verdict_state: (S, 4) int32 on the device, ``Verdicts.st`` after this push's update.  One
         pinned upload, two launches, no synchronisation."""
-        b = _slots(slots, self.S)
+        b = slots_of(slots, self.S)
         A = b.size
         if (not isinstance(chunk, torch.Tensor) or chunk.dtype != torch.float32 or chunk.shape != (A, self.hop)
                 or chunk.device != self.device):
@@ -314,23 +296,15 @@ class Evidence:
         if (not isinstance(verdict_state, torch.Tensor) or verdict_state.dtype != torch.int32 or verdict_state.shape != (self.S, 4)
                 or verdict_state.device != self.device):
             raise ValueError(f"verdict_state: an int32 tensor of shape {(self.S, 4)} on {self.device}")
-        k = np.asarray(hop_index)
-        if k.dtype == bool or not np.issubdtype(k.dtype, np.integer) or k.ndim > 1 or (k.ndim == 1 and k.size != A):
-            raise ValueError(f"hop_index: an int or {A} ints")
-        k = np.broadcast_to(k.astype(np.int64).reshape(-1), (A,))
-        if A and (k.min() < 1 or k.max() > N_MAX):
-            raise ValueError("hop_index: 1 or more, below 2^31")
+        k = hop_indices(hop_index, A, 1)
         if not A:
             return
-        if self.device.type != "cuda":
-            raise AfxError("evidence is recorded on the GPU; there is no CPU fallback")
+        need_gpu(self.device, "evidence is recorded")
         if scores is not None and A > 1 and scores.stride(0) < 1:  # (an expanded view: the kernel reads scores[i * stride])
             scores = scores.contiguous()
         chunk, vst = chunk.contiguous(), verdict_state.contiguous()
         with torch.cuda.device(self.device):
-            hdr = torch.empty(A, 2, dtype=torch.int32, pin_memory=True)
-            hdr.numpy()[:] = np.stack([b, k], axis=1)
-            d = hdr.to(self.device, non_blocking=True)
+            d = upload_pairs(b, k, self.device)
             check(call_on(self.hist, lib().afx_k_evidence_mark, ptr(d), A, ptr(vst), self.S, self.pre, self.post, ptr(self.rec),
                           ptr(self.left), ptr(self._claim), ptr(self._pool), self.clips, ptr(self.counters), ptr(self._work)))
             check(call_on(self.hist, lib().afx_k_evidence_copy, ptr(chunk), ptr(scores), 1 if scores is None else max(scores.stride(0), 1),
@@ -342,7 +316,7 @@ class Evidence:
         """The named slots begin a new stream: a clip one of them is recording becomes TRUNCATED (kept with the hops it
         has), ``rec = -1``, ``left = 0``.  The rings are left as they are: ``first_hop >= 1`` keeps a new session from
         reading them.  No synchronisation."""
-        b = _slots(slots, self.S)
+        b = slots_of(slots, self.S)
         if b.size:
             with _on(self.device):
                 rows = torch.from_numpy(b).to(self.device)
@@ -356,7 +330,7 @@ class Evidence:
         """-> (evidence_hist (n, P hop) fp32, evidence_scores (n, P) fp32) of the named slots, on the device: the raw ring
         rows (a hop's position is a function of its hop number, so they move as they are)."""
         with _on(self.device):
-            rows = torch.from_numpy(_slots(slots, self.S)).to(self.device)
+            rows = torch.from_numpy(slots_of(slots, self.S)).to(self.device)
             return self.hist[rows].clone(), self.sring[rows].clone()
 
     def check_rows(self, hist, sring, n):
@@ -368,7 +342,7 @@ class Evidence:
 
     def import_rows(self, slots, hist, sring):
         """The named slots take the (checked) ring rows; what they were recording is TRUNCATED, as in ``reset``."""
-        b = _slots(slots, self.S)
+        b = slots_of(slots, self.S)
         if b.size:
             self.reset(b)
             with _on(self.device):
@@ -417,9 +391,10 @@ class Evidence:
                     recording=int((status == RECORDING).sum()), finished=int((status >= COMPLETE).sum()))
 
 
-class EvidenceScorer:
-    """``scorer`` (a ``VerdictScorer``) with the evidence recorder behind it under ``policy``; see the module docstring.  It
-    presents the surface the fronts and the gate drive an inner scorer through and goes where the verdict layer goes:
+class EvidenceScorer(Layer):
+    """``scorer`` (a ``VerdictScorer``: the one kind this layer goes around, ``afx._layer.EXACTLY``) with the evidence
+    recorder behind it under ``policy``; see the module docstring.  It presents the surface the fronts and the gate drive an
+    inner scorer through and goes where the verdict layer goes:
     ``JitterScorer(GatedScorer(EvidenceScorer(VerdictScorer(CascadeScorer(...), vpolicy), epolicy)), 8000, "mulaw", depth)``.
 
     ``push`` returns exactly what the inner ``push`` returns, then records the hops it was given: one small upload and two
@@ -427,43 +402,21 @@ class EvidenceScorer:
     ``smoothed``, ``alarm_since`` and ``take_events()`` are the verdict layer's; ``take_clips()`` is the only read-back of
     this one, ``stats()`` its counters.
 
-    Sessions: ``export_slots`` adds the raw ring rows, so a moved session keeps its pre-roll.  A recording in progress does
-    NOT move: the clip stays in the source's pool, keeps filling while the source slot is pushed, and is TRUNCATED when
-    the source slot is next reset or imported over.  The pool and the counters belong to the scorer, not to a session."""
+    Sessions: the part of a ``StreamState`` is ``evidence_hist`` ((n, (pre + 1) hop) fp32) and ``evidence_scores``
+    ((n, pre + 1) fp32), the raw ring rows, meta ``evidence`` (format) and ``evidence_pre`` (``post``, ``clips`` and
+    ``encoding`` may differ where the sessions go): a moved session keeps its pre-roll.  A recording in progress does NOT
+    move: the clip stays in the source's pool, keeps filling while the source slot is pushed, and is TRUNCATED when the
+    source slot is next reset or imported over, as is what the destination's named slots were recording.  The pool and the
+    counters belong to the scorer, not to a session."""
+
+    layer = "evidence"
+    _keys = ("evidence_hist", "evidence_scores")
+    _part = "evidence part (it was not exported by an EvidenceScorer)"
 
     def __init__(self, scorer, policy):
-        if not isinstance(scorer, VerdictScorer):
-            raise ValueError("EvidenceScorer wraps a VerdictScorer: EvidenceScorer(VerdictScorer(scorer, verdict_policy), policy), "
-                             "inside the gate and the fronts")
-        if not isinstance(policy, EvidencePolicy):
-            raise ValueError("policy: an EvidencePolicy")
-        self.scorer, self.policy = scorer, policy
+        super().__init__(scorer)
+        self.policy = policy
         self.evidence = Evidence(scorer.S, policy, scorer.hop, scorer.device, window=scorer.window)
-
-    # ---- the surface the fronts and the gate use -------------------------------------------------------------------------
-    @property
-    def S(self):
-        return self.scorer.S
-
-    @property
-    def device(self):
-        return self.scorer.device
-
-    @property
-    def hop(self):
-        return self.scorer.hop
-
-    @property
-    def window(self):
-        return self.scorer.window
-
-    @property
-    def samples_seen(self):
-        """(S,) int64: the samples each slot's session has seen since its last ``reset`` (the inner scorer's count)."""
-        return self.scorer.samples_seen
-
-    def _slot_list(self, slots, ordered=False):
-        return self.scorer._slot_list(slots, ordered=ordered)
 
     @property
     def alarm(self):
@@ -492,11 +445,10 @@ class EvidenceScorer:
     def push(self, chunk, slots=None):
         """chunk and slots: the inner scorer's own rule -> exactly what the inner ``push`` returns; then one
         ``Evidence.update`` over the named slots with ``hop_index = samples_seen // hop``."""
-        if self.device.type != "cuda":
-            raise AfxError("hops are scored and recorded on the GPU; there is no CPU fallback")
+        need_gpu(self.device, "hops are scored and recorded")
         inner = self.scorer
         scores = inner.push(chunk, slots)
-        idx = list(range(self.S)) if slots is None else self._slot_list(slots, ordered=True)
+        idx = self._named(slots)
         A = len(idx)
         if not A:
             return scores
@@ -506,47 +458,21 @@ class EvidenceScorer:
                              scores=scores, verdict_state=inner.verdicts.st)
         return scores
 
-    def reset(self, slots):
-        """The named slots begin a new stream: the inner session, the verdict state, and a clip being recorded is TRUNCATED."""
-        idx = self._slot_list(slots)
-        self.scorer.reset(idx)
-        self.evidence.reset(idx)
-
-    # ---- sessions ------------------------------------------------------------------------------------------------------------
+    # ---- sessions (afx._layer.Layer) -----------------------------------------------------------------------------------------
     def _meta(self):
         return dict(evidence=EVIDENCE_FORMAT, evidence_pre=self.evidence.pre)
 
-    def state_meta(self):
-        return dict(self.scorer.state_meta(), **self._meta())
+    def _reset(self, idx):
+        self.evidence.reset(idx)
 
-    def export_slots(self, slots):
-        """The inner scorer's ``StreamState`` of the named slots plus ``evidence_hist`` ((n, (pre + 1) hop) fp32) and
-        ``evidence_scores`` ((n, pre + 1) fp32), the raw ring rows; meta ``evidence`` (format) and ``evidence_pre``.  No byte
-        of the scorer changes; the pool does not move, and neither does a recording in progress (see the class docstring)."""
-        idx = self._slot_list(slots, ordered=True)
-        meta = self._meta()
-        st = self.scorer.export_slots(idx)
+    def _export(self, idx, st):
         hist, sring = self.evidence.export_rows(idx)
-        return StreamState(dict(st.meta, **meta), st.seen, dict(st.tensors, evidence_hist=hist, evidence_scores=sring))
+        return dict(evidence_hist=hist, evidence_scores=sring)
 
-    def import_slots(self, slots, state):
-        """The named slots take over the sessions of ``state``, a state of an EvidenceScorer with the same format, ``pre``
-        and hop around the same kind of scorer (``post``, ``clips`` and ``encoding`` may differ); anything else, or a state
-        with no evidence part, is a ValueError before anything changes.  What the named slots were recording is TRUNCATED."""
-        idx = self._slot_list(slots, ordered=True)
-        if not isinstance(state, StreamState):
-            raise ValueError("import_slots takes a StreamState (export_slots / StreamState.from_state_dict)")
-        mine = self._meta()
-        if any(k not in state.tensors for k in _STATE_KEYS) or any(k not in state.meta for k in mine):
-            raise ValueError("import_slots: the state has no evidence part (it was not exported by an EvidenceScorer)")
-        for k, v in mine.items():
-            if state.meta[k] != v:
-                raise ValueError(f"import_slots: the state's {k} {state.meta[k]!r} is not this scorer's {v!r}")
-        n, t = len(state), state.tensors
-        if n != len(idx):
-            raise ValueError(f"the state holds {n} sessions for {len(idx)} named slots")
-        self.evidence.check_rows(t["evidence_hist"], t["evidence_scores"], n)
-        inner = StreamState({k: v for k, v in state.meta.items() if k not in mine}, state.seen,
-                            {k: v for k, v in t.items() if k not in _STATE_KEYS})
-        self.scorer.import_slots(idx, inner)  # (refuses a foreign state before changing anything)
-        self.evidence.import_rows(idx, t["evidence_hist"], t["evidence_scores"])
+    def _check(self, state, n):
+        rows = state.tensors["evidence_hist"], state.tensors["evidence_scores"]
+        self.evidence.check_rows(*rows, n)
+        return rows
+
+    def _import(self, idx, rows):
+        self.evidence.import_rows(idx, *rows)

@@ -31,6 +31,7 @@ import ctypes as C
 import numpy as np
 import torch
 
+from ._layer import check_pending, export_pending, import_pending, peel, rows_on, wrap
 from ._lib import AfxError, call_on, check, lib, ptr
 from .resample import FILTER_ID
 from .streaming import FeedResult, _Front  # noqa: F401  (FeedResult is part of this module's interface)
@@ -265,16 +266,16 @@ class PacketScorer(_Front):
         and filter history.  No byte of the scorer changes."""
         idx = self.scorer._slot_list(slots, ordered=True)
         st = self.scorer.export_slots(idx)
-        return self._wrap(st, ingest_pending=self._export_pending(idx, self._head[idx], self._fill[idx]),
-                          ingest_fill=torch.from_numpy(self._fill[idx]), ingest_in=torch.from_numpy(self._in[idx]),
-                          resample_hist=self.hist.index_select(0, self._dev_rows(idx)))
+        return wrap(st, self._meta(), ingest_pending=export_pending(self.ring, idx, self._head[idx], self._fill[idx], self.max_pending * self.hop),
+                    ingest_fill=torch.from_numpy(self._fill[idx]), ingest_in=torch.from_numpy(self._in[idx]),
+                    resample_hist=self.hist.index_select(0, rows_on(idx, self.device)))
 
     def import_slots(self, slots, state):
         """The named slots take over the sessions of ``state``, a state of a PacketScorer at the same input rate, filter and
         ingest format whose pending samples fit this scorer's ``max_pending``; anything else is a ValueError before
         anything changes."""
         idx = self.scorer._slot_list(slots, ordered=True)
-        inner = self._peel(state, _STATE_KEYS, self._meta(), "packet-ingest part (it was not exported by a PacketScorer)")
+        inner = peel(state, _STATE_KEYS, self._meta(), "packet-ingest part (it was not exported by a PacketScorer)")
         n = len(state)
         pend, h = state.tensors["ingest_pending"], state.tensors["resample_hist"]
         fill, nin = state.tensors["ingest_fill"].cpu().reshape(-1), state.tensors["ingest_in"].cpu().reshape(-1)
@@ -282,15 +283,15 @@ class PacketScorer(_Front):
             raise ValueError("import_slots: ingest_fill / ingest_in are (n,) int64")
         fill, nin = fill.numpy(), nin.numpy()
         self._check_hist(h, n)
-        self._check_pending("ingest_pending", pend, fill, n)
+        check_pending("ingest_pending", pend, fill, n, self.max_pending * self.hop)
         made = np.array([-(-v * self.L // self.M) for v in nin.tolist()], dtype=np.int64)
         if (nin < 0).any() or not np.array_equal(made, state.seen.numpy() + fill):
             raise ValueError("import_slots: a session's input count does not match its scored and pending samples")
         self.scorer.import_slots(idx, inner)  # (refuses a foreign state before changing anything)
         if idx:
-            self._import_pending(idx, pend)
+            import_pending(self.ring, idx, pend)
             if self.hist.shape[1]:
-                self.hist[self._dev_rows(idx)] = h.to(self.device)
+                self.hist[rows_on(idx, self.device)] = h.to(self.device)
             self._head[idx] = 0
             self._fill[idx] = fill
             self._in[idx] = nin

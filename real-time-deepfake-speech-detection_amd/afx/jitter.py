@@ -47,10 +47,11 @@ import numpy as np
 import torch
 
 from . import rtp
+from ._layer import _on, check_pending, export_pending, import_pending, peel, rows_on, wrap
 from ._lib import call_on, check, lib, ptr
 from .ingest import _MAX_SAMPLES, _SAMPLE, ENCODINGS, _at, _encoding, layout
 from .resample import FILTER_ID
-from .streaming import _Front, _on
+from .streaming import _Front
 
 JITTER_FORMAT = 1  # layout of the jitter part of a StreamState: import_slots refuses any other
 CONCEAL = ("zero", "repeat")  # the library's mode numbers 0, 1
@@ -558,7 +559,7 @@ class JitterScorer(_Front):
         with _on(dev):
             nxt, held = torch.from_numpy(b.next[idx]), torch.from_numpy(b.hi[idx] - b.next[idx])
             k = torch.arange(width)
-            jr = self.jring[self._dev_rows(idx)[:, None], ((nxt[:, None] - self.lookback + k) % self.J).to(dev)]
+            jr = self.jring[rows_on(idx, dev)[:, None], ((nxt[:, None] - self.lookback + k) % self.J).to(dev)]
             jr.masked_fill_((k[None, :] >= self.lookback + held[:, None]).to(dev), 0.0)
         ivs = [b.intervals(s) for s in idx]
         K = max([len(v) for v in ivs] + [1])
@@ -568,7 +569,8 @@ class JitterScorer(_Front):
                 table[i, :len(v)] = v
         book = np.stack([getattr(b, f)[idx] for f in _BOOK], axis=1).reshape(len(idx), len(_BOOK))
         stats = np.stack([getattr(b, f)[idx] for f in _COUNTERS], axis=1).reshape(len(idx), len(_COUNTERS))
-        return self._wrap(st, jitter_pending=self._export_pending(idx, b.head[idx], b.fill[idx]), jitter_fill=torch.from_numpy(b.fill[idx]),
+        return wrap(st, self._meta(), jitter_pending=export_pending(self.ring, idx, b.head[idx], b.fill[idx], self.max_pending * self.hop),
+                    jitter_fill=torch.from_numpy(b.fill[idx]),
                           jitter_ring=jr, jitter_book=torch.from_numpy(book), jitter_stats=torch.from_numpy(stats),
                           jitter_intervals=torch.from_numpy(table))
 
@@ -577,7 +579,7 @@ class JitterScorer(_Front):
         depth, concealment mode, period and fade whose pending samples fit this scorer's ``max_pending``; anything else,
         or a state whose counters contradict each other, is a ValueError before anything changes."""
         idx = self.scorer._slot_list(slots, ordered=True)
-        inner = self._peel(state, _STATE_KEYS, self._meta(), "jitter-buffer part (it was not exported by a JitterScorer)")
+        inner = peel(state, _STATE_KEYS, self._meta(), "jitter-buffer part (it was not exported by a JitterScorer)")
         n = len(state)
         pend, jr = state.tensors["jitter_pending"], state.tensors["jitter_ring"]
         ints = [state.tensors[k].cpu() for k in ("jitter_fill", "jitter_book", "jitter_stats", "jitter_intervals")]
@@ -590,7 +592,7 @@ class JitterScorer(_Front):
         width = self.lookback + self.depth
         if tuple(jr.shape) != (n, width) or jr.dtype != torch.float32:
             raise ValueError(f"import_slots: jitter_ring {tuple(jr.shape)} {jr.dtype} does not fit this scorer ({(n, width)} float32)")
-        self._check_pending("jitter_pending", pend, fill, n)
+        check_pending("jitter_pending", pend, fill, n, self.max_pending * self.hop)
         col = {f: book[:, c] for c, f in enumerate(_BOOK)}
         nxt, hi, gap = col["next"], col["hi"], col["gap"]
         made = np.array([-(-int(v) * self.L // self.M) for v in nxt.tolist()], dtype=np.int64)
@@ -610,9 +612,9 @@ class JitterScorer(_Front):
         if not idx:
             return
         dev, b = self.device, self._b
-        self._import_pending(idx, pend)
+        import_pending(self.ring, idx, pend)
         with _on(dev):
-            rows = self._dev_rows(idx)
+            rows = rows_on(idx, dev)
             self.jring[rows] = 0.0
             k = torch.arange(width)
             cols = (torch.from_numpy(nxt.copy())[:, None] - self.lookback + k) % self.J

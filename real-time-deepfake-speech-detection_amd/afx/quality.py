@@ -55,70 +55,24 @@ All defaults are engineering defaults, not tuned ones: there is no labelled corp
 eight samples at 98 % of full scale in a hop; ``flat_run``: 20 ms of one repeated value at 16 kHz; ``quiet``: a mean square
 of 1e-7 (-70 dBFS); ``dc``: a mean of 5 % of full scale; ``max_bad=0``: one flagged hop in the window withholds the score.
 """
-import math
-
 import numpy as np
 import torch
 
-from ._lib import AfxError, call_on, check, lib, ptr
-from .cascade import CascadeScorer
-from .streaming import SlidingWindowScorer, StreamState, _Front, _on
+from ._layer import N_MAX, Layer, _on, fp32, hop_indices, integer, need_gpu, slot_count, slots_of, upload_pairs
+from ._lib import call_on, check, lib, ptr
 
 QUALITY_FORMAT = 1   # layout of the quality part of a StreamState: import_slots refuses any other
-MAX_ROWS = 8192      # rows of one afx_k_quality launch
 MAX_W = 1024         # hops of window
 MAX_HOP = 1 << 24    # samples of a hop
-N_MAX = (1 << 31) - 1
 QNAN_BITS = 0x7fc00000
 NONFINITE, CLIPPED, FLAT, QUIET, DC = 1, 2, 4, 8, 16
 FLAG_NAMES = ("nonfinite", "clipped", "flat", "quiet", "dc")
-_STATE_KEYS = ("quality_ring", "quality_state", "quality_totals")
-
-
-def _integer(name, v, least, most=N_MAX):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-        raise ValueError(f"{name}: an integer, got {v!r}")
-    v = int(v)
-    if not least <= v <= most:
-        raise ValueError(f"{name} {v!r}: {least} to {most}")
-    return v
-
-
-def _fp32(name, v, positive):
-    """``v`` rounded to fp32 once; NaN, a negative number (``positive``: or zero) and a finite number that is not an fp32
-    number are refused.  +inf is a number: the flag it bounds never comes."""
-    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
-        raise ValueError(f"{name}: a number, got {v!r}")
-    if math.isnan(v):
-        raise ValueError(f"{name} is NaN")
-    with np.errstate(over="ignore"):
-        t = np.float32(v)
-    if np.isinf(t) and not math.isinf(v):
-        raise ValueError(f"{name} {v!r} is not an fp32 number")
-    if t < 0 or (positive and t == 0):
-        raise ValueError(f"{name} {v!r}: {'above 0' if positive else '0 or more'} (as an fp32 number)")
-    return t
-
-
-def _slots(slots, S):
-    """Distinct slot indices in [0, S), in the order given (None: every slot)."""
-    if slots is None:
-        return np.arange(S, dtype=np.int64)
-    b = np.asarray(slots)
-    if b.dtype == bool or (b.size and not np.issubdtype(b.dtype, np.integer)) or b.ndim > 1:
-        raise ValueError("slots: a list of slot indices")
-    b = b.astype(np.int64).reshape(-1)
-    if b.size and (b.min() < 0 or b.max() >= S):
-        raise ValueError(f"a slot index outside 0..{S - 1}")
-    if np.unique(b).size != b.size:
-        raise ValueError("a slot is named twice")
-    return b
 
 
 def window_hops(window, hop):
     """W = ceil(window / hop), the hops the window count looks back over; 1 <= W <= 1024 and 1 <= hop <= 2^24."""
-    hop = _integer("hop", hop, 1, MAX_HOP)
-    window = _integer("window", window, 1)
+    hop = integer("hop", hop, 1, MAX_HOP)
+    window = integer("window", window, 1)
     W = -(-window // hop)
     if W > MAX_W:
         raise ValueError(f"a window of {window} samples is {W} hops of {hop}: at most {MAX_W}")
@@ -183,12 +137,12 @@ class QualityPolicy:
     abstain=False: measure and flag only, every score passes.  All defaults are engineering defaults, not tuned ones."""
 
     def __init__(self, clip=0.98, clip_count=8, flat_run=320, quiet=1e-7, dc=0.05, mask=31, max_bad=0, abstain=True):
-        self.clip32 = _fp32("clip", clip, True)
-        self.quiet32, self.dc32 = _fp32("quiet", quiet, False), _fp32("dc", dc, False)
-        self.clip_count = _integer("clip_count", clip_count, 1)
-        self.flat_run = _integer("flat_run", flat_run, 2)
-        self.mask = _integer("mask", mask, 0, 31)
-        self.max_bad = _integer("max_bad", max_bad, 0)
+        self.clip32 = fp32("clip", clip, True)
+        self.quiet32, self.dc32 = fp32("quiet", quiet, False), fp32("dc", dc, False)
+        self.clip_count = integer("clip_count", clip_count, 1)
+        self.flat_run = integer("flat_run", flat_run, 2)
+        self.mask = integer("mask", mask, 0, 31)
+        self.max_bad = integer("max_bad", max_bad, 0)
         if not isinstance(abstain, (bool, np.bool_)):
             raise ValueError(f"abstain: True or False, got {abstain!r}")
         self.abstain = bool(abstain)
@@ -213,16 +167,13 @@ class QualityPolicy:
         if not isinstance(state, QualityState):
             raise ValueError("state: a QualityState")
         S, W = state.ring.shape
-        b = _slots(slots, S)
+        b = slots_of(slots, S)
         A = b.size
         x = np.ascontiguousarray(hops, dtype=np.float32)
         if x.ndim != 2 or x.shape[0] != A or not 1 <= x.shape[1] <= MAX_HOP:
             raise ValueError("hops: (A, h) float32, one hop per named slot")
         h = x.shape[1]
-        k = np.asarray(hop_index)
-        if k.dtype == bool or not np.issubdtype(k.dtype, np.integer) or k.ndim > 1 or (k.ndim == 1 and k.size != A):
-            raise ValueError(f"hop_index: an int or {A} ints")
-        k = np.broadcast_to(k.astype(np.int64).reshape(-1), (A,)).copy()
+        k = hop_indices(hop_index, A).copy()
         s_in = None if scores is None else np.asarray(scores, dtype=np.float32).reshape(-1).copy()
         if s_in is not None and s_in.size != A:
             raise ValueError("slots, hops, hop_index and scores name the same rows")
@@ -315,14 +266,9 @@ class Quality:
     ``stats()`` is the only read-back."""
 
     def __init__(self, S, policy, hop, window, device="cuda"):
-        if isinstance(S, bool) or not isinstance(S, (int, np.integer)) or S < 1:
-            raise ValueError(f"S {S!r}: a positive number of slots")
-        if S > MAX_ROWS:
-            raise ValueError(f"{S} slots: one update takes at most {MAX_ROWS} rows")
-        if not isinstance(policy, QualityPolicy):
-            raise ValueError("policy: a QualityPolicy")
+        S = slot_count(S, policy, QualityPolicy)
         self.W = window_hops(window, hop)
-        self.S, self.policy, self.hop, self.window = int(S), policy, int(hop), int(window)
+        self.S, self.policy, self.hop, self.window = S, policy, int(hop), int(window)
         self.e_quiet, self.d = (float(v) for v in policy.bounds(self.hop))
         self.ring = torch.zeros(self.S, self.W, dtype=torch.uint8, device=device)
         self.device = self.ring.device  # (with its index: every launch of an update goes to THIS GPU)
@@ -364,17 +310,12 @@ class Quality:
         row i the hop of slot slots[i] (None: every slot, in order; the slots are distinct); hop_index: an int or (A,) ints
         on the host, 1 or more; scores: (A,) fp32 on the device (any stride: a column is read in place) or None -> ``(out,
         meas)`` on the device: (A,) fp32 or None, (A, 8) int32.  One pinned upload, one launch, no synchronisation."""
-        b = _slots(slots, self.S)
+        b = slots_of(slots, self.S)
         A = b.size
         if (not isinstance(hops, torch.Tensor) or hops.dtype != torch.float32 or hops.shape != (A, self.hop)
                 or hops.device != self.device):
             raise ValueError(f"hops: an fp32 tensor of shape {(A, self.hop)} on {self.device}")
-        k = np.asarray(hop_index)
-        if k.dtype == bool or not np.issubdtype(k.dtype, np.integer) or k.ndim > 1 or (k.ndim == 1 and k.size != A):
-            raise ValueError(f"hop_index: an int or {A} ints")
-        k = np.broadcast_to(k.astype(np.int64).reshape(-1), (A,))
-        if A and (k.min() < 1 or k.max() > N_MAX):
-            raise ValueError("hop_index: 1 or more, below 2^31")
+        k = hop_indices(hop_index, A, 1)
         if scores is not None and (not isinstance(scores, torch.Tensor) or scores.dtype != torch.float32 or scores.shape != (A,)
                                    or scores.device != self.device):
             raise ValueError(f"scores: an fp32 tensor of shape {(A,)} on {self.device}")
@@ -384,17 +325,14 @@ class Quality:
         return self._update(hops, b, k, scores)
 
     def _update(self, hops, slots, hop_index, scores):
-        if self.device.type != "cuda":
-            raise AfxError("hops are measured on the GPU; there is no CPU fallback")
+        need_gpu(self.device, "hops are measured")
         p, A = self.policy, len(slots)
         if hops.stride(1) != 1 or (A > 1 and hops.stride(0) < self.hop):  # (a transposed or expanded view)
             hops = hops.contiguous()
         if scores is not None and A > 1 and scores.stride(0) < 1:
             scores = scores.contiguous()
         with torch.cuda.device(self.device):
-            hdr = torch.empty(A, 2, dtype=torch.int32, pin_memory=True)
-            hdr.numpy()[:] = np.stack([slots, hop_index], axis=1)
-            d = hdr.to(self.device, non_blocking=True)
+            d = upload_pairs(slots, hop_index, self.device)
             meas = torch.empty(A, 8, dtype=torch.int32, device=self.device)
             out = None if scores is None else torch.empty(A, dtype=torch.float32, device=self.device)
             check(call_on(self.ring, lib().afx_k_quality, ptr(hops), max(hops.stride(0), self.hop), A, self.hop, ptr(d), ptr(scores),
@@ -407,7 +345,7 @@ class Quality:
     def reset(self, slots):
         """The named slots begin a new stream: ``q_state = (0, 0, 0)`` and ``q_totals = 0``.  The ring is left alone: a new
         session's window count never reaches back before its first hop."""
-        b = _slots(slots, self.S)
+        b = slots_of(slots, self.S)
         if b.size:
             with _on(self.device):
                 rows = torch.from_numpy(b).to(self.device)
@@ -418,7 +356,7 @@ class Quality:
         """-> (quality_ring (n, W) uint8 on the device, quality_state (n, 3) and quality_totals (n, 6) int64 on the host) of
         the named slots."""
         with _on(self.device):
-            rows = torch.from_numpy(_slots(slots, self.S)).to(self.device)
+            rows = torch.from_numpy(slots_of(slots, self.S)).to(self.device)
             return self.ring[rows].clone(), self.st[rows].to("cpu", torch.int64), self.totals[rows].to("cpu", torch.int64)
 
     def check_rows(self, ring, st, totals, n):
@@ -445,7 +383,7 @@ class Quality:
 
     def import_rows(self, slots, ring, st, totals):
         """The named slots take the (checked) state rows."""
-        b = _slots(slots, self.S)
+        b = slots_of(slots, self.S)
         if b.size:
             with _on(self.device):
                 rows = torch.from_numpy(b).to(self.device)
@@ -454,10 +392,10 @@ class Quality:
                 self.totals[rows] = totals.to(self.device, torch.int32)
 
 
-class QualityScorer:
-    """``scorer`` (a SlidingWindowScorer, IncrementalScorer or KVCachedScorer, or a ``CascadeScorer`` around one) with the
-    quality layer behind it under ``policy``; see the module docstring.  It presents the surface the verdict layer, the
-    gate and the fronts drive an inner scorer through and goes where the cascade goes, inside the verdict layer:
+class QualityScorer(Layer):
+    """``scorer`` (whatever stands below the quality layer in the stack order of ``afx._layer``) with the quality layer
+    behind it under ``policy``; see the module docstring.  It presents the surface the verdict layer, the gate and the
+    fronts drive an inner scorer through and goes where the cascade goes, inside the verdict layer:
     ``JitterScorer(GatedScorer(EvidenceScorer(VerdictScorer(QualityScorer(CascadeScorer(...), qpolicy), vpolicy), epolicy)),
     8000, "mulaw", depth)``.
 
@@ -469,51 +407,25 @@ class QualityScorer:
     ``flags`` ((S,) uint8, each slot's newest flags).  ``stats()`` is the only read-back.  Around a cascade ``verified``,
     ``verified_at`` and ``take_events`` are the cascade's, and with ``abstain`` on ``last_verified()`` has NaN for the
     verifier scores of the slots that are not valid (on the device, no synchronisation): an invalid slot's verifier score
-    raises nothing in the verdict layer."""
+    raises nothing in the verdict layer.
+
+    Sessions: the part of a ``StreamState`` is ``quality_ring`` ((n, W) uint8), ``quality_state`` ((n, 3) int64: last, run,
+    bad) and ``quality_totals`` ((n, 6) int64), meta ``quality`` (format) and ``quality_window`` (W and hop); rows that
+    cannot belong to a session (a negative ``run``, ``bad > W``) are refused.  The ring holds raw flags, so ``clip``,
+    ``flat_run``, ``mask`` and ``max_bad`` may differ where the sessions go (``bad`` is recounted under the new ``mask`` at
+    the slot's next hop)."""
+
+    layer = "quality"
+    _keys = ("quality_ring", "quality_state", "quality_totals")
+    _part = "quality part (it was not exported by a QualityScorer)"
 
     def __init__(self, scorer, policy=None):
-        from .evidence import EvidenceScorer
-        from .vad import GatedScorer
-        from .verdict import VerdictScorer
-        if isinstance(scorer, (_Front, GatedScorer, VerdictScorer, EvidenceScorer, QualityScorer)):
-            raise ValueError("the quality layer goes inside the verdict layer, the gate and the fronts: "
-                             "VerdictScorer(QualityScorer(scorer, policy), ...), GatedScorer(QualityScorer(...))")
-        if not isinstance(scorer, (SlidingWindowScorer, CascadeScorer)):
-            raise ValueError("QualityScorer wraps a SlidingWindowScorer, IncrementalScorer or KVCachedScorer (or a CascadeScorer around one)")
-        policy = QualityPolicy() if policy is None else policy
-        if not isinstance(policy, QualityPolicy):
-            raise ValueError("policy: a QualityPolicy")
-        if scorer.S > MAX_ROWS:
-            raise ValueError(f"a scorer of {scorer.S} slots: one update takes at most {MAX_ROWS} rows")
-        self.scorer, self.policy = scorer, policy
-        self.quality = Quality(scorer.S, policy, scorer.hop, scorer.window, scorer.device)
+        super().__init__(scorer)
+        self.policy = QualityPolicy() if policy is None else policy
+        self.quality = Quality(scorer.S, self.policy, scorer.hop, scorer.window, scorer.device)
         self.last_meas = torch.empty(0, 8, dtype=torch.int32, device=self.quality.device)
+        self._cascade = self._below("cascade")
         self._last = None  # (slots, verifier scores with the invalid slots' made NaN) of the newest push
-
-    # ---- the surface the layers above use --------------------------------------------------------------------------------
-    @property
-    def S(self):
-        return self.scorer.S
-
-    @property
-    def device(self):
-        return self.scorer.device
-
-    @property
-    def hop(self):
-        return self.scorer.hop
-
-    @property
-    def window(self):
-        return self.scorer.window
-
-    @property
-    def samples_seen(self):
-        """(S,) int64: the samples each slot's session has seen since its last ``reset`` (the inner scorer's count)."""
-        return self.scorer.samples_seen
-
-    def _slot_list(self, slots, ordered=False):
-        return self.scorer._slot_list(slots, ordered=ordered)
 
     @property
     def valid(self):
@@ -549,10 +461,9 @@ class QualityScorer:
     def push(self, chunk, slots=None):
         """chunk and slots: the inner scorer's own rule (an fp32 chunk on the scorer's GPU) -> the inner scores with NaN
         where the slot's score is withheld, ``None`` where the inner ``push`` returned ``None``."""
-        if self.device.type != "cuda":
-            raise AfxError("hops are scored and measured on the GPU; there is no CPU fallback")
+        need_gpu(self.device, "hops are scored and measured")
         inner = self.scorer
-        idx = list(range(self.S)) if slots is None else self._slot_list(slots, ordered=True)
+        idx = self._named(slots)
         A = len(idx)
         if (not isinstance(chunk, torch.Tensor) or chunk.device != self.quality.device or chunk.dtype != torch.float32
                 or chunk.shape != (A, self.hop)):
@@ -566,7 +477,7 @@ class QualityScorer:
         if scores is not None and scores.dtype != torch.float32:
             scores = scores.to(torch.float32)
         out, self.last_meas = self.quality.update(chunk, idx, hop_index=(inner.samples_seen[idx] // self.hop).numpy(), scores=scores)
-        last = inner.last_verified() if isinstance(inner, CascadeScorer) else None
+        last = self._cascade.last_verified() if self._cascade is not None else None
         if last is not None and self.policy.abstain:
             chosen, v = last
             with torch.cuda.device(self.device):
@@ -577,48 +488,19 @@ class QualityScorer:
         self._last = last
         return out
 
-    def reset(self, slots):
-        """The named slots begin a new stream: the inner session and the quality state (the ring is left alone)."""
-        idx = self._slot_list(slots)
-        self.scorer.reset(idx)
-        self.quality.reset(idx)
-
-    # ---- sessions ------------------------------------------------------------------------------------------------------------
+    # ---- sessions (afx._layer.Layer) -----------------------------------------------------------------------------------------
     def _meta(self):
         return dict(quality=QUALITY_FORMAT, quality_window=dict(W=self.quality.W, hop=self.hop))
 
-    def state_meta(self):
-        return dict(self.scorer.state_meta(), **self._meta())
+    def _reset(self, idx):
+        self.quality.reset(idx)
 
-    def export_slots(self, slots):
-        """The inner scorer's ``StreamState`` of the named slots plus the quality layer's: ``quality_ring`` ((n, W) uint8),
-        ``quality_state`` ((n, 3) int64: last, run, bad) and ``quality_totals`` ((n, 6) int64); meta ``quality`` and
-        ``quality_window``.  No byte of the scorer changes.  The ring holds raw flags, so ``clip``, ``flat_run``, ``mask`` and
-        ``max_bad`` may differ where the sessions go (``bad`` is recounted under the new ``mask`` at the slot's next hop)."""
-        idx = self._slot_list(slots, ordered=True)
-        meta = self._meta()
-        st = self.scorer.export_slots(idx)
+    def _export(self, idx, st):
         ring, state, totals = self.quality.export_rows(idx)
-        return StreamState(dict(st.meta, **meta), st.seen, dict(st.tensors, quality_ring=ring, quality_state=state, quality_totals=totals))
+        return dict(quality_ring=ring, quality_state=state, quality_totals=totals)
 
-    def import_slots(self, slots, state):
-        """The named slots take over the sessions of ``state``, a state of a QualityScorer with the same format, W and hop
-        around the same kind of scorer; anything else, a state with no quality part, or rows that cannot belong to a
-        session (a negative ``run``, ``bad > W``), is a ValueError before anything changes."""
-        idx = self._slot_list(slots, ordered=True)
-        if not isinstance(state, StreamState):
-            raise ValueError("import_slots takes a StreamState (export_slots / StreamState.from_state_dict)")
-        mine = self._meta()
-        if any(k not in state.tensors for k in _STATE_KEYS) or any(k not in state.meta for k in mine):
-            raise ValueError("import_slots: the state has no quality part (it was not exported by a QualityScorer)")
-        for k, v in mine.items():
-            if state.meta[k] != v:
-                raise ValueError(f"import_slots: the state's {k} {state.meta[k]!r} is not this scorer's {v!r}")
-        n, t = len(state), state.tensors
-        if n != len(idx):
-            raise ValueError(f"the state holds {n} sessions for {len(idx)} named slots")
-        rows = self.quality.check_rows(t["quality_ring"], t["quality_state"], t["quality_totals"], n)
-        inner = StreamState({k: v for k, v in state.meta.items() if k not in mine}, state.seen,
-                            {k: v for k, v in t.items() if k not in _STATE_KEYS})
-        self.scorer.import_slots(idx, inner)  # (refuses a foreign state before changing anything)
+    def _check(self, state, n):
+        return self.quality.check_rows(*(state.tensors[k] for k in self._keys), n)
+
+    def _import(self, idx, rows):
         self.quality.import_rows(idx, *rows)

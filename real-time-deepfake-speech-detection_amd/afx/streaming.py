@@ -50,7 +50,6 @@ model, weights, window and hop take those sessions over (a reset of the slots, t
 bit for bit as if it had never moved, whatever the destination's number of slots and whatever its other slots hold (the
 same row-wise argument), and the other slots of the destination are untouched.
 """
-import contextlib
 import hashlib
 
 import numpy as np
@@ -58,13 +57,12 @@ import torch
 
 from . import harness
 from . import kernels as K
+from ._layer import STATE_FORMAT, StreamState, _on, peel, rows_on, sample_cols, wrap
 from ._lib import AfxError, call_on, check, lib, ptr, stream_ptr
 from .resample import FILTER_ID, TARGET_RATE, Resampler
 
 CONV_KS = [(10, 5), (3, 2), (3, 2), (3, 2), (3, 2), (2, 2), (2, 2)]
-STATE_FORMAT = 1  # StreamState layout version: import_slots refuses any other
 _META_CHECKED = ("format", "kind", "arch", "head", "dtype", "n_layers", "extractor_mode", "window", "hop", "fingerprint")
-_HOST_KEYS = ("kv_meta", "c6w")  # StreamState tensors that stay on the host whatever ``to`` is given
 
 
 def weights_fingerprint(state_dict):
@@ -87,58 +85,6 @@ def _frames5(n):
     return n
 
 
-def _on(device):
-    return torch.cuda.device(device) if device.type == "cuda" else contextlib.nullcontext()
-
-
-class StreamState:
-    """A copy of some slots' streaming sessions (``export_slots``), in the order they were named: ``seen`` (n,) samples per
-    session, ``tensors`` the per-session state (row i = session i), ``meta`` what the sessions need of a scorer to continue
-    in it (format, scorer kind, engine arch and head, dtype, layers, extractor mode, window, hop, weights fingerprint) and
-    the library build id (for information)."""
-
-    def __init__(self, meta, seen, tensors):
-        self.meta = dict(meta)
-        self.seen = torch.as_tensor(seen, dtype=torch.int64).cpu().reshape(-1)
-        self.tensors = dict(tensors)
-        for k, t in self.tensors.items():
-            if t.shape[0] != len(self):
-                raise ValueError(f"state tensor {k!r} has {t.shape[0]} rows for {len(self)} sessions")
-
-    def __len__(self):
-        return int(self.seen.numel())
-
-    def to(self, device, pin_memory=False):
-        """A copy on ``device`` ("cpu", "cuda:1", ...); pin_memory: host tensors in page-locked memory (device-to-host
-        copies without staging, host-to-device copies that can overlap)."""
-        dev = torch.device(device)
-        out = {}
-        for k, t in self.tensors.items():
-            if k in _HOST_KEYS:
-                out[k] = t
-            elif dev.type == "cpu" and pin_memory:
-                out[k] = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
-                out[k].copy_(t, non_blocking=True)
-            else:
-                out[k] = t.to(dev)
-        if dev.type == "cpu" and pin_memory:
-            for d in {t.device for t in self.tensors.values() if t.is_cuda}:
-                torch.cuda.current_stream(d).synchronize()
-        return StreamState(self.meta, self.seen, out)
-
-    def state_dict(self):
-        """Plain tensors, strings and ints (``torch.save`` / ``torch.load(weights_only=True)``)."""
-        return {"meta": dict(self.meta), "seen": self.seen.clone(), "tensors": dict(self.tensors)}
-
-    @classmethod
-    def from_state_dict(cls, d):
-        if not isinstance(d, dict) or set(d) != {"meta", "seen", "tensors"}:
-            raise ValueError("a StreamState state_dict has the keys 'meta', 'seen' and 'tensors'")
-        if d["meta"].get("format") != STATE_FORMAT:
-            raise ValueError(f"StreamState format {d['meta'].get('format')!r}, this build reads format {STATE_FORMAT}")
-        return cls(d["meta"], d["seen"], d["tensors"])
-
-
 class FeedResult:
     """What a ``feed`` / ``drain`` completed: ``counts`` (len(slots),) int64 on the host, the hops each named slot
     completed; ``scores`` (counts.sum(),) fp32 on the scorer's device, the first named slot's scores in hop order, then the
@@ -155,8 +101,10 @@ class _Front:
     """What the wrappers that stand in front of a streaming scorer share (``ResamplingScorer``, ``afx.ingest.PacketScorer``,
     ``afx.jitter.JitterScorer``): the inner ``scorer``, the ``Resampler`` of their input rate, and, for the two that take
     packets, the pending ring ((S, ring_len) fp32 of 16 kHz samples per slot, its head and fill kept on the host), the
-    pop rounds that hand its whole hops to the inner scorer, the execution of a planned call and the session moves."""
+    pop rounds that hand its whole hops to the inner scorer and the execution of a planned call.  How a front's part rides in
+    a ``StreamState`` and how the pending ring is exported, checked and imported is ``afx._layer``'s."""
 
+    layer = "front"      # (afx._layer.ORDER)
     _WORK = "resampled"  # what the device does for this front (the refusal of a scorer that has no GPU behind it)
 
     def __init__(self, scorer, input_rate):
@@ -278,52 +226,6 @@ class _Front:
                 scores = scores.index_select(0, d[toffs[-1]:toffs[-1] + 8 * base].view(torch.int64))
         return FeedResult(counts, scores)
 
-    # ---- session moves -------------------------------------------------------------------------------------------------
-    def _dev_rows(self, idx):
-        return torch.tensor(idx, dtype=torch.long, device=self.device)
-
-    def _wrap(self, st, **tensors):
-        """The inner state ``st`` with this front's tensors and meta added."""
-        return StreamState(dict(st.meta, **self._meta()), st.seen, dict(st.tensors, **tensors))
-
-    @staticmethod
-    def _peel(state, state_keys, mine, what, names=None):
-        """``state`` must be a StreamState that has the tensors ``state_keys`` and the meta of ``mine`` (this front's own,
-        equal value by value; ``names``: how a message calls a key), else a ValueError -> the inner scorer's StreamState,
-        without them."""
-        if not isinstance(state, StreamState):
-            raise ValueError("import_slots takes a StreamState (export_slots / StreamState.from_state_dict)")
-        if any(k not in state.tensors for k in state_keys) or any(k not in state.meta for k in mine):
-            raise ValueError(f"import_slots: the state has no {what}")
-        for k, v in mine.items():
-            if state.meta[k] != v:
-                raise ValueError(f"import_slots: the state's {(names or {}).get(k, k)} {state.meta[k]!r} is not this scorer's {v!r}")
-        return StreamState({k: v for k, v in state.meta.items() if k not in mine}, state.seen,
-                           {k: t for k, t in state.tensors.items() if k not in state_keys})
-
-    def _export_pending(self, idx, head, fill):
-        """-> (n, max_pending * hop) fp32: the pending samples of the slots ``idx`` (ring heads ``head``, ``fill`` samples
-        each; int64 arrays over idx), left-aligned, zeros after."""
-        with _on(self.device):
-            j = torch.arange(self.max_pending * self.hop)
-            cols = (torch.from_numpy(head)[:, None] + j) % self.ring_len
-            pend = self.ring[self._dev_rows(idx)[:, None], cols.to(self.device)]
-            return pend.masked_fill_((j[None, :] >= torch.from_numpy(fill)[:, None]).to(self.device), 0.0)
-
-    def _check_pending(self, key, pend, fill, n):
-        """The checks of an exported pending ring ``pend`` (state tensor ``key``) with ``fill`` (n,) samples per session."""
-        if pend.ndim != 2 or pend.shape[0] != n or pend.dtype != torch.float32:
-            raise ValueError(f"import_slots: {key} {tuple(pend.shape)} {pend.dtype} is not (n, pending) float32")
-        if (fill < 0).any() or (fill > pend.shape[1]).any() or (fill > self.max_pending * self.hop).any():
-            raise ValueError(f"import_slots: a session holds more pending samples than max_pending = {self.max_pending} hops "
-                             f"of {self.hop} (or than its own buffer)")
-
-    def _import_pending(self, idx, pend):
-        """The slots ``idx`` take the pending samples ``pend`` (checked), at ring head 0."""
-        with _on(self.device):
-            w = min(pend.shape[1], self.ring_len)
-            self.ring[self._dev_rows(idx), :w] = pend[:, :w].to(self.device)
-
     def _check_hist(self, h, n):
         if tuple(h.shape) != (n, self.rs.history) or h.dtype != torch.float32:
             raise ValueError(f"import_slots: resample_hist {tuple(h.shape)} {h.dtype} does not fit this scorer "
@@ -331,6 +233,8 @@ class _Front:
 
 
 class SlidingWindowScorer:
+    layer = "scorer"  # (afx._layer.ORDER; the two subclasses are the same kind)
+
     def __init__(self, model, n_streams, window=64000, hop=4000, device="cuda", state_dict=None):
         """model: anything with ``forward(batch (S, window)) -> (S, 2)`` on the GPU (an afx Engine or
         one of the drop-in ``models.*`` modules).  state_dict: the weights the model was built with, for the fingerprint
@@ -540,17 +444,9 @@ class SlidingWindowScorer:
     def _state_shapes(self, n):
         return {"samples": (n, self.window)}
 
-    def _sample_cols(self, seen):
-        """(ring columns (n, window) of each session's last min(seen, window) samples, oldest first; their count (n, 1)),
-        on the ring's device: sample i since a session's start sits at ring column i % window."""
-        dev = self.ring.device
-        m = seen.clamp(max=self.window).to(dev)[:, None]
-        j = torch.arange(self.window, device=dev)
-        return (seen.to(dev)[:, None] - m + j) % self.window, m
-
     def _export(self, idx):
         """The last min(seen, window) samples of each slot, oldest first (left-aligned, zeros after)."""
-        cols, m = self._sample_cols(self._seen[idx])
+        cols, m = sample_cols(self._seen[idx], self.window, self.ring.device)
         out = self.ring[torch.tensor(idx, device=self.ring.device)[:, None], cols]
         out.masked_fill_(torch.arange(self.window, device=out.device)[None, :] >= m, 0.0)
         return {"samples": out}
@@ -558,7 +454,7 @@ class SlidingWindowScorer:
     def _import(self, idx, st):
         """Sample i since a session's start to ring column i % window (the layout ``_store`` / ``_store_slots`` keep).  The
         whole row is written: a session younger than the window never reads the columns past its samples before it writes them."""
-        cols, _ = self._sample_cols(st.seen)
+        cols, _ = sample_cols(st.seen, self.window, self.ring.device)
         self.ring[torch.tensor(idx, device=self.ring.device)[:, None], cols] = st.tensors["samples"].to(self.ring.device)
         self._seen[idx] = st.seen
 
@@ -1077,16 +973,16 @@ class ResamplingScorer(_Front):
     def export_slots(self, slots):
         """The inner scorer's ``StreamState`` of the named slots plus their filter history."""
         idx = self.scorer._slot_list(slots, ordered=True)
-        return self._wrap(self.scorer.export_slots(idx), resample_hist=self.hist[self._dev_rows(idx)].clone())
+        return wrap(self.scorer.export_slots(idx), self._meta(), resample_hist=self.hist[rows_on(idx, self.device)].clone())
 
     def import_slots(self, slots, state):
         """The named slots take over the sessions of ``state``, a state of a ResamplingScorer at the same input rate and
         filter; anything else is a ValueError before anything changes."""
         idx = self.scorer._slot_list(slots, ordered=True)
-        inner = self._peel(state, ("resample_hist",), self._meta(), "resampler history (it was not exported by a ResamplingScorer)",
+        inner = peel(state, ("resample_hist",), self._meta(), "resampler history (it was not exported by a ResamplingScorer)",
                            names={"input_rate": "input rate"})
         h = state.tensors["resample_hist"]
         self._check_hist(h, len(state))
         self.scorer.import_slots(idx, inner)  # (refuses a foreign state before changing anything)
         if idx:
-            self.hist[self._dev_rows(idx)] = h.to(self.device)
+            self.hist[rows_on(idx, self.device)] = h.to(self.device)

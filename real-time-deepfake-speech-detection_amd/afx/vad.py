@@ -52,16 +52,11 @@ import math
 import numpy as np
 import torch
 
+from ._layer import Layer, StreamState, _on, check_pending, export_pending, import_pending, need_gpu, rows_on, upload_pairs
 from ._lib import AfxError, call_on, check, lib, ptr
-from .cascade import CascadeScorer
-from .verdict import VerdictScorer
-from .evidence import EvidenceScorer
-from .quality import QualityScorer
-from .streaming import SlidingWindowScorer, StreamState, _Front, _on
 
 GATE_FORMAT = 1  # layout of the gate part of a StreamState: import_slots refuses any other
 MAX_FRAMES = 512  # frames of a row one afx_k_gate launch takes (the library splits longer rows itself)
-_STATE_KEYS = ("gate_pending", "gate_fill", "gate_hang", "gate_inner_seen", "gate_nf")
 
 
 def frame_energies(x, frame):
@@ -201,26 +196,34 @@ def emitted(scores):
     return ~torch.isnan(scores.scores if hasattr(scores, "scores") else scores)
 
 
-class GatedScorer:
-    """``scorer`` (a SlidingWindowScorer, IncrementalScorer or KVCachedScorer, or an ``afx.cascade.CascadeScorer`` around
-    one: screen and verifier then see the same gated stream) behind a ``SpeechGate`` (default: the default gate); see the module docstring for the contract.  It presents the surface the fronts drive an inner scorer through, so
-    it goes INSIDE them: ``PacketScorer(GatedScorer(inner), 8000, "mulaw")``.
+class GatedScorer(Layer):
+    """``scorer`` (whatever stands below the gate in the stack order of ``afx._layer``; around a cascade, screen and
+    verifier then see the same gated stream) behind a ``SpeechGate`` (default: the default gate); see the module docstring
+    for the contract.  It presents the surface the fronts drive an inner scorer through, so it goes INSIDE them:
+    ``PacketScorer(GatedScorer(inner), 8000, "mulaw")``.
 
-    Per slot a ring of 2 hops of kept samples on the device: a slot holds less than one hop before a push and gains at most
-    one, so at most one hop pops.  Ring head and fill are the host's: the head moves only at pops, the fill grows by what
-    the push's one read-back says was kept."""
+    Per slot a ring of 2 hops of kept samples on the device (the fronts' pending ring with ``max_pending = 1``): a slot
+    holds less than one hop before a push and gains at most one, so at most one hop pops.  Ring head and fill are the
+    host's: the head moves only at pops, the fill grows by what the push's one read-back says was kept.
+
+    Sessions: the part of a ``StreamState`` is ``gate_pending`` ((n, hop) fp32, the kept samples waiting, left-aligned,
+    zeros after), ``gate_fill``, ``gate_hang``, ``gate_inner_seen`` ((n,) int64: pending samples, hangover frames left, the
+    inner session's samples) and ``gate_nf`` ((n,) fp32), meta ``gate`` (format) and ``gate_params``; the state's ``seen``
+    is the gate's ``samples_seen``.  Counters, a hangover or a noise floor that cannot be a gate's are refused."""
+
+    layer = "gate"
+    _keys = ("gate_pending", "gate_fill", "gate_hang", "gate_inner_seen", "gate_nf")
+    _part = "speech-gate part (it was not exported by a GatedScorer)"
+    _inner_seen = "gate_inner_seen"
 
     def __init__(self, scorer, gate=None):
-        if isinstance(scorer, (_Front, GatedScorer)):
-            raise ValueError("the gate goes inside the fronts: PacketScorer(GatedScorer(scorer), ...), not around them")
-        if not isinstance(scorer, (SlidingWindowScorer, CascadeScorer, QualityScorer, VerdictScorer, EvidenceScorer)):
-            raise ValueError("GatedScorer wraps a SlidingWindowScorer, IncrementalScorer or KVCachedScorer (or a CascadeScorer around one)")
+        super().__init__(scorer)
         gate = SpeechGate() if gate is None else gate
         if not isinstance(gate, SpeechGate):
             raise ValueError("gate: a SpeechGate")
         if scorer.hop % gate.frame:
             raise ValueError(f"a hop of {scorer.hop} samples is not a whole number of {gate.frame}-sample frames")
-        self.scorer, self.gate = scorer, gate
+        self.gate = gate
         self.ring_len = 2 * scorer.hop
         dev, S = scorer.device, scorer.S
         self.ring = torch.zeros(S, self.ring_len, dtype=torch.float32, device=dev)
@@ -229,26 +232,6 @@ class GatedScorer:
         self._head = np.zeros(S, dtype=np.int64)  # ring position of each slot's oldest pending sample (host)
         self._fill = np.zeros(S, dtype=np.int64)  # pending kept samples per slot (host), always < hop between pushes
         self._seen = np.zeros(S, dtype=np.int64)  # samples pushed per slot since its reset (host)
-
-    # ---- the surface the fronts use --------------------------------------------------------------------------------------
-    @property
-    def S(self):
-        return self.scorer.S
-
-    @property
-    def device(self):
-        return self.scorer.device
-
-    @property
-    def hop(self):
-        return self.scorer.hop
-
-    @property
-    def window(self):
-        return self.scorer.window
-
-    def _slot_list(self, slots, ordered=False):
-        return self.scorer._slot_list(slots, ordered=ordered)
 
     @property
     def samples_seen(self):
@@ -272,10 +255,9 @@ class GatedScorer:
         the order named: the inner scorer's score where this push completed a hop of the slot's gated stream, NaN where it
         did not (that slot's inner session has not moved).  One ``afx_k_gate`` launch, one read-back of A int32 (see the
         module docstring), one ``afx_k_ingest_pop`` and one inner ``push`` over the ready slots."""
-        idx = list(range(self.S)) if slots is None else self._slot_list(slots, ordered=True)
+        idx = self._named(slots)
         dev, hop, A = self.device, self.hop, len(idx)
-        if dev.type != "cuda":
-            raise AfxError("hops are gated and scored on the GPU; there is no CPU fallback")
+        need_gpu(dev, "hops are gated and scored")
         if not isinstance(chunk, torch.Tensor) or not chunk.is_cuda or chunk.dtype != torch.float32 or chunk.shape != (A, hop):
             raise ValueError(f"expected a CUDA fp32 tensor of shape {(A, hop)} (one hop per named slot)")
         if not A:
@@ -283,10 +265,9 @@ class GatedScorer:
         slot = np.asarray(idx, dtype=np.int64)
         head, fill = self._head[slot], self._fill[slot]
         with torch.cuda.device(dev):
-            hdr = torch.empty(A, 2, dtype=torch.int32, pin_memory=True)
-            hdr.numpy()[:] = np.stack([slot, (head + fill) % self.ring_len], axis=1)
+            hdr = upload_pairs(slot, (head + fill) % self.ring_len, dev)
             kept = torch.empty(A, dtype=torch.int32, device=dev)
-            self.gate._launch(chunk.to(dev).contiguous(), hdr.to(dev, non_blocking=True), self.nf, self.h, self.ring, kept)
+            self.gate._launch(chunk.to(dev).contiguous(), hdr, self.nf, self.h, self.ring, kept)
             host = torch.empty(A, dtype=torch.int32, pin_memory=True)
             host.copy_(kept, non_blocking=True)
             torch.cuda.current_stream(dev).synchronize()  # the one read-back: which slots completed a hop is in the audio
@@ -314,59 +295,36 @@ class GatedScorer:
                     out.index_copy_(0, d[2 * R:].long(), sc.to(torch.float32))
         return out
 
-    def reset(self, slots):
-        """The named slots begin a new stream: the inner session, the noise floor (``nf = inf``), the hangover, the pending
-        samples and the counters are dropped."""
-        idx = self._slot_list(slots)
-        self.scorer.reset(idx)
+    def _reset(self, idx):
+        """The noise floor (``nf = inf``), the hangover, the pending samples and the counters are dropped."""
         if idx:
             with _on(self.device):
-                rows = torch.tensor(idx, dtype=torch.long, device=self.device)
+                rows = rows_on(idx, self.device)
                 self.nf[rows] = float("inf")
                 self.h[rows] = 0
             self._head[idx] = 0
             self._fill[idx] = 0
             self._seen[idx] = 0
 
-    # ---- sessions ------------------------------------------------------------------------------------------------------------
+    # ---- sessions (afx._layer.Layer) -----------------------------------------------------------------------------------------
     def _meta(self):
         return dict(gate=GATE_FORMAT, gate_params=self.gate.params())
 
-    def state_meta(self):
-        return dict(self.scorer.state_meta(), **self._meta())
-
     def export_slots(self, slots):
-        """The inner scorer's ``StreamState`` of the named slots plus the gate's: ``gate_pending`` ((n, hop) fp32, the kept
-        samples waiting, left-aligned, zeros after), ``gate_fill``, ``gate_hang``, ``gate_inner_seen`` ((n,) int64: pending
-        samples, hangover frames left, the inner session's samples) and ``gate_nf`` ((n,) fp32), meta ``gate`` and
-        ``gate_params``.  ``seen`` is the gate's ``samples_seen``.  No byte of the scorer changes."""
-        idx = self._slot_list(slots, ordered=True)
-        st = self.scorer.export_slots(idx)
-        with _on(self.device):
-            rows = torch.tensor(idx, dtype=torch.long, device=self.device)
-            j = torch.arange(self.hop)
-            cols = (torch.from_numpy(self._head[idx])[:, None] + j) % self.ring_len
-            pend = self.ring[rows[:, None], cols.to(self.device)]
-            pend.masked_fill_((j[None, :] >= torch.from_numpy(self._fill[idx])[:, None]).to(self.device), 0.0)
-            tensors = dict(st.tensors, gate_pending=pend, gate_fill=torch.from_numpy(self._fill[idx]),
-                           gate_hang=self.h[rows].to("cpu", torch.int64), gate_inner_seen=st.seen.clone(),
-                           gate_nf=self.nf[rows].clone())
-        return StreamState(dict(st.meta, **self._meta()), torch.from_numpy(self._seen[idx]), tensors)
+        """``Layer.export_slots`` with the gate's own sample counts as the state's ``seen`` (the inner sessions' ride in
+        ``gate_inner_seen``)."""
+        st = super().export_slots(slots)
+        return StreamState(st.meta, self._seen[self._slot_list(slots, ordered=True)], st.tensors)
 
-    def import_slots(self, slots, state):
-        """The named slots take over the sessions of ``state``, a state of a GatedScorer with the same gate parameters and
-        format around the same kind of scorer; anything else, or a state whose counters, hangover or noise floor cannot be a
-        gate's, is a ValueError before anything changes."""
-        idx = self._slot_list(slots, ordered=True)
-        if not isinstance(state, StreamState):
-            raise ValueError("import_slots takes a StreamState (export_slots / StreamState.from_state_dict)")
-        mine = self._meta()
-        if any(k not in state.tensors for k in _STATE_KEYS) or any(k not in state.meta for k in mine):
-            raise ValueError("import_slots: the state has no speech-gate part (it was not exported by a GatedScorer)")
-        for k, v in mine.items():
-            if state.meta[k] != v:
-                raise ValueError(f"import_slots: the state's {k} {state.meta[k]!r} is not this scorer's {v!r}")
-        n, hop, t = len(state), self.hop, state.tensors
+    def _export(self, idx, st):
+        with _on(self.device):
+            rows = rows_on(idx, self.device)
+            return dict(gate_pending=export_pending(self.ring, idx, self._head[idx], self._fill[idx], self.hop),
+                        gate_fill=torch.from_numpy(self._fill[idx]), gate_hang=self.h[rows].to("cpu", torch.int64),
+                        gate_inner_seen=st.seen.clone(), gate_nf=self.nf[rows].clone())
+
+    def _check(self, state, n):
+        hop, t = self.hop, state.tensors
         counts = []
         for k in ("gate_fill", "gate_hang", "gate_inner_seen"):
             c = t[k].cpu().reshape(-1)
@@ -376,11 +334,12 @@ class GatedScorer:
         fill, hang, inner_seen = counts
         seen = state.seen.numpy()
         pend, nf = t["gate_pending"], t["gate_nf"]
-        if tuple(pend.shape) != (n, hop) or pend.dtype != torch.float32:
-            raise ValueError(f"import_slots: gate_pending {tuple(pend.shape)} {pend.dtype} is not {(n, hop)} float32")
+        check_pending("gate_pending", pend, fill, n, hop)
+        if pend.shape[1] != hop:
+            raise ValueError(f"import_slots: gate_pending {tuple(pend.shape)} is not {(n, hop)}")
         if tuple(nf.shape) != (n,) or nf.dtype != torch.float32:
             raise ValueError(f"import_slots: gate_nf {tuple(nf.shape)} {nf.dtype} is not {(n,)} float32")
-        if ((fill < 0) | (fill >= hop) | (fill % self.gate.frame != 0)).any():
+        if ((fill >= hop) | (fill % self.gate.frame != 0)).any():
             raise ValueError(f"import_slots: a session's pending samples are not whole {self.gate.frame}-sample frames short of a hop")
         if ((inner_seen < 0) | (seen < 0) | (inner_seen % hop != 0) | (seen % hop != 0)).any():
             raise ValueError("import_slots: a session's sample count is not a whole number of hops")
@@ -391,15 +350,16 @@ class GatedScorer:
         nf_host = nf.cpu()
         if bool(torch.isnan(nf_host).any()) or bool((nf_host < float(self.gate.nf_min)).any()):
             raise ValueError(f"import_slots: a session's noise floor is NaN or below the gate's minimum {float(self.gate.nf_min)!r}")
-        inner = StreamState({k: v for k, v in state.meta.items() if k not in mine}, torch.from_numpy(inner_seen.copy()),
-                            {k: v for k, v in t.items() if k not in _STATE_KEYS})
-        self.scorer.import_slots(idx, inner)  # (refuses a foreign state before changing anything)
+        return pend, nf, hang, fill, seen
+
+    def _import(self, idx, rows):
+        pend, nf, hang, fill, seen = rows
         if idx:
+            import_pending(self.ring, idx, pend)
             with _on(self.device):
-                rows = torch.tensor(idx, dtype=torch.long, device=self.device)
-                self.ring[rows, :hop] = pend.to(self.device)
-                self.nf[rows] = nf.to(self.device)
-                self.h[rows] = torch.from_numpy(hang).to(self.device, torch.int32)
+                dev_rows = rows_on(idx, self.device)
+                self.nf[dev_rows] = nf.to(self.device)
+                self.h[dev_rows] = torch.from_numpy(hang).to(self.device, torch.int32)
             self._head[idx] = 0
             self._fill[idx] = fill
             self._seen[idx] = seen

@@ -44,57 +44,14 @@ state always advances.  Kinds: 1 raised by the smoothed score, 2 raised by the v
 The defaults (``alpha=1``, ``confirm = release = min_scores = 1``, ``exit = enter``: a plain threshold on the raw score) are
 engineering defaults, not tuned ones: there is no labelled speech behind them, and the score is not calibrated.
 """
-import math
-
 import numpy as np
 import torch
 
-from ._lib import AfxError, call_on, check, lib, ptr
-from .cascade import CascadeScorer
-from .streaming import SlidingWindowScorer, StreamState, _Front, _on
+from ._layer import N_MAX, Layer, _on, fp32, hop_indices, integer, need_gpu, slot_count, slots_of, upload_pairs
+from ._lib import call_on, check, lib, ptr
 
 VERDICT_FORMAT = 1  # layout of the verdict part of a StreamState: import_slots refuses any other
-MAX_ROWS = 8192     # rows of one afx_k_verdict launch
-N_MAX = (1 << 31) - 1
 RAISED, RAISED_BY_VERIFIER, CLEARED = 1, 2, 3
-_STATE_KEYS = ("verdict_m", "verdict_state")
-
-
-def _integer(name, v):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-        raise ValueError(f"{name}: an integer, got {v!r}")
-    v = int(v)
-    if not 1 <= v <= N_MAX:
-        raise ValueError(f"{name} {v!r}: 1 or more (below 2^31)")
-    return v
-
-
-def _fp32(name, v):
-    """``v`` rounded to fp32 once; NaN, and a finite number that is not an fp32 number, are refused."""
-    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
-        raise ValueError(f"{name}: a number, got {v!r}")
-    if math.isnan(v):
-        raise ValueError(f"{name} is NaN")
-    with np.errstate(over="ignore"):
-        t = np.float32(v)
-    if np.isinf(t) and not math.isinf(v):
-        raise ValueError(f"{name} {v!r} is not an fp32 number")
-    return t
-
-
-def _slots(slots, S):
-    """Distinct slot indices in [0, S), in the order given (None: every slot)."""
-    if slots is None:
-        return np.arange(S, dtype=np.int64)
-    b = np.asarray(slots)
-    if b.dtype == bool or (b.size and not np.issubdtype(b.dtype, np.integer)) or b.ndim > 1:
-        raise ValueError("slots: a list of slot indices")
-    b = b.astype(np.int64).reshape(-1)
-    if b.size and (b.min() < 0 or b.max() >= S):
-        raise ValueError(f"a slot index outside 0..{S - 1}")
-    if np.unique(b).size != b.size:
-        raise ValueError("a slot is named twice")
-    return b
 
 
 class VerdictPolicy:
@@ -108,18 +65,18 @@ class VerdictPolicy:
     raises the alarm at once, whatever ``min_scores`` and ``confirm``; any other verifier score restarts the confirm run."""
 
     def __init__(self, enter, exit=None, alpha=1.0, confirm=1, release=1, min_scores=1, latch=False, verifier_enter=None):
-        self.enter32 = _fp32("enter", enter)
-        self.exit32 = self.enter32 if exit is None else _fp32("exit", exit)
+        self.enter32 = fp32("enter", enter)
+        self.exit32 = self.enter32 if exit is None else fp32("exit", exit)
         if self.exit32 < self.enter32:
             raise ValueError(f"exit {exit!r} is below enter {enter!r}")
-        self.verifier_enter32 = None if verifier_enter is None else _fp32("verifier_enter", verifier_enter)
+        self.verifier_enter32 = None if verifier_enter is None else fp32("verifier_enter", verifier_enter)
         if isinstance(alpha, bool) or not isinstance(alpha, (int, float, np.integer, np.floating)):
             raise ValueError(f"alpha: a number, got {alpha!r}")
         self.alpha32 = np.float32(alpha)
         if not (0.0 < float(alpha) <= 1.0 and self.alpha32 > 0):
             raise ValueError(f"alpha {alpha!r}: in (0, 1] (as an fp32 number)")
-        self.confirm, self.release = _integer("confirm", confirm), _integer("release", release)
-        self.min_scores = _integer("min_scores", min_scores)
+        self.confirm, self.release = integer("confirm", confirm, 1), integer("release", release, 1)
+        self.min_scores = integer("min_scores", min_scores, 1)
         if not isinstance(latch, (bool, np.bool_)):
             raise ValueError(f"latch: True or False, got {latch!r}")
         self.latch = bool(latch)
@@ -140,7 +97,7 @@ class VerdictPolicy:
         if not (isinstance(m, np.ndarray) and m.dtype == np.float32 and m.ndim == 1 and isinstance(st, np.ndarray)
                 and np.issubdtype(st.dtype, np.integer) and st.shape == (m.size, 4)):
             raise ValueError("m: a (S,) float32 array, st: a (S, 4) integer array")
-        b = _slots(slots, m.size)
+        b = slots_of(slots, m.size)
         s = np.asarray(scores, dtype=np.float32).reshape(-1)
         k = np.broadcast_to(np.asarray(hop_index, dtype=np.int64).reshape(-1), b.shape) if np.ndim(hop_index) == 0 \
             else np.asarray(hop_index, dtype=np.int64).reshape(-1)
@@ -212,13 +169,7 @@ class Verdicts:
     every few pushes."""
 
     def __init__(self, S, policy, device="cuda"):
-        if isinstance(S, bool) or not isinstance(S, (int, np.integer)) or S < 1:
-            raise ValueError(f"S {S!r}: a positive number of slots")
-        if S > MAX_ROWS:
-            raise ValueError(f"{S} slots: one update takes at most {MAX_ROWS} rows")
-        if not isinstance(policy, VerdictPolicy):
-            raise ValueError("policy: a VerdictPolicy")
-        self.S, self.policy = int(S), policy
+        self.S, self.policy = slot_count(S, policy, VerdictPolicy), policy
         self.cap = max(4 * self.S, 1024)
         m, st = new_state(self.S)
         self.m = torch.from_numpy(m).to(device)
@@ -250,16 +201,11 @@ class Verdicts:
         slot slots[i] (None: every slot, in order; the slots are distinct); hop_index: an int or (A,) ints on the host;
         verified: (A,) fp32 on the device, NaN where the verifier gave no score (ignored when the policy has no
         ``verifier_enter``).  One pinned upload, one launch, no synchronisation."""
-        b = _slots(slots, self.S)
+        b = slots_of(slots, self.S)
         A = b.size
         if not isinstance(scores, torch.Tensor) or scores.dtype != torch.float32 or scores.shape != (A,) or scores.device != self.device:
             raise ValueError(f"scores: an fp32 tensor of shape {(A,)} on {self.device}")
-        k = np.asarray(hop_index)
-        if k.dtype == bool or not np.issubdtype(k.dtype, np.integer) or k.ndim > 1 or (k.ndim == 1 and k.size != A):
-            raise ValueError(f"hop_index: an int or {A} ints")
-        k = np.broadcast_to(k.astype(np.int64).reshape(-1), (A,))
-        if A and (k.min() < 0 or k.max() > N_MAX):
-            raise ValueError("hop_index: 0 or more, below 2^31")
+        k = hop_indices(hop_index, A, 0)
         if self.policy.verifier_enter32 is None:
             verified = None
         if verified is not None and (not isinstance(verified, torch.Tensor) or verified.dtype != torch.float32
@@ -275,15 +221,12 @@ class Verdicts:
         self._pending += A
 
     def _launch(self, scores, verified, slots, hop_index):
-        if self.device.type != "cuda":
-            raise AfxError("verdicts are updated on the GPU; there is no CPU fallback")
+        need_gpu(self.device, "verdicts are updated")
         p, A = self.policy, slots.size
         if A > 1 and scores.stride(0) < 1:  # (an expanded or reversed view: the kernel reads scores[i * stride], stride >= 1)
             scores = scores.contiguous()
         with torch.cuda.device(self.device):
-            hdr = torch.empty(A, 2, dtype=torch.int32, pin_memory=True)
-            hdr.numpy()[:] = np.stack([slots, hop_index], axis=1)
-            d = hdr.to(self.device, non_blocking=True)
+            d = upload_pairs(slots, hop_index, self.device)
             check(call_on(self.m, lib().afx_k_verdict, ptr(scores), max(scores.stride(0), 1), ptr(verified), ptr(d), A, ptr(self.m),
                           ptr(self.st), self.S, p.alpha, p.enter, p.exit, 0.0 if p.verifier_enter is None else p.verifier_enter,
                           p.confirm, p.release, p.min_scores, int(p.latch), ptr(self.log), self.cap))
@@ -322,7 +265,7 @@ class Verdicts:
     # ---- sessions ------------------------------------------------------------------------------------------------------------
     def reset(self, slots):
         """The named slots begin a new stream: ``m = NaN``, ``(n, run, on, since) = (0, 0, 0, -1)``.  The log is untouched."""
-        b = _slots(slots, self.S)
+        b = slots_of(slots, self.S)
         if b.size:
             with _on(self.device):
                 rows = torch.from_numpy(b).to(self.device)
@@ -332,7 +275,7 @@ class Verdicts:
     def export_rows(self, slots):
         """-> (verdict_m (n,) fp32 on the device, verdict_state (n, 4) int64 on the host) of the named slots."""
         with _on(self.device):
-            rows = torch.from_numpy(_slots(slots, self.S)).to(self.device)
+            rows = torch.from_numpy(slots_of(slots, self.S)).to(self.device)
             return self.m[rows].clone(), self.st[rows].to("cpu", torch.int64)
 
     def check_rows(self, m, st, n):
@@ -359,7 +302,7 @@ class Verdicts:
 
     def import_rows(self, slots, m, st):
         """The named slots take the (checked) state rows."""
-        b = _slots(slots, self.S)
+        b = slots_of(slots, self.S)
         if b.size:
             with _on(self.device):
                 rows = torch.from_numpy(b).to(self.device)
@@ -367,64 +310,35 @@ class Verdicts:
                 self.st[rows] = st.to(self.device, torch.int32)
 
 
-class VerdictScorer:
-    """``scorer`` (a SlidingWindowScorer, IncrementalScorer or KVCachedScorer, or a ``CascadeScorer`` around one, or an
-    ``afx.quality.QualityScorer`` around either: its withheld scores are NaN rows, which change nothing) with the
-    verdict layer behind it under ``policy``; see the module docstring.  It presents the surface the fronts and the gate
-    drive an inner scorer through and goes where the cascade goes:
+class VerdictScorer(Layer):
+    """``scorer`` (whatever stands below the verdict layer in the stack order of ``afx._layer``; a quality layer's withheld
+    scores are NaN rows, which change nothing) with the verdict layer behind it under ``policy``; see the module docstring.
+    It presents the surface the fronts and the gate drive an inner scorer through and goes where the cascade goes:
     ``JitterScorer(GatedScorer(VerdictScorer(CascadeScorer(...), policy)), 8000, "mulaw", depth)``.
 
     ``push`` returns exactly what the inner ``push`` returns (a KV-cached ``None`` updates nothing), then updates the
-    verdicts with ``hop_index = samples_seen // hop``: one small upload and one launch, no synchronisation.  Around a
-    ``CascadeScorer`` under a policy with ``verifier_enter``, the verifier scores of this push go with it (read from the
-    cascade's ``last_verified()`` on the device; the cascade's own event log is left for its caller).
+    verdicts with ``hop_index = samples_seen // hop``: one small upload and one launch, no synchronisation.  With a
+    ``CascadeScorer`` below and a policy with ``verifier_enter``, the verifier scores of this push go with it (read from
+    the inner ``last_verified()`` on the device; the cascade's own event log is left for its caller).
 
     Results: ``alarm`` ((S,) bool), ``smoothed`` ((S,) fp32), ``alarm_since`` ((S,) int32), all on the device, and
     ``take_events()``, the only read-back.  The event log belongs to the scorer, not to a session: ``reset`` and session
-    moves leave it."""
+    moves leave it.
+
+    Sessions: the part of a ``StreamState`` is ``verdict_m`` ((n,) fp32) and ``verdict_state`` ((n, 4) int64: n, run, on,
+    since), meta ``verdict`` (format) and ``verdict_policy``; rows that cannot be a session's under this policy are
+    refused."""
+
+    layer = "verdict"
+    _keys = ("verdict_m", "verdict_state")
+    _part = "verdict part (it was not exported by a VerdictScorer)"
 
     def __init__(self, scorer, policy):
-        from .quality import QualityScorer
-        from .vad import GatedScorer
-        if isinstance(scorer, (_Front, GatedScorer, VerdictScorer)):
-            raise ValueError("the verdict layer goes inside the gate and the fronts: GatedScorer(VerdictScorer(scorer, policy)), "
-                             "PacketScorer(VerdictScorer(...), ...)")
-        if not isinstance(scorer, (SlidingWindowScorer, CascadeScorer, QualityScorer)):
-            raise ValueError("VerdictScorer wraps a SlidingWindowScorer, IncrementalScorer or KVCachedScorer (or a CascadeScorer around one, "
-                             "or a QualityScorer around either)")
-        if not isinstance(policy, VerdictPolicy):
-            raise ValueError("policy: a VerdictPolicy")
-        if scorer.S > MAX_ROWS:
-            raise ValueError(f"a scorer of {scorer.S} slots: one update takes at most {MAX_ROWS} rows")
-        self.scorer, self.policy = scorer, policy
+        super().__init__(scorer)
+        self.policy = policy
         self.verdicts = Verdicts(scorer.S, policy, scorer.device)
-        cascade = scorer.scorer if isinstance(scorer, QualityScorer) else scorer  # (the quality layer hands the verifier scores on)
-        self._verified = isinstance(cascade, CascadeScorer) and policy.verifier_enter is not None
-
-    # ---- the surface the fronts and the gate use -------------------------------------------------------------------------
-    @property
-    def S(self):
-        return self.scorer.S
-
-    @property
-    def device(self):
-        return self.scorer.device
-
-    @property
-    def hop(self):
-        return self.scorer.hop
-
-    @property
-    def window(self):
-        return self.scorer.window
-
-    @property
-    def samples_seen(self):
-        """(S,) int64: the samples each slot's session has seen since its last ``reset`` (the inner scorer's count)."""
-        return self.scorer.samples_seen
-
-    def _slot_list(self, slots, ordered=False):
-        return self.scorer._slot_list(slots, ordered=ordered)
+        # (a quality layer in between hands the verifier scores on)
+        self._verified = self._below("cascade") is not None and policy.verifier_enter is not None
 
     @property
     def alarm(self):
@@ -445,13 +359,12 @@ class VerdictScorer:
     def push(self, chunk, slots=None):
         """chunk and slots: the inner scorer's own rule -> exactly what the inner ``push`` returns; then one
         ``Verdicts.update`` over the named slots (none when the inner scorer emitted no score)."""
-        if self.device.type != "cuda":
-            raise AfxError("hops are scored and judged on the GPU; there is no CPU fallback")
+        need_gpu(self.device, "hops are scored and judged")
         inner = self.scorer
         scores = inner.push(chunk, slots)
         if scores is None:
             return None
-        idx = list(range(self.S)) if slots is None else self._slot_list(slots, ordered=True)
+        idx = self._named(slots)
         A = len(idx)
         if not A:
             return scores
@@ -470,47 +383,19 @@ class VerdictScorer:
         self.verdicts.update(scores, idx, hop_index=(inner.samples_seen[idx] // self.hop).numpy(), verified=verified)
         return scores
 
-    def reset(self, slots):
-        """The named slots begin a new stream: the inner session and the verdict state (clear, no smoothed score)."""
-        idx = self._slot_list(slots)
-        self.scorer.reset(idx)
-        self.verdicts.reset(idx)
-
-    # ---- sessions ------------------------------------------------------------------------------------------------------------
+    # ---- sessions (afx._layer.Layer) -----------------------------------------------------------------------------------------
     def _meta(self):
         return dict(verdict=VERDICT_FORMAT, verdict_policy=self.policy.params())
 
-    def state_meta(self):
-        return dict(self.scorer.state_meta(), **self._meta())
+    def _reset(self, idx):
+        self.verdicts.reset(idx)
 
-    def export_slots(self, slots):
-        """The inner scorer's ``StreamState`` of the named slots plus the verdict's: ``verdict_m`` ((n,) fp32) and
-        ``verdict_state`` ((n, 4) int64: n, run, on, since); meta ``verdict`` and ``verdict_policy``.  No byte of the scorer
-        changes; the event log does not move."""
-        idx = self._slot_list(slots, ordered=True)
-        meta = self._meta()
-        st = self.scorer.export_slots(idx)
+    def _export(self, idx, st):
         m, state = self.verdicts.export_rows(idx)
-        return StreamState(dict(st.meta, **meta), st.seen, dict(st.tensors, verdict_m=m, verdict_state=state))
+        return dict(verdict_m=m, verdict_state=state)
 
-    def import_slots(self, slots, state):
-        """The named slots take over the sessions of ``state``, a state of a VerdictScorer with the same format and policy
-        around the same kind of scorer; anything else, a state with no verdict part, or verdict rows that cannot be a
-        session's under this policy, is a ValueError before anything changes."""
-        idx = self._slot_list(slots, ordered=True)
-        if not isinstance(state, StreamState):
-            raise ValueError("import_slots takes a StreamState (export_slots / StreamState.from_state_dict)")
-        mine = self._meta()
-        if any(k not in state.tensors for k in _STATE_KEYS) or any(k not in state.meta for k in mine):
-            raise ValueError("import_slots: the state has no verdict part (it was not exported by a VerdictScorer)")
-        for k, v in mine.items():
-            if state.meta[k] != v:
-                raise ValueError(f"import_slots: the state's {k} {state.meta[k]!r} is not this scorer's {v!r}")
-        n, t = len(state), state.tensors
-        if n != len(idx):
-            raise ValueError(f"the state holds {n} sessions for {len(idx)} named slots")
-        m, st = self.verdicts.check_rows(t["verdict_m"], t["verdict_state"], n)
-        inner = StreamState({k: v for k, v in state.meta.items() if k not in mine}, state.seen,
-                            {k: v for k, v in t.items() if k not in _STATE_KEYS})
-        self.scorer.import_slots(idx, inner)  # (refuses a foreign state before changing anything)
-        self.verdicts.import_rows(idx, m, st)
+    def _check(self, state, n):
+        return self.verdicts.check_rows(state.tensors["verdict_m"], state.tensors["verdict_state"], n)
+
+    def _import(self, idx, rows):
+        self.verdicts.import_rows(idx, *rows)
