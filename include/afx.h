@@ -359,6 +359,31 @@ int afx_k_jitter_release(const float* jring, int S, int J, const int* hdr, int r
  * launches on the same stream that carry nf, h and kept through device memory: the result does not depend on the split. */
 int afx_k_gate(const float* x, int A, int n, const int* hdr, int frame, float e_floor, float ratio, float rise, int hang,
                float* nf, int* h, float* ring, int S, int ring_len, int* kept, unsigned char* mask, void* stream);
+/* Look-ahead gate (afx/vad.py LookaheadGate): onset pre-roll.  The decision per frame (energy order, speech, nf, h, keep)
+ * is afx_k_gate's, unchanged.  On top of it a delay line of `pre` frames per slot (1 <= pre <= 31).  With G the index of a
+ * frame in its stream since the reset (0, 1, ...), per frame, in stream order, after the decision above:
+ *     if (speech)   every frame now in the line is flagged
+ *     if (G >= pre) frame G - pre leaves the line; it is EMITTED iff its flag is set
+ *     frame G enters the line with flag = keep
+ * that is keep'[g] = keep[g] || any(speech[g+1 .. g+pre]): frame g is decided, and emitted if kept, while frame g + pre is
+ * processed; the newest `pre` frames of a stream are always undecided (a hop of zeros decides them: a zero frame is never
+ * speech and flags nothing).  The gated stream is the concatenation of the emitted frames, copied bit for bit.
+ * afx_k_gate_la: x, n, frame, the constants, nf, h, ring, kept as for afx_k_gate; kept[i] = the samples EMITTED by row i.
+ *     hdr (device, A x 4 int32) = slot, wpos, F, 0: F = the frames the slot was pushed since its reset (so row i holds
+ *     frames F .. F + n/frame - 1); wpos and ring_len are whole frames.
+ *     flags (S,) int32: bit (g mod pre) is the flag of delayed frame g; bits of blocks not yet filled are 0.
+ *     line (S, pre * frame) fp32: delayed frame g at block g mod pre; the delayed frames are [max(0, F - pre), F).
+ *     src (S, ring_len / frame) int32: entry w / frame = the index g of the frame emitted at ring position w.
+ *     mask, (A, n / frame) bytes or NULL: entry j = keep' of frame F - pre + j, 0 where that is negative.
+ * A new stream has F = 0 and flags = 0 (the line's contents are then never read).  A row with slot outside [0, S), wpos
+ * outside [0, ring_len) or off the frame grid, n > ring_len, F < 0 or F + n/frame >= 2^31 is skipped whole with kept[i] = 0
+ * and nothing else written.  Rows of slots not named are untouched.  ring_len a multiple of frame, at most 2^30.  Rows of
+ * more than 512 frames go in successive launches that carry nf, h, flags, line and kept through device memory: the result
+ * does not depend on the split.  Within a launch the frames that leave the line are copied out of it before any frame is
+ * stored into it (frame G enters the block frame G - pre leaves). */
+int afx_k_gate_la(const float* x, int A, int n, const int* hdr, int frame, float e_floor, float ratio, float rise, int hang,
+                  int pre, float* nf, int* h, int* flags, float* line, float* ring, int* src, int S, int ring_len, int* kept,
+                  unsigned char* mask, void* stream);
 /* Cascade (afx/cascade.py): a cheap screen scores every slot at every hop; the windows of the slots whose score looks
  * suspicious are gathered for a second model, under a per-push budget and a per-slot cooldown.  Every index comes from a
  * host-built header (device int32), nothing is allocated, all three run on `stream`.  State: hist (S, window) fp32, the

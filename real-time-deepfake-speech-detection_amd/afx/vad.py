@@ -37,11 +37,30 @@ begins in the middle of speech has set its floor from speech and is kept only fr
 (the floor follows the dip down at once and climbs back by ``rise`` per frame).  The defaults are engineering defaults,
 not tuned on data: there is no speech corpus in this repository.
 
+Onset pre-roll by look-ahead (``LookaheadGate``; also stated in include/afx.h, afx_k_gate_la).  The plain gate hands the
+model every talk spurt with its first consonant cut at a frame edge.  ``LookaheadGate(floor, ratio, rise, hang, frame, pre)``
+has one more parameter, ``pre``: frames of pre-roll, 1 <= pre <= 31, default 5 = 50 ms (an engineering default too).  The
+decision per frame above is unchanged -- the energy order, ``speech``, the ``nf`` update, ``h`` and ``keep``.  On top of it
+sits a delay line of ``pre`` frames per stream.  With G the index of a frame in its stream since the reset (0, 1, ...),
+after the decision::
+
+    if speech:      every frame now in the line is flagged
+    if G >= pre:    frame G - pre leaves the line; it is EMITTED iff its flag is set
+    frame G enters the line with flag = keep
+
+Equivalently ``keep'[g] = keep[g] or any(speech[g+1 .. g+pre])``: frame g is decided, and emitted if kept, while frame
+g + pre is processed.  The gated stream G' is the concatenation of the emitted frames, copied bit for bit.  The newest ``pre``
+frames of a stream are always undecided, and a push of n frames decides at most n, so a slot still gains at most one hop
+per push.  Every emitted frame carries its source index g (``GatedScorer.last_span``): scores, verdict events and clips
+count hops of the gated stream, and with look-ahead the emission also lags the input, so only the kernel that copies the
+frames can say where in the call a scored hop came from.  ``reset`` drops the line.  A caller that wants the tail of a
+finished call decided pushes one hop of zeros: zero frames are never speech, so they flag nothing.
+
 The contract of ``GatedScorer``: for a slot, let R be the concatenation of the hops it was pushed since its reset and G its
-gated stream.  The slot's j-th non-NaN score equals, bit for bit, score j of a fresh inner scorer of the same kind pushed G
-hop by hop, and it is emitted by the push in which sample ``(j + 1) * hop - 1`` of G was kept.  Nothing depends on the other
-slots, on the order or subsets in which slots are named, or on session moves.  Behind a front, R is what that front's
-contract defines it to be.
+gated stream (G' with a ``LookaheadGate``).  The slot's j-th non-NaN score equals, bit for bit, score j of a fresh inner
+scorer of the same kind pushed G hop by hop, and it is emitted by the push in which sample ``(j + 1) * hop - 1`` of G was
+kept (emitted from the delay line).  Nothing depends on the other slots, on the order or subsets in which slots are named,
+or on session moves.  Behind a front, R is what that front's contract defines it to be.
 
 The one read-back.  Which slots advance depends on the audio, so a push copies ``kept`` (one int32 per named slot) to pinned
 host memory and waits for it: A x 4 bytes once per hop.  Everything else (ring heads, fills, counters) is host arithmetic
@@ -116,31 +135,34 @@ class SpeechGate:
         return {"nf": np.float32(np.inf), "h": 0}
 
     # ---- the numpy restatement -------------------------------------------------------------------------------------------
+    def _decide(self, x, st):
+        """The per-frame decision over x (whole frames) from the state st -> (frames (m, frame), speech, keep, nf, h)."""
+        x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+        if x.size % self.frame:
+            raise ValueError(f"{x.size} samples are not whole frames of {self.frame}")
+        nf, h = np.float32(st["nf"]), int(st["h"])
+        E_floor, ratio, rise, nf_min, inf = self.E_floor, self.ratio32, self.rise32, self.nf_min, np.float32(np.inf)
+        e_all = frame_energies(x, self.frame)
+        speech, keep = np.zeros(e_all.size, dtype=bool), np.zeros(e_all.size, dtype=bool)
+        with np.errstate(over="ignore"):
+            for f, e in enumerate(e_all):
+                fin = bool(e < inf)
+                speech[f] = fin and bool(e > max(E_floor, np.float32(ratio * nf)))
+                if fin:
+                    nf = max(nf_min, min(e, np.float32(nf * rise)))
+                if speech[f]:
+                    h = self.hang
+                keep[f] = speech[f] or h > 0
+                if not speech[f] and h > 0:
+                    h -= 1
+        return x.reshape(-1, self.frame), speech, keep, np.float32(nf), h
+
     def gate_reference(self, x, state=None):
         """The function in numpy.  x: host fp32 array of whole frames (1-D, a multiple of ``frame`` samples); state: what an
         earlier call returned (None: a new stream; it is not modified) -> (keep_mask (frames,) bool, the kept samples, the
         state after x).  Chunked at any frame boundaries with the state carried it gives what the whole stream gives."""
-        x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
-        if x.size % self.frame:
-            raise ValueError(f"{x.size} samples are not whole frames of {self.frame}")
-        st = self.new_state() if state is None else state
-        nf, h = np.float32(st["nf"]), int(st["h"])
-        E_floor, ratio, rise, nf_min, inf = self.E_floor, self.ratio32, self.rise32, self.nf_min, np.float32(np.inf)
-        e_all = frame_energies(x, self.frame)
-        keep = np.zeros(e_all.size, dtype=bool)
-        with np.errstate(over="ignore"):
-            for f, e in enumerate(e_all):
-                fin = bool(e < inf)
-                speech = fin and bool(e > max(E_floor, np.float32(ratio * nf)))
-                if fin:
-                    nf = max(nf_min, min(e, np.float32(nf * rise)))
-                if speech:
-                    h = self.hang
-                keep[f] = speech or h > 0
-                if not speech and h > 0:
-                    h -= 1
-        kept = x.reshape(-1, self.frame)[keep].reshape(-1).copy()
-        return keep, kept, {"nf": np.float32(nf), "h": h}
+        frames, _, keep, nf, h = self._decide(x, self.new_state() if state is None else state)
+        return keep, frames[keep].reshape(-1).copy(), {"nf": nf, "h": h}
 
     # ---- the device form ---------------------------------------------------------------------------------------------------
     def _launch(self, x, hdr, nf, h, ring, kept, mask=None):
@@ -190,6 +212,101 @@ class SpeechGate:
         return (out, masks) if return_mask else out
 
 
+class LookaheadGate(SpeechGate):
+    """The gate with ``pre`` frames of onset pre-roll by look-ahead (1 <= pre <= 31, default 5 = 50 ms); see the module
+    docstring for the function.  ``GatedScorer(scorer, LookaheadGate(...))`` runs it streamed."""
+
+    def __init__(self, floor=1e-6, ratio=8.0, rise=1.01, hang=20, frame=160, pre=5):
+        super().__init__(floor, ratio, rise, hang, frame)
+        self.pre = _number("pre", pre, integer=True)
+        if not 1 <= self.pre <= 31:
+            raise ValueError(f"pre {pre!r}: 1 to 31 frames of pre-roll")
+
+    def params(self):
+        return dict(super().params(), pre=self.pre)
+
+    def new_state(self):
+        """A new stream: the plain gate's state, an empty delay line (``line`` (d, frame) fp32, the d <= pre delayed
+        frames, oldest first; ``flags`` (d,) bool) and ``F`` = 0 frames seen."""
+        return {"nf": np.float32(np.inf), "h": 0, "line": np.zeros((0, self.frame), dtype=np.float32),
+                "flags": np.zeros(0, dtype=bool), "F": 0}
+
+    def gate_reference(self, x, state=None):
+        """The function in numpy.  x: host fp32 array of whole frames; state: what an earlier call returned (None: a new
+        stream; it is not modified) -> (keep' of the frames this chunk DECIDED, (decided,) bool: frames max(0, F - pre) ..
+        F + frames - pre - 1 of the stream; the emitted samples; their source indices, int64; the state after x).
+        Chunked at any frame boundaries with the state carried it gives what the whole stream gives."""
+        st = self.new_state() if state is None else state
+        frames, speech, keep, nf, h = self._decide(x, st)
+        F, d = int(st["F"]), len(st["flags"])  # d = min(F, pre) frames are delayed
+        both = np.concatenate([np.asarray(st["line"], dtype=np.float32).reshape(d, self.frame), frames])
+        flags = np.concatenate([np.asarray(st["flags"], dtype=bool), keep])
+        for j in np.flatnonzero(speech):  # chunk frame j sits at d + j: the line then holds the (up to) pre frames before it
+            flags[max(0, d + j - self.pre):d + j] = True
+        decided = max(0, d + frames.shape[0] - self.pre)
+        mask = flags[:decided].copy()
+        sources = (F - d + np.flatnonzero(mask)).astype(np.int64)
+        new = {"nf": nf, "h": h, "line": both[decided:].copy(), "flags": flags[decided:].copy(), "F": F + frames.shape[0]}
+        return mask, both[:decided][mask].reshape(-1).copy(), sources, new
+
+    # ---- the device form ---------------------------------------------------------------------------------------------------
+    def _launch_la(self, x, hdr, nf, h, flags, line, ring, src, kept, mask=None):
+        """afx_k_gate_la over the rows of x ((A, n) fp32 on the GPU, contiguous; hdr (A, 4)) with this gate's constants."""
+        check(call_on(x, lib().afx_k_gate_la, ptr(x), x.shape[0], x.shape[1], ptr(hdr), self.frame, float(self.E_floor),
+                      float(self.ratio32), float(self.rise32), self.hang, self.pre, ptr(nf), ptr(h), ptr(flags), ptr(line),
+                      ptr(ring), ptr(src), ring.shape[0], ring.shape[1], ptr(kept), ptr(mask)))
+
+    def gate(self, clips, return_mask=False, return_sources=False):
+        """The offline form: ``afx_k_gate_la`` over whole clips, each with fresh state and ``pre`` zero frames appended so
+        that every real frame is decided (zero frames flag nothing and never leave the line).  clips as for
+        ``SpeechGate.gate`` -> the list of gated-audio tensors; with ``return_mask`` also the list of per-frame bool masks
+        (keep' of every real frame), with ``return_sources`` also the list of int64 tensors of the emitted frames' indices.
+        Trailing samples short of a whole frame are dropped."""
+        clips = list(clips.unbind(0)) if isinstance(clips, torch.Tensor) and clips.ndim == 2 else list(clips)
+        for c in clips:
+            if not isinstance(c, torch.Tensor) or c.ndim != 1 or c.dtype != torch.float32:
+                raise ValueError("gate: a list of 1-D fp32 tensors or a (B, n) tensor")
+            if not c.is_cuda:
+                raise AfxError("the gate runs on the GPU; there is no CPU fallback (gate_reference is the numpy restatement)")
+        out, masks, srcs = [None] * len(clips), [None] * len(clips), [None] * len(clips)
+        groups = {}
+        for i, c in enumerate(clips):
+            groups.setdefault((c.device, c.numel() // self.frame), []).append(i)
+        for (dev, frames), rows in groups.items():
+            if frames == 0:
+                for i in rows:
+                    out[i] = torch.empty(0, dtype=torch.float32, device=dev)
+                    masks[i] = torch.zeros(0, dtype=torch.bool, device=dev)
+                    srcs[i] = torch.zeros(0, dtype=torch.int64, device=dev)
+                continue
+            n, total = frames * self.frame, frames + self.pre
+            with torch.cuda.device(dev):
+                for lo in range(0, len(rows), 65535):
+                    part = rows[lo:lo + 65535]
+                    A = len(part)
+                    x = torch.zeros(A, total * self.frame, dtype=torch.float32, device=dev)
+                    x[:, :n] = torch.stack([clips[i][:n] for i in part])
+                    hdr = torch.zeros(A, 4, dtype=torch.int32)
+                    hdr[:, 0] = torch.arange(A, dtype=torch.int32)
+                    hdr = hdr.to(dev)
+                    nf = torch.full((A,), float("inf"), dtype=torch.float32, device=dev)
+                    h = torch.zeros(A, dtype=torch.int32, device=dev)
+                    flags = torch.zeros(A, dtype=torch.int32, device=dev)
+                    line = torch.empty(A, self.pre * self.frame, dtype=torch.float32, device=dev)
+                    ring = torch.empty(A, total * self.frame, dtype=torch.float32, device=dev)
+                    src = torch.full((A, total), -1, dtype=torch.int32, device=dev)
+                    kept = torch.zeros(A, dtype=torch.int32, device=dev)
+                    mask = torch.zeros(A, total, dtype=torch.uint8, device=dev) if return_mask else None
+                    self._launch_la(x, hdr, nf, h, flags, line, ring, src, kept, mask)
+                    for r, (i, k) in enumerate(zip(part, kept.tolist())):
+                        out[i] = ring[r, :k].clone()
+                        srcs[i] = src[r, :k // self.frame].long()
+                        if return_mask:
+                            masks[i] = mask[r, self.pre:].bool()  # (entry j is the frame j - pre)
+        res = (out,) + ((masks,) if return_mask else ()) + ((srcs,) if return_sources else ())
+        return res if len(res) > 1 else out
+
+
 def emitted(scores):
     """``GatedScorer.push``'s result (or a FeedResult of a front around it) -> bool tensor: which entries are scores (a NaN
     stands for a push that completed no hop of speech)."""
@@ -209,7 +326,17 @@ class GatedScorer(Layer):
     Sessions: the part of a ``StreamState`` is ``gate_pending`` ((n, hop) fp32, the kept samples waiting, left-aligned,
     zeros after), ``gate_fill``, ``gate_hang``, ``gate_inner_seen`` ((n,) int64: pending samples, hangover frames left, the
     inner session's samples) and ``gate_nf`` ((n,) fp32), meta ``gate`` (format) and ``gate_params``; the state's ``seen``
-    is the gate's ``samples_seen``.  Counters, a hangover or a noise floor that cannot be a gate's are refused."""
+    is the gate's ``samples_seen``.  Counters, a hangover or a noise floor that cannot be a gate's are refused.
+
+    With a ``LookaheadGate`` the push launches ``afx_k_gate_la`` (state ``flags``, ``line``, ``src``; F = samples_seen /
+    frame is host arithmetic) and sets ``last_span``: (A, 2) int64 on the device, in the row order of the newest push,
+    [first source sample, one past the last source sample) of the hop that push completed, counted in the gate's input
+    stream since the reset, and (-1, -1) where none completed -- read from ``src`` by device indexing, no synchronisation
+    (with a plain gate it stays None).  A session's part then gains ``gate_line`` ((n, pre * frame) fp32, the delayed
+    frames, oldest first, zero frames in front where fewer than ``pre`` are delayed), ``gate_flags`` ((n,) int64, bit j =
+    the j-th oldest delayed frame's flag) and ``gate_sources`` ((n, hop / frame) int64, the pending frames' source
+    indices, -1 after the fill); flags beyond the delayed frames and sources that are not strictly increasing below the
+    oldest delayed frame are refused.  A plain-gate state and a look-ahead state refuse each other (``gate_params``)."""
 
     layer = "gate"
     _keys = ("gate_pending", "gate_fill", "gate_hang", "gate_inner_seen", "gate_nf")
@@ -232,6 +359,13 @@ class GatedScorer(Layer):
         self._head = np.zeros(S, dtype=np.int64)  # ring position of each slot's oldest pending sample (host)
         self._fill = np.zeros(S, dtype=np.int64)  # pending kept samples per slot (host), always < hop between pushes
         self._seen = np.zeros(S, dtype=np.int64)  # samples pushed per slot since its reset (host)
+        self._la = isinstance(gate, LookaheadGate)
+        self.last_span = None
+        if self._la:
+            self._keys = GatedScorer._keys + ("gate_line", "gate_flags", "gate_sources")
+            self.flags = torch.zeros(S, dtype=torch.int32, device=dev)
+            self.line = torch.zeros(S, gate.pre * gate.frame, dtype=torch.float32, device=dev)
+            self.src = torch.full((S, self.ring_len // gate.frame), -1, dtype=torch.int32, device=dev)
 
     @property
     def samples_seen(self):
@@ -260,14 +394,26 @@ class GatedScorer(Layer):
         need_gpu(dev, "hops are gated and scored")
         if not isinstance(chunk, torch.Tensor) or not chunk.is_cuda or chunk.dtype != torch.float32 or chunk.shape != (A, hop):
             raise ValueError(f"expected a CUDA fp32 tensor of shape {(A, hop)} (one hop per named slot)")
+        la, frame = self._la, self.gate.frame
         if not A:
+            if la:
+                self.last_span = torch.empty(0, 2, dtype=torch.int64, device=dev)
             return torch.empty(0, dtype=torch.float32, device=dev)
         slot = np.asarray(idx, dtype=np.int64)
         head, fill = self._head[slot], self._fill[slot]
+        if la and (self._seen[slot] + hop >= frame << 31).any():
+            raise ValueError("a slot has seen 2^31 frames since its reset: reset it")
         with torch.cuda.device(dev):
-            hdr = upload_pairs(slot, (head + fill) % self.ring_len, dev)
             kept = torch.empty(A, dtype=torch.int32, device=dev)
-            self.gate._launch(chunk.to(dev).contiguous(), hdr, self.nf, self.h, self.ring, kept)
+            if la:
+                hdr = torch.zeros(A, 4, dtype=torch.int32, pin_memory=True)
+                hdr.numpy()[:, :3] = np.stack([slot, (head + fill) % self.ring_len, self._seen[slot] // frame], axis=1)
+                self.gate._launch_la(chunk.to(dev).contiguous(), hdr.to(dev, non_blocking=True), self.nf, self.h, self.flags,
+                                     self.line, self.ring, self.src, kept)
+                span = torch.full((A, 2), -1, dtype=torch.int64, device=dev)
+            else:
+                hdr = upload_pairs(slot, (head + fill) % self.ring_len, dev)
+                self.gate._launch(chunk.to(dev).contiguous(), hdr, self.nf, self.h, self.ring, kept)
             host = torch.empty(A, dtype=torch.int32, pin_memory=True)
             host.copy_(kept, non_blocking=True)
             torch.cuda.current_stream(dev).synchronize()  # the one read-back: which slots completed a hop is in the audio
@@ -278,9 +424,13 @@ class GatedScorer(Layer):
             rows = np.flatnonzero(fill >= hop)
             if rows.size:
                 R = rows.size
-                tab = torch.empty(3 * R, dtype=torch.int32, pin_memory=True)  # the pop table (slot, head), then the result rows
+                # the pop table (slot, head), then the result rows (look-ahead: and the src entries of each hop's ends)
+                tab = torch.empty((5 if la else 3) * R, dtype=torch.int32, pin_memory=True)
                 tab.numpy()[:2 * R] = np.stack([slot[rows], head[rows]], axis=1).reshape(-1)
-                tab.numpy()[2 * R:] = rows
+                tab.numpy()[2 * R:3 * R] = rows
+                if la:
+                    tab.numpy()[3 * R:4 * R] = head[rows] // frame
+                    tab.numpy()[4 * R:] = ((head[rows] + hop) // frame - 1) % (self.ring_len // frame)
                 d = tab.to(dev, non_blocking=True)
                 ready = torch.empty(R, hop, dtype=torch.float32, device=dev)
                 check(call_on(self.ring, lib().afx_k_ingest_pop, ptr(self.ring), self.S, self.ring_len, ptr(d), R, hop, ptr(ready)))
@@ -292,7 +442,14 @@ class GatedScorer(Layer):
                 if R == A:
                     out = sc.to(torch.float32)
                 else:
-                    out.index_copy_(0, d[2 * R:].long(), sc.to(torch.float32))
+                    out.index_copy_(0, d[2 * R:3 * R].long(), sc.to(torch.float32))
+                if la:
+                    of = self.src[d[:2 * R:2].long()]  # (R, ring_len / frame): the popped slots' source indices
+                    ends = torch.stack([of.gather(1, d[3 * R:4 * R].long()[:, None])[:, 0],
+                                        of.gather(1, d[4 * R:].long()[:, None])[:, 0] + 1], dim=1)
+                    span.index_copy_(0, d[2 * R:3 * R].long(), ends.long() * frame)
+            if la:
+                self.last_span = span
         return out
 
     def _reset(self, idx):
@@ -302,6 +459,9 @@ class GatedScorer(Layer):
                 rows = rows_on(idx, self.device)
                 self.nf[rows] = float("inf")
                 self.h[rows] = 0
+                if self._la:
+                    self.flags[rows] = 0
+                    self.src[rows] = -1
             self._head[idx] = 0
             self._fill[idx] = 0
             self._seen[idx] = 0
@@ -319,9 +479,34 @@ class GatedScorer(Layer):
     def _export(self, idx, st):
         with _on(self.device):
             rows = rows_on(idx, self.device)
-            return dict(gate_pending=export_pending(self.ring, idx, self._head[idx], self._fill[idx], self.hop),
+            part = dict(gate_pending=export_pending(self.ring, idx, self._head[idx], self._fill[idx], self.hop),
                         gate_fill=torch.from_numpy(self._fill[idx]), gate_hang=self.h[rows].to("cpu", torch.int64),
                         gate_inner_seen=st.seen.clone(), gate_nf=self.nf[rows].clone())
+            if self._la:
+                part.update(self._export_line(idx, rows))
+            return part
+
+    def _delayed(self, seen):
+        """seen: (n,) samples per session -> (F frames seen, d = min(F, pre) frames delayed, the line block of the exported
+        block c (n, pre): exported block c holds frame F - pre + c, which sits at block (F + c) mod pre)."""
+        F = np.asarray(seen, dtype=np.int64) // self.gate.frame
+        return F, np.minimum(F, self.gate.pre), (F[:, None] + np.arange(self.gate.pre)) % self.gate.pre
+
+    def _export_line(self, idx, rows):
+        pre, frame, dev, n = self.gate.pre, self.gate.frame, self.device, len(idx)
+        F, d, block = self._delayed(self._seen[idx])
+        c = np.arange(pre)
+        line = self.line.view(self.S, pre, frame)[rows[:, None], torch.from_numpy(block).to(dev)]
+        line = line.masked_fill_(torch.from_numpy(c[None, :] < (pre - d)[:, None]).to(dev)[:, :, None], 0.0)
+        dev_flags = self.flags[rows].cpu().numpy().astype(np.int64)
+        bits = (dev_flags[:, None] >> block) & (c[None, :] >= (pre - d)[:, None])  # by exported block c; the j-th oldest is c = pre - d + j
+        flags = np.array([sum(int(bits[i, pre - d[i] + j]) << j for j in range(d[i])) for i in range(n)], dtype=np.int64)
+        per = self.hop // frame
+        j = np.arange(per)
+        ent = (self._head[idx][:, None] // frame + j) % (self.ring_len // frame)
+        sources = self.src[rows[:, None], torch.from_numpy(ent).to(dev)].to("cpu", torch.int64)
+        sources[torch.from_numpy(j[None, :] >= (self._fill[idx] // frame)[:, None])] = -1
+        return dict(gate_line=line.reshape(n, pre * frame), gate_flags=torch.from_numpy(flags), gate_sources=sources)
 
     def _check(self, state, n):
         hop, t = self.hop, state.tensors
@@ -350,16 +535,48 @@ class GatedScorer(Layer):
         nf_host = nf.cpu()
         if bool(torch.isnan(nf_host).any()) or bool((nf_host < float(self.gate.nf_min)).any()):
             raise ValueError(f"import_slots: a session's noise floor is NaN or below the gate's minimum {float(self.gate.nf_min)!r}")
-        return pend, nf, hang, fill, seen
+        return (pend, nf, hang, fill, seen) + (self._check_line(t, n, fill, seen) if self._la else ())
+
+    def _check_line(self, t, n, fill, seen):
+        pre, frame, per = self.gate.pre, self.gate.frame, self.hop // self.gate.frame
+        line, flags, sources = t["gate_line"], t["gate_flags"], t["gate_sources"]
+        if tuple(line.shape) != (n, pre * frame) or line.dtype != torch.float32:
+            raise ValueError(f"import_slots: gate_line {tuple(line.shape)} {line.dtype} is not {(n, pre * frame)} float32")
+        if flags.dtype != torch.int64 or tuple(flags.shape) != (n,):
+            raise ValueError("import_slots: gate_flags is (n,) int64")
+        if sources.dtype != torch.int64 or tuple(sources.shape) != (n, per):
+            raise ValueError(f"import_slots: gate_sources is {(n, per)} int64")
+        F, d, block = self._delayed(seen)
+        fl, so = flags.cpu().numpy(), sources.cpu().numpy()
+        if ((fl < 0) | ((fl >> d) != 0)).any():
+            raise ValueError("import_slots: a session flags a frame beyond those its delay line holds")
+        pending = np.arange(per)[None, :] < (fill // frame)[:, None]
+        if (so[~pending] != -1).any():
+            raise ValueError("import_slots: gate_sources is -1 after a session's pending frames")
+        if (((so < 0) | (so >= (F - d)[:, None])) & pending).any():
+            raise ValueError("import_slots: a pending frame's source index is not below the session's oldest delayed frame")
+        if ((np.diff(so, axis=1) <= 0) & pending[:, 1:]).any():
+            raise ValueError("import_slots: a session's pending source indices are not strictly increasing")
+        dev_flags = np.array([sum(((int(fl[i]) >> j) & 1) << int(block[i, pre - d[i] + j]) for j in range(d[i])) for i in range(n)],
+                             dtype=np.int32)
+        return line, dev_flags, block, sources
 
     def _import(self, idx, rows):
-        pend, nf, hang, fill, seen = rows
+        pend, nf, hang, fill, seen = rows[:5]
         if idx:
             import_pending(self.ring, idx, pend)
             with _on(self.device):
                 dev_rows = rows_on(idx, self.device)
                 self.nf[dev_rows] = nf.to(self.device)
                 self.h[dev_rows] = torch.from_numpy(hang).to(self.device, torch.int32)
+                if self._la:
+                    line, dev_flags, block, sources = rows[5:]
+                    pre, frame, dev = self.gate.pre, self.gate.frame, self.device
+                    self.line.view(self.S, pre, frame)[dev_rows[:, None], torch.from_numpy(block).to(dev)] = \
+                        line.reshape(len(idx), pre, frame).to(dev)
+                    self.flags[dev_rows] = torch.from_numpy(dev_flags).to(dev)
+                    self.src[dev_rows] = -1
+                    self.src[dev_rows, :sources.shape[1]] = sources.to(dev, torch.int32)
             self._head[idx] = 0
             self._fill[idx] = fill
             self._seen[idx] = seen

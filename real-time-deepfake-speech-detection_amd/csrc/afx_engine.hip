@@ -2905,6 +2905,12 @@ extern "C" int afx_k_gate(const float* x, int A, int n, const int* hdr, int fram
   KRET(launch_gate(x, A, n, hdr, frame, e_floor, ratio, rise, hang, nf, h, ring, S, ring_len, kept, mask,
                    (hipStream_t)stream));
 }
+extern "C" int afx_k_gate_la(const float* x, int A, int n, const int* hdr, int frame, float e_floor, float ratio, float rise,
+                             int hang, int pre, float* nf, int* h, int* flags, float* line, float* ring, int* src, int S,
+                             int ring_len, int* kept, unsigned char* mask, void* stream) {
+  KRET(launch_gate_la(x, A, n, hdr, frame, e_floor, ratio, rise, hang, pre, nf, h, flags, line, ring, src, S, ring_len, kept,
+                      mask, (hipStream_t)stream));
+}
 extern "C" int afx_k_cascade_store(const float* x, int A, int hop, const int* hdr, float* hist, int S, int window,
                                    void* stream) {
   KRET(launch_cascade_store(x, A, hop, hdr, hist, S, window, (hipStream_t)stream));

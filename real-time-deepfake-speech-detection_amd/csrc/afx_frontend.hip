@@ -1246,6 +1246,132 @@ const char* launch_gate(const float* x, int A, int n, const int* hdr, int frame,
 }
 
 // ---------------------------------------------------------------------------------
+// Look-ahead gate (afx/vad.py LookaheadGate; the function is stated in include/afx.h afx_k_gate_la): the plain gate's
+// decision per frame, behind a delay line of `pre` frames per slot.  Frame G (counted from the slot's reset) enters the line
+// with flag = keep; a speech frame flags every frame then in the line; frame G - pre leaves while frame G is processed and
+// is emitted into the pending ring iff its flag is set, with its index G - pre recorded in src.  One workgroup per row, the
+// phases of gate_kernel: energies to LDS; thread 0 runs the recurrence and writes, per frame of the launch, the offset of
+// the frame that LEAVES (-1: none, or dropped); the waves copy.  Two hazards:
+//   block reuse: frame G - pre leaves from the line block (G mod pre) that frame G enters.  A launch therefore copies the
+//      leaving frames that an earlier launch stored (the first min(pre, nframes) steps) out of the line, then a barrier,
+//      and only then stores its own last min(pre, nframes) frames into the line.  A frame that enters and leaves within one
+//      launch is copied from x directly and never touches the line;
+//   rows longer than GATE_MAX_FRAMES: launch_gate_la splits them into successive launches, each complete in itself (it
+//      leaves its last frames in the line, flags in flags, nf, h and the samples emitted so far in kept), so the next finds
+//      everything in device memory and the result does not depend on the split.
+// wpos and ring_len are whole frames, so no frame straddles the ring's wrap.
+// ---------------------------------------------------------------------------------
+struct GateLaArgs {
+  const float* x;    // (A, n) samples, row i = the next n samples of slot hdr[i][0]
+  const int* hdr;    // (A, 4): slot, wpos, F (frames the slot was pushed before this row), 0
+  float* nf;         // (S,) noise floor per slot
+  int* h;            // (S,) hangover frames left per slot
+  int* flags;        // (S,) bit (g mod pre): the flag of delayed frame g
+  float* line;       // (S, pre * frame) delayed frame g at block g mod pre
+  float* ring;       // (S, ring_len)
+  int* src;          // (S, ring_len / frame) source index of the frame at ring position w, at entry w / frame
+  int* kept;         // (A,) samples emitted of each row
+  unsigned char* mask;  // (A, n / frame) entry j: keep' of source frame F - pre + j (0 where negative), or nullptr
+  int n, frame, f0, nframes, pre;  // this launch: frames [f0, f0 + nframes) of the n / frame of a row
+  int S, ring_len, hang;
+  float e_floor, ratio, rise, nf_min;
+};
+
+__global__ __launch_bounds__(256) void gate_la_kernel(GateLaArgs a) {
+  __shared__ float s_e[GATE_MAX_FRAMES];
+  __shared__ int s_off[GATE_MAX_FRAMES];  // offset, among this launch's emitted samples, of the frame leaving at step j; -1: none
+  __shared__ int s_base;                  // samples of the row emitted by the launches before this one
+  const int row = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int slot = a.hdr[4 * row], wpos = a.hdr[4 * row + 1], F = a.hdr[4 * row + 2];
+  const int frames = a.n / a.frame;
+  if (!(slot >= 0 && slot < a.S && wpos >= 0 && wpos < a.ring_len && wpos % a.frame == 0 && a.n <= a.ring_len && F >= 0 &&
+        F <= 0x7fffffff - frames)) {
+    if (tid == 0 && a.f0 == 0) a.kept[row] = 0;
+    return;
+  }
+  const int G0 = F + a.f0, pre = a.pre;  // the index of this launch's first frame
+  const float* x = a.x + (long long)row * a.n + (long long)a.f0 * a.frame;
+  for (int f = wave; f < a.nframes; f += 4) {
+    const float e = gate_frame_energy(x + (long long)f * a.frame, a.frame, lane);
+    if (lane == 0) s_e[f] = e;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    float nf = a.nf[slot];
+    int h = a.h[slot], off = 0, b = G0 % pre;  // b = G mod pre: the block frame G enters and frame G - pre leaves
+    unsigned fl = (unsigned)a.flags[slot];
+    const unsigned all = (1u << pre) - 1u;
+    for (int f = 0; f < a.nframes; ++f) {
+      const int G = G0 + f;
+      const float e = s_e[f];
+      const bool fin = e < INFINITY;  // (false for a NaN too)
+      const bool speech = fin && e > fmaxf(a.e_floor, a.ratio * nf);
+      if (fin) nf = fmaxf(a.nf_min, fminf(e, nf * a.rise));
+      if (speech) h = a.hang;
+      const bool keep = speech || h > 0;
+      if (!speech && h > 0) --h;
+      if (speech) fl = G >= pre ? all : (1u << G) - 1u;  // every frame now in the line (blocks not yet filled stay 0)
+      const bool out = G >= pre && ((fl >> b) & 1u);
+      s_off[f] = out ? off : -1;
+      if (out) off += a.frame;
+      fl = (fl & ~(1u << b)) | ((unsigned)keep << b);
+      if (a.mask) a.mask[(long long)row * frames + a.f0 + f] = out;
+      b = b + 1 == pre ? 0 : b + 1;
+    }
+    const int base = a.f0 ? a.kept[row] : 0;
+    a.nf[slot] = nf;
+    a.h[slot] = h;
+    a.flags[slot] = (int)fl;
+    a.kept[row] = base + off;
+    s_base = base;
+  }
+  __syncthreads();
+  float* out = a.ring + (long long)slot * a.ring_len;
+  int* so = a.src + (long long)slot * (a.ring_len / a.frame);
+  float* ln = a.line + (long long)slot * pre * a.frame;
+  const int w0 = wpos + s_base;  // base + off + frame <= n <= ring_len: one wrap, at a frame edge
+  const int old = min(pre, a.nframes);  // steps whose leaving frame an earlier launch stored in the line
+  for (int f = wave; f < a.nframes; f += 4) {
+    const int off = s_off[f];
+    if (off < 0) continue;
+    const float* from = f < old ? ln + (long long)((G0 + f) % pre) * a.frame : x + (long long)(f - pre) * a.frame;
+    const int w = w0 + off < a.ring_len ? w0 + off : w0 + off - a.ring_len;
+    for (int k = lane; k < a.frame; k += 64) out[w + k] = from[k];
+    if (lane == 0) so[w / a.frame] = G0 + f - pre;
+  }
+  __syncthreads();  // every copy out of the line is done before a frame of this launch is stored into it
+  for (int f = a.nframes - old + wave; f < a.nframes; f += 4) {
+    const float* from = x + (long long)f * a.frame;
+    float* to = ln + (long long)((G0 + f) % pre) * a.frame;
+    for (int k = lane; k < a.frame; k += 64) to[k] = from[k];
+  }
+}
+
+const char* launch_gate_la(const float* x, int A, int n, const int* hdr, int frame, float e_floor, float ratio, float rise,
+                           int hang, int pre, float* nf, int* h, int* flags, float* line, float* ring, int* src, int S,
+                           int ring_len, int* kept, unsigned char* mask, hipStream_t s) {
+  if (!x || !hdr || !nf || !h || !flags || !line || !ring || !src || !kept) return "gate_la: null argument";
+  if (A <= 0 || A > 65535) return "gate_la: 1 to 65535 rows";
+  if (frame <= 0 || n <= 0 || n % frame) return "gate_la: a row is a positive whole number of frames";
+  if (S <= 0 || ring_len <= 0 || ring_len > (1 << 30) || ring_len % frame)
+    return "gate_la: no slots, or a ring that is not whole frames (at most 2^30 samples)";
+  if (pre < 1 || pre > 31) return "gate_la: 1 to 31 frames of pre-roll";
+  if (!(e_floor > 0.f && e_floor < INFINITY && ratio > 1.f && ratio < INFINITY && rise >= 1.f && rise < INFINITY) || hang < 0)
+    return "gate_la: floor > 0, ratio > 1, rise >= 1 (all finite) and hang >= 0";
+  GateLaArgs a{};
+  a.x = x; a.hdr = hdr; a.nf = nf; a.h = h; a.flags = flags; a.line = line; a.ring = ring; a.src = src; a.kept = kept;
+  a.mask = mask; a.n = n; a.frame = frame; a.pre = pre; a.S = S; a.ring_len = ring_len; a.hang = hang;
+  a.e_floor = e_floor; a.ratio = ratio; a.rise = rise; a.nf_min = e_floor / ratio;  // (one IEEE fp32 division, on the host)
+  const int frames = n / frame;
+  for (a.f0 = 0; a.f0 < frames; a.f0 += GATE_MAX_FRAMES) {
+    a.nframes = min(GATE_MAX_FRAMES, frames - a.f0);
+    hipLaunchKernelGGL(gate_la_kernel, dim3(A), dim3(256), 0, s, a);
+  }
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+// ---------------------------------------------------------------------------------
 // Cascade (afx/cascade.py; the functions are stated in include/afx.h afx_k_cascade_store / _select / _windows): a cheap
 // screen scores every slot at every hop, and the windows of the slots whose score looks suspicious are gathered for a
 // second model.  Three launches per push, every index from a host-built header:

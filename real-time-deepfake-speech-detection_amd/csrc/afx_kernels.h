@@ -158,6 +158,12 @@ const char* launch_jitter_release(const float* jring, int S, int J, const int* h
 // mask (optional) the keep flag of every frame
 const char* launch_gate(const float* x, int A, int n, const int* hdr, int frame, float e_floor, float ratio, float rise, int hang,
                         float* nf, int* h, float* ring, int S, int ring_len, int* kept, unsigned char* mask, hipStream_t s);
+// look-ahead gate (include/afx.h afx_k_gate_la): the same decision behind a delay line of `pre` frames per slot (flags, line);
+// a frame is emitted, `pre` frames late, if it was kept or a speech frame followed within `pre`; src records the source
+// index of every emitted frame, mask (optional) keep' of the frames decided
+const char* launch_gate_la(const float* x, int A, int n, const int* hdr, int frame, float e_floor, float ratio, float rise,
+                           int hang, int pre, float* nf, int* h, int* flags, float* line, float* ring, int* src, int S,
+                           int ring_len, int* kept, unsigned char* mask, hipStream_t s);
 // cascade (include/afx.h afx_k_cascade_store / _select / _windows): the named slots' hops into the retained-audio ring; the
 // candidates among the rows ranked by (score, slot), the first `budget` row positions into sel, the cooldown counters
 // advanced; the windows of the rows sel names gathered from the ring (sel is read on the device)

@@ -5,9 +5,12 @@ tremolo at -14 dBFS, silence = noise at -54 dBFS), the student scores them in KV
   gated     afx.vad.GatedScorer around the KV-cached scorer: every hop one ``push`` of all S slots (one afx_k_gate launch,
             one read-back of S int32, one pop and one inner push over the slots that completed a hop of kept audio);
   bare      the KV-cached scorer alone pushed the same hops lock-stepped: every slot scored every hop, what the parent of
-            the gate could do.
+            the gate could do;
+  lookahead (with --pre N) the gated path with ``LookaheadGate(pre=N)``: ``afx_k_gate_la`` in place of ``afx_k_gate`` (one
+            more read and write of N frames per slot and the source indices), timed in the same process.  It keeps N more
+            frames per onset, so it scores slightly more hops: read its time beside its own share of slot-pushes.
 
-    python tools/gate_bench.py [--streams 2048] [--activity 0.4] [--hops 8] [--reps 3]
+    python tools/gate_bench.py [--streams 2048] [--activity 0.4] [--hops 8] [--reps 3] [--pre 5]
     rocprofv3 --kernel-trace --stats ... -- python tools/gate_bench.py --profile   (gated path only, 4 hops: kernel times)
 
 The two paths score different audio by design (the gate drops frames), so their scores are not compared; the gate's own
@@ -28,7 +31,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "real-time-deepfake-speech-detection_am
 from afx import engine, synth  # noqa: E402
 from afx._lib import lib  # noqa: E402
 from afx.streaming import KVCachedScorer  # noqa: E402
-from afx.vad import GatedScorer, SpeechGate, emitted  # noqa: E402
+from afx.vad import GatedScorer, LookaheadGate, SpeechGate, emitted  # noqa: E402
 
 W, H = 64000, 4000
 
@@ -55,6 +58,7 @@ def main():
     ap.add_argument("--bank", type=int, default=64, help="distinct synthetic streams the slots draw from")
     ap.add_argument("--hops", type=int, default=8, help="hops per timed pass")
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--pre", type=int, default=0, help="also time the look-ahead gate with this many frames of pre-roll")
     ap.add_argument("--profile", action="store_true", help="the gated path only, a short pass (for a rocprofv3 run)")
     args = ap.parse_args()
     S = args.streams
@@ -80,9 +84,10 @@ def main():
           f"talk spurts ({args.activity:.0%} talk), gate {SpeechGate().params()}; {hops} hops per pass, {args.reps} timed passes "
           f"per path after a warm-up pass of {warm} hops", flush=True)
     results = {}
-    for name in (["gated"] if args.profile else ["gated", "bare"]):
+    look = ["lookahead"] if args.pre else []
+    for name in (["gated"] + look if args.profile else ["gated"] + look + ["bare"]):
         inner = KVCachedScorer(eng, sd, S, window=W, hop=H)
-        front = GatedScorer(inner) if name == "gated" else inner
+        front = {"gated": GatedScorer, "lookahead": lambda sc: GatedScorer(sc, LookaheadGate(pre=args.pre)), "bare": lambda sc: sc}[name](inner)
         pushes = scores = 0
 
         def run(t0, n):
@@ -95,7 +100,7 @@ def main():
                 outs.append(front.push(c))
             torch.cuda.synchronize()
             dt = time.perf_counter() - begin
-            if name == "gated":
+            if name != "bare":
                 pushes += n * S
                 scores += int(sum(emitted(o).sum() for o in outs))
             return dt
@@ -110,10 +115,10 @@ def main():
         med = times[len(times) // 2]
         results[name] = (med, times)
         extra = ""
-        if name == "gated":
+        if name != "bare":
             kept = float(front.samples_kept.sum()) / float(front.samples_seen.sum())
             extra = f"; {scores / pushes:.1%} of {pushes} slot-pushes emitted a score, {kept:.1%} of the samples kept"
-        print(f"  {name:6s} {med * 1e3:8.2f} ms per hop (min {times[0] * 1e3:.2f}, max {times[-1] * 1e3:.2f}); RTF {med / 0.25:.3f}{extra}",
+        print(f"  {name:9s} {med * 1e3:8.2f} ms per hop (min {times[0] * 1e3:.2f}, max {times[-1] * 1e3:.2f}); RTF {med / 0.25:.3f}{extra}",
               flush=True)
         del front, inner
         torch.cuda.empty_cache()
@@ -121,6 +126,10 @@ def main():
         (mg, tg), (mb, tb) = results["gated"], results["bare"]
         print(f"  gated / bare {mg / mb:.2f}x (spread of bare: {(tb[-1] - tb[0]) / mb * 100:.1f} % of its median, of gated: "
               f"{(tg[-1] - tg[0]) / mg * 100:.1f} %)", flush=True)
+        if look:
+            ml, tl = results["lookahead"]
+            print(f"  lookahead (pre {args.pre}) / gated {ml / mg:.2f}x (spread of lookahead: {(tl[-1] - tl[0]) / ml * 100:.1f} % of its "
+                  f"median)", flush=True)
 
 
 if __name__ == "__main__":
