@@ -222,12 +222,28 @@ const char* afx_profile_class_name(int cls);
  * attention / 0 the fp32 VALU kernel; "fuse_conformer" 1 fused row chains / 0 one kernel per op; "fuse_conv_ln" 1 conv +
  * LayerNorm + GELU in one kernel / 0 two.  They act on THIS handle only. */
 int afx_engine_set(afx_handle h, const char* key, int value);
+/* "concurrent" (afx_engine_set, default 0): 1 says that the native calls which follow run beside another forward on a second
+ * stream (Engine.forward_lanes / forward_overlapped set it around their calls and clear it after).  Launch shapes are then
+ * chosen for CU time (workgroups x unit: what a launch keeps from the other forward) instead of makespan (rounds x unit: the
+ * launch alone on the chip) -- taller GEMM tiles, 8 waves per workgroup in the fused Conformer chains.  Same rows, bit for
+ * bit.  afx_engine_get reads "concurrent" back and "objective": what the last native call on the handle ran under. */
+int afx_engine_get(afx_handle h, const char* key, int* value);
+/* The launch plan of a half- or split-precision product, host arithmetic only (no device, no handle).  rpb / kchunk: 0 = M / K
+ * (a plain product).  flags: 1 fused LayerNorm epilogue (N = 512), 2 split precision, 4 an activation outside the lean
+ * epilogue, 8 never the deep 128x64 tile.  objective: 0 makespan, 1 CU time, -1 the calling thread's.  out[8]: tile family,
+ * instance, tile rows, tile slots, rows of the first launch when split (else 0), the remainder's instance, its tile slots,
+ * the objective used.  afx_conf_chain_waves: waves per workgroup of a fused Conformer chain over M token rows. */
+int afx_gemm_plan(int M, int N, int K, int rpb, int kchunk, int groups, int flags, int objective, int* out);
+int afx_conf_chain_waves(int M, int objective);
 /* tuning knobs for A/B measurements (process-wide; not part of the drop-in surface).
  * "gemm_map": workgroup->tile order of the MFMA GEMM, -1 default, 0 linear, 1 XCD-
  * contiguous, 2 XCD-contiguous + grouped.  "gemm_tile": -1 auto, 0 128x128, 1 256x256.
  * "fuse_conv_ln": 1 (default) conv layers 1-6 use the fused LayerNorm epilogue, 0 two kernels.
  * "aasist_conv_slots": 0 automatic, n > 0 caps the grid of the AASIST back-end's persistent conv kernel at n workgroups
  * (a test knob: a small problem then walks many tiles per workgroup).
+ * "dispatch_objective": -1 per call (default), 0 / 1 every launch by makespan / CU time.  "dispatch_cu_mask": which decisions
+ * the CU-time objective takes over (1 height of the 256-wide tile, 2 chain waves, 4 height of the conv tile, 8 the two row
+ * splits; default 3: the two that won their A/B).  "conf_chain_waves": 0 by the objective, 4 / 8 forced.
  * None of these changes WHAT is computed; the timing-only switches that do ("gemm_nodma") exist only in the
  * attribution build (make attr), the product library refuses them. */
 int afx_debug_set(const char* key, int value);

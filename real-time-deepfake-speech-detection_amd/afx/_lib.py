@@ -57,6 +57,9 @@ SIGNATURES = {
     "afx_tail_forward_windows": (_I, [_P, _P, C.c_longlong, C.POINTER(C.c_longlong), _I, _I, _P, _P, _Z, _P]),
     "afx_conformer_forward": (_I, [_P, _P, _I, _I, _P, _P, _P, _Z, _P]),
     "afx_engine_set": (_I, [_P, C.c_char_p, _I]),
+    "afx_engine_get": (_I, [_P, C.c_char_p, C.POINTER(C.c_int)]),
+    "afx_gemm_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_int)]),
+    "afx_conf_chain_waves": (_I, [_I, _I]),
     "afx_kv_create": (_I, [_P, _I, C.POINTER(_P)]),
     "afx_kv_destroy": (None, [_P]),
     "afx_kv_state_bytes": (_Z, [_P]),

@@ -1,6 +1,7 @@
 """Host-side handle on the native engine: owns an afx_handle, feeds it weights by
 their reference checkpoint names and runs forwards on the current HIP stream.
 PyTorch is used for device memory and streams only."""
+import contextlib
 import ctypes as C
 import os
 
@@ -193,13 +194,15 @@ class Engine:
             elif slot["head_done"] is not None:
                 cur.wait_event(slot["head_done"])  # this workspace's previous head (two calls ago) must be done with it
             ws = slot["ws"]
-            check(l.afx_trunk_forward(self._h, ptr(x), B, L, ptr(ws), ws.numel(), C.c_void_p(cur.cuda_stream)))
+            with self._concurrent():
+                check(l.afx_trunk_forward(self._h, ptr(x), B, L, ptr(ws), ws.numel(), C.c_void_p(cur.cuda_stream)))
             trunk_done = torch.cuda.Event()
             trunk_done.record(cur)
             out = torch.empty(B, 2, dtype=torch.float32, device=self.device)
             self._side.wait_event(trunk_done)
             out.record_stream(self._side)
-            check(l.afx_head_from_workspace(self._h, B, L, ptr(out), ptr(ws), ws.numel(), C.c_void_p(self._side.cuda_stream)))
+            with self._concurrent():
+                check(l.afx_head_from_workspace(self._h, B, L, ptr(out), ptr(ws), ws.numel(), C.c_void_p(self._side.cuda_stream)))
             slot["head_done"] = torch.cuda.Event()
             slot["head_done"].record(self._side)
             self._last_head = slot["head_done"]
@@ -242,7 +245,8 @@ class Engine:
             ws = slot["ws"]
             out = torch.empty(B, 2, dtype=torch.float32, device=self.device)
             if k == 0:
-                check(l.afx_forward(self._h, ptr(x), B, L, ptr(out), ptr(ws), ws.numel(), C.c_void_p(cur.cuda_stream)))
+                with self._concurrent():
+                    check(l.afx_forward(self._h, ptr(x), B, L, ptr(out), ptr(ws), ws.numel(), C.c_void_p(cur.cuda_stream)))
                 self._last_stream = cur
             else:
                 ready = torch.cuda.Event()
@@ -250,12 +254,32 @@ class Engine:
                 self._side.wait_event(ready)
                 x.record_stream(self._side)
                 out.record_stream(self._side)
-                check(l.afx_forward(self._h, ptr(x), B, L, ptr(out), ptr(ws), ws.numel(), C.c_void_p(self._side.cuda_stream)))
+                with self._concurrent():
+                    check(l.afx_forward(self._h, ptr(x), B, L, ptr(out), ptr(ws), ws.numel(), C.c_void_p(self._side.cuda_stream)))
                 slot["done"] = torch.cuda.Event()
                 slot["done"].record(self._side)
                 self._last_head = slot["done"]
                 self._last_stream = self._side
         return out
+
+    @contextlib.contextmanager
+    def _concurrent(self):
+        """The native calls inside run beside another forward on the other stream: the engine's "concurrent" switch is on for
+        them -- launch shapes chosen for CU time (workgroups x unit), not makespan (afx.h) -- and off again after, so ``forward``,
+        graph capture, the streaming and KV paths keep the one-stream choices whatever was issued before.  Same bits either way."""
+        l = lib()
+        check(l.afx_engine_set(self._h, b"concurrent", 1))
+        try:
+            yield
+        finally:
+            l.afx_engine_set(self._h, b"concurrent", 0)
+
+    @property
+    def last_objective(self):
+        """What the launch shapes of the last native call on this engine were chosen for: 0 makespan, 1 CU time."""
+        v = C.c_int(0)
+        check(lib().afx_engine_get(self._h, b"objective", C.byref(v)))
+        return v.value
 
     def set_issue(self, form):
         """Which two-stream form ``forward_overlapped`` issues: "overlap" (the back-end beside the next trunk) or "lanes" (whole

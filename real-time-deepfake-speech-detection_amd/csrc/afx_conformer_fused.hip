@@ -43,17 +43,12 @@ constexpr int EK = 5;   // 32-wide k-steps covering E (144 -> 160, the pad colum
 constexpr int HT6 = 6;  // the FF hidden layer is walked in 6 parts of 6 tiles (96 columns = 3 k-steps)
 constexpr int RING = 4, BUFSZ = 32 * 1024, DUMP = RING * BUFSZ;  // + one 1-KB dump block
 constexpr int PARAMS = DUMP + 1024;  // byte offset of the parameter block behind the ring and the dump block
-// Waves per workgroup (16 token rows each).  The chain is a latency path per wave, not a throughput one: at
-// B = 64 there are only 796 row tiles, so 8 waves per workgroup fill 100 of the 256 CUs with two waves per SIMD
-// contending for the LDS fragment reads, 4 waves fill 199 CUs with one wave per SIMD: 30.9 -> 27.3 us per
-// launch, bit-identical results (tools/chain_ab.py; each weight byte is then fetched once per 64 rows
-// instead of 128 -- from L2, 0.66 MB per chain, not a cost).
-#ifndef CHAIN_NWAVE
-#define CHAIN_NWAVE 4
-#endif
-constexpr int NWAVE = CHAIN_NWAVE;
-constexpr int DPW = 32 / NWAVE;     // LDS-DMA instructions per wave per weight chunk
-static_assert(NWAVE == 8 || NWAVE == 4, "wave count");
+// Waves per workgroup (16 token rows each): a template parameter (NWAVE, 4 or 8) of the chain.  The chain is a latency
+// path per wave, not a throughput one: at B = 64 there are only 796 row tiles, so 8 waves per workgroup fill 100 of the
+// 256 CUs with two waves per SIMD contending for the LDS fragment reads, 4 waves fill 199 CUs with one wave per SIMD:
+// 30.9 -> 27.3 us per launch alone on the chip, bit-identical results (tools/chain_ab.py; each weight byte is then fetched
+// once per 64 rows instead of 128 -- from L2, 0.66 MB per chain, not a cost).  That is the makespan choice; in CU time 4 waves
+// hold 199 CUs x 27.3 us against 100 x 30.9, so with a second forward queued beside this one launch_conf_chain takes 8.
 template <int N>
 __device__ __forceinline__ void chain_wait_vmcnt() {
   static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
@@ -97,8 +92,10 @@ __device__ __forceinline__ ChunkDesc chunk_of(const ConfChainArgs& p, int idx) {
 template <int STAGE, bool S3> constexpr int kChunks = S3 ? (STAGE == 0 ? 30 + 9 : STAGE == 1 ? 3 + 12 : 9 + 30)
                                                          : (STAGE == 0 ? 12 + 5 : STAGE == 1 ? 2 + 6 : 3 + 12);
 
-template <class HT, int STAGE, bool S3>
+template <class HT, int STAGE, bool S3, int NWAVE>
 struct Chain {
+  static_assert(NWAVE == 8 || NWAVE == 4, "wave count");
+  static constexpr int DPW = 32 / NWAVE;  // LDS-DMA instructions per wave per weight chunk
   typedef typename HT::T T;
   typedef typename HT::V8 V8;
   // the A operand of one 32-wide k-step: this lane's 8 consecutive k; in split precision their hi and lo halves
@@ -395,9 +392,9 @@ struct Chain {
 
 }  // namespace
 
-template <class HT, int STAGE, bool S3>
+template <class HT, int STAGE, bool S3, int NWAVE>
 __global__ __launch_bounds__(64 * NWAVE) void conf_chain_kernel(ConfChainArgs p) {
-  typedef Chain<HT, STAGE, S3> C;
+  typedef Chain<HT, STAGE, S3, NWAVE> C;
   typedef typename C::AF AF;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   C c(p, smem);
@@ -501,13 +498,29 @@ __global__ __launch_bounds__(64 * NWAVE) void conf_chain_kernel(ConfChainArgs p)
   }
 }
 
-template <class HT, int STAGE, bool S3>
+template <class HT, int STAGE, bool S3, int NWAVE>
 static hipError_t launch_conf_chain_t(const ConfChainArgs& p, hipStream_t s) {
   constexpr int lds = PARAMS + (kChainParamFloats + (S3 ? kChainScaleFloats : 0)) * 4;
   static LdsLimit lim;
-  if (hipError_t e = lim.ensure((const void*)conf_chain_kernel<HT, STAGE, S3>, lds); e != hipSuccess) return e;
-  hipLaunchKernelGGL((conf_chain_kernel<HT, STAGE, S3>), dim3((unsigned)((p.M + 16 * NWAVE - 1) / (16 * NWAVE))), dim3(64 * NWAVE), lds, s, p);
+  if (hipError_t e = lim.ensure((const void*)conf_chain_kernel<HT, STAGE, S3, NWAVE>, lds); e != hipSuccess) return e;
+  hipLaunchKernelGGL((conf_chain_kernel<HT, STAGE, S3, NWAVE>), dim3((unsigned)((p.M + 16 * NWAVE - 1) / (16 * NWAVE))), dim3(64 * NWAVE), lds, s, p);
   return hipGetLastError();
+}
+template <class HT, bool S3, int NWAVE>
+static hipError_t launch_conf_chain_s(const ConfChainArgs& p, int stage, hipStream_t s) {
+  return stage == 0 ? launch_conf_chain_t<HT, 0, S3, NWAVE>(p, s) : stage == 1 ? launch_conf_chain_t<HT, 1, S3, NWAVE>(p, s) : launch_conf_chain_t<HT, 2, S3, NWAVE>(p, s);
+}
+
+static int g_chain_waves = 0;  // test / A/B knob: 0 = by the objective, 4 / 8 forced
+void conf_chain_set_waves(int v) { g_chain_waves = v == 4 || v == 8 ? v : 0; }
+// Waves per workgroup of a chain launch over M token rows: 4 by makespan; by CU time workgroups x unit (one workgroup per CU
+// either way: 27.3 us with 4 waves, 30.9 with 8), so 8 wherever it halves the workgroups and 4 where one workgroup serves
+// all rows in both forms.
+int conf_chain_waves_of(int M, int obj) {
+  if (g_chain_waves) return g_chain_waves;
+  if (!dispatch_cu(obj, CU_CHAIN_WAVES)) return 4;
+  const long w4 = (M + 63) / 64, w8 = (M + 127) / 128;
+  return w8 * 309 < w4 * 273 ? 8 : 4;
 }
 
 // dtype DT_FP16X3: fp32 operand rows in (in_h), pair-form weights (+ the scale block behind the parameter block), fp32 out
@@ -515,13 +528,14 @@ const char* launch_conf_chain(const ConfChainArgs& p, int stage, int dtype, hipS
   if (p.E != 16 * ET || p.Ep < 32 * EK || p.FFp != 4 * 16 * ET) return "conf_chain: the fused Conformer chains are built for emb 144 / ff 576";
   if (dtype == DT_FP32) return "conf_chain: half-precision operands only";
   if (p.M <= 0 || stage < 0 || stage > 2) return "conf_chain: bad arguments";
+  const bool w8 = conf_chain_waves_of(p.M, dispatch_objective()) == 8;
   hipError_t e;
   if (dtype == DT_FP16X3)
-    e = stage == 0 ? launch_conf_chain_t<FP16, 0, true>(p, s) : stage == 1 ? launch_conf_chain_t<FP16, 1, true>(p, s) : launch_conf_chain_t<FP16, 2, true>(p, s);
+    e = w8 ? launch_conf_chain_s<FP16, true, 8>(p, stage, s) : launch_conf_chain_s<FP16, true, 4>(p, stage, s);
   else if (dtype == DT_BF16)
-    e = stage == 0 ? launch_conf_chain_t<BF16, 0, false>(p, s) : stage == 1 ? launch_conf_chain_t<BF16, 1, false>(p, s) : launch_conf_chain_t<BF16, 2, false>(p, s);
+    e = w8 ? launch_conf_chain_s<BF16, false, 8>(p, stage, s) : launch_conf_chain_s<BF16, false, 4>(p, stage, s);
   else
-    e = stage == 0 ? launch_conf_chain_t<FP16, 0, false>(p, s) : stage == 1 ? launch_conf_chain_t<FP16, 1, false>(p, s) : launch_conf_chain_t<FP16, 2, false>(p, s);
+    e = w8 ? launch_conf_chain_s<FP16, false, 8>(p, stage, s) : launch_conf_chain_s<FP16, false, 4>(p, stage, s);
   return e == hipSuccess ? nullptr : hipGetErrorString(e);
 }
 

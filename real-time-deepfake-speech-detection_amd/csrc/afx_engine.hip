@@ -126,6 +126,8 @@ struct afx_engine {
   int fuse_conformer = 1;   // Conformer block: row-local chains fused (afx_conformer_fused.hip); 0 = per-op path
   int fuse_conv_ln = 1;     // conv layers 1-6: LayerNorm + GELU in the GEMM epilogue (0: two kernels)
   int gemm_small_deep = 1;  // products with at most two 128x64 tiles per CU: the deep form of that tile (0: the two-buffer form)
+  int concurrent = 0;  // 1: the calls that follow run beside another forward on a second stream -- launch shapes by CU time (OBJ_CU_TIME)
+  int last_objective = 0;  // the objective the last native call on this handle ran under (afx_engine_get "objective")
   std::unordered_map<std::string, TapRec> taps;
   // overflow guard: device counters [0] rows of the trunk's final LayerNorm with non-finite statistics, [1] non-finite logits
   // (written by those kernels of every forward, read and cleared by afx_check_finite)
@@ -991,6 +993,8 @@ static const char* P_rownorm(const RowNormArgs& a_in, int dt, hipStream_t s) {
 static void begin_call(afx_engine* e, const Ws* w) {
   t_prof = e->prof;
   t_no_deep = e->gemm_small_deep ? 0 : 1;
+  dispatch_set_objective(e->concurrent ? OBJ_CU_TIME : OBJ_MAKESPAN);
+  e->last_objective = dispatch_objective();
   t_ln_scale = &e->ln_scale;
   t_s3planes = w ? w->s3planes : nullptr;
   t_s3bytes = w ? w->s3bytes : 0;
@@ -2673,6 +2677,7 @@ extern "C" size_t afx_head_workspace_bytes(afx_handle h, int B, int T) {
 extern "C" int afx_k_gemm(int dtype, const void* A, long lda, const void* W, long ldw, int M, int N, int K,
                           const float* bias, int act, float alpha, const float* resid, long ldr, float* out_f,
                           long ldo_f, void* out_h, long ldo_h, void* stream) {
+  dispatch_set_objective(OBJ_MAKESPAN);  // (a single-kernel entry point is no concurrent forward)
   GemmArgs g = plain_gemm(A, lda, W, ldw, M, N, K);
   g.bias = bias; g.act = act; g.alpha = alpha; g.resid = resid; g.ldr = ldr;
   g.out_f = out_f; g.ldo_f = ldo_f; g.out_h = out_h; g.ldo_h = ldo_h;
@@ -2705,6 +2710,7 @@ extern "C" int afx_k_gemm(int dtype, const void* A, long lda, const void* W, lon
 }
 extern "C" int afx_k_conv_gemm(int dtype, const void* in_h, const void* Wp, int B, int Tin, int Tout, int Cin, int k,
                                int s_, int N, const float* bias, float* out_f, void* stream) {
+  dispatch_set_objective(OBJ_MAKESPAN);  // (a single-kernel entry point is no concurrent forward)
   GemmArgs g = plain_gemm(in_h, 0, Wp, (long)k * Cin, B * Tout, N, k * Cin);
   g.rpb = Tout; g.a_batch = (long)Tin * Cin; g.a_row = (long)s_ * Cin;
   g.o_batch_rows = Tout; g.oh_batch_rows = Tout;
@@ -2714,6 +2720,7 @@ extern "C" int afx_k_conv_gemm(int dtype, const void* in_h, const void* Wp, int 
 extern "C" int afx_k_conv_ln_act(int dtype, const void* in_h, const void* Wp, int B, int Tin, int Tout, int Cin,
                                  int k, int s_, const float* bias, const float* gamma, const float* beta, float eps,
                                  int act, float* out_f, void* out_h, void* stream) {
+  dispatch_set_objective(OBJ_MAKESPAN);  // (a single-kernel entry point is no concurrent forward)
   GemmArgs g = plain_gemm(in_h, 0, Wp, (long)k * Cin, B * Tout, 512, k * Cin);
   g.rpb = Tout; g.a_batch = (long)Tin * Cin; g.a_row = (long)s_ * Cin;
   g.o_batch_rows = Tout; g.oh_batch_rows = Tout;
@@ -2804,6 +2811,18 @@ extern "C" int afx_debug_set(const char* key, int value) {
     gemm_set_fit(value);
     return 0;
   }
+  if (!strcmp(key, "dispatch_objective")) {
+    dispatch_force_objective(value);
+    return 0;
+  }
+  if (!strcmp(key, "dispatch_cu_mask")) {
+    dispatch_set_cu_mask(value);
+    return 0;
+  }
+  if (!strcmp(key, "conf_chain_waves")) {
+    conf_chain_set_waves(value);
+    return 0;
+  }
   if (!strcmp(key, "conf_attn_waves")) {
     conf_attn_mfma_set_waves(value);
     return 0;
@@ -2858,8 +2877,38 @@ extern "C" int afx_engine_set(afx_handle h, const char* key, int value) {
   else if (!strcmp(key, "fuse_conformer")) h->fuse_conformer = value != 0;
   else if (!strcmp(key, "fuse_conv_ln")) h->fuse_conv_ln = value != 0;
   else if (!strcmp(key, "gemm_small_deep")) h->gemm_small_deep = value != 0;
+  else if (!strcmp(key, "concurrent")) h->concurrent = value != 0;
   else return fail("afx_engine_set: unknown key '%s'", key);
   return 0;
+}
+extern "C" int afx_engine_get(afx_handle h, const char* key, int* value) {
+  if (!h || !key || !value) return fail("afx_engine_get: null argument");
+  if (!strcmp(key, "concurrent")) *value = h->concurrent;
+  else if (!strcmp(key, "objective")) *value = h->last_objective;
+  else return fail("afx_engine_get: unknown key '%s'", key);
+  return 0;
+}
+// The launch plan of a product, from host arithmetic alone (no device, no handle): what launch_gemm would do with it.
+// flags: 1 fused LayerNorm epilogue (the conv layers), 2 split precision (K counts fp32 elements), 4 an activation outside the
+// lean epilogue (swish / selu), 8 never the deep 128x64 tile.  objective: 0 makespan, 1 CU time, -1 the calling thread's.
+// out[8]: family, instance, tile rows, tile slots, split rows, remainder instance, remainder tile slots, objective used.
+extern "C" int afx_gemm_plan(int M, int N, int K, int rpb, int kchunk, int groups, int flags, int objective, int* out) {
+  if (!out || M <= 0 || N <= 0 || K <= 0 || groups <= 0) return fail("afx_gemm_plan: bad arguments");
+  GemmArgs g = plain_gemm(nullptr, K, nullptr, K, M, N, K);
+  if (rpb > 0) g.rpb = rpb;
+  if (kchunk > 0) g.kchunk = kchunk;
+  if (flags & 1) g.ln_gamma = g.ln_beta = g.bias = (const float*)out;  // (never dereferenced: the plan reads shapes only)
+  if (flags & 2) { g.k1 = K; g.K = 2 * K; g.kchunk = 2 * g.kchunk; }
+  if (flags & 4) g.act = ACT_SWISH;
+  if (flags & 8) g.no_deep = 1;
+  const int obj = objective < 0 ? dispatch_objective() : (objective ? OBJ_CU_TIME : OBJ_MAKESPAN);
+  const GemmPlan pl = gemm_plan(g, groups, obj);
+  out[0] = pl.family; out[1] = pl.tile; out[2] = pl.rows; out[3] = (int)pl.tiles;
+  out[4] = pl.split_rows; out[5] = pl.rem_tile; out[6] = (int)pl.rem_tiles; out[7] = obj;
+  return 0;
+}
+extern "C" int afx_conf_chain_waves(int M, int objective) {
+  return conf_chain_waves_of(M, objective < 0 ? dispatch_objective() : (objective ? OBJ_CU_TIME : OBJ_MAKESPAN));
 }
 extern "C" int afx_k_pre_emphasis(const float* x, int B, int L, float coef, float* y, void* stream) {
   KRET(launch_pre_emphasis(x, B, L, coef, y, (hipStream_t)stream));

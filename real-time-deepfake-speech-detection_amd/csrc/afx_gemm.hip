@@ -1795,8 +1795,29 @@ static int g_split = 1;  // A/B knob
 void gemm_set_split(int v) { g_split = v; }
 static int g_s3_small = 0;  // A/B knob (split precision, small-M products): 0 = the fp16 dispatch's choice (deep 128x64), 1 = 128x128 2-stage, 2 = 128x64 2-stage
 void gemm_set_s3_small(int v) { g_s3_small = v; }
+// ---- the objective of a launch shape (afx_kernels.h: OBJ_MAKESPAN / OBJ_CU_TIME) ------------------------------------
+static thread_local int t_objective = OBJ_MAKESPAN;
+static int g_objective = -1;  // test / A/B knob: -1 = the calling thread's, 0 / 1 forced for every launch
+// What the CU-time objective decides (A/B knob "dispatch_cu_mask").  Measured in the two-lanes form, each alone and together
+// (profiles/cu_time_dispatch_ab.txt): the height of the 256-wide tile and the chain's waves win on both models and precisions;
+// the conv tile's height and the two row splits do not beat the run-to-run spread and stay on their makespan choices.
+static int g_cu_mask = CU_GEMM8_HEIGHT | CU_CHAIN_WAVES;
+void dispatch_set_objective(int obj) { t_objective = obj == OBJ_CU_TIME ? OBJ_CU_TIME : OBJ_MAKESPAN; }
+void dispatch_force_objective(int obj) { g_objective = obj < 0 ? -1 : (obj == OBJ_CU_TIME ? OBJ_CU_TIME : OBJ_MAKESPAN); }
+void dispatch_set_cu_mask(int mask) { g_cu_mask = mask; }
+int dispatch_objective() { return g_objective >= 0 ? g_objective : t_objective; }
+bool dispatch_cu(int obj, int bit) { return obj == OBJ_CU_TIME && (g_cu_mask & bit) != 0; }
+
+// ---- the cost model of every GEMM launch shape, in one place ---------------------------------------------------------
+// Units are those of the fits below: an 8-phase 256-wide tile of MF fragments costs MF + 5, a row-complete 128x512 tile MF + 6,
+// a 128x128 tile (two per CU, ~15 % slower per FLOP than the 256-wide kernel) 13 x 1.15 / 4.  The makespan objective charges
+// ROUNDS of the 256 CUs x unit -- the launch alone on the chip; the CU-time objective charges TILES x unit -- what the launch
+// keeps from a second forward queued beside it.  Ties go to the taller tile.
+constexpr long kCUs = 256;
+constexpr double kUnit128 = 13 * 1.15 / 4;
+static long gemm_units(long tiles, int unit, bool cu) { return (cu ? tiles : (tiles + kCUs - 1) / kCUs) * unit; }
+
 static int gemm_split_rows(const GemmArgs& p, int groups) {
-  constexpr int kCUs = 256;
   if (!g_split || groups != 1 || p.ln_gamma || !plain_k(p) || p.rpb < p.M || gemm_is_narrow(p.N)) return 0;
   const long nN = (p.N + 255) / 256, nM = (p.M + 255) / 256, tiles = nN * nM;
   if (tiles <= kCUs || tiles % kCUs == 0) return 0;
@@ -1810,18 +1831,20 @@ static int gemm_split_rows(const GemmArgs& p, int groups) {
 }
 
 // Height of the 8-phase 256-wide tile for a product that is NOT round-split: fragments per wave row (8 = 256 rows).
-// Cost model: rounds x (MF + 5) -- fitted to tools/bench_teacher_gemm.py (M = 12736, N = 4096: 33.4 / 30.3 / 27.3 / 25.6 us
+// Cost model: MF + 5 per tile -- fitted to tools/bench_teacher_gemm.py (M = 12736, N = 4096: 33.4 / 30.3 / 27.3 / 25.6 us
 // per round at 8 / 7 / 6 / 5 fragments): the operand DMA of a K-tile does not shrink with the height, only the MFMAs do.
+// By makespan M = 12736 takes 224-row tiles (228 / 684 / 912 of them at N = 1024 / 3072 / 4096: one round fewer or the same
+// rounds at a cheaper unit); by CU time 256-row tiles (200 / 600 / 800): 12 % fewer tiles at an 8 % dearer unit.
 static int g_ph4 = 0;  // A/B knob: 0 = default (256-wide tiles: two-phase K-tile over a three-buffer A ring; conv tile: two-phase, two buffers), 1 = the 4-phase K-tile (16-MFMA segments) on the full-height tiles, 2 = the two-buffer two-phase form on the 256-wide tiles
 void gemm_set_ph4(int v) { g_ph4 = v; }
 static int g_conv_split = 1;  // A/B knob: remainder split of multi-round conv layers
 void gemm_set_conv_split(int v) { g_conv_split = v; }
 static int g_fit = 1;  // A/B knob: 0 = always 256 rows, 1 = fitted, 5..8 = forced
 void gemm_set_fit(int v) { g_fit = v; }
-static int gemm8_fit_mf(const GemmArgs& p, long* cost_out = nullptr) {
-  constexpr long kCUs = 256;
-  const long nN = (p.N + 255) / 256;
-  auto cost_of = [&](int mf) { return ((nN * ((p.M + mf * 32 - 1) / (mf * 32)) + kCUs - 1) / kCUs) * (mf + 5); };
+static long gemm8_tiles(const GemmArgs& p, int mf) { return (long)((p.N + 255) / 256) * ((p.M + mf * 32 - 1) / (mf * 32)); }
+static int gemm8_fit_mf(const GemmArgs& p, int obj, long* cost_out = nullptr) {
+  const bool cu = dispatch_cu(obj, CU_GEMM8_HEIGHT);
+  auto cost_of = [&](int mf) { return gemm_units(gemm8_tiles(p, mf), mf + 5, cu); };
   int best = 8;
   if (g_fit >= 5 && g_fit <= 8) {
     best = g_fit;
@@ -1836,15 +1859,16 @@ static int gemm8_fit_mf(const GemmArgs& p, long* cost_out = nullptr) {
 // The same for the row-complete 128x512 tile (4 fragments per wave row = 128 rows; 3 = 96, 2 = 64): the conv layers of
 // a small batch (B = 16: 200 / 100 / 50 / 25 / 13 / 7 tiles of 128 rows on 256 CUs) spread over more CUs.  The weight
 // panel flows at 64 KB per K-tile whatever the height, so a tile's time shrinks less than its rows: cost MF + 6 (41.9 / 37.2 / 33.5 us at 128 / 96 / 64 rows, one round each).
-static int gemm8_fit_rowln(const GemmArgs& p) {
-  constexpr long kCUs = 256;
+// By CU time the spread is a loss: B = 64, layer 6 is 199 tiles of 64 rows by makespan, 100 of 128 rows by CU time.
+static int gemm8_fit_rowln(const GemmArgs& p, int obj) {
   if (!g_fit) return 4;
   if (g_fit >= 12 && g_fit <= 14) return g_fit - 10;  // forced (A/B): 12, 13, 14
+  const bool cu = dispatch_cu(obj, CU_ROWLN_HEIGHT);
   int best = 4;
   long best_cost = 0;
   for (int mf = 4; mf >= 2; --mf) {
     const long tiles = (p.M + mf * 32 - 1) / (mf * 32);
-    const long cost = ((tiles + kCUs - 1) / kCUs) * (mf + 6);
+    const long cost = gemm_units(tiles, mf + 6, cu);
     if (mf == 4 || cost < best_cost) {
       best = mf;
       best_cost = cost;
@@ -1853,7 +1877,8 @@ static int gemm8_fit_rowln(const GemmArgs& p) {
   return best;
 }
 
-int gemm_tile_of(const GemmArgs& p, int groups) {
+// Which tile FAMILY serves a problem (the id list above); the height and the splits follow in gemm_plan.
+static int gemm_family_of(const GemmArgs& p, int groups, int obj) {
   if (p.ln_gamma) return g_deep != 0 && plain_k(p) ? 8 : 3;
   if (gemm_is_narrow(p.N)) {
     // (narrow products with at most two 128x64 tiles per CU: the deep form of the tile, as below)
@@ -1891,11 +1916,93 @@ int gemm_tile_of(const GemmArgs& p, int groups) {
     if (g_small_deep && !p.no_deep && b128 <= 256 && plain_k(p) && lean && p.m_lo == 0) return 92;
     return 1;
   }
-  if (gemm_split_rows(p, groups) > 0) return 7;  // whole rounds on the 8-phase kernel + a 128x128 remainder
+  if (gemm_split_rows(p, groups) > 0) return 7;  // whole rounds on the 8-phase kernel + a 128x128 remainder (gemm_plan decides)
+  if (dispatch_cu(obj, CU_GEMM8_HEIGHT) && plain_k(p)) {
+    // CU time: the tiles of each family x its unit, the 256-wide kernel at the height gemm_plan will give it
+    long c256 = 0;
+    gemm8_fit_mf(p, obj, &c256);
+    if ((double)c256 > (double)b128 * kUnit128) return 0;
+    return 7;
+  }
   const double e128 = (double)b128 / (double)(((b128 + 511) / 512) * 512);
   const double e256 = 1.15 * (double)b256 / (double)(((b256 + 255) / 256) * 256);
   if (e256 <= e128) return 0;
   return plain_k(p) ? 7 : (p.k1 ? 0 : 2);  // the 8-phase kernel where its addressing applies (no chunked K)
+}
+int gemm_tile_of(const GemmArgs& p, int groups) { return gemm_family_of(p, groups, dispatch_objective()); }
+
+// Everything launch_gemm decides for (p, groups) under `obj`: family, height, the two splits.  With OBJ_MAKESPAN this is the
+// dispatch of rounds 1-4, shape for shape (tests/test_cpu_gemm_plan.py holds the table).
+GemmPlan gemm_plan(const GemmArgs& p, int groups, int obj) {
+  GemmPlan pl{};
+  int tile = gemm_family_of(p, groups, obj);
+  pl.family = tile;
+  if ((tile == 7 || tile == 8) && ((p.act != ACT_NONE && p.act != ACT_GELU) || (p.N & 7)))
+    tile = tile == 7 ? 0 : 3;  // the 8-phase kernels carry the lean epilogue: everything else stays on the 2-stage tiles
+  const long nN128 = (p.N + 127) / 128;
+  int m1 = tile == 7 && g_tile_override < 0 ? gemm_split_rows(p, groups) : 0;
+  if (m1 > 0) {
+    const long t1 = (long)(m1 / 256) * ((p.N + 255) / 256);
+    if (dispatch_cu(obj, CU_SPLITS)) {
+      // CU time: the whole product at the height it would get, against full-height tiles on the leading rows + 128x128 tiles
+      const int mf = gemm8_fit_mf(p, obj);
+      const double whole = (double)gemm8_tiles(p, mf) * (mf + 5);
+      const double split = (double)t1 * 13 + (double)((p.M - m1 + 127) / 128) * nN128 * kUnit128;
+      if (g_fit == 1 && whole <= split) m1 = 0;
+    } else {
+      // round split against a fitted height on the whole problem, in the same units: whole rounds at full height plus
+      // the remainder kernel (~10: measured 84.9 us split against 82.2 us as 3 rounds of 224-row tiles for QKV at M = 12736,
+      // 123.7 against 121.1 as 4 rounds for FC1 -- profiles/r02_gemm_dma_spread_ab.txt).  (Both sides by makespan, whatever
+      // decides the height of the whole product afterwards.)
+      long fitted = 0;
+      gemm8_fit_mf(p, OBJ_MAKESPAN, &fitted);
+      const long split = ((t1 + 255) / 256) * 13 + 10;
+      if (g_fit == 1 && fitted <= split) m1 = 0;
+    }
+  }
+  if (m1 > 0) {  // rows [0, m1) on the 8-phase kernel, rows [m1, M) on the 128x128 kernel
+    pl.tile = 7;
+    pl.rows = 256;
+    pl.tiles = (long)(m1 / 256) * ((p.N + 255) / 256);
+    pl.split_rows = m1;
+    pl.rem_tile = 0;
+    pl.rem_tiles = (long)((p.M - m1 + 127) / 128) * nN128;
+    return pl;
+  }
+  if (tile == 7) {
+    const int mf = gemm8_fit_mf(p, obj);
+    if (mf < 8) tile = 70 + mf;
+    pl.rows = mf * 32;
+    pl.tiles = gemm8_tiles(p, mf);
+  } else if (tile == 8) {
+    const int mf = gemm8_fit_rowln(p, obj);
+    if (mf < 4) tile = 80 + mf;
+    pl.rows = mf * 32;
+    pl.tiles = (p.M - p.m_lo + mf * 32 - 1) / (mf * 32);
+    // Remainder split of a multi-round conv layer: T tiles of 128 rows on 256 CUs cost ceil(T / 256) rounds however few tiles
+    // the last one holds (B = 64: layer 1 3200 tiles = 12.5 rounds, layer 2 1600 = 6.25, layer 3 800 = 3.125).  When the
+    // last round is at most 3/8 full, the whole rounds run at 128 rows and the remaining rows as 64-row tiles of the same
+    // kernel in a second launch (rows [m_lo, M) -- same rows, bit for bit).  Worth 2-4 % of such a layer (209 -> 203 us at
+    // 800 tiles; the persistent grid's tail is cheaper than a full round, so less than the tile count suggests).
+    // By CU time the same split is taken only where its tiles cost less: 64-row tiles are 8 units per 64 rows against 10 per 128.
+    const long t128 = (p.M + 127) / 128, frac = t128 % 256;
+    if (mf == 4 && g_fit == 1 && g_conv_split && t128 > 256 && frac != 0 && p.K >= 1536 && p.m_lo == 0) {
+      const long head = (t128 / 256) * 256, rem64 = (p.M - head * 128 + 63) / 64;
+      const bool take = dispatch_cu(obj, CU_SPLITS) ? head * 10 + rem64 * 8 < t128 * 10 : frac <= 96;
+      if (take) {
+        pl.tiles = head;
+        pl.split_rows = (int)(head * 128);
+        pl.rem_tile = 82;
+        pl.rem_tiles = rem64;
+      }
+    }
+  } else {
+    const int bm = tile == 2 ? 256 : 128, bn = tile == 2 ? 256 : (tile == 3 ? 512 : (tile == 1 || tile == 92 ? 64 : 128));
+    pl.rows = bm;
+    pl.tiles = (long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn) * groups;
+  }
+  pl.tile = tile;
+  return pl;
 }
 
 template <class HT>
@@ -1958,22 +2065,11 @@ const char* launch_gemm(const GemmArgs& p_in, int dtype, int groups, hipStream_t
   if (const char* e = check_gemm(p_in, groups)) return e;
   GemmArgs p = p_in;
   p.map_mode = g_map_override >= 0 ? g_map_override : 2;
-  int tile = gemm_tile_of(p, groups);
-  if ((tile == 7 || tile == 8) && ((p.act != ACT_NONE && p.act != ACT_GELU) || (p.N & 7)))
-    tile = tile == 7 ? 0 : 3;  // the 8-phase kernels carry the lean epilogue: everything else stays on the 2-stage tiles
-  p.a_nt = g_ant_override >= 0 ? g_ant_override : (tile == 3 ? 1 : 0);
+  const GemmPlan pl = gemm_plan(p, groups, dispatch_objective());
+  p.a_nt = g_ant_override >= 0 ? g_ant_override : (pl.tile == 3 ? 1 : 0);
   p.dbg_nodma = g_nodma;
-  int m1 = tile == 7 && g_tile_override < 0 ? gemm_split_rows(p, groups) : 0;
-  if (m1 > 0) {
-    // round split against a fitted height on the whole problem, in the same units: whole rounds at full height plus
-    // the remainder kernel (~10: measured 84.9 us split against 82.2 us as 3 rounds of 224-row tiles for QKV at M = 12736,
-    // 123.7 against 121.1 as 4 rounds for FC1 -- profiles/r02_gemm_dma_spread_ab.txt)
-    long fitted = 0;
-    gemm8_fit_mf(p, &fitted);
-    const long split = (((long)(m1 / 256) * ((p.N + 255) / 256) + 255) / 256) * 13 + 10;
-    if (g_fit == 1 && fitted <= split) m1 = 0;
-  }
-  if (m1 > 0) {  // rows [0, m1) on the 8-phase kernel, rows [m1, M) on the 128x128 kernel
+  if (pl.split_rows > 0 && pl.tile == 7) {  // rows [0, m1) on the 8-phase kernel, rows [m1, M) on the 128x128 kernel
+    const int m1 = pl.split_rows;
     const size_t hs = 2;
     GemmArgs a = p, b = p;
     a.M = m1; a.rpb = m1; a.o_batch_rows = m1; a.oh_batch_rows = m1;
@@ -1983,31 +2079,18 @@ const char* launch_gemm(const GemmArgs& p_in, int dtype, int groups, hipStream_t
     if (p.out_f) b.out_f = p.out_f + (size_t)m1 * p.ldo_f;
     if (p.out_h) b.out_h = (char*)p.out_h + (size_t)m1 * p.ldo_h * (p.k1 ? 4 : hs);
     hipError_t err = AFX_DISPATCH_GEMM(a, 7);
-    if (err == hipSuccess) err = AFX_DISPATCH_GEMM(b, 0);
+    if (err == hipSuccess) err = AFX_DISPATCH_GEMM(b, pl.rem_tile);
     return err == hipSuccess ? nullptr : hipGetErrorString(err);
   }
-  if (tile == 7) {
-    const int mf = gemm8_fit_mf(p);
-    if (mf < 8) tile = 70 + mf;
-  } else if (tile == 8) {
-    const int mf = gemm8_fit_rowln(p);
-    if (mf < 4) tile = 80 + mf;
-    // Remainder split of a multi-round conv layer: T tiles of 128 rows on 256 CUs cost ceil(T / 256) rounds however few tiles
-    // the last one holds (B = 64: layer 1 3200 tiles = 12.5 rounds, layer 2 1600 = 6.25, layer 3 800 = 3.125).  When the
-    // last round is at most 3/8 full, the whole rounds run at 128 rows and the remaining rows as 64-row tiles of the same
-    // kernel in a second launch (rows [m_lo, M) -- same rows, bit for bit).  Worth 2-4 % of such a layer (209 -> 203 us at
-    // 800 tiles; the persistent grid's tail is cheaper than a full round, so less than the tile count suggests).
-    const long t128 = (p.M + 127) / 128, frac = t128 % 256;
-    if (mf == 4 && g_fit == 1 && g_conv_split && t128 > 256 && frac != 0 && frac <= 96 && p.K >= 1536 && p.m_lo == 0) {
-      GemmArgs a = p, b = p;
-      a.M = (int)((t128 / 256) * 256 * 128);
-      b.m_lo = a.M;
-      hipError_t err = AFX_DISPATCH_GEMM(a, 8);
-      if (err == hipSuccess) err = AFX_DISPATCH_GEMM(b, 82);
-      return err == hipSuccess ? nullptr : hipGetErrorString(err);
-    }
+  if (pl.split_rows > 0) {  // conv layer: whole rounds of 128-row tiles, then rows [m_lo, M) as 64-row tiles of the same kernel
+    GemmArgs a = p, b = p;
+    a.M = pl.split_rows;
+    b.m_lo = a.M;
+    hipError_t err = AFX_DISPATCH_GEMM(a, pl.tile);
+    if (err == hipSuccess) err = AFX_DISPATCH_GEMM(b, pl.rem_tile);
+    return err == hipSuccess ? nullptr : hipGetErrorString(err);
   }
-  const hipError_t err = AFX_DISPATCH_GEMM(p, tile);
+  const hipError_t err = AFX_DISPATCH_GEMM(p, pl.tile);
   return err == hipSuccess ? nullptr : hipGetErrorString(err);
 }
 

@@ -94,7 +94,32 @@ const char* launch_gemm(const GemmArgs& p, int dtype, int groups, hipStream_t s)
 const char* launch_gemm_rows(const GemmArgs& p, int dtype, hipStream_t s);  // out_h rows from GemmArgs::oh_rows (afx_gemm.hip)
 const char* launch_gemm_f32(const GemmArgs& p, int groups, hipStream_t s);  // afx_gemm_f32.hip (DT_FP32 operands)
 bool gemm_is_narrow(int N);  // true: the 128x64 tile instance serves this N
-int gemm_tile_of(const GemmArgs& p, int groups);  // tile instance id (afx_gemm.hip)
+int gemm_tile_of(const GemmArgs& p, int groups);  // tile family id under the calling thread's objective (afx_gemm.hip)
+// ---- what a launch shape is chosen FOR (afx_gemm.hip) ------------------------------------------------------------
+// OBJ_MAKESPAN: the launch alone on an empty chip -- rounds x unit (every choice up to round 4 was fitted to this).
+// OBJ_CU_TIME: a second forward is queued on another stream and takes the CUs this launch leaves free, so the step
+// pays workgroups x unit (CUs held x time) and a shorter makespan bought with more tiles is a loss.
+// The objective is a property of the CALL: begin_call (afx_engine.hip) copies the engine's "concurrent" switch into a
+// thread-local, the launchers read it; the single-kernel entry points reset it.  Either way the rows are the same bits.
+enum { OBJ_MAKESPAN = 0, OBJ_CU_TIME = 1 };
+// the decisions the CU-time objective may change, one bit each ("dispatch_cu_mask", an A/B knob; default: the first two)
+enum { CU_GEMM8_HEIGHT = 1, CU_CHAIN_WAVES = 2, CU_ROWLN_HEIGHT = 4, CU_SPLITS = 8 };
+void dispatch_set_objective(int obj);    // this thread's objective for the launches that follow
+void dispatch_force_objective(int obj);  // test / A/B knob: -1 = per call (default), 0 / 1 = every launch of the process
+void dispatch_set_cu_mask(int mask);
+int dispatch_objective();                // the objective in force on this thread
+bool dispatch_cu(int obj, int bit);      // does objective `obj` decide `bit` by CU time?
+// The whole launch plan of a product, host arithmetic only (no device): what launch_gemm does with (p, groups).
+struct GemmPlan {
+  int family;     // tile family (gemm_tile_of): 0 128x128, 1 128x64, 92 its deep form, 2 256x256 2-stage, 3 / 8 row-complete 128x512, 7 8-phase 256-wide
+  int tile;       // the instance launched for the main part (7 / 75..77: 8-phase at 8 / 5..7 fragments, 8 / 82 / 83: row-complete at 4 / 2 / 3)
+  int rows;       // its tile height
+  long tiles;     // its tile slots (a persistent kernel's grid is min(tiles, CUs))
+  int split_rows; // > 0: the main launch covers rows [0, split_rows) and a second launch the rest
+  int rem_tile;   // ... with this instance (0: 128x128, 82: 64-row row-complete tiles)
+  long rem_tiles;
+};
+GemmPlan gemm_plan(const GemmArgs& p, int groups, int objective);
 void gemm_set_s3_small(int v);  // A/B knob: split-precision small-M products (0 default, 1 = 128x128, 2 = 128x64 2-stage)
 void gemm_set_map_mode(int m);  // A/B knob: -1 default, else force map_mode
 void gemm_set_small_deep(int v);  // A/B knob: 1 (default) = deep form of the 128x64 tile at <= two tiles per CU
@@ -322,6 +347,8 @@ struct ConfChainArgs {
   long ld_out2;
 };
 const char* launch_conf_chain(const ConfChainArgs& p, int stage, int dtype, hipStream_t s);
+void conf_chain_set_waves(int v);            // test / A/B knob: 0 = by the objective (default), 4 / 8 = waves per workgroup forced
+int conf_chain_waves_of(int M, int objective);  // waves per workgroup launch_conf_chain takes for M token rows
 // logits = fc5(token0):  x (B*N, E) fp32 rows, token row = b*N.
 // nonfinite (device counter or null): += 1 for every output that is not finite
 const char* launch_small_linear(const float* x, long row_stride, int rows, int K, const float* w, const float* b,
