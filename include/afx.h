@@ -317,6 +317,23 @@ int afx_k_resample_stream(const float* x, int A, int n_in, float* hist, const in
  * would leave stage, hist or ring is skipped whole.  M/L <= 12, T - 1 <= 256. */
 int afx_k_ingest(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_out, int encoding,
                  const float* taps, int L, int M, int T, float* hist, float* ring, int S, int ring_len, void* stream);
+/* afx_k_ingest over rows of different formats (afx/ingest.py MixedPacketScorer): a format is (encoding, taps, L, M, T), taps
+ * NULL with L = M = T = 1 the identity, as above.  formats (HOST, n_formats entries, 1..16) is read during the call and travels
+ * to the kernel by value: there is no device table; taps are device pointers.  hdr rows are afx_k_ingest's with the eighth int
+ * = the row's format index; a row is validated against ITS format (index in range, p0 < L, offset a multiple of its sample
+ * size, payload inside stage, and afx_k_ingest's other checks) and skipped whole when it fails.  Output k of a row has the
+ * value afx_k_ingest gives it in a launch of that one format: the same decoder, inputs, taps and ascending-j fma chain.
+ * max_out (HOST, n_formats ints): per format the largest n_out among its rows of this call, 0 = no row of it (its rows, if
+ * any, then write no output).  hist (S, Hs) fp32, Hs >= every format's T - 1: a slot of format f carries its T_f - 1 samples
+ * in the first columns of its row, which one further launch over all rows advances (identity rows are skipped); hist may be
+ * NULL when every format is the identity.  Refused with nothing launched: n_formats outside 1..16, a bad encoding, a bad
+ * filter shape, T - 1 > 256, M/L above 12, a null stage / hdr / ring, a max_out beyond ring_len, Hs below a format's T - 1. */
+typedef struct afx_ingest_format {
+  const float* taps; /* device, (L, T) fp32; NULL: the identity */
+  int encoding, L, M, T;
+} afx_ingest_format;
+int afx_k_ingest_mixed(const void* stage, long long stage_bytes, const int* hdr, int rows, const afx_ingest_format* formats,
+                       int n_formats, const int* max_out, float* hist, int Hs, float* ring, int S, int ring_len, void* stream);
 /* out (A, hop) fp32: out[i][k] = ring[slot_i][(head_i + k) mod ring_len], table (device, A x 2 int32) = (slot_i, head_i):
  * the next hop of the named slots as the streaming scorers' push takes it.  The ring is only read. */
 int afx_k_ingest_pop(const float* ring, int S, int ring_len, const int* table, int A, int hop, float* out, void* stream);
@@ -331,6 +348,12 @@ int afx_k_ingest_pop(const float* ring, int S, int ring_len, const int* table, i
  *     max_n = the largest n <= J.  A row whose header would leave stage or jring is skipped whole. */
 int afx_k_jitter_place(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n, int encoding,
                        float* jring, int S, int J, void* stream);
+/* afx_k_jitter_place_mixed: afx_k_jitter_place with the encoding read per row.  hdr (device, rows x 5 int32), per row: slot,
+ *     byte offset (a multiple of the row's sample size), n, ring column c, encoding (0..3 as for afx_k_ingest).  The ring is
+ *     decoded, so rows of different encodings may follow each other in one slot's stream.  A row with an encoding outside 0..3
+ *     is skipped whole, like one that would leave stage or jring. */
+int afx_k_jitter_place_mixed(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n, float* jring, int S,
+                             int J, void* stream);
 /* afx_k_jitter_conceal: a released gap of E that began at index a is written into the ring.  hdr (device, rows x 4 int32),
  *     per row: slot, a mod J, d_lo, d_hi: for d in [d_lo, d_hi), E[a + d] = jring[slot][(a + d) mod J] =
  *         mode 0 (zero):    0

@@ -29,6 +29,12 @@ class Config(C.Structure):
 
 _P, _I, _L, _F, _Z = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_size_t
 
+
+class IngestFormat(C.Structure):
+    """afx_ingest_format: one entry of afx_k_ingest_mixed's host format table."""
+    _fields_ = [("taps", C.c_void_p), ("encoding", C.c_int), ("L", C.c_int), ("M", C.c_int), ("T", C.c_int)]
+
+
 # symbol -> (restype, argtypes); must list every function include/afx.h declares
 SIGNATURES = {
     "afx_create": (_I, [C.POINTER(Config), C.POINTER(_P)]),
@@ -95,8 +101,10 @@ SIGNATURES = {
     "afx_k_resample": (_I, [_P, _P, _P, _I, C.c_longlong, _P, _I, _I, _I, _P, _P]),
     "afx_k_resample_stream": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P]),
     "afx_k_ingest": (_I, [_P, C.c_longlong, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _I, _I, _P]),
+    "afx_k_ingest_mixed": (_I, [_P, C.c_longlong, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _P]),
     "afx_k_ingest_pop": (_I, [_P, _I, _I, _P, _I, _I, _P, _P]),
     "afx_k_jitter_place": (_I, [_P, C.c_longlong, _P, _I, _I, _I, _P, _I, _I, _P]),
+    "afx_k_jitter_place_mixed": (_I, [_P, C.c_longlong, _P, _I, _I, _P, _I, _I, _P]),
     "afx_k_jitter_conceal": (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _I, _I, _P]),
     "afx_k_jitter_release": (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _I, _I, _P, _I, _P]),
     "afx_k_gate": (_I, [_P, _I, _I, _P, _I, _F, _F, _F, _I, _P, _P, _P, _I, _I, _P, _P, _P]),

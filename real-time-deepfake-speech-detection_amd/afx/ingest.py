@@ -25,6 +25,17 @@ Sessions: ``reset`` drops pending samples, filter history and counters with the 
 ``ingest_pending`` ((n, max_pending*hop) fp32, left-aligned, zeros after), ``ingest_fill``, ``ingest_in`` ((n,) int64) and
 ``resample_hist`` to the inner ``StreamState``, with meta ``input_rate``, ``resampler`` and ``ingest``.  What is stored is
 decoded: the encoding is no part of a state.
+
+Several formats on one scorer: ``MixedPacketScorer(scorer, formats)`` gives every slot its own (input_rate, encoding) out of
+up to 16, chosen at ``reset``.  The contract: let (r, e) be slot s's format.  Slot s's scores are, bit for bit, those of
+``PacketScorer(inner, r, e)`` fed the same packets -- the inner scorer's scores on ``Resampler(r)(decode(stream, e))`` --
+whatever formats the other slots have, however the packets were cut and in whatever order slots are named.  It holds
+because the format is a per-row value of the same launch (``afx_k_ingest_mixed``: the row's header names its format, the
+workgroup runs the one-format kernel's validation, decoder and tile body with that format's filter) and the host plans each
+row with its slot's own L, M and sample size.  A feed is still one upload, and one ingest launch plus one history launch
+per round whatever the number of formats; the slot pool and the inner scorer's batch are shared by all of them.  A mixed
+state carries the per-session ``ingest_rate`` ((n,) int64) in place of the meta's one ``input_rate``, ``resample_hist`` is
+(n, Hs) with Hs the widest T - 1 of the scorer's formats (zeros beyond a session's own), and the meta says ``ingest_mixed``.
 """
 import ctypes as C
 
@@ -32,13 +43,14 @@ import numpy as np
 import torch
 
 from ._layer import check_pending, export_pending, import_pending, peel, rows_on, wrap
-from ._lib import AfxError, call_on, check, lib, ptr
-from .resample import FILTER_ID
+from ._lib import AfxError, IngestFormat, call_on, check, lib, ptr
+from .resample import FILTER_ID, Resampler
 from .streaming import FeedResult, _Front  # noqa: F401  (FeedResult is part of this module's interface)
 
 ENCODINGS = ("pcm_f32le", "pcm_s16le", "mulaw", "alaw")  # the library's encoding numbers 0..3
 INGEST_FORMAT = 1  # layout of the ingest part of a StreamState: import_slots refuses any other
-HDR = 8  # int32 per afx_k_ingest row: slot, byte offset, n_in, n_out, p0, d0, wpos, 0
+HDR = 8  # int32 per afx_k_ingest row: slot, byte offset, n_in, n_out, p0, d0, wpos, 0 (afx_k_ingest_mixed: the format index)
+MAX_FORMATS = 16  # formats of one MixedPacketScorer (the table afx_k_ingest_mixed takes by value)
 ALIGN = 16  # every payload and table starts on a 16-byte boundary of the staging buffer
 _SAMPLE = {"pcm_f32le": np.dtype("<f4"), "pcm_s16le": np.dtype("<i2"), "mulaw": np.dtype("u1"), "alaw": np.dtype("u1")}
 _MAX_SAMPLES = 1 << 30
@@ -166,13 +178,25 @@ class PacketScorer(_Front):
         return torch.from_numpy(self._in.copy())
 
     # ---- planning (host arithmetic only) ---------------------------------------------------------------------------
+    def _ratios(self, slot):
+        """(L, M, bytes per sample, format index) of the slots ``slot``: int64 arrays over them."""
+        n = len(slot)
+        return (np.full(n, self.L, dtype=np.int64), np.full(n, self.M, dtype=np.int64),
+                np.full(n, _SAMPLE[self.encoding].itemsize, dtype=np.int64), np.zeros(n, dtype=np.int64))
+
+    def _payloads(self, packets, idx):
+        """-> (one block per named slot, their byte counts, their sample counts), each packet read in its slot's encoding."""
+        pay, nbytes = self._packets(packets, len(idx), self.encoding)
+        return pay, nbytes, nbytes // _SAMPLE[self.encoding].itemsize
+
     def _plan(self, idx, sizes, offs, score):
         """The launches of a feed / drain over the slots ``idx`` (sizes[i] new samples for idx[i], their payload at byte
         offs[i]; None: a drain) -> (ops, per-slot hop counts, the counters after it).  ops: ("ingest", header rows, the
         largest n_out) and ("pop", (A, 2) table of slot and ring head, the slots).  No state changes here.  int64 arrays over
         the named slots (distinct); the products stay below 2**63 for sessions of less than 2**48 samples."""
-        L, M, R, bps = self.L, self.M, self.ring_len, _SAMPLE[self.encoding].itemsize
+        R = self.ring_len
         slot = np.asarray(idx, dtype=np.int64).reshape(-1)
+        L, M, bps, fmt = self._ratios(slot)
         head, fill, nin = self._head[slot], self._fill[slot], self._in[slot]  # (copies: over the named slots from here on)
         size = np.zeros(len(idx), dtype=np.int64) if sizes is None else np.asarray(sizes, dtype=np.int64).reshape(-1)
         offs = np.zeros(len(idx), dtype=np.int64) if offs is None else np.asarray(offs, dtype=np.int64).reshape(-1)
@@ -181,14 +205,15 @@ class PacketScorer(_Front):
         ops = []
         while True:
             k = np.flatnonzero(done < size)
-            made = -(-nin[k] * L // M)
-            m = np.minimum(size[k] - done[k], (made + R - fill[k]) * M // L - nin[k])  # what the ring has room for
+            made = -(-nin[k] * L[k] // M[k])
+            m = np.minimum(size[k] - done[k], (made + R - fill[k]) * M[k] // L[k] - nin[k])  # what the ring has room for
             k, made, m = k[m > 0], made[m > 0], m[m > 0]
             if k.size:
-                n_out = -(-(nin[k] + m) * L // M) - made
+                Lk, Mk = L[k], M[k]
+                n_out = -(-(nin[k] + m) * Lk // Mk) - made
                 rows = np.zeros((k.size, HDR), dtype=np.int32)
-                for c, v in enumerate((slot[k], offs[k] + done[k] * bps, m, n_out, made * M % L, made * M // L - nin[k],
-                                       (head[k] + fill[k]) % R)):
+                for c, v in enumerate((slot[k], offs[k] + done[k] * bps[k], m, n_out, made * Mk % Lk, made * Mk // Lk - nin[k],
+                                       (head[k] + fill[k]) % R, fmt[k])):
                     rows[:, c] = v
                 ops.append(("ingest", rows, int(n_out.max())))
                 done[k] += m
@@ -214,11 +239,11 @@ class PacketScorer(_Front):
         score=False: the packets are decoded, resampled and buffered only (``drain`` scores them); a slot whose buffer would
         hold more than ``max_pending`` hops is a ValueError.  Everything is checked before anything changes.  -> FeedResult."""
         idx = self.scorer._slot_list(slots, ordered=True)
-        pay, nbytes = self._packets(packets, len(idx), self.encoding)
-        sizes = nbytes // _SAMPLE[self.encoding].itemsize
+        pay, nbytes, sizes = self._payloads(packets, idx)
         if not score and idx:
             N, n = self._in[idx], sizes
-            after = self._fill[idx] - (-(N + n) * self.L // self.M) + (-N * self.L // self.M)  # fill + n_out
+            L, M, _, _ = self._ratios(np.asarray(idx, dtype=np.int64))
+            after = self._fill[idx] - (-(N + n) * L // M) + (-N * L // M)  # fill + n_out
             over = np.flatnonzero(after > self.max_pending * self.hop)
             if over.size:
                 raise ValueError(f"slot {idx[over[0]]} would hold {after[over[0]]} pending samples, more than max_pending = "
@@ -233,13 +258,20 @@ class PacketScorer(_Front):
         idx = list(range(self.S)) if slots is None else self.scorer._slot_list(slots, ordered=True)
         return self._run(idx, [], None, None, True)
 
-    def _run(self, idx, pay, sizes, offs, score):
-        ops, counts, after = self._plan(idx, sizes, offs, score)
+    def _ingest(self):
+        """-> ingest(d, off, op): the launch of one ("ingest", rows, largest n_out) op whose table sits at byte ``off`` of the
+        uploaded buffer ``d``."""
         enc, (taps, L, M, T) = ENCODINGS.index(self.encoding), self._filter()
 
         def ingest(d, off, op):
             check(call_on(self.ring, lib().afx_k_ingest, _at(d, 0), d.numel(), _at(d, off), len(op[1]), int(op[2]), enc, taps, L, M,
                           T, ptr(self.hist) if T > 1 else None, ptr(self.ring), self.S, self.ring_len))
+
+        return ingest
+
+    def _run(self, idx, pay, sizes, offs, score):
+        ops, counts, after = self._plan(idx, sizes, offs, score)
+        ingest = self._ingest()
 
         def commit():
             self._head, self._fill, self._in = (np.array(v, dtype=np.int64) for v in after)
@@ -295,3 +327,207 @@ class PacketScorer(_Front):
             self._head[idx] = 0
             self._fill[idx] = fill
             self._in[idx] = nin
+
+
+def _format(f):
+    """One (input_rate, encoding) pair, checked -> (rate as an int, encoding)."""
+    from .resample import _rate
+    if isinstance(f, (str, bytes)) or not hasattr(f, "__len__") or len(f) != 2:
+        raise ValueError(f"a format is an (input_rate, encoding) pair, got {f!r}")
+    return _rate(f[0]), _encoding(f[1])
+
+
+class MixedPacketScorer(PacketScorer):
+    """``scorer`` fed encoded packets, every slot in its own format out of ``formats``: 1 to 16 distinct
+    (input_rate, encoding) pairs (rates as for ``Resampler``, encodings ``ENCODINGS``); see the module docstring for the
+    contract.  A slot's format is chosen at ``reset`` (a fresh scorer has every slot at format 0) and never changes between
+    resets.  ``feed``, ``drain``, ``samples_in``, ``pending`` and ``samples_seen`` are ``PacketScorer``'s."""
+
+    def __init__(self, scorer, formats, max_pending=4):
+        if isinstance(formats, (str, bytes)) or not hasattr(formats, "__len__") or not hasattr(formats, "__iter__"):
+            raise ValueError("formats: a sequence of (input_rate, encoding) pairs")
+        fm = tuple(_format(f) for f in formats)
+        if not 1 <= len(fm) <= MAX_FORMATS:
+            raise ValueError(f"{len(fm)} formats: 1 to {MAX_FORMATS}")
+        if len(set(fm)) != len(fm):
+            raise ValueError("formats: a format is listed twice")
+        if isinstance(max_pending, bool) or not isinstance(max_pending, int) or max_pending < 1:
+            raise ValueError("max_pending: a positive number of hops")
+        self.scorer, self.formats = scorer, fm
+        self._rs = {}  # one Resampler per rate, shared by the formats at that rate
+        for r, _ in fm:
+            if r not in self._rs:
+                self._rs[r] = Resampler(r, scorer.device)
+        rs = [self._rs[r] for r, _ in fm]
+        arr = lambda v: np.array(v, dtype=np.int64)
+        self._frate, self._fenc = arr([r for r, _ in fm]), arr([ENCODINGS.index(e) for _, e in fm])
+        self._fL, self._fM = arr([x.L for x in rs]), arr([x.M for x in rs])
+        self._fH = arr([0 if x.identity else x.T - 1 for x in rs])  # carried samples per format
+        self._fbps = arr([_SAMPLE[e].itemsize for _, e in fm])
+        self._fdelay = np.array([x.delay for x in rs], dtype=np.float64)
+        self._fname = np.array([e for _, e in fm], dtype=object)
+        self.Hs = int(self._fH.max())
+        self._table = (IngestFormat * len(fm))()  # afx_k_ingest_mixed's host table (the taps are the Resamplers' tensors)
+        for t, x, e in zip(self._table, rs, self._fenc.tolist()):
+            t.taps = None if x.identity else x.taps.data_ptr()
+            t.encoding, t.L, t.M, t.T = e, x.L, x.M, 1 if x.identity else x.T
+        self._new_ring(max_pending)
+        self.hist = torch.zeros(scorer.S, self.Hs, dtype=torch.float32, device=scorer.device)
+        self._head = np.zeros(scorer.S, dtype=np.int64)
+        self._fill = np.zeros(scorer.S, dtype=np.int64)
+        self._in = np.zeros(scorer.S, dtype=np.int64)
+        self._fmt = np.zeros(scorer.S, dtype=np.int64)  # format index of each slot (host)
+
+    # ---- per-slot formats ------------------------------------------------------------------------------------------------
+    @property
+    def format_of(self):
+        """(S,) int64: the index into ``formats`` of each slot's format."""
+        return torch.from_numpy(self._fmt.copy())
+
+    @property
+    def rates(self):
+        """(S,) int64: each slot's input rate in Hz."""
+        return torch.from_numpy(self._frate[self._fmt])
+
+    @property
+    def delays(self):
+        """(S,) float64: each slot's ``Resampler.delay``, the lag of its resampled stream in 16 kHz samples."""
+        return torch.from_numpy(self._fdelay[self._fmt])
+
+    @property
+    def delay(self):
+        raise AttributeError("a MixedPacketScorer has one delay per slot: delays")
+
+    def _index(self, f):
+        """A format given as an index into ``formats`` or as a pair -> its index."""
+        if isinstance(f, (int, np.integer)) and not isinstance(f, bool):
+            if not 0 <= f < len(self.formats):
+                raise ValueError(f"format index {f} outside 0..{len(self.formats) - 1}")
+            return int(f)
+        f = _format(f)
+        if f not in self.formats:
+            raise ValueError(f"format {f!r} is not one of this scorer's {self.formats}")
+        return self.formats.index(f)
+
+    def _indices(self, formats, n):
+        """``formats``: one format (index or pair) for n slots, or n of them -> (n,) int64 array of indices."""
+        def one(f):
+            return (isinstance(f, (int, np.integer)) and not isinstance(f, bool)) or (
+                isinstance(f, (tuple, list)) and len(f) == 2 and isinstance(f[1], str))
+        if isinstance(formats, torch.Tensor):
+            formats = formats.tolist()
+        if isinstance(formats, np.ndarray):
+            formats = formats.tolist()
+        if one(formats):
+            return np.full(n, self._index(formats), dtype=np.int64)
+        if isinstance(formats, (str, bytes)) or not hasattr(formats, "__len__"):
+            raise ValueError("formats: one format (an index or an (input_rate, encoding) pair) or one per named slot")
+        if len(formats) != n:
+            raise ValueError(f"{len(formats)} formats for {n} named slots")
+        return np.array([self._index(f) for f in formats], dtype=np.int64).reshape(n)
+
+    def _ratios(self, slot):
+        f = self._fmt[slot]
+        return self._fL[f], self._fM[f], self._fbps[f], f
+
+    def _payloads(self, packets, idx):
+        f = self._fmt[np.asarray(idx, dtype=np.int64)]
+        pay, nbytes = self._packets_each(packets, self._fname[f].tolist(), self._fbps[f])
+        return pay, nbytes, nbytes // self._fbps[f]
+
+    def _ingest(self):
+        nf, hist = len(self.formats), ptr(self.hist) if self.Hs else None
+
+        def ingest(d, off, op):
+            rows = op[1]
+            most = np.zeros(nf, dtype=np.int32)  # per format the largest n_out of this launch
+            for f in np.unique(rows[:, 7]).tolist():
+                most[f] = rows[rows[:, 7] == f, 3].max()
+            check(call_on(self.ring, lib().afx_k_ingest_mixed, _at(d, 0), d.numel(), _at(d, off), len(rows),
+                          C.cast(self._table, C.c_void_p), nf, most.ctypes.data_as(C.c_void_p), hist, self.Hs, ptr(self.ring),
+                          self.S, self.ring_len))
+
+        return ingest
+
+    # ---- sessions ----------------------------------------------------------------------------------------------------
+    def reset(self, slots, formats=None):
+        """The named slots begin a new stream in ``formats``: one format (an index into ``formats`` or a pair) for all of
+        them, or one per named slot; None keeps each slot's format.  Everything is checked before anything changes."""
+        idx = self.scorer._slot_list(slots, ordered=True)
+        new = None if formats is None else self._indices(formats, len(idx))
+        super().reset(idx)
+        if idx and new is not None:
+            self._fmt[idx] = new
+
+    def _meta(self):
+        return dict(resampler=FILTER_ID, ingest=INGEST_FORMAT, ingest_mixed=1)
+
+    def export_slots(self, slots):
+        """``PacketScorer.export_slots`` with the per-session ``ingest_rate`` ((n,) int64) and ``resample_hist`` (n, Hs),
+        zeros beyond each session's own T - 1 (module docstring).  No byte of the scorer changes."""
+        idx = self.scorer._slot_list(slots, ordered=True)
+        st = super().export_slots(idx)
+        return wrap(st, {}, ingest_rate=torch.from_numpy(self._frate[self._fmt[idx]]))
+
+    def import_slots(self, slots, state, formats=None):
+        """The named slots take over the sessions of ``state``: a state of a MixedPacketScorer, or of a plain
+        ``PacketScorer`` (one ``input_rate`` in its meta), with the same filter and ingest format.  ``formats``: the format
+        each session continues in (one for all or one per session, at the session's rate); default: this scorer's first
+        format at the session's rate.  A rate this scorer does not list, a format at another rate than the session's, a
+        history with non-zero columns beyond a session's own T - 1, pending samples beyond ``max_pending`` or counters that
+        contradict each other are a ValueError before anything changes."""
+        idx = self.scorer._slot_list(slots, ordered=True)
+        what = "packet-ingest part (it was not exported by a PacketScorer or a MixedPacketScorer)"
+        n = len(state) if hasattr(state, "seen") else 0
+        if hasattr(state, "meta") and "ingest_mixed" not in state.meta and "input_rate" in state.meta:  # a plain PacketScorer's
+            rate = state.meta["input_rate"]
+            inner = peel(state, _STATE_KEYS, dict(input_rate=rate, resampler=FILTER_ID, ingest=INGEST_FORMAT), what)
+            rates = np.full(n, rate, dtype=np.int64)
+        else:
+            inner = peel(state, _STATE_KEYS + ("ingest_rate",), self._meta(), what)
+            rates = state.tensors["ingest_rate"].cpu().reshape(-1)
+            if rates.dtype != torch.int64 or rates.numel() != n:
+                raise ValueError("import_slots: ingest_rate is (n,) int64")
+            rates = rates.numpy()
+        if len(idx) != n:
+            raise ValueError(f"the state holds {n} sessions for {len(idx)} named slots")
+        if formats is None:
+            first = {}
+            for i, (r, _) in enumerate(self.formats):
+                first.setdefault(r, i)
+            missing = [r for r in rates.tolist() if r not in first]
+            if missing:
+                raise ValueError(f"import_slots: a session at {missing[0]} Hz, which is none of this scorer's rates {sorted(first)}")
+            fmt = np.array([first[r] for r in rates.tolist()], dtype=np.int64)
+        else:
+            fmt = self._indices(formats, n)
+            bad = np.flatnonzero(self._frate[fmt] != rates)
+            if bad.size:
+                raise ValueError(f"import_slots: session {bad[0]} is at {rates[bad[0]]} Hz, format {self.formats[fmt[bad[0]]]!r} is not")
+        pend, h = state.tensors["ingest_pending"], state.tensors["resample_hist"]
+        fill, nin = state.tensors["ingest_fill"].cpu().reshape(-1), state.tensors["ingest_in"].cpu().reshape(-1)
+        if fill.dtype != torch.int64 or nin.dtype != torch.int64 or fill.numel() != n or nin.numel() != n:
+            raise ValueError("import_slots: ingest_fill / ingest_in are (n,) int64")
+        fill, nin = fill.numpy(), nin.numpy()
+        own = self._fH[fmt]  # each session's own T - 1
+        if h.ndim != 2 or h.shape[0] != n or h.dtype != torch.float32 or (n and h.shape[1] < own.max()):
+            raise ValueError(f"import_slots: resample_hist {tuple(h.shape)} {h.dtype} does not hold its sessions' carried samples "
+                             f"((n, >= {int(own.max()) if n else 0}) float32)")
+        if n and h.shape[1] and bool((h.cpu() * (torch.arange(h.shape[1])[None, :] >= torch.from_numpy(own)[:, None])).ne(0).any()):
+            raise ValueError("import_slots: resample_hist has non-zero columns beyond a session's own T - 1")
+        check_pending("ingest_pending", pend, fill, n, self.max_pending * self.hop)
+        made = np.array([-(-v * l // m) for v, l, m in zip(nin.tolist(), self._fL[fmt].tolist(), self._fM[fmt].tolist())], dtype=np.int64)
+        if (nin < 0).any() or not np.array_equal(made, state.seen.numpy() + fill):
+            raise ValueError("import_slots: a session's input count does not match its scored and pending samples")
+        self.scorer.import_slots(idx, inner)  # (refuses a foreign state before changing anything)
+        if idx:
+            import_pending(self.ring, idx, pend)
+            if self.Hs:
+                w = min(self.Hs, h.shape[1])
+                rows = rows_on(idx, self.device)
+                self.hist[rows] = 0.0
+                self.hist[rows, :w] = h[:, :w].to(self.device)
+            self._head[idx] = 0
+            self._fill[idx] = fill
+            self._in[idx] = nin
+            self._fmt[idx] = fmt

@@ -42,6 +42,12 @@ Sessions: ``export_slots`` adds ``jitter_pending`` / ``jitter_fill`` (pending 16
 columns [next - lookback, hi) left-aligned), ``jitter_book`` (origin, started, next, hi, open gap, largest start, last
 sequence number, SSRC), ``jitter_stats`` and ``jitter_intervals`` ((n, K, 2), -1 padded) to the inner state, with meta
 ``jitter`` (format), ``jitter_depth``, ``jitter_conceal``, ``jitter_period``, ``jitter_fade``, ``input_rate`` and ``resampler``.
+
+Several encodings at one clock rate: the reorder ring is decoded, so a session does not depend on how a packet was encoded.
+``JitterScorer(scorer, input_rate, ("mulaw", "alaw"), ...)`` lists the encodings its packets may come in: ``feed`` takes one
+per packet (``encodings``; default: the first listed), ``feed_rtp`` any datagram whose payload type maps to a listed one, and
+a stream may change between them from packet to packet.  The place rows then carry their encoding
+(``afx_k_jitter_place_mixed``: the same kernel with the encoding read per row).  State layout and contract are unchanged.
 """
 import numpy as np
 import torch
@@ -56,10 +62,12 @@ from .streaming import _Front
 JITTER_FORMAT = 1  # layout of the jitter part of a StreamState: import_slots refuses any other
 CONCEAL = ("zero", "repeat")  # the library's mode numbers 0, 1
 PLACE_HDR, CONCEAL_HDR, RELEASE_HDR = 4, 4, 8  # int32 per row of the three tables (include/afx.h)
+PLACE_MIXED_HDR = 5  # afx_k_jitter_place_mixed: a place row, then its encoding's number
 STATS = ("received", "late", "duplicate", "concealed", "out_of_order")
 _STATE_KEYS = ("jitter_pending", "jitter_fill", "jitter_ring", "jitter_book", "jitter_stats", "jitter_intervals")
 _BOOK = ("origin", "started", "next", "hi", "gap", "max_start", "max_seq", "ssrc")  # jitter_book columns
 _COUNTERS = ("received", "late", "dup", "concealed", "ooo")  # jitter_stats columns (STATS order)
+_BPS = np.array([_SAMPLE[e].itemsize for e in ENCODINGS], dtype=np.int64)  # bytes per sample by encoding number
 
 
 def _nonneg_int(v, name, least=0):
@@ -152,7 +160,8 @@ class Plan:
 
 class JitterScorer(_Front):
     """``scorer`` (a SlidingWindowScorer, IncrementalScorer or KVCachedScorer) fed timestamped packets at ``input_rate`` Hz
-    in ``encoding`` (``afx.ingest.ENCODINGS``); see the module docstring for the contract.
+    in ``encoding`` (``afx.ingest.ENCODINGS``; a tuple of them: any of these per packet, the first the default); see the
+    module docstring for the contract.
 
     ``depth``: the playout delay in input samples (60 ms is common; 0 is legal; the filter's ``delay`` comes on top of it).
     ``conceal``: "repeat" or "zero".  ``period``: the repeat period P in input samples, default 10 ms (input_rate // 100).  ``fade``: the fade length F in
@@ -163,7 +172,15 @@ class JitterScorer(_Front):
     _WORK = "decoded, concealed, resampled"
 
     def __init__(self, scorer, input_rate, encoding, depth, conceal="repeat", period=None, fade=None, max_pending=4, ts_bits=32):
-        self.encoding = _encoding(encoding)
+        if isinstance(encoding, str):
+            self.encodings, self._mixed = (_encoding(encoding),), False
+        else:
+            if not isinstance(encoding, (tuple, list)) or not encoding:
+                raise ValueError(f"encoding {encoding!r}: one of {ENCODINGS}, or a tuple of them")
+            self.encodings, self._mixed = tuple(_encoding(e) for e in encoding), True
+            if len(set(self.encodings)) != len(self.encodings):
+                raise ValueError("encoding: an encoding is listed twice")
+        self.encoding = self.encodings[0]
         self.depth = _nonneg_int(depth, "depth")
         if conceal not in CONCEAL:
             raise ValueError(f"conceal {conceal!r}: one of {CONCEAL}")
@@ -223,11 +240,13 @@ class JitterScorer(_Front):
         mod = 1 << self.ts_bits
         return ref + ((t - ref + mod // 2) % mod) - mod // 2
 
-    def _place_rows(self, b, slot, size, ts, offs, seqs):
+    def _place_rows(self, b, slot, size, ts, offs, seqs, encs=None):
         """Phase 1 of a feed: the bookkeeping of every row, in order -> placements (int64 arrays: slot, first index, n, byte
-        offset).  Rows that continue a hole-free slot at its ``hi`` (the common case) are handled for all slots at once;
-        the others one by one."""
-        bps = _SAMPLE[self.encoding].itemsize
+        offset, encoding number).  Rows that continue a hole-free slot at its ``hi`` (the common case) are handled for all
+        slots at once; the others one by one.  ``encs``: the encoding number of every row (None: this scorer's first)."""
+        if encs is None:
+            encs = np.full(slot.size, ENCODINGS.index(self.encoding), dtype=np.int64)
+        bps_of = _BPS[encs]
         once = np.bincount(slot, minlength=self.S)[slot] == 1
         ref = b.origin[slot] + b.hi[slot]
         rel = self._unwrap(ts, ref) - b.origin[slot]
@@ -244,7 +263,7 @@ class JitterScorer(_Front):
             b.hi[s] += n
             b.received[s] += n
             keep = n > 0
-            place.append(np.stack([s[keep], r[keep], n[keep], offs[fast][keep]]))
+            place.append(np.stack([s[keep], r[keep], n[keep], offs[fast][keep], encs[fast][keep]]))
         slow = []
         rest = np.flatnonzero(~fast)
         if rest.size:  # plain Python ints over the slots these rows name: read once, written back once
@@ -254,7 +273,8 @@ class JitterScorer(_Front):
                 dict(zip(ss.tolist(), getattr(b, f)[ss].tolist())) for f in keys)
             ivs_of = {}
             seq_rest = [None] * rest.size if seqs is None else seqs[rest].tolist()
-            for s, n, t, off, q in zip(slot[rest].tolist(), size[rest].tolist(), ts[rest].tolist(), offs[rest].tolist(), seq_rest):
+            for s, n, t, off, q, enc, bps in zip(slot[rest].tolist(), size[rest].tolist(), ts[rest].tolist(), offs[rest].tolist(), seq_rest,
+                                               encs[rest].tolist(), bps_of[rest].tolist()):
                 first = not started[s]
                 if first:
                     started[s], origin[s], r = 1, t, 0
@@ -281,7 +301,7 @@ class JitterScorer(_Front):
                 dup[s] += hi - lo - got
                 received[s] += got
                 for a, e in new:
-                    slow.append((s, a, e - a, off + (a - r) * bps))
+                    slow.append((s, a, e - a, off + (a - r) * bps, enc))
                 hi_[s] = max(hi_[s], hi)
                 ivs_of[s] = _merge([list(v) for v in ivs], new)
             order = ss.tolist()
@@ -291,7 +311,7 @@ class JitterScorer(_Front):
                 b.set_intervals(s, ivs)
         if slow:
             place.append(np.array(slow, dtype=np.int64).T)
-        return np.concatenate(place, axis=1) if place else np.zeros((4, 0), dtype=np.int64)
+        return np.concatenate(place, axis=1) if place else np.zeros((5, 0), dtype=np.int64)
 
     def _take_gaps(self, b, U, tgt):
         """Phase 2: the named slots U release [next, tgt) -> {position in U: [[origin, lo, hi], ...]} (the gaps of that
@@ -315,19 +335,19 @@ class JitterScorer(_Front):
             b.set_intervals(s, [[max(a, hi), e] for a, e in ivs if e > hi])
         return gaps
 
-    def _plan(self, slots, sizes=None, ts=None, offs=None, seqs=None, mode="feed", upto=None, score=True):
+    def _plan(self, slots, sizes=None, ts=None, offs=None, seqs=None, mode="feed", upto=None, score=True, encs=None):
         """The launches of a call over the rows ``slots`` (feed: sizes[i] samples with timestamp ts[i] and payload at byte
         offs[i] for slots[i], a slot possibly named more than once; flush / advance / drain: distinct slots) -> Plan.  No
         state changes here: ``_commit(plan.book)`` (or ``_run``) makes it so."""
         b = self._b.copy()
         L, M, R, hop, J, W, F = self.L, self.M, self.ring_len, self.hop, self.J, self.W, self.fade_len
-        bps = _SAMPLE[self.encoding].itemsize
         slot = np.asarray(slots, dtype=np.int64).reshape(-1)
         if mode == "feed":
             pl = self._place_rows(b, slot, np.asarray(sizes, dtype=np.int64).reshape(-1), np.asarray(ts, dtype=np.int64).reshape(-1),
-                                  np.asarray(offs, dtype=np.int64).reshape(-1), None if seqs is None else np.asarray(seqs, dtype=np.int64))
+                                  np.asarray(offs, dtype=np.int64).reshape(-1), None if seqs is None else np.asarray(seqs, dtype=np.int64),
+                                  None if encs is None else np.asarray(encs, dtype=np.int64).reshape(-1))
         else:
-            pl = np.zeros((4, 0), dtype=np.int64)
+            pl = np.zeros((5, 0), dtype=np.int64)
         _, first = np.unique(slot, return_index=True)
         first.sort()
         U = slot[first]  # the named slots, once each, in the order they were first named
@@ -354,7 +374,8 @@ class JitterScorer(_Front):
         gaps = self._take_gaps(b, U, tgt)
         pos = np.full(self.S, -1, dtype=np.int64)
         pos[U] = np.arange(U.size)
-        pu, pstart, pn, poff = pos[pl[0]], pl[1], pl[2], pl[3]
+        pu, pstart, pn, poff, penc = pos[pl[0]], pl[1], pl[2], pl[3], pl[4]
+        bps = _BPS[penc]
         pdone = np.zeros_like(pn)
         head, fill = b.head[U].copy(), b.fill[U].copy()
         counts = np.zeros(U.size, dtype=np.int64)
@@ -365,7 +386,8 @@ class JitterScorer(_Front):
             take = np.clip(cur[pu] + W - (pstart + pdone), 0, pn - pdone)
             k = np.flatnonzero(take > 0)
             if k.size:
-                rows = np.stack([U[pu[k]], poff[k] + pdone[k] * bps, take[k], (pstart[k] + pdone[k]) % J], axis=1).astype(np.int32)
+                cols = [U[pu[k]], poff[k] + pdone[k] * bps[k], take[k], (pstart[k] + pdone[k]) % J] + ([penc[k]] if self._mixed else [])
+                rows = np.stack(cols, axis=1).astype(np.int32)
                 ops.append(("place", rows, int(take[k].max())))
                 pdone[k] += take[k]
                 progress = True
@@ -447,30 +469,44 @@ class JitterScorer(_Front):
             raise ValueError(f"a timestamp outside {low}..{lim - 1}" + (f" (ts_bits = {self.ts_bits})" if self.ts_bits else ""))
         return vals.astype(np.int64)
 
-    def feed(self, packets, slots, timestamps, score=True, _seqs=None):
+    def feed(self, packets, slots, timestamps, score=True, _seqs=None, encodings=None):
         """packets[i]: a packet of slot slots[i] whose first sample has timestamp timestamps[i] (Python ints or an int64
         array, in input-rate samples), any length, in any order; a slot may be named more than once (its rows are taken in
         the order given).  Afterwards each named slot has released [next, max(next, hi - depth)).  score=True: every hop a
         named slot completes is scored; score=False: buffered only (``drain`` scores them; a slot whose buffer would hold
         more than ``max_pending`` hops is a ValueError).  Everything is checked before anything changes.  -> FeedResult
-        with one count per row of ``slots`` (a slot named twice has its hops at its first row)."""
-        return self._run(*self._plan_feed(packets, slots, timestamps, score, _seqs))
+        with one count per row of ``slots`` (a slot named twice has its hops at its first row).  ``encodings``: the encoding
+        of every packet, each one of this scorer's listed encodings (None: the first listed, for all)."""
+        return self._run(*self._plan_feed(packets, slots, timestamps, score, _seqs, encodings))
 
-    def _plan_feed(self, packets, slots, timestamps, score=True, seqs=None):
+    def _plan_feed(self, packets, slots, timestamps, score=True, seqs=None, encodings=None):
         """The checks and the plan of a ``feed`` -> (Plan, payload blocks).  No state changes."""
         idx = self._rows(slots, repeats=True)
-        pay, nbytes = self._packets(packets, len(idx), self.encoding)
+        if encodings is None:
+            pay, nbytes = self._packets(packets, len(idx), self.encoding)
+            encs, bps = None, _SAMPLE[self.encoding].itemsize
+        else:
+            if isinstance(encodings, str) or not hasattr(encodings, "__len__"):
+                raise ValueError("encodings: one encoding per packet")
+            encodings = list(encodings)
+            for e in encodings:
+                if e not in self.encodings:
+                    raise ValueError(f"encoding {e!r} is not one of this scorer's {self.encodings}")
+            if len(encodings) != len(idx):
+                raise ValueError(f"{len(encodings)} encodings for {len(idx)} named slots")
+            pay, nbytes = self._packets_each(packets, encodings)
+            encs = np.array([ENCODINGS.index(e) for e in encodings], dtype=np.int64)
+            bps = _BPS[encs]
         ts = self._timestamps(timestamps, len(idx))
-        bps = _SAMPLE[self.encoding].itemsize
         offs, total = layout(nbytes)
         if total >= 1 << 31:
             raise ValueError("a feed carries less than 2 GiB")
-        return self._plan(idx, nbytes // bps, ts, offs, seqs, "feed", score=score), pay
+        return self._plan(idx, nbytes // bps, ts, offs, seqs, "feed", score=score, encs=encs), pay
 
     def feed_rtp(self, datagrams, slots, payload_types=None, score=True):
-        """datagrams[i]: one RTP datagram (RFC 3550) of slot slots[i].  Its payload type must name this scorer's encoding:
-        0 is mulaw and 8 alaw (RFC 3551), ``payload_types`` ({number: encoding}) adds the dynamic ones; its SSRC must be the
-        session's (the first datagram after ``reset`` sets it).  Placement uses the timestamps; the sequence numbers only
+        """datagrams[i]: one RTP datagram (RFC 3550) of slot slots[i].  Its payload type must name this scorer's encoding (one
+        of its listed encodings): 0 is mulaw and 8 alaw (RFC 3551), ``payload_types`` ({number: encoding}) adds the dynamic
+        ones; its SSRC must be the session's (the first datagram after ``reset`` sets it).  Placement uses the timestamps; the sequence numbers only
         count packets out of order for ``stats()``.  Anything else is a ValueError before anything changes."""
         idx = self._rows(slots, repeats=True)
         if isinstance(datagrams, (bytes, bytearray, memoryview)):
@@ -483,12 +519,13 @@ class JitterScorer(_Front):
         types = {**rtp.STATIC_PAYLOAD_TYPES, **(payload_types or {})}
         ssrc = {}
         for s, p in zip(idx, pk):
-            if types.get(p.payload_type) != self.encoding:
-                raise ValueError(f"slot {s}: RTP payload type {p.payload_type} is not this scorer's {self.encoding}")
+            if types.get(p.payload_type) not in self.encodings:
+                raise ValueError(f"slot {s}: RTP payload type {p.payload_type} is not this scorer's {' / '.join(self.encodings)}")
             mine = ssrc.setdefault(s, int(self._b.ssrc[s]) if self._b.ssrc[s] >= 0 else p.ssrc)
             if p.ssrc != mine:
                 raise ValueError(f"slot {s}: SSRC {p.ssrc:#010x} is not the session's {mine:#010x}")
-        res = self.feed([p.payload for p in pk], idx, [p.timestamp for p in pk], score=score, _seqs=[p.seq for p in pk])
+        res = self.feed([p.payload for p in pk], idx, [p.timestamp for p in pk], score=score, _seqs=[p.seq for p in pk],
+                        encodings=[types[p.payload_type] for p in pk] if self._mixed else None)
         for s, v in ssrc.items():
             self._b.ssrc[s] = v
         return res
@@ -522,6 +559,10 @@ class JitterScorer(_Front):
         l, S, J = lib(), self.S, self.J
 
         def place(d, off, op):
+            if self._mixed:  # (the rows carry their encoding)
+                check(call_on(self.jring, l.afx_k_jitter_place_mixed, _at(d, 0), d.numel(), _at(d, off), len(op[1]), op[2],
+                              ptr(self.jring), S, J))
+                return
             check(call_on(self.jring, l.afx_k_jitter_place, _at(d, 0), d.numel(), _at(d, off), len(op[1]), op[2], enc, ptr(self.jring),
                           S, J))
 

@@ -166,6 +166,25 @@ class _Front:
             payload(out[i], encoding)  # (raises, with the message)
         return out, nbytes
 
+    @staticmethod
+    def _packets_each(packets, encodings, bps=None):
+        """``_packets`` with one encoding per packet (``encodings``: a list of names; ``bps``: their bytes per sample as an
+        int64 array, where the caller has it) -> (blocks, byte counts)."""
+        from .ingest import _MAX_SAMPLES, _SAMPLE, payload
+        if isinstance(packets, (bytes, bytearray, memoryview, np.ndarray, torch.Tensor)):
+            raise ValueError("packets: a list with one packet per named slot")
+        packets = list(packets)
+        if len(packets) != len(encodings):
+            raise ValueError(f"{len(packets)} packets for {len(encodings)} named slots")
+        if bps is None:
+            bps = np.fromiter((_SAMPLE[e].itemsize for e in encodings), dtype=np.int64, count=len(encodings))
+        out = packets if set(map(type, packets)) <= {bytes} else [
+            p if type(p) is bytes else payload(p, e) for p, e in zip(packets, encodings)]
+        nbytes = np.fromiter(map(len, out), dtype=np.int64, count=len(out))
+        for i in np.flatnonzero((nbytes % bps != 0) | (nbytes // bps >= _MAX_SAMPLES)):
+            payload(out[i], encodings[i])  # (raises, with the message)
+        return out, nbytes
+
     def _pop_rounds(self, ops, slots, head, fill, counts):
         """Planning: one ("pop", (A, 2) table of slot and ring head, the slots) op per round in which some of ``slots`` hold
         a whole hop; ``head``, ``fill`` and ``counts`` (int64 arrays over ``slots``) move with them -> rounds made."""

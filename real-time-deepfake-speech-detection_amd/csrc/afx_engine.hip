@@ -2932,6 +2932,13 @@ extern "C" int afx_k_ingest(const void* stage, long long stage_bytes, const int*
   KRET(launch_ingest(stage, stage_bytes, hdr, rows, max_out, encoding, taps, L, M, T, hist, ring, S, ring_len,
                      (hipStream_t)stream));
 }
+extern "C" int afx_k_ingest_mixed(const void* stage, long long stage_bytes, const int* hdr, int rows,
+                                  const afx_ingest_format* formats, int n_formats, const int* max_out, float* hist, int Hs,
+                                  float* ring, int S, int ring_len, void* stream) {
+  static_assert(sizeof(afx_ingest_format) == sizeof(IngestFormatDesc), "afx_ingest_format is IngestFormatDesc");
+  KRET(launch_ingest_mixed(stage, stage_bytes, hdr, rows, (const IngestFormatDesc*)formats, n_formats, max_out, hist, Hs, ring, S,
+                           ring_len, (hipStream_t)stream));
+}
 extern "C" int afx_k_ingest_pop(const float* ring, int S, int ring_len, const int* table, int A, int hop, float* out,
                                 void* stream) {
   KRET(launch_ingest_pop(ring, S, ring_len, table, A, hop, out, (hipStream_t)stream));
@@ -2939,6 +2946,10 @@ extern "C" int afx_k_ingest_pop(const float* ring, int S, int ring_len, const in
 extern "C" int afx_k_jitter_place(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n, int encoding,
                                   float* jring, int S, int J, void* stream) {
   KRET(launch_jitter_place(stage, stage_bytes, hdr, rows, max_n, encoding, jring, S, J, (hipStream_t)stream));
+}
+extern "C" int afx_k_jitter_place_mixed(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n,
+                                        float* jring, int S, int J, void* stream) {
+  KRET(launch_jitter_place_mixed(stage, stage_bytes, hdr, rows, max_n, jring, S, J, (hipStream_t)stream));
 }
 extern "C" int afx_k_jitter_conceal(float* jring, int S, int J, const int* hdr, int rows, int max_n, const float* fade, int P,
                                     int F, int mode, void* stream) {

@@ -891,11 +891,13 @@ struct PacketSource {
   }
 };
 
+// one row of an ingest launch; hs: the row stride of hist (T - 1, or the widest T - 1 of a scorer of several formats: a slot
+// then uses the first T - 1 columns of its row)
 template <bool IDENT, bool LDS_TAPS>
-__global__ __launch_bounds__(256) void ingest_kernel(IngestArgs a) {
+__device__ __forceinline__ void ingest_tiles(const IngestArgs& a, int row, int hs) {
   int slot, n_in, n_out, p0, d0, wpos;
   const unsigned char* pay;
-  if (!ingest_row(a, blockIdx.y, slot, pay, n_in, n_out, p0, d0, wpos)) return;
+  if (!ingest_row(a, row, slot, pay, n_in, n_out, p0, d0, wpos)) return;
   float* out = a.ring + (long long)slot * a.ring_len;
   if (IDENT) {
     for (int r = 0; r < a.f.R; ++r) {
@@ -908,17 +910,23 @@ __global__ __launch_bounds__(256) void ingest_kernel(IngestArgs a) {
   }
   if ((long long)blockIdx.x * a.f.R * RS_TILE >= n_out) return;  // (a short row of a ragged launch: no taps staged for it)
   const int H = a.f.T - 1;
-  polyphase_tiles<LDS_TAPS>(a.f, n_out, p0, d0, PacketSource{pay, a.enc, n_in, a.hist + (long long)slot * H, H},
+  polyphase_tiles<LDS_TAPS>(a.f, n_out, p0, d0, PacketSource{pay, a.enc, n_in, a.hist + (long long)slot * hs, H},
                             RingSink{out, wpos, a.ring_len});
 }
 
-__global__ __launch_bounds__(256) void ingest_hist_kernel(IngestArgs a) {
+__device__ __forceinline__ void ingest_hist_row(const IngestArgs& a, int row, int hs) {
   int slot, n_in, n_out, p0, d0, wpos;
   const unsigned char* pay;
-  if (!ingest_row(a, blockIdx.x, slot, pay, n_in, n_out, p0, d0, wpos)) return;
-  const int H = a.f.T - 1;
-  hist_shift(a.hist + (long long)slot * H, H, n_in, PacketSource{pay, a.enc, n_in, nullptr, 0});
+  if (!ingest_row(a, row, slot, pay, n_in, n_out, p0, d0, wpos)) return;
+  hist_shift(a.hist + (long long)slot * hs, a.f.T - 1, n_in, PacketSource{pay, a.enc, n_in, nullptr, 0});
 }
+
+template <bool IDENT, bool LDS_TAPS>
+__global__ __launch_bounds__(256) void ingest_kernel(IngestArgs a) {
+  ingest_tiles<IDENT, LDS_TAPS>(a, blockIdx.y, a.f.T - 1);
+}
+
+__global__ __launch_bounds__(256) void ingest_hist_kernel(IngestArgs a) { ingest_hist_row(a, blockIdx.x, a.f.T - 1); }
 
 const char* launch_ingest(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_out, int enc,
                           const float* taps, int L, int M, int T, float* hist, float* ring, int S, int ring_len,
@@ -947,6 +955,105 @@ const char* launch_ingest(const void* stage, long long stage_bytes, const int* h
   }
   if (T == 1) return nullptr;
   hipLaunchKernelGGL(ingest_hist_kernel, dim3(rows), dim3(256), 0, s, a);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+// ---------------------------------------------------------------------------------
+// Packet ingest over rows of different formats (afx/ingest.py MixedPacketScorer; include/afx.h afx_k_ingest_mixed): the
+// format (encoding, taps, L, M, T) is a per-row value, the eighth int of the row's header, instead of a launch-wide one.  The
+// table of a scorer's formats (at most ING_MAX_FORMATS) travels by value in the argument struct; a workgroup reads its row's
+// entry, makes the row's IngestArgs of it and runs ingest_tiles / ingest_hist_row above: the same validation, decoder, tile
+// body and history shift, so every output comes from the fmaf chain a one-format launch gives it.  The branch on the tap
+// placement is uniform per workgroup.  hist is (S, Hs), Hs >= every format's T - 1.
+// ---------------------------------------------------------------------------------
+constexpr int ING_MAX_FORMATS = 16;
+
+struct IngestFormat {
+  PolyFilter f;                  // Tp, R from poly_grid
+  int enc, lds_taps;             // taps == nullptr: the identity
+};
+
+struct IngestMixedArgs {
+  const unsigned char* stage;
+  long long stage_bytes;
+  const int* hdr;                // (rows, ING_HDR), the eighth int = the row's format
+  float* hist;                   // (S, Hs)
+  float* ring;                   // (S, ring_len)
+  int S, ring_len, Hs, nf;
+  IngestFormat fmt[ING_MAX_FORMATS];
+};
+
+// the launch's arguments as one row's format sees them; false for a format index outside the table
+__device__ __forceinline__ bool ingest_mixed_row(const IngestMixedArgs& m, int row, IngestArgs& a, int& lds_taps) {
+  const int fi = __builtin_amdgcn_readfirstlane(m.hdr[(long long)row * ING_HDR + 7]);
+  if (fi < 0 || fi >= m.nf) return false;
+  a.stage = m.stage; a.stage_bytes = m.stage_bytes; a.hdr = m.hdr; a.f = m.fmt[fi].f; a.hist = m.hist; a.ring = m.ring;
+  a.enc = m.fmt[fi].enc; a.S = m.S; a.ring_len = m.ring_len;
+  lds_taps = m.fmt[fi].lds_taps;
+  return true;
+}
+
+__global__ __launch_bounds__(256) void ingest_mixed_kernel(IngestMixedArgs m) {
+  IngestArgs a;
+  int lds_taps;
+  if (!ingest_mixed_row(m, blockIdx.y, a, lds_taps)) return;
+  if (!a.f.taps) ingest_tiles<true, false>(a, blockIdx.y, m.Hs);
+  else if (lds_taps) ingest_tiles<false, true>(a, blockIdx.y, m.Hs);
+  else ingest_tiles<false, false>(a, blockIdx.y, m.Hs);
+}
+
+__global__ __launch_bounds__(256) void ingest_mixed_hist_kernel(IngestMixedArgs m) {
+  IngestArgs a;
+  int lds_taps;
+  if (!ingest_mixed_row(m, blockIdx.x, a, lds_taps) || a.f.T == 1) return;
+  ingest_hist_row(a, blockIdx.x, m.Hs);
+}
+
+const char* launch_ingest_mixed(const void* stage, long long stage_bytes, const int* hdr, int rows, const IngestFormatDesc* formats,
+                                int n_formats, const int* max_out, float* hist, int Hs, float* ring, int S, int ring_len,
+                                hipStream_t s) {
+  if (n_formats < 1 || n_formats > ING_MAX_FORMATS) return "ingest_mixed: 1 to 16 formats";
+  if (!formats || !max_out) return "ingest_mixed: null format table or output counts";
+  IngestMixedArgs m{};
+  PolyGrid g[ING_MAX_FORMATS];
+  bool carried = false;
+  for (int i = 0; i < n_formats; ++i) {
+    const IngestFormatDesc& d = formats[i];
+    if (d.encoding < 0 || d.encoding > 3) return "ingest_mixed: encoding 0 (pcm_f32le), 1 (pcm_s16le), 2 (mulaw) or 3 (alaw)";
+    if (d.L <= 0 || d.M <= 0 || d.T <= 0) return "ingest_mixed: bad filter shape";
+    const bool ident = d.taps == nullptr;
+    if (ident && (d.L != 1 || d.M != 1 || d.T != 1)) return "ingest_mixed: bad filter shape (no taps is the identity, L = M = T = 1)";
+    if (d.T - 1 > 256) return "ingest_mixed: more than 256 carried samples";
+    m.fmt[i].f = PolyFilter{d.taps, d.L, d.M, d.T, 0, 0};
+    m.fmt[i].enc = d.encoding;
+    if (!poly_grid(m.fmt[i].f, ident, max_out[i] > 0 ? max_out[i] : 0, g[i])) return "ingest_mixed: input / output ratio above 12";
+    m.fmt[i].lds_taps = g[i].lds_taps;
+    carried = carried || d.T > 1;
+  }
+  if (!stage || !hdr || !ring || stage_bytes <= 0) return "ingest_mixed: null staging buffer, header table or ring";
+  if (rows <= 0 || rows > 65535) return "ingest_mixed: 1 to 65535 rows";
+  if (S <= 0 || ring_len <= 0) return "ingest_mixed: a row's outputs must fit its slot's ring";
+  long long gx = 0;
+  size_t lds = 0;
+  for (int i = 0; i < n_formats; ++i) {
+    if (max_out[i] < 0 || max_out[i] > ring_len) return "ingest_mixed: a row's outputs must fit its slot's ring";
+    if (formats[i].T - 1 > Hs) return "ingest_mixed: the history rows are narrower than a format's T - 1";
+    if (max_out[i] > 0) {
+      gx = g[i].gx > gx ? g[i].gx : gx;
+      lds = g[i].lds > lds ? g[i].lds : lds;
+    }
+  }
+  if (carried && !hist) return "ingest_mixed: null history";
+  m.stage = (const unsigned char*)stage; m.stage_bytes = stage_bytes; m.hdr = hdr; m.hist = hist; m.ring = ring;
+  m.S = S; m.ring_len = ring_len; m.Hs = Hs; m.nf = n_formats;
+  if (gx > 0) {
+    hipLaunchKernelGGL(ingest_mixed_kernel, dim3((unsigned)gx, rows), dim3(256), lds, s, m);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hipGetErrorString(e);
+  }
+  if (!carried) return nullptr;
+  hipLaunchKernelGGL(ingest_mixed_hist_kernel, dim3(rows), dim3(256), 0, s, m);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? nullptr : hipGetErrorString(e);
 }
@@ -991,13 +1098,13 @@ const char* launch_ingest_pop(const float* ring, int S, int ring_len, const int*
 //            16 kHz ring: outputs n_done .. of the stream, each with the bits afx_k_resample gives it over all of E.
 // ---------------------------------------------------------------------------------
 constexpr int JIT_PLACE_HDR = 4;    // ints per row: slot, byte offset of the first sample, n, ring column of the first sample
+constexpr int JIT_PLACE_MIXED_HDR = 5;  // the same four, then the row's encoding (afx_k_jitter_place_mixed)
 constexpr int JIT_CONCEAL_HDR = 4;  // ints per row: slot, ring column of the gap origin a, d_lo, d_hi
 constexpr int JIT_RELEASE_HDR = 8;  // ints per row: slot, ring column of a0, n_in, n_out, p0, d0, wpos, 0
 
-__global__ __launch_bounds__(256) void jitter_place_kernel(const unsigned char* __restrict__ stage, long long stage_bytes,
-                                                           const int* __restrict__ hdr, int enc, float* __restrict__ jring,
-                                                           int S, int J) {
-  const int* h = hdr + (long long)blockIdx.y * JIT_PLACE_HDR;
+// one row of a place launch: h[0..3] = slot, byte offset, n, column; enc the row's encoding (validated by the caller)
+__device__ __forceinline__ void jitter_place_row(const unsigned char* __restrict__ stage, long long stage_bytes, const int* h, int enc,
+                                                 float* __restrict__ jring, int S, int J) {
   const int slot = h[0], n = h[2], col = h[3];
   const long long off = h[1];
   const int bps = ingest_bytes_per_sample(enc);
@@ -1012,6 +1119,22 @@ __global__ __launch_bounds__(256) void jitter_place_kernel(const unsigned char* 
   }
 }
 
+__global__ __launch_bounds__(256) void jitter_place_kernel(const unsigned char* __restrict__ stage, long long stage_bytes,
+                                                           const int* __restrict__ hdr, int enc, float* __restrict__ jring,
+                                                           int S, int J) {
+  jitter_place_row(stage, stage_bytes, hdr + (long long)blockIdx.y * JIT_PLACE_HDR, enc, jring, S, J);
+}
+
+// the same with the encoding read per row (the fifth int of a JIT_PLACE_MIXED_HDR row); a row with a bad one is skipped whole
+__global__ __launch_bounds__(256) void jitter_place_mixed_kernel(const unsigned char* __restrict__ stage, long long stage_bytes,
+                                                                 const int* __restrict__ hdr, float* __restrict__ jring, int S,
+                                                                 int J) {
+  const int* h = hdr + (long long)blockIdx.y * JIT_PLACE_MIXED_HDR;
+  const int enc = h[4];
+  if (enc < 0 || enc > 3) return;
+  jitter_place_row(stage, stage_bytes, h, enc, jring, S, J);
+}
+
 const char* launch_jitter_place(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n, int enc,
                                 float* jring, int S, int J, hipStream_t s) {
   if (!stage || !hdr || !jring || stage_bytes <= 0) return "jitter_place: null staging buffer, header table or ring";
@@ -1021,6 +1144,18 @@ const char* launch_jitter_place(const void* stage, long long stage_bytes, const 
   if (max_n == 0) return nullptr;
   hipLaunchKernelGGL(jitter_place_kernel, dim3(min((max_n + 255) / 256, 64), rows), dim3(256), 0, s,
                      (const unsigned char*)stage, stage_bytes, hdr, enc, jring, S, J);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+const char* launch_jitter_place_mixed(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n, float* jring,
+                                      int S, int J, hipStream_t s) {
+  if (!stage || !hdr || !jring || stage_bytes <= 0) return "jitter_place_mixed: null staging buffer, header table or ring";
+  if (rows <= 0 || rows > 65535) return "jitter_place_mixed: 1 to 65535 rows";
+  if (S <= 0 || J <= 0 || max_n < 0 || max_n > J) return "jitter_place_mixed: a row's samples must fit its slot's ring";
+  if (max_n == 0) return nullptr;
+  hipLaunchKernelGGL(jitter_place_mixed_kernel, dim3(min((max_n + 255) / 256, 64), rows), dim3(256), 0, s,
+                     (const unsigned char*)stage, stage_bytes, hdr, jring, S, J);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? nullptr : hipGetErrorString(e);
 }

@@ -170,10 +170,20 @@ const char* launch_ingest(const void* stage, long long stage_bytes, const int* h
                           hipStream_t s);
 const char* launch_ingest_pop(const float* ring, int S, int ring_len, const int* table, int A, int hop, float* out,
                               hipStream_t s);
+// the same ingest over rows of different formats (include/afx.h afx_k_ingest_mixed): formats / max_out are HOST arrays of
+// n_formats entries (IngestFormatDesc has the layout of afx_ingest_format), the row's format is the eighth int of its header,
+// hist is (S, Hs)
+struct IngestFormatDesc { const float* taps; int encoding, L, M, T; };
+const char* launch_ingest_mixed(const void* stage, long long stage_bytes, const int* hdr, int rows, const IngestFormatDesc* formats,
+                                int n_formats, const int* max_out, float* hist, int Hs, float* ring, int S, int ring_len,
+                                hipStream_t s);
 // jitter buffer (include/afx.h afx_k_jitter_place / _conceal / _release): packet sub-ranges decoded into each slot's reorder
 // ring at their timestamps' columns; released gaps concealed in the ring; released samples resampled into the pending ring
 const char* launch_jitter_place(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n, int enc,
                                 float* jring, int S, int J, hipStream_t s);
+// (place with the encoding read per row: rows x 5 int32, the fifth the row's encoding)
+const char* launch_jitter_place_mixed(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n, float* jring,
+                                      int S, int J, hipStream_t s);
 const char* launch_jitter_conceal(float* jring, int S, int J, const int* hdr, int rows, int max_n, const float* fade, int P,
                                   int F, int mode, hipStream_t s);
 const char* launch_jitter_release(const float* jring, int S, int J, const int* hdr, int rows, int max_out, const float* taps,
