@@ -56,8 +56,51 @@ count hops of the gated stream, and with look-ahead the emission also lags the i
 frames can say where in the call a scored hop came from.  ``reset`` drops the line.  A caller that wants the tail of a
 finished call decided pushes one hop of zeros: zero frames are never speech, so they flag nothing.
 
+Call tones (``ToneGate``; also stated in include/afx.h, afx_k_gate_tone).  The first seconds of a call are ringback, dial or
+busy tone, IVR beeps, in-band DTMF, fax CNG / CED: loud, so the energy gate passes them as speech, and far outside anything
+an anti-spoof model was trained on.  ``ToneGate(floor, ratio, rise, hang, frame, freqs=TELEPHONY_TONES, frac=0.85,
+confirm=4, hold=3)`` is the plain gate (the first five parameters, the same checks, the same derived constants) plus a
+Goertzel bank per frame at ``freqs`` (1 to 16 distinct frequencies in Hz, 0 < f < 8000; the gate works at 16 kHz).
+``TELEPHONY_TONES`` is DTMF (697, 770, 852, 941, 1209, 1336, 1477, 1633), North American call progress (350, 440, 480, 620),
+ETSI call progress (425), the 1004 Hz test tone, fax CNG (1100) and fax CED / echo-canceller disable (2100).  ``frac`` is a
+finite fp32 number, 0 < frac <= 2; ``confirm`` >= 1 and ``hold`` >= 0 are frames.  Derived, each computed in float64 and
+rounded to fp32 once on the host: ``c_k = fp32(2 cos(2 pi f_k / 16000))`` and ``thr = fp32(frac * frame / 2)``.  A sinusoid
+of amplitude a over N samples has energy about a^2 N / 2 and Goertzel power about a^2 N^2 / 4, so ``T >= thr * e`` reads "at
+least ``frac`` of the frame's energy sits at one or two bank frequencies".  Per stream the state is the plain gate's ``nf``
+and ``h`` plus ``r`` (tonal frames in a row), ``q`` (hold frames left) and ``tones`` (tone frames since the reset), all 0 for
+a new stream.  Every arithmetic operation is a single correctly rounded fp32 multiply, add or subtract (no fma).  Per frame,
+in stream order::
+
+    e, speech, the nf update:  exactly the plain gate's (same energy order, same operations)
+
+    for every k:  s1 = s2 = +0.0
+                  for i = 0 .. frame-1:   t = c_k * s1;  t = t - s2;  s0 = x[i] + t;  s2 = s1;  s1 = s0
+                  a = s1 * s1;  b = s2 * s2;  m = c_k * s1;  m = m * s2;  P_k = (a + b) - m
+    p1, p2 = the two largest of { P_k : P_k > +0.0 } as a multiset (a NaN or non-positive P_k counts as +0.0;
+             fewer than two leave +0.0);   T = p1 + p2
+    tonal  = (e < inf) and e > E_floor and T >= thr * e            (one fp32 multiply; false for any NaN)
+
+    r = min(r + 1, 2^31 - 1) if tonal else 0
+    if r >= confirm:  q = hold
+    tone = r >= confirm or q > 0
+    if r < confirm and q > 0:  q -= 1
+    tones = min(tones + tone, 2^31 - 1)
+
+    if tone:    speech = False;  h = 0          # a tone is not speech and ends the hangover
+    if speech:  h = hang
+    keep = speech or h > 0
+    if not speech and h > 0:  h -= 1
+
+Invariants: ``r >= confirm`` implies ``q == hold``, and ``0 <= q <= hold``.  The gated stream is the concatenation of the
+kept frames, copied bit for bit, as for the plain gate.  Consequences: the first ``confirm - 1`` frames of a tone burst are
+still decided as the plain gate decides them and may be kept -- the gate has no look-ahead; exactly ``hold`` frames after the
+last confirmed frame are still tone, which bridges the beat nulls of 440 + 480 Hz ringback; a stream in which no frame is
+ever ``tonal`` is gated exactly as ``SpeechGate`` with the same first five parameters gates it.  The defaults are
+engineering defaults too, not tuned: there is no corpus in this repository.  ``ToneGate`` is not a ``LookaheadGate``:
+tone rejection behind the delay line (which could also drop the first ``confirm - 1`` frames of a burst) is not built.
+
 The contract of ``GatedScorer``: for a slot, let R be the concatenation of the hops it was pushed since its reset and G its
-gated stream (G' with a ``LookaheadGate``).  The slot's j-th non-NaN score equals, bit for bit, score j of a fresh inner
+gated stream (G' with a ``LookaheadGate``; G as the function above defines it with a ``ToneGate``).  The slot's j-th non-NaN score equals, bit for bit, score j of a fresh inner
 scorer of the same kind pushed G hop by hop, and it is emitted by the push in which sample ``(j + 1) * hop - 1`` of G was
 kept (emitted from the delay line).  Nothing depends on the other slots, on the order or subsets in which slots are named,
 or on session moves.  Behind a front, R is what that front's contract defines it to be.
@@ -71,11 +114,15 @@ import math
 import numpy as np
 import torch
 
-from ._layer import Layer, StreamState, _on, check_pending, export_pending, import_pending, need_gpu, rows_on, upload_pairs
+from ._layer import N_MAX, Layer, StreamState, _on, check_pending, export_pending, import_pending, need_gpu, rows_on, upload_pairs
 from ._lib import AfxError, call_on, check, lib, ptr
 
 GATE_FORMAT = 1  # layout of the gate part of a StreamState: import_slots refuses any other
 MAX_FRAMES = 512  # frames of a row one afx_k_gate launch takes (the library splits longer rows itself)
+MAX_TONES = 16  # frequencies of a ToneGate's bank (afx_k_gate_tone)
+# the telephone network's signalling frequencies in Hz: DTMF rows and columns, North American call progress (dial, ringback,
+# busy, reorder), ETSI call progress, the 1004 Hz test tone, fax CNG, fax CED / echo-canceller disable
+TELEPHONY_TONES = (697, 770, 852, 941, 1209, 1336, 1477, 1633, 350, 440, 480, 620, 425, 1004, 1100, 2100)
 
 
 def frame_energies(x, frame):
@@ -307,6 +354,176 @@ class LookaheadGate(SpeechGate):
         return res if len(res) > 1 else out
 
 
+class ToneGate(SpeechGate):
+    """The gate that also rejects call tones: a Goertzel bank at ``freqs`` per frame, ``confirm`` tonal frames in a row make
+    a tone, which lasts ``hold`` frames past the run; see the module docstring for the function.
+    ``GatedScorer(scorer, ToneGate())`` runs it streamed."""
+
+    def __init__(self, floor=1e-6, ratio=8.0, rise=1.01, hang=20, frame=160, freqs=TELEPHONY_TONES, frac=0.85, confirm=4, hold=3):
+        super().__init__(floor, ratio, rise, hang, frame)
+        if isinstance(freqs, (str, bytes)) or not isinstance(freqs, (tuple, list, np.ndarray)) or np.ndim(freqs) != 1:
+            raise ValueError(f"freqs {freqs!r}: 1 to {MAX_TONES} frequencies in Hz")
+        self.freqs = tuple(_number(f"freqs[{i}]", f) for i, f in enumerate(freqs))
+        if not 1 <= len(self.freqs) <= MAX_TONES:
+            raise ValueError(f"freqs: 1 to {MAX_TONES} frequencies, got {len(self.freqs)}")
+        if len(set(self.freqs)) != len(self.freqs):
+            raise ValueError(f"freqs {freqs!r}: a frequency is named twice")
+        if not all(0 < f < 8000 for f in self.freqs):
+            raise ValueError(f"freqs {freqs!r}: each above 0 and below 8000 Hz (the gate works at 16 kHz)")
+        self.frac = _number("frac", frac)
+        if not (0 < self.frac <= 2 and np.float32(self.frac) > 0):
+            raise ValueError(f"frac {frac!r}: an fp32 number above 0, at most 2")
+        self.confirm, self.hold = _number("confirm", confirm, integer=True), _number("hold", hold, integer=True)
+        if self.confirm < 1 or self.confirm >= 1 << 31:
+            raise ValueError(f"confirm {confirm!r}: a number of frames, 1 or more")
+        if self.hold < 0 or self.hold >= 1 << 31:
+            raise ValueError(f"hold {hold!r}: a number of frames, 0 or more")
+        self.coef = np.array([2.0 * math.cos(2.0 * math.pi * f / 16000.0) for f in self.freqs], dtype=np.float64).astype(np.float32)
+        self.thr = np.float32(self.frac * self.frame / 2)
+        if not (np.isfinite(self.thr) and self.thr > 0):
+            raise ValueError("frac * frame / 2 must be a positive fp32 number")
+
+    def params(self):
+        return dict(super().params(), freqs=list(self.freqs), frac=self.frac, confirm=self.confirm, hold=self.hold)
+
+    @staticmethod
+    def new_state():
+        return {"nf": np.float32(np.inf), "h": 0, "r": 0, "q": 0, "tones": 0}
+
+    # ---- the numpy restatement -------------------------------------------------------------------------------------------
+    def _frames(self, x):
+        x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+        if x.size % self.frame:
+            raise ValueError(f"{x.size} samples are not whole frames of {self.frame}")
+        return x.reshape(-1, self.frame)
+
+    def tone_powers(self, x):
+        """x: host fp32 array of whole frames -> (frames, K) fp32, the Goertzel power P_k of every frame at every bank
+        frequency, in the operation order the module docstring states."""
+        f = self._frames(x)
+        c = self.coef[None, :]
+        s1 = np.zeros((f.shape[0], c.shape[1]), dtype=np.float32)
+        s2 = s1.copy()
+        with np.errstate(all="ignore"):
+            for i in range(self.frame):
+                t = c * s1
+                t = t - s2
+                s0 = f[:, i, None] + t
+                s2 = s1
+                s1 = s0
+            a, b = s1 * s1, s2 * s2
+            m = c * s1
+            m = m * s2
+            return (a + b) - m
+
+    def _tone_sums(self, x):
+        """-> (frames,) fp32: T, the sum of the two largest positive powers of every frame."""
+        P = self.tone_powers(x)
+        with np.errstate(all="ignore"):
+            v = np.sort(np.where(P > 0, P, np.float32(0.0)).astype(np.float32), axis=1)
+            second = v[:, -2] if v.shape[1] > 1 else np.zeros(v.shape[0], dtype=np.float32)
+            return (v[:, -1] + second).astype(np.float32)
+
+    def _decide_tone(self, x, st):
+        """The per-frame decision over x (whole frames) from the state st -> (frames (m, frame), T, tonal, tone, keep, the
+        state after x)."""
+        frames = self._frames(x)
+        nf, h, r, q, tones = np.float32(st["nf"]), int(st["h"]), int(st["r"]), int(st["q"]), int(st["tones"])
+        E_floor, ratio, rise, nf_min, inf = self.E_floor, self.ratio32, self.rise32, self.nf_min, np.float32(np.inf)
+        top = (1 << 31) - 1
+        e_all, T_all = frame_energies(frames, self.frame), self._tone_sums(frames)
+        tonal_all, tone_all, keep_all = (np.zeros(e_all.size, dtype=bool) for _ in range(3))
+        with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+            for f, (e, T) in enumerate(zip(e_all, T_all)):
+                fin = bool(e < inf)
+                speech = fin and bool(e > max(E_floor, np.float32(ratio * nf)))
+                if fin:
+                    nf = max(nf_min, min(e, np.float32(nf * rise)))
+                tonal = fin and bool(e > E_floor) and bool(T >= np.float32(self.thr * e))
+                r = min(r + 1, top) if tonal else 0
+                if r >= self.confirm:
+                    q = self.hold
+                tone = r >= self.confirm or q > 0
+                if r < self.confirm and q > 0:
+                    q -= 1
+                tones = min(tones + tone, top)
+                if tone:
+                    speech, h = False, 0
+                if speech:
+                    h = self.hang
+                keep = speech or h > 0
+                if not speech and h > 0:
+                    h -= 1
+                tonal_all[f], tone_all[f], keep_all[f] = tonal, tone, keep
+        return frames, T_all, tonal_all, tone_all, keep_all, {"nf": np.float32(nf), "h": h, "r": r, "q": q, "tones": tones}
+
+    def gate_reference(self, x, state=None):
+        """The function in numpy.  x: host fp32 array of whole frames; state: what an earlier call returned (None: a new
+        stream; it is not modified) -> (keep_mask (frames,) bool, the kept samples, the state after x).  Chunked at any
+        frame boundaries with the state carried it gives what the whole stream gives."""
+        frames, _, _, _, keep, new = self._decide_tone(x, self.new_state() if state is None else state)
+        return keep, frames[keep].reshape(-1).copy(), new
+
+    def decide_reference(self, x, state=None):
+        """For tests and tuning: per frame of x (whole frames, from ``state``, None: a new stream) -> (T (frames,) fp32,
+        tonal, tone, keep: (frames,) bool)."""
+        return self._decide_tone(x, self.new_state() if state is None else state)[1:5]
+
+    # ---- the device form ---------------------------------------------------------------------------------------------------
+    def _launch_tone(self, x, hdr, coef, nf, h, tone_state, ring, kept, ntone=None, mask=None, tsum=None):
+        """afx_k_gate_tone over the rows of x ((A, n) fp32 on the GPU, contiguous) with this gate's constants; coef: this
+        gate's ``coef`` on x's device."""
+        check(call_on(x, lib().afx_k_gate_tone, ptr(x), x.shape[0], x.shape[1], ptr(hdr), self.frame, float(self.E_floor),
+                      float(self.ratio32), float(self.rise32), self.hang, ptr(coef), coef.numel(), float(self.thr), self.confirm,
+                      self.hold, ptr(nf), ptr(h), ptr(tone_state), ptr(ring), ring.shape[0], ring.shape[1], ptr(kept), ptr(ntone),
+                      ptr(mask), ptr(tsum)))
+
+    def gate(self, clips, return_mask=False, return_tones=False):
+        """The offline form: ``afx_k_gate_tone`` over whole clips, each with fresh state.  clips as for ``SpeechGate.gate``
+        -> the list of kept-audio tensors; with ``return_mask`` also the list of per-frame bool keep masks, with
+        ``return_tones`` also the list of per-frame bool tone masks.  Trailing samples short of a whole frame are dropped.
+        One launch sequence and one read-back of the counts per distinct clip length."""
+        clips = list(clips.unbind(0)) if isinstance(clips, torch.Tensor) and clips.ndim == 2 else list(clips)
+        for c in clips:
+            if not isinstance(c, torch.Tensor) or c.ndim != 1 or c.dtype != torch.float32:
+                raise ValueError("gate: a list of 1-D fp32 tensors or a (B, n) tensor")
+            if not c.is_cuda:
+                raise AfxError("the gate runs on the GPU; there is no CPU fallback (gate_reference is the numpy restatement)")
+        out, masks, tones = [None] * len(clips), [None] * len(clips), [None] * len(clips)
+        want = return_mask or return_tones
+        groups = {}
+        for i, c in enumerate(clips):
+            groups.setdefault((c.device, c.numel() // self.frame), []).append(i)
+        for (dev, frames), rows in groups.items():
+            if frames == 0:
+                for i in rows:
+                    out[i] = torch.empty(0, dtype=torch.float32, device=dev)
+                    masks[i] = torch.zeros(0, dtype=torch.bool, device=dev)
+                    tones[i] = torch.zeros(0, dtype=torch.bool, device=dev)
+                continue
+            n = frames * self.frame
+            with torch.cuda.device(dev):
+                coef = torch.from_numpy(self.coef).to(dev)
+                for lo in range(0, len(rows), 65535):
+                    part = rows[lo:lo + 65535]
+                    A = len(part)
+                    x = torch.stack([clips[i][:n] for i in part]).contiguous()
+                    hdr = torch.stack([torch.arange(A, dtype=torch.int32), torch.zeros(A, dtype=torch.int32)], dim=1).to(dev)
+                    nf = torch.full((A,), float("inf"), dtype=torch.float32, device=dev)
+                    h = torch.zeros(A, dtype=torch.int32, device=dev)
+                    tone_state = torch.zeros(A, 3, dtype=torch.int32, device=dev)
+                    ring = torch.empty(A, n, dtype=torch.float32, device=dev)
+                    kept = torch.zeros(A, dtype=torch.int32, device=dev)
+                    mask = torch.zeros(A, frames, dtype=torch.uint8, device=dev) if want else None
+                    self._launch_tone(x, hdr, coef, nf, h, tone_state, ring, kept, mask=mask)
+                    for r, (i, k) in enumerate(zip(part, kept.tolist())):
+                        out[i] = ring[r, :k].clone()
+                        if want:
+                            masks[i], tones[i] = (mask[r] & 1).bool(), (mask[r] & 2).bool()
+        res = (out,) + ((masks,) if return_mask else ()) + ((tones,) if return_tones else ())
+        return res if len(res) > 1 else out
+
+
 def emitted(scores):
     """``GatedScorer.push``'s result (or a FeedResult of a front around it) -> bool tensor: which entries are scores (a NaN
     stands for a push that completed no hop of speech)."""
@@ -336,7 +553,15 @@ class GatedScorer(Layer):
     frames, oldest first, zero frames in front where fewer than ``pre`` are delayed), ``gate_flags`` ((n,) int64, bit j =
     the j-th oldest delayed frame's flag) and ``gate_sources`` ((n, hop / frame) int64, the pending frames' source
     indices, -1 after the fill); flags beyond the delayed frames and sources that are not strictly increasing below the
-    oldest delayed frame are refused.  A plain-gate state and a look-ahead state refuse each other (``gate_params``)."""
+    oldest delayed frame are refused.  A plain-gate state and a look-ahead state refuse each other (``gate_params``).
+
+    With a ``ToneGate`` the push launches ``afx_k_gate_tone`` (the coefficient table is uploaded once, at construction; state
+    ``tone_state`` (S, 3) int32 = r, q, tones) -- still one gate launch, one read-back of A int32, one pop and one inner
+    push.  ``tone_frames`` is the (S,) int32 view on the device of the tone frames since each slot's reset and
+    ``last_tone_frames`` the (A,) int32 device tensor of the newest push's tone frames, in its row order (None with the
+    other gates).  A session's part then gains ``gate_tone`` ((n, 3) int64: r, q, tones); a negative r, a q outside
+    0..hold, ``r >= confirm`` with ``q != hold`` and a tones count that is negative or above the frames the session has seen
+    are refused.  A tone state and a plain or look-ahead state refuse each other (``gate_params``, ``gate_tone``)."""
 
     layer = "gate"
     _keys = ("gate_pending", "gate_fill", "gate_hang", "gate_inner_seen", "gate_nf")
@@ -360,7 +585,13 @@ class GatedScorer(Layer):
         self._fill = np.zeros(S, dtype=np.int64)  # pending kept samples per slot (host), always < hop between pushes
         self._seen = np.zeros(S, dtype=np.int64)  # samples pushed per slot since its reset (host)
         self._la = isinstance(gate, LookaheadGate)
+        self._tone = isinstance(gate, ToneGate)
         self.last_span = None
+        self.last_tone_frames = None
+        if self._tone:
+            self._keys = GatedScorer._keys + ("gate_tone",)
+            self.coef = torch.from_numpy(gate.coef.copy()).to(dev)
+            self.tone_state = torch.zeros(S, 3, dtype=torch.int32, device=dev)
         if self._la:
             self._keys = GatedScorer._keys + ("gate_line", "gate_flags", "gate_sources")
             self.flags = torch.zeros(S, dtype=torch.int32, device=dev)
@@ -382,6 +613,12 @@ class GatedScorer(Layer):
         """(S,) int64: the kept samples waiting for their hop to fill, always < hop."""
         return torch.from_numpy(self._fill.copy())
 
+    @property
+    def tone_frames(self):
+        """(S,) int32 view on the device: the tone frames a ``ToneGate`` rejected per slot since its reset (None with the
+        other gates)."""
+        return self.tone_state[:, 2] if self._tone else None
+
     emitted = staticmethod(emitted)
 
     def push(self, chunk, slots=None):
@@ -398,6 +635,8 @@ class GatedScorer(Layer):
         if not A:
             if la:
                 self.last_span = torch.empty(0, 2, dtype=torch.int64, device=dev)
+            if self._tone:
+                self.last_tone_frames = torch.empty(0, dtype=torch.int32, device=dev)
             return torch.empty(0, dtype=torch.float32, device=dev)
         slot = np.asarray(idx, dtype=np.int64)
         head, fill = self._head[slot], self._fill[slot]
@@ -411,6 +650,12 @@ class GatedScorer(Layer):
                 self.gate._launch_la(chunk.to(dev).contiguous(), hdr.to(dev, non_blocking=True), self.nf, self.h, self.flags,
                                      self.line, self.ring, self.src, kept)
                 span = torch.full((A, 2), -1, dtype=torch.int64, device=dev)
+            elif self._tone:
+                hdr = upload_pairs(slot, (head + fill) % self.ring_len, dev)
+                ntone = torch.empty(A, dtype=torch.int32, device=dev)
+                self.gate._launch_tone(chunk.to(dev).contiguous(), hdr, self.coef, self.nf, self.h, self.tone_state, self.ring,
+                                       kept, ntone=ntone)
+                self.last_tone_frames = ntone
             else:
                 hdr = upload_pairs(slot, (head + fill) % self.ring_len, dev)
                 self.gate._launch(chunk.to(dev).contiguous(), hdr, self.nf, self.h, self.ring, kept)
@@ -462,6 +707,8 @@ class GatedScorer(Layer):
                 if self._la:
                     self.flags[rows] = 0
                     self.src[rows] = -1
+                if self._tone:
+                    self.tone_state[rows] = 0
             self._head[idx] = 0
             self._fill[idx] = 0
             self._seen[idx] = 0
@@ -484,6 +731,8 @@ class GatedScorer(Layer):
                         gate_inner_seen=st.seen.clone(), gate_nf=self.nf[rows].clone())
             if self._la:
                 part.update(self._export_line(idx, rows))
+            if self._tone:
+                part["gate_tone"] = self.tone_state[rows].to("cpu", torch.int64)
             return part
 
     def _delayed(self, seen):
@@ -535,7 +784,23 @@ class GatedScorer(Layer):
         nf_host = nf.cpu()
         if bool(torch.isnan(nf_host).any()) or bool((nf_host < float(self.gate.nf_min)).any()):
             raise ValueError(f"import_slots: a session's noise floor is NaN or below the gate's minimum {float(self.gate.nf_min)!r}")
-        return (pend, nf, hang, fill, seen) + (self._check_line(t, n, fill, seen) if self._la else ())
+        return (pend, nf, hang, fill, seen) + (self._check_line(t, n, fill, seen) if self._la else ()) + (
+            self._check_tone(t, n, seen) if self._tone else ())
+
+    def _check_tone(self, t, n, seen):
+        tone = t["gate_tone"]
+        if tone.dtype != torch.int64 or tuple(tone.shape) != (n, 3):
+            raise ValueError(f"import_slots: gate_tone is {(n, 3)} int64")
+        r, q, tones = tone.cpu().numpy().T
+        if (r < 0).any() or (r > N_MAX).any():
+            raise ValueError("import_slots: a session's run of tonal frames is negative (or 2^31 or more)")
+        if ((q < 0) | (q > self.gate.hold)).any():
+            raise ValueError(f"import_slots: a session's tone hold is outside 0..{self.gate.hold} frames")
+        if ((r >= self.gate.confirm) & (q != self.gate.hold)).any():
+            raise ValueError("import_slots: a session inside a confirmed tone does not hold the full hold")
+        if ((tones < 0) | (tones > seen // self.gate.frame)).any():
+            raise ValueError("import_slots: a session counts more tone frames than it has seen frames (or fewer than 0)")
+        return (tone,)
 
     def _check_line(self, t, n, fill, seen):
         pre, frame, per = self.gate.pre, self.gate.frame, self.hop // self.gate.frame
@@ -577,6 +842,8 @@ class GatedScorer(Layer):
                     self.flags[dev_rows] = torch.from_numpy(dev_flags).to(dev)
                     self.src[dev_rows] = -1
                     self.src[dev_rows, :sources.shape[1]] = sources.to(dev, torch.int32)
+                if self._tone:
+                    self.tone_state[dev_rows] = rows[5].to(self.device, torch.int32)
             self._head[idx] = 0
             self._fill[idx] = fill
             self._seen[idx] = seen

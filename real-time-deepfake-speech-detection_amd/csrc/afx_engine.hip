@@ -2971,6 +2971,13 @@ extern "C" int afx_k_gate_la(const float* x, int A, int n, const int* hdr, int f
   KRET(launch_gate_la(x, A, n, hdr, frame, e_floor, ratio, rise, hang, pre, nf, h, flags, line, ring, src, S, ring_len, kept,
                       mask, (hipStream_t)stream));
 }
+extern "C" int afx_k_gate_tone(const float* x, int A, int n, const int* hdr, int frame, float e_floor, float ratio, float rise,
+                               int hang, const float* coef, int K, float thr, int confirm, int hold, float* nf, int* h,
+                               int* tone_state, float* ring, int S, int ring_len, int* kept, int* ntone, unsigned char* mask,
+                               float* tsum, void* stream) {
+  KRET(launch_gate_tone(x, A, n, hdr, frame, e_floor, ratio, rise, hang, coef, K, thr, confirm, hold, nf, h, tone_state, ring,
+                        S, ring_len, kept, ntone, mask, tsum, (hipStream_t)stream));
+}
 extern "C" int afx_k_cascade_store(const float* x, int A, int hop, const int* hdr, float* hist, int S, int window,
                                    void* stream) {
   KRET(launch_cascade_store(x, A, hop, hdr, hist, S, window, (hipStream_t)stream));

@@ -1507,6 +1507,195 @@ const char* launch_gate_la(const float* x, int A, int n, const int* hdr, int fra
 }
 
 // ---------------------------------------------------------------------------------
+// Tone gate (afx/vad.py ToneGate; the function is stated in include/afx.h afx_k_gate_tone): the plain gate's decision plus
+// a Goertzel bank of K <= 16 signalling frequencies per frame.  A frame whose two largest bank powers hold at least
+// thr * e is `tonal`; `confirm` tonal frames in a row make a tone, which lasts `hold` frames past the run; a tone frame is
+// not speech, is not kept and ends the hangover.  One workgroup per row, gate_kernel's three phases and one more:
+//   1. frame energies to LDS (gate_frame_energy, shared with gate_kernel);
+//   2. the (frame, k) pairs of the launch are spread over the 256 threads, k fastest (a frame's K lanes read one sample
+//      address): each pair runs the second-order recurrence over its frame's samples sequentially, three dependent fp32
+//      operations per sample with contraction off, and leaves its power in LDS; then one thread per frame folds the K
+//      powers into T = the sum of the two largest positive ones;
+//   3. thread 0 runs the state machine (nf, h, then r, q, tones) and writes offsets, mask and tsum;
+//   4. the copy of gate_kernel.
+// LDS at GATE_MAX_FRAMES: 3 tables of 512 x 4 bytes and the powers, 512 x 16 x 4 = 32 KB; 38 KB of a workgroup's 64 KB.
+// The samples are read eight at a time so that the loads run ahead of the dependent chain.
+// ---------------------------------------------------------------------------------
+constexpr int GATE_MAX_TONES = 16;  // frequencies of a bank (include/afx.h states it)
+
+struct GateToneArgs {
+  const float* x;     // (A, n) samples, row i = the next n samples of slot hdr[i][0]
+  const int* hdr;     // (A, 2): slot, wpos
+  const float* coef;  // (K,) 2 cos(2 pi f_k / 16000)
+  float* nf;          // (S,) noise floor per slot
+  int* h;             // (S,) hangover frames left per slot
+  int* tone_state;    // (S, 3): r (tonal frames in a row), q (hold frames left), tones (tone frames since the reset)
+  float* ring;        // (S, ring_len)
+  int* kept;          // (A,) samples kept of each row
+  int* ntone;         // (A,) tone frames of each row, or nullptr
+  unsigned char* mask;  // (A, n / frame) bit 0 keep, bit 1 tone, bit 2 tonal, or nullptr
+  float* tsum;        // (A, n / frame) T of every frame, or nullptr
+  int n, frame, f0, nframes;  // this launch: frames [f0, f0 + nframes) of the n / frame of a row
+  int S, ring_len, hang, K, confirm, hold;
+  float e_floor, ratio, rise, nf_min, thr;
+};
+
+// the Goertzel power of one frame at the coefficient c: every operation one correctly rounded fp32 multiply, add or subtract
+__device__ __forceinline__ float gate_tone_power(const float* __restrict__ x, int frame, float c) {
+#pragma clang fp contract(off)
+  float s1 = 0.f, s2 = 0.f;
+  int i = 0;
+  for (; i + 8 <= frame; i += 8) {
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = x[i + j];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float t = c * s1;
+      t = t - s2;
+      const float s0 = v[j] + t;
+      s2 = s1;
+      s1 = s0;
+    }
+  }
+  for (; i < frame; ++i) {
+    float t = c * s1;
+    t = t - s2;
+    const float s0 = x[i] + t;
+    s2 = s1;
+    s1 = s0;
+  }
+  const float a = s1 * s1, b = s2 * s2;
+  float m = c * s1;
+  m = m * s2;
+  const float ab = a + b;
+  return ab - m;
+}
+
+__global__ __launch_bounds__(256) void gate_tone_kernel(GateToneArgs a) {
+  __shared__ float s_e[GATE_MAX_FRAMES];
+  __shared__ float s_t[GATE_MAX_FRAMES];  // T of the frame
+  __shared__ int s_off[GATE_MAX_FRAMES];  // offset of the frame among this launch's kept samples, -1: dropped
+  __shared__ float s_p[GATE_MAX_FRAMES * GATE_MAX_TONES];  // power of pair f * K + k
+  __shared__ int s_base;                  // samples of the row kept by the launches before this one
+  const int row = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int slot = a.hdr[2 * row], wpos = a.hdr[2 * row + 1];
+  if (!(slot >= 0 && slot < a.S && wpos >= 0 && wpos < a.ring_len && a.n <= a.ring_len)) {
+    if (tid == 0 && a.f0 == 0) {
+      a.kept[row] = 0;
+      if (a.ntone) a.ntone[row] = 0;
+    }
+    return;
+  }
+  const float* x = a.x + (long long)row * a.n + (long long)a.f0 * a.frame;
+  for (int f = wave; f < a.nframes; f += 4) {
+    const float e = gate_frame_energy(x + (long long)f * a.frame, a.frame, lane);
+    if (lane == 0) s_e[f] = e;
+  }
+  const int K = a.K;
+  for (int p = tid; p < a.nframes * K; p += 256) {  // (nframes * K <= 512 * 16)
+    const int f = p / K, k = p - f * K;
+    s_p[p] = gate_tone_power(x + (long long)f * a.frame, a.frame, a.coef[k]);
+  }
+  __syncthreads();
+  for (int f = tid; f < a.nframes; f += 256) {
+    float p1 = 0.f, p2 = 0.f;  // the two largest positive powers (a NaN or non-positive power counts as +0.0)
+    for (int k = 0; k < K; ++k) {
+      const float v = s_p[f * K + k];
+      if (v > p1) {
+        p2 = p1;
+        p1 = v;
+      } else if (v > p2) {
+        p2 = v;
+      }
+    }
+    s_t[f] = p1 + p2;
+  }
+  __syncthreads();
+  if (tid == 0) {
+#pragma clang fp contract(off)
+    const long long frames = a.n / a.frame;
+    float nf = a.nf[slot];
+    int h = a.h[slot], off = 0, nt = 0;
+    int r = a.tone_state[3 * slot], q = a.tone_state[3 * slot + 1], tones = a.tone_state[3 * slot + 2];
+    for (int f = 0; f < a.nframes; ++f) {
+      const float e = s_e[f], T = s_t[f];
+      const bool fin = e < INFINITY;  // (false for a NaN too)
+      bool speech = fin && e > fmaxf(a.e_floor, a.ratio * nf);
+      if (fin) nf = fmaxf(a.nf_min, fminf(e, nf * a.rise));
+      const float bound = a.thr * e;
+      const bool tonal = fin && e > a.e_floor && T >= bound;
+      r = tonal ? (r < 0x7fffffff ? r + 1 : r) : 0;
+      if (r >= a.confirm) q = a.hold;
+      const bool tone = r >= a.confirm || q > 0;
+      if (r < a.confirm && q > 0) --q;
+      if (tone) {
+        if (tones < 0x7fffffff) ++tones;
+        ++nt;
+        speech = false;
+        h = 0;
+      }
+      if (speech) h = a.hang;
+      const bool keep = speech || h > 0;
+      if (!speech && h > 0) --h;
+      s_off[f] = keep ? off : -1;
+      if (keep) off += a.frame;
+      if (a.mask) a.mask[row * frames + a.f0 + f] = (unsigned char)((keep ? 1 : 0) | (tone ? 2 : 0) | (tonal ? 4 : 0));
+      if (a.tsum) a.tsum[row * frames + a.f0 + f] = T;
+    }
+    const int base = a.f0 ? a.kept[row] : 0;
+    a.nf[slot] = nf;
+    a.h[slot] = h;
+    a.tone_state[3 * slot] = r;
+    a.tone_state[3 * slot + 1] = q;
+    a.tone_state[3 * slot + 2] = tones;
+    a.kept[row] = base + off;
+    if (a.ntone) a.ntone[row] = (a.f0 ? a.ntone[row] : 0) + nt;
+    s_base = base;
+  }
+  __syncthreads();
+  float* out = a.ring + (long long)slot * a.ring_len;
+  const long long w0 = (long long)wpos + s_base;  // base + off + k < n <= ring_len: one wrap
+  for (int f = wave; f < a.nframes; f += 4) {
+    const int off = s_off[f];
+    if (off < 0) continue;
+    const float* src = x + (long long)f * a.frame;
+    for (int k = lane; k < a.frame; k += 64) {
+      const long long w = w0 + off + k;
+      out[w < a.ring_len ? w : w - a.ring_len] = src[k];
+    }
+  }
+}
+
+const char* launch_gate_tone(const float* x, int A, int n, const int* hdr, int frame, float e_floor, float ratio, float rise,
+                             int hang, const float* coef, int K, float thr, int confirm, int hold, float* nf, int* h,
+                             int* tone_state, float* ring, int S, int ring_len, int* kept, int* ntone, unsigned char* mask,
+                             float* tsum, hipStream_t s) {
+  if (!x || !hdr || !coef || !nf || !h || !tone_state || !ring || !kept) return "gate_tone: null argument";
+  if (A <= 0 || A > 65535) return "gate_tone: 1 to 65535 rows";
+  if (frame <= 0 || n <= 0 || n % frame) return "gate_tone: a row is a positive whole number of frames";
+  if (S <= 0 || ring_len <= 0) return "gate_tone: no slots or no ring";
+  if (!(e_floor > 0.f && e_floor < INFINITY && ratio > 1.f && ratio < INFINITY && rise >= 1.f && rise < INFINITY) || hang < 0)
+    return "gate_tone: floor > 0, ratio > 1, rise >= 1 (all finite) and hang >= 0";
+  if (K < 1 || K > GATE_MAX_TONES) return "gate_tone: a bank of 1 to 16 frequencies";
+  if (!(thr > 0.f && thr < INFINITY) || confirm < 1 || hold < 0)
+    return "gate_tone: thr > 0 (finite), confirm >= 1 and hold >= 0";
+  GateToneArgs a{};
+  a.x = x; a.hdr = hdr; a.coef = coef; a.nf = nf; a.h = h; a.tone_state = tone_state; a.ring = ring; a.kept = kept;
+  a.ntone = ntone; a.mask = mask; a.tsum = tsum;
+  a.n = n; a.frame = frame; a.S = S; a.ring_len = ring_len; a.hang = hang; a.K = K; a.confirm = confirm; a.hold = hold;
+  a.e_floor = e_floor; a.ratio = ratio; a.rise = rise; a.nf_min = e_floor / ratio;  // (one IEEE fp32 division, on the host)
+  a.thr = thr;
+  const int frames = n / frame;
+  for (a.f0 = 0; a.f0 < frames; a.f0 += GATE_MAX_FRAMES) {
+    a.nframes = min(GATE_MAX_FRAMES, frames - a.f0);
+    hipLaunchKernelGGL(gate_tone_kernel, dim3(A), dim3(256), 0, s, a);
+  }
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+// ---------------------------------------------------------------------------------
 // Cascade (afx/cascade.py; the functions are stated in include/afx.h afx_k_cascade_store / _select / _windows): a cheap
 // screen scores every slot at every hop, and the windows of the slots whose score looks suspicious are gathered for a
 // second model.  Three launches per push, every index from a host-built header:

@@ -199,6 +199,13 @@ const char* launch_gate(const float* x, int A, int n, const int* hdr, int frame,
 const char* launch_gate_la(const float* x, int A, int n, const int* hdr, int frame, float e_floor, float ratio, float rise,
                            int hang, int pre, float* nf, int* h, int* flags, float* line, float* ring, int* src, int S,
                            int ring_len, int* kept, unsigned char* mask, hipStream_t s);
+// tone gate (include/afx.h afx_k_gate_tone): the plain gate plus a Goertzel bank of K <= 16 frequencies (coef, device) per
+// frame; a confirmed tone (tone_state (S, 3): r, q, tones) is not speech, is not kept and ends the hangover; ntone, mask
+// (bit 0 keep, bit 1 tone, bit 2 tonal) and tsum are optional outputs
+const char* launch_gate_tone(const float* x, int A, int n, const int* hdr, int frame, float e_floor, float ratio, float rise,
+                             int hang, const float* coef, int K, float thr, int confirm, int hold, float* nf, int* h,
+                             int* tone_state, float* ring, int S, int ring_len, int* kept, int* ntone, unsigned char* mask,
+                             float* tsum, hipStream_t s);
 // cascade (include/afx.h afx_k_cascade_store / _select / _windows): the named slots' hops into the retained-audio ring; the
 // candidates among the rows ranked by (score, slot), the first `budget` row positions into sel, the cooldown counters
 // advanced; the windows of the rows sel names gathered from the ring (sel is read on the device)
