@@ -708,50 +708,40 @@ static void launch_mhsa_t(const void* qkv, void* out, int B, int T, int H, float
     hipLaunchKernelGGL((mhsa_kernel<HT, 7, 7>), grid, dim3(448), 0, s, (const Tt*)qkv, (Tt*)out, T, H, scale, lens, MhsaRing{});
 }
 
-// KV-cached streaming attention (see MhsaRing): ring (S, 256 slots, 3 H 64) operand type, out (S, 16, H 64); cnt[16] = valid
-// frames per 16-slot group, q_tile = the group of the newest chunk.
+// KV-cached streaming attention (see MhsaRing): ring (S, 256 slots, 3 H 64) operand type, out (S, 16, H 64).  The form
+// (MhsaRingForm, afx_kernels.h) says where the valid counts and the query tile come from; the checks are made once, here.
 #undef ring_qtile
-const char* launch_mhsa_ring(const void* ring, void* out, int S, int H, int q_tile, const int* cnt, int dtype, hipStream_t s) {
-  if (S <= 0 || S > 65535 || H <= 0 || q_tile < 0 || q_tile > 15) return "mhsa_ring: bad shape";
-  if (dtype != DT_FP16 && dtype != DT_BF16) return "mhsa_ring: half-precision operands only";
-  MhsaRing r;
-  r.q_tile = q_tile;
-  for (int i = 0; i < 16; ++i) {
-    if (cnt[i] < 0 || cnt[i] > 16) return "mhsa_ring: a group holds at most 16 frames";
-    r.cnt[i] = (unsigned char)cnt[i];
+static const char* ring_args(int S, int H, const MhsaRingForm& f, bool dtype_ok, MhsaRing* r) {
+  if (S <= 0 || S > 65535 || H <= 0 || f.form < 1 || f.form > 3) return "mhsa_ring: bad shape";
+  if (f.form < 3 && (f.q_tile < 0 || f.q_tile > 15)) return "mhsa_ring: bad shape";
+  if (f.form == 1 ? !f.cnt : !f.tab) return "mhsa_ring: bad shape";
+  if (!dtype_ok) return "mhsa_ring: half-precision operands only";
+  *r = MhsaRing{};
+  if (f.form < 3) r->q_tile = f.q_tile;
+  for (int i = 0; f.form == 1 && i < 16; ++i) {
+    if (f.cnt[i] < 0 || f.cnt[i] > 16) return "mhsa_ring: a group holds at most 16 frames";
+    r->cnt[i] = (unsigned char)f.cnt[i];
   }
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((mhsa_kernel<BF16, 8, 4, true, true>), dim3(H, S, 1), dim3(256), 0, s, (const BF16::T*)ring, (BF16::T*)out, 256, H, 0.125f, nullptr, r);
-  else
-    hipLaunchKernelGGL((mhsa_kernel<FP16, 8, 4, true, true>), dim3(H, S, 1), dim3(256), 0, s, (const FP16::T*)ring, (FP16::T*)out, 256, H, 0.125f, nullptr, r);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+  return nullptr;
 }
-
-// the per-stream form (RING == 2): tab = (S, 8) ints per stream, [0] base group, bytes [16, 32) the 16 valid counts
-const char* launch_mhsa_ring_tab(const void* ring, void* out, int S, int H, int q_tile, const int* tab, int dtype, hipStream_t s) {
-  if (S <= 0 || S > 65535 || H <= 0 || q_tile < 0 || q_tile > 15 || !tab) return "mhsa_ring: bad shape";
-  if (dtype != DT_FP16 && dtype != DT_BF16) return "mhsa_ring: half-precision operands only";
-  MhsaRing r = {};
-  r.q_tile = q_tile;
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((mhsa_kernel<BF16, 8, 4, 2, true>), dim3(H, S, 1), dim3(256), 0, s, (const BF16::T*)ring, (BF16::T*)out, 256, H, 0.125f, tab, r);
+template <class HT>
+static void launch_mhsa_ring_t(const void* ring, void* out, int S, int H, int form, const int* tab, const MhsaRing& r, hipStream_t s) {
+  using Tt = typename HT::T;
+  const dim3 grid(H, S, 1), blk(256);
+  if (form == 1)
+    hipLaunchKernelGGL((mhsa_kernel<HT, 8, 4, true, true>), grid, blk, 0, s, (const Tt*)ring, (Tt*)out, 256, H, 0.125f, nullptr, r);
+  else if (form == 2)
+    hipLaunchKernelGGL((mhsa_kernel<HT, 8, 4, 2, true>), grid, blk, 0, s, (const Tt*)ring, (Tt*)out, 256, H, 0.125f, tab, r);
   else
-    hipLaunchKernelGGL((mhsa_kernel<FP16, 8, 4, 2, true>), dim3(H, S, 1), dim3(256), 0, s, (const FP16::T*)ring, (FP16::T*)out, 256, H, 0.125f, tab, r);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+    hipLaunchKernelGGL((mhsa_kernel<HT, 8, 4, 3, true>), grid, blk, 0, s, (const Tt*)ring, (Tt*)out, 256, H, 0.125f, tab, r);
 }
-
-// the active-list form (RING == 3): S = list length, tab = (S, 8) ints per list entry -- [0] base group, [1] the stream's newest
-// group, [2] its ring index, bytes [16, 32) its 16 valid counts
-const char* launch_mhsa_ring_active(const void* ring, void* out, int S, int H, const int* tab, int dtype, hipStream_t s) {
-  if (S <= 0 || S > 65535 || H <= 0 || !tab) return "mhsa_ring: bad shape";
-  if (dtype != DT_FP16 && dtype != DT_BF16) return "mhsa_ring: half-precision operands only";
-  MhsaRing r = {};
+const char* launch_mhsa_ring(const void* ring, void* out, int S, int H, const MhsaRingForm& f, int dtype, hipStream_t s) {
+  MhsaRing r;
+  if (const char* m = ring_args(S, H, f, dtype == DT_FP16 || dtype == DT_BF16, &r)) return m;
   if (dtype == DT_BF16)
-    hipLaunchKernelGGL((mhsa_kernel<BF16, 8, 4, 3, true>), dim3(H, S, 1), dim3(256), 0, s, (const BF16::T*)ring, (BF16::T*)out, 256, H, 0.125f, tab, r);
+    launch_mhsa_ring_t<BF16>(ring, out, S, H, f.form, f.tab, r, s);
   else
-    hipLaunchKernelGGL((mhsa_kernel<FP16, 8, 4, 3, true>), dim3(H, S, 1), dim3(256), 0, s, (const FP16::T*)ring, (FP16::T*)out, 256, H, 0.125f, tab, r);
+    launch_mhsa_ring_t<FP16>(ring, out, S, H, f.form, f.tab, r, s);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? nullptr : hipGetErrorString(e);
 }
@@ -769,18 +759,19 @@ const char* launch_mhsa_split(const float* qkv, float* out, int B, int T, int H,
   return e == hipSuccess ? nullptr : hipGetErrorString(e);
 }
 
-// the ring form in split precision: fp32 [q | k | v] slots in, fp32 rows (or pair-form rows) out -- (S, 16, H*64)
-const char* launch_mhsa_ring_split(const float* ring, float* out, int S, int H, int q_tile, const int* cnt, hipStream_t s, bool out_pairs,
+// the ring forms in split precision: fp32 [q | k | v] slots in, fp32 rows (or pair-form rows) out -- (S, 16, H*64)
+const char* launch_mhsa_ring_split(const float* ring, float* out, int S, int H, const MhsaRingForm& f, hipStream_t s, bool out_pairs,
                                    float out_scale) {
-  if (S <= 0 || S > 65535 || H <= 0 || q_tile < 0 || q_tile > 15) return "mhsa_ring: bad shape";
   MhsaRing r;
-  r.q_tile = q_tile;
-  for (int i = 0; i < 16; ++i) {
-    if (cnt[i] < 0 || cnt[i] > 16) return "mhsa_ring: a group holds at most 16 frames";
-    r.cnt[i] = (unsigned char)cnt[i];
-  }
-  hipLaunchKernelGGL((mhsa_split_kernel<8, 4, true>), dim3(H, S, 1), dim3(256), 0, s, ring, out, 256, H, 0.125f, nullptr, out_pairs ? 1 : 0,
-                     out_scale, r);
+  if (const char* m = ring_args(S, H, f, true, &r)) return m;
+  const dim3 grid(H, S, 1), blk(256);
+  const int pairs = out_pairs ? 1 : 0;
+  if (f.form == 1)
+    hipLaunchKernelGGL((mhsa_split_kernel<8, 4, true>), grid, blk, 0, s, ring, out, 256, H, 0.125f, nullptr, pairs, out_scale, r);
+  else if (f.form == 2)
+    hipLaunchKernelGGL((mhsa_split_kernel<8, 4, 2>), grid, blk, 0, s, ring, out, 256, H, 0.125f, f.tab, pairs, out_scale, r);
+  else
+    hipLaunchKernelGGL((mhsa_split_kernel<8, 4, 3>), grid, blk, 0, s, ring, out, 256, H, 0.125f, f.tab, pairs, out_scale, r);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? nullptr : hipGetErrorString(e);
 }
@@ -797,30 +788,6 @@ const char* launch_mhsa(const void* qkv, void* out, int B, int T, int H, int dty
     launch_mhsa_t<BF16>(qkv, out, B, T, H, scale, lens, s);
   else
     launch_mhsa_t<FP16>(qkv, out, B, T, H, scale, lens, s);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? nullptr : hipGetErrorString(e);
-}
-
-// the per-stream form of the split-precision ring (see launch_mhsa_ring_tab)
-const char* launch_mhsa_ring_split_tab(const float* ring, float* out, int S, int H, int q_tile, const int* tab, hipStream_t s, bool out_pairs,
-                                       float out_scale) {
-  if (S <= 0 || S > 65535 || H <= 0 || q_tile < 0 || q_tile > 15 || !tab) return "mhsa_ring: bad shape";
-  MhsaRing r = {};
-  r.q_tile = q_tile;
-  hipLaunchKernelGGL((mhsa_split_kernel<8, 4, 2>), dim3(H, S, 1), dim3(256), 0, s, ring, out, 256, H, 0.125f, tab, out_pairs ? 1 : 0,
-                     out_scale, r);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? nullptr : hipGetErrorString(e);
-}
-
-
-// the active-list form of the split-precision ring (see launch_mhsa_ring_active)
-const char* launch_mhsa_ring_split_active(const float* ring, float* out, int S, int H, const int* tab, hipStream_t s, bool out_pairs,
-                                          float out_scale) {
-  if (S <= 0 || S > 65535 || H <= 0 || !tab) return "mhsa_ring: bad shape";
-  MhsaRing r = {};
-  hipLaunchKernelGGL((mhsa_split_kernel<8, 4, 3>), dim3(H, S, 1), dim3(256), 0, s, ring, out, 256, H, 0.125f, tab, out_pairs ? 1 : 0,
-                     out_scale, r);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? nullptr : hipGetErrorString(e);
 }

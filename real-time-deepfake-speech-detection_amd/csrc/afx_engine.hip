@@ -1062,6 +1062,21 @@ static RowNormArgs plain_norm(const float* x, long ldx, int rows, int C, const f
     if (e->taps_on && tap(e, std::string(nm).c_str(), (p), (n), (op), s, (ld))) return 1; \
   } while (0)
 
+// the positional conv as a grouped product (chunked K over time-padded operand rows) + GELU, added to x in place: `rows` =
+// the first operand row of utterance 0's output frame 0, `batch_rows` operand rows from one utterance to the next, B x T frames
+static const char* posconv_product(afx_engine* e, const void* rows, long batch_rows, int B, int T, float* x, int dt, hipStream_t s) {
+  const int cpg = kD / kPosG;
+  GemmArgs g = plain_gemm(rows, 0, e->posw, (long)cpg * kPosK, B * T, cpg, cpg * kPosK);
+  g.rpb = T; g.a_batch = batch_rows * kD; g.a_row = kD;
+  g.kchunk = cpg; g.kchunk_stride = kD;
+  g.g_a = cpg; g.g_w = (long)cpg * cpg * kPosK; g.g_n = cpg;
+  g.bias = e->F("ssl.encoder.pos_conv.0.bias");
+  g.act = ACT_GELU;
+  g.resid = x; g.ldr = kD;
+  g.out_f = x; g.ldo_f = kD; g.o_batch_rows = T; g.oh_batch_rows = T;
+  return launch_gemm(g, dt, kPosG, s);
+}
+
 // l5: null = start from the waveform; else the output of conv layer 5, (B, T[5], 512) operand type (tail mode)
 // l5_batch: elements between two utterances of l5 (0 = packed, T[5] * 512): a streaming caller keeps its window inside a longer ring
 static int run_trunk(afx_engine* e, const float* wave, int B, int L, Ws& w, hipStream_t s, const void* l5 = nullptr, long l5_batch = 0) {
@@ -1169,16 +1184,7 @@ static int run_trunk(afx_engine* e, const float* wave, int B, int L, Ws& w, hipS
     pc.x = w.x; pc.B = B; pc.T = Tt;
     KOK(timed(PC_POSCONV, 2.0 * M * kD * (kD / kPosG) * kPosK, s, [&] { return launch_posconv(pc, dt, s); }));
   } else {
-    const int cpg = kD / kPosG;
-    GemmArgs g = plain_gemm(w.xpad, 0, e->posw, (long)cpg * kPosK, M, cpg, cpg * kPosK);
-    g.rpb = Tt; g.a_batch = (long)(Tt + kPosK) * kD; g.a_row = kD;
-    g.kchunk = cpg; g.kchunk_stride = kD;
-    g.g_a = cpg; g.g_w = (long)cpg * cpg * kPosK; g.g_n = cpg;
-    g.bias = e->F("ssl.encoder.pos_conv.0.bias");
-    g.act = ACT_GELU;
-    g.resid = w.x; g.ldr = kD;
-    g.out_f = w.x; g.ldo_f = kD; g.o_batch_rows = Tt; g.oh_batch_rows = Tt;
-    KOK(launch_gemm(g, dt, kPosG, s));
+    KOK(posconv_product(e, w.xpad, Tt + kPosK, B, Tt, w.x, dt, s));
   }
   if (tap(e, "pos", w.x, (size_t)M * kD, false, s)) return 1;
   // transformer layers (pre-LN)
@@ -1457,6 +1463,20 @@ __global__ void f32_to_half_kernel(const float* in, uint16_t* out, size_t n, int
 // State per stream: 24 x 256 x 3072 halfs of [q | k | v] rows (16-slot groups, one per chunk), 64 projected frames, the
 // feature window.  The whole step runs on new frames only: S x n_c rows through the products, one query tile per
 // (stream, head) in the attention.
+// The step has three entry points over ONE body (kv_trunk: feature LayerNorm .. final encoder LayerNorm).  An entry point
+// checks its arguments, uploads its tables, describes itself to the body in a KvForm, then updates the windows and runs the
+// back-end.  What a form supplies:
+//                    afx_kv_step (lock-step)      afx_kv_step_ragged (sessions)    afx_kv_step_active (a list)
+//   rows             S                            S                                A
+//   history in       2-D copy                     2-D copy                         kv_hist_kernel by id
+//   history out      2-D copy                     kv_hist_kernel (own n_s)         kv_hist_kernel by id
+//   zero padding     past n                       past 64 + n_s (meta)             past 64 + n_i (meta)
+//   QKV rows         ring row 16 group + r        ring row 16 group + r            row table: 256 ids[i] + 16 own group + r
+//   ring attention   form 1: host cnt, group      form 2: tab, group               form 3: the list's table
+//   final LayerNorm  into the other window        dense rows (w.fl)                dense rows (w.fl)
+//                    buffer, after its shift
+//   window update    (the shift above)            kv_feat_kernel, ping-pong        kv_shift_kernel, in place
+//   back-end         uniform window, run_head     kv_score_windows                 kv_score_windows by id
 // ---------------------------------------------------------------------------------
 constexpr int kKvGroups = 16, kKvSlots = 256, kKvHist = 64, kKvFeat = 208, kKvWindow = 200;
 struct afx_kv {
@@ -1486,6 +1506,17 @@ struct KvWs {
   void* s3planes = nullptr;  // split precision: pair-form scratch of the chunk's products
   size_t s3bytes = 0;
   Ws head;
+};
+// what an entry point supplies to the shared body of the step (kv_trunk); the table above
+struct KvForm {
+  int rows;              // S, or the length of the list: M = rows x n
+  const int* dn;         // device: frames per row block (null: every stream brings n) -- the history leaves by kv_hist_kernel
+  const int* ids;        // device: the stream of each row block (a list; null: block b is stream b) -- the history also enters by it
+  const int* pad_lens;   // device: 64 + frames per row block, the rows past them are zeroed (null: 64 + n)
+  const int* qkv_rows;   // device: first ring row of each row block's chunk (a list); null: row 16 ring.q_tile of the block's own ring
+  MhsaRingForm ring;
+  float* win_next;       // lock-step: the window moves up by n into this buffer and the final LayerNorm writes the chunk's rows
+                         // below it; null: the final LayerNorm writes dense rows into w.fl
 };
 static size_t kv_carve(const afx_engine* e, int S, int n, int Th, void* base, KvWs* k, bool per_stream = false) {
   Carver c(base);
@@ -1551,142 +1582,11 @@ extern "C" size_t afx_kv_workspace_bytes(const afx_kv* k, int n_frames) {
   KvWs w;
   return kv_carve(k->e, k->S, n_frames, kKvWindow, nullptr, &w);
 }
-// feats6: device (S, n, 512) fp32 -- the n NEW frames of conv layer 6 (conv + LayerNorm + GELU applied: what the conv stack
-// hands the feature LayerNorm), 1 <= n <= 16.  logits: device (S, 2): the back-end's logits on the window that ends with this chunk.
-extern "C" int afx_kv_step(afx_kv* k, const float* feats6, int n, float* logits, void* ws, size_t ws_bytes, void* stream) {
-  if (n < 1 || n > 16) return fail("afx_kv_step: a chunk brings 1..16 frames (got %d)", n);
-  if (!k || !feats6 || !logits || !ws) return fail("afx_kv_step: null argument");
-  if (k->active) return fail("afx_kv_step: this state holds per-stream ring positions (afx_kv_step_active): continue with afx_kv_step_active");
-  if (k->per_stream) return fail("afx_kv_step: this state holds per-stream sessions (afx_kv_reset / afx_kv_step_ragged): continue with afx_kv_step_ragged");
-  afx_engine* e = k->e;
-  const int S = k->S, dt = e->dt, M = S * n, Tp = kKvHist + n, group = (int)(k->hop % kKvGroups);
-  const int Th = std::min(k->nfeat + n, kKvWindow);
-  if (e->cfg.arch == AFX_ARCH_XLSR_AASIST && Th < 6) return fail("afx_kv_step: the AASIST head needs at least 6 frames in the window");
-  KvWs w;
-  const size_t needb = kv_carve(e, S, n, Th, ws, &w);
-  if (ws_bytes < needb) return fail("afx_kv_step: workspace too small (%zu < %zu bytes)", ws_bytes, needb);
-  hipStream_t s = (hipStream_t)stream;
-  begin_call(e, nullptr);
-  if (e->s3) {  // split precision: the chunk's products take pair-form operands written by their producers, or converted into the scratch
-    t_s3planes = w.s3planes;
-    t_s3bytes = w.s3bytes;
-    s3_begin({w.feats_h, w.hbuf, w.att, w.ff, w.xpad, (char*)w.xpad + (size_t)kKvHist * kD * e->hsz});  // (+ the chunk's view of the padded rows)
-  }
-  const size_t hs = e->hsz;
-  k->cnt[group] = n;
-  // feature LayerNorm -> operand type
-  {
-    RowNormArgs a = plain_norm(feats6, kC, M, kC, e->F("ssl.layer_norm.weight"), e->F("ssl.layer_norm.bias"));
-    a.out_h = w.feats_h; a.ldo_h = kC;
-    KOK(launch_rownorm(a, dt, s));
-  }
-  // positional conv operand: [64 zero rows | 64 cached projected frames | the chunk | 64 zero rows] per stream
-  const size_t xrow = (size_t)kD * hs, xpad_pitch = (size_t)(Tp + kPosK) * xrow;
-  HIP_OK(hipMemcpy2DAsync((char*)w.xpad + kPosPad * xrow, xpad_pitch, k->hist, kKvHist * xrow, kKvHist * xrow, S, hipMemcpyDeviceToDevice, s));
-  {
-    GemmArgs g = plain_gemm(w.feats_h, kC, e->projw, kC, M, kD, kC);
-    g.rpb = n; g.a_batch = (long)n * kC; g.a_row = kC;
-    g.bias = e->F("ssl.post_extract_proj.bias");
-    g.out_f = w.x; g.ldo_f = kD; g.o_batch_rows = n;  // the chunk's residual rows, dense (S, n, 1024)
-    g.out_h = w.xpad; g.ldo_h = kD; g.oh_batch_rows = Tp + kPosK; g.oh_row_off = kPosPad + kKvHist;
-    KOK(launch_gemm(g, dt, 1, s));
-    KOK(timed(PC_MISC, 0, s, [&] { return launch_zero_pad_rows(w.xpad, S, Tp, kD, kPosPad, kPosK - kPosPad, dt, s, nullptr); }));
-  }
-  // The positional conv of the chunk's n frames ONLY (round 4: it used to run over all 64 + n rows of the padded layout and
-  // keep the last n -- 6x the work at n = 13): output frame j reads rows [64 + j, 192 + j) of the stream's padded rows, i.e. rows
-  // [j, j + 128) from the first cached frame on.
-  void* xchunk = (char*)w.xpad + (size_t)kKvHist * xrow;
-  if (!e->s3) {
-    PosConvArgs pc;
-    memset(&pc, 0, sizeof pc);
-    pc.xpad = xchunk; pc.xpad_batch = (long)(Tp + kPosK) * kD; pc.W = e->posw; pc.bias = e->F("ssl.encoder.pos_conv.0.bias");
-    pc.x = w.x; pc.B = S; pc.T = n;
-    KOK(timed(PC_POSCONV, 2.0 * S * n * kD * (kD / kPosG) * kPosK, s, [&] { return launch_posconv(pc, dt, s); }));
-  } else {  // split precision: the grouped product of run_trunk (chunked K over the time-padded pair-form rows)
-    const int cpg = kD / kPosG;
-    s3_set(xchunk, kS3ScaleFree);  // (history rows copied in above + the rows the projection just wrote: pair form, scale 1)
-    GemmArgs g = plain_gemm(xchunk, 0, e->posw, (long)cpg * kPosK, S * n, cpg, cpg * kPosK);
-    g.rpb = n; g.a_batch = (long)(Tp + kPosK) * kD; g.a_row = kD;
-    g.kchunk = cpg; g.kchunk_stride = kD;
-    g.g_a = cpg; g.g_w = (long)cpg * cpg * kPosK; g.g_n = cpg;
-    g.bias = e->F("ssl.encoder.pos_conv.0.bias");
-    g.act = ACT_GELU;
-    g.resid = w.x; g.ldr = kD;
-    g.out_f = w.x; g.ldo_f = kD; g.o_batch_rows = n; g.oh_batch_rows = n;
-    KOK(launch_gemm(g, dt, kPosG, s));
-  }
-  // the newest 64 projected frames become the next chunk's left context
-  HIP_OK(hipMemcpy2DAsync(k->hist, kKvHist * xrow, (char*)w.xpad + (size_t)(kPosPad + n) * xrow, xpad_pitch, kKvHist * xrow, S, hipMemcpyDeviceToDevice, s));
-  for (int l = 0; l < e->cfg.n_layers; ++l) {
-    const std::string P = "ssl.encoder.layers." + std::to_string(l) + ".";
-    void* ring = (char*)k->rings + (size_t)l * S * kKvSlots * 3 * kD * hs;
-    RowNormArgs n1 = plain_norm(w.x, kD, M, kD, e->F(P + "self_attn_layer_norm.weight"), e->F(P + "self_attn_layer_norm.bias"));
-    n1.out_h = w.hbuf; n1.ldo_h = kD;
-    KOK(launch_rownorm(n1, dt, s));
-    // q | k | v of the chunk go straight into its 16-slot group of the ring (row remap of the epilogue): K / V are cached by being written
-    GemmArgs q = plain_gemm(w.hbuf, kD, e->wqkv[l], kD, M, 3 * kD, kD);
-    q.rpb = n; q.a_batch = (long)n * kD; q.a_row = kD;
-    q.bias = e->bqkv[l];
-    q.out_h = ring; q.ldo_h = 3 * kD; q.oh_batch_rows = kKvSlots; q.oh_row_off = group * 16;
-    KOK(launch_gemm(q, dt, 1, s));
-    KOK(timed(PC_MHSA, 4.0 * S * kH * 16.0 * kKvSlots * 64, s, [&] {
-      if (e->s3) {  // fp32 [q | k | v] slots, hi / lo pairs split in the kernel; the output leaves as the output projection's pair-form operand
-        const bool pairs = s3_ok(w.att);
-        s3_set(w.att, pairs ? kS3ScaleFree : 0.f);
-        return launch_mhsa_ring_split((const float*)ring, (float*)w.att, S, kH, group, k->cnt, s, pairs, kS3ScaleFree);
-      }
-      return launch_mhsa_ring(ring, w.att, S, kH, group, k->cnt, dt, s);
-    }));
-    GemmArgs o = plain_gemm(w.att, kD, e->wo[l], kD, M, kD, kD);
-    o.rpb = n; o.a_batch = 16L * kD; o.a_row = kD; o.o_batch_rows = n;
-    o.bias = e->F(P + "self_attn.out_proj.bias"); o.resid = w.x; o.ldr = kD; o.out_f = w.x; o.ldo_f = kD;
-    KOK(launch_gemm(o, dt, 1, s));
-    RowNormArgs n2 = plain_norm(w.x, kD, M, kD, e->F(P + "final_layer_norm.weight"), e->F(P + "final_layer_norm.bias"));
-    n2.out_h = w.hbuf; n2.ldo_h = kD;
-    KOK(launch_rownorm(n2, dt, s));
-    GemmArgs f1 = plain_gemm(w.hbuf, kD, e->w1[l], kD, M, kF, kD);
-    f1.bias = e->F(P + "fc1.bias"); f1.act = ACT_GELU; f1.out_h = w.ff; f1.ldo_h = kF;
-    KOK(launch_gemm(f1, dt, 1, s));
-    GemmArgs f2 = plain_gemm(w.ff, kF, e->w2[l], kF, M, kD, kF);
-    f2.bias = e->F(P + "fc2.bias"); f2.resid = w.x; f2.ldr = kD; f2.out_f = w.x; f2.ldo_f = kD;
-    KOK(launch_gemm(f2, dt, 1, s));
-  }
-  // final LayerNorm: the chunk's features join the right-aligned window (old frames move up by n in the other buffer)
-  float *cur = k->feat[k->pp], *nxt = k->feat[k->pp ^ 1];
-  const size_t frow = (size_t)kD * 4, fpitch = (size_t)kKvFeat * frow;
-  HIP_OK(hipMemcpy2DAsync(nxt, fpitch, (char*)cur + (size_t)n * frow, fpitch, (size_t)(kKvFeat - n) * frow, S, hipMemcpyDeviceToDevice, s));
-  {
-    RowNormArgs nf = plain_norm(w.x, kD, M, kD, e->F("ssl.encoder.layer_norm.weight"), e->F("ssl.encoder.layer_norm.bias"));
-    nf.out_f = nxt; nf.ldo_f = kD; nf.rpb = n; nf.o_batch_rows = kKvFeat; nf.o_row_off = kKvFeat - n;
-    nf.nonfinite = e->nonfinite;
-    KOK(launch_rownorm(nf, dt, s));
-  }
-  k->pp ^= 1;
-  k->nfeat = std::min(k->nfeat + n, kKvFeat);
-  // back-end on the window of the last Th frames
-  HIP_OK(hipMemcpy2DAsync(w.head.ssl_f, (size_t)Th * frow, (char*)nxt + (size_t)(kKvFeat - Th) * frow, fpitch, (size_t)Th * frow, S, hipMemcpyDeviceToDevice, s));
-  if (e->cfg.arch == AFX_ARCH_CONFORMER) {
-    if (e->s3) {  // (fp32 operand buffers: the head's LL converts the rows it reads into its own scratch)
-      HIP_OK(hipMemcpyAsync(w.head.ssl_h, w.head.ssl_f, (size_t)S * Th * kD * 4, hipMemcpyDeviceToDevice, s));
-    } else {
-      hipLaunchKernelGGL(f32_to_half_kernel, dim3(1024), dim3(256), 0, s, w.head.ssl_f, (uint16_t*)w.head.ssl_h, (size_t)S * Th * kD, dt == AFX_DT_BF16 ? 1 : 0);
-      HIP_OK(hipGetLastError());
-    }
-  }
-  k->hop += 1;
-  if (e->taps_on && tap(e, "ssl", w.head.ssl_f, (size_t)S * Th * kD, false, s)) return 1;
-  begin_call(e, &w.head);  // (the back-end's products use the back-end workspace's own scratch and buffer list)
-  return run_head(e, S, Th, w.head, logits, s);
-}
-
-
 // ---------------------------------------------------------------------------------
-// Per-stream sessions of the KV-cached mode: streams that start (afx_kv_reset) at different ticks.  Every stream still
-// brings one chunk per step and the ring group stays global (group = step % 16, the QKV epilogue unchanged), so a stream's
-// last 16 chunks are always the last 16 groups; what is per stream is its base group (where its first chunk sits), its
-// valid-count row, its frame count per step (12 or 13 from its own first sample: n_s <= n_max, rows padded to n_max) and
-// its window length.  The ring attention visits the slots rotated by the base group, so a stream's keys are summed in the
-// order of a stream that started at group 0: a session scores bit for bit as that stream alone from the start.
+// Per-stream sessions (afx_kv_reset, afx_kv_step_ragged): streams that start at different ticks.  The ring group stays
+// global (group = step % 16); per stream are its base group (where its first chunk sits), its valid counts, its frames per
+// step (n_s <= n_max, rows padded to n_max) and its window length.  The ring attention visits the slots rotated by the base
+// group, the key order of a stream that started at group 0: a session scores bit for bit as that stream alone from the start.
 // ---------------------------------------------------------------------------------
 __global__ void kv_reset_kernel(const int* __restrict__ slots, int* __restrict__ tab, int base_group, u32x4* __restrict__ hist,
                                 long hist_words, u32x4* __restrict__ f0, u32x4* __restrict__ f1, long feat_words) {
@@ -1783,119 +1683,89 @@ extern "C" int afx_kv_reset(afx_kv* k, const int* slots, int n_slots, void* stre
   return 0;
 }
 
-extern "C" size_t afx_kv_ragged_workspace_bytes(const afx_kv* k, int n_max) {
-  if (!k || n_max <= 0 || n_max > 16) return 0;
-  KvWs w;
-  return kv_carve(k->e, k->S, n_max, kKvWindow, nullptr, &w, true);
-}
-
-// feats6: device (S, n_max, 512) fp32, stream b's n_frames[b] new frames first (rows past them are read but never score);
-// n_frames: host, S entries, 1 <= n_frames[b] <= n_max <= 16.  Same function per stream as afx_kv_step on that stream alone.
-extern "C" int afx_kv_step_ragged(afx_kv* k, const float* feats6, int n, const int* n_frames, float* logits, void* ws, size_t ws_bytes,
-                                  void* stream) {
-  if (n < 1 || n > 16) return fail("afx_kv_step_ragged: a chunk brings 1..16 frames (got n_max %d)", n);
-  if (!k || !feats6 || !n_frames || !logits || !ws) return fail("afx_kv_step_ragged: null argument");
-  if (k->active) return fail("afx_kv_step_ragged: this state holds per-stream ring positions (afx_kv_step_active): continue with afx_kv_step_active");
+// The shared body of the three steps: the chunk's rows (f.rows blocks of n) from the feature LayerNorm to the final encoder
+// LayerNorm.  Every difference between the forms is a field of KvForm.
+static int kv_trunk(afx_kv* k, const KvForm& f, const float* feats6, int n, KvWs& w, hipStream_t s) {
   afx_engine* e = k->e;
-  const int S = k->S, dt = e->dt, M = S * n, Tp = kKvHist + n, group = (int)(k->hop % kKvGroups);
-  for (int b = 0; b < S; ++b)
-    if (n_frames[b] < 1 || n_frames[b] > n) return fail("afx_kv_step_ragged: stream %d brings %d frames (1..%d)", b, n_frames[b], n);
-  hipStream_t s = (hipStream_t)stream;
-  if (kv_to_per_stream(k, s)) return 1;
-  int Thmax = 0;
-  std::vector<int>& hm = k->hmeta;
-  for (int b = 0; b < S; ++b) {
-    const int th = std::min(k->nfeat_s[b] + n_frames[b], kKvWindow);
-    if (e->cfg.arch == AFX_ARCH_XLSR_AASIST && th < 6) return fail("afx_kv_step_ragged: the AASIST head needs at least 6 frames in stream %d's window", b);
-    hm[b] = n_frames[b];
-    hm[S + b] = kKvHist + n_frames[b];
-    hm[2 * S + b] = th;
-    Thmax = std::max(Thmax, th);
-  }
-  KvWs w;
-  const size_t needb = kv_carve(e, S, n, Thmax, ws, &w, true);
-  if (ws_bytes < needb) return fail("afx_kv_step_ragged: workspace too small (%zu < %zu bytes)", ws_bytes, needb);
-  // AASIST: the streams grouped by window length (one uniform sub-batch each, as afx_forward_ragged does)
-  std::vector<std::pair<int, int>> buckets;  // (length, first index into the slot list)
-  if (e->cfg.arch == AFX_ARCH_XLSR_AASIST) {
-    std::vector<int> order(S);
-    for (int b = 0; b < S; ++b) order[b] = b;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int c) { return hm[2 * S + a] < hm[2 * S + c]; });
-    for (int i = 0; i < S; ++i) {
-      hm[3 * S + i] = order[i];
-      if (i == 0 || hm[2 * S + order[i]] != hm[2 * S + order[i - 1]]) buckets.push_back({hm[2 * S + order[i]], i});
-    }
-  }
-  const int* dn = k->meta;
-  HIP_OK(hipMemcpyAsync(k->meta, hm.data(), (size_t)S * 16, hipMemcpyHostToDevice, s));
-  HIP_OK(hipStreamSynchronize(s));  // (pageable host memory)
+  const int R = f.rows, dt = e->dt, M = R * n, Tp = kKvHist + n;
+  const size_t hs = e->hsz, xrow = (size_t)kD * hs, xpad_pitch = (size_t)(Tp + kPosK) * xrow;
   begin_call(e, nullptr);
-  if (e->s3) {
+  if (e->s3) {  // split precision: the chunk's products take pair-form operands written by their producers, or converted into the scratch
     t_s3planes = w.s3planes;
     t_s3bytes = w.s3bytes;
-    s3_begin({w.feats_h, w.hbuf, w.att, w.ff, w.xpad, (char*)w.xpad + (size_t)kKvHist * kD * e->hsz});
+    s3_begin({w.feats_h, w.hbuf, w.att, w.ff, w.xpad, (char*)w.xpad + (size_t)kKvHist * kD * e->hsz});  // (+ the chunk's view of the padded rows)
   }
-  const size_t hs = e->hsz;
-  hipLaunchKernelGGL(kv_count_kernel, dim3((S + 255) / 256), dim3(256), 0, s, k->tab, dn, S, group);
-  HIP_OK(hipGetLastError());
+  // feature LayerNorm -> operand type
   {
     RowNormArgs a = plain_norm(feats6, kC, M, kC, e->F("ssl.layer_norm.weight"), e->F("ssl.layer_norm.bias"));
     a.out_h = w.feats_h; a.ldo_h = kC;
     KOK(launch_rownorm(a, dt, s));
   }
-  const size_t xrow = (size_t)kD * hs, xpad_pitch = (size_t)(Tp + kPosK) * xrow;
-  HIP_OK(hipMemcpy2DAsync((char*)w.xpad + kPosPad * xrow, xpad_pitch, k->hist, kKvHist * xrow, kKvHist * xrow, S, hipMemcpyDeviceToDevice, s));
+  // positional conv operand: [64 zero rows | 64 cached projected frames | the chunk | 64 zero rows] per row block
+  if (f.ids) {
+    hipLaunchKernelGGL(kv_hist_kernel, dim3(32, R), dim3(256), 0, s, (u32x4*)k->hist, (u32x4*)w.xpad, f.dn, (long)(xrow / 16),
+                       (long)(Tp + kPosK), kPosPad, f.ids, 1);
+    HIP_OK(hipGetLastError());
+  } else {
+    HIP_OK(hipMemcpy2DAsync((char*)w.xpad + kPosPad * xrow, xpad_pitch, k->hist, kKvHist * xrow, kKvHist * xrow, R, hipMemcpyDeviceToDevice, s));
+  }
   {
     GemmArgs g = plain_gemm(w.feats_h, kC, e->projw, kC, M, kD, kC);
     g.rpb = n; g.a_batch = (long)n * kC; g.a_row = kC;
     g.bias = e->F("ssl.post_extract_proj.bias");
-    g.out_f = w.x; g.ldo_f = kD; g.o_batch_rows = n;
+    g.out_f = w.x; g.ldo_f = kD; g.o_batch_rows = n;  // the chunk's residual rows, dense (rows, n, 1024)
     g.out_h = w.xpad; g.ldo_h = kD; g.oh_batch_rows = Tp + kPosK; g.oh_row_off = kPosPad + kKvHist;
     KOK(launch_gemm(g, dt, 1, s));
-    // a stream's chunk rows past its own n_s are zero, as beyond its chunk when it steps alone
-    KOK(timed(PC_MISC, 0, s, [&] { return launch_zero_pad_rows(w.xpad, S, Tp, kD, kPosPad, kPosK - kPosPad, dt, s, dn + S); }));
+    // (per-stream counts: a block's chunk rows past its own n_s are zero, as beyond its chunk when the stream steps alone)
+    KOK(timed(PC_MISC, 0, s, [&] { return launch_zero_pad_rows(w.xpad, R, Tp, kD, kPosPad, kPosK - kPosPad, dt, s, f.pad_lens); }));
   }
+  // The positional conv of the chunk's n frames ONLY (round 4: it used to run over all 64 + n rows of the padded layout and
+  // keep the last n -- 6x the work at n = 13): output frame j reads rows [64 + j, 192 + j) of the block's padded rows, i.e. rows
+  // [j, j + 128) from the first cached frame on.
   void* xchunk = (char*)w.xpad + (size_t)kKvHist * xrow;
   if (!e->s3) {
     PosConvArgs pc;
     memset(&pc, 0, sizeof pc);
     pc.xpad = xchunk; pc.xpad_batch = (long)(Tp + kPosK) * kD; pc.W = e->posw; pc.bias = e->F("ssl.encoder.pos_conv.0.bias");
-    pc.x = w.x; pc.B = S; pc.T = n;
-    KOK(timed(PC_POSCONV, 2.0 * S * n * kD * (kD / kPosG) * kPosK, s, [&] { return launch_posconv(pc, dt, s); }));
-  } else {
-    const int cpg = kD / kPosG;
-    s3_set(xchunk, kS3ScaleFree);
-    GemmArgs g = plain_gemm(xchunk, 0, e->posw, (long)cpg * kPosK, S * n, cpg, cpg * kPosK);
-    g.rpb = n; g.a_batch = (long)(Tp + kPosK) * kD; g.a_row = kD;
-    g.kchunk = cpg; g.kchunk_stride = kD;
-    g.g_a = cpg; g.g_w = (long)cpg * cpg * kPosK; g.g_n = cpg;
-    g.bias = e->F("ssl.encoder.pos_conv.0.bias");
-    g.act = ACT_GELU;
-    g.resid = w.x; g.ldr = kD;
-    g.out_f = w.x; g.ldo_f = kD; g.o_batch_rows = n; g.oh_batch_rows = n;
-    KOK(launch_gemm(g, dt, kPosG, s));
+    pc.x = w.x; pc.B = R; pc.T = n;
+    KOK(timed(PC_POSCONV, 2.0 * R * n * kD * (kD / kPosG) * kPosK, s, [&] { return launch_posconv(pc, dt, s); }));
+  } else {  // split precision: the grouped product of run_trunk
+    s3_set(xchunk, kS3ScaleFree);  // (history rows copied in above + the rows the projection just wrote: pair form, scale 1)
+    KOK(posconv_product(e, xchunk, Tp + kPosK, R, n, w.x, dt, s));
   }
-  hipLaunchKernelGGL(kv_hist_kernel, dim3(32, S), dim3(256), 0, s, (u32x4*)k->hist, (u32x4*)w.xpad, dn, (long)(xrow / 16),
-                     (long)(Tp + kPosK), kPosPad, (const int*)nullptr, 0);
-  HIP_OK(hipGetLastError());
+  // the newest 64 projected frames become the next chunk's left context
+  if (f.dn) {
+    hipLaunchKernelGGL(kv_hist_kernel, dim3(32, R), dim3(256), 0, s, (u32x4*)k->hist, (u32x4*)w.xpad, f.dn, (long)(xrow / 16),
+                       (long)(Tp + kPosK), kPosPad, f.ids, 0);
+    HIP_OK(hipGetLastError());
+  } else {
+    HIP_OK(hipMemcpy2DAsync(k->hist, kKvHist * xrow, (char*)w.xpad + (size_t)(kPosPad + n) * xrow, xpad_pitch, kKvHist * xrow, R, hipMemcpyDeviceToDevice, s));
+  }
   for (int l = 0; l < e->cfg.n_layers; ++l) {
     const std::string P = "ssl.encoder.layers." + std::to_string(l) + ".";
-    void* ring = (char*)k->rings + (size_t)l * S * kKvSlots * 3 * kD * hs;
+    void* ring = (char*)k->rings + (size_t)l * k->S * kKvSlots * 3 * kD * hs;
     RowNormArgs n1 = plain_norm(w.x, kD, M, kD, e->F(P + "self_attn_layer_norm.weight"), e->F(P + "self_attn_layer_norm.bias"));
     n1.out_h = w.hbuf; n1.ldo_h = kD;
     KOK(launch_rownorm(n1, dt, s));
+    // q | k | v of the chunk go straight into its 16-slot group of the ring (row remap or row table of the epilogue): K / V are
+    // cached by being written
     GemmArgs q = plain_gemm(w.hbuf, kD, e->wqkv[l], kD, M, 3 * kD, kD);
     q.rpb = n; q.a_batch = (long)n * kD; q.a_row = kD;
     q.bias = e->bqkv[l];
-    q.out_h = ring; q.ldo_h = 3 * kD; q.oh_batch_rows = kKvSlots; q.oh_row_off = group * 16;
-    KOK(launch_gemm(q, dt, 1, s));
-    KOK(timed(PC_MHSA, 4.0 * S * kH * 16.0 * kKvSlots * 64, s, [&] {
-      if (e->s3) {
+    q.out_h = ring; q.ldo_h = 3 * kD;
+    if (f.qkv_rows) {
+      q.oh_rows = f.qkv_rows;
+    } else {
+      q.oh_batch_rows = kKvSlots; q.oh_row_off = f.ring.q_tile * 16;
+    }
+    KOK(launch_gemm(q, dt, 1, s, f.qkv_rows != nullptr));
+    KOK(timed(PC_MHSA, 4.0 * R * kH * 16.0 * kKvSlots * 64, s, [&] {
+      if (e->s3) {  // fp32 [q | k | v] slots, hi / lo pairs split in the kernel; the output leaves as the output projection's pair-form operand
         const bool pairs = s3_ok(w.att);
         s3_set(w.att, pairs ? kS3ScaleFree : 0.f);
-        return launch_mhsa_ring_split_tab((const float*)ring, (float*)w.att, S, kH, group, k->tab, s, pairs, kS3ScaleFree);
+        return launch_mhsa_ring_split((const float*)ring, (float*)w.att, R, kH, f.ring, s, pairs, kS3ScaleFree);
       }
-      return launch_mhsa_ring_tab(ring, w.att, S, kH, group, k->tab, dt, s);
+      return launch_mhsa_ring(ring, w.att, R, kH, f.ring, dt, s);
     }));
     GemmArgs o = plain_gemm(w.att, kD, e->wo[l], kD, M, kD, kD);
     o.rpb = n; o.a_batch = 16L * kD; o.a_row = kD; o.o_batch_rows = n;
@@ -1911,54 +1781,169 @@ extern "C" int afx_kv_step_ragged(afx_kv* k, const float* feats6, int n, const i
     f2.bias = e->F(P + "fc2.bias"); f2.resid = w.x; f2.ldr = kD; f2.out_f = w.x; f2.ldo_f = kD;
     KOK(launch_gemm(f2, dt, 1, s));
   }
-  float *cur = k->feat[k->pp], *nxt = k->feat[k->pp ^ 1];
-  {
-    RowNormArgs nf = plain_norm(w.x, kD, M, kD, e->F("ssl.encoder.layer_norm.weight"), e->F("ssl.encoder.layer_norm.bias"));
+  RowNormArgs nf = plain_norm(w.x, kD, M, kD, e->F("ssl.encoder.layer_norm.weight"), e->F("ssl.encoder.layer_norm.bias"));
+  if (f.win_next) {
+    const size_t frow = (size_t)kD * 4, fpitch = (size_t)kKvFeat * frow;
+    HIP_OK(hipMemcpy2DAsync(f.win_next, fpitch, (char*)k->feat[k->pp] + (size_t)n * frow, fpitch, (size_t)(kKvFeat - n) * frow, R, hipMemcpyDeviceToDevice, s));
+    nf.out_f = f.win_next; nf.ldo_f = kD; nf.rpb = n; nf.o_batch_rows = kKvFeat; nf.o_row_off = kKvFeat - n;
+  } else {
     nf.out_f = w.fl; nf.ldo_f = kD;
-    nf.nonfinite = e->nonfinite;
-    KOK(launch_rownorm(nf, dt, s));
   }
+  nf.nonfinite = e->nonfinite;
+  KOK(launch_rownorm(nf, dt, s));
+  return 0;
+}
+
+// feats6: device (S, n, 512) fp32 -- the n NEW frames of conv layer 6 (conv + LayerNorm + GELU applied: what the conv stack
+// hands the feature LayerNorm), 1 <= n <= 16.  logits: device (S, 2): the back-end's logits on the window that ends with this chunk.
+extern "C" int afx_kv_step(afx_kv* k, const float* feats6, int n, float* logits, void* ws, size_t ws_bytes, void* stream) {
+  if (n < 1 || n > 16) return fail("afx_kv_step: a chunk brings 1..16 frames (got %d)", n);
+  if (!k || !feats6 || !logits || !ws) return fail("afx_kv_step: null argument");
+  if (k->active) return fail("afx_kv_step: this state holds per-stream ring positions (afx_kv_step_active): continue with afx_kv_step_active");
+  if (k->per_stream) return fail("afx_kv_step: this state holds per-stream sessions (afx_kv_reset / afx_kv_step_ragged): continue with afx_kv_step_ragged");
+  afx_engine* e = k->e;
+  const int S = k->S, dt = e->dt, group = (int)(k->hop % kKvGroups);
+  const int Th = std::min(k->nfeat + n, kKvWindow);
+  if (e->cfg.arch == AFX_ARCH_XLSR_AASIST && Th < 6) return fail("afx_kv_step: the AASIST head needs at least 6 frames in the window");
+  KvWs w;
+  const size_t needb = kv_carve(e, S, n, Th, ws, &w);
+  if (ws_bytes < needb) return fail("afx_kv_step: workspace too small (%zu < %zu bytes)", ws_bytes, needb);
+  hipStream_t s = (hipStream_t)stream;
+  k->cnt[group] = n;
+  // the chunk's features join the right-aligned window (old frames move up by n in the other buffer)
+  float* nxt = k->feat[k->pp ^ 1];
+  KvForm f = {};
+  f.rows = S;
+  f.ring = MhsaRingForm{1, group, k->cnt, nullptr};
+  f.win_next = nxt;
+  if (kv_trunk(k, f, feats6, n, w, s)) return 1;
+  k->pp ^= 1;
+  k->nfeat = std::min(k->nfeat + n, kKvFeat);
+  // back-end on the window of the last Th frames
+  const size_t frow = (size_t)kD * 4, fpitch = (size_t)kKvFeat * frow;
+  HIP_OK(hipMemcpy2DAsync(w.head.ssl_f, (size_t)Th * frow, (char*)nxt + (size_t)(kKvFeat - Th) * frow, fpitch, (size_t)Th * frow, S, hipMemcpyDeviceToDevice, s));
+  if (e->cfg.arch == AFX_ARCH_CONFORMER) {
+    if (e->s3) {  // (fp32 operand buffers: the head's LL converts the rows it reads into its own scratch)
+      HIP_OK(hipMemcpyAsync(w.head.ssl_h, w.head.ssl_f, (size_t)S * Th * kD * 4, hipMemcpyDeviceToDevice, s));
+    } else {
+      hipLaunchKernelGGL(f32_to_half_kernel, dim3(1024), dim3(256), 0, s, w.head.ssl_f, (uint16_t*)w.head.ssl_h, (size_t)S * Th * kD, dt == AFX_DT_BF16 ? 1 : 0);
+      HIP_OK(hipGetLastError());
+    }
+  }
+  k->hop += 1;
+  if (e->taps_on && tap(e, "ssl", w.head.ssl_f, (size_t)S * Th * kD, false, s)) return 1;
+  begin_call(e, &w.head);  // (the back-end's products use the back-end workspace's own scratch and buffer list)
+  return run_head(e, S, Th, w.head, logits, s);
+}
+
+// AASIST scores uniform batches: the entries grouped by window length (one sub-batch each, as afx_forward_ragged does).
+// order = the entries sorted by length (stable); returns (length, first position in the order) per bucket
+static std::vector<std::pair<int, int>> kv_buckets(const int* th, int count, int* order) {
+  std::vector<std::pair<int, int>> buckets;
+  for (int i = 0; i < count; ++i) order[i] = i;
+  std::stable_sort(order, order + count, [&](int a, int c) { return th[a] < th[c]; });
+  for (int i = 0; i < count; ++i)
+    if (i == 0 || th[order[i]] != th[order[i - 1]]) buckets.push_back({th[order[i]], i});
+  return buckets;
+}
+
+// The back-end of the per-stream steps: entry i of `count` scores the last dth[i] (<= Thmax) rows of its stream's window in `win`
+struct KvWindows {
+  const float* win;
+  int count, Thmax;
+  const int *ids, *dth;      // device.  Conformer, every window left-aligned in one batch with key-padding lengths
+                             // (afx_forward_ragged's head): entry i is stream ids[i] (null: stream i), its length dth[i]
+  const int *b_ids, *b_row;  // device.  AASIST, the bucket loop: position j of the order is stream b_ids[j], logits row b_row[j]
+  std::vector<std::pair<int, int>> buckets;  // AASIST: kv_buckets
+};
+static int kv_score_windows(afx_engine* e, KvWs& w, const KvWindows& v, float* logits, hipStream_t s) {
+  const int count = v.count, Thmax = v.Thmax;
+  if (e->cfg.arch == AFX_ARCH_CONFORMER) {
+    hipLaunchKernelGGL(kv_gather_kernel, dim3(32, count), dim3(256), 0, s, (const f32x4*)v.win, v.ids, v.dth, 0, Thmax, (f32x4*)w.head.ssl_f);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(w.head.lens, v.dth, (size_t)count * 4, hipMemcpyDeviceToDevice, s));
+    if (e->s3) {  // (fp32 operand buffers: the head's LL converts the rows it reads into its own scratch)
+      HIP_OK(hipMemcpyAsync(w.head.ssl_h, w.head.ssl_f, (size_t)count * Thmax * kD * 4, hipMemcpyDeviceToDevice, s));
+    } else {
+      hipLaunchKernelGGL(f32_to_half_kernel, dim3(1024), dim3(256), 0, s, w.head.ssl_f, (uint16_t*)w.head.ssl_h, (size_t)count * Thmax * kD, e->dt == AFX_DT_BF16 ? 1 : 0);
+      HIP_OK(hipGetLastError());
+    }
+    begin_call(e, &w.head);
+    return run_head(e, count, Thmax, w.head, logits, s);
+  }
+  begin_call(e, &w.head);
+  for (size_t bi = 0; bi < v.buckets.size(); ++bi) {
+    const int t = v.buckets[bi].first, i0 = v.buckets[bi].second;
+    const int nb = (bi + 1 < v.buckets.size() ? v.buckets[bi + 1].second : count) - i0;
+    hipLaunchKernelGGL(kv_gather_kernel, dim3(32, nb), dim3(256), 0, s, (const f32x4*)v.win, v.b_ids + i0, (const int*)nullptr, t, t, (f32x4*)w.head.bucket_f);
+    HIP_OK(hipGetLastError());
+    if (const char* m = aasist_forward(e->aw, w.head.bucket_f, nb, t, w.head.aa, w.head.bucket_logits, s, e->nonfinite + 1)) return fail("%s", m);
+    hipLaunchKernelGGL(kv_scatter_logits_kernel, dim3((2 * nb + 255) / 256), dim3(256), 0, s, w.head.bucket_logits, v.b_row + i0, nb, logits);
+    HIP_OK(hipGetLastError());
+  }
+  return 0;
+}
+
+extern "C" size_t afx_kv_ragged_workspace_bytes(const afx_kv* k, int n_max) {
+  if (!k || n_max <= 0 || n_max > 16) return 0;
+  KvWs w;
+  return kv_carve(k->e, k->S, n_max, kKvWindow, nullptr, &w, true);
+}
+
+// feats6: device (S, n_max, 512) fp32, stream b's n_frames[b] new frames first (rows past them are read but never score);
+// n_frames: host, S entries, 1 <= n_frames[b] <= n_max <= 16.  Same function per stream as afx_kv_step on that stream alone.
+extern "C" int afx_kv_step_ragged(afx_kv* k, const float* feats6, int n, const int* n_frames, float* logits, void* ws, size_t ws_bytes,
+                                  void* stream) {
+  if (n < 1 || n > 16) return fail("afx_kv_step_ragged: a chunk brings 1..16 frames (got n_max %d)", n);
+  if (!k || !feats6 || !n_frames || !logits || !ws) return fail("afx_kv_step_ragged: null argument");
+  if (k->active) return fail("afx_kv_step_ragged: this state holds per-stream ring positions (afx_kv_step_active): continue with afx_kv_step_active");
+  afx_engine* e = k->e;
+  const int S = k->S, group = (int)(k->hop % kKvGroups);
+  for (int b = 0; b < S; ++b)
+    if (n_frames[b] < 1 || n_frames[b] > n) return fail("afx_kv_step_ragged: stream %d brings %d frames (1..%d)", b, n_frames[b], n);
+  hipStream_t s = (hipStream_t)stream;
+  if (kv_to_per_stream(k, s)) return 1;
+  int Thmax = 0;
+  std::vector<int>& hm = k->hmeta;  // meta: n | 64 + n | window lengths | back-end order
+  for (int b = 0; b < S; ++b) {
+    const int th = std::min(k->nfeat_s[b] + n_frames[b], kKvWindow);
+    if (e->cfg.arch == AFX_ARCH_XLSR_AASIST && th < 6) return fail("afx_kv_step_ragged: the AASIST head needs at least 6 frames in stream %d's window", b);
+    hm[b] = n_frames[b];
+    hm[S + b] = kKvHist + n_frames[b];
+    hm[2 * S + b] = th;
+    Thmax = std::max(Thmax, th);
+  }
+  KvWs w;
+  const size_t needb = kv_carve(e, S, n, Thmax, ws, &w, true);
+  if (ws_bytes < needb) return fail("afx_kv_step_ragged: workspace too small (%zu < %zu bytes)", ws_bytes, needb);
+  const int* dn = k->meta;
+  KvWindows v = {nullptr, S, Thmax, nullptr, dn + 2 * S, dn + 3 * S, dn + 3 * S, {}};  // (every stream, in place; scores in bucket order)
+  if (e->cfg.arch == AFX_ARCH_XLSR_AASIST) v.buckets = kv_buckets(&hm[2 * S], S, &hm[3 * S]);
+  HIP_OK(hipMemcpyAsync(k->meta, hm.data(), (size_t)S * 16, hipMemcpyHostToDevice, s));
+  HIP_OK(hipStreamSynchronize(s));  // (pageable host memory)
+  hipLaunchKernelGGL(kv_count_kernel, dim3((S + 255) / 256), dim3(256), 0, s, k->tab, dn, S, group);
+  HIP_OK(hipGetLastError());
+  KvForm f = {};
+  f.rows = S;
+  f.dn = dn;
+  f.pad_lens = dn + S;
+  f.ring = MhsaRingForm{2, group, nullptr, k->tab};
+  if (kv_trunk(k, f, feats6, n, w, s)) return 1;
+  float *cur = k->feat[k->pp], *nxt = k->feat[k->pp ^ 1];
   hipLaunchKernelGGL(kv_feat_kernel, dim3(64, S), dim3(256), 0, s, (const f32x4*)cur, (f32x4*)nxt, (const f32x4*)w.fl, dn, n);
   HIP_OK(hipGetLastError());
   k->pp ^= 1;
   for (int b = 0; b < S; ++b) k->nfeat_s[b] = std::min(k->nfeat_s[b] + n_frames[b], kKvFeat);
   k->hop += 1;
-  const int* dth = dn + 2 * S;
-  if (e->cfg.arch == AFX_ARCH_CONFORMER) {  // every stream's window left-aligned, key-padding lengths (afx_forward_ragged's head)
-    hipLaunchKernelGGL(kv_gather_kernel, dim3(32, S), dim3(256), 0, s, (const f32x4*)nxt, (const int*)nullptr, dth, 0, Thmax, (f32x4*)w.head.ssl_f);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(w.head.lens, dth, (size_t)S * 4, hipMemcpyDeviceToDevice, s));
-    if (e->s3) {
-      HIP_OK(hipMemcpyAsync(w.head.ssl_h, w.head.ssl_f, (size_t)S * Thmax * kD * 4, hipMemcpyDeviceToDevice, s));
-    } else {
-      hipLaunchKernelGGL(f32_to_half_kernel, dim3(1024), dim3(256), 0, s, w.head.ssl_f, (uint16_t*)w.head.ssl_h, (size_t)S * Thmax * kD, dt == AFX_DT_BF16 ? 1 : 0);
-      HIP_OK(hipGetLastError());
-    }
-    begin_call(e, &w.head);
-    return run_head(e, S, Thmax, w.head, logits, s);
-  }
-  begin_call(e, &w.head);
-  for (size_t bi = 0; bi < buckets.size(); ++bi) {
-    const int t = buckets[bi].first, i0 = buckets[bi].second;
-    const int nb = (bi + 1 < buckets.size() ? buckets[bi + 1].second : S) - i0;
-    const int* ids = dn + 3 * S + i0;
-    hipLaunchKernelGGL(kv_gather_kernel, dim3(32, nb), dim3(256), 0, s, (const f32x4*)nxt, ids, (const int*)nullptr, t, t, (f32x4*)w.head.bucket_f);
-    HIP_OK(hipGetLastError());
-    if (const char* m = aasist_forward(e->aw, w.head.bucket_f, nb, t, w.head.aa, w.head.bucket_logits, s, e->nonfinite + 1)) return fail("%s", m);
-    hipLaunchKernelGGL(kv_scatter_logits_kernel, dim3((2 * nb + 255) / 256), dim3(256), 0, s, w.head.bucket_logits, ids, nb, logits);
-    HIP_OK(hipGetLastError());
-  }
-  return 0;
+  v.win = nxt;
+  return kv_score_windows(e, w, v, logits, s);
 }
 
 // ---------------------------------------------------------------------------------
 // Steps over a list of active streams (afx_kv_step_active): only the listed streams advance, the others keep every byte of
 // their state.  The ring group is per stream from the first such step on -- tab[8 s + 1] is stream s's next group, its base
 // group plus its own step count mod 16 -- so a stream's chunks still fill consecutive groups from its base and the rotated
-// visit of the per-stream attention gives the key order of a fresh stream.  The list's QKV product writes entry b's chunk at
-// ring row 256 ids[b] + 16 group + r from the epilogue (launch_gemm_rows), the ring attention walks the list (RING == 3),
-// and the state kernels read and write by id: positional-conv context, the feature window (shifted in place per stream),
-// the back-end's windows.  Everything else runs on the A x n dense rows of the list.
+// visit gives the key order of a fresh stream.  Everything runs on the A x n dense rows of the list; state is reached by id.
 // ---------------------------------------------------------------------------------
 // every stream's next group = the lock-stepped group (the first active step of a state)
 __global__ void kv_activate_kernel(int* __restrict__ tab, int S, int group) {
@@ -2014,7 +1999,7 @@ extern "C" int afx_kv_step_active(afx_kv* k, const int* slots, int A, const floa
   if (n < 1 || n > 16) return fail("afx_kv_step_active: a chunk brings 1..16 frames (got n_max %d)", n);
   if (!slots || !feats6 || !n_frames || !logits || !ws) return fail("afx_kv_step_active: null argument");
   afx_engine* e = k->e;
-  const int S = k->S, dt = e->dt, M = A * n, Tp = kKvHist + n;
+  const int S = k->S;
   {
     std::vector<char> seen(S, 0);
     for (int i = 0; i < A; ++i) {
@@ -2048,140 +2033,29 @@ extern "C" int afx_kv_step_active(afx_kv* k, const int* slots, int A, const floa
     hm[2 * A + i] = th[i];
     hm[3 * A + i] = slots[i];
   }
-  std::vector<std::pair<int, int>> buckets;  // AASIST: (window length, first position in the back-end order)
-  if (e->cfg.arch == AFX_ARCH_XLSR_AASIST) {
-    std::vector<int> order(A);
-    for (int i = 0; i < A; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int c) { return th[a] < th[c]; });
-    for (int i = 0; i < A; ++i) {
-      hm[4 * A + i] = order[i];
-      hm[5 * A + i] = slots[order[i]];
-      if (i == 0 || th[order[i]] != th[order[i - 1]]) buckets.push_back({th[order[i]], i});
-    }
-  }
   int* dn = k->meta;
   const int *dids = dn + 3 * A, *drows = dn + 6 * A, *datab = dn + 8 * A;
+  KvWindows v = {k->feat[k->pp], A, Thmax, dids, dn + 2 * A, dn + 5 * A, dn + 4 * A, {}};  // (active steps: every window stays in this buffer)
+  if (e->cfg.arch == AFX_ARCH_XLSR_AASIST) {
+    v.buckets = kv_buckets(th.data(), A, &hm[4 * A]);
+    for (int i = 0; i < A; ++i) hm[5 * A + i] = slots[hm[4 * A + i]];
+  }
   HIP_OK(hipMemcpyAsync(dn, hm.data(), (size_t)6 * A * 4, hipMemcpyHostToDevice, s));
   HIP_OK(hipStreamSynchronize(s));  // (pageable host memory)
   hipLaunchKernelGGL(kv_active_tab_kernel, dim3((A + 255) / 256), dim3(256), 0, s, k->tab, dids, dn, A, dn + 8 * A, dn + 6 * A);
   HIP_OK(hipGetLastError());
-  begin_call(e, nullptr);
-  if (e->s3) {
-    t_s3planes = w.s3planes;
-    t_s3bytes = w.s3bytes;
-    s3_begin({w.feats_h, w.hbuf, w.att, w.ff, w.xpad, (char*)w.xpad + (size_t)kKvHist * kD * e->hsz});
-  }
-  const size_t hs = e->hsz;
-  {
-    RowNormArgs a = plain_norm(feats6, kC, M, kC, e->F("ssl.layer_norm.weight"), e->F("ssl.layer_norm.bias"));
-    a.out_h = w.feats_h; a.ldo_h = kC;
-    KOK(launch_rownorm(a, dt, s));
-  }
-  const size_t xrow = (size_t)kD * hs;
-  hipLaunchKernelGGL(kv_hist_kernel, dim3(32, A), dim3(256), 0, s, (u32x4*)k->hist, (u32x4*)w.xpad, dn, (long)(xrow / 16),
-                     (long)(Tp + kPosK), kPosPad, dids, 1);
-  HIP_OK(hipGetLastError());
-  {
-    GemmArgs g = plain_gemm(w.feats_h, kC, e->projw, kC, M, kD, kC);
-    g.rpb = n; g.a_batch = (long)n * kC; g.a_row = kC;
-    g.bias = e->F("ssl.post_extract_proj.bias");
-    g.out_f = w.x; g.ldo_f = kD; g.o_batch_rows = n;
-    g.out_h = w.xpad; g.ldo_h = kD; g.oh_batch_rows = Tp + kPosK; g.oh_row_off = kPosPad + kKvHist;
-    KOK(launch_gemm(g, dt, 1, s));
-    KOK(timed(PC_MISC, 0, s, [&] { return launch_zero_pad_rows(w.xpad, A, Tp, kD, kPosPad, kPosK - kPosPad, dt, s, dn + A); }));
-  }
-  void* xchunk = (char*)w.xpad + (size_t)kKvHist * xrow;
-  if (!e->s3) {
-    PosConvArgs pc;
-    memset(&pc, 0, sizeof pc);
-    pc.xpad = xchunk; pc.xpad_batch = (long)(Tp + kPosK) * kD; pc.W = e->posw; pc.bias = e->F("ssl.encoder.pos_conv.0.bias");
-    pc.x = w.x; pc.B = A; pc.T = n;
-    KOK(timed(PC_POSCONV, 2.0 * A * n * kD * (kD / kPosG) * kPosK, s, [&] { return launch_posconv(pc, dt, s); }));
-  } else {
-    const int cpg = kD / kPosG;
-    s3_set(xchunk, kS3ScaleFree);
-    GemmArgs g = plain_gemm(xchunk, 0, e->posw, (long)cpg * kPosK, A * n, cpg, cpg * kPosK);
-    g.rpb = n; g.a_batch = (long)(Tp + kPosK) * kD; g.a_row = kD;
-    g.kchunk = cpg; g.kchunk_stride = kD;
-    g.g_a = cpg; g.g_w = (long)cpg * cpg * kPosK; g.g_n = cpg;
-    g.bias = e->F("ssl.encoder.pos_conv.0.bias");
-    g.act = ACT_GELU;
-    g.resid = w.x; g.ldr = kD;
-    g.out_f = w.x; g.ldo_f = kD; g.o_batch_rows = n; g.oh_batch_rows = n;
-    KOK(launch_gemm(g, dt, kPosG, s));
-  }
-  hipLaunchKernelGGL(kv_hist_kernel, dim3(32, A), dim3(256), 0, s, (u32x4*)k->hist, (u32x4*)w.xpad, dn, (long)(xrow / 16),
-                     (long)(Tp + kPosK), kPosPad, dids, 0);
-  HIP_OK(hipGetLastError());
-  for (int l = 0; l < e->cfg.n_layers; ++l) {
-    const std::string P = "ssl.encoder.layers." + std::to_string(l) + ".";
-    void* ring = (char*)k->rings + (size_t)l * S * kKvSlots * 3 * kD * hs;
-    RowNormArgs n1 = plain_norm(w.x, kD, M, kD, e->F(P + "self_attn_layer_norm.weight"), e->F(P + "self_attn_layer_norm.bias"));
-    n1.out_h = w.hbuf; n1.ldo_h = kD;
-    KOK(launch_rownorm(n1, dt, s));
-    // entry b's q | k | v rows go to ring row 256 ids[b] + 16 group + r (the row table of the epilogue)
-    GemmArgs q = plain_gemm(w.hbuf, kD, e->wqkv[l], kD, M, 3 * kD, kD);
-    q.rpb = n; q.a_batch = (long)n * kD; q.a_row = kD;
-    q.bias = e->bqkv[l];
-    q.out_h = ring; q.ldo_h = 3 * kD; q.oh_rows = drows;
-    KOK(launch_gemm(q, dt, 1, s, true));
-    KOK(timed(PC_MHSA, 4.0 * A * kH * 16.0 * kKvSlots * 64, s, [&] {
-      if (e->s3) {
-        const bool pairs = s3_ok(w.att);
-        s3_set(w.att, pairs ? kS3ScaleFree : 0.f);
-        return launch_mhsa_ring_split_active((const float*)ring, (float*)w.att, A, kH, datab, s, pairs, kS3ScaleFree);
-      }
-      return launch_mhsa_ring_active(ring, w.att, A, kH, datab, dt, s);
-    }));
-    GemmArgs o = plain_gemm(w.att, kD, e->wo[l], kD, M, kD, kD);
-    o.rpb = n; o.a_batch = 16L * kD; o.a_row = kD; o.o_batch_rows = n;
-    o.bias = e->F(P + "self_attn.out_proj.bias"); o.resid = w.x; o.ldr = kD; o.out_f = w.x; o.ldo_f = kD;
-    KOK(launch_gemm(o, dt, 1, s));
-    RowNormArgs n2 = plain_norm(w.x, kD, M, kD, e->F(P + "final_layer_norm.weight"), e->F(P + "final_layer_norm.bias"));
-    n2.out_h = w.hbuf; n2.ldo_h = kD;
-    KOK(launch_rownorm(n2, dt, s));
-    GemmArgs f1 = plain_gemm(w.hbuf, kD, e->w1[l], kD, M, kF, kD);
-    f1.bias = e->F(P + "fc1.bias"); f1.act = ACT_GELU; f1.out_h = w.ff; f1.ldo_h = kF;
-    KOK(launch_gemm(f1, dt, 1, s));
-    GemmArgs f2 = plain_gemm(w.ff, kF, e->w2[l], kF, M, kD, kF);
-    f2.bias = e->F(P + "fc2.bias"); f2.resid = w.x; f2.ldr = kD; f2.out_f = w.x; f2.ldo_f = kD;
-    KOK(launch_gemm(f2, dt, 1, s));
-  }
-  float* win = k->feat[k->pp];  // (active steps: every window stays in this buffer)
-  {
-    RowNormArgs nf = plain_norm(w.x, kD, M, kD, e->F("ssl.encoder.layer_norm.weight"), e->F("ssl.encoder.layer_norm.bias"));
-    nf.out_f = w.fl; nf.ldo_f = kD;
-    nf.nonfinite = e->nonfinite;
-    KOK(launch_rownorm(nf, dt, s));
-  }
-  hipLaunchKernelGGL(kv_shift_kernel, dim3(kD / 4 / 32, A), dim3(256), 0, s, (f32x4*)win, (const f32x4*)w.fl, dids, dn, n);
+  KvForm f = {};
+  f.rows = A;
+  f.dn = dn;
+  f.ids = dids;
+  f.pad_lens = dn + A;
+  f.qkv_rows = drows;
+  f.ring = MhsaRingForm{3, 0, nullptr, datab};
+  if (kv_trunk(k, f, feats6, n, w, s)) return 1;
+  hipLaunchKernelGGL(kv_shift_kernel, dim3(kD / 4 / 32, A), dim3(256), 0, s, (f32x4*)k->feat[k->pp], (const f32x4*)w.fl, dids, dn, n);
   HIP_OK(hipGetLastError());
   for (int i = 0; i < A; ++i) k->nfeat_s[slots[i]] = std::min(k->nfeat_s[slots[i]] + n_frames[i], kKvFeat);
-  const int* dth = dn + 2 * A;
-  if (e->cfg.arch == AFX_ARCH_CONFORMER) {
-    hipLaunchKernelGGL(kv_gather_kernel, dim3(32, A), dim3(256), 0, s, (const f32x4*)win, dids, dth, 0, Thmax, (f32x4*)w.head.ssl_f);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(w.head.lens, dth, (size_t)A * 4, hipMemcpyDeviceToDevice, s));
-    if (e->s3) {
-      HIP_OK(hipMemcpyAsync(w.head.ssl_h, w.head.ssl_f, (size_t)A * Thmax * kD * 4, hipMemcpyDeviceToDevice, s));
-    } else {
-      hipLaunchKernelGGL(f32_to_half_kernel, dim3(1024), dim3(256), 0, s, w.head.ssl_f, (uint16_t*)w.head.ssl_h, (size_t)A * Thmax * kD, dt == AFX_DT_BF16 ? 1 : 0);
-      HIP_OK(hipGetLastError());
-    }
-    begin_call(e, &w.head);
-    return run_head(e, A, Thmax, w.head, logits, s);
-  }
-  begin_call(e, &w.head);
-  for (size_t bi = 0; bi < buckets.size(); ++bi) {
-    const int t = buckets[bi].first, i0 = buckets[bi].second;
-    const int nb = (bi + 1 < buckets.size() ? buckets[bi + 1].second : A) - i0;
-    hipLaunchKernelGGL(kv_gather_kernel, dim3(32, nb), dim3(256), 0, s, (const f32x4*)win, dn + 5 * A + i0, (const int*)nullptr, t, t, (f32x4*)w.head.bucket_f);
-    HIP_OK(hipGetLastError());
-    if (const char* m = aasist_forward(e->aw, w.head.bucket_f, nb, t, w.head.aa, w.head.bucket_logits, s, e->nonfinite + 1)) return fail("%s", m);
-    hipLaunchKernelGGL(kv_scatter_logits_kernel, dim3((2 * nb + 255) / 256), dim3(256), 0, s, w.head.bucket_logits, dn + 4 * A + i0, nb, logits);
-    HIP_OK(hipGetLastError());
-  }
-  return 0;
+  return kv_score_windows(e, w, v, logits, s);
 }
 
 // ---------------------------------------------------------------------------------

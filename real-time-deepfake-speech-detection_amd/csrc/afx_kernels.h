@@ -295,22 +295,24 @@ void mhsa_set_vtr(int v);  // A/B knob: V row-major in LDS + ds_read_b64_tr_b16 
 // out_pairs: `out` receives the pair form of out_scale x the result (row by row, in place of the fp32 rows) instead of fp32 rows
 const char* launch_mhsa_split(const float* qkv, float* out, int B, int T, int H, hipStream_t s, const int* lens = nullptr,
                               bool out_pairs = false, float out_scale = 1.f);
-// KV-cached streaming attention (afx_kv_step; not a reference function): ring (S, 256, 3*H*64) rows [q | k | v] in 16-slot
-// groups, cnt[16] valid frames per group, the queries are group q_tile's slots; out (S, 16, H*64)
-const char* launch_mhsa_ring(const void* ring, void* out, int S, int H, int q_tile, const int* cnt, int dtype, hipStream_t s);
+// KV-cached streaming attention (afx_kv_step*; not a reference function): ring (S, 256, 3*H*64) rows [q | k | v] in 16-slot
+// groups; each of the S blocks attends from one group's 16 query slots to every valid slot; out (S, 16, H*64).  The form:
+//   1 (lock-step)          cnt = host, 16 valid counts shared by the streams; the queries are group q_tile's slots
+//   2 (per-stream sessions) tab = device (S, 8) ints per stream -- [0] its base group, bytes [16, 32) its 16 valid counts; the
+//                          slots are visited rotated by the base group (the key order of a stream that started at group 0);
+//                          the queries are group q_tile's slots
+//   3 (a list of streams)  tab = device (S, 8) ints per list entry -- as form 2, [1] the stream's newest group (its query
+//                          tile), [2] its ring index; output block b = entry b's
+struct MhsaRingForm {
+  int form;
+  int q_tile;      // forms 1, 2: 0..15
+  const int* cnt;  // form 1
+  const int* tab;  // forms 2, 3
+};
+const char* launch_mhsa_ring(const void* ring, void* out, int S, int H, const MhsaRingForm& f, int dtype, hipStream_t s);
 // the same in split precision (dtype "fp16x3"): fp32 [q | k | v] slots in; fp32 rows or (out_pairs) pair-form rows out
-const char* launch_mhsa_ring_split(const float* ring, float* out, int S, int H, int q_tile, const int* cnt, hipStream_t s,
+const char* launch_mhsa_ring_split(const float* ring, float* out, int S, int H, const MhsaRingForm& f, hipStream_t s,
                                    bool out_pairs = false, float out_scale = 1.f);
-// per-stream sessions (afx_kv_step_ragged): tab = (S, 8) ints per stream -- [0] the stream's base group, bytes [16, 32) its
-// 16 valid counts; the slots are visited rotated by the base group (the key order of a stream that started at group 0)
-const char* launch_mhsa_ring_tab(const void* ring, void* out, int S, int H, int q_tile, const int* tab, int dtype, hipStream_t s);
-const char* launch_mhsa_ring_split_tab(const float* ring, float* out, int S, int H, int q_tile, const int* tab, hipStream_t s,
-                                       bool out_pairs, float out_scale);
-// a step over a list of active streams (afx_kv_step_active): tab = (A, 8) ints per list entry -- [0] base group, [1] the
-// stream's newest group (its query tile), [2] its ring index, bytes [16, 32) its valid counts; output row b = entry b's
-const char* launch_mhsa_ring_active(const void* ring, void* out, int A, int H, const int* tab, int dtype, hipStream_t s);
-const char* launch_mhsa_ring_split_active(const float* ring, float* out, int A, int H, const int* tab, hipStream_t s, bool out_pairs,
-                                          float out_scale);
 
 // ---- Conformer student head (afx_conformer.hip) ----------------------------------
 // y = selu(bn(x)) for rows 1..T of each utterance, row 0 = class token; x is the LL

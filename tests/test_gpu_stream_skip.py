@@ -104,6 +104,29 @@ def test_kv_cached_skipping_slots_score_bit_identical_to_fresh_lockstep_streams(
     _check("kv", eng, sd, f"{arch} kv-cached")
 
 
+def test_kv_cached_forms_agree_in_bf16():
+    """The three forms of the KV-cached step through the bf16 ring attention.  Skipping slots (list steps) score bit for bit
+    as fresh lock-stepped streams; then lock-stepped pushes, a reset and per-stream (ragged) steps: the restarted slot scores
+    as a fresh stream fed its audio, the others as if nothing happened.  No bf16 accuracy against the oracle is claimed
+    (measured, not gated)."""
+    from afx import synth
+    eng, sd = _engine("xlsr_aasist", "bf16")
+    _check("kv", eng, sd, "xlsr_aasist bf16 kv-cached")
+    n, at = 20, 3  # (17 per-stream steps: the 16-group ring wraps in this form too)
+    audio = synth.waveforms(S, n * H, batch_idx=5500).reshape(S, n, H)
+    a, b, c = _make("kv", eng, sd), _make("kv", eng, sd), _make("kv", eng, sd)
+    for t in range(n):
+        if t == at:
+            a.reset([1])
+        got = a.push(audio[:, t].cuda()).clone().cpu()
+        ref = b.push(audio[:, t].cuda()).clone().cpu()  # never reset: lock-stepped throughout
+        keep = [0, 2, 3] if t >= at else [0, 1, 2, 3]
+        assert torch.equal(got[keep], ref[keep]), f"bf16 ragged step, tick {t}: the slots that were not reset"
+        if t >= at:
+            fresh = c.push(audio[:, t].cuda()).clone().cpu()  # slot 1's session from its first hop
+            assert torch.equal(got[1], fresh[1]), f"bf16 ragged step, tick {t}: the restarted slot"
+
+
 def test_kv_cached_skipping_in_split_precision_holds_bits_and_the_offline_restatement():
     from oracle import streaming as ostream
     eng, sd = _engine("xlsr_aasist", "fp16x3")
