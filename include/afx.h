@@ -375,6 +375,40 @@ int afx_k_jitter_conceal(float* jring, int S, int J, const int* hdr, int rows, i
  *     leave a ring is skipped whole. */
 int afx_k_jitter_release(const float* jring, int S, int J, const int* hdr, int rows, int max_out, const float* taps, int L,
                          int M, int T, float* ring, int ring_len, void* stream);
+/* The jitter buffer over slots of different clock rates (afx/jitter.py MixedJitterScorer).  A rate is (taps, L, M, T) as for
+ * afx_k_jitter_release (taps NULL with L = M = T = 1: the identity), its ring length J = lookback + W with
+ * lookback = max(T-1, P+F), its repeat period P and fade length F in that rate's samples and its fade table (device, max(F, 1)
+ * fp32; read in mode 1 only).  rates (HOST, n_rates entries, 1..16) is read during the call and travels to the kernels by
+ * value: there is no device table; taps and fade are device pointers.  jring is (S, Js) fp32 with Js >= every rate's J: a slot
+ * at rate f keeps sample i of its stream at column i mod J_f of its row, uses the columns [0, J_f) only and never touches a
+ * column at or beyond J_f, so the sizing invariant above holds per slot with its own J_f.  A row names its rate by an index, the
+ * last int of its header, and is validated against ITS rate (index in range, column < J_f, n <= J_f, d_hi + P_f <= J_f,
+ * p0 < L_f, and the one-rate kernel's other checks); a row that fails writes nothing.  Every value written is the one the
+ * one-rate entry point writes in a launch of that rate: the same decoder, the same single fp32 multiply, the same inputs, taps
+ * and ascending-j fma chain.
+ * afx_k_jitter_place_rates: hdr (device, rows x 6 int32): afx_k_jitter_place_mixed's five ints, then the rate index;
+ *     jring[slot][(c + k) mod J_f] = decode(sample k), k < n.  max_n = the largest n <= Js.
+ * afx_k_jitter_conceal_rates: hdr (device, rows x 5 int32): afx_k_jitter_conceal's four ints, then the rate index; the
+ *     function of afx_k_jitter_conceal with the row's P_f, F_f, fade_f and J_f.  mode (0 zero, 1 repeat) is the launch's; in
+ *     mode 0 the rates' P, F and fade are not read.  max_n = the largest d_hi - d_lo <= Js.
+ * afx_k_jitter_release_rates: hdr (device, rows x 8 int32): afx_k_jitter_release's, the eighth int the rate index.  max_out
+ *     (HOST, n_rates ints): per rate the largest n_out among its rows of this call, 0 = no row of it (a row with more outputs than its
+ *     rate's max_out writes nothing).  The grid and the dynamic LDS are the largest over the rates present; a workgroup beyond its row's
+ *     outputs leaves before it stages anything.
+ * Refused with nothing launched: n_rates outside 1..16, a null table, a bad filter shape, T - 1 > J, J outside 1..Js, M/L
+ * above 12, mode 1 with a null fade or P <= 0, a null stage / hdr / jring / ring / max_out, rows outside 1..65535, max_n beyond
+ * Js, a max_out beyond ring_len. */
+typedef struct afx_jitter_rate {
+  const float* taps; /* device, (L, T) fp32; NULL: the identity */
+  const float* fade; /* device, (max(F, 1),) fp32: fp32(1 - d/F); may be NULL in mode 0 */
+  int L, M, T, J, P, F;
+} afx_jitter_rate;
+int afx_k_jitter_place_rates(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n,
+                             const afx_jitter_rate* rates, int n_rates, float* jring, int S, int Js, void* stream);
+int afx_k_jitter_conceal_rates(float* jring, int S, int Js, const int* hdr, int rows, int max_n, const afx_jitter_rate* rates,
+                               int n_rates, int mode, void* stream);
+int afx_k_jitter_release_rates(const float* jring, int S, int Js, const int* hdr, int rows, const afx_jitter_rate* rates,
+                               int n_rates, const int* max_out, float* ring, int ring_len, void* stream);
 /* Speech gate (afx/vad.py): an energy gate with noise-floor tracking and hangover over frames of `frame` 16 kHz samples
  * (160 = 10 ms), per slot.  Constants, fp32: e_floor (the mean-square floor times frame), ratio > 1, rise >= 1, and
  * nf_min = e_floor / ratio (one fp32 division); hang >= 0 frames.  State per slot: nf (S,) fp32, +inf for a new stream, and

@@ -35,6 +35,12 @@ class IngestFormat(C.Structure):
     _fields_ = [("taps", C.c_void_p), ("encoding", C.c_int), ("L", C.c_int), ("M", C.c_int), ("T", C.c_int)]
 
 
+class JitterRate(C.Structure):
+    """afx_jitter_rate: one entry of the host rate table of afx_k_jitter_place_rates / _conceal_rates / _release_rates."""
+    _fields_ = [("taps", C.c_void_p), ("fade", C.c_void_p), ("L", C.c_int), ("M", C.c_int), ("T", C.c_int), ("J", C.c_int),
+                ("P", C.c_int), ("F", C.c_int)]
+
+
 # symbol -> (restype, argtypes); must list every function include/afx.h declares
 SIGNATURES = {
     "afx_create": (_I, [C.POINTER(Config), C.POINTER(_P)]),
@@ -107,6 +113,9 @@ SIGNATURES = {
     "afx_k_jitter_place_mixed": (_I, [_P, C.c_longlong, _P, _I, _I, _P, _I, _I, _P]),
     "afx_k_jitter_conceal": (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _I, _I, _P]),
     "afx_k_jitter_release": (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _I, _I, _P, _I, _P]),
+    "afx_k_jitter_place_rates": (_I, [_P, C.c_longlong, _P, _I, _I, _P, _I, _P, _I, _I, _P]),
+    "afx_k_jitter_conceal_rates": (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _I, _P]),
+    "afx_k_jitter_release_rates": (_I, [_P, _I, _I, _P, _I, _P, _I, _P, _P, _I, _P]),
     "afx_k_gate": (_I, [_P, _I, _I, _P, _I, _F, _F, _F, _I, _P, _P, _P, _I, _I, _P, _P, _P]),
     "afx_k_gate_la": (_I, [_P, _I, _I, _P, _I, _F, _F, _F, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P]),
     "afx_k_gate_tone": (_I, [_P, _I, _I, _P, _I, _F, _F, _F, _I, _P, _I, _F, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),

@@ -48,21 +48,44 @@ Several encodings at one clock rate: the reorder ring is decoded, so a session d
 per packet (``encodings``; default: the first listed), ``feed_rtp`` any datagram whose payload type maps to a listed one, and
 a stream may change between them from packet to packet.  The place rows then carry their encoding
 (``afx_k_jitter_place_mixed``: the same kernel with the encoding read per row).  State layout and contract are unchanged.
+
+Every slot its own clock rate: ``MixedJitterScorer(scorer, formats, depth_ms, ...)`` takes 1 to 16 (input_rate, encoding)
+pairs; a slot's rate is chosen at ``reset(slots, rates)``.  Per rate r, in that rate's samples: depth_r = depth_ms * r //
+1000, P_r = r // 100 (``period_ms`` given: max(1, period_ms * r // 1000)), F_r = 3 P_r (``fade_ms`` given: fade_ms * r //
+1000); P_r = F_r = 0 with conceal="zero".  The contract: take a slot s at rate r, whatever the other slots' rates.  Its
+scores, hop counts per call, ``stats()``, ``samples_in``, ``buffered`` and ``pending`` are, bit for bit and call for call,
+those of ``JitterScorer(inner, r, encodings_at_r, depth_r, conceal, period=P_r, fade=F_r, max_pending, ts_bits)`` fed the
+slot's own packets in the same calls: the inner scorer runs on ``Resampler(r)(E_s)`` with E_s the played-out stream defined
+above.  No new arithmetic: the rate is a per-row value of the same three launches (``afx_k_jitter_place_rates`` /
+``_conceal_rates`` / ``_release_rates``: the row's last int names its rate, the workgroup runs the one-rate kernel's row
+body with that rate's J, P, F, fade table and filter), so every value comes from the same decoder, the same single fp32
+multiply and the same taps and ascending-j fma chain as in a one-rate launch, and the host plans each slot with its own
+L, M, J, W, F and depth.  Sizing: per rate JitterScorer's lookback_r = max(T_r - 1, P_r + F_r), W_r = depth_r +
+ceil(hop * M_r / L_r) + 1, J_r = lookback_r + W_r; one ring (S, Js), Js = max J_r; a slot at rate r uses the columns
+[0, J_r) of its row with modulus J_r and never a column at or beyond J_r, so the invariant above holds per slot with its own
+J_r.  A mixed state has ``jitter_ring`` (n, widest lookback_r + depth_r), zeros beyond a session's own columns,
+``jitter_rate`` ((n,) int64) and ``jitter_params`` ((n, 3) int64: depth, period, fade), and the meta ``jitter``,
+``jitter_conceal``, ``resampler`` and ``jitter_mixed``; a plain JitterScorer's state imports where its rate is listed and
+its parameters are that rate's.  Out of scope: a rate change without a reset, per-slot depth within one rate, big-endian
+L16 payloads (swap the bytes), per-slot conceal modes.
 """
+import ctypes as C
+
 import numpy as np
 import torch
 
 from . import rtp
 from ._layer import _on, check_pending, export_pending, import_pending, peel, rows_on, wrap
-from ._lib import call_on, check, lib, ptr
-from .ingest import _MAX_SAMPLES, _SAMPLE, ENCODINGS, _at, _encoding, layout
-from .resample import FILTER_ID
+from ._lib import JitterRate, call_on, check, lib, ptr
+from .ingest import _MAX_SAMPLES, _SAMPLE, ENCODINGS, MAX_FORMATS, _at, _encoding, _format, layout
+from .resample import FILTER_ID, Resampler
 from .streaming import _Front
 
 JITTER_FORMAT = 1  # layout of the jitter part of a StreamState: import_slots refuses any other
 CONCEAL = ("zero", "repeat")  # the library's mode numbers 0, 1
 PLACE_HDR, CONCEAL_HDR, RELEASE_HDR = 4, 4, 8  # int32 per row of the three tables (include/afx.h)
 PLACE_MIXED_HDR = 5  # afx_k_jitter_place_mixed: a place row, then its encoding's number
+PLACE_RATES_HDR, CONCEAL_RATES_HDR = 6, 5  # afx_k_jitter_place_rates / _conceal_rates: the row, then its rate's index
 STATS = ("received", "late", "duplicate", "concealed", "out_of_order")
 _STATE_KEYS = ("jitter_pending", "jitter_fill", "jitter_ring", "jitter_book", "jitter_stats", "jitter_intervals")
 _BOOK = ("origin", "started", "next", "hi", "gap", "max_start", "max_seq", "ssrc")  # jitter_book columns
@@ -170,6 +193,7 @@ class JitterScorer(_Front):
     crossing 2**32 is seamless; None takes absolute indices."""
 
     _WORK = "decoded, concealed, resampled"
+    _rated = False  # (MixedJitterScorer: the rows of a plan carry their slot's rate index)
 
     def __init__(self, scorer, input_rate, encoding, depth, conceal="repeat", period=None, fade=None, max_pending=4, ts_bits=32):
         if isinstance(encoding, str):
@@ -233,6 +257,11 @@ class JitterScorer(_Front):
         return {k: torch.from_numpy(getattr(self._b, f).copy()) for k, f in zip(STATS, _COUNTERS)}
 
     # ---- planning (host arithmetic only) -----------------------------------------------------------------------------
+    def _geometry(self, slot):
+        """(L, M, J, W, F, depth, rate index) of the slots ``slot``: int64 arrays over them."""
+        n = len(slot)
+        return tuple(np.full(n, v, dtype=np.int64) for v in (self.L, self.M, self.J, self.W, self.fade_len, self.depth, 0))
+
     def _unwrap(self, t, ref):
         """Timestamp t as the absolute value nearest ref (ts_bits), or as it is."""
         if self.ts_bits is None:
@@ -340,7 +369,7 @@ class JitterScorer(_Front):
         offs[i] for slots[i], a slot possibly named more than once; flush / advance / drain: distinct slots) -> Plan.  No
         state changes here: ``_commit(plan.book)`` (or ``_run``) makes it so."""
         b = self._b.copy()
-        L, M, R, hop, J, W, F = self.L, self.M, self.ring_len, self.hop, self.J, self.W, self.fade_len
+        R, hop = self.ring_len, self.hop
         slot = np.asarray(slots, dtype=np.int64).reshape(-1)
         if mode == "feed":
             pl = self._place_rows(b, slot, np.asarray(sizes, dtype=np.int64).reshape(-1), np.asarray(ts, dtype=np.int64).reshape(-1),
@@ -351,9 +380,10 @@ class JitterScorer(_Front):
         _, first = np.unique(slot, return_index=True)
         first.sort()
         U = slot[first]  # the named slots, once each, in the order they were first named
+        L, M, J, W, F, depth, rate = self._geometry(U)  # (int64 arrays over U: a scorer of one rate passes constants)
         cur = b.next[U].copy()
         if mode == "feed":
-            tgt = np.maximum(cur, b.hi[U] - self.depth)
+            tgt = np.maximum(cur, b.hi[U] - depth)
         elif mode == "flush":
             tgt = b.hi[U].copy()
         elif mode == "advance":
@@ -383,10 +413,11 @@ class JitterScorer(_Front):
         while True:
             progress = False
             # place what the window [cur, cur + W) of each slot takes
-            take = np.clip(cur[pu] + W - (pstart + pdone), 0, pn - pdone)
+            take = np.clip(cur[pu] + W[pu] - (pstart + pdone), 0, pn - pdone)
             k = np.flatnonzero(take > 0)
             if k.size:
-                cols = [U[pu[k]], poff[k] + pdone[k] * bps[k], take[k], (pstart[k] + pdone[k]) % J] + ([penc[k]] if self._mixed else [])
+                cols = [U[pu[k]], poff[k] + pdone[k] * bps[k], take[k], (pstart[k] + pdone[k]) % J[pu[k]]] + (
+                    [penc[k]] if self._mixed else []) + ([rate[pu[k]]] if self._rated else [])
                 rows = np.stack(cols, axis=1).astype(np.int32)
                 ops.append(("place", rows, int(take[k].max())))
                 pdone[k] += take[k]
@@ -396,26 +427,29 @@ class JitterScorer(_Front):
             m = np.maximum(np.minimum(np.minimum(tgt - cur, W), (made + R - fill) * M // L - cur), 0)
             ranks = []
             for u, gl in gaps.items():  # the gaps inside [cur, cur + m) of the slots that have any, by rank within the slot
-                c0, c1, s, rank = int(cur[u]), int(cur[u] + m[u]), int(U[u]), 0
+                c0, c1, s, rank, Fu, Ju = int(cur[u]), int(cur[u] + m[u]), int(U[u]), 0, int(F[u]), int(J[u])
+                tail = (int(rate[u]),) if self._rated else ()
                 for a, lo, hi in gl:
                     lo, hi = max(lo, c0), min(hi, c1)
                     if lo >= hi:
                         continue
                     d_lo, d_hi = lo - a, hi - a
-                    if d_lo >= F:  # all zeros from here on: the same row counted from a + d_lo - F (d stays small)
-                        a, d_lo, d_hi = a + d_lo - F, F, F + d_hi - d_lo
+                    if d_lo >= Fu:  # all zeros from here on: the same row counted from a + d_lo - F (d stays small)
+                        a, d_lo, d_hi = a + d_lo - Fu, Fu, Fu + d_hi - d_lo
                     if rank == len(ranks):
                         ranks.append([])
-                    ranks[rank].append((s, a % J, d_lo, d_hi))
+                    ranks[rank].append((s, a % Ju, d_lo, d_hi) + tail)
                     rank += 1
             for rows in ranks:
                 rows = np.array(rows, dtype=np.int32)
                 ops.append(("conceal", rows, int((rows[:, 3] - rows[:, 2]).max())))
             k = np.flatnonzero(m > 0)
             if k.size:
-                n_out = -(-(cur[k] + m[k]) * L // M) - made[k]
+                Lk, Mk = L[k], M[k]
+                n_out = -(-(cur[k] + m[k]) * Lk // Mk) - made[k]
                 rows = np.zeros((k.size, RELEASE_HDR), dtype=np.int32)
-                for c, v in enumerate((U[k], cur[k] % J, m[k], n_out, made[k] * M % L, made[k] * M // L - cur[k], (head[k] + fill[k]) % R)):
+                for c, v in enumerate((U[k], cur[k] % J[k], m[k], n_out, made[k] * Mk % Lk, made[k] * Mk // Lk - cur[k],
+                                       (head[k] + fill[k]) % R, rate[k] if self._rated else 0)):
                     rows[:, c] = v
                 ops.append(("release", rows, int(n_out.max())))
                 cur[k] += m[k]
@@ -622,7 +656,17 @@ class JitterScorer(_Front):
         idx = self.scorer._slot_list(slots, ordered=True)
         inner = peel(state, _STATE_KEYS, self._meta(), "jitter-buffer part (it was not exported by a JitterScorer)")
         n = len(state)
-        pend, jr = state.tensors["jitter_pending"], state.tensors["jitter_ring"]
+        width = self.lookback + self.depth
+        jr = state.tensors["jitter_ring"]
+        if tuple(jr.shape) != (n, width) or jr.dtype != torch.float32:
+            raise ValueError(f"import_slots: jitter_ring {tuple(jr.shape)} {jr.dtype} does not fit this scorer ({(n, width)} float32)")
+        self._install(idx, inner, self._check_sessions(state, n, np.zeros(n, dtype=np.int64)))
+
+    def _check_sessions(self, state, n, rate):
+        """The checks of the jitter part of ``state`` (n sessions, session i at this scorer's rate index rate[i]) -> what
+        ``_install`` takes.  A ValueError for counters that contradict each other; nothing changes."""
+        L, M, J, _, _, depth, _ = self._geometry_of(rate)
+        pend = state.tensors["jitter_pending"]
         ints = [state.tensors[k].cpu() for k in ("jitter_fill", "jitter_book", "jitter_stats", "jitter_intervals")]
         if any(t.dtype != torch.int64 for t in ints):
             raise ValueError("import_slots: jitter_fill, jitter_book, jitter_stats and jitter_intervals are int64")
@@ -630,14 +674,11 @@ class JitterScorer(_Front):
         fill = fill.reshape(-1)
         if fill.size != n or book.shape != (n, len(_BOOK)) or stats.shape != (n, len(_COUNTERS)) or table.ndim != 3 or table.shape[2] != 2:
             raise ValueError("import_slots: jitter_fill (n,), jitter_book (n, 8), jitter_stats (n, 5), jitter_intervals (n, K, 2)")
-        width = self.lookback + self.depth
-        if tuple(jr.shape) != (n, width) or jr.dtype != torch.float32:
-            raise ValueError(f"import_slots: jitter_ring {tuple(jr.shape)} {jr.dtype} does not fit this scorer ({(n, width)} float32)")
         check_pending("jitter_pending", pend, fill, n, self.max_pending * self.hop)
         col = {f: book[:, c] for c, f in enumerate(_BOOK)}
         nxt, hi, gap = col["next"], col["hi"], col["gap"]
-        made = np.array([-(-int(v) * self.L // self.M) for v in nxt.tolist()], dtype=np.int64)
-        bad = ((nxt < 0) | (hi < nxt) | (hi - nxt > self.depth) | ((col["started"] != 0) & (col["started"] != 1)) |
+        made = np.array([-(-int(v) * l // m) for v, l, m in zip(nxt.tolist(), L.tolist(), M.tolist())], dtype=np.int64)
+        bad = ((nxt < 0) | (hi < nxt) | (hi - nxt > depth) | ((col["started"] != 0) & (col["started"] != 1)) |
                ((col["started"] == 0) & (hi != 0)) | (gap < -1) | (gap >= nxt) | (stats < 0).any(axis=1) |
                (stats[:, 3] > nxt) | (col["max_seq"] < -1) | (col["max_seq"] > 0xFFFF) | (col["ssrc"] < -1) | (col["ssrc"] >= 1 << 32))
         if bad.any() or not np.array_equal(made, state.seen.numpy() + fill):
@@ -649,22 +690,340 @@ class JitterScorer(_Front):
             if not ok or (not v and hi[i] != nxt[i]) or sum(e - a for a, e in v) > stats[i, 0]:
                 raise ValueError("import_slots: a session's received intervals contradict its counters")
             lists.append(v)
-        self.scorer.import_slots(idx, inner)  # (refuses a foreign state before changing anything)
+        return pend, state.tensors["jitter_ring"], fill, col, stats, lists, rate
+
+    def _geometry_of(self, rate):
+        """``_geometry`` by rate index (one entry per session of a state)."""
+        return self._geometry(rate)
+
+    def _lookbacks(self, rate):
+        return np.full(len(rate), self.lookback, dtype=np.int64)
+
+    def _install(self, idx, inner, checked):
+        """The inner scorer imports ``inner`` (it refuses a foreign state before changing anything), then the named slots take
+        the checked jitter part: ring columns [next - lookback, ...) at their places modulo each session's own J."""
+        pend, jr, fill, col, stats, lists, rate = checked
+        self.scorer.import_slots(idx, inner)
         if not idx:
             return
         dev, b = self.device, self._b
+        geo = self._geometry_of(rate)
+        J, lookback = geo[2], self._lookbacks(rate)
+        own = lookback + geo[5]  # each session's own columns of jitter_ring: lookback + depth
         import_pending(self.ring, idx, pend)
         with _on(dev):
             rows = rows_on(idx, dev)
             self.jring[rows] = 0.0
-            k = torch.arange(width)
-            cols = (torch.from_numpy(nxt.copy())[:, None] - self.lookback + k) % self.J
-            self.jring[rows[:, None], cols.to(dev)] = jr.to(dev)
+            for w in np.unique(own).tolist():  # (sessions of one rate at a time: a ring row may be wider than their own columns)
+                sel = np.flatnonzero(own == w)
+                k = torch.arange(w)
+                cols = (torch.from_numpy(col["next"][sel].copy())[:, None] - torch.from_numpy(lookback[sel])[:, None] + k) % \
+                    torch.from_numpy(J[sel])[:, None]
+                self.jring[rows[torch.from_numpy(sel).to(dev)][:, None], cols.to(dev)] = jr[torch.from_numpy(sel)][:, :w].to(dev)
         b.clear(idx)
         for f in _BOOK:
             getattr(b, f)[idx] = col[f]
         for c, f in enumerate(_COUNTERS):
             getattr(b, f)[idx] = stats[:, c]
         b.fill[idx] = fill
-        for s, v in zip(idx, lists):
-            b.set_intervals(s, v)
+        for s_, v in zip(idx, lists):
+            b.set_intervals(s_, v)
+
+
+def _fade_table(F, device):
+    return torch.from_numpy((1.0 - np.arange(max(F, 1), dtype=np.float64) / max(F, 1)).astype(np.float32)).to(device)
+
+
+class MixedJitterScorer(JitterScorer):
+    """``scorer`` fed timestamped packets, every slot at its own clock rate: ``formats`` is 1 to 16 distinct
+    (input_rate, encoding) pairs; their distinct rates are the scorer's rates, and the encodings listed at a rate are the ones
+    a packet of a slot at that rate may come in (the first listed: the default).  ``depth_ms``, ``period_ms`` (default 10)
+    and ``fade_ms`` (default three periods) are whole milliseconds; at rate r, depth = depth_ms * r // 1000,
+    P = r // 100 (``period_ms`` given: max(1, period_ms * r // 1000)) and F = 3 P (``fade_ms`` given: fade_ms * r // 1000) of
+    that rate's samples.  A slot's rate is chosen at ``reset`` (a fresh scorer has every slot at the first format's rate)
+    and never changes between resets; everything a ``JitterScorer`` counts in input samples is, per slot, in the slot's own
+    rate.  See the module docstring for the contract."""
+
+    _rated = True
+
+    def __init__(self, scorer, formats, depth_ms, conceal="repeat", period_ms=None, fade_ms=None, max_pending=4, ts_bits=32):
+        if isinstance(formats, (str, bytes)) or not hasattr(formats, "__len__") or not hasattr(formats, "__iter__"):
+            raise ValueError("formats: a sequence of (input_rate, encoding) pairs")
+        fm = tuple(_format(f) for f in formats)
+        if not 1 <= len(fm) <= MAX_FORMATS:
+            raise ValueError(f"{len(fm)} formats: 1 to {MAX_FORMATS}")
+        if len(set(fm)) != len(fm):
+            raise ValueError("formats: a format is listed twice")
+        depth_ms = _nonneg_int(depth_ms, "depth_ms")
+        if conceal not in CONCEAL:
+            raise ValueError(f"conceal {conceal!r}: one of {CONCEAL}")
+        period_ms = None if period_ms is None else _nonneg_int(period_ms, "period_ms")
+        fade_ms = None if fade_ms is None else _nonneg_int(fade_ms, "fade_ms")
+        max_pending = _nonneg_int(max_pending, "max_pending", 1)
+        if ts_bits is not None and (isinstance(ts_bits, bool) or not isinstance(ts_bits, (int, np.integer)) or not 8 <= ts_bits <= 48):
+            raise ValueError("ts_bits: None (absolute indices) or the width of the timestamp counter, 8..48")
+        self.ts_bits = None if ts_bits is None else int(ts_bits)
+        self.scorer, self.formats, self.conceal, self._mixed = scorer, fm, conceal, True
+        self.depth_ms, self.period_ms, self.fade_ms = depth_ms, period_ms, fade_ms
+        self._rates = tuple(dict.fromkeys(r for r, _ in fm))  # the distinct rates, in the order first listed
+        self._encs_at = [tuple(e for q, e in fm if q == r) for r in self._rates]
+        self._rs = [Resampler(r, scorer.device) for r in self._rates]
+        arr = lambda v: np.array(v, dtype=np.int64)
+        rate = arr(self._rates)
+        self._rrate, self._rL, self._rM = rate, arr([x.L for x in self._rs]), arr([x.M for x in self._rs])
+        self._rdepth = depth_ms * rate // 1000
+        if conceal == "repeat":
+            self._rP = rate // 100 if period_ms is None else np.maximum(1, period_ms * rate // 1000)
+            self._rF = 3 * self._rP if fade_ms is None else fade_ms * rate // 1000
+        else:
+            self._rP = self._rF = np.zeros_like(rate)  # (no part of the "zero" function)
+        # per rate exactly JitterScorer's sizing: lookback = max(T - 1, P + F), W = depth + one hop of input + 1, J = lookback + W
+        self._rlookback = np.maximum(arr([0 if x.identity else x.T - 1 for x in self._rs]), self._rP + self._rF)
+        self._rW = self._rdepth + -(-scorer.hop * self._rM // self._rL) + 1
+        self._rJ = self._rlookback + self._rW
+        self._rdelay = np.array([x.delay for x in self._rs], dtype=np.float64)
+        self.Js = int(self._rJ.max())
+        if self.Js >= _MAX_SAMPLES:
+            raise ValueError("depth + period + fade: less than 2**30 samples")
+        self._new_ring(max_pending)
+        self.jring = torch.zeros(scorer.S, self.Js, dtype=torch.float32, device=scorer.device)
+        self._fades = [_fade_table(int(F), scorer.device) for F in self._rF]  # one device table per rate
+        self._table = (JitterRate * len(self._rates))()  # the host table the three launches take (pointers: the tensors above)
+        for i, (t, x) in enumerate(zip(self._table, self._rs)):
+            t.taps = None if x.identity else x.taps.data_ptr()
+            t.fade = self._fades[i].data_ptr()
+            t.L, t.M, t.T = x.L, x.M, 1 if x.identity else x.T
+            t.J, t.P, t.F = int(self._rJ[i]), int(self._rP[i]), int(self._rF[i])
+        self._b = _Book(scorer.S)
+        self._rate_of = np.zeros(scorer.S, dtype=np.int64)  # rate index of each slot (host)
+
+    # ---- per-slot quantities ---------------------------------------------------------------------------------------------
+    @property
+    def rates(self):
+        """(S,) int64: each slot's clock rate in Hz."""
+        return torch.from_numpy(self._rrate[self._rate_of])
+
+    @property
+    def depths(self):
+        """(S,) int64: each slot's playout delay in its own rate's samples."""
+        return torch.from_numpy(self._rdepth[self._rate_of])
+
+    @property
+    def periods(self):
+        """(S,) int64: each slot's repeat period P in its own rate's samples (0 with conceal="zero")."""
+        return torch.from_numpy(self._rP[self._rate_of])
+
+    @property
+    def fades(self):
+        """(S,) int64: each slot's fade length F in its own rate's samples (0 with conceal="zero")."""
+        return torch.from_numpy(self._rF[self._rate_of])
+
+    @property
+    def delays(self):
+        """(S,) float64: each slot's ``Resampler.delay``, the lag of its resampled stream in 16 kHz samples."""
+        return torch.from_numpy(self._rdelay[self._rate_of])
+
+    @property
+    def delay(self):
+        raise AttributeError("a MixedJitterScorer has one delay per slot: delays")
+
+    @property
+    def depth(self):
+        raise AttributeError("a MixedJitterScorer has one depth per slot: depths")
+
+    @property
+    def period(self):
+        raise AttributeError("a MixedJitterScorer has one period per slot: periods")
+
+    @property
+    def input_rate(self):
+        raise AttributeError("a MixedJitterScorer has one input rate per slot: rates")
+
+    def _geometry_of(self, rate):
+        return (self._rL[rate], self._rM[rate], self._rJ[rate], self._rW[rate], self._rF[rate], self._rdepth[rate], rate)
+
+    def _geometry(self, slot):
+        return self._geometry_of(self._rate_of[slot])
+
+    def _lookbacks(self, rate):
+        return self._rlookback[rate]
+
+    def _rate_indices(self, rates, n):
+        """``rates``: one rate in Hz for n slots, or n of them -> (n,) int64 array of indices into this scorer's rates."""
+        if isinstance(rates, (torch.Tensor, np.ndarray)):
+            rates = rates.tolist()
+        one = isinstance(rates, (int, np.integer)) and not isinstance(rates, bool)
+        if not one and (isinstance(rates, (str, bytes)) or not hasattr(rates, "__len__")):
+            raise ValueError("rates: one rate in Hz, or one per named slot")
+        vals = [rates] * n if one else list(rates)
+        if len(vals) != n:
+            raise ValueError(f"{len(vals)} rates for {n} named slots")
+        for r in vals:
+            if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or int(r) not in self._rates:
+                raise ValueError(f"rate {r!r} is not one of this scorer's {self._rates}")
+        return np.array([self._rates.index(int(r)) for r in vals], dtype=np.int64).reshape(n)
+
+    # ---- the public calls ------------------------------------------------------------------------------------------------
+    def _plan_feed(self, packets, slots, timestamps, score=True, seqs=None, encodings=None):
+        idx = self._rows(slots, repeats=True)
+        ri = self._rate_of[np.asarray(idx, dtype=np.int64)].tolist()
+        if encodings is None:
+            names = [self._encs_at[r][0] for r in ri]
+        else:
+            if isinstance(encodings, str) or not hasattr(encodings, "__len__"):
+                raise ValueError("encodings: one encoding per packet")
+            names = list(encodings)
+            if len(names) != len(idx):
+                raise ValueError(f"{len(names)} encodings for {len(idx)} named slots")
+            for s, r, e in zip(idx, ri, names):
+                if e not in self._encs_at[r]:
+                    raise ValueError(f"slot {s}: encoding {e!r} is not one of this scorer's {self._encs_at[r]} at {self._rates[r]} Hz")
+        pay, nbytes = self._packets_each(packets, names)
+        encs = np.array([ENCODINGS.index(e) for e in names], dtype=np.int64)
+        ts = self._timestamps(timestamps, len(idx))
+        offs, total = layout(nbytes)
+        if total >= 1 << 31:
+            raise ValueError("a feed carries less than 2 GiB")
+        return self._plan(idx, nbytes // _BPS[encs], ts, offs, seqs, "feed", score=score, encs=encs), pay
+
+    def feed_rtp(self, datagrams, slots, payload_types=None, score=True):
+        """``JitterScorer.feed_rtp`` with ``payload_types`` mapping a number to an (input_rate, encoding) pair: 0 and 8 are
+        (8000, "mulaw") and (8000, "alaw") (RFC 3551).  A datagram whose type maps to another rate than its slot's, or to a
+        pair this scorer does not list, is a ValueError before anything changes."""
+        idx = self._rows(slots, repeats=True)
+        if isinstance(datagrams, (bytes, bytearray, memoryview)):
+            raise ValueError("datagrams: a list with one datagram per named slot")
+        pk = [rtp.parse(d) for d in datagrams]
+        if len(pk) != len(idx):
+            raise ValueError(f"{len(pk)} datagrams for {len(idx)} named slots")
+        if self.ts_bits != 32:
+            raise ValueError("feed_rtp: RTP timestamps are 32 bits wide (ts_bits = 32)")
+        types = {pt: (8000, e) for pt, e in rtp.STATIC_PAYLOAD_TYPES.items()}
+        for pt, f in (payload_types or {}).items():
+            types[pt] = _format(f)
+        ssrc = {}
+        for s, p in zip(idx, pk):
+            f = types.get(p.payload_type)
+            if f not in self.formats:
+                raise ValueError(f"slot {s}: RTP payload type {p.payload_type} maps to none of this scorer's formats {self.formats}")
+            if f[0] != self._rates[self._rate_of[s]]:
+                raise ValueError(f"slot {s}: RTP payload type {p.payload_type} is {f[0]} Hz, the slot is at "
+                                 f"{self._rates[self._rate_of[s]]} Hz")
+            mine = ssrc.setdefault(s, int(self._b.ssrc[s]) if self._b.ssrc[s] >= 0 else p.ssrc)
+            if p.ssrc != mine:
+                raise ValueError(f"slot {s}: SSRC {p.ssrc:#010x} is not the session's {mine:#010x}")
+        res = self.feed([p.payload for p in pk], idx, [p.timestamp for p in pk], score=score, _seqs=[p.seq for p in pk],
+                        encodings=[types[p.payload_type][1] for p in pk])
+        for s, v in ssrc.items():
+            self._b.ssrc[s] = v
+        return res
+
+    def _run(self, plan, pay):
+        l, S, Js, nr = lib(), self.S, self.Js, len(self._rates)
+        table, mode = C.cast(self._table, C.c_void_p), CONCEAL.index(self.conceal)
+
+        def place(d, off, op):
+            check(call_on(self.jring, l.afx_k_jitter_place_rates, _at(d, 0), d.numel(), _at(d, off), len(op[1]), op[2], table, nr,
+                          ptr(self.jring), S, Js))
+
+        def conceal(d, off, op):
+            check(call_on(self.jring, l.afx_k_jitter_conceal_rates, ptr(self.jring), S, Js, _at(d, off), len(op[1]), op[2], table, nr,
+                          mode))
+
+        def release(d, off, op):
+            rows = op[1]
+            most = np.zeros(nr, dtype=np.int32)  # per rate the largest n_out of this launch
+            np.maximum.at(most, rows[:, 7], rows[:, 3])
+            check(call_on(self.jring, l.afx_k_jitter_release_rates, ptr(self.jring), S, Js, _at(d, off), len(rows), table, nr,
+                          most.ctypes.data_as(C.c_void_p), ptr(self.ring), self.ring_len))
+
+        return self._execute(plan.ops, plan.slots, plan.counts, pay, {"place": place, "conceal": conceal, "release": release},
+                             lambda: self._commit(plan.book))
+
+    # ---- sessions --------------------------------------------------------------------------------------------------------
+    def reset(self, slots, rates=None):
+        """The named slots begin a new stream at ``rates``: one rate in Hz for all of them, or one per named slot; None keeps
+        each slot's rate.  A rate this scorer does not list is a ValueError before anything changes."""
+        idx = self.scorer._slot_list(slots, ordered=True)
+        new = None if rates is None else self._rate_indices(rates, len(idx))
+        super().reset(idx)
+        if idx and new is not None:
+            self._rate_of[idx] = new
+
+    def _meta(self):
+        return dict(resampler=FILTER_ID, jitter=JITTER_FORMAT, jitter_conceal=self.conceal, jitter_mixed=1)
+
+    def export_slots(self, slots):
+        """``JitterScorer.export_slots`` with ``jitter_ring`` (n, widest lookback + depth of this scorer's rates), zeros
+        beyond each session's own columns, the per-session ``jitter_rate`` ((n,) int64, Hz) and ``jitter_params`` ((n, 3)
+        int64: depth, period, fade in the session's own rate).  No byte of the scorer changes."""
+        idx = self.scorer._slot_list(slots, ordered=True)
+        st = self.scorer.export_slots(idx)
+        dev, b = self.device, self._b
+        ri = self._rate_of[idx]
+        lb, J = self._rlookback[ri], self._rJ[ri]
+        width = int((self._rlookback + self._rdepth).max())
+        with _on(dev):
+            nxt, held = torch.from_numpy(b.next[idx]), torch.from_numpy(b.hi[idx] - b.next[idx])
+            k = torch.arange(width)
+            cols = (nxt[:, None] - torch.from_numpy(lb)[:, None] + k) % torch.from_numpy(J)[:, None]
+            jr = self.jring[rows_on(idx, dev)[:, None], cols.to(dev)]
+            jr.masked_fill_((k[None, :] >= (torch.from_numpy(lb) + held)[:, None]).to(dev), 0.0)
+        ivs = [b.intervals(s) for s in idx]
+        K = max([len(v) for v in ivs] + [1])
+        table = np.full((len(idx), K, 2), -1, dtype=np.int64)
+        for i, v in enumerate(ivs):
+            if v:
+                table[i, :len(v)] = v
+        book = np.stack([getattr(b, f)[idx] for f in _BOOK], axis=1).reshape(len(idx), len(_BOOK))
+        stats = np.stack([getattr(b, f)[idx] for f in _COUNTERS], axis=1).reshape(len(idx), len(_COUNTERS))
+        params = np.stack([self._rdepth[ri], self._rP[ri], self._rF[ri]], axis=1).reshape(len(idx), 3)
+        return wrap(st, self._meta(), jitter_pending=export_pending(self.ring, idx, b.head[idx], b.fill[idx], self.max_pending * self.hop),
+                    jitter_fill=torch.from_numpy(b.fill[idx]), jitter_ring=jr, jitter_book=torch.from_numpy(book),
+                    jitter_stats=torch.from_numpy(stats), jitter_intervals=torch.from_numpy(table),
+                    jitter_rate=torch.from_numpy(self._rrate[ri]), jitter_params=torch.from_numpy(params))
+
+    def import_slots(self, slots, state):
+        """The named slots take over the sessions of ``state``, each at its own rate: a state of a MixedJitterScorer, or of a
+        plain ``JitterScorer`` (one ``input_rate`` in its meta) whose rate is listed here and whose depth, period, fade and
+        concealment mode are that rate's here.  A rate this scorer does not list, parameters that differ, ring columns that
+        are non-zero beyond a session's own, or anything ``JitterScorer.import_slots`` refuses is a ValueError before
+        anything changes."""
+        idx = self.scorer._slot_list(slots, ordered=True)
+        what = "jitter-buffer part (it was not exported by a JitterScorer or a MixedJitterScorer)"
+        n = len(state) if hasattr(state, "seen") else 0
+        if hasattr(state, "meta") and "jitter_mixed" not in state.meta and "input_rate" in state.meta:  # a plain JitterScorer's
+            rate = state.meta["input_rate"]
+            if rate not in self._rates:
+                raise ValueError(f"import_slots: a session at {rate} Hz, which is none of this scorer's rates {self._rates}")
+            r = self._rates.index(rate)
+            mine = dict(input_rate=rate, resampler=FILTER_ID, jitter=JITTER_FORMAT, jitter_depth=int(self._rdepth[r]),
+                        jitter_conceal=self.conceal, jitter_period=int(self._rP[r]), jitter_fade=int(self._rF[r]))
+            inner = peel(state, _STATE_KEYS, mine, what)
+            ri = np.full(n, r, dtype=np.int64)
+        else:
+            inner = peel(state, _STATE_KEYS + ("jitter_rate", "jitter_params"), self._meta(), what)
+            rates, params = state.tensors["jitter_rate"].cpu().reshape(-1), state.tensors["jitter_params"].cpu()
+            if rates.dtype != torch.int64 or rates.numel() != n or params.dtype != torch.int64 or tuple(params.shape) != (n, 3):
+                raise ValueError("import_slots: jitter_rate is (n,) int64, jitter_params (n, 3) int64")
+            missing = [r for r in rates.tolist() if r not in self._rates]
+            if missing:
+                raise ValueError(f"import_slots: a session at {missing[0]} Hz, which is none of this scorer's rates {self._rates}")
+            ri = np.array([self._rates.index(r) for r in rates.tolist()], dtype=np.int64)
+            here = np.stack([self._rdepth[ri], self._rP[ri], self._rF[ri]], axis=1).reshape(n, 3)
+            bad = np.flatnonzero((params.numpy() != here).any(axis=1))
+            if bad.size:
+                raise ValueError(f"import_slots: session {bad[0]} has depth, period, fade {params[bad[0]].tolist()}, this scorer's at "
+                                 f"{rates[bad[0]]} Hz are {here[bad[0]].tolist()}")
+        if len(idx) != n:
+            raise ValueError(f"the state holds {n} sessions for {len(idx)} named slots")
+        jr = state.tensors["jitter_ring"]
+        own = self._rlookback[ri] + self._rdepth[ri]
+        if jr.ndim != 2 or jr.shape[0] != n or jr.dtype != torch.float32 or (n and jr.shape[1] < own.max()):
+            raise ValueError(f"import_slots: jitter_ring {tuple(jr.shape)} {jr.dtype} does not hold its sessions' columns "
+                             f"((n, >= {int(own.max()) if n else 0}) float32)")
+        if n and jr.shape[1] and bool((jr.cpu() * (torch.arange(jr.shape[1])[None, :] >= torch.from_numpy(own)[:, None])).ne(0).any()):
+            raise ValueError("import_slots: jitter_ring has non-zero columns beyond a session's own lookback + depth")
+        self._install(idx, inner, self._check_sessions(state, n, ri))
+        if idx:
+            self._rate_of[idx] = ri

@@ -2833,6 +2833,21 @@ extern "C" int afx_k_jitter_release(const float* jring, int S, int J, const int*
                                     int L, int M, int T, float* ring, int ring_len, void* stream) {
   KRET(launch_jitter_release(jring, S, J, hdr, rows, max_out, taps, L, M, T, ring, ring_len, (hipStream_t)stream));
 }
+extern "C" int afx_k_jitter_place_rates(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n,
+                                        const afx_jitter_rate* rates, int n_rates, float* jring, int S, int Js, void* stream) {
+  static_assert(sizeof(afx_jitter_rate) == sizeof(JitterRateDesc), "afx_jitter_rate is JitterRateDesc");
+  KRET(launch_jitter_place_rates(stage, stage_bytes, hdr, rows, max_n, (const JitterRateDesc*)rates, n_rates, jring, S, Js,
+                                 (hipStream_t)stream));
+}
+extern "C" int afx_k_jitter_conceal_rates(float* jring, int S, int Js, const int* hdr, int rows, int max_n,
+                                          const afx_jitter_rate* rates, int n_rates, int mode, void* stream) {
+  KRET(launch_jitter_conceal_rates(jring, S, Js, hdr, rows, max_n, (const JitterRateDesc*)rates, n_rates, mode, (hipStream_t)stream));
+}
+extern "C" int afx_k_jitter_release_rates(const float* jring, int S, int Js, const int* hdr, int rows, const afx_jitter_rate* rates,
+                                          int n_rates, const int* max_out, float* ring, int ring_len, void* stream) {
+  KRET(launch_jitter_release_rates(jring, S, Js, hdr, rows, (const JitterRateDesc*)rates, n_rates, max_out, ring, ring_len,
+                                   (hipStream_t)stream));
+}
 extern "C" int afx_k_gate(const float* x, int A, int n, const int* hdr, int frame, float e_floor, float ratio, float rise,
                           int hang, float* nf, int* h, float* ring, int S, int ring_len, int* kept, unsigned char* mask,
                           void* stream) {

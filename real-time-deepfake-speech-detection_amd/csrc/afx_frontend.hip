@@ -1102,9 +1102,10 @@ constexpr int JIT_PLACE_MIXED_HDR = 5;  // the same four, then the row's encodin
 constexpr int JIT_CONCEAL_HDR = 4;  // ints per row: slot, ring column of the gap origin a, d_lo, d_hi
 constexpr int JIT_RELEASE_HDR = 8;  // ints per row: slot, ring column of a0, n_in, n_out, p0, d0, wpos, 0
 
-// one row of a place launch: h[0..3] = slot, byte offset, n, column; enc the row's encoding (validated by the caller)
+// one row of a place launch: h[0..3] = slot, byte offset, n, column; enc the row's encoding (validated by the caller); the
+// slot's ring is the first J columns of a row of `stride` floats (stride = J but for a scorer of several rates)
 __device__ __forceinline__ void jitter_place_row(const unsigned char* __restrict__ stage, long long stage_bytes, const int* h, int enc,
-                                                 float* __restrict__ jring, int S, int J) {
+                                                 float* __restrict__ jring, int S, int J, int stride) {
   const int slot = h[0], n = h[2], col = h[3];
   const long long off = h[1];
   const int bps = ingest_bytes_per_sample(enc);
@@ -1112,7 +1113,7 @@ __device__ __forceinline__ void jitter_place_row(const unsigned char* __restrict
         off + (long long)n * bps <= stage_bytes))
     return;
   const unsigned char* pay = stage + off;
-  float* row = jring + (long long)slot * J;
+  float* row = jring + (long long)slot * stride;
   for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += gridDim.x * blockDim.x) {
     const int w = col + k;
     row[w < J ? w : w - J] = ingest_sample(pay, k, enc);
@@ -1122,7 +1123,7 @@ __device__ __forceinline__ void jitter_place_row(const unsigned char* __restrict
 __global__ __launch_bounds__(256) void jitter_place_kernel(const unsigned char* __restrict__ stage, long long stage_bytes,
                                                            const int* __restrict__ hdr, int enc, float* __restrict__ jring,
                                                            int S, int J) {
-  jitter_place_row(stage, stage_bytes, hdr + (long long)blockIdx.y * JIT_PLACE_HDR, enc, jring, S, J);
+  jitter_place_row(stage, stage_bytes, hdr + (long long)blockIdx.y * JIT_PLACE_HDR, enc, jring, S, J, J);
 }
 
 // the same with the encoding read per row (the fifth int of a JIT_PLACE_MIXED_HDR row); a row with a bad one is skipped whole
@@ -1132,7 +1133,7 @@ __global__ __launch_bounds__(256) void jitter_place_mixed_kernel(const unsigned 
   const int* h = hdr + (long long)blockIdx.y * JIT_PLACE_MIXED_HDR;
   const int enc = h[4];
   if (enc < 0 || enc > 3) return;
-  jitter_place_row(stage, stage_bytes, h, enc, jring, S, J);
+  jitter_place_row(stage, stage_bytes, h, enc, jring, S, J, J);
 }
 
 const char* launch_jitter_place(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n, int enc,
@@ -1161,13 +1162,13 @@ const char* launch_jitter_place_mixed(const void* stage, long long stage_bytes, 
 }
 
 // E[a + d] for d in [d_lo, d_hi): 0 (mode 0, or d >= F), else fade[d] * E[a - P + d mod P] (one fp32 multiply of two stored
-// values).  The source columns [a - P, a) and the written ones [a + d_lo, a + d_hi) are disjoint for d_hi + P <= J.
-__global__ __launch_bounds__(256) void jitter_conceal_kernel(float* __restrict__ jring, int S, int J, const int* __restrict__ hdr,
-                                                             const float* __restrict__ fade, int P, int F, int mode) {
-  const int* h = hdr + (long long)blockIdx.y * JIT_CONCEAL_HDR;
+// values).  The source columns [a - P, a) and the written ones [a + d_lo, a + d_hi) are disjoint for d_hi + P <= J.  One row of
+// a conceal launch: h[0..3] = slot, column of a, d_lo, d_hi; the slot's ring is the first J columns of a row of `stride` floats.
+__device__ __forceinline__ void jitter_conceal_row(float* __restrict__ jring, int S, int J, int stride, const int* h,
+                                                   const float* __restrict__ fade, int P, int F, int mode) {
   const int slot = h[0], ac = h[1], lo = h[2], hi = h[3];
   if (!(slot >= 0 && slot < S && ac >= 0 && ac < J && lo >= 0 && hi >= lo && (long long)hi + P <= J)) return;
-  float* row = jring + (long long)slot * J;
+  float* row = jring + (long long)slot * stride;
   const int src0 = ac >= P ? ac - P : ac - P + J;
   for (int d = lo + blockIdx.x * blockDim.x + threadIdx.x; d < hi; d += gridDim.x * blockDim.x) {
     float v = 0.f;
@@ -1178,6 +1179,11 @@ __global__ __launch_bounds__(256) void jitter_conceal_kernel(float* __restrict__
     const int w = ac + d;  // < 2 J
     row[w < J ? w : w - J] = v;
   }
+}
+
+__global__ __launch_bounds__(256) void jitter_conceal_kernel(float* __restrict__ jring, int S, int J, const int* __restrict__ hdr,
+                                                             const float* __restrict__ fade, int P, int F, int mode) {
+  jitter_conceal_row(jring, S, J, J, hdr + (long long)blockIdx.y * JIT_CONCEAL_HDR, fade, P, F, mode);
 }
 
 const char* launch_jitter_conceal(float* jring, int S, int J, const int* hdr, int rows, int max_n, const float* fade, int P,
@@ -1256,6 +1262,178 @@ const char* launch_jitter_release(const float* jring, int S, int J, const int* h
   if (ident) hipLaunchKernelGGL((jitter_release_kernel<true, false>), grid, dim3(256), g.lds, s, a);
   else if (g.lds_taps) hipLaunchKernelGGL((jitter_release_kernel<false, true>), grid, dim3(256), g.lds, s, a);
   else hipLaunchKernelGGL((jitter_release_kernel<false, false>), grid, dim3(256), g.lds, s, a);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+// ---------------------------------------------------------------------------------
+// Jitter buffer over slots of different clock rates (afx/jitter.py MixedJitterScorer; include/afx.h afx_k_jitter_place_rates /
+// _conceal_rates / _release_rates): the rate (taps, L, M, T, its ring length J, repeat period P, fade length F and fade table)
+// is a per-row value, the last int of the row's header, instead of a launch-wide one.  jring is (S, Js), Js >= every rate's J:
+// a slot at rate f uses the first J_f columns of its row with modulus J_f and never a column at or beyond J_f.  The table of a
+// scorer's rates (at most JIT_MAX_RATES) travels by value in the argument struct; a workgroup reads its row's entry (the index
+// made wave-uniform, so the entry is scalar loads from the kernel arguments) and runs jitter_place_row / jitter_conceal_row /
+// jitter_release_row with that rate's values: the same validation, decoder, multiply and tile body, so every value is
+// the one a one-rate launch gives it.  The branch on the tap placement is uniform per workgroup.
+// ---------------------------------------------------------------------------------
+constexpr int JIT_MAX_RATES = 16;
+constexpr int JIT_PLACE_RATES_HDR = 6;    // a JIT_PLACE_MIXED_HDR row, then the row's rate index
+constexpr int JIT_CONCEAL_RATES_HDR = 5;  // a JIT_CONCEAL_HDR row, then the row's rate index
+                                          // (a release row is JIT_RELEASE_HDR ints: its eighth is the rate index)
+
+struct JitterRate {
+  PolyFilter f;                  // Tp, R from poly_grid (release only)
+  const float* fade;             // (max(F, 1),) fp32 (conceal only)
+  int J, P, F, lds_taps;
+  int max_out;                   // release: the largest n_out the launch was shaped for (a row beyond it writes nothing)
+};
+
+struct JitterRatesArgs {
+  const unsigned char* stage;    // place
+  long long stage_bytes;
+  const int* hdr;
+  float* jring;                  // (S, Js)
+  float* ring;                   // release: (S, ring_len)
+  int S, Js, ring_len, nr, mode;
+  JitterRate r[JIT_MAX_RATES];
+};
+
+__global__ __launch_bounds__(256) void jitter_place_rates_kernel(JitterRatesArgs m) {
+  const int* h = m.hdr + (long long)blockIdx.y * JIT_PLACE_RATES_HDR;
+  const int enc = h[4], ri = __builtin_amdgcn_readfirstlane(h[5]);
+  if (enc < 0 || enc > 3 || ri < 0 || ri >= m.nr) return;
+  jitter_place_row(m.stage, m.stage_bytes, h, enc, m.jring, m.S, m.r[ri].J, m.Js);
+}
+
+__global__ __launch_bounds__(256) void jitter_conceal_rates_kernel(JitterRatesArgs m) {
+  const int* h = m.hdr + (long long)blockIdx.y * JIT_CONCEAL_RATES_HDR;
+  const int ri = __builtin_amdgcn_readfirstlane(h[4]);
+  if (ri < 0 || ri >= m.nr) return;
+  jitter_conceal_row(m.jring, m.S, m.r[ri].J, m.Js, h, m.r[ri].fade, m.r[ri].P, m.r[ri].F, m.mode);
+}
+
+// jitter_release_kernel's row with the ring's row stride apart from its modulus: the same checks against a.J (the row's
+// J_f), the same copy, the same call of polyphase_tiles.  (The one-rate kernel keeps its own text: routed through this function
+// the compiler allocates its registers differently, and its instructions are to stay as they were.)
+template <bool IDENT, bool LDS_TAPS>
+__device__ __forceinline__ void jitter_release_row(const JitterReleaseArgs& a, const int* h, int stride) {
+  const int slot = h[0], col0 = h[1], n_in = h[2], n_out = h[3], p0 = h[4], d0 = h[5], wpos = h[6];
+  if (!(slot >= 0 && slot < a.S && col0 >= 0 && col0 < a.J && n_in >= 0 && n_in <= a.J && n_out >= 0 && n_out <= a.ring_len &&
+        wpos >= 0 && wpos < a.ring_len && p0 >= 0 && p0 < a.f.L && d0 >= 0))
+    return;
+  const float* src = a.jring + (long long)slot * stride;
+  float* out = a.ring + (long long)slot * a.ring_len;
+  if (IDENT) {
+    for (int r = 0; r < a.f.R; ++r) {
+      const int k = (blockIdx.x * a.f.R + r) * RS_TILE + threadIdx.x;
+      if (k >= n_out || k >= n_in) break;
+      const int c = col0 + k, w = wpos + k;
+      out[w < a.ring_len ? w : w - a.ring_len] = src[c < a.J ? c : c - a.J];
+    }
+    return;
+  }
+  if ((long long)blockIdx.x * a.f.R * RS_TILE >= n_out) return;  // (beyond the row's outputs: nothing is staged)
+  polyphase_tiles<LDS_TAPS>(a.f, n_out, p0, d0, RingSource{src, col0, a.J, n_in}, RingSink{out, wpos, a.ring_len});
+}
+
+__global__ __launch_bounds__(256) void jitter_release_rates_kernel(JitterRatesArgs m) {
+  const int* h = m.hdr + (long long)blockIdx.y * JIT_RELEASE_HDR;
+  const int ri = __builtin_amdgcn_readfirstlane(h[7]);
+  if (ri < 0 || ri >= m.nr || h[3] > m.r[ri].max_out) return;
+  JitterReleaseArgs a;
+  a.jring = m.jring; a.hdr = m.hdr; a.f = m.r[ri].f; a.ring = m.ring; a.J = m.r[ri].J; a.S = m.S; a.ring_len = m.ring_len;
+  if (!a.f.taps) jitter_release_row<true, false>(a, h, m.Js);
+  else if (m.r[ri].lds_taps) jitter_release_row<false, true>(a, h, m.Js);
+  else jitter_release_row<false, false>(a, h, m.Js);
+}
+
+static const char* jitter_rates_msg(const char* who, const char* what) {
+  static thread_local char msg[160];
+  snprintf(msg, sizeof msg, "%s: %s", who, what);
+  return msg;
+}
+
+// the rate table of a launch as the kernels take it, or the refusal; mode < 0: a launch that does not conceal.  max_out
+// (release only): the per-rate largest n_out, whose grids go to g
+static const char* jitter_rates_table(const char* who, const JitterRateDesc* rates, int n_rates, int Js, int mode, const int* max_out,
+                                      JitterRatesArgs& m, PolyGrid* g) {
+  if (n_rates < 1 || n_rates > JIT_MAX_RATES) return jitter_rates_msg(who, "1 to 16 rates");
+  if (!rates) return jitter_rates_msg(who, "null rate table");
+  if (Js <= 0) return jitter_rates_msg(who, "a rate's ring must fit the ring's rows (1 <= J <= Js)");
+  for (int i = 0; i < n_rates; ++i) {
+    const JitterRateDesc& d = rates[i];
+    if (d.L <= 0 || d.M <= 0 || d.T <= 0) return jitter_rates_msg(who, "bad filter shape");
+    const bool ident = d.taps == nullptr;
+    if (ident && (d.L != 1 || d.M != 1 || d.T != 1)) return jitter_rates_msg(who, "bad filter shape (no taps is the identity, L = M = T = 1)");
+    if (d.J <= 0 || d.J > Js) return jitter_rates_msg(who, "a rate's ring must fit the ring's rows (1 <= J <= Js)");
+    if (d.T - 1 > d.J) return jitter_rates_msg(who, "the filter history must fit the rate's ring");
+    if (mode == 1 && (!d.fade || d.P <= 0 || d.F < 0)) return jitter_rates_msg(who, "repeat needs a fade table, a period and a fade length");
+    JitterRate& r = m.r[i];
+    r.f = PolyFilter{d.taps, d.L, d.M, d.T, 0, 0};
+    r.fade = d.fade; r.J = d.J; r.P = mode == 1 ? d.P : 0; r.F = mode == 1 ? d.F : 0; r.lds_taps = 0;
+    PolyGrid pg;
+    if (!poly_grid(r.f, ident, max_out && max_out[i] > 0 ? max_out[i] : 0, pg)) return jitter_rates_msg(who, "input / output ratio above 12");
+    r.lds_taps = pg.lds_taps;
+    r.max_out = max_out && max_out[i] > 0 ? max_out[i] : 0;
+    if (g) g[i] = pg;
+  }
+  m.nr = n_rates; m.Js = Js; m.mode = mode;
+  return nullptr;
+}
+
+const char* launch_jitter_place_rates(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n,
+                                      const JitterRateDesc* rates, int n_rates, float* jring, int S, int Js, hipStream_t s) {
+  const char* who = "jitter_place_rates";
+  JitterRatesArgs m{};
+  if (const char* e = jitter_rates_table(who, rates, n_rates, Js, -1, nullptr, m, nullptr)) return e;
+  if (!stage || !hdr || !jring || stage_bytes <= 0) return jitter_rates_msg(who, "null staging buffer, header table or ring");
+  if (rows <= 0 || rows > 65535) return jitter_rates_msg(who, "1 to 65535 rows");
+  if (S <= 0 || max_n < 0 || max_n > Js) return jitter_rates_msg(who, "a row's samples must fit its slot's ring");
+  if (max_n == 0) return nullptr;
+  m.stage = (const unsigned char*)stage; m.stage_bytes = stage_bytes; m.hdr = hdr; m.jring = jring; m.S = S;
+  hipLaunchKernelGGL(jitter_place_rates_kernel, dim3(min((max_n + 255) / 256, 64), rows), dim3(256), 0, s, m);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+const char* launch_jitter_conceal_rates(float* jring, int S, int Js, const int* hdr, int rows, int max_n, const JitterRateDesc* rates,
+                                        int n_rates, int mode, hipStream_t s) {
+  const char* who = "jitter_conceal_rates";
+  if (mode != 0 && mode != 1) return jitter_rates_msg(who, "mode 0 (zero) or 1 (repeat)");
+  JitterRatesArgs m{};
+  if (const char* e = jitter_rates_table(who, rates, n_rates, Js, mode, nullptr, m, nullptr)) return e;
+  if (!jring || !hdr) return jitter_rates_msg(who, "null ring or header table");
+  if (rows <= 0 || rows > 65535) return jitter_rates_msg(who, "1 to 65535 rows");
+  if (S <= 0 || max_n < 0 || max_n > Js) return jitter_rates_msg(who, "a row's samples and its source must fit the ring");
+  if (max_n == 0) return nullptr;
+  m.hdr = hdr; m.jring = jring; m.S = S;
+  hipLaunchKernelGGL(jitter_conceal_rates_kernel, dim3(min((max_n + 255) / 256, 64), rows), dim3(256), 0, s, m);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+const char* launch_jitter_release_rates(const float* jring, int S, int Js, const int* hdr, int rows, const JitterRateDesc* rates,
+                                        int n_rates, const int* max_out, float* ring, int ring_len, hipStream_t s) {
+  const char* who = "jitter_release_rates";
+  JitterRatesArgs m{};
+  PolyGrid g[JIT_MAX_RATES];
+  if (!max_out) return jitter_rates_msg(who, "null output counts");
+  if (const char* e = jitter_rates_table(who, rates, n_rates, Js, -1, max_out, m, g)) return e;
+  if (!jring || !hdr || !ring) return jitter_rates_msg(who, "null ring or header table");
+  if (rows <= 0 || rows > 65535) return jitter_rates_msg(who, "1 to 65535 rows");
+  if (S <= 0 || ring_len <= 0) return jitter_rates_msg(who, "a row's outputs must fit its slot's ring");
+  long long gx = 0;
+  size_t lds = 0;
+  for (int i = 0; i < n_rates; ++i) {
+    if (max_out[i] < 0 || max_out[i] > ring_len) return jitter_rates_msg(who, "a row's outputs must fit its slot's ring");
+    if (max_out[i] > 0) {
+      gx = g[i].gx > gx ? g[i].gx : gx;
+      lds = g[i].lds > lds ? g[i].lds : lds;
+    }
+  }
+  if (gx == 0) return nullptr;
+  m.hdr = hdr; m.jring = const_cast<float*>(jring); m.ring = ring; m.S = S; m.ring_len = ring_len;
+  hipLaunchKernelGGL(jitter_release_rates_kernel, dim3((unsigned)gx, rows), dim3(256), lds, s, m);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? nullptr : hipGetErrorString(e);
 }

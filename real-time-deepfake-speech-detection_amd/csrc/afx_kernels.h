@@ -188,6 +188,16 @@ const char* launch_jitter_conceal(float* jring, int S, int J, const int* hdr, in
                                   int F, int mode, hipStream_t s);
 const char* launch_jitter_release(const float* jring, int S, int J, const int* hdr, int rows, int max_out, const float* taps,
                                   int L, int M, int T, float* ring, int ring_len, hipStream_t s);
+// the same three over slots of different clock rates (include/afx.h afx_k_jitter_place_rates / _conceal_rates / _release_rates):
+// rates / max_out are HOST arrays of n_rates entries (JitterRateDesc has the layout of afx_jitter_rate), a row's rate index is
+// the last int of its header (place: rows x 6, conceal: rows x 5, release: the eighth of 8), jring is (S, Js), Js >= every J
+struct JitterRateDesc { const float* taps; const float* fade; int L, M, T, J, P, F; };
+const char* launch_jitter_place_rates(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n,
+                                      const JitterRateDesc* rates, int n_rates, float* jring, int S, int Js, hipStream_t s);
+const char* launch_jitter_conceal_rates(float* jring, int S, int Js, const int* hdr, int rows, int max_n, const JitterRateDesc* rates,
+                                        int n_rates, int mode, hipStream_t s);
+const char* launch_jitter_release_rates(const float* jring, int S, int Js, const int* hdr, int rows, const JitterRateDesc* rates,
+                                        int n_rates, const int* max_out, float* ring, int ring_len, hipStream_t s);
 // speech gate (include/afx.h afx_k_gate): per-slot energy gate with noise-floor tracking and hangover over the frames of each
 // row; the kept frames are compacted into the slot's pending ring, kept[i] = the samples kept of row i,
 // mask (optional) the keep flag of every frame

@@ -1,0 +1,516 @@
+"""Every slot its own clock rate in one jitter buffer, on the GPU (afx/jitter.py MixedJitterScorer, afx_k_jitter_place_rates /
+_conceal_rates / _release_rates).  The references are what this change leaves alone: the numpy restatement of the played-out
+stream E with the offline ``Resampler`` over it (and float64 upfirdn), and the one-rate ``JitterScorer`` fed a slot's own
+packets in the same calls.  Every comparison is exact but the float64 one, whose bound is tests/test_gpu_jitter.py's."""
+import random
+import struct
+
+import numpy as np
+import pytest
+import torch
+from scipy import signal
+
+pytestmark = pytest.mark.gpu
+
+H = 4000
+BPS = {"pcm_f32le": 4, "pcm_s16le": 2, "mulaw": 1, "alaw": 1}
+FORMATS = [(8000, "mulaw"), (8000, "alaw"), (11025, "pcm_s16le"), (16000, "pcm_f32le"), (48000, "pcm_s16le")]
+ENC_AT = {8000: ("mulaw", "alaw"), 11025: ("pcm_s16le",), 16000: ("pcm_f32le",), 48000: ("pcm_s16le",)}
+DEPTH_MS = 60
+
+
+def _mulaw_table():
+    t = []
+    for c in range(256):
+        u = ~c & 0xFF
+        v = ((((u & 15) << 3) + 132) << ((u >> 4) & 7)) - 132
+        t.append(-v if u & 0x80 else v)
+    return np.array(t, dtype=np.float32)
+
+
+def _alaw_table():
+    t = []
+    for c in range(256):
+        a = c ^ 0x55
+        e, m = (a >> 4) & 7, a & 15
+        v = ((m << 4) + 264) << (e - 1) if e else (m << 4) + 8
+        t.append(v if a & 0x80 else -v)
+    return np.array(t, dtype=np.float32)
+
+
+TABLES = {"mulaw": _mulaw_table(), "alaw": _alaw_table()}
+
+
+def _packet(encoding, n, g, quiet=False):
+    """n random samples as ``encoding`` -> (the bytes, their host-decoded fp32 values)."""
+    if encoding == "pcm_f32le":
+        x = (0.1 * g.standard_normal(n)).astype("<f4")
+        return x.tobytes(), x.astype(np.float32)
+    if encoding == "pcm_s16le":
+        v = (g.integers(-32768, 32768, n) // 8).astype("<i2")
+        return v.tobytes(), v.astype(np.float32) / np.float32(32768)
+    c = (g.integers(96, 160, n) if quiet else g.integers(0, 256, n)).astype(np.uint8)
+    return c.tobytes(), TABLES[encoding][c] / np.float32(32768)
+
+
+def _sizing(rate, mode, hop=H):
+    """(depth, P, F, lookback, W, J) of a rate as the issue states them, from the Resampler's L, M, T alone."""
+    from afx.resample import Resampler
+    rs = Resampler(rate)
+    depth = DEPTH_MS * rate // 1000
+    P, F = (rate // 100, 3 * (rate // 100)) if mode == "repeat" else (0, 0)
+    lookback = max(0 if rs.identity else rs.T - 1, P + F)
+    W = depth + -(-hop * rs.M // rs.L) + 1
+    return depth, P, F, lookback, W, lookback + W
+
+
+# ---- the reference: one slot's played-out stream (tests/test_gpu_jitter.py's, restated) ----------------------------------------
+class Ref:
+    def __init__(self, depth, mode, P, F, cap):
+        self.depth, self.mode, self.P, self.F = depth, mode, P, F
+        self.fade = (1.0 - np.arange(max(F, 1), dtype=np.float64) / max(F, 1)).astype(np.float32)
+        self.val, self.have, self.E = np.zeros(cap, np.float32), np.zeros(cap, bool), np.zeros(cap, np.float32)
+        self.next = self.hi = 0
+        self.gap = None  # the origin of the gap the playout point stands in
+        self.late = self.dup = self.received = self.concealed = 0
+        self.releases = []  # the gaps of every release
+        self.spans = []  # every gap of E as [origin, end), pieces of one gap released by several calls joined
+
+    def packet(self, t, x):
+        n = len(x)
+        lo = min(max(t, self.next), t + n)
+        self.late += lo - t
+        if lo < t + n:
+            new = ~self.have[lo:t + n]
+            self.val[lo:t + n][new] = x[lo - t:][new]
+            self.have[lo:t + n] = True
+            self.dup += int((~new).sum())
+            self.received += int(new.sum())
+            self.hi = max(self.hi, t + n)
+
+    def release(self, upto):
+        i, gaps = self.next, []
+        while i < upto:
+            run = self.have[i:upto]
+            flips = np.flatnonzero(run != run[0])
+            j = i + int(flips[0]) if flips.size else upto
+            if run[0]:
+                self.E[i:j], self.gap = self.val[i:j], None
+            else:
+                a = self.gap = i if self.gap is None else self.gap
+                d = np.arange(i - a, j - a)
+                v = np.zeros(j - i, np.float32)
+                if self.mode == "repeat":
+                    m = d < self.F
+                    src = a - self.P + d[m] % self.P
+                    v[m] = self.fade[d[m]] * np.where(src >= 0, self.E[np.maximum(src, 0)], np.float32(0))
+                self.E[i:j] = v
+                self.concealed += j - i
+                gaps.append((i, j))
+                if self.spans and self.spans[-1][0] == a:
+                    self.spans[-1][1] = j
+                else:
+                    self.spans.append([a, j])
+            i = j
+        if upto > self.next:
+            self.releases.append(gaps)
+            self.next = upto
+        self.hi = max(self.hi, self.next)
+
+    def after_feed(self):
+        self.release(max(self.next, self.hi - self.depth))
+
+
+class Schedule:
+    """One slot's traffic (tests/test_gpu_jitter.py's, restated, with packet k in encodings[k % len(encodings)]): 20-ms packets
+    (one short one), a forward jump, losses, duplicates and shuffles within the depth, grouped into ticks (the packets one
+    ``feed`` delivers).  ``lossy``: drop 5 % at random and the forced gaps."""
+
+    def __init__(self, rate, encodings, seed, jump=0, P=0, lossy=True, n_pk=72, origin=None, depth_pk=3, quiet=False):
+        rng = random.Random(seed)
+        g = np.random.default_rng(seed)
+        n = rate // 50
+        sizes = [n] * n_pk
+        sizes[11] = max(1, P // 2) if lossy else n  # between two lost packets: two gaps closer than P
+        offs = np.concatenate([[0], np.cumsum(sizes)]).tolist()
+        self.enc = [encodings[k % len(encodings)] for k in range(n_pk)]
+        self.pk = [_packet(self.enc[k], sizes[k], g, quiet) for k in range(n_pk)]
+        self.origin = rng.randrange(1 << 32) if origin is None else origin
+        self.start = [offs[k] + (jump if k >= 44 else 0) for k in range(n_pk)]  # packet 44 begins `jump` samples late
+        self.size, self.cap = sizes, offs[-1] + jump + 8
+        forced = {10, 12, 25, 26, 27, 28} if lossy else set()  # 25..28: 80 ms > F + P
+        calm = set(range(6, 34)) if lossy else set()  # delivered in order around the forced gaps
+        self.lost = set(forced)
+        ticks, k = [], 0
+        while k < n_pk:
+            if lossy and k == 11:  # the short packet and four more in one feed: both gaps fall in its release
+                ticks.append([11, 13, 14, 15, 16])
+                k = 17
+                continue
+            if k in calm:
+                if k not in forced:
+                    ticks.append([k])
+                k += 1
+                continue
+            blk = [q for q in range(k, min(k + depth_pk, n_pk)) if q not in calm]
+            k = blk[-1] + 1
+            if lossy:
+                for q in list(blk):
+                    if q and rng.random() < 0.05:
+                        blk.remove(q)
+                        self.lost.add(q)
+            blk += [q for q in blk if rng.random() < 0.15]  # duplicates
+            rng.shuffle(blk)  # within depth_pk packets = the depth: every packet is on time
+            if 0 in blk:  # the first packet accepted is the session's origin: index 0 here
+                blk.remove(0)
+                blk.insert(0, 0)
+            while blk:
+                m = rng.randint(1, 3)
+                ticks.append(blk[:m])
+                blk = blk[m:]
+        self.ticks, self.at = ticks, 0
+
+    def done(self):
+        return self.at >= len(self.ticks)
+
+    def tick(self):
+        """-> [(timestamp, relative index, bytes, decoded, encoding)] of the next tick."""
+        ks = self.ticks[self.at]
+        self.at += 1
+        return [((self.origin + self.start[k]) % (1 << 32), self.start[k], self.pk[k][0], self.pk[k][1], self.enc[k]) for k in ks]
+
+
+def _tap(S):
+    from afx.streaming import SlidingWindowScorer
+
+    class Tap(SlidingWindowScorer):
+        def __init__(self):
+            super().__init__(None, S, window=4 * H, hop=H, device="cuda")
+            self.got = [[] for _ in range(S)]
+
+        def push(self, chunk, slots=None):
+            idx = self._slot_list(slots, ordered=True)
+            assert chunk.is_cuda and chunk.dtype == torch.float32 and chunk.shape == (len(idx), H)
+            for i, s in enumerate(idx):
+                self.got[s].append(chunk[i].clone())
+            self._seen[idx] += H
+            return torch.zeros(len(idx), device=chunk.device)
+
+    return Tap()
+
+
+def _ref64(x, rate):
+    from afx.resample import design_filter
+    L, M, h = design_filter(rate)
+    if L == M:
+        return np.asarray(x, dtype=np.float64)
+    return signal.upfirdn(h, np.asarray(x, dtype=np.float64), L, M)[: -(-len(x) * L // M)]
+
+
+def _offline(E, rate):
+    from afx.resample import Resampler
+    return Resampler(rate)(torch.from_numpy(np.ascontiguousarray(E)).cuda()[None])[0]
+
+
+def _rows_of(ticks, rng):
+    """{slot: its tick} -> the rows of one feed: the slots' rows interleaved, each slot's own rows in their order of arrival."""
+    order = [s for s, r in ticks.items() for _ in r]
+    rng.shuffle(order)
+    its = {s: iter(r) for s, r in ticks.items()}
+    return [(s,) + next(its[s]) for s in order]
+
+
+SLOT_RATES = [8000, 8000, 11025, 16000, 48000, 11025]  # slot 0 alternates mu-law and A-law per packet
+
+
+@pytest.mark.parametrize("mode", ["repeat", "zero"])
+def test_played_out_stream_of_every_rate_is_the_offline_resampling_of_the_numpy_stream(mode):
+    from afx.jitter import MixedJitterScorer
+    from afx.resample import Resampler
+    S = 6
+    tap = _tap(S)
+    ms = MixedJitterScorer(tap, FORMATS, DEPTH_MS, conceal=mode, max_pending=3)
+    ms.reset(list(range(S)), SLOT_RATES)
+    # the tap placements this test is about: LDS taps, taps from global memory, the identity, M / L = 3
+    shape = {r: Resampler(r) for r in set(SLOT_RATES)}
+    assert shape[8000].L * (shape[8000].T | 1) <= 12288 < shape[11025].L * (shape[11025].T | 1) and shape[16000].identity
+    assert (shape[48000].L, shape[48000].M) == (1, 3)
+    geo = [_sizing(r, mode) for r in SLOT_RATES]
+    depth, P, F, J = ([g[i] for g in geo] for i in (0, 1, 2, 5))
+    assert (ms.rates.tolist(), ms.depths.tolist(), ms.periods.tolist(), ms.fades.tolist()) == (SLOT_RATES, depth, P, F)
+    assert ms.Js == max(J) and tuple(ms.jring.shape) == (S, ms.Js) and len(set(J)) == 4
+    # columns at and beyond a slot's own J: a NaN pattern that must come through the run bit for bit
+    sentinel = torch.full((S, ms.Js), float("nan"), device="cuda").view(torch.int32) + torch.arange(ms.Js, device="cuda", dtype=torch.int32)
+    for s in range(S):
+        ms.jring[s, J[s]:] = sentinel.view(torch.float32)[s, J[s]:]
+    assert torch.isnan(ms.jring[0, J[0]:]).all() and not ms.jring[:, :min(J)].any()
+    seed = 77 + (7 if mode == "zero" else 0)
+    rng = random.Random(seed)
+    Pn = [r // 100 for r in SLOT_RATES]  # the traffic is made for the 10-ms period and its 30-ms fade in either mode
+    Fn = [3 * p for p in Pn]
+    sch = [Schedule(r, ENC_AT[r] if s == 0 or r != 8000 else ("alaw",), seed + 1000 * s, jump=J[s] + 123 + s, P=Pn[s],
+                    origin=(1 << 32) - 3000 if s in (0, 4) else None) for s, r in enumerate(SLOT_RATES)]
+    assert set(sch[0].enc) == {"mulaw", "alaw"}
+    refs = [Ref(depth[s], mode, P[s], F[s], sc.cap) for s, sc in enumerate(sch)]
+    L, M = [shape[r].L for r in SLOT_RATES], [shape[r].M for r in SLOT_RATES]
+    hops = [0] * S
+    while not all(sc.done() for sc in sch):
+        ticks = {s: sch[s].tick() for s in range(S) if not sch[s].done() and rng.random() < 0.8}
+        if not ticks:
+            continue
+        rows = _rows_of(ticks, rng)
+        named = []
+        for s, ts, t, raw, x, e in rows:
+            refs[s].packet(t, x)
+            named += [s] if s not in named else []
+        for s in named:
+            refs[s].after_feed()
+        made = {s: -(-refs[s].next * L[s] // M[s]) for s in named}
+        score = rng.random() < 0.6 or any(made[s] - hops[s] * H > 3 * H for s in named)
+        res = ms.feed([r[3] for r in rows], [r[0] for r in rows], [r[1] for r in rows], score=score, encodings=[r[5] for r in rows])
+        assert res.counts.shape == (len(rows),) and res.scores.shape == (int(res.counts.sum()),)
+        for s in named:
+            if score:  # every hop whose last input sample has been released is out, in this call
+                assert len(tap.got[s]) == made[s] // H and int(ms.pending[s]) == made[s] % H
+            assert int(ms.pending[s]) + H * len(tap.got[s]) == made[s] and int(ms.samples_in[s]) == refs[s].next
+            assert int(ms.buffered[s]) == refs[s].hi - refs[s].next <= depth[s]
+            hops[s] = len(tap.got[s])
+    ms.flush()
+    st = ms.stats()
+    for s, rate in enumerate(SLOT_RATES):
+        r = refs[s]
+        r.release(r.hi)
+        assert int(ms.samples_in[s]) == r.next == r.hi and int(ms.buffered[s]) == 0
+        assert (int(st["received"][s]), int(st["late"][s]), int(st["duplicate"][s]), int(st["concealed"][s])) == \
+            (r.received, r.late, r.dup, r.concealed)
+        # the traffic: two gaps closer than P in one release, a gap beyond the fade, a jump beyond the slot's own J
+        assert any(len(g) >= 2 and any(b[0] - a[1] < Pn[s] for a, b in zip(g, g[1:])) for g in r.releases)
+        lens = [e - a for a, e in r.spans]
+        assert max(lens) > J[s] and sum(1 for n in lens if Fn[s] + Pn[s] < n < J[s]) >= 1 and r.dup > 0 and len(sch[s].lost) >= 6
+        E = r.E[:r.next]
+        whole = _offline(E, rate)
+        n_h = whole.numel() // H
+        assert len(tap.got[s]) == n_h >= 6 and int(ms.pending[s]) == whole.numel() - n_h * H
+        got = torch.cat(tap.got[s])
+        assert torch.equal(got, whole[: n_h * H]), (rate, mode, s)
+        assert np.abs(got.cpu().double().numpy() - _ref64(E, rate)[: n_h * H]).max() <= 2e-6 * float(np.abs(E).max())
+        ex = ms.export_slots([s])
+        k = int(ex.tensors["jitter_fill"][0])
+        assert torch.equal(ex.tensors["jitter_pending"][0, :k], whole[n_h * H:]) and not ex.tensors["jitter_pending"][0, k:].any()
+        # the slot wrapped its ring at its own J and never touched a column at or beyond it
+        assert r.next > 2 * J[s] and torch.equal(ms.jring[s, J[s]:].view(torch.int32), sentinel[s, J[s]:])
+
+
+def test_a_feed_of_every_rate_is_one_place_and_one_release_call_per_round(monkeypatch):
+    from afx._lib import lib
+    from afx.jitter import MixedJitterScorer
+    S = 6
+    tap = _tap(S)
+    ms = MixedJitterScorer(tap, FORMATS, DEPTH_MS)
+    ms.reset(list(range(S)), SLOT_RATES)
+    l = lib()
+    names = ("afx_k_jitter_place_rates", "afx_k_jitter_conceal_rates", "afx_k_jitter_release_rates", "afx_k_jitter_place",
+             "afx_k_jitter_place_mixed", "afx_k_jitter_conceal", "afx_k_jitter_release", "afx_k_ingest_pop")
+    calls = {n: 0 for n in names}
+    for name in names:
+        real = getattr(l, name)
+
+        def counted(*args, _real=real, _name=name):
+            calls[_name] += 1
+            return _real(*args)
+
+        monkeypatch.setattr(l, name, counted)
+    g = np.random.default_rng(3)
+    encs = ["mulaw", "alaw", "pcm_s16le", "pcm_f32le", "pcm_s16le", "pcm_s16le"]
+    order = [4, 0, 5, 2, 1, 3]
+    t = 0
+    per_feed = []
+    data = [[] for _ in range(S)]
+    for k in range(8):  # 160 ms of in-order audio per slot: one round per feed, a release from the fourth feed on
+        before = dict(calls)
+        pk = {s: _packet(encs[s], SLOT_RATES[s] // 50, g) for s in order}
+        for s in order:
+            data[s].append(pk[s][1])
+        res = ms.feed([pk[s][0] for s in order], order, [k * (SLOT_RATES[s] // 50) for s in order], encodings=[encs[s] for s in order])
+        per_feed.append({n: calls[n] - before[n] for n in names})
+        assert int(res.counts.sum()) == 0
+    for k, c in enumerate(per_feed):  # whatever the number of rates: one place and at most one release, no one-rate entry point
+        assert c["afx_k_jitter_place_rates"] == 1 and c["afx_k_jitter_release_rates"] == (1 if k >= 3 else 0), (k, c)
+        assert not any(c[n] for n in names[3:7]) and c["afx_k_jitter_conceal_rates"] == 0
+    monkeypatch.undo()
+    ms.flush()
+    for s, rate in enumerate(SLOT_RATES):  # and it computed the right thing
+        whole = _offline(np.concatenate(data[s]), rate)
+        k = int(ms.pending[s])
+        assert k == whole.numel() and torch.equal(ms.export_slots([s]).tensors["jitter_pending"][0, :k], whole)
+
+
+# ---- over the real scorers -------------------------------------------------------------------------------------------------
+_ENGINE = []
+
+
+def _inner(kind, S):
+    from afx import engine, synth
+    from afx.streaming import IncrementalScorer, KVCachedScorer
+    if not _ENGINE:
+        sd = synth.model_state_dict("ConformerModel", n_layers=1, n_encoders=1)
+        eng = engine.Engine("conformer", n_layers=1, dtype="fp16", conf_blocks=1)
+        eng.load_state_dict(sd)
+        _ENGINE.append((eng, sd))
+    eng, sd = _ENGINE[0]
+    if kind == "incremental":
+        return IncrementalScorer(eng, sd, S, window=16000, hop=H)
+    return KVCachedScorer(eng, sd, S, window=64000, hop=H)
+
+
+def _one_rate(kind, rate, mode):
+    """The scorer of the contract for a slot at ``rate``: a JitterScorer of that rate over a same-weights inner scorer."""
+    from afx.jitter import JitterScorer
+    depth, P, F, _, _, _ = _sizing(rate, mode)
+    kw = dict(period=P, fade=F) if mode == "repeat" else {}
+    return JitterScorer(_inner(kind, 1), rate, ENC_AT[rate], depth, conceal=mode, **kw)
+
+
+def _by_slot(res, slots):
+    """A FeedResult over the rows ``slots`` -> {slot: (its scores, its hop count)}."""
+    out = {}
+    for s, part in zip(slots, res.split()):
+        out.setdefault(s, []).append(part)
+    return {s: (torch.cat(p), sum(x.numel() for x in p)) for s, p in out.items()}
+
+
+@pytest.mark.parametrize("kind,mode", [("incremental", "repeat"), ("kv", "zero")])
+def test_mixed_scores_stats_and_counts_equal_the_one_rate_jitter_scorers(kind, mode):
+    from afx.jitter import MixedJitterScorer
+    S = 6
+    rates = list(SLOT_RATES)
+    ms = MixedJitterScorer(_inner(kind, S), FORMATS, DEPTH_MS, conceal=mode)
+    ms.reset(list(range(S)), rates)
+    refs = [_one_rate(kind, r, mode) for r in rates]  # slot s's reference, fed slot s's packets alone (as its slot 0)
+    rng = random.Random(11 + len(kind))
+    new = lambda s, seed: Schedule(rates[s], ENC_AT[rates[s]] if s == 0 or rates[s] != 8000 else ("alaw",), seed,
+                                   jump=_sizing(rates[s], mode)[5] + 50 if s == 2 else 0, P=rates[s] // 100, quiet=True)
+    sch = [new(s, 500 + s) for s in range(S)]
+    emitted, calls, buffered, changed = [0] * S, 0, 0, False
+    while not all(sc.done() for sc in sch):
+        calls += 1
+        if calls == 25:  # slot 4 (48 kHz) ends its call and starts an 8 kHz one; its neighbours go on
+            ms.reset([4], 8000)
+            rates[4], changed = 8000, True
+            refs[4] = _one_rate(kind, 8000, mode)
+            sch[4] = new(4, 900)
+            assert ms.rates.tolist() == rates and int(ms.samples_in[4]) == 0 and int(ms.pending[4]) == 0
+        ticks = {s: sch[s].tick() for s in range(S) if not sch[s].done() and rng.random() < 0.8}
+        if not ticks:
+            continue
+        rows = _rows_of(ticks, rng)
+        slots = [r[0] for r in rows]
+        fits = all(int(ms.pending[s]) + 2 * (int(ms.buffered[s]) + sum(len(r[4]) for r in rows if r[0] == s)) + 2 <= 4 * H for s in ticks)
+        score = not (calls % 4 == 2 and fits)
+        buffered += not score
+        got = _by_slot(ms.feed([r[3] for r in rows], slots, [r[1] for r in rows], score=score, encodings=[r[5] for r in rows]), slots)
+        for s in ticks:
+            mine = [r for r in rows if r[0] == s]
+            want = refs[s].feed([r[3] for r in mine], [0] * len(mine), [r[1] for r in mine], score=score, encodings=[r[5] for r in mine])
+            assert got[s][1] == int(want.counts.sum()) and torch.equal(got[s][0], want.scores), (kind, s, calls)
+            emitted[s] += got[s][1]
+        if calls % 4 == 3:  # what the buffered feed before this one left comes out of a drain, slot by slot as in the reference
+            res = ms.drain()
+            for s, part in enumerate(res.split()):
+                assert torch.equal(part, refs[s].drain([0]).scores), (kind, s, calls)
+                emitted[s] += part.numel()
+        for s in range(S):
+            a, b = ms.stats(), refs[s].stats()
+            assert all(int(a[k][s]) == int(b[k][0]) for k in a), (s, calls)
+            assert (int(ms.samples_in[s]), int(ms.buffered[s]), int(ms.pending[s])) == \
+                (int(refs[s].samples_in[0]), int(refs[s].buffered[0]), int(refs[s].pending[0]))
+    res = ms.flush()
+    for s, part in enumerate(res.split()):
+        assert torch.equal(part, refs[s].flush([0]).scores)
+        emitted[s] += part.numel()
+    assert changed and buffered >= 3 and all(e >= 3 for e in emitted) and int(ms.stats()["concealed"].min()) > 0
+    assert ms.samples_seen.tolist() == [int(refs[s].samples_seen[0]) for s in range(S)]
+
+
+def _gapped(rate, encoding, seed, n_pk=40, lost=(10, 11, 24)):
+    """In-order 20-ms packets of one stream with a few lost -> [(timestamp, bytes)]; after packet 13 has been fed with a depth
+    of three packets the playout point stands inside the gap of packets 10 and 11."""
+    g = np.random.default_rng(seed)
+    n = rate // 50
+    return [((seed * 7919 + k * n) % (1 << 32), _packet(encoding, n, g, quiet=True)[0]) for k in range(n_pk) if k not in lost]
+
+
+def test_sessions_move_mid_gap_between_mixed_scorers_and_in_from_a_plain_jitter_scorer():
+    from afx.jitter import JitterScorer, MixedJitterScorer
+    from afx.streaming import StreamState
+    kind = "incremental"
+    A = MixedJitterScorer(_inner(kind, 3), [(8000, "mulaw"), (48000, "pcm_s16le"), (16000, "pcm_s16le")], DEPTH_MS)
+    A.reset([0, 1], [8000, 48000])
+    B = MixedJitterScorer(_inner(kind, 3), [(48000, "pcm_s16le"), (16000, "pcm_f32le"), (8000, "alaw"), (8000, "mulaw")], DEPTH_MS,
+                          max_pending=3)
+    P = JitterScorer(_inner(kind, 2), 48000, "pcm_s16le", DEPTH_MS * 48)  # (its default period and fade are the mixed scorer's)
+    streams = [_gapped(8000, "mulaw", 1), _gapped(48000, "pcm_s16le", 2), _gapped(48000, "pcm_s16le", 3)]
+    src = [(A, 0), (A, 1), (P, 1)]
+    for k in range(12):  # packets 0..9, 12 and 13: hi is 14 packets, the playout point 11 packets, in the gap that began at 10
+        for (sc, s), st in zip(src, streams):
+            sc.feed([st[k][1]], [s], [st[k][0]])
+    for (sc, s), r in zip(src, (8000, 48000, 48000)):
+        book = sc.export_slots([s]).tensors["jitter_book"][0].tolist()
+        assert book[2:5] == [11 * (r // 50), 14 * (r // 50), 10 * (r // 50)]
+    st = A.export_slots([1, 0])
+    assert st.tensors["jitter_rate"].tolist() == [48000, 8000] and st.tensors["jitter_params"].tolist() == [[2880, 480, 1440], [480, 80, 240]]
+    own = 80 + 240 + 480
+    assert tuple(st.tensors["jitter_ring"].shape) == (2, 480 + 1440 + 2880) and st.tensors["jitter_ring"][1, :own].any()
+    assert not st.tensors["jitter_ring"][1, own:].any() and "input_rate" not in st.meta and st.meta["jitter_mixed"] == 1
+    B.import_slots([2, 0], StreamState.from_state_dict(st.to("cpu").state_dict()))
+    B.import_slots([1], P.export_slots([1]).to("cpu"))
+    assert B.rates.tolist() == [8000, 48000, 48000] and B.samples_in.tolist() == [11 * 160, 11 * 960, 11 * 960]
+    moved = {0: 0, 2: 1, 1: 2}  # B's slot -> the stream (and its unmoved source)
+    scores = 0
+    for k in range(12, len(streams[0])):
+        named = [2, 0, 1] if k % 2 else [1, 2, 0]
+        res = B.feed([streams[moved[b]][k][1] for b in named], named, [streams[moved[b]][k][0] for b in named],
+                     encodings=["mulaw" if moved[b] == 0 else "pcm_s16le" for b in named])  # (B's default at 8 kHz is A-law)
+        for b, part in zip(named, res.split()):
+            sc, s = src[moved[b]]
+            assert torch.equal(part, sc.feed([streams[moved[b]][k][1]], [s], [streams[moved[b]][k][0]]).scores), (b, k)
+            scores += part.numel()
+    res = B.flush([0, 2, 1])
+    for b, part in zip([0, 2, 1], res.split()):
+        sc, s = src[moved[b]]
+        assert torch.equal(part, sc.flush([s]).scores)
+        scores += part.numel()
+        assert {k: int(v[b]) for k, v in B.stats().items()} == {k: int(v[s]) for k, v in sc.stats().items()}
+    assert scores >= 6 and int(B.stats()["concealed"].min()) == 3 * 160
+
+
+def _rtp(seq, ts, pt, payload, ssrc):
+    return struct.pack("!BBHII", 0x80, pt, seq & 0xFFFF, ts & 0xFFFFFFFF, ssrc) + payload
+
+
+def test_feed_rtp_with_static_and_dynamic_payload_types_equals_feed():
+    from afx.jitter import MixedJitterScorer
+    formats = [(8000, "mulaw"), (8000, "alaw"), (16000, "pcm_s16le")]
+    ta, tb = _tap(2), _tap(2)
+    a, b = MixedJitterScorer(ta, formats, DEPTH_MS), MixedJitterScorer(tb, formats, DEPTH_MS)
+    for m in (a, b):
+        m.reset([1], 16000)
+    g = np.random.default_rng(4)
+    order = [k for k in range(60) if k not in (7, 20, 21)]
+    order[30], order[32], order[40], order[41] = order[32], order[30], order[41], order[40]
+    types = {96: (16000, "pcm_s16le")}
+    for k in order:
+        pt = 0 if k % 2 else 8
+        enc = ["mulaw" if pt == 0 else "alaw", "pcm_s16le"]
+        pay = [_packet(enc[0], 160, g)[0], _packet(enc[1], 320, g)[0]]
+        ts = [((1 << 32) - 1000 + k * 160) % (1 << 32), (77 + k * 320) % (1 << 32)]
+        a.feed_rtp([_rtp(65530 + k, ts[1], 96, pay[1], 0xB), _rtp(65530 + k, ts[0], pt, pay[0], 0xA)], [1, 0], payload_types=types)
+        b.feed([pay[1], pay[0]], [1, 0], [ts[1], ts[0]], encodings=[enc[1], enc[0]])
+    with pytest.raises(ValueError):
+        a.feed_rtp([_rtp(1, 0, 0, bytes(160), 0xB)], [1], payload_types=types)  # PT 0 is 8 kHz, slot 1 is at 16 kHz
+    a.flush()
+    b.flush()
+    for s in (0, 1):
+        assert len(ta.got[s]) == len(tb.got[s]) >= 4 and torch.equal(torch.cat(ta.got[s]), torch.cat(tb.got[s]))
+    assert a.stats()["concealed"].tolist() == [3 * 160, 3 * 320] == b.stats()["concealed"].tolist()
+    assert a.stats()["out_of_order"].tolist() == b.stats()["out_of_order"].tolist() and min(a.stats()["out_of_order"].tolist()) >= 2
