@@ -341,6 +341,9 @@ int afx_k_ingest_pop(const float* ring, int S, int ring_len, const int* table, i
  * played-out stream E (indexed from the session's first accepted timestamp) lives at column i mod J.  All indices are the
  * host's (playout point, received intervals, gaps); nothing is read back.  With lookback = max(T-1, P+F) the host keeps every
  * launch of a round that has released E below `cur` inside the J consecutive indices [cur - lookback, cur + J - lookback).
+ * Each of the three verbs (place, conceal, release) is one kernel over a table of rates (afx_k_jitter_*_rates below); the four
+ * entry points here are its case of one rate, built from their scalar arguments: one table entry, Js = J, rows without a rate
+ * index.  What they write and what they refuse is stated here.
  * afx_k_jitter_place: one launch for all packet sub-ranges of a feed.  hdr (device, rows x 4 int32), per row: slot, byte
  *     offset of the sub-range's first sample in stage (a multiple of the sample size), n samples, ring column c of the
  *     first: jring[slot][(c + k) mod J] = decode(sample k), k < n, with afx_k_ingest's encodings and exact decode.  The rows
@@ -361,7 +364,7 @@ int afx_k_jitter_place_mixed(const void* stage, long long stage_bytes, const int
  *     one fp32 multiply of two stored fp32 values; fade (device, F fp32), P the repeat period, F the fade length.  The
  *     source [a - P, a) is read from the ring as it stands (it may hold an earlier gap's concealed samples): gaps of one
  *     slot go in successive launches, the rows of one launch are of distinct slots.  max_n = the largest d_hi - d_lo; a row
- *     needs d_hi + P <= J (source and written columns disjoint), else it is skipped whole. */
+ *     needs d_hi + P <= J (source and written columns disjoint), else it is skipped whole; max_n + P > J is refused. */
 int afx_k_jitter_conceal(float* jring, int S, int J, const int* hdr, int rows, int max_n, const float* fade, int P, int F,
                          int mode, void* stream);
 /* afx_k_jitter_release: afx_k_ingest with the ring as its input.  hdr (device, rows x 8 int32), per row: slot, a0 mod J,
@@ -372,7 +375,7 @@ int afx_k_jitter_conceal(float* jring, int S, int J, const int* hdr, int rows, i
  *     after a reset) -- the same inputs, fp32 taps and ascending-j fma chain -- written to ring[slot][(wpos + k) mod
  *     ring_len], the pending 16 kHz ring afx_k_ingest_pop reads.  taps NULL with L = M = T = 1: a copy.  Slots of one launch
  *     are distinct; max_out = the largest n_out <= ring_len; n_in <= J, T - 1 <= J, M/L <= 12.  A row whose header would
- *     leave a ring is skipped whole. */
+ *     leave a ring, or with n_out > max_out, is skipped whole: it writes nothing.  The eighth int is not read. */
 int afx_k_jitter_release(const float* jring, int S, int J, const int* hdr, int rows, int max_out, const float* taps, int L,
                          int M, int T, float* ring, int ring_len, void* stream);
 /* The jitter buffer over slots of different clock rates (afx/jitter.py MixedJitterScorer).  A rate is (taps, L, M, T) as for
@@ -383,21 +386,24 @@ int afx_k_jitter_release(const float* jring, int S, int J, const int* hdr, int r
  * at rate f keeps sample i of its stream at column i mod J_f of its row, uses the columns [0, J_f) only and never touches a
  * column at or beyond J_f, so the sizing invariant above holds per slot with its own J_f.  A row names its rate by an index, the
  * last int of its header, and is validated against ITS rate (index in range, column < J_f, n <= J_f, d_hi + P_f <= J_f,
- * p0 < L_f, and the one-rate kernel's other checks); a row that fails writes nothing.  Every value written is the one the
- * one-rate entry point writes in a launch of that rate: the same decoder, the same single fp32 multiply, the same inputs, taps
- * and ascending-j fma chain.
+ * p0 < L_f, and the other checks stated above); a row that fails writes nothing.  Every value written is the one the
+ * one-rate entry point writes in a launch of that rate: it is the same kernel, so the same decoder, the same single fp32
+ * multiply, the same inputs, taps and ascending-j fma chain.
  * afx_k_jitter_place_rates: hdr (device, rows x 6 int32): afx_k_jitter_place_mixed's five ints, then the rate index;
- *     jring[slot][(c + k) mod J_f] = decode(sample k), k < n.  max_n = the largest n <= Js.
+ *     jring[slot][(c + k) mod J_f] = decode(sample k), k < n.  max_n = the largest n.
  * afx_k_jitter_conceal_rates: hdr (device, rows x 5 int32): afx_k_jitter_conceal's four ints, then the rate index; the
  *     function of afx_k_jitter_conceal with the row's P_f, F_f, fade_f and J_f.  mode (0 zero, 1 repeat) is the launch's; in
- *     mode 0 the rates' P, F and fade are not read.  max_n = the largest d_hi - d_lo <= Js.
+ *     mode 0 the rates' P, F and fade are not read (P_f = 0 below).  max_n = the largest d_hi - d_lo.
+ *     For both, max_n is refused when NO rate of the table can hold such a row, max_n + P_f > J_f for every f (place: P_f = 0):
+ *     with one rate that is max_n > J, or max_n + P > J; with several it refuses only launches whose largest row every rate
+ *     would skip on the device anyway.
  * afx_k_jitter_release_rates: hdr (device, rows x 8 int32): afx_k_jitter_release's, the eighth int the rate index.  max_out
  *     (HOST, n_rates ints): per rate the largest n_out among its rows of this call, 0 = no row of it (a row with more outputs than its
  *     rate's max_out writes nothing).  The grid and the dynamic LDS are the largest over the rates present; a workgroup beyond its row's
  *     outputs leaves before it stages anything.
  * Refused with nothing launched: n_rates outside 1..16, a null table, a bad filter shape, T - 1 > J, J outside 1..Js, M/L
- * above 12, mode 1 with a null fade or P <= 0, a null stage / hdr / jring / ring / max_out, rows outside 1..65535, max_n beyond
- * Js, a max_out beyond ring_len. */
+ * above 12, mode 1 with a null fade or P <= 0, a null stage / hdr / jring / ring / max_out, rows outside 1..65535, a max_n no
+ * rate can hold, a max_out beyond ring_len.  Each refusal names its entry point; the one-rate entry points refuse the same. */
 typedef struct afx_jitter_rate {
   const float* taps; /* device, (L, T) fp32; NULL: the identity */
   const float* fade; /* device, (max(F, 1),) fp32: fp32(1 - d/F); may be NULL in mode 0 */

@@ -57,19 +57,21 @@ scores, hop counts per call, ``stats()``, ``samples_in``, ``buffered`` and ``pen
 those of ``JitterScorer(inner, r, encodings_at_r, depth_r, conceal, period=P_r, fade=F_r, max_pending, ts_bits)`` fed the
 slot's own packets in the same calls: the inner scorer runs on ``Resampler(r)(E_s)`` with E_s the played-out stream defined
 above.  No new arithmetic: the rate is a per-row value of the same three launches (``afx_k_jitter_place_rates`` /
-``_conceal_rates`` / ``_release_rates``: the row's last int names its rate, the workgroup runs the one-rate kernel's row
-body with that rate's J, P, F, fade table and filter), so every value comes from the same decoder, the same single fp32
-multiply and the same taps and ascending-j fma chain as in a one-rate launch, and the host plans each slot with its own
-L, M, J, W, F and depth.  Sizing: per rate JitterScorer's lookback_r = max(T_r - 1, P_r + F_r), W_r = depth_r +
-ceil(hop * M_r / L_r) + 1, J_r = lookback_r + W_r; one ring (S, Js), Js = max J_r; a slot at rate r uses the columns
-[0, J_r) of its row with modulus J_r and never a column at or beyond J_r, so the invariant above holds per slot with its own
-J_r.  A mixed state has ``jitter_ring`` (n, widest lookback_r + depth_r), zeros beyond a session's own columns,
+``_conceal_rates`` / ``_release_rates``: the row's last int names its rate, the workgroup runs its verb's one row body
+with that rate's J, P, F, fade table and filter; a one-rate launch is the same kernel with a table of one entry), so every
+value comes from the same decoder, the same single fp32 multiply and the same taps and ascending-j fma chain as in a
+one-rate launch, and the host plans each slot with its own L, M, J, W, F and depth: ``JitterScorer`` is the scorer whose
+table of rates has one entry and whose every slot is at index 0.  Sizing: per rate JitterScorer's lookback_r =
+max(T_r - 1, P_r + F_r), W_r = depth_r + ceil(hop * M_r / L_r) + 1, J_r = lookback_r + W_r; one ring (S, Js), Js = max J_r;
+a slot at rate r uses the columns [0, J_r) of its row with modulus J_r and never a column at or beyond J_r, so the
+invariant above holds per slot with its own J_r.  A mixed state has ``jitter_ring`` (n, widest lookback_r + depth_r), zeros beyond a session's own columns,
 ``jitter_rate`` ((n,) int64) and ``jitter_params`` ((n, 3) int64: depth, period, fade), and the meta ``jitter``,
 ``jitter_conceal``, ``resampler`` and ``jitter_mixed``; a plain JitterScorer's state imports where its rate is listed and
 its parameters are that rate's.  Out of scope: a rate change without a reset, per-slot depth within one rate, big-endian
 L16 payloads (swap the bytes), per-slot conceal modes.
 """
 import ctypes as C
+from itertools import repeat
 
 import numpy as np
 import torch
@@ -91,6 +93,7 @@ _STATE_KEYS = ("jitter_pending", "jitter_fill", "jitter_ring", "jitter_book", "j
 _BOOK = ("origin", "started", "next", "hi", "gap", "max_start", "max_seq", "ssrc")  # jitter_book columns
 _COUNTERS = ("received", "late", "dup", "concealed", "ooo")  # jitter_stats columns (STATS order)
 _BPS = np.array([_SAMPLE[e].itemsize for e in ENCODINGS], dtype=np.int64)  # bytes per sample by encoding number
+_NUMBER = {e: i for i, e in enumerate(ENCODINGS)}  # the library's encoding numbers
 
 
 def _nonneg_int(v, name, least=0):
@@ -190,7 +193,10 @@ class JitterScorer(_Front):
     ``conceal``: "repeat" or "zero".  ``period``: the repeat period P in input samples, default 10 ms (input_rate // 100).  ``fade``: the fade length F in
     input samples, default 3 P (30 ms).  ``max_pending``: the whole hops a slot may buffer between ``feed(..., score=False)``
     and ``drain``.  ``ts_bits``: 32 (default) unwraps each timestamp to the value nearest the slot's ``hi``, so a stream
-    crossing 2**32 is seamless; None takes absolute indices."""
+    crossing 2**32 is seamless; None takes absolute indices.
+
+    Every jitter scorer owns a table of its rates (``_size``) and each slot's index into it; this one's table has one entry,
+    every slot is at index 0, and the entry's values go by the names below (``depth``, ``period``, ``J`` ...)."""
 
     _WORK = "decoded, concealed, resampled"
     _rated = False  # (MixedJitterScorer: the rows of a plan carry their slot's rate index)
@@ -206,33 +212,60 @@ class JitterScorer(_Front):
                 raise ValueError("encoding: an encoding is listed twice")
         self.encoding = self.encodings[0]
         self.depth = _nonneg_int(depth, "depth")
+        max_pending = self._checked(conceal, max_pending, ts_bits)
+        super().__init__(scorer, input_rate)
+        self.period = self.fade_len = 0  # (no part of the "zero" function: not recorded in a state either)
+        if conceal == "repeat":
+            self.period = _nonneg_int(self.input_rate // 100 if period is None else period, "period", 1)
+            self.fade_len = _nonneg_int(3 * self.period if fade is None else fade, "fade")
+        self._size([self.rs], [self.encodings], [self.depth], [self.period], [self.fade_len], max_pending)
+        self.L, self.M, self.J, self.fade = self.rs.L, self.rs.M, self.Js, self._fades[0]
+        self.lookback, self.W = int(self._rlookback[0]), int(self._rW[0])
+
+    def _checked(self, conceal, max_pending, ts_bits):
+        """The constructor arguments every jitter scorer takes, checked: sets ``conceal`` and ``ts_bits`` -> max_pending."""
         if conceal not in CONCEAL:
             raise ValueError(f"conceal {conceal!r}: one of {CONCEAL}")
         max_pending = _nonneg_int(max_pending, "max_pending", 1)
         if ts_bits is not None and (isinstance(ts_bits, bool) or not isinstance(ts_bits, (int, np.integer)) or not 8 <= ts_bits <= 48):
             raise ValueError("ts_bits: None (absolute indices) or the width of the timestamp counter, 8..48")
-        self.ts_bits = None if ts_bits is None else int(ts_bits)
-        super().__init__(scorer, input_rate)
-        self.L, self.M = self.rs.L, self.rs.M
-        self.conceal = conceal
-        if conceal == "repeat":
-            self.period = _nonneg_int(self.input_rate // 100 if period is None else period, "period", 1)
-            self.fade_len = _nonneg_int(3 * self.period if fade is None else fade, "fade")
-        else:
-            self.period = self.fade_len = 0  # (no part of the "zero" function: not recorded in a state either)
-        # the sizing invariant (module docstring): J = lookback + W, W >= depth; the slack beyond depth is what a round can
-        # place and release at once (one hop of input: an ordinary packet never takes a second round)
-        self.lookback = max(0 if self.rs.identity else self.rs.T - 1, self.period + self.fade_len)
-        self.W = self.depth + -(-scorer.hop * self.M // self.L) + 1
-        self.J = self.lookback + self.W
-        if self.J >= _MAX_SAMPLES:
+        self.conceal, self.ts_bits = conceal, None if ts_bits is None else int(ts_bits)
+        return max_pending
+
+    def _size(self, rs, encs_at, depth, P, F, max_pending):
+        """The table of this scorer's rates, one entry per Resampler of ``rs`` (int64 arrays over the rates; ``depth``, ``P``
+        and ``F`` in each rate's own samples, ``encs_at`` the encodings listed at each), the device buffers sized from it, the
+        host table the ``_rates`` launches take, and every slot at rate index 0."""
+        scorer = self.scorer
+        arr = lambda v: np.array(v, dtype=np.int64)
+        self._rs, self._encs_at = list(rs), [tuple(e) for e in encs_at]
+        self._rates = tuple(x.rate for x in rs)  # in Hz, in the order first listed
+        self._renc = arr([_NUMBER[e[0]] for e in self._encs_at])  # the default encoding's number
+        self._listed = np.zeros((len(rs), len(ENCODINGS) + 1), dtype=bool)  # [rate index, encoding number]: listed at that rate
+        for i, e in enumerate(self._encs_at):
+            self._listed[i, [_NUMBER[v] for v in e]] = True
+        self._rrate, self._rL, self._rM = arr(self._rates), arr([x.L for x in rs]), arr([x.M for x in rs])
+        self._rdepth, self._rP, self._rF = arr(depth), arr(P), arr(F)
+        # the sizing invariant (module docstring), per rate: J = lookback + W, W >= depth; the slack beyond depth is what a
+        # round can place and release at once (one hop of input: an ordinary packet never takes a second round)
+        self._rlookback = np.maximum(arr([0 if x.identity else x.T - 1 for x in rs]), self._rP + self._rF)
+        self._rW = self._rdepth + -(-scorer.hop * self._rM // self._rL) + 1
+        self._rJ = self._rlookback + self._rW
+        self._rdelay = np.array([x.delay for x in rs], dtype=np.float64)
+        self.Js = int(self._rJ.max())
+        if self.Js >= _MAX_SAMPLES:
             raise ValueError("depth + period + fade: less than 2**30 samples")
         self._new_ring(max_pending)
-        self.jring = torch.zeros(scorer.S, self.J, dtype=torch.float32, device=scorer.device)
-        F = self.fade_len
-        table = (1.0 - np.arange(max(F, 1), dtype=np.float64) / max(F, 1)).astype(np.float32)
-        self.fade = torch.from_numpy(table).to(scorer.device)
+        self.jring = torch.zeros(scorer.S, self.Js, dtype=torch.float32, device=scorer.device)
+        self._fades = [_fade_table(int(f), scorer.device) for f in self._rF]  # one device table per rate
+        self._table = (JitterRate * len(rs))()  # (pointers: the tensors above)
+        for i, (t, x) in enumerate(zip(self._table, rs)):
+            t.taps = None if x.identity else x.taps.data_ptr()
+            t.fade = self._fades[i].data_ptr()
+            t.L, t.M, t.T = x.L, x.M, 1 if x.identity else x.T
+            t.J, t.P, t.F = int(self._rJ[i]), int(self._rP[i]), int(self._rF[i])
         self._b = _Book(scorer.S)
+        self._rate_of = np.zeros(scorer.S, dtype=np.int64)  # rate index of each slot (host)
 
     # ---- properties ----------------------------------------------------------------------------------------------------
     @property
@@ -257,10 +290,9 @@ class JitterScorer(_Front):
         return {k: torch.from_numpy(getattr(self._b, f).copy()) for k, f in zip(STATS, _COUNTERS)}
 
     # ---- planning (host arithmetic only) -----------------------------------------------------------------------------
-    def _geometry(self, slot):
-        """(L, M, J, W, F, depth, rate index) of the slots ``slot``: int64 arrays over them."""
-        n = len(slot)
-        return tuple(np.full(n, v, dtype=np.int64) for v in (self.L, self.M, self.J, self.W, self.fade_len, self.depth, 0))
+    def _geometry(self, rate):
+        """(L, M, J, W, F, depth, lookback) at the rate indices ``rate``: int64 arrays over them."""
+        return tuple(a[rate] for a in (self._rL, self._rM, self._rJ, self._rW, self._rF, self._rdepth, self._rlookback))
 
     def _unwrap(self, t, ref):
         """Timestamp t as the absolute value nearest ref (ts_bits), or as it is."""
@@ -274,7 +306,7 @@ class JitterScorer(_Front):
         offset, encoding number).  Rows that continue a hole-free slot at its ``hi`` (the common case) are handled for all
         slots at once; the others one by one.  ``encs``: the encoding number of every row (None: this scorer's first)."""
         if encs is None:
-            encs = np.full(slot.size, ENCODINGS.index(self.encoding), dtype=np.int64)
+            encs = self._renc[self._rate_of[slot]]
         bps_of = _BPS[encs]
         once = np.bincount(slot, minlength=self.S)[slot] == 1
         ref = b.origin[slot] + b.hi[slot]
@@ -380,7 +412,8 @@ class JitterScorer(_Front):
         _, first = np.unique(slot, return_index=True)
         first.sort()
         U = slot[first]  # the named slots, once each, in the order they were first named
-        L, M, J, W, F, depth, rate = self._geometry(U)  # (int64 arrays over U: a scorer of one rate passes constants)
+        rate = self._rate_of[U]
+        L, M, J, W, F, depth, _ = self._geometry(rate)  # (int64 arrays over U, each slot with its own rate's values)
         cur = b.next[U].copy()
         if mode == "feed":
             tgt = np.maximum(cur, b.hi[U] - depth)
@@ -516,26 +549,42 @@ class JitterScorer(_Front):
     def _plan_feed(self, packets, slots, timestamps, score=True, seqs=None, encodings=None):
         """The checks and the plan of a ``feed`` -> (Plan, payload blocks).  No state changes."""
         idx = self._rows(slots, repeats=True)
-        if encodings is None:
-            pay, nbytes = self._packets(packets, len(idx), self.encoding)
-            encs, bps = None, _SAMPLE[self.encoding].itemsize
+        ri = self._rate_of[np.asarray(idx, dtype=np.int64)]
+        if encodings is None:  # the first listed at each slot's rate
+            encs = self._renc[ri]
+            names = np.array(ENCODINGS, dtype=object)[encs].tolist()
         else:
             if isinstance(encodings, str) or not hasattr(encodings, "__len__"):
                 raise ValueError("encodings: one encoding per packet")
-            encodings = list(encodings)
-            for e in encodings:
-                if e not in self.encodings:
-                    raise ValueError(f"encoding {e!r} is not one of this scorer's {self.encodings}")
-            if len(encodings) != len(idx):
-                raise ValueError(f"{len(encodings)} encodings for {len(idx)} named slots")
-            pay, nbytes = self._packets_each(packets, encodings)
-            encs = np.array([ENCODINGS.index(e) for e in encodings], dtype=np.int64)
-            bps = _BPS[encs]
+            names = list(encodings)
+            if len(names) != len(idx):
+                raise ValueError(f"{len(names)} encodings for {len(idx)} named slots")
+            try:  # (a name that is no encoding at all gets the number of the table's last column, where nothing is listed)
+                encs = np.fromiter(map(_NUMBER.get, names, repeat(len(ENCODINGS))), dtype=np.int64, count=len(names))
+            except TypeError:
+                raise ValueError("encodings: one encoding per packet") from None
+            bad = np.flatnonzero(~self._listed[ri, encs])
+            if bad.size:
+                i, r = int(bad[0]), int(ri[bad[0]])
+                what = f"encoding {names[i]!r} is not one of this scorer's {self._encs_at[r]}"
+                raise ValueError(f"slot {idx[i]}: {what} at {self._rates[r]} Hz" if self._rated else what)
+        bps = _BPS[encs]
+        pay, nbytes = self._packets_each(packets, names, bps)
         ts = self._timestamps(timestamps, len(idx))
         offs, total = layout(nbytes)
         if total >= 1 << 31:
             raise ValueError("a feed carries less than 2 GiB")
         return self._plan(idx, nbytes // bps, ts, offs, seqs, "feed", score=score, encs=encs), pay
+
+    def _rtp_types(self, payload_types):
+        """What ``feed_rtp`` looks a payload type up in: 0 is mulaw and 8 alaw (RFC 3551), ``payload_types`` adds to them."""
+        return {**rtp.STATIC_PAYLOAD_TYPES, **(payload_types or {})}
+
+    def _rtp_encoding(self, s, pt, types):
+        """The encoding of a datagram of slot s with payload type pt, or the ValueError."""
+        if types.get(pt) not in self.encodings:
+            raise ValueError(f"slot {s}: RTP payload type {pt} is not this scorer's {' / '.join(self.encodings)}")
+        return types[pt]
 
     def feed_rtp(self, datagrams, slots, payload_types=None, score=True):
         """datagrams[i]: one RTP datagram (RFC 3550) of slot slots[i].  Its payload type must name this scorer's encoding (one
@@ -550,16 +599,15 @@ class JitterScorer(_Front):
             raise ValueError(f"{len(pk)} datagrams for {len(idx)} named slots")
         if self.ts_bits != 32:
             raise ValueError("feed_rtp: RTP timestamps are 32 bits wide (ts_bits = 32)")
-        types = {**rtp.STATIC_PAYLOAD_TYPES, **(payload_types or {})}
-        ssrc = {}
+        types = self._rtp_types(payload_types)
+        ssrc, encs = {}, []
         for s, p in zip(idx, pk):
-            if types.get(p.payload_type) not in self.encodings:
-                raise ValueError(f"slot {s}: RTP payload type {p.payload_type} is not this scorer's {' / '.join(self.encodings)}")
+            encs.append(self._rtp_encoding(s, p.payload_type, types))
             mine = ssrc.setdefault(s, int(self._b.ssrc[s]) if self._b.ssrc[s] >= 0 else p.ssrc)
             if p.ssrc != mine:
                 raise ValueError(f"slot {s}: SSRC {p.ssrc:#010x} is not the session's {mine:#010x}")
         res = self.feed([p.payload for p in pk], idx, [p.timestamp for p in pk], score=score, _seqs=[p.seq for p in pk],
-                        encodings=[types[p.payload_type] for p in pk] if self._mixed else None)
+                        encodings=encs if self._mixed else None)
         for s, v in ssrc.items():
             self._b.ssrc[s] = v
         return res
@@ -627,15 +675,20 @@ class JitterScorer(_Front):
     def export_slots(self, slots):
         """The inner scorer's ``StreamState`` of the named slots plus their jitter-buffer sessions (module docstring).  What is
         stored is decoded.  No byte of the scorer changes."""
-        idx = self.scorer._slot_list(slots, ordered=True)
+        return self._export(self.scorer._slot_list(slots, ordered=True))
+
+    def _export(self, idx, **more):
+        """``export_slots`` of the slots ``idx``; ``more``: tensors a subclass adds.  ``jitter_ring`` is as wide as the widest
+        lookback + depth of this scorer's rates, zeros beyond what a session holds."""
         st = self.scorer.export_slots(idx)
         dev, b = self.device, self._b
-        width = self.lookback + self.depth
+        _, _, J, _, _, _, lb = (torch.from_numpy(a) for a in self._geometry(self._rate_of[idx]))
+        width = int((self._rlookback + self._rdepth).max())
         with _on(dev):
             nxt, held = torch.from_numpy(b.next[idx]), torch.from_numpy(b.hi[idx] - b.next[idx])
             k = torch.arange(width)
-            jr = self.jring[rows_on(idx, dev)[:, None], ((nxt[:, None] - self.lookback + k) % self.J).to(dev)]
-            jr.masked_fill_((k[None, :] >= self.lookback + held[:, None]).to(dev), 0.0)
+            jr = self.jring[rows_on(idx, dev)[:, None], ((nxt[:, None] - lb[:, None] + k) % J[:, None]).to(dev)]
+            jr.masked_fill_((k[None, :] >= (lb + held)[:, None]).to(dev), 0.0)
         ivs = [b.intervals(s) for s in idx]
         K = max([len(v) for v in ivs] + [1])
         table = np.full((len(idx), K, 2), -1, dtype=np.int64)
@@ -645,9 +698,8 @@ class JitterScorer(_Front):
         book = np.stack([getattr(b, f)[idx] for f in _BOOK], axis=1).reshape(len(idx), len(_BOOK))
         stats = np.stack([getattr(b, f)[idx] for f in _COUNTERS], axis=1).reshape(len(idx), len(_COUNTERS))
         return wrap(st, self._meta(), jitter_pending=export_pending(self.ring, idx, b.head[idx], b.fill[idx], self.max_pending * self.hop),
-                    jitter_fill=torch.from_numpy(b.fill[idx]),
-                          jitter_ring=jr, jitter_book=torch.from_numpy(book), jitter_stats=torch.from_numpy(stats),
-                          jitter_intervals=torch.from_numpy(table))
+                    jitter_fill=torch.from_numpy(b.fill[idx]), jitter_ring=jr, jitter_book=torch.from_numpy(book),
+                    jitter_stats=torch.from_numpy(stats), jitter_intervals=torch.from_numpy(table), **more)
 
     def import_slots(self, slots, state):
         """The named slots take over the sessions of ``state``, a state of a JitterScorer with the same input rate, filter,
@@ -665,7 +717,7 @@ class JitterScorer(_Front):
     def _check_sessions(self, state, n, rate):
         """The checks of the jitter part of ``state`` (n sessions, session i at this scorer's rate index rate[i]) -> what
         ``_install`` takes.  A ValueError for counters that contradict each other; nothing changes."""
-        L, M, J, _, _, depth, _ = self._geometry_of(rate)
+        L, M, J, _, _, depth, _ = self._geometry(rate)
         pend = state.tensors["jitter_pending"]
         ints = [state.tensors[k].cpu() for k in ("jitter_fill", "jitter_book", "jitter_stats", "jitter_intervals")]
         if any(t.dtype != torch.int64 for t in ints):
@@ -692,13 +744,6 @@ class JitterScorer(_Front):
             lists.append(v)
         return pend, state.tensors["jitter_ring"], fill, col, stats, lists, rate
 
-    def _geometry_of(self, rate):
-        """``_geometry`` by rate index (one entry per session of a state)."""
-        return self._geometry(rate)
-
-    def _lookbacks(self, rate):
-        return np.full(len(rate), self.lookback, dtype=np.int64)
-
     def _install(self, idx, inner, checked):
         """The inner scorer imports ``inner`` (it refuses a foreign state before changing anything), then the named slots take
         the checked jitter part: ring columns [next - lookback, ...) at their places modulo each session's own J."""
@@ -707,9 +752,8 @@ class JitterScorer(_Front):
         if not idx:
             return
         dev, b = self.device, self._b
-        geo = self._geometry_of(rate)
-        J, lookback = geo[2], self._lookbacks(rate)
-        own = lookback + geo[5]  # each session's own columns of jitter_ring: lookback + depth
+        _, _, J, _, _, depth, lookback = self._geometry(rate)
+        own = lookback + depth  # each session's own columns of jitter_ring
         import_pending(self.ring, idx, pend)
         with _on(dev):
             rows = rows_on(idx, dev)
@@ -742,7 +786,8 @@ class MixedJitterScorer(JitterScorer):
     P = r // 100 (``period_ms`` given: max(1, period_ms * r // 1000)) and F = 3 P (``fade_ms`` given: fade_ms * r // 1000) of
     that rate's samples.  A slot's rate is chosen at ``reset`` (a fresh scorer has every slot at the first format's rate)
     and never changes between resets; everything a ``JitterScorer`` counts in input samples is, per slot, in the slot's own
-    rate.  See the module docstring for the contract."""
+    rate.  ``feed_rtp`` takes ``payload_types`` as {number: (input_rate, encoding)}.  See the module docstring for the
+    contract."""
 
     _rated = True
 
@@ -755,47 +800,19 @@ class MixedJitterScorer(JitterScorer):
         if len(set(fm)) != len(fm):
             raise ValueError("formats: a format is listed twice")
         depth_ms = _nonneg_int(depth_ms, "depth_ms")
-        if conceal not in CONCEAL:
-            raise ValueError(f"conceal {conceal!r}: one of {CONCEAL}")
         period_ms = None if period_ms is None else _nonneg_int(period_ms, "period_ms")
         fade_ms = None if fade_ms is None else _nonneg_int(fade_ms, "fade_ms")
-        max_pending = _nonneg_int(max_pending, "max_pending", 1)
-        if ts_bits is not None and (isinstance(ts_bits, bool) or not isinstance(ts_bits, (int, np.integer)) or not 8 <= ts_bits <= 48):
-            raise ValueError("ts_bits: None (absolute indices) or the width of the timestamp counter, 8..48")
-        self.ts_bits = None if ts_bits is None else int(ts_bits)
-        self.scorer, self.formats, self.conceal, self._mixed = scorer, fm, conceal, True
+        max_pending = self._checked(conceal, max_pending, ts_bits)
+        self.scorer, self.formats, self._mixed = scorer, fm, True
         self.depth_ms, self.period_ms, self.fade_ms = depth_ms, period_ms, fade_ms
-        self._rates = tuple(dict.fromkeys(r for r, _ in fm))  # the distinct rates, in the order first listed
-        self._encs_at = [tuple(e for q, e in fm if q == r) for r in self._rates]
-        self._rs = [Resampler(r, scorer.device) for r in self._rates]
-        arr = lambda v: np.array(v, dtype=np.int64)
-        rate = arr(self._rates)
-        self._rrate, self._rL, self._rM = rate, arr([x.L for x in self._rs]), arr([x.M for x in self._rs])
-        self._rdepth = depth_ms * rate // 1000
+        rates = tuple(dict.fromkeys(r for r, _ in fm))  # the distinct rates, in the order first listed
+        rate = np.array(rates, dtype=np.int64)
+        P = F = np.zeros_like(rate)  # (no part of the "zero" function)
         if conceal == "repeat":
-            self._rP = rate // 100 if period_ms is None else np.maximum(1, period_ms * rate // 1000)
-            self._rF = 3 * self._rP if fade_ms is None else fade_ms * rate // 1000
-        else:
-            self._rP = self._rF = np.zeros_like(rate)  # (no part of the "zero" function)
-        # per rate exactly JitterScorer's sizing: lookback = max(T - 1, P + F), W = depth + one hop of input + 1, J = lookback + W
-        self._rlookback = np.maximum(arr([0 if x.identity else x.T - 1 for x in self._rs]), self._rP + self._rF)
-        self._rW = self._rdepth + -(-scorer.hop * self._rM // self._rL) + 1
-        self._rJ = self._rlookback + self._rW
-        self._rdelay = np.array([x.delay for x in self._rs], dtype=np.float64)
-        self.Js = int(self._rJ.max())
-        if self.Js >= _MAX_SAMPLES:
-            raise ValueError("depth + period + fade: less than 2**30 samples")
-        self._new_ring(max_pending)
-        self.jring = torch.zeros(scorer.S, self.Js, dtype=torch.float32, device=scorer.device)
-        self._fades = [_fade_table(int(F), scorer.device) for F in self._rF]  # one device table per rate
-        self._table = (JitterRate * len(self._rates))()  # the host table the three launches take (pointers: the tensors above)
-        for i, (t, x) in enumerate(zip(self._table, self._rs)):
-            t.taps = None if x.identity else x.taps.data_ptr()
-            t.fade = self._fades[i].data_ptr()
-            t.L, t.M, t.T = x.L, x.M, 1 if x.identity else x.T
-            t.J, t.P, t.F = int(self._rJ[i]), int(self._rP[i]), int(self._rF[i])
-        self._b = _Book(scorer.S)
-        self._rate_of = np.zeros(scorer.S, dtype=np.int64)  # rate index of each slot (host)
+            P = rate // 100 if period_ms is None else np.maximum(1, period_ms * rate // 1000)
+            F = 3 * P if fade_ms is None else fade_ms * rate // 1000
+        self._size([Resampler(r, scorer.device) for r in rates], [tuple(e for q, e in fm if q == r) for r in rates],
+                   depth_ms * rate // 1000, P, F, max_pending)
 
     # ---- per-slot quantities ---------------------------------------------------------------------------------------------
     @property
@@ -839,15 +856,6 @@ class MixedJitterScorer(JitterScorer):
     def input_rate(self):
         raise AttributeError("a MixedJitterScorer has one input rate per slot: rates")
 
-    def _geometry_of(self, rate):
-        return (self._rL[rate], self._rM[rate], self._rJ[rate], self._rW[rate], self._rF[rate], self._rdepth[rate], rate)
-
-    def _geometry(self, slot):
-        return self._geometry_of(self._rate_of[slot])
-
-    def _lookbacks(self, rate):
-        return self._rlookback[rate]
-
     def _rate_indices(self, rates, n):
         """``rates``: one rate in Hz for n slots, or n of them -> (n,) int64 array of indices into this scorer's rates."""
         if isinstance(rates, (torch.Tensor, np.ndarray)):
@@ -864,59 +872,21 @@ class MixedJitterScorer(JitterScorer):
         return np.array([self._rates.index(int(r)) for r in vals], dtype=np.int64).reshape(n)
 
     # ---- the public calls ------------------------------------------------------------------------------------------------
-    def _plan_feed(self, packets, slots, timestamps, score=True, seqs=None, encodings=None):
-        idx = self._rows(slots, repeats=True)
-        ri = self._rate_of[np.asarray(idx, dtype=np.int64)].tolist()
-        if encodings is None:
-            names = [self._encs_at[r][0] for r in ri]
-        else:
-            if isinstance(encodings, str) or not hasattr(encodings, "__len__"):
-                raise ValueError("encodings: one encoding per packet")
-            names = list(encodings)
-            if len(names) != len(idx):
-                raise ValueError(f"{len(names)} encodings for {len(idx)} named slots")
-            for s, r, e in zip(idx, ri, names):
-                if e not in self._encs_at[r]:
-                    raise ValueError(f"slot {s}: encoding {e!r} is not one of this scorer's {self._encs_at[r]} at {self._rates[r]} Hz")
-        pay, nbytes = self._packets_each(packets, names)
-        encs = np.array([ENCODINGS.index(e) for e in names], dtype=np.int64)
-        ts = self._timestamps(timestamps, len(idx))
-        offs, total = layout(nbytes)
-        if total >= 1 << 31:
-            raise ValueError("a feed carries less than 2 GiB")
-        return self._plan(idx, nbytes // _BPS[encs], ts, offs, seqs, "feed", score=score, encs=encs), pay
-
-    def feed_rtp(self, datagrams, slots, payload_types=None, score=True):
-        """``JitterScorer.feed_rtp`` with ``payload_types`` mapping a number to an (input_rate, encoding) pair: 0 and 8 are
+    def _rtp_types(self, payload_types):
+        """``feed_rtp`` here takes ``payload_types`` mapping a number to an (input_rate, encoding) pair: 0 and 8 are
         (8000, "mulaw") and (8000, "alaw") (RFC 3551).  A datagram whose type maps to another rate than its slot's, or to a
         pair this scorer does not list, is a ValueError before anything changes."""
-        idx = self._rows(slots, repeats=True)
-        if isinstance(datagrams, (bytes, bytearray, memoryview)):
-            raise ValueError("datagrams: a list with one datagram per named slot")
-        pk = [rtp.parse(d) for d in datagrams]
-        if len(pk) != len(idx):
-            raise ValueError(f"{len(pk)} datagrams for {len(idx)} named slots")
-        if self.ts_bits != 32:
-            raise ValueError("feed_rtp: RTP timestamps are 32 bits wide (ts_bits = 32)")
         types = {pt: (8000, e) for pt, e in rtp.STATIC_PAYLOAD_TYPES.items()}
-        for pt, f in (payload_types or {}).items():
-            types[pt] = _format(f)
-        ssrc = {}
-        for s, p in zip(idx, pk):
-            f = types.get(p.payload_type)
-            if f not in self.formats:
-                raise ValueError(f"slot {s}: RTP payload type {p.payload_type} maps to none of this scorer's formats {self.formats}")
-            if f[0] != self._rates[self._rate_of[s]]:
-                raise ValueError(f"slot {s}: RTP payload type {p.payload_type} is {f[0]} Hz, the slot is at "
-                                 f"{self._rates[self._rate_of[s]]} Hz")
-            mine = ssrc.setdefault(s, int(self._b.ssrc[s]) if self._b.ssrc[s] >= 0 else p.ssrc)
-            if p.ssrc != mine:
-                raise ValueError(f"slot {s}: SSRC {p.ssrc:#010x} is not the session's {mine:#010x}")
-        res = self.feed([p.payload for p in pk], idx, [p.timestamp for p in pk], score=score, _seqs=[p.seq for p in pk],
-                        encodings=[types[p.payload_type][1] for p in pk])
-        for s, v in ssrc.items():
-            self._b.ssrc[s] = v
-        return res
+        types.update((pt, _format(f)) for pt, f in (payload_types or {}).items())
+        return types
+
+    def _rtp_encoding(self, s, pt, types):
+        f, mine = types.get(pt), self._rates[self._rate_of[s]]
+        if f not in self.formats:
+            raise ValueError(f"slot {s}: RTP payload type {pt} maps to none of this scorer's formats {self.formats}")
+        if f[0] != mine:
+            raise ValueError(f"slot {s}: RTP payload type {pt} is {f[0]} Hz, the slot is at {mine} Hz")
+        return f[1]
 
     def _run(self, plan, pay):
         l, S, Js, nr = lib(), self.S, self.Js, len(self._rates)
@@ -954,34 +924,12 @@ class MixedJitterScorer(JitterScorer):
         return dict(resampler=FILTER_ID, jitter=JITTER_FORMAT, jitter_conceal=self.conceal, jitter_mixed=1)
 
     def export_slots(self, slots):
-        """``JitterScorer.export_slots`` with ``jitter_ring`` (n, widest lookback + depth of this scorer's rates), zeros
-        beyond each session's own columns, the per-session ``jitter_rate`` ((n,) int64, Hz) and ``jitter_params`` ((n, 3)
+        """``JitterScorer.export_slots`` with the per-session ``jitter_rate`` ((n,) int64, Hz) and ``jitter_params`` ((n, 3)
         int64: depth, period, fade in the session's own rate).  No byte of the scorer changes."""
         idx = self.scorer._slot_list(slots, ordered=True)
-        st = self.scorer.export_slots(idx)
-        dev, b = self.device, self._b
         ri = self._rate_of[idx]
-        lb, J = self._rlookback[ri], self._rJ[ri]
-        width = int((self._rlookback + self._rdepth).max())
-        with _on(dev):
-            nxt, held = torch.from_numpy(b.next[idx]), torch.from_numpy(b.hi[idx] - b.next[idx])
-            k = torch.arange(width)
-            cols = (nxt[:, None] - torch.from_numpy(lb)[:, None] + k) % torch.from_numpy(J)[:, None]
-            jr = self.jring[rows_on(idx, dev)[:, None], cols.to(dev)]
-            jr.masked_fill_((k[None, :] >= (torch.from_numpy(lb) + held)[:, None]).to(dev), 0.0)
-        ivs = [b.intervals(s) for s in idx]
-        K = max([len(v) for v in ivs] + [1])
-        table = np.full((len(idx), K, 2), -1, dtype=np.int64)
-        for i, v in enumerate(ivs):
-            if v:
-                table[i, :len(v)] = v
-        book = np.stack([getattr(b, f)[idx] for f in _BOOK], axis=1).reshape(len(idx), len(_BOOK))
-        stats = np.stack([getattr(b, f)[idx] for f in _COUNTERS], axis=1).reshape(len(idx), len(_COUNTERS))
         params = np.stack([self._rdepth[ri], self._rP[ri], self._rF[ri]], axis=1).reshape(len(idx), 3)
-        return wrap(st, self._meta(), jitter_pending=export_pending(self.ring, idx, b.head[idx], b.fill[idx], self.max_pending * self.hop),
-                    jitter_fill=torch.from_numpy(b.fill[idx]), jitter_ring=jr, jitter_book=torch.from_numpy(book),
-                    jitter_stats=torch.from_numpy(stats), jitter_intervals=torch.from_numpy(table),
-                    jitter_rate=torch.from_numpy(self._rrate[ri]), jitter_params=torch.from_numpy(params))
+        return self._export(idx, jitter_rate=torch.from_numpy(self._rrate[ri]), jitter_params=torch.from_numpy(params))
 
     def import_slots(self, slots, state):
         """The named slots take over the sessions of ``state``, each at its own rate: a state of a MixedJitterScorer, or of a

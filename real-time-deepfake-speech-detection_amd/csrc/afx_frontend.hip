@@ -1082,13 +1082,16 @@ const char* launch_ingest_pop(const float* ring, int S, int ring_len, const int*
 }
 
 // ---------------------------------------------------------------------------------
-// Jitter buffer (afx/jitter.py; the functions are stated in include/afx.h afx_k_jitter_place / _conceal / _release): one
-// DECODED reorder ring per slot, jring (S, J) fp32, input-rate sample i of the slot's played-out stream E at column i mod J.
+// Jitter buffer (afx/jitter.py; the functions are stated in include/afx.h afx_k_jitter_place / _conceal / _release and their
+// _mixed / _rates forms): one DECODED reorder ring per slot, jring (S, Js) fp32.  A slot has a RATE: its filter (taps, L, M, T),
+// its ring length J <= Js, its repeat period P, fade length F and fade table.  Input-rate sample i of the slot's played-out
+// stream E sits at column i mod J of its row; the slot uses the columns [0, J) only and never touches one at or beyond J.
 // The host keeps every index (playout point `next`, received intervals, gaps) and plans rounds so that, with
 // lookback = max(T - 1, P + F) and W = J - lookback, every launch of a round that has released E up to `cur` touches only
 // indices in [cur - lookback, cur + W): a window of J consecutive indices, so no two of them share a column.  That is the
 // sizing invariant: what place writes at i >= cur destroys only i - J < cur - lookback, which neither the filter (T - 1
 // samples back) nor a fading gap (source [a - P, a), read until a + F) will read again.
+// Three verbs, one kernel and one row body each:
 //   place:   decodes sub-ranges of packets into their columns (the rows of one launch are disjoint: the host splits a packet
 //            at the playout point and at what was received before; first arrival wins).
 //   conceal: writes a released gap's samples INTO the ring (zeros, or the faded repetition of the P samples before the
@@ -1096,14 +1099,48 @@ const char* launch_ingest_pop(const float* ring, int S, int ring_len, const int*
 //            ordered by the host: one launch per rank of gap within the slot.
 //   release: polyphase_tiles (above) with the source = ring[(a0 + k) mod J], k >= -(T-1), and the sink = the slot's pending
 //            16 kHz ring: outputs n_done .. of the stream, each with the bits afx_k_resample gives it over all of E.
+// The rates of a launch (at most JIT_MAX_RATES) travel by value in the argument struct; a row names its rate by an index, the
+// last int of its header, or, in a launch whose rows carry none (the one-rate entry points: a table of one entry, Js = J), is
+// at rate 0.  A workgroup reads its row's entry (the index made wave-uniform, so the entry is scalar loads from the kernel
+// arguments) and runs the row body with that rate's values; the branch on the tap placement is uniform per workgroup.
 // ---------------------------------------------------------------------------------
-constexpr int JIT_PLACE_HDR = 4;    // ints per row: slot, byte offset of the first sample, n, ring column of the first sample
-constexpr int JIT_PLACE_MIXED_HDR = 5;  // the same four, then the row's encoding (afx_k_jitter_place_mixed)
-constexpr int JIT_CONCEAL_HDR = 4;  // ints per row: slot, ring column of the gap origin a, d_lo, d_hi
-constexpr int JIT_RELEASE_HDR = 8;  // ints per row: slot, ring column of a0, n_in, n_out, p0, d0, wpos, 0
+constexpr int JIT_MAX_RATES = 16;
+// ints per row.  place: slot, byte offset of the first sample, n, ring column of the first sample [, encoding [, rate index]];
+// conceal: slot, ring column of the gap origin a, d_lo, d_hi [, rate index]; release: slot, ring column of a0, n_in, n_out,
+// p0, d0, wpos, rate index (read only where the launch says its rows carry one)
+constexpr int JIT_PLACE_HDR = 4, JIT_PLACE_MIXED_HDR = 5, JIT_PLACE_RATES_HDR = 6;
+constexpr int JIT_CONCEAL_HDR = 4, JIT_CONCEAL_RATES_HDR = 5;
+constexpr int JIT_RELEASE_HDR = 8;
+
+struct JitterRate {
+  PolyFilter f;                  // Tp, R from poly_grid (release only)
+  const float* fade;             // (max(F, 1),) fp32 (conceal only)
+  int J, P, F, lds_taps;
+  int max_out;                   // release: the largest n_out the launch was shaped for (a row beyond it writes nothing)
+};
+
+struct JitterRatesArgs {
+  const unsigned char* stage;    // place
+  long long stage_bytes;
+  const int* hdr;                // (rows, hdr_ints)
+  float* jring;                  // (S, Js)
+  float* ring;                   // release: (S, ring_len) pending 16 kHz samples
+  int S, Js, ring_len, nr, mode;
+  int hdr_ints;                  // the row stride
+  int enc;                       // place: the encoding of rows of JIT_PLACE_HDR ints (longer rows name their own, the fifth int)
+  int rated;                     // the last int of a row is its rate index (else every row is at rate 0)
+  JitterRate r[JIT_MAX_RATES];
+};
+
+// the calling workgroup's row and its rate index (the caller checks its range)
+__device__ __forceinline__ const int* jitter_row(const JitterRatesArgs& m, int& ri) {
+  const int* h = m.hdr + (long long)blockIdx.y * m.hdr_ints;
+  ri = m.rated ? __builtin_amdgcn_readfirstlane(h[m.hdr_ints - 1]) : 0;
+  return h;
+}
 
 // one row of a place launch: h[0..3] = slot, byte offset, n, column; enc the row's encoding (validated by the caller); the
-// slot's ring is the first J columns of a row of `stride` floats (stride = J but for a scorer of several rates)
+// slot's ring is the first J columns of a row of `stride` floats
 __device__ __forceinline__ void jitter_place_row(const unsigned char* __restrict__ stage, long long stage_bytes, const int* h, int enc,
                                                  float* __restrict__ jring, int S, int J, int stride) {
   const int slot = h[0], n = h[2], col = h[3];
@@ -1120,45 +1157,13 @@ __device__ __forceinline__ void jitter_place_row(const unsigned char* __restrict
   }
 }
 
-__global__ __launch_bounds__(256) void jitter_place_kernel(const unsigned char* __restrict__ stage, long long stage_bytes,
-                                                           const int* __restrict__ hdr, int enc, float* __restrict__ jring,
-                                                           int S, int J) {
-  jitter_place_row(stage, stage_bytes, hdr + (long long)blockIdx.y * JIT_PLACE_HDR, enc, jring, S, J, J);
-}
-
-// the same with the encoding read per row (the fifth int of a JIT_PLACE_MIXED_HDR row); a row with a bad one is skipped whole
-__global__ __launch_bounds__(256) void jitter_place_mixed_kernel(const unsigned char* __restrict__ stage, long long stage_bytes,
-                                                                 const int* __restrict__ hdr, float* __restrict__ jring, int S,
-                                                                 int J) {
-  const int* h = hdr + (long long)blockIdx.y * JIT_PLACE_MIXED_HDR;
-  const int enc = h[4];
-  if (enc < 0 || enc > 3) return;
-  jitter_place_row(stage, stage_bytes, h, enc, jring, S, J, J);
-}
-
-const char* launch_jitter_place(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n, int enc,
-                                float* jring, int S, int J, hipStream_t s) {
-  if (!stage || !hdr || !jring || stage_bytes <= 0) return "jitter_place: null staging buffer, header table or ring";
-  if (enc < 0 || enc > 3) return "jitter_place: encoding 0 (pcm_f32le), 1 (pcm_s16le), 2 (mulaw) or 3 (alaw)";
-  if (rows <= 0 || rows > 65535) return "jitter_place: 1 to 65535 rows";
-  if (S <= 0 || J <= 0 || max_n < 0 || max_n > J) return "jitter_place: a row's samples must fit its slot's ring";
-  if (max_n == 0) return nullptr;
-  hipLaunchKernelGGL(jitter_place_kernel, dim3(min((max_n + 255) / 256, 64), rows), dim3(256), 0, s,
-                     (const unsigned char*)stage, stage_bytes, hdr, enc, jring, S, J);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? nullptr : hipGetErrorString(e);
-}
-
-const char* launch_jitter_place_mixed(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n, float* jring,
-                                      int S, int J, hipStream_t s) {
-  if (!stage || !hdr || !jring || stage_bytes <= 0) return "jitter_place_mixed: null staging buffer, header table or ring";
-  if (rows <= 0 || rows > 65535) return "jitter_place_mixed: 1 to 65535 rows";
-  if (S <= 0 || J <= 0 || max_n < 0 || max_n > J) return "jitter_place_mixed: a row's samples must fit its slot's ring";
-  if (max_n == 0) return nullptr;
-  hipLaunchKernelGGL(jitter_place_mixed_kernel, dim3(min((max_n + 255) / 256, 64), rows), dim3(256), 0, s,
-                     (const unsigned char*)stage, stage_bytes, hdr, jring, S, J);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+// a row with a bad encoding or rate index is skipped whole
+__global__ __launch_bounds__(256) void jitter_place_kernel(JitterRatesArgs m) {
+  int ri;
+  const int* h = jitter_row(m, ri);
+  const int enc = m.hdr_ints > JIT_PLACE_HDR ? h[4] : m.enc;
+  if (enc < 0 || enc > 3 || ri < 0 || ri >= m.nr) return;
+  jitter_place_row(m.stage, m.stage_bytes, h, enc, m.jring, m.S, m.r[ri].J, m.Js);
 }
 
 // E[a + d] for d in [d_lo, d_hi): 0 (mode 0, or d >= F), else fade[d] * E[a - P + d mod P] (one fp32 multiply of two stored
@@ -1181,33 +1186,12 @@ __device__ __forceinline__ void jitter_conceal_row(float* __restrict__ jring, in
   }
 }
 
-__global__ __launch_bounds__(256) void jitter_conceal_kernel(float* __restrict__ jring, int S, int J, const int* __restrict__ hdr,
-                                                             const float* __restrict__ fade, int P, int F, int mode) {
-  jitter_conceal_row(jring, S, J, J, hdr + (long long)blockIdx.y * JIT_CONCEAL_HDR, fade, P, F, mode);
+__global__ __launch_bounds__(256) void jitter_conceal_kernel(JitterRatesArgs m) {
+  int ri;
+  const int* h = jitter_row(m, ri);
+  if (ri < 0 || ri >= m.nr) return;
+  jitter_conceal_row(m.jring, m.S, m.r[ri].J, m.Js, h, m.r[ri].fade, m.r[ri].P, m.r[ri].F, m.mode);
 }
-
-const char* launch_jitter_conceal(float* jring, int S, int J, const int* hdr, int rows, int max_n, const float* fade, int P,
-                                  int F, int mode, hipStream_t s) {
-  if (!jring || !hdr) return "jitter_conceal: null ring or header table";
-  if (mode != 0 && mode != 1) return "jitter_conceal: mode 0 (zero) or 1 (repeat)";
-  if (mode == 1 && (!fade || P <= 0 || F < 0)) return "jitter_conceal: repeat needs a fade table, a period and a fade length";
-  if (rows <= 0 || rows > 65535) return "jitter_conceal: 1 to 65535 rows";
-  if (mode == 0) { P = 0; F = 0; }
-  if (S <= 0 || J <= 0 || max_n < 0 || (long long)max_n + P > J) return "jitter_conceal: a row's samples and its source must fit the ring";
-  if (max_n == 0) return nullptr;
-  hipLaunchKernelGGL(jitter_conceal_kernel, dim3(min((max_n + 255) / 256, 64), rows), dim3(256), 0, s, jring, S, J, hdr, fade,
-                     P, F, mode);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? nullptr : hipGetErrorString(e);
-}
-
-struct JitterReleaseArgs {
-  const float* jring;            // (S, J) decoded input-rate samples
-  const int* hdr;                // (rows, JIT_RELEASE_HDR)
-  PolyFilter f;
-  float* ring;                   // (S, ring_len) pending 16 kHz samples
-  int J, S, ring_len;
-};
 
 // sample k of the released range that starts at ring column col0 (zeros past its end: never reached by an output the host
 // counted); k >= -(T-1) >= -J and k < n_in <= J, so one wrap either way
@@ -1221,221 +1205,177 @@ struct RingSource {
   }
 };
 
+// one row of a release launch at a rate with filter f and ring length J: the identity copies, the others are polyphase_tiles
 template <bool IDENT, bool LDS_TAPS>
-__global__ __launch_bounds__(256) void jitter_release_kernel(JitterReleaseArgs a) {
-  const int* h = a.hdr + (long long)blockIdx.y * JIT_RELEASE_HDR;
+__device__ __forceinline__ void jitter_release_row(const JitterRatesArgs& m, const PolyFilter& f, int J, const int* h) {
   const int slot = h[0], col0 = h[1], n_in = h[2], n_out = h[3], p0 = h[4], d0 = h[5], wpos = h[6];
-  if (!(slot >= 0 && slot < a.S && col0 >= 0 && col0 < a.J && n_in >= 0 && n_in <= a.J && n_out >= 0 && n_out <= a.ring_len &&
-        wpos >= 0 && wpos < a.ring_len && p0 >= 0 && p0 < a.f.L && d0 >= 0))
+  if (!(slot >= 0 && slot < m.S && col0 >= 0 && col0 < J && n_in >= 0 && n_in <= J && n_out >= 0 && n_out <= m.ring_len &&
+        wpos >= 0 && wpos < m.ring_len && p0 >= 0 && p0 < f.L && d0 >= 0))
     return;
-  const float* src = a.jring + (long long)slot * a.J;
-  float* out = a.ring + (long long)slot * a.ring_len;
+  const float* src = m.jring + (long long)slot * m.Js;
+  float* out = m.ring + (long long)slot * m.ring_len;
   if (IDENT) {
-    for (int r = 0; r < a.f.R; ++r) {
-      const int k = (blockIdx.x * a.f.R + r) * RS_TILE + threadIdx.x;
+    for (int r = 0; r < f.R; ++r) {
+      const int k = (blockIdx.x * f.R + r) * RS_TILE + threadIdx.x;
       if (k >= n_out || k >= n_in) break;
       const int c = col0 + k, w = wpos + k;
-      out[w < a.ring_len ? w : w - a.ring_len] = src[c < a.J ? c : c - a.J];
+      out[w < m.ring_len ? w : w - m.ring_len] = src[c < J ? c : c - J];
     }
     return;
   }
-  if ((long long)blockIdx.x * a.f.R * RS_TILE >= n_out) return;
-  polyphase_tiles<LDS_TAPS>(a.f, n_out, p0, d0, RingSource{src, col0, a.J, n_in}, RingSink{out, wpos, a.ring_len});
+  if ((long long)blockIdx.x * f.R * RS_TILE >= n_out) return;  // (beyond the row's outputs: nothing is staged)
+  polyphase_tiles<LDS_TAPS>(f, n_out, p0, d0, RingSource{src, col0, J, n_in}, RingSink{out, wpos, m.ring_len});
 }
 
-const char* launch_jitter_release(const float* jring, int S, int J, const int* hdr, int rows, int max_out, const float* taps,
-                                  int L, int M, int T, float* ring, int ring_len, hipStream_t s) {
-  if (!jring || !hdr || !ring) return "jitter_release: null ring or header table";
-  if (rows <= 0 || rows > 65535) return "jitter_release: 1 to 65535 rows";
-  if (S <= 0 || J <= 0 || ring_len <= 0 || max_out < 0 || max_out > ring_len) return "jitter_release: a row's outputs must fit its slot's ring";
-  if (L <= 0 || M <= 0 || T <= 0) return "jitter_release: bad filter shape";
-  const bool ident = taps == nullptr;
-  if (ident && (L != 1 || M != 1 || T != 1)) return "jitter_release: no taps is the identity (L = M = T = 1)";
-  if (T - 1 > J) return "jitter_release: the filter history must fit the ring";
-  if (max_out == 0) return nullptr;
-  JitterReleaseArgs a{};
-  a.jring = jring; a.hdr = hdr; a.f = PolyFilter{taps, L, M, T, 0, 0}; a.ring = ring;
-  a.J = J; a.S = S; a.ring_len = ring_len;
-  PolyGrid g;
-  if (!poly_grid(a.f, ident, max_out, g)) return "jitter_release: input / output ratio above 12";
-  const dim3 grid((unsigned)g.gx, rows);
-  if (ident) hipLaunchKernelGGL((jitter_release_kernel<true, false>), grid, dim3(256), g.lds, s, a);
-  else if (g.lds_taps) hipLaunchKernelGGL((jitter_release_kernel<false, true>), grid, dim3(256), g.lds, s, a);
-  else hipLaunchKernelGGL((jitter_release_kernel<false, false>), grid, dim3(256), g.lds, s, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? nullptr : hipGetErrorString(e);
-}
-
-// ---------------------------------------------------------------------------------
-// Jitter buffer over slots of different clock rates (afx/jitter.py MixedJitterScorer; include/afx.h afx_k_jitter_place_rates /
-// _conceal_rates / _release_rates): the rate (taps, L, M, T, its ring length J, repeat period P, fade length F and fade table)
-// is a per-row value, the last int of the row's header, instead of a launch-wide one.  jring is (S, Js), Js >= every rate's J:
-// a slot at rate f uses the first J_f columns of its row with modulus J_f and never a column at or beyond J_f.  The table of a
-// scorer's rates (at most JIT_MAX_RATES) travels by value in the argument struct; a workgroup reads its row's entry (the index
-// made wave-uniform, so the entry is scalar loads from the kernel arguments) and runs jitter_place_row / jitter_conceal_row /
-// jitter_release_row with that rate's values: the same validation, decoder, multiply and tile body, so every value is
-// the one a one-rate launch gives it.  The branch on the tap placement is uniform per workgroup.
-// ---------------------------------------------------------------------------------
-constexpr int JIT_MAX_RATES = 16;
-constexpr int JIT_PLACE_RATES_HDR = 6;    // a JIT_PLACE_MIXED_HDR row, then the row's rate index
-constexpr int JIT_CONCEAL_RATES_HDR = 5;  // a JIT_CONCEAL_HDR row, then the row's rate index
-                                          // (a release row is JIT_RELEASE_HDR ints: its eighth is the rate index)
-
-struct JitterRate {
-  PolyFilter f;                  // Tp, R from poly_grid (release only)
-  const float* fade;             // (max(F, 1),) fp32 (conceal only)
-  int J, P, F, lds_taps;
-  int max_out;                   // release: the largest n_out the launch was shaped for (a row beyond it writes nothing)
-};
-
-struct JitterRatesArgs {
-  const unsigned char* stage;    // place
-  long long stage_bytes;
-  const int* hdr;
-  float* jring;                  // (S, Js)
-  float* ring;                   // release: (S, ring_len)
-  int S, Js, ring_len, nr, mode;
-  JitterRate r[JIT_MAX_RATES];
-};
-
-__global__ __launch_bounds__(256) void jitter_place_rates_kernel(JitterRatesArgs m) {
-  const int* h = m.hdr + (long long)blockIdx.y * JIT_PLACE_RATES_HDR;
-  const int enc = h[4], ri = __builtin_amdgcn_readfirstlane(h[5]);
-  if (enc < 0 || enc > 3 || ri < 0 || ri >= m.nr) return;
-  jitter_place_row(m.stage, m.stage_bytes, h, enc, m.jring, m.S, m.r[ri].J, m.Js);
-}
-
-__global__ __launch_bounds__(256) void jitter_conceal_rates_kernel(JitterRatesArgs m) {
-  const int* h = m.hdr + (long long)blockIdx.y * JIT_CONCEAL_RATES_HDR;
-  const int ri = __builtin_amdgcn_readfirstlane(h[4]);
-  if (ri < 0 || ri >= m.nr) return;
-  jitter_conceal_row(m.jring, m.S, m.r[ri].J, m.Js, h, m.r[ri].fade, m.r[ri].P, m.r[ri].F, m.mode);
-}
-
-// jitter_release_kernel's row with the ring's row stride apart from its modulus: the same checks against a.J (the row's
-// J_f), the same copy, the same call of polyphase_tiles.  (The one-rate kernel keeps its own text: routed through this function
-// the compiler allocates its registers differently, and its instructions are to stay as they were.)
-template <bool IDENT, bool LDS_TAPS>
-__device__ __forceinline__ void jitter_release_row(const JitterReleaseArgs& a, const int* h, int stride) {
-  const int slot = h[0], col0 = h[1], n_in = h[2], n_out = h[3], p0 = h[4], d0 = h[5], wpos = h[6];
-  if (!(slot >= 0 && slot < a.S && col0 >= 0 && col0 < a.J && n_in >= 0 && n_in <= a.J && n_out >= 0 && n_out <= a.ring_len &&
-        wpos >= 0 && wpos < a.ring_len && p0 >= 0 && p0 < a.f.L && d0 >= 0))
-    return;
-  const float* src = a.jring + (long long)slot * stride;
-  float* out = a.ring + (long long)slot * a.ring_len;
-  if (IDENT) {
-    for (int r = 0; r < a.f.R; ++r) {
-      const int k = (blockIdx.x * a.f.R + r) * RS_TILE + threadIdx.x;
-      if (k >= n_out || k >= n_in) break;
-      const int c = col0 + k, w = wpos + k;
-      out[w < a.ring_len ? w : w - a.ring_len] = src[c < a.J ? c : c - a.J];
-    }
-    return;
-  }
-  if ((long long)blockIdx.x * a.f.R * RS_TILE >= n_out) return;  // (beyond the row's outputs: nothing is staged)
-  polyphase_tiles<LDS_TAPS>(a.f, n_out, p0, d0, RingSource{src, col0, a.J, n_in}, RingSink{out, wpos, a.ring_len});
-}
-
-__global__ __launch_bounds__(256) void jitter_release_rates_kernel(JitterRatesArgs m) {
-  const int* h = m.hdr + (long long)blockIdx.y * JIT_RELEASE_HDR;
-  const int ri = __builtin_amdgcn_readfirstlane(h[7]);
+// a row with a bad rate index, or with more outputs than the launch was shaped for at its rate, writes nothing
+__global__ __launch_bounds__(256) void jitter_release_kernel(JitterRatesArgs m) {
+  int ri;
+  const int* h = jitter_row(m, ri);
   if (ri < 0 || ri >= m.nr || h[3] > m.r[ri].max_out) return;
-  JitterReleaseArgs a;
-  a.jring = m.jring; a.hdr = m.hdr; a.f = m.r[ri].f; a.ring = m.ring; a.J = m.r[ri].J; a.S = m.S; a.ring_len = m.ring_len;
-  if (!a.f.taps) jitter_release_row<true, false>(a, h, m.Js);
-  else if (m.r[ri].lds_taps) jitter_release_row<false, true>(a, h, m.Js);
-  else jitter_release_row<false, false>(a, h, m.Js);
+  const PolyFilter f = m.r[ri].f;
+  if (!f.taps) jitter_release_row<true, false>(m, f, m.r[ri].J, h);
+  else if (m.r[ri].lds_taps) jitter_release_row<false, true>(m, f, m.r[ri].J, h);
+  else jitter_release_row<false, false>(m, f, m.r[ri].J, h);
 }
 
-static const char* jitter_rates_msg(const char* who, const char* what) {
+enum JitterVerb { JIT_PLACE, JIT_CONCEAL, JIT_RELEASE };
+
+static const char* jitter_msg(const char* who, const char* what) {
   static thread_local char msg[160];
   snprintf(msg, sizeof msg, "%s: %s", who, what);
   return msg;
 }
 
-// the rate table of a launch as the kernels take it, or the refusal; mode < 0: a launch that does not conceal.  max_out
-// (release only): the per-rate largest n_out, whose grids go to g
-static const char* jitter_rates_table(const char* who, const JitterRateDesc* rates, int n_rates, int Js, int mode, const int* max_out,
-                                      JitterRatesArgs& m, PolyGrid* g) {
-  if (n_rates < 1 || n_rates > JIT_MAX_RATES) return jitter_rates_msg(who, "1 to 16 rates");
-  if (!rates) return jitter_rates_msg(who, "null rate table");
-  if (Js <= 0) return jitter_rates_msg(who, "a rate's ring must fit the ring's rows (1 <= J <= Js)");
+// The launch of a verb for the entry point `who`: every check (a refusal carries who's name, and nothing is launched), the rate
+// table as the kernels take it, the grid.  m comes with the verb's buffers, S, Js, ring_len, mode and the row layout set.
+// most: place / conceal: one int, the largest row of the launch; release: per rate the largest n_out (n_rates ints).
+static const char* jitter_launch(const char* who, JitterVerb verb, JitterRatesArgs m, const JitterRateDesc* rates, int n_rates,
+                                 int rows, const int* most, hipStream_t s) {
+  const bool repeat = verb == JIT_CONCEAL && m.mode == 1;
+  const char* fit = verb == JIT_PLACE ? "a row's samples must fit its slot's ring"
+                  : verb == JIT_CONCEAL ? "a row's samples and its source must fit the ring" : "a row's outputs must fit its slot's ring";
+  if (verb == JIT_CONCEAL && m.mode != 0 && m.mode != 1) return jitter_msg(who, "mode 0 (zero) or 1 (repeat)");
+  if (verb == JIT_PLACE && m.hdr_ints == JIT_PLACE_HDR && (m.enc < 0 || m.enc > 3))
+    return jitter_msg(who, "encoding 0 (pcm_f32le), 1 (pcm_s16le), 2 (mulaw) or 3 (alaw)");
+  if (n_rates < 1 || n_rates > JIT_MAX_RATES) return jitter_msg(who, "1 to 16 rates");
+  if (!rates) return jitter_msg(who, "null rate table");
+  if (!most) return jitter_msg(who, "null output counts");
+  if (!m.hdr || !m.jring || (verb == JIT_PLACE && (!m.stage || m.stage_bytes <= 0)) || (verb == JIT_RELEASE && !m.ring))
+    return jitter_msg(who, verb == JIT_PLACE ? "null staging buffer, header table or ring" : "null ring or header table");
+  if (rows <= 0 || rows > 65535) return jitter_msg(who, "1 to 65535 rows");
+  // (a launch without rate indices has one rate whose ring is the whole row: a bad J there is a row that does not fit)
+  const char* ring_fit = m.rated ? "a rate's ring must fit the ring's rows (1 <= J <= Js)" : fit;
+  if (m.Js <= 0) return jitter_msg(who, ring_fit);
+  if (m.S <= 0 || (verb == JIT_RELEASE ? m.ring_len <= 0 : most[0] < 0)) return jitter_msg(who, fit);
+  bool fits = false;  // place / conceal: some rate can hold the largest row
+  long long gx = 0;   // release: the largest grid and dynamic LDS over the rates present
+  size_t lds = 0;
   for (int i = 0; i < n_rates; ++i) {
     const JitterRateDesc& d = rates[i];
-    if (d.L <= 0 || d.M <= 0 || d.T <= 0) return jitter_rates_msg(who, "bad filter shape");
+    if (d.L <= 0 || d.M <= 0 || d.T <= 0) return jitter_msg(who, "bad filter shape");
     const bool ident = d.taps == nullptr;
-    if (ident && (d.L != 1 || d.M != 1 || d.T != 1)) return jitter_rates_msg(who, "bad filter shape (no taps is the identity, L = M = T = 1)");
-    if (d.J <= 0 || d.J > Js) return jitter_rates_msg(who, "a rate's ring must fit the ring's rows (1 <= J <= Js)");
-    if (d.T - 1 > d.J) return jitter_rates_msg(who, "the filter history must fit the rate's ring");
-    if (mode == 1 && (!d.fade || d.P <= 0 || d.F < 0)) return jitter_rates_msg(who, "repeat needs a fade table, a period and a fade length");
+    if (ident && (d.L != 1 || d.M != 1 || d.T != 1)) return jitter_msg(who, "bad filter shape (no taps is the identity, L = M = T = 1)");
+    if (d.J <= 0 || d.J > m.Js) return jitter_msg(who, ring_fit);
+    if (d.T - 1 > d.J) return jitter_msg(who, "the filter history must fit the rate's ring");
+    if (repeat && (!d.fade || d.P <= 0 || d.F < 0)) return jitter_msg(who, "repeat needs a fade table, a period and a fade length");
     JitterRate& r = m.r[i];
     r.f = PolyFilter{d.taps, d.L, d.M, d.T, 0, 0};
-    r.fade = d.fade; r.J = d.J; r.P = mode == 1 ? d.P : 0; r.F = mode == 1 ? d.F : 0; r.lds_taps = 0;
-    PolyGrid pg;
-    if (!poly_grid(r.f, ident, max_out && max_out[i] > 0 ? max_out[i] : 0, pg)) return jitter_rates_msg(who, "input / output ratio above 12");
-    r.lds_taps = pg.lds_taps;
-    r.max_out = max_out && max_out[i] > 0 ? max_out[i] : 0;
-    if (g) g[i] = pg;
+    r.fade = d.fade; r.J = d.J; r.P = repeat ? d.P : 0; r.F = repeat ? d.F : 0;
+    r.max_out = verb == JIT_RELEASE && most[i] > 0 ? most[i] : 0;
+    PolyGrid g;
+    if (!poly_grid(r.f, ident, r.max_out, g)) return jitter_msg(who, "input / output ratio above 12");
+    r.lds_taps = g.lds_taps;
+    if (verb != JIT_RELEASE) {
+      fits = fits || (long long)most[0] + r.P <= d.J;
+    } else {
+      if (most[i] < 0 || most[i] > m.ring_len) return jitter_msg(who, fit);
+      if (r.max_out > 0) {
+        gx = g.gx > gx ? g.gx : gx;
+        lds = g.lds > lds ? g.lds : lds;
+      }
+    }
   }
-  m.nr = n_rates; m.Js = Js; m.mode = mode;
-  return nullptr;
-}
-
-const char* launch_jitter_place_rates(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n,
-                                      const JitterRateDesc* rates, int n_rates, float* jring, int S, int Js, hipStream_t s) {
-  const char* who = "jitter_place_rates";
-  JitterRatesArgs m{};
-  if (const char* e = jitter_rates_table(who, rates, n_rates, Js, -1, nullptr, m, nullptr)) return e;
-  if (!stage || !hdr || !jring || stage_bytes <= 0) return jitter_rates_msg(who, "null staging buffer, header table or ring");
-  if (rows <= 0 || rows > 65535) return jitter_rates_msg(who, "1 to 65535 rows");
-  if (S <= 0 || max_n < 0 || max_n > Js) return jitter_rates_msg(who, "a row's samples must fit its slot's ring");
-  if (max_n == 0) return nullptr;
-  m.stage = (const unsigned char*)stage; m.stage_bytes = stage_bytes; m.hdr = hdr; m.jring = jring; m.S = S;
-  hipLaunchKernelGGL(jitter_place_rates_kernel, dim3(min((max_n + 255) / 256, 64), rows), dim3(256), 0, s, m);
+  m.nr = n_rates;
+  if (verb != JIT_RELEASE) {
+    if (!fits) return jitter_msg(who, fit);
+    gx = min((most[0] + 255) / 256, 64);
+  }
+  if (gx == 0) return nullptr;  // no samples to place or conceal, no outputs to release
+  const dim3 grid((unsigned)gx, rows);
+  if (verb == JIT_PLACE) hipLaunchKernelGGL(jitter_place_kernel, grid, dim3(256), 0, s, m);
+  else if (verb == JIT_CONCEAL) hipLaunchKernelGGL(jitter_conceal_kernel, grid, dim3(256), 0, s, m);
+  else hipLaunchKernelGGL(jitter_release_kernel, grid, dim3(256), lds, s, m);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+static const char* jitter_place_launch(const char* who, const void* stage, long long stage_bytes, const int* hdr, int hdr_ints, int rows,
+                                       int max_n, int enc, const JitterRateDesc* rates, int n_rates, float* jring, int S, int Js,
+                                       hipStream_t s) {
+  JitterRatesArgs m{};
+  m.stage = (const unsigned char*)stage; m.stage_bytes = stage_bytes; m.hdr = hdr; m.jring = jring; m.S = S; m.Js = Js;
+  m.hdr_ints = hdr_ints; m.enc = enc; m.rated = hdr_ints == JIT_PLACE_RATES_HDR;
+  return jitter_launch(who, JIT_PLACE, m, rates, n_rates, rows, &max_n, s);
+}
+
+static const char* jitter_conceal_launch(const char* who, float* jring, int S, int Js, const int* hdr, int hdr_ints, int rows, int max_n,
+                                         const JitterRateDesc* rates, int n_rates, int mode, hipStream_t s) {
+  JitterRatesArgs m{};
+  m.hdr = hdr; m.jring = jring; m.S = S; m.Js = Js; m.mode = mode;
+  m.hdr_ints = hdr_ints; m.rated = hdr_ints == JIT_CONCEAL_RATES_HDR;
+  return jitter_launch(who, JIT_CONCEAL, m, rates, n_rates, rows, &max_n, s);
+}
+
+static const char* jitter_release_launch(const char* who, const float* jring, int S, int Js, const int* hdr, bool rated, int rows,
+                                         const JitterRateDesc* rates, int n_rates, const int* max_out, float* ring, int ring_len,
+                                         hipStream_t s) {
+  JitterRatesArgs m{};
+  m.hdr = hdr; m.jring = const_cast<float*>(jring); m.ring = ring; m.S = S; m.Js = Js; m.ring_len = ring_len;
+  m.hdr_ints = JIT_RELEASE_HDR; m.rated = rated;
+  return jitter_launch(who, JIT_RELEASE, m, rates, n_rates, rows, max_out, s);
+}
+
+// the one-rate entry points: a table of one entry built from their scalar arguments, Js = J, rows without a rate index
+const char* launch_jitter_place(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n, int enc,
+                                float* jring, int S, int J, hipStream_t s) {
+  const JitterRateDesc one{nullptr, nullptr, 1, 1, 1, J, 0, 0};
+  return jitter_place_launch("jitter_place", stage, stage_bytes, hdr, JIT_PLACE_HDR, rows, max_n, enc, &one, 1, jring, S, J, s);
+}
+
+const char* launch_jitter_place_mixed(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n, float* jring,
+                                      int S, int J, hipStream_t s) {
+  const JitterRateDesc one{nullptr, nullptr, 1, 1, 1, J, 0, 0};
+  return jitter_place_launch("jitter_place_mixed", stage, stage_bytes, hdr, JIT_PLACE_MIXED_HDR, rows, max_n, 0, &one, 1,
+                             jring, S, J, s);
+}
+
+const char* launch_jitter_conceal(float* jring, int S, int J, const int* hdr, int rows, int max_n, const float* fade, int P,
+                                  int F, int mode, hipStream_t s) {
+  const JitterRateDesc one{nullptr, fade, 1, 1, 1, J, P, F};
+  return jitter_conceal_launch("jitter_conceal", jring, S, J, hdr, JIT_CONCEAL_HDR, rows, max_n, &one, 1, mode, s);
+}
+
+const char* launch_jitter_release(const float* jring, int S, int J, const int* hdr, int rows, int max_out, const float* taps,
+                                  int L, int M, int T, float* ring, int ring_len, hipStream_t s) {
+  const JitterRateDesc one{taps, nullptr, L, M, T, J, 0, 0};
+  return jitter_release_launch("jitter_release", jring, S, J, hdr, false, rows, &one, 1, &max_out, ring, ring_len, s);
+}
+
+// the _rates entry points: the caller's table, rows that end in their rate index
+const char* launch_jitter_place_rates(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n,
+                                      const JitterRateDesc* rates, int n_rates, float* jring, int S, int Js, hipStream_t s) {
+  return jitter_place_launch("jitter_place_rates", stage, stage_bytes, hdr, JIT_PLACE_RATES_HDR, rows, max_n, 0, rates,
+                             n_rates, jring, S, Js, s);
 }
 
 const char* launch_jitter_conceal_rates(float* jring, int S, int Js, const int* hdr, int rows, int max_n, const JitterRateDesc* rates,
                                         int n_rates, int mode, hipStream_t s) {
-  const char* who = "jitter_conceal_rates";
-  if (mode != 0 && mode != 1) return jitter_rates_msg(who, "mode 0 (zero) or 1 (repeat)");
-  JitterRatesArgs m{};
-  if (const char* e = jitter_rates_table(who, rates, n_rates, Js, mode, nullptr, m, nullptr)) return e;
-  if (!jring || !hdr) return jitter_rates_msg(who, "null ring or header table");
-  if (rows <= 0 || rows > 65535) return jitter_rates_msg(who, "1 to 65535 rows");
-  if (S <= 0 || max_n < 0 || max_n > Js) return jitter_rates_msg(who, "a row's samples and its source must fit the ring");
-  if (max_n == 0) return nullptr;
-  m.hdr = hdr; m.jring = jring; m.S = S;
-  hipLaunchKernelGGL(jitter_conceal_rates_kernel, dim3(min((max_n + 255) / 256, 64), rows), dim3(256), 0, s, m);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+  return jitter_conceal_launch("jitter_conceal_rates", jring, S, Js, hdr, JIT_CONCEAL_RATES_HDR, rows, max_n, rates, n_rates, mode, s);
 }
 
 const char* launch_jitter_release_rates(const float* jring, int S, int Js, const int* hdr, int rows, const JitterRateDesc* rates,
                                         int n_rates, const int* max_out, float* ring, int ring_len, hipStream_t s) {
-  const char* who = "jitter_release_rates";
-  JitterRatesArgs m{};
-  PolyGrid g[JIT_MAX_RATES];
-  if (!max_out) return jitter_rates_msg(who, "null output counts");
-  if (const char* e = jitter_rates_table(who, rates, n_rates, Js, -1, max_out, m, g)) return e;
-  if (!jring || !hdr || !ring) return jitter_rates_msg(who, "null ring or header table");
-  if (rows <= 0 || rows > 65535) return jitter_rates_msg(who, "1 to 65535 rows");
-  if (S <= 0 || ring_len <= 0) return jitter_rates_msg(who, "a row's outputs must fit its slot's ring");
-  long long gx = 0;
-  size_t lds = 0;
-  for (int i = 0; i < n_rates; ++i) {
-    if (max_out[i] < 0 || max_out[i] > ring_len) return jitter_rates_msg(who, "a row's outputs must fit its slot's ring");
-    if (max_out[i] > 0) {
-      gx = g[i].gx > gx ? g[i].gx : gx;
-      lds = g[i].lds > lds ? g[i].lds : lds;
-    }
-  }
-  if (gx == 0) return nullptr;
-  m.hdr = hdr; m.jring = const_cast<float*>(jring); m.ring = ring; m.S = S; m.ring_len = ring_len;
-  hipLaunchKernelGGL(jitter_release_rates_kernel, dim3((unsigned)gx, rows), dim3(256), lds, s, m);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+  return jitter_release_launch("jitter_release_rates", jring, S, Js, hdr, true, rows, rates, n_rates, max_out, ring, ring_len, s);
 }
 
 // ---------------------------------------------------------------------------------

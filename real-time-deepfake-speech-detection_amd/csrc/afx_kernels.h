@@ -178,7 +178,8 @@ const char* launch_ingest_mixed(const void* stage, long long stage_bytes, const 
                                 int n_formats, const int* max_out, float* hist, int Hs, float* ring, int S, int ring_len,
                                 hipStream_t s);
 // jitter buffer (include/afx.h afx_k_jitter_place / _conceal / _release): packet sub-ranges decoded into each slot's reorder
-// ring at their timestamps' columns; released gaps concealed in the ring; released samples resampled into the pending ring
+// ring at their timestamps' columns; released gaps concealed in the ring; released samples resampled into the pending ring.
+// One kernel per verb, which takes a table of rates; these four are its one-entry case (Js = J, rows without a rate index)
 const char* launch_jitter_place(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n, int enc,
                                 float* jring, int S, int J, hipStream_t s);
 // (place with the encoding read per row: rows x 5 int32, the fifth the row's encoding)
@@ -188,8 +189,8 @@ const char* launch_jitter_conceal(float* jring, int S, int J, const int* hdr, in
                                   int F, int mode, hipStream_t s);
 const char* launch_jitter_release(const float* jring, int S, int J, const int* hdr, int rows, int max_out, const float* taps,
                                   int L, int M, int T, float* ring, int ring_len, hipStream_t s);
-// the same three over slots of different clock rates (include/afx.h afx_k_jitter_place_rates / _conceal_rates / _release_rates):
-// rates / max_out are HOST arrays of n_rates entries (JitterRateDesc has the layout of afx_jitter_rate), a row's rate index is
+// the same three kernels over slots of different clock rates (include/afx.h afx_k_jitter_place_rates / _conceal_rates /
+// _release_rates): rates / max_out are HOST arrays of n_rates entries (JitterRateDesc has the layout of afx_jitter_rate), a row's rate index is
 // the last int of its header (place: rows x 6, conceal: rows x 5, release: the eighth of 8), jring is (S, Js), Js >= every J
 struct JitterRateDesc { const float* taps; const float* fade; int L, M, T, J, P, F; };
 const char* launch_jitter_place_rates(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n,

@@ -1,7 +1,9 @@
 """Every slot its own clock rate in one jitter buffer, on the GPU (afx/jitter.py MixedJitterScorer, afx_k_jitter_place_rates /
 _conceal_rates / _release_rates).  The references are what this change leaves alone: the numpy restatement of the played-out
 stream E with the offline ``Resampler`` over it (and float64 upfirdn), and the one-rate ``JitterScorer`` fed a slot's own
-packets in the same calls.  Every comparison is exact but the float64 one, whose bound is tests/test_gpu_jitter.py's."""
+packets in the same calls.  Every comparison is exact but the float64 one, whose bound is tests/test_gpu_jitter.py's.
+The one-rate and the ``_rates`` entry points are one kernel per verb behind two wrappers; the last test drives all seven
+directly against the numpy restatement of tests/test_cpu_jitter_mixed.py."""
 import random
 import struct
 
@@ -514,3 +516,114 @@ def test_feed_rtp_with_static_and_dynamic_payload_types_equals_feed():
         assert len(ta.got[s]) == len(tb.got[s]) >= 4 and torch.equal(torch.cat(ta.got[s]), torch.cat(tb.got[s]))
     assert a.stats()["concealed"].tolist() == [3 * 160, 3 * 320] == b.stats()["concealed"].tolist()
     assert a.stats()["out_of_order"].tolist() == b.stats()["out_of_order"].tolist() and min(a.stats()["out_of_order"].tolist()) >= 2
+
+
+def test_one_rate_entry_points_are_the_rates_kernels_with_a_table_of_one_entry():
+    """The seven entry points driven directly.  Each verb runs through its one-rate entry point and, on a clone of the
+    buffers, through its ``_rates`` entry point with a table of two rates in which the rate under test is entry 1: the
+    whole buffers must come out bit-equal, sentinels included.  Place and conceal must equal the numpy restatement of
+    tests/test_cpu_jitter_mixed.py bit for bit; release the float64 sum over the same fp32 taps within the bound of the
+    float64 comparison above (2e-6 of the largest input).  The rows wrap the ring column and ``wpos``, one has n = 0, one names
+    slot S and must be skipped whole; the three rates take the copy, the LDS-tap and the global-tap path of the release."""
+    import ctypes as C
+    from types import SimpleNamespace
+
+    from afx._lib import JitterRate, call_on, check, lib, ptr
+    from afx.ingest import ENCODINGS, layout, plan as ingest_plan
+    from afx.resample import Resampler
+    from test_cpu_jitter_mixed import NumpyDevice, _packet as packet_of
+    l, S, hop, P, F = lib(), 3, 512, 8, 16
+    R = 2 * hop  # the pending ring
+    rs = {r: Resampler(r) for r in (16000, 8000, 11025)}
+    path = {r: "copy" if x.identity else "lds" if x.L * (x.T | 1) <= 12288 else "global" for r, x in rs.items()}  # poly_grid's rule
+    assert sorted(path.values()) == ["copy", "global", "lds"], path
+    bits = lambda t: t.view(torch.int32)
+    fade_of = lambda n: torch.from_numpy((1.0 - np.arange(max(n, 1), dtype=np.float64) / max(n, 1)).astype(np.float32)).cuda()
+    sentinel = lambda *shape: (torch.arange(int(np.prod(shape)), dtype=torch.int32) + 0x3C000000).view(torch.float32).reshape(shape)
+
+    def both(one, rated, buf):
+        a, b = buf.clone(), buf.clone()
+        one(a)
+        rated(b)
+        torch.cuda.synchronize()
+        assert torch.equal(bits(a), bits(b))
+        return a
+
+    for rate, x in rs.items():
+        g = np.random.default_rng(rate)
+        L, M, T = x.L, x.M, 1 if x.identity else x.T
+        taps = None if x.identity else ptr(x.taps)
+        J = max(T - 1, P + F) + -(-hop * M // L) + 1  # lookback + W at depth 0
+        assert J >= 281 and J + 8 <= R
+        # the table: entry 0 another rate with its own J, P, F and fade; entry 1 the rate under test; Js = J
+        other, fades = rs[8000 if x.identity else 16000], [fade_of(8), fade_of(F)]
+        table = (JitterRate * 2)()
+        for t, y, geo, f in zip(table, (other, x), ((J - 7, 4, 8), (J, P, F)), fades):
+            t.taps, t.fade = None if y.identity else y.taps.data_ptr(), f.data_ptr()
+            t.L, t.M, t.T = y.L, y.M, 1 if y.identity else y.T
+            t.J, t.P, t.F = geo
+        tp = C.cast(table, C.c_void_p)
+        host = SimpleNamespace(_rated=True, jring=sentinel(S, J), _table=table, _fades=[f.cpu() for f in fades], S=S, ring_len=R,
+                               _rate_of=np.ones(S, dtype=np.int64), conceal="repeat")
+        ref = NumpyDevice(host)  # (its ring is host.jring's memory)
+        jr = host.jring.clone().cuda()
+
+        def upload(rows):
+            return torch.from_numpy(np.array(rows, dtype=np.int32)).cuda()
+
+        # ---- place: four encodings through place_mixed, then one launch of afx_k_jitter_place -------------------------------
+        launches = [[(0, "mulaw", 40, J - 3), (1, "alaw", 0, 5), (2, "pcm_s16le", 270, 7), (S, "pcm_f32le", 20, 0)],
+                    [(1, "pcm_f32le", 33, J - 3), (0, "alaw", 17, 50), (2, "mulaw", 0, 9)],
+                    [(2, "pcm_s16le", 64, J - 3), (0, "pcm_s16le", 9, 0), (S, "pcm_s16le", 5, 1)]]
+        for k, rows in enumerate(launches):
+            pay = [packet_of(e, n, g)[0] for _, e, n, _ in rows]
+            offs, total = layout([len(p) for p in pay])
+            stage = np.zeros(total, dtype=np.uint8)
+            for o, p in zip(offs, pay):
+                stage[o:o + len(p)] = np.frombuffer(p, dtype=np.uint8)
+            stage = torch.from_numpy(stage).cuda()
+            r6 = [(s, o, n, c, ENCODINGS.index(e), 1) for (s, e, n, c), o in zip(rows, offs)]
+            most = max(r[2] for r in r6)
+            h6 = upload(r6)
+            if k < 2:
+                h, one = upload([r[:5] for r in r6]), lambda b: check(call_on(b, l.afx_k_jitter_place_mixed, ptr(stage), total, ptr(h), len(r6), most, ptr(b), S, J))
+            else:
+                h, one = upload([r[:4] for r in r6]), lambda b: check(call_on(b, l.afx_k_jitter_place, ptr(stage), total, ptr(h), len(r6), most, ENCODINGS.index("pcm_s16le"), ptr(b), S, J))
+            jr = both(one, lambda b: check(call_on(b, l.afx_k_jitter_place_rates, ptr(stage), total, ptr(h6), len(r6), most, tp, 2, ptr(b), S, J)), jr)
+            ref.run(SimpleNamespace(ops=[("place", np.array([r for r in r6 if r[0] < S and r[2] > 0], dtype=np.int32), most)]), pay)
+            assert torch.equal(bits(jr.cpu()), bits(host.jring)), (rate, "place", k)
+        # ---- conceal: repeat (a wrap, beyond the fade, n = 0, slot S), then zero over more than one block ------------------------
+        for mode, rows in (("repeat", [(0, J - 3, 0, 40), (1, 30, 5, 5), (2, 20, 3, 10), (S, 0, 0, 5)]), ("zero", [(1, J - 3, 0, 260), (S, 4, 0, 9)])):
+            host.conceal, m = mode, ("zero", "repeat").index(mode)
+            most = max(hi - lo for _, _, lo, hi in rows)
+            h4, h5 = upload(rows), upload([r + (1,) for r in rows])
+            jr = both(lambda b: check(call_on(b, l.afx_k_jitter_conceal, ptr(b), S, J, ptr(h4), len(rows), most, ptr(fades[1]), P, F, m)),
+                      lambda b: check(call_on(b, l.afx_k_jitter_conceal_rates, ptr(b), S, J, ptr(h5), len(rows), most, tp, 2, m)), jr)
+            ref.run(SimpleNamespace(ops=[("conceal", np.array([r + (1,) for r in rows if r[0] < S and r[3] > r[2]], dtype=np.int32), most)]), [])
+            assert torch.equal(bits(jr.cpu()), bits(host.jring)), (rate, "conceal", mode)
+        # ---- release: the one-rate entry point does not read the eighth int, so both take the same rows --------------------------
+        rows = [(s, N % J, n_in) + ingest_plan(N, n_in, L, M) + (wpos, 1)
+                for s, N, n_in, wpos in ((0, 3 * J - 3, J - max(T - 1, P + F), R - 5), (1, J + 11, 0, 7), (2, 2 * J + 40, 100, 0), (S, 0, 10, 0))]
+        most = max(r[3] for r in rows)
+        assert rows[0][1] == J - 3 and 256 < most <= R and rows[1][3] == 0
+        h8, counts = upload(rows), np.array([0, most], dtype=np.int32)
+        ring0 = sentinel(S, R).cuda()
+        ring = both(lambda b: check(call_on(b, l.afx_k_jitter_release, ptr(jr), S, J, ptr(h8), len(rows), most, taps, L, M, T, ptr(b), R)),
+                    lambda b: check(call_on(b, l.afx_k_jitter_release_rates, ptr(jr), S, J, ptr(h8), len(rows), tp, 2,
+                                            counts.ctypes.data_as(C.c_void_p), ptr(b), R)), ring0).cpu()
+        assert torch.equal(bits(jr.cpu()), bits(host.jring))  # (only read)
+        untouched = torch.ones(S, R, dtype=torch.bool)
+        w64 = None if x.identity else x.taps.cpu().double().numpy()
+        for s, col, n_in, n_out, p0, d0, wpos, _ in rows[:3]:
+            v = host.jring[s].double().numpy()
+            q = np.arange(n_out) * M + p0
+            idx = (col + d0 + q // L)[:, None] - np.arange(T)[None, :]
+            assert n_out == 0 or (idx.min() >= col - (T - 1) and idx.max() < col + n_in)
+            want = v[idx[:, 0] % J] if x.identity else (w64[q % L] * v[idx % J]).sum(axis=1)
+            at = (wpos + np.arange(n_out)) % R
+            got = ring[s, at].double().numpy()
+            tol = 0.0 if x.identity or not n_out else 2e-6 * float(np.abs(v[idx % J]).max())
+            assert n_out == 0 or np.abs(got - want).max() <= tol, (rate, s, float(np.abs(got - want).max()), tol)
+            untouched[s, at] = False
+        assert not untouched[0, R - 5:].any() and not untouched[0, :5].any()  # (the wrap of wpos)
+        assert torch.equal(bits(ring)[untouched], bits(ring0.cpu())[untouched]), (rate, "release")
