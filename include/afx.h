@@ -137,7 +137,15 @@ int afx_tail_forward_windows(afx_handle h, const void* conv5_h, long long total_
  * n_streams lock-stepped streams (K / V rings of every layer, the positional conv's left context, the feature window);
  * afx_kv_step consumes the NEW frames of conv layer 6 of every stream, (n_streams, n, 512) fp32 with 1 <= n <= 16, and
  * returns the back-end's logits on the window that ends with this chunk.  The handle must outlive its afx_kv objects; weights
- * reloaded into the handle do not refresh keys / values already cached. */
+ * reloaded into the handle do not refresh keys / values already cached.
+ * Layout of the state (what a host-side model of it may assume; oracle/insitu_kv.py does): per layer and stream a ring of
+ * 256 [q | k | v] rows (3072 operand-type elements) in 16 groups of 16 slots, stream s's slot i at ring row 256 s + i.  The
+ * chunk of step number `hop` (counted from afx_kv_create, every lock-step and ragged step adds one) is written to group
+ * hop % 16 of every stream, frame r at slot 16 group + r; the group then holds as many live slots as the chunk brought
+ * frames (a shorter chunk leaves the previous occupant's rows in the slots past its count: written earlier, never live).
+ * The positional conv's left context is the stream's newest 64 projected rows in the operand type (zeros before its
+ * first chunk); the feature window is a 208-row fp32 buffer per stream, right-aligned, zeros above the frames it has, of
+ * which the back-end scores the newest min(frames, 200). */
 typedef struct afx_kv afx_kv;
 int afx_kv_create(afx_handle h, int n_streams, afx_kv** out);
 void afx_kv_destroy(afx_kv* kv);
@@ -149,7 +157,10 @@ int afx_kv_step(afx_kv* kv, const float* feats6, int n_frames, float* logits, vo
  * cached keys / values, positional-conv context and feature window are dropped.  afx_kv_step_ragged takes the chunks as
  * (n_streams, n_max, 512) fp32 with stream b's n_frames[b] (host array, 1 <= n_frames[b] <= n_max <= 16) frames first;
  * each stream's logits equal, bit for bit, those of the same stream stepped from its reset in a fresh afx_kv.  Once
- * either is called, the state is per stream and afx_kv_step refuses it. */
+ * either is called, the state is per stream and afx_kv_step refuses it.  A reset stream's base group (the group of its
+ * first chunk, from which its 16 groups are visited in order) is the group the next step writes, hop % 16; its 16 valid
+ * counts, its left context and its window start empty.  A block's rows past its own n_frames[b] are computed and written
+ * to their slots but never live, and they are zero in the positional conv's operand. */
 int afx_kv_reset(afx_kv* kv, const int* slots, int n_slots, void* stream);
 size_t afx_kv_ragged_workspace_bytes(const afx_kv* kv, int n_max);
 int afx_kv_step_ragged(afx_kv* kv, const float* feats6, int n_max, const int* n_frames, float* logits, void* ws, size_t ws_bytes,
@@ -162,7 +173,9 @@ int afx_kv_step_ragged(afx_kv* kv, const float* feats6, int n_max, const int* n_
  * count), so a stream's logits equal, bit for bit, those of the same stream stepped on every step of a fresh afx_kv.
  * n_active == 0 launches nothing.  The workspace is carved for n_active streams (afx_kv_active_workspace_bytes).  The
  * first call makes the state per stream; afx_kv_step and afx_kv_step_ragged then refuse it (afx_kv_reset still applies:
- * a reset stream starts at its own next group). */
+ * a reset stream starts at its own next group, which becomes its base group).  At the first call every stream's next
+ * group is the group a lock-step or ragged step would have written, hop % 16; from then on a listed stream writes its
+ * own next group and moves it on by one (mod 16), and the step count `hop` stands still. */
 size_t afx_kv_active_workspace_bytes(const afx_kv* kv, int n_active, int n_max);
 int afx_kv_step_active(afx_kv* kv, const int* slots, int n_active, const float* feats6, int n_max, const int* n_frames,
                        float* logits, void* ws, size_t ws_bytes, void* stream);

@@ -31,6 +31,11 @@ the worst ratio |got - ref| / bound):
   C_FLIP 3 one-ulp flips per row at an internal rounding point (and per output column for the posconv weights, whose
          weight norm the device computes in fp32 before it rounds them).
   Bias   fp16 / bf16 operand outputs measured within +-0.015 ulp (BIAS_MAX 0.05).
+  The KV-cached step (oracle/insitu_kv.py: the same kernel families on the chunk's 1 .. 48 rows, the ring attention over <=
+  256 live slots) is judged with these constants unchanged.  tests/test_gpu_insitu_kv.py's summary on an MI355X, worst
+  ratio fp16 / bf16 / fp16x3: kv_product 0.495 / 0.499 / 0.078, kv_layernorm 0.479 / 0.497 / 0.004, kv_posconv 0.279 /
+  0.166 / 0.039, kv_ring 0.599 / 0.516 / 0.005 (bias of the products and LayerNorms within +-0.008 ulp; the ring
+  attention's statistic is reported only: too few independent samples at <= 48 query rows).
 
 The AASIST back-end (``aasist_walk`` and the functions above it) is fp32 throughout, so its bounds carry no operand ulp:
 

@@ -550,7 +550,18 @@ class Engine:
                   0 .. 5; aa.w1 (B img, 128), aa.w2 (B img, 64) the two attention maps over the padded pixels; e_S, e_T;
                   gat_S, gat_T, out_S, out_T; per branch k = 1, 2: b{k}_xp (type-projected nodes, temporal first),
                   b{k}_T1, b{k}_S1, b{k}_m1, b{k}_T1p, b{k}_S1p (pooled), b{k}_xp2, b{k}_Ta, b{k}_Sa, b{k}_ma; hidden;
-                  logits"""
+                  logits
+          KV step (``KVState.step``, all three forms; R row blocks = the streams or the list's entries, n = n_max rows each,
+                  dense (R n, .) unless said): kv.feats (feature LayerNorm), kv.proj (projected residual rows, fp32), kv.xpad
+                  (the whole padded operand buffer after its pad rows are zeroed, (R, 192 + n, 1024): [64 zero | 64 cached |
+                  chunk | 64 zero]), kv.pos (after the positional conv); per layer l: kv.l{l}.ln1, kv.l{l}.ring (the
+                  layer's WHOLE ring after the QKV launch, (S, 256, 3072), every stream of the state), kv.l{l}.att (a
+                  16-row block per row block, (R, 16, 1024)), kv.l{l}.mid, kv.l{l}.ln2, kv.l{l}.ff, kv.layer{l}; kv.fl
+                  (the final LayerNorm's rows; per-stream forms only -- lock-step writes them straight into the window:
+                  the last n rows of every stream's kv.win); kv.win (the window buffer that is current after the step's
+                  update, (S, 208, 1024), right-aligned); ssl (the head's input: lock-step (S, Th, 1024), the per-stream
+                  forms with the Conformer head (R, Th_max, 1024), every window left-aligned, zeros after); the AASIST
+                  bucket loop taps each gathered bucket as kv.bucket{i} (nb, t, 1024)"""
         n = C.c_size_t(0)
         with torch.cuda.device(self.device):
             check(lib().afx_tap(self._h, name.encode(), None, 0, C.byref(n), self._stream()))

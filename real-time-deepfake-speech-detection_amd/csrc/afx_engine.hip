@@ -1701,6 +1701,7 @@ static int kv_trunk(afx_kv* k, const KvForm& f, const float* feats6, int n, KvWs
     a.out_h = w.feats_h; a.ldo_h = kC;
     KOK(launch_rownorm(a, dt, s));
   }
+  TAP("kv.feats", w.feats_h, (size_t)M * kC, true, kC);
   // positional conv operand: [64 zero rows | 64 cached projected frames | the chunk | 64 zero rows] per row block
   if (f.ids) {
     hipLaunchKernelGGL(kv_hist_kernel, dim3(32, R), dim3(256), 0, s, (u32x4*)k->hist, (u32x4*)w.xpad, f.dn, (long)(xrow / 16),
@@ -1719,6 +1720,8 @@ static int kv_trunk(afx_kv* k, const KvForm& f, const float* feats6, int n, KvWs
     // (per-stream counts: a block's chunk rows past its own n_s are zero, as beyond its chunk when the stream steps alone)
     KOK(timed(PC_MISC, 0, s, [&] { return launch_zero_pad_rows(w.xpad, R, Tp, kD, kPosPad, kPosK - kPosPad, dt, s, f.pad_lens); }));
   }
+  TAP("kv.xpad", w.xpad, (size_t)R * (Tp + kPosK) * kD, true, kD);  // (the whole padded buffer of every row block, pad rows included)
+  TAP("kv.proj", w.x, (size_t)M * kD, false, kD);
   // The positional conv of the chunk's n frames ONLY (round 4: it used to run over all 64 + n rows of the padded layout and
   // keep the last n -- 6x the work at n = 13): output frame j reads rows [64 + j, 192 + j) of the block's padded rows, i.e. rows
   // [j, j + 128) from the first cached frame on.
@@ -1733,6 +1736,7 @@ static int kv_trunk(afx_kv* k, const KvForm& f, const float* feats6, int n, KvWs
     s3_set(xchunk, kS3ScaleFree);  // (history rows copied in above + the rows the projection just wrote: pair form, scale 1)
     KOK(posconv_product(e, xchunk, Tp + kPosK, R, n, w.x, dt, s));
   }
+  TAP("kv.pos", w.x, (size_t)M * kD, false, kD);
   // the newest 64 projected frames become the next chunk's left context
   if (f.dn) {
     hipLaunchKernelGGL(kv_hist_kernel, dim3(32, R), dim3(256), 0, s, (u32x4*)k->hist, (u32x4*)w.xpad, f.dn, (long)(xrow / 16),
@@ -1744,9 +1748,11 @@ static int kv_trunk(afx_kv* k, const KvForm& f, const float* feats6, int n, KvWs
   for (int l = 0; l < e->cfg.n_layers; ++l) {
     const std::string P = "ssl.encoder.layers." + std::to_string(l) + ".";
     void* ring = (char*)k->rings + (size_t)l * k->S * kKvSlots * 3 * kD * hs;
+    auto lp = [l](const char* leaf) { return "kv.l" + std::to_string(l) + "." + leaf; };  // (tap names: built only while taps are on)
     RowNormArgs n1 = plain_norm(w.x, kD, M, kD, e->F(P + "self_attn_layer_norm.weight"), e->F(P + "self_attn_layer_norm.bias"));
     n1.out_h = w.hbuf; n1.ldo_h = kD;
     KOK(launch_rownorm(n1, dt, s));
+    TAP(lp("ln1"), w.hbuf, (size_t)M * kD, true, kD);
     // q | k | v of the chunk go straight into its 16-slot group of the ring (row remap or row table of the epilogue): K / V are
     // cached by being written
     GemmArgs q = plain_gemm(w.hbuf, kD, e->wqkv[l], kD, M, 3 * kD, kD);
@@ -1759,6 +1765,7 @@ static int kv_trunk(afx_kv* k, const KvForm& f, const float* feats6, int n, KvWs
       q.oh_batch_rows = kKvSlots; q.oh_row_off = f.ring.q_tile * 16;
     }
     KOK(launch_gemm(q, dt, 1, s, f.qkv_rows != nullptr));
+    TAP(lp("ring"), ring, (size_t)k->S * kKvSlots * 3 * kD, true, 3 * kD);  // (this layer's whole ring, every stream of the state)
     KOK(timed(PC_MHSA, 4.0 * R * kH * 16.0 * kKvSlots * 64, s, [&] {
       if (e->s3) {  // fp32 [q | k | v] slots, hi / lo pairs split in the kernel; the output leaves as the output projection's pair-form operand
         const bool pairs = s3_ok(w.att);
@@ -1767,19 +1774,24 @@ static int kv_trunk(afx_kv* k, const KvForm& f, const float* feats6, int n, KvWs
       }
       return launch_mhsa_ring(ring, w.att, R, kH, f.ring, dt, s);
     }));
+    TAP(lp("att"), w.att, (size_t)R * 16 * kD, true, kD);  // (a 16-row block per row block)
     GemmArgs o = plain_gemm(w.att, kD, e->wo[l], kD, M, kD, kD);
     o.rpb = n; o.a_batch = 16L * kD; o.a_row = kD; o.o_batch_rows = n;
     o.bias = e->F(P + "self_attn.out_proj.bias"); o.resid = w.x; o.ldr = kD; o.out_f = w.x; o.ldo_f = kD;
     KOK(launch_gemm(o, dt, 1, s));
+    TAP(lp("mid"), w.x, (size_t)M * kD, false, kD);
     RowNormArgs n2 = plain_norm(w.x, kD, M, kD, e->F(P + "final_layer_norm.weight"), e->F(P + "final_layer_norm.bias"));
     n2.out_h = w.hbuf; n2.ldo_h = kD;
     KOK(launch_rownorm(n2, dt, s));
+    TAP(lp("ln2"), w.hbuf, (size_t)M * kD, true, kD);
     GemmArgs f1 = plain_gemm(w.hbuf, kD, e->w1[l], kD, M, kF, kD);
     f1.bias = e->F(P + "fc1.bias"); f1.act = ACT_GELU; f1.out_h = w.ff; f1.ldo_h = kF;
     KOK(launch_gemm(f1, dt, 1, s));
+    TAP(lp("ff"), w.ff, (size_t)M * kF, true, kF);
     GemmArgs f2 = plain_gemm(w.ff, kF, e->w2[l], kF, M, kD, kF);
     f2.bias = e->F(P + "fc2.bias"); f2.resid = w.x; f2.ldr = kD; f2.out_f = w.x; f2.ldo_f = kD;
     KOK(launch_gemm(f2, dt, 1, s));
+    TAP("kv.layer" + std::to_string(l), w.x, (size_t)M * kD, false, kD);
   }
   RowNormArgs nf = plain_norm(w.x, kD, M, kD, e->F("ssl.encoder.layer_norm.weight"), e->F("ssl.encoder.layer_norm.bias"));
   if (f.win_next) {
@@ -1791,6 +1803,7 @@ static int kv_trunk(afx_kv* k, const KvForm& f, const float* feats6, int n, KvWs
   }
   nf.nonfinite = e->nonfinite;
   KOK(launch_rownorm(nf, dt, s));
+  if (!f.win_next) TAP("kv.fl", w.fl, (size_t)M * kD, false, kD);  // (lock-step: the rows are the last n of every stream's "kv.win")
   return 0;
 }
 
@@ -1817,6 +1830,7 @@ extern "C" int afx_kv_step(afx_kv* k, const float* feats6, int n, float* logits,
   f.ring = MhsaRingForm{1, group, k->cnt, nullptr};
   f.win_next = nxt;
   if (kv_trunk(k, f, feats6, n, w, s)) return 1;
+  TAP("kv.win", nxt, (size_t)S * kKvFeat * kD, false, kD);
   k->pp ^= 1;
   k->nfeat = std::min(k->nfeat + n, kKvFeat);
   // back-end on the window of the last Th frames
@@ -1861,6 +1875,7 @@ static int kv_score_windows(afx_engine* e, KvWs& w, const KvWindows& v, float* l
   if (e->cfg.arch == AFX_ARCH_CONFORMER) {
     hipLaunchKernelGGL(kv_gather_kernel, dim3(32, count), dim3(256), 0, s, (const f32x4*)v.win, v.ids, v.dth, 0, Thmax, (f32x4*)w.head.ssl_f);
     HIP_OK(hipGetLastError());
+    TAP("ssl", w.head.ssl_f, (size_t)count * Thmax * kD, false, kD);  // (the head's input: every window left-aligned, zeros after)
     HIP_OK(hipMemcpyAsync(w.head.lens, v.dth, (size_t)count * 4, hipMemcpyDeviceToDevice, s));
     if (e->s3) {  // (fp32 operand buffers: the head's LL converts the rows it reads into its own scratch)
       HIP_OK(hipMemcpyAsync(w.head.ssl_h, w.head.ssl_f, (size_t)count * Thmax * kD * 4, hipMemcpyDeviceToDevice, s));
@@ -1877,6 +1892,7 @@ static int kv_score_windows(afx_engine* e, KvWs& w, const KvWindows& v, float* l
     const int nb = (bi + 1 < v.buckets.size() ? v.buckets[bi + 1].second : count) - i0;
     hipLaunchKernelGGL(kv_gather_kernel, dim3(32, nb), dim3(256), 0, s, (const f32x4*)v.win, v.b_ids + i0, (const int*)nullptr, t, t, (f32x4*)w.head.bucket_f);
     HIP_OK(hipGetLastError());
+    TAP("kv.bucket" + std::to_string(bi), w.head.bucket_f, (size_t)nb * t * kD, false, kD);
     if (const char* m = aasist_forward(e->aw, w.head.bucket_f, nb, t, w.head.aa, w.head.bucket_logits, s, e->nonfinite + 1)) return fail("%s", m);
     hipLaunchKernelGGL(kv_scatter_logits_kernel, dim3((2 * nb + 255) / 256), dim3(256), 0, s, w.head.bucket_logits, v.b_row + i0, nb, logits);
     HIP_OK(hipGetLastError());
@@ -1932,6 +1948,7 @@ extern "C" int afx_kv_step_ragged(afx_kv* k, const float* feats6, int n, const i
   float *cur = k->feat[k->pp], *nxt = k->feat[k->pp ^ 1];
   hipLaunchKernelGGL(kv_feat_kernel, dim3(64, S), dim3(256), 0, s, (const f32x4*)cur, (f32x4*)nxt, (const f32x4*)w.fl, dn, n);
   HIP_OK(hipGetLastError());
+  TAP("kv.win", nxt, (size_t)S * kKvFeat * kD, false, kD);
   k->pp ^= 1;
   for (int b = 0; b < S; ++b) k->nfeat_s[b] = std::min(k->nfeat_s[b] + n_frames[b], kKvFeat);
   k->hop += 1;
@@ -2054,6 +2071,7 @@ extern "C" int afx_kv_step_active(afx_kv* k, const int* slots, int A, const floa
   if (kv_trunk(k, f, feats6, n, w, s)) return 1;
   hipLaunchKernelGGL(kv_shift_kernel, dim3(kD / 4 / 32, A), dim3(256), 0, s, (f32x4*)k->feat[k->pp], (const f32x4*)w.fl, dids, dn, n);
   HIP_OK(hipGetLastError());
+  TAP("kv.win", k->feat[k->pp], (size_t)S * kKvFeat * kD, false, kD);  // (every stream of the state: the unnamed ones keep every byte)
   for (int i = 0; i < A; ++i) k->nfeat_s[slots[i]] = std::min(k->nfeat_s[slots[i]] + n_frames[i], kKvFeat);
   return kv_score_windows(e, w, v, logits, s);
 }
