@@ -428,6 +428,29 @@ int afx_k_jitter_conceal_rates(float* jring, int S, int Js, const int* hdr, int 
                                int n_rates, int mode, void* stream);
 int afx_k_jitter_release_rates(const float* jring, int S, int Js, const int* hdr, int rows, const afx_jitter_rate* rates,
                                int n_rates, const int* max_out, float* ring, int ring_len, void* stream);
+/* Comfort noise (afx/jitter.py ComfortNoise; RFC 3389 silence in a DTX call): the fourth verb of the jitter buffer.  The host
+ * splits a released gap at its governing silence marks; the parts after a mark are noise, written into the ring like concealed
+ * samples.  The value of index i (64 bits, from the session's origin) at level l (0..127, -dBov) with the launch's seed, all
+ * integer arithmetic mod 2^32:
+ *         x = lo32(i) * 0x9E3779B9 + hi32(i) * 0x85EBCA6B + seed
+ *         x ^= x >> 16;  x *= 0x7FEB352D;  x ^= x >> 15;  x *= 0x846CA68B;  x ^= x >> 16
+ *         k = int32(x) >> 8                  (arithmetic shift: -2^23 <= k < 2^23, exactly an fp32 number)
+ *         E[i] = amp[l] * fp32(k)            (one correctly rounded fp32 multiply)
+ *     amp (device, 128 fp32): amp[l] = fp32(sqrt(3) * 10^(-l/20) / 2^23), computed in float64 and rounded once: uniform white
+ *     noise of RMS 10^(-l/20) of the decoders' full scale.  The value depends on (seed, i, l) only; nothing is clipped.
+ * afx_k_jitter_noise: hdr (device, rows x 6 int32), per row: slot, ring column c of the first index i0, n, lo32(i0), hi32(i0),
+ *     level: jring[slot][(c + k) mod J] = amp[level] * fp32(k(seed, i0 + k)), k < n.  The rows of one launch write disjoint
+ *     ranges; a slot may have several (noise has no source, so there are no ranks).  max_n = the largest n <= J.  A row is
+ *     skipped whole, writing nothing, when its slot is outside [0, S), c outside [0, J), n outside [0, J], level outside
+ *     0..127 or hi32(i0) < 0.
+ * afx_k_jitter_noise_rates: hdr (device, rows x 7 int32): the six ints, then the rate index; the same function with the row's
+ *     J_f; a row with a rate index out of range is skipped whole.  Of a rate only J is read.
+ * Refused with nothing launched, as for the other verbs: a null jring / hdr / amp, rows outside 1..65535, a max_n no rate can
+ * hold, and for _rates what afx_k_jitter_place_rates refuses of a table.  Each refusal names its entry point. */
+int afx_k_jitter_noise(float* jring, int S, int J, const int* hdr, int rows, int max_n, unsigned seed, const float* amp,
+                       void* stream);
+int afx_k_jitter_noise_rates(float* jring, int S, int Js, const int* hdr, int rows, int max_n, const afx_jitter_rate* rates,
+                             int n_rates, unsigned seed, const float* amp, void* stream);
 /* Speech gate (afx/vad.py): an energy gate with noise-floor tracking and hangover over frames of `frame` 16 kHz samples
  * (160 = 10 ms), per slot.  Constants, fp32: e_floor (the mean-square floor times frame), ratio > 1, rise >= 1, and
  * nf_min = e_floor / ratio (one fp32 division); hang >= 0 frames.  State per slot: nf (S,) fp32, +inf for a new stream, and

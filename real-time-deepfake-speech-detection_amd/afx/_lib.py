@@ -116,6 +116,8 @@ SIGNATURES = {
     "afx_k_jitter_place_rates": (_I, [_P, C.c_longlong, _P, _I, _I, _P, _I, _P, _I, _I, _P]),
     "afx_k_jitter_conceal_rates": (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _I, _P]),
     "afx_k_jitter_release_rates": (_I, [_P, _I, _I, _P, _I, _P, _I, _P, _P, _I, _P]),
+    "afx_k_jitter_noise": (_I, [_P, _I, _I, _P, _I, _I, C.c_uint, _P, _P]),
+    "afx_k_jitter_noise_rates": (_I, [_P, _I, _I, _P, _I, _I, _P, _I, C.c_uint, _P, _P]),
     "afx_k_gate": (_I, [_P, _I, _I, _P, _I, _F, _F, _F, _I, _P, _P, _P, _I, _I, _P, _P, _P]),
     "afx_k_gate_la": (_I, [_P, _I, _I, _P, _I, _F, _F, _F, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P]),
     "afx_k_gate_tone": (_I, [_P, _I, _I, _P, _I, _F, _F, _F, _I, _P, _I, _F, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),

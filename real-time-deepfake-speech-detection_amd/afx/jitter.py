@@ -69,6 +69,46 @@ invariant above holds per slot with its own J_r.  A mixed state has ``jitter_rin
 ``jitter_conceal``, ``resampler`` and ``jitter_mixed``; a plain JitterScorer's state imports where its rate is listed and
 its parameters are that rate's.  Out of scope: a rate change without a reset, per-slot depth within one rate, big-endian
 L16 payloads (swap the bytes), per-slot conceal modes.
+
+Silence suppression (DTX) and comfort noise (RFC 3389): a sender with VAD on stops sending in a pause and says so with a
+CN packet: from this timestamp on there is silence, and the background noise is this many dB below overload.  A scorer built
+with ``comfort_noise=ComfortNoise(seed)`` plays noise of that level where a scorer without it conceals a loss.  Opt-in: a
+scorer without it is in every respect the scorer described above.
+  marks        per slot the host keeps silence marks (t, level): t an index of E (unwrapped like a packet timestamp), level
+               in 0..127.  A mark covers no samples and moves neither ``hi`` nor the origin.  ``silence(slots, timestamps,
+               levels)`` registers them (``feed_rtp``: a datagram of payload type 13, or of a type mapped to "cn"; level =
+               payload[0] & 0x7f; the spectral bytes after it are read past: a receiver of model order 0).  A mark for a slot
+               without a session, or with t < ``next`` at the call that brings it, is dropped and counted (``marks_late``); of
+               two marks of a slot at one t the first arrival wins.
+  concealment  gains one case.  Let i be a released index that was not received and g the start of the maximal run of
+               non-received indices that contains i (the gap origin a above).  If the slot holds a mark with g <= t <= i,
+               E[i] is comfort noise at the level l of the mark with the largest such t; otherwise E[i] is concealed as
+               above with d = i - g.  So a gap [g, b) with a mark at t is loss in [g, t) -- the lost last packet of a talk
+               spurt is still concealed -- and noise in [t, b), whatever d is; a later mark in the run changes the level
+               from its own t on.  E[i] is fixed by the call that releases i, from the intervals and marks accepted up to
+               and including that call.  Received samples are never modified; the source [a - P, a) of a later loss gap may
+               hold noise.  Marks inside received intervals govern nothing; marks are dropped as the playout point passes.
+  noise        i is a 64-bit index, all integer arithmetic is mod 2**32, the one floating-point operation is one fp32 multiply:
+                   x = lo32(i) * 0x9E3779B9 + hi32(i) * 0x85EBCA6B + seed
+                   x ^= x >> 16;  x *= 0x7FEB352D;  x ^= x >> 15;  x *= 0x846CA68B;  x ^= x >> 16
+                   k = int32(x) >> 8                     (arithmetic: -2**23 <= k < 2**23, exactly an fp32 number)
+                   E[i] = amp[l] * fp32(k),   amp[l] = fp32(sqrt(3) * 10**(-l/20) / 2**23)   (float64, rounded once)
+               uniform white noise of RMS 10**(-l/20) of the decoders' full scale (RFC 3389's -dBov, a full-scale square
+               wave being 0 dBov).  It depends on (seed, i, l) only: not on the slot, the cut into calls or a session move.
+               Nothing is clipped.  ``ComfortNoise.samples`` / ``.ints`` / ``.amp`` are the statement in numpy.
+Device side: a fourth verb, ``afx_k_jitter_noise`` (``_noise_rates``): rows of (slot, column, n, lo32(i0), hi32(i0), level),
+the launch shape of place.  A released gap is split at its governing marks into loss parts (conceal rows, ranked as before)
+and noise parts (noise rows).  Per round: place, ONE noise launch, the conceal ranks, release, pop -- so a loss gap whose
+source is this round's noise reads it.  Noise is written inside the released range only, as concealed samples are: ring
+sizing and the J-window invariant are unchanged.  ``advance`` beyond ``hi`` continues a silence in force as noise.
+``stats()`` adds ``comfort`` (noise samples released), ``marks`` (accepted) and ``marks_late``; ``concealed`` then counts
+loss-concealed samples only.  ``export_slots`` adds ``jitter_cn_marks`` ((n, K, 2) int64, -1 padded: the marks at t >= next),
+``jitter_cn_open`` ((n,) int64: the level in force for the open gap, -1 none), ``jitter_cn_stats`` ((n, 3) int64) and the
+meta ``jitter_cn`` (the seed).  A state without them imports into a comfort-noise scorer with no marks; a state with them is
+refused by a scorer without ``ComfortNoise`` or of another seed.  ``feed_rtp(..., ignore_types=(101,))`` parses and
+SSRC-checks datagrams of those payload types (RFC 4733 telephone-events) and drops them.  Out of scope: spectral shaping from
+the CN payload, inferring silence from the RTP marker bit, G.729 / AMR SID frames, per-slot seeds, noise in loss gaps,
+generating CN on a sending side.
 """
 import ctypes as C
 from itertools import repeat
@@ -77,7 +117,7 @@ import numpy as np
 import torch
 
 from . import rtp
-from ._layer import _on, check_pending, export_pending, import_pending, peel, rows_on, wrap
+from ._layer import StreamState, _on, check_pending, export_pending, import_pending, peel, rows_on, wrap
 from ._lib import JitterRate, call_on, check, lib, ptr
 from .ingest import _MAX_SAMPLES, _SAMPLE, ENCODINGS, MAX_FORMATS, _at, _encoding, _format, layout
 from .resample import FILTER_ID, Resampler
@@ -94,6 +134,11 @@ _BOOK = ("origin", "started", "next", "hi", "gap", "max_start", "max_seq", "ssrc
 _COUNTERS = ("received", "late", "dup", "concealed", "ooo")  # jitter_stats columns (STATS order)
 _BPS = np.array([_SAMPLE[e].itemsize for e in ENCODINGS], dtype=np.int64)  # bytes per sample by encoding number
 _NUMBER = {e: i for i, e in enumerate(ENCODINGS)}  # the library's encoding numbers
+NOISE_HDR, NOISE_RATES_HDR = 6, 7  # afx_k_jitter_noise / _noise_rates: slot, column, n, lo32(i0), hi32(i0), level [, rate index]
+CN_STATS = ("comfort", "marks", "marks_late")  # what stats() adds with a ComfortNoise
+_CN_KEYS = ("jitter_cn_marks", "jitter_cn_open", "jitter_cn_stats")  # what export_slots adds with a ComfortNoise
+_CN_COUNTERS = ("comfort", "nmarks", "marks_late")  # jitter_cn_stats columns (CN_STATS order)
+_M32 = 0xFFFFFFFF
 
 
 def _nonneg_int(v, name, least=0):
@@ -102,34 +147,67 @@ def _nonneg_int(v, name, least=0):
     return int(v)
 
 
+class ComfortNoise:
+    """The comfort noise of a jitter scorer (module docstring, "noise"): ``seed`` is an integer in [0, 2**32), one for the
+    whole scorer.  ``amp``: (128,) fp32, the amplitude of each level.  ``ints(i0, n)``: k of the indices i0 .. i0 + n - 1
+    (int32); ``samples(i0, n, level)``: E of those indices at ``level`` (fp32), operation by operation what the kernel does."""
+
+    def __init__(self, seed=0):
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed <= _M32:
+            raise ValueError(f"seed: an integer in 0..2**32 - 1, got {seed!r}")
+        self.seed = int(seed)
+        self.amp = (np.sqrt(3.0) * 10.0 ** (-np.arange(128, dtype=np.float64) / 20.0) / 2.0 ** 23).astype(np.float32)
+
+    def ints(self, i0, n):
+        if not 0 <= i0 < 1 << 63 or n < 0:
+            raise ValueError("ints: 0 <= i0 < 2**63 and n >= 0")
+        i, m = np.uint64(i0) + np.arange(int(n), dtype=np.uint64), np.uint64(_M32)
+        x = ((i & m) * np.uint64(0x9E3779B9) + (i >> np.uint64(32)) * np.uint64(0x85EBCA6B) + np.uint64(self.seed)) & m
+        x ^= x >> np.uint64(16)
+        x = (x * np.uint64(0x7FEB352D)) & m
+        x ^= x >> np.uint64(15)
+        x = (x * np.uint64(0x846CA68B)) & m
+        x ^= x >> np.uint64(16)
+        return x.astype(np.uint32).view(np.int32) >> 8
+
+    def samples(self, i0, n, level):
+        if isinstance(level, bool) or not isinstance(level, (int, np.integer)) or not 0 <= level <= 127:
+            raise ValueError(f"level: an integer in 0..127, got {level!r}")
+        return self.amp[level] * self.ints(i0, n).astype(np.float32)
+
+
 class _Book:
     """The host's bookkeeping of every slot (int64 arrays over S) and, for the slots that currently have holes, their
     received intervals (``holes``: slot -> sorted disjoint [start, end) lists inside [next, hi)).  A slot that is not in
-    ``holes`` has received exactly [next, hi)."""
+    ``holes`` has received exactly [next, hi).  Comfort noise: ``cn_open`` (the level in force for the open gap, -1 none),
+    its counters and ``marks`` (slot -> the pending silence marks [t, level], sorted by t, every t >= next)."""
+
+    _ARRAYS = _BOOK + _COUNTERS + _CN_COUNTERS + ("cn_open", "head", "fill")
 
     def __init__(self, S):
-        for f in _BOOK + _COUNTERS + ("head", "fill"):
+        for f in self._ARRAYS:
             setattr(self, f, np.zeros(S, dtype=np.int64))
-        for f in ("gap", "max_seq", "ssrc"):
+        for f in ("gap", "max_seq", "ssrc", "cn_open"):
             getattr(self, f)[:] = -1
         self.holey = np.zeros(S, dtype=bool)
-        self.holes = {}
+        self.holes, self.marks = {}, {}
 
     def copy(self):
         b = _Book.__new__(_Book)
-        for f in _BOOK + _COUNTERS + ("head", "fill", "holey"):
+        for f in self._ARRAYS + ("holey",):
             setattr(b, f, getattr(self, f).copy())
-        b.holes = dict(self.holes)  # (the lists are replaced, never edited in place)
+        b.holes, b.marks = dict(self.holes), dict(self.marks)  # (the lists are replaced, never edited in place)
         return b
 
     def clear(self, idx):
-        for f in _BOOK + _COUNTERS + ("head", "fill"):
+        for f in self._ARRAYS:
             getattr(self, f)[idx] = 0
-        for f in ("gap", "max_seq", "ssrc"):
+        for f in ("gap", "max_seq", "ssrc", "cn_open"):
             getattr(self, f)[idx] = -1
         self.holey[idx] = False
         for s in idx:
             self.holes.pop(s, None)
+            self.marks.pop(s, None)
 
     def intervals(self, s):
         """The received intervals of slot s in [next, hi)."""
@@ -177,7 +255,7 @@ def _merge(ivs, new):
 
 
 class Plan:
-    """What a call will do: ``ops`` (the launches, in order: ("place" | "conceal" | "release", int32 rows, largest row) and
+    """What a call will do: ``ops`` (the launches, in order: ("place" | "noise" | "conceal" | "release", int32 rows, largest row) and
     ("pop", (A, 2) table, slots)), ``counts`` (hops per named row) and ``book`` (the bookkeeping after it)."""
 
     def __init__(self, ops, slots, counts, book):
@@ -193,7 +271,8 @@ class JitterScorer(_Front):
     ``conceal``: "repeat" or "zero".  ``period``: the repeat period P in input samples, default 10 ms (input_rate // 100).  ``fade``: the fade length F in
     input samples, default 3 P (30 ms).  ``max_pending``: the whole hops a slot may buffer between ``feed(..., score=False)``
     and ``drain``.  ``ts_bits``: 32 (default) unwraps each timestamp to the value nearest the slot's ``hi``, so a stream
-    crossing 2**32 is seamless; None takes absolute indices.
+    crossing 2**32 is seamless; None takes absolute indices.  ``comfort_noise``: a ``ComfortNoise``, for calls with silence
+    suppression (module docstring); None: silence marks and RTP payload type 13 are refused.
 
     Every jitter scorer owns a table of its rates (``_size``) and each slot's index into it; this one's table has one entry,
     every slot is at index 0, and the entry's values go by the names below (``depth``, ``period``, ``J`` ...)."""
@@ -201,7 +280,8 @@ class JitterScorer(_Front):
     _WORK = "decoded, concealed, resampled"
     _rated = False  # (MixedJitterScorer: the rows of a plan carry their slot's rate index)
 
-    def __init__(self, scorer, input_rate, encoding, depth, conceal="repeat", period=None, fade=None, max_pending=4, ts_bits=32):
+    def __init__(self, scorer, input_rate, encoding, depth, conceal="repeat", period=None, fade=None, max_pending=4, ts_bits=32,
+                 comfort_noise=None):
         if isinstance(encoding, str):
             self.encodings, self._mixed = (_encoding(encoding),), False
         else:
@@ -212,7 +292,7 @@ class JitterScorer(_Front):
                 raise ValueError("encoding: an encoding is listed twice")
         self.encoding = self.encodings[0]
         self.depth = _nonneg_int(depth, "depth")
-        max_pending = self._checked(conceal, max_pending, ts_bits)
+        max_pending = self._checked(conceal, max_pending, ts_bits, comfort_noise)
         super().__init__(scorer, input_rate)
         self.period = self.fade_len = 0  # (no part of the "zero" function: not recorded in a state either)
         if conceal == "repeat":
@@ -222,8 +302,11 @@ class JitterScorer(_Front):
         self.L, self.M, self.J, self.fade = self.rs.L, self.rs.M, self.Js, self._fades[0]
         self.lookback, self.W = int(self._rlookback[0]), int(self._rW[0])
 
-    def _checked(self, conceal, max_pending, ts_bits):
-        """The constructor arguments every jitter scorer takes, checked: sets ``conceal`` and ``ts_bits`` -> max_pending."""
+    def _checked(self, conceal, max_pending, ts_bits, comfort_noise=None):
+        """The constructor arguments every jitter scorer takes, checked: sets ``conceal``, ``ts_bits`` and ``cn`` -> max_pending."""
+        if comfort_noise is not None and not isinstance(comfort_noise, ComfortNoise):
+            raise ValueError("comfort_noise: a ComfortNoise, or None")
+        self.cn = comfort_noise
         if conceal not in CONCEAL:
             raise ValueError(f"conceal {conceal!r}: one of {CONCEAL}")
         max_pending = _nonneg_int(max_pending, "max_pending", 1)
@@ -258,6 +341,7 @@ class JitterScorer(_Front):
         self._new_ring(max_pending)
         self.jring = torch.zeros(scorer.S, self.Js, dtype=torch.float32, device=scorer.device)
         self._fades = [_fade_table(int(f), scorer.device) for f in self._rF]  # one device table per rate
+        self._amp = None if self.cn is None else torch.from_numpy(self.cn.amp).to(scorer.device)
         self._table = (JitterRate * len(rs))()  # (pointers: the tensors above)
         for i, (t, x) in enumerate(zip(self._table, rs)):
             t.taps = None if x.identity else x.taps.data_ptr()
@@ -286,8 +370,10 @@ class JitterScorer(_Front):
         """Per-slot int64 counters since each slot's reset: ``received`` (samples placed), ``late`` (samples below the
         playout point on arrival), ``duplicate`` (samples already covered), ``concealed`` (released gap samples) and
         ``out_of_order`` (packets that arrived behind an earlier one: by sequence number in ``feed_rtp``, by timestamp in
-        ``feed``)."""
-        return {k: torch.from_numpy(getattr(self._b, f).copy()) for k, f in zip(STATS, _COUNTERS)}
+        ``feed``).  With a ``ComfortNoise``: also ``comfort`` (released noise samples), ``marks`` (silence marks accepted)
+        and ``marks_late`` (marks dropped: no session yet, or below the playout point); ``concealed`` is then loss only."""
+        names, fields = (STATS, _COUNTERS) if self.cn is None else (STATS + CN_STATS, _COUNTERS + _CN_COUNTERS)
+        return {k: torch.from_numpy(getattr(self._b, f).copy()) for k, f in zip(names, fields)}
 
     # ---- planning (host arithmetic only) -----------------------------------------------------------------------------
     def _geometry(self, rate):
@@ -375,32 +461,79 @@ class JitterScorer(_Front):
         return np.concatenate(place, axis=1) if place else np.zeros((5, 0), dtype=np.int64)
 
     def _take_gaps(self, b, U, tgt):
-        """Phase 2: the named slots U release [next, tgt) -> {position in U: [[origin, lo, hi], ...]} (the gaps of that
-        range, in order), and the bookkeeping moves to next = tgt.  Per-slot work only for slots with holes."""
+        """Phase 2: the named slots U release [next, tgt) -> ({position in U: [[origin, lo, hi], ...]} (the loss gaps of that
+        range, in order), {position in U: [[lo, hi, level], ...]} (its comfort-noise parts)), and the bookkeeping moves to
+        next = tgt.  Per-slot work only for slots with holes or marks."""
         nxt = b.next[U].copy()
-        gaps = {}
+        gaps, noise = {}, {}
         moved = tgt > nxt
         plain = moved & ~b.holey[U]
         b.gap[U[plain]] = -1
         b.next[U[plain]] = tgt[plain]
+        if self.cn is not None:
+            b.cn_open[U[plain]] = -1
         for u in np.flatnonzero(moved & b.holey[U]).tolist():
             s, lo, hi = int(U[u]), int(nxt[u]), int(tgt[u])
             ivs = b.holes[s]
             g = _subtract(lo, hi, ivs)
+            level = -1
             if g:
                 opened = int(b.gap[s])
-                gaps[u] = [[opened if k == 0 and a == lo and opened >= 0 else a, a, e] for k, (a, e) in enumerate(g)]
-                b.concealed[s] += sum(e - a for a, e in g)
-            b.gap[s] = gaps[u][-1][0] if g and g[-1][1] == hi else -1
+                gl = [[opened if k == 0 and a == lo and opened >= 0 else a, a, e] for k, (a, e) in enumerate(g)]
+                origin = gl[-1][0]
+                marks, level = b.marks.get(s), int(b.cn_open[s]) if gl[0][0] != gl[0][1] else -1
+                if marks or level >= 0:  # split at the governing marks: loss before the first of a run, noise from it on
+                    loss, nz = [], []
+                    for o, a, e in gl:
+                        level = level if o != a else -1  # (a run that began before this release keeps the level in force)
+                        for t, l in marks or ():
+                            if a <= t < e:
+                                if t > a:
+                                    loss.append([o, a, t]) if level < 0 else nz.append([a, t, level])
+                                a, level = t, l
+                        loss.append([o, a, e]) if level < 0 else nz.append([a, e, level])
+                    gl = loss
+                    noise[u] = nz
+                    b.comfort[s] += sum(e - a for a, e, _ in nz)
+                if gl:
+                    gaps[u] = gl
+                b.concealed[s] += sum(e - a for _, a, e in gl)
+            open_ = bool(g) and g[-1][1] == hi
+            b.gap[s] = origin if open_ else -1
+            b.cn_open[s] = level if open_ else -1
             b.next[s] = hi
             b.set_intervals(s, [[max(a, hi), e] for a, e in ivs if e > hi])
-        return gaps
+        if b.marks:  # marks are dropped as the playout point passes them
+            for s, up in zip(U.tolist(), tgt.tolist()):
+                if s in b.marks and b.marks[s][0][0] < up:
+                    b.marks[s] = [m for m in b.marks[s] if m[0] >= up]
+                    if not b.marks[s]:
+                        del b.marks[s]
+        return gaps, noise
 
-    def _plan(self, slots, sizes=None, ts=None, offs=None, seqs=None, mode="feed", upto=None, score=True, encs=None):
+    def _mark_rows(self, b, slot, ts, level):
+        """The silence marks (slot[i], timestamp ts[i], level[i]) go into the book ``b``, in order."""
+        for s, t, l in zip(slot, ts, level):
+            if not b.started[s]:
+                b.marks_late[s] += 1
+                continue
+            origin = int(b.origin[s])
+            r = self._unwrap(t, origin + int(b.hi[s])) - origin
+            have = b.marks.get(s, [])
+            if r < b.next[s]:
+                b.marks_late[s] += 1
+            elif all(m[0] != r for m in have):  # (of two marks at one t the first arrival wins)
+                b.marks[s] = sorted(have + [[r, l]])
+                b.nmarks[s] += 1
+
+    def _plan(self, slots, sizes=None, ts=None, offs=None, seqs=None, mode="feed", upto=None, score=True, encs=None, marks=None):
         """The launches of a call over the rows ``slots`` (feed: sizes[i] samples with timestamp ts[i] and payload at byte
         offs[i] for slots[i], a slot possibly named more than once; flush / advance / drain: distinct slots) -> Plan.  No
-        state changes here: ``_commit(plan.book)`` (or ``_run``) makes it so."""
+        state changes here: ``_commit(plan.book)`` (or ``_run``) makes it so.  ``marks``: (slots, timestamps, levels) of
+        the silence marks the call brings, registered before its rows are planned."""
         b = self._b.copy()
+        if marks is not None:
+            self._mark_rows(b, *marks)
         R, hop = self.ring_len, self.hop
         slot = np.asarray(slots, dtype=np.int64).reshape(-1)
         if mode == "feed":
@@ -434,7 +567,7 @@ class JitterScorer(_Front):
             if over.size:
                 raise ValueError(f"slot {U[over[0]]} would hold {after[over[0]]} pending samples, more than max_pending = "
                                  f"{self.max_pending} hops of {hop}: drain it first")
-        gaps = self._take_gaps(b, U, tgt)
+        gaps, noise = self._take_gaps(b, U, tgt)
         pos = np.full(self.S, -1, dtype=np.int64)
         pos[U] = np.arange(U.size)
         pu, pstart, pn, poff, penc = pos[pl[0]], pl[1], pl[2], pl[3], pl[4]
@@ -458,6 +591,17 @@ class JitterScorer(_Front):
             # release what is due, the window holds and the pending ring has room for
             made = -(-cur * L // M)
             m = np.maximum(np.minimum(np.minimum(tgt - cur, W), (made + R - fill) * M // L - cur), 0)
+            rows = []
+            for u, nl in noise.items():  # the noise parts inside [cur, cur + m): one launch (noise has no source, so no ranks)
+                c0, c1, s, Ju = int(cur[u]), int(cur[u] + m[u]), int(U[u]), int(J[u])
+                tail = (int(rate[u]),) if self._rated else ()
+                for lo, hi, level in nl:
+                    lo, hi = max(lo, c0), min(hi, c1)
+                    if lo < hi:
+                        rows.append((s, lo % Ju, hi - lo, lo & _M32, lo >> 32, level) + tail)
+            if rows:
+                rows = np.array(rows, dtype=np.int64)
+                ops.append(("noise", rows.astype(np.int32), int(rows[:, 2].max())))  # (lo32 keeps its bits as an int32)
             ranks = []
             for u, gl in gaps.items():  # the gaps inside [cur, cur + m) of the slots that have any, by rank within the slot
                 c0, c1, s, rank, Fu, Ju = int(cur[u]), int(cur[u] + m[u]), int(U[u]), 0, int(F[u]), int(J[u])
@@ -536,7 +680,7 @@ class JitterScorer(_Front):
             raise ValueError(f"a timestamp outside {low}..{lim - 1}" + (f" (ts_bits = {self.ts_bits})" if self.ts_bits else ""))
         return vals.astype(np.int64)
 
-    def feed(self, packets, slots, timestamps, score=True, _seqs=None, encodings=None):
+    def feed(self, packets, slots, timestamps, score=True, _seqs=None, encodings=None, _marks=None):
         """packets[i]: a packet of slot slots[i] whose first sample has timestamp timestamps[i] (Python ints or an int64
         array, in input-rate samples), any length, in any order; a slot may be named more than once (its rows are taken in
         the order given).  Afterwards each named slot has released [next, max(next, hi - depth)).  score=True: every hop a
@@ -544,10 +688,10 @@ class JitterScorer(_Front):
         more than ``max_pending`` hops is a ValueError).  Everything is checked before anything changes.  -> FeedResult
         with one count per row of ``slots`` (a slot named twice has its hops at its first row).  ``encodings``: the encoding
         of every packet, each one of this scorer's listed encodings (None: the first listed, for all)."""
-        return self._run(*self._plan_feed(packets, slots, timestamps, score, _seqs, encodings))
+        return self._run(*self._plan_feed(packets, slots, timestamps, score, _seqs, encodings, _marks))
 
-    def _plan_feed(self, packets, slots, timestamps, score=True, seqs=None, encodings=None):
-        """The checks and the plan of a ``feed`` -> (Plan, payload blocks).  No state changes."""
+    def _plan_feed(self, packets, slots, timestamps, score=True, seqs=None, encodings=None, marks=None):
+        """The checks and the plan of a ``feed`` -> (Plan, payload blocks).  No state changes.  ``marks``: as for ``_plan``."""
         idx = self._rows(slots, repeats=True)
         ri = self._rate_of[np.asarray(idx, dtype=np.int64)]
         if encodings is None:  # the first listed at each slot's rate
@@ -574,23 +718,78 @@ class JitterScorer(_Front):
         offs, total = layout(nbytes)
         if total >= 1 << 31:
             raise ValueError("a feed carries less than 2 GiB")
-        return self._plan(idx, nbytes // bps, ts, offs, seqs, "feed", score=score, encs=encs), pay
+        return self._plan(idx, nbytes // bps, ts, offs, seqs, "feed", score=score, encs=encs, marks=marks), pay
+
+    def silence(self, slots, timestamps, levels):
+        """Silence marks (module docstring): from timestamps[i] on, slot slots[i] is silent with a background noise
+        ``levels[i]`` dB below overload (an int in 0..127).  A slot may be named more than once; timestamps as for ``feed``.
+        Host only: nothing is released or launched.  Everything is checked before anything changes; a scorer without a
+        ``ComfortNoise`` refuses."""
+        if self.cn is None:
+            raise ValueError("silence: this scorer has no ComfortNoise (comfort_noise=)")
+        idx = self._rows(slots, repeats=True)
+        ts = self._timestamps(timestamps, len(idx))
+        b = self._b.copy()
+        self._mark_rows(b, idx, ts.tolist(), self._levels(levels, len(idx)))
+        self._commit(b)
+
+    @staticmethod
+    def _levels(levels, n):
+        if isinstance(levels, (torch.Tensor, np.ndarray)):
+            levels = levels.tolist()
+        if isinstance(levels, (str, bytes)) or not hasattr(levels, "__len__") or len(levels) != n:
+            raise ValueError(f"levels: one int in 0..127 per named slot ({n})")
+        for l in levels:
+            if isinstance(l, bool) or not isinstance(l, (int, np.integer)) or not 0 <= l <= 127:
+                raise ValueError(f"level {l!r}: an int in 0..127")
+        return [int(l) for l in levels]
 
     def _rtp_types(self, payload_types):
         """What ``feed_rtp`` looks a payload type up in: 0 is mulaw and 8 alaw (RFC 3551), ``payload_types`` adds to them."""
-        return {**rtp.STATIC_PAYLOAD_TYPES, **(payload_types or {})}
+        cn = {} if self.cn is None else {rtp.CN_PAYLOAD_TYPE: "cn"}
+        return {**rtp.STATIC_PAYLOAD_TYPES, **cn, **(payload_types or {})}
 
     def _rtp_encoding(self, s, pt, types):
-        """The encoding of a datagram of slot s with payload type pt, or the ValueError."""
+        """The encoding of a datagram of slot s with payload type pt ("cn": a silence mark), or the ValueError."""
+        if self.cn is not None and types.get(pt) == "cn":
+            return "cn"
         if types.get(pt) not in self.encodings:
             raise ValueError(f"slot {s}: RTP payload type {pt} is not this scorer's {' / '.join(self.encodings)}")
         return types[pt]
 
-    def feed_rtp(self, datagrams, slots, payload_types=None, score=True):
+    def feed_rtp(self, datagrams, slots, payload_types=None, score=True, ignore_types=()):
         """datagrams[i]: one RTP datagram (RFC 3550) of slot slots[i].  Its payload type must name this scorer's encoding (one
         of its listed encodings): 0 is mulaw and 8 alaw (RFC 3551), ``payload_types`` ({number: encoding}) adds the dynamic
         ones; its SSRC must be the session's (the first datagram after ``reset`` sets it).  Placement uses the timestamps; the sequence numbers only
-        count packets out of order for ``stats()``.  Anything else is a ValueError before anything changes."""
+        count packets out of order for ``stats()``.  Anything else is a ValueError before anything changes.
+        With a ``ComfortNoise``, a datagram of type 13 (RFC 3389), or of a type ``payload_types`` maps to "cn", is a
+        silence mark at its timestamp with level payload[0] & 0x7f (an empty payload is a ValueError); all marks of a call
+        are registered before its audio is planned.  ``ignore_types``: datagrams of these payload types (RFC 4733
+        telephone-events, typically 101) are parsed and SSRC-checked, then dropped.  Marks and dropped datagrams count 0
+        hops at their rows; a slot's hops are at its first audio row."""
+        args, kw, audio, n, ssrc = self._rtp_rows(datagrams, slots, payload_types, ignore_types)
+        res = self.feed(*args, score=score, **kw)
+        for s, v in ssrc.items():
+            self._b.ssrc[s] = v
+        if len(audio) != n:  # the hops of the audio rows at their places among all rows
+            counts = torch.zeros(n, dtype=torch.int64)
+            counts[audio] = res.counts
+            res = type(res)(counts, res.scores)
+        return res
+
+    def _plan_rtp(self, datagrams, slots, payload_types=None, score=True, ignore_types=()):
+        """The checks and the plan of a ``feed_rtp`` -> (Plan, payload blocks, {slot: its session's SSRC}).  No state changes."""
+        args, kw, audio, n, ssrc = self._rtp_rows(datagrams, slots, payload_types, ignore_types)
+        plan, pay = self._plan_feed(*args, score, kw["_seqs"], kw["encodings"], kw.get("_marks"))
+        if len(audio) != n:
+            counts = np.zeros(n, dtype=np.int64)
+            counts[audio] = plan.counts
+            plan.counts = counts
+        return plan, pay, ssrc
+
+    def _rtp_rows(self, datagrams, slots, payload_types, ignore_types):
+        """The checks of a ``feed_rtp`` -> (the positional and keyword arguments of the ``feed`` of its audio rows, their
+        positions among all rows, the number of rows, {slot: its session's SSRC}).  No state changes."""
         idx = self._rows(slots, repeats=True)
         if isinstance(datagrams, (bytes, bytearray, memoryview)):
             raise ValueError("datagrams: a list with one datagram per named slot")
@@ -600,17 +799,30 @@ class JitterScorer(_Front):
         if self.ts_bits != 32:
             raise ValueError("feed_rtp: RTP timestamps are 32 bits wide (ts_bits = 32)")
         types = self._rtp_types(payload_types)
-        ssrc, encs = {}, []
-        for s, p in zip(idx, pk):
-            encs.append(self._rtp_encoding(s, p.payload_type, types))
+        try:
+            ignore = frozenset(ignore_types)
+        except TypeError:
+            ignore = None
+        if ignore is None or any(isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 0 <= t <= 127 for t in ignore):
+            raise ValueError("ignore_types: payload type numbers, 0..127")
+        ssrc, encs, audio, marks = {}, [], [], ([], [], [])
+        for i, (s, p) in enumerate(zip(idx, pk)):
+            enc = None if p.payload_type in ignore else self._rtp_encoding(s, p.payload_type, types)
             mine = ssrc.setdefault(s, int(self._b.ssrc[s]) if self._b.ssrc[s] >= 0 else p.ssrc)
             if p.ssrc != mine:
                 raise ValueError(f"slot {s}: SSRC {p.ssrc:#010x} is not the session's {mine:#010x}")
-        res = self.feed([p.payload for p in pk], idx, [p.timestamp for p in pk], score=score, _seqs=[p.seq for p in pk],
-                        encodings=encs if self._mixed else None)
-        for s, v in ssrc.items():
-            self._b.ssrc[s] = v
-        return res
+            if enc == "cn":
+                if not len(p.payload):
+                    raise ValueError(f"slot {s}: a comfort-noise datagram without a payload (RFC 3389: the first byte is the level)")
+                for col, v in zip(marks, (s, p.timestamp, p.payload[0] & 0x7F)):
+                    col.append(v)
+            elif enc is not None:
+                audio.append(i)
+                encs.append(enc)
+        kw = dict(_seqs=[pk[i].seq for i in audio], encodings=encs if self._mixed else None)
+        if marks[0]:
+            kw["_marks"] = marks
+        return ([pk[i].payload for i in audio], [idx[i] for i in audio], [pk[i].timestamp for i in audio]), kw, audio, len(idx), ssrc
 
     def flush(self, slots=None, score=True):
         """The named (default: all) slots release everything received, up to ``hi`` -> FeedResult."""
@@ -656,8 +868,12 @@ class JitterScorer(_Front):
             check(call_on(self.jring, l.afx_k_jitter_release, ptr(self.jring), S, J, _at(d, off), len(op[1]), op[2], taps, L, M, T,
                           ptr(self.ring), self.ring_len))
 
-        return self._execute(plan.ops, plan.slots, plan.counts, pay, {"place": place, "conceal": conceal, "release": release},
-                             lambda: self._commit(plan.book))
+        def noise(d, off, op):
+            check(call_on(self.jring, l.afx_k_jitter_noise, ptr(self.jring), S, J, _at(d, off), len(op[1]), op[2], self.cn.seed,
+                          ptr(self._amp)))
+
+        return self._execute(plan.ops, plan.slots, plan.counts, pay,
+                             {"place": place, "noise": noise, "conceal": conceal, "release": release}, lambda: self._commit(plan.book))
 
     # ---- sessions ----------------------------------------------------------------------------------------------------
     def reset(self, slots):
@@ -670,7 +886,19 @@ class JitterScorer(_Front):
 
     def _meta(self):
         return dict(input_rate=self.input_rate, resampler=FILTER_ID, jitter=JITTER_FORMAT, jitter_depth=self.depth,
-                    jitter_conceal=self.conceal, jitter_period=self.period, jitter_fade=self.fade_len)
+                    jitter_conceal=self.conceal, jitter_period=self.period, jitter_fade=self.fade_len, **self._cn_meta())
+
+    def _cn_meta(self):
+        return {} if self.cn is None else dict(jitter_cn=self.cn.seed)
+
+    def _cn_part(self, state, mine):
+        """What ``peel`` takes of ``state``'s comfort-noise part -> (its state keys, ``mine`` as far as the state must match
+        it).  A state with marks is refused by a scorer without a ``ComfortNoise``; a state without them imports with none."""
+        has = isinstance(state, StreamState) and "jitter_cn" in state.meta
+        if has and self.cn is None:
+            raise ValueError(f"import_slots: the state carries comfort noise (jitter_cn {state.meta['jitter_cn']!r}) and this scorer "
+                             "has no ComfortNoise")
+        return (_CN_KEYS, mine) if has else ((), {k: v for k, v in mine.items() if k != "jitter_cn"})
 
     def export_slots(self, slots):
         """The inner scorer's ``StreamState`` of the named slots plus their jitter-buffer sessions (module docstring).  What is
@@ -697,6 +925,15 @@ class JitterScorer(_Front):
                 table[i, :len(v)] = v
         book = np.stack([getattr(b, f)[idx] for f in _BOOK], axis=1).reshape(len(idx), len(_BOOK))
         stats = np.stack([getattr(b, f)[idx] for f in _COUNTERS], axis=1).reshape(len(idx), len(_COUNTERS))
+        if self.cn is not None:
+            marks = [b.marks.get(s, []) for s in idx]
+            mt = np.full((len(idx), max([len(v) for v in marks] + [1]), 2), -1, dtype=np.int64)
+            for i, v in enumerate(marks):
+                if v:
+                    mt[i, :len(v)] = v
+            cstats = np.stack([getattr(b, f)[idx] for f in _CN_COUNTERS], axis=1).reshape(len(idx), len(_CN_COUNTERS))
+            more = dict(more, jitter_cn_marks=torch.from_numpy(mt), jitter_cn_open=torch.from_numpy(b.cn_open[idx]),
+                        jitter_cn_stats=torch.from_numpy(cstats))
         return wrap(st, self._meta(), jitter_pending=export_pending(self.ring, idx, b.head[idx], b.fill[idx], self.max_pending * self.hop),
                     jitter_fill=torch.from_numpy(b.fill[idx]), jitter_ring=jr, jitter_book=torch.from_numpy(book),
                     jitter_stats=torch.from_numpy(stats), jitter_intervals=torch.from_numpy(table), **more)
@@ -704,9 +941,11 @@ class JitterScorer(_Front):
     def import_slots(self, slots, state):
         """The named slots take over the sessions of ``state``, a state of a JitterScorer with the same input rate, filter,
         depth, concealment mode, period and fade whose pending samples fit this scorer's ``max_pending``; anything else,
-        or a state whose counters contradict each other, is a ValueError before anything changes."""
+        or a state whose counters contradict each other, is a ValueError before anything changes.  Comfort noise: a state
+        with silence marks needs a ``ComfortNoise`` of its seed here; one without them imports with no marks."""
         idx = self.scorer._slot_list(slots, ordered=True)
-        inner = peel(state, _STATE_KEYS, self._meta(), "jitter-buffer part (it was not exported by a JitterScorer)")
+        keys, mine = self._cn_part(state, self._meta())
+        inner = peel(state, _STATE_KEYS + keys, mine, "jitter-buffer part (it was not exported by a JitterScorer)")
         n = len(state)
         width = self.lookback + self.depth
         jr = state.tensors["jitter_ring"]
@@ -742,12 +981,32 @@ class JitterScorer(_Front):
             if not ok or (not v and hi[i] != nxt[i]) or sum(e - a for a, e in v) > stats[i, 0]:
                 raise ValueError("import_slots: a session's received intervals contradict its counters")
             lists.append(v)
-        return pend, state.tensors["jitter_ring"], fill, col, stats, lists, rate
+        cn = None
+        if "jitter_cn" in state.meta:
+            ints = [state.tensors[k].cpu() for k in _CN_KEYS]
+            if any(t.dtype != torch.int64 for t in ints):
+                raise ValueError("import_slots: jitter_cn_marks, jitter_cn_open and jitter_cn_stats are int64")
+            mt, opened, cstats = (t.numpy() for t in ints)
+            opened = opened.reshape(-1)
+            if mt.ndim != 3 or mt.shape[0] != n or mt.shape[2] != 2 or opened.size != n or cstats.shape != (n, len(_CN_COUNTERS)):
+                raise ValueError("import_slots: jitter_cn_marks (n, K, 2), jitter_cn_open (n,), jitter_cn_stats (n, 3)")
+            if ((opened < -1) | (opened > 127) | ((opened >= 0) & (gap < 0)) | (cstats < 0).any(axis=1) |
+                    (cstats[:, 0] + stats[:, 3] > nxt)).any():
+                raise ValueError("import_slots: a session's comfort-noise counters contradict each other")
+            marks = []
+            for i in range(n):
+                v = [r for r in mt[i].tolist() if r != [-1, -1]]
+                if not all(t >= nxt[i] and 0 <= l <= 127 for t, l in v) or not all(p[0] < q[0] for p, q in zip(v, v[1:])) or \
+                        len(v) > cstats[i, 1]:
+                    raise ValueError("import_slots: a session's silence marks contradict its counters")
+                marks.append(v)
+            cn = (marks, opened, cstats)
+        return pend, state.tensors["jitter_ring"], fill, col, stats, lists, rate, cn
 
     def _install(self, idx, inner, checked):
         """The inner scorer imports ``inner`` (it refuses a foreign state before changing anything), then the named slots take
         the checked jitter part: ring columns [next - lookback, ...) at their places modulo each session's own J."""
-        pend, jr, fill, col, stats, lists, rate = checked
+        pend, jr, fill, col, stats, lists, rate, cn = checked
         self.scorer.import_slots(idx, inner)
         if not idx:
             return
@@ -772,6 +1031,13 @@ class JitterScorer(_Front):
         b.fill[idx] = fill
         for s_, v in zip(idx, lists):
             b.set_intervals(s_, v)
+        if cn is not None:
+            marks, b.cn_open[idx], cstats = cn
+            for c, f in enumerate(_CN_COUNTERS):
+                getattr(b, f)[idx] = cstats[:, c]
+            for s_, v in zip(idx, marks):
+                if v:
+                    b.marks[s_] = v
 
 
 def _fade_table(F, device):
@@ -787,11 +1053,13 @@ class MixedJitterScorer(JitterScorer):
     that rate's samples.  A slot's rate is chosen at ``reset`` (a fresh scorer has every slot at the first format's rate)
     and never changes between resets; everything a ``JitterScorer`` counts in input samples is, per slot, in the slot's own
     rate.  ``feed_rtp`` takes ``payload_types`` as {number: (input_rate, encoding)}.  See the module docstring for the
-    contract."""
+    contract.  ``comfort_noise``: as for ``JitterScorer``; a CN payload type maps to (input_rate, "cn"), in the slot's clock
+    (13 is (8000, "cn"), RFC 3551)."""
 
     _rated = True
 
-    def __init__(self, scorer, formats, depth_ms, conceal="repeat", period_ms=None, fade_ms=None, max_pending=4, ts_bits=32):
+    def __init__(self, scorer, formats, depth_ms, conceal="repeat", period_ms=None, fade_ms=None, max_pending=4, ts_bits=32,
+                 comfort_noise=None):
         if isinstance(formats, (str, bytes)) or not hasattr(formats, "__len__") or not hasattr(formats, "__iter__"):
             raise ValueError("formats: a sequence of (input_rate, encoding) pairs")
         fm = tuple(_format(f) for f in formats)
@@ -802,7 +1070,7 @@ class MixedJitterScorer(JitterScorer):
         depth_ms = _nonneg_int(depth_ms, "depth_ms")
         period_ms = None if period_ms is None else _nonneg_int(period_ms, "period_ms")
         fade_ms = None if fade_ms is None else _nonneg_int(fade_ms, "fade_ms")
-        max_pending = self._checked(conceal, max_pending, ts_bits)
+        max_pending = self._checked(conceal, max_pending, ts_bits, comfort_noise)
         self.scorer, self.formats, self._mixed = scorer, fm, True
         self.depth_ms, self.period_ms, self.fade_ms = depth_ms, period_ms, fade_ms
         rates = tuple(dict.fromkeys(r for r, _ in fm))  # the distinct rates, in the order first listed
@@ -877,12 +1145,18 @@ class MixedJitterScorer(JitterScorer):
         (8000, "mulaw") and (8000, "alaw") (RFC 3551).  A datagram whose type maps to another rate than its slot's, or to a
         pair this scorer does not list, is a ValueError before anything changes."""
         types = {pt: (8000, e) for pt, e in rtp.STATIC_PAYLOAD_TYPES.items()}
-        types.update((pt, _format(f)) for pt, f in (payload_types or {}).items())
+        if self.cn is not None:
+            types[rtp.CN_PAYLOAD_TYPE] = (8000, "cn")
+        cn = lambda f: self.cn is not None and isinstance(f, (tuple, list)) and len(f) == 2 and f[1] == "cn" and f[0] in self._rates
+        types.update((pt, (int(f[0]), "cn") if cn(f) else _format(f)) for pt, f in (payload_types or {}).items())
         return types
 
     def _rtp_encoding(self, s, pt, types):
         f, mine = types.get(pt), self._rates[self._rate_of[s]]
-        if f not in self.formats:
+        cn = self.cn is not None and f is not None and f[1] == "cn"  # a silence mark, in the slot's clock
+        if cn and f[0] == mine:
+            return "cn"
+        if not cn and f not in self.formats:
             raise ValueError(f"slot {s}: RTP payload type {pt} maps to none of this scorer's formats {self.formats}")
         if f[0] != mine:
             raise ValueError(f"slot {s}: RTP payload type {pt} is {f[0]} Hz, the slot is at {mine} Hz")
@@ -907,8 +1181,12 @@ class MixedJitterScorer(JitterScorer):
             check(call_on(self.jring, l.afx_k_jitter_release_rates, ptr(self.jring), S, Js, _at(d, off), len(rows), table, nr,
                           most.ctypes.data_as(C.c_void_p), ptr(self.ring), self.ring_len))
 
-        return self._execute(plan.ops, plan.slots, plan.counts, pay, {"place": place, "conceal": conceal, "release": release},
-                             lambda: self._commit(plan.book))
+        def noise(d, off, op):
+            check(call_on(self.jring, l.afx_k_jitter_noise_rates, ptr(self.jring), S, Js, _at(d, off), len(op[1]), op[2], table, nr,
+                          self.cn.seed, ptr(self._amp)))
+
+        return self._execute(plan.ops, plan.slots, plan.counts, pay,
+                             {"place": place, "noise": noise, "conceal": conceal, "release": release}, lambda: self._commit(plan.book))
 
     # ---- sessions --------------------------------------------------------------------------------------------------------
     def reset(self, slots, rates=None):
@@ -921,7 +1199,7 @@ class MixedJitterScorer(JitterScorer):
             self._rate_of[idx] = new
 
     def _meta(self):
-        return dict(resampler=FILTER_ID, jitter=JITTER_FORMAT, jitter_conceal=self.conceal, jitter_mixed=1)
+        return dict(resampler=FILTER_ID, jitter=JITTER_FORMAT, jitter_conceal=self.conceal, jitter_mixed=1, **self._cn_meta())
 
     def export_slots(self, slots):
         """``JitterScorer.export_slots`` with the per-session ``jitter_rate`` ((n,) int64, Hz) and ``jitter_params`` ((n, 3)
@@ -946,11 +1224,13 @@ class MixedJitterScorer(JitterScorer):
                 raise ValueError(f"import_slots: a session at {rate} Hz, which is none of this scorer's rates {self._rates}")
             r = self._rates.index(rate)
             mine = dict(input_rate=rate, resampler=FILTER_ID, jitter=JITTER_FORMAT, jitter_depth=int(self._rdepth[r]),
-                        jitter_conceal=self.conceal, jitter_period=int(self._rP[r]), jitter_fade=int(self._rF[r]))
-            inner = peel(state, _STATE_KEYS, mine, what)
+                        jitter_conceal=self.conceal, jitter_period=int(self._rP[r]), jitter_fade=int(self._rF[r]), **self._cn_meta())
+            keys, mine = self._cn_part(state, mine)
+            inner = peel(state, _STATE_KEYS + keys, mine, what)
             ri = np.full(n, r, dtype=np.int64)
         else:
-            inner = peel(state, _STATE_KEYS + ("jitter_rate", "jitter_params"), self._meta(), what)
+            keys, mine = self._cn_part(state, self._meta())
+            inner = peel(state, _STATE_KEYS + ("jitter_rate", "jitter_params") + keys, mine, what)
             rates, params = state.tensors["jitter_rate"].cpu().reshape(-1), state.tensors["jitter_params"].cpu()
             if rates.dtype != torch.int64 or rates.numel() != n or params.dtype != torch.int64 or tuple(params.shape) != (n, 3):
                 raise ValueError("import_slots: jitter_rate is (n,) int64, jitter_params (n, 3) int64")

@@ -8,6 +8,8 @@ import collections
 Packet = collections.namedtuple("Packet", "seq timestamp payload_type ssrc marker payload")
 
 STATIC_PAYLOAD_TYPES = {0: "mulaw", 8: "alaw"}  # RFC 3551: PCMU, PCMA (8 kHz; the RTP clock is the sample rate)
+CN_PAYLOAD_TYPE = 13  # RFC 3389 comfort noise (8 kHz clock, RFC 3551): payload[0] & 0x7f is the noise level in -dBov; a
+# jitter scorer with a ComfortNoise takes it as a silence mark (other clock rates negotiate a dynamic type for it)
 
 
 def parse(datagram):

@@ -2866,6 +2866,14 @@ extern "C" int afx_k_jitter_release_rates(const float* jring, int S, int Js, con
   KRET(launch_jitter_release_rates(jring, S, Js, hdr, rows, (const JitterRateDesc*)rates, n_rates, max_out, ring, ring_len,
                                    (hipStream_t)stream));
 }
+extern "C" int afx_k_jitter_noise(float* jring, int S, int J, const int* hdr, int rows, int max_n, unsigned seed, const float* amp,
+                                  void* stream) {
+  KRET(launch_jitter_noise(jring, S, J, hdr, rows, max_n, seed, amp, (hipStream_t)stream));
+}
+extern "C" int afx_k_jitter_noise_rates(float* jring, int S, int Js, const int* hdr, int rows, int max_n, const afx_jitter_rate* rates,
+                                        int n_rates, unsigned seed, const float* amp, void* stream) {
+  KRET(launch_jitter_noise_rates(jring, S, Js, hdr, rows, max_n, (const JitterRateDesc*)rates, n_rates, seed, amp, (hipStream_t)stream));
+}
 extern "C" int afx_k_gate(const float* x, int A, int n, const int* hdr, int frame, float e_floor, float ratio, float rise,
                           int hang, float* nf, int* h, float* ring, int S, int ring_len, int* kept, unsigned char* mask,
                           void* stream) {

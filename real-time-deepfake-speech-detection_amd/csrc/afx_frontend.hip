@@ -1091,12 +1091,15 @@ const char* launch_ingest_pop(const float* ring, int S, int ring_len, const int*
 // indices in [cur - lookback, cur + W): a window of J consecutive indices, so no two of them share a column.  That is the
 // sizing invariant: what place writes at i >= cur destroys only i - J < cur - lookback, which neither the filter (T - 1
 // samples back) nor a fading gap (source [a - P, a), read until a + F) will read again.
-// Three verbs, one kernel and one row body each:
+// Four verbs, one kernel and one row body each:
 //   place:   decodes sub-ranges of packets into their columns (the rows of one launch are disjoint: the host splits a packet
 //            at the playout point and at what was received before; first arrival wins).
 //   conceal: writes a released gap's samples INTO the ring (zeros, or the faded repetition of the P samples before the
 //            gap), so that a later gap, and the filter, read them as they read received samples.  Gaps of one slot are
 //            ordered by the host: one launch per rank of gap within the slot.
+//   noise:   writes the comfort-noise part of a released gap INTO the ring (RFC 3389 silence, afx_k_jitter_noise): a hash
+//            of the 64-bit stream index and the seed times the level's amplitude.  No source, so no ranks: one launch per
+//            round, before the conceal ranks (a loss gap whose source holds this round's noise then reads it).
 //   release: polyphase_tiles (above) with the source = ring[(a0 + k) mod J], k >= -(T-1), and the sink = the slot's pending
 //            16 kHz ring: outputs n_done .. of the stream, each with the bits afx_k_resample gives it over all of E.
 // The rates of a launch (at most JIT_MAX_RATES) travel by value in the argument struct; a row names its rate by an index, the
@@ -1111,6 +1114,8 @@ constexpr int JIT_MAX_RATES = 16;
 constexpr int JIT_PLACE_HDR = 4, JIT_PLACE_MIXED_HDR = 5, JIT_PLACE_RATES_HDR = 6;
 constexpr int JIT_CONCEAL_HDR = 4, JIT_CONCEAL_RATES_HDR = 5;
 constexpr int JIT_RELEASE_HDR = 8;
+// noise: slot, ring column of the first index, n, lo32(i0), hi32(i0), level [, rate index]
+constexpr int JIT_NOISE_HDR = 6, JIT_NOISE_RATES_HDR = 7;
 
 struct JitterRate {
   PolyFilter f;                  // Tp, R from poly_grid (release only)
@@ -1129,6 +1134,8 @@ struct JitterRatesArgs {
   int hdr_ints;                  // the row stride
   int enc;                       // place: the encoding of rows of JIT_PLACE_HDR ints (longer rows name their own, the fifth int)
   int rated;                     // the last int of a row is its rate index (else every row is at rate 0)
+  unsigned seed;                 // noise
+  const float* amp;              // noise: (128,) fp32, the amplitude of each level
   JitterRate r[JIT_MAX_RATES];
 };
 
@@ -1193,6 +1200,37 @@ __global__ __launch_bounds__(256) void jitter_conceal_kernel(JitterRatesArgs m) 
   jitter_conceal_row(m.jring, m.S, m.r[ri].J, m.Js, h, m.r[ri].fade, m.r[ri].P, m.r[ri].F, m.mode);
 }
 
+// E[i] = amp * fp32(k(seed, i)): a 32-bit hash of the 64-bit index i (all integer arithmetic mod 2^32), its top 24 bits as
+// a signed integer (exactly an fp32 number), one fp32 multiply
+__device__ __forceinline__ float jitter_noise_value(unsigned long long i, unsigned seed, float amp) {
+  unsigned x = (unsigned)i * 0x9E3779B9u + (unsigned)(i >> 32) * 0x85EBCA6Bu + seed;
+  x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
+  return amp * (float)((int)x >> 8);
+}
+
+// one row of a noise launch: h[0..5] = slot, column of index i0, n, lo32(i0), hi32(i0), level; the slot's ring is the first J
+// columns of a row of `stride` floats
+__device__ __forceinline__ void jitter_noise_row(float* __restrict__ jring, int S, int J, int stride, const int* h, unsigned seed,
+                                                 const float* __restrict__ amp) {
+  const int slot = h[0], col = h[1], n = h[2], level = h[5];
+  if (!(slot >= 0 && slot < S && col >= 0 && col < J && n >= 0 && n <= J && level >= 0 && level <= 127 && h[4] >= 0)) return;
+  const unsigned long long i0 = ((unsigned long long)(unsigned)h[4] << 32) | (unsigned)h[3];
+  const float a = amp[level];
+  float* row = jring + (long long)slot * stride;
+  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += gridDim.x * blockDim.x) {
+    const int w = col + k;
+    row[w < J ? w : w - J] = jitter_noise_value(i0 + (unsigned long long)k, seed, a);
+  }
+}
+
+// a row with a bad rate index is skipped whole
+__global__ __launch_bounds__(256) void jitter_noise_kernel(JitterRatesArgs m) {
+  int ri;
+  const int* h = jitter_row(m, ri);
+  if (ri < 0 || ri >= m.nr) return;
+  jitter_noise_row(m.jring, m.S, m.r[ri].J, m.Js, h, m.seed, m.amp);
+}
+
 // sample k of the released range that starts at ring column col0 (zeros past its end: never reached by an output the host
 // counted); k >= -(T-1) >= -J and k < n_in <= J, so one wrap either way
 struct RingSource {
@@ -1238,7 +1276,7 @@ __global__ __launch_bounds__(256) void jitter_release_kernel(JitterRatesArgs m) 
   else jitter_release_row<false, false>(m, f, m.r[ri].J, h);
 }
 
-enum JitterVerb { JIT_PLACE, JIT_CONCEAL, JIT_RELEASE };
+enum JitterVerb { JIT_PLACE, JIT_CONCEAL, JIT_RELEASE, JIT_NOISE };
 
 static const char* jitter_msg(const char* who, const char* what) {
   static thread_local char msg[160];
@@ -1252,7 +1290,7 @@ static const char* jitter_msg(const char* who, const char* what) {
 static const char* jitter_launch(const char* who, JitterVerb verb, JitterRatesArgs m, const JitterRateDesc* rates, int n_rates,
                                  int rows, const int* most, hipStream_t s) {
   const bool repeat = verb == JIT_CONCEAL && m.mode == 1;
-  const char* fit = verb == JIT_PLACE ? "a row's samples must fit its slot's ring"
+  const char* fit = verb == JIT_PLACE || verb == JIT_NOISE ? "a row's samples must fit its slot's ring"
                   : verb == JIT_CONCEAL ? "a row's samples and its source must fit the ring" : "a row's outputs must fit its slot's ring";
   if (verb == JIT_CONCEAL && m.mode != 0 && m.mode != 1) return jitter_msg(who, "mode 0 (zero) or 1 (repeat)");
   if (verb == JIT_PLACE && m.hdr_ints == JIT_PLACE_HDR && (m.enc < 0 || m.enc > 3))
@@ -1262,6 +1300,7 @@ static const char* jitter_launch(const char* who, JitterVerb verb, JitterRatesAr
   if (!most) return jitter_msg(who, "null output counts");
   if (!m.hdr || !m.jring || (verb == JIT_PLACE && (!m.stage || m.stage_bytes <= 0)) || (verb == JIT_RELEASE && !m.ring))
     return jitter_msg(who, verb == JIT_PLACE ? "null staging buffer, header table or ring" : "null ring or header table");
+  if (verb == JIT_NOISE && !m.amp) return jitter_msg(who, "null amplitude table");
   if (rows <= 0 || rows > 65535) return jitter_msg(who, "1 to 65535 rows");
   // (a launch without rate indices has one rate whose ring is the whole row: a bad J there is a row that does not fit)
   const char* ring_fit = m.rated ? "a rate's ring must fit the ring's rows (1 <= J <= Js)" : fit;
@@ -1304,6 +1343,7 @@ static const char* jitter_launch(const char* who, JitterVerb verb, JitterRatesAr
   const dim3 grid((unsigned)gx, rows);
   if (verb == JIT_PLACE) hipLaunchKernelGGL(jitter_place_kernel, grid, dim3(256), 0, s, m);
   else if (verb == JIT_CONCEAL) hipLaunchKernelGGL(jitter_conceal_kernel, grid, dim3(256), 0, s, m);
+  else if (verb == JIT_NOISE) hipLaunchKernelGGL(jitter_noise_kernel, grid, dim3(256), 0, s, m);
   else hipLaunchKernelGGL(jitter_release_kernel, grid, dim3(256), lds, s, m);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? nullptr : hipGetErrorString(e);
@@ -1335,6 +1375,14 @@ static const char* jitter_release_launch(const char* who, const float* jring, in
   return jitter_launch(who, JIT_RELEASE, m, rates, n_rates, rows, max_out, s);
 }
 
+static const char* jitter_noise_launch(const char* who, float* jring, int S, int Js, const int* hdr, int hdr_ints, int rows, int max_n,
+                                       const JitterRateDesc* rates, int n_rates, unsigned seed, const float* amp, hipStream_t s) {
+  JitterRatesArgs m{};
+  m.hdr = hdr; m.jring = jring; m.S = S; m.Js = Js; m.seed = seed; m.amp = amp;
+  m.hdr_ints = hdr_ints; m.rated = hdr_ints == JIT_NOISE_RATES_HDR;
+  return jitter_launch(who, JIT_NOISE, m, rates, n_rates, rows, &max_n, s);
+}
+
 // the one-rate entry points: a table of one entry built from their scalar arguments, Js = J, rows without a rate index
 const char* launch_jitter_place(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n, int enc,
                                 float* jring, int S, int J, hipStream_t s) {
@@ -1361,7 +1409,18 @@ const char* launch_jitter_release(const float* jring, int S, int J, const int* h
   return jitter_release_launch("jitter_release", jring, S, J, hdr, false, rows, &one, 1, &max_out, ring, ring_len, s);
 }
 
+const char* launch_jitter_noise(float* jring, int S, int J, const int* hdr, int rows, int max_n, unsigned seed, const float* amp,
+                                hipStream_t s) {
+  const JitterRateDesc one{nullptr, nullptr, 1, 1, 1, J, 0, 0};
+  return jitter_noise_launch("jitter_noise", jring, S, J, hdr, JIT_NOISE_HDR, rows, max_n, &one, 1, seed, amp, s);
+}
+
 // the _rates entry points: the caller's table, rows that end in their rate index
+const char* launch_jitter_noise_rates(float* jring, int S, int Js, const int* hdr, int rows, int max_n, const JitterRateDesc* rates,
+                                      int n_rates, unsigned seed, const float* amp, hipStream_t s) {
+  return jitter_noise_launch("jitter_noise_rates", jring, S, Js, hdr, JIT_NOISE_RATES_HDR, rows, max_n, rates, n_rates, seed, amp, s);
+}
+
 const char* launch_jitter_place_rates(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n,
                                       const JitterRateDesc* rates, int n_rates, float* jring, int S, int Js, hipStream_t s) {
   return jitter_place_launch("jitter_place_rates", stage, stage_bytes, hdr, JIT_PLACE_RATES_HDR, rows, max_n, 0, rates,

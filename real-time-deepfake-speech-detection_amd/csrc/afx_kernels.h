@@ -199,6 +199,12 @@ const char* launch_jitter_conceal_rates(float* jring, int S, int Js, const int* 
                                         int n_rates, int mode, hipStream_t s);
 const char* launch_jitter_release_rates(const float* jring, int S, int Js, const int* hdr, int rows, const JitterRateDesc* rates,
                                         int n_rates, const int* max_out, float* ring, int ring_len, hipStream_t s);
+// comfort noise (include/afx.h afx_k_jitter_noise / _noise_rates): the noise parts of released gaps written into the ring; the
+// fourth verb, the same kernel shape as place (rows x 6 int32, or 7 with the rate index)
+const char* launch_jitter_noise(float* jring, int S, int J, const int* hdr, int rows, int max_n, unsigned seed, const float* amp,
+                                hipStream_t s);
+const char* launch_jitter_noise_rates(float* jring, int S, int Js, const int* hdr, int rows, int max_n, const JitterRateDesc* rates,
+                                      int n_rates, unsigned seed, const float* amp, hipStream_t s);
 // speech gate (include/afx.h afx_k_gate): per-slot energy gate with noise-floor tracking and hangover over the frames of each
 // row; the kept frames are compacted into the slot's pending ring, kept[i] = the samples kept of row i,
 // mask (optional) the keep flag of every frame

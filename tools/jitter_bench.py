@@ -7,6 +7,19 @@ random phase against the 250-ms hop), the student scores them in KV-cached mode.
   packets   afx.ingest.PacketScorer fed the same streams losslessly and in order, one packet per slot and tick: what the
             parent of the jitter front could do.
 
+  --dtx     silence suppression instead: talk-spurt traffic (about 40 % activity; spurts and pauses of geometric length, mean
+            1 s and 1.5 s), a CN mark (RFC 3389) at each spurt end and every 200 ms of silence, --loss of all datagrams lost, in
+            order.  Three scorers of this build in one process, the same inner scorer and call pattern as above:
+            every tick ``feed(..., score=False)`` with what arrived, then ``advance`` of all streams to the playout clock (a silent
+            stream sends nothing to release it), one ``drain()`` per hop:
+              dtx       a JitterScorer with comfort_noise: ``silence`` with the tick's marks before the ``feed``;
+              filtered  the same traffic with the CN datagrams removed, a JitterScorer without comfort_noise: every pause is a
+                        loss gap (what a caller could do before);
+              plain     ordinary traffic (every stream talks all the time), a JitterScorer without comfort_noise, for scale.
+            Whether ordinary traffic through a scorer without comfort_noise costs what it cost before is the default mode's
+            "jitter" line of this tree against the parent commit's on the same box.
+            --out FILE appends what was printed to FILE (profiles/jitter_dtx.txt).
+
     python tools/jitter_bench.py [--streams 2048] [--rate 8000] [--encoding mulaw] [--packet-ms 20] [--depth-ms 60]
                                  [--loss 0.02] [--reorder 0.1] [--hops 8] [--reps 3]
     rocprofv3 --kernel-trace --stats ... -- python tools/jitter_bench.py --profile   (jitter path only, 4 hops: kernel times)
@@ -29,10 +42,101 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "real-time-deepfake-speech-detection_am
 from afx import engine, synth  # noqa: E402
 from afx._lib import lib  # noqa: E402
 from afx.ingest import ENCODINGS, PacketScorer  # noqa: E402
-from afx.jitter import JitterScorer  # noqa: E402
+from afx.jitter import ComfortNoise, JitterScorer  # noqa: E402
 from afx.streaming import KVCachedScorer  # noqa: E402
 
 W, H = 64000, 4000
+
+
+def dtx(args, eng, sd):
+    """The --dtx measurement (module docstring)."""
+    S, rate, enc = args.streams, args.rate, args.encoding
+    bps = {"pcm_f32le": 4, "pcm_s16le": 2}.get(enc, 1)
+    pk = rate * args.packet_ms // 1000
+    depth = rate * args.depth_ms // 1000
+    hop_in = -(-H * rate // 16000)
+    ticks = args.hops * hop_in // pk
+    warm_ticks = (W // H + 2) * hop_in // pk
+    n_ticks = warm_ticks + (1 + args.reps) * ticks
+    g = np.random.default_rng(13)
+    data = {"pcm_f32le": lambda n: (0.1 * g.standard_normal(n)).astype("<f4"), "pcm_s16le": lambda n: g.integers(-4000, 4000, n).astype("<i2")
+            }.get(enc, lambda n: g.integers(0, 256, n).astype(np.uint8))
+    audio = [data(n_ticks * pk) for _ in range(S)]
+    origin = g.integers(0, 1 << 32, S)
+    # the senders: talking[s, k]; a two-state chain with mean spurt 1 s and mean pause 1.5 s (40 % activity)
+    p_stop, p_start = args.packet_ms / 1000.0, args.packet_ms / 1500.0
+    talking = np.ones((S, n_ticks), dtype=bool)
+    u = g.random((S, n_ticks))
+    for k in range(1, n_ticks):
+        talking[:, k] = np.where(talking[:, k - 1], u[:, k] >= p_stop, u[:, k] < p_start)
+    run_len = np.zeros(S, dtype=np.int64)  # ticks of silence so far
+    cn_at = np.zeros((S, n_ticks), dtype=bool)  # a CN at the spurt end and every 200 ms of silence
+    every = max(1, 200 // args.packet_ms)
+    for k in range(n_ticks):
+        run_len = np.where(talking[:, k], 0, run_len + 1)
+        cn_at[:, k] = ~talking[:, k] & ((run_len - 1) % every == 0)
+    level = g.integers(30, 71, (S, n_ticks))
+    lost = g.random((S, n_ticks)) < args.loss
+    lost[:, 0] = False  # (the first packet sets the origin)
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+
+    say(f"jitter_bench --dtx: build {lib().afx_build_id().decode()}; student fp16 (6 layers), KV-cached, {S} streams, {rate} Hz {enc}, "
+        f"{args.packet_ms}-ms packets ({pk * bps} bytes), depth {args.depth_ms} ms, loss {args.loss:.3f}, in order; activity "
+        f"{talking.mean():.3f}, {int(cn_at.sum())} CN datagrams; {args.hops} hops ({ticks} ticks) per pass, {args.reps} timed passes per "
+        f"path after a warm-up pass")
+    ts_of = lambda s, k: (int(origin[s]) + k * pk) % (1 << 32)
+    results = {}
+    for name in ("dtx", "filtered", "plain"):
+        inner = KVCachedScorer(eng, sd, S, window=W, hop=H)
+        front = JitterScorer(inner, rate, enc, depth, comfort_noise=ComfortNoise(1) if name == "dtx" else None)
+        calls = []
+        for k in range(n_ticks):
+            sent = ~lost[:, k] if name == "plain" else talking[:, k] & ~lost[:, k]
+            ss = np.flatnonzero(sent).tolist()
+            feed = ([audio[s][k * pk:(k + 1) * pk].tobytes() for s in ss], ss, np.array([ts_of(s, k) for s in ss], dtype=np.int64))
+            ms = np.flatnonzero(cn_at[:, k] & ~lost[:, k]).tolist() if name == "dtx" else []
+            calls.append((feed, (ms, np.array([ts_of(s, k) for s in ms], dtype=np.int64), level[ms, k].tolist()) if ms else None))
+
+        def run(t0, n):
+            torch.cuda.synchronize()
+            t_host, start = 0.0, time.perf_counter()
+            for t in range(t0, t0 + n):
+                feed, marks = calls[t]
+                a = time.perf_counter()
+                if marks is not None:
+                    front.silence(*marks)
+                front.feed(*feed, score=False)
+                front.advance(everyone, max(0, (t + 1) * pk - depth), score=False)  # the playout clock: a silent stream sends nothing
+                if ((t + 1) * pk) // hop_in > (t * pk) // hop_in:  # a hop's worth of audio has gone by: score
+                    front.drain()
+                t_host += time.perf_counter() - a
+            torch.cuda.synchronize()
+            return time.perf_counter() - start, t_host
+
+        everyone = list(range(S))
+        run(0, warm_ticks)
+        times, host = [], []
+        for r in range(1 + args.reps):
+            dt, th = run(warm_ticks + r * ticks, ticks)
+            if r > 0:
+                times.append(dt / args.hops)
+                host.append(th / args.hops)
+        times.sort()
+        host.sort()
+        med = results[name] = times[len(times) // 2]
+        st = {k: int(v.sum()) for k, v in front.stats().items()}
+        say(f"  {name:8s} {med * 1e3:8.2f} ms per 250 ms of audio (min {times[0] * 1e3:.2f}, max {times[-1] * 1e3:.2f}); host time inside "
+            f"silence / feed / drain calls {host[len(host) // 2] * 1e3:.2f} ms; RTF {med / 0.25:.3f}; stats over all streams {st}")
+        del front, inner
+        torch.cuda.empty_cache()
+    say(f"  dtx / filtered {results['dtx'] / results['filtered']:.2f}x, dtx / plain {results['dtx'] / results['plain']:.2f}x")
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
 
 
 def main():
@@ -47,6 +151,8 @@ def main():
     ap.add_argument("--hops", type=int, default=8, help="hops of audio per timed pass")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--profile", action="store_true", help="the jitter path only, a short pass (for a rocprofv3 run)")
+    ap.add_argument("--dtx", action="store_true", help="silence-suppression traffic through a comfort-noise scorer (see above)")
+    ap.add_argument("--out", default=None, help="--dtx: append the printed lines to this file")
     args = ap.parse_args()
     S, rate, enc = args.streams, args.rate, args.encoding
     bps = {"pcm_f32le": 4, "pcm_s16le": 2}.get(enc, 1)
@@ -58,6 +164,8 @@ def main():
     sd = synth.model_state_dict("ConformerModel", n_layers=6)
     eng = engine.Engine("conformer", n_layers=6, dtype="fp16")
     eng.load_state_dict(sd)
+    if args.dtx:
+        return dtx(args, eng, sd)
     passes = 1 if args.profile else 1 + args.reps
     hops = 4 if args.profile else args.hops
     ticks = hops * hop_in // pk
