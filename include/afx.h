@@ -350,6 +350,29 @@ int afx_k_ingest_mixed(const void* stage, long long stage_bytes, const int* hdr,
 /* out (A, hop) fp32: out[i][k] = ring[slot_i][(head_i + k) mod ring_len], table (device, A x 2 int32) = (slot_i, head_i):
  * the next hop of the named slots as the streaming scorers' push takes it.  The ring is only read. */
 int afx_k_ingest_pop(const float* ring, int S, int ring_len, const int* table, int A, int hop, float* out, void* stream);
+/* Payload expand (afx/codecs.py): the verb that runs before ingest / place.  The kernels above and below read a payload by
+ * random access; a payload they cannot index that way is first written as fp32 samples into another zone of the same staging
+ * buffer and read from there as encoding 0 (pcm_f32le).  stage (device, stage_bytes) is read AND written; hdr (device,
+ * rows x 4 int32), per row:
+ *     source byte offset in stage, source bytes B, destination byte offset in stage (a multiple of 4), codec number
+ * The row's n samples go to ((float*)(stage + destination))[0..n); the rows of one launch write disjoint ranges that no row
+ * reads.  Codec numbers, every decode exact in fp32:
+ *     0 dvi4       RFC 3551 4.5.1 (IMA ADPCM), the payload is ONE block: predict (int16, big-endian), index (uint8), one
+ *                  reserved byte, then 4-bit codes, the high nibble of each byte first; n = 2 (B - 4).  The header is the state
+ *                  before the first code.  Per code c, with the standard 89-entry step table and the index table
+ *                  (-1, -1, -1, -1, 2, 4, 6, 8) twice:
+ *                      step = STEP[index];  index = clamp(index + IDX[c], 0, 88)
+ *                      d = (step >> 3) + (c & 4 ? step : 0) + (c & 2 ? step >> 1 : 0) + (c & 1 ? step >> 2 : 0)
+ *                      pred = clamp(c & 8 ? pred - d : pred + d, -32768, 32767);  sample = pred / 32768
+ *     1 pcm_s16be  big-endian int16, v / 32768; n = B / 2
+ *     2 pcm_s24be  big-endian 24-bit two's complement, v / 8388608; n = B / 3
+ *     3 pcm_u8     offset-128 bytes, (b - 128) / 128; n = B
+ * One wave per DVI4 block: 64 codes a step, both recurrences as prefix scans over clamp-add maps, (pred, index) carried from
+ * step to step; the PCM codecs are a map.  max_n = the largest n of the launch.  A row is skipped whole, writing nothing, when
+ * its codec number is outside 0..3, its source splits a sample, it is a DVI4 block under 4 bytes or with header index > 88, or
+ * its source or destination leaves stage.  Refused with nothing launched, each with a message naming the entry point: a null
+ * stage / hdr, rows outside 1..65535, a max_n below 0 or beyond what stage can hold (4 max_n > stage_bytes). */
+int afx_k_payload_expand(void* stage, long long stage_bytes, const int* hdr, int rows, int max_n, void* stream);
 /* Jitter buffer (afx/jitter.py): per slot one DECODED reorder ring, jring (S, J) fp32; input-rate sample i of the slot's
  * played-out stream E (indexed from the session's first accepted timestamp) lives at column i mod J.  All indices are the
  * host's (playout point, received intervals, gaps); nothing is read back.  With lookback = max(T-1, P+F) the host keeps every

@@ -109,6 +109,7 @@ SIGNATURES = {
     "afx_k_ingest": (_I, [_P, C.c_longlong, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _I, _I, _P]),
     "afx_k_ingest_mixed": (_I, [_P, C.c_longlong, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _P]),
     "afx_k_ingest_pop": (_I, [_P, _I, _I, _P, _I, _I, _P, _P]),
+    "afx_k_payload_expand": (_I, [_P, C.c_longlong, _P, _I, _I, _P]),
     "afx_k_jitter_place": (_I, [_P, C.c_longlong, _P, _I, _I, _I, _P, _I, _I, _P]),
     "afx_k_jitter_place_mixed": (_I, [_P, C.c_longlong, _P, _I, _I, _P, _I, _I, _P]),
     "afx_k_jitter_conceal": (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _I, _I, _P]),

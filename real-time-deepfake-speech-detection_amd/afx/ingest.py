@@ -36,14 +36,34 @@ row with its slot's own L, M and sample size.  A feed is still one upload, and o
 per round whatever the number of formats; the slot pool and the inner scorer's batch are shared by all of them.  A mixed
 state carries the per-session ``ingest_rate`` ((n,) int64) in place of the meta's one ``input_rate``, ``resample_hist`` is
 (n, Hs) with Hs the widest T - 1 of the scorer's formats (zeros beyond a session's own), and the meta says ``ingest_mixed``.
+
+Expanded codecs: wherever a front takes an ``encoding`` it takes a name from ``ENCODINGS + CODECS`` (``afx.codecs``: ``dvi4``,
+RFC 3551's IMA ADPCM, and the network-order ``pcm_s16be``, ``pcm_s24be`` and ``pcm_u8``, RTP's L16 / L24 / L8).  The kernels
+of the fronts read a payload by random access, which a recurrence within a packet does not allow; so right after payload
+validation a packet in a codec becomes, for every planner, a virtual pcm_f32le block of n = ``codecs.samples(nbytes, codec)``
+samples in a *decoded zone* that follows the uploaded payloads and tables in the call's device buffer, each block 16-byte
+aligned; a sub-range that starts k samples into the packet is read at zone offset + 4 k.  ``plan``, ``_plan``, the rounds and
+all bookkeeping then run as they always did, on encoding 0 with 4 bytes per sample, behind one ("expand", rows, largest n) op
+that is issued before the first ingest / place of the call (``afx_k_payload_expand``: one wave per DVI4 block, a map for the
+PCM codecs).  The upload is still one pinned copy, into the front of a buffer that also holds the zone, and "a feed carries
+less than 2 GiB" counts the zone.  A call without a packet in a codec plans and issues exactly what it did.  The contract is
+the one above with D the concatenation of the decoded packets, ``codecs.reference`` of each: for DVI4 a packet is a block,
+decoded from its own header whatever came before it; for the PCM codecs "however cut" holds on whole samples.  A DVI4 packet
+under 4 bytes or with a header index above 88, and an s16be / s24be packet that splits a sample, are a ValueError before
+anything changes.  States store decoded samples: a session exported from a ``dvi4`` scorer imports into a ``pcm_s16le`` one at
+the same rate, and back.  A format of a ``MixedPacketScorer`` in a codec has a device entry that says encoding 0.  Out of
+scope: stereo / channel de-interleave, G.722 / G.726 and other codecs whose state runs across packets, IMA file blocks (first
+sample in the header), DVI4 encoding on the device.
 """
 import ctypes as C
 
 import numpy as np
 import torch
 
+from . import codecs
 from ._layer import check_pending, export_pending, import_pending, peel, rows_on, wrap
 from ._lib import AfxError, IngestFormat, call_on, check, lib, ptr
+from .codecs import CODECS, EXPAND_HDR
 from .resample import FILTER_ID, Resampler
 from .streaming import FeedResult, _Front  # noqa: F401  (FeedResult is part of this module's interface)
 
@@ -53,22 +73,58 @@ HDR = 8  # int32 per afx_k_ingest row: slot, byte offset, n_in, n_out, p0, d0, w
 MAX_FORMATS = 16  # formats of one MixedPacketScorer (the table afx_k_ingest_mixed takes by value)
 ALIGN = 16  # every payload and table starts on a 16-byte boundary of the staging buffer
 _SAMPLE = {"pcm_f32le": np.dtype("<f4"), "pcm_s16le": np.dtype("<i2"), "mulaw": np.dtype("u1"), "alaw": np.dtype("u1")}
+_UNIT = dict({e: t.itemsize for e, t in _SAMPLE.items()}, **codecs.UNIT)  # bytes a packet is a whole number of
 _MAX_SAMPLES = 1 << 30
 _ZEROS = bytes(ALIGN)
 _STATE_KEYS = ("ingest_pending", "ingest_fill", "ingest_in", "resample_hist")
 
 
 def _encoding(encoding):
-    if encoding not in ENCODINGS:
-        raise ValueError(f"encoding {encoding!r}: one of {ENCODINGS}")
+    if encoding not in ENCODINGS + CODECS:
+        raise ValueError(f"encoding {encoding!r}: one of {ENCODINGS + CODECS}")
     return encoding
+
+
+def device_encoding(encoding):
+    """(the library's encoding number, bytes per sample) the ingest / place kernels read a packet of ``encoding`` with: its
+    own for ``ENCODINGS``; an expanded codec's samples are read from the decoded zone, as pcm_f32le."""
+    return (ENCODINGS.index(encoding), _SAMPLE[encoding].itemsize) if encoding in ENCODINGS else (0, 4)
+
+
+def expand_zone(nbytes, offs, total, codec):
+    """The decoded zone of a call whose packets (``nbytes`` bytes at the byte offsets ``offs`` of ``total`` payload bytes)
+    are in the codecs ``codec`` (int64 array: the number in ``CODECS``, -1 for a packet the kernels read as it is) ->
+    (samples per packet (for the others nothing is said: 0), the offset each packet is read at, the ``afx_k_payload_expand``
+    rows or None, the zone's bytes).  A packet in a codec becomes a pcm_f32le block, 16-byte aligned, in a zone that is
+    planned from byte ``total`` on: ``_Front._stage`` moves it behind the tables once their sizes are known."""
+    nbytes, offs = np.asarray(nbytes, dtype=np.int64).reshape(-1), np.asarray(offs, dtype=np.int64).reshape(-1)
+    e = np.flatnonzero(codec >= 0)
+    n, at = np.zeros(len(nbytes), dtype=np.int64), offs.copy()
+    if not e.size:
+        return n, at, None, 0
+    n[e] = codecs.samples_each(nbytes[e], codec[e])
+    zoffs, zbytes = layout(4 * n[e])
+    at[e] = total + np.asarray(zoffs, dtype=np.int64)
+    e = e[n[e] > 0]
+    rows = np.stack([offs[e], nbytes[e], at[e], codec[e]], axis=1).astype(np.int32) if e.size else None
+    return n, at, rows, zbytes
+
+
+def with_expand(ops, rows, kinds=("ingest", "place")):
+    """``ops`` with one ("expand", rows, largest n) op before its first ingest / place op (none: ``ops`` as it is)."""
+    first = next((i for i, op in enumerate(ops) if op[0] in kinds), None)
+    if rows is None or first is None:
+        return ops
+    most = int(codecs.samples_each(rows[:, 1], rows[:, 3]).max())
+    return ops[:first] + [("expand", rows, most)] + ops[first:]
 
 
 def payload(packet, encoding):
     """One packet as a contiguous 1-D uint8 array of whole little-endian samples (no copy where the input allows it).
     ``packet``: bytes / bytearray / memoryview, or a 1-D numpy array / CPU tensor of uint8 or, for the PCM encodings, of the
     sample type.  Anything else, or bytes that split a sample, is a ValueError."""
-    st = _SAMPLE[_encoding(encoding)]
+    name = _encoding(encoding)
+    st, unit = _SAMPLE.get(name, np.dtype("u1")), _UNIT[name]  # (a packet in a codec is bytes)
     if isinstance(packet, torch.Tensor):
         if packet.is_cuda or packet.ndim != 1:
             raise ValueError("a packet tensor is 1-D and on the host")
@@ -87,9 +143,11 @@ def payload(packet, encoding):
                              f", got {packet.dtype}")
     else:
         raise ValueError(f"a packet is bytes, a bytearray, a memoryview, a numpy array or a CPU tensor, got {type(packet).__name__}")
-    if a.size % st.itemsize:
-        raise ValueError(f"a {encoding} packet of {a.size} bytes splits a {st.itemsize}-byte sample")
-    if a.size // st.itemsize >= _MAX_SAMPLES:
+    if a.size % unit:
+        raise ValueError(f"a {encoding} packet of {a.size} bytes splits a {unit}-byte sample")
+    if name == "dvi4":
+        codecs.dvi4_header(a)  # (a malformed block raises)
+    if a.size // unit >= _MAX_SAMPLES:
         raise ValueError("a packet holds fewer than 2**30 samples")
     return a
 
@@ -135,12 +193,24 @@ def _at(t, off):
 
 def decode(data, encoding, device="cuda"):
     """One packet or a whole file of ``encoding`` -> (n,) fp32 on the GPU: the device decode ``PacketScorer`` runs
-    (pcm_s16le v / 32768; G.711 to the 16-bit linear value, / 32768; exact)."""
+    (pcm_s16le v / 32768; G.711 to the 16-bit linear value, / 32768; a codec of ``afx.codecs`` as stated there -- for dvi4
+    ``data`` is one block; exact)."""
     a = payload(data, encoding)
-    n = a.size // _SAMPLE[encoding].itemsize
     dev = torch.device(device)
     if dev.type != "cuda":
         raise AfxError("decode runs on the GPU; there is no CPU fallback")
+    if encoding in CODECS:  # one expand row: the payload, then its table, then the samples
+        n = codecs.samples(a.size, encoding)
+        if n == 0:
+            return torch.empty(0, dtype=torch.float32, device=dev)
+        (_, th), up = layout([a.size, 4 * EXPAND_HDR])
+        buf, _, _ = pack([a], [np.array([[0, a.size, up, CODECS.index(encoding)]], dtype=np.int32)], pinned=True)
+        with torch.cuda.device(dev):
+            d = torch.empty(up + 4 * n, dtype=torch.uint8, device=dev)
+            d[:up].copy_(buf, non_blocking=True)
+            check(call_on(d, lib().afx_k_payload_expand, _at(d, 0), d.numel(), _at(d, th), 1, n))
+        return d[up:].view(torch.float32)
+    n = a.size // _SAMPLE[encoding].itemsize
     out = torch.empty(1, n, dtype=torch.float32, device=dev)
     if n == 0:
         return out[0]
@@ -155,7 +225,7 @@ def decode(data, encoding, device="cuda"):
 
 class PacketScorer(_Front):
     """``scorer`` (a SlidingWindowScorer, IncrementalScorer or KVCachedScorer) fed encoded packets of any size at
-    ``input_rate`` Hz (any integer 8 000 - 192 000) in ``encoding`` (``ENCODINGS``); see the module docstring for the
+    ``input_rate`` Hz (any integer 8 000 - 192 000) in ``encoding`` (``ENCODINGS`` or ``CODECS``); see the module docstring for the
     contract.  ``max_pending``: the whole hops a slot may buffer between ``feed(..., score=False)`` and ``drain``."""
 
     _WORK = "decoded, resampled"
@@ -182,12 +252,14 @@ class PacketScorer(_Front):
         """(L, M, bytes per sample, format index) of the slots ``slot``: int64 arrays over them."""
         n = len(slot)
         return (np.full(n, self.L, dtype=np.int64), np.full(n, self.M, dtype=np.int64),
-                np.full(n, _SAMPLE[self.encoding].itemsize, dtype=np.int64), np.zeros(n, dtype=np.int64))
+                np.full(n, device_encoding(self.encoding)[1], dtype=np.int64), np.zeros(n, dtype=np.int64))
 
     def _payloads(self, packets, idx):
-        """-> (one block per named slot, their byte counts, their sample counts), each packet read in its slot's encoding."""
+        """-> (one block per named slot, their byte counts, their sample counts as far as the kernels read them as they are,
+        each packet's number in ``CODECS`` or -1), each packet read in its slot's encoding."""
         pay, nbytes = self._packets(packets, len(idx), self.encoding)
-        return pay, nbytes, nbytes // _SAMPLE[self.encoding].itemsize
+        c = CODECS.index(self.encoding) if self.encoding in CODECS else -1
+        return pay, nbytes, nbytes // _UNIT[self.encoding], np.full(len(idx), c, dtype=np.int64)
 
     def _plan(self, idx, sizes, offs, score):
         """The launches of a feed / drain over the slots ``idx`` (sizes[i] new samples for idx[i], their payload at byte
@@ -238,8 +310,17 @@ class PacketScorer(_Front):
         slot completes is scored (in rounds, while the packets are ingested; afterwards no named slot holds a whole hop).
         score=False: the packets are decoded, resampled and buffered only (``drain`` scores them); a slot whose buffer would
         hold more than ``max_pending`` hops is a ValueError.  Everything is checked before anything changes.  -> FeedResult."""
+        return self._run(*self._plan_feed(packets, slots, score))
+
+    def _plan_feed(self, packets, slots, score=True):
+        """The checks and the plan of a ``feed`` -> what ``_run`` takes: (named slots, payload blocks, (ops, per-slot hop
+        counts, the counters after it)).  No state changes.  Packets in a codec are planned as pcm_f32le blocks of the decoded
+        zone (``expand_zone``), behind one "expand" op."""
         idx = self.scorer._slot_list(slots, ordered=True)
-        pay, nbytes, sizes = self._payloads(packets, idx)
+        pay, nbytes, sizes, codec = self._payloads(packets, idx)
+        offs, total = layout(nbytes)
+        n, offs, rows, zone = expand_zone(nbytes, offs, total, codec)
+        sizes = np.where(codec >= 0, n, sizes)
         if not score and idx:
             N, n = self._in[idx], sizes
             L, M, _, _ = self._ratios(np.asarray(idx, dtype=np.int64))
@@ -248,20 +329,20 @@ class PacketScorer(_Front):
             if over.size:
                 raise ValueError(f"slot {idx[over[0]]} would hold {after[over[0]]} pending samples, more than max_pending = "
                                  f"{self.max_pending} hops of {self.hop}: drain it first")
-        offs, total = layout(nbytes)
-        if total >= 1 << 31:
+        if total + zone >= 1 << 31:
             raise ValueError("a feed carries less than 2 GiB")
-        return self._run(idx, pay, sizes, offs, score)
+        ops, counts, after = self._plan(idx, sizes, offs, score)
+        return idx, pay, (with_expand(ops, rows), counts, after)
 
     def drain(self, slots=None):
         """Score every completed hop of the named (default: all) slots -> FeedResult."""
         idx = list(range(self.S)) if slots is None else self.scorer._slot_list(slots, ordered=True)
-        return self._run(idx, [], None, None, True)
+        return self._run(idx, [], self._plan(idx, None, None, True))
 
     def _ingest(self):
         """-> ingest(d, off, op): the launch of one ("ingest", rows, largest n_out) op whose table sits at byte ``off`` of the
         uploaded buffer ``d``."""
-        enc, (taps, L, M, T) = ENCODINGS.index(self.encoding), self._filter()
+        enc, (taps, L, M, T) = device_encoding(self.encoding)[0], self._filter()
 
         def ingest(d, off, op):
             check(call_on(self.ring, lib().afx_k_ingest, _at(d, 0), d.numel(), _at(d, off), len(op[1]), int(op[2]), enc, taps, L, M,
@@ -269,8 +350,8 @@ class PacketScorer(_Front):
 
         return ingest
 
-    def _run(self, idx, pay, sizes, offs, score):
-        ops, counts, after = self._plan(idx, sizes, offs, score)
+    def _run(self, idx, pay, planned):
+        ops, counts, after = planned
         ingest = self._ingest()
 
         def commit():
@@ -339,7 +420,7 @@ def _format(f):
 
 class MixedPacketScorer(PacketScorer):
     """``scorer`` fed encoded packets, every slot in its own format out of ``formats``: 1 to 16 distinct
-    (input_rate, encoding) pairs (rates as for ``Resampler``, encodings ``ENCODINGS``); see the module docstring for the
+    (input_rate, encoding) pairs (rates as for ``Resampler``, encodings ``ENCODINGS`` or ``CODECS``); see the module docstring for the
     contract.  A slot's format is chosen at ``reset`` (a fresh scorer has every slot at format 0) and never changes between
     resets.  ``feed``, ``drain``, ``samples_in``, ``pending`` and ``samples_seen`` are ``PacketScorer``'s."""
 
@@ -360,10 +441,13 @@ class MixedPacketScorer(PacketScorer):
                 self._rs[r] = Resampler(r, scorer.device)
         rs = [self._rs[r] for r, _ in fm]
         arr = lambda v: np.array(v, dtype=np.int64)
-        self._frate, self._fenc = arr([r for r, _ in fm]), arr([ENCODINGS.index(e) for _, e in fm])
+        # (a format in a codec reads its expanded samples: its device entry says encoding 0, 4 bytes per sample)
+        self._frate, self._fenc = arr([r for r, _ in fm]), arr([device_encoding(e)[0] for _, e in fm])
         self._fL, self._fM = arr([x.L for x in rs]), arr([x.M for x in rs])
         self._fH = arr([0 if x.identity else x.T - 1 for x in rs])  # carried samples per format
-        self._fbps = arr([_SAMPLE[e].itemsize for _, e in fm])
+        self._fbps = arr([device_encoding(e)[1] for _, e in fm])
+        self._funit = arr([_UNIT[e] for _, e in fm])  # bytes a packet of the format is a whole number of
+        self._fcodec = arr([CODECS.index(e) if e in CODECS else -1 for _, e in fm])
         self._fdelay = np.array([x.delay for x in rs], dtype=np.float64)
         self._fname = np.array([e for _, e in fm], dtype=object)
         self.Hs = int(self._fH.max())
@@ -432,8 +516,8 @@ class MixedPacketScorer(PacketScorer):
 
     def _payloads(self, packets, idx):
         f = self._fmt[np.asarray(idx, dtype=np.int64)]
-        pay, nbytes = self._packets_each(packets, self._fname[f].tolist(), self._fbps[f])
-        return pay, nbytes, nbytes // self._fbps[f]
+        pay, nbytes = self._packets_each(packets, self._fname[f].tolist(), self._funit[f])
+        return pay, nbytes, nbytes // self._funit[f], self._fcodec[f]
 
     def _ingest(self):
         nf, hist = len(self.formats), ptr(self.hist) if self.Hs else None

@@ -67,8 +67,20 @@ a slot at rate r uses the columns [0, J_r) of its row with modulus J_r and never
 invariant above holds per slot with its own J_r.  A mixed state has ``jitter_ring`` (n, widest lookback_r + depth_r), zeros beyond a session's own columns,
 ``jitter_rate`` ((n,) int64) and ``jitter_params`` ((n, 3) int64: depth, period, fade), and the meta ``jitter``,
 ``jitter_conceal``, ``resampler`` and ``jitter_mixed``; a plain JitterScorer's state imports where its rate is listed and
-its parameters are that rate's.  Out of scope: a rate change without a reset, per-slot depth within one rate, big-endian
-L16 payloads (swap the bytes), per-slot conceal modes.
+its parameters are that rate's.  Out of scope: a rate change without a reset, per-slot depth within one rate, per-slot
+conceal modes.
+
+Expanded codecs: a listed encoding may be one of ``afx.codecs.CODECS`` (``dvi4``, ``pcm_s16be``, ``pcm_s24be``, ``pcm_u8``), and
+packets of different codecs may share a call (``encodings=``).  DVI4 fits the decoded reorder ring because each RTP packet
+carries its own predictor state: a packet decodes on its own, whatever was lost or reordered, and one with timestamp t and B
+bytes covers [t, t + 2 (B - 4)).  Right after payload validation such a packet becomes a pcm_f32le block of the call's decoded
+zone (``afx.ingest`` module docstring): placement, holes, late / duplicate trimming and the rounds run as above on encoding 0
+with 4 bytes per sample -- a sub-range that starts k samples into a packet is read at its block + 4 k -- behind one "expand"
+op (``afx_k_payload_expand``) issued before the call's first place.  A call without such a packet plans and issues what it
+did.  ``feed_rtp`` knows RFC 3551's static audio types (``afx.rtp.STATIC_AUDIO_FORMATS``: 5, 6, 16, 17 are DVI4 at 8, 16,
+11.025 and 22.05 kHz, 11 is mono L16 at 44.1 kHz in network byte order) and takes one without ``payload_types`` when its
+(rate, encoding) is listed at the slot's rate.  The ring is decoded, so a state does not say which codec fed it.  Out of
+scope: stereo (PT 10) / channel de-interleave, G.722 / G.726 and other codecs whose state runs across packets.
 
 Silence suppression (DTX) and comfort noise (RFC 3389): a sender with VAD on stops sending in a pause and says so with a
 CN packet: from this timestamp on there is silence, and the background noise is this many dB below overload.  A scorer built
@@ -119,7 +131,9 @@ import torch
 from . import rtp
 from ._layer import StreamState, _on, check_pending, export_pending, import_pending, peel, rows_on, wrap
 from ._lib import JitterRate, call_on, check, lib, ptr
-from .ingest import _MAX_SAMPLES, _SAMPLE, ENCODINGS, MAX_FORMATS, _at, _encoding, _format, layout
+from .codecs import CODECS
+from .ingest import (_MAX_SAMPLES, _SAMPLE, _UNIT, ENCODINGS, MAX_FORMATS, _at, _encoding, _format, device_encoding, expand_zone, layout,
+                     with_expand)
 from .resample import FILTER_ID, Resampler
 from .streaming import _Front
 
@@ -133,7 +147,9 @@ _STATE_KEYS = ("jitter_pending", "jitter_fill", "jitter_ring", "jitter_book", "j
 _BOOK = ("origin", "started", "next", "hi", "gap", "max_start", "max_seq", "ssrc")  # jitter_book columns
 _COUNTERS = ("received", "late", "dup", "concealed", "ooo")  # jitter_stats columns (STATS order)
 _BPS = np.array([_SAMPLE[e].itemsize for e in ENCODINGS], dtype=np.int64)  # bytes per sample by encoding number
-_NUMBER = {e: i for i, e in enumerate(ENCODINGS)}  # the library's encoding numbers
+_NAMES = ENCODINGS + CODECS  # what a packet may come in, by the host's number: an encoding's own, then 4 + the codec's
+_HOST_NUMBER = {e: i for i, e in enumerate(_NAMES)}
+_HOST_UNIT = np.array([_UNIT[e] for e in _NAMES], dtype=np.int64)  # bytes a packet is a whole number of, by host number
 NOISE_HDR, NOISE_RATES_HDR = 6, 7  # afx_k_jitter_noise / _noise_rates: slot, column, n, lo32(i0), hi32(i0), level [, rate index]
 CN_STATS = ("comfort", "marks", "marks_late")  # what stats() adds with a ComfortNoise
 _CN_KEYS = ("jitter_cn_marks", "jitter_cn_open", "jitter_cn_stats")  # what export_slots adds with a ComfortNoise
@@ -264,7 +280,7 @@ class Plan:
 
 class JitterScorer(_Front):
     """``scorer`` (a SlidingWindowScorer, IncrementalScorer or KVCachedScorer) fed timestamped packets at ``input_rate`` Hz
-    in ``encoding`` (``afx.ingest.ENCODINGS``; a tuple of them: any of these per packet, the first the default); see the
+    in ``encoding`` (``afx.ingest.ENCODINGS`` or ``afx.codecs.CODECS``; a tuple of them: any of these per packet, the first the default); see the
     module docstring for the contract.
 
     ``depth``: the playout delay in input samples (60 ms is common; 0 is legal; the filter's ``delay`` comes on top of it).
@@ -286,7 +302,7 @@ class JitterScorer(_Front):
             self.encodings, self._mixed = (_encoding(encoding),), False
         else:
             if not isinstance(encoding, (tuple, list)) or not encoding:
-                raise ValueError(f"encoding {encoding!r}: one of {ENCODINGS}, or a tuple of them")
+                raise ValueError(f"encoding {encoding!r}: one of {ENCODINGS + CODECS}, or a tuple of them")
             self.encodings, self._mixed = tuple(_encoding(e) for e in encoding), True
             if len(set(self.encodings)) != len(self.encodings):
                 raise ValueError("encoding: an encoding is listed twice")
@@ -323,10 +339,11 @@ class JitterScorer(_Front):
         arr = lambda v: np.array(v, dtype=np.int64)
         self._rs, self._encs_at = list(rs), [tuple(e) for e in encs_at]
         self._rates = tuple(x.rate for x in rs)  # in Hz, in the order first listed
-        self._renc = arr([_NUMBER[e[0]] for e in self._encs_at])  # the default encoding's number
-        self._listed = np.zeros((len(rs), len(ENCODINGS) + 1), dtype=bool)  # [rate index, encoding number]: listed at that rate
+        self._renc = arr([device_encoding(e[0])[0] for e in self._encs_at])  # the default encoding's number, as place reads it
+        self._rdefault = arr([_HOST_NUMBER[e[0]] for e in self._encs_at])  # the default encoding's host number
+        self._listed = np.zeros((len(rs), len(_NAMES) + 1), dtype=bool)  # [rate index, host number]: listed at that rate
         for i, e in enumerate(self._encs_at):
-            self._listed[i, [_NUMBER[v] for v in e]] = True
+            self._listed[i, [_HOST_NUMBER[v] for v in e]] = True
         self._rrate, self._rL, self._rM = arr(self._rates), arr([x.L for x in rs]), arr([x.M for x in rs])
         self._rdepth, self._rP, self._rF = arr(depth), arr(P), arr(F)
         # the sizing invariant (module docstring), per rate: J = lookback + W, W >= depth; the slack beyond depth is what a
@@ -695,8 +712,8 @@ class JitterScorer(_Front):
         idx = self._rows(slots, repeats=True)
         ri = self._rate_of[np.asarray(idx, dtype=np.int64)]
         if encodings is None:  # the first listed at each slot's rate
-            encs = self._renc[ri]
-            names = np.array(ENCODINGS, dtype=object)[encs].tolist()
+            encs = self._rdefault[ri]
+            names = np.array(_NAMES, dtype=object)[encs].tolist()
         else:
             if isinstance(encodings, str) or not hasattr(encodings, "__len__"):
                 raise ValueError("encodings: one encoding per packet")
@@ -704,7 +721,7 @@ class JitterScorer(_Front):
             if len(names) != len(idx):
                 raise ValueError(f"{len(names)} encodings for {len(idx)} named slots")
             try:  # (a name that is no encoding at all gets the number of the table's last column, where nothing is listed)
-                encs = np.fromiter(map(_NUMBER.get, names, repeat(len(ENCODINGS))), dtype=np.int64, count=len(names))
+                encs = np.fromiter(map(_HOST_NUMBER.get, names, repeat(len(_NAMES))), dtype=np.int64, count=len(names))
             except TypeError:
                 raise ValueError("encodings: one encoding per packet") from None
             bad = np.flatnonzero(~self._listed[ri, encs])
@@ -712,13 +729,19 @@ class JitterScorer(_Front):
                 i, r = int(bad[0]), int(ri[bad[0]])
                 what = f"encoding {names[i]!r} is not one of this scorer's {self._encs_at[r]}"
                 raise ValueError(f"slot {idx[i]}: {what} at {self._rates[r]} Hz" if self._rated else what)
-        bps = _BPS[encs]
-        pay, nbytes = self._packets_each(packets, names, bps)
+        unit = _HOST_UNIT[encs]
+        pay, nbytes = self._packets_each(packets, names, unit)
         ts = self._timestamps(timestamps, len(idx))
         offs, total = layout(nbytes)
-        if total >= 1 << 31:
+        # a packet in a codec is, for the planner, a pcm_f32le block of the decoded zone (afx.ingest.expand_zone)
+        codec = encs - len(ENCODINGS)
+        n, offs, rows, zone = expand_zone(nbytes, offs, total, codec)
+        if total + zone >= 1 << 31:
             raise ValueError("a feed carries less than 2 GiB")
-        return self._plan(idx, nbytes // bps, ts, offs, seqs, "feed", score=score, encs=encs, marks=marks), pay
+        plan = self._plan(idx, np.where(codec >= 0, n, nbytes // unit), ts, offs, seqs, "feed", score=score,
+                          encs=np.where(codec >= 0, 0, encs), marks=marks)
+        plan.ops = with_expand(plan.ops, rows)
+        return plan, pay
 
     def silence(self, slots, timestamps, levels):
         """Silence marks (module docstring): from timestamps[i] on, slot slots[i] is silent with a background noise
@@ -745,9 +768,11 @@ class JitterScorer(_Front):
         return [int(l) for l in levels]
 
     def _rtp_types(self, payload_types):
-        """What ``feed_rtp`` looks a payload type up in: 0 is mulaw and 8 alaw (RFC 3551), ``payload_types`` adds to them."""
+        """What ``feed_rtp`` looks a payload type up in: 0 is mulaw and 8 alaw (RFC 3551), the other static audio types
+        (``rtp.STATIC_AUDIO_FORMATS``) whose clock rate is this scorer's, and ``payload_types`` adds to them."""
         cn = {} if self.cn is None else {rtp.CN_PAYLOAD_TYPE: "cn"}
-        return {**rtp.STATIC_PAYLOAD_TYPES, **cn, **(payload_types or {})}
+        static = {pt: e for pt, (r, e) in rtp.STATIC_AUDIO_FORMATS.items() if r == self.input_rate}
+        return {**static, **rtp.STATIC_PAYLOAD_TYPES, **cn, **(payload_types or {})}
 
     def _rtp_encoding(self, s, pt, types):
         """The encoding of a datagram of slot s with payload type pt ("cn": a silence mark), or the ValueError."""
@@ -849,7 +874,7 @@ class JitterScorer(_Front):
         return self._run(self._plan(idx, mode="drain"), [])
 
     def _run(self, plan, pay):
-        enc, (taps, L, M, T) = ENCODINGS.index(self.encoding), self._filter()
+        enc, (taps, L, M, T) = device_encoding(self.encoding)[0], self._filter()
         l, S, J = lib(), self.S, self.J
 
         def place(d, off, op):
@@ -1144,7 +1169,7 @@ class MixedJitterScorer(JitterScorer):
         """``feed_rtp`` here takes ``payload_types`` mapping a number to an (input_rate, encoding) pair: 0 and 8 are
         (8000, "mulaw") and (8000, "alaw") (RFC 3551).  A datagram whose type maps to another rate than its slot's, or to a
         pair this scorer does not list, is a ValueError before anything changes."""
-        types = {pt: (8000, e) for pt, e in rtp.STATIC_PAYLOAD_TYPES.items()}
+        types = {**rtp.STATIC_AUDIO_FORMATS, **{pt: (8000, e) for pt, e in rtp.STATIC_PAYLOAD_TYPES.items()}}
         if self.cn is not None:
             types[rtp.CN_PAYLOAD_TYPE] = (8000, "cn")
         cn = lambda f: self.cn is not None and isinstance(f, (tuple, list)) and len(f) == 2 and f[1] == "cn" and f[0] in self._rates

@@ -8,6 +8,10 @@ import collections
 Packet = collections.namedtuple("Packet", "seq timestamp payload_type ssrc marker payload")
 
 STATIC_PAYLOAD_TYPES = {0: "mulaw", 8: "alaw"}  # RFC 3551: PCMU, PCMA (8 kHz; the RTP clock is the sample rate)
+# RFC 3551's static audio payload types a front can score, as (clock rate, encoding): PCMU, DVI4 at its four rates, PCMA and
+# mono L16 (network byte order).  10 (stereo L16) is not mapped: channels are not de-interleaved.
+STATIC_AUDIO_FORMATS = {0: (8000, "mulaw"), 5: (8000, "dvi4"), 6: (16000, "dvi4"), 8: (8000, "alaw"), 11: (44100, "pcm_s16be"),
+                        16: (11025, "dvi4"), 17: (22050, "dvi4")}
 CN_PAYLOAD_TYPE = 13  # RFC 3389 comfort noise (8 kHz clock, RFC 3551): payload[0] & 0x7f is the noise level in -dBov; a
 # jitter scorer with a ComfortNoise takes it as a silence mark (other clock rates negotiate a dynamic type for it)
 

@@ -153,36 +153,48 @@ class _Front:
     def _packets(packets, n, encoding):
         """-> (one block of whole samples per named slot: bytes as they are, anything else through ``payload``; their byte
         counts)."""
-        from .ingest import _MAX_SAMPLES, _SAMPLE, payload
+        from .ingest import _MAX_SAMPLES, _UNIT, payload
         if isinstance(packets, (bytes, bytearray, memoryview, np.ndarray, torch.Tensor)):
             raise ValueError("packets: a list with one packet per named slot")
         packets = list(packets)
         if len(packets) != n:
             raise ValueError(f"{len(packets)} packets for {n} named slots")
-        bps = _SAMPLE[encoding].itemsize
+        bps = _UNIT[encoding]
         out = [p if type(p) is bytes else payload(p, encoding) for p in packets]
         nbytes = np.fromiter(map(len, out), dtype=np.int64, count=len(out))
         for i in np.flatnonzero((nbytes % bps != 0) | (nbytes // bps >= _MAX_SAMPLES)):
             payload(out[i], encoding)  # (raises, with the message)
+        if encoding == "dvi4":
+            _Front._dvi4_blocks(out, range(len(out)))
         return out, nbytes
+
+    @staticmethod
+    def _dvi4_blocks(blocks, which):
+        """The DVI4 blocks ``which`` of ``blocks`` have a header (4 bytes, index <= 88); a malformed one is a ValueError."""
+        from .ingest import payload
+        for i in which:
+            if len(blocks[i]) < 4 or blocks[i][2] > 88:
+                payload(blocks[i], "dvi4")  # (raises, with the message)
 
     @staticmethod
     def _packets_each(packets, encodings, bps=None):
         """``_packets`` with one encoding per packet (``encodings``: a list of names; ``bps``: their bytes per sample as an
         int64 array, where the caller has it) -> (blocks, byte counts)."""
-        from .ingest import _MAX_SAMPLES, _SAMPLE, payload
+        from .ingest import _MAX_SAMPLES, _UNIT, payload
         if isinstance(packets, (bytes, bytearray, memoryview, np.ndarray, torch.Tensor)):
             raise ValueError("packets: a list with one packet per named slot")
         packets = list(packets)
         if len(packets) != len(encodings):
             raise ValueError(f"{len(packets)} packets for {len(encodings)} named slots")
         if bps is None:
-            bps = np.fromiter((_SAMPLE[e].itemsize for e in encodings), dtype=np.int64, count=len(encodings))
+            bps = np.fromiter((_UNIT[e] for e in encodings), dtype=np.int64, count=len(encodings))
         out = packets if set(map(type, packets)) <= {bytes} else [
             p if type(p) is bytes else payload(p, e) for p, e in zip(packets, encodings)]
         nbytes = np.fromiter(map(len, out), dtype=np.int64, count=len(out))
         for i in np.flatnonzero((nbytes % bps != 0) | (nbytes // bps >= _MAX_SAMPLES)):
             payload(out[i], encodings[i])  # (raises, with the message)
+        if "dvi4" in encodings:
+            _Front._dvi4_blocks(out, [i for i, e in enumerate(encodings) if e == "dvi4"])
         return out, nbytes
 
     def _pop_rounds(self, ops, slots, head, fill, counts):
@@ -199,9 +211,40 @@ class _Front:
             rounds += 1
         return rounds
 
+    _SRC = {"ingest": 1, "place": 1}  # the int of a row that says at which byte of the buffer its samples are read
+
+    @staticmethod
+    def _stage(ops, tables, pay):
+        """Where the decoded zone of a planned call comes to lie.  The device buffer is the payloads, the tables, then the
+        zone; a plan is made before the sizes of its tables are known, so it counts the zone from the end of the payloads
+        (``afx.ingest.expand_zone``).  -> (``tables`` with the zone moved behind them: the destinations of the "expand" rows
+        and every ingest / place row that reads the zone, as copies; the zone's bytes).  A call without an "expand" op:
+        (``tables`` as they are, 0)."""
+        from .codecs import samples_each
+        from .ingest import ALIGN, layout
+        if not any(op[0] == "expand" for op in ops):
+            return tables, 0
+        sizes = [len(b) for b in pay]
+        _, front = layout(sizes)
+        _, up = layout(sizes + [t.nbytes for t in tables])
+        tables, end = list(tables), front
+        for i, op in enumerate(ops):
+            if op[0] == "expand":
+                t = op[1].copy()
+                end = max(end, int((t[:, 2] + 4 * samples_each(t[:, 1], t[:, 3])).max()))
+                t[:, 2] += up - front
+            elif op[0] in _Front._SRC:
+                t, c = op[1].copy(), _Front._SRC[op[0]]
+                t[t[:, c] >= front, c] += up - front
+            else:
+                continue
+            tables[i] = t
+        return tables, -(-(end - front) // ALIGN) * ALIGN
+
     def _execute(self, ops, slots, counts, pay, launch, commit):
-        """Issue a planned call: one pinned upload (the payload blocks ``pay``, then every op's table), then the ops in
-        order.  ``launch[kind](d, off, op)`` issues an op of the subclass's (d: the uploaded buffer, off: the byte offset of
+        """Issue a planned call: one pinned upload (the payload blocks ``pay``, then every op's table; with an "expand" op, into
+        the front of a buffer that also holds the decoded zone, ``_stage``), then the ops in order: an "expand" is
+        ``afx_k_payload_expand`` over the buffer, ``launch[kind](d, off, op)`` issues an op of the subclass's (d: the uploaded buffer, off: the byte offset of
         the op's table in it); a "pop" hands a round of whole hops to the inner scorer.  ``commit()`` makes the planned
         bookkeeping the scorer's once every launch has been issued.  ``slots``: the named slots, once each, in the order
         the result lists their scores; ``counts``: hops per named row -> FeedResult."""
@@ -224,11 +267,19 @@ class _Front:
         tables = [op[1] for op in ops]
         if perm != list(range(base)):
             tables.append(np.array(perm, dtype=np.int64))
+        tables, zone = self._stage(ops, tables, pay)
         buf, _, toffs = pack(pay, tables, pinned=True)
         outs = []
         with torch.cuda.device(dev):
-            d = buf.to(dev, non_blocking=True)  # the one upload
+            if zone:  # the upload goes to the front of a buffer that also holds the decoded zone
+                d = torch.empty(buf.numel() + zone, dtype=torch.uint8, device=dev)
+                d[:buf.numel()].copy_(buf, non_blocking=True)
+            else:
+                d = buf.to(dev, non_blocking=True)  # the one upload
             for op, off in zip(ops, toffs):
+                if op[0] == "expand":
+                    check(call_on(d, lib().afx_k_payload_expand, _at(d, 0), d.numel(), _at(d, off), len(op[1]), int(op[2])))
+                    continue
                 if op[0] != "pop":
                     launch[op[0]](d, off, op)
                     continue

@@ -2835,6 +2835,9 @@ extern "C" int afx_k_ingest_pop(const float* ring, int S, int ring_len, const in
                                 void* stream) {
   KRET(launch_ingest_pop(ring, S, ring_len, table, A, hop, out, (hipStream_t)stream));
 }
+extern "C" int afx_k_payload_expand(void* stage, long long stage_bytes, const int* hdr, int rows, int max_n, void* stream) {
+  KRET(launch_payload_expand(stage, stage_bytes, hdr, rows, max_n, (hipStream_t)stream));
+}
 extern "C" int afx_k_jitter_place(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n, int encoding,
                                   float* jring, int S, int J, void* stream) {
   KRET(launch_jitter_place(stage, stage_bytes, hdr, rows, max_n, encoding, jring, S, J, (hipStream_t)stream));

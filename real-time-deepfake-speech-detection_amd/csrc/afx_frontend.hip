@@ -1082,6 +1082,123 @@ const char* launch_ingest_pop(const float* ring, int S, int ring_len, const int*
 }
 
 // ---------------------------------------------------------------------------------
+// Payload expand (afx/codecs.py; the function is stated in include/afx.h afx_k_payload_expand): the verb that runs before
+// ingest / place.  The kernels above read a payload by random access (ingest_sample); a payload they cannot index that way
+// -- DVI4 is a recurrence within its block, network-order PCM needs its bytes put together -- is first written as fp32
+// samples into another zone of the same staging buffer, and read from there as encoding 0.  One workgroup of ONE wave per
+// (column of the grid, row); a row's codec is uniform over its workgroups, so every branch below is.
+//   PCM codecs: a grid-stride map over the row's samples.
+//   DVI4: the wave of grid column 0 walks the block 64 codes a step and carries the concrete (pred, index) from step to step.
+//   Within a step both recurrences are prefix scans over clamp-add maps x -> min(max(x + a, lo), hi), which are closed under
+//   composition (clamp_then): an exclusive scan of the index maps gives each lane its index, the lane looks up its step size
+//   (table in LDS) and forms +-d, an inclusive scan of the predictor maps gives its pred.  Integer VALU and __shfl_up only;
+//   over 64 codes |a| <= 64 * 61438 and the sentinels of the identity stay inside +-2^29, so nothing overflows int32.
+// ---------------------------------------------------------------------------------
+constexpr int EXP_HDR = 4;  // ints per row: source byte offset, source bytes, destination byte offset, codec number
+constexpr int EXP_DVI4 = 0, EXP_S16BE = 1, EXP_S24BE = 2, EXP_U8 = 3;
+constexpr int EXP_INF = 1 << 28;  // the bounds of a map that does not clamp
+
+__constant__ int DVI4_STEP[89] = {
+    7, 8, 9, 10, 11, 12, 13, 14, 16, 17, 19, 21, 23, 25, 28, 31, 34, 37, 41, 45, 50, 55, 60, 66, 73, 80, 88, 97, 107, 118, 130, 143,
+    157, 173, 190, 209, 230, 253, 279, 307, 337, 371, 408, 449, 494, 544, 598, 658, 724, 796, 876, 963, 1060, 1166, 1282, 1411,
+    1552, 1707, 1878, 2066, 2272, 2499, 2749, 3024, 3327, 3660, 4026, 4428, 4871, 5358, 5894, 6484, 7132, 7845, 8630, 9493, 10442,
+    11487, 12635, 13899, 15289, 16818, 18500, 20350, 22385, 24623, 27086, 29794, 32767};
+
+struct ClampAdd { int a, lo, hi; };  // x -> min(max(x + a, lo), hi), lo <= hi
+
+__device__ __forceinline__ int clamp_int(int x, int lo, int hi) { return min(max(x, lo), hi); }
+__device__ __forceinline__ int clamp_apply(const ClampAdd& m, int x) { return clamp_int(x + m.a, m.lo, m.hi); }
+// g after f
+__device__ __forceinline__ ClampAdd clamp_then(const ClampAdd& f, const ClampAdd& g) {
+  return ClampAdd{f.a + g.a, clamp_int(f.lo + g.a, g.lo, g.hi), clamp_int(f.hi + g.a, g.lo, g.hi)};
+}
+// lane i: the composition of the maps of lanes 0..i, in lane order (the block is one wave of 64)
+__device__ __forceinline__ ClampAdd clamp_scan(ClampAdd m, int lane) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const ClampAdd f{__shfl_up(m.a, d, 64), __shfl_up(m.lo, d, 64), __shfl_up(m.hi, d, 64)};
+    if (lane >= d) m = clamp_then(f, m);
+  }
+  return m;
+}
+
+// one DVI4 block (RFC 3551 4.5.1) of n = 2 (bytes - 4) codes, header validated by the caller -> out[0..n)
+__device__ __forceinline__ void expand_dvi4(const unsigned char* src, int n, float* out, const int* steps) {
+  const int lane = threadIdx.x;
+  int pred = (short)((src[0] << 8) | src[1]), index = src[2];
+  for (int base = 0; base < n; base += 64) {
+    const int k = base + lane;
+    const bool active = k < n;
+    int c = 0;
+    if (active) {
+      const int b = src[4 + (k >> 1)];
+      c = (k & 1) ? (b & 15) : (b >> 4);  // the high nibble first
+    }
+    const ClampAdd none{0, -EXP_INF, EXP_INF};
+    const ClampAdd im = clamp_scan(active ? ClampAdd{(c & 7) < 4 ? -1 : ((c & 7) - 3) * 2, 0, 88} : none, lane);
+    const int after = clamp_apply(im, index);  // the index after this lane's code
+    int mine = __shfl_up(after, 1, 64);        // the index this lane's code is decoded with
+    if (lane == 0) mine = index;
+    const int st = steps[mine];
+    const int d = (st >> 3) + ((c & 4) ? st : 0) + ((c & 2) ? st >> 1 : 0) + ((c & 1) ? st >> 2 : 0);
+    const ClampAdd pm = clamp_scan(active ? ClampAdd{(c & 8) ? -d : d, -32768, 32767} : none, lane);
+    const int p = clamp_apply(pm, pred);
+    if (active) out[k] = (float)p * (1.0f / 32768.0f);
+    index = __shfl(after, 63, 64);  // (lanes past the block's end are the identity: lane 63 holds the state after the last code)
+    pred = __shfl(p, 63, 64);
+  }
+}
+
+// a row that has a bad codec, splits a sample, is a malformed DVI4 block or leaves stage is skipped whole: nothing is written
+__global__ __launch_bounds__(64) void payload_expand_kernel(unsigned char* stage, long long stage_bytes, const int* __restrict__ hdr) {
+  __shared__ int steps[89];
+  const int* h = hdr + (long long)blockIdx.y * EXP_HDR;
+  const long long src_off = h[0], nbytes = h[1], dst_off = h[2];
+  const int codec = __builtin_amdgcn_readfirstlane(h[3]);
+  if (codec < EXP_DVI4 || codec > EXP_U8 || src_off < 0 || nbytes < 0 || src_off + nbytes > stage_bytes) return;
+  const unsigned char* src = stage + src_off;
+  long long n;
+  if (codec == EXP_DVI4) {
+    if (nbytes < 4 || src[2] > 88) return;
+    n = 2 * (nbytes - 4);
+  } else {
+    const int unit = codec == EXP_S16BE ? 2 : codec == EXP_S24BE ? 3 : 1;
+    if (nbytes % unit) return;
+    n = nbytes / unit;
+  }
+  if (dst_off < 0 || (dst_off & 3) || dst_off + 4 * n > stage_bytes) return;
+  float* out = (float*)(stage + dst_off);
+  if (codec == EXP_DVI4) {
+    if (blockIdx.x) return;
+    for (int i = threadIdx.x; i < 89; i += 64) steps[i] = DVI4_STEP[i];
+    __syncthreads();
+    expand_dvi4(src, (int)n, out, steps);
+    return;
+  }
+  for (long long k = (long long)blockIdx.x * 64 + threadIdx.x; k < n; k += (long long)gridDim.x * 64) {
+    if (codec == EXP_S16BE) {
+      out[k] = (float)(short)((src[2 * k] << 8) | src[2 * k + 1]) * (1.0f / 32768.0f);
+    } else if (codec == EXP_S24BE) {
+      const int v = ((int)(signed char)src[3 * k] << 16) | (src[3 * k + 1] << 8) | src[3 * k + 2];
+      out[k] = (float)v * (1.0f / 8388608.0f);
+    } else {
+      out[k] = (float)((int)src[k] - 128) * (1.0f / 128.0f);
+    }
+  }
+}
+
+const char* launch_payload_expand(void* stage, long long stage_bytes, const int* hdr, int rows, int max_n, hipStream_t s) {
+  if (!stage || !hdr || stage_bytes <= 0) return "afx_k_payload_expand: null staging buffer or header table";
+  if (rows <= 0 || rows > 65535) return "afx_k_payload_expand: 1 to 65535 rows";
+  if (max_n < 0 || 4LL * max_n > stage_bytes) return "afx_k_payload_expand: a row's samples must fit the staging buffer";
+  if (max_n == 0) return nullptr;  // no samples to write
+  hipLaunchKernelGGL(payload_expand_kernel, dim3(min((max_n + 255) / 256, 64), rows), dim3(64), 0, s, (unsigned char*)stage,
+                     stage_bytes, hdr);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+// ---------------------------------------------------------------------------------
 // Jitter buffer (afx/jitter.py; the functions are stated in include/afx.h afx_k_jitter_place / _conceal / _release and their
 // _mixed / _rates forms): one DECODED reorder ring per slot, jring (S, Js) fp32.  A slot has a RATE: its filter (taps, L, M, T),
 // its ring length J <= Js, its repeat period P, fade length F and fade table.  Input-rate sample i of the slot's played-out

@@ -170,6 +170,10 @@ const char* launch_ingest(const void* stage, long long stage_bytes, const int* h
                           hipStream_t s);
 const char* launch_ingest_pop(const float* ring, int S, int ring_len, const int* table, int A, int hop, float* out,
                               hipStream_t s);
+// payload expand (include/afx.h afx_k_payload_expand): the verb before ingest / place; rows of DVI4 / network-order PCM
+// payloads in stage -> their fp32 samples in another zone of stage (rows x 4 int32: source offset, source bytes, destination
+// offset, codec number)
+const char* launch_payload_expand(void* stage, long long stage_bytes, const int* hdr, int rows, int max_n, hipStream_t s);
 // the same ingest over rows of different formats (include/afx.h afx_k_ingest_mixed): formats / max_out are HOST arrays of
 // n_formats entries (IngestFormatDesc has the layout of afx_ingest_format), the row's format is the eighth int of its header,
 // hist is (S, Hs)
