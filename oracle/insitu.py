@@ -37,6 +37,26 @@ the worst ratio |got - ref| / bound):
   0.166 / 0.039, kv_ring 0.599 / 0.516 / 0.005 (bias of the products and LayerNorms within +-0.008 ulp; the ring
   attention's statistic is reported only: too few independent samples at <= 48 query rows).
 
+  Under key-padding masks (``lens``: ragged batches, judged on the rows of each clip's own length: ``masked_rows``), at the
+  two ends of a forward and for the attention kernel alone on lively logits, the constants are the same.  Worst ratio on
+  an MI355X (tests/test_gpu_insitu_ragged.py's summary), fp16 / bf16 / fp32 / fp16x3: mhsa_masked 0.409 / 0.415 / 0.022 /
+  0.358, mhsa_long (the blocked kernel, uniform and masked; fp16x3: the VALU fallback) 0.357 / 0.363 / 0.034 / 0.017,
+  mhsa_few (uniform, 1 .. 3 clips) 0.358 / 0.373 / 0.028 / 0.250, shaw_masked 0.424 / 0.536 / 0.028 / 0.014, dwconv_masked
+  0.479 / 0.497 / 0.004 / 0.005, final_ln (both outputs) 0.479 / 0.497 / 0.006 / 0.004, tokens 0.067 / 0.062 / 0.160 /
+  0.048, logits 0.015 / 0.015 / 0.013 / 0.013; ``afx.kernels.mhsa`` alone on logits of spread ~9 with planted dominating
+  keys, fp16 / bf16 / fp16x3: mhsa_k (one-pass families) 0.457 / 0.612 / 0.234, mhsa_k_long (blocked) 0.457 / 0.623.
+  The fp16x3 figures of the short clips and the fp16 figures on lively logits are WITH the absolute-floor terms
+  (``F16_FLOOR``, derived at ``_softmax_av``); without them those launches measured 1.3 .. 4.0 and 1.02 .. 1.46.
+  The floor terms enter ``mhsa``'s bound for every fp16 and (up to 224 frames) fp16x3 launch, the earlier class "mhsa"
+  included: fp16 gains sum_j min(P~_j, 2^-25) |v_j| / sum P~, which for weights above 2^-14 is 2^-14 of the u_op term it
+  stands beside (nothing measurable on the earlier shapes, whose logits are flat); fp16x3 gains 2^-24 per element plus
+  the q / k term, an absolute addition that matters where |v| is small.  tests/test_cpu_insitu.py shows that an error of
+  2^-20 and a dropped key on rows with |v| ~ 2^-10 still fail.
+  Bias: the new trunk-attention classes are asserted against the P-rounded reference (``_p_rounded``) and measure within
+  +-0.007 ulp (fp16 and bf16, every class above); against the exact reference the same launches read bf16 -0.35 .. +0.17
+  ulp at 3 clips and -0.05 at 25, fp16 up to -0.06: P's rounding, shared by the elements of an (utterance, head), not the
+  store.  shaw_masked is reported like shaw: +0.014 (fp16), +0.175 (bf16).
+
 The AASIST back-end (``aasist_walk`` and the functions above it) is fp32 throughout, so its bounds carry no operand ulp:
 
   * products and convs (LL, conv1 / conv2 / downsample as chunked-K products over the padded image, the two 1x1 maps):
@@ -79,6 +99,10 @@ BIAS_MAX = 0.05
 # rounding of P (several ulps of the output), and its mean signed error measured +0.06 .. +0.30 ulp (fp16 / bf16) on the
 # first MI355X run -- an open item, not a rounding-mode defect of the output store
 BIAS_REPORTED = ("shaw",)
+# "shaw_masked" is the same launch as "shaw" under key-padding masks and shares its open item: measured +0.014 (fp16) and
+# +0.175 ulp (bf16) on an MI355X.  The TRUNK attention's new classes (mhsa_masked, mhsa_long, mhsa_few, mhsa_k,
+# mhsa_k_long) are asserted, against the reference that rounds P as the kernel does (``mhsa(..., bias_ref=True)``).
+BIAS_REPORTED += ("shaw_masked",)
 # unit roundoff of the operand copies (fp16x3: the pair form of an fp32 value, ~2^-22)
 U_OP = {"fp16": 2.0 ** -11, "bf16": 2.0 ** -8, "fp32": 2.0 ** -24, "fp16x3": 2.0 ** -22}
 _MANT = {"fp16": 10, "bf16": 7, "fp32": 23, "fp16x3": 23}
@@ -234,9 +258,46 @@ def pos_weight(sd):
     return g * v / v.pow(2).sum(dim=(0, 1), keepdim=True).sqrt()
 
 
-def posconv(sd, xpad, x, rows, T, dt, groups=16):
+def masked_rows(lens, T):
+    """The flat rows (utterance b owns rows b T .. b T + T - 1, lens[b] of them valid) a launch of a ragged batch is
+    judged on, in the style of the tests' ``check_rows``: valid rows only -- rows at or past a clip's own length are
+    unread by contract -- and among them every row of the first and the last utterance, the LAST valid row of every
+    utterance, every valid row whose frame index mod 16 is 0 or 15 (so mod 64: 0, 15, 63 as well, the corners of the
+    attention's 16-row query tiles and 64-row blocks), every 7th valid row."""
+    lens = [int(n) for n in lens]
+    B = len(lens)
+    t = torch.arange(T)
+    out = []
+    for b, n in enumerate(lens):
+        assert 1 <= n <= T, (n, T)
+        m = (t % 16 == 0) | (t % 16 == 15) | (t == n - 1) | ((b * T + t) % 7 == 0)
+        if b == 0 or b == B - 1:
+            m = m | True
+        out.append(b * T + t[m & (t < n)])
+    return torch.cat(out)
+
+
+def valid_rows(lens, T):
+    """Every valid flat row of a ragged batch (lens[b] of utterance b's T rows)."""
+    return torch.cat([b * T + torch.arange(int(n)) for b, n in enumerate(lens)])
+
+
+def _key_mask(lens, b_i, keys, add=0):
+    """(R, keys) bool: True where key j is past the own length (lens[b] + add) of the row's utterance; None without lens."""
+    if lens is None:
+        return None
+    n = torch.as_tensor([int(v) for v in lens])[b_i] + add
+    return torch.arange(keys)[None, :] >= n[:, None]
+
+
+def posconv(sd, xpad, x, rows, T, dt, groups=16, lens=None):
     """Positional conv launch: x (B T, D) fp32 += GELU(conv(xpad) + bias) for the flat rows `rows`.  xpad: the operand
-    copy (B, T + 128, D), frame t of utterance b at padded row t + 64; output frame t reads padded rows t .. t + 127."""
+    copy (B, T + 128, D), frame t of utterance b at padded row t + 64; output frame t reads padded rows t .. t + 127.
+    lens (ragged batch): the reference still reads xpad as tapped, whose rows 64 + lens[b] .. of utterance b must be
+    exactly 0 (alone, the clip's conv would see zero padding there): asserted here."""
+    if lens is not None:
+        for b, n in enumerate(lens):
+            assert bool((xpad[b, 64 + int(n):] == 0).all()), f"xpad: utterance {b} has nonzero rows past its {int(n)} frames"
     w32 = pos_weight({k: v.float() if torch.is_tensor(v) else v for k, v in sd.items() if k.startswith("encoder.pos_conv")})
     w = op(w32.float(), dt)  # (D, D / groups, 128): the device computes the weight norm in fp32, then rounds
     D, cpg, K = w.shape
@@ -253,9 +314,25 @@ def posconv(sd, xpad, x, rows, T, dt, groups=16):
     return xr + gelu(z), (C_ACC[dt] * s + wflip) * dgelu(z) + C_ACC[dt] * xr.abs() + C_POLY * (1 + z.abs())
 
 
-def mhsa(qkv, rows, T, dt, heads=16):
+ATT_CHUNK = 96  # query rows per pass of the attention references (each gathers its own (keys, H, dh) k and v in float64)
+
+
+def _chunked(fn, rows):
+    """fn(rows chunk) -> (ref, bound), over ATT_CHUNK rows at a time (every row's sums are its own: the same numbers)."""
+    parts = [fn(rows[i:i + ATT_CHUNK]) for i in range(0, len(rows), ATT_CHUNK)]
+    return tuple(torch.cat([p[i] for p in parts]) for i in range(len(parts[0])))
+
+
+def mhsa(qkv, rows, T, dt, heads=16, lens=None, bias_ref=False, blocked=None):
     """Trunk self-attention launch for the flat query rows `rows`: qkv (B T, 3 D) operand values (q unscaled) -> (R, D)
-    operand type.  The kernel scales the fp32 logits by dh^-0.5 and rounds P to the operand type before P.V."""
+    operand type.  The kernel scales the fp32 logits by dh^-0.5 and rounds P to the operand type before P.V.
+    lens (ragged batch: valid frames per utterance): a query row of utterance b attends to keys < lens[b] only; the
+    rows past lens[b] may hold anything (NaN included): the reference selects, it never multiplies by a mask.
+    bias_ref: -> (ref, bound, pref), pref = the same output with P rounded where the kernel rounds it (``_p_rounded``; the
+    reference of the rounding-bias statistic, ``check(..., bias_ref=pref)``); blocked: the kernel is the key-blocked one
+    (default: T > 224, the dispatch of launch_mhsa_t; True as well under its mhsa_force_long knob)."""
+    if (lens is not None or T > 256) and len(rows) > ATT_CHUNK:  # (the shapes checked before masks existed: one pass, as ever)
+        return _chunked(lambda r: mhsa(qkv, r, T, dt, heads, lens, bias_ref, blocked), rows)
     D = qkv.shape[1] // 3
     dh = D // heads
     B = qkv.shape[0] // T
@@ -264,14 +341,70 @@ def mhsa(qkv, rows, T, dt, heads=16):
     q = x[b_i, t_i, 0]  # (R, H, dh)
     k = x[b_i, :, 1]  # (R, T, H, dh)
     v = x[b_i, :, 2]
+    mask = _key_mask(lens, b_i, T)
+    if mask is not None:
+        k = torch.where(mask[:, :, None, None], torch.zeros_like(k), k)
+        v = torch.where(mask[:, :, None, None], torch.zeros_like(v), v)
     s = torch.einsum("rhd,rthd->rht", q, k) * dh ** -0.5
     sa = torch.einsum("rhd,rthd->rht", q.abs(), k.abs()) * dh ** -0.5
-    return _softmax_av(s, sa, v, dt)
+    # fp16's absolute floor (F16_FLOOR): fp16 rounds P itself; fp16x3 up to 224 frames is the split-precision kernel, whose
+    # q, k, v, P and pair-form output are UNSCALED hi / lo pairs (beyond 224 frames that mode runs the fp32 VALU attention)
+    floor = "p" if dt == "fp16" else "pairs" if dt == "fp16x3" and T <= 224 else None
+    extra = F16_FLOOR * (q.abs().sum(-1)[..., None] + k.abs().sum(-1).transpose(1, 2)) * dh ** -0.5 if floor == "pairs" else None
+    ref, bnd = _softmax_av(s, sa, v, dt, extra=extra, mask=mask, floor=floor)
+    if not bias_ref:
+        return ref, bnd
+    sm = s if mask is None else s.masked_fill(mask[:, None, :], -float("inf"))
+    return ref, bnd, _p_rounded(sm, v, dt, 128 if (T > 224 if blocked is None else blocked) else None)
 
 
-def _softmax_av(s, sa, v, dt, extra=None):
+def _p_rounded(s, v, dt, block):
+    """The attention output with P rounded to the operand type where the trunk kernels round it, everything else exact:
+    sum_j op(P~_j) v_j / sum_j P~_j, the numerator's weights rounded, the row's sum not.  One-pass kernels (block None):
+    P~ = exp(s - max over all keys).  The key-blocked kernel (block = 128 keys): P~ = exp(s - running max) per block,
+    accumulator and sum rescaled by exp(old max - new max) when the maximum rises.  A correctly rounding output store
+    leaves the bias statistic of got against THIS value near 0 whatever the logits: against the exact output the statistic
+    also carries P's rounding, which all elements of one (utterance, head) share (bf16 -0.35 .. +0.17 ulp at 3 clips).
+    s (R, H, keys) with -inf at masked keys, v (R, keys, H, dh) -> (R, H * dh)."""
+    R, H, K = s.shape
+    if block is None:
+        p = torch.exp(s - s.amax(-1, keepdim=True))
+        out = torch.einsum("rht,rthd->rhd", op(p, dt), v) / p.sum(-1)[..., None]
+        return out.reshape(R, -1)
+    m = torch.full((R, H), -float("inf"), dtype=torch.float64)
+    l = torch.zeros(R, H, dtype=torch.float64)
+    acc = torch.zeros(R, H, v.shape[-1], dtype=torch.float64)
+    for j0 in range(0, K, block):
+        sb = s[..., j0:j0 + block]
+        mn = torch.maximum(m, sb.amax(-1))
+        corr = torch.where(torch.isinf(m), torch.zeros_like(m), torch.exp(m - mn))
+        p = torch.where(torch.isinf(sb), torch.zeros_like(sb), torch.exp(sb - mn[..., None]))
+        l = l * corr + p.sum(-1)
+        acc = acc * corr[..., None] + torch.einsum("rht,rthd->rhd", op(p, dt), v[:, j0:j0 + block])
+        m = mn
+    return (acc / l[..., None]).reshape(R, -1)
+
+
+# Absolute rounding floor of fp16: below 2^-14 its values are 2^-24 apart, so a rounding there errs by up to 2^-25 however
+# small the value (and by at most the value itself, when it rounds to 0).  The relative terms of the attention bound (u_op per
+# weight) do not cover it.  Derived from the number format, for the two places the trunk attention meets it (measured
+# on lively logits and on short clips: tests/test_gpu_insitu_ragged.py):
+#   "p"      fp16 operands: P~ = exp(s - max) is rounded to fp16 before P.V; a weight below 2^-14 errs by min(P~, 2^-25),
+#            not by 2^-11 P~.  |d out| <= sum_j min(P~_j, 2^-25) |v_j| / sum P~.  (bf16 has fp32's exponent range.)
+#   "pairs"  fp16x3, split-precision kernel: an UNSCALED hi / lo pair x = hi + lo has lo = fp16(x - hi) below 2^-14 whenever
+#            |x| < 2^-3, so the pair errs by up to 2^-25 absolutely, not by 2^-22 |x|.  That holds for v (|d out| <= sum_j
+#            P_j 2^-25 = 2^-25), for P~ (the term above), for the pair-form output row (2^-25) and for q and k, whose
+#            floors move a logit by <= (sum_d |q_d| + sum_d |k_d|) 2^-25 dh^-0.5 (passed as `extra`).
+F16_FLOOR = 2.0 ** -25
+
+
+def _softmax_av(s, sa, v, dt, extra=None, mask=None, floor=None):
     """P = softmax(s) over the last axis, out = P.v (v: (R, keys, H, dh)) -> (R, H * dh) operand type and its bound: P's
-    rounding (u_op per weight), the logits' accumulation (C_ACC * sa) moving P, the output's own ulp."""
+    rounding (u_op per weight), the logits' accumulation (C_ACC * sa) moving P, the output's own ulp.  mask (R, keys):
+    True = a key past the utterance's own length, P exactly 0 there (its k / v were zeroed by the caller).  floor: the
+    absolute-floor terms of F16_FLOOR ("p", "pairs" or None)."""
+    if mask is not None:
+        s = s.masked_fill(mask[:, None, :], -float("inf"))
     p = torch.softmax(s, dim=-1)
     out = torch.einsum("rht,rthd->rhd", p, v)
     pv = torch.einsum("rht,rthd->rhd", p, v.abs())
@@ -279,15 +412,22 @@ def _softmax_av(s, sa, v, dt, extra=None):
     # |d out| <= sum_j P_j |v_j - out| (|ds_j| + max |ds|) <= 2 max |ds| sum_j P_j (|v_j| + |out|)
     ds = es.amax(-1)[..., None]
     e = U_OP[dt] * 1.01 * pv + 2 * ds * (pv + out.abs()) + C_ACC[dt] * 16 * pv
+    if floor is not None:  # (P~_j = P_j / max P; sum P~ = 1 / max P)
+        e = e + torch.einsum("rht,rthd->rhd", torch.minimum(p, F16_FLOOR * p.amax(-1, keepdim=True)), v.abs())
+        if floor == "pairs":
+            e = e + 2 * F16_FLOOR
     R = out.shape[0]
     out, e = out.reshape(R, -1), e.reshape(R, -1)
     return out, e + ulp(out, dt)
 
 
-def shaw(qkv32, rel, rows, N, dt, heads=4):
+def shaw(qkv32, rel, rows, N, dt, heads=4, lens=None):
     """Conformer Shaw attention launch for flat query rows `rows`: qkv32 (B N, 3 inner) fp32 -> (R, inner) operand type.
     logits[i, j] = q_i.k_j + q_i.E[clamp(i - j, +-512) + 512] with q scaled by dh^-0.5 before it is rounded (fp16 / bf16),
-    k, v and the table rounded to the operand type."""
+    k, v and the table rounded to the operand type.  lens (ragged batch: valid FRAMES per utterance): a query row of
+    utterance b attends to the tokens < lens[b] + 1 only (the class token and its own frames)."""
+    if lens is not None and len(rows) > ATT_CHUNK:
+        return _chunked(lambda r: shaw(qkv32, rel, r, N, dt, heads, lens), rows)
     inner = qkv32.shape[1] // 3
     dh = inner // heads
     B = qkv32.shape[0] // N
@@ -299,12 +439,19 @@ def shaw(qkv32, rel, rows, N, dt, heads=4):
         qs = 1.0
     else:
         q, qs = x[b_i, t_i, 0], sc
-    k, v = op(x[b_i, :, 1], dt), op(x[b_i, :, 2], dt)
+    k, v = x[b_i, :, 1], x[b_i, :, 2]
+    mask = _key_mask(lens, b_i, N, 1)
+    if mask is not None:
+        k = torch.where(mask[:, :, None, None], torch.zeros_like(k), k)
+        v = torch.where(mask[:, :, None, None], torch.zeros_like(v), v)
+    k, v = op(k, dt), op(v, dt)
     dist = (t_i[:, None] - torch.arange(N)[None, :]).clamp(-MAX_POS, MAX_POS) + MAX_POS  # (R, N)
     E = op(d(rel), dt)[dist]  # (R, N, dh)
     s = (torch.einsum("rhd,rthd->rht", q, k) + torch.einsum("rhd,rtd->rht", q, E)) * qs
     sa = (torch.einsum("rhd,rthd->rht", q.abs(), k.abs()) + torch.einsum("rhd,rtd->rht", q.abs(), E.abs())) * qs
-    return _softmax_av(s, sa, v, dt)
+    if mask is not None:
+        sa = sa.masked_fill(mask[:, None, :], 0.0)
+    return _softmax_av(s, sa, v, dt, mask=mask)
 
 
 # ---- Conformer chains --------------------------------------------------------------------------------------------------
@@ -361,10 +508,16 @@ def chain_c(sd, p, x, u, dt):
     return layernorm(xd, sd[p + "post_norm.weight"], sd[p + "post_norm.bias"], dt, out="f32", acc=ed + ec)
 
 
-def glu_dwconv(sd, p, glu, B, N, dt):
-    """GLU -> depthwise conv (same padding) -> BatchNorm (eval) -> swish, glu (B N, 2 C2) fp32 -> (B N, C2) operand type."""
+def glu_dwconv(sd, p, glu, B, N, dt, lens=None):
+    """GLU -> depthwise conv (same padding) -> BatchNorm (eval) -> swish, glu (B N, 2 C2) fp32 -> (B N, C2) operand type.
+    lens (ragged batch: valid FRAMES per utterance): the gated input past lens[b] + 1 tokens is zero (selected, whatever
+    the rows hold), as the clip alone would see its zero padding; only the rows < lens[b] + 1 of the result mean anything."""
     a, g = glu.reshape(B, N, -1).chunk(2, dim=-1)
-    h = (a * torch.sigmoid(g)).transpose(1, 2)  # (B, C2, N)
+    h = a * torch.sigmoid(g)
+    if lens is not None:
+        past = torch.arange(N)[None, :] >= (torch.as_tensor([int(v) for v in lens]) + 1)[:, None]  # (B, N)
+        h = torch.where(past[:, :, None], torch.zeros_like(h), h)
+    h = h.transpose(1, 2)  # (B, C2, N)
     w = d(sd[p + "conv.net.4.conv.weight"])
     k = w.shape[-1]
     pad = (k // 2, k // 2 - (k + 1) % 2)
@@ -378,6 +531,39 @@ def glu_dwconv(sd, p, glu, B, N, dt):
     e = (dswish(zz) * C_ACC["fp16x3"] * 16 * (s * sc.abs()[None, :, None] + zz.abs() + sh.abs()[None, :, None] + 1) +
          C_POLY * (1 + zz.abs())).transpose(1, 2).reshape(B * N, -1)
     return y, e + ulp(y, dt)
+
+
+# ---- the two ends of a forward ----------------------------------------------------------------------------------------
+def final_layernorm(x, g, b, dt):
+    """The trunk's final LayerNorm: ONE launch, two outputs of the same fp32 value -- the fp32 feature rows (the "ssl" tap)
+    and the operand copy the back-end's first product reads ("ssl.op").  x (M, D) the last layer's fp32 rows ->
+    ((ref, bound) of the fp32 output, (ref, bound) of the operand output)."""
+    return layernorm(x, g, b, dt, out="f32"), layernorm(x, g, b, dt, out="op")
+
+
+def conf_tokens(sd, ssl_op, B, T, dt):
+    """The Conformer's tokens: the LL product (a GEMM launch, fp32 out) -> BatchNorm2d(1) (eval: one scalar scale and
+    shift, folded on the host in fp32) -> SELU -> the class token at row 0 of every utterance.  ssl_op (B T, 1024)
+    operand values -> (B (T + 1), E) fp32.  Bound: the product's, through one fp32 fma and the device's SELU (C_FN ulps
+    of its expf: ``selu_err``); the class-token rows are copies (bound 0)."""
+    z, e = product(ssl_op, sd["LL.weight"], sd["LL.bias"], dt)
+    sc32 = sd["first_bn.weight"].float() / torch.sqrt(sd["first_bn.running_var"].float() + torch.tensor(BN_EPS, dtype=torch.float32))
+    sh32 = sd["first_bn.bias"].float() - sd["first_bn.running_mean"].float() * sc32
+    sc, sh = d(sc32).reshape(()), d(sh32).reshape(())  # (the scalars as the engine folds them: fp32)
+    u = z * sc + sh
+    y, ey = selu(u), selu_err(u, e * sc.abs() + F32 * ((z * sc).abs() + sh.abs()))
+    E = z.shape[1]
+    cls = d(sd["conformer.class_token"]).reshape(1, 1, E).expand(B, 1, E)
+    ref = torch.cat([cls, y.reshape(B, T, E)], 1).reshape(B * (T + 1), E)
+    bnd = torch.cat([torch.zeros(B, 1, E, dtype=torch.float64), ey.reshape(B, T, E)], 1).reshape(B * (T + 1), E)
+    return ref, bnd
+
+
+def conf_logits(sd, block, B, N):
+    """The Conformer's classifier: fc5 on token 0 of every utterance, an fp32 fma chain per logit (64 lanes, then a wave
+    sum).  block (B N, E) the last block's fp32 rows -> (B, 2)."""
+    x0 = block.reshape(B, N, -1)[:, 0]
+    return aas_product(x0, d(sd["conformer.fc5.weight"]), sd["conformer.fc5.bias"], False)
 
 
 # ---- AASIST back-end --------------------------------------------------------------------------------------------------
@@ -767,9 +953,11 @@ def aasist_walk(sd, feats, tap, split):
 
 
 # ---- the check ---------------------------------------------------------------------------------------------------------
-def check(got, ref, bound, dt=None, rows=None):
+def check(got, ref, bound, dt=None, rows=None, bias_ref=None):
     """-> dict(ratio = max |got - ref| / bound, row (of `rows` when given), col, got / ref / bound of the worst element,
-    bias = the rounding-bias statistic (None unless dt names the operand type of got), n = elements checked)."""
+    bias = the rounding-bias statistic (None unless dt names the operand type of got), n = elements checked).
+    bias_ref: the value the output store rounds, where it is known more closely than `ref` (``mhsa(..., bias_ref=True)``):
+    the statistic is taken against it; the ratio always against `ref`."""
     ref = ref.reshape(ref.shape[0], -1)
     got, bound = d(got).reshape(ref.shape), bound.reshape(ref.shape) + ulp(ref, "fp32")  # (every tap is an fp32 value)
     err = (got - ref).abs()
@@ -779,9 +967,10 @@ def check(got, ref, bound, dt=None, rows=None):
     row, col = divmod(i, ref.shape[1])
     bias = None
     if dt is not None:
-        u = ulp(ref, dt)
-        m = (ref.abs() >= 2.0 ** _EMIN[dt]) & (ref != 0)
+        c = ref if bias_ref is None else bias_ref.reshape(ref.shape)
+        u = ulp(c, dt)
+        m = (c.abs() >= 2.0 ** _EMIN[dt]) & (c != 0)
         if bool(m.any()):
-            bias = float((torch.sign(ref) * (got - ref) / u)[m].mean())
+            bias = float((torch.sign(c) * (got - c) / u)[m].mean())
     return dict(ratio=float(r.reshape(-1)[i]), row=int(rows[row]) if rows is not None else row, col=col, got=float(got[row, col]),
                 ref=float(ref[row, col]), bound=float(bound[row, col]), bias=bias, n=ref.numel())

@@ -538,7 +538,10 @@ class Engine:
         decoded to (hi + lo) / scale).  Names:
           trunk   c0 .. c5 (conv layers' operand outputs), conv (layer 6, fp32), feats (feature LayerNorm), proj, xpad
                   (time-padded operand rows, pad rows included), pos, then per layer l: l{l}.ln1, l{l}.qkv, l{l}.att,
-                  l{l}.mid (x after the out-projection), l{l}.ln2, l{l}.ff, layer{l}; ssl (final LayerNorm, fp32)
+                  l{l}.mid (x after the out-projection), l{l}.ln2, l{l}.ff, layer{l}; ssl (final LayerNorm, fp32),
+                  ssl.op (the same launch's operand copy, what the back-end's first product reads).  A ragged forward
+                  taps the same names: rows past a clip's own length are unread by contract and hold whatever the
+                  workspace held
           head    tokens, then per block b: b{b}.xa, b{b}.qkv (after chain A / FF1 + QKV), b{b}.ao (attention output,
                   padded rows), b{b}.xb, b{b}.glu (after chain B), b{b}.u (depthwise conv output, padded rows), block{b};
                   the per-op path (``set("fuse_conformer", 0)``) also b{b}.{ff1,attn,conv,ff2}.hc (LayerNorm outputs),

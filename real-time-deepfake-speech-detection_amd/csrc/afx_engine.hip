@@ -1237,8 +1237,10 @@ static int run_trunk(afx_engine* e, const float* wave, int B, int L, Ws& w, hipS
   nf.out_f = w.ssl_f; nf.ldo_f = kD;
   nf.out_h = w.ssl_h; nf.ldo_h = kD;
   nf.nonfinite = e->nonfinite;  // overflow guard: an operand copy that left fp16's range anywhere in the trunk ends here as inf / NaN
+  nf.nf_lens = w.lens; nf.nf_rpb = Tt;  // (ragged batch: only the rows of an utterance's own length are judged; the others hold stale workspace)
   KOK(launch_rownorm(nf, dt, s));
   if (tap(e, "ssl", w.ssl_f, (size_t)M * kD, false, s)) return 1;
+  TAP("ssl.op", w.ssl_h, (size_t)M * kD, true, kD);
   return 0;
 }
 

@@ -2841,7 +2841,10 @@ __global__ __launch_bounds__(256) void rownorm_kernel(RowNormArgs a) {
     const float var = wave_sum(sq) * inv;
     const float rstd = 1.0f / sqrtf(var + a.eps);
     // overflow guard: an operand copy that left fp16's range upstream arrives here as inf / NaN statistics (NaN fails every compare)
-    if (a.nonfinite && lane == 0 && !(fabsf(mean) <= 3.0e38f && var <= 3.0e38f)) atomicAdd(a.nonfinite, 1);
+    // (ragged batch: a row past its utterance's own length is nobody's feature row -- its statistics are not judged)
+    if (a.nonfinite && lane == 0 && !(fabsf(mean) <= 3.0e38f && var <= 3.0e38f) &&
+        (!a.nf_lens || (int)(r % a.nf_rpb) < a.nf_lens[r / a.nf_rpb]))
+      atomicAdd(a.nonfinite, 1);
     const long orow = (r / a.rpb) * a.o_batch_rows + (r % a.rpb) + a.o_row_off;
     // the activation branch sits OUTSIDE the element loops: inlined per element, the three activations were
     // 3 k of this kernel's 3.8 k instructions (every LayerNorm of the two models is activation-free)

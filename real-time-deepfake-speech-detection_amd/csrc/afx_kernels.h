@@ -273,6 +273,8 @@ struct RowNormArgs {
   long ldo_h;
   int rpb, o_batch_rows, o_row_off;
   int* nonfinite;  // device counter or null: += 1 for every row whose statistics are not finite (the engine's overflow guard on the trunk's final LayerNorm)
+  const int* nf_lens;  // ragged batch (device, or null = every row counts): the guard judges row r only if r % nf_rpb < nf_lens[r / nf_rpb] --
+  int nf_rpb;          // the rows past an utterance's own length hold whatever the workspace held (the attention stores no such query row)
   int oh_pairs;  // split precision (with DT_FP32): != 0 = out_h receives the PAIR FORM of oh_scale x y in place of the fp32 row (ldo_h % 32 == 0)
   float oh_scale;
 };

@@ -1,6 +1,8 @@
 """Per-launch parity inside real forwards on an MI355X: every tapped launch of the SSL trunk, of the Conformer head and
 of the AASIST back-end against its fp64 reference (oracle/insitu.py) built from the launch's own tapped inputs, element by element within the
-bounds stated there.  Large products are checked on a deterministic subset of rows (``check_rows``).  The module's
+bounds stated there, from the conv stack to the final LayerNorm's two outputs and from the Conformer's tokens to its
+logits.  Large products are checked on a deterministic subset of rows (``check_rows``).  ``trunk_checks`` and
+``head_checks`` also take ragged batches (``clips``); tests/test_gpu_insitu_ragged.py runs those.  The module's
 summary line gives, per launch class and dtype, the worst |got - ref| / bound and the rounding-bias statistic."""
 import pytest
 import torch
@@ -68,14 +70,38 @@ def gate(cls, dt, where, res, insitu, fails, op_dt=False):
         fails.append(f"{where} [{dt}]: rounding bias {res['bias']:+.3f} ulp")
 
 
-def trunk_checks(mods, eng, sd, wave, dt, mode="layer_norm", conv=True):
-    """Run one taps-on forward of `eng` on `wave` and check every tapped launch of the trunk."""
+def _ragged(ST, clips):
+    """clips (1-D waveforms) -> (zero-padded batch (B, Lmax), per conv layer the valid lengths of every clip)."""
+    L = max(c.numel() for c in clips)
+    wave = torch.zeros(len(clips), L)
+    for b, c in enumerate(clips):
+        wave[b, :c.numel()] = c
+    per = [ST.conv_out_lengths(c.numel()) for c in clips]
+    return wave, [[p[i] for p in per] for i in range(7)]
+
+
+def trunk_checks(mods, eng, sd, wave, dt, mode="layer_norm", conv=True, clips=None, frames=None, few=False):
+    """Run one taps-on forward of `eng` on `wave` and check every tapped launch of the trunk.  clips (a list of 1-D
+    waveforms, `wave` ignored): the forward is ``eng.ssl_ragged(clips)`` and every launch is judged under the
+    key-padding masks, on the rows of each clip's own length only (``insitu.masked_rows``); frames: the frame counts the
+    clips were cut for (asserted with ``conv_out_lengths``).  -> the forward's profile (``Engine.profile_end``)."""
     engine, synth, I, ST = mods
+    lens_i = None
+    if clips is not None:
+        wave, lens_i = _ragged(ST, clips)
+        assert frames is None or lens_i[6] == list(frames), (lens_i[6], frames)
     B, L = wave.shape
     Ts = ST.conv_out_lengths(L)
     T = Ts[-1]
+    lens = lens_i[6] if clips is not None else None
     eng.enable_taps()
-    eng.ssl(wave.cuda())
+    eng.profile_begin()
+    if clips is not None:
+        _, got_frames = eng.ssl_ragged([c.cuda() for c in clips])
+        assert got_frames == lens
+    else:
+        eng.ssl(wave.cuda())
+    prof = eng.profile_end()
     torch.cuda.synchronize()
     tap = lambda n: eng.tap(n).cpu().double()
 
@@ -89,50 +115,65 @@ def trunk_checks(mods, eng, sd, wave, dt, mode="layer_norm", conv=True):
         prev = None
         for i in range(6):
             cur = tap(f"c{i}").reshape(B * Ts[i], C)
-            rows = conv_rows(B, Ts[i])
+            rows = conv_rows(B, Ts[i]) if lens is None else I.masked_rows(lens_i[i], Ts[i])
             ref = I.conv0(sd, wave, rows, dt, mode) if i == 0 else I.conv_layer(sd, i, prev, B, rows, dt, mode)
             g("conv0" if i == 0 else "conv", f"c{i}", cur[rows], ref, True, rows)
             prev = cur
-        rows = conv_rows(B, T)
+        rows = conv_rows(B, T) if lens is None else I.masked_rows(lens, T)
         g("conv", "conv", tap("conv").reshape(B * T, C)[rows], I.conv_layer(sd, 6, prev, B, rows, dt, mode, out="f32"), False, rows)
     if mode != "layer_norm":
         eng.enable_taps(False)
         assert not fails, "\n".join(fails)
-        return
+        return prof
+    # every valid row (row-local launches checked whole) and the subset the large launches are checked on
+    vr = torch.arange(B * T) if lens is None else I.valid_rows(lens, T)
+    rows = check_rows(B, T) if lens is None else I.masked_rows(lens, T)
     conv6 = tap("conv").reshape(B * T, C)
-    g("layernorm", "feats", tap("feats").reshape(B * T, C),
-      I.layernorm(conv6, sd["layer_norm.weight"], sd["layer_norm.bias"], dt), True)
+    g("layernorm", "feats", tap("feats").reshape(B * T, C)[vr],
+      I.layernorm(conv6[vr], sd["layer_norm.weight"], sd["layer_norm.bias"], dt), True, vr)
     feats = tap("feats").reshape(B * T, C)
-    rows = check_rows(B, T)
     D = 1024
     proj = tap("proj").reshape(B * T, D)
-    g("product", "proj", proj[rows], I.product(feats[rows], sd["post_extract_proj.weight"], sd["post_extract_proj.bias"], dt), False)
+    g("product", "proj", proj[rows], I.product(feats[rows], sd["post_extract_proj.weight"], sd["post_extract_proj.bias"], dt), False, rows)
     xpad = tap("xpad").reshape(B, T + 128, D)
     assert bool((xpad[:, :64] == 0).all()) and bool((xpad[:, 64 + T:] == 0).all()), f"xpad [{dt}]: nonzero pad rows"
     g("product", "xpad", xpad[:, 64:64 + T].reshape(B * T, D)[rows],
-      I.product(feats[rows], sd["post_extract_proj.weight"], sd["post_extract_proj.bias"], dt, out="op"), True)
+      I.product(feats[rows], sd["post_extract_proj.weight"], sd["post_extract_proj.bias"], dt, out="op"), True, rows)
     x = tap("pos").reshape(B * T, D)
-    g("posconv", "pos", x[rows], I.posconv(sd, xpad, proj, rows, T, dt), False)
+    g("posconv", "pos", x[rows], I.posconv(sd, xpad, proj, rows, T, dt, lens=lens), False, rows)
     wqkv = lambda p, k: torch.cat([sd[p + f"self_attn.{n}_proj.{k}"] for n in "qkv"], 0)
+    # "mhsa": the uniform batches this module has always run, bias asserted against the exact reference as ever.  The new
+    # batches -- under masks ("mhsa_masked"; "mhsa_long" from 225 frames on, the blocked any-length kernel) or uniform with
+    # few clips (`few`: "mhsa_few" / "mhsa_long") -- assert it too, against the reference that rounds P as the kernel does
+    # (insitu._p_rounded): with 1 .. 25 clips the exact reference's statistic carries P's own rounding, shared by all
+    # elements of an (utterance, head), and says nothing about the store
+    p_ref = lens is not None or few
+    att_cls = "mhsa" if not p_ref else "mhsa_long" if T > 224 else "mhsa_few" if lens is None else "mhsa_masked"
     for l in range(ST.num_layers(sd)):
         p, n = f"encoder.layers.{l}.", f"l{l}."
         ln1 = tap(n + "ln1").reshape(B * T, D)
-        g("layernorm", n + "ln1", ln1, I.layernorm(x, sd[p + "self_attn_layer_norm.weight"], sd[p + "self_attn_layer_norm.bias"], dt), True)
+        g("layernorm", n + "ln1", ln1[vr], I.layernorm(x[vr], sd[p + "self_attn_layer_norm.weight"], sd[p + "self_attn_layer_norm.bias"], dt), True, vr)
         qkv = tap(n + "qkv").reshape(B * T, 3 * D)
-        g("product", n + "qkv", qkv[rows], I.product(ln1[rows], wqkv(p, "weight"), wqkv(p, "bias"), dt, out="op"), True)
+        g("product", n + "qkv", qkv[rows], I.product(ln1[rows], wqkv(p, "weight"), wqkv(p, "bias"), dt, out="op"), True, rows)
         att = tap(n + "att").reshape(B * T, D)
-        g("mhsa", n + "att", att[rows], I.mhsa(qkv, rows, T, dt), True)
+        ar = I.mhsa(qkv, rows, T, dt, lens=lens, bias_ref=p_ref)
+        gate(att_cls, dt, n + "att", I.check(att[rows], ar[0], ar[1], dt, rows, bias_ref=ar[2] if p_ref else None), I, fails, True)
         mid = tap(n + "mid").reshape(B * T, D)
         g("product", n + "mid", mid[rows], I.product(att[rows], sd[p + "self_attn.out_proj.weight"], sd[p + "self_attn.out_proj.bias"],
-                                                      dt, resid=x[rows]), False)
+                                                      dt, resid=x[rows]), False, rows)
         ln2 = tap(n + "ln2").reshape(B * T, D)
-        g("layernorm", n + "ln2", ln2, I.layernorm(mid, sd[p + "final_layer_norm.weight"], sd[p + "final_layer_norm.bias"], dt), True)
+        g("layernorm", n + "ln2", ln2[vr], I.layernorm(mid[vr], sd[p + "final_layer_norm.weight"], sd[p + "final_layer_norm.bias"], dt), True, vr)
         ff = tap(n + "ff").reshape(B * T, 4096)
-        g("product", n + "ff", ff[rows], I.product(ln2[rows], sd[p + "fc1.weight"], sd[p + "fc1.bias"], dt, act="gelu", out="op"), True)
+        g("product", n + "ff", ff[rows], I.product(ln2[rows], sd[p + "fc1.weight"], sd[p + "fc1.bias"], dt, act="gelu", out="op"), True, rows)
         x = tap(f"layer{l}").reshape(B * T, D)
-        g("product", f"layer{l}", x[rows], I.product(ff[rows], sd[p + "fc2.weight"], sd[p + "fc2.bias"], dt, resid=mid[rows]), False)
+        g("product", f"layer{l}", x[rows], I.product(ff[rows], sd[p + "fc2.weight"], sd[p + "fc2.bias"], dt, resid=mid[rows]), False, rows)
+    # the final LayerNorm: one launch, the fp32 feature rows and the operand copy the back-end reads
+    r32, rop = I.final_layernorm(x[vr], sd["encoder.layer_norm.weight"], sd["encoder.layer_norm.bias"], dt)
+    g("final_ln", "ssl", tap("ssl").reshape(B * T, D)[vr], r32, False, vr)
+    g("final_ln", "ssl.op", tap("ssl.op").reshape(B * T, D)[vr], rop, True, vr)
     eng.enable_taps(False)
     assert not fails, "\n".join(fails)
+    return prof
 
 
 def _trunk(mods, n_layers, dt, mode="layer_norm"):
@@ -155,6 +196,24 @@ def test_trunk_launches_other_shapes_fp16(mods, B, L):
     trunk_checks(mods, eng, sd, mods[1].waveforms(B, L, batch_idx=B + L), "fp16", conv=B < 64)
 
 
+# uniform batches in the attention families the shapes above never reach: (3, 100) = mhsa_kernel<4,4> with the z-split,
+# (2, 449) = the blocked any-length kernel over four 128-key blocks (fp16x3: the fp32 VALU attention and the product-form
+# positional conv), and in the dtypes that had run (16, 199) only (3, 201) = <7,7> and (1, 1) = <2,4>.  The profile has
+# ONE class for every trunk-attention kernel, so it cannot tell the families apart: the family follows from T and H * B by
+# launch_mhsa_t's dispatch; the positional conv's two forms are told apart by the "posconv_kernel" class.
+@pytest.mark.parametrize("B,T,dt", [(B, T, dt) for B, T in ((3, 100), (2, 449)) for dt in ("fp16", "bf16", "fp32", "fp16x3")] +
+                         [(B, T, dt) for B, T in ((3, 201), (1, 1)) for dt in ("bf16", "fp32", "fp16x3")])
+def test_trunk_launches_uniform_attention_families(mods, B, T, dt):
+    engine, synth, I, ST = mods
+    L = 400 + 320 * (T - 1)
+    assert ST.conv_out_lengths(L)[-1] == T
+    eng, sd = _trunk(mods, 1, dt)
+    prof = trunk_checks(mods, eng, sd, synth.waveforms(B, L, batch_idx=3 * B + T), dt, conv=False, few=True)
+    assert prof["mhsa_kernel"]["launches"] == 1
+    if dt in I.HALF:
+        assert prof["posconv_kernel"]["launches"] == (1 if T <= 224 else 0)
+
+
 def test_trunk_posconv_gemm_form(mods):
     eng, sd = _trunk(mods, 1, "fp16")
     eng.set("posconv_sliding", 0)
@@ -167,13 +226,27 @@ def test_trunk_group_norm_extractor(mods):
 
 
 # ---- Conformer head ------------------------------------------------------------------------------------------------------
-def head_checks(mods, eng, sd, feats, dt, fused):
+def head_checks(mods, eng, sd, feats, dt, fused, clips=None, wave=None, frames=None):
+    """One taps-on forward and every tapped launch of the Conformer head, from the tokens to the classifier's logits.
+    feats (B, T, 1024): ``eng.head(feats)``.  wave (B, L): a whole ``eng.forward(wave)``, the head reads the trunk's
+    operand copy ("ssl.op").  clips (a list of 1-D waveforms): ``eng.forward_ragged(clips)``, every launch judged under
+    the key-padding masks on the tokens of each clip's own length (its frames + 1) only."""
     engine, synth, I, ST = mods
-    B, T, _ = feats.shape
+    eng.enable_taps()
+    lens = None
+    if clips is not None:
+        lens = [ST.conv_out_lengths(c.numel())[-1] for c in clips]
+        assert frames is None or lens == list(frames), (lens, frames)
+        B, T = len(clips), max(lens)
+        logits = eng.forward_ragged([c.cuda() for c in clips])
+    elif wave is not None:
+        B, T = wave.shape[0], ST.conv_out_lengths(wave.shape[1])[-1]
+        logits = eng.forward(wave.cuda())
+    else:
+        B, T, _ = feats.shape
+        logits = eng.head(feats.cuda())
     N, E = T + 1, 144
     M = B * N
-    eng.enable_taps()
-    eng.head(feats.cuda())
     torch.cuda.synchronize()
     tap = lambda n: eng.tap(n).cpu().double()
 
@@ -182,25 +255,33 @@ def head_checks(mods, eng, sd, feats, dt, fused):
     def g(cls, where, got, ref_bnd, op_dt, rows=None):
         gate(cls, dt, where, I.check(got, ref_bnd[0], ref_bnd[1], dt if op_dt else None, rows), I, fails, op_dt)
 
+    # vr: every token row that means something; rows: the subset the attention is checked on
+    vr = torch.arange(M) if lens is None else I.valid_rows([n + 1 for n in lens], N)
+    rows = check_rows(B, N) if lens is None else I.masked_rows([n + 1 for n in lens], N)
+    # the head's input as its first product reads it: the trunk's operand copy, or the given features rounded
+    ssl_op = I.op(I.d(feats).reshape(B * T, 1024), dt) if feats is not None else tap("ssl.op").reshape(B * T, 1024)
     x = tap("tokens").reshape(M, E)
+    tok = I.conf_tokens(sd, ssl_op, B, T, dt)
+    g("tokens", "tokens", x[vr], (tok[0][vr], tok[1][vr]), False, vr)
     Ep = eng.tap("b0.ao").numel() // M  # (operand rows padded to whole 64-column K-steps)
-    rows = check_rows(B, N)
+    shaw_cls, dw_cls = ("shaw", "dwconv") if lens is None else ("shaw_masked", "dwconv_masked")
     for b in range(2):
         p, n = f"conformer.encoder_blocks.{b}.", f"b{b}."
-        (xa_r, qkv_r) = I.chain_a(sd, p, x, dt)
+        (xa_r, qkv_r) = I.chain_a(sd, p, x[vr], dt)
         xa, qkv = tap(n + "xa").reshape(M, E), tap(n + "qkv").reshape(M, 3 * E)
-        g("chain_a", n + "xa", xa, xa_r, False)
-        g("chain_a", n + "qkv", qkv, qkv_r, False)
+        g("chain_a", n + "xa", xa[vr], xa_r, False, vr)
+        g("chain_a", n + "qkv", qkv[vr], qkv_r, False, vr)
         ao = tap(n + "ao").reshape(M, Ep)
         if not bool((ao[:, E:] == 0).all()):
             fails.append(f"{n}ao [{dt}]: nonzero pad columns")
-        g("shaw", n + "ao", ao[rows, :E], I.shaw(qkv, sd[p + "attn.fn.rel_pos_emb.weight"], rows, N, dt), True, rows)
-        xb_r, glu_r = I.chain_b(sd, p, xa, ao[:, :E], dt)
+        g(shaw_cls, n + "ao", ao[rows, :E], I.shaw(qkv, sd[p + "attn.fn.rel_pos_emb.weight"], rows, N, dt, lens=lens), True, rows)
+        xb_r, glu_r = I.chain_b(sd, p, xa[vr], ao[vr, :E], dt)
         xb, glu = tap(n + "xb").reshape(M, E), tap(n + "glu").reshape(M, 576)
-        g("chain_b", n + "xb", xb, xb_r, False)
-        g("chain_b", n + "glu", glu, glu_r, False)
+        g("chain_b", n + "xb", xb[vr], xb_r, False, vr)
+        g("chain_b", n + "glu", glu[vr], glu_r, False, vr)
         u = tap(n + "u").reshape(M, -1)
-        g("dwconv", n + "u", u[:, :288], I.glu_dwconv(sd, p, glu, B, N, dt), True)
+        dw = I.glu_dwconv(sd, p, glu, B, N, dt, lens=lens)
+        g(dw_cls, n + "u", u[vr, :288], (dw[0][vr], dw[1][vr]), True, vr)
         if not fused:  # (the fused chain C reads the 288 real columns of u only; the per-op product reads them all)
             if not bool((u[:, 288:] == 0).all()):
                 fails.append(f"{n}u [{dt}]: nonzero pad columns")
@@ -210,8 +291,11 @@ def head_checks(mods, eng, sd, feats, dt, fused):
                 if not bool((t[:, k:] == 0).all()):
                     fails.append(f"{n}{h} [{dt}]: nonzero pad columns")
         blk = tap(f"block{b}").reshape(M, E)
-        g("chain_c", f"block{b}", blk, I.chain_c(sd, p, xb, u[:, :288], dt), False)
+        g("chain_c", f"block{b}", blk[vr], I.chain_c(sd, p, xb[vr], u[vr, :288], dt), False, vr)
         x = blk
+    # the classifier reads token 0 of every utterance
+    first = torch.arange(B) * N
+    g("logits", "logits", logits.cpu().double(), I.conf_logits(sd, x[first], B, 1), False)
     eng.enable_taps(False)
     assert not fails, "\n".join(fails)
 
@@ -247,6 +331,14 @@ def test_head_launches_edge_shapes(mods, B, T, dt, fused):
 def test_head_launches_even_kernel(mods):
     eng, sd = _head(mods, "fp16", 1, kernel=16)
     head_checks(mods, eng, sd, _feats(3, 124, 7), "fp16", 1)
+
+
+@pytest.mark.parametrize("dt,fused", [("fp16", 1), ("bf16", 1), ("fp16x3", 0), ("fp32", 0)])
+def test_conformer_forward_both_ends(mods, dt, fused):
+    """A whole ``forward``: the head's tokens from the trunk's own operand copy of the final LayerNorm ("ssl.op", the
+    second output of that launch), every head launch, and the classifier's logits as the call returns them."""
+    eng, sd = _head(mods, dt, fused)
+    head_checks(mods, eng, sd, None, dt, fused, wave=mods[1].waveforms(3, 16000, batch_idx=31))
 
 
 # ---- AASIST back-end ---------------------------------------------------------------------------------------------------------
