@@ -182,27 +182,35 @@ class SpeechGate:
         return {"nf": np.float32(np.inf), "h": 0}
 
     # ---- the numpy restatement -------------------------------------------------------------------------------------------
-    def _decide(self, x, st):
-        """The per-frame decision over x (whole frames) from the state st -> (frames (m, frame), speech, keep, nf, h)."""
+    def _frames(self, x):
         x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
         if x.size % self.frame:
             raise ValueError(f"{x.size} samples are not whole frames of {self.frame}")
+        return x.reshape(-1, self.frame)
+
+    def _decide(self, x, st, between=None):
+        """The per-frame decision over x (whole frames) from the state st -> (frames (m, frame), speech, keep, nf, h).
+        ``between(f, e, speech, h) -> (speech, h)`` is a form's own step on frame f of energy e, between the floor update
+        and the hangover (the ``ToneGate``'s: the module docstring states that it belongs there)."""
+        frames = self._frames(x)
         nf, h = np.float32(st["nf"]), int(st["h"])
         E_floor, ratio, rise, nf_min, inf = self.E_floor, self.ratio32, self.rise32, self.nf_min, np.float32(np.inf)
-        e_all = frame_energies(x, self.frame)
+        e_all = frame_energies(frames, self.frame)
         speech, keep = np.zeros(e_all.size, dtype=bool), np.zeros(e_all.size, dtype=bool)
-        with np.errstate(over="ignore"):
+        with np.errstate(over="ignore", invalid="ignore", under="ignore"):
             for f, e in enumerate(e_all):
                 fin = bool(e < inf)
-                speech[f] = fin and bool(e > max(E_floor, np.float32(ratio * nf)))
+                sp = fin and bool(e > max(E_floor, np.float32(ratio * nf)))
                 if fin:
                     nf = max(nf_min, min(e, np.float32(nf * rise)))
-                if speech[f]:
+                if between is not None:
+                    sp, h = between(f, e, sp, h)
+                if sp:
                     h = self.hang
-                keep[f] = speech[f] or h > 0
-                if not speech[f] and h > 0:
+                speech[f], keep[f] = sp, sp or h > 0
+                if not sp and h > 0:
                     h -= 1
-        return x.reshape(-1, self.frame), speech, keep, np.float32(nf), h
+        return frames, speech, keep, np.float32(nf), h
 
     def gate_reference(self, x, state=None):
         """The function in numpy.  x: host fp32 array of whole frames (1-D, a multiple of ``frame`` samples); state: what an
@@ -212,51 +220,77 @@ class SpeechGate:
         return keep, frames[keep].reshape(-1).copy(), {"nf": nf, "h": h}
 
     # ---- the device form ---------------------------------------------------------------------------------------------------
-    def _launch(self, x, hdr, nf, h, ring, kept, mask=None):
-        """afx_k_gate over the rows of x ((A, n) fp32 on the GPU, contiguous) with this gate's constants."""
+    # What a form supplies to the offline form below and to ``GatedScorer``: the session keys it adds, the zero frames the
+    # offline form appends, its per-slot device state beyond nf and h, its header, its launch and what it collects per clip.
+    _session_keys = ()
+    _pad = 0
+
+    def _new_extra(self, S, ring_len, dev):
+        """The form's device state beyond ``nf`` and ``h`` for S fresh slots with rings of ring_len samples (and the tables
+        its launch reads) -> a dict of tensors; a ``GatedScorer`` shows them as attributes of these names."""
+        return {}
+
+    def _reset_extra(self, extra, rows):
+        """Slots ``rows`` (a device index tensor) of the form's state become a new stream's."""
+
+    def _header(self, slot, wpos, seen, dev):
+        """-> the launch's header on ``dev``, without synchronisation: per row the slot, its ring's write position and
+        whatever the form derives from the samples the slot has seen."""
+        return upload_pairs(slot, wpos, dev)
+
+    def _launch(self, x, hdr, nf, h, ring, kept, extra, mask=None):
+        """afx_k_gate over the rows of x ((A, n) fp32 on the GPU, contiguous) with this gate's constants -> the form's
+        by-product of a streamed push (``ToneGate``: the tone frames of each row; else None)."""
         check(call_on(x, lib().afx_k_gate, ptr(x), x.shape[0], x.shape[1], ptr(hdr), self.frame, float(self.E_floor),
                       float(self.ratio32), float(self.rise32), self.hang, ptr(nf), ptr(h), ptr(ring), ring.shape[0], ring.shape[1],
                       ptr(kept), ptr(mask)))
 
-    def gate(self, clips, return_mask=False):
-        """The offline form: ``afx_k_gate`` over whole clips, each with fresh state.  clips: a list of 1-D CUDA fp32 tensors
-        (any lengths) or a (B, n) CUDA tensor -> the list of kept-audio tensors (1-D, possibly empty), ready for
-        ``model.forward_ragged``; with ``return_mask`` also the list of per-frame bool masks.  Trailing samples short of a
-        whole frame are dropped.  One launch sequence and one read-back of the counts per distinct clip length."""
+    def _collect(self, extra, mask, r, k):
+        """-> what the offline form returns for row r beside its k kept samples (mask: (A, frames + _pad) uint8 or None)."""
+        return () if mask is None else (mask[r].bool(),)
+
+    def _offline(self, clips, want_mask, picks):
+        """The offline form of every gate: the form's launch over whole clips, each with fresh state and ``_pad`` zero
+        frames appended; one launch sequence and one read-back of the counts per distinct clip length (and 65535 clips).
+        -> per pick j the list over the clips of entry j of (kept audio, *_collect(...)); a single pick: that list."""
         clips = list(clips.unbind(0)) if isinstance(clips, torch.Tensor) and clips.ndim == 2 else list(clips)
         for c in clips:
             if not isinstance(c, torch.Tensor) or c.ndim != 1 or c.dtype != torch.float32:
                 raise ValueError("gate: a list of 1-D fp32 tensors or a (B, n) tensor")
             if not c.is_cuda:
                 raise AfxError("the gate runs on the GPU; there is no CPU fallback (gate_reference is the numpy restatement)")
-        out, masks = [None] * len(clips), [None] * len(clips)
+        got = [None] * len(clips)
         groups = {}
         for i, c in enumerate(clips):
             groups.setdefault((c.device, c.numel() // self.frame), []).append(i)
         for (dev, frames), rows in groups.items():
-            if frames == 0:
-                for i in rows:
-                    out[i] = torch.empty(0, dtype=torch.float32, device=dev)
-                    masks[i] = torch.zeros(0, dtype=torch.bool, device=dev)
-                continue
-            n = frames * self.frame
+            n, total = frames * self.frame, frames + self._pad
             with torch.cuda.device(dev):
                 for lo in range(0, len(rows), 65535):
                     part = rows[lo:lo + 65535]
                     A = len(part)
-                    x = torch.stack([clips[i][:n] for i in part]).contiguous()
-                    hdr = torch.stack([torch.arange(A, dtype=torch.int32), torch.zeros(A, dtype=torch.int32)], dim=1).to(dev)
-                    nf = torch.full((A,), float("inf"), dtype=torch.float32, device=dev)
-                    h = torch.zeros(A, dtype=torch.int32, device=dev)
-                    ring = torch.empty(A, n, dtype=torch.float32, device=dev)
+                    extra = self._new_extra(A, total * self.frame, dev)
+                    mask = torch.zeros(A, total, dtype=torch.uint8, device=dev) if want_mask else None
+                    ring = torch.empty(A, total * self.frame, dtype=torch.float32, device=dev)
                     kept = torch.zeros(A, dtype=torch.int32, device=dev)
-                    mask = torch.zeros(A, frames, dtype=torch.uint8, device=dev) if return_mask else None
-                    self._launch(x, hdr, nf, h, ring, kept, mask)
+                    if frames:  # (a clip without a whole frame: nothing to launch, nothing kept)
+                        x = torch.stack([clips[i][:n] for i in part])
+                        x = torch.nn.functional.pad(x, (0, self._pad * self.frame)) if self._pad else x.contiguous()
+                        hdr = self._header(np.arange(A), np.zeros(A, dtype=np.int64), np.zeros(A, dtype=np.int64), dev)
+                        nf = torch.full((A,), float("inf"), dtype=torch.float32, device=dev)
+                        h = torch.zeros(A, dtype=torch.int32, device=dev)
+                        self._launch(x, hdr, nf, h, ring, kept, extra, mask)
                     for r, (i, k) in enumerate(zip(part, kept.tolist())):
-                        out[i] = ring[r, :k].clone()
-                        if return_mask:
-                            masks[i] = mask[r].bool()
-        return (out, masks) if return_mask else out
+                        got[i] = (ring[r, :k].clone(),) + self._collect(extra, mask, r, k)
+        res = tuple([g[j] for g in got] for j in picks)
+        return res if len(res) > 1 else res[0]
+
+    def gate(self, clips, return_mask=False):
+        """The offline form: ``afx_k_gate`` over whole clips, each with fresh state.  clips: a list of 1-D CUDA fp32 tensors
+        (any lengths) or a (B, n) CUDA tensor -> the list of kept-audio tensors (1-D, possibly empty), ready for
+        ``model.forward_ragged``; with ``return_mask`` also the list of per-frame bool masks.  Trailing samples short of a
+        whole frame are dropped.  One launch sequence and one read-back of the counts per distinct clip length."""
+        return self._offline(clips, return_mask, (0, 1) if return_mask else (0,))
 
 
 class LookaheadGate(SpeechGate):
@@ -297,11 +331,32 @@ class LookaheadGate(SpeechGate):
         return mask, both[:decided][mask].reshape(-1).copy(), sources, new
 
     # ---- the device form ---------------------------------------------------------------------------------------------------
-    def _launch_la(self, x, hdr, nf, h, flags, line, ring, src, kept, mask=None):
+    _session_keys = ("gate_line", "gate_flags", "gate_sources")
+    _pad = property(lambda self: self.pre)
+
+    def _new_extra(self, S, ring_len, dev):
+        return dict(flags=torch.zeros(S, dtype=torch.int32, device=dev),
+                    line=torch.zeros(S, self.pre * self.frame, dtype=torch.float32, device=dev),
+                    src=torch.full((S, ring_len // self.frame), -1, dtype=torch.int32, device=dev))
+
+    def _reset_extra(self, extra, rows):
+        extra["flags"][rows] = 0  # (the line's frames are then flagged by nobody and leave unemitted)
+        extra["src"][rows] = -1
+
+    def _header(self, slot, wpos, seen, dev):
+        hdr = torch.zeros(len(slot), 4, dtype=torch.int32, pin_memory=True)
+        hdr.numpy()[:, :3] = np.stack([slot, wpos, seen // self.frame], axis=1)  # F is host arithmetic
+        return hdr.to(dev, non_blocking=True)
+
+    def _launch(self, x, hdr, nf, h, ring, kept, extra, mask=None):
         """afx_k_gate_la over the rows of x ((A, n) fp32 on the GPU, contiguous; hdr (A, 4)) with this gate's constants."""
         check(call_on(x, lib().afx_k_gate_la, ptr(x), x.shape[0], x.shape[1], ptr(hdr), self.frame, float(self.E_floor),
-                      float(self.ratio32), float(self.rise32), self.hang, self.pre, ptr(nf), ptr(h), ptr(flags), ptr(line),
-                      ptr(ring), ptr(src), ring.shape[0], ring.shape[1], ptr(kept), ptr(mask)))
+                      float(self.ratio32), float(self.rise32), self.hang, self.pre, ptr(nf), ptr(h), ptr(extra["flags"]),
+                      ptr(extra["line"]), ptr(ring), ptr(extra["src"]), ring.shape[0], ring.shape[1], ptr(kept), ptr(mask)))
+
+    def _collect(self, extra, mask, r, k):
+        sources = extra["src"][r, :k // self.frame].long()
+        return (sources,) if mask is None else (sources, mask[r, self.pre:].bool())  # (mask entry j is the frame j - pre)
 
     def gate(self, clips, return_mask=False, return_sources=False):
         """The offline form: ``afx_k_gate_la`` over whole clips, each with fresh state and ``pre`` zero frames appended so
@@ -309,49 +364,7 @@ class LookaheadGate(SpeechGate):
         ``SpeechGate.gate`` -> the list of gated-audio tensors; with ``return_mask`` also the list of per-frame bool masks
         (keep' of every real frame), with ``return_sources`` also the list of int64 tensors of the emitted frames' indices.
         Trailing samples short of a whole frame are dropped."""
-        clips = list(clips.unbind(0)) if isinstance(clips, torch.Tensor) and clips.ndim == 2 else list(clips)
-        for c in clips:
-            if not isinstance(c, torch.Tensor) or c.ndim != 1 or c.dtype != torch.float32:
-                raise ValueError("gate: a list of 1-D fp32 tensors or a (B, n) tensor")
-            if not c.is_cuda:
-                raise AfxError("the gate runs on the GPU; there is no CPU fallback (gate_reference is the numpy restatement)")
-        out, masks, srcs = [None] * len(clips), [None] * len(clips), [None] * len(clips)
-        groups = {}
-        for i, c in enumerate(clips):
-            groups.setdefault((c.device, c.numel() // self.frame), []).append(i)
-        for (dev, frames), rows in groups.items():
-            if frames == 0:
-                for i in rows:
-                    out[i] = torch.empty(0, dtype=torch.float32, device=dev)
-                    masks[i] = torch.zeros(0, dtype=torch.bool, device=dev)
-                    srcs[i] = torch.zeros(0, dtype=torch.int64, device=dev)
-                continue
-            n, total = frames * self.frame, frames + self.pre
-            with torch.cuda.device(dev):
-                for lo in range(0, len(rows), 65535):
-                    part = rows[lo:lo + 65535]
-                    A = len(part)
-                    x = torch.zeros(A, total * self.frame, dtype=torch.float32, device=dev)
-                    x[:, :n] = torch.stack([clips[i][:n] for i in part])
-                    hdr = torch.zeros(A, 4, dtype=torch.int32)
-                    hdr[:, 0] = torch.arange(A, dtype=torch.int32)
-                    hdr = hdr.to(dev)
-                    nf = torch.full((A,), float("inf"), dtype=torch.float32, device=dev)
-                    h = torch.zeros(A, dtype=torch.int32, device=dev)
-                    flags = torch.zeros(A, dtype=torch.int32, device=dev)
-                    line = torch.empty(A, self.pre * self.frame, dtype=torch.float32, device=dev)
-                    ring = torch.empty(A, total * self.frame, dtype=torch.float32, device=dev)
-                    src = torch.full((A, total), -1, dtype=torch.int32, device=dev)
-                    kept = torch.zeros(A, dtype=torch.int32, device=dev)
-                    mask = torch.zeros(A, total, dtype=torch.uint8, device=dev) if return_mask else None
-                    self._launch_la(x, hdr, nf, h, flags, line, ring, src, kept, mask)
-                    for r, (i, k) in enumerate(zip(part, kept.tolist())):
-                        out[i] = ring[r, :k].clone()
-                        srcs[i] = src[r, :k // self.frame].long()
-                        if return_mask:
-                            masks[i] = mask[r, self.pre:].bool()  # (entry j is the frame j - pre)
-        res = (out,) + ((masks,) if return_mask else ()) + ((srcs,) if return_sources else ())
-        return res if len(res) > 1 else out
+        return self._offline(clips, return_mask, (0,) + ((2,) if return_mask else ()) + ((1,) if return_sources else ()))
 
 
 class ToneGate(SpeechGate):
@@ -391,12 +404,6 @@ class ToneGate(SpeechGate):
         return {"nf": np.float32(np.inf), "h": 0, "r": 0, "q": 0, "tones": 0}
 
     # ---- the numpy restatement -------------------------------------------------------------------------------------------
-    def _frames(self, x):
-        x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
-        if x.size % self.frame:
-            raise ValueError(f"{x.size} samples are not whole frames of {self.frame}")
-        return x.reshape(-1, self.frame)
-
     def tone_powers(self, x):
         """x: host fp32 array of whole frames -> (frames, K) fp32, the Goertzel power P_k of every frame at every bank
         frequency, in the operation order the module docstring states."""
@@ -427,35 +434,26 @@ class ToneGate(SpeechGate):
     def _decide_tone(self, x, st):
         """The per-frame decision over x (whole frames) from the state st -> (frames (m, frame), T, tonal, tone, keep, the
         state after x)."""
-        frames = self._frames(x)
-        nf, h, r, q, tones = np.float32(st["nf"]), int(st["h"]), int(st["r"]), int(st["q"]), int(st["tones"])
-        E_floor, ratio, rise, nf_min, inf = self.E_floor, self.ratio32, self.rise32, self.nf_min, np.float32(np.inf)
-        top = (1 << 31) - 1
-        e_all, T_all = frame_energies(frames, self.frame), self._tone_sums(frames)
-        tonal_all, tone_all, keep_all = (np.zeros(e_all.size, dtype=bool) for _ in range(3))
-        with np.errstate(over="ignore", invalid="ignore", under="ignore"):
-            for f, (e, T) in enumerate(zip(e_all, T_all)):
-                fin = bool(e < inf)
-                speech = fin and bool(e > max(E_floor, np.float32(ratio * nf)))
-                if fin:
-                    nf = max(nf_min, min(e, np.float32(nf * rise)))
-                tonal = fin and bool(e > E_floor) and bool(T >= np.float32(self.thr * e))
-                r = min(r + 1, top) if tonal else 0
-                if r >= self.confirm:
-                    q = self.hold
-                tone = r >= self.confirm or q > 0
-                if r < self.confirm and q > 0:
-                    q -= 1
-                tones = min(tones + tone, top)
-                if tone:
-                    speech, h = False, 0
-                if speech:
-                    h = self.hang
-                keep = speech or h > 0
-                if not speech and h > 0:
-                    h -= 1
-                tonal_all[f], tone_all[f], keep_all[f] = tonal, tone, keep
-        return frames, T_all, tonal_all, tone_all, keep_all, {"nf": np.float32(nf), "h": h, "r": r, "q": q, "tones": tones}
+        T_all = self._tone_sums(x)
+        r, q, tones = int(st["r"]), int(st["q"]), int(st["tones"])
+        top, inf = (1 << 31) - 1, np.float32(np.inf)
+        tonal_all, tone_all = np.zeros(T_all.size, dtype=bool), np.zeros(T_all.size, dtype=bool)
+
+        def between(f, e, speech, h):
+            nonlocal r, q, tones
+            tonal = bool(e < inf) and bool(e > self.E_floor) and bool(T_all[f] >= np.float32(self.thr * e))
+            r = min(r + 1, top) if tonal else 0
+            if r >= self.confirm:
+                q = self.hold
+            tone = r >= self.confirm or q > 0
+            if r < self.confirm and q > 0:
+                q -= 1
+            tones = min(tones + tone, top)
+            tonal_all[f], tone_all[f] = tonal, tone
+            return (False, 0) if tone else (speech, h)  # a tone is not speech and ends the hangover
+
+        frames, _, keep, nf, h = self._decide(x, st, between)
+        return frames, T_all, tonal_all, tone_all, keep, {"nf": nf, "h": h, "r": r, "q": q, "tones": tones}
 
     def gate_reference(self, x, state=None):
         """The function in numpy.  x: host fp32 array of whole frames; state: what an earlier call returned (None: a new
@@ -470,58 +468,33 @@ class ToneGate(SpeechGate):
         return self._decide_tone(x, self.new_state() if state is None else state)[1:5]
 
     # ---- the device form ---------------------------------------------------------------------------------------------------
-    def _launch_tone(self, x, hdr, coef, nf, h, tone_state, ring, kept, ntone=None, mask=None, tsum=None):
-        """afx_k_gate_tone over the rows of x ((A, n) fp32 on the GPU, contiguous) with this gate's constants; coef: this
-        gate's ``coef`` on x's device."""
+    _session_keys = ("gate_tone",)
+
+    def _new_extra(self, S, ring_len, dev):
+        return dict(coef=torch.from_numpy(self.coef.copy()).to(dev), tone_state=torch.zeros(S, 3, dtype=torch.int32, device=dev))
+
+    def _reset_extra(self, extra, rows):
+        extra["tone_state"][rows] = 0
+
+    def _launch(self, x, hdr, nf, h, ring, kept, extra, mask=None):
+        """afx_k_gate_tone over the rows of x ((A, n) fp32 on the GPU, contiguous) with this gate's constants -> (A,) int32
+        on the device: the tone frames of each row."""
+        coef, ntone = extra["coef"], torch.empty(x.shape[0], dtype=torch.int32, device=x.device)
         check(call_on(x, lib().afx_k_gate_tone, ptr(x), x.shape[0], x.shape[1], ptr(hdr), self.frame, float(self.E_floor),
                       float(self.ratio32), float(self.rise32), self.hang, ptr(coef), coef.numel(), float(self.thr), self.confirm,
-                      self.hold, ptr(nf), ptr(h), ptr(tone_state), ptr(ring), ring.shape[0], ring.shape[1], ptr(kept), ptr(ntone),
-                      ptr(mask), ptr(tsum)))
+                      self.hold, ptr(nf), ptr(h), ptr(extra["tone_state"]), ptr(ring), ring.shape[0], ring.shape[1], ptr(kept),
+                      ptr(ntone), ptr(mask), None))
+        return ntone
+
+    def _collect(self, extra, mask, r, k):
+        return () if mask is None else ((mask[r] & 1).bool(), (mask[r] & 2).bool())
 
     def gate(self, clips, return_mask=False, return_tones=False):
         """The offline form: ``afx_k_gate_tone`` over whole clips, each with fresh state.  clips as for ``SpeechGate.gate``
         -> the list of kept-audio tensors; with ``return_mask`` also the list of per-frame bool keep masks, with
         ``return_tones`` also the list of per-frame bool tone masks.  Trailing samples short of a whole frame are dropped.
         One launch sequence and one read-back of the counts per distinct clip length."""
-        clips = list(clips.unbind(0)) if isinstance(clips, torch.Tensor) and clips.ndim == 2 else list(clips)
-        for c in clips:
-            if not isinstance(c, torch.Tensor) or c.ndim != 1 or c.dtype != torch.float32:
-                raise ValueError("gate: a list of 1-D fp32 tensors or a (B, n) tensor")
-            if not c.is_cuda:
-                raise AfxError("the gate runs on the GPU; there is no CPU fallback (gate_reference is the numpy restatement)")
-        out, masks, tones = [None] * len(clips), [None] * len(clips), [None] * len(clips)
-        want = return_mask or return_tones
-        groups = {}
-        for i, c in enumerate(clips):
-            groups.setdefault((c.device, c.numel() // self.frame), []).append(i)
-        for (dev, frames), rows in groups.items():
-            if frames == 0:
-                for i in rows:
-                    out[i] = torch.empty(0, dtype=torch.float32, device=dev)
-                    masks[i] = torch.zeros(0, dtype=torch.bool, device=dev)
-                    tones[i] = torch.zeros(0, dtype=torch.bool, device=dev)
-                continue
-            n = frames * self.frame
-            with torch.cuda.device(dev):
-                coef = torch.from_numpy(self.coef).to(dev)
-                for lo in range(0, len(rows), 65535):
-                    part = rows[lo:lo + 65535]
-                    A = len(part)
-                    x = torch.stack([clips[i][:n] for i in part]).contiguous()
-                    hdr = torch.stack([torch.arange(A, dtype=torch.int32), torch.zeros(A, dtype=torch.int32)], dim=1).to(dev)
-                    nf = torch.full((A,), float("inf"), dtype=torch.float32, device=dev)
-                    h = torch.zeros(A, dtype=torch.int32, device=dev)
-                    tone_state = torch.zeros(A, 3, dtype=torch.int32, device=dev)
-                    ring = torch.empty(A, n, dtype=torch.float32, device=dev)
-                    kept = torch.zeros(A, dtype=torch.int32, device=dev)
-                    mask = torch.zeros(A, frames, dtype=torch.uint8, device=dev) if want else None
-                    self._launch_tone(x, hdr, coef, nf, h, tone_state, ring, kept, mask=mask)
-                    for r, (i, k) in enumerate(zip(part, kept.tolist())):
-                        out[i] = ring[r, :k].clone()
-                        if want:
-                            masks[i], tones[i] = (mask[r] & 1).bool(), (mask[r] & 2).bool()
-        res = (out,) + ((masks,) if return_mask else ()) + ((tones,) if return_tones else ())
-        return res if len(res) > 1 else out
+        return self._offline(clips, return_mask or return_tones, (0,) + ((1,) if return_mask else ()) + ((2,) if return_tones else ()))
 
 
 def emitted(scores):
@@ -584,19 +557,15 @@ class GatedScorer(Layer):
         self._head = np.zeros(S, dtype=np.int64)  # ring position of each slot's oldest pending sample (host)
         self._fill = np.zeros(S, dtype=np.int64)  # pending kept samples per slot (host), always < hop between pushes
         self._seen = np.zeros(S, dtype=np.int64)  # samples pushed per slot since its reset (host)
-        self._la = isinstance(gate, LookaheadGate)
+        self._la = isinstance(gate, LookaheadGate)  # (which part a session carries; push notes last_span with look-ahead)
         self._tone = isinstance(gate, ToneGate)
         self.last_span = None
         self.last_tone_frames = None
-        if self._tone:
-            self._keys = GatedScorer._keys + ("gate_tone",)
-            self.coef = torch.from_numpy(gate.coef.copy()).to(dev)
-            self.tone_state = torch.zeros(S, 3, dtype=torch.int32, device=dev)
-        if self._la:
-            self._keys = GatedScorer._keys + ("gate_line", "gate_flags", "gate_sources")
-            self.flags = torch.zeros(S, dtype=torch.int32, device=dev)
-            self.line = torch.zeros(S, gate.pre * gate.frame, dtype=torch.float32, device=dev)
-            self.src = torch.full((S, self.ring_len // gate.frame), -1, dtype=torch.int32, device=dev)
+        self._keys = GatedScorer._keys + gate._session_keys
+        # the gate's own per-slot state, also as attributes: flags, line, src (look-ahead); coef, tone_state (tones)
+        self._extra = gate._new_extra(S, self.ring_len, dev)
+        for name, t in self._extra.items():
+            setattr(self, name, t)
 
     @property
     def samples_seen(self):
@@ -644,21 +613,10 @@ class GatedScorer(Layer):
             raise ValueError("a slot has seen 2^31 frames since its reset: reset it")
         with torch.cuda.device(dev):
             kept = torch.empty(A, dtype=torch.int32, device=dev)
+            hdr = self.gate._header(slot, (head + fill) % self.ring_len, self._seen[slot], dev)
+            self.last_tone_frames = self.gate._launch(chunk.to(dev).contiguous(), hdr, self.nf, self.h, self.ring, kept, self._extra)
             if la:
-                hdr = torch.zeros(A, 4, dtype=torch.int32, pin_memory=True)
-                hdr.numpy()[:, :3] = np.stack([slot, (head + fill) % self.ring_len, self._seen[slot] // frame], axis=1)
-                self.gate._launch_la(chunk.to(dev).contiguous(), hdr.to(dev, non_blocking=True), self.nf, self.h, self.flags,
-                                     self.line, self.ring, self.src, kept)
                 span = torch.full((A, 2), -1, dtype=torch.int64, device=dev)
-            elif self._tone:
-                hdr = upload_pairs(slot, (head + fill) % self.ring_len, dev)
-                ntone = torch.empty(A, dtype=torch.int32, device=dev)
-                self.gate._launch_tone(chunk.to(dev).contiguous(), hdr, self.coef, self.nf, self.h, self.tone_state, self.ring,
-                                       kept, ntone=ntone)
-                self.last_tone_frames = ntone
-            else:
-                hdr = upload_pairs(slot, (head + fill) % self.ring_len, dev)
-                self.gate._launch(chunk.to(dev).contiguous(), hdr, self.nf, self.h, self.ring, kept)
             host = torch.empty(A, dtype=torch.int32, pin_memory=True)
             host.copy_(kept, non_blocking=True)
             torch.cuda.current_stream(dev).synchronize()  # the one read-back: which slots completed a hop is in the audio
@@ -698,17 +656,13 @@ class GatedScorer(Layer):
         return out
 
     def _reset(self, idx):
-        """The noise floor (``nf = inf``), the hangover, the pending samples and the counters are dropped."""
+        """The noise floor (``nf = inf``), the hangover, the gate's own state, the pending samples and the counters are dropped."""
         if idx:
             with _on(self.device):
                 rows = rows_on(idx, self.device)
                 self.nf[rows] = float("inf")
                 self.h[rows] = 0
-                if self._la:
-                    self.flags[rows] = 0
-                    self.src[rows] = -1
-                if self._tone:
-                    self.tone_state[rows] = 0
+                self.gate._reset_extra(self._extra, rows)
             self._head[idx] = 0
             self._fill[idx] = 0
             self._seen[idx] = 0

@@ -1395,7 +1395,8 @@ __global__ __launch_bounds__(256) void jitter_release_kernel(JitterRatesArgs m) 
 
 enum JitterVerb { JIT_PLACE, JIT_CONCEAL, JIT_RELEASE, JIT_NOISE };
 
-static const char* jitter_msg(const char* who, const char* what) {
+// a refusal in the name of the entry point `who` (the jitter and the gate launch cores)
+static const char* launch_msg(const char* who, const char* what) {
   static thread_local char msg[160];
   snprintf(msg, sizeof msg, "%s: %s", who, what);
   return msg;
@@ -1409,42 +1410,42 @@ static const char* jitter_launch(const char* who, JitterVerb verb, JitterRatesAr
   const bool repeat = verb == JIT_CONCEAL && m.mode == 1;
   const char* fit = verb == JIT_PLACE || verb == JIT_NOISE ? "a row's samples must fit its slot's ring"
                   : verb == JIT_CONCEAL ? "a row's samples and its source must fit the ring" : "a row's outputs must fit its slot's ring";
-  if (verb == JIT_CONCEAL && m.mode != 0 && m.mode != 1) return jitter_msg(who, "mode 0 (zero) or 1 (repeat)");
+  if (verb == JIT_CONCEAL && m.mode != 0 && m.mode != 1) return launch_msg(who, "mode 0 (zero) or 1 (repeat)");
   if (verb == JIT_PLACE && m.hdr_ints == JIT_PLACE_HDR && (m.enc < 0 || m.enc > 3))
-    return jitter_msg(who, "encoding 0 (pcm_f32le), 1 (pcm_s16le), 2 (mulaw) or 3 (alaw)");
-  if (n_rates < 1 || n_rates > JIT_MAX_RATES) return jitter_msg(who, "1 to 16 rates");
-  if (!rates) return jitter_msg(who, "null rate table");
-  if (!most) return jitter_msg(who, "null output counts");
+    return launch_msg(who, "encoding 0 (pcm_f32le), 1 (pcm_s16le), 2 (mulaw) or 3 (alaw)");
+  if (n_rates < 1 || n_rates > JIT_MAX_RATES) return launch_msg(who, "1 to 16 rates");
+  if (!rates) return launch_msg(who, "null rate table");
+  if (!most) return launch_msg(who, "null output counts");
   if (!m.hdr || !m.jring || (verb == JIT_PLACE && (!m.stage || m.stage_bytes <= 0)) || (verb == JIT_RELEASE && !m.ring))
-    return jitter_msg(who, verb == JIT_PLACE ? "null staging buffer, header table or ring" : "null ring or header table");
-  if (verb == JIT_NOISE && !m.amp) return jitter_msg(who, "null amplitude table");
-  if (rows <= 0 || rows > 65535) return jitter_msg(who, "1 to 65535 rows");
+    return launch_msg(who, verb == JIT_PLACE ? "null staging buffer, header table or ring" : "null ring or header table");
+  if (verb == JIT_NOISE && !m.amp) return launch_msg(who, "null amplitude table");
+  if (rows <= 0 || rows > 65535) return launch_msg(who, "1 to 65535 rows");
   // (a launch without rate indices has one rate whose ring is the whole row: a bad J there is a row that does not fit)
   const char* ring_fit = m.rated ? "a rate's ring must fit the ring's rows (1 <= J <= Js)" : fit;
-  if (m.Js <= 0) return jitter_msg(who, ring_fit);
-  if (m.S <= 0 || (verb == JIT_RELEASE ? m.ring_len <= 0 : most[0] < 0)) return jitter_msg(who, fit);
+  if (m.Js <= 0) return launch_msg(who, ring_fit);
+  if (m.S <= 0 || (verb == JIT_RELEASE ? m.ring_len <= 0 : most[0] < 0)) return launch_msg(who, fit);
   bool fits = false;  // place / conceal: some rate can hold the largest row
   long long gx = 0;   // release: the largest grid and dynamic LDS over the rates present
   size_t lds = 0;
   for (int i = 0; i < n_rates; ++i) {
     const JitterRateDesc& d = rates[i];
-    if (d.L <= 0 || d.M <= 0 || d.T <= 0) return jitter_msg(who, "bad filter shape");
+    if (d.L <= 0 || d.M <= 0 || d.T <= 0) return launch_msg(who, "bad filter shape");
     const bool ident = d.taps == nullptr;
-    if (ident && (d.L != 1 || d.M != 1 || d.T != 1)) return jitter_msg(who, "bad filter shape (no taps is the identity, L = M = T = 1)");
-    if (d.J <= 0 || d.J > m.Js) return jitter_msg(who, ring_fit);
-    if (d.T - 1 > d.J) return jitter_msg(who, "the filter history must fit the rate's ring");
-    if (repeat && (!d.fade || d.P <= 0 || d.F < 0)) return jitter_msg(who, "repeat needs a fade table, a period and a fade length");
+    if (ident && (d.L != 1 || d.M != 1 || d.T != 1)) return launch_msg(who, "bad filter shape (no taps is the identity, L = M = T = 1)");
+    if (d.J <= 0 || d.J > m.Js) return launch_msg(who, ring_fit);
+    if (d.T - 1 > d.J) return launch_msg(who, "the filter history must fit the rate's ring");
+    if (repeat && (!d.fade || d.P <= 0 || d.F < 0)) return launch_msg(who, "repeat needs a fade table, a period and a fade length");
     JitterRate& r = m.r[i];
     r.f = PolyFilter{d.taps, d.L, d.M, d.T, 0, 0};
     r.fade = d.fade; r.J = d.J; r.P = repeat ? d.P : 0; r.F = repeat ? d.F : 0;
     r.max_out = verb == JIT_RELEASE && most[i] > 0 ? most[i] : 0;
     PolyGrid g;
-    if (!poly_grid(r.f, ident, r.max_out, g)) return jitter_msg(who, "input / output ratio above 12");
+    if (!poly_grid(r.f, ident, r.max_out, g)) return launch_msg(who, "input / output ratio above 12");
     r.lds_taps = g.lds_taps;
     if (verb != JIT_RELEASE) {
       fits = fits || (long long)most[0] + r.P <= d.J;
     } else {
-      if (most[i] < 0 || most[i] > m.ring_len) return jitter_msg(who, fit);
+      if (most[i] < 0 || most[i] > m.ring_len) return launch_msg(who, fit);
       if (r.max_out > 0) {
         gx = g.gx > gx ? g.gx : gx;
         lds = g.lds > lds ? g.lds : lds;
@@ -1453,7 +1454,7 @@ static const char* jitter_launch(const char* who, JitterVerb verb, JitterRatesAr
   }
   m.nr = n_rates;
   if (verb != JIT_RELEASE) {
-    if (!fits) return jitter_msg(who, fit);
+    if (!fits) return launch_msg(who, fit);
     gx = min((most[0] + 255) / 256, 64);
   }
   if (gx == 0) return nullptr;  // no samples to place or conceal, no outputs to release
@@ -1557,26 +1558,38 @@ const char* launch_jitter_release_rates(const float* jring, int S, int Js, const
 // ---------------------------------------------------------------------------------
 // Speech gate (afx/vad.py; the function is stated in include/afx.h afx_k_gate): a per-slot energy gate over frames of
 // `frame` 16 kHz samples with a tracked noise floor and a hangover; the kept frames of a row are compacted, bit for bit, into
-// the slot's pending ring (the layout ingest_pop_kernel reads).  One workgroup per row, three phases:
-//   1. the four waves compute the frame energies into LDS: lane l sums sq[l], sq[l + 64], ... in ascending order, then a
-//      shuffle-down tree folds the 64 partials (w = 32 .. 1).  Every operation is one correctly rounded fp32 multiply or
-//      add (contraction is off in gate_frame_energy: p + v * v must not become an fma), so numpy float32 restates it;
-//   2. thread 0 runs the state machine over the frames in stream order (a serial recurrence of a few ops per frame),
-//      writes each frame's offset among the kept samples (or -1: dropped) to LDS and stores nf, h and kept;
-//   3. the four waves copy the kept frames, 64 consecutive samples per step.
-// A launch takes at most GATE_MAX_FRAMES frames of a row (what its LDS tables hold); launch_gate splits a longer row into
+// the slot's pending ring (the layout ingest_pop_kernel reads).  The gate has three forms -- plain (gate_kernel), with onset
+// look-ahead (gate_la_kernel) and with call-tone rejection (gate_tone_kernel) -- and each kernel is a composition of the
+// phases below, every shared phase written once.  One workgroup per row:
+//   guard     gate_row: slot and wpos from the header; a row that fails a condition writes nothing but kept = 0;
+//   energies  gate_energies: the four waves compute the frame energies into LDS: lane l sums sq[l], sq[l + 64], ... in
+//             ascending order, then a shuffle-down tree folds the 64 partials (w = 32 .. 1).  Every operation is one
+//             correctly rounded fp32 multiply or add (contraction is off in gate_frame_energy: p + v * v must not become
+//             an fma), so numpy float32 restates it;
+//   decision  thread 0 runs the state machine over the frames in stream order (a serial recurrence of a few ops per
+//             frame): gate_speech (speech, and the floor update), the form's own lines, gate_keep (hangover and keep),
+//             then each frame's offset among the samples the launch keeps (or -1: dropped) to LDS;
+//   epilogue  gate_store: nf, h and kept (accumulated over the launches of a row) to device memory;
+//   copy      gate_copy_kept: the four waves copy the kept frames, 64 consecutive samples per step (plain and tone; the
+//             look-ahead kernel copies out of its delay line and has a copy of its own).
+// The helpers hold no barrier: every __syncthreads() stands in a kernel body, between the phases it separates.
+// A launch takes at most GATE_MAX_FRAMES frames of a row (what its LDS tables hold); gate_launch splits a longer row into
 // successive launches that find nf, h and the samples kept so far in device memory.
 // ---------------------------------------------------------------------------------
 constexpr int GATE_MAX_FRAMES = 512;  // frames of a row per launch: 2 x 512 x 4 bytes of LDS (include/afx.h states it)
 
-struct GateArgs {
+// What the three forms share; GateLaArgs and GateToneArgs hold one and add their own fields.  100 bytes without tail
+// padding (hence the attribute), so that the look-ahead kernel's arguments fill the 128 bytes they always did: a kernel
+// reads its arguments from memory with scalar loads that the compiler places where it likes, some of them late, and with
+// one more line of arguments such a load can miss on its own (profiles/gate_refactor_ab.txt has both layouts).
+struct __attribute__((packed, aligned(4))) GateArgs {
   const float* x;    // (A, n) samples, row i = the next n samples of slot hdr[i][0]
-  const int* hdr;    // (A, 2): slot, wpos
+  const int* hdr;    // (A, 2 or 4): slot, wpos, then the form's own columns
   float* nf;         // (S,) noise floor per slot
   int* h;            // (S,) hangover frames left per slot
   float* ring;       // (S, ring_len)
-  int* kept;         // (A,) samples kept of each row
-  unsigned char* mask;  // (A, n / frame) keep flag of every frame, or nullptr
+  int* kept;         // (A,) samples kept (look-ahead: emitted) of each row
+  unsigned char* mask;  // (A, n / frame) per frame, what the form states, or nullptr
   int n, frame, f0, nframes;  // this launch: frames [f0, f0 + nframes) of the n / frame of a row
   int S, ring_len, hang;
   float e_floor, ratio, rise, nf_min;
@@ -1602,76 +1615,141 @@ __device__ __forceinline__ float gate_frame_energy(const float* __restrict__ x, 
   return p;
 }
 
+// guard: slot and wpos of the row from its header of hdr_ints columns, and whether the row is gated: the conditions of
+// every form and `own`, the calling form's.  A row that fails writes nothing but kept = 0, once (at the first launch of a
+// split row).
+__device__ __forceinline__ bool gate_row(const GateArgs& g, int row, int tid, int hdr_ints, bool own, int& slot, int& wpos) {
+  slot = g.hdr[hdr_ints * row];
+  wpos = g.hdr[hdr_ints * row + 1];
+  if (own && slot >= 0 && slot < g.S && wpos >= 0 && wpos < g.ring_len && g.n <= g.ring_len) return true;
+  if (tid == 0 && g.f0 == 0) g.kept[row] = 0;
+  return false;
+}
+
+// the launch's first sample of the row
+__device__ __forceinline__ const float* gate_row_x(const GateArgs& g, int row) {
+  return g.x + (long long)row * g.n + (long long)g.f0 * g.frame;
+}
+
+// energies: the frames of the launch (x: the first) to s_e, a frame per wave and step
+__device__ __forceinline__ void gate_energies(const GateArgs& g, const float* __restrict__ x, int wave, int lane, float* s_e) {
+  for (int f = wave; f < g.nframes; f += 4) {
+    const float e = gate_frame_energy(x + (long long)f * g.frame, g.frame, lane);
+    if (lane == 0) s_e[f] = e;
+  }
+}
+
+// decision, first half: is the frame of energy e speech against the floor nf, and the floor's update
+__device__ __forceinline__ bool gate_speech(const GateArgs& g, float e, float& nf) {
+#pragma clang fp contract(off)
+  const bool fin = e < INFINITY;  // (false for a NaN too)
+  const bool speech = fin && e > fmaxf(g.e_floor, g.ratio * nf);
+  if (fin) nf = fmaxf(g.nf_min, fminf(e, nf * g.rise));
+  return speech;
+}
+
+// decision, second half: the hangover h and whether the frame is kept.  (Two halves: between them the tone gate
+// takes speech and the hangover away from a tone frame.)
+__device__ __forceinline__ bool gate_keep(const GateArgs& g, bool speech, int& h) {
+#pragma clang fp contract(off)
+  if (speech) h = g.hang;
+  const bool keep = speech || h > 0;
+  if (!speech && h > 0) --h;
+  return keep;
+}
+
+// epilogue (thread 0): the slot's state, the row's count over the launches so far, and the count before this launch for the copy
+__device__ __forceinline__ void gate_store(const GateArgs& g, int slot, int row, float nf, int h, int off, int* s_base) {
+  const int base = g.f0 ? g.kept[row] : 0;
+  g.nf[slot] = nf;
+  g.h[slot] = h;
+  g.kept[row] = base + off;
+  *s_base = base;
+}
+
+// one frame, 64 consecutive samples per step, where neither side wraps
+__device__ __forceinline__ void gate_copy_frame(float* __restrict__ to, const float* __restrict__ from, int frame, int lane) {
+  for (int k = lane; k < frame; k += 64) to[k] = from[k];
+}
+
+// copy: the frames with an offset in s_off from x into the slot's ring behind wpos + base, a frame per wave and step
+__device__ __forceinline__ void gate_copy_kept(const GateArgs& g, const float* __restrict__ x, int slot, int wpos, int base,
+                                               const int* s_off, int wave, int lane) {
+  float* out = g.ring + (long long)slot * g.ring_len;
+  const long long w0 = (long long)wpos + base;  // base + off + k < n <= ring_len: one wrap
+  for (int f = wave; f < g.nframes; f += 4) {
+    const int off = s_off[f];
+    if (off < 0) continue;
+    const float* src = x + (long long)f * g.frame;
+    for (int k = lane; k < g.frame; k += 64) {
+      const long long w = w0 + off + k;
+      out[w < g.ring_len ? w : w - g.ring_len] = src[k];
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void gate_kernel(GateArgs a) {
   __shared__ float s_e[GATE_MAX_FRAMES];
   __shared__ int s_off[GATE_MAX_FRAMES];  // offset of the frame among this launch's kept samples, -1: dropped
   __shared__ int s_base;                  // samples of the row kept by the launches before this one
   const int row = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int slot = a.hdr[2 * row], wpos = a.hdr[2 * row + 1];
-  if (!(slot >= 0 && slot < a.S && wpos >= 0 && wpos < a.ring_len && a.n <= a.ring_len)) {
-    if (tid == 0 && a.f0 == 0) a.kept[row] = 0;
-    return;
-  }
-  const float* x = a.x + (long long)row * a.n + (long long)a.f0 * a.frame;
-  for (int f = wave; f < a.nframes; f += 4) {
-    const float e = gate_frame_energy(x + (long long)f * a.frame, a.frame, lane);
-    if (lane == 0) s_e[f] = e;
-  }
+  int slot, wpos;
+  if (!gate_row(a, row, tid, 2, true, slot, wpos)) return;
+  const float* x = gate_row_x(a, row);
+  gate_energies(a, x, wave, lane, s_e);
   __syncthreads();
   if (tid == 0) {
     float nf = a.nf[slot];
     int h = a.h[slot], off = 0;
     for (int f = 0; f < a.nframes; ++f) {
-      const float e = s_e[f];
-      const bool fin = e < INFINITY;  // (false for a NaN too)
-      const bool speech = fin && e > fmaxf(a.e_floor, a.ratio * nf);
-      if (fin) nf = fmaxf(a.nf_min, fminf(e, nf * a.rise));
-      if (speech) h = a.hang;
-      const bool keep = speech || h > 0;
-      if (!speech && h > 0) --h;
+      const bool speech = gate_speech(a, s_e[f], nf);
+      const bool keep = gate_keep(a, speech, h);
       s_off[f] = keep ? off : -1;
       if (keep) off += a.frame;
       if (a.mask) a.mask[(long long)row * (a.n / a.frame) + a.f0 + f] = keep;
     }
-    const int base = a.f0 ? a.kept[row] : 0;
-    a.nf[slot] = nf;
-    a.h[slot] = h;
-    a.kept[row] = base + off;
-    s_base = base;
+    gate_store(a, slot, row, nf, h, off, &s_base);
   }
   __syncthreads();
-  float* out = a.ring + (long long)slot * a.ring_len;
-  const long long w0 = (long long)wpos + s_base;  // base + off + k < n <= ring_len: one wrap
-  for (int f = wave; f < a.nframes; f += 4) {
-    const int off = s_off[f];
-    if (off < 0) continue;
-    const float* src = x + (long long)f * a.frame;
-    for (int k = lane; k < a.frame; k += 64) {
-      const long long w = w0 + off + k;
-      out[w < a.ring_len ? w : w - a.ring_len] = src[k];
-    }
+  gate_copy_kept(a, x, slot, wpos, s_base, s_off, wave, lane);
+}
+
+// The launch of a form for the entry point `who`: the checks the forms share (a refusal carries who's name, and nothing is
+// launched), nf_min, and one launch per GATE_MAX_FRAMES frames of a row.  g comes with the buffers, shapes and constants
+// set; launch(g) launches the form's kernel over g with f0 and nframes set.  The form's own checks are its launcher's.
+template <class Launch>
+static const char* gate_launch(const char* who, GateArgs g, int A, Launch launch) {
+  if (!g.x || !g.hdr || !g.nf || !g.h || !g.ring || !g.kept) return launch_msg(who, "null argument");
+  if (A <= 0 || A > 65535) return launch_msg(who, "1 to 65535 rows");
+  if (g.frame <= 0 || g.n <= 0 || g.n % g.frame) return launch_msg(who, "a row is a positive whole number of frames");
+  if (g.S <= 0 || g.ring_len <= 0) return launch_msg(who, "no slots or no ring");
+  if (!(g.e_floor > 0.f && g.e_floor < INFINITY && g.ratio > 1.f && g.ratio < INFINITY && g.rise >= 1.f && g.rise < INFINITY) ||
+      g.hang < 0)
+    return launch_msg(who, "floor > 0, ratio > 1, rise >= 1 (all finite) and hang >= 0");
+  g.nf_min = g.e_floor / g.ratio;  // (one IEEE fp32 division, on the host)
+  const int frames = g.n / g.frame;
+  for (g.f0 = 0; g.f0 < frames; g.f0 += GATE_MAX_FRAMES) {
+    g.nframes = min(GATE_MAX_FRAMES, frames - g.f0);
+    launch(g);
   }
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+// the arguments every form's entry point takes, as the kernels take them
+static GateArgs gate_args(const float* x, int n, const int* hdr, int frame, float e_floor, float ratio, float rise, int hang,
+                          float* nf, int* h, float* ring, int S, int ring_len, int* kept, unsigned char* mask) {
+  GateArgs g{};
+  g.x = x; g.hdr = hdr; g.nf = nf; g.h = h; g.ring = ring; g.kept = kept; g.mask = mask;
+  g.n = n; g.frame = frame; g.S = S; g.ring_len = ring_len; g.hang = hang;
+  g.e_floor = e_floor; g.ratio = ratio; g.rise = rise;
+  return g;
 }
 
 const char* launch_gate(const float* x, int A, int n, const int* hdr, int frame, float e_floor, float ratio, float rise, int hang,
                         float* nf, int* h, float* ring, int S, int ring_len, int* kept, unsigned char* mask, hipStream_t s) {
-  if (!x || !hdr || !nf || !h || !ring || !kept) return "gate: null argument";
-  if (A <= 0 || A > 65535) return "gate: 1 to 65535 rows";
-  if (frame <= 0 || n <= 0 || n % frame) return "gate: a row is a positive whole number of frames";
-  if (S <= 0 || ring_len <= 0) return "gate: no slots or no ring";
-  if (!(e_floor > 0.f && e_floor < INFINITY && ratio > 1.f && ratio < INFINITY && rise >= 1.f && rise < INFINITY) || hang < 0)
-    return "gate: floor > 0, ratio > 1, rise >= 1 (all finite) and hang >= 0";
-  GateArgs a{};
-  a.x = x; a.hdr = hdr; a.nf = nf; a.h = h; a.ring = ring; a.kept = kept; a.mask = mask;
-  a.n = n; a.frame = frame; a.S = S; a.ring_len = ring_len; a.hang = hang;
-  a.e_floor = e_floor; a.ratio = ratio; a.rise = rise; a.nf_min = e_floor / ratio;  // (one IEEE fp32 division, on the host)
-  const int frames = n / frame;
-  for (a.f0 = 0; a.f0 < frames; a.f0 += GATE_MAX_FRAMES) {
-    a.nframes = min(GATE_MAX_FRAMES, frames - a.f0);
-    hipLaunchKernelGGL(gate_kernel, dim3(A), dim3(256), 0, s, a);
-  }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+  return gate_launch("gate", gate_args(x, n, hdr, frame, e_floor, ratio, rise, hang, nf, h, ring, S, ring_len, kept, mask), A,
+                     [&](const GateArgs& g) { hipLaunchKernelGGL(gate_kernel, dim3(A), dim3(256), 0, s, g); });
 }
 
 // ---------------------------------------------------------------------------------
@@ -1679,159 +1757,120 @@ const char* launch_gate(const float* x, int A, int n, const int* hdr, int frame,
 // decision per frame, behind a delay line of `pre` frames per slot.  Frame G (counted from the slot's reset) enters the line
 // with flag = keep; a speech frame flags every frame then in the line; frame G - pre leaves while frame G is processed and
 // is emitted into the pending ring iff its flag is set, with its index G - pre recorded in src.  One workgroup per row, the
-// phases of gate_kernel: energies to LDS; thread 0 runs the recurrence and writes, per frame of the launch, the offset of
-// the frame that LEAVES (-1: none, or dropped); the waves copy.  Two hazards:
+// shared phases (guard, energies, decision halves, epilogue) and three departures: the guard also wants wpos on the frame
+// grid and F with room for the row's frames; between the decision's halves and after them thread 0 keeps the line's flags
+// and writes, per frame of the launch, the offset of the frame that LEAVES (-1: none, or dropped); and the copy is this
+// kernel's own, because a leaving frame comes out of the line or out of x and its source index goes to src.  Two hazards:
 //   block reuse: frame G - pre leaves from the line block (G mod pre) that frame G enters.  A launch therefore copies the
 //      leaving frames that an earlier launch stored (the first min(pre, nframes) steps) out of the line, then a barrier,
 //      and only then stores its own last min(pre, nframes) frames into the line.  A frame that enters and leaves within one
 //      launch is copied from x directly and never touches the line;
-//   rows longer than GATE_MAX_FRAMES: launch_gate_la splits them into successive launches, each complete in itself (it
+//   rows longer than GATE_MAX_FRAMES: gate_launch splits them into successive launches, each complete in itself (it
 //      leaves its last frames in the line, flags in flags, nf, h and the samples emitted so far in kept), so the next finds
 //      everything in device memory and the result does not depend on the split.
 // wpos and ring_len are whole frames, so no frame straddles the ring's wrap.
 // ---------------------------------------------------------------------------------
 struct GateLaArgs {
-  const float* x;    // (A, n) samples, row i = the next n samples of slot hdr[i][0]
-  const int* hdr;    // (A, 4): slot, wpos, F (frames the slot was pushed before this row), 0
-  float* nf;         // (S,) noise floor per slot
-  int* h;            // (S,) hangover frames left per slot
+  GateArgs g;        // hdr (A, 4): slot, wpos, F (frames the slot was pushed before this row), 0; kept: samples emitted;
+                     // mask entry j: keep' of source frame F - pre + j (0 where negative)
+  int pre;           // (behind g's 100 bytes, so that the pointers follow without padding)
   int* flags;        // (S,) bit (g mod pre): the flag of delayed frame g
   float* line;       // (S, pre * frame) delayed frame g at block g mod pre
-  float* ring;       // (S, ring_len)
   int* src;          // (S, ring_len / frame) source index of the frame at ring position w, at entry w / frame
-  int* kept;         // (A,) samples emitted of each row
-  unsigned char* mask;  // (A, n / frame) entry j: keep' of source frame F - pre + j (0 where negative), or nullptr
-  int n, frame, f0, nframes, pre;  // this launch: frames [f0, f0 + nframes) of the n / frame of a row
-  int S, ring_len, hang;
-  float e_floor, ratio, rise, nf_min;
 };
+static_assert(sizeof(GateLaArgs) == 128, "gate_la_kernel's arguments: 128 bytes (see GateArgs)");
 
 __global__ __launch_bounds__(256) void gate_la_kernel(GateLaArgs a) {
   __shared__ float s_e[GATE_MAX_FRAMES];
   __shared__ int s_off[GATE_MAX_FRAMES];  // offset, among this launch's emitted samples, of the frame leaving at step j; -1: none
   __shared__ int s_base;                  // samples of the row emitted by the launches before this one
+  const GateArgs& g = a.g;
   const int row = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int slot = a.hdr[4 * row], wpos = a.hdr[4 * row + 1], F = a.hdr[4 * row + 2];
-  const int frames = a.n / a.frame;
-  if (!(slot >= 0 && slot < a.S && wpos >= 0 && wpos < a.ring_len && wpos % a.frame == 0 && a.n <= a.ring_len && F >= 0 &&
-        F <= 0x7fffffff - frames)) {
-    if (tid == 0 && a.f0 == 0) a.kept[row] = 0;
-    return;
-  }
-  const int G0 = F + a.f0, pre = a.pre;  // the index of this launch's first frame
-  const float* x = a.x + (long long)row * a.n + (long long)a.f0 * a.frame;
-  for (int f = wave; f < a.nframes; f += 4) {
-    const float e = gate_frame_energy(x + (long long)f * a.frame, a.frame, lane);
-    if (lane == 0) s_e[f] = e;
-  }
+  const int F = g.hdr[4 * row + 2], frames = g.n / g.frame;
+  int slot, wpos;
+  if (!gate_row(g, row, tid, 4, g.hdr[4 * row + 1] % g.frame == 0 && F >= 0 && F <= 0x7fffffff - frames, slot, wpos)) return;
+  const int G0 = F + g.f0, pre = a.pre;  // the index of this launch's first frame
+  const float* x = gate_row_x(g, row);
+  gate_energies(g, x, wave, lane, s_e);
   __syncthreads();
   if (tid == 0) {
-    float nf = a.nf[slot];
-    int h = a.h[slot], off = 0, b = G0 % pre;  // b = G mod pre: the block frame G enters and frame G - pre leaves
+    float nf = g.nf[slot];
+    int h = g.h[slot], off = 0, b = G0 % pre;  // b = G mod pre: the block frame G enters and frame G - pre leaves
     unsigned fl = (unsigned)a.flags[slot];
     const unsigned all = (1u << pre) - 1u;
-    for (int f = 0; f < a.nframes; ++f) {
+    for (int f = 0; f < g.nframes; ++f) {
       const int G = G0 + f;
-      const float e = s_e[f];
-      const bool fin = e < INFINITY;  // (false for a NaN too)
-      const bool speech = fin && e > fmaxf(a.e_floor, a.ratio * nf);
-      if (fin) nf = fmaxf(a.nf_min, fminf(e, nf * a.rise));
-      if (speech) h = a.hang;
-      const bool keep = speech || h > 0;
-      if (!speech && h > 0) --h;
+      const bool speech = gate_speech(g, s_e[f], nf);
       if (speech) fl = G >= pre ? all : (1u << G) - 1u;  // every frame now in the line (blocks not yet filled stay 0)
       const bool out = G >= pre && ((fl >> b) & 1u);
+      const bool keep = gate_keep(g, speech, h);
+      fl = (fl & ~(1u << b)) | ((unsigned)keep << b);  // frame G enters with flag = keep
       s_off[f] = out ? off : -1;
-      if (out) off += a.frame;
-      fl = (fl & ~(1u << b)) | ((unsigned)keep << b);
-      if (a.mask) a.mask[(long long)row * frames + a.f0 + f] = out;
+      if (out) off += g.frame;
+      if (g.mask) g.mask[(long long)row * frames + g.f0 + f] = out;
       b = b + 1 == pre ? 0 : b + 1;
     }
-    const int base = a.f0 ? a.kept[row] : 0;
-    a.nf[slot] = nf;
-    a.h[slot] = h;
     a.flags[slot] = (int)fl;
-    a.kept[row] = base + off;
-    s_base = base;
+    gate_store(g, slot, row, nf, h, off, &s_base);
   }
   __syncthreads();
-  float* out = a.ring + (long long)slot * a.ring_len;
-  int* so = a.src + (long long)slot * (a.ring_len / a.frame);
-  float* ln = a.line + (long long)slot * pre * a.frame;
+  float* out = g.ring + (long long)slot * g.ring_len;
+  int* so = a.src + (long long)slot * (g.ring_len / g.frame);
+  float* ln = a.line + (long long)slot * pre * g.frame;
   const int w0 = wpos + s_base;  // base + off + frame <= n <= ring_len: one wrap, at a frame edge
-  const int old = min(pre, a.nframes);  // steps whose leaving frame an earlier launch stored in the line
-  for (int f = wave; f < a.nframes; f += 4) {
+  const int old = min(pre, g.nframes);  // steps whose leaving frame an earlier launch stored in the line
+  for (int f = wave; f < g.nframes; f += 4) {
     const int off = s_off[f];
     if (off < 0) continue;
-    const float* from = f < old ? ln + (long long)((G0 + f) % pre) * a.frame : x + (long long)(f - pre) * a.frame;
-    const int w = w0 + off < a.ring_len ? w0 + off : w0 + off - a.ring_len;
-    for (int k = lane; k < a.frame; k += 64) out[w + k] = from[k];
-    if (lane == 0) so[w / a.frame] = G0 + f - pre;
+    const float* from = f < old ? ln + (long long)((G0 + f) % pre) * g.frame : x + (long long)(f - pre) * g.frame;
+    const int w = w0 + off < g.ring_len ? w0 + off : w0 + off - g.ring_len;
+    gate_copy_frame(out + w, from, g.frame, lane);
+    if (lane == 0) so[w / g.frame] = G0 + f - pre;
   }
   __syncthreads();  // every copy out of the line is done before a frame of this launch is stored into it
-  for (int f = a.nframes - old + wave; f < a.nframes; f += 4) {
-    const float* from = x + (long long)f * a.frame;
-    float* to = ln + (long long)((G0 + f) % pre) * a.frame;
-    for (int k = lane; k < a.frame; k += 64) to[k] = from[k];
-  }
+  for (int f = g.nframes - old + wave; f < g.nframes; f += 4)
+    gate_copy_frame(ln + (long long)((G0 + f) % pre) * g.frame, x + (long long)f * g.frame, g.frame, lane);
 }
 
 const char* launch_gate_la(const float* x, int A, int n, const int* hdr, int frame, float e_floor, float ratio, float rise,
                            int hang, int pre, float* nf, int* h, int* flags, float* line, float* ring, int* src, int S,
                            int ring_len, int* kept, unsigned char* mask, hipStream_t s) {
-  if (!x || !hdr || !nf || !h || !flags || !line || !ring || !src || !kept) return "gate_la: null argument";
-  if (A <= 0 || A > 65535) return "gate_la: 1 to 65535 rows";
-  if (frame <= 0 || n <= 0 || n % frame) return "gate_la: a row is a positive whole number of frames";
-  if (S <= 0 || ring_len <= 0 || ring_len > (1 << 30) || ring_len % frame)
+  if (!flags || !line || !src) return "gate_la: null argument";
+  if (frame > 0 && (S <= 0 || ring_len <= 0 || ring_len > (1 << 30) || ring_len % frame))
     return "gate_la: no slots, or a ring that is not whole frames (at most 2^30 samples)";
   if (pre < 1 || pre > 31) return "gate_la: 1 to 31 frames of pre-roll";
-  if (!(e_floor > 0.f && e_floor < INFINITY && ratio > 1.f && ratio < INFINITY && rise >= 1.f && rise < INFINITY) || hang < 0)
-    return "gate_la: floor > 0, ratio > 1, rise >= 1 (all finite) and hang >= 0";
-  GateLaArgs a{};
-  a.x = x; a.hdr = hdr; a.nf = nf; a.h = h; a.flags = flags; a.line = line; a.ring = ring; a.src = src; a.kept = kept;
-  a.mask = mask; a.n = n; a.frame = frame; a.pre = pre; a.S = S; a.ring_len = ring_len; a.hang = hang;
-  a.e_floor = e_floor; a.ratio = ratio; a.rise = rise; a.nf_min = e_floor / ratio;  // (one IEEE fp32 division, on the host)
-  const int frames = n / frame;
-  for (a.f0 = 0; a.f0 < frames; a.f0 += GATE_MAX_FRAMES) {
-    a.nframes = min(GATE_MAX_FRAMES, frames - a.f0);
+  GateLaArgs a{gate_args(x, n, hdr, frame, e_floor, ratio, rise, hang, nf, h, ring, S, ring_len, kept, mask), pre, flags, line, src};
+  return gate_launch("gate_la", a.g, A, [&](const GateArgs& g) {
+    a.g = g;
     hipLaunchKernelGGL(gate_la_kernel, dim3(A), dim3(256), 0, s, a);
-  }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+  });
 }
 
 // ---------------------------------------------------------------------------------
 // Tone gate (afx/vad.py ToneGate; the function is stated in include/afx.h afx_k_gate_tone): the plain gate's decision plus
 // a Goertzel bank of K <= 16 signalling frequencies per frame.  A frame whose two largest bank powers hold at least
 // thr * e is `tonal`; `confirm` tonal frames in a row make a tone, which lasts `hold` frames past the run; a tone frame is
-// not speech, is not kept and ends the hangover.  One workgroup per row, gate_kernel's three phases and one more:
-//   1. frame energies to LDS (gate_frame_energy, shared with gate_kernel);
-//   2. the (frame, k) pairs of the launch are spread over the 256 threads, k fastest (a frame's K lanes read one sample
-//      address): each pair runs the second-order recurrence over its frame's samples sequentially, three dependent fp32
-//      operations per sample with contraction off, and leaves its power in LDS; then one thread per frame folds the K
-//      powers into T = the sum of the two largest positive ones;
-//   3. thread 0 runs the state machine (nf, h, then r, q, tones) and writes offsets, mask and tsum;
-//   4. the copy of gate_kernel.
+// not speech, is not kept and ends the hangover.  One workgroup per row, the plain gate's phases (guard, energies, decision
+// halves, epilogue, gate_copy_kept) and two departures:
+//   powers    beside the energies, the (frame, k) pairs of the launch are spread over the 256 threads, k fastest (a
+//             frame's K lanes read one sample address): each pair runs the second-order recurrence over its frame's
+//             samples sequentially, three dependent fp32 operations per sample with contraction off, and leaves its power
+//             in LDS; then one thread per frame folds the K powers into T = the sum of the two largest positive ones;
+//   decision  between gate_speech and gate_keep thread 0 runs r, q and tones, and a tone frame loses speech and the
+//             hangover there; it also writes tsum and counts ntone (which a skipped row zeroes beside kept).
 // LDS at GATE_MAX_FRAMES: 3 tables of 512 x 4 bytes and the powers, 512 x 16 x 4 = 32 KB; 38 KB of a workgroup's 64 KB.
 // The samples are read eight at a time so that the loads run ahead of the dependent chain.
 // ---------------------------------------------------------------------------------
 constexpr int GATE_MAX_TONES = 16;  // frequencies of a bank (include/afx.h states it)
 
 struct GateToneArgs {
-  const float* x;     // (A, n) samples, row i = the next n samples of slot hdr[i][0]
-  const int* hdr;     // (A, 2): slot, wpos
+  GateArgs g;         // hdr (A, 2): slot, wpos; mask: bit 0 keep, bit 1 tone, bit 2 tonal
   const float* coef;  // (K,) 2 cos(2 pi f_k / 16000)
-  float* nf;          // (S,) noise floor per slot
-  int* h;             // (S,) hangover frames left per slot
   int* tone_state;    // (S, 3): r (tonal frames in a row), q (hold frames left), tones (tone frames since the reset)
-  float* ring;        // (S, ring_len)
-  int* kept;          // (A,) samples kept of each row
   int* ntone;         // (A,) tone frames of each row, or nullptr
-  unsigned char* mask;  // (A, n / frame) bit 0 keep, bit 1 tone, bit 2 tonal, or nullptr
   float* tsum;        // (A, n / frame) T of every frame, or nullptr
-  int n, frame, f0, nframes;  // this launch: frames [f0, f0 + nframes) of the n / frame of a row
-  int S, ring_len, hang, K, confirm, hold;
-  float e_floor, ratio, rise, nf_min, thr;
+  int K, confirm, hold;
+  float thr;
 };
 
 // the Goertzel power of one frame at the coefficient c: every operation one correctly rounded fp32 multiply, add or subtract
@@ -1872,27 +1911,22 @@ __global__ __launch_bounds__(256) void gate_tone_kernel(GateToneArgs a) {
   __shared__ int s_off[GATE_MAX_FRAMES];  // offset of the frame among this launch's kept samples, -1: dropped
   __shared__ float s_p[GATE_MAX_FRAMES * GATE_MAX_TONES];  // power of pair f * K + k
   __shared__ int s_base;                  // samples of the row kept by the launches before this one
+  const GateArgs& g = a.g;
   const int row = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int slot = a.hdr[2 * row], wpos = a.hdr[2 * row + 1];
-  if (!(slot >= 0 && slot < a.S && wpos >= 0 && wpos < a.ring_len && a.n <= a.ring_len)) {
-    if (tid == 0 && a.f0 == 0) {
-      a.kept[row] = 0;
-      if (a.ntone) a.ntone[row] = 0;
-    }
+  int slot, wpos;
+  if (!gate_row(g, row, tid, 2, true, slot, wpos)) {
+    if (tid == 0 && g.f0 == 0 && a.ntone) a.ntone[row] = 0;
     return;
   }
-  const float* x = a.x + (long long)row * a.n + (long long)a.f0 * a.frame;
-  for (int f = wave; f < a.nframes; f += 4) {
-    const float e = gate_frame_energy(x + (long long)f * a.frame, a.frame, lane);
-    if (lane == 0) s_e[f] = e;
-  }
+  const float* x = gate_row_x(g, row);
+  gate_energies(g, x, wave, lane, s_e);
   const int K = a.K;
-  for (int p = tid; p < a.nframes * K; p += 256) {  // (nframes * K <= 512 * 16)
+  for (int p = tid; p < g.nframes * K; p += 256) {  // (nframes * K <= 512 * 16)
     const int f = p / K, k = p - f * K;
-    s_p[p] = gate_tone_power(x + (long long)f * a.frame, a.frame, a.coef[k]);
+    s_p[p] = gate_tone_power(x + (long long)f * g.frame, g.frame, a.coef[k]);
   }
   __syncthreads();
-  for (int f = tid; f < a.nframes; f += 256) {
+  for (int f = tid; f < g.nframes; f += 256) {
     float p1 = 0.f, p2 = 0.f;  // the two largest positive powers (a NaN or non-positive power counts as +0.0)
     for (int k = 0; k < K; ++k) {
       const float v = s_p[f * K + k];
@@ -1908,17 +1942,15 @@ __global__ __launch_bounds__(256) void gate_tone_kernel(GateToneArgs a) {
   __syncthreads();
   if (tid == 0) {
 #pragma clang fp contract(off)
-    const long long frames = a.n / a.frame;
-    float nf = a.nf[slot];
-    int h = a.h[slot], off = 0, nt = 0;
+    const long long frames = g.n / g.frame;
+    float nf = g.nf[slot];
+    int h = g.h[slot], off = 0, nt = 0;
     int r = a.tone_state[3 * slot], q = a.tone_state[3 * slot + 1], tones = a.tone_state[3 * slot + 2];
-    for (int f = 0; f < a.nframes; ++f) {
+    for (int f = 0; f < g.nframes; ++f) {
       const float e = s_e[f], T = s_t[f];
-      const bool fin = e < INFINITY;  // (false for a NaN too)
-      bool speech = fin && e > fmaxf(a.e_floor, a.ratio * nf);
-      if (fin) nf = fmaxf(a.nf_min, fminf(e, nf * a.rise));
+      bool speech = gate_speech(g, e, nf);
       const float bound = a.thr * e;
-      const bool tonal = fin && e > a.e_floor && T >= bound;
+      const bool tonal = e < INFINITY && e > g.e_floor && T >= bound;  // (false for a NaN e or T)
       r = tonal ? (r < 0x7fffffff ? r + 1 : r) : 0;
       if (r >= a.confirm) q = a.hold;
       const bool tone = r >= a.confirm || q > 0;
@@ -1929,64 +1961,36 @@ __global__ __launch_bounds__(256) void gate_tone_kernel(GateToneArgs a) {
         speech = false;
         h = 0;
       }
-      if (speech) h = a.hang;
-      const bool keep = speech || h > 0;
-      if (!speech && h > 0) --h;
+      const bool keep = gate_keep(g, speech, h);
       s_off[f] = keep ? off : -1;
-      if (keep) off += a.frame;
-      if (a.mask) a.mask[row * frames + a.f0 + f] = (unsigned char)((keep ? 1 : 0) | (tone ? 2 : 0) | (tonal ? 4 : 0));
-      if (a.tsum) a.tsum[row * frames + a.f0 + f] = T;
+      if (keep) off += g.frame;
+      if (g.mask) g.mask[row * frames + g.f0 + f] = (unsigned char)((keep ? 1 : 0) | (tone ? 2 : 0) | (tonal ? 4 : 0));
+      if (a.tsum) a.tsum[row * frames + g.f0 + f] = T;
     }
-    const int base = a.f0 ? a.kept[row] : 0;
-    a.nf[slot] = nf;
-    a.h[slot] = h;
     a.tone_state[3 * slot] = r;
     a.tone_state[3 * slot + 1] = q;
     a.tone_state[3 * slot + 2] = tones;
-    a.kept[row] = base + off;
-    if (a.ntone) a.ntone[row] = (a.f0 ? a.ntone[row] : 0) + nt;
-    s_base = base;
+    if (a.ntone) a.ntone[row] = (g.f0 ? a.ntone[row] : 0) + nt;
+    gate_store(g, slot, row, nf, h, off, &s_base);
   }
   __syncthreads();
-  float* out = a.ring + (long long)slot * a.ring_len;
-  const long long w0 = (long long)wpos + s_base;  // base + off + k < n <= ring_len: one wrap
-  for (int f = wave; f < a.nframes; f += 4) {
-    const int off = s_off[f];
-    if (off < 0) continue;
-    const float* src = x + (long long)f * a.frame;
-    for (int k = lane; k < a.frame; k += 64) {
-      const long long w = w0 + off + k;
-      out[w < a.ring_len ? w : w - a.ring_len] = src[k];
-    }
-  }
+  gate_copy_kept(g, x, slot, wpos, s_base, s_off, wave, lane);
 }
 
 const char* launch_gate_tone(const float* x, int A, int n, const int* hdr, int frame, float e_floor, float ratio, float rise,
                              int hang, const float* coef, int K, float thr, int confirm, int hold, float* nf, int* h,
                              int* tone_state, float* ring, int S, int ring_len, int* kept, int* ntone, unsigned char* mask,
                              float* tsum, hipStream_t s) {
-  if (!x || !hdr || !coef || !nf || !h || !tone_state || !ring || !kept) return "gate_tone: null argument";
-  if (A <= 0 || A > 65535) return "gate_tone: 1 to 65535 rows";
-  if (frame <= 0 || n <= 0 || n % frame) return "gate_tone: a row is a positive whole number of frames";
-  if (S <= 0 || ring_len <= 0) return "gate_tone: no slots or no ring";
-  if (!(e_floor > 0.f && e_floor < INFINITY && ratio > 1.f && ratio < INFINITY && rise >= 1.f && rise < INFINITY) || hang < 0)
-    return "gate_tone: floor > 0, ratio > 1, rise >= 1 (all finite) and hang >= 0";
+  if (!coef || !tone_state) return "gate_tone: null argument";
   if (K < 1 || K > GATE_MAX_TONES) return "gate_tone: a bank of 1 to 16 frequencies";
   if (!(thr > 0.f && thr < INFINITY) || confirm < 1 || hold < 0)
     return "gate_tone: thr > 0 (finite), confirm >= 1 and hold >= 0";
-  GateToneArgs a{};
-  a.x = x; a.hdr = hdr; a.coef = coef; a.nf = nf; a.h = h; a.tone_state = tone_state; a.ring = ring; a.kept = kept;
-  a.ntone = ntone; a.mask = mask; a.tsum = tsum;
-  a.n = n; a.frame = frame; a.S = S; a.ring_len = ring_len; a.hang = hang; a.K = K; a.confirm = confirm; a.hold = hold;
-  a.e_floor = e_floor; a.ratio = ratio; a.rise = rise; a.nf_min = e_floor / ratio;  // (one IEEE fp32 division, on the host)
-  a.thr = thr;
-  const int frames = n / frame;
-  for (a.f0 = 0; a.f0 < frames; a.f0 += GATE_MAX_FRAMES) {
-    a.nframes = min(GATE_MAX_FRAMES, frames - a.f0);
+  GateToneArgs a{gate_args(x, n, hdr, frame, e_floor, ratio, rise, hang, nf, h, ring, S, ring_len, kept, mask),
+                 coef, tone_state, ntone, tsum, K, confirm, hold, thr};
+  return gate_launch("gate_tone", a.g, A, [&](const GateArgs& g) {
+    a.g = g;
     hipLaunchKernelGGL(gate_tone_kernel, dim3(A), dim3(256), 0, s, a);
-  }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+  });
 }
 
 // ---------------------------------------------------------------------------------

@@ -363,6 +363,49 @@ def test_bad_rows_are_skipped_whole_and_bad_arguments_launch_nothing():
     dev.check(after, "good arguments")
 
 
+def test_the_three_forms_share_one_decision_on_the_device():
+    """afx_k_gate, afx_k_gate_la (pre 5) and afx_k_gate_tone (the default bank) over the same audio, 40 launches of 10
+    frames for 3 slots: where no frame is tonal the three kernels leave the same ``nf`` bits and ``h`` after every launch,
+    and the tone form keeps, copies and masks exactly what the plain form does.  The audio is that of
+    tests/test_cpu_vad_tone.py::test_without_a_tonal_frame_it_is_the_plain_gate, and the noise bursts once more with an
+    onset frame made +inf and another made NaN (each then not speech: the plain decision changes at exactly those two)."""
+    import test_cpu_vad_tone as host
+    from test_gpu_vad import _Raw as Plain
+    from test_gpu_vad_lookahead import _Raw as Lookahead
+    from afx.vad import LookaheadGate, SpeechGate, ToneGate
+    S, n, total, L = 3, 1600, 64000, 3200
+    noise = (0.002 * np.random.default_rng(9).standard_normal(total)).astype(f32)
+    bursts = host._noise_bursts(total, 3) + noise
+    voice = host._voice(total, 4) * np.repeat((np.arange(total // 8000) % 2).astype(f32), 8000) + noise
+    broken = bursts.copy()
+    broken[19 * 160 + 17], broken[161 * 160 + 5] = np.inf, np.nan  # frames 19 and 161: the first two onsets of the bursts
+    streams = [bursts, voice, broken]
+    gate = ToneGate()
+    keeps = []
+    for x in streams:  # on the reference, before the GPU is touched: no frame is tonal, and keep takes both values
+        _, tonal, is_tone, keep = gate.decide_reference(x)
+        assert not tonal.any() and not is_tone.any() and keep.any() and not keep.all()
+        keeps.append(keep)
+    assert np.flatnonzero(keeps[2] != keeps[0]).tolist() == [19, 161]
+    plain, la, tone = Plain(SpeechGate(), S, L, seed=4), Lookahead(LookaheadGate(pre=5), S, L, seed=4), _Device(gate, S, L, 4)
+    assert tone.ring.cpu().numpy().tobytes() == plain.m_ring.tobytes()  # (the same bytes to begin with)
+    slots, w, w_la = list(range(S)), [0] * S, [0] * S
+    for t in range(total // n):
+        rows = np.stack([x[t * n:(t + 1) * n] for x in streams])
+        rc_p, kept_p, mask_p = plain.launch(rows, slots, wpos=w, mask=True)
+        rc_l, kept_l, _ = la.launch(rows, slots, wpos=w_la, F=[t * 10] * S)
+        rc_t, kept_t, _, mask_t, _ = tone.launch(rows, slots, w)
+        assert rc_p == rc_l == rc_t == 0, t
+        nf = plain.nf.cpu().numpy().tobytes()
+        assert la.nf.cpu().numpy().tobytes() == nf and tone.nf.cpu().numpy().tobytes() == nf, t
+        assert plain.h.tolist() == la.h.tolist() == tone.h.tolist(), t
+        assert kept_t.tolist() == kept_p and tone.ring.cpu().numpy().tobytes() == plain.ring.cpu().numpy().tobytes(), t
+        assert np.array_equal(mask_t.cpu().numpy() & 1, mask_p) and mask_p.tolist() == [k[t * 10:(t + 1) * 10].tolist() for k in keeps], t
+        assert tone.ts.tolist() == [[0, 0, 0]] * S, t
+        w = [(a + k) % L for a, k in zip(w, kept_p)]
+        w_la = [(a + k) % L for a, k in zip(w_la, kept_l)]
+
+
 # ---- 2. streamed equals offline ----------------------------------------------------------------------------------------------------
 def _tap(S, hop):
     from afx.streaming import SlidingWindowScorer
