@@ -119,12 +119,13 @@ class KvModel:
         return self.feat[s][-WINDOW:]
 
 
-def kv_walk(sd, dt, tap, model, plan, feats6, prev_rings, heads=16, buckets=False):
+def kv_walk(sd, dt, tap, model, plan, feats6, prev_rings, heads=16, buckets=False, check_kw=None):
     """Every launch of ONE step against its reference.  sd: the trunk's state dict (oracle key names); tap(name) -> the
     tapped buffer (flat, float64); model / plan: the ``KvModel`` and its ``begin`` plan of this step; feats6 the step's
     input (blocks, n, 512); prev_rings: per layer the previous step's tapped ring (S, 256, 3 D) (zeros before the first).
     buckets: the back-end is the AASIST bucket loop, which in the per-stream forms gathers the entries by window length
     (ascending, stable) into one uniform batch per length, tapped as kv.bucket{i}, instead of one left-aligned batch.
+    check_kw: further keywords of ``insitu.check`` (unique_rows / rounding_only, for streams that repeat rows).
     -> (results, fails, rings): results = [(class, tap name, check() dict, operand-typed output?)], fails = the exact
     statements that do not hold, rings = this step's tapped rings.  Advances the model (``end``)."""
     res, fails = [], []
@@ -135,7 +136,7 @@ def kv_walk(sd, dt, tap, model, plan, feats6, prev_rings, heads=16, buckets=Fals
     streams = [b["stream"] for b in blocks]
 
     def put(cls, name, got, rb, op_dt):
-        res.append((cls, name, I.check(got, rb[0], rb[1], dt if op_dt else None, rows), op_dt))
+        res.append((cls, name, I.check(got, rb[0], rb[1], dt if op_dt else None, rows, **(check_kw or {})), op_dt))
 
     def same(name, a, b, what):
         if a.shape != b.shape or not torch.equal(a, b):

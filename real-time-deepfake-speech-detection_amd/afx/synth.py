@@ -235,3 +235,85 @@ def waveforms(batch, length=64000, batch_idx=0, scale=0.1):
     g = torch.Generator(device="cpu")
     g.manual_seed(1234 + batch_idx)
     return torch.randn(batch, length, generator=g, dtype=torch.float32) * scale
+
+
+# ---- call audio: what the streaming fronts hand the model ----------------------------------------------------------------
+CALL_KINDS = ("silence", "burst_silence", "dc", "clipped", "idle", "click", "tone", "mulaw", "comfort", "repeat", "noise")
+CALL_RATE = 16000
+
+
+def _phase(n, hz):
+    """sin(2 pi hz n / 16000) with the phase reduced in integers: a periodic signal repeats bit for bit."""
+    return torch.sin(2.0 * math.pi * ((n * hz) % CALL_RATE).double() / CALL_RATE)
+
+
+def _carrier(n):
+    """A voiced-speech-like carrier: eight harmonics of 140 Hz at 1 / k, under a 3 Hz envelope, peak 0.3 (float64)."""
+    c = sum(_phase(n, 140 * k) / k for k in range(1, 9))
+    env = 0.5 * (1.0 - torch.cos(2.0 * math.pi * 3.0 * n.double() / CALL_RATE))
+    return 0.3 * env * c / 1.8
+
+
+def _mulaw_round_trip(x):
+    """G.711 mu-law encode / decode of samples in [-1, 1) (float64 -> float64): the 16-bit linear value of the code, / 32768."""
+    s = torch.clamp(torch.round(x * 32768.0), -32635, 32635).long()
+    mag = s.abs() + 132
+    exp = torch.floor(torch.log2(mag.double())).long() - 7
+    mant = (mag >> (exp + 3)) & 15
+    v = (((mant << 3) + 132) << exp) - 132
+    return torch.where(s < 0, -v, v).double() / 32768.0
+
+
+def call_waveforms(kinds=CALL_KINDS, length=16000, seed=0):
+    """(len(kinds), length) fp32 at 16 kHz, one row per kind: the inputs the telephony fronts manufacture, which white noise
+    (``waveforms``) never resembles.  Deterministic: a kind's row depends on (kind, length, seed) only.
+
+      silence        exact zeros ("zero" concealment)
+      burst_silence  the carrier (140 Hz harmonics under a 3 Hz envelope, peak ~0.3) plus 0.02 randn over the first 3 / 8
+                     of the clip, then exact zeros (a speech-gate burst cut at a frame border)
+      dc             constant 0.25
+      clipped        a 300 Hz square wave at +-1.0
+      idle           random +-2^-15 (one PCM16 step: an idle line)
+      click          exact zeros, one sample of 1.0 in the middle
+      tone           0.5 sin(2 pi 440 t)
+      mulaw          the carrier over the whole clip through a G.711 mu-law encode / decode round trip
+      comfort        uniform noise of RMS 10^-3 (-60 dBov: ``afx.jitter.ComfortNoise`` at level 60)
+      repeat         200 ms of the carrier, its last 10 ms repeated under a 30 ms linear fade, then zeros ("repeat" concealment)
+      noise          ``waveforms(1, length, batch_idx=seed)``: one non-degenerate clip in every batch
+    """
+    n = torch.arange(length)
+    out = torch.zeros(len(kinds), length, dtype=torch.float32)
+    for i, kind in enumerate(kinds):
+        g = _gen(f"call_waveforms.{kind}.{seed}")
+        if kind == "silence":
+            continue
+        elif kind == "burst_silence":
+            m = 3 * length // 8
+            out[i, :m] = (_carrier(n[:m]) + 0.02 * torch.randn(m, generator=g, dtype=torch.float64)).float()
+        elif kind == "dc":
+            out[i] = 0.25
+        elif kind == "clipped":
+            out[i] = torch.where((n * 600 // CALL_RATE) % 2 == 0, 1.0, -1.0)
+        elif kind == "idle":
+            out[i] = (2.0 * torch.randint(0, 2, (length,), generator=g) - 1.0) * 2.0 ** -15
+        elif kind == "click":
+            out[i, length // 2] = 1.0
+        elif kind == "tone":
+            out[i] = (0.5 * _phase(n, 440)).float()
+        elif kind == "mulaw":
+            out[i] = _mulaw_round_trip(_carrier(n + 2000)).float()  # (from 125 ms on: the envelope is open at sample 0)
+        elif kind == "comfort":
+            a = math.sqrt(3.0) * 10.0 ** (-60 / 20.0)
+            out[i] = ((2.0 * torch.rand(length, generator=g, dtype=torch.float64) - 1.0) * a).float()
+        elif kind == "repeat":
+            a, P, Fd = CALL_RATE // 5, CALL_RATE // 100, 3 * CALL_RATE // 100
+            e = torch.zeros(max(length, a + Fd), dtype=torch.float64)
+            e[:a] = _carrier(torch.arange(2000, 2000 + a))
+            dd = torch.arange(Fd)
+            e[a:a + Fd] = e[a - P + dd % P] * (1.0 - dd.double() / Fd)
+            out[i] = e[:length].float()
+        elif kind == "noise":
+            out[i] = waveforms(1, length, batch_idx=seed)[0]
+        else:
+            raise ValueError(f"call_waveforms: kind {kind!r} is none of {CALL_KINDS}")
+    return out

@@ -52,7 +52,7 @@ def tap_names(form):
 class Walker:
     """A KVState and its KvModel side by side: every step runs with taps on and is walked launch by launch."""
 
-    def __init__(self, dt, n_streams=S, arch="conformer"):
+    def __init__(self, dt, n_streams=S, arch="conformer", call=None):
         from oracle import insitu, insitu_kv
         self.I, self.K, self.dt = insitu, insitu_kv, dt
         self.eng, self.sd = _engine(dt, arch)
@@ -61,6 +61,9 @@ class Walker:
         self.model = insitu_kv.KvModel(n_streams)
         self.prev = [torch.zeros(n_streams, insitu_kv.SLOTS, 3 * 1024, dtype=torch.float64) for _ in range(LAYERS)]
         self.fails, self.steps = [], 0
+        # call (tests/test_gpu_insitu_call.py: dict(suffix, summary)): the classes go under the suffix into that module's table
+        self.summary, self.suffix = (SUMMARY, "") if call is None else (call["summary"], call["suffix"])
+        self.check_kw = None if call is None else dict(unique_rows=True, rounding_only=True)
         self.eng.enable_taps()
 
     def reset(self, slots):
@@ -71,18 +74,19 @@ class Walker:
         plan = self.model.begin(f.shape[1], n_frames, slots)
         out = self.kv.step(f.cuda(), n_frames, slots).cpu()
         tap = lambda name: self.eng.tap(name).cpu().double()
-        res, fails, self.prev = self.K.kv_walk(self.sd, self.dt, tap, self.model, plan, f, self.prev, buckets=self.buckets)
+        res, fails, self.prev = self.K.kv_walk(self.sd, self.dt, tap, self.model, plan, f, self.prev, buckets=self.buckets,
+                                                   check_kw=self.check_kw)
         where = f"step {self.steps} (form {plan['form']}, n {[b['n'] for b in plan['blocks']]}, streams {[b['stream'] for b in plan['blocks']]})"
         for cls, name, r, op_dt in res:
-            key = (cls, self.dt)
-            r0, b0 = SUMMARY.get(key, (0.0, None))
+            key = (cls + self.suffix, self.dt)
+            r0, b0 = self.summary.get(key, (0.0, None))
             # The rounding-bias statistic (oracle/insitu.py) needs thousands of independent samples: BIAS_MAX is 0.05 ulp and
             # one element's rounding error has sigma 0.29 ulp, so a launch is judged from 16384 elements on (sigma 0.002).
             # The ring attention is reported, not asserted: its output error is P's rounding (several output ulps, shared
             # by the 64 columns of a head), so <= 48 query rows give <= 768 independent samples and a standard error above
             # BIAS_MAX; the output store is the dense attention's, whose statistic tests/test_gpu_insitu.py asserts.
             b = r["bias"] if op_dt and self.dt in self.I.HALF and r["n"] >= 16384 and cls != "kv_ring" else None
-            SUMMARY[key] = (max(r0, r["ratio"]), b if b0 is None or (b is not None and abs(b) > abs(b0)) else b0)
+            self.summary[key] = (max(r0, r["ratio"]), b if b0 is None or (b is not None and abs(b) > abs(b0)) else b0)
             if not r["ratio"] <= 1.0:
                 self.fails.append(f"{where} {name} [{self.dt}]: |got - ref| = {r['ratio']:.2f} x bound at row {r['row']}, col {r['col']} "
                                   f"(got {r['got']:.6e}, ref {r['ref']:.6e}, bound {r['bound']:.2e})")
