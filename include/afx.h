@@ -555,6 +555,46 @@ int afx_k_gate_la(const float* x, int A, int n, const int* hdr, int frame, float
 int afx_k_gate_tone(const float* x, int A, int n, const int* hdr, int frame, float e_floor, float ratio, float rise, int hang,
                     const float* coef, int K, float thr, int confirm, int hold, float* nf, int* h, int* tone_state, float* ring,
                     int S, int ring_len, int* kept, int* ntone, unsigned char* mask, float* tsum, void* stream);
+/* Talk spurts (afx/turns.py): a slot's stream cut into turns, each scored as one utterance.  A turn is a maximal run of
+ * kept frames (bit 0 of a gate's mask, hangover frames included), cut when it reaches max_frames.  Two buffers per slot:
+ * bufs (S, 2, max_frames * frame) fp32.  State per slot, all 0 for a new stream: state (S, 3) int32 = open (0 / 1: the buffer
+ * that collects the open turn), n (its frames, 0 <= n < max_frames), g (the source index of its first frame); totals (S, 4)
+ * int32 = scored, short, cut, kept, each saturating at 2^31 - 1.  A launch names rows i = 0..A-1 of distinct slots: hdr
+ * (device, A x 3 int32) = slot, wpos, g0; row i holds the F frames g0 .. g0 + F - 1 of the slot's stream, mask (A, F) bytes
+ * says which are kept, and the kept ones stand in order, frame after frame, at staging[slot][(wpos + k) mod ring_len]
+ * (staging (S, ring_len) fp32: what a gate launch with ring = staging and that wpos wrote).  Per row, r = 0 and
+ * done = (0, 0, 0, 0); for j = 0 .. F-1 with G = g0 + j:
+ *     if (mask[j] & 1) {
+ *         if (n == 0) g = G;
+ *         bufs[slot][open][n * frame .. (n + 1) * frame) = staging frame r   (bit for bit);   r += 1; n += 1; kept += 1
+ *         if (n == max_frames) { done = (open, n, g, G + 1); scored += 1; cut += 1; open ^= 1; n = 0; }
+ *     } else if (n > 0) {
+ *         if (n >= min_frames) { done = (open, n, g, G); scored += 1; open ^= 1; }
+ *         else                 short += 1;
+ *         n = 0;
+ *     }
+ * done (A, 4) int32 = buffer, frames, first source frame, one past the last, of the turn the row completed; (0, 0, 0, 0) when
+ * it completed none.  With F <= min_frames a row completes at most one scored turn, so after the row the buffer that is not
+ * `open` holds the completed turn or nothing of use: afx_k_turn_collect reads it before the slot's next row.  A turn shorter
+ * than min_frames is dropped and counted; the remainder of a cut turn is a new turn.  The contents of a buffer beyond the
+ * open turn's n frames (and beyond a completed turn's) are not defined: a dropped turn's frames need not be copied.
+ * afx_k_turn: one workgroup of 256 threads per row; thread 0 runs the recurrence and writes a per-frame copy plan to LDS,
+ * the four waves then copy a frame per wave and step, 16 bytes per lane where frame, ring_len and wpos are multiples of 4
+ * and staging and bufs are 16-byte aligned, one sample per lane otherwise.  A row with slot outside [0, S), wpos outside
+ * [0, ring_len), g0 < 0 or g0 + F >= 2^31 (or whose slot's state is no turn state: open not 0 / 1, n outside [0, max_frames))
+ * is skipped whole: done[i] = (-1, -1, -1, -1) and nothing else is written.  Rows of slots not named are untouched.  Refused
+ * with nothing launched: a NULL pointer, A outside 1..65535, F outside 1..512, frame <= 0, min_frames < F, min_frames >
+ * max_frames, S <= 0, F * frame > ring_len, max_frames * frame > 2^30. */
+int afx_k_turn(const float* staging, int S, int ring_len, const unsigned char* mask, const int* hdr, int A, int F, int frame,
+               int min_frames, int max_frames, float* bufs, int* state, int* totals, int* done, void* stream);
+/* The clip of a turn of L = frames * frame samples is the turn repeated to the window, clip[k] = turn[k mod L] for
+ * k < max_frames * frame (afx_k_tile_crop's function with start 0; a cut turn is its own clip).
+ * afx_k_turn_collect: rows (device, R x 3 int32) = slot, buffer, frames; out[r][k] = bufs[slot][buffer][k mod L], out
+ * (R, max_frames * frame) fp32, copied bit for bit.  Grid over (column tiles, row); four samples per lane where frame is a
+ * multiple of 4 and bufs and out are 16-byte aligned, one otherwise.  A row with slot outside [0, S), buffer outside 0..1 or
+ * frames outside 1..max_frames is skipped whole (its output row is left as it was).  Refused with nothing launched: a NULL
+ * pointer, S <= 0, R outside 1..65535, frame <= 0, max_frames <= 0, max_frames * frame > 2^30. */
+int afx_k_turn_collect(const float* bufs, int S, int max_frames, int frame, const int* rows, int R, float* out, void* stream);
 /* Cascade (afx/cascade.py): a cheap screen scores every slot at every hop; the windows of the slots whose score looks
  * suspicious are gathered for a second model, under a per-push budget and a per-slot cooldown.  Every index comes from a
  * host-built header (device int32), nothing is allocated, all three run on `stream`.  State: hist (S, window) fp32, the

@@ -503,6 +503,48 @@ def emitted(scores):
     return ~torch.isnan(scores.scores if hasattr(scores, "scores") else scores)
 
 
+# ---- the checks of a gate's part of a session, shared by the layers of kind "gate" (GatedScorer, afx.turns.TurnScorer) ------
+def session_counts(t, keys, n):
+    """The state tensors ``keys`` of ``t``, each (n,) int64 -> their host arrays."""
+    counts = []
+    for k in keys:
+        c = t[k].cpu().reshape(-1)
+        if c.dtype != torch.int64 or c.numel() != n:
+            raise ValueError(f"import_slots: {k} is (n,) int64")
+        counts.append(c.numpy())
+    return counts
+
+
+def check_floor_shape(nf, n):
+    if tuple(nf.shape) != (n,) or nf.dtype != torch.float32:
+        raise ValueError(f"import_slots: gate_nf {tuple(nf.shape)} {nf.dtype} is not {(n,)} float32")
+
+
+def check_hang_and_floor(gate, hang, nf):
+    if ((hang < 0) | (hang > gate.hang)).any():
+        raise ValueError(f"import_slots: a session's hangover is outside 0..{gate.hang} frames")
+    nf_host = nf.cpu()
+    if bool(torch.isnan(nf_host).any()) or bool((nf_host < float(gate.nf_min)).any()):
+        raise ValueError(f"import_slots: a session's noise floor is NaN or below the gate's minimum {float(gate.nf_min)!r}")
+
+
+def check_tone(gate, t, n, seen):
+    """The checks of ``gate_tone`` (a ``ToneGate``'s r, q, tones per session) -> (the tensor,)."""
+    tone = t["gate_tone"]
+    if tone.dtype != torch.int64 or tuple(tone.shape) != (n, 3):
+        raise ValueError(f"import_slots: gate_tone is {(n, 3)} int64")
+    r, q, tones = tone.cpu().numpy().T
+    if (r < 0).any() or (r > N_MAX).any():
+        raise ValueError("import_slots: a session's run of tonal frames is negative (or 2^31 or more)")
+    if ((q < 0) | (q > gate.hold)).any():
+        raise ValueError(f"import_slots: a session's tone hold is outside 0..{gate.hold} frames")
+    if ((r >= gate.confirm) & (q != gate.hold)).any():
+        raise ValueError("import_slots: a session inside a confirmed tone does not hold the full hold")
+    if ((tones < 0) | (tones > seen // gate.frame)).any():
+        raise ValueError("import_slots: a session counts more tone frames than it has seen frames (or fewer than 0)")
+    return (tone,)
+
+
 class GatedScorer(Layer):
     """``scorer`` (whatever stands below the gate in the stack order of ``afx._layer``; around a cascade, screen and
     verifier then see the same gated stream) behind a ``SpeechGate`` (default: the default gate); see the module docstring
@@ -713,48 +755,25 @@ class GatedScorer(Layer):
 
     def _check(self, state, n):
         hop, t = self.hop, state.tensors
-        counts = []
-        for k in ("gate_fill", "gate_hang", "gate_inner_seen"):
-            c = t[k].cpu().reshape(-1)
-            if c.dtype != torch.int64 or c.numel() != n:
-                raise ValueError(f"import_slots: {k} is (n,) int64")
-            counts.append(c.numpy())
-        fill, hang, inner_seen = counts
+        fill, hang, inner_seen = session_counts(t, ("gate_fill", "gate_hang", "gate_inner_seen"), n)
         seen = state.seen.numpy()
         pend, nf = t["gate_pending"], t["gate_nf"]
         check_pending("gate_pending", pend, fill, n, hop)
         if pend.shape[1] != hop:
             raise ValueError(f"import_slots: gate_pending {tuple(pend.shape)} is not {(n, hop)}")
-        if tuple(nf.shape) != (n,) or nf.dtype != torch.float32:
-            raise ValueError(f"import_slots: gate_nf {tuple(nf.shape)} {nf.dtype} is not {(n,)} float32")
+        check_floor_shape(nf, n)
         if ((fill >= hop) | (fill % self.gate.frame != 0)).any():
             raise ValueError(f"import_slots: a session's pending samples are not whole {self.gate.frame}-sample frames short of a hop")
         if ((inner_seen < 0) | (seen < 0) | (inner_seen % hop != 0) | (seen % hop != 0)).any():
             raise ValueError("import_slots: a session's sample count is not a whole number of hops")
         if (inner_seen + fill > seen).any():
             raise ValueError("import_slots: a session kept more samples than it was pushed")
-        if ((hang < 0) | (hang > self.gate.hang)).any():
-            raise ValueError(f"import_slots: a session's hangover is outside 0..{self.gate.hang} frames")
-        nf_host = nf.cpu()
-        if bool(torch.isnan(nf_host).any()) or bool((nf_host < float(self.gate.nf_min)).any()):
-            raise ValueError(f"import_slots: a session's noise floor is NaN or below the gate's minimum {float(self.gate.nf_min)!r}")
+        check_hang_and_floor(self.gate, hang, nf)
         return (pend, nf, hang, fill, seen) + (self._check_line(t, n, fill, seen) if self._la else ()) + (
             self._check_tone(t, n, seen) if self._tone else ())
 
     def _check_tone(self, t, n, seen):
-        tone = t["gate_tone"]
-        if tone.dtype != torch.int64 or tuple(tone.shape) != (n, 3):
-            raise ValueError(f"import_slots: gate_tone is {(n, 3)} int64")
-        r, q, tones = tone.cpu().numpy().T
-        if (r < 0).any() or (r > N_MAX).any():
-            raise ValueError("import_slots: a session's run of tonal frames is negative (or 2^31 or more)")
-        if ((q < 0) | (q > self.gate.hold)).any():
-            raise ValueError(f"import_slots: a session's tone hold is outside 0..{self.gate.hold} frames")
-        if ((r >= self.gate.confirm) & (q != self.gate.hold)).any():
-            raise ValueError("import_slots: a session inside a confirmed tone does not hold the full hold")
-        if ((tones < 0) | (tones > seen // self.gate.frame)).any():
-            raise ValueError("import_slots: a session counts more tone frames than it has seen frames (or fewer than 0)")
-        return (tone,)
+        return check_tone(self.gate, t, n, seen)
 
     def _check_line(self, t, n, fill, seen):
         pre, frame, per = self.gate.pre, self.gate.frame, self.hop // self.gate.frame

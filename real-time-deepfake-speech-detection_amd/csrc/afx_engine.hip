@@ -2898,6 +2898,16 @@ extern "C" int afx_k_gate_tone(const float* x, int A, int n, const int* hdr, int
   KRET(launch_gate_tone(x, A, n, hdr, frame, e_floor, ratio, rise, hang, coef, K, thr, confirm, hold, nf, h, tone_state, ring,
                         S, ring_len, kept, ntone, mask, tsum, (hipStream_t)stream));
 }
+extern "C" int afx_k_turn(const float* staging, int S, int ring_len, const unsigned char* mask, const int* hdr, int A, int F,
+                          int frame, int min_frames, int max_frames, float* bufs, int* state, int* totals, int* done,
+                          void* stream) {
+  KRET(launch_turn(staging, S, ring_len, mask, hdr, A, F, frame, min_frames, max_frames, bufs, state, totals, done,
+                   (hipStream_t)stream));
+}
+extern "C" int afx_k_turn_collect(const float* bufs, int S, int max_frames, int frame, const int* rows, int R, float* out,
+                                  void* stream) {
+  KRET(launch_turn_collect(bufs, S, max_frames, frame, rows, R, out, (hipStream_t)stream));
+}
 extern "C" int afx_k_cascade_store(const float* x, int A, int hop, const int* hdr, float* hist, int S, int window,
                                    void* stream) {
   KRET(launch_cascade_store(x, A, hop, hdr, hist, S, window, (hipStream_t)stream));

@@ -1994,6 +1994,165 @@ const char* launch_gate_tone(const float* x, int A, int n, const int* hdr, int f
 }
 
 // ---------------------------------------------------------------------------------
+// Talk spurts (afx/turns.py; the function is stated in include/afx.h afx_k_turn / afx_k_turn_collect): behind a gate launch
+// that compacted the kept frames of each row into a staging ring and wrote the per-frame mask, turn_kernel cuts each slot's
+// stream into turns -- maximal runs of kept frames, cut at max_frames -- and appends the row's kept frames to the slot's open
+// turn, in one of two buffers per slot; turn_collect_kernel then tiles the turns the push completed into padded clips.  Both
+// are copies: no floating-point arithmetic.  turn_kernel, one workgroup per row, in the gate kernels' phases:
+//   guard     slot, wpos and g0 from the header and the slot's state; a row that fails writes done = (-1, -1, -1, -1) only;
+//   plan      thread 0 walks the mask in stream order (a serial recurrence of a few integer ops per frame) and writes per
+//             frame (staging frame r or -1, destination frame among the slot's 2 x max_frames) to LDS, then state, totals
+//             and done.  The frames of a turn the row itself drops as short are taken out of the plan again: the next turn
+//             starts at the same place of the same buffer, and two waves must not write one destination;
+//   copy      after the barrier the four waves copy a frame per wave and step: 16 bytes per lane where frame, the ring
+//             length and wpos are multiples of 4 and both bases are 16-byte aligned (a 4-vector then never straddles the
+//             ring's wrap), one sample per lane otherwise.
+// ---------------------------------------------------------------------------------
+constexpr int TURN_MAX_FRAMES = 512;  // frames of a row: the plan, 512 x 8 bytes of LDS (include/afx.h states it)
+
+struct TurnArgs {
+  const float* staging;       // (S, ring_len): the row's kept frames in order from wpos on
+  const unsigned char* mask;  // (A, F): bit 0 = kept
+  const int* hdr;             // (A, 3): slot, wpos, g0
+  float* bufs;                // (S, 2, max_frames * frame)
+  int* state;                 // (S, 3): open, n, g
+  int* totals;                // (S, 4): scored, short, cut, kept, saturating
+  int* done;                  // (A, 4): buffer, frames, first source frame, one past the last
+  int S, ring_len, F, frame, min_frames, max_frames, vec;
+};
+
+__device__ __forceinline__ int turn_count(int v) { return v < 0x7fffffff ? v + 1 : v; }
+
+__global__ __launch_bounds__(256) void turn_kernel(TurnArgs a) {
+  __shared__ int2 s_plan[TURN_MAX_FRAMES];  // x: the staging frame, -1: nothing to copy; y: open * max_frames + n
+  const int row = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int slot = a.hdr[3 * row], wpos = a.hdr[3 * row + 1], g0 = a.hdr[3 * row + 2];
+  bool ok = slot >= 0 && slot < a.S && wpos >= 0 && wpos < a.ring_len && g0 >= 0 && g0 <= 0x7fffffff - a.F;
+  int open = 0, n = 0;
+  if (ok) {  // (a state that is not a turn state would leave the buffers: such a row is skipped too)
+    open = a.state[3 * slot];
+    n = a.state[3 * slot + 1];
+    ok = (open == 0 || open == 1) && n >= 0 && n < a.max_frames;
+  }
+  if (!ok) {
+    if (tid < 4) a.done[4 * row + tid] = -1;
+    return;
+  }
+  if (tid == 0) {
+    int g = a.state[3 * slot + 2];
+    int* tot = a.totals + 4 * slot;
+    int scored = tot[0], shrt = tot[1], cut = tot[2], kept = tot[3];
+    int d0 = 0, d1 = 0, d2 = 0, d3 = 0, r = 0, j0 = 0;  // j0: the open turn's first frame in this row
+    const unsigned char* m = a.mask + (long long)row * a.F;
+    for (int j = 0; j < a.F; ++j) {
+      const int G = g0 + j;
+      if (m[j] & 1) {
+        if (n == 0) { g = G; j0 = j; }
+        s_plan[j] = make_int2(r, open * a.max_frames + n);
+        ++r; ++n;
+        kept = turn_count(kept);
+        if (n == a.max_frames) {
+          d0 = open; d1 = n; d2 = g; d3 = G + 1;
+          scored = turn_count(scored); cut = turn_count(cut);
+          open ^= 1; n = 0;
+        }
+      } else {
+        s_plan[j] = make_int2(-1, 0);
+        if (n > 0) {
+          if (n >= a.min_frames) {
+            d0 = open; d1 = n; d2 = g; d3 = G;
+            scored = turn_count(scored);
+            open ^= 1;
+          } else {
+            shrt = turn_count(shrt);
+            for (int k = j0; k < j; ++k) s_plan[k].x = -1;
+          }
+          n = 0;
+        }
+      }
+    }
+    a.state[3 * slot] = open; a.state[3 * slot + 1] = n; a.state[3 * slot + 2] = g;
+    tot[0] = scored; tot[1] = shrt; tot[2] = cut; tot[3] = kept;
+    a.done[4 * row] = d0; a.done[4 * row + 1] = d1; a.done[4 * row + 2] = d2; a.done[4 * row + 3] = d3;
+  }
+  __syncthreads();
+  const float* src = a.staging + (long long)slot * a.ring_len;
+  float* dst = a.bufs + (long long)slot * 2 * a.max_frames * a.frame;
+  const bool vec = a.vec && (wpos & 3) == 0;
+  for (int f = wave; f < a.F; f += 4) {
+    const int2 p = s_plan[f];
+    if (p.x < 0) continue;
+    const long long w0 = (long long)wpos + (long long)p.x * a.frame;  // r < F and F * frame <= ring_len: one wrap
+    float* to = dst + (long long)p.y * a.frame;
+    if (vec) {
+      for (int k = 4 * lane; k < a.frame; k += 256) {
+        const long long w = w0 + k;
+        *reinterpret_cast<uint4*>(to + k) = *reinterpret_cast<const uint4*>(src + (w < a.ring_len ? w : w - a.ring_len));
+      }
+    } else {
+      for (int k = lane; k < a.frame; k += 64) {
+        const long long w = w0 + k;
+        to[k] = src[w < a.ring_len ? w : w - a.ring_len];
+      }
+    }
+  }
+}
+
+static bool host_aligned16(const void* p) { return ((unsigned long long)p & 15ull) == 0; }
+
+const char* launch_turn(const float* staging, int S, int ring_len, const unsigned char* mask, const int* hdr, int A, int F,
+                        int frame, int min_frames, int max_frames, float* bufs, int* state, int* totals, int* done,
+                        hipStream_t s) {
+  if (!staging || !mask || !hdr || !bufs || !state || !totals || !done) return "turn: null argument";
+  if (A <= 0 || A > 65535) return "turn: 1 to 65535 rows";
+  if (F < 1 || F > TURN_MAX_FRAMES) return "turn: 1 to 512 frames in a row";
+  if (frame <= 0) return "turn: a frame is a positive number of samples";
+  if (min_frames < F) return "turn: min_frames is at least the frames of a row (else a row could complete two turns)";
+  if (min_frames > max_frames) return "turn: min_frames is at most max_frames";
+  if (S <= 0 || (long long)F * frame > ring_len) return "turn: no slots, or a staging ring shorter than a row";
+  if ((long long)max_frames * frame > 0x3fffffff) return "turn: a turn of more than 2^30 samples";
+  TurnArgs a{staging, mask, hdr, bufs, state, totals, done, S, ring_len, F, frame, min_frames, max_frames,
+             frame % 4 == 0 && ring_len % 4 == 0 && host_aligned16(staging) && host_aligned16(bufs)};
+  hipLaunchKernelGGL(turn_kernel, dim3(A), dim3(256), 0, s, a);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+// out[r][k] = bufs[slot_r][buffer_r][k mod L_r], L_r = frames_r * frame, k < max_frames * frame: a turn tiled to the window
+// (tile_crop_kernel's function with start 0).  rows (R, 3): slot, buffer, frames.  Grid (column tiles, R); four samples per
+// lane where frame is a multiple of 4 and both bases are 16-byte aligned (L is then a multiple of 4: no 4-vector straddles
+// the wrap), one sample per lane otherwise.  A row out of range writes nothing.
+__global__ __launch_bounds__(256) void turn_collect_kernel(const float* __restrict__ bufs, int S, int max_frames, int frame,
+                                                           const int* __restrict__ rows, float* __restrict__ out, int vec) {
+  const int row = blockIdx.y, slot = rows[3 * row], buf = rows[3 * row + 1], frames = rows[3 * row + 2];
+  if (slot < 0 || slot >= S || buf < 0 || buf > 1 || frames < 1 || frames > max_frames) return;
+  const int W = max_frames * frame, L = frames * frame;
+  const float* src = bufs + ((long long)slot * 2 + buf) * W;
+  float* to = out + (long long)row * W;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x, step = gridDim.x * blockDim.x;
+  if (vec) {
+    for (int k = 4 * t; k < W; k += 4 * step)
+      *reinterpret_cast<uint4*>(to + k) = *reinterpret_cast<const uint4*>(src + k % L);
+  } else {
+    for (int k = t; k < W; k += step) to[k] = src[k % L];
+  }
+}
+
+const char* launch_turn_collect(const float* bufs, int S, int max_frames, int frame, const int* rows, int R, float* out,
+                                hipStream_t s) {
+  if (!bufs || !rows || !out) return "turn_collect: null argument";
+  if (S <= 0 || R <= 0 || R > 65535) return "turn_collect: 1 to 65535 rows";
+  if (frame <= 0 || max_frames <= 0 || (long long)max_frames * frame > 0x3fffffff)
+    return "turn_collect: a window of 1 to 2^30 samples in whole frames";
+  const int W = max_frames * frame, vec = frame % 4 == 0 && host_aligned16(bufs) && host_aligned16(out);
+  const int per = vec ? 1024 : 256;
+  hipLaunchKernelGGL(turn_collect_kernel, dim3(min((W + per - 1) / per, 64), R), dim3(256), 0, s, bufs, S, max_frames, frame,
+                     rows, out, vec);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+// ---------------------------------------------------------------------------------
 // Cascade (afx/cascade.py; the functions are stated in include/afx.h afx_k_cascade_store / _select / _windows): a cheap
 // screen scores every slot at every hop, and the windows of the slots whose score looks suspicious are gathered for a
 // second model.  Three launches per push, every index from a host-built header:

@@ -227,6 +227,16 @@ const char* launch_gate_tone(const float* x, int A, int n, const int* hdr, int f
                              int hang, const float* coef, int K, float thr, int confirm, int hold, float* nf, int* h,
                              int* tone_state, float* ring, int S, int ring_len, int* kept, int* ntone, unsigned char* mask,
                              float* tsum, hipStream_t s);
+// talk spurts (include/afx.h afx_k_turn): behind a gate launch into a staging ring, each row's kept frames are appended to
+// the slot's open turn (bufs (S, 2, max_frames * frame); state (S, 3) = open, n, g; totals (S, 4)); done (A, 4) names the
+// turn a row completed: buffer, frames, first source frame, one past the last
+const char* launch_turn(const float* staging, int S, int ring_len, const unsigned char* mask, const int* hdr, int A, int F,
+                        int frame, int min_frames, int max_frames, float* bufs, int* state, int* totals, int* done,
+                        hipStream_t s);
+// the clips of completed turns (include/afx.h afx_k_turn_collect): out[r][k] = bufs[slot][buffer][k mod (frames * frame)],
+// rows (R, 3) = slot, buffer, frames
+const char* launch_turn_collect(const float* bufs, int S, int max_frames, int frame, const int* rows, int R, float* out,
+                                hipStream_t s);
 // cascade (include/afx.h afx_k_cascade_store / _select / _windows): the named slots' hops into the retained-audio ring; the
 // candidates among the rows ranked by (score, slot), the first `budget` row positions into sel, the cooldown counters
 // advanced; the windows of the rows sel names gathered from the ring (sel is read on the device)
