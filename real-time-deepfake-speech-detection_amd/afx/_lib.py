@@ -124,6 +124,9 @@ SIGNATURES = {
     "afx_k_gate_tone": (_I, [_P, _I, _I, _P, _I, _F, _F, _F, _I, _P, _I, _F, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "afx_k_turn": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "afx_k_turn_collect": (_I, [_P, _I, _I, _I, _P, _I, _P, _P]),
+    "afx_k_turn_close": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "afx_k_turn_scan": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
+    "afx_k_turn_clips": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, _P, _P]),
     "afx_k_cascade_store":(_I, [_P, _I, _I, _P, _P, _I, _I, _P]),
     "afx_k_cascade_select": (_I, [_P, _I, _P, _I, _P, _P, _I, _F, _I, _I, _P, _P]),
     "afx_k_cascade_windows": (_I, [_P, _I, _I, _P, _I, _P, _I, _P, _P]),

@@ -316,6 +316,42 @@ def produce_timeline_file(dataset, model, device, save_path, window=64000, hop=4
     return names, timelines
 
 
+def write_turns_file(save_path, utt_ids, turns):
+    """One line per scored turn: ``"{utt_id} {start_s:.3f} {end_s:.3f} {score}"`` (the score as the reference's writer prints it)."""
+    d = os.path.dirname(save_path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(save_path, "w") as fh:
+        for f, tn in zip(utt_ids, turns):
+            for (s, e), cm in zip(tn.times().tolist(), tn.scores.tolist()):
+                fh.write("{} {:.3f} {:.3f} {}\n".format(f, s, e, cm))
+
+
+def produce_turns_file(dataset, model, device, save_path, gate=None, policy=None, window=64000, close_end=True, batch_size=8,
+                       num_workers=4, state_dict=None):
+    """Per-turn scores of UN-CROPPED clips (afx.turns.score_turns): ``model`` is a drop-in ``models.*`` module, or an afx
+    Engine; ``gate``, ``policy``, ``window`` and ``close_end`` as there; ``batch_size`` clips per loader batch; one line per
+    scored turn in dataset order (``write_turns_file``).  The per-utterance writer (``produce_evaluation_file*``) is
+    untouched."""
+    from torch.utils import data
+
+    from .turns import score_turns
+    if hasattr(model, "eval"):
+        model.eval()
+    dev = _as_device(device)
+    names, turns = [], []
+    loader = data.DataLoader(dataset, batch_size=batch_size, shuffle=False, drop_last=False, num_workers=num_workers,
+                             collate_fn=ragged_collate)
+    with torch.no_grad():
+        for utt_id, clips, _label in loader:
+            turns.extend(score_turns(model, [torch.as_tensor(c).to(dev) for c in clips], gate=gate, policy=policy, window=window,
+                                     close_end=close_end, state_dict=state_dict))
+            names.extend(utt_id)
+    _check_finite(model)
+    write_turns_file(save_path, names, turns)
+    return names, turns
+
+
 def evaluate(model, loader, device, loss_fn=None, preprocessor=None):
     """trainer.py:85-132: (mean loss, accuracy %) over a loader."""
     model.eval()

@@ -39,8 +39,26 @@ slot's j-th non-NaN score equals, bit for bit, score j of a fresh inner scorer o
 a ``SlidingWindowScorer`` inside that is ``model.forward(C_j[None])[0, 1]``.  The score is returned by the push that brings
 the frame that closes the turn -- the first non-kept frame, or the ``max_frames``-th kept one; every other push returns NaN
 for the slot and the inner session does not move.  Nothing depends on the other slots, on the order or subsets in which
-slots are named, or on session moves.  The end of a call is decided as for the gate: the caller pushes hops of zeros until
-the hangover has run out.  Onset pre-roll (``LookaheadGate``) is not built for turns.
+slots are named, or on session moves.  Onset pre-roll (``LookaheadGate``) is not built for turns.
+
+The end of a call is the *close* step (``afx_k_turn_close``, ``TurnScorer.flush``), applied to ``(open, n, g, totals)``::
+
+    if n >= min_frames:  done = (open, n, g, g + n); scored += 1; open ^= 1
+    elif n > 0:          short += 1;                 done = (0, 0, 0, 0)
+    else:                                            done = (0, 0, 0, 0)
+    n = 0
+
+``cut`` and ``kept`` do not move.  ``flush`` scores the turn that is open at hang-up at once and as it is: no hop of zeros
+has to be pushed until the hangover runs out, and no frame of made-up silence joins the clip.
+
+The offline form, ``score_turns``: a recording is the stream pushed hop by hop and then flushed.  The *cut* of a keep mask of
+n frames is the recurrence above from a new stream's state over all n frames and then, with ``close_end``, the close step;
+the scored turns are the ``done`` values with frames > 0 in stream order, each ``(first, end)`` in source frames with two
+flags, ``cut`` (it closed by reaching ``max_frames``) and ``at_end`` (the close step closed it); short turns are counted,
+not listed; without ``close_end`` the turn still open at the end is ``open = (first, frames)``, else ``(-1, 0)``.  A turn is
+a run of kept frames, so its samples are contiguous in the source, ``x[first*frame : end*frame]``, and its clip is tiled
+straight from the recording (``afx_k_turn_clips``): no staging ring and no buffers.  ``afx_k_turn_scan`` cuts the masks of
+all recordings of a call in one go, ``SCAN_STEP`` frames a step per recording (include/afx.h states both).
 
 What the layers inside then mean: a verdict's hop index counts utterances; an evidence "hop" is a whole padded utterance;
 the quality guard measures the padded clip, and its window count ``W`` is 1; a cascade's teacher re-scores a suspect
@@ -53,11 +71,12 @@ import numpy as np
 import torch
 
 from ._layer import N_MAX, Layer, StreamState, _on, integer, need_gpu, rows_on
-from ._lib import call_on, check, lib, ptr
+from ._lib import AfxError, call_on, check, lib, ptr
 from .vad import GATE_FORMAT, LookaheadGate, SpeechGate, ToneGate, check_floor_shape, check_hang_and_floor, check_tone, emitted, session_counts
 
 TURN_FORMAT = 1  # layout of the turn part of a StreamState: import_slots refuses any other
 MAX_FRAMES = 512  # frames of a push (afx_k_turn's plan table)
+SCAN_STEP = 4096  # frames a workgroup of afx_k_turn_scan takes per step: 256 threads x 16 mask bytes
 
 
 def _count(v):
@@ -141,6 +160,52 @@ class TurnPolicy:
         totals = (scored, len(turns) - scored, sum(t["cut"] for t in turns), kept_frames)
         return turns, totals, (None if first is None else (first, keep.size - first))
 
+    def close_reference(self, state):
+        """The close step on a host mirror: the end of a call.  state: as for ``step_reference`` (it is not modified) -> (the
+        state after it, done); the closed turn, if it is scored, stands in buffer ``done[0]`` as after a push."""
+        opn, n, g = state["open"], state["n"], state["g"]
+        scored, short, cut, total = state["totals"]
+        done = (0, 0, 0, 0)
+        if n >= self.min_frames:
+            done = (opn, n, g, g + n)
+            scored, opn = _count(scored), opn ^ 1
+        elif n > 0:
+            short = _count(short)
+        return {"open": opn, "n": 0, "g": g, "totals": (scored, short, cut, total), "max_frames": state["max_frames"]}, done
+
+    def cut_reference(self, keep, max_frames, close_end=True):
+        """A whole stream cut at once, from its mask alone (the module docstring's *cut*).  keep: (n,) mask bytes or bools
+        (bit 0 counts) -> (turns, totals, open): ``turns`` the scored turns in order, each a dict of ``first``, ``end``
+        (source frames, end exclusive), ``cut`` and ``at_end``; ``totals`` = (scored, short, cut, kept); ``open`` = (first,
+        frames) of the turn still open behind the last frame, (-1, 0) when there is none or with ``close_end``.  Stated as
+        ``afx_k_turn_scan`` computes it, over whole arrays: frame G of a run that starts at s has position p = G - s; it
+        closes a cut turn [G + 1 - max, G + 1) when (p + 1) % max == 0, else a natural turn [s + p // max * max, G + 1) of
+        p % max + 1 frames when frame G + 1 is not kept (or is the end, with ``close_end``).  It equals ``step_reference``
+        chained over pushes of any size, then ``close_reference``."""
+        top = integer("max_frames", max_frames, self.min_frames)
+        k = (np.asarray(keep).reshape(-1).astype(np.uint8) & 1).astype(bool)
+        n = k.size
+        if n >= 1 << 31:
+            raise ValueError("a stream of 2^31 frames or more")
+        idx = np.arange(n, dtype=np.int64)
+        before = np.concatenate([[False], k[:-1]])
+        after = np.concatenate([k[1:], [False]])
+        s = np.maximum.accumulate(np.where(k & ~before, idx, -1)) if n else idx
+        p = idx - s
+        is_cut = k & ((p + 1) % top == 0)
+        ends = k & ~is_cut & ~after
+        if not close_end and n:
+            ends[n - 1] = False
+        length = p % top + 1
+        is_scored = is_cut | (ends & (length >= self.min_frames))
+        turns = [dict(first=int(G + 1 - top) if is_cut[G] else int(G + 1 - length[G]), end=int(G + 1), cut=bool(is_cut[G]),
+                      at_end=bool(close_end and G == n - 1 and not is_cut[G])) for G in np.flatnonzero(is_scored)]
+        totals = (int(is_scored.sum()), int((ends & ~is_scored).sum()), int(is_cut.sum()), int(k.sum()))
+        still = (-1, 0)
+        if n and not close_end and k[n - 1] and not is_cut[n - 1]:
+            still = (int(n - length[n - 1]), int(length[n - 1]))
+        return turns, totals, still
+
     @staticmethod
     def clip_reference(audio, window):
         """The padded clip of a turn: its samples repeated to ``window`` (``clip[k] = audio[k mod L]``)."""
@@ -156,9 +221,10 @@ class TurnScorer(Layer):
 
     Per slot two buffers of one window on the device (2 x window x 4 bytes: 512 KB at 4 s) and a staging ring of one hop.
     A push is the gate's own launch into the staging ring (with its mask), one ``afx_k_turn``, the read-back of ``done``,
-    and -- if a row completed a turn -- one ``afx_k_turn_collect`` and one inner ``push`` over those rows.
+    and -- if a row completed a turn -- one ``afx_k_turn_collect`` and one inner ``push`` over those rows.  ``flush`` ends a
+    call: the close step in the place of the gate's launch and ``afx_k_turn``, the rest the same.
 
-    ``last_turn``: (A, 2) int64 on the device, in the row order of the newest push: [first source sample, one past the last)
+    ``last_turn``: (A, 2) int64 on the device, in the row order of the newest push or flush: [first source sample, one past the last)
     of the turn that push scored, (-1, -1) where it scored none; computed on the device from ``done``.  ``turn_totals``: the
     (S, 4) int32 device view of (scored, short, cut, kept).  ``stats()`` reads them back.
 
@@ -278,33 +344,70 @@ class TurnScorer(Layer):
             th = th.to(dev, non_blocking=True)
             check(call_on(self.staging, lib().afx_k_turn, ptr(self.staging), self.S, hop, ptr(mask), ptr(th), A, self.F, frame,
                           self.min_frames, self.max_frames, ptr(self.bufs), ptr(self.turn_state), ptr(self._totals), ptr(done)))
-            host = torch.empty(A, 4, dtype=torch.int32, pin_memory=True)
-            host.copy_(done, non_blocking=True)
-            wide = done.long()
-            self.last_turn = torch.where(wide[:, 1:2] > 0, wide[:, 2:4] * frame, torch.full_like(wide[:, 2:4], -1))
-            torch.cuda.current_stream(dev).synchronize()  # the one read-back: which rows closed a turn is in the audio
-            d = host.numpy()
-            if (d[:, 1] < 0).any():
-                raise RuntimeError("afx_k_turn skipped a row: a slot's turn state is not a turn state")
+            d = self._read_done(done, "afx_k_turn")
             self._seen[slot] += hop
-            out = torch.full((A,), float("nan"), dtype=torch.float32, device=dev)
-            rows = np.flatnonzero(d[:, 1] > 0)
-            if rows.size:
-                R = rows.size
-                tab = torch.empty(4 * R, dtype=torch.int32, pin_memory=True)  # the collect table (slot, buffer, frames), then the result rows
-                tab.numpy()[:3 * R] = np.stack([slot[rows], d[rows, 0], d[rows, 1]], axis=1).reshape(-1)
-                tab.numpy()[3 * R:] = rows
-                t = tab.to(dev, non_blocking=True)
-                clips = torch.empty(R, self.window, dtype=torch.float32, device=dev)
-                check(call_on(self.bufs, lib().afx_k_turn_collect, ptr(self.bufs), self.S, self.max_frames, frame, ptr(t), R,
-                              ptr(clips)))
-                sc = self.scorer.push(clips, slot[rows].tolist())
-                if sc is None:
-                    raise RuntimeError("the inner scorer emitted no score for a turn")
-                if R == A:
-                    out = sc.to(torch.float32)
-                else:
-                    out.index_copy_(0, t[3 * R:].long(), sc.to(torch.float32))
+            return self._score_done(slot, d)
+
+    def flush(self, slots=None):
+        """The call has ended for the named slots (None: every slot, in order): the close step of the module docstring -> (A,)
+        fp32 in the order named: the inner scorer's score of the turn that was open, as it is, NaN where none was or where
+        it was shorter than ``min_frames`` (dropped and counted).  One ``afx_k_turn_close``, the read-back of ``done``, and
+        -- where a row closed a scored turn -- ``afx_k_turn_collect`` and one inner ``push``, as in ``push``; ``last_turn``
+        is set as a push sets it.  The score is bit for bit what the inner scorer gives the clip of the open turn.  The
+        gate's state (noise floor, hangover, tone state) and ``samples_seen`` do not move: if the stream goes on, its next
+        kept frame opens a new turn.  A second ``flush`` finds nothing open."""
+        idx = self._named(slots)
+        dev, A = self.device, len(idx)
+        need_gpu(dev, "turns are cut and scored")
+        if self._tone:
+            self.last_tone_frames = torch.zeros(A, dtype=torch.int32, device=dev)
+        if not A:
+            self.last_turn = torch.empty(0, 2, dtype=torch.int64, device=dev)
+            return torch.empty(0, dtype=torch.float32, device=dev)
+        slot = np.asarray(idx, dtype=np.int64)
+        with torch.cuda.device(dev):
+            th = torch.empty(A, dtype=torch.int32, pin_memory=True)
+            th.numpy()[:] = slot
+            th = th.to(dev, non_blocking=True)
+            done = torch.empty(A, 4, dtype=torch.int32, device=dev)
+            check(call_on(self.turn_state, lib().afx_k_turn_close, ptr(th), A, self.S, self.min_frames, self.max_frames,
+                          ptr(self.turn_state), ptr(self._totals), ptr(done)))
+            return self._score_done(slot, self._read_done(done, "afx_k_turn_close"))
+
+    def _read_done(self, done, who):
+        """``done`` (A, 4) of a launch -> its host copy, with ``last_turn`` set from it on the device."""
+        host = torch.empty(done.shape[0], 4, dtype=torch.int32, pin_memory=True)
+        host.copy_(done, non_blocking=True)
+        wide = done.long()
+        self.last_turn = torch.where(wide[:, 1:2] > 0, wide[:, 2:4] * self.gate.frame, torch.full_like(wide[:, 2:4], -1))
+        torch.cuda.current_stream(self.device).synchronize()  # the one read-back: which rows closed a turn is in the audio
+        d = host.numpy()
+        if (d[:, 1] < 0).any():
+            raise RuntimeError(f"{who} skipped a row: a slot's turn state is not a turn state")
+        return d
+
+    def _score_done(self, slot, d):
+        """The clips of the turns ``d`` names (rows of slots ``slot``), collected and pushed to the inner scorer -> (A,) fp32,
+        NaN where a row completed no turn."""
+        dev, A = self.device, len(slot)
+        out = torch.full((A,), float("nan"), dtype=torch.float32, device=dev)
+        rows = np.flatnonzero(d[:, 1] > 0)
+        if rows.size:
+            R = rows.size
+            tab = torch.empty(4 * R, dtype=torch.int32, pin_memory=True)  # the collect table (slot, buffer, frames), then the result rows
+            tab.numpy()[:3 * R] = np.stack([slot[rows], d[rows, 0], d[rows, 1]], axis=1).reshape(-1)
+            tab.numpy()[3 * R:] = rows
+            t = tab.to(dev, non_blocking=True)
+            clips = torch.empty(R, self.window, dtype=torch.float32, device=dev)
+            check(call_on(self.bufs, lib().afx_k_turn_collect, ptr(self.bufs), self.S, self.max_frames, self.gate.frame, ptr(t), R,
+                          ptr(clips)))
+            sc = self.scorer.push(clips, slot[rows].tolist())
+            if sc is None:
+                raise RuntimeError("the inner scorer emitted no score for a turn")
+            if R == A:
+                out = sc.to(torch.float32)
+            else:
+                out.index_copy_(0, t[3 * R:].long(), sc.to(torch.float32))
         return out
 
     def _reset(self, idx):
@@ -389,3 +492,177 @@ class TurnScorer(Layer):
                 if self._tone:
                     self.tone_state[dev_rows] = rows[7].to(dev, torch.int32)
             self._seen[idx] = seen
+
+
+# ---- the offline form ----------------------------------------------------------------------------------------------------------
+class Turns:
+    """The scored turns of one recording, in order: ``scores`` (n,) fp32 CPU, bonafide scores (class 1: low means spoof);
+    ``starts`` / ``ends`` (n,) float64 bounds of each turn in input-rate samples (the resampler's delay taken out at other
+    rates); ``cut`` / ``at_end`` (n,) bool: the turn closed by reaching the window / by the end of the recording; ``totals``:
+    a dict of ``scored``, ``short``, ``cut``, ``kept_frames`` and ``open_frames`` (the frames of the turn still open at the
+    end: 0 with ``close_end``); ``sample_rate`` the input rate."""
+
+    def __init__(self, scores, starts, ends, cut, at_end, totals=None, sample_rate=16000):
+        self.scores = torch.as_tensor(scores, dtype=torch.float32).cpu().reshape(-1)
+        self.starts = torch.as_tensor(starts, dtype=torch.float64).cpu().reshape(-1)
+        self.ends = torch.as_tensor(ends, dtype=torch.float64).cpu().reshape(-1)
+        self.cut = torch.as_tensor(cut, dtype=torch.bool).cpu().reshape(-1)
+        self.at_end = torch.as_tensor(at_end, dtype=torch.bool).cpu().reshape(-1)
+        self.totals = dict(scored=len(self), short=0, cut=int(self.cut.sum()), kept_frames=0, open_frames=0) if totals is None else dict(totals)
+        self.sample_rate = int(sample_rate)
+        if not self.scores.numel() == self.starts.numel() == self.ends.numel() == self.cut.numel() == self.at_end.numel():
+            raise ValueError("scores, starts, ends, cut and at_end differ in length")
+
+    def __len__(self):
+        return int(self.scores.numel())
+
+    def times(self):
+        """(n, 2) float64: each turn's (start, end) in seconds."""
+        return torch.stack([self.starts, self.ends], dim=1) / self.sample_rate
+
+    def segments(self, threshold):
+        """The (start_s, end_s) of the turns scoring below ``threshold``; the pieces of one run of speech that the window cut
+        (a turn that begins where the one before it ends) are merged when both score below it."""
+        out, last = [], None  # last: where the turn before this one ended, if it scored below the threshold
+        for s, e, low in zip(self.starts.tolist(), self.ends.tolist(), (self.scores < threshold).tolist()):
+            if low and s == last:
+                out[-1] = (out[-1][0], e / self.sample_rate)
+            elif low:
+                out.append((s / self.sample_rate, e / self.sample_rate))
+            last = e if low else None
+        return out
+
+    def alarms(self, policy):
+        """The alarms a ``VerdictPolicy`` raises over these turns (``policy.run_reference`` over ``scores``, the hop index
+        counting utterances 1, 2, ...: what a ``VerdictScorer`` inside a one-slot ``TurnScorer`` logs): a list of
+        ``(raised_s, cleared_s or None, kind)`` -- the ends, in seconds, of the turns at which the alarm was raised and
+        cleared (None: still on at the end), and the raise's kind."""
+        events, _ = policy.run_reference(self.scores.numpy())
+        ends = (self.ends / self.sample_rate).tolist()
+        out = []
+        for _slot, kind, j, _bits in events:
+            if kind == 3:
+                out[-1] = (out[-1][0], ends[j - 1], out[-1][2])
+            else:
+                out.append((ends[j - 1], None, kind))
+        return out
+
+    def summary(self, threshold):
+        """The number of turns, min, mean and the fraction of turns scoring below ``threshold`` (flagged as spoof)."""
+        n = len(self)
+        if n == 0:
+            return {"turns": 0, "min": float("nan"), "mean": float("nan"), "flagged": 0.0}
+        return {"turns": n, "min": float(self.scores.min()), "mean": float(self.scores.double().mean()),
+                "flagged": float((self.scores < threshold).double().mean())}
+
+
+_stage = None  # a callable(name) that is told where each stage of score_turns begins (tools/turn_bench.py times them)
+
+
+def _mark(name):
+    if _stage is not None:
+        _stage(name)
+
+
+def score_turns(model, recordings, gate=None, policy=None, window=64000, sample_rate=16000, close_end=True, batch=None,
+                state_dict=None):
+    """Score every talk spurt of recorded calls as one utterance (the module docstring's offline form) -> one ``Turns`` per
+    recording; a recording with no scored turn yields an empty one.
+
+    model: an afx ``Engine`` (``state_dict`` is accepted as for ``score_timeline``), or a drop-in ``models.*`` module.
+    recordings: a list of 1-D waveforms of any lengths at ``sample_rate``, on the host or on the GPU; trailing samples short
+    of a frame are dropped, as in ``gate()``.  gate: a ``SpeechGate`` or a ``ToneGate`` (default: the default
+    ``SpeechGate``); policy: a ``TurnPolicy``; window: the clip length the model scores, whole frames; ``close_end``: the end
+    of a recording is the end of the call (False: the turn open there is not scored and is reported in ``totals``).  At
+    another sample rate the recordings are resampled first (``Resampler.clips``) and the spans mapped back.
+
+    The gate's offline launch gives the keep masks; one ``afx_k_turn_scan`` cuts them all, one read-back says how many turns
+    there are, and per batch of at most ``batch`` turns (default: ``timeline.default_batch``) one ``afx_k_turn_clips`` tiles
+    the clips from the recordings and ``Engine.forward`` scores them.  Contract: turn j of recording i has the spans of
+    ``cut_reference`` on that recording's mask, its score is bit for bit ``model.forward(clip[None])[0, 1]``, and for a
+    recording of whole hops the scores are, in order, the non-NaN scores of one slot of a ``TurnScorer`` over a
+    ``SlidingWindowScorer(model, S, window, window)`` pushed the recording hop by hop and then flushed."""
+    from .timeline import _resolve, default_batch
+    eng, _ = _resolve(model, state_dict)
+    gate = SpeechGate() if gate is None else gate
+    policy = TurnPolicy() if policy is None else policy
+    if not isinstance(gate, SpeechGate):
+        raise ValueError("gate: a SpeechGate or a ToneGate")
+    if isinstance(gate, LookaheadGate):
+        raise ValueError("gate: a SpeechGate or a ToneGate; onset pre-roll (LookaheadGate) is not built for turns")
+    if not isinstance(policy, TurnPolicy):
+        raise ValueError("policy: a TurnPolicy")
+    window, frame, least = integer("window", window, 1, 1 << 30), gate.frame, policy.min_frames
+    if window % frame:
+        raise ValueError(f"a window of {window} samples is not a whole number of {frame}-sample frames")
+    top = window // frame
+    if least > top:
+        raise ValueError(f"min_frames {least}: at most the {top} frames of the window")
+    recs = [torch.as_tensor(x).reshape(-1) for x in recordings]
+    if len(recs) > 65535:
+        raise ValueError("at most 65535 recordings a call")
+    batch = default_batch(eng) if batch is None else integer("batch", batch, 1, 65535)
+    if not torch.cuda.is_available():
+        raise AfxError("turns are cut and scored on the GPU; there is no CPU fallback")
+    dev = torch.device(eng.device)
+    rate, delay = 16000, 0.0
+    with torch.cuda.device(dev):
+        if sample_rate != 16000:
+            from .resample import Resampler
+            rs = Resampler(sample_rate, dev)
+            rate, delay = rs.rate, rs.delay
+            recs = rs.clips([x.to(dev) for x in recs])
+        recs = [x.to(dev, torch.float32) for x in recs]
+        A = len(recs)
+        if not A:
+            return []
+        _mark("gate")
+        masks = gate.gate(recs, return_mask=True)[1]
+        _mark("scan")
+        n = np.array([m.numel() for m in masks], dtype=np.int64)
+        cap = int((n // least).sum())  # (a scored turn has at least min_frames frames)
+        hdr = torch.empty(2, A + 1, dtype=torch.int64, pin_memory=True)  # frame offsets, sample offsets
+        hdr.numpy()[0, 0], hdr.numpy()[0, 1:] = 0, np.cumsum(n)
+        hdr.numpy()[1] = hdr.numpy()[0] * frame
+        hdr = hdr.to(dev, non_blocking=True)
+        c4 = 4 * max(cap, 1)
+
+        def parts(t):  # the scan's outputs stand in one buffer, for one copy to the host: table, row_base, totals, open
+            return t[:c4].view(-1, 4), t[c4:c4 + A + 1], t[c4 + A + 1:c4 + 5 * A + 1].view(A, 4), t[c4 + 5 * A + 1:].view(A, 2)
+
+        ints = torch.zeros(c4 + 7 * A + 1, dtype=torch.int32, device=dev)
+        table, row_base, totals, still = parts(ints)
+        R = 0
+        if int(n.sum()):
+            mask = torch.cat([m.to(torch.uint8) for m in masks])
+            check(call_on(mask, lib().afx_k_turn_scan, ptr(mask), ptr(hdr[0]), A, least, top, int(bool(close_end)), ptr(table),
+                          cap, ptr(row_base), ptr(totals), ptr(still)))
+            R = int(row_base[A])  # the one read-back before the clips: how many turns there are
+            if R > cap:
+                raise RuntimeError(f"afx_k_turn_scan counted {R} turns where at most {cap} fit")
+        else:
+            still[:, 0] = -1
+        scores = torch.empty(R, dtype=torch.float32, device=dev)
+        if R:
+            x = torch.cat([r[:k * frame] for r, k in zip(recs, n.tolist())])
+            for r0 in range(0, R, batch):
+                Rb = min(batch, R - r0)
+                _mark("clips")
+                clips = torch.empty(Rb, window, dtype=torch.float32, device=dev)
+                check(call_on(x, lib().afx_k_turn_clips, ptr(x), ptr(hdr[1]), A, frame, top, ptr(table), r0, Rb, ptr(clips)))
+                _mark("forward")
+                scores[r0:r0 + Rb] = eng.forward(clips)[:, 1]
+        _mark("end")
+        table, base, totals, still = parts(ints.cpu())
+        scores = scores.cpu()
+    table, base, totals, still = table[:R], base.tolist(), totals.tolist(), still.tolist()
+    scale = rate / 16000.0
+    out = []
+    for i in range(A):
+        t = table[base[i]:base[i + 1]]
+        st, en = t[:, 1].double() * frame, t[:, 2].double() * frame
+        if delay:  # 16 kHz sample k of the resampled stream is input time (k - delay) / 16000 s
+            st, en = (st - delay).clamp(min=0), (en - delay).clamp(min=0)
+        tot = dict(scored=totals[i][0], short=totals[i][1], cut=totals[i][2], kept_frames=totals[i][3], open_frames=still[i][1])
+        out.append(Turns(scores[base[i]:base[i + 1]], st * scale, en * scale, (t[:, 3] & 1).bool(), (t[:, 3] & 2).bool(), tot, rate))
+    return out

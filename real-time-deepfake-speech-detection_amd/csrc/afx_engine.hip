@@ -2908,6 +2908,19 @@ extern "C" int afx_k_turn_collect(const float* bufs, int S, int max_frames, int 
                                   void* stream) {
   KRET(launch_turn_collect(bufs, S, max_frames, frame, rows, R, out, (hipStream_t)stream));
 }
+extern "C" int afx_k_turn_close(const int* slots, int A, int S, int min_frames, int max_frames, int* state, int* totals, int* done,
+                                void* stream) {
+  KRET(launch_turn_close(slots, A, S, min_frames, max_frames, state, totals, done, (hipStream_t)stream));
+}
+extern "C" int afx_k_turn_scan(const unsigned char* mask, const long long* offs, int A, int min_frames, int max_frames,
+                               int close_end, int* table, int cap, int* row_base, int* totals, int* open, void* stream) {
+  KRET(launch_turn_scan(mask, offs, A, min_frames, max_frames, close_end, table, cap, row_base, totals, open,
+                        (hipStream_t)stream));
+}
+extern "C" int afx_k_turn_clips(const float* x, const long long* xoffs, int A, int frame, int max_frames, const int* table, int r0,
+                                int R, float* out, void* stream) {
+  KRET(launch_turn_clips(x, xoffs, A, frame, max_frames, table, r0, R, out, (hipStream_t)stream));
+}
 extern "C" int afx_k_cascade_store(const float* x, int A, int hop, const int* hdr, float* hist, int S, int window,
                                    void* stream) {
   KRET(launch_cascade_store(x, A, hop, hdr, hist, S, window, (hipStream_t)stream));

@@ -2152,6 +2152,307 @@ const char* launch_turn_collect(const float* bufs, int S, int max_frames, int fr
   return e == hipSuccess ? nullptr : hipGetErrorString(e);
 }
 
+// The close step of the recurrence (include/afx.h afx_k_turn_close): the end of a call.  One thread per named slot; a slot
+// out of range, or whose state is no turn state, gets done = (-1, -1, -1, -1) and nothing else.
+__global__ __launch_bounds__(256) void turn_close_kernel(const int* __restrict__ slots, int A, int S, int min_frames, int max_frames,
+                                                         int* state, int* totals, int* __restrict__ done) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= A) return;
+  const int slot = slots[i];
+  int open = 0, n = 0;
+  bool ok = slot >= 0 && slot < S;
+  if (ok) {
+    open = state[3 * slot];
+    n = state[3 * slot + 1];
+    ok = (open == 0 || open == 1) && n >= 0 && n < max_frames;
+  }
+  int d0 = 0, d1 = 0, d2 = 0, d3 = 0;
+  if (!ok) {
+    d0 = d1 = d2 = d3 = -1;
+  } else {
+    if (n >= min_frames) {
+      const int g = state[3 * slot + 2];
+      d0 = open; d1 = n; d2 = g; d3 = g + n;
+      totals[4 * slot] = turn_count(totals[4 * slot]);
+      state[3 * slot] = open ^ 1;
+    } else if (n > 0) {
+      totals[4 * slot + 1] = turn_count(totals[4 * slot + 1]);
+    }
+    state[3 * slot + 1] = 0;
+  }
+  done[4 * i] = d0; done[4 * i + 1] = d1; done[4 * i + 2] = d2; done[4 * i + 3] = d3;
+}
+
+const char* launch_turn_close(const int* slots, int A, int S, int min_frames, int max_frames, int* state, int* totals, int* done,
+                              hipStream_t s) {
+  if (!slots || !state || !totals || !done) return "turn_close: null argument";
+  if (A <= 0 || A > 65535) return "turn_close: 1 to 65535 rows";
+  if (S <= 0) return "turn_close: no slots";
+  if (min_frames < 1) return "turn_close: min_frames is at least 1";
+  if (min_frames > max_frames) return "turn_close: min_frames is at most max_frames";
+  hipLaunchKernelGGL(turn_close_kernel, dim3((A + 255) / 256), dim3(256), 0, s, slots, A, S, min_frames, max_frames, state, totals,
+                     done);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+// ---------------------------------------------------------------------------------
+// Turns offline (afx/turns.py score_turns; the functions are stated in include/afx.h afx_k_turn_scan / afx_k_turn_clips): the
+// recurrence of turn_kernel over whole recordings at once.  The masks of A recordings stand back to back; one workgroup of 256
+// threads per recording walks its mask TURN_SCAN_STEP frames a step, each thread one 16-byte load of 16 frames.  What makes
+// the recurrence serial is only the state a thread's first frame meets, (n, g) of the open turn, and that follows from the
+// start of the run the previous frame belongs to: a run of `run` frames before frame f0 leaves n = run % max_frames and
+// g = f0 - n.  Per step:
+//   load      16 mask bytes per thread, packed to 16 bits.  Chunks are aligned to 16 bytes of the ADDRESS, so a recording that
+//             starts off that grid still loads 16 bytes a lane; only the chunks that hold a row's first or last frames (and the
+//             one virtual not-kept frame behind the last that is the close step) go byte by byte;
+//   starts    a frame starts a run when it is kept and the frame before it is not (the neighbour thread's last bit through
+//             LDS, the last step's through the carry); the thread's last start, an exclusive max-scan over the workgroup
+//             (__shfl_up within a wave, four wave totals through LDS) and the carry give the run start its first frame meets;
+//   walk      the thread runs the stated recurrence over its 16 frames from that state and counts the turns it scores; an
+//             exclusive sum-scan places them behind the turns of the step's earlier threads, of the earlier steps (the carry)
+//             and of the earlier rows (row_base).  The table's order is the stream's: no atomic takes part in it.
+// Three launches: the count pass (row counts into row_base, totals, open), one workgroup that turns the A counts into their
+// exclusive prefix sums, and the write pass (the same walk, now storing).  Integer VALU, byte and 16-byte loads only.
+// ---------------------------------------------------------------------------------
+constexpr int TURN_SCAN_LANE = 16;                    // frames of a thread and step
+constexpr int TURN_SCAN_STEP = 256 * TURN_SCAN_LANE;  // frames of a step (afx.turns.SCAN_STEP; include/afx.h states it)
+
+struct TurnScanArgs {
+  const unsigned char* mask;  // the rows' frames back to back: bit 0 = kept
+  const long long* offs;      // (A + 1): row i is mask[offs[i] .. offs[i + 1])
+  int* table;                 // (cap, 4): row, first, end, flags (bit 0 cut, bit 1 at_end)
+  int* row_base;              // (A + 1): the count pass leaves row i's scored turns in [i]; then their exclusive prefix sums
+  int* totals;                // (A, 4): scored, short, cut, kept
+  int* open;                  // (A, 2): first, frames of the turn still open; (-1, 0): none
+  int A, min_frames, max_frames, close_end, cap;
+};
+
+struct TurnScanMax { __device__ __forceinline__ int operator()(int a, int b) const { return max(a, b); } };
+struct TurnScanSum { __device__ __forceinline__ int operator()(int a, int b) const { return a + b; } };
+
+// An exclusive scan of v over the 256 threads in thread order, and its total: within a wave by __shfl_up, the four wave
+// totals through s_wave.  Every thread of the workgroup calls it (two barriers).
+template <class Op>
+__device__ __forceinline__ int turn_scan_excl(int v, int ident, int* s_wave, Op op, int& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int u = __shfl_up(v, d, 64);
+    if (lane >= d) v = op(u, v);
+  }
+  int mine = __shfl_up(v, 1, 64);
+  if (lane == 0) mine = ident;
+  __syncthreads();  // (the last scan's readers are done with s_wave)
+  if (lane == 63) s_wave[wave] = v;
+  __syncthreads();
+  int before = ident;
+  total = ident;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const int t = s_wave[w];
+    if (w < wave) before = op(before, t);
+    total = op(total, t);
+  }
+  return op(before, mine);
+}
+
+// The stated recurrence over the thread's frames f0 .. f0 + 15 (bit j of bits: frame f0 + j is kept), from (n, g); frames
+// outside [0, end) are passed over, and frame n_row (there only with close_end: end = n_row + 1) is the close step.  -> the
+// turns scored; with WRITE they go to table rows at, at + 1, ... below cap.
+template <bool WRITE>
+__device__ __forceinline__ int turn_scan_walk(unsigned bits, long long f0, long long end, int n_row, int n, int g, int min_frames,
+                                              int max_frames, int& shrt, int& cut, int* table, long long at, int cap, int row) {
+  int emitted = 0;
+#pragma unroll
+  for (int j = 0; j < TURN_SCAN_LANE; ++j) {
+    const long long G = f0 + j;
+    if (G < 0 || G >= end) continue;
+    int first = -1, last = 0, flags = 0;
+    if ((bits >> j) & 1) {
+      if (n == 0) g = (int)G;
+      if (++n == max_frames) {
+        first = g; last = (int)G + 1; flags = 1;
+        ++cut;
+        n = 0;
+      }
+    } else if (n > 0) {
+      if (n >= min_frames) {
+        first = g; last = (int)G; flags = G == n_row ? 2 : 0;
+      } else {
+        ++shrt;
+      }
+      n = 0;
+    }
+    if (first >= 0) {
+      if (WRITE && at + emitted < cap) {
+        int* t = table + 4 * (at + emitted);
+        t[0] = row; t[1] = first; t[2] = last; t[3] = flags;
+      }
+      ++emitted;
+    }
+  }
+  return emitted;
+}
+
+template <bool WRITE>
+__global__ __launch_bounds__(256) void turn_scan_kernel(TurnScanArgs a) {
+  __shared__ int s_wave[4];
+  __shared__ unsigned short s_bits[256];
+  __shared__ int s_tot[3][4];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const long long o0 = a.offs[row], len = a.offs[row + 1] - o0;
+  // (offsets that are negative, decrease or span 2^31 frames or more: the row is taken as one of no frames)
+  const int n_row = o0 >= 0 && len > 0 && len < (1LL << 31) ? (int)len : 0;
+  if (n_row == 0) {
+    if (!WRITE && tid < 4) a.totals[4 * row + tid] = 0;
+    if (!WRITE && tid < 2) a.open[2 * row + tid] = tid ? 0 : -1;
+    if (!WRITE && tid == 0) a.row_base[row] = 0;
+    return;
+  }
+  const unsigned char* m = a.mask + o0;
+  const int mis = (int)((unsigned long long)m & 15ull);  // the row's first frame stands that far into a 16-byte group
+  const long long end = (long long)n_row + (a.close_end ? 1 : 0);
+  const long long at0 = WRITE ? a.row_base[row] : 0;
+  int c_prev = 0, c_start = -1, c_scored = 0;  // the carry: was the step's last frame kept; the newest run start; turns scored
+  int shrt = 0, cut = 0, kept = 0;             // this thread's share of the totals
+  for (long long base = -mis; base < end; base += TURN_SCAN_STEP) {
+    const long long f0 = base + tid * TURN_SCAN_LANE;
+    unsigned bits = 0;
+    if (f0 >= 0 && f0 + TURN_SCAN_LANE <= n_row) {
+      const uint4 v = *reinterpret_cast<const uint4*>(m + f0);
+      const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        bits |= ((w[k] & 1u) | ((w[k] >> 7) & 2u) | ((w[k] >> 14) & 4u) | ((w[k] >> 21) & 8u)) << (4 * k);
+    } else {
+#pragma unroll
+      for (int j = 0; j < TURN_SCAN_LANE; ++j) {
+        const long long f = f0 + j;
+        if (f >= 0 && f < n_row) bits |= (unsigned)(m[f] & 1) << j;
+      }
+    }
+    s_bits[tid] = (unsigned short)bits;
+    __syncthreads();
+    const int prev = tid ? (s_bits[tid - 1] >> 15) & 1 : c_prev;
+    const int step_last = (s_bits[255] >> 15) & 1;
+    const unsigned starts = bits & ~((bits << 1) | (unsigned)prev) & 0xffffu;
+    const int my_start = starts ? (int)f0 + 31 - __clz(starts) : -1;
+    int newest;
+    const int before = max(c_start, turn_scan_excl(my_start, -1, s_wave, TurnScanMax(), newest));
+    // the open turn this thread's first frame meets: the run it continues has f0 - before frames (1 to 2^31 - 1)
+    const int n = prev ? (int)((unsigned)(f0 - before) % (unsigned)a.max_frames) : 0;
+    const int g = (int)f0 - n;
+    int d_short = 0, d_cut = 0, step_scored;
+    const int mine = turn_scan_walk<false>(bits, f0, end, n_row, n, g, a.min_frames, a.max_frames, d_short, d_cut, nullptr, 0, 0, row);
+    const int ahead = turn_scan_excl(mine, 0, s_wave, TurnScanSum(), step_scored);
+    shrt += d_short; cut += d_cut; kept += __popc(bits);
+    if (WRITE)
+      turn_scan_walk<true>(bits, f0, end, n_row, n, g, a.min_frames, a.max_frames, d_short, d_cut, a.table,
+                           at0 + c_scored + ahead, a.cap, row);
+    c_prev = step_last;
+    c_start = max(c_start, newest);
+    c_scored += step_scored;
+  }
+  if (WRITE) return;
+  // the totals: each wave sums its lanes, thread 0 the four waves
+  int part[3] = {shrt, cut, kept};
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) part[k] += __shfl_down(part[k], d, 64);
+    if ((tid & 63) == 0) s_tot[k][tid >> 6] = part[k];
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int* tot = a.totals + 4 * row;
+    tot[0] = c_scored;
+    for (int k = 0; k < 3; ++k) tot[1 + k] = s_tot[k][0] + s_tot[k][1] + s_tot[k][2] + s_tot[k][3];
+    a.row_base[row] = c_scored;
+    int first = -1, frames = 0;
+    if (!a.close_end && (m[n_row - 1] & 1)) {  // the run at the row's end began at c_start; what a cut left of it is open
+      frames = (int)((unsigned)(n_row - c_start) % (unsigned)a.max_frames);
+      first = frames ? n_row - frames : -1;
+    }
+    a.open[2 * row] = first;
+    a.open[2 * row + 1] = frames;
+  }
+}
+
+// row_base[i] <- the sum of row_base[0 .. i), i = 0 .. A, clamped to 2^31 - 1: one workgroup, a contiguous share per thread
+__global__ __launch_bounds__(256) void turn_scan_base_kernel(int* row_base, int A) {
+  __shared__ long long s_sum[256];
+  const int tid = threadIdx.x, per = (A + 255) / 256, lo = min(tid * per, A), hi = min(lo + per, A);
+  long long sum = 0;
+  for (int i = lo; i < hi; ++i) sum += row_base[i];
+  s_sum[tid] = sum;
+  __syncthreads();
+  long long run = 0;
+  for (int t = 0; t < tid; ++t) run += s_sum[t];
+  for (int i = lo; i < hi; ++i) {
+    const int c = row_base[i];
+    row_base[i] = (int)min(run, 0x7fffffffLL);
+    run += c;
+  }
+  if (tid == 255) row_base[A] = (int)min(run, 0x7fffffffLL);  // (the shares end at A: behind the last one `run` is the total)
+}
+
+const char* launch_turn_scan(const unsigned char* mask, const long long* offs, int A, int min_frames, int max_frames,
+                             int close_end, int* table, int cap, int* row_base, int* totals, int* open, hipStream_t s) {
+  if (!mask || !offs || !table || !row_base || !totals || !open) return "turn_scan: null argument";
+  if (A <= 0 || A > 65535) return "turn_scan: 1 to 65535 rows";
+  if (min_frames < 1) return "turn_scan: min_frames is at least 1";
+  if (min_frames > max_frames) return "turn_scan: min_frames is at most max_frames";
+  if (cap < 0) return "turn_scan: a table of 0 or more rows";
+  TurnScanArgs a{mask, offs, table, row_base, totals, open, A, min_frames, max_frames, close_end ? 1 : 0, cap};
+  hipLaunchKernelGGL(turn_scan_kernel<false>, dim3(A), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(turn_scan_base_kernel, dim3(1), dim3(256), 0, s, row_base, A);
+  if (cap > 0) hipLaunchKernelGGL(turn_scan_kernel<true>, dim3(A), dim3(256), 0, s, a);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+// out[r][k] = x[xoffs[row] + first * frame + k mod L], L = (end - first) * frame, k < max_frames * frame, (row, first, end)
+// from table row r, read on the device: a scored turn is contiguous in its recording, so its clip is tiled from the source
+// (turn_collect_kernel's function without the buffers).  Grid (column tiles, R); four samples per lane where frame is a
+// multiple of 4, out is 16-byte aligned and the turn's first sample is; one sample per lane otherwise.  A row that names no
+// turn of its recording writes nothing.
+__global__ __launch_bounds__(256) void turn_clips_kernel(const float* __restrict__ x, const long long* __restrict__ xoffs, int A,
+                                                         int frame, int max_frames, const int* __restrict__ table,
+                                                         float* __restrict__ out, int vec) {
+  const int r = blockIdx.y;
+  const int* t = table + 4 * (long long)r;
+  const int row = t[0], first = t[1], end = t[2];
+  if (row < 0 || row >= A || first < 0 || end <= first || end - first > max_frames) return;
+  const long long x0 = xoffs[row], x1 = xoffs[row + 1];
+  if (x0 < 0 || (long long)end * frame > x1 - x0) return;
+  const int W = max_frames * frame, L = (end - first) * frame;
+  const float* src = x + x0 + (long long)first * frame;
+  float* to = out + (long long)r * W;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x, step = gridDim.x * blockDim.x;
+  if (vec && ((unsigned long long)src & 15ull) == 0) {
+    for (int k = 4 * i; k < W; k += 4 * step)
+      *reinterpret_cast<uint4*>(to + k) = *reinterpret_cast<const uint4*>(src + k % L);
+  } else {
+    for (int k = i; k < W; k += step) to[k] = src[k % L];
+  }
+}
+
+const char* launch_turn_clips(const float* x, const long long* xoffs, int A, int frame, int max_frames, const int* table, int r0,
+                              int R, float* out, hipStream_t s) {
+  if (!x || !xoffs || !table || !out) return "turn_clips: null argument";
+  if (A <= 0) return "turn_clips: no recordings";
+  if (r0 < 0 || R <= 0 || R > 65535) return "turn_clips: 1 to 65535 table rows from row r0 >= 0";
+  if (frame <= 0 || max_frames <= 0 || (long long)max_frames * frame > 0x3fffffff)
+    return "turn_clips: a window of 1 to 2^30 samples in whole frames";
+  const int W = max_frames * frame, vec = frame % 4 == 0 && host_aligned16(out);
+  const int per = vec ? 1024 : 256;
+  hipLaunchKernelGGL(turn_clips_kernel, dim3(min((W + per - 1) / per, 64), R), dim3(256), 0, s, x, xoffs, A, frame, max_frames,
+                     table + 4 * (long long)r0, out, vec);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
 // ---------------------------------------------------------------------------------
 // Cascade (afx/cascade.py; the functions are stated in include/afx.h afx_k_cascade_store / _select / _windows): a cheap
 // screen scores every slot at every hop, and the windows of the slots whose score looks suspicious are gathered for a

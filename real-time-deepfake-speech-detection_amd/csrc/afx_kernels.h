@@ -237,6 +237,17 @@ const char* launch_turn(const float* staging, int S, int ring_len, const unsigne
 // rows (R, 3) = slot, buffer, frames
 const char* launch_turn_collect(const float* bufs, int S, int max_frames, int frame, const int* rows, int R, float* out,
                                 hipStream_t s);
+// the close step of the turn recurrence for A distinct slots (include/afx.h afx_k_turn_close): the end of a call
+const char* launch_turn_close(const int* slots, int A, int S, int min_frames, int max_frames, int* state, int* totals, int* done,
+                              hipStream_t s);
+// turns offline (include/afx.h afx_k_turn_scan): the recurrence over the whole masks of A recordings, packed back to back at
+// offs; table (cap, 4) = row, first, end, flags of the scored turns in order, row_base (A + 1) their exclusive prefix sums
+// per row, totals (A, 4), open (A, 2).  Three launches: count, prefix, write
+const char* launch_turn_scan(const unsigned char* mask, const long long* offs, int A, int min_frames, int max_frames,
+                             int close_end, int* table, int cap, int* row_base, int* totals, int* open, hipStream_t s);
+// the clips of table rows r0 .. r0 + R - 1, tiled from the packed recordings x at xoffs (include/afx.h afx_k_turn_clips)
+const char* launch_turn_clips(const float* x, const long long* xoffs, int A, int frame, int max_frames, const int* table, int r0,
+                              int R, float* out, hipStream_t s);
 // cascade (include/afx.h afx_k_cascade_store / _select / _windows): the named slots' hops into the retained-audio ring; the
 // candidates among the rows ranked by (score, slot), the first `budget` row positions into sel, the cooldown counters
 // advanced; the windows of the rows sel names gathered from the ring (sel is read on the device)
