@@ -265,6 +265,16 @@ int afx_debug_set(const char* key, int value);
  * fp16 device arrays according to `dtype`; fp32 arrays for AFX_DT_FP32 and, in afx_k_gemm / afx_k_mhsa, for
  * AFX_DT_FP16X3: the split-precision forms take and return fp32 -- afx_k_gemm then builds the hi / lo operand forms
  * per call in temporary device memory and synchronises: a test hook) --------------------------------------------- */
+/* out = resid + alpha act(A W^T + bias): A (M, K) with row stride lda, W (N, K) with row stride ldw, resid / out_f fp32 (M, N)
+ * with row strides ldr / ldo_f, out_h operand type (fp32 for the fp32 operand types) with row stride ldo_h; strides count
+ * elements.  Shapes: M >= 1, N % 4 == 0, K % 64 == 0 (fp32: K % 16 == 0; fp16x3: K % 32 == 0 and packed rows, lda == ldw
+ * == K).  Alignment: the kernels read 16 bytes of an operand row at a time and read and write fp32 rows 16 bytes at a
+ * time, so every row must START on a 16-byte boundary: A, W, bias, resid, out_f 16-byte aligned, lda % 8 == 0 and ldw % 8 ==
+ * 0 for the half types (% 4 for fp32), ldr % 4 == 0, ldo_f % 4 == 0.  out_h is written 8 halfs at a time where N % 8 == 0
+ * (out_h 16-byte aligned, ldo_h % 8 == 0) and 4 at a time otherwise (8-byte aligned, ldo_h % 4 == 0); as fp32: 16-byte
+ * aligned, ldo_h % 4 == 0.  Nothing is read past column K of a row, past row M - 1 of A / resid or row N - 1 of W, and
+ * nothing is written outside the M x N elements of an output.  A violation of the shape or alignment rules: non-zero,
+ * afx_last_error names `gemm`, nothing launched. */
 int afx_k_gemm(int dtype, const void* A, long lda, const void* W, long ldw, int M, int N, int K, const float* bias,
                int act, float alpha, const float* resid, long ldr, float* out_f, long ldo_f, void* out_h, long ldo_h,
                void* stream);
@@ -802,6 +812,10 @@ int afx_k_evidence_copy(const float* x, const float* scores, int stride, const i
 int afx_k_quality(const float* x, long long stride, int A, int hop, const int* hdr, const float* scores, int sstride,
                   float clip, int clip_count, int flat_run, float e_quiet, float dc, int mask, int max_bad, int abstain,
                   unsigned char* ring, int W, int* state, int* totals, int S, int* meas, float* out, void* stream);
+/* Row LayerNorm (+ activation) of fp32 rows: 0 < C <= 1024, C % 4 == 0, any rows >= 1; out_f and / or out_h.  ldx, ldo_f,
+ * ldo_h count elements (>= C).  A lane reads and writes 4 columns at a time, so rows must be aligned to that access: x,
+ * gamma, beta, out_f 16-byte aligned with ldx % 4 == 0 and ldo_f % 4 == 0; out_h 8-byte aligned (16 for the fp32 operand
+ * types) with ldo_h % 4 == 0.  A violation: non-zero, afx_last_error names `rownorm`, nothing launched. */
 int afx_k_rownorm(int dtype, const float* x, long ldx, int rows, int C, const float* gamma, const float* beta,
                   float eps, int act, float* out_f, long ldo_f, void* out_h, long ldo_h, void* stream);
 int afx_k_mhsa(int dtype, const void* qkv, void* out, int B, int T, int H, void* stream);

@@ -108,6 +108,17 @@ ulps of one sign -- a correct kernel reads -0.39 ulp on conv 1 of a GroupNorm'd 
 of the silence row are taken out).  ``check(..., unique_rows=True, rounding_only=True)`` restricts the statistic to the
 first of equal rows and to store-dominated elements; both default to off, the call-audio tests pass both and assert from
 16 384 remaining elements on (tests/test_cpu_insitu_call.py has the figures and shows a truncating store still fails).
+
+The single-kernel entry points at the edges of their contract (oracle/kernel_edges.py: M around every tile height, ragged
+last column blocks, the narrow-store fallback, 1 / 2 / 3 / 5 K-tiles, padded strides, NaN pools around the operands and guard
+patterns around the outputs; tests/test_gpu_kernel_edges.py) are judged with every constant unchanged; ``product`` gained
+``act="selu"`` from ``selu`` / ``selu_err``.  Its summary on an MI355X, worst ratio fp16 / bf16 / fp16x3: edge_gemm, the lean
+epilogue on every tile instance (0, 1, 2, 7, 75, 76, 77, 92) 0.498 / 0.500 / 0.051, non-lean (swish, SELU) 0.499 / 0.500 / 0.219,
+narrow-store 0.499 / 0.500 / 0.272, fp32 0.170 / 0.289 / 0.304 for the three forms; edge_conv 0.056 / 0.052, fp32 0.148;
+edge_convln (instances 3, 8, 82, 83) 0.485 / 0.498; edge_rownorm 0.494 / 0.499 / 0.021, fp32 0.029, the two-rows-per-wave form
+0.494 / 0.499 / 0.022, fp32 0.041.  Bias (fp16 / bf16, asserted per instance and epilogue form, ``rounding_only``): every
+edge_gemm class within +-0.0005 ulp over 4.0 M .. 19.5 M elements, edge_convln -0.0006 / +0.0018 (1.17 M / 1.32 M per instance),
+edge_rownorm -0.0005 / +0.0009 (526 k / 571 k), two-row form -0.0008 / +0.0005 (1.16 M / 1.25 M).  No launch was found wrong.
 """
 import math
 
@@ -194,14 +205,17 @@ def linear(a, w, b, dt):
 def product(a, w, b, dt, act=None, alpha=1.0, resid=None, out="f32"):
     """GEMM launch: out = resid + alpha act(a w^T + b), fp32 (out="f32") or operand type (out="op")."""
     z, s = linear(a, w, b, dt)
-    if act == "gelu":
-        y, g = gelu(z), dgelu(z)
-    elif act == "swish":
-        y, g = swish(z), dswish(z)
+    if act == "selu":  # (the device's expf form: C_FN ulps of e^z through ``selu_err``, no polynomial term)
+        y, e = alpha * selu(z), alpha * selu_err(z, C_ACC[dt] * s)
     else:
-        y, g = z, torch.ones_like(z)
-    y = alpha * y
-    e = alpha * (C_ACC[dt] * s * g + (C_POLY * (1 + z.abs()) if act else 0))
+        if act == "gelu":
+            y, g = gelu(z), dgelu(z)
+        elif act == "swish":
+            y, g = swish(z), dswish(z)
+        else:
+            y, g = z, torch.ones_like(z)
+        y = alpha * y
+        e = alpha * (C_ACC[dt] * s * g + (C_POLY * (1 + z.abs()) if act else 0))
     if resid is not None:
         y = y + resid
         e = e + C_ACC[dt] * resid.abs()

@@ -1,5 +1,6 @@
 """Python faces of the single-kernel C entry points (afx_k_*), used by the unit
-parity tests.  All tensors must be contiguous CUDA tensors; ``dtype`` is "bf16" or
+parity tests.  All tensors must be contiguous CUDA tensors (``gemm`` and ``rownorm`` also take row-strided views with unit
+column stride, and preallocated outputs: tests/test_gpu_kernel_edges.py); ``dtype`` is "bf16" or
 "fp16" and names the matrix-core operand type of the half-precision arguments."""
 import torch
 
@@ -9,15 +10,29 @@ from .engine import DTYPES, torch_dtype
 ACTS = {None: ACT_NONE, "gelu": ACT_GELU, "swish": ACT_SWISH, "selu": ACT_SELU}
 
 
+def _out(out, shape, dtype, device):
+    """An output argument: False / None -> no output, True -> a new packed tensor, a tensor -> that one (a 2-D view with
+    unit column stride; its row stride is passed on as the leading dimension)."""
+    if out is None or out is False:
+        return None
+    if out is True:
+        return torch.empty(*shape, dtype=dtype, device=device)
+    assert out.dtype == dtype and tuple(out.shape) == tuple(shape) and out.stride(-1) == 1, (out.dtype, out.shape, out.stride())
+    return out
+
+
 def gemm(dtype, A, W, bias=None, act=None, alpha=1.0, resid=None, out_f=True, out_h=False):
     """A (M,K) half, W (N,K) half -> fp32 and/or half (M,N).  dtype "fp16x3" (split precision): A and W are FP32 and the
-    "operand type" output is fp32 too; the entry point builds the hi / lo operand forms per call (test hook)."""
+    "operand type" output is fp32 too; the entry point builds the hi / lo operand forms per call (test hook).
+    A, W, resid and the outputs may be row-strided views (unit column stride): their row strides are passed on as lda, ldw,
+    ldr, ldo_f, ldo_h.  out_f / out_h: True = a new packed tensor, a tensor = written in place and returned."""
     M, K = A.shape
     N = W.shape[0]
-    of = torch.empty(M, N, dtype=torch.float32, device=A.device) if out_f else None
-    oh = torch.empty(M, N, dtype=torch_dtype(dtype), device=A.device) if out_h else None
+    of = _out(out_f, (M, N), torch.float32, A.device)
+    oh = _out(out_h, (M, N), torch_dtype(dtype), A.device)
     check(call_on(A, lib().afx_k_gemm, DTYPES[dtype], ptr(A), A.stride(0), ptr(W), W.stride(0), M, N, K, ptr(bias), ACTS[act],
-                           alpha, ptr(resid), N, ptr(of), N, ptr(oh), N))
+                           alpha, ptr(resid), N if resid is None else resid.stride(0), ptr(of), N if of is None else of.stride(0),
+                           ptr(oh), N if oh is None else oh.stride(0)))
     return of, oh
 
 
@@ -36,22 +51,30 @@ def pack_conv(dtype, w):
     return out
 
 
-def conv_gemm(dtype, x_h, wp, k, s, bias=None):
-    """x_h (B,Tin,Cin) half channel-last, wp (N,k*Cin) packed -> (B,Tout,N) fp32."""
+def _packed(out, shape, dtype, device):
+    """As _out, for the entry points that take no leading dimension: a given tensor must be contiguous."""
+    out = _out(out, shape, dtype, device)
+    assert out is None or out.is_contiguous()
+    return out
+
+
+def conv_gemm(dtype, x_h, wp, k, s, bias=None, out=True):
+    """x_h (B,Tin,Cin) half channel-last, wp (N,k*Cin) packed -> (B,Tout,N) fp32 (out: a contiguous tensor to write into)."""
     B, Tin, Cin = x_h.shape
     N = wp.shape[0]
     Tout = (Tin - k) // s + 1
-    out = torch.empty(B, Tout, N, dtype=torch.float32, device=x_h.device)
+    out = _packed(out, (B, Tout, N), torch.float32, x_h.device)
     check(call_on(x_h, lib().afx_k_conv_gemm, DTYPES[dtype], ptr(x_h), ptr(wp), B, Tin, Tout, Cin, k, s, N, ptr(bias), ptr(out)))
     return out
 
 
 def conv_ln_act(dtype, x_h, wp, k, s, bias, gamma, beta, act="gelu", eps=1e-5, out_f=False, out_h=True):
-    """Conv1d(512->512,k,s) + LayerNorm(512) + activation in one kernel; x_h (B,Tin,512) half."""
+    """Conv1d(Cin->512,k,s) + LayerNorm(512) + activation in one kernel; x_h (B,Tin,Cin) half.  out_f / out_h: True = a new
+    tensor, a contiguous (B,Tout,512) tensor = written in place."""
     B, Tin, Cin = x_h.shape
     Tout = (Tin - k) // s + 1
-    of = torch.empty(B, Tout, 512, dtype=torch.float32, device=x_h.device) if out_f else None
-    oh = torch.empty(B, Tout, 512, dtype=torch_dtype(dtype), device=x_h.device) if out_h else None
+    of = _packed(out_f, (B, Tout, 512), torch.float32, x_h.device)
+    oh = _packed(out_h, (B, Tout, 512), torch_dtype(dtype), x_h.device)
     check(call_on(x_h, lib().afx_k_conv_ln_act, DTYPES[dtype], ptr(x_h), ptr(wp), B, Tin, Tout, Cin, k, s, ptr(bias), ptr(gamma),
                                   ptr(beta), eps, ACTS[act], ptr(of), ptr(oh)))
     return of, oh
@@ -84,11 +107,12 @@ def conv0_packed(dtype, wave, pack, w, bias, gamma, beta, pre_emph=False, coef=0
 
 
 def rownorm(dtype, x, gamma, beta, eps=1e-5, act=None, out_f=True, out_h=False):
+    """x (rows, C) fp32, a row-strided view allowed (ldx = its row stride); out_f / out_h as in gemm."""
     rows, Cc = x.shape
-    of = torch.empty(rows, Cc, dtype=torch.float32, device=x.device) if out_f else None
-    oh = torch.empty(rows, Cc, dtype=torch_dtype(dtype), device=x.device) if out_h else None
+    of = _out(out_f, (rows, Cc), torch.float32, x.device)
+    oh = _out(out_h, (rows, Cc), torch_dtype(dtype), x.device)
     check(call_on(x, lib().afx_k_rownorm, DTYPES[dtype], ptr(x), x.stride(0), rows, Cc, ptr(gamma), ptr(beta), eps, ACTS[act],
-                              ptr(of), Cc, ptr(oh), Cc))
+                              ptr(of), Cc if of is None else of.stride(0), ptr(oh), Cc if oh is None else oh.stride(0)))
     return of, oh
 
 

@@ -3355,6 +3355,12 @@ __global__ __launch_bounds__(256) void rownorm_kernel(RowNormArgs a) {
 const char* launch_rownorm(const RowNormArgs& a, int dtype, hipStream_t s) {
   if (a.rows <= 0 || a.C <= 0 || a.C > 1024 || a.C % 4) return "rownorm: need 0 < C <= 1024, C % 4 == 0";
   if (!a.out_f && !a.out_h) return "rownorm: no output";
+  // a lane reads and writes 4 columns at a time: 16 bytes of an fp32 row, 8 bytes of a half row
+  if (((size_t)a.x & 15) || (a.ldx & 3) || ((size_t)a.gamma & 15) || ((size_t)a.beta & 15))
+    return "rownorm: input rows must start on 16-byte boundaries (x, gamma, beta 16-byte aligned; ldx % 4 == 0)";
+  if (a.out_f && (((size_t)a.out_f & 15) || (a.ldo_f & 3))) return "rownorm: fp32 output rows must start on 16-byte boundaries (out_f 16-byte aligned, ldo_f % 4 == 0)";
+  if (a.out_h && (((size_t)a.out_h & (dtype == DT_FP32 || dtype == DT_FP16X3 ? 15 : 7)) || (a.ldo_h & 3)))
+    return "rownorm: operand-type output rows must start on the store's boundary (halfs: out_h 8-byte aligned, fp32: 16-byte; ldo_h % 4 == 0)";
   // two rows per wave once there are enough rows to keep 8+ waves on every CU; below that (the teacher's
   // 16 x 199 rows) one row per wave = twice the waves in flight, which is what this latency-bound size lacks
   if (a.rows >= 16384) {

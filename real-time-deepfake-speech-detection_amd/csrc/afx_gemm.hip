@@ -1771,6 +1771,22 @@ static const char* check_gemm(const GemmArgs& p, int groups) {
     if (((size_t)p.A & 15) || ((size_t)p.W & 15) || (p.a_row & 63) || (p.a_batch & 63) || (p.g_a & 63) || (p.ldw & 63) || (p.g_w & 63) || (p.kchunk_stride & 63))
       return "gemm: split precision: pair-form rows start on whole 32-element groups";
   }
+  // Alignment: the loaders read 16 bytes of a row at a time, the epilogues read and write fp32 rows 16 bytes at a time and
+  // operand-type rows 16 bytes at a time where N % 8 == 0, 8 bytes in the narrow-store fallback.  A row is aligned when its
+  // base pointer and every stride that leads to it are (include/afx.h states this for afx_k_gemm).
+  if (!p.k1 && (((size_t)p.A & 15) || ((size_t)p.W & 15) || (p.a_row & 7) || (p.a_batch & 7) || (p.g_a & 7) || (p.ldw & 7) || (p.g_w & 7) || (p.kchunk_stride & 7)))
+    return "gemm: operand rows must start on 16-byte boundaries (A, W 16-byte aligned; lda, ldw and every batch / chunk / group stride % 8 == 0)";
+  if (((size_t)p.bias & 15) || (p.ln_gamma && (((size_t)p.ln_gamma & 15) || ((size_t)p.ln_beta & 15))))
+    return "gemm: bias (and LayerNorm gamma / beta) must be 16-byte aligned";
+  if (p.resid && (((size_t)p.resid & 15) || (p.ldr & 3))) return "gemm: residual rows must start on 16-byte boundaries (resid 16-byte aligned, ldr % 4 == 0)";
+  if (p.out_f && (((size_t)p.out_f & 15) || (p.ldo_f & 3))) return "gemm: fp32 output rows must start on 16-byte boundaries (out_f 16-byte aligned, ldo_f % 4 == 0)";
+  if (p.out_h) {
+    const bool wide = !p.k1 && (p.N & 7) == 0;  // 8 halfs per store; fp32 (split precision) and the narrow fallback: 4 elements
+    if (((size_t)p.out_h & (p.k1 || wide ? 15 : 7)) || (p.ldo_h & (wide ? 7 : 3)))
+      return "gemm: operand-type output rows must start on the store's boundary (16 bytes: ldo_h % 8 == 0 for halfs with N % 8 == 0, % 4 == 0 for fp32; 8 bytes: ldo_h % 4 == 0 for halfs with N % 8 != 0)";
+    if (groups > 1 && wide && (p.g_n & 7)) return "gemm: the column offset per group must keep operand-type stores on 16-byte boundaries (g_n % 8 == 0)";
+  }
+  if (groups > 1 && (p.g_n & 3)) return "gemm: the column offset per group must be a multiple of 4";
   if (p.ln_gamma) {
     if (p.N != 512 || groups != 1) return "gemm: the fused LayerNorm epilogue needs N == 512 (row-complete tile)";
     if (!p.ln_beta || !p.bias || p.resid || p.alpha != 1.f) return "gemm: fused LayerNorm epilogue: bias + LN + act only";

@@ -106,6 +106,13 @@ const char* launch_gemm_f32(const GemmArgs& p, int groups, hipStream_t s) {
   if (p.ln_gamma) return "gemm(fp32): the fused LayerNorm epilogue is a half-precision tile feature";
   if (!p.out_f && !p.out_h) return "gemm(fp32): no output";
   if (p.rpb <= 0) return "gemm(fp32): rows per batch must be positive";
+  // every access is 4 floats of one row: a row is aligned when its base pointer and the strides that lead to it are
+  if (((size_t)p.A & 15) || ((size_t)p.W & 15) || (p.a_row & 3) || (p.a_batch & 3) || (p.g_a & 3) || (p.ldw & 3) || (p.g_w & 3) || (p.kchunk_stride & 3))
+    return "gemm(fp32): operand rows must start on 16-byte boundaries (A, W 16-byte aligned; lda, ldw and every batch / chunk / group stride % 4 == 0)";
+  if (((size_t)p.bias & 15) || (groups > 1 && (p.g_n & 3))) return "gemm(fp32): bias must be 16-byte aligned, the column offset per group a multiple of 4";
+  if (p.resid && (((size_t)p.resid & 15) || (p.ldr & 3))) return "gemm(fp32): residual rows must start on 16-byte boundaries (resid 16-byte aligned, ldr % 4 == 0)";
+  if (p.out_f && (((size_t)p.out_f & 15) || (p.ldo_f & 3))) return "gemm(fp32): fp32 output rows must start on 16-byte boundaries (out_f 16-byte aligned, ldo_f % 4 == 0)";
+  if (p.out_h && (((size_t)p.out_h & 15) || (p.ldo_h & 3))) return "gemm(fp32): operand-type output rows must start on 16-byte boundaries (out_h 16-byte aligned, ldo_h % 4 == 0)";
   const long mt = (p.M + 127) / 128;
   // 128-column tiles unless that leaves the 256 CUs under two workgroups each
   if (p.N > 64 && mt * ((p.N + 127) / 128) * groups >= 512)
