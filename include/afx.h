@@ -243,7 +243,8 @@ int afx_engine_set(afx_handle h, const char* key, int value);
 int afx_engine_get(afx_handle h, const char* key, int* value);
 /* The launch plan of a half- or split-precision product, host arithmetic only (no device, no handle).  rpb / kchunk: 0 = M / K
  * (a plain product).  flags: 1 fused LayerNorm epilogue (N = 512), 2 split precision, 4 an activation outside the lean
- * epilogue, 8 never the deep 128x64 tile.  objective: 0 makespan, 1 CU time, -1 the calling thread's.  out[8]: tile family,
+ * epilogue, 8 never the deep 128x64 tile.  objective: 0 makespan, 1 CU time, -1 what a launch outside any forward gets (the
+ * forced "dispatch_objective" knob when it is set, else makespan; no call leaves an objective behind).  out[8]: tile family,
  * instance, tile rows, tile slots, rows of the first launch when split (else 0), the remainder's instance, its tile slots,
  * the objective used.  afx_conf_chain_waves: waves per workgroup of a fused Conformer chain over M token rows. */
 int afx_gemm_plan(int M, int N, int K, int rpb, int kchunk, int groups, int flags, int objective, int* out);

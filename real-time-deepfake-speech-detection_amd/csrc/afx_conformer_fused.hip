@@ -528,7 +528,7 @@ const char* launch_conf_chain(const ConfChainArgs& p, int stage, int dtype, hipS
   if (p.E != 16 * ET || p.Ep < 32 * EK || p.FFp != 4 * 16 * ET) return "conf_chain: the fused Conformer chains are built for emb 144 / ff 576";
   if (dtype == DT_FP32) return "conf_chain: half-precision operands only";
   if (p.M <= 0 || stage < 0 || stage > 2) return "conf_chain: bad arguments";
-  const bool w8 = conf_chain_waves_of(p.M, dispatch_objective()) == 8;
+  const bool w8 = conf_chain_waves_of(p.M, dispatch_objective(p.objective)) == 8;
   hipError_t e;
   if (dtype == DT_FP16X3)
     e = w8 ? launch_conf_chain_s<FP16, true, 8>(p, stage, s) : launch_conf_chain_s<FP16, true, 4>(p, stage, s);

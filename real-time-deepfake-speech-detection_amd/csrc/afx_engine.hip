@@ -209,7 +209,7 @@ extern "C" int afx_create(const afx_config* cfg, afx_handle* out) {
   afx_engine* e = new afx_engine();
   e->cfg = *cfg;
   // split precision: activations and every non-GEMM kernel as in exact mode (fp32); the dense products on the fp16 matrix
-  // pipe with hi / lo operand pairs (P_gemm below).  A weight element is 4 bytes either way (fp32, or an fp16 hi + lo pair).
+  // pipe with hi / lo operand pairs (Call::gemm below).  A weight element is 4 bytes either way (fp32, or an fp16 hi + lo pair).
   e->s3 = cfg->dtype == AFX_DT_FP16X3;
   e->dt = e->s3 ? (int)DT_FP32 : cfg->dtype;
   e->hsz = dtype_size(e->dt);
@@ -766,7 +766,6 @@ extern "C" size_t afx_workspace_bytes(afx_handle h, int B, int L) {
   return carve(h, B, L, 0, nullptr, &w);
 }
 
-static float s3_pairs_in(const void* p);
 // ---------------------------------------------------------------------------------
 // taps (debug): engine-owned fp32 copies of intermediates
 // ---------------------------------------------------------------------------------
@@ -793,30 +792,6 @@ __global__ void pairs_to_f32_kernel(const uint16_t* in, float* out, size_t n, lo
     memcpy(&lo, &row[s3_pair_index(k) + 32], 2);
     out[i] = ((float)hi + (float)lo) * inv_scale;
   }
-}
-// is_half: `src` is an operand buffer (operand type; split precision: fp32 rows or pair-form rows of stride ld elements)
-static int tap(afx_engine* e, const char* name, const void* src, size_t n, bool is_half, hipStream_t s, long ld = 0) {
-  if (!e->taps_on) return 0;
-  TapRec& t = e->taps[name];
-  if (t.cap < n) {
-    if (t.p) (void)hipFree(t.p);
-    HIP_OK(hipMalloc((void**)&t.p, n * 4));
-    t.cap = n;
-  }
-  t.n = n;
-  const float pair_scale = is_half && e->s3 ? s3_pairs_in(src) : 0.f;
-  if (pair_scale != 0.f) {
-    if (ld <= 0 || ld % 32 || n % ld) return fail("tap '%s': pair-form rows need a row stride that is a multiple of 32", name);
-    hipLaunchKernelGGL(pairs_to_f32_kernel, dim3(1024), dim3(256), 0, s, (const uint16_t*)src, t.p, n, ld, 1.0f / pair_scale);
-    HIP_OK(hipGetLastError());
-  } else if (is_half && e->dt != AFX_DT_FP32) {
-    hipLaunchKernelGGL(half_to_f32_kernel, dim3(1024), dim3(256), 0, s, (const uint16_t*)src, t.p, n,
-                       e->dt == AFX_DT_BF16 ? 1 : 0);
-    HIP_OK(hipGetLastError());
-  } else {
-    HIP_OK(hipMemcpyAsync(t.p, src, n * 4, hipMemcpyDeviceToDevice, s));
-  }
-  return 0;
 }
 extern "C" int afx_tap(afx_handle h, const char* name, float* out, size_t cap, size_t* n_out, void* stream) {
   if (!h || !name) return fail("afx_tap: null argument");
@@ -855,44 +830,6 @@ struct Profiler {
     return pool[used++];
   }
 };
-static thread_local Profiler* t_prof = nullptr;  // the profiler of the engine whose forward runs on this thread
-// split precision: the plane scratch of the workspace the forward on this thread runs in (null: another mode)
-static thread_local void* t_s3planes = nullptr;
-static thread_local size_t t_s3bytes = 0;
-// Operand buffers whose ONLY readers are dense products may receive their producer's result directly as the product's A
-// operand (the PAIR FORM of the row -- afx_kernels.h -- in place of its fp32 values: same bytes, row by row) -- the LayerNorms,
-// the GELU / LayerNorm epilogues of the products and the attention write the operand themselves and the separate split launch
-// disappears.  t_s3ok: the buffers of this forward that qualify; t_s3reg: which of them currently hold pair-form rows.
-constexpr int kS3Bufs = 10;
-struct S3Reg { const void* p; float scale; };  // scale: the power of two the rows were multiplied by before the split (0: fp32 values)
-static thread_local const void* t_s3ok[kS3Bufs] = {nullptr};
-static thread_local S3Reg t_s3reg[kS3Bufs] = {};
-static void s3_begin(std::initializer_list<const void*> ok) {
-  int i = 0;
-  for (const void* p : ok)
-    if (p && i < kS3Bufs) t_s3ok[i++] = p;
-  for (; i < kS3Bufs; ++i) t_s3ok[i] = nullptr;
-  for (S3Reg& r : t_s3reg) r = S3Reg{nullptr, 0.f};
-}
-static bool s3_ok(const void* p) {
-  if (!p || !t_s3planes) return false;
-  for (const void* q : t_s3ok) if (q == p) return true;
-  return false;
-}
-static void s3_set(const void* p, float scale) {  // 0: the buffer holds fp32 values again
-  for (S3Reg& r : t_s3reg) if (r.p == p) { r.scale = scale; if (scale == 0.f) r.p = nullptr; return; }
-  if (scale == 0.f) return;
-  for (S3Reg& r : t_s3reg) if (!r.p) { r = S3Reg{p, scale}; return; }
-}
-static float s3_pairs_in(const void* p) {  // the scale of the pair-form rows `p` holds, 0 when it holds fp32 values
-  for (const S3Reg& r : t_s3reg) if (r.p && r.p == p) return r.scale;
-  return 0.f;
-}
-// per-call context of the forward running on this thread: the engine's profiler, its A/B switches, and (split precision) the
-// pair-form scratch of the workspace plus the buffers whose producers may write pair-form rows in place
-static thread_local int t_no_deep = 0;
-static thread_local const std::unordered_map<const float*, float>* t_ln_scale = nullptr;
-static void begin_call(afx_engine* e, const Ws* w);
 static void prof_forget(afx_engine* e) {
   if (!e->prof) return;
   for (hipEvent_t ev : e->prof->pool) (void)hipEventDestroy(ev);
@@ -900,35 +837,94 @@ static void prof_forget(afx_engine* e) {
   e->prof = nullptr;
 }
 
-template <class F>
-static const char* timed(int cls, double flops, hipStream_t s, F&& f) {
-  Profiler* p = t_prof;
-  if (!p || !p->on) return f();
-  hipEvent_t a = p->ev(), b = p->ev();
-  if (!a || !b) return "profiler: hipEventCreate failed";
-  (void)hipEventRecord(a, s);
-  const char* m = f();
-  (void)hipEventRecord(b, s);
-  p->recs.push_back({cls, a, b, flops});
-  return m;
-}
-// Split precision (P_gemm below): x.w ~ xh.wl + xl.wh + xh.wh on the fp16 matrix pipe.  Both operands go in PAIR FORM
+// ---------------------------------------------------------------------------------
+// The call context: ONE native call on ONE handle.  Every entry point that launches builds a Call on its stack and hands it
+// by reference to whatever launches for it; nothing here is shared between calls, handles or threads, and nothing of it
+// outlives the call except the handle's `last_objective` read-back.  It holds the stream, the launch-shape objective (read
+// once from the handle's "concurrent" switch: fixed for the whole call), the handle's profiler, and -- split precision -- the
+// pair-form scratch of the workspace the call runs in with the registry below.  The engine's other switches ("gemm_small_deep",
+// the LayerNorm scales) are read from `e` where they are used.
+// Pair-form registry: operand buffers whose ONLY readers are dense products may receive their producer's result directly as
+// the product's A operand (the PAIR FORM of the row -- afx_kernels.h -- in place of its fp32 values: same bytes, row by row) --
+// the LayerNorms, the GELU / LayerNorm epilogues of the products and the attention write the operand themselves and the
+// separate split launch disappears.  s3ok: the buffers of this call that qualify; s3reg: which of them currently hold
+// pair-form rows.
+// ---------------------------------------------------------------------------------
+constexpr int kS3Bufs = 10;
+struct S3Reg { const void* p; float scale; };  // scale: the power of two the rows were multiplied by before the split (0: fp32 values)
+struct Call {
+  afx_engine* const e;
+  const hipStream_t s;
+  const int objective;   // OBJ_*: every product and chain of the call is shaped for it (GemmArgs / ConfChainArgs::objective)
+  Profiler* const prof;
+  void* const s3planes;  // null: not a split-precision engine
+  const size_t s3bytes;
+  const void* s3ok[kS3Bufs] = {nullptr};
+  S3Reg s3reg[kS3Bufs] = {};
+
+  Call(afx_engine* e_, void* stream, void* planes = nullptr, size_t bytes = 0, std::initializer_list<const void*> ok = {})
+      : e(e_), s((hipStream_t)stream), objective(e_->concurrent ? OBJ_CU_TIME : OBJ_MAKESPAN), prof(e_->prof), s3planes(planes), s3bytes(bytes) {
+    e->last_objective = dispatch_objective(objective);
+    int i = 0;
+    for (const void* p : ok)
+      if (p && i < kS3Bufs) s3ok[i++] = p;
+  }
+  Call(afx_engine* e_, void* stream, const Ws& w)
+      : Call(e_, stream, w.s3planes, w.s3bytes, {w.bufA, w.bufB, w.feats_h, w.hbuf, w.att, w.ff, w.xpad, w.hc, w.ssl_h, w.hid}) {}
+  Call(const Call&) = delete;
+
+  bool s3_ok(const void* p) const {
+    if (!p || !s3planes) return false;
+    for (const void* q : s3ok) if (q == p) return true;
+    return false;
+  }
+  void s3_set(const void* p, float scale) {  // 0: the buffer holds fp32 values again
+    for (S3Reg& r : s3reg) if (r.p == p) { r.scale = scale; if (scale == 0.f) r.p = nullptr; return; }
+    if (scale == 0.f) return;
+    for (S3Reg& r : s3reg) if (!r.p) { r = S3Reg{p, scale}; return; }
+  }
+  float s3_pairs_in(const void* p) const {  // the scale of the pair-form rows `p` holds, 0 when it holds fp32 values
+    for (const S3Reg& r : s3reg) if (r.p && r.p == p) return r.scale;
+    return 0.f;
+  }
+  // the scale a LayerNorm's output takes as a pair-form operand: what finalize chose for its gamma (afx_engine::ln_scale)
+  float ln_scale(const float* gamma) const {
+    auto it = e->ln_scale.find(gamma);
+    return it != e->ln_scale.end() ? it->second : kS3ScaleBounded;
+  }
+
+  template <class F>
+  const char* timed(int cls, double flops, F&& f) {
+    if (!prof || !prof->on) return f();
+    hipEvent_t a = prof->ev(), b = prof->ev();
+    if (!a || !b) return "profiler: hipEventCreate failed";
+    (void)hipEventRecord(a, s);
+    const char* m = f();
+    (void)hipEventRecord(b, s);
+    prof->recs.push_back({cls, a, b, flops});
+    return m;
+  }
+  const char* gemm(const GemmArgs& g_in, int dt, int groups, bool rows = false);
+  const char* rownorm(const RowNormArgs& a_in, int dt);
+};
+// Split precision (Call::gemm): x.w ~ xh.wl + xl.wh + xh.wh on the fp16 matrix pipe.  Both operands go in PAIR FORM
 // (afx_kernels.h): the weight is stored that way with per-row scales behind it (pack_linear), the fp32 A operand is either
 // already there (its producer wrote pair-form rows in place: s3_pairs_in) or the span the product addresses is converted into
 // the workspace's scratch; ONE launch then walks the 2 K halfs of a row like a plain fp16 operand and issues three matrix
 // instructions per K-step on the fragments it reads anyway (round 3 walked K three times over separate hi / lo planes: 1.5x
 // the K-tiles, operand bytes and fragment reads for the same matrix-pipe work).
 // rows: the product goes to launch_gemm_rows (GemmArgs::oh_rows holds its output row table)
-static const char* P_gemm(const GemmArgs& g_in, int dt, int groups, hipStream_t s, bool rows = false) {
+const char* Call::gemm(const GemmArgs& g_in, int dt, int groups, bool rows) {
   GemmArgs g = g_in;
-  g.no_deep = t_no_deep;  // (the engine's "gemm_small_deep" switch)
+  g.no_deep = e->gemm_small_deep ? 0 : 1;
+  g.objective = objective;
   const double fl = 2.0 * g.M * g.N * (g.k_algo ? g.k_algo : g.K) * groups;
   // profiler class of a tile id (afx_gemm.hip::gemm_tile_of): 92 = the deep form of the 128x64 tile, a class of its own
   auto cls_of = [](int tile) -> int {
     static const int cls[9] = {PC_GEMM128, PC_GEMM64, PC_GEMM256, PC_GEMM_ROWLN, PC_GEMM256, PC_GEMM256, PC_GEMM_ROWLN, PC_GEMM8_256, PC_GEMM8_ROWLN};
     return tile == 92 ? PC_GEMM64_DEEP : (tile >= 0 && tile < 9 ? cls[tile] : PC_GEMM128);
   };
-  if (dt == DT_FP32 && t_s3planes) {
+  if (dt == DT_FP32 && s3planes) {
     const bool groups32 = !(g.K % 32 || g.kchunk % 32 || g.a_row % 32 || g.a_batch % 32 || g.g_a % 32 || g.kchunk_stride % 32 || g.ldw % 32 || g.g_w % 32);
     if (!groups32 || ((size_t)g.A & 15)) {  // (rows the pair form cannot address in whole 32-element groups: the fp32 instruction)
       if (rows) return "split-precision product with a row table: the operands must be pair-form addressable";
@@ -942,10 +938,10 @@ static const char* P_gemm(const GemmArgs& g_in, int dt, int groups, hipStream_t 
       long span = (last / g.rpb) * g.a_batch + (last % g.rpb) * g.a_row + (long)(g.K / g.kchunk - 1) * g.kchunk_stride + g.kchunk +
                   (long)(groups - 1) * g.g_a;
       span = (span + 31) & ~31L;
-      if ((size_t)span * 4 > t_s3bytes) return "split-precision product: the A operand exceeds the pair-form scratch";
+      if ((size_t)span * 4 > s3bytes) return "split-precision product: the A operand exceeds the pair-form scratch";
       a_scale = kS3ScaleFree;
-      if (const char* m = timed(PC_MISC, 0, s, [&] { return launch_split_pairs((const float*)g.A, span, t_s3planes, a_scale, s); })) return m;
-      q.A = t_s3planes;
+      if (const char* m = timed(PC_MISC, 0, [&] { return launch_split_pairs((const float*)g.A, span, s3planes, a_scale, s); })) return m;
+      q.A = s3planes;
     }
     // every K-side length counts halfs of the pair form: twice the fp32-element value
     q.k1 = g.K;
@@ -969,37 +965,48 @@ static const char* P_gemm(const GemmArgs& g_in, int dt, int groups, hipStream_t 
       s3_set(g.out_h, pairs_out ? q.oh_scale : 0.f);
     }
     const int tile = gemm_tile_of(q, groups);
-    return timed(cls_of(tile), fl, s, [&] { return rows ? launch_gemm_rows(q, DT_FP16X3, s) : launch_gemm(q, DT_FP16X3, groups, s); });
+    return timed(cls_of(tile), fl, [&] { return rows ? launch_gemm_rows(q, DT_FP16X3, s) : launch_gemm(q, DT_FP16X3, groups, s); });
   }
   if (rows && (dt == DT_FP32 || groups != 1)) return "gemm with a row table: half- or split-precision operands, one group";
-  return timed(dt == DT_FP32 ? PC_GEMM_F32 : cls_of(gemm_tile_of(g, groups)), fl, s,
+  return timed(dt == DT_FP32 ? PC_GEMM_F32 : cls_of(gemm_tile_of(g, groups)), fl,
                [&] { return rows ? launch_gemm_rows(g, dt, s) : launch_gemm(g, dt, groups, s); });
 }
-static const char* P_rownorm(const RowNormArgs& a_in, int dt, hipStream_t s) {
+const char* Call::rownorm(const RowNormArgs& a_in, int dt) {
   RowNormArgs a = a_in;
-  if (a.out_h && t_s3planes) {  // split precision: the LayerNorm writes the next product's A operand (pair-form rows) itself
+  if (a.out_h && s3planes) {  // split precision: the LayerNorm writes the next product's A operand (pair-form rows) itself
     const bool pairs_out = dt == DT_FP32 && s3_ok(a.out_h) && (a.ldo_h & 31) == 0 && a.out_h != (const void*)a.x;
     a.oh_pairs = pairs_out ? 1 : 0;
-    a.oh_scale = kS3ScaleBounded;  // |LayerNorm output| <= sqrt(C) max|gamma| + max|beta|: the scale finalize chose for this LayerNorm
-    if (t_ln_scale) {
-      auto it = t_ln_scale->find(a.gamma);
-      if (it != t_ln_scale->end()) a.oh_scale = it->second;
-    }
+    a.oh_scale = ln_scale(a.gamma);  // |LayerNorm output| <= sqrt(C) max|gamma| + max|beta|: the scale finalize chose for this LayerNorm
     s3_set(a.out_h, pairs_out ? a.oh_scale : 0.f);
   }
-  return timed(PC_ROWNORM, 0, s, [&] { return launch_rownorm(a, dt, s); });
+  return timed(PC_ROWNORM, 0, [&] { return launch_rownorm(a, dt, s); });
 }
 
-static void begin_call(afx_engine* e, const Ws* w) {
-  t_prof = e->prof;
-  t_no_deep = e->gemm_small_deep ? 0 : 1;
-  dispatch_set_objective(e->concurrent ? OBJ_CU_TIME : OBJ_MAKESPAN);
-  e->last_objective = dispatch_objective();
-  t_ln_scale = &e->ln_scale;
-  t_s3planes = w ? w->s3planes : nullptr;
-  t_s3bytes = w ? w->s3bytes : 0;
-  if (w) s3_begin({w->bufA, w->bufB, w->feats_h, w->hbuf, w->att, w->ff, w->xpad, w->hc, w->ssl_h, w->hid});
-  else s3_begin({});
+// debug tap: an engine-owned fp32 copy of an intermediate (afx_tap reads it back)
+// is_half: `src` is an operand buffer (operand type; split precision: fp32 rows or pair-form rows of stride ld elements)
+static int tap(Call& cx, const char* name, const void* src, size_t n, bool is_half, long ld = 0) {
+  afx_engine* e = cx.e;
+  if (!e->taps_on) return 0;
+  TapRec& t = e->taps[name];
+  if (t.cap < n) {
+    if (t.p) (void)hipFree(t.p);
+    HIP_OK(hipMalloc((void**)&t.p, n * 4));
+    t.cap = n;
+  }
+  t.n = n;
+  const float pair_scale = is_half && e->s3 ? cx.s3_pairs_in(src) : 0.f;
+  if (pair_scale != 0.f) {
+    if (ld <= 0 || ld % 32 || n % ld) return fail("tap '%s': pair-form rows need a row stride that is a multiple of 32", name);
+    hipLaunchKernelGGL(pairs_to_f32_kernel, dim3(1024), dim3(256), 0, cx.s, (const uint16_t*)src, t.p, n, ld, 1.0f / pair_scale);
+    HIP_OK(hipGetLastError());
+  } else if (is_half && e->dt != AFX_DT_FP32) {
+    hipLaunchKernelGGL(half_to_f32_kernel, dim3(1024), dim3(256), 0, cx.s, (const uint16_t*)src, t.p, n,
+                       e->dt == AFX_DT_BF16 ? 1 : 0);
+    HIP_OK(hipGetLastError());
+  } else {
+    HIP_OK(hipMemcpyAsync(t.p, src, n * 4, hipMemcpyDeviceToDevice, cx.s));
+  }
+  return 0;
 }
 
 extern "C" int afx_profile_begin(afx_handle h) {
@@ -1054,17 +1061,16 @@ static RowNormArgs plain_norm(const float* x, long ldx, int rows, int C, const f
   return a;
 }
 
-#define launch_gemm P_gemm
-#define launch_rownorm P_rownorm
 // debug tap at a launch boundary (the name is only built while taps are on): op = an operand buffer of row stride ld
-#define TAP(nm, p, n, op, ld)                                                               \
-  do {                                                                                      \
-    if (e->taps_on && tap(e, std::string(nm).c_str(), (p), (n), (op), s, (ld))) return 1; \
+#define TAP(nm, p, n, op, ld)                                                                \
+  do {                                                                                       \
+    if (cx.e->taps_on && tap(cx, std::string(nm).c_str(), (p), (n), (op), (ld))) return 1; \
   } while (0)
 
 // the positional conv as a grouped product (chunked K over time-padded operand rows) + GELU, added to x in place: `rows` =
 // the first operand row of utterance 0's output frame 0, `batch_rows` operand rows from one utterance to the next, B x T frames
-static const char* posconv_product(afx_engine* e, const void* rows, long batch_rows, int B, int T, float* x, int dt, hipStream_t s) {
+static const char* posconv_product(Call& cx, const void* rows, long batch_rows, int B, int T, float* x, int dt) {
+  afx_engine* e = cx.e;
   const int cpg = kD / kPosG;
   GemmArgs g = plain_gemm(rows, 0, e->posw, (long)cpg * kPosK, B * T, cpg, cpg * kPosK);
   g.rpb = T; g.a_batch = batch_rows * kD; g.a_row = kD;
@@ -1074,12 +1080,14 @@ static const char* posconv_product(afx_engine* e, const void* rows, long batch_r
   g.act = ACT_GELU;
   g.resid = x; g.ldr = kD;
   g.out_f = x; g.ldo_f = kD; g.o_batch_rows = T; g.oh_batch_rows = T;
-  return launch_gemm(g, dt, kPosG, s);
+  return cx.gemm(g, dt, kPosG);
 }
 
 // l5: null = start from the waveform; else the output of conv layer 5, (B, T[5], 512) operand type (tail mode)
 // l5_batch: elements between two utterances of l5 (0 = packed, T[5] * 512): a streaming caller keeps its window inside a longer ring
-static int run_trunk(afx_engine* e, const float* wave, int B, int L, Ws& w, hipStream_t s, const void* l5 = nullptr, long l5_batch = 0) {
+static int run_trunk(Call& cx, const float* wave, int B, int L, Ws& w, const void* l5 = nullptr, long l5_batch = 0) {
+  afx_engine* e = cx.e;
+  const hipStream_t s = cx.s;
   const int dt = e->dt;
   const int* T = w.T;
   if (T[6] < 1) return fail("afx_forward: %d samples are too few for one output frame (need >= 400)", L);
@@ -1089,18 +1097,14 @@ static int run_trunk(afx_engine* e, const float* wave, int B, int L, Ws& w, hipS
   // layer 0: waveform -> (B,T0,512) operand type, normalisation + GELU fused
   const bool gn = e->cfg.extractor_mode == AFX_EXTRACTOR_GROUP_NORM;
   if (!l5)
-    KOK(timed(PC_CONV0, 2.0 * B * T[0] * kC * kConvK[0], s, [&] {
+    KOK(cx.timed(PC_CONV0, 2.0 * B * T[0] * kC * kConvK[0], [&] {
       if (gn)  // wav2vec2-base: GroupNorm over time per (utterance, channel), two passes over the cheap convolution
         return launch_conv0_groupnorm(wave, B, L, T[0], cf(0, ".0.weight"), cf(0, ".2.weight"), cf(0, ".2.bias"), kLnEps,
                                       w.gn_stats, w.bufA, dt, s);
       if (e->s3) {  // split precision: the same matrix-core kernel as the fp16 engines; its rows leave as conv layer 1's pair-form operand
-        float sc = 0.f;
-        if (s3_ok(w.bufA)) {
-          sc = kS3ScaleBounded;  // (LayerNorm + GELU output: bounded by the LayerNorm's gains -- the scale finalize chose for it)
-          auto it = e->ln_scale.find(cf(0, ".2.1.weight"));
-          if (it != e->ln_scale.end()) sc = it->second;
-        }
-        s3_set(w.bufA, sc);
+        // (LayerNorm + GELU output: bounded by the LayerNorm's gains -- the scale finalize chose for it)
+        const float sc = cx.s3_ok(w.bufA) ? cx.ln_scale(cf(0, ".2.1.weight")) : 0.f;
+        cx.s3_set(w.bufA, sc);
         return launch_conv0(wave, B, L, T[0], cf(0, ".0.weight"), cf(0, ".0.bias"), cf(0, ".2.1.weight"), cf(0, ".2.1.bias"),
                             e->cfg.pre_emphasis, e->cfg.pre_emphasis_coef, w.bufA, DT_FP16X3, s, e->conv0pack, sc);
       }
@@ -1125,7 +1129,7 @@ static int run_trunk(afx_engine* e, const float* wave, int B, int L, Ws& w, hipS
       } else {
         g.out_f = w.tmp32; g.ldo_f = kC;
       }
-      KOK(launch_gemm(g, dt, 1, s));
+      KOK(cx.gemm(g, dt, 1));
     } else if (e->fuse_conv_ln && dt != DT_FP32) {
       // (split precision takes the two-kernel form below: measured, the row-complete tile with the pair-form walk and the fp32
       // erf-GELU in its epilogue is SLOWER than the 256-wide tile + a LayerNorm pass that writes the next layer's pair-form
@@ -1136,11 +1140,11 @@ static int run_trunk(afx_engine* e, const float* wave, int B, int L, Ws& w, hipS
       } else {
         g.out_f = w.tmp32; g.ldo_f = kC;  // fp32: the feature LayerNorm follows
       }
-      KOK(launch_gemm(g, dt, 1, s));
+      KOK(cx.gemm(g, dt, 1));
     } else {  // two-kernel form (kept for A/B measurements)
       g.act = ACT_NONE;
       g.out_f = w.tmp32; g.ldo_f = kC;
-      KOK(launch_gemm(g, dt, 1, s));
+      KOK(cx.gemm(g, dt, 1));
       RowNormArgs n = plain_norm(w.tmp32, kC, M, kC, cf(i, ".2.1.weight"), cf(i, ".2.1.bias"));
       n.act = ACT_GELU;
       if (i < 6) {
@@ -1148,18 +1152,18 @@ static int run_trunk(afx_engine* e, const float* wave, int B, int L, Ws& w, hipS
       } else {
         n.out_f = w.tmp32; n.ldo_f = kC;  // in place: a row is register-resident before it is written
       }
-      KOK(launch_rownorm(n, dt, s));
+      KOK(cx.rownorm(n, dt));
     }
     if (i < 6) TAP("c" + std::to_string(i), out, (size_t)M * kC, true, kC);
     void* t = in; in = out; out = t;
   }
   const int Tt = T[6], M = B * Tt;
-  if (tap(e, "conv", w.tmp32, (size_t)M * kC, false, s)) return 1;
+  if (tap(cx, "conv", w.tmp32, (size_t)M * kC, false)) return 1;
   // feature LayerNorm(512) -> operand type
   {
     RowNormArgs n = plain_norm(w.tmp32, kC, M, kC, e->F("ssl.layer_norm.weight"), e->F("ssl.layer_norm.bias"));
     n.out_h = w.feats_h; n.ldo_h = kC;
-    KOK(launch_rownorm(n, dt, s));
+    KOK(cx.rownorm(n, dt));
   }
   TAP("feats", w.feats_h, (size_t)M * kC, true, kC);
   // post_extract_proj: fp32 residual stream x + operand copy into the time-padded buffer
@@ -1169,49 +1173,49 @@ static int run_trunk(afx_engine* e, const float* wave, int B, int L, Ws& w, hipS
     g.bias = e->F("ssl.post_extract_proj.bias");
     g.out_f = w.x; g.ldo_f = kD; g.o_batch_rows = Tt; g.o_row_off = 0;
     g.out_h = w.xpad; g.ldo_h = kD; g.oh_batch_rows = Tt + kPosK; g.oh_row_off = kPosPad;
-    KOK(launch_gemm(g, dt, 1, s));
+    KOK(cx.gemm(g, dt, 1));
     // (ragged batch: the frames past an utterance's own length are zeroed too -- alone, its positional conv would
     // see zero padding there)
-    KOK(timed(PC_MISC, 0, s, [&] { return launch_zero_pad_rows(w.xpad, B, Tt, kD, kPosPad, kPosK - kPosPad, dt, s, w.lens); }));
+    KOK(cx.timed(PC_MISC, 0, [&] { return launch_zero_pad_rows(w.xpad, B, Tt, kD, kPosPad, kPosK - kPosPad, dt, s, w.lens); }));
   }
   TAP("xpad", w.xpad, (size_t)B * (Tt + kPosK) * kD, true, kD);
-  if (tap(e, "proj", w.x, (size_t)M * kD, false, s)) return 1;
+  if (tap(cx, "proj", w.x, (size_t)M * kD, false)) return 1;
   // positional conv (grouped, k=128) + GELU, added to x in place
   if (e->posconv_sliding && dt != DT_FP32 && Tt <= 224) {  // (reads the zero-padded operand copy: ragged batches need nothing more)
     PosConvArgs pc;
     memset(&pc, 0, sizeof pc);
     pc.xpad = w.xpad; pc.xpad_batch = (long)(Tt + kPosK) * kD; pc.W = e->posw; pc.bias = e->F("ssl.encoder.pos_conv.0.bias");
     pc.x = w.x; pc.B = B; pc.T = Tt;
-    KOK(timed(PC_POSCONV, 2.0 * M * kD * (kD / kPosG) * kPosK, s, [&] { return launch_posconv(pc, dt, s); }));
+    KOK(cx.timed(PC_POSCONV, 2.0 * M * kD * (kD / kPosG) * kPosK, [&] { return launch_posconv(pc, dt, s); }));
   } else {
-    KOK(posconv_product(e, w.xpad, Tt + kPosK, B, Tt, w.x, dt, s));
+    KOK(posconv_product(cx, w.xpad, Tt + kPosK, B, Tt, w.x, dt));
   }
-  if (tap(e, "pos", w.x, (size_t)M * kD, false, s)) return 1;
+  if (tap(cx, "pos", w.x, (size_t)M * kD, false)) return 1;
   // transformer layers (pre-LN)
   auto resid_product = [&](const void* A, long lda, const void* W, int K, const float* bias) -> const char* {
     GemmArgs o = plain_gemm(A, lda, W, K, M, kD, K);
     o.bias = bias; o.resid = w.x; o.ldr = kD; o.out_f = w.x; o.ldo_f = kD;
-    return launch_gemm(o, dt, 1, s);
+    return cx.gemm(o, dt, 1);
   };
   for (int l = 0; l < e->cfg.n_layers; ++l) {
     const std::string P = "ssl.encoder.layers." + std::to_string(l) + ".";
     RowNormArgs n1 = plain_norm(w.x, kD, M, kD, e->F(P + "self_attn_layer_norm.weight"), e->F(P + "self_attn_layer_norm.bias"));
     n1.out_h = w.hbuf; n1.ldo_h = kD;
-    KOK(launch_rownorm(n1, dt, s));
+    KOK(cx.rownorm(n1, dt));
     const std::string lp = "l" + std::to_string(l) + ".";
     TAP(lp + "ln1", w.hbuf, (size_t)M * kD, true, kD);
     GemmArgs q = plain_gemm(w.hbuf, kD, e->wqkv[l], kD, M, 3 * kD, kD);
     q.bias = e->bqkv[l];
     q.out_h = w.qkv; q.ldo_h = 3 * kD;
-    KOK(launch_gemm(q, dt, 1, s));
+    KOK(cx.gemm(q, dt, 1));
     TAP(lp + "qkv", w.qkv, (size_t)M * 3 * kD, true, 3 * kD);
-    KOK(timed(PC_MHSA, 4.0 * B * kH * (double)Tt * Tt * 64, s, [&] {
+    KOK(cx.timed(PC_MHSA, 4.0 * B * kH * (double)Tt * Tt * 64, [&] {
       if (e->s3 && Tt <= 224) {  // split precision: the matrix-core form; its output goes out as the output projection's A planes
-        const bool pairs = s3_ok(w.att);
-        s3_set(w.att, pairs ? kS3ScaleFree : 0.f);
+        const bool pairs = cx.s3_ok(w.att);
+        cx.s3_set(w.att, pairs ? kS3ScaleFree : 0.f);
         return launch_mhsa_split((const float*)w.qkv, (float*)w.att, B, Tt, kH, s, w.lens, pairs, kS3ScaleFree);
       }
-      if (e->s3) s3_set(w.att, 0.f);
+      if (e->s3) cx.s3_set(w.att, 0.f);
       return launch_mhsa(w.qkv, w.att, B, Tt, kH, dt, s, w.lens);
     }));
     TAP(lp + "att", w.att, (size_t)M * kD, true, kD);
@@ -1219,17 +1223,17 @@ static int run_trunk(afx_engine* e, const float* wave, int B, int L, Ws& w, hipS
     TAP(lp + "mid", w.x, (size_t)M * kD, false, kD);
     RowNormArgs n2 = plain_norm(w.x, kD, M, kD, e->F(P + "final_layer_norm.weight"), e->F(P + "final_layer_norm.bias"));
     n2.out_h = w.hbuf; n2.ldo_h = kD;
-    KOK(launch_rownorm(n2, dt, s));
+    KOK(cx.rownorm(n2, dt));
     TAP(lp + "ln2", w.hbuf, (size_t)M * kD, true, kD);
     GemmArgs f1 = plain_gemm(w.hbuf, kD, e->w1[l], kD, M, kF, kD);
     f1.bias = e->F(P + "fc1.bias"); f1.act = ACT_GELU;
     f1.out_h = w.ff; f1.ldo_h = kF;
-    KOK(launch_gemm(f1, dt, 1, s));
+    KOK(cx.gemm(f1, dt, 1));
     TAP(lp + "ff", w.ff, (size_t)M * kF, true, kF);
     KOK(resid_product(w.ff, kF, e->w2[l], kF, e->F(P + "fc2.bias")));
     if (e->taps_on) {
       const std::string nm = "layer" + std::to_string(l);
-      if (tap(e, nm.c_str(), w.x, (size_t)M * kD, false, s)) return 1;
+      if (tap(cx, nm.c_str(), w.x, (size_t)M * kD, false)) return 1;
     }
   }
   // final encoder LayerNorm -> fp32 features (API output / AASIST input) + operand copy (LL GEMM)
@@ -1238,8 +1242,8 @@ static int run_trunk(afx_engine* e, const float* wave, int B, int L, Ws& w, hipS
   nf.out_h = w.ssl_h; nf.ldo_h = kD;
   nf.nonfinite = e->nonfinite;  // overflow guard: an operand copy that left fp16's range anywhere in the trunk ends here as inf / NaN
   nf.nf_lens = w.lens; nf.nf_rpb = Tt;  // (ragged batch: only the rows of an utterance's own length are judged; the others hold stale workspace)
-  KOK(launch_rownorm(nf, dt, s));
-  if (tap(e, "ssl", w.ssl_f, (size_t)M * kD, false, s)) return 1;
+  KOK(cx.rownorm(nf, dt));
+  if (tap(cx, "ssl", w.ssl_f, (size_t)M * kD, false)) return 1;
   TAP("ssl.op", w.ssl_h, (size_t)M * kD, true, kD);
   return 0;
 }
@@ -1247,22 +1251,23 @@ static int run_trunk(afx_engine* e, const float* wave, int B, int L, Ws& w, hipS
 // Conformer head from SSL features already in w.ssl_h (operand type)
 // tokens: null = from the SSL features in w.ssl_h (Model / MyModel.forward); else the (B,T,E) fp32 rows MyConformer.forward
 // is given (models/conformer_baseline.py:22-29).  embedding (device (B,E) fp32, may be null) receives token 0 of every utterance.
-static int run_conformer(afx_engine* e, int B, int T, Ws& w, float* logits, hipStream_t s, const float* tokens = nullptr,
-                         float* embedding = nullptr) {
+static int run_conformer(Call& cx, int B, int T, Ws& w, float* logits, const float* tokens = nullptr, float* embedding = nullptr) {
+  afx_engine* e = cx.e;
+  const hipStream_t s = cx.s;
   const int dt = e->dt, E = e->E, Ep = e->Ep, N = T + 1, M = B * N;
   if (tokens) {  // class token + the rows as they are
-    KOK(timed(PC_MISC, 0, s, [&] { return launch_conf_tokens(tokens, e->F("conformer.class_token"), 1.f, 0.f, B, T, E, w.xc, s, true); }));
+    KOK(cx.timed(PC_MISC, 0, [&] { return launch_conf_tokens(tokens, e->F("conformer.class_token"), 1.f, 0.f, B, T, E, w.xc, s, true); }));
   } else {
     // LL -> BatchNorm2d(1) -> SELU -> class token
     GemmArgs ll = plain_gemm(w.ssl_h, kD, e->conf_ll, kD, B * T, E, kD);
     ll.bias = e->F("LL.bias");
     ll.out_f = w.ll32; ll.ldo_f = E;
-    KOK(launch_gemm(ll, dt, 1, s));
-    KOK(timed(PC_MISC, 0, s, [&] {
+    KOK(cx.gemm(ll, dt, 1));
+    KOK(cx.timed(PC_MISC, 0, [&] {
       return launch_conf_tokens(w.ll32, e->F("conformer.class_token"), e->conf_bn_scale, e->conf_bn_shift, B, T, E, w.xc, s);
     }));
   }
-  if (tap(e, "tokens", w.xc, (size_t)M * E, false, s)) return 1;
+  if (tap(cx, "tokens", w.xc, (size_t)M * E, false)) return 1;
   // K-padding columns of the operand buffers must read as zero (the fused chains only read past
   // the real columns of the attention output: 144 -> 160)
   const size_t hs = dtype_size(dt);
@@ -1281,7 +1286,7 @@ static int run_conformer(afx_engine* e, int B, int T, Ws& w, float* logits, hipS
     ConfBlock& K = e->blk[b];
     ConfChainArgs c;
     memset(&c, 0, sizeof c);
-    c.M = M; c.E = E; c.Ep = Ep; c.FFp = e->FFp;
+    c.M = M; c.E = E; c.Ep = Ep; c.FFp = e->FFp; c.objective = cx.objective;
     c.x_in = w.xc; c.x_out = w.xc;  // in place: a wave reads and writes only its own 16 rows
     auto ff = [&](void* w1, void* w2) { c.ff_w1 = w1; c.ff_w2 = w2; };
     const double ff_fl = 2.0 * M * E * e->FF * 2;
@@ -1289,11 +1294,11 @@ static int run_conformer(afx_engine* e, int B, int T, Ws& w, float* logits, hipS
     c.params = K.chain_prm[0];
     c.w_a = K.wqkv; c.ld_w_a = Ep;
     c.out2 = w.qkv32; c.ld_out2 = 3 * e->inner;
-    KOK(timed(PC_CONF_CHAIN, ff_fl + 2.0 * M * E * 3 * e->inner, s, [&] { return launch_conf_chain(c, 0, chain_dt, s); }));
+    KOK(cx.timed(PC_CONF_CHAIN, ff_fl + 2.0 * M * E * 3 * e->inner, [&] { return launch_conf_chain(c, 0, chain_dt, s); }));
     const std::string bp = "b" + std::to_string(b) + ".";
     TAP(bp + "xa", w.xc, (size_t)M * E, false, E);
     TAP(bp + "qkv", w.qkv32, (size_t)M * 3 * e->inner, false, 3 * e->inner);
-    KOK(timed(PC_CONF_ATTN, 6.0 * B * e->heads * (double)N * N * e->dh, s, [&] {
+    KOK(cx.timed(PC_CONF_ATTN, 6.0 * B * e->heads * (double)N * N * e->dh, [&] {
       if (e->conf_attn_mfma && dt != DT_FP32 && e->dh == 36)
         return launch_conf_attn_mfma(w.qkv32, 3 * e->inner, w.qkv32 + e->inner, 3 * e->inner, K.rel_h, 512, B, N, e->heads,
                                      e->dh, w.ao, Ep, dt, s, w.lens, 1);
@@ -1309,10 +1314,10 @@ static int run_conformer(afx_engine* e, int B, int T, Ws& w, float* logits, hipS
     c.w_a = K.wout;
     c.w_b = K.pw1;
     c.out2 = w.glu32; c.ld_out2 = 2 * e->C2;
-    KOK(timed(PC_CONF_CHAIN, 2.0 * M * E * (e->inner + 2 * e->C2), s, [&] { return launch_conf_chain(c, 1, chain_dt, s); }));
+    KOK(cx.timed(PC_CONF_CHAIN, 2.0 * M * E * (e->inner + 2 * e->C2), [&] { return launch_conf_chain(c, 1, chain_dt, s); }));
     TAP(bp + "xb", w.xc, (size_t)M * E, false, E);
     TAP(bp + "glu", w.glu32, (size_t)M * 2 * e->C2, false, 2 * e->C2);
-    KOK(timed(PC_CONF_DWCONV, 2.0 * B * N * e->C2 * e->ck, s, [&] {
+    KOK(cx.timed(PC_CONF_DWCONV, 2.0 * B * N * e->C2 * e->ck, [&] {
       return launch_conf_dwconv(w.glu32, 2 * e->C2, e->F(P + "conv.net.4.conv.weight"),
                                 e->F(P + "conv.net.4.conv.bias"), K.bn_scale, K.bn_shift, B, N, e->C2, e->ck, w.u,
                                 e->C2p, dt, s, w.lens, 1);
@@ -1323,10 +1328,10 @@ static int run_conformer(afx_engine* e, int B, int T, Ws& w, float* logits, hipS
     c.w_a = K.pw2; c.ld_w_a = e->C2p;
     ff(K.ff2_w1, K.ff2_w2);
     c.w_b = nullptr; c.out2 = nullptr;
-    KOK(timed(PC_CONF_CHAIN, ff_fl + 2.0 * M * e->C2 * E, s, [&] { return launch_conf_chain(c, 2, chain_dt, s); }));
+    KOK(cx.timed(PC_CONF_CHAIN, ff_fl + 2.0 * M * e->C2 * E, [&] { return launch_conf_chain(c, 2, chain_dt, s); }));
     if (e->taps_on) {
       const std::string nm = "block" + std::to_string(b);
-      if (tap(e, nm.c_str(), w.xc, (size_t)M * E, false, s)) return 1;
+      if (tap(cx, nm.c_str(), w.xc, (size_t)M * E, false)) return 1;
     }
   }
   for (int b = 0; !fused && b < e->nblk; ++b) {
@@ -1336,7 +1341,7 @@ static int run_conformer(afx_engine* e, int B, int T, Ws& w, float* logits, hipS
     auto norm_to_h = [&](const char* nm) -> const char* {
       RowNormArgs n = plain_norm(w.xc, E, M, E, e->F(P + nm + ".weight"), e->F(P + nm + ".bias"));
       n.out_h = w.hc; n.ldo_h = Ep;
-      return launch_rownorm(n, dt, s);
+      return cx.rownorm(n, dt);
     };
     auto feed_forward = [&](const char* ff, void* w1, void* w2) -> int {
       KOK(norm_to_h((std::string(ff) + ".fn.norm").c_str()));
@@ -1345,13 +1350,13 @@ static int run_conformer(afx_engine* e, int B, int T, Ws& w, float* logits, hipS
       a.k_algo = E;
       a.bias = e->F(P + ff + ".fn.fn.net.0.bias"); a.act = ACT_SWISH;
       a.out_h = w.hid; a.ldo_h = e->FFp;
-      KOK(launch_gemm(a, dt, 1, s));
+      KOK(cx.gemm(a, dt, 1));
       TAP(bp + ff + ".hid", w.hid, (size_t)M * e->FFp, true, e->FFp);
       GemmArgs c = plain_gemm(w.hid, e->FFp, w2, e->FFp, M, E, e->FFp);
       c.k_algo = e->FF;
       c.bias = e->F(P + ff + ".fn.fn.net.3.bias"); c.alpha = 0.5f;
       c.resid = w.xc; c.ldr = E; c.out_f = w.xc; c.ldo_f = E;
-      KOK(launch_gemm(c, dt, 1, s));
+      KOK(cx.gemm(c, dt, 1));
       return 0;
     };
     if (feed_forward("ff1", K.ff1_w1, K.ff1_w2)) return 1;
@@ -1362,9 +1367,9 @@ static int run_conformer(afx_engine* e, int B, int T, Ws& w, float* logits, hipS
     GemmArgs q = plain_gemm(w.hc, Ep, K.wqkv, Ep, M, 3 * e->inner, Ep);
     q.k_algo = E;
     q.out_f = w.qkv32; q.ldo_f = 3 * e->inner;
-    KOK(launch_gemm(q, dt, 1, s));
+    KOK(cx.gemm(q, dt, 1));
     TAP(bp + "qkv", w.qkv32, (size_t)M * 3 * e->inner, false, 3 * e->inner);
-    KOK(timed(PC_CONF_ATTN, 6.0 * B * e->heads * (double)N * N * e->dh, s, [&] {
+    KOK(cx.timed(PC_CONF_ATTN, 6.0 * B * e->heads * (double)N * N * e->dh, [&] {
       if (e->conf_attn_mfma && dt != DT_FP32 && e->dh == 36)
         return launch_conf_attn_mfma(w.qkv32, 3 * e->inner, w.qkv32 + e->inner, 3 * e->inner, K.rel_h, 512, B, N, e->heads,
                                      e->dh, w.ao, Ep, dt, s, w.lens, 1);
@@ -1379,7 +1384,7 @@ static int run_conformer(afx_engine* e, int B, int T, Ws& w, float* logits, hipS
     o.k_algo = e->inner;
     o.bias = e->F(P + "attn.fn.to_out.bias");
     o.resid = w.xc; o.ldr = E; o.out_f = w.xc; o.ldo_f = E;
-    KOK(launch_gemm(o, dt, 1, s));
+    KOK(cx.gemm(o, dt, 1));
     TAP(bp + "xb", w.xc, (size_t)M * E, false, E);
     // conv module
     KOK(norm_to_h("conv.net.0"));
@@ -1388,9 +1393,9 @@ static int run_conformer(afx_engine* e, int B, int T, Ws& w, float* logits, hipS
     p1.k_algo = E;
     p1.bias = e->F(P + "conv.net.2.bias");
     p1.out_f = w.glu32; p1.ldo_f = 2 * e->C2;
-    KOK(launch_gemm(p1, dt, 1, s));
+    KOK(cx.gemm(p1, dt, 1));
     TAP(bp + "glu", w.glu32, (size_t)M * 2 * e->C2, false, 2 * e->C2);
-    KOK(timed(PC_CONF_DWCONV, 2.0 * B * N * e->C2 * e->ck, s, [&] {
+    KOK(cx.timed(PC_CONF_DWCONV, 2.0 * B * N * e->C2 * e->ck, [&] {
       return launch_conf_dwconv(w.glu32, 2 * e->C2, e->F(P + "conv.net.4.conv.weight"),
                                 e->F(P + "conv.net.4.conv.bias"), K.bn_scale, K.bn_shift, B, N, e->C2, e->ck, w.u,
                                 e->C2p, dt, s, w.lens, 1);
@@ -1400,19 +1405,19 @@ static int run_conformer(afx_engine* e, int B, int T, Ws& w, float* logits, hipS
     p2.k_algo = e->C2;
     p2.bias = e->F(P + "conv.net.7.bias");
     p2.resid = w.xc; p2.ldr = E; p2.out_f = w.xc; p2.ldo_f = E;
-    KOK(launch_gemm(p2, dt, 1, s));
+    KOK(cx.gemm(p2, dt, 1));
     TAP(bp + "xc", w.xc, (size_t)M * E, false, E);
     if (feed_forward("ff2", K.ff2_w1, K.ff2_w2)) return 1;
     TAP(bp + "xd", w.xc, (size_t)M * E, false, E);
     RowNormArgs pn = plain_norm(w.xc, E, M, E, e->F(P + "post_norm.weight"), e->F(P + "post_norm.bias"));
     pn.out_f = w.xc; pn.ldo_f = E;
-    KOK(launch_rownorm(pn, dt, s));
+    KOK(cx.rownorm(pn, dt));
     if (e->taps_on) {
       const std::string nm = "block" + std::to_string(b);
-      if (tap(e, nm.c_str(), w.xc, (size_t)M * E, false, s)) return 1;
+      if (tap(cx, nm.c_str(), w.xc, (size_t)M * E, false)) return 1;
     }
   }
-  KOK(timed(PC_MISC, 0, s, [&] {
+  KOK(cx.timed(PC_MISC, 0, [&] {
     return launch_small_linear(w.xc, (long)N * E, B, E, e->F("conformer.fc5.weight"), e->F("conformer.fc5.bias"), 2,
                                logits, s, e->nonfinite + 1);
   }));
@@ -1421,26 +1426,25 @@ static int run_conformer(afx_engine* e, int B, int T, Ws& w, float* logits, hipS
   return 0;
 }
 
-static int run_head(afx_engine* e, int B, int T, Ws& w, float* logits, hipStream_t s) {
-  if (e->cfg.arch == AFX_ARCH_CONFORMER) return run_conformer(e, B, T, w, logits, s);
+static int run_head(Call& cx, int B, int T, Ws& w, float* logits) {
+  afx_engine* e = cx.e;
+  const hipStream_t s = cx.s;
+  if (e->cfg.arch == AFX_ARCH_CONFORMER) return run_conformer(cx, B, T, w, logits);
   if (e->cfg.arch == AFX_ARCH_XLSR_AASIST) {
     // taps on: the back-end hands every launch's output to tap() before a later launch overwrites it
-    struct TapCtx { afx_engine* e; hipStream_t s; } tc{e, s};
-    w.aa.tap = e->taps_on ? +[](void* c, const char* nm, const float* p, size_t n) {
-      return tap(((TapCtx*)c)->e, nm, p, n, false, ((TapCtx*)c)->s);
-    } : nullptr;
-    w.aa.tap_ctx = e->taps_on ? &tc : nullptr;
-    const char* m = timed(PC_AASIST, 2.0 * B * 1.399e9 / 2, s, [&] { return aasist_forward(e->aw, w.ssl_f, B, T, w.aa, logits, s, e->nonfinite + 1); });
+    w.aa.tap = e->taps_on ? +[](void* c, const char* nm, const float* p, size_t n) { return tap(*(Call*)c, nm, p, n, false); } : nullptr;
+    w.aa.tap_ctx = e->taps_on ? &cx : nullptr;
+    const char* m = cx.timed(PC_AASIST, 2.0 * B * 1.399e9 / 2, [&] { return aasist_forward(e->aw, w.ssl_f, B, T, w.aa, logits, s, e->nonfinite + 1); });
     w.aa.tap = nullptr;
     w.aa.tap_ctx = nullptr;
     if (m) return fail("%s", m);
     if (e->taps_on) {
-      if (tap(e, "logits", logits, (size_t)B * 2, false, s)) return 1;
-      if (tap(e, "e_S", w.aa.eS, (size_t)B * 42 * 64, false, s)) return 1;
-      if (tap(e, "e_T", w.aa.eT, (size_t)B * (T / 3) * 64, false, s)) return 1;
-      if (tap(e, "hidden", w.aa.hidden, (size_t)B * 160, false, s)) return 1;
+      if (tap(cx, "logits", logits, (size_t)B * 2, false)) return 1;
+      if (tap(cx, "e_S", w.aa.eS, (size_t)B * 42 * 64, false)) return 1;
+      if (tap(cx, "e_T", w.aa.eT, (size_t)B * (T / 3) * 64, false)) return 1;
+      if (tap(cx, "hidden", w.aa.hidden, (size_t)B * 160, false)) return 1;
       for (int i = 0; i < w.aa.dbg_count; ++i)
-        if (tap(e, w.aa.dbg_name[i], w.aa.dbg_ptr[i], w.aa.dbg_n[i], false, s)) return 1;
+        if (tap(cx, w.aa.dbg_name[i], w.aa.dbg_ptr[i], w.aa.dbg_n[i], false)) return 1;
     }
     return 0;
   }
@@ -1685,23 +1689,28 @@ extern "C" int afx_kv_reset(afx_kv* k, const int* slots, int n_slots, void* stre
   return 0;
 }
 
+// The two contexts of a step, each with the scratch and the buffer list of its own workspace.  chunk: the chunk's products take
+// pair-form operands written by their producers, or converted into the chunk workspace's scratch (its buffers + the chunk's
+// view of the padded rows); head: the back-end's products on the window.
+struct KvCalls {
+  Call chunk, head;
+  KvCalls(afx_engine* e, void* stream, const KvWs& w)
+      : chunk(e, stream, w.s3planes, w.s3bytes, {w.feats_h, w.hbuf, w.att, w.ff, w.xpad, (char*)w.xpad + (size_t)kKvHist * kD * e->hsz}),
+        head(e, stream, w.head) {}
+};
 // The shared body of the three steps: the chunk's rows (f.rows blocks of n) from the feature LayerNorm to the final encoder
 // LayerNorm.  Every difference between the forms is a field of KvForm.
-static int kv_trunk(afx_kv* k, const KvForm& f, const float* feats6, int n, KvWs& w, hipStream_t s) {
-  afx_engine* e = k->e;
+// cx: the chunk's context (KvCalls::chunk)
+static int kv_trunk(Call& cx, afx_kv* k, const KvForm& f, const float* feats6, int n, KvWs& w) {
+  afx_engine* e = cx.e;
+  const hipStream_t s = cx.s;
   const int R = f.rows, dt = e->dt, M = R * n, Tp = kKvHist + n;
   const size_t hs = e->hsz, xrow = (size_t)kD * hs, xpad_pitch = (size_t)(Tp + kPosK) * xrow;
-  begin_call(e, nullptr);
-  if (e->s3) {  // split precision: the chunk's products take pair-form operands written by their producers, or converted into the scratch
-    t_s3planes = w.s3planes;
-    t_s3bytes = w.s3bytes;
-    s3_begin({w.feats_h, w.hbuf, w.att, w.ff, w.xpad, (char*)w.xpad + (size_t)kKvHist * kD * e->hsz});  // (+ the chunk's view of the padded rows)
-  }
   // feature LayerNorm -> operand type
   {
     RowNormArgs a = plain_norm(feats6, kC, M, kC, e->F("ssl.layer_norm.weight"), e->F("ssl.layer_norm.bias"));
     a.out_h = w.feats_h; a.ldo_h = kC;
-    KOK(launch_rownorm(a, dt, s));
+    KOK(cx.rownorm(a, dt));
   }
   TAP("kv.feats", w.feats_h, (size_t)M * kC, true, kC);
   // positional conv operand: [64 zero rows | 64 cached projected frames | the chunk | 64 zero rows] per row block
@@ -1718,9 +1727,9 @@ static int kv_trunk(afx_kv* k, const KvForm& f, const float* feats6, int n, KvWs
     g.bias = e->F("ssl.post_extract_proj.bias");
     g.out_f = w.x; g.ldo_f = kD; g.o_batch_rows = n;  // the chunk's residual rows, dense (rows, n, 1024)
     g.out_h = w.xpad; g.ldo_h = kD; g.oh_batch_rows = Tp + kPosK; g.oh_row_off = kPosPad + kKvHist;
-    KOK(launch_gemm(g, dt, 1, s));
+    KOK(cx.gemm(g, dt, 1));
     // (per-stream counts: a block's chunk rows past its own n_s are zero, as beyond its chunk when the stream steps alone)
-    KOK(timed(PC_MISC, 0, s, [&] { return launch_zero_pad_rows(w.xpad, R, Tp, kD, kPosPad, kPosK - kPosPad, dt, s, f.pad_lens); }));
+    KOK(cx.timed(PC_MISC, 0, [&] { return launch_zero_pad_rows(w.xpad, R, Tp, kD, kPosPad, kPosK - kPosPad, dt, s, f.pad_lens); }));
   }
   TAP("kv.xpad", w.xpad, (size_t)R * (Tp + kPosK) * kD, true, kD);  // (the whole padded buffer of every row block, pad rows included)
   TAP("kv.proj", w.x, (size_t)M * kD, false, kD);
@@ -1733,10 +1742,10 @@ static int kv_trunk(afx_kv* k, const KvForm& f, const float* feats6, int n, KvWs
     memset(&pc, 0, sizeof pc);
     pc.xpad = xchunk; pc.xpad_batch = (long)(Tp + kPosK) * kD; pc.W = e->posw; pc.bias = e->F("ssl.encoder.pos_conv.0.bias");
     pc.x = w.x; pc.B = R; pc.T = n;
-    KOK(timed(PC_POSCONV, 2.0 * R * n * kD * (kD / kPosG) * kPosK, s, [&] { return launch_posconv(pc, dt, s); }));
+    KOK(cx.timed(PC_POSCONV, 2.0 * R * n * kD * (kD / kPosG) * kPosK, [&] { return launch_posconv(pc, dt, s); }));
   } else {  // split precision: the grouped product of run_trunk
-    s3_set(xchunk, kS3ScaleFree);  // (history rows copied in above + the rows the projection just wrote: pair form, scale 1)
-    KOK(posconv_product(e, xchunk, Tp + kPosK, R, n, w.x, dt, s));
+    cx.s3_set(xchunk, kS3ScaleFree);  // (history rows copied in above + the rows the projection just wrote: pair form, scale 1)
+    KOK(posconv_product(cx, xchunk, Tp + kPosK, R, n, w.x, dt));
   }
   TAP("kv.pos", w.x, (size_t)M * kD, false, kD);
   // the newest 64 projected frames become the next chunk's left context
@@ -1753,7 +1762,7 @@ static int kv_trunk(afx_kv* k, const KvForm& f, const float* feats6, int n, KvWs
     auto lp = [l](const char* leaf) { return "kv.l" + std::to_string(l) + "." + leaf; };  // (tap names: built only while taps are on)
     RowNormArgs n1 = plain_norm(w.x, kD, M, kD, e->F(P + "self_attn_layer_norm.weight"), e->F(P + "self_attn_layer_norm.bias"));
     n1.out_h = w.hbuf; n1.ldo_h = kD;
-    KOK(launch_rownorm(n1, dt, s));
+    KOK(cx.rownorm(n1, dt));
     TAP(lp("ln1"), w.hbuf, (size_t)M * kD, true, kD);
     // q | k | v of the chunk go straight into its 16-slot group of the ring (row remap or row table of the epilogue): K / V are
     // cached by being written
@@ -1766,12 +1775,12 @@ static int kv_trunk(afx_kv* k, const KvForm& f, const float* feats6, int n, KvWs
     } else {
       q.oh_batch_rows = kKvSlots; q.oh_row_off = f.ring.q_tile * 16;
     }
-    KOK(launch_gemm(q, dt, 1, s, f.qkv_rows != nullptr));
+    KOK(cx.gemm(q, dt, 1, f.qkv_rows != nullptr));
     TAP(lp("ring"), ring, (size_t)k->S * kKvSlots * 3 * kD, true, 3 * kD);  // (this layer's whole ring, every stream of the state)
-    KOK(timed(PC_MHSA, 4.0 * R * kH * 16.0 * kKvSlots * 64, s, [&] {
+    KOK(cx.timed(PC_MHSA, 4.0 * R * kH * 16.0 * kKvSlots * 64, [&] {
       if (e->s3) {  // fp32 [q | k | v] slots, hi / lo pairs split in the kernel; the output leaves as the output projection's pair-form operand
-        const bool pairs = s3_ok(w.att);
-        s3_set(w.att, pairs ? kS3ScaleFree : 0.f);
+        const bool pairs = cx.s3_ok(w.att);
+        cx.s3_set(w.att, pairs ? kS3ScaleFree : 0.f);
         return launch_mhsa_ring_split((const float*)ring, (float*)w.att, R, kH, f.ring, s, pairs, kS3ScaleFree);
       }
       return launch_mhsa_ring(ring, w.att, R, kH, f.ring, dt, s);
@@ -1780,19 +1789,19 @@ static int kv_trunk(afx_kv* k, const KvForm& f, const float* feats6, int n, KvWs
     GemmArgs o = plain_gemm(w.att, kD, e->wo[l], kD, M, kD, kD);
     o.rpb = n; o.a_batch = 16L * kD; o.a_row = kD; o.o_batch_rows = n;
     o.bias = e->F(P + "self_attn.out_proj.bias"); o.resid = w.x; o.ldr = kD; o.out_f = w.x; o.ldo_f = kD;
-    KOK(launch_gemm(o, dt, 1, s));
+    KOK(cx.gemm(o, dt, 1));
     TAP(lp("mid"), w.x, (size_t)M * kD, false, kD);
     RowNormArgs n2 = plain_norm(w.x, kD, M, kD, e->F(P + "final_layer_norm.weight"), e->F(P + "final_layer_norm.bias"));
     n2.out_h = w.hbuf; n2.ldo_h = kD;
-    KOK(launch_rownorm(n2, dt, s));
+    KOK(cx.rownorm(n2, dt));
     TAP(lp("ln2"), w.hbuf, (size_t)M * kD, true, kD);
     GemmArgs f1 = plain_gemm(w.hbuf, kD, e->w1[l], kD, M, kF, kD);
     f1.bias = e->F(P + "fc1.bias"); f1.act = ACT_GELU; f1.out_h = w.ff; f1.ldo_h = kF;
-    KOK(launch_gemm(f1, dt, 1, s));
+    KOK(cx.gemm(f1, dt, 1));
     TAP(lp("ff"), w.ff, (size_t)M * kF, true, kF);
     GemmArgs f2 = plain_gemm(w.ff, kF, e->w2[l], kF, M, kD, kF);
     f2.bias = e->F(P + "fc2.bias"); f2.resid = w.x; f2.ldr = kD; f2.out_f = w.x; f2.ldo_f = kD;
-    KOK(launch_gemm(f2, dt, 1, s));
+    KOK(cx.gemm(f2, dt, 1));
     TAP("kv.layer" + std::to_string(l), w.x, (size_t)M * kD, false, kD);
   }
   RowNormArgs nf = plain_norm(w.x, kD, M, kD, e->F("ssl.encoder.layer_norm.weight"), e->F("ssl.encoder.layer_norm.bias"));
@@ -1804,7 +1813,7 @@ static int kv_trunk(afx_kv* k, const KvForm& f, const float* feats6, int n, KvWs
     nf.out_f = w.fl; nf.ldo_f = kD;
   }
   nf.nonfinite = e->nonfinite;
-  KOK(launch_rownorm(nf, dt, s));
+  KOK(cx.rownorm(nf, dt));
   if (!f.win_next) TAP("kv.fl", w.fl, (size_t)M * kD, false, kD);  // (lock-step: the rows are the last n of every stream's "kv.win")
   return 0;
 }
@@ -1823,7 +1832,9 @@ extern "C" int afx_kv_step(afx_kv* k, const float* feats6, int n, float* logits,
   KvWs w;
   const size_t needb = kv_carve(e, S, n, Th, ws, &w);
   if (ws_bytes < needb) return fail("afx_kv_step: workspace too small (%zu < %zu bytes)", ws_bytes, needb);
-  hipStream_t s = (hipStream_t)stream;
+  KvCalls calls(e, stream, w);
+  Call& cx = calls.chunk;
+  const hipStream_t s = cx.s;
   k->cnt[group] = n;
   // the chunk's features join the right-aligned window (old frames move up by n in the other buffer)
   float* nxt = k->feat[k->pp ^ 1];
@@ -1831,7 +1842,7 @@ extern "C" int afx_kv_step(afx_kv* k, const float* feats6, int n, float* logits,
   f.rows = S;
   f.ring = MhsaRingForm{1, group, k->cnt, nullptr};
   f.win_next = nxt;
-  if (kv_trunk(k, f, feats6, n, w, s)) return 1;
+  if (kv_trunk(cx, k, f, feats6, n, w)) return 1;
   TAP("kv.win", nxt, (size_t)S * kKvFeat * kD, false, kD);
   k->pp ^= 1;
   k->nfeat = std::min(k->nfeat + n, kKvFeat);
@@ -1847,9 +1858,8 @@ extern "C" int afx_kv_step(afx_kv* k, const float* feats6, int n, float* logits,
     }
   }
   k->hop += 1;
-  if (e->taps_on && tap(e, "ssl", w.head.ssl_f, (size_t)S * Th * kD, false, s)) return 1;
-  begin_call(e, &w.head);  // (the back-end's products use the back-end workspace's own scratch and buffer list)
-  return run_head(e, S, Th, w.head, logits, s);
+  if (e->taps_on && tap(cx, "ssl", w.head.ssl_f, (size_t)S * Th * kD, false)) return 1;
+  return run_head(calls.head, S, Th, w.head, logits);
 }
 
 // AASIST scores uniform batches: the entries grouped by window length (one sub-batch each, as afx_forward_ragged does).
@@ -1872,7 +1882,10 @@ struct KvWindows {
   const int *b_ids, *b_row;  // device.  AASIST, the bucket loop: position j of the order is stream b_ids[j], logits row b_row[j]
   std::vector<std::pair<int, int>> buckets;  // AASIST: kv_buckets
 };
-static int kv_score_windows(afx_engine* e, KvWs& w, const KvWindows& v, float* logits, hipStream_t s) {
+// cx: the back-end's context (KvCalls::head)
+static int kv_score_windows(Call& cx, KvWs& w, const KvWindows& v, float* logits) {
+  afx_engine* e = cx.e;
+  const hipStream_t s = cx.s;
   const int count = v.count, Thmax = v.Thmax;
   if (e->cfg.arch == AFX_ARCH_CONFORMER) {
     hipLaunchKernelGGL(kv_gather_kernel, dim3(32, count), dim3(256), 0, s, (const f32x4*)v.win, v.ids, v.dth, 0, Thmax, (f32x4*)w.head.ssl_f);
@@ -1885,10 +1898,8 @@ static int kv_score_windows(afx_engine* e, KvWs& w, const KvWindows& v, float* l
       hipLaunchKernelGGL(f32_to_half_kernel, dim3(1024), dim3(256), 0, s, w.head.ssl_f, (uint16_t*)w.head.ssl_h, (size_t)count * Thmax * kD, e->dt == AFX_DT_BF16 ? 1 : 0);
       HIP_OK(hipGetLastError());
     }
-    begin_call(e, &w.head);
-    return run_head(e, count, Thmax, w.head, logits, s);
+    return run_head(cx, count, Thmax, w.head, logits);
   }
-  begin_call(e, &w.head);
   for (size_t bi = 0; bi < v.buckets.size(); ++bi) {
     const int t = v.buckets[bi].first, i0 = v.buckets[bi].second;
     const int nb = (bi + 1 < v.buckets.size() ? v.buckets[bi + 1].second : count) - i0;
@@ -1934,6 +1945,8 @@ extern "C" int afx_kv_step_ragged(afx_kv* k, const float* feats6, int n, const i
   KvWs w;
   const size_t needb = kv_carve(e, S, n, Thmax, ws, &w, true);
   if (ws_bytes < needb) return fail("afx_kv_step_ragged: workspace too small (%zu < %zu bytes)", ws_bytes, needb);
+  KvCalls calls(e, stream, w);
+  Call& cx = calls.chunk;
   const int* dn = k->meta;
   KvWindows v = {nullptr, S, Thmax, nullptr, dn + 2 * S, dn + 3 * S, dn + 3 * S, {}};  // (every stream, in place; scores in bucket order)
   if (e->cfg.arch == AFX_ARCH_XLSR_AASIST) v.buckets = kv_buckets(&hm[2 * S], S, &hm[3 * S]);
@@ -1946,7 +1959,7 @@ extern "C" int afx_kv_step_ragged(afx_kv* k, const float* feats6, int n, const i
   f.dn = dn;
   f.pad_lens = dn + S;
   f.ring = MhsaRingForm{2, group, nullptr, k->tab};
-  if (kv_trunk(k, f, feats6, n, w, s)) return 1;
+  if (kv_trunk(cx, k, f, feats6, n, w)) return 1;
   float *cur = k->feat[k->pp], *nxt = k->feat[k->pp ^ 1];
   hipLaunchKernelGGL(kv_feat_kernel, dim3(64, S), dim3(256), 0, s, (const f32x4*)cur, (f32x4*)nxt, (const f32x4*)w.fl, dn, n);
   HIP_OK(hipGetLastError());
@@ -1955,7 +1968,7 @@ extern "C" int afx_kv_step_ragged(afx_kv* k, const float* feats6, int n, const i
   for (int b = 0; b < S; ++b) k->nfeat_s[b] = std::min(k->nfeat_s[b] + n_frames[b], kKvFeat);
   k->hop += 1;
   v.win = nxt;
-  return kv_score_windows(e, w, v, logits, s);
+  return kv_score_windows(calls.head, w, v, logits);
 }
 
 // ---------------------------------------------------------------------------------
@@ -2037,7 +2050,9 @@ extern "C" int afx_kv_step_active(afx_kv* k, const int* slots, int A, const floa
   KvWs w;
   const size_t needb = kv_carve(e, A, n, Thmax, ws, &w, true);
   if (ws_bytes < needb) return fail("afx_kv_step_active: workspace too small (%zu < %zu bytes)", ws_bytes, needb);
-  hipStream_t s = (hipStream_t)stream;
+  KvCalls calls(e, stream, w);
+  Call& cx = calls.chunk;
+  const hipStream_t s = cx.s;
   if (kv_to_per_stream(k, s)) return 1;
   if (!k->active) {  // every stream's next group = the group a lock-stepped or ragged step would write now
     hipLaunchKernelGGL(kv_activate_kernel, dim3((S + 255) / 256), dim3(256), 0, s, k->tab, S, (int)(k->hop % kKvGroups));
@@ -2070,12 +2085,12 @@ extern "C" int afx_kv_step_active(afx_kv* k, const int* slots, int A, const floa
   f.pad_lens = dn + A;
   f.qkv_rows = drows;
   f.ring = MhsaRingForm{3, 0, nullptr, datab};
-  if (kv_trunk(k, f, feats6, n, w, s)) return 1;
+  if (kv_trunk(cx, k, f, feats6, n, w)) return 1;
   hipLaunchKernelGGL(kv_shift_kernel, dim3(kD / 4 / 32, A), dim3(256), 0, s, (f32x4*)k->feat[k->pp], (const f32x4*)w.fl, dids, dn, n);
   HIP_OK(hipGetLastError());
   TAP("kv.win", k->feat[k->pp], (size_t)S * kKvFeat * kD, false, kD);  // (every stream of the state: the unnamed ones keep every byte)
   for (int i = 0; i < A; ++i) k->nfeat_s[slots[i]] = std::min(k->nfeat_s[slots[i]] + n_frames[i], kKvFeat);
-  return kv_score_windows(e, w, v, logits, s);
+  return kv_score_windows(calls.head, w, v, logits);
 }
 
 // ---------------------------------------------------------------------------------
@@ -2249,9 +2264,6 @@ extern "C" int afx_kv_import(afx_kv* k, const int* slots, int n, const void* pay
   return 0;
 }
 
-#undef launch_gemm
-#undef launch_rownorm
-
 static int check_call(afx_handle h, const void* in, int B, int L, const void* out, void* ws, bool needs_trunk = false) {
   if (!h || !in || !out || !ws) return fail("afx: null argument");
   if (needs_trunk && h->cfg.arch == AFX_ARCH_CONFORMER_HEAD) return fail("afx: this handle holds Conformer blocks only (MyConformer); use afx_conformer_forward");
@@ -2259,17 +2271,20 @@ static int check_call(afx_handle h, const void* in, int B, int L, const void* ou
   if (B <= 0 || L <= 0) return fail("afx: empty batch (B=%d, L=%d)", B, L);
   return 0;
 }
+// ... then carves the caller's workspace (carve's own arguments) and refuses one that is too small
+static int carve_ws(const char* who, afx_handle h, int B, int L, int Th, void* ws, size_t ws_bytes, Ws* w, int T5 = 0, bool ragged = false) {
+  const size_t needb = carve(h, B, L, Th, ws, w, T5, ragged);
+  return ws_bytes < needb ? fail("%s: workspace too small (%zu < %zu bytes)", who, ws_bytes, needb) : 0;
+}
 
 extern "C" int afx_forward(afx_handle h, const float* wave, int B, int L, float* logits, void* ws, size_t ws_bytes,
                            void* stream) {
   if (check_call(h, wave, B, L, logits, ws, true)) return 1;
   Ws w;
-  const size_t needb = carve(h, B, L, 0, ws, &w);
-  if (ws_bytes < needb) return fail("afx_forward: workspace too small (%zu < %zu bytes)", ws_bytes, needb);
-  hipStream_t s = (hipStream_t)stream;
-  begin_call(h, &w);
-  if (run_trunk(h, wave, B, L, w, s)) return 1;
-  return run_head(h, B, w.T[6], w, logits, s);
+  if (carve_ws("afx_forward", h, B, L, 0, ws, ws_bytes, &w)) return 1;
+  Call cx(h, stream, w);
+  if (run_trunk(cx, wave, B, L, w)) return 1;
+  return run_head(cx, B, w.T[6], w, logits);
 }
 
 // The forward in two halves, so that a scoring loop can run the back-end of batch i on a second stream under the trunk of
@@ -2279,29 +2294,21 @@ extern "C" int afx_forward(afx_handle h, const float* wave, int B, int L, float*
 extern "C" int afx_trunk_forward(afx_handle h, const float* wave, int B, int L, void* ws, size_t ws_bytes, void* stream) {
   if (check_call(h, wave, B, L, ws, ws, true)) return 1;
   Ws w;
-  const size_t needb = carve(h, B, L, 0, ws, &w);
-  if (ws_bytes < needb) return fail("afx_trunk_forward: workspace too small (%zu < %zu bytes)", ws_bytes, needb);
-  begin_call(h, &w);
-  return run_trunk(h, wave, B, L, w, (hipStream_t)stream);
+  if (carve_ws("afx_trunk_forward", h, B, L, 0, ws, ws_bytes, &w)) return 1;
+  Call cx(h, stream, w);
+  return run_trunk(cx, wave, B, L, w);
 }
 extern "C" int afx_head_from_workspace(afx_handle h, int B, int L, float* logits, void* ws, size_t ws_bytes, void* stream) {
   if (check_call(h, ws, B, L, logits, ws, true)) return 1;
   if (h->cfg.arch == AFX_ARCH_SSL) return fail("afx_head_from_workspace: this handle has no back-end");
   Ws w;
-  const size_t needb = carve(h, B, L, 0, ws, &w);
-  if (ws_bytes < needb) return fail("afx_head_from_workspace: workspace too small (%zu < %zu bytes)", ws_bytes, needb);
+  if (carve_ws("afx_head_from_workspace", h, B, L, 0, ws, ws_bytes, &w)) return 1;
   if (w.T[6] < 1) return fail("afx_head_from_workspace: %d samples are too few for one output frame", L);
-  begin_call(h, &w);
-  // split precision: what afx_trunk_forward left in the workspace for a dense product of the head -- the Conformer head's LL
-  // reads the features' operand copy, which the trunk's final LayerNorm wrote as pair-form rows (run_trunk: P_rownorm) -- is
-  // re-registered here: the registry of which buffers hold pair-form rows lives per call, and this is a second call
-  if (h->s3 && s3_ok(w.ssl_h) && (kD & 31) == 0) {
-    float sc = kS3ScaleBounded;
-    auto it = h->ln_scale.find(h->F("ssl.encoder.layer_norm.weight"));
-    if (it != h->ln_scale.end()) sc = it->second;
-    s3_set(w.ssl_h, sc);
-  }
-  return run_head(h, B, w.T[6], w, logits, (hipStream_t)stream);
+  Call cx(h, stream, w);
+  // split precision: the Conformer head's LL reads the features' operand copy, which the trunk's final LayerNorm wrote as
+  // pair-form rows (run_trunk: Call::rownorm).  That was afx_trunk_forward's call; this one starts from what the workspace holds
+  if (cx.s3_ok(w.ssl_h)) cx.s3_set(w.ssl_h, cx.ln_scale(h->F("ssl.encoder.layer_norm.weight")));
+  return run_head(cx, B, w.T[6], w, logits);
 }
 
 // The path from the output of conv layer 5 on (conv layer 6, feature LayerNorm, projection, positional conv,
@@ -2320,13 +2327,11 @@ extern "C" int afx_tail_forward_strided(afx_handle h, const void* conv5_h, long 
   if (batch_stride % 8) return fail("afx_tail_forward_strided: the batch stride must keep rows 16-byte aligned");
   if (h->s3 && batch_stride != 0 && batch_stride != (long)T5 * kC) return fail("afx_tail_forward_strided: split precision reads a packed window");
   Ws w;
-  const size_t needb = carve(h, B, 0, 0, ws, &w, T5);
-  if (ws_bytes < needb) return fail("afx_tail_forward: workspace too small (%zu < %zu bytes)", ws_bytes, needb);
+  if (carve_ws("afx_tail_forward", h, B, 0, 0, ws, ws_bytes, &w, T5)) return 1;
   if (w.T[6] < 1) return fail("afx_tail_forward: %d conv-layer-5 frames are too few for one output frame", T5);
-  hipStream_t s = (hipStream_t)stream;
-  begin_call(h, &w);
-  if (run_trunk(h, nullptr, B, 0, w, s, conv5_h, batch_stride)) return 1;
-  return run_head(h, B, w.T[6], w, logits, s);
+  Call cx(h, stream, w);
+  if (run_trunk(cx, nullptr, B, 0, w, conv5_h, batch_stride)) return 1;
+  return run_head(cx, B, w.T[6], w, logits);
 }
 extern "C" int afx_tail_forward(afx_handle h, const void* conv5_h, int B, int T5, float* logits, void* ws, size_t ws_bytes,
                                 void* stream) {
@@ -2393,9 +2398,9 @@ extern "C" int afx_tail_forward_windows(afx_handle h, const void* conv5_h, long 
     hipLaunchKernelGGL(gather_windows_kernel, dim3((unsigned)gx, nb), dim3(256), 0, s, g);
     HIP_OK(hipGetLastError());
   }
-  begin_call(h, &w);
-  if (run_trunk(h, nullptr, B, 0, w, s, ws, 0)) return 1;
-  return run_head(h, B, w.T[6], w, logits, s);
+  Call cx(h, stream, w);
+  if (run_trunk(cx, nullptr, B, 0, w, ws, 0)) return 1;
+  return run_head(cx, B, w.T[6], w, logits);
 }
 
 // ---------------------------------------------------------------------------------
@@ -2435,15 +2440,14 @@ extern "C" int afx_forward_ragged(afx_handle h, const float* wave, int B, int Lm
   if (h->cfg.pre_emphasis) return fail("afx_forward_ragged: engine-side pre-emphasis is not supported on ragged batches");
   if (h->cfg.extractor_mode == AFX_EXTRACTOR_GROUP_NORM) return fail("afx_forward_ragged: the group-norm extractor normalises over the whole clip; zero padding would enter its statistics");
   Ws w;
-  const size_t needb = carve(h, B, Lmax, 0, ws, &w, 0, true);
-  if (ws_bytes < needb) return fail("afx_forward_ragged: workspace too small (%zu < %zu bytes)", ws_bytes, needb);
+  if (carve_ws("afx_forward_ragged", h, B, Lmax, 0, ws, ws_bytes, &w, 0, true)) return 1;
   hipStream_t s = (hipStream_t)stream;
   std::vector<int> frames;
   if (ragged_setup(h, B, Lmax, n_samples, w, frames, s)) return 1;
-  begin_call(h, &w);
-  if (run_trunk(h, wave, B, Lmax, w, s)) return 1;
+  Call cx(h, stream, w);
+  if (run_trunk(cx, wave, B, Lmax, w)) return 1;
   const int Tmax = w.T[6];
-  if (h->cfg.arch == AFX_ARCH_CONFORMER) return run_head(h, B, Tmax, w, logits, s);
+  if (h->cfg.arch == AFX_ARCH_CONFORMER) return run_head(cx, B, Tmax, w, logits);
   // AASIST: one uniform sub-batch per distinct length
   std::vector<char> done(B, 0);
   for (int b0 = 0; b0 < B; ++b0) {
@@ -2472,13 +2476,12 @@ extern "C" int afx_ssl_forward_ragged(afx_handle h, const float* wave, int B, in
   if (h->cfg.pre_emphasis) return fail("afx_ssl_forward_ragged: engine-side pre-emphasis is not supported on ragged batches");
   if (h->cfg.extractor_mode == AFX_EXTRACTOR_GROUP_NORM) return fail("afx_ssl_forward_ragged: the group-norm extractor normalises over the whole clip; zero padding would enter its statistics");
   Ws w;
-  const size_t needb = carve(h, B, Lmax, 0, ws, &w, 0, true);
-  if (ws_bytes < needb) return fail("afx_ssl_forward_ragged: workspace too small (%zu < %zu bytes)", ws_bytes, needb);
+  if (carve_ws("afx_ssl_forward_ragged", h, B, Lmax, 0, ws, ws_bytes, &w, 0, true)) return 1;
   hipStream_t s = (hipStream_t)stream;
   std::vector<int> frames;
   if (ragged_setup(h, B, Lmax, n_samples, w, frames, s)) return 1;
-  begin_call(h, &w);
-  if (run_trunk(h, wave, B, Lmax, w, s)) return 1;
+  Call cx(h, stream, w);
+  if (run_trunk(cx, wave, B, Lmax, w)) return 1;
   const int Tmax = w.T[6];
   HIP_OK(hipMemcpyAsync(feats, w.ssl_f, (size_t)B * Tmax * kD * 4, hipMemcpyDeviceToDevice, s));
   for (int b = 0; b < B; ++b) {
@@ -2493,11 +2496,10 @@ extern "C" int afx_ssl_forward(afx_handle h, const float* wave, int B, int L, fl
                                void* stream) {
   if (check_call(h, wave, B, L, feats, ws, true)) return 1;
   Ws w;
-  const size_t needb = carve(h, B, L, 0, ws, &w);
-  if (ws_bytes < needb) return fail("afx_ssl_forward: workspace too small (%zu < %zu bytes)", ws_bytes, needb);
+  if (carve_ws("afx_ssl_forward", h, B, L, 0, ws, ws_bytes, &w)) return 1;
   hipStream_t s = (hipStream_t)stream;
-  begin_call(h, &w);
-  if (run_trunk(h, wave, B, L, w, s)) return 1;
+  Call cx(h, stream, w);
+  if (run_trunk(cx, wave, B, L, w)) return 1;
   HIP_OK(hipMemcpyAsync(feats, w.ssl_f, (size_t)B * w.T[6] * kD * 4, hipMemcpyDeviceToDevice, s));
   return 0;
 }
@@ -2521,8 +2523,7 @@ extern "C" int afx_head_forward(afx_handle h, const float* feats, int B, int T, 
   if (h->cfg.arch == AFX_ARCH_CONFORMER_HEAD) return fail("afx_head_forward: this handle holds Conformer blocks only; use afx_conformer_forward");
   Ws w;
   memset(&w, 0, sizeof w);
-  const size_t needb = carve(h, B, 0, T, ws, &w);
-  if (ws_bytes < needb) return fail("afx_head_forward: workspace too small (%zu < %zu bytes)", ws_bytes, needb);
+  if (carve_ws("afx_head_forward", h, B, 0, T, ws, ws_bytes, &w)) return 1;
   hipStream_t s = (hipStream_t)stream;
   const size_t n = (size_t)B * T * kD;
   HIP_OK(hipMemcpyAsync(w.ssl_f, feats, n * 4, hipMemcpyDeviceToDevice, s));
@@ -2533,8 +2534,8 @@ extern "C" int afx_head_forward(afx_handle h, const float* feats, int B, int T, 
                        h->dt == AFX_DT_BF16 ? 1 : 0);
     HIP_OK(hipGetLastError());
   }
-  begin_call(h, &w);
-  return run_head(h, B, T, w, logits, s);
+  Call cx(h, stream, w);
+  return run_head(cx, B, T, w, logits);
 }
 
 // MyConformer.forward alone (models/conformer_baseline.py:22-29): tokens (B,T,emb) fp32 -> class token prepended -> the
@@ -2546,10 +2547,9 @@ extern "C" int afx_conformer_forward(afx_handle h, const float* tokens, int B, i
     return fail("afx_conformer_forward: this handle holds no Conformer blocks");
   Ws w;
   memset(&w, 0, sizeof w);
-  const size_t needb = carve(h, B, 0, T, ws, &w);
-  if (ws_bytes < needb) return fail("afx_conformer_forward: workspace too small (%zu < %zu bytes)", ws_bytes, needb);
-  begin_call(h, &w);
-  return run_conformer(h, B, T, w, logits, (hipStream_t)stream, tokens, embedding);
+  if (carve_ws("afx_conformer_forward", h, B, 0, T, ws, ws_bytes, &w)) return 1;
+  Call cx(h, stream, w);
+  return run_conformer(cx, B, T, w, logits, tokens, embedding);
 }
 
 extern "C" size_t afx_head_workspace_bytes(afx_handle h, int B, int T) {
@@ -2571,7 +2571,6 @@ extern "C" size_t afx_head_workspace_bytes(afx_handle h, int B, int T) {
 extern "C" int afx_k_gemm(int dtype, const void* A, long lda, const void* W, long ldw, int M, int N, int K,
                           const float* bias, int act, float alpha, const float* resid, long ldr, float* out_f,
                           long ldo_f, void* out_h, long ldo_h, void* stream) {
-  dispatch_set_objective(OBJ_MAKESPAN);  // (a single-kernel entry point is no concurrent forward)
   GemmArgs g = plain_gemm(A, lda, W, ldw, M, N, K);
   g.bias = bias; g.act = act; g.alpha = alpha; g.resid = resid; g.ldr = ldr;
   g.out_f = out_f; g.ldo_f = ldo_f; g.out_h = out_h; g.ldo_h = ldo_h;
@@ -2604,7 +2603,6 @@ extern "C" int afx_k_gemm(int dtype, const void* A, long lda, const void* W, lon
 }
 extern "C" int afx_k_conv_gemm(int dtype, const void* in_h, const void* Wp, int B, int Tin, int Tout, int Cin, int k,
                                int s_, int N, const float* bias, float* out_f, void* stream) {
-  dispatch_set_objective(OBJ_MAKESPAN);  // (a single-kernel entry point is no concurrent forward)
   GemmArgs g = plain_gemm(in_h, 0, Wp, (long)k * Cin, B * Tout, N, k * Cin);
   g.rpb = Tout; g.a_batch = (long)Tin * Cin; g.a_row = (long)s_ * Cin;
   g.o_batch_rows = Tout; g.oh_batch_rows = Tout;
@@ -2614,7 +2612,6 @@ extern "C" int afx_k_conv_gemm(int dtype, const void* in_h, const void* Wp, int 
 extern "C" int afx_k_conv_ln_act(int dtype, const void* in_h, const void* Wp, int B, int Tin, int Tout, int Cin,
                                  int k, int s_, const float* bias, const float* gamma, const float* beta, float eps,
                                  int act, float* out_f, void* out_h, void* stream) {
-  dispatch_set_objective(OBJ_MAKESPAN);  // (a single-kernel entry point is no concurrent forward)
   GemmArgs g = plain_gemm(in_h, 0, Wp, (long)k * Cin, B * Tout, 512, k * Cin);
   g.rpb = Tout; g.a_batch = (long)Tin * Cin; g.a_row = (long)s_ * Cin;
   g.o_batch_rows = Tout; g.oh_batch_rows = Tout;
@@ -2784,7 +2781,8 @@ extern "C" int afx_engine_get(afx_handle h, const char* key, int* value) {
 }
 // The launch plan of a product, from host arithmetic alone (no device, no handle): what launch_gemm would do with it.
 // flags: 1 fused LayerNorm epilogue (the conv layers), 2 split precision (K counts fp32 elements), 4 an activation outside the
-// lean epilogue (swish / selu), 8 never the deep 128x64 tile.  objective: 0 makespan, 1 CU time, -1 the calling thread's.
+// lean epilogue (swish / selu), 8 never the deep 128x64 tile.  objective: 0 makespan, 1 CU time, -1 what a launch outside any
+// forward gets (the forced "dispatch_objective" knob when it is set, else makespan).
 // out[8]: family, instance, tile rows, tile slots, split rows, remainder instance, remainder tile slots, objective used.
 extern "C" int afx_gemm_plan(int M, int N, int K, int rpb, int kchunk, int groups, int flags, int objective, int* out) {
   if (!out || M <= 0 || N <= 0 || K <= 0 || groups <= 0) return fail("afx_gemm_plan: bad arguments");
@@ -2795,14 +2793,14 @@ extern "C" int afx_gemm_plan(int M, int N, int K, int rpb, int kchunk, int group
   if (flags & 2) { g.k1 = K; g.K = 2 * K; g.kchunk = 2 * g.kchunk; }
   if (flags & 4) g.act = ACT_SWISH;
   if (flags & 8) g.no_deep = 1;
-  const int obj = objective < 0 ? dispatch_objective() : (objective ? OBJ_CU_TIME : OBJ_MAKESPAN);
+  const int obj = objective < 0 ? dispatch_objective(OBJ_MAKESPAN) : (objective ? OBJ_CU_TIME : OBJ_MAKESPAN);
   const GemmPlan pl = gemm_plan(g, groups, obj);
   out[0] = pl.family; out[1] = pl.tile; out[2] = pl.rows; out[3] = (int)pl.tiles;
   out[4] = pl.split_rows; out[5] = pl.rem_tile; out[6] = (int)pl.rem_tiles; out[7] = obj;
   return 0;
 }
 extern "C" int afx_conf_chain_waves(int M, int objective) {
-  return conf_chain_waves_of(M, objective < 0 ? dispatch_objective() : (objective ? OBJ_CU_TIME : OBJ_MAKESPAN));
+  return conf_chain_waves_of(M, objective < 0 ? dispatch_objective(OBJ_MAKESPAN) : (objective ? OBJ_CU_TIME : OBJ_MAKESPAN));
 }
 extern "C" int afx_k_pre_emphasis(const float* x, int B, int L, float coef, float* y, void* stream) {
   KRET(launch_pre_emphasis(x, B, L, coef, y, (hipStream_t)stream));

@@ -1812,16 +1812,14 @@ void gemm_set_split(int v) { g_split = v; }
 static int g_s3_small = 0;  // A/B knob (split precision, small-M products): 0 = the fp16 dispatch's choice (deep 128x64), 1 = 128x128 2-stage, 2 = 128x64 2-stage
 void gemm_set_s3_small(int v) { g_s3_small = v; }
 // ---- the objective of a launch shape (afx_kernels.h: OBJ_MAKESPAN / OBJ_CU_TIME) ------------------------------------
-static thread_local int t_objective = OBJ_MAKESPAN;
-static int g_objective = -1;  // test / A/B knob: -1 = the calling thread's, 0 / 1 forced for every launch
+static int g_objective = -1;  // test / A/B knob: -1 = each launch's own (GemmArgs::objective), 0 / 1 forced for every launch
 // What the CU-time objective decides (A/B knob "dispatch_cu_mask").  Measured in the two-lanes form, each alone and together
 // (profiles/cu_time_dispatch_ab.txt): the height of the 256-wide tile and the chain's waves win on both models and precisions;
 // the conv tile's height and the two row splits do not beat the run-to-run spread and stay on their makespan choices.
 static int g_cu_mask = CU_GEMM8_HEIGHT | CU_CHAIN_WAVES;
-void dispatch_set_objective(int obj) { t_objective = obj == OBJ_CU_TIME ? OBJ_CU_TIME : OBJ_MAKESPAN; }
 void dispatch_force_objective(int obj) { g_objective = obj < 0 ? -1 : (obj == OBJ_CU_TIME ? OBJ_CU_TIME : OBJ_MAKESPAN); }
 void dispatch_set_cu_mask(int mask) { g_cu_mask = mask; }
-int dispatch_objective() { return g_objective >= 0 ? g_objective : t_objective; }
+int dispatch_objective(int of_launch) { return g_objective >= 0 ? g_objective : (of_launch == OBJ_CU_TIME ? OBJ_CU_TIME : OBJ_MAKESPAN); }
 bool dispatch_cu(int obj, int bit) { return obj == OBJ_CU_TIME && (g_cu_mask & bit) != 0; }
 
 // ---- the cost model of every GEMM launch shape, in one place ---------------------------------------------------------
@@ -1945,7 +1943,7 @@ static int gemm_family_of(const GemmArgs& p, int groups, int obj) {
   if (e256 <= e128) return 0;
   return plain_k(p) ? 7 : (p.k1 ? 0 : 2);  // the 8-phase kernel where its addressing applies (no chunked K)
 }
-int gemm_tile_of(const GemmArgs& p, int groups) { return gemm_family_of(p, groups, dispatch_objective()); }
+int gemm_tile_of(const GemmArgs& p, int groups) { return gemm_family_of(p, groups, dispatch_objective(p.objective)); }
 
 // Everything launch_gemm decides for (p, groups) under `obj`: family, height, the two splits.  With OBJ_MAKESPAN this is the
 // dispatch of rounds 1-4, shape for shape (tests/test_cpu_gemm_plan.py holds the table).
@@ -2081,7 +2079,7 @@ const char* launch_gemm(const GemmArgs& p_in, int dtype, int groups, hipStream_t
   if (const char* e = check_gemm(p_in, groups)) return e;
   GemmArgs p = p_in;
   p.map_mode = g_map_override >= 0 ? g_map_override : 2;
-  const GemmPlan pl = gemm_plan(p, groups, dispatch_objective());
+  const GemmPlan pl = gemm_plan(p, groups, dispatch_objective(p.objective));
   p.a_nt = g_ant_override >= 0 ? g_ant_override : (pl.tile == 3 ? 1 : 0);
   p.dbg_nodma = g_nodma;
   if (pl.split_rows > 0 && pl.tile == 7) {  // rows [0, m1) on the 8-phase kernel, rows [m1, M) on the 128x128 kernel

@@ -81,6 +81,10 @@ struct GemmArgs {
   // the inverse of the A operand's activation scale) before the bias, and writes `out_h` as FP32 (the engine's operand
   // buffers are fp32 in that mode).
   int k1;
+  // host only like no_deep, OBJ_* below: what the launch shape is chosen for (set by the engine's wrapper from its call; 0 =
+  // makespan).  It sits in the four bytes of padding before the next pointer: no field a kernel reads moves, the compiled
+  // kernels are byte for byte those of the struct without it
+  int objective;
   const float* pre_scale;
   float a_inv;
   // split precision, output side: oh_pairs != 0 = `out_h` receives the result AS the next product's A operand -- the pair
@@ -94,20 +98,21 @@ const char* launch_gemm(const GemmArgs& p, int dtype, int groups, hipStream_t s)
 const char* launch_gemm_rows(const GemmArgs& p, int dtype, hipStream_t s);  // out_h rows from GemmArgs::oh_rows (afx_gemm.hip)
 const char* launch_gemm_f32(const GemmArgs& p, int groups, hipStream_t s);  // afx_gemm_f32.hip (DT_FP32 operands)
 bool gemm_is_narrow(int N);  // true: the 128x64 tile instance serves this N
-int gemm_tile_of(const GemmArgs& p, int groups);  // tile family id under the calling thread's objective (afx_gemm.hip)
+int gemm_tile_of(const GemmArgs& p, int groups);  // tile family id under p.objective (afx_gemm.hip)
 // ---- what a launch shape is chosen FOR (afx_gemm.hip) ------------------------------------------------------------
 // OBJ_MAKESPAN: the launch alone on an empty chip -- rounds x unit (every choice up to round 4 was fitted to this).
 // OBJ_CU_TIME: a second forward is queued on another stream and takes the CUs this launch leaves free, so the step
 // pays workgroups x unit (CUs held x time) and a shorter makespan bought with more tiles is a loss.
-// The objective is a property of the CALL: begin_call (afx_engine.hip) copies the engine's "concurrent" switch into a
-// thread-local, the launchers read it; the single-kernel entry points reset it.  Either way the rows are the same bits.
+// The objective is a property of the CALL and travels with the launch arguments: the engine's call context (afx_engine.hip,
+// struct Call) reads the handle's "concurrent" switch once and its wrappers put the value into GemmArgs::objective and
+// ConfChainArgs::objective; a launch that sets neither (the single-kernel entry points) is shaped by makespan.  Either way
+// the rows are the same bits.
 enum { OBJ_MAKESPAN = 0, OBJ_CU_TIME = 1 };
 // the decisions the CU-time objective may change, one bit each ("dispatch_cu_mask", an A/B knob; default: the first two)
 enum { CU_GEMM8_HEIGHT = 1, CU_CHAIN_WAVES = 2, CU_ROWLN_HEIGHT = 4, CU_SPLITS = 8 };
-void dispatch_set_objective(int obj);    // this thread's objective for the launches that follow
 void dispatch_force_objective(int obj);  // test / A/B knob: -1 = per call (default), 0 / 1 = every launch of the process
 void dispatch_set_cu_mask(int mask);
-int dispatch_objective();                // the objective in force on this thread
+int dispatch_objective(int of_launch);   // the objective a launch runs under: the forced knob when set, else its own
 bool dispatch_cu(int obj, int bit);      // does objective `obj` decide `bit` by CU time?
 // The whole launch plan of a product, host arithmetic only (no device): what launch_gemm does with (p, groups).
 struct GemmPlan {
@@ -403,6 +408,7 @@ struct ConfChainArgs {
   const void *ff_w1, *ff_w2;                       // feed-forward module (stages 0 and 2): packed [4E][Ep], [E][FFp]
   const void* w_a;                                 // stage 0: W_qkv [3E][Ep]; 1: W_out [E][Ep]; 2: W_pw2 [E][ld_w_a]
   int ld_w_a;
+  int objective;                                   // host only, OBJ_*: set by the engine from its call (0 = makespan)
   const void* w_b;                                 // stage 1: W_pw1 [4E][Ep]
   const void* in_h;                                // stage 1: attention output (M, ld_in_h); 2: depthwise-conv output
   long ld_in_h;

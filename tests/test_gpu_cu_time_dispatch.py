@@ -117,10 +117,69 @@ def test_engine_lanes_run_under_cu_time_and_forward_does_not(mods):
     assert eng.last_objective == 0  # a plain forward after set_issue("lanes"): today's plan
     assert torch.equal(again, want)
     out = (C.c_int * 8)()
-    check(lib.afx_gemm_plan(B * 49, 3072, 1024, 0, 0, 1, 0, -1, out))  # the calling thread's objective is makespan again
+    check(lib.afx_gemm_plan(B * 49, 3072, 1024, 0, 0, 1, 0, -1, out))  # a query outside any call: makespan, whatever ran before
     assert out[7] == 0
     outs = [eng.forward_overlapped(wave) for _ in range(2)]  # (issues the lanes form now)
     assert eng.last_objective == 1
     eng.join()
     torch.cuda.synchronize()
     assert all(torch.equal(o, want) for o in outs)
+
+
+def test_call_state_belongs_to_the_call_and_the_handle(mods):
+    """Two engines interleaved on ONE thread share nothing: the objective, the "gemm_small_deep" switch, the profiler and the
+    split-precision scratch of a call come from its handle and its workspace, never from what the call before it left behind.
+
+    P (fp16x3, concurrent = 1, profiling on) and Q (fp16, gemm_small_deep = 0) are 1-layer students on 3 clips of 4000 samples
+    (12 frames: the trunk's products take the small-M path, where the deep-tile switch and the pair-form scratch decide
+    something).  Every interleaved output equals the engine's solo output bit for bit, each handle reports its own objective
+    after every call, P's profile counts P's launches only, and a plan query outside any call answers makespan.  The commit
+    before the call context satisfied all of these but the last: there the query read the CU-time objective that P's call
+    had left in the thread."""
+    engine, K, synth, check, lib = mods
+    B, L = 3, 4000
+    sd = synth.model_state_dict("ConformerModel", n_layers=1)
+    P = engine.Engine("conformer", n_layers=1, dtype="fp16x3")
+    Q = engine.Engine("conformer", n_layers=1, dtype="fp16")
+    P.load_state_dict(sd)
+    Q.load_state_dict(sd)
+    P.set("concurrent", 1)
+    Q.set("gemm_small_deep", 0)
+    wave = synth.waveforms(B, L).cuda()
+    g = torch.Generator().manual_seed(11)
+    x = torch.randn(B, 12, 144, generator=g).cuda()
+    feats6 = torch.randn(B, 4, 512, generator=g).cuda()
+
+    def launches(prof):
+        return {k: v["launches"] for k, v in prof.items()}
+
+    def solo(call):  # P alone: its output and its launch counts per class
+        P.profile_begin()
+        out = call()
+        return out, launches(P.profile_end())
+
+    (p_fwd, n_fwd), (p_conf, n_conf) = solo(lambda: P.forward(wave)), solo(lambda: P.conformer(x))
+    p_step, n_step = solo(lambda: P.kv_state(B).step(feats6))  # (a fresh state: its first chunk)
+    q_fwd = Q.forward(wave)
+    assert n_fwd["rownorm_kernel"] > 0 and n_conf["conf_chain_kernel"] > 0 and n_step["mhsa_kernel"] > 0
+    assert P.last_objective == 1 and Q.last_objective == 0
+
+    def plan_objective():
+        out = (C.c_int * 8)()
+        check(lib.afx_gemm_plan(B * 12, 3072, 1024, 0, 0, 1, 0, -1, out))
+        return out[7]
+
+    kv = P.kv_state(B)
+    P.profile_begin()
+    for who, call, want in [(P, lambda: P.forward(wave), p_fwd), (Q, lambda: Q.forward(wave), q_fwd),
+                            (P, lambda: P.conformer(x), p_conf), (Q, lambda: Q.forward(wave), q_fwd),
+                            (P, lambda: kv.step(feats6), p_step), (Q, lambda: Q.forward(wave), q_fwd),
+                            (P, lambda: P.forward(wave), p_fwd)]:
+        got = call()
+        assert P.last_objective == 1 and Q.last_objective == 0
+        if who is P:
+            assert plan_objective() == 0
+        for a, b in zip(got if isinstance(got, tuple) else (got,), want if isinstance(want, tuple) else (want,)):
+            assert torch.equal(a, b)
+    mixed = launches(P.profile_end())
+    assert mixed == {k: 2 * n_fwd[k] + n_conf[k] + n_step[k] for k in n_fwd}
