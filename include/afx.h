@@ -485,6 +485,46 @@ int afx_k_jitter_noise(float* jring, int S, int J, const int* hdr, int rows, int
                        void* stream);
 int afx_k_jitter_noise_rates(float* jring, int S, int Js, const int* hdr, int rows, int max_n, const afx_jitter_rate* rates,
                              int n_rates, unsigned seed, const float* amp, void* stream);
+/* Pitch-period concealment (afx/jitter.py conceal="pitch_sync"): a released gap repeats the last PITCH PERIOD of E, found by an
+ * exact integer search, under a hold and a fade.  afx_k_jitter_conceal and its mode argument are unchanged (mode 2 stays
+ * refused); these are two verbs of their own.  Lengths in the slot's input-rate samples: lags Pmin..Pmax, correlation window
+ * Wc, fallback period P0 in [Pmin, Pmax], hold Hd, fade F, G = Hd + F, history Lh = Pmax + Wc.  For a gap with origin a, d = i - a:
+ *         q[j]  = quant(E[j]) for j in [a - Lh, a);  E[<0] = 0 (the ring's zeros after a reset)
+ *         quant(x): y = x * 32768f (one fp32 multiply);  NaN -> 0;  else clamp(rint(y) (ties to even), -32768, 32767), an integer
+ *         for p in Pmin..Pmax:
+ *             c(p) = sum_{j in [a-Wc, a)} q[j] * q[j-p]           (exact integers: any summation order gives the same number)
+ *             e(p) = sum_{j in [a-Wc, a)} q[j-p]^2
+ *             s(p) = (double(c) * double(c)) / double(e)  if c > 0 and e > 0, else no candidate
+ *                    (one fp64 multiply and one fp64 divide, each correctly rounded)
+ *         p* = the p with the largest s(p), the smallest such p on a tie;  P0 if there is no candidate
+ *         E[a + d] = gain[d] * E[a - p* + (d mod p*)]  for d < G   (one fp32 multiply of two stored fp32 values);  0 for d >= G
+ *         gain[d] = 1 for d < Hd;  fp32(1 - (d - Hd)/F) for Hd <= d < G    (computed in float64, rounded once)
+ * afx_k_jitter_pitch: the estimate.  hdr (device, rows x 2 int32), per row: slot, a mod J, for the gaps whose origin is released
+ *     now; rows of one launch are of distinct slots.  One workgroup per row writes p* to period[slot] (device, (S,) int32: state
+ *     of the slot's open gap, never read back).  A row is skipped whole, writing nothing, when its slot is outside [0, S), its
+ *     column outside [0, J) or Lh > J.
+ * afx_k_jitter_conceal_period: the synthesis.  hdr as for afx_k_jitter_conceal (rows x 4 int32: slot, a mod J, d_lo, d_hi), gain
+ *     (device, max(G, 1) fp32), p* read from period[slot]; a stored value outside [Pmin, Pmax] is read as P0, so a row never
+ *     reads outside [a - Pmax, a).  max_n = the largest d_hi - d_lo; a row needs d_hi + Pmax <= J (source and written columns
+ *     disjoint), else it is skipped whole.
+ * The _rates forms: rows end in their rate index (3 and 5 int32); lags (HOST, n_rates entries) is parallel to rates and travels
+ *     by value like it.  Of a rate J is read, and by the synthesis fade (its gain table, Hd_f + F_f entries) and F; a row with a
+ *     rate index out of range, or Lh_f > J_f, is skipped whole.  The one-rate entry points are the table of one entry.
+ * Refused with nothing launched, each refusal naming its entry point: a null jring / hdr / period / table (synthesis: gain), rows
+ *     outside 1..65535, Pmin < 1, Pmax < Pmin, Wc < 1, P0 outside [Pmin, Pmax], a negative hold or fade, no rate whose ring holds
+ *     Lh (estimate) or max_n + Pmax (synthesis), an Lh beyond 32000 samples (64 KB of LDS), and what afx_k_jitter_place_rates
+ *     refuses of a table. */
+typedef struct afx_jitter_lags {
+  int Pmin, Pmax, Wc, P0, Hd;
+} afx_jitter_lags;
+int afx_k_jitter_pitch(const float* jring, int S, int J, const int* hdr, int rows, int Pmin, int Pmax, int Wc, int P0, int* period,
+                       void* stream);
+int afx_k_jitter_pitch_rates(const float* jring, int S, int Js, const int* hdr, int rows, const afx_jitter_rate* rates,
+                             const afx_jitter_lags* lags, int n_rates, int* period, void* stream);
+int afx_k_jitter_conceal_period(float* jring, int S, int J, const int* hdr, int rows, int max_n, const float* gain,
+                                const int* period, int Pmin, int Pmax, int P0, int Hd, int F, void* stream);
+int afx_k_jitter_conceal_period_rates(float* jring, int S, int Js, const int* hdr, int rows, int max_n, const afx_jitter_rate* rates,
+                                      const afx_jitter_lags* lags, int n_rates, const int* period, void* stream);
 /* Speech gate (afx/vad.py): an energy gate with noise-floor tracking and hangover over frames of `frame` 16 kHz samples
  * (160 = 10 ms), per slot.  Constants, fp32: e_floor (the mean-square floor times frame), ratio > 1, rise >= 1, and
  * nf_min = e_floor / ratio (one fp32 division); hang >= 0 frames.  State per slot: nf (S,) fp32, +inf for a new stream, and

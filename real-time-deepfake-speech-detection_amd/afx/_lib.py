@@ -41,6 +41,11 @@ class JitterRate(C.Structure):
                 ("P", C.c_int), ("F", C.c_int)]
 
 
+class JitterLags(C.Structure):
+    """afx_jitter_lags: one entry of the host table parallel to the rates of afx_k_jitter_pitch_rates / _conceal_period_rates."""
+    _fields_ = [("Pmin", C.c_int), ("Pmax", C.c_int), ("Wc", C.c_int), ("P0", C.c_int), ("Hd", C.c_int)]
+
+
 # symbol -> (restype, argtypes); must list every function include/afx.h declares
 SIGNATURES = {
     "afx_create": (_I, [C.POINTER(Config), C.POINTER(_P)]),
@@ -119,6 +124,10 @@ SIGNATURES = {
     "afx_k_jitter_release_rates": (_I, [_P, _I, _I, _P, _I, _P, _I, _P, _P, _I, _P]),
     "afx_k_jitter_noise": (_I, [_P, _I, _I, _P, _I, _I, C.c_uint, _P, _P]),
     "afx_k_jitter_noise_rates": (_I, [_P, _I, _I, _P, _I, _I, _P, _I, C.c_uint, _P, _P]),
+    "afx_k_jitter_pitch": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "afx_k_jitter_pitch_rates": (_I, [_P, _I, _I, _P, _I, _P, _P, _I, _P, _P]),
+    "afx_k_jitter_conceal_period": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "afx_k_jitter_conceal_period_rates": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _I, _P, _P]),
     "afx_k_gate": (_I, [_P, _I, _I, _P, _I, _F, _F, _F, _I, _P, _P, _P, _I, _I, _P, _P, _P]),
     "afx_k_gate_la": (_I, [_P, _I, _I, _P, _I, _F, _F, _F, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P]),
     "afx_k_gate_tone": (_I, [_P, _I, _I, _P, _I, _F, _F, _F, _I, _P, _I, _F, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),

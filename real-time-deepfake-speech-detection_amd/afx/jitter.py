@@ -82,6 +82,43 @@ did.  ``feed_rtp`` knows RFC 3551's static audio types (``afx.rtp.STATIC_AUDIO_F
 (rate, encoding) is listed at the slot's rate.  The ring is decoded, so a state does not say which codec fed it.  Out of
 scope: stereo (PT 10) / channel de-interleave, G.722 / G.726 and other codecs whose state runs across packets.
 
+Pitch-period concealment: ``conceal="pitch_sync"`` repeats the last PITCH PERIOD of E instead of a fixed 10 ms, as telephone
+endpoints do (G.711 Appendix I and its descendants), so a gap in voiced speech carries no discontinuity at every wrap and no
+100 Hz buzz.  All lengths in the slot's input-rate samples at rate r; module constants, engineering defaults, NOT tuned:
+Pmin = r // 400 (2.5 ms, 400 Hz), Pmax = 3 r // 200 (15 ms, 66.7 Hz), Wc = r // 50 (the 20 ms correlation window)
+(``pitch_lags``); P0 = r // 100, the fallback period (``period``, inside [Pmin, Pmax]); Hd = r // 100, 10 ms at full level
+(``hold``); F = r // 20, the fade (``fade``); G = Hd + F; Lh = Pmax + Wc.  A released gap with origin a (the start of the maximal
+run of non-received indices, as above) is, with d = i - a:
+      q[j]  = quant(E[j]) for j in [a - Lh, a);  E[<0] = 0
+      quant(x): y = x * 32768f (one fp32 multiply);  NaN -> 0;  else clamp(rint(y) (ties to even), -32768, 32767), an integer
+      for p in Pmin..Pmax:
+          c(p) = sum_{j in [a-Wc, a)} q[j] * q[j-p]                       (exact integers, < 2**43)
+          e(p) = sum_{j in [a-Wc, a)} q[j-p]**2
+          s(p) = (float64(c) * float64(c)) / float64(e)   if c > 0 and e > 0, else "no candidate"
+      p* = the p with the largest s(p), the smallest such p on a tie;  P0 if there is no candidate
+      E[a + d] = gain[d] * E[a - p* + (d mod p*)]  for d < G  (one fp32 multiply of two stored fp32 values);  0 for d >= G
+      gain[d] = 1 for d < Hd;  fp32(1 - (d - Hd)/F) for Hd <= d < G   (computed in float64, rounded once)
+The search is exact integer arithmetic, so any summation order gives the same numbers; the floating-point operations are one
+fp32 multiply per written sample and, per lag, one float64 multiply and one float64 divide, each correctly rounded.  p* is fixed
+when index a is released, from E as it stands then (it may hold an earlier gap's concealed samples or comfort noise), and holds
+for the whole gap, however many calls and rounds release it.  Received samples are never modified; with comfort noise the loss
+part before a mark is concealed by this rule, counted from the run's origin; ``stats()`` counts what it counts.
+``quantize``, ``pitch_reference(history, rate)`` and ``gain_table(hold, fade)`` are the statement in numpy.
+Device side: two verbs of their own (``afx_k_jitter_conceal`` keeps refusing any mode but 0 and 1).  ``afx_k_jitter_pitch`` (rows
+of (slot, a mod J [, rate index]): one workgroup per gap whose origin is released) writes p* to ``jperiod`` ((S,) int32, device
+state: the host never learns it, nothing is read back); ``afx_k_jitter_conceal_period`` is the conceal launch with the row's
+period read from there (a stored value outside [Pmin, Pmax] reads as P0).  Plan: per rank, a ("pitch", rows, Lh) op with the
+rank's d_lo = 0 rows, if any, directly before the rank's ("conceal", ...) op, so the estimate obeys the order of the gaps too.
+Sizing: lookback = max(T - 1, Pmax + max(Wc, G)) -- Pmax + Wc is the search history when a is released, Pmax + G the source of
+a gap's last audible sample -- with W and J as above and the same J-window invariant; an all-zero row is rebased past G.
+Sessions: ``reset`` zeroes the slot's period; ``export_slots`` adds ``jitter_pitch`` ((n,) int64: the period of the slot's open
+loss gap, 0 where none is open; masked on the device) and the meta ``jitter_hold`` and ``jitter_lags`` ((Pmin, Pmax, Wc)), in this
+mode only; ``import_slots`` refuses a gap younger than G whose period is outside [Pmin, Pmax]; states of different modes refuse
+each other.  ``MixedJitterScorer(..., hold_ms=)``: per rate as ``period_ms`` / ``fade_ms``; its ``jitter_params`` gain a fourth
+column, the hold.  A scorer built with "zero" or "repeat" plans, launches and exports exactly what it did.  Out of scope:
+overlap-add into released or received samples (the contract forbids modifying them), multi-period repetition for long gaps,
+voicing decisions, per-slot modes.
+
 Silence suppression (DTX) and comfort noise (RFC 3389): a sender with VAD on stops sending in a pause and says so with a
 CN packet: from this timestamp on there is silence, and the background noise is this many dB below overload.  A scorer built
 with ``comfort_noise=ComfortNoise(seed)`` plays noise of that level where a scorer without it conceals a loss.  Opt-in: a
@@ -130,7 +167,7 @@ import torch
 
 from . import rtp
 from ._layer import StreamState, _on, check_pending, export_pending, import_pending, peel, rows_on, wrap
-from ._lib import JitterRate, call_on, check, lib, ptr
+from ._lib import JitterLags, JitterRate, call_on, check, lib, ptr
 from .codecs import CODECS
 from .ingest import (_MAX_SAMPLES, _SAMPLE, _UNIT, ENCODINGS, MAX_FORMATS, _at, _encoding, _format, device_encoding, expand_zone, layout,
                      with_expand)
@@ -138,8 +175,9 @@ from .resample import FILTER_ID, Resampler
 from .streaming import _Front
 
 JITTER_FORMAT = 1  # layout of the jitter part of a StreamState: import_slots refuses any other
-CONCEAL = ("zero", "repeat")  # the library's mode numbers 0, 1
+CONCEAL = ("zero", "repeat", "pitch_sync")  # "zero" and "repeat": the library's mode numbers 0, 1; "pitch_sync": verbs of its own
 PLACE_HDR, CONCEAL_HDR, RELEASE_HDR = 4, 4, 8  # int32 per row of the three tables (include/afx.h)
+PITCH_HDR, PITCH_RATES_HDR = 2, 3  # afx_k_jitter_pitch / _pitch_rates: slot, column of the gap origin [, rate index]
 PLACE_MIXED_HDR = 5  # afx_k_jitter_place_mixed: a place row, then its encoding's number
 PLACE_RATES_HDR, CONCEAL_RATES_HDR = 6, 5  # afx_k_jitter_place_rates / _conceal_rates: the row, then its rate's index
 STATS = ("received", "late", "duplicate", "concealed", "out_of_order")
@@ -161,6 +199,44 @@ def _nonneg_int(v, name, least=0):
     if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < least:
         raise ValueError(f"{name}: an integer >= {least}, got {v!r}")
     return int(v)
+
+
+def pitch_lags(rate):
+    """(Pmin, Pmax, Wc) of "pitch_sync" at ``rate`` Hz, in samples: the lags of 400 Hz and 66.7 Hz and the 20 ms correlation
+    window (module docstring; engineering defaults, not tuned)."""
+    return rate // 400, 3 * rate // 200, rate // 50
+
+
+def quantize(x):
+    """``quant`` of "pitch_sync" (module docstring): fp32 samples -> the integers the pitch search runs on (int64 array)."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        y = np.asarray(x, dtype=np.float32) * np.float32(32768)
+        return np.where(np.isnan(y), np.float32(0), np.clip(np.rint(y), -32768, 32767)).astype(np.int64)
+
+
+def gain_table(hold, fade):
+    """``gain`` of "pitch_sync": (hold + fade,) fp32, 1 for ``hold`` samples, then fp32(1 - (d - hold)/fade)."""
+    d = np.arange(hold + fade, dtype=np.float64)
+    return np.where(d < hold, 1.0, 1.0 - (d - hold) / max(fade, 1)).astype(np.float32)
+
+
+def pitch_reference(history, rate, period=None):
+    """p* of "pitch_sync" for a gap at ``rate`` Hz whose origin follows ``history`` (fp32, the samples of E before it, oldest
+    first; the last Pmax + Wc are read, zeros stand before a shorter one); ``period``: the fallback P0, default rate // 100.
+    Operation by operation what ``afx_k_jitter_pitch`` does: exact integer sums, one float64 multiply and divide per lag."""
+    Pmin, Pmax, Wc = pitch_lags(rate)
+    best, best_s, Lh = rate // 100 if period is None else period, None, Pmax + Wc
+    h = quantize(np.asarray(history, dtype=np.float32).reshape(-1)[-Lh:])
+    q = np.zeros(Lh, dtype=np.int64)
+    q[Lh - h.size:] = h
+    for p in range(Pmin, Pmax + 1):
+        ref = q[Pmax - p:Lh - p]
+        c, e = int(q[Pmax:] @ ref), int(ref @ ref)
+        if c > 0 and e > 0:
+            s = np.float64(c) * np.float64(c) / np.float64(e)
+            if best_s is None or s > best_s:  # (ascending p: of equal scores the smallest lag stays)
+                best, best_s = p, s
+    return best
 
 
 class ComfortNoise:
@@ -271,7 +347,7 @@ def _merge(ivs, new):
 
 
 class Plan:
-    """What a call will do: ``ops`` (the launches, in order: ("place" | "noise" | "conceal" | "release", int32 rows, largest row) and
+    """What a call will do: ``ops`` (the launches, in order: ("place" | "noise" | "pitch" | "conceal" | "release", int32 rows, largest row) and
     ("pop", (A, 2) table, slots)), ``counts`` (hops per named row) and ``book`` (the bookkeeping after it)."""
 
     def __init__(self, ops, slots, counts, book):
@@ -284,8 +360,11 @@ class JitterScorer(_Front):
     module docstring for the contract.
 
     ``depth``: the playout delay in input samples (60 ms is common; 0 is legal; the filter's ``delay`` comes on top of it).
-    ``conceal``: "repeat" or "zero".  ``period``: the repeat period P in input samples, default 10 ms (input_rate // 100).  ``fade``: the fade length F in
-    input samples, default 3 P (30 ms).  ``max_pending``: the whole hops a slot may buffer between ``feed(..., score=False)``
+    ``conceal``: "repeat", "zero" or "pitch_sync".  ``period``: the repeat period P in input samples, default 10 ms (input_rate // 100).  ``fade``: the fade length F in
+    input samples, default 3 P (30 ms).  With "pitch_sync" (module docstring) ``period`` is the fallback P0 of the pitch search
+    and must lie in its lags, ``fade`` defaults to 50 ms and ``hold`` (10 ms; this mode only) is the full-level part before the
+    fade; ``lags`` = (Pmin, Pmax) and ``corr`` = Wc are the search's range and window.
+    ``max_pending``: the whole hops a slot may buffer between ``feed(..., score=False)``
     and ``drain``.  ``ts_bits``: 32 (default) unwraps each timestamp to the value nearest the slot's ``hi``, so a stream
     crossing 2**32 is seamless; None takes absolute indices.  ``comfort_noise``: a ``ComfortNoise``, for calls with silence
     suppression (module docstring); None: silence marks and RTP payload type 13 are refused.
@@ -297,7 +376,7 @@ class JitterScorer(_Front):
     _rated = False  # (MixedJitterScorer: the rows of a plan carry their slot's rate index)
 
     def __init__(self, scorer, input_rate, encoding, depth, conceal="repeat", period=None, fade=None, max_pending=4, ts_bits=32,
-                 comfort_noise=None):
+                 comfort_noise=None, hold=None):
         if isinstance(encoding, str):
             self.encodings, self._mixed = (_encoding(encoding),), False
         else:
@@ -311,10 +390,21 @@ class JitterScorer(_Front):
         max_pending = self._checked(conceal, max_pending, ts_bits, comfort_noise)
         super().__init__(scorer, input_rate)
         self.period = self.fade_len = 0  # (no part of the "zero" function: not recorded in a state either)
+        self.hold, self.lags, self.corr = 0, (0, 0), 0  # (parts of the "pitch_sync" function only)
+        if hold is not None and conceal != "pitch_sync":
+            raise ValueError(f'hold: a part of conceal="pitch_sync", not of {conceal!r}')
         if conceal == "repeat":
             self.period = _nonneg_int(self.input_rate // 100 if period is None else period, "period", 1)
             self.fade_len = _nonneg_int(3 * self.period if fade is None else fade, "fade")
-        self._size([self.rs], [self.encodings], [self.depth], [self.period], [self.fade_len], max_pending)
+        elif conceal == "pitch_sync":
+            Pmin, Pmax, self.corr = pitch_lags(self.input_rate)
+            self.lags = (Pmin, Pmax)
+            self.period = _nonneg_int(self.input_rate // 100 if period is None else period, "period", 1)
+            if not Pmin <= self.period <= Pmax:
+                raise ValueError(f"period {self.period}: the fallback of the pitch search lies in its lags, {Pmin}..{Pmax}")
+            self.fade_len = _nonneg_int(self.input_rate // 20 if fade is None else fade, "fade")
+            self.hold = _nonneg_int(self.input_rate // 100 if hold is None else hold, "hold")
+        self._size([self.rs], [self.encodings], [self.depth], [self.period], [self.fade_len], max_pending, [self.hold])
         self.L, self.M, self.J, self.fade = self.rs.L, self.rs.M, self.Js, self._fades[0]
         self.lookback, self.W = int(self._rlookback[0]), int(self._rW[0])
 
@@ -331,10 +421,10 @@ class JitterScorer(_Front):
         self.conceal, self.ts_bits = conceal, None if ts_bits is None else int(ts_bits)
         return max_pending
 
-    def _size(self, rs, encs_at, depth, P, F, max_pending):
-        """The table of this scorer's rates, one entry per Resampler of ``rs`` (int64 arrays over the rates; ``depth``, ``P``
-        and ``F`` in each rate's own samples, ``encs_at`` the encodings listed at each), the device buffers sized from it, the
-        host table the ``_rates`` launches take, and every slot at rate index 0."""
+    def _size(self, rs, encs_at, depth, P, F, max_pending, hold):
+        """The table of this scorer's rates, one entry per Resampler of ``rs`` (int64 arrays over the rates; ``depth``, ``P``,
+        ``F`` and ``hold`` in each rate's own samples, ``encs_at`` the encodings listed at each), the device buffers sized from
+        it, the host table the ``_rates`` launches take, and every slot at rate index 0."""
         scorer = self.scorer
         arr = lambda v: np.array(v, dtype=np.int64)
         self._rs, self._encs_at = list(rs), [tuple(e) for e in encs_at]
@@ -348,7 +438,13 @@ class JitterScorer(_Front):
         self._rdepth, self._rP, self._rF = arr(depth), arr(P), arr(F)
         # the sizing invariant (module docstring), per rate: J = lookback + W, W >= depth; the slack beyond depth is what a
         # round can place and release at once (one hop of input: an ordinary packet never takes a second round)
-        self._rlookback = np.maximum(arr([0 if x.identity else x.T - 1 for x in rs]), self._rP + self._rF)
+        pitch = self.conceal == "pitch_sync"
+        self._rHd = arr(hold)
+        self._rG = self._rHd + self._rF  # the samples of a gap that are not zeros (F itself outside "pitch_sync")
+        self._rPmin, self._rPmax, self._rWc = (arr(v) for v in zip(*(pitch_lags(r) if pitch else (0, 0, 0) for r in self._rates)))
+        # the source a gap reads until it is silent; "pitch_sync": also the search history Pmax + Wc when its origin is released
+        back = self._rPmax + np.maximum(self._rWc, self._rG) if pitch else self._rP + self._rF
+        self._rlookback = np.maximum(arr([0 if x.identity else x.T - 1 for x in rs]), back)
         self._rW = self._rdepth + -(-scorer.hop * self._rM // self._rL) + 1
         self._rJ = self._rlookback + self._rW
         self._rdelay = np.array([x.delay for x in rs], dtype=np.float64)
@@ -357,7 +453,14 @@ class JitterScorer(_Front):
             raise ValueError("depth + period + fade: less than 2**30 samples")
         self._new_ring(max_pending)
         self.jring = torch.zeros(scorer.S, self.Js, dtype=torch.float32, device=scorer.device)
-        self._fades = [_fade_table(int(f), scorer.device) for f in self._rF]  # one device table per rate
+        if pitch:  # one gain table per rate, and the period of each slot's open gap (device state: written by the estimate)
+            self._fades = [torch.from_numpy(gain_table(int(h), int(f)) if h + f else np.ones(1, np.float32)).to(scorer.device)
+                           for h, f in zip(self._rHd, self._rF)]
+            self.jperiod = torch.zeros(scorer.S, dtype=torch.int32, device=scorer.device)
+            self._lags = (JitterLags * len(rs))(*(JitterLags(*(int(a[i]) for a in (self._rPmin, self._rPmax, self._rWc, self._rP, self._rHd)))
+                                                  for i in range(len(rs))))
+        else:
+            self._fades = [_fade_table(int(f), scorer.device) for f in self._rF]  # one device table per rate
         self._amp = None if self.cn is None else torch.from_numpy(self.cn.amp).to(scorer.device)
         self._table = (JitterRate * len(rs))()  # (pointers: the tensors above)
         for i, (t, x) in enumerate(zip(self._table, rs)):
@@ -394,8 +497,9 @@ class JitterScorer(_Front):
 
     # ---- planning (host arithmetic only) -----------------------------------------------------------------------------
     def _geometry(self, rate):
-        """(L, M, J, W, F, depth, lookback) at the rate indices ``rate``: int64 arrays over them."""
-        return tuple(a[rate] for a in (self._rL, self._rM, self._rJ, self._rW, self._rF, self._rdepth, self._rlookback))
+        """(L, M, J, W, G, depth, lookback) at the rate indices ``rate``: int64 arrays over them (G: the samples of a gap that
+        are not zeros: the fade length F, in "pitch_sync" hold + F)."""
+        return tuple(a[rate] for a in (self._rL, self._rM, self._rJ, self._rW, self._rG, self._rdepth, self._rlookback))
 
     def _unwrap(self, t, ref):
         """Timestamp t as the absolute value nearest ref (ts_bits), or as it is."""
@@ -564,6 +668,7 @@ class JitterScorer(_Front):
         U = slot[first]  # the named slots, once each, in the order they were first named
         rate = self._rate_of[U]
         L, M, J, W, F, depth, _ = self._geometry(rate)  # (int64 arrays over U, each slot with its own rate's values)
+        pitch, Lh = self.conceal == "pitch_sync", (self._rPmax + self._rWc)[rate]
         cur = b.next[U].copy()
         if mode == "feed":
             tgt = np.maximum(cur, b.hi[U] - depth)
@@ -619,7 +724,7 @@ class JitterScorer(_Front):
             if rows:
                 rows = np.array(rows, dtype=np.int64)
                 ops.append(("noise", rows.astype(np.int32), int(rows[:, 2].max())))  # (lo32 keeps its bits as an int32)
-            ranks = []
+            ranks, opens = [], []  # per rank: the conceal rows, and ("pitch_sync") the rows of the gaps whose origin is released
             for u, gl in gaps.items():  # the gaps inside [cur, cur + m) of the slots that have any, by rank within the slot
                 c0, c1, s, rank, Fu, Ju = int(cur[u]), int(cur[u] + m[u]), int(U[u]), 0, int(F[u]), int(J[u])
                 tail = (int(rate[u]),) if self._rated else ()
@@ -632,9 +737,14 @@ class JitterScorer(_Front):
                         a, d_lo, d_hi = a + d_lo - Fu, Fu, Fu + d_hi - d_lo
                     if rank == len(ranks):
                         ranks.append([])
+                        opens.append([])
                     ranks[rank].append((s, a % Ju, d_lo, d_hi) + tail)
+                    if pitch and d_lo == 0:  # p* is fixed here, from E as it stands before this rank's conceal
+                        opens[rank].append((s, a % Ju) + tail)
                     rank += 1
-            for rows in ranks:
+            for rows, first_rows in zip(ranks, opens):
+                if first_rows:
+                    ops.append(("pitch", np.array(first_rows, dtype=np.int32), int(Lh[pos[[r[0] for r in first_rows]]].max())))
                 rows = np.array(rows, dtype=np.int32)
                 ops.append(("conceal", rows, int((rows[:, 3] - rows[:, 2]).max())))
             k = np.flatnonzero(m > 0)
@@ -886,8 +996,16 @@ class JitterScorer(_Front):
                           S, J))
 
         def conceal(d, off, op):
+            if self.conceal == "pitch_sync":  # (the period of each row is the device's: what the estimate wrote for its gap)
+                check(call_on(self.jring, l.afx_k_jitter_conceal_period, ptr(self.jring), S, J, _at(d, off), len(op[1]), op[2],
+                              ptr(self.fade), ptr(self.jperiod), *self.lags, self.period, self.hold, self.fade_len))
+                return
             check(call_on(self.jring, l.afx_k_jitter_conceal, ptr(self.jring), S, J, _at(d, off), len(op[1]), op[2], ptr(self.fade),
                           self.period, self.fade_len, CONCEAL.index(self.conceal)))
+
+        def pitch(d, off, op):
+            check(call_on(self.jring, l.afx_k_jitter_pitch, ptr(self.jring), S, J, _at(d, off), len(op[1]), *self.lags, self.corr,
+                          self.period, ptr(self.jperiod)))
 
         def release(d, off, op):
             check(call_on(self.jring, l.afx_k_jitter_release, ptr(self.jring), S, J, _at(d, off), len(op[1]), op[2], taps, L, M, T,
@@ -898,7 +1016,8 @@ class JitterScorer(_Front):
                           ptr(self._amp)))
 
         return self._execute(plan.ops, plan.slots, plan.counts, pay,
-                             {"place": place, "noise": noise, "conceal": conceal, "release": release}, lambda: self._commit(plan.book))
+                             {"place": place, "noise": noise, "pitch": pitch, "conceal": conceal, "release": release},
+                             lambda: self._commit(plan.book))
 
     # ---- sessions ----------------------------------------------------------------------------------------------------
     def reset(self, slots):
@@ -908,10 +1027,22 @@ class JitterScorer(_Front):
         if idx:
             self._b.clear(idx)
             self.jring[idx] = 0.0
+            if self.conceal == "pitch_sync":
+                self.jperiod[idx] = 0
 
     def _meta(self):
         return dict(input_rate=self.input_rate, resampler=FILTER_ID, jitter=JITTER_FORMAT, jitter_depth=self.depth,
-                    jitter_conceal=self.conceal, jitter_period=self.period, jitter_fade=self.fade_len, **self._cn_meta())
+                    jitter_conceal=self.conceal, jitter_period=self.period, jitter_fade=self.fade_len, **self._cn_meta(),
+                    **self._pitch_meta(0))
+
+    def _pitch_meta(self, r):
+        """What a state says of the "pitch_sync" function at rate index r beyond period and fade (other modes: nothing)."""
+        if self.conceal != "pitch_sync":
+            return {}
+        return dict(jitter_hold=int(self._rHd[r]), jitter_lags=(int(self._rPmin[r]), int(self._rPmax[r]), int(self._rWc[r])))
+
+    def _pitch_keys(self):
+        return ("jitter_pitch",) if self.conceal == "pitch_sync" else ()
 
     def _cn_meta(self):
         return {} if self.cn is None else dict(jitter_cn=self.cn.seed)
@@ -942,6 +1073,9 @@ class JitterScorer(_Front):
             k = torch.arange(width)
             jr = self.jring[rows_on(idx, dev)[:, None], ((nxt[:, None] - lb[:, None] + k) % J[:, None]).to(dev)]
             jr.masked_fill_((k[None, :] >= (lb + held)[:, None]).to(dev), 0.0)
+            if self.conceal == "pitch_sync":  # the period of each open loss gap, masked on the device: nothing is read back
+                live = torch.from_numpy((b.gap[idx] >= 0) & (b.cn_open[idx] < 0)).to(dev)
+                more = dict(more, jitter_pitch=(self.jperiod[rows_on(idx, dev)] * live).to(torch.int64))
         ivs = [b.intervals(s) for s in idx]
         K = max([len(v) for v in ivs] + [1])
         table = np.full((len(idx), K, 2), -1, dtype=np.int64)
@@ -970,7 +1104,7 @@ class JitterScorer(_Front):
         with silence marks needs a ``ComfortNoise`` of its seed here; one without them imports with no marks."""
         idx = self.scorer._slot_list(slots, ordered=True)
         keys, mine = self._cn_part(state, self._meta())
-        inner = peel(state, _STATE_KEYS + keys, mine, "jitter-buffer part (it was not exported by a JitterScorer)")
+        inner = peel(state, _STATE_KEYS + keys + self._pitch_keys(), mine, "jitter-buffer part (it was not exported by a JitterScorer)")
         n = len(state)
         width = self.lookback + self.depth
         jr = state.tensors["jitter_ring"]
@@ -1026,16 +1160,27 @@ class JitterScorer(_Front):
                     raise ValueError("import_slots: a session's silence marks contradict its counters")
                 marks.append(v)
             cn = (marks, opened, cstats)
-        return pend, state.tensors["jitter_ring"], fill, col, stats, lists, rate, cn
+        pit = None
+        if self.conceal == "pitch_sync":  # a gap that still sounds needs the period it opened with
+            pit = state.tensors["jitter_pitch"].cpu().reshape(-1)
+            if pit.dtype != torch.int64 or pit.numel() != n:
+                raise ValueError("import_slots: jitter_pitch is (n,) int64")
+            pit = pit.numpy()
+            sounds = (gap >= 0) & (nxt - gap < self._rG[rate]) & (True if cn is None else cn[1] < 0)
+            if ((pit < 0) | (pit > self._rPmax[rate]) | (sounds & (pit < self._rPmin[rate]))).any():
+                raise ValueError("import_slots: jitter_pitch holds a period outside its rate's lags for a gap younger than hold + fade")
+        return pend, state.tensors["jitter_ring"], fill, col, stats, lists, rate, cn, pit
 
     def _install(self, idx, inner, checked):
         """The inner scorer imports ``inner`` (it refuses a foreign state before changing anything), then the named slots take
         the checked jitter part: ring columns [next - lookback, ...) at their places modulo each session's own J."""
-        pend, jr, fill, col, stats, lists, rate, cn = checked
+        pend, jr, fill, col, stats, lists, rate, cn, pit = checked
         self.scorer.import_slots(idx, inner)
         if not idx:
             return
         dev, b = self.device, self._b
+        if pit is not None:
+            self.jperiod[rows_on(idx, dev)] = torch.from_numpy(pit.astype(np.int32)).to(dev)
         _, _, J, _, _, depth, lookback = self._geometry(rate)
         own = lookback + depth  # each session's own columns of jitter_ring
         import_pending(self.ring, idx, pend)
@@ -1079,12 +1224,13 @@ class MixedJitterScorer(JitterScorer):
     and never changes between resets; everything a ``JitterScorer`` counts in input samples is, per slot, in the slot's own
     rate.  ``feed_rtp`` takes ``payload_types`` as {number: (input_rate, encoding)}.  See the module docstring for the
     contract.  ``comfort_noise``: as for ``JitterScorer``; a CN payload type maps to (input_rate, "cn"), in the slot's clock
-    (13 is (8000, "cn"), RFC 3551)."""
+    (13 is (8000, "cn"), RFC 3551).  conceal="pitch_sync": P0 = r // 100 (``period_ms`` given: period_ms * r // 1000, inside the
+    rate's lags), F = r // 20 (``fade_ms``), Hd = r // 100 (``hold_ms``: hold_ms * r // 1000; this mode only)."""
 
     _rated = True
 
     def __init__(self, scorer, formats, depth_ms, conceal="repeat", period_ms=None, fade_ms=None, max_pending=4, ts_bits=32,
-                 comfort_noise=None):
+                 comfort_noise=None, hold_ms=None):
         if isinstance(formats, (str, bytes)) or not hasattr(formats, "__len__") or not hasattr(formats, "__iter__"):
             raise ValueError("formats: a sequence of (input_rate, encoding) pairs")
         fm = tuple(_format(f) for f in formats)
@@ -1095,17 +1241,28 @@ class MixedJitterScorer(JitterScorer):
         depth_ms = _nonneg_int(depth_ms, "depth_ms")
         period_ms = None if period_ms is None else _nonneg_int(period_ms, "period_ms")
         fade_ms = None if fade_ms is None else _nonneg_int(fade_ms, "fade_ms")
+        hold_ms = None if hold_ms is None else _nonneg_int(hold_ms, "hold_ms")
         max_pending = self._checked(conceal, max_pending, ts_bits, comfort_noise)
+        if hold_ms is not None and conceal != "pitch_sync":
+            raise ValueError(f'hold_ms: a part of conceal="pitch_sync", not of {conceal!r}')
         self.scorer, self.formats, self._mixed = scorer, fm, True
-        self.depth_ms, self.period_ms, self.fade_ms = depth_ms, period_ms, fade_ms
+        self.depth_ms, self.period_ms, self.fade_ms, self.hold_ms = depth_ms, period_ms, fade_ms, hold_ms
         rates = tuple(dict.fromkeys(r for r, _ in fm))  # the distinct rates, in the order first listed
         rate = np.array(rates, dtype=np.int64)
-        P = F = np.zeros_like(rate)  # (no part of the "zero" function)
+        P = F = Hd = np.zeros_like(rate)  # (no part of the "zero" function)
         if conceal == "repeat":
             P = rate // 100 if period_ms is None else np.maximum(1, period_ms * rate // 1000)
             F = 3 * P if fade_ms is None else fade_ms * rate // 1000
+        elif conceal == "pitch_sync":
+            P = rate // 100 if period_ms is None else period_ms * rate // 1000
+            F = rate // 20 if fade_ms is None else fade_ms * rate // 1000
+            Hd = rate // 100 if hold_ms is None else hold_ms * rate // 1000
+            for r, p in zip(rates, P.tolist()):
+                if not pitch_lags(r)[0] <= p <= pitch_lags(r)[1]:
+                    raise ValueError(f"period_ms {period_ms}: {p} samples at {r} Hz, outside the lags of the pitch search, "
+                                     f"{pitch_lags(r)[0]}..{pitch_lags(r)[1]}")
         self._size([Resampler(r, scorer.device) for r in rates], [tuple(e for q, e in fm if q == r) for r in rates],
-                   depth_ms * rate // 1000, P, F, max_pending)
+                   depth_ms * rate // 1000, P, F, max_pending, Hd)
 
     # ---- per-slot quantities ---------------------------------------------------------------------------------------------
     @property
@@ -1127,6 +1284,11 @@ class MixedJitterScorer(JitterScorer):
     def fades(self):
         """(S,) int64: each slot's fade length F in its own rate's samples (0 with conceal="zero")."""
         return torch.from_numpy(self._rF[self._rate_of])
+
+    @property
+    def holds(self):
+        """(S,) int64: each slot's hold Hd in its own rate's samples (0 outside conceal="pitch_sync")."""
+        return torch.from_numpy(self._rHd[self._rate_of])
 
     @property
     def delays(self):
@@ -1189,15 +1351,25 @@ class MixedJitterScorer(JitterScorer):
 
     def _run(self, plan, pay):
         l, S, Js, nr = lib(), self.S, self.Js, len(self._rates)
+        pitched = self.conceal == "pitch_sync"
         table, mode = C.cast(self._table, C.c_void_p), CONCEAL.index(self.conceal)
+        lags = C.cast(self._lags, C.c_void_p) if pitched else None
 
         def place(d, off, op):
             check(call_on(self.jring, l.afx_k_jitter_place_rates, _at(d, 0), d.numel(), _at(d, off), len(op[1]), op[2], table, nr,
                           ptr(self.jring), S, Js))
 
         def conceal(d, off, op):
+            if pitched:
+                check(call_on(self.jring, l.afx_k_jitter_conceal_period_rates, ptr(self.jring), S, Js, _at(d, off), len(op[1]), op[2],
+                              table, lags, nr, ptr(self.jperiod)))
+                return
             check(call_on(self.jring, l.afx_k_jitter_conceal_rates, ptr(self.jring), S, Js, _at(d, off), len(op[1]), op[2], table, nr,
                           mode))
+
+        def pitch(d, off, op):
+            check(call_on(self.jring, l.afx_k_jitter_pitch_rates, ptr(self.jring), S, Js, _at(d, off), len(op[1]), table, lags, nr,
+                          ptr(self.jperiod)))
 
         def release(d, off, op):
             rows = op[1]
@@ -1211,7 +1383,8 @@ class MixedJitterScorer(JitterScorer):
                           self.cn.seed, ptr(self._amp)))
 
         return self._execute(plan.ops, plan.slots, plan.counts, pay,
-                             {"place": place, "noise": noise, "conceal": conceal, "release": release}, lambda: self._commit(plan.book))
+                             {"place": place, "noise": noise, "pitch": pitch, "conceal": conceal, "release": release},
+                             lambda: self._commit(plan.book))
 
     # ---- sessions --------------------------------------------------------------------------------------------------------
     def reset(self, slots, rates=None):
@@ -1226,12 +1399,18 @@ class MixedJitterScorer(JitterScorer):
     def _meta(self):
         return dict(resampler=FILTER_ID, jitter=JITTER_FORMAT, jitter_conceal=self.conceal, jitter_mixed=1, **self._cn_meta())
 
+    def _params(self, ri):
+        """``jitter_params`` of sessions at the rate indices ``ri``: depth, period, fade ("pitch_sync": and hold), int64."""
+        cols = [self._rdepth[ri], self._rP[ri], self._rF[ri]] + ([self._rHd[ri]] if self.conceal == "pitch_sync" else [])
+        return np.stack(cols, axis=1).reshape(len(ri), len(cols))
+
     def export_slots(self, slots):
         """``JitterScorer.export_slots`` with the per-session ``jitter_rate`` ((n,) int64, Hz) and ``jitter_params`` ((n, 3)
-        int64: depth, period, fade in the session's own rate).  No byte of the scorer changes."""
+        int64: depth, period, fade in the session's own rate; "pitch_sync": (n, 4), the fourth the hold -- the lags and the
+        correlation window are functions of the rate).  No byte of the scorer changes."""
         idx = self.scorer._slot_list(slots, ordered=True)
         ri = self._rate_of[idx]
-        params = np.stack([self._rdepth[ri], self._rP[ri], self._rF[ri]], axis=1).reshape(len(idx), 3)
+        params = self._params(ri)
         return self._export(idx, jitter_rate=torch.from_numpy(self._rrate[ri]), jitter_params=torch.from_numpy(params))
 
     def import_slots(self, slots, state):
@@ -1249,24 +1428,27 @@ class MixedJitterScorer(JitterScorer):
                 raise ValueError(f"import_slots: a session at {rate} Hz, which is none of this scorer's rates {self._rates}")
             r = self._rates.index(rate)
             mine = dict(input_rate=rate, resampler=FILTER_ID, jitter=JITTER_FORMAT, jitter_depth=int(self._rdepth[r]),
-                        jitter_conceal=self.conceal, jitter_period=int(self._rP[r]), jitter_fade=int(self._rF[r]), **self._cn_meta())
+                        jitter_conceal=self.conceal, jitter_period=int(self._rP[r]), jitter_fade=int(self._rF[r]), **self._cn_meta(),
+                        **self._pitch_meta(r))
             keys, mine = self._cn_part(state, mine)
-            inner = peel(state, _STATE_KEYS + keys, mine, what)
+            inner = peel(state, _STATE_KEYS + keys + self._pitch_keys(), mine, what)
             ri = np.full(n, r, dtype=np.int64)
         else:
             keys, mine = self._cn_part(state, self._meta())
-            inner = peel(state, _STATE_KEYS + ("jitter_rate", "jitter_params") + keys, mine, what)
+            inner = peel(state, _STATE_KEYS + ("jitter_rate", "jitter_params") + keys + self._pitch_keys(), mine, what)
             rates, params = state.tensors["jitter_rate"].cpu().reshape(-1), state.tensors["jitter_params"].cpu()
-            if rates.dtype != torch.int64 or rates.numel() != n or params.dtype != torch.int64 or tuple(params.shape) != (n, 3):
-                raise ValueError("import_slots: jitter_rate is (n,) int64, jitter_params (n, 3) int64")
+            width = 4 if self.conceal == "pitch_sync" else 3
+            if rates.dtype != torch.int64 or rates.numel() != n or params.dtype != torch.int64 or tuple(params.shape) != (n, width):
+                raise ValueError(f"import_slots: jitter_rate is (n,) int64, jitter_params (n, {width}) int64")
             missing = [r for r in rates.tolist() if r not in self._rates]
             if missing:
                 raise ValueError(f"import_slots: a session at {missing[0]} Hz, which is none of this scorer's rates {self._rates}")
             ri = np.array([self._rates.index(r) for r in rates.tolist()], dtype=np.int64)
-            here = np.stack([self._rdepth[ri], self._rP[ri], self._rF[ri]], axis=1).reshape(n, 3)
+            here = self._params(ri)
             bad = np.flatnonzero((params.numpy() != here).any(axis=1))
             if bad.size:
-                raise ValueError(f"import_slots: session {bad[0]} has depth, period, fade {params[bad[0]].tolist()}, this scorer's at "
+                names = "depth, period, fade" + ", hold" * (width == 4)
+                raise ValueError(f"import_slots: session {bad[0]} has {names} {params[bad[0]].tolist()}, this scorer's at "
                                  f"{rates[bad[0]]} Hz are {here[bad[0]].tolist()}")
         if len(idx) != n:
             raise ValueError(f"the state holds {n} sessions for {len(idx)} named slots")

@@ -2877,6 +2877,26 @@ extern "C" int afx_k_jitter_noise_rates(float* jring, int S, int Js, const int* 
                                         int n_rates, unsigned seed, const float* amp, void* stream) {
   KRET(launch_jitter_noise_rates(jring, S, Js, hdr, rows, max_n, (const JitterRateDesc*)rates, n_rates, seed, amp, (hipStream_t)stream));
 }
+extern "C" int afx_k_jitter_pitch(const float* jring, int S, int J, const int* hdr, int rows, int Pmin, int Pmax, int Wc, int P0,
+                                  int* period, void* stream) {
+  KRET(launch_jitter_pitch(jring, S, J, hdr, rows, Pmin, Pmax, Wc, P0, period, (hipStream_t)stream));
+}
+extern "C" int afx_k_jitter_pitch_rates(const float* jring, int S, int Js, const int* hdr, int rows, const afx_jitter_rate* rates,
+                                        const afx_jitter_lags* lags, int n_rates, int* period, void* stream) {
+  static_assert(sizeof(afx_jitter_lags) == sizeof(JitterLagDesc), "afx_jitter_lags is JitterLagDesc");
+  KRET(launch_jitter_pitch_rates(jring, S, Js, hdr, rows, (const JitterRateDesc*)rates, (const JitterLagDesc*)lags, n_rates, period,
+                                 (hipStream_t)stream));
+}
+extern "C" int afx_k_jitter_conceal_period(float* jring, int S, int J, const int* hdr, int rows, int max_n, const float* gain,
+                                           const int* period, int Pmin, int Pmax, int P0, int Hd, int F, void* stream) {
+  KRET(launch_jitter_conceal_period(jring, S, J, hdr, rows, max_n, gain, period, Pmin, Pmax, P0, Hd, F, (hipStream_t)stream));
+}
+extern "C" int afx_k_jitter_conceal_period_rates(float* jring, int S, int Js, const int* hdr, int rows, int max_n,
+                                                 const afx_jitter_rate* rates, const afx_jitter_lags* lags, int n_rates,
+                                                 const int* period, void* stream) {
+  KRET(launch_jitter_conceal_period_rates(jring, S, Js, hdr, rows, max_n, (const JitterRateDesc*)rates, (const JitterLagDesc*)lags,
+                                          n_rates, period, (hipStream_t)stream));
+}
 extern "C" int afx_k_gate(const float* x, int A, int n, const int* hdr, int frame, float e_floor, float ratio, float rise,
                           int hang, float* nf, int* h, float* ring, int S, int ring_len, int* kept, unsigned char* mask,
                           void* stream) {

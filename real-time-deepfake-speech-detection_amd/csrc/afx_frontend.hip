@@ -1402,6 +1402,16 @@ static const char* launch_msg(const char* who, const char* what) {
   return msg;
 }
 
+// what every verb refuses of one entry of a rate table (ring_fit: how the entry point calls a J outside 1..Js)
+static const char* jitter_rate_refusal(const char* who, const JitterRateDesc& d, int Js, const char* ring_fit) {
+  if (d.L <= 0 || d.M <= 0 || d.T <= 0) return launch_msg(who, "bad filter shape");
+  if (d.taps == nullptr && (d.L != 1 || d.M != 1 || d.T != 1))
+    return launch_msg(who, "bad filter shape (no taps is the identity, L = M = T = 1)");
+  if (d.J <= 0 || d.J > Js) return launch_msg(who, ring_fit);
+  if (d.T - 1 > d.J) return launch_msg(who, "the filter history must fit the rate's ring");
+  return nullptr;
+}
+
 // The launch of a verb for the entry point `who`: every check (a refusal carries who's name, and nothing is launched), the rate
 // table as the kernels take it, the grid.  m comes with the verb's buffers, S, Js, ring_len, mode and the row layout set.
 // most: place / conceal: one int, the largest row of the launch; release: per rate the largest n_out (n_rates ints).
@@ -1429,11 +1439,8 @@ static const char* jitter_launch(const char* who, JitterVerb verb, JitterRatesAr
   size_t lds = 0;
   for (int i = 0; i < n_rates; ++i) {
     const JitterRateDesc& d = rates[i];
-    if (d.L <= 0 || d.M <= 0 || d.T <= 0) return launch_msg(who, "bad filter shape");
+    if (const char* bad = jitter_rate_refusal(who, d, m.Js, ring_fit)) return bad;
     const bool ident = d.taps == nullptr;
-    if (ident && (d.L != 1 || d.M != 1 || d.T != 1)) return launch_msg(who, "bad filter shape (no taps is the identity, L = M = T = 1)");
-    if (d.J <= 0 || d.J > m.Js) return launch_msg(who, ring_fit);
-    if (d.T - 1 > d.J) return launch_msg(who, "the filter history must fit the rate's ring");
     if (repeat && (!d.fade || d.P <= 0 || d.F < 0)) return launch_msg(who, "repeat needs a fade table, a period and a fade length");
     JitterRate& r = m.r[i];
     r.f = PolyFilter{d.taps, d.L, d.M, d.T, 0, 0};
@@ -1553,6 +1560,192 @@ const char* launch_jitter_conceal_rates(float* jring, int S, int Js, const int* 
 const char* launch_jitter_release_rates(const float* jring, int S, int Js, const int* hdr, int rows, const JitterRateDesc* rates,
                                         int n_rates, const int* max_out, float* ring, int ring_len, hipStream_t s) {
   return jitter_release_launch("jitter_release_rates", jring, S, Js, hdr, true, rows, rates, n_rates, max_out, ring, ring_len, s);
+}
+
+// ---------------------------------------------------------------------------------
+// Pitch-period concealment (conceal="pitch_sync"; the function is stated in include/afx.h afx_k_jitter_pitch): a released gap
+// repeats the last PITCH PERIOD p* of E instead of a fixed 10 ms.  Two verbs beside the four above, on the same ring and under
+// the same sizing invariant (lookback >= Pmax + max(Wc, G)):
+//   pitch:          one workgroup per gap whose origin a is released now.  The Lh = Pmax + Wc samples before a are quantised to
+//                   16-bit integers into LDS; thread t takes the lags Pmin + t, Pmin + t + 256, ...: c(p) and e(p) are exact
+//                   integer sums (64-bit accumulation of 32-bit products: any order gives the same numbers), the score
+//                   s = c*c / e one fp64 multiply and one IEEE fp64 divide.  The window element q[j] is one LDS address for the
+//                   whole wave (a broadcast), q[j - p] consecutive 16-bit words across lanes.  The argmax over the total order
+//                   (s descending, p ascending) is a shuffle reduction per wave and the four wave results through LDS.  p*
+//                   goes to period[slot]: device state, never read back.
+//   conceal_period: jitter_conceal_row with the period read from period[slot] (outside [Pmin, Pmax]: P0) and a gain table of
+//                   G = Hd + F entries (1 for Hd samples, then the fade).
+// The lag parameters of a rate travel by value beside the rates, as they do.
+// ---------------------------------------------------------------------------------
+constexpr int JIT_PITCH_HDR = 2, JIT_PITCH_RATES_HDR = 3;  // pitch: slot, ring column of the gap origin a [, rate index]
+
+struct JitterLag {
+  const float* gain;             // (max(G, 1),) fp32 (conceal_period only)
+  int J, Pmin, Pmax, Wc, P0, G;
+};
+
+struct JitterLagArgs {
+  const int* hdr;                // (rows, hdr_ints)
+  float* jring;                  // (S, Js)
+  int* period;                   // (S,)
+  int S, Js, nr, hdr_ints, rated;
+  JitterLag r[JIT_MAX_RATES];
+};
+
+// x -> the 16-bit integer the search runs on: one fp32 multiply, NaN -> 0, round to nearest even, clamp
+__device__ __forceinline__ int jitter_quant(float x) {
+  const float y = x * 32768.f;
+  return y != y ? 0 : (int)fminf(fmaxf(rintf(y), -32768.f), 32767.f);
+}
+
+// (s, p) a is before b in the order "s descending, p ascending"; s < 0: no candidate (after every candidate)
+__device__ __forceinline__ bool pitch_before(double sa, int pa, double sb, int pb) { return sa > sb || (sa == sb && pa < pb); }
+
+__global__ __launch_bounds__(256) void jitter_pitch_kernel(JitterLagArgs m) {
+  extern __shared__ short pitch_q[];  // the Lh quantised samples before a: pitch_q[k] = q[a - Lh + k]
+  __shared__ double wave_s[4];
+  __shared__ int wave_p[4];
+  const int* h = m.hdr + (long long)blockIdx.y * m.hdr_ints;
+  const int ri = m.rated ? __builtin_amdgcn_readfirstlane(h[m.hdr_ints - 1]) : 0;
+  if (ri < 0 || ri >= m.nr) return;
+  const JitterLag& r = m.r[ri];
+  const int slot = h[0], ac = h[1], J = r.J, Pmin = r.Pmin, Pmax = r.Pmax, Wc = r.Wc, Lh = Pmax + Wc;
+  if (!(slot >= 0 && slot < m.S && ac >= 0 && ac < J && Lh <= J)) return;  // (uniform over the workgroup)
+  const float* row = m.jring + (long long)slot * m.Js;
+  for (int k = threadIdx.x; k < Lh; k += blockDim.x) {
+    int c = ac - Lh + k;  // >= -J
+    c = c < 0 ? c + J : c;
+    pitch_q[k] = (short)jitter_quant(row[c]);
+  }
+  __syncthreads();
+  double best_s = -1.0;
+  int best_p = 0x7fffffff;
+  const short* win = pitch_q + Pmax;  // win[t] = q[a - Wc + t]
+  for (int p = Pmin + (int)threadIdx.x; p <= Pmax; p += blockDim.x) {
+    long long c = 0, e = 0;
+    for (int t = 0; t < Wc; ++t) {
+      const int x = win[t], y = win[t - p];
+      c += (long long)(x * y);
+      e += (long long)(y * y);
+    }
+    if (c > 0 && e > 0) {
+      const double s = ((double)c * (double)c) / (double)e;
+      if (pitch_before(s, p, best_s, best_p)) { best_s = s; best_p = p; }
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    const double s = __shfl_down(best_s, off, 64);
+    const int p = __shfl_down(best_p, off, 64);
+    if (pitch_before(s, p, best_s, best_p)) { best_s = s; best_p = p; }
+  }
+  if ((threadIdx.x & 63) == 0) { wave_s[threadIdx.x >> 6] = best_s; wave_p[threadIdx.x >> 6] = best_p; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w)
+      if (pitch_before(wave_s[w], wave_p[w], best_s, best_p)) { best_s = wave_s[w]; best_p = wave_p[w]; }
+    m.period[slot] = best_s < 0.0 ? r.P0 : best_p;
+  }
+}
+
+// jitter_conceal_row in mode 1 with the row's period from period[slot]: E[a + d] = gain[d] * E[a - p + d mod p] for d < G, else 0.
+// p is inside [Pmin, Pmax] (a stored value outside it is read as P0), so the source stays inside [a - Pmax, a), disjoint from the
+// written columns for d_hi + Pmax <= J.
+__global__ __launch_bounds__(256) void jitter_conceal_period_kernel(JitterLagArgs m) {
+  const int* h = m.hdr + (long long)blockIdx.y * m.hdr_ints;
+  const int ri = m.rated ? __builtin_amdgcn_readfirstlane(h[m.hdr_ints - 1]) : 0;
+  if (ri < 0 || ri >= m.nr) return;
+  const JitterLag& r = m.r[ri];
+  const int slot = h[0], ac = h[1], lo = h[2], hi = h[3], J = r.J, G = r.G;
+  if (!(slot >= 0 && slot < m.S && ac >= 0 && ac < J && lo >= 0 && hi >= lo && (long long)hi + r.Pmax <= J)) return;
+  int P = m.period[slot];
+  P = P < r.Pmin || P > r.Pmax ? r.P0 : P;
+  float* row = m.jring + (long long)slot * m.Js;
+  const int src0 = ac >= P ? ac - P : ac - P + J;
+  for (int d = lo + blockIdx.x * blockDim.x + threadIdx.x; d < hi; d += gridDim.x * blockDim.x) {
+    float v = 0.f;
+    if (d < G) {
+      const int c = src0 + d % P;
+      v = r.gain[d] * row[c < J ? c : c - J];
+    }
+    const int w = ac + d;  // < 2 J
+    row[w < J ? w : w - J] = v;
+  }
+}
+
+// The launch of the two verbs for the entry point `who`: the estimate (one workgroup per row; max_n is not read) or the synthesis
+// (max_n = the largest d_hi - d_lo).  Every check first; a refusal carries who's name, and nothing is launched.
+static const char* jitter_lag_launch(const char* who, bool estimate, float* jring, int S, int Js, const int* hdr, int hdr_ints, bool rated,
+                                     int rows, int max_n, const JitterRateDesc* rates, const JitterLagDesc* lags, int n_rates,
+                                     int* period, hipStream_t s) {
+  if (n_rates < 1 || n_rates > JIT_MAX_RATES) return launch_msg(who, "1 to 16 rates");
+  if (!rates || !lags) return launch_msg(who, "null rate table");
+  if (!hdr || !jring || !period) return launch_msg(who, "null ring, header table or period state");
+  if (rows <= 0 || rows > 65535) return launch_msg(who, "1 to 65535 rows");
+  const char* ring_fit = rated ? "a rate's ring must fit the ring's rows (1 <= J <= Js)"
+                       : estimate ? "the search history Pmax + Wc must fit a rate's ring" : "a row's samples and its source must fit the ring";
+  const char* rows_fit = "a row's samples and its source must fit the ring";
+  if (Js <= 0 || S <= 0 || (!estimate && max_n < 0)) return launch_msg(who, Js <= 0 ? ring_fit : rows_fit);
+  JitterLagArgs m{};
+  m.hdr = hdr; m.jring = jring; m.period = period; m.S = S; m.Js = Js; m.nr = n_rates; m.hdr_ints = hdr_ints; m.rated = rated;
+  bool fits = false;  // some rate can hold the history (estimate) or the largest row and its source (synthesis)
+  int lh = 0;         // estimate: the longest history among the rates that hold theirs
+  for (int i = 0; i < n_rates; ++i) {
+    const JitterRateDesc& d = rates[i];
+    const JitterLagDesc& g = lags[i];
+    if (const char* bad = jitter_rate_refusal(who, d, Js, ring_fit)) return bad;
+    if (g.Pmin < 1) return launch_msg(who, "the shortest lag Pmin must be at least 1");
+    if (g.Pmax < g.Pmin) return launch_msg(who, "the longest lag Pmax must not be below Pmin");
+    if (g.Wc < 1) return launch_msg(who, "the correlation window Wc must be at least 1");
+    if (g.P0 < g.Pmin || g.P0 > g.Pmax) return launch_msg(who, "the fallback period P0 must lie in [Pmin, Pmax]");
+    if (!estimate && (!d.fade || g.Hd < 0 || d.F < 0)) return launch_msg(who, "synthesis needs a gain table, a hold and a fade length");
+    m.r[i] = JitterLag{d.fade, d.J, g.Pmin, g.Pmax, g.Wc, g.P0, estimate ? 0 : g.Hd + d.F};
+    const long long Lh = (long long)g.Pmax + g.Wc;
+    if (estimate ? Lh <= d.J : (long long)max_n + g.Pmax <= d.J) {
+      fits = true;
+      lh = Lh > lh ? (int)Lh : lh;
+    } else if (estimate) {
+      m.r[i].J = 0;  // (a rate whose ring cannot hold its history: every row of it is skipped, whatever Lh is as an int)
+    }
+  }
+  if (!fits) return launch_msg(who, estimate ? "the search history Pmax + Wc must fit a rate's ring" : rows_fit);
+  if (estimate) {
+    if (lh > 32000) return launch_msg(who, "the search history Pmax + Wc must fit 64 KB of LDS as 16-bit samples");
+    hipLaunchKernelGGL(jitter_pitch_kernel, dim3(1, rows), dim3(256), (size_t)lh * sizeof(short), s, m);
+  } else {
+    const int gx = min((max_n + 255) / 256, 64);
+    if (gx == 0) return nullptr;  // no samples to conceal
+    hipLaunchKernelGGL(jitter_conceal_period_kernel, dim3(gx, rows), dim3(256), 0, s, m);
+  }
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
+const char* launch_jitter_pitch(const float* jring, int S, int J, const int* hdr, int rows, int Pmin, int Pmax, int Wc, int P0,
+                                int* period, hipStream_t s) {
+  const JitterRateDesc one{nullptr, nullptr, 1, 1, 1, J, 0, 0};
+  const JitterLagDesc lag{Pmin, Pmax, Wc, P0, 0};
+  return jitter_lag_launch("jitter_pitch", true, const_cast<float*>(jring), S, J, hdr, JIT_PITCH_HDR, false, rows, 0, &one, &lag, 1, period, s);
+}
+
+const char* launch_jitter_pitch_rates(const float* jring, int S, int Js, const int* hdr, int rows, const JitterRateDesc* rates,
+                                      const JitterLagDesc* lags, int n_rates, int* period, hipStream_t s) {
+  return jitter_lag_launch("jitter_pitch_rates", true, const_cast<float*>(jring), S, Js, hdr, JIT_PITCH_RATES_HDR, true, rows, 0, rates, lags,
+                           n_rates, period, s);
+}
+
+const char* launch_jitter_conceal_period(float* jring, int S, int J, const int* hdr, int rows, int max_n, const float* gain,
+                                         const int* period, int Pmin, int Pmax, int P0, int Hd, int F, hipStream_t s) {
+  const JitterRateDesc one{nullptr, gain, 1, 1, 1, J, P0, F};
+  const JitterLagDesc lag{Pmin, Pmax, 1, P0, Hd};  // (the synthesis reads no correlation window)
+  return jitter_lag_launch("jitter_conceal_period", false, jring, S, J, hdr, JIT_CONCEAL_HDR, false, rows, max_n, &one, &lag, 1,
+                           const_cast<int*>(period), s);
+}
+
+const char* launch_jitter_conceal_period_rates(float* jring, int S, int Js, const int* hdr, int rows, int max_n,
+                                               const JitterRateDesc* rates, const JitterLagDesc* lags, int n_rates, const int* period,
+                                               hipStream_t s) {
+  return jitter_lag_launch("jitter_conceal_period_rates", false, jring, S, Js, hdr, JIT_CONCEAL_RATES_HDR, true, rows, max_n, rates, lags,
+                           n_rates, const_cast<int*>(period), s);
 }
 
 // ---------------------------------------------------------------------------------

@@ -214,6 +214,20 @@ const char* launch_jitter_noise(float* jring, int S, int J, const int* hdr, int 
                                 hipStream_t s);
 const char* launch_jitter_noise_rates(float* jring, int S, int Js, const int* hdr, int rows, int max_n, const JitterRateDesc* rates,
                                       int n_rates, unsigned seed, const float* amp, hipStream_t s);
+// pitch-period concealment (include/afx.h afx_k_jitter_pitch / _conceal_period and their _rates forms): the estimate writes the
+// pitch period of each gap that opens (rows x 2 int32: slot, column of the gap origin [, rate index]) to period (S,) int32; the
+// synthesis is conceal with the row's period read from there.  lags: a HOST table parallel to rates (JitterLagDesc has the
+// layout of afx_jitter_lags); a rate's fade is then its gain table of Hd + F entries
+struct JitterLagDesc { int Pmin, Pmax, Wc, P0, Hd; };
+const char* launch_jitter_pitch(const float* jring, int S, int J, const int* hdr, int rows, int Pmin, int Pmax, int Wc, int P0,
+                                int* period, hipStream_t s);
+const char* launch_jitter_pitch_rates(const float* jring, int S, int Js, const int* hdr, int rows, const JitterRateDesc* rates,
+                                      const JitterLagDesc* lags, int n_rates, int* period, hipStream_t s);
+const char* launch_jitter_conceal_period(float* jring, int S, int J, const int* hdr, int rows, int max_n, const float* gain,
+                                         const int* period, int Pmin, int Pmax, int P0, int Hd, int F, hipStream_t s);
+const char* launch_jitter_conceal_period_rates(float* jring, int S, int Js, const int* hdr, int rows, int max_n,
+                                               const JitterRateDesc* rates, const JitterLagDesc* lags, int n_rates, const int* period,
+                                               hipStream_t s);
 // speech gate (include/afx.h afx_k_gate): per-slot energy gate with noise-floor tracking and hangover over the frames of each
 // row; the kept frames are compacted into the slot's pending ring, kept[i] = the samples kept of row i,
 // mask (optional) the keep flag of every frame

@@ -6,6 +6,8 @@ random phase against the 250-ms hop), the student scores them in KV-cached mode.
             ``feed(packets, slots, timestamps, score=False)`` with whatever arrived (a slot 0 to 3 times), one ``drain()`` per hop;
   packets   afx.ingest.PacketScorer fed the same streams losslessly and in order, one packet per slot and tick: what the
             parent of the jitter front could do.
+  --conceal {zero,repeat,pitch_sync}: the jitter path's concealment mode; --against MODE: a second jitter path in that mode on
+            the same arrivals.  Every path is warmed up first and the timed passes alternate between the paths.
 
   --dtx     silence suppression instead: talk-spurt traffic (about 40 % activity; spurts and pauses of geometric length, mean
             1 s and 1.5 s), a CN mark (RFC 3389) at each spurt end and every 200 ms of silence, --loss of all datagrams lost, in
@@ -21,7 +23,7 @@ random phase against the 250-ms hop), the student scores them in KV-cached mode.
             --out FILE appends what was printed to FILE (profiles/jitter_dtx.txt).
 
     python tools/jitter_bench.py [--streams 2048] [--rate 8000] [--encoding mulaw] [--packet-ms 20] [--depth-ms 60]
-                                 [--loss 0.02] [--reorder 0.1] [--hops 8] [--reps 3]
+                                 [--loss 0.02] [--reorder 0.1] [--hops 8] [--reps 3] [--conceal repeat] [--against MODE]
     rocprofv3 --kernel-trace --stats ... -- python tools/jitter_bench.py --profile   (jitter path only, 4 hops: kernel times)
 
 The two paths score different audio where packets were lost (concealed samples instead of the sent ones), so their scores are
@@ -42,7 +44,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "real-time-deepfake-speech-detection_am
 from afx import engine, synth  # noqa: E402
 from afx._lib import lib  # noqa: E402
 from afx.ingest import ENCODINGS, PacketScorer  # noqa: E402
-from afx.jitter import ComfortNoise, JitterScorer  # noqa: E402
+from afx.jitter import CONCEAL, ComfortNoise, JitterScorer  # noqa: E402
 from afx.streaming import KVCachedScorer  # noqa: E402
 
 W, H = 64000, 4000
@@ -150,6 +152,8 @@ def main():
     ap.add_argument("--reorder", type=float, default=0.1, help="fraction of packets that arrive one or two packets late")
     ap.add_argument("--hops", type=int, default=8, help="hops of audio per timed pass")
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--conceal", default="repeat", choices=CONCEAL, help="the jitter path's concealment mode")
+    ap.add_argument("--against", default=None, choices=CONCEAL, help="a second jitter path in this mode, its passes alternating with the first's")
     ap.add_argument("--profile", action="store_true", help="the jitter path only, a short pass (for a rocprofv3 run)")
     ap.add_argument("--dtx", action="store_true", help="silence-suppression traffic through a comfort-noise scorer (see above)")
     ap.add_argument("--out", default=None, help="--dtx: append the printed lines to this file")
@@ -198,56 +202,66 @@ def main():
           f"{args.packet_ms}-ms packets ({pk * bps} bytes), depth {args.depth_ms} ms, loss {args.loss:.3f}, reordered {args.reorder:.3f}; "
           f"{hops} hops ({ticks} ticks) per pass, {args.reps} timed passes per path after a warm-up pass", flush=True)
     results = {}
-    for name in (["jitter"] if args.profile else ["jitter", "packets"]):
+    names = ["jitter"] + ([f"jitter ({args.against})"] if args.against else []) + ([] if args.profile else ["packets"])
+    slots = list(range(S))
+    fronts, kept, timed = {}, {n: [[] for _ in range(S)] for n in names}, {n: ([], []) for n in names}
+    for name in names:
         inner = KVCachedScorer(eng, sd, S, window=W, hop=H)
-        front = JitterScorer(inner, rate, enc, depth) if name == "jitter" else PacketScorer(inner, rate, enc)
-        scores = [[] for _ in range(S)]
-        slots = list(range(S))
+        mode = args.against if name.endswith(")") else args.conceal
+        fronts[name] = PacketScorer(inner, rate, enc) if name == "packets" else JitterScorer(inner, rate, enc, depth, conceal=mode)
 
-        def tick_args(t):
-            if name == "packets":
-                return ([packet(s, t)[1] for s in slots], slots)
-            rows = arrivals[t]
-            pt = [packet(s, k) for s, k in rows]
-            return ([p[1] for p in pt], [s for s, _ in rows], np.array([p[0] for p in pt], dtype=np.int64))
+    def tick_args(name, t):
+        if name == "packets":
+            return ([packet(s, t)[1] for s in slots], slots)
+        rows = arrivals[t]
+        pt = [packet(s, k) for s, k in rows]
+        return ([p[1] for p in pt], [s for s, _ in rows], np.array([p[0] for p in pt], dtype=np.int64))
 
-        def run(t0, n, keep):
-            """Ticks t0 .. t0 + n - 1 -> (wall seconds, host seconds inside the calls)."""
-            calls = [tick_args(t) for t in range(t0, t0 + n)]
-            torch.cuda.synchronize()
-            t_host, start, fed = 0.0, time.perf_counter(), 0
-            for i, c in enumerate(calls):
-                a = time.perf_counter()
-                front.feed(*c, score=False)
-                res = None
-                if ((t0 + i + 1) * pk) // hop_in > ((t0 + i) * pk) // hop_in:  # a hop's worth of audio has gone by: score
-                    res = front.drain()
-                t_host += time.perf_counter() - a
-                if keep and res is not None:
-                    for s, v in zip(np.repeat(np.arange(S), res.counts.numpy()).tolist(), res.scores.tolist()):
-                        scores[s].append(v)
-            torch.cuda.synchronize()
-            return time.perf_counter() - start, t_host
+    # every path warms up, then the timed passes alternate between the paths (pass r of each before pass r + 1 of any, the
+    # order rotating), so a drift of the box falls on all of them
+    for rep in range(-1, passes):
+        for name in names[rep % len(names):] + names[:rep % len(names)]:
+            front, scores = fronts[name], kept[name]
 
-        run(0, warm_ticks, True)
-        times, host = [], []
-        for rep in range(passes):
+            def run(t0, n, keep):
+                """Ticks t0 .. t0 + n - 1 -> (wall seconds, host seconds inside the calls)."""
+                calls = [tick_args(name, t) for t in range(t0, t0 + n)]
+                torch.cuda.synchronize()
+                t_host, start, fed = 0.0, time.perf_counter(), 0
+                for i, c in enumerate(calls):
+                    a = time.perf_counter()
+                    front.feed(*c, score=False)
+                    res = None
+                    if ((t0 + i + 1) * pk) // hop_in > ((t0 + i) * pk) // hop_in:  # a hop's worth of audio has gone by: score
+                        res = front.drain()
+                    t_host += time.perf_counter() - a
+                    if keep and res is not None:
+                        for s, v in zip(np.repeat(np.arange(S), res.counts.numpy()).tolist(), res.scores.tolist()):
+                            scores[s].append(v)
+                torch.cuda.synchronize()
+                return time.perf_counter() - start, t_host
+
+            if rep < 0:
+                run(0, warm_ticks, True)
+                continue
             dt, th = run(warm_ticks + rep * ticks, ticks, False)
             if rep > 0 or args.profile:
-                times.append(dt / hops)
-                host.append(th / hops)
-        times.sort()
-        host.sort()
+                timed[name][0].append(dt / hops)
+                timed[name][1].append(th / hops)
+    for name in names:
+        times, host = sorted(timed[name][0]), sorted(timed[name][1])
         med = times[len(times) // 2]
-        results[name] = (med, times, scores)
+        results[name] = (med, times, kept[name])
         extra = ""
-        if name == "jitter":
-            st = {k: int(v.sum()) for k, v in front.stats().items()}
-            extra = f"; stats over all streams {st}"
+        if name != "packets":
+            st = {k: int(v.sum()) for k, v in fronts[name].stats().items()}
+            extra = f"; conceal {fronts[name].conceal}; stats over all streams {st}"
         print(f"  {name:8s} {med * 1e3:8.2f} ms per 250 ms of audio (min {times[0] * 1e3:.2f}, max {times[-1] * 1e3:.2f}); "
               f"host time inside feed / drain calls {host[len(host) // 2] * 1e3:.2f} ms; RTF {med / 0.25:.3f}{extra}", flush=True)
-        del front, inner
-        torch.cuda.empty_cache()
+    if args.against:
+        (ma, ta, _), (mb, tb, _) = results["jitter"], results[names[1]]
+        print(f"  {args.conceal} / {args.against} {ma / mb:.3f}x (spread of {args.against}: {(tb[-1] - tb[0]) / mb * 100:.1f} % of its median, "
+              f"of {args.conceal}: {(ta[-1] - ta[0]) / ma * 100:.1f} %)", flush=True)
     if not args.profile:
         (mj, tj, a), (mp, tp, b) = results["jitter"], results["packets"]
         print(f"  jitter / packets {mj / mp:.2f}x (spread of packets: {(tp[-1] - tp[0]) / mp * 100:.1f} % of its median, of jitter: "
