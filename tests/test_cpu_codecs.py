@@ -6,11 +6,14 @@ new entry point in the header, the library and the ctypes table."""
 import ctypes
 import os
 import re
-import struct
 
 import numpy as np
 import pytest
 import torch
+
+import packet_helpers
+from oracle.jitter import rtp as _rtp
+from packet_helpers import inner as _inner
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 H = 4000
@@ -18,10 +21,7 @@ H = 4000
 
 @pytest.fixture(scope="module")
 def built():
-    import __graft_entry__ as entry
-    entry.build()
-    from afx import _lib
-    return _lib
+    return packet_helpers.built()
 
 
 def _block(pred, index, body):
@@ -119,11 +119,6 @@ def test_pcm_codecs_are_exact_for_every_code_and_the_extremes():
 
 
 # ---- what a feed in a codec plans ------------------------------------------------------------------------------------------
-def _inner(S):
-    from afx.streaming import SlidingWindowScorer
-    return SlidingWindowScorer(None, S, window=16000, hop=H, device="cpu")
-
-
 def _snap(ps):
     e = ps.export_slots(list(range(ps.S)))
     return [ps.pending, ps.samples_in, ps.samples_seen] + [e.tensors[k] for k in sorted(e.tensors)]
@@ -277,10 +272,6 @@ def test_jitter_feed_in_two_codecs_plans_one_expand_op_and_place_rows_of_encodin
     assert plan.ops[0][0] == "expand" and plan.ops[0][1].tolist() == [[0, 1764, 1776, 1]]
 
 
-def _rtp(seq, ts, pt, payload, ssrc=0x11223344):
-    return struct.pack("!BBHII", 0x80, pt, seq, ts, ssrc) + payload
-
-
 def test_static_audio_formats_and_what_feed_rtp_takes_without_payload_types(built):
     from afx import rtp
     from afx._lib import AfxError
@@ -289,33 +280,33 @@ def test_static_audio_formats_and_what_feed_rtp_takes_without_payload_types(buil
     assert rtp.STATIC_AUDIO_FORMATS == {0: (8000, "mulaw"), 5: (8000, "dvi4"), 6: (16000, "dvi4"), 8: (8000, "alaw"),
                                         11: (44100, "pcm_s16be"), 16: (11025, "dvi4"), 17: (22050, "dvi4")}
     js = _jitter(("mulaw", "dvi4"), depth=0)
-    plan, pay, _ = js._plan_rtp([_rtp(1, 800, 0, bytes(160)), _rtp(2, 960, 5, bytes(84))], [0, 0])
+    plan, pay, _ = js._plan_rtp([_rtp(1, 800, pt=0, payload=bytes(160)), _rtp(2, 960, pt=5, payload=bytes(84))], [0, 0])
     assert plan.ops[0][0] == "expand" and [r[4] for r in plan.ops[1][1].tolist()] == [2, 0]
     for pt, rate in ((6, 16000), (16, 11025), (17, 22050)):
-        assert JitterScorer(_inner(1), rate, "dvi4", 0)._plan_rtp([_rtp(1, 0, pt, bytes(84))], [0])[0].ops[0][0] == "expand"
-    assert JitterScorer(_inner(1), 44100, "pcm_s16be", 0)._plan_rtp([_rtp(1, 0, 11, bytes(64))], [0])[0].ops[0][0] == "expand"
+        assert JitterScorer(_inner(1), rate, "dvi4", 0)._plan_rtp([_rtp(1, 0, pt=pt, payload=bytes(84))], [0])[0].ops[0][0] == "expand"
+    assert JitterScorer(_inner(1), 44100, "pcm_s16be", 0)._plan_rtp([_rtp(1, 0, pt=11, payload=bytes(64))], [0])[0].ops[0][0] == "expand"
     before = _jsnap(js)
     for pt, payload in ((6, bytes(84)), (8, bytes(160)), (10, bytes(64)), (11, bytes(64)), (96, bytes(84)), (5, bytes(3)),
                         (5, _block(0, 89, bytes(4)))):  # another rate's type, a type not listed, stereo, unknown; malformed
         with pytest.raises(ValueError):
-            js.feed_rtp([_rtp(1, 800, pt, payload)], [0])
+            js.feed_rtp([_rtp(1, 800, pt=pt, payload=payload)], [0])
     assert all(torch.equal(a, b) for a, b in zip(before, _jsnap(js)))
     with pytest.raises(ValueError, match="payload type 5"):  # a scorer that does not list dvi4 refuses it as before
-        _jitter("mulaw").feed_rtp([_rtp(1, 800, 5, bytes(84))], [0])
+        _jitter("mulaw").feed_rtp([_rtp(1, 800, pt=5, payload=bytes(84))], [0])
     with pytest.raises(ValueError, match="payload type 11"):  # little-endian L16 is not what PT 11 carries
-        JitterScorer(_inner(1), 44100, "pcm_s16le", 0).feed_rtp([_rtp(1, 0, 11, bytes(64))], [0])
+        JitterScorer(_inner(1), 44100, "pcm_s16le", 0).feed_rtp([_rtp(1, 0, pt=11, payload=bytes(64))], [0])
     with pytest.raises(AfxError):  # accepted and planned
-        js.feed_rtp([_rtp(1, 800, 5, bytes(84))], [0])
+        js.feed_rtp([_rtp(1, 800, pt=5, payload=bytes(84))], [0])
     mx = MixedJitterScorer(_inner(4), [(8000, "mulaw"), (8000, "dvi4"), (16000, "dvi4"), (44100, "pcm_s16be")], 60)
     mx.reset([1], 16000)
     mx.reset([2], 44100)
-    d = [_rtp(1, 0, 0, bytes(160)), _rtp(1, 0, 6, bytes(4 + 160)), _rtp(1, 0, 11, bytes(2 * 882)), _rtp(1, 0, 5, bytes(84))]
+    d = [_rtp(1, 0, pt=0, payload=bytes(160)), _rtp(1, 0, pt=6, payload=bytes(4 + 160)), _rtp(1, 0, pt=11, payload=bytes(2 * 882)), _rtp(1, 0, pt=5, payload=bytes(84))]
     plan, pay, _ = mx._plan_rtp(d, [0, 1, 2, 3])
     assert plan.ops[0][0] == "expand" and plan.ops[0][1][:, 3].tolist() == [0, 1, 0] and plan.ops[0][2] == 882
     assert sorted((r[0], r[4], r[5]) for r in plan.ops[1][1].tolist()) == [(0, 2, 0), (1, 0, 1), (2, 0, 2), (3, 0, 0)]
     for pt, slot in ((5, 1), (6, 0), (11, 0), (10, 2), (16, 0), (17, 1)):
         with pytest.raises(ValueError):
-            mx.feed_rtp([_rtp(1, 0, pt, bytes(84))], [slot])
+            mx.feed_rtp([_rtp(1, 0, pt=pt, payload=bytes(84))], [slot])
     assert not mx._b.started.any()
 
 

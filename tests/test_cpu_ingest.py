@@ -12,32 +12,16 @@ import numpy as np
 import pytest
 import torch
 
+import packet_helpers
+from oracle.jitter import TABLES
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RATES = [8000, 11025, 22050, 44100, 48000, 192000]
 H = 4000
 
 
-def mulaw_table():
-    t = []
-    for c in range(256):
-        u = ~c & 0xFF
-        v = ((((u & 15) << 3) + 132) << ((u >> 4) & 7)) - 132
-        t.append(-v if u & 0x80 else v)
-    return np.array(t, dtype=np.int64)
-
-
-def alaw_table():
-    t = []
-    for c in range(256):
-        a = c ^ 0x55
-        e, m = (a >> 4) & 7, a & 15
-        v = ((m << 4) + 264) << (e - 1) if e else (m << 4) + 8
-        t.append(v if a & 0x80 else -v)
-    return np.array(t, dtype=np.int64)
-
-
 def test_g711_tables_known_answers_and_symmetry():
-    mu, al = mulaw_table(), alaw_table()
+    mu, al = ((TABLES[law] * np.float32(32768)).astype(np.int64) for law in ("mulaw", "alaw"))  # (whole numbers, exact in fp32)
     assert (mu[0x00], mu[0x80], mu[0x7F], mu[0xFF]) == (-32124, 32124, 0, 0)
     assert (al[0xD5], al[0x55], al[0xAA], al[0x2A]) == (8, -8, 32256, -32256)
     c = np.arange(128)
@@ -133,10 +117,7 @@ def test_plan_reduces_long_sessions_to_small_numbers():
 # ---- the packer, the refusals and the state, on a host-only scorer -------------------------------------------------------
 @pytest.fixture(scope="module")
 def built():
-    import __graft_entry__ as ge
-    ge.build()  # a state records the library's build id
-    from afx import _lib
-    return _lib
+    return packet_helpers.built()
 
 
 def _host(S=2, rate=8000, encoding="pcm_s16le", max_pending=4):

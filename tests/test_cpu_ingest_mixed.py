@@ -7,11 +7,14 @@ packets of mixed encodings."""
 import ctypes
 import os
 import re
-import struct
 
 import numpy as np
 import pytest
 import torch
+
+import packet_helpers
+from oracle.jitter import rtp as _rtp
+from packet_helpers import inner as _inner
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 H = 4000
@@ -21,15 +24,7 @@ BPS = {"pcm_f32le": 4, "pcm_s16le": 2, "mulaw": 1, "alaw": 1}
 
 @pytest.fixture(scope="module")
 def built():
-    import __graft_entry__ as ge
-    ge.build()  # a state records the library's build id
-    from afx import _lib
-    return _lib
-
-
-def _inner(S):
-    from afx.streaming import SlidingWindowScorer
-    return SlidingWindowScorer(None, S, window=16000, hop=H, device="cpu")
+    return packet_helpers.built()
 
 
 def _mixed(S=4, formats=FORMATS, max_pending=2, spread=True):
@@ -304,10 +299,6 @@ def _jitter(encoding, S=2, depth=160, **kw):
     return JitterScorer(_inner(S), 8000, encoding, depth, **kw)
 
 
-def _rtp(seq, ts, pt, payload, ssrc=0x11223344):
-    return struct.pack("!BBHII", 0x80, pt, seq, ts, ssrc) + payload
-
-
 def test_jitter_place_rows_carry_each_packets_encoding(built):
     from afx.ingest import ENCODINGS
     from afx.jitter import PLACE_HDR, PLACE_MIXED_HDR
@@ -360,7 +351,7 @@ def test_jitter_place_rows_carry_each_packets_encoding(built):
 def test_feed_rtp_takes_every_listed_payload_type(built):
     from afx._lib import AfxError
     both, mu = _jitter(("mulaw", "alaw"), depth=0), _jitter("mulaw", depth=0)
-    d0, d8 = _rtp(1, 800, 0, bytes(160)), _rtp(2, 960, 8, bytes(160))
+    d0, d8 = _rtp(1, 800, pt=0, payload=bytes(160)), _rtp(2, 960, pt=8, payload=bytes(160))
     seen = []
     orig = both.feed
     both.feed = lambda *a, **kw: seen.append(kw["encodings"]) or orig(*a, **kw)
@@ -375,11 +366,11 @@ def test_feed_rtp_takes_every_listed_payload_type(built):
         mu.feed_rtp([d0, d8], [0, 0])
     assert mu.buffered.tolist() == [0, 0] and not mu._b.started.any()
     with pytest.raises(ValueError, match="payload type 96"):
-        both.feed_rtp([_rtp(1, 800, 96, bytes(320))], [0])
+        both.feed_rtp([_rtp(1, 800, pt=96, payload=bytes(320))], [0])
     with pytest.raises(AfxError):  # a dynamic type mapped to a listed encoding is taken; to one not listed, refused
-        both.feed_rtp([_rtp(1, 800, 96, bytes(160))], [1], payload_types={96: "alaw"})
+        both.feed_rtp([_rtp(1, 800, pt=96, payload=bytes(160))], [1], payload_types={96: "alaw"})
     with pytest.raises(ValueError, match="payload type 96"):
-        both.feed_rtp([_rtp(1, 800, 96, bytes(320))], [1], payload_types={96: "pcm_s16le"})
+        both.feed_rtp([_rtp(1, 800, pt=96, payload=bytes(320))], [1], payload_types={96: "pcm_s16le"})
     with pytest.raises(AfxError):
         mu.feed_rtp([d0], [0])
 

@@ -1,7 +1,7 @@
-"""The jitter buffer (afx/jitter.py, afx/rtp.py) without a GPU.  The reference for the played-out stream E is restated here
-in plain numpy and per sample: a dict of received samples (first arrival wins), the playout point, and the concealment
-recurrence over E itself.  ``JitterScorer``'s plan (the rows of afx_k_jitter_place / _conceal / _release it would launch) is
-run by a numpy restatement of the three kernels on a numpy ring, and what that releases must equal the reference bit for
+"""The jitter buffer (afx/jitter.py, afx/rtp.py) without a GPU.  The reference for the played-out stream E is
+oracle/jitter.py's ``RefSlot``, in plain numpy and per sample: a dict of received samples (first arrival wins), the playout
+point, and the concealment recurrence over E itself.  ``JitterScorer``'s plan (the rows of afx_k_jitter_place / _conceal /
+_release it would launch) is run by its ``NumpyDevice``, the kernels restated on a numpy ring, and what that releases must equal the reference bit for
 bit, with its counters, on random arrival sequences (late, partly late, duplicate, overlapping packets, jumps beyond the
 ring).  Also: timestamp unwrapping across 2**32, ``rtp.parse`` on hand-built datagrams, the shape of the launch plan
 (disjoint rows, gap order, rounds), refusals that leave a host-only scorer unchanged, the state an export adds and the
@@ -16,151 +16,23 @@ import numpy as np
 import pytest
 import torch
 
+import packet_helpers
+from oracle.jitter import BPS, NumpyDevice, RefSlot, decode_ref, rtp as _rtp
+from packet_helpers import bits as _bits
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 H = 4000
 
 
-def mulaw_table():
-    t = []
-    for c in range(256):
-        u = ~c & 0xFF
-        v = ((((u & 15) << 3) + 132) << ((u >> 4) & 7)) - 132
-        t.append(-v if u & 0x80 else v)
-    return np.array(t, dtype=np.float32) / np.float32(32768)
-
-
-def decode_ref(raw, encoding):
-    if encoding == "mulaw":
-        return mulaw_table()[np.frombuffer(raw, dtype=np.uint8)]
-    if encoding == "pcm_s16le":
-        return np.frombuffer(raw, dtype="<i2").astype(np.float32) / np.float32(32768)
-    assert encoding == "pcm_f32le"
-    return np.frombuffer(raw, dtype="<f4").astype(np.float32)
-
-
-BPS = {"pcm_f32le": 4, "pcm_s16le": 2, "mulaw": 1}
-
-
 @pytest.fixture(scope="module", autouse=True)
 def built():
-    import __graft_entry__ as ge
-    ge.build()  # a state records the library's build id, and the entry points are looked up in the built library
-    from afx import _lib
-    return _lib
-
-
-# ---- the reference: one slot's played-out stream, per sample ---------------------------------------------------------------
-class RefSlot:
-    def __init__(self, depth, mode, P, F):
-        self.depth, self.mode, self.P, self.F = depth, mode, P, F
-        self.fade = (1.0 - np.arange(max(F, 1), dtype=np.float64) / max(F, 1)).astype(np.float32)
-        self.got, self.E = {}, []
-        self.next = self.hi = 0
-        self.gap = None
-        self.max_start = None
-        self.stats = dict(received=0, late=0, duplicate=0, concealed=0, out_of_order=0)
-
-    def packet(self, t, values):
-        if self.max_start is not None and t < self.max_start:
-            self.stats["out_of_order"] += 1
-        self.max_start = t if self.max_start is None else max(self.max_start, t)
-        for k, v in enumerate(values):
-            i = t + k
-            if i < self.next:
-                self.stats["late"] += 1
-            elif i in self.got:
-                self.stats["duplicate"] += 1
-            else:
-                self.got[i] = v
-                self.stats["received"] += 1
-                self.hi = max(self.hi, i + 1)
-
-    def release(self, upto):
-        for i in range(self.next, upto):
-            if i in self.got:
-                v, self.gap = self.got.pop(i), None
-            else:
-                if self.gap is None:
-                    self.gap = i
-                d = i - self.gap
-                v = np.float32(0)
-                if self.mode == "repeat" and d < self.F:
-                    j = self.gap - self.P + d % self.P
-                    v = np.float32(self.fade[d] * (self.E[j] if j >= 0 else np.float32(0)))
-                self.stats["concealed"] += 1
-            self.E.append(np.float32(v))
-        self.next = max(self.next, upto)
-        self.hi = max(self.hi, self.next)
-
-    def after_feed(self):
-        self.release(max(self.next, self.hi - self.depth))
-
-
-# ---- the three kernels restated on a numpy ring ------------------------------------------------------------------------------
-class NumpyDevice:
-    """Runs a Plan's launches as include/afx.h states them, checks what the host promises about them (rows inside the
-    ring, rows of one launch disjoint, headers equal to ingest.plan of the playout counter) and collects what each slot
-    releases."""
-
-    def __init__(self, js):
-        self.js = js
-        self.ring = js.jring.numpy()  # the host-only scorer's own (CPU) ring: export_slots / import_slots see what is placed here
-        self.out = [[] for _ in range(js.S)]
-        self.N = [0] * js.S
-        self.launches = []
-
-    def reset(self, s):
-        self.ring[s] = 0
-        self.out[s], self.N[s] = [], 0
-
-    def run(self, plan, pay):
-        from afx.ingest import layout, plan as ingest_plan
-        js, J = self.js, self.js.J
-        offs, total = layout([len(p) for p in pay])
-        stage = bytearray(total)
-        for o, p in zip(offs, pay):
-            stage[o:o + len(p)] = bytes(p)
-        bps = BPS[js.encoding]
-        for op in plan.ops:
-            self.launches.append(op[0])
-            if op[0] == "pop":
-                continue
-            rows = op[1]
-            assert rows.dtype == np.int32 and len(rows) >= 1
-            if op[0] == "place":
-                written = set()
-                for s, off, n, col in rows.tolist():
-                    assert 0 < n <= op[2] <= js.W and 0 <= col < J and off % bps == 0 and off + n * bps <= total
-                    cols = {(s, (col + k) % J) for k in range(n)}
-                    assert not (cols & written)  # the rows of one launch write disjoint ranges
-                    written |= cols
-                    self.ring[s, (col + np.arange(n)) % J] = decode_ref(bytes(stage[off:off + n * bps]), js.encoding)
-            elif op[0] == "conceal":
-                assert len(set(rows[:, 0].tolist())) == len(rows)  # one gap per slot and launch: gaps of a slot are ordered
-                for s, ac, lo, hi in rows.tolist():
-                    assert 0 <= ac < J and 0 <= lo < hi and hi - lo <= op[2] and hi + js.period <= J
-                    for d in range(lo, hi):
-                        v = np.float32(0)
-                        if js.conceal == "repeat" and d < js.fade_len:
-                            v = np.float32(js.fade.numpy()[d] * self.ring[s, (ac - js.period + d % js.period) % J])
-                        self.ring[s, (ac + d) % J] = v
-            else:
-                assert op[0] == "release" and len(set(rows[:, 0].tolist())) == len(rows)
-                for s, col, n_in, n_out, p0, d0, wpos, z in rows.tolist():
-                    assert (n_out, p0, d0) == ingest_plan(self.N[s], n_in, js.L, js.M) and col == self.N[s] % J and z == 0
-                    assert 0 < n_in <= js.W and n_out <= op[2] <= js.ring_len and 0 <= wpos < js.ring_len
-                    self.out[s].extend(self.ring[s, (col + np.arange(n_in)) % J].tolist())
-                    self.N[s] += n_in
+    return packet_helpers.built()
 
 
 def _host(S=3, rate=8000, encoding="pcm_s16le", depth=160, **kw):
     from afx.jitter import JitterScorer
     from afx.streaming import SlidingWindowScorer
     return JitterScorer(SlidingWindowScorer(None, S, window=16000, hop=H, device="cpu"), rate, encoding, depth, **kw)
-
-
-def _bits(x):
-    return np.asarray(x, dtype=np.float32).view(np.uint32)
 
 
 def _check(js, dev, refs, origin):
@@ -403,18 +275,6 @@ def test_timestamps_unwrap_across_two_to_the_32():
 
 
 # ---- RTP -----------------------------------------------------------------------------------------------------------------
-def _rtp(seq, ts, pt=0, ssrc=0x11223344, payload=b"", marker=False, csrc=(), ext=None, pad=0, version=2):
-    b0 = (version << 6) | (0x20 if pad else 0) | (0x10 if ext is not None else 0) | len(csrc)
-    out = struct.pack("!BBHII", b0, (0x80 if marker else 0) | pt, seq, ts, ssrc)
-    out += b"".join(struct.pack("!I", c) for c in csrc)
-    if ext is not None:
-        out += struct.pack("!HH", 0xBEDE, len(ext) // 4) + ext
-    out += payload
-    if pad:
-        out += bytes(pad - 1) + bytes([pad])
-    return out
-
-
 def test_rtp_parse_on_hand_built_datagrams():
     from afx import rtp
     pay = bytes(range(1, 21))

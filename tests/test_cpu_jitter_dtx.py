@@ -1,8 +1,8 @@
 """Silence suppression and comfort noise in the jitter buffer (afx/jitter.py ``ComfortNoise``, ``silence``, ``feed_rtp`` with
-RFC 3389 payloads) without a GPU.  The reference for the played-out stream E is restated per sample: a dict of received
-samples, a dict of silence marks, the playout point, and for every released index either its received value, comfort noise
-at the level of the latest mark of its run of missing samples, or the loss concealment of the contract.  The planner's
-launches (place, noise, conceal, release) are run by a numpy restatement of the four kernels on the scorer's own ring, and
+RFC 3389 payloads) without a GPU.  The reference for the played-out stream E is oracle/jitter.py's ``RefSlot``, per sample: a dict of
+received samples, a dict of silence marks, the playout point, and for every released index either its received value, comfort
+noise at the level of the latest mark of its run of missing samples, or the loss concealment of the contract.  The planner's
+launches (place, noise, conceal, release) are run by its ``NumpyDevice``, the kernels restated on the scorer's own ring, and
 what that releases must equal the reference bit for bit, with its counters.  Also: known answers and statistics of the noise
 function, hand-made gaps, "no marks, no change", ``feed_rtp``, sessions moved mid-silence, the mixed-rate scorer against
 the one-rate scorer, and the new entry points in the header, the library and the ctypes table."""
@@ -10,66 +10,22 @@ import ctypes
 import os
 import random
 import re
-import struct
 
 import numpy as np
 import pytest
 import torch
 
+import packet_helpers
+from oracle.jitter import NumpyDevice as _Device, RefSlot, dtx_events, k_ref, noise_ref, rtp as _rtp
+from packet_helpers import bits as _bits, go as _go, inner as _inner
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 H = 4000
-ENCODINGS = ("pcm_f32le", "pcm_s16le", "mulaw", "alaw")
-BPS = {"pcm_f32le": 4, "pcm_s16le": 2, "mulaw": 1, "alaw": 1}
-
-
-def _mulaw_table():
-    t = []
-    for c in range(256):
-        u = ~c & 0xFF
-        v = ((((u & 15) << 3) + 132) << ((u >> 4) & 7)) - 132
-        t.append(-v if u & 0x80 else v)
-    return np.array(t, dtype=np.float32) / np.float32(32768)
-
-
-def decode_ref(raw, encoding):
-    if encoding == "mulaw":
-        return _mulaw_table()[np.frombuffer(raw, dtype=np.uint8)]
-    if encoding == "pcm_s16le":
-        return np.frombuffer(raw, dtype="<i2").astype(np.float32) / np.float32(32768)
-    assert encoding == "pcm_f32le"
-    return np.frombuffer(raw, dtype="<f4").astype(np.float32)
 
 
 @pytest.fixture(scope="module", autouse=True)
 def built():
-    import __graft_entry__ as ge
-    ge.build()  # a state records the library's build id, and the entry points are looked up in the built library
-    from afx import _lib
-    return _lib
-
-
-def _bits(x):
-    return np.asarray(x, dtype=np.float32).view(np.uint32)
-
-
-# ---- the noise function, restated with Python integers ------------------------------------------------------------------------
-def k_ref(seed, i):
-    m = 0xFFFFFFFF
-    x = ((i & m) * 0x9E3779B9 + (i >> 32) * 0x85EBCA6B + seed) & m
-    x ^= x >> 16
-    x = x * 0x7FEB352D & m
-    x ^= x >> 15
-    x = x * 0x846CA68B & m
-    x ^= x >> 16
-    return (x - (1 << 32) if x & 0x80000000 else x) >> 8
-
-
-def amp_ref(level):
-    return np.float32(np.sqrt(3.0) * 10.0 ** (-level / 20.0) / 2.0 ** 23)
-
-
-def noise_ref(seed, i, level):
-    return np.float32(amp_ref(level) * np.float32(k_ref(seed, i)))
+    return packet_helpers.built()
 
 
 def test_known_answers_of_the_noise_function():
@@ -113,153 +69,8 @@ def test_noise_statistics_on_one_fixed_input():
     assert np.abs(x).max() <= np.sqrt(3.0) * 1e-3 * (1 + 1e-6)  # uniform: bounded by sqrt(3) RMS, nothing clipped
 
 
-# ---- the reference: one slot's played-out stream, per sample ---------------------------------------------------------------
-class RefSlot:
-    def __init__(self, depth, mode, P, F, seed):
-        self.depth, self.mode, self.P, self.F, self.seed = depth, mode, P, F, seed
-        self.fade = (1.0 - np.arange(max(F, 1), dtype=np.float64) / max(F, 1)).astype(np.float32)
-        self.got, self.marks, self.E = {}, {}, []
-        self.next = self.hi = 0
-        self.started = False
-        self.gap = None    # the first index of the run of missing samples the playout point stands in
-        self.level = -1    # the level of the latest mark of that run, -1: none
-        self.max_start = None
-        self.kinds = []    # per released index: "r" received, "n" noise, "l" loss
-        self.stats = dict(received=0, late=0, duplicate=0, concealed=0, out_of_order=0, comfort=0, marks=0, marks_late=0)
-
-    def mark(self, t, level):
-        if not self.started or t < self.next:
-            self.stats["marks_late"] += 1
-        elif t not in self.marks:
-            self.marks[t] = level
-            self.stats["marks"] += 1
-
-    def packet(self, t, values, by_seq=False):
-        self.started = True
-        if not by_seq and self.max_start is not None and t < self.max_start:
-            self.stats["out_of_order"] += 1
-        self.max_start = t if self.max_start is None else max(self.max_start, t)
-        for k, v in enumerate(values):
-            i = t + k
-            if i < self.next:
-                self.stats["late"] += 1
-            elif i in self.got:
-                self.stats["duplicate"] += 1
-            else:
-                self.got[i] = v
-                self.stats["received"] += 1
-                self.hi = max(self.hi, i + 1)
-
-    def release(self, upto):
-        for i in range(self.next, upto):
-            if i in self.got:
-                v, self.gap, self.level = self.got.pop(i), None, -1
-                self.kinds.append("r")
-            else:
-                if self.gap is None:
-                    self.gap = i
-                if i in self.marks:
-                    self.level = self.marks[i]
-                if self.level >= 0:
-                    v = noise_ref(self.seed, i, self.level)
-                    self.stats["comfort"] += 1
-                    self.kinds.append("n")
-                else:
-                    d = i - self.gap
-                    v = np.float32(0)
-                    if self.mode == "repeat" and d < self.F:
-                        j = self.gap - self.P + d % self.P
-                        v = np.float32(self.fade[d] * (self.E[j] if j >= 0 else np.float32(0)))
-                    self.stats["concealed"] += 1
-                    self.kinds.append("l")
-            self.E.append(np.float32(v))
-        self.next = max(self.next, upto)
-        self.hi = max(self.hi, self.next)
-        self.marks = {t: l for t, l in self.marks.items() if t >= self.next}
-
-    def after_feed(self):
-        self.release(max(self.next, self.hi - self.depth))
-
-
-# ---- the four kernels restated on a numpy ring --------------------------------------------------------------------------------
-class NumpyDevice:
-    """Runs a Plan's launches as include/afx.h states them, for a one-rate or a mixed scorer (a row's last int is then its
-    rate index), checks that the rows of a place or noise launch write disjoint columns and that noise comes once per round,
-    before the conceal ranks, and collects what each slot releases."""
-
-    def __init__(self, js):
-        self.js = js
-        self.ring = js.jring.numpy()
-        self.out = [[] for _ in range(js.S)]
-        self.N = [0] * js.S
-        self.launches = []
-        self.noise_rows = 0
-
-    def run(self, plan, pay):
-        from afx.ingest import layout
-        js = self.js
-        offs, total = layout([len(p) for p in pay])
-        stage = bytearray(total)
-        for o, p in zip(offs, pay):
-            stage[o:o + len(p)] = bytes(p)
-        kinds = [op[0] for op in plan.ops]
-        for a, b in zip(kinds, kinds[1:]):  # the order of a round: place, ONE noise, the conceal ranks, release, pop
-            assert not (a == "noise" and b == "noise") and not (a == "conceal" and b in ("noise", "place"))
-            assert not (a == "noise" and b == "place")
-        for op in plan.ops:
-            self.launches.append(op[0])
-            if op[0] == "pop":
-                js.scorer._seen[op[2]] += H  # (the inner session counts the hop it would have been pushed)
-                continue
-            rows = op[1]
-            assert rows.dtype == np.int32 and len(rows) >= 1
-            written = set()
-            for row in rows.tolist():
-                ri = row[-1] if js._rated else 0
-                J, P, F = int(js._rJ[ri]), int(js._rP[ri]), int(js._rF[ri])
-                s = row[0]
-                assert ri == js._rate_of[s]
-                if op[0] == "place":
-                    off, n, col = row[1:4]
-                    enc = ENCODINGS[row[4]] if js._mixed else js.encoding
-                    assert 0 < n <= op[2] and 0 <= col < J
-                    cols = {(s, (col + k) % J) for k in range(n)}
-                    assert not (cols & written)
-                    written |= cols
-                    self.ring[s, (col + np.arange(n)) % J] = decode_ref(bytes(stage[off:off + n * BPS[enc]]), enc)
-                elif op[0] == "noise":
-                    assert len(row) == (7 if js._rated else 6)
-                    col, n, lo, hi, level = row[1:6]
-                    i0 = (hi << 32) | (lo & 0xFFFFFFFF)
-                    assert 0 < n <= min(op[2], J) and op[2] <= js.Js and col == i0 % J and hi >= 0 and 0 <= level <= 127
-                    assert self.N[s] <= i0 and i0 + n <= self.N[s] + J  # inside the released range of this round
-                    cols = {(s, (col + k) % J) for k in range(n)}
-                    assert not (cols & written)  # the rows of one noise launch write disjoint ranges
-                    written |= cols
-                    self.ring[s, (col + np.arange(n)) % J] = js.cn.samples(i0, n, level)
-                    self.noise_rows += 1
-                elif op[0] == "conceal":
-                    ac, lo, hi = row[1:4]
-                    assert 0 <= ac < J and 0 <= lo < hi and hi - lo <= op[2] and hi + P <= J
-                    fade = js._fades[ri].numpy()
-                    for d in range(lo, hi):
-                        v = np.float32(0)
-                        if js.conceal == "repeat" and d < F:
-                            v = np.float32(fade[d] * self.ring[s, (ac - P + d % P) % J])
-                        self.ring[s, (ac + d) % J] = v
-                else:
-                    assert op[0] == "release"
-                    col, n_in = row[1:3]
-                    assert col == self.N[s] % J and 0 < n_in <= J
-                    self.out[s].extend(self.ring[s, (col + np.arange(n_in)) % J].tolist())
-                    self.N[s] += n_in
-            if op[0] == "conceal":
-                assert len(set(rows[:, 0].tolist())) == len(rows)
-
-
-def _inner(S):
-    from afx.streaming import SlidingWindowScorer
-    return SlidingWindowScorer(None, S, window=16000, hop=H, device="cpu")
+def NumpyDevice(js):
+    return _Device(js, count_pops=True)  # (the inner session counts the hop it would have been pushed)
 
 
 def _host(S=3, rate=8000, encoding="pcm_f32le", depth=160, seed=7, **kw):
@@ -268,53 +79,8 @@ def _host(S=3, rate=8000, encoding="pcm_f32le", depth=160, seed=7, **kw):
     return JitterScorer(_inner(S), rate, encoding, depth, comfort_noise=cn, **kw)
 
 
-def _go(js, dev, plan, pay=()):
-    dev.run(plan, list(pay))
-    js._commit(plan.book)
-    return plan
-
-
 def _stats(js, s):
     return {k: int(v[s]) for k, v in js.stats().items()}
-
-
-# ---- seeded DTX traffic ---------------------------------------------------------------------------------------------------------
-def dtx_events(rate, seed, n_spurts=6):
-    """One slot's traffic as a list of ("pkt", t, fp32 samples) / ("cn", t, level): talk spurts of 20-ms packets, a CN at the
-    end of each spurt and every 200 ms of silence with a new level; every third spurt loses its last speech packet, every
-    fourth its first CN, 5 % other loss; duplicate marks; some level updates arrive late; arrival shuffled within blocks of
-    three."""
-    rng, g = random.Random(seed), np.random.default_rng(seed)
-    n = rate // 50
-    t, ev, late = 0, [], []
-    for k in range(n_spurts):
-        length = rng.randint(3, 8)
-        for q in range(length):
-            x = (0.1 * g.standard_normal(n)).astype("<f4")
-            lost = k % 3 == 1 if q == length - 1 else (k or q) and rng.random() < 0.05
-            if not lost:
-                ev.append(("pkt", t, x))
-            t += n
-        level = rng.randrange(30, 80)
-        for q in range(rng.randint(12, 24) if k % 4 == 3 or k % 3 == 2 else rng.randint(4, 24)):
-            if q % 10 == 0:
-                level = rng.randrange(30, 80) if q else level
-                if q or k % 4 != 3:  # (else: a lost CN)
-                    ev.append(("cn", t, level))
-                    if q and k % 3 == 2:
-                        late.append(ev[-1])
-                    if rng.random() < 0.3:
-                        ev.append(("cn", t, (level + 5) % 128))  # a second mark at the same t: the first arrival wins
-            t += n
-    out = ev[:1]
-    for i in range(1, len(ev), 3):
-        blk = ev[i:i + 3]
-        rng.shuffle(blk)
-        out += blk
-    for e in late:  # late marks: they arrive well behind the playout point
-        i = next(i for i, v in enumerate(out) if v is e)
-        out.insert(min(len(out), i + 9), out.pop(i))
-    return out
 
 
 @pytest.mark.parametrize("rate", [8000, 16000])
@@ -324,7 +90,7 @@ def test_played_out_stream_with_marks_equals_a_per_sample_simulation(mode, rate)
     P, F = (rate // 100, 3 * (rate // 100)) if mode == "repeat" else (0, 0)
     js = _host(S=S, rate=rate, depth=depth, conceal=mode, seed=seed)
     dev = NumpyDevice(js)
-    refs = [RefSlot(depth, mode, P, F, seed) for _ in range(S)]
+    refs = [RefSlot(depth, mode, P, F, noise=seed) for _ in range(S)]
     origin = [(1 << 32) - 5 * (rate // 50) - 3, 123456]  # slot 0's timestamps wrap in its sixth packet
     ev = [dtx_events(rate, 1000 * rate // 8000 + 17 * s + (5 if mode == "zero" else 0)) for s in range(S)]
     at = [0] * S
@@ -541,10 +307,6 @@ def test_a_scorer_that_never_gets_a_mark_plans_what_a_scorer_without_comfort_noi
 
 
 # ---- RTP ------------------------------------------------------------------------------------------------------------------------------
-def _rtp(seq, ts, pt=0, ssrc=0x11223344, payload=b""):
-    return struct.pack("!BBHII", 0x80, pt, seq, ts, ssrc) + payload
-
-
 def test_feed_rtp_takes_comfort_noise_and_ignored_types():
     from afx import rtp
     assert rtp.CN_PAYLOAD_TYPE == 13 and 13 not in rtp.STATIC_PAYLOAD_TYPES
@@ -618,7 +380,7 @@ def test_a_session_exported_mid_silence_continues_in_another_scorer_and_the_refu
     kw = dict(depth=depth, conceal="repeat", period=P, fade=F, ts_bits=None)
     A, B = _host(S=2, seed=11, **kw), _host(S=3, seed=11, max_pending=2, **kw)
     da, db = NumpyDevice(A), NumpyDevice(B)
-    ref = RefSlot(depth, "repeat", P, F, 11)
+    ref = RefSlot(depth, "repeat", P, F, noise=11)
     x = np.arange(1, 401, dtype=np.float32)
 
     def feed(js, dev, slot, t, n, marks=()):

@@ -1,7 +1,7 @@
 """Every slot its own clock rate in one jitter buffer (afx/jitter.py MixedJitterScorer), without a GPU.  The three new entry
 points (afx_k_jitter_place_rates / _conceal_rates / _release_rates) are restated in numpy exactly as include/afx.h states
-them, on the host-only scorer's own ring, from the host table the launches would take; what a slot releases must equal a
-per-sample simulation of its played-out stream E bit for bit, with its counters, whatever the other slots' rates.  Also: a
+them (oracle/jitter.py's ``NumpyDevice``), on the host-only scorer's own ring, from the host table the launches would take; what
+a slot releases must equal the per-sample simulation of its played-out stream E (its ``RefSlot``) bit for bit, with its counters, whatever the other slots' rates.  Also: a
 slot wraps its ring at its own J and leaves the columns beyond it alone, the plan for a pool all at one rate is the one-rate
 ``JitterScorer``'s plan with a rate column, the checks and refusals (each leaving the scorer unchanged), the state an export
 adds with the cross-refusals, and the new entry points in the header, the library and the ctypes table."""
@@ -9,282 +9,34 @@ import ctypes
 import os
 import random
 import re
-import struct
 
 import numpy as np
 import pytest
 import torch
 
+import packet_helpers
+from oracle.jitter import NumpyDevice, RefSlot, Schedule as _Schedule, packet, per_packet, rtp as _rtp, sizing as _sizing
+from packet_helpers import bits as _bits, go as _go, inner as _inner, same as _same, snap as _snap
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 H = 4000
-ENCODINGS = ("pcm_f32le", "pcm_s16le", "mulaw", "alaw")
-BPS = {"pcm_f32le": 4, "pcm_s16le": 2, "mulaw": 1, "alaw": 1}
 FORMATS = [(8000, "mulaw"), (8000, "alaw"), (11025, "pcm_s16le"), (16000, "pcm_f32le"), (48000, "pcm_s16le")]
 ENC_AT = {8000: ("mulaw", "alaw"), 11025: ("pcm_s16le",), 16000: ("pcm_f32le",), 48000: ("pcm_s16le",)}
 SLOT_RATES = [8000, 11025, 16000, 48000, 8000, 48000]
 DEPTH_MS = 60
 
 
-def _mulaw_table():
-    t = []
-    for c in range(256):
-        u = ~c & 0xFF
-        v = ((((u & 15) << 3) + 132) << ((u >> 4) & 7)) - 132
-        t.append(-v if u & 0x80 else v)
-    return np.array(t, dtype=np.float32) / np.float32(32768)
-
-
-def _alaw_table():
-    t = []
-    for c in range(256):
-        a = c ^ 0x55
-        e, m = (a >> 4) & 7, a & 15
-        v = ((m << 4) + 264) << (e - 1) if e else (m << 4) + 8
-        t.append(v if a & 0x80 else -v)
-    return np.array(t, dtype=np.float32) / np.float32(32768)
-
-
-TABLES = {"mulaw": _mulaw_table(), "alaw": _alaw_table()}
-
-
-def decode_ref(raw, encoding):
-    if encoding in TABLES:
-        return TABLES[encoding][np.frombuffer(raw, dtype=np.uint8)]
-    if encoding == "pcm_s16le":
-        return np.frombuffer(raw, dtype="<i2").astype(np.float32) / np.float32(32768)
-    assert encoding == "pcm_f32le"
-    return np.frombuffer(raw, dtype="<f4").astype(np.float32)
-
-
 def _packet(encoding, n, g):
-    """n random samples as ``encoding`` -> (the bytes, their decoded fp32 values)."""
-    if encoding == "pcm_f32le":
-        raw = g.standard_normal(n).astype("<f4").tobytes()
-    elif encoding == "pcm_s16le":
-        raw = g.integers(-32768, 32768, n).astype("<i2").tobytes()
-    else:
-        raw = g.integers(0, 256, n).astype(np.uint8).tobytes()
-    return raw, decode_ref(raw, encoding)
+    return packet(encoding, n, g, amp=1.0, div=1)  # full-scale noise
+
+
+def Schedule(rate, encodings, seed, jump=0, P=0, **kw):
+    return _Schedule(rate, encodings, seed, jump=jump, short=max(1, P // 2), payload=per_packet(amp=1.0, div=1), **kw)
 
 
 @pytest.fixture(scope="module", autouse=True)
 def built():
-    import __graft_entry__ as ge
-    ge.build()  # a state records the library's build id, and the entry points are looked up in the built library
-    from afx import _lib
-    return _lib
-
-
-def _sizing(rate, mode="repeat", depth_ms=DEPTH_MS, hop=H):
-    """(depth, P, F, lookback, W, J) of a rate as the issue states them, from the Resampler's L, M, T alone."""
-    from afx.resample import Resampler
-    rs = Resampler(rate, "cpu")
-    depth = depth_ms * rate // 1000
-    P, F = (rate // 100, 3 * (rate // 100)) if mode == "repeat" else (0, 0)
-    lookback = max(0 if rs.identity else rs.T - 1, P + F)
-    W = depth + -(-hop * rs.M // rs.L) + 1
-    return depth, P, F, lookback, W, lookback + W
-
-
-# ---- the reference: one slot's played-out stream, per sample (tests/test_cpu_jitter.py's, restated; it also keeps the gaps) ----
-class RefSlot:
-    def __init__(self, depth, mode, P, F):
-        self.depth, self.mode, self.P, self.F = depth, mode, P, F
-        self.fade = (1.0 - np.arange(max(F, 1), dtype=np.float64) / max(F, 1)).astype(np.float32)
-        self.got, self.E = {}, []
-        self.next = self.hi = 0
-        self.gap = None
-        self.max_start = None
-        self.stats = dict(received=0, late=0, duplicate=0, concealed=0, out_of_order=0)
-        self.releases, self.spans = [], []  # the gaps [i, j) of every release; every gap of E as [origin, end)
-
-    def packet(self, t, values):
-        if self.max_start is not None and t < self.max_start:
-            self.stats["out_of_order"] += 1
-        self.max_start = t if self.max_start is None else max(self.max_start, t)
-        for k, v in enumerate(values):
-            i = t + k
-            if i < self.next:
-                self.stats["late"] += 1
-            elif i in self.got:
-                self.stats["duplicate"] += 1
-            else:
-                self.got[i] = v
-                self.stats["received"] += 1
-                self.hi = max(self.hi, i + 1)
-
-    def release(self, upto):
-        gaps = []
-        for i in range(self.next, upto):
-            if i in self.got:
-                v, self.gap = self.got.pop(i), None
-            else:
-                if self.gap is None:
-                    self.gap = i
-                d = i - self.gap
-                v = np.float32(0)
-                if self.mode == "repeat" and d < self.F:
-                    j = self.gap - self.P + d % self.P
-                    v = np.float32(self.fade[d] * (self.E[j] if j >= 0 else np.float32(0)))
-                self.stats["concealed"] += 1
-                if gaps and gaps[-1][1] == i:
-                    gaps[-1][1] = i + 1
-                else:
-                    gaps.append([i, i + 1])
-                if self.spans and self.spans[-1][0] == self.gap:
-                    self.spans[-1][1] = i + 1
-                else:
-                    self.spans.append([self.gap, i + 1])
-            self.E.append(np.float32(v))
-        if upto > self.next:
-            self.releases.append(gaps)
-        self.next = max(self.next, upto)
-        self.hi = max(self.hi, self.next)
-
-    def after_feed(self):
-        self.release(max(self.next, self.hi - self.depth))
-
-
-class Schedule:
-    """One slot's traffic (tests/test_gpu_jitter.py's, restated, with packet k in encodings[k % len(encodings)]): 20-ms packets
-    (one short one between two lost ones), a forward jump, losses, duplicates and shuffles within the depth, grouped into
-    ticks (the packets one ``feed`` delivers)."""
-
-    def __init__(self, rate, encodings, seed, jump=0, P=0, n_pk=72, origin=None, depth_pk=3):
-        rng = random.Random(seed)
-        g = np.random.default_rng(seed)
-        n = rate // 50
-        sizes = [n] * n_pk
-        sizes[11] = max(1, P // 2)  # between two lost packets: two gaps closer than P
-        offs = np.concatenate([[0], np.cumsum(sizes)]).tolist()
-        self.enc = [encodings[k % len(encodings)] for k in range(n_pk)]
-        self.pk = [_packet(self.enc[k], sizes[k], g) for k in range(n_pk)]
-        self.origin = rng.randrange(1 << 32) if origin is None else origin
-        self.start = [offs[k] + (jump if k >= 44 else 0) for k in range(n_pk)]  # packet 44 begins `jump` samples late
-        forced = {10, 12, 25, 26, 27, 28}  # 25..28: 80 ms > F + P
-        calm = set(range(6, 34))  # delivered in order around the forced gaps
-        self.lost = set(forced)
-        ticks, k = [], 0
-        while k < n_pk:
-            if k == 11:  # the short packet and four more in one feed: both gaps fall in its release
-                ticks.append([11, 13, 14, 15, 16])
-                k = 17
-                continue
-            if k in calm:
-                if k not in forced:
-                    ticks.append([k])
-                k += 1
-                continue
-            blk = [q for q in range(k, min(k + depth_pk, n_pk)) if q not in calm]
-            k = blk[-1] + 1
-            for q in list(blk):
-                if q and rng.random() < 0.05:
-                    blk.remove(q)
-                    self.lost.add(q)
-            blk += [q for q in blk if rng.random() < 0.15]  # duplicates
-            rng.shuffle(blk)  # within depth_pk packets = the depth: every packet is on time
-            if 0 in blk:  # the first packet accepted is the session's origin: index 0 here
-                blk.remove(0)
-                blk.insert(0, 0)
-            while blk:
-                m = rng.randint(1, 3)
-                ticks.append(blk[:m])
-                blk = blk[m:]
-        self.ticks, self.at = ticks, 0
-
-    def done(self):
-        return self.at >= len(self.ticks)
-
-    def tick(self):
-        """-> [(timestamp, relative index, bytes, decoded, encoding)] of the next tick."""
-        ks = self.ticks[self.at]
-        self.at += 1
-        return [((self.origin + self.start[k]) % (1 << 32), self.start[k], self.pk[k][0], self.pk[k][1], self.enc[k]) for k in ks]
-
-
-# ---- the jitter kernels restated on a numpy ring ---------------------------------------------------------------------------
-class NumpyDevice:
-    """Runs a Plan's launches as include/afx.h states them for the three ``_rates`` entry points (a one-rate scorer's plan:
-    for afx_k_jitter_place / _place_mixed / _conceal / _release), validates every row against ITS rate as the device does,
-    checks what the host promises (rows of one launch disjoint, headers equal to ingest.plan of the playout counter) and
-    collects what each slot releases.  A rate's J, P, F, L, M come from the host table the launches take."""
-
-    def __init__(self, js):
-        self.js, self.rated = js, js._rated
-        self.ring = js.jring.numpy()  # the host-only scorer's own (CPU) ring
-        if self.rated:
-            self.rate = [dict(J=t.J, P=t.P, F=t.F, L=t.L, M=t.M, T=t.T, fade=js._fades[i].numpy()) for i, t in enumerate(js._table)]
-            assert all(r["fade"].size == max(r["F"], 1) for r in self.rate)
-        else:
-            self.rate = [dict(J=js.J, P=js.period, F=js.fade_len, L=js.L, M=js.M, fade=js.fade.numpy())]
-        self.Js = self.ring.shape[1]
-        self.out = [[] for _ in range(js.S)]
-        self.N = [0] * js.S
-        self.launches, self.rounds = [], []
-
-    def reset(self, s):
-        self.out[s], self.N[s] = [], 0
-
-    def _rate_of_row(self, s, tail):
-        if not self.rated:
-            assert not tail
-            return self.rate[0]
-        (ri,) = tail
-        assert 0 <= ri < len(self.rate) and ri == int(self.js._rate_of[s])  # a row carries its slot's rate
-        return self.rate[ri]
-
-    def run(self, plan, pay):
-        from afx.ingest import layout, plan as ingest_plan
-        js = self.js
-        offs, total = layout([len(p) for p in pay])
-        stage = bytearray(total)
-        for o, p in zip(offs, pay):
-            stage[o:o + len(p)] = bytes(p)
-        self.rounds.append([op[0] for op in plan.ops])
-        for op in plan.ops:
-            self.launches.append(op[0])
-            if op[0] == "pop":
-                continue
-            rows = op[1]
-            assert rows.dtype == np.int32 and len(rows) >= 1
-            if op[0] == "place":
-                assert rows.shape[1] == (6 if self.rated else 5)
-                written = set()
-                for s, off, n, col, enc, *tail in rows.tolist():
-                    r = self._rate_of_row(s, tail)
-                    J, bps = r["J"], BPS[ENCODINGS[enc]]
-                    assert 0 < n <= op[2] <= self.Js and n <= J and 0 <= col < J and off % bps == 0 and off + n * bps <= total
-                    cols = {(s, (col + k) % J) for k in range(n)}
-                    assert not (cols & written)  # the rows of one launch write disjoint ranges
-                    written |= cols
-                    self.ring[s, (col + np.arange(n)) % J] = decode_ref(bytes(stage[off:off + n * bps]), ENCODINGS[enc])
-            elif op[0] == "conceal":
-                assert rows.shape[1] == (5 if self.rated else 4)
-                assert len(set(rows[:, 0].tolist())) == len(rows)  # one gap per slot and launch: gaps of a slot are ordered
-                for s, ac, lo, hi, *tail in rows.tolist():
-                    r = self._rate_of_row(s, tail)
-                    J, P, F = r["J"], r["P"], r["F"]
-                    assert 0 <= ac < J and 0 <= lo < hi and hi - lo <= op[2] and hi + P <= J
-                    for d in range(lo, hi):
-                        v = np.float32(0)
-                        if js.conceal == "repeat" and d < F:
-                            v = np.float32(r["fade"][d] * self.ring[s, (ac - P + d % P) % J])
-                        self.ring[s, (ac + d) % J] = v
-            else:
-                assert op[0] == "release" and rows.shape[1] == 8 and len(set(rows[:, 0].tolist())) == len(rows)
-                for s, col, n_in, n_out, p0, d0, wpos, ri in rows.tolist():
-                    r = self._rate_of_row(s, (ri,) if self.rated else ())
-                    assert self.rated or ri == 0
-                    J = r["J"]
-                    assert (n_out, p0, d0) == ingest_plan(self.N[s], n_in, r["L"], r["M"]) and col == self.N[s] % J and p0 < r["L"]
-                    assert 0 < n_in <= J and n_out <= op[2] <= js.ring_len and 0 <= wpos < js.ring_len
-                    self.out[s].extend(self.ring[s, (col + np.arange(n_in)) % J].tolist())
-                    self.N[s] += n_in
-
-
-def _inner(S):
-    from afx.streaming import SlidingWindowScorer
-    return SlidingWindowScorer(None, S, window=16000, hop=H, device="cpu")
+    return packet_helpers.built()
 
 
 def _mixed(S=6, formats=FORMATS, depth_ms=DEPTH_MS, rates=None, **kw):
@@ -300,25 +52,6 @@ def _plain(S, rate, mode="repeat", depth_ms=DEPTH_MS, **kw):
     from afx.jitter import JitterScorer
     depth, P, F, _, _, _ = _sizing(rate, mode, depth_ms)
     return JitterScorer(_inner(S), rate, ENC_AT[rate], depth, conceal=mode, period=P or None, fade=F if mode == "repeat" else None, **kw)
-
-
-def _bits(x):
-    return np.asarray(x, dtype=np.float32).view(np.uint32)
-
-
-def _go(js, dev, plan, pay=()):
-    dev.run(plan, list(pay))
-    js._commit(plan.book)
-
-
-def _snap(js):
-    e = js.export_slots(list(range(js.S)))
-    extra = [js.rates] if js._rated else []
-    return [js.pending, js.samples_in, js.buffered, js.samples_seen] + extra + list(js.stats().values()) + [e.tensors[k] for k in sorted(e.tensors)]
-
-
-def _same(a, b):
-    return len(a) == len(b) and all(torch.equal(x, y) for x, y in zip(a, b))
 
 
 SENTINEL = np.float32(-7.25)
@@ -465,10 +198,6 @@ def test_timestamps_unwrap_across_two_to_the_32_in_a_48_khz_slot():
 
 
 # ---- checks and refusals -------------------------------------------------------------------------------------------------
-def _rtp(seq, ts, pt=0, ssrc=0x11223344, payload=b""):
-    return struct.pack("!BBHII", 0x80, pt, seq, ts, ssrc) + payload
-
-
 def test_constructor_refusals_and_per_slot_properties():
     from afx.jitter import MixedJitterScorer
     sc = _inner(2)

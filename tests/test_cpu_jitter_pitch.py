@@ -1,8 +1,9 @@
 """Pitch-period loss concealment, the host side (afx/jitter.py conceal="pitch_sync"): the numpy statement of the function itself
 (``pitch_reference``, ``quantize``, ``gain_table``) on the signals it was prototyped on, the geometry it adds to a scorer, the
 plans of a host-only scorer (where the estimate goes, and that a "repeat" scorer plans what it planned), the played-out stream
-of those plans run on a numpy ring against a per-sample simulation, the refusals of the four entry points and the session
-state.  No GPU: the kernels are restated in numpy from include/afx.h."""
+of those plans run on a numpy ring against the per-sample simulation, the refusals of the four entry points and the session
+state.  No GPU: the kernels restated in numpy from include/afx.h and the simulation are oracle/jitter.py's ``NumpyDevice`` and
+``RefSlot``."""
 import ctypes
 import os
 import re
@@ -10,6 +11,10 @@ import re
 import numpy as np
 import pytest
 import torch
+
+import packet_helpers
+from oracle.jitter import NumpyDevice, RefSlot, voiced
+from packet_helpers import bits as _bits, go as _go
 
 H = 4000
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,17 +24,7 @@ RATES = (8000, 16000, 48000)
 
 @pytest.fixture(scope="module", autouse=True)
 def built():
-    import __graft_entry__ as ge
-    ge.build()  # a state records the library's build id, and the entry points are looked up in the built library
-    from afx import _lib
-    return _lib
-
-
-def voiced(rate, f0, n, seed):
-    """The signal the rule was prototyped on: seven harmonics of f0 and a little noise, fp32."""
-    t = np.arange(n) / rate
-    x = 0.1 * sum(np.sin(2 * np.pi * f0 * k * t + k) / k for k in range(1, 8))
-    return (x + 0.003 * np.random.default_rng(seed).standard_normal(n)).astype(np.float32)
+    return packet_helpers.built()
 
 
 def _host(S=3, rate=8000, encoding="pcm_f32le", depth=160, **kw):
@@ -130,98 +125,6 @@ def test_constructor_refusals():
     assert ms._rlookback.tolist() == [600, 3600] and ms._rJ.tolist() == [_host(rate=r, depth=60 * r // 1000, conceal="pitch_sync").J for r, _ in fm]
 
 
-# ---- the kernels restated on a numpy ring ------------------------------------------------------------------------------------------
-class NumpyDevice:
-    """Runs a Plan's launches as include/afx.h states them (pcm_f32le packets; a rated plan's rows end in their rate index),
-    checks what the host promises of the new launches and collects what each slot releases."""
-
-    def __init__(self, js):
-        self.js, self.ring, self.period = js, js.jring.numpy(), js.jperiod.numpy()
-        self.out = [[] for _ in range(js.S)]
-        self.kinds = []
-
-    def run(self, plan, pay):
-        from afx.ingest import layout
-        from afx.jitter import pitch_reference
-        js = self.js
-        offs, total = layout([len(p) for p in pay])
-        stage = bytearray(total)
-        for o, p in zip(offs, pay):
-            stage[o:o + len(p)] = bytes(p)
-        for op in plan.ops:
-            self.kinds.append(op[0])
-            if op[0] == "pop":
-                continue
-            rows = op[1].tolist()
-            for row in rows:
-                s, r = row[0], row[-1] if js._rated else 0
-                assert not js._rated or r == js._rate_of[s]
-                J, rate = int(js._rJ[r]), js._rates[r]
-                Pmin, Pmax, Wc, P0, G = (int(a[r]) for a in (js._rPmin, js._rPmax, js._rWc, js._rP, js._rG))
-                if op[0] == "place":
-                    _, off, n, col = row[:4]
-                    self.ring[s, (col + np.arange(n)) % J] = np.frombuffer(bytes(stage[off:off + 4 * n]), dtype="<f4")
-                elif op[0] == "pitch":
-                    ac, Lh = row[1], Pmax + Wc
-                    assert len(row) == (3 if js._rated else 2) and 0 <= ac < J and Lh <= J and op[2] >= Lh
-                    self.period[s] = pitch_reference(self.ring[s, (ac - Lh + np.arange(Lh)) % J], rate, P0)
-                elif op[0] == "conceal":
-                    _, ac, lo, hi = row[:4]
-                    assert 0 <= ac < J and 0 <= lo < hi and hi - lo <= op[2] and hi + Pmax <= J
-                    p = int(self.period[s]) if Pmin <= self.period[s] <= Pmax else P0
-                    gain = js._fades[r].numpy()
-                    for d in range(lo, hi):
-                        self.ring[s, (ac + d) % J] = gain[d] * self.ring[s, (ac - p + d % p) % J] if d < G else np.float32(0)
-                else:
-                    assert op[0] == "release"
-                    _, col, n_in = row[:3]
-                    self.out[s].extend(self.ring[s, (col + np.arange(n_in)) % J].tolist())
-            if op[0] in ("pitch", "conceal"):
-                assert len({row[0] for row in rows}) == len(rows)  # one gap per slot and launch
-
-
-class RefSlot:
-    """One slot's played-out stream, per sample, from the function as the module docstring states it."""
-
-    def __init__(self, rate, depth, hold=None, fade=None):
-        from afx.jitter import gain_table, pitch_lags
-        self.rate, self.depth = rate, depth
-        (_, self.Pmax, self.Wc), self.Hd, self.F = pitch_lags(rate), rate // 100 if hold is None else hold, rate // 20 if fade is None else fade
-        self.gain = gain_table(self.Hd, self.F)
-        self.got, self.E, self.next, self.hi, self.gap, self.p, self.periods = {}, [], 0, 0, None, None, []
-
-    def packet(self, t, values):
-        for k, v in enumerate(values):
-            if t + k >= self.next and t + k not in self.got:
-                self.got[t + k] = v
-                self.hi = max(self.hi, t + k + 1)
-
-    def release(self, upto):
-        from afx.jitter import pitch_reference
-        for i in range(self.next, upto):
-            if i in self.got:
-                v, self.gap = self.got.pop(i), None
-            else:
-                if self.gap is None:
-                    self.gap, self.p = i, pitch_reference(np.array(self.E[-(self.Pmax + self.Wc):], dtype=np.float32), self.rate)
-                    self.periods.append(self.p)
-                d = i - self.gap
-                v = self.gain[d] * (self.E[self.gap - self.p + d % self.p] if self.gap - self.p + d % self.p >= 0 else np.float32(0)) \
-                    if d < self.Hd + self.F else np.float32(0)
-            self.E.append(np.float32(v))
-        self.next = max(self.next, upto)
-        self.hi = max(self.hi, self.next)
-
-
-def _go(js, dev, plan, pay=()):
-    dev.run(plan, list(pay))
-    js._commit(plan.book)
-
-
-def _bits(x):
-    return np.asarray(x, dtype=np.float32).view(np.uint32)
-
-
 # ---- plans -------------------------------------------------------------------------------------------------------------------------
 def _kinds(plan):
     return [op[0] for op in plan.ops if op[0] != "pop"]
@@ -237,7 +140,7 @@ def _feed(js, dev, x, k, n, slot=0):
 def test_a_gap_released_over_three_calls_has_one_pitch_row_at_the_first():
     n, x = 160, voiced(8000, 125, 40 * 160, 5)
     js = _host(S=2, depth=3 * n, conceal="pitch_sync")
-    dev, ref = NumpyDevice(js), RefSlot(8000, 3 * n)
+    dev, ref = NumpyDevice(js), RefSlot(3 * n, "pitch_sync", rate=8000)
     plans = {}
     for k in [q for q in range(20) if q not in (6, 7, 8, 9)]:  # 80 ms lost: released by the feeds of packets 10, 11 and 12
         plans[k] = _feed(js, dev, x, k, n, slot=1)
@@ -258,7 +161,7 @@ def test_a_gap_released_over_three_calls_has_one_pitch_row_at_the_first():
 def test_two_gaps_of_one_slot_in_one_release_are_estimated_in_rank_order():
     n, x = 160, voiced(8000, 97, 40 * 160, 6)
     js = _host(S=1, depth=0, conceal="pitch_sync")
-    dev, ref = NumpyDevice(js), RefSlot(8000, 0)
+    dev, ref = NumpyDevice(js), RefSlot(0, "pitch_sync", rate=8000)
     for k in range(4):
         _feed(js, dev, x, k, n)
     # packets 4 and 6 lost, 5 and 7 in one feed: the second gap's history holds the first gap's concealed samples
@@ -275,7 +178,7 @@ def test_two_gaps_of_one_slot_in_one_release_are_estimated_in_rank_order():
 def test_a_row_past_hold_and_fade_is_rebased_and_has_no_pitch():
     n, x = 160, voiced(8000, 180, 40 * 160, 7)
     js = _host(S=1, depth=0, conceal="pitch_sync", hold=40, fade=100)
-    dev, ref = NumpyDevice(js), RefSlot(8000, 0, 40, 100)
+    dev, ref = NumpyDevice(js), RefSlot(0, "pitch_sync", rate=8000, hold=40, fade=100)
     for k in range(3):
         _feed(js, dev, x, k, n)
     adv = js._plan([0], mode="advance", upto=3 * n + 100)  # the gap opens: d in [0, 100)
@@ -338,7 +241,7 @@ def test_a_lossy_stream_of_a_host_scorer_equals_the_per_sample_simulation():
     ms.reset([0, 1], [11025, 8000])
     one = _host(S=1, rate=11025, depth=40 * 11025 // 1000, conceal="pitch_sync")
     devs, rates = (NumpyDevice(ms), NumpyDevice(one)), (11025, 8000)
-    refs = [RefSlot(r, 40 * r // 1000) for r in rates]
+    refs = [RefSlot(40 * r // 1000, "pitch_sync", rate=r) for r in rates]
     xs = [voiced(r, f, 50 * (r // 50), 9) for r, f in zip(rates, (180, 97))]
     lost = [{k for k in range(3, 50) if rng.random() < 0.2} | {20, 21, 22, 23, 24}, {k for k in range(3, 50) if rng.random() < 0.2}]
     for k0 in range(0, 50, 2):
@@ -361,7 +264,7 @@ def test_a_lossy_stream_of_a_host_scorer_equals_the_per_sample_simulation():
         assert np.array_equal(_bits(devs[0].out[s]), _bits(refs[s].E)) and len(refs[s].periods) >= 4
         assert any(p != rates[s] // 100 for p in refs[s].periods)
     assert np.array_equal(_bits(devs[1].out[0]), _bits(refs[0].E)) and int(devs[1].period[0]) == int(devs[0].period[0])
-    assert devs[0].kinds.count("pitch") >= 4 and "pitch" in devs[1].kinds
+    assert devs[0].launches.count("pitch") >= 4 and "pitch" in devs[1].launches
 
 
 # ---- the ABI -------------------------------------------------------------------------------------------------------------------------
@@ -460,6 +363,7 @@ def test_the_period_of_an_open_gap_moves_with_its_session():
     assert other.jperiod.tolist() == [0, 64] and other.export_slots([1]).tensors["jitter_pitch"].tolist() == [64]
     # ... and the gap goes on in the new scorer with that period: the same samples as in the old one
     a, b = NumpyDevice(js), NumpyDevice(other)
+    a.N[2] = b.N[1] = 4 * 160 + 100  # (the playout counter of the session both devices take up)
     _go(js, a, js._plan([2], mode="advance", upto=4 * 160 + 300))
     _go(other, b, other._plan([1], mode="advance", upto=4 * 160 + 300))
     assert len(a.out[2]) == 200 and np.array_equal(_bits(a.out[2]), _bits(b.out[1])) and np.count_nonzero(a.out[2]) > 190

@@ -3,34 +3,17 @@ blocks on, under and over the 64-code step, on both clamps, and PCM rows, with b
 poison; then every front in a codec against the same front in a native encoding fed ``codecs.reference`` of the same packets
 in the same calls.  Every equality is bit for bit."""
 import random
-import struct
 
 import numpy as np
 import pytest
 import torch
 
+from oracle.jitter import rtp
+from packet_helpers import tap as _tap
+
 pytestmark = pytest.mark.gpu
 
 H = 4000
-
-
-def _tap(S):
-    from afx.streaming import SlidingWindowScorer
-
-    class Tap(SlidingWindowScorer):
-        def __init__(self):
-            super().__init__(None, S, window=4 * H, hop=H, device="cuda")
-            self.got = [[] for _ in range(S)]
-
-        def push(self, chunk, slots=None):
-            idx = self._slot_list(slots, ordered=True)
-            assert chunk.is_cuda and chunk.dtype == torch.float32 and chunk.shape == (len(idx), H)
-            for i, s in enumerate(idx):
-                self.got[s].append(chunk[i].clone())
-            self._seen[idx] += H
-            return torch.zeros(len(idx), device=chunk.device)
-
-    return Tap()
 
 
 def _same_hops(a, b, least=1):
@@ -214,7 +197,7 @@ def test_jitter_scorer_with_two_codecs_on_a_lossy_network_equals_the_native_one(
 
 # ---- every slot its own rate and codec, fed as RTP ----------------------------------------------------------------------
 def _rtp(seq, ts, pt, payload, ssrc):
-    return struct.pack("!BBHII", 0x80, pt, seq & 0xFFFF, ts & 0xFFFFFFFF, ssrc) + payload
+    return rtp(seq & 0xFFFF, ts & 0xFFFFFFFF, pt=pt, ssrc=ssrc, payload=payload)  # (the callers' counters run past the wrap)
 
 
 FORMATS = [(8000, "mulaw"), (8000, "dvi4"), (16000, "dvi4"), (44100, "pcm_s16be")]

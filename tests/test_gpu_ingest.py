@@ -11,48 +11,18 @@ import random
 import numpy as np
 import pytest
 import torch
-from scipy import signal
+
+from oracle.jitter import BPS, ENCODINGS, TABLES, packet
+from packet_helpers import ref64 as _ref64, tap as _tap
 
 pytestmark = pytest.mark.gpu
 
 H = 4000
-ENCODINGS = ("pcm_f32le", "pcm_s16le", "mulaw", "alaw")
-
-
-def _mulaw_table():
-    t = []
-    for c in range(256):
-        u = ~c & 0xFF
-        v = ((((u & 15) << 3) + 132) << ((u >> 4) & 7)) - 132
-        t.append(-v if u & 0x80 else v)
-    return np.array(t, dtype=np.float32)
-
-
-def _alaw_table():
-    t = []
-    for c in range(256):
-        a = c ^ 0x55
-        e, m = (a >> 4) & 7, a & 15
-        v = ((m << 4) + 264) << (e - 1) if e else (m << 4) + 8
-        t.append(v if a & 0x80 else -v)
-    return np.array(t, dtype=np.float32)
-
-
-TABLES = {"mulaw": _mulaw_table(), "alaw": _alaw_table()}
-BPS = {"pcm_f32le": 4, "pcm_s16le": 2, "mulaw": 1, "alaw": 1}
 
 
 def _stream(encoding, n, seed):
-    """n random samples as ``encoding`` -> (the bytes, their host-decoded fp32 values)."""
-    g = np.random.default_rng(seed)
-    if encoding == "pcm_f32le":
-        x = (0.1 * g.standard_normal(n)).astype("<f4")
-        return x.tobytes(), x.astype(np.float32)
-    if encoding == "pcm_s16le":
-        v = g.integers(-32768, 32768, n).astype("<i2")
-        return v.tobytes(), v.astype(np.float32) / np.float32(32768)
-    c = g.integers(0, 256, n).astype(np.uint8)
-    return c.tobytes(), TABLES[encoding][c] / np.float32(32768)
+    """n random samples as ``encoding`` (16-bit ones at full scale) -> (the bytes, their host-decoded fp32 values)."""
+    return packet(encoding, n, np.random.default_rng(seed), div=1)
 
 
 def test_decode_is_exact_for_every_code_and_every_int16():
@@ -61,7 +31,7 @@ def test_decode_is_exact_for_every_code_and_every_int16():
     for law in ("mulaw", "alaw"):
         got = decode(codes, law)
         assert got.is_cuda and got.dtype == torch.float32 and got.shape == (256,)
-        assert torch.equal(got.cpu(), torch.from_numpy(TABLES[law] / np.float32(32768)))
+        assert torch.equal(got.cpu(), torch.from_numpy(TABLES[law]))
         assert torch.equal(decode(np.frombuffer(codes, dtype=np.uint8)[::-1].copy(), law).cpu().flip(0), got.cpu())
     v = np.arange(-32768, 32768, dtype=np.int16)
     want = torch.from_numpy(v.astype(np.float32) / np.float32(32768))
@@ -75,33 +45,6 @@ def test_decode_is_exact_for_every_code_and_every_int16():
 
 
 # ---- ragged resampling alone: a scorer that only records what it is pushed -----------------------------------------------
-def _tap(S):
-    from afx.streaming import SlidingWindowScorer
-
-    class Tap(SlidingWindowScorer):
-        def __init__(self):
-            super().__init__(None, S, window=4 * H, hop=H, device="cuda")
-            self.got = [[] for _ in range(S)]
-
-        def push(self, chunk, slots=None):
-            idx = self._slot_list(slots, ordered=True)
-            assert chunk.is_cuda and chunk.dtype == torch.float32 and chunk.shape == (len(idx), H)
-            for i, s in enumerate(idx):
-                self.got[s].append(chunk[i].clone())
-            self._seen[idx] += H
-            return torch.zeros(len(idx), device=chunk.device)
-
-    return Tap()
-
-
-def _ref64(x, rate):
-    from afx.resample import design_filter
-    L, M, h = design_filter(rate)
-    if L == M:
-        return np.asarray(x, dtype=np.float64)
-    return signal.upfirdn(h, np.asarray(x, dtype=np.float64), L, M)[: -(-len(x) * L // M)]
-
-
 def _sizes(rate, T):
     hop_in = H * rate / 16000
     out = [0, 1, 7, rate // 50, {8000: 263, 11025: 367, 16000: 523, 22050: 727, 44100: 1453, 48000: 1583, 96000: 3167}[rate],

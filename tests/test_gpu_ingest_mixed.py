@@ -3,75 +3,27 @@ a tuple of encodings, afx_k_jitter_place_mixed).  The reference is what this cha
 over ``decode`` of a slot's whole stream, the single-format ``PacketScorer`` and the single-encoding ``JitterScorer``.  Every
 comparison is exact (``torch.equal``): the mixed launch gives an output the fmaf chain the one-format launch gives it."""
 import random
-import struct
 
 import numpy as np
 import pytest
 import torch
 
+from oracle.jitter import BPS, TABLES, packet, rtp
+from packet_helpers import tap
+
 pytestmark = pytest.mark.gpu
 
 H = 4000
-BPS = {"pcm_f32le": 4, "pcm_s16le": 2, "mulaw": 1, "alaw": 1}
 PRIME = {8000: 263, 11025: 367, 16000: 523, 22050: 727, 44100: 1453, 48000: 1583, 96000: 3167}
-
-
-def _mulaw_table():
-    t = []
-    for c in range(256):
-        u = ~c & 0xFF
-        v = ((((u & 15) << 3) + 132) << ((u >> 4) & 7)) - 132
-        t.append(-v if u & 0x80 else v)
-    return np.array(t, dtype=np.float32)
-
-
-def _alaw_table():
-    t = []
-    for c in range(256):
-        a = c ^ 0x55
-        e, m = (a >> 4) & 7, a & 15
-        v = ((m << 4) + 264) << (e - 1) if e else (m << 4) + 8
-        t.append(v if a & 0x80 else -v)
-    return np.array(t, dtype=np.float32)
-
-
-TABLES = {"mulaw": _mulaw_table(), "alaw": _alaw_table()}
 
 
 def _stream(encoding, n, seed, quiet=False):
     """n random samples as ``encoding`` -> their bytes (quiet: speech-like levels rather than full-scale noise)."""
-    g = np.random.default_rng(seed)
-    if encoding == "pcm_f32le":
-        return (0.1 * g.standard_normal(n)).astype("<f4").tobytes()
-    if encoding == "pcm_s16le":
-        v = g.integers(-32768, 32768, n)
-        return (v // 8 if quiet else v).astype("<i2").tobytes()
-    return g.integers(0, 256, n).astype(np.uint8).tobytes()
+    return packet(encoding, n, np.random.default_rng(seed), div=8 if quiet else 1)[0]
 
 
 def _tap(S):
-    """A scorer that only records the hops it is pushed."""
-    from afx.streaming import SlidingWindowScorer
-
-    class Tap(SlidingWindowScorer):
-        def __init__(self):
-            super().__init__(None, S, window=4 * H, hop=H, device="cuda")
-            self.got = [[] for _ in range(S)]
-
-        def _reset_slots(self, idx):
-            super()._reset_slots(idx)
-            for s in idx:
-                self.got[s] = []
-
-        def push(self, chunk, slots=None):
-            idx = self._slot_list(slots, ordered=True)
-            assert chunk.is_cuda and chunk.dtype == torch.float32 and chunk.shape == (len(idx), H)
-            for i, s in enumerate(idx):
-                self.got[s].append(chunk[i].clone())
-            self._seen[idx] += H
-            return torch.zeros(len(idx), device=chunk.device)
-
-    return Tap()
+    return tap(S, clear_on_reset=True)
 
 
 def _offline(data, rate, encoding):
@@ -343,7 +295,7 @@ def test_sessions_move_between_mixed_scorers_and_from_a_plain_packet_scorer():
 
 # ---- jitter: PT 0 and PT 8 on one scorer -------------------------------------------------------------------------------------
 def _rtp(seq, ts, pt, payload, ssrc):
-    return struct.pack("!BBHII", 0x80, pt, seq & 0xFFFF, ts & 0xFFFFFFFF, ssrc) + payload
+    return rtp(seq & 0xFFFF, ts & 0xFFFFFFFF, pt=pt, ssrc=ssrc, payload=payload)  # (the callers' counters run past the wrap)
 
 
 def test_jitter_scores_do_not_depend_on_how_a_packet_was_encoded():
@@ -362,7 +314,7 @@ def test_jitter_scores_do_not_depend_on_how_a_packet_was_encoded():
             codes = g.integers(0, 256, n).astype(np.uint8)
             ts = t0[s] + k * n
             items.append((s, _rtp(k + 7, ts, pt, codes.tobytes(), 0xA0 + s), ts & 0xFFFFFFFF,
-                          (TABLES[law[pt]][codes] / np.float32(32768)).astype("<f4").tobytes()))
+                          TABLES[law[pt]][codes].astype("<f4").tobytes()))
     per = {s: [it for it in items if it[0] == s] for s in (0, 1)}
     for s, (i, j, lost) in ((0, (11, 12, 30)), (1, (20, 21, 41))):  # a reordered pair and a lost datagram per slot
         per[s][i], per[s][j] = per[s][j], per[s][i]

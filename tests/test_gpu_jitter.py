@@ -1,6 +1,6 @@
 """The jitter buffer on the GPU (afx/jitter.py, afx_k_jitter_place / _conceal / _release).  The reference for the played-out
-stream E is restated here in numpy: decode tables, received-sample bookkeeping (first arrival wins, late samples dropped),
-the playout rule and the concealment recurrence over E itself.  A slot's popped 16 kHz stream must be bit-identical to the
+stream E is oracle/jitter.py's ``RefSlot`` in numpy: decode tables, received-sample bookkeeping (first arrival wins, late
+samples dropped), the playout rule and the concealment recurrence over E itself.  A slot's popped 16 kHz stream must be bit-identical to the
 offline ``Resampler`` over that E (and within 2e-6 * max|x| of float64 upfirdn) at four rates, in all four encodings and
 both concealment modes, under a network that drops 5 % of the packets, duplicates some and shuffles within the depth,
 with two gaps closer than P in one release, a gap longer than F and a jump longer than the ring.  The corollaries:
@@ -14,195 +14,21 @@ import random
 import numpy as np
 import pytest
 import torch
-from scipy import signal
+
+from oracle.jitter import BPS, ENCODINGS, RefSlot, Schedule as _Schedule, packet
+from packet_helpers import offline as _offline, ref64 as _ref64, tap as _tap
 
 pytestmark = pytest.mark.gpu
 
 H = 4000
-ENCODINGS = ("pcm_f32le", "pcm_s16le", "mulaw", "alaw")
-BPS = {"pcm_f32le": 4, "pcm_s16le": 2, "mulaw": 1, "alaw": 1}
-
-
-def _mulaw_table():
-    t = []
-    for c in range(256):
-        u = ~c & 0xFF
-        v = ((((u & 15) << 3) + 132) << ((u >> 4) & 7)) - 132
-        t.append(-v if u & 0x80 else v)
-    return np.array(t, dtype=np.float32)
-
-
-def _alaw_table():
-    t = []
-    for c in range(256):
-        a = c ^ 0x55
-        e, m = (a >> 4) & 7, a & 15
-        v = ((m << 4) + 264) << (e - 1) if e else (m << 4) + 8
-        t.append(v if a & 0x80 else -v)
-    return np.array(t, dtype=np.float32)
-
-
-TABLES = {"mulaw": _mulaw_table(), "alaw": _alaw_table()}
 
 
 def _stream(encoding, n, seed):
-    """n random samples as ``encoding`` -> (the bytes, their host-decoded fp32 values)."""
-    g = np.random.default_rng(seed)
-    if encoding == "pcm_f32le":
-        x = (0.1 * g.standard_normal(n)).astype("<f4")
-        return x.tobytes(), x.astype(np.float32)
-    if encoding == "pcm_s16le":
-        v = (g.integers(-32768, 32768, n) // 8).astype("<i2")
-        return v.tobytes(), v.astype(np.float32) / np.float32(32768)
-    c = g.integers(0, 256, n).astype(np.uint8)
-    return c.tobytes(), TABLES[encoding][c] / np.float32(32768)
+    return packet(encoding, n, np.random.default_rng(seed))
 
 
-# ---- the reference: one slot's played-out stream ---------------------------------------------------------------------------
-class Ref:
-    def __init__(self, depth, mode, P, F, cap):
-        self.depth, self.mode, self.P, self.F = depth, mode, P, F
-        self.fade = (1.0 - np.arange(max(F, 1), dtype=np.float64) / max(F, 1)).astype(np.float32)
-        self.val, self.have, self.E = np.zeros(cap, np.float32), np.zeros(cap, bool), np.zeros(cap, np.float32)
-        self.next = self.hi = 0
-        self.gap = None  # the origin of the gap the playout point stands in
-        self.late = self.dup = self.received = self.concealed = 0
-        self.releases = []  # the gaps of every release
-        self.spans = []  # every gap of E as [origin, end), pieces of one gap released by several calls joined
-
-    def packet(self, t, x):
-        n = len(x)
-        lo = min(max(t, self.next), t + n)
-        self.late += lo - t
-        if lo < t + n:
-            new = ~self.have[lo:t + n]
-            self.val[lo:t + n][new] = x[lo - t:][new]
-            self.have[lo:t + n] = True
-            self.dup += int((~new).sum())
-            self.received += int(new.sum())
-            self.hi = max(self.hi, t + n)
-
-    def release(self, upto):
-        i, gaps = self.next, []
-        while i < upto:
-            run = self.have[i:upto]
-            flips = np.flatnonzero(run != run[0])
-            j = i + int(flips[0]) if flips.size else upto
-            if run[0]:
-                self.E[i:j], self.gap = self.val[i:j], None
-            else:
-                a = self.gap = i if self.gap is None else self.gap
-                d = np.arange(i - a, j - a)
-                v = np.zeros(j - i, np.float32)
-                if self.mode == "repeat":
-                    m = d < self.F
-                    src = a - self.P + d[m] % self.P
-                    v[m] = self.fade[d[m]] * np.where(src >= 0, self.E[np.maximum(src, 0)], np.float32(0))
-                self.E[i:j] = v
-                self.concealed += j - i
-                gaps.append((i, j))
-                if self.spans and self.spans[-1][0] == a:
-                    self.spans[-1][1] = j
-                else:
-                    self.spans.append([a, j])
-            i = j
-        if upto > self.next:
-            self.releases.append(gaps)
-            self.next = upto
-        self.hi = max(self.hi, self.next)
-
-    def after_feed(self):
-        self.release(max(self.next, self.hi - self.depth))
-
-
-class Schedule:
-    """One slot's traffic: 20-ms packets (one short one), a forward jump, losses, duplicates and shuffles within the depth,
-    grouped into ticks (the packets one ``feed`` delivers).  ``lossy``: drop 5 % at random and the forced gaps."""
-
-    def __init__(self, rate, encoding, seed, jump=0, P=0, lossy=True, n_pk=72, origin=None, depth_pk=3):
-        rng = random.Random(seed)
-        n = rate // 50
-        sizes = [n] * n_pk
-        sizes[11] = max(1, P // 2) if lossy else n  # between two lost packets: two gaps closer than P
-        offs = np.concatenate([[0], np.cumsum(sizes)]).tolist()
-        self.raw, self.x = _stream(encoding, offs[-1], seed)
-        bps = BPS[encoding]
-        self.origin = rng.randrange(1 << 32) if origin is None else origin
-        self.start = [offs[k] + (jump if k >= 44 else 0) for k in range(n_pk)]  # packet 44 begins `jump` samples late
-        self.size, self.cap = sizes, offs[-1] + jump + 8
-        self.pk = [(self.raw[offs[k] * bps:offs[k + 1] * bps], self.x[offs[k]:offs[k + 1]]) for k in range(n_pk)]
-        forced = {10, 12, 25, 26, 27, 28} if lossy else set()  # 25..28: 80 ms > F + P
-        calm = set(range(6, 34)) if lossy else set()  # delivered in order around the forced gaps
-        self.lost = set(forced)
-        ticks, k = [], 0
-        while k < n_pk:
-            if lossy and k == 11:  # the short packet and four more in one feed: both gaps fall in its release
-                ticks.append([11, 13, 14, 15, 16])
-                k = 17
-                continue
-            if k in calm:
-                if k not in forced:
-                    ticks.append([k])
-                k += 1
-                continue
-            blk = [q for q in range(k, min(k + depth_pk, n_pk)) if q not in calm]
-            k = blk[-1] + 1
-            if lossy:
-                for q in list(blk):
-                    if q and rng.random() < 0.05:
-                        blk.remove(q)
-                        self.lost.add(q)
-            blk += [q for q in blk if rng.random() < 0.15]  # duplicates
-            rng.shuffle(blk)  # within depth_pk packets = the depth: every packet is on time
-            if 0 in blk:  # the first packet accepted is the session's origin: index 0 here
-                blk.remove(0)
-                blk.insert(0, 0)
-            while blk:
-                m = rng.randint(1, 3)
-                ticks.append(blk[:m])
-                blk = blk[m:]
-        self.ticks, self.at = ticks, 0
-
-    def done(self):
-        return self.at >= len(self.ticks)
-
-    def tick(self):
-        """-> [(timestamp, relative index, bytes, decoded)] of the next tick."""
-        ks = self.ticks[self.at]
-        self.at += 1
-        return [((self.origin + self.start[k]) % (1 << 32), self.start[k], self.pk[k][0], self.pk[k][1]) for k in ks]
-
-
-def _tap(S):
-    from afx.streaming import SlidingWindowScorer
-
-    class Tap(SlidingWindowScorer):
-        def __init__(self):
-            super().__init__(None, S, window=4 * H, hop=H, device="cuda")
-            self.got = [[] for _ in range(S)]
-
-        def push(self, chunk, slots=None):
-            idx = self._slot_list(slots, ordered=True)
-            assert chunk.is_cuda and chunk.dtype == torch.float32 and chunk.shape == (len(idx), H)
-            for i, s in enumerate(idx):
-                self.got[s].append(chunk[i].clone())
-            self._seen[idx] += H
-            return torch.zeros(len(idx), device=chunk.device)
-
-    return Tap()
-
-
-def _ref64(x, rate):
-    from afx.resample import design_filter
-    L, M, h = design_filter(rate)
-    if L == M:
-        return np.asarray(x, dtype=np.float64)
-    return signal.upfirdn(h, np.asarray(x, dtype=np.float64), L, M)[: -(-len(x) * L // M)]
-
-
-def _offline(E, rate):
-    from afx.resample import Resampler
-    return Resampler(rate)(torch.from_numpy(np.ascontiguousarray(E)).cuda()[None])[0]
+def Schedule(rate, encoding, seed, P=0, **kw):
+    return _Schedule(rate, encoding, seed, short=max(1, P // 2), **kw)
 
 
 @pytest.mark.parametrize("mode", ["repeat", "zero"])
@@ -220,7 +46,7 @@ def test_played_out_stream_is_the_offline_resampling_of_the_numpy_stream(rate, e
     rng = random.Random(seed)
     sch = [Schedule(rate, encoding, seed + 1000 * s, jump=js.J + 123 + s, P=P, origin=(1 << 32) - 3000 if s == 0 else None)
            for s in range(S)]
-    refs = [Ref(depth, mode, P, F, sc.cap) for sc in sch]
+    refs = [RefSlot(depth, mode, P, F) for sc in sch]
     hops = [0] * S
     while not all(sc.done() for sc in sch):
         ticks = {s: sch[s].tick() for s in range(S) if not sch[s].done() and rng.random() < 0.8}
@@ -231,7 +57,7 @@ def test_played_out_stream_is_the_offline_resampling_of_the_numpy_stream(rate, e
         its = {s: iter(r) for s, r in ticks.items()}
         rows = [(s,) + next(its[s]) for s in order]
         named = []
-        for s, ts, t, raw, x in rows:
+        for s, ts, t, raw, x, e in rows:
             refs[s].packet(t, x)
             named += [s] if s not in named else []
         for s in named:
@@ -253,12 +79,12 @@ def test_played_out_stream_is_the_offline_resampling_of_the_numpy_stream(rate, e
         r.release(r.hi)
         assert int(js.samples_in[s]) == r.next == r.hi and int(js.buffered[s]) == 0
         assert (int(st["received"][s]), int(st["late"][s]), int(st["duplicate"][s]), int(st["concealed"][s])) == \
-            (r.received, r.late, r.dup, r.concealed)
+            tuple(r.stats[k] for k in ("received", "late", "duplicate", "concealed"))
         # the traffic was what the issue asks for: two gaps closer than P in one release, a gap beyond the fade, a jump beyond J
         assert any(len(g) >= 2 and any(b[0] - a[1] < max(P, 1) for a, b in zip(g, g[1:])) for g in r.releases)
         lens = [e - a for a, e in r.spans]
-        assert max(lens) > js.J and sum(1 for n in lens if F + P < n < js.J) >= 1 and r.dup > 0 and len(sch[s].lost) >= 6
-        E = r.E[:r.next]
+        assert max(lens) > js.J and sum(1 for n in lens if F + P < n < js.J) >= 1 and r.stats["duplicate"] > 0 and len(sch[s].lost) >= 6
+        E = np.array(r.E, dtype=np.float32)
         if mode == "repeat":  # concealed samples are there, and they are not zeros
             a, e = next((a, e) for a, e in r.spans if a >= 10 * (rate // 50))
             assert np.count_nonzero(E[a:min(e, a + F)]) > 0.8 * min(e - a, F) - 1
@@ -364,7 +190,7 @@ class _Pair:
     def start(self, s, sch):
         self.sch[s], self.checked[s] = sch, 0
         self.begun.discard(s)  # (a session's origin is its first packet: before it there is nothing to play out)
-        self.ref[s] = Ref(self.P.depth, self.P.conceal, self.P.period, self.P.fade_len, sch.cap + 4 * self.P.J)
+        self.ref[s] = RefSlot(self.P.depth, self.P.conceal, self.P.period, self.P.fade_len)
 
     def made(self, s):
         return -(-self.ref[s].next * self.P.L // self.P.M)
@@ -380,7 +206,7 @@ class _Pair:
         parts = iter(parts)
         for s, w in zip(named, want):
             got = next(parts) if w else res.scores[:0]
-            offline = _offline(self.ref[s].E[:self.ref[s].next], self.rate) if w else None
+            offline = _offline(self.ref[s].E, self.rate) if w else None
             for j in range(w):  # every emitted score of every slot
                 hop = offline[self.checked[s] * H:(self.checked[s] + 1) * H]
                 ref = self.R.push(hop[None].contiguous(), [s])
@@ -393,7 +219,7 @@ class _Pair:
         """One ``feed`` with the next tick of each named slot (rows shuffled by the caller's order)."""
         rows = [(s,) + r for s in slots_ticks for r in self.sch[s].tick()]
         named = []
-        for s, ts, t, raw, x in rows:
+        for s, ts, t, raw, x, e in rows:
             self.ref[s].packet(t, x)
             named += [s] if s not in named else []
         for s in named:
@@ -496,8 +322,8 @@ def test_jitter_scores_equal_inner_on_the_offline_stream(kind, rate, encoding, m
     for s in (1, 0):
         Y.ref[s].release(Y.ref[s].hi)
     Y.check(Y.P.flush([1, 0]), [1, 0])
-    assert Y.checked[1] >= n0 + 3 and Y.ref[1].concealed > 0
-    assert int(Y.P.stats()["concealed"][1]) == Y.ref[1].concealed and int(Y.P.stats()["late"][1]) == Y.ref[1].late
+    assert Y.checked[1] >= n0 + 3 and Y.ref[1].stats["concealed"] > 0
+    assert int(Y.P.stats()["concealed"][1]) == Y.ref[1].stats["concealed"] and int(Y.P.stats()["late"][1]) == Y.ref[1].stats["late"]
     # a packet, a resampling and a bare state are refused before anything changes, and the reverse
     keep = _snap(Y.P, [0, 1])
     for foreign in (PacketScorer(_inner(kind, 2), rate, encoding).export_slots([0]), X.R.export_slots([0]),

@@ -3,7 +3,7 @@ bit against ``ComfortNoise.samples`` on a ring prefilled with a sentinel, every 
 of a DTX call (talk spurts, CN marks, lost CNs and lost last packets, late marks, ``advance`` through a silence) against the
 offline resampling of the per-sample numpy stream; the scores against a fresh inner scorer pushed that stream; a session moved
 in mid-silence; and ``feed_rtp`` with CN datagrams and an ignored telephone-event type.  The per-sample reference and the
-traffic are those of tests/test_cpu_jitter_dtx.py."""
+traffic are oracle/jitter.py's ``RefSlot`` and ``dtx_events``."""
 import ctypes
 import io
 import random
@@ -12,21 +12,13 @@ import numpy as np
 import pytest
 import torch
 
-from test_cpu_jitter_dtx import RefSlot, _bits, _rtp, dtx_events
+from oracle.jitter import RefSlot, TABLES, dtx_events, rtp as _rtp
+from packet_helpers import bits as _bits, offline as _offline, tap as _tap
 
 pytestmark = pytest.mark.gpu
 
 H = 4000
 SENTINEL = 7.5
-
-
-def _mulaw_table():
-    t = []
-    for c in range(256):
-        u = ~c & 0xFF
-        v = ((((u & 15) << 3) + 132) << ((u >> 4) & 7)) - 132
-        t.append(-v if u & 0x80 else v)
-    return np.array(t, dtype=np.float32)
 
 
 def _encoded(events, encoding, seed):
@@ -37,35 +29,11 @@ def _encoded(events, encoding, seed):
             out.append((kind, t, v))
         elif encoding == "mulaw":
             c = g.integers(0, 256, len(v)).astype(np.uint8)
-            out.append((kind, t, c.tobytes(), _mulaw_table()[c] / np.float32(32768)))
+            out.append((kind, t, c.tobytes(), TABLES["mulaw"][c]))
         else:
             q = (g.integers(-32768, 32768, len(v)) // 8).astype("<i2")
             out.append((kind, t, q.tobytes(), q.astype(np.float32) / np.float32(32768)))
     return out
-
-
-def _tap(S):
-    from afx.streaming import SlidingWindowScorer
-
-    class Tap(SlidingWindowScorer):
-        def __init__(self):
-            super().__init__(None, S, window=4 * H, hop=H, device="cuda")
-            self.got = [[] for _ in range(S)]
-
-        def push(self, chunk, slots=None):
-            idx = self._slot_list(slots, ordered=True)
-            assert chunk.is_cuda and chunk.dtype == torch.float32 and chunk.shape == (len(idx), H)
-            for i, s in enumerate(idx):
-                self.got[s].append(chunk[i].clone())
-            self._seen[idx] += H
-            return torch.zeros(len(idx), device=chunk.device)
-
-    return Tap()
-
-
-def _offline(E, rate):
-    from afx.resample import Resampler
-    return Resampler(rate)(torch.from_numpy(np.ascontiguousarray(np.asarray(E, dtype=np.float32))).cuda()[None])[0]
 
 
 # ---- the kernel alone -------------------------------------------------------------------------------------------------------------
@@ -135,7 +103,7 @@ class _Call:
         from afx.jitter import ComfortNoise, JitterScorer
         self.rate, self.depth = rate, 3 * (rate // 50)
         self.js = JitterScorer(inner, rate, encoding, self.depth, conceal=mode, comfort_noise=ComfortNoise(cn_seed), **kw)
-        self.refs = [RefSlot(self.depth, mode, self.js.period, self.js.fade_len, cn_seed) for _ in range(S)]
+        self.refs = [RefSlot(self.depth, mode, self.js.period, self.js.fade_len, noise=cn_seed) for _ in range(S)]
         self.ev = [_encoded(dtx_events(rate, seed + 31 * s, n_spurts), encoding, seed + s) for s in range(S)]
         self.origin = [(1 << 32) - 4 * (rate // 50) - 1] + [1000 * s for s in range(1, S)]
         self.at, self.silent = [0] * S, [False] * S
@@ -289,7 +257,7 @@ def test_a_session_moved_on_the_device_in_mid_silence_continues_bit_for_bit():
     c.js = B  # the rest of slot 0's traffic goes to slot 2 of B: the slot index is no part of the function
     c.refs, c.ev, c.origin, c.at, c.silent = [None, None, r], [[], [], c.ev[0]], [0, 0, c.origin[0]], [0, 0, c.at[0]], [False] * 3
     for i in (0, 1):
-        c.refs[i] = RefSlot(c.depth, "repeat", B.period, B.fade_len, 77)
+        c.refs[i] = RefSlot(c.depth, "repeat", B.period, B.fade_len, noise=77)
     while not c.done():
         c.step([2])
         if c.silent[2] and c.rng.random() < 0.3:

@@ -1,217 +1,32 @@
 """Every slot its own clock rate in one jitter buffer, on the GPU (afx/jitter.py MixedJitterScorer, afx_k_jitter_place_rates /
-_conceal_rates / _release_rates).  The references are what this change leaves alone: the numpy restatement of the played-out
-stream E with the offline ``Resampler`` over it (and float64 upfirdn), and the one-rate ``JitterScorer`` fed a slot's own
+_conceal_rates / _release_rates).  The references are what this change leaves alone: the numpy statement of the played-out
+stream E (oracle/jitter.py) with the offline ``Resampler`` over it (and float64 upfirdn), and the one-rate ``JitterScorer`` fed a slot's own
 packets in the same calls.  Every comparison is exact but the float64 one, whose bound is tests/test_gpu_jitter.py's.
 The one-rate and the ``_rates`` entry points are one kernel per verb behind two wrappers; the last test drives all seven
-directly against the numpy restatement of tests/test_cpu_jitter_mixed.py."""
+directly against oracle/jitter.py's ``NumpyDevice``."""
 import random
-import struct
 
 import numpy as np
 import pytest
 import torch
-from scipy import signal
+
+from oracle.jitter import NumpyDevice, RefSlot, Schedule as _Schedule, packet as _packet, per_packet, rtp, sizing
+from packet_helpers import offline as _offline, ref64 as _ref64, tap as _tap
 
 pytestmark = pytest.mark.gpu
 
 H = 4000
-BPS = {"pcm_f32le": 4, "pcm_s16le": 2, "mulaw": 1, "alaw": 1}
 FORMATS = [(8000, "mulaw"), (8000, "alaw"), (11025, "pcm_s16le"), (16000, "pcm_f32le"), (48000, "pcm_s16le")]
 ENC_AT = {8000: ("mulaw", "alaw"), 11025: ("pcm_s16le",), 16000: ("pcm_f32le",), 48000: ("pcm_s16le",)}
 DEPTH_MS = 60
 
 
-def _mulaw_table():
-    t = []
-    for c in range(256):
-        u = ~c & 0xFF
-        v = ((((u & 15) << 3) + 132) << ((u >> 4) & 7)) - 132
-        t.append(-v if u & 0x80 else v)
-    return np.array(t, dtype=np.float32)
+def _sizing(rate, mode):
+    return sizing(rate, mode, DEPTH_MS, H)
 
 
-def _alaw_table():
-    t = []
-    for c in range(256):
-        a = c ^ 0x55
-        e, m = (a >> 4) & 7, a & 15
-        v = ((m << 4) + 264) << (e - 1) if e else (m << 4) + 8
-        t.append(v if a & 0x80 else -v)
-    return np.array(t, dtype=np.float32)
-
-
-TABLES = {"mulaw": _mulaw_table(), "alaw": _alaw_table()}
-
-
-def _packet(encoding, n, g, quiet=False):
-    """n random samples as ``encoding`` -> (the bytes, their host-decoded fp32 values)."""
-    if encoding == "pcm_f32le":
-        x = (0.1 * g.standard_normal(n)).astype("<f4")
-        return x.tobytes(), x.astype(np.float32)
-    if encoding == "pcm_s16le":
-        v = (g.integers(-32768, 32768, n) // 8).astype("<i2")
-        return v.tobytes(), v.astype(np.float32) / np.float32(32768)
-    c = (g.integers(96, 160, n) if quiet else g.integers(0, 256, n)).astype(np.uint8)
-    return c.tobytes(), TABLES[encoding][c] / np.float32(32768)
-
-
-def _sizing(rate, mode, hop=H):
-    """(depth, P, F, lookback, W, J) of a rate as the issue states them, from the Resampler's L, M, T alone."""
-    from afx.resample import Resampler
-    rs = Resampler(rate)
-    depth = DEPTH_MS * rate // 1000
-    P, F = (rate // 100, 3 * (rate // 100)) if mode == "repeat" else (0, 0)
-    lookback = max(0 if rs.identity else rs.T - 1, P + F)
-    W = depth + -(-hop * rs.M // rs.L) + 1
-    return depth, P, F, lookback, W, lookback + W
-
-
-# ---- the reference: one slot's played-out stream (tests/test_gpu_jitter.py's, restated) ----------------------------------------
-class Ref:
-    def __init__(self, depth, mode, P, F, cap):
-        self.depth, self.mode, self.P, self.F = depth, mode, P, F
-        self.fade = (1.0 - np.arange(max(F, 1), dtype=np.float64) / max(F, 1)).astype(np.float32)
-        self.val, self.have, self.E = np.zeros(cap, np.float32), np.zeros(cap, bool), np.zeros(cap, np.float32)
-        self.next = self.hi = 0
-        self.gap = None  # the origin of the gap the playout point stands in
-        self.late = self.dup = self.received = self.concealed = 0
-        self.releases = []  # the gaps of every release
-        self.spans = []  # every gap of E as [origin, end), pieces of one gap released by several calls joined
-
-    def packet(self, t, x):
-        n = len(x)
-        lo = min(max(t, self.next), t + n)
-        self.late += lo - t
-        if lo < t + n:
-            new = ~self.have[lo:t + n]
-            self.val[lo:t + n][new] = x[lo - t:][new]
-            self.have[lo:t + n] = True
-            self.dup += int((~new).sum())
-            self.received += int(new.sum())
-            self.hi = max(self.hi, t + n)
-
-    def release(self, upto):
-        i, gaps = self.next, []
-        while i < upto:
-            run = self.have[i:upto]
-            flips = np.flatnonzero(run != run[0])
-            j = i + int(flips[0]) if flips.size else upto
-            if run[0]:
-                self.E[i:j], self.gap = self.val[i:j], None
-            else:
-                a = self.gap = i if self.gap is None else self.gap
-                d = np.arange(i - a, j - a)
-                v = np.zeros(j - i, np.float32)
-                if self.mode == "repeat":
-                    m = d < self.F
-                    src = a - self.P + d[m] % self.P
-                    v[m] = self.fade[d[m]] * np.where(src >= 0, self.E[np.maximum(src, 0)], np.float32(0))
-                self.E[i:j] = v
-                self.concealed += j - i
-                gaps.append((i, j))
-                if self.spans and self.spans[-1][0] == a:
-                    self.spans[-1][1] = j
-                else:
-                    self.spans.append([a, j])
-            i = j
-        if upto > self.next:
-            self.releases.append(gaps)
-            self.next = upto
-        self.hi = max(self.hi, self.next)
-
-    def after_feed(self):
-        self.release(max(self.next, self.hi - self.depth))
-
-
-class Schedule:
-    """One slot's traffic (tests/test_gpu_jitter.py's, restated, with packet k in encodings[k % len(encodings)]): 20-ms packets
-    (one short one), a forward jump, losses, duplicates and shuffles within the depth, grouped into ticks (the packets one
-    ``feed`` delivers).  ``lossy``: drop 5 % at random and the forced gaps."""
-
-    def __init__(self, rate, encodings, seed, jump=0, P=0, lossy=True, n_pk=72, origin=None, depth_pk=3, quiet=False):
-        rng = random.Random(seed)
-        g = np.random.default_rng(seed)
-        n = rate // 50
-        sizes = [n] * n_pk
-        sizes[11] = max(1, P // 2) if lossy else n  # between two lost packets: two gaps closer than P
-        offs = np.concatenate([[0], np.cumsum(sizes)]).tolist()
-        self.enc = [encodings[k % len(encodings)] for k in range(n_pk)]
-        self.pk = [_packet(self.enc[k], sizes[k], g, quiet) for k in range(n_pk)]
-        self.origin = rng.randrange(1 << 32) if origin is None else origin
-        self.start = [offs[k] + (jump if k >= 44 else 0) for k in range(n_pk)]  # packet 44 begins `jump` samples late
-        self.size, self.cap = sizes, offs[-1] + jump + 8
-        forced = {10, 12, 25, 26, 27, 28} if lossy else set()  # 25..28: 80 ms > F + P
-        calm = set(range(6, 34)) if lossy else set()  # delivered in order around the forced gaps
-        self.lost = set(forced)
-        ticks, k = [], 0
-        while k < n_pk:
-            if lossy and k == 11:  # the short packet and four more in one feed: both gaps fall in its release
-                ticks.append([11, 13, 14, 15, 16])
-                k = 17
-                continue
-            if k in calm:
-                if k not in forced:
-                    ticks.append([k])
-                k += 1
-                continue
-            blk = [q for q in range(k, min(k + depth_pk, n_pk)) if q not in calm]
-            k = blk[-1] + 1
-            if lossy:
-                for q in list(blk):
-                    if q and rng.random() < 0.05:
-                        blk.remove(q)
-                        self.lost.add(q)
-            blk += [q for q in blk if rng.random() < 0.15]  # duplicates
-            rng.shuffle(blk)  # within depth_pk packets = the depth: every packet is on time
-            if 0 in blk:  # the first packet accepted is the session's origin: index 0 here
-                blk.remove(0)
-                blk.insert(0, 0)
-            while blk:
-                m = rng.randint(1, 3)
-                ticks.append(blk[:m])
-                blk = blk[m:]
-        self.ticks, self.at = ticks, 0
-
-    def done(self):
-        return self.at >= len(self.ticks)
-
-    def tick(self):
-        """-> [(timestamp, relative index, bytes, decoded, encoding)] of the next tick."""
-        ks = self.ticks[self.at]
-        self.at += 1
-        return [((self.origin + self.start[k]) % (1 << 32), self.start[k], self.pk[k][0], self.pk[k][1], self.enc[k]) for k in ks]
-
-
-def _tap(S):
-    from afx.streaming import SlidingWindowScorer
-
-    class Tap(SlidingWindowScorer):
-        def __init__(self):
-            super().__init__(None, S, window=4 * H, hop=H, device="cuda")
-            self.got = [[] for _ in range(S)]
-
-        def push(self, chunk, slots=None):
-            idx = self._slot_list(slots, ordered=True)
-            assert chunk.is_cuda and chunk.dtype == torch.float32 and chunk.shape == (len(idx), H)
-            for i, s in enumerate(idx):
-                self.got[s].append(chunk[i].clone())
-            self._seen[idx] += H
-            return torch.zeros(len(idx), device=chunk.device)
-
-    return Tap()
-
-
-def _ref64(x, rate):
-    from afx.resample import design_filter
-    L, M, h = design_filter(rate)
-    if L == M:
-        return np.asarray(x, dtype=np.float64)
-    return signal.upfirdn(h, np.asarray(x, dtype=np.float64), L, M)[: -(-len(x) * L // M)]
-
-
-def _offline(E, rate):
-    from afx.resample import Resampler
-    return Resampler(rate)(torch.from_numpy(np.ascontiguousarray(E)).cuda()[None])[0]
+def Schedule(rate, encodings, seed, jump=0, P=0, quiet=False, **kw):
+    return _Schedule(rate, encodings, seed, jump=jump, short=max(1, P // 2), payload=per_packet(quiet=quiet), **kw)
 
 
 def _rows_of(ticks, rng):
@@ -253,7 +68,7 @@ def test_played_out_stream_of_every_rate_is_the_offline_resampling_of_the_numpy_
     sch = [Schedule(r, ENC_AT[r] if s == 0 or r != 8000 else ("alaw",), seed + 1000 * s, jump=J[s] + 123 + s, P=Pn[s],
                     origin=(1 << 32) - 3000 if s in (0, 4) else None) for s, r in enumerate(SLOT_RATES)]
     assert set(sch[0].enc) == {"mulaw", "alaw"}
-    refs = [Ref(depth[s], mode, P[s], F[s], sc.cap) for s, sc in enumerate(sch)]
+    refs = [RefSlot(depth[s], mode, P[s], F[s]) for s in range(S)]
     L, M = [shape[r].L for r in SLOT_RATES], [shape[r].M for r in SLOT_RATES]
     hops = [0] * S
     while not all(sc.done() for sc in sch):
@@ -284,12 +99,12 @@ def test_played_out_stream_of_every_rate_is_the_offline_resampling_of_the_numpy_
         r.release(r.hi)
         assert int(ms.samples_in[s]) == r.next == r.hi and int(ms.buffered[s]) == 0
         assert (int(st["received"][s]), int(st["late"][s]), int(st["duplicate"][s]), int(st["concealed"][s])) == \
-            (r.received, r.late, r.dup, r.concealed)
+            tuple(r.stats[k] for k in ("received", "late", "duplicate", "concealed"))
         # the traffic: two gaps closer than P in one release, a gap beyond the fade, a jump beyond the slot's own J
         assert any(len(g) >= 2 and any(b[0] - a[1] < Pn[s] for a, b in zip(g, g[1:])) for g in r.releases)
         lens = [e - a for a, e in r.spans]
-        assert max(lens) > J[s] and sum(1 for n in lens if Fn[s] + Pn[s] < n < J[s]) >= 1 and r.dup > 0 and len(sch[s].lost) >= 6
-        E = r.E[:r.next]
+        assert max(lens) > J[s] and sum(1 for n in lens if Fn[s] + Pn[s] < n < J[s]) >= 1 and r.stats["duplicate"] > 0 and len(sch[s].lost) >= 6
+        E = np.array(r.E, dtype=np.float32)
         whole = _offline(E, rate)
         n_h = whole.numel() // H
         assert len(tap.got[s]) == n_h >= 6 and int(ms.pending[s]) == whole.numel() - n_h * H
@@ -487,7 +302,7 @@ def test_sessions_move_mid_gap_between_mixed_scorers_and_in_from_a_plain_jitter_
 
 
 def _rtp(seq, ts, pt, payload, ssrc):
-    return struct.pack("!BBHII", 0x80, pt, seq & 0xFFFF, ts & 0xFFFFFFFF, ssrc) + payload
+    return rtp(seq & 0xFFFF, ts & 0xFFFFFFFF, pt=pt, ssrc=ssrc, payload=payload)  # (the callers' counters run past the wrap)
 
 
 def test_feed_rtp_with_static_and_dynamic_payload_types_equals_feed():
@@ -521,8 +336,8 @@ def test_feed_rtp_with_static_and_dynamic_payload_types_equals_feed():
 def test_one_rate_entry_points_are_the_rates_kernels_with_a_table_of_one_entry():
     """The seven entry points driven directly.  Each verb runs through its one-rate entry point and, on a clone of the
     buffers, through its ``_rates`` entry point with a table of two rates in which the rate under test is entry 1: the
-    whole buffers must come out bit-equal, sentinels included.  Place and conceal must equal the numpy restatement of
-    tests/test_cpu_jitter_mixed.py bit for bit; release the float64 sum over the same fp32 taps within the bound of the
+    whole buffers must come out bit-equal, sentinels included.  Place and conceal must equal oracle/jitter.py's
+    ``NumpyDevice`` bit for bit; release the float64 sum over the same fp32 taps within the bound of the
     float64 comparison above (2e-6 of the largest input).  The rows wrap the ring column and ``wpos``, one has n = 0, one names
     slot S and must be skipped whole; the three rates take the copy, the LDS-tap and the global-tap path of the release."""
     import ctypes as C
@@ -531,7 +346,7 @@ def test_one_rate_entry_points_are_the_rates_kernels_with_a_table_of_one_entry()
     from afx._lib import JitterRate, call_on, check, lib, ptr
     from afx.ingest import ENCODINGS, layout, plan as ingest_plan
     from afx.resample import Resampler
-    from test_cpu_jitter_mixed import NumpyDevice, _packet as packet_of
+    packet_of = lambda e, n, g: _packet(e, n, g, amp=1.0, div=1)  # full-scale noise
     l, S, hop, P, F = lib(), 3, 512, 8, 16
     R = 2 * hop  # the pending ring
     rs = {r: Resampler(r) for r in (16000, 8000, 11025)}
@@ -563,7 +378,7 @@ def test_one_rate_entry_points_are_the_rates_kernels_with_a_table_of_one_entry()
             t.L, t.M, t.T = y.L, y.M, 1 if y.identity else y.T
             t.J, t.P, t.F = geo
         tp = C.cast(table, C.c_void_p)
-        host = SimpleNamespace(_rated=True, jring=sentinel(S, J), _table=table, _fades=[f.cpu() for f in fades], S=S, ring_len=R,
+        host = SimpleNamespace(_rated=True, _mixed=True, jring=sentinel(S, J), _table=table, _fades=[f.cpu() for f in fades], S=S, ring_len=R,
                                _rate_of=np.ones(S, dtype=np.int64), conceal="repeat")
         ref = NumpyDevice(host)  # (its ring is host.jring's memory)
         jr = host.jring.clone().cuda()

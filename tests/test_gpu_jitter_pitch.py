@@ -3,8 +3,8 @@ _rates forms).  Every comparison is exact.  The estimate kernel alone against ``
 noise, silence, an exact tie of scores, a history across the ring's wrap and one that begins in the zeros before the origin,
 NaN / inf / out-of-range samples, rows that must write nothing); the synthesis kernel alone against its numpy statement (d
 ranges across the hold, the fade's end and the ring's wrap, periods at both ends of the lags and a prime between, a stored
-period outside the lags read as P0).  Then the played-out stream: the numpy reference of tests/test_gpu_jitter.py with the new
-rule (``Ref``), under a network that loses, duplicates and shuffles packets, with two gaps closer than the search history in
+period outside the lags read as P0).  Then the played-out stream: the numpy reference (oracle/jitter.py's ``RefSlot``
+at "pitch_sync"), under a network that loses, duplicates and shuffles packets, with two gaps closer than the search history in
 one release, a gap longer than hold + fade, a gap released over three calls and a jump beyond the ring; a mixed-rate scorer
 against the one-rate scorers; comfort noise after a mark; a session moved mid-gap through host memory; and one real model."""
 import ctypes as C
@@ -14,46 +14,21 @@ import numpy as np
 import pytest
 import torch
 
+from oracle.jitter import RefSlot, Schedule as _Schedule, coded as _stream, voiced, voiced_stream
+from packet_helpers import offline as _offline, tap as _tap
+
 pytestmark = pytest.mark.gpu
 
 H = 4000
-BPS = {"pcm_f32le": 4, "pcm_s16le": 2, "mulaw": 1}
 SENTINEL = np.float32(-7.25)
 
 
-def _mulaw_table():
-    t = []
-    for c in range(256):
-        u = ~c & 0xFF
-        v = ((((u & 15) << 3) + 132) << ((u >> 4) & 7)) - 132
-        t.append(-v if u & 0x80 else v)
-    return np.array(t, dtype=np.float32)
+def Schedule(rate, encoding, seed, f0=None, **kw):
+    return _Schedule(rate, encoding, seed, short=rate // 200, payload=voiced_stream(f0), **kw)  # 5 ms between two lost packets
 
 
-MULAW = _mulaw_table()
-
-
-def voiced(rate, f0, n, seed, t0=0):
-    """The issue's test signal: seven harmonics of f0 and a little noise, fp32."""
-    t = (t0 + np.arange(n)) / rate
-    x = 0.1 * sum(np.sin(2 * np.pi * f0 * k * t + k) / k for k in range(1, 8))
-    return (x + 0.003 * np.random.default_rng(seed).standard_normal(n)).astype(np.float32)
-
-
-def _stream(encoding, n, seed, f0=None, rate=8000):
-    """n samples as ``encoding`` (noise, or the voiced signal at f0) -> (the bytes, their host-decoded fp32 values)."""
-    g = np.random.default_rng(seed)
-    x = (0.1 * g.standard_normal(n)).astype(np.float32) if f0 is None else voiced(rate, f0, n, seed)
-    if encoding == "pcm_f32le":
-        return x.astype("<f4").tobytes(), x
-    if encoding == "pcm_s16le":
-        v = np.clip(np.rint(x * 32768.0), -32768, 32767).astype("<i2")
-        return v.tobytes(), v.astype(np.float32) / np.float32(32768)
-    order = np.argsort(MULAW, kind="stable")  # the nearest mu-law code of every sample
-    levels = MULAW[order]
-    k = np.clip(np.searchsorted(levels, x * 32768.0), 1, 255)
-    c = order[np.where(np.abs(levels[k] - x * 32768.0) < np.abs(levels[k - 1] - x * 32768.0), k, k - 1)].astype(np.uint8)
-    return c.tobytes(), MULAW[c] / np.float32(32768)
+def Ref(rate, depth, cn=None):
+    return RefSlot(depth, "pitch_sync", rate=rate, noise=cn)
 
 
 def bits(t):
@@ -165,153 +140,6 @@ def test_the_synthesis_kernel_repeats_the_stored_period_under_hold_and_fade(rate
     assert torch.equal(bits(b.cpu()), bits(torch.from_numpy(want)))
 
 
-# ---- the reference: one slot's played-out stream (tests/test_gpu_jitter.py's, with the new rule) -----------------------------------
-class Ref:
-    def __init__(self, rate, depth, cap, cn=None):
-        from afx.jitter import gain_table
-        self.rate, self.depth, self.cn = rate, depth, cn
-        self.Pmin, self.Pmax, self.Wc, self.P0, self.Hd, self.F = _params(rate)
-        self.G, self.Lh, self.gain = self.Hd + self.F, self.Pmax + self.Wc, gain_table(self.Hd, self.F)
-        self.val, self.have, self.E = np.zeros(cap, np.float32), np.zeros(cap, bool), np.zeros(cap, np.float32)
-        self.next = self.hi = 0
-        self.gap = self.p = None  # the origin of the gap the playout point stands in, and its period
-        self.level, self.marks = None, {}  # comfort noise: the level in force for that gap; {index: level}
-        self.late = self.dup = self.received = self.concealed = self.comfort = 0
-        self.releases, self.spans, self.calls, self.periods = [], [], [], []  # per release its gaps; every gap [origin, end), the
-        # releases that wrote it and its period
-
-    def packet(self, t, x):
-        n = len(x)
-        lo = min(max(t, self.next), t + n)
-        self.late += lo - t
-        if lo < t + n:
-            new = ~self.have[lo:t + n]
-            self.val[lo:t + n][new] = x[lo - t:][new]
-            self.have[lo:t + n] = True
-            self.dup += int((~new).sum())
-            self.received += int(new.sum())
-            self.hi = max(self.hi, t + n)
-
-    def release(self, upto):
-        from afx.jitter import pitch_reference
-        i, gaps = self.next, []
-        while i < upto:
-            run = self.have[i:upto]
-            flips = np.flatnonzero(run != run[0])
-            j = i + int(flips[0]) if flips.size else upto
-            if run[0]:
-                self.E[i:j], self.gap, self.level = self.val[i:j], None, None
-            else:
-                if self.gap is None:
-                    self.gap, self.p = i, pitch_reference(self.E[max(0, i - self.Lh):i], self.rate)
-                    self.spans.append([i, i])
-                    self.calls.append(0)
-                    self.periods.append(self.p)
-                a, p = self.gap, self.p
-                for k in range(i, j):  # (per sample: a mark may change what governs it)
-                    self.level = self.marks.get(k, self.level)
-                    if self.level is not None:
-                        self.E[k] = self.cn.samples(k, 1, self.level)[0]
-                        self.comfort += 1
-                        continue
-                    d = k - a
-                    src = a - p + d % p
-                    self.E[k] = self.gain[d] * (self.E[src] if src >= 0 else np.float32(0)) if d < self.G else np.float32(0)
-                    self.concealed += 1
-                gaps.append((i, j))
-                self.spans[-1][1] = j
-                self.calls[-1] += 1
-            i = j
-        if upto > self.next:
-            self.releases.append(gaps)
-            self.next = upto
-        self.hi = max(self.hi, self.next)
-
-    def after_feed(self):
-        self.release(max(self.next, self.hi - self.depth))
-
-
-class Schedule:
-    """One slot's traffic: 20-ms packets (one short one), a forward jump, losses, duplicates and shuffles within the depth,
-    grouped into ticks (the packets one ``feed`` delivers).  ``f0``: the voiced signal instead of noise."""
-
-    def __init__(self, rate, encoding, seed, jump=0, n_pk=72, origin=None, depth_pk=3, f0=None):
-        rng = random.Random(seed)
-        n = rate // 50
-        sizes = [n] * n_pk
-        sizes[11] = rate // 200  # 5 ms between two lost packets: two gaps closer than the search history
-        offs = np.concatenate([[0], np.cumsum(sizes)]).tolist()
-        self.raw, self.x = _stream(encoding, offs[-1], seed, f0, rate)
-        bps = BPS[encoding]
-        self.origin = rng.randrange(1 << 32) if origin is None else origin
-        self.start = [offs[k] + (jump if k >= 44 else 0) for k in range(n_pk)]  # packet 44 begins `jump` samples late
-        self.size, self.cap = sizes, offs[-1] + jump + 8
-        self.pk = [(self.raw[offs[k] * bps:offs[k + 1] * bps], self.x[offs[k]:offs[k + 1]]) for k in range(n_pk)]
-        forced = {10, 12, 25, 26, 27, 28}  # 25..28: 80 ms > hold + fade, released by three feeds of one packet each
-        calm = set(range(6, 34))  # delivered in order around the forced gaps
-        self.lost = set(forced)
-        ticks, k = [], 0
-        while k < n_pk:
-            if k == 11:  # the short packet and four more in one feed: both gaps fall in its release
-                ticks.append([11, 13, 14, 15, 16])
-                k = 17
-                continue
-            if k in calm:
-                if k not in forced:
-                    ticks.append([k])
-                k += 1
-                continue
-            blk = [q for q in range(k, min(k + depth_pk, n_pk)) if q not in calm]
-            k = blk[-1] + 1
-            for q in list(blk):
-                if q and rng.random() < 0.05:
-                    blk.remove(q)
-                    self.lost.add(q)
-            blk += [q for q in blk if rng.random() < 0.15]  # duplicates
-            rng.shuffle(blk)  # within depth_pk packets = the depth: every packet is on time
-            if 0 in blk:  # the first packet accepted is the session's origin: index 0 here
-                blk.remove(0)
-                blk.insert(0, 0)
-            while blk:
-                m = rng.randint(1, 3)
-                ticks.append(blk[:m])
-                blk = blk[m:]
-        self.ticks, self.at = ticks, 0
-
-    def done(self):
-        return self.at >= len(self.ticks)
-
-    def tick(self):
-        """-> [(timestamp, relative index, bytes, decoded)] of the next tick."""
-        ks = self.ticks[self.at]
-        self.at += 1
-        return [((self.origin + self.start[k]) % (1 << 32), self.start[k], self.pk[k][0], self.pk[k][1]) for k in ks]
-
-
-def _tap(S):
-    from afx.streaming import SlidingWindowScorer
-
-    class Tap(SlidingWindowScorer):
-        def __init__(self):
-            super().__init__(None, S, window=4 * H, hop=H, device="cuda")
-            self.got = [[] for _ in range(S)]
-
-        def push(self, chunk, slots=None):
-            idx = self._slot_list(slots, ordered=True)
-            assert chunk.is_cuda and chunk.dtype == torch.float32 and chunk.shape == (len(idx), H)
-            for i, s in enumerate(idx):
-                self.got[s].append(chunk[i].clone())
-            self._seen[idx] += H
-            return torch.zeros(len(idx), device=chunk.device)
-
-    return Tap()
-
-
-def _offline(E, rate):
-    from afx.resample import Resampler
-    return Resampler(rate)(torch.from_numpy(np.ascontiguousarray(E)).cuda()[None])[0]
-
-
 def _rows(ticks, rng):
     """The rows of one feed from {slot: its tick}: the slots' rows interleaved, each slot's own in their order of arrival
     -> (rows of (slot, timestamp, index, bytes, decoded), the slots in the order first named)."""
@@ -337,14 +165,14 @@ def test_played_out_stream_is_the_offline_resampling_of_the_numpy_stream(rate, e
     rng = random.Random(seed)
     sch = [Schedule(rate, encoding, seed + 1000 * s, jump=js.J + 123 + s, origin=(1 << 32) - 3000 if s == 0 else None,
                     f0=(None, 125, None)[s]) for s in range(S)]
-    refs = [Ref(rate, depth, sc.cap) for sc in sch]
+    refs = [Ref(rate, depth) for sc in sch]
     hops = [0] * S
     while not all(sc.done() for sc in sch):
         ticks = {s: sch[s].tick() for s in range(S) if not sch[s].done() and rng.random() < 0.8}
         if not ticks:
             continue
         rows, named = _rows(ticks, rng)
-        for s, ts, t, raw, x in rows:
+        for s, ts, t, raw, x, e in rows:
             refs[s].packet(t, x)
         for s in named:
             refs[s].after_feed()
@@ -365,18 +193,18 @@ def test_played_out_stream_is_the_offline_resampling_of_the_numpy_stream(rate, e
         r.release(r.hi)
         assert int(js.samples_in[s]) == r.next == r.hi and int(js.buffered[s]) == 0
         assert (int(st["received"][s]), int(st["late"][s]), int(st["duplicate"][s]), int(st["concealed"][s])) == \
-            (r.received, r.late, r.dup, r.concealed)
+            tuple(r.stats[k] for k in ("received", "late", "duplicate", "concealed"))
         # the traffic was what the issue asks for: two gaps closer than Lh in one release, a gap beyond hold + fade, a gap
         # released by at least three calls, a jump beyond J
         assert any(len(g) >= 2 and any(b[0] - a[1] < Lh for a, b in zip(g, g[1:])) for g in r.releases)
         lens = [e - a for a, e in r.spans]
-        assert max(lens) > js.J and sum(1 for n in lens if G + Pmax < n < js.J) >= 1 and r.dup > 0 and len(sch[s].lost) >= 6
+        assert max(lens) > js.J and sum(1 for n in lens if G + Pmax < n < js.J) >= 1 and r.stats["duplicate"] > 0 and len(sch[s].lost) >= 6
         assert max(c for c, n in zip(r.calls, lens) if n < js.J) >= 3
-        E = r.E[:r.next]
+        E = np.array(r.E, dtype=np.float32)
         a, e = next((a, e) for a, e in r.spans if a >= 10 * (rate // 50))  # concealed samples are there, and they are not zeros
         assert np.count_nonzero(E[a:min(e, a + G)]) > 0.8 * min(e - a, G) - 1
         if s == 1:  # the voiced slot, after Lh received samples: the search found the pitch (a multiple of rate / 125)
-            found = [p for p, (a, _) in zip(r.periods, r.spans) if a > Lh and r.have[a - Lh:a].all()]
+            found = [p for p, (a, _) in zip(r.periods, r.spans) if a > Lh and set(r.kinds[a - Lh:a]) == {"r"}]
             assert found and all(abs(p / (rate / 125) - round(p / (rate / 125))) * (rate / 125) <= 1 for p in found)
         whole = _offline(E, rate)
         n_h = whole.numel() // H
@@ -431,23 +259,23 @@ def test_a_gap_with_a_mark_is_concealed_by_the_new_rule_before_it_and_noise_afte
     tap = _tap(S)
     js = JitterScorer(tap, rate, "pcm_f32le", 3 * n, conceal="pitch_sync", comfort_noise=cn)
     x = voiced(rate, 180, 60 * n, 3)
-    ref = Ref(rate, 3 * n, 60 * n + 8, cn)
+    ref = Ref(rate, 3 * n, cn)
     mark = 11 * n + 7
-    ref.marks[mark] = 40
     lost = {10, 11, 12, 13, 30, 31}
     for k in range(60):
         if k in lost:
             continue
         if k == 14:
             js.silence([1], [mark], [40])
+            ref.mark(mark, 40)
         js.feed([x[k * n:(k + 1) * n].tobytes()], [1], [k * n])
         ref.packet(k * n, x[k * n:(k + 1) * n])
         ref.after_feed()
     js.flush([1])
     ref.release(ref.hi)
     st = js.stats()
-    assert (int(st["concealed"][1]), int(st["comfort"][1])) == (ref.concealed, ref.comfort) == (n + 7 + 2 * n, 3 * n - 7)
-    E = ref.E[:ref.next]
+    assert (int(st["concealed"][1]), int(st["comfort"][1])) == (ref.stats["concealed"], ref.stats["comfort"]) == (n + 7 + 2 * n, 3 * n - 7)
+    E = np.array(ref.E, dtype=np.float32)
     assert ref.periods[0] != ref.P0 and np.count_nonzero(E[10 * n:mark]) > n  # the loss part: the voiced period, repeated
     assert np.array_equal(E[mark:14 * n], cn.samples(mark, 14 * n - mark, 40))
     got = torch.cat(tap.got[1])
@@ -462,7 +290,7 @@ def test_a_session_moved_mid_gap_through_host_memory_continues_bit_for_bit():
     ta, tb, tc = _tap(2), _tap(2), _tap(3)
     A, B, Cc = (JitterScorer(t, rate, "mulaw", depth, conceal="pitch_sync") for t in (ta, tb, tc))
     raw, x = _stream("mulaw", 70 * n, 21, f0=97, rate=rate)
-    ref = Ref(rate, depth, 70 * n + 8)
+    ref = Ref(rate, depth)
     lost = {20, 21, 22, 23, 40}
     moved = None
     for k in range(70):
@@ -492,7 +320,7 @@ def test_a_session_moved_mid_gap_through_host_memory_continues_bit_for_bit():
     A.flush([1])
     Cc.flush([0])
     ref.release(ref.hi)
-    whole = _offline(ref.E[:ref.next], rate)
+    whole = _offline(ref.E, rate)
     got = torch.cat(ta.got[1])
     assert moved is not None and len(tc.got[0]) >= 3 and torch.equal(bits(got), bits(whole[:got.numel()]))
     assert torch.equal(bits(torch.cat(tb.got[1][:moved] + tc.got[0])), bits(got))
@@ -513,14 +341,14 @@ def test_the_student_scores_the_offline_resampling_of_the_played_out_stream():
     inner = KVCachedScorer(eng, sd, S, window=64000, hop=H)
     rng = random.Random(3)
     sch = [Schedule(rate, "mulaw", 900 + s, jump=js.J + 40, f0=(125, None)[s]) for s in range(S)]
-    refs = [Ref(rate, js.depth, sc.cap) for sc in sch]
+    refs = [Ref(rate, js.depth) for sc in sch]
     scores = [[] for _ in range(S)]
     while not all(sc.done() for sc in sch):
         ticks = {s: sch[s].tick() for s in range(S) if not sch[s].done() and rng.random() < 0.8}
         if not ticks:
             continue
         rows, named = _rows(ticks, rng)
-        for s, ts, t, raw, x in rows:
+        for s, ts, t, raw, x, e in rows:
             refs[s].packet(t, x)
         res = js.feed([r[3] for r in rows], [r[0] for r in rows], [r[1] for r in rows])
         for r, part in zip(rows, res.split()):
@@ -533,8 +361,8 @@ def test_the_student_scores_the_offline_resampling_of_the_played_out_stream():
         scores[s].append(part)
     for s in range(S):
         refs[s].release(refs[s].hi)
-        whole = _offline(refs[s].E[:refs[s].next], rate)
+        whole = _offline(refs[s].E, rate)
         want = torch.cat([inner.push(whole[j * H:(j + 1) * H][None].contiguous(), [s]) for j in range(whole.numel() // H)])
         got = torch.cat(scores[s])
         assert got.numel() == want.numel() >= 5 and torch.equal(bits(got), bits(want)), s
-        assert refs[s].concealed > 0 and int(js.stats()["concealed"][s]) == refs[s].concealed
+        assert refs[s].stats["concealed"] > 0 and int(js.stats()["concealed"][s]) == refs[s].stats["concealed"]
