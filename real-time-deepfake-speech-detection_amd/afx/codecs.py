@@ -2,7 +2,7 @@
 
 ``afx.ingest.ENCODINGS`` are the four encodings every kernel of the fronts indexes by sample.  The codecs here cannot be read
 that way -- DVI4 is a recurrence within a packet, the network-order PCM payloads of RFC 3551 need their bytes put together --
-so a front expands them first: ``afx_k_payload_expand`` (csrc/afx_frontend.hip) writes each packet's samples as fp32 into a
+so a front expands them first: ``afx_k_payload_expand`` (csrc/afx_packets.hip) writes each packet's samples as fp32 into a
 zone of the call's device buffer, and everything downstream reads them there as ``pcm_f32le``.  This module is the statement
 the kernel is bit-exact to; every decode is exact in fp32.
 

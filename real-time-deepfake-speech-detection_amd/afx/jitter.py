@@ -28,7 +28,7 @@ So with no loss and every packet arriving before the playout point passes its st
 are an in-order lossless ``PacketScorer``'s whatever the permutation, the cuts and the duplicates; and ``depth = 0`` with
 in-order input is ``PacketScorer``, call by call.
 
-Device side (csrc/afx_frontend.hip): one decoded reorder ring per slot, (S, J) fp32, index i at column i mod J.
+Device side (csrc/afx_packets.hip): one decoded reorder ring per slot, (S, J) fp32, index i at column i mod J.
 ``afx_k_jitter_place`` decodes all placed sub-ranges of a feed in one launch, ``afx_k_jitter_conceal`` writes released gaps
 into the ring (one launch per rank of gap within a slot, so a gap whose source overlaps an earlier gap reads concealed
 data), ``afx_k_jitter_release`` resamples released samples from the ring into the pending 16 kHz ring with the offline

@@ -1,4 +1,5 @@
-// libafx engine: weight store + forward orchestration + the C ABI of include/afx.h.
+// libafx engine: weight store + forward orchestration + the C ABI of include/afx.h
+// (but for the streaming kernels' entry points, defined beside their kernels).
 // Host code (C++) over the HIP runtime; the only device code here is a few one-off
 // weight-preparation kernels.  The forward is a fixed sequence of asynchronous kernel
 // launches on the caller's stream: no allocation, no synchronisation, no host<->device
@@ -19,6 +20,7 @@
 #include "afx_common.h"
 #include "afx_kernels.h"
 #include "afx_aasist.h"
+#include "afx_entry.h"
 
 using namespace afx;
 
@@ -26,7 +28,7 @@ using namespace afx;
 // errors
 // ---------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
-static int fail(const char* fmt, ...) {
+int afx::fail(const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof g_err, fmt, ap);
@@ -2562,12 +2564,6 @@ extern "C" size_t afx_head_workspace_bytes(afx_handle h, int B, int T) {
 // ---------------------------------------------------------------------------------
 // single-kernel entry points
 // ---------------------------------------------------------------------------------
-#define KRET(expr)                       \
-  do {                                   \
-    const char* m_ = (expr);             \
-    return m_ ? fail("%s", m_) : 0;      \
-  } while (0)
-
 extern "C" int afx_k_gemm(int dtype, const void* A, long lda, const void* W, long ldw, int M, int N, int K,
                           const float* bias, int act, float alpha, const float* resid, long ldr, float* out_f,
                           long ldo_f, void* out_h, long ldo_h, void* stream) {
@@ -2809,170 +2805,6 @@ extern "C" int afx_k_tile_crop(const float* x, const long long* offs, const long
                                float* out, void* stream) {
   if (!x || !offs || !out) return fail("afx_k_tile_crop: null argument");
   KRET(launch_tile_crop(x, offs, starts, B, duration, out, (hipStream_t)stream));
-}
-extern "C" int afx_k_resample(const float* x, const long long* in_offs, const long long* out_offs, int B,
-                              long long max_out, const float* taps, int L, int M, int T, float* out, void* stream) {
-  KRET(launch_resample(x, in_offs, out_offs, B, max_out, taps, L, M, T, out, (hipStream_t)stream));
-}
-extern "C" int afx_k_resample_stream(const float* x, int A, int n_in, float* hist, const int* slot, const float* taps,
-                                     int L, int M, int T, float* out, void* stream) {
-  KRET(launch_resample_stream(x, A, n_in, hist, slot, taps, L, M, T, out, (hipStream_t)stream));
-}
-extern "C" int afx_k_ingest(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_out, int encoding,
-                            const float* taps, int L, int M, int T, float* hist, float* ring, int S, int ring_len,
-                            void* stream) {
-  KRET(launch_ingest(stage, stage_bytes, hdr, rows, max_out, encoding, taps, L, M, T, hist, ring, S, ring_len,
-                     (hipStream_t)stream));
-}
-extern "C" int afx_k_ingest_mixed(const void* stage, long long stage_bytes, const int* hdr, int rows,
-                                  const afx_ingest_format* formats, int n_formats, const int* max_out, float* hist, int Hs,
-                                  float* ring, int S, int ring_len, void* stream) {
-  static_assert(sizeof(afx_ingest_format) == sizeof(IngestFormatDesc), "afx_ingest_format is IngestFormatDesc");
-  KRET(launch_ingest_mixed(stage, stage_bytes, hdr, rows, (const IngestFormatDesc*)formats, n_formats, max_out, hist, Hs, ring, S,
-                           ring_len, (hipStream_t)stream));
-}
-extern "C" int afx_k_ingest_pop(const float* ring, int S, int ring_len, const int* table, int A, int hop, float* out,
-                                void* stream) {
-  KRET(launch_ingest_pop(ring, S, ring_len, table, A, hop, out, (hipStream_t)stream));
-}
-extern "C" int afx_k_payload_expand(void* stage, long long stage_bytes, const int* hdr, int rows, int max_n, void* stream) {
-  KRET(launch_payload_expand(stage, stage_bytes, hdr, rows, max_n, (hipStream_t)stream));
-}
-extern "C" int afx_k_jitter_place(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n, int encoding,
-                                  float* jring, int S, int J, void* stream) {
-  KRET(launch_jitter_place(stage, stage_bytes, hdr, rows, max_n, encoding, jring, S, J, (hipStream_t)stream));
-}
-extern "C" int afx_k_jitter_place_mixed(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n,
-                                        float* jring, int S, int J, void* stream) {
-  KRET(launch_jitter_place_mixed(stage, stage_bytes, hdr, rows, max_n, jring, S, J, (hipStream_t)stream));
-}
-extern "C" int afx_k_jitter_conceal(float* jring, int S, int J, const int* hdr, int rows, int max_n, const float* fade, int P,
-                                    int F, int mode, void* stream) {
-  KRET(launch_jitter_conceal(jring, S, J, hdr, rows, max_n, fade, P, F, mode, (hipStream_t)stream));
-}
-extern "C" int afx_k_jitter_release(const float* jring, int S, int J, const int* hdr, int rows, int max_out, const float* taps,
-                                    int L, int M, int T, float* ring, int ring_len, void* stream) {
-  KRET(launch_jitter_release(jring, S, J, hdr, rows, max_out, taps, L, M, T, ring, ring_len, (hipStream_t)stream));
-}
-extern "C" int afx_k_jitter_place_rates(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n,
-                                        const afx_jitter_rate* rates, int n_rates, float* jring, int S, int Js, void* stream) {
-  static_assert(sizeof(afx_jitter_rate) == sizeof(JitterRateDesc), "afx_jitter_rate is JitterRateDesc");
-  KRET(launch_jitter_place_rates(stage, stage_bytes, hdr, rows, max_n, (const JitterRateDesc*)rates, n_rates, jring, S, Js,
-                                 (hipStream_t)stream));
-}
-extern "C" int afx_k_jitter_conceal_rates(float* jring, int S, int Js, const int* hdr, int rows, int max_n,
-                                          const afx_jitter_rate* rates, int n_rates, int mode, void* stream) {
-  KRET(launch_jitter_conceal_rates(jring, S, Js, hdr, rows, max_n, (const JitterRateDesc*)rates, n_rates, mode, (hipStream_t)stream));
-}
-extern "C" int afx_k_jitter_release_rates(const float* jring, int S, int Js, const int* hdr, int rows, const afx_jitter_rate* rates,
-                                          int n_rates, const int* max_out, float* ring, int ring_len, void* stream) {
-  KRET(launch_jitter_release_rates(jring, S, Js, hdr, rows, (const JitterRateDesc*)rates, n_rates, max_out, ring, ring_len,
-                                   (hipStream_t)stream));
-}
-extern "C" int afx_k_jitter_noise(float* jring, int S, int J, const int* hdr, int rows, int max_n, unsigned seed, const float* amp,
-                                  void* stream) {
-  KRET(launch_jitter_noise(jring, S, J, hdr, rows, max_n, seed, amp, (hipStream_t)stream));
-}
-extern "C" int afx_k_jitter_noise_rates(float* jring, int S, int Js, const int* hdr, int rows, int max_n, const afx_jitter_rate* rates,
-                                        int n_rates, unsigned seed, const float* amp, void* stream) {
-  KRET(launch_jitter_noise_rates(jring, S, Js, hdr, rows, max_n, (const JitterRateDesc*)rates, n_rates, seed, amp, (hipStream_t)stream));
-}
-extern "C" int afx_k_jitter_pitch(const float* jring, int S, int J, const int* hdr, int rows, int Pmin, int Pmax, int Wc, int P0,
-                                  int* period, void* stream) {
-  KRET(launch_jitter_pitch(jring, S, J, hdr, rows, Pmin, Pmax, Wc, P0, period, (hipStream_t)stream));
-}
-extern "C" int afx_k_jitter_pitch_rates(const float* jring, int S, int Js, const int* hdr, int rows, const afx_jitter_rate* rates,
-                                        const afx_jitter_lags* lags, int n_rates, int* period, void* stream) {
-  static_assert(sizeof(afx_jitter_lags) == sizeof(JitterLagDesc), "afx_jitter_lags is JitterLagDesc");
-  KRET(launch_jitter_pitch_rates(jring, S, Js, hdr, rows, (const JitterRateDesc*)rates, (const JitterLagDesc*)lags, n_rates, period,
-                                 (hipStream_t)stream));
-}
-extern "C" int afx_k_jitter_conceal_period(float* jring, int S, int J, const int* hdr, int rows, int max_n, const float* gain,
-                                           const int* period, int Pmin, int Pmax, int P0, int Hd, int F, void* stream) {
-  KRET(launch_jitter_conceal_period(jring, S, J, hdr, rows, max_n, gain, period, Pmin, Pmax, P0, Hd, F, (hipStream_t)stream));
-}
-extern "C" int afx_k_jitter_conceal_period_rates(float* jring, int S, int Js, const int* hdr, int rows, int max_n,
-                                                 const afx_jitter_rate* rates, const afx_jitter_lags* lags, int n_rates,
-                                                 const int* period, void* stream) {
-  KRET(launch_jitter_conceal_period_rates(jring, S, Js, hdr, rows, max_n, (const JitterRateDesc*)rates, (const JitterLagDesc*)lags,
-                                          n_rates, period, (hipStream_t)stream));
-}
-extern "C" int afx_k_gate(const float* x, int A, int n, const int* hdr, int frame, float e_floor, float ratio, float rise,
-                          int hang, float* nf, int* h, float* ring, int S, int ring_len, int* kept, unsigned char* mask,
-                          void* stream) {
-  KRET(launch_gate(x, A, n, hdr, frame, e_floor, ratio, rise, hang, nf, h, ring, S, ring_len, kept, mask,
-                   (hipStream_t)stream));
-}
-extern "C" int afx_k_gate_la(const float* x, int A, int n, const int* hdr, int frame, float e_floor, float ratio, float rise,
-                             int hang, int pre, float* nf, int* h, int* flags, float* line, float* ring, int* src, int S,
-                             int ring_len, int* kept, unsigned char* mask, void* stream) {
-  KRET(launch_gate_la(x, A, n, hdr, frame, e_floor, ratio, rise, hang, pre, nf, h, flags, line, ring, src, S, ring_len, kept,
-                      mask, (hipStream_t)stream));
-}
-extern "C" int afx_k_gate_tone(const float* x, int A, int n, const int* hdr, int frame, float e_floor, float ratio, float rise,
-                               int hang, const float* coef, int K, float thr, int confirm, int hold, float* nf, int* h,
-                               int* tone_state, float* ring, int S, int ring_len, int* kept, int* ntone, unsigned char* mask,
-                               float* tsum, void* stream) {
-  KRET(launch_gate_tone(x, A, n, hdr, frame, e_floor, ratio, rise, hang, coef, K, thr, confirm, hold, nf, h, tone_state, ring,
-                        S, ring_len, kept, ntone, mask, tsum, (hipStream_t)stream));
-}
-extern "C" int afx_k_turn(const float* staging, int S, int ring_len, const unsigned char* mask, const int* hdr, int A, int F,
-                          int frame, int min_frames, int max_frames, float* bufs, int* state, int* totals, int* done,
-                          void* stream) {
-  KRET(launch_turn(staging, S, ring_len, mask, hdr, A, F, frame, min_frames, max_frames, bufs, state, totals, done,
-                   (hipStream_t)stream));
-}
-extern "C" int afx_k_turn_collect(const float* bufs, int S, int max_frames, int frame, const int* rows, int R, float* out,
-                                  void* stream) {
-  KRET(launch_turn_collect(bufs, S, max_frames, frame, rows, R, out, (hipStream_t)stream));
-}
-extern "C" int afx_k_turn_close(const int* slots, int A, int S, int min_frames, int max_frames, int* state, int* totals, int* done,
-                                void* stream) {
-  KRET(launch_turn_close(slots, A, S, min_frames, max_frames, state, totals, done, (hipStream_t)stream));
-}
-extern "C" int afx_k_turn_scan(const unsigned char* mask, const long long* offs, int A, int min_frames, int max_frames,
-                               int close_end, int* table, int cap, int* row_base, int* totals, int* open, void* stream) {
-  KRET(launch_turn_scan(mask, offs, A, min_frames, max_frames, close_end, table, cap, row_base, totals, open,
-                        (hipStream_t)stream));
-}
-extern "C" int afx_k_turn_clips(const float* x, const long long* xoffs, int A, int frame, int max_frames, const int* table, int r0,
-                                int R, float* out, void* stream) {
-  KRET(launch_turn_clips(x, xoffs, A, frame, max_frames, table, r0, R, out, (hipStream_t)stream));
-}
-extern "C" int afx_k_cascade_store(const float* x, int A, int hop, const int* hdr, float* hist, int S, int window,
-                                   void* stream) {
-  KRET(launch_cascade_store(x, A, hop, hdr, hist, S, window, (hipStream_t)stream));
-}
-extern "C" int afx_k_cascade_select(const float* scores, int stride, const int* hdr, int A, int* wait, int* counts, int S,
-                                    float threshold, int budget, int cooldown, int* sel, void* stream) {
-  KRET(launch_cascade_select(scores, stride, hdr, A, wait, counts, S, threshold, budget, cooldown, sel, (hipStream_t)stream));
-}
-extern "C" int afx_k_cascade_windows(const float* hist, int S, int window, const int* hdr, int A, const int* sel, int budget,
-                                     float* out, void* stream) {
-  KRET(launch_cascade_windows(hist, S, window, hdr, A, sel, budget, out, (hipStream_t)stream));
-}
-extern "C" int afx_k_verdict(const float* scores, int stride, const float* vscores, const int* hdr, int A, float* m, int* st,
-                             int S, float alpha, float enter, float exit_, float verifier_enter, int confirm, int release,
-                             int min_scores, int latch, int* log, int cap, void* stream) {
-  KRET(launch_verdict(scores, stride, vscores, hdr, A, m, st, S, alpha, enter, exit_, verifier_enter, confirm, release, min_scores,
-                      latch, log, cap, (hipStream_t)stream));
-}
-extern "C" int afx_k_evidence_mark(const int* hdr, int A, const int* vst, int S, int pre, int post, int* rec, int* left, int* claim,
-                                   int* pool, int clips, int* counters, int* work, void* stream) {
-  KRET(launch_evidence_mark(hdr, A, vst, S, pre, post, rec, left, claim, pool, clips, counters, work, (hipStream_t)stream));
-}
-extern "C" int afx_k_evidence_copy(const float* x, const float* scores, int stride, const int* hdr, const int* work, int A, int hop,
-                                   int pre, int post, float* hist, float* sring, int S, void* audio, float* cscores, int clips,
-                                   int encoding, void* stream) {
-  KRET(launch_evidence_copy(x, scores, stride, hdr, work, A, hop, pre, post, hist, sring, S, audio, cscores, clips, encoding,
-                            (hipStream_t)stream));
-}
-extern "C" int afx_k_quality(const float* x, long long stride, int A, int hop, const int* hdr, const float* scores, int sstride,
-                             float clip, int clip_count, int flat_run, float e_quiet, float dc, int mask, int max_bad,
-                             int abstain, unsigned char* ring, int W, int* state, int* totals, int S, int* meas, float* out,
-                             void* stream) {
-  KRET(launch_quality(x, stride, A, hop, hdr, scores, sstride, clip, clip_count, flat_run, e_quiet, dc, mask, max_bad, abstain, ring,
-                      W, state, totals, S, meas, out, (hipStream_t)stream));
 }
 extern "C" int afx_k_rownorm(int dtype, const float* x, long ldx, int rows, int C, const float* gamma,
                              const float* beta, float eps, int act, float* out_f, long ldo_f, void* out_h, long ldo_h,

@@ -1,6 +1,8 @@
-// Host-visible launchers of the gfx950 kernels (internal to libafx; the public
-// C ABI is include/afx.h).  Every launcher is asynchronous on the given stream,
+// Host-visible launchers of the gfx950 kernels the ENGINE launches (internal to libafx; the
+// public C ABI is include/afx.h).  Every launcher is asynchronous on the given stream,
 // allocates nothing, and returns nullptr on success or a static error string.
+// (The streaming kernels -- afx_packets / afx_gate / afx_layers.hip -- have no launcher here:
+// the engine never calls them, and each unit defines its afx_k_* entry points itself.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -162,138 +164,6 @@ size_t conv0_groupnorm_stats_floats(int B, int T0);
 // ragged batch (packed, offs[B+1]) -> (B, duration): out[b][i] = x_b[(start_b + i) mod n_b]; starts may be null
 const char* launch_tile_crop(const float* x, const long long* offs, const long long* starts, int B, int duration,
                              float* out, hipStream_t s);
-// polyphase resampling (include/afx.h afx_k_resample / afx_k_resample_stream): offline over packed clips with int64 input
-// and output offsets (max_out = the longest output row), or streamed rows with per-slot carried samples hist (S, T-1)
-const char* launch_resample(const float* x, const long long* in_offs, const long long* out_offs, int B, long long max_out,
-                            const float* taps, int L, int M, int T, float* out, hipStream_t s);
-const char* launch_resample_stream(const float* x, int A, int n_in, float* hist, const int* slot, const float* taps, int L,
-                                   int M, int T, float* out, hipStream_t s);
-// packet ingest (include/afx.h afx_k_ingest / afx_k_ingest_pop): encoded packets of any length -> decoded, resampled at
-// each slot's carried phase into its pending ring, history advanced; and the first hop of named slots' rings -> (A, hop)
-const char* launch_ingest(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_out, int enc,
-                          const float* taps, int L, int M, int T, float* hist, float* ring, int S, int ring_len,
-                          hipStream_t s);
-const char* launch_ingest_pop(const float* ring, int S, int ring_len, const int* table, int A, int hop, float* out,
-                              hipStream_t s);
-// payload expand (include/afx.h afx_k_payload_expand): the verb before ingest / place; rows of DVI4 / network-order PCM
-// payloads in stage -> their fp32 samples in another zone of stage (rows x 4 int32: source offset, source bytes, destination
-// offset, codec number)
-const char* launch_payload_expand(void* stage, long long stage_bytes, const int* hdr, int rows, int max_n, hipStream_t s);
-// the same ingest over rows of different formats (include/afx.h afx_k_ingest_mixed): formats / max_out are HOST arrays of
-// n_formats entries (IngestFormatDesc has the layout of afx_ingest_format), the row's format is the eighth int of its header,
-// hist is (S, Hs)
-struct IngestFormatDesc { const float* taps; int encoding, L, M, T; };
-const char* launch_ingest_mixed(const void* stage, long long stage_bytes, const int* hdr, int rows, const IngestFormatDesc* formats,
-                                int n_formats, const int* max_out, float* hist, int Hs, float* ring, int S, int ring_len,
-                                hipStream_t s);
-// jitter buffer (include/afx.h afx_k_jitter_place / _conceal / _release): packet sub-ranges decoded into each slot's reorder
-// ring at their timestamps' columns; released gaps concealed in the ring; released samples resampled into the pending ring.
-// One kernel per verb, which takes a table of rates; these four are its one-entry case (Js = J, rows without a rate index)
-const char* launch_jitter_place(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n, int enc,
-                                float* jring, int S, int J, hipStream_t s);
-// (place with the encoding read per row: rows x 5 int32, the fifth the row's encoding)
-const char* launch_jitter_place_mixed(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n, float* jring,
-                                      int S, int J, hipStream_t s);
-const char* launch_jitter_conceal(float* jring, int S, int J, const int* hdr, int rows, int max_n, const float* fade, int P,
-                                  int F, int mode, hipStream_t s);
-const char* launch_jitter_release(const float* jring, int S, int J, const int* hdr, int rows, int max_out, const float* taps,
-                                  int L, int M, int T, float* ring, int ring_len, hipStream_t s);
-// the same three kernels over slots of different clock rates (include/afx.h afx_k_jitter_place_rates / _conceal_rates /
-// _release_rates): rates / max_out are HOST arrays of n_rates entries (JitterRateDesc has the layout of afx_jitter_rate), a row's rate index is
-// the last int of its header (place: rows x 6, conceal: rows x 5, release: the eighth of 8), jring is (S, Js), Js >= every J
-struct JitterRateDesc { const float* taps; const float* fade; int L, M, T, J, P, F; };
-const char* launch_jitter_place_rates(const void* stage, long long stage_bytes, const int* hdr, int rows, int max_n,
-                                      const JitterRateDesc* rates, int n_rates, float* jring, int S, int Js, hipStream_t s);
-const char* launch_jitter_conceal_rates(float* jring, int S, int Js, const int* hdr, int rows, int max_n, const JitterRateDesc* rates,
-                                        int n_rates, int mode, hipStream_t s);
-const char* launch_jitter_release_rates(const float* jring, int S, int Js, const int* hdr, int rows, const JitterRateDesc* rates,
-                                        int n_rates, const int* max_out, float* ring, int ring_len, hipStream_t s);
-// comfort noise (include/afx.h afx_k_jitter_noise / _noise_rates): the noise parts of released gaps written into the ring; the
-// fourth verb, the same kernel shape as place (rows x 6 int32, or 7 with the rate index)
-const char* launch_jitter_noise(float* jring, int S, int J, const int* hdr, int rows, int max_n, unsigned seed, const float* amp,
-                                hipStream_t s);
-const char* launch_jitter_noise_rates(float* jring, int S, int Js, const int* hdr, int rows, int max_n, const JitterRateDesc* rates,
-                                      int n_rates, unsigned seed, const float* amp, hipStream_t s);
-// pitch-period concealment (include/afx.h afx_k_jitter_pitch / _conceal_period and their _rates forms): the estimate writes the
-// pitch period of each gap that opens (rows x 2 int32: slot, column of the gap origin [, rate index]) to period (S,) int32; the
-// synthesis is conceal with the row's period read from there.  lags: a HOST table parallel to rates (JitterLagDesc has the
-// layout of afx_jitter_lags); a rate's fade is then its gain table of Hd + F entries
-struct JitterLagDesc { int Pmin, Pmax, Wc, P0, Hd; };
-const char* launch_jitter_pitch(const float* jring, int S, int J, const int* hdr, int rows, int Pmin, int Pmax, int Wc, int P0,
-                                int* period, hipStream_t s);
-const char* launch_jitter_pitch_rates(const float* jring, int S, int Js, const int* hdr, int rows, const JitterRateDesc* rates,
-                                      const JitterLagDesc* lags, int n_rates, int* period, hipStream_t s);
-const char* launch_jitter_conceal_period(float* jring, int S, int J, const int* hdr, int rows, int max_n, const float* gain,
-                                         const int* period, int Pmin, int Pmax, int P0, int Hd, int F, hipStream_t s);
-const char* launch_jitter_conceal_period_rates(float* jring, int S, int Js, const int* hdr, int rows, int max_n,
-                                               const JitterRateDesc* rates, const JitterLagDesc* lags, int n_rates, const int* period,
-                                               hipStream_t s);
-// speech gate (include/afx.h afx_k_gate): per-slot energy gate with noise-floor tracking and hangover over the frames of each
-// row; the kept frames are compacted into the slot's pending ring, kept[i] = the samples kept of row i,
-// mask (optional) the keep flag of every frame
-const char* launch_gate(const float* x, int A, int n, const int* hdr, int frame, float e_floor, float ratio, float rise, int hang,
-                        float* nf, int* h, float* ring, int S, int ring_len, int* kept, unsigned char* mask, hipStream_t s);
-// look-ahead gate (include/afx.h afx_k_gate_la): the same decision behind a delay line of `pre` frames per slot (flags, line);
-// a frame is emitted, `pre` frames late, if it was kept or a speech frame followed within `pre`; src records the source
-// index of every emitted frame, mask (optional) keep' of the frames decided
-const char* launch_gate_la(const float* x, int A, int n, const int* hdr, int frame, float e_floor, float ratio, float rise,
-                           int hang, int pre, float* nf, int* h, int* flags, float* line, float* ring, int* src, int S,
-                           int ring_len, int* kept, unsigned char* mask, hipStream_t s);
-// tone gate (include/afx.h afx_k_gate_tone): the plain gate plus a Goertzel bank of K <= 16 frequencies (coef, device) per
-// frame; a confirmed tone (tone_state (S, 3): r, q, tones) is not speech, is not kept and ends the hangover; ntone, mask
-// (bit 0 keep, bit 1 tone, bit 2 tonal) and tsum are optional outputs
-const char* launch_gate_tone(const float* x, int A, int n, const int* hdr, int frame, float e_floor, float ratio, float rise,
-                             int hang, const float* coef, int K, float thr, int confirm, int hold, float* nf, int* h,
-                             int* tone_state, float* ring, int S, int ring_len, int* kept, int* ntone, unsigned char* mask,
-                             float* tsum, hipStream_t s);
-// talk spurts (include/afx.h afx_k_turn): behind a gate launch into a staging ring, each row's kept frames are appended to
-// the slot's open turn (bufs (S, 2, max_frames * frame); state (S, 3) = open, n, g; totals (S, 4)); done (A, 4) names the
-// turn a row completed: buffer, frames, first source frame, one past the last
-const char* launch_turn(const float* staging, int S, int ring_len, const unsigned char* mask, const int* hdr, int A, int F,
-                        int frame, int min_frames, int max_frames, float* bufs, int* state, int* totals, int* done,
-                        hipStream_t s);
-// the clips of completed turns (include/afx.h afx_k_turn_collect): out[r][k] = bufs[slot][buffer][k mod (frames * frame)],
-// rows (R, 3) = slot, buffer, frames
-const char* launch_turn_collect(const float* bufs, int S, int max_frames, int frame, const int* rows, int R, float* out,
-                                hipStream_t s);
-// the close step of the turn recurrence for A distinct slots (include/afx.h afx_k_turn_close): the end of a call
-const char* launch_turn_close(const int* slots, int A, int S, int min_frames, int max_frames, int* state, int* totals, int* done,
-                              hipStream_t s);
-// turns offline (include/afx.h afx_k_turn_scan): the recurrence over the whole masks of A recordings, packed back to back at
-// offs; table (cap, 4) = row, first, end, flags of the scored turns in order, row_base (A + 1) their exclusive prefix sums
-// per row, totals (A, 4), open (A, 2).  Three launches: count, prefix, write
-const char* launch_turn_scan(const unsigned char* mask, const long long* offs, int A, int min_frames, int max_frames,
-                             int close_end, int* table, int cap, int* row_base, int* totals, int* open, hipStream_t s);
-// the clips of table rows r0 .. r0 + R - 1, tiled from the packed recordings x at xoffs (include/afx.h afx_k_turn_clips)
-const char* launch_turn_clips(const float* x, const long long* xoffs, int A, int frame, int max_frames, const int* table, int r0,
-                              int R, float* out, hipStream_t s);
-// cascade (include/afx.h afx_k_cascade_store / _select / _windows): the named slots' hops into the retained-audio ring; the
-// candidates among the rows ranked by (score, slot), the first `budget` row positions into sel, the cooldown counters
-// advanced; the windows of the rows sel names gathered from the ring (sel is read on the device)
-const char* launch_cascade_store(const float* x, int A, int hop, const int* hdr, float* hist, int S, int window,
-                                 hipStream_t s);
-const char* launch_cascade_select(const float* scores, int stride, const int* hdr, int A, int* wait, int* counts, int S,
-                                  float threshold, int budget, int cooldown, int* sel, hipStream_t s);
-const char* launch_cascade_windows(const float* hist, int S, int window, const int* hdr, int A, const int* sel, int budget,
-                                   float* out, hipStream_t s);
-// verdicts (include/afx.h afx_k_verdict): the scores of one push smoothed per slot, the hysteresis state machine advanced, the
-// raise / clear events appended to the device log in row order; one workgroup, no atomics
-const char* launch_verdict(const float* scores, int stride, const float* vscores, const int* hdr, int A, float* m, int* st,
-                           int S, float alpha, float enter, float exit_, float verifier_enter, int confirm, int release,
-                           int min_scores, int latch, int* log, int cap, hipStream_t s);
-// evidence clips (include/afx.h afx_k_evidence_mark / _copy): mark decides, in one workgroup and in row order, which rows append
-// to a clip and which open one (rec, left, clip headers, counters, one work item per row); copy moves the samples and scores
-const char* launch_evidence_mark(const int* hdr, int A, const int* vst, int S, int pre, int post, int* rec, int* left, int* claim,
-                                 int* pool, int clips, int* counters, int* work, hipStream_t s);
-const char* launch_evidence_copy(const float* x, const float* scores, int stride, const int* hdr, const int* work, int A, int hop,
-                                 int pre, int post, float* hist, float* sring, int S, void* audio, float* cscores, int clips,
-                                 int encoding, hipStream_t s);
-// input quality (include/afx.h afx_k_quality): per row the hop's non-finite / clipped counts, peak, energy, sum and longest run
-// of identical samples, the five flags into the slot's ring, the flagged hops of the last W, the score passed on or made NaN;
-// one workgroup per row, no atomics
-const char* launch_quality(const float* x, long long stride, int A, int hop, const int* hdr, const float* scores, int sstride,
-                           float clip, int clip_count, int flat_run, float e_quiet, float dc, int mask, int max_bad, int abstain,
-                           unsigned char* ring, int W, int* state, int* totals, int S, int* meas, float* out, hipStream_t s);
 void conv0_set_mfma(int v);  // A/B knob: 1 (default) = matrix-core forms (split-precision fp16 when packed), 2 = fp32 MFMA form, 0 = VALU form
 // y[t] = x[t] - coef * x[t-1] with a reflect pad on the left; (B,L) fp32 -> (B,L) fp32
 const char* launch_pre_emphasis(const float* x, int B, int L, float coef, float* y, hipStream_t s);
