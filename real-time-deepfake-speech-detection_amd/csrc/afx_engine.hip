@@ -102,11 +102,42 @@ struct TapRec {
   size_t cap = 0, n = 0;
 };
 
+// The weight tables.  afx_create allocates the packed operands; resolve_weights (run by every afx_finalize) fills in every raw
+// fp32 tensor a launch reads, checked for presence and element count.  The launch paths read these fields and nothing else.
+struct LnW {  // a LayerNorm the engine launches
+  const float *g = nullptr, *b = nullptr;
+  // split precision: the scale its output takes as a pair-form operand, chosen at finalize (s3_layernorm_scales) from
+  // |y| <= sqrt(C) max|gamma| + max|beta|: the largest power of two <= kS3ScaleBounded that keeps the hi half inside fp16 -- a
+  // LayerNorm output cannot overflow whatever the checkpoint's gains are
+  float scale = kS3ScaleBounded;
+};
+struct ConvLayer {  // conv feature encoder, layer 0..6 (the packed weights of layers 1-6: afx_engine::convw)
+  const float* bias = nullptr;  // group-norm mode: null (bias-free convs)
+  LnW ln;                       // layer_norm mode
+  const float *w0 = nullptr, *gn_g = nullptr, *gn_b = nullptr;  // layer 0: fp32 weight; group-norm mode: GroupNorm(512,512)
+};
+struct TrunkLayer {
+  void *wqkv = nullptr, *wo = nullptr, *w1 = nullptr, *w2 = nullptr;  // packed operands
+  float* bqkv = nullptr;
+  LnW ln1, ln2;  // self_attn_layer_norm, final_layer_norm
+  const float *bo = nullptr, *b1 = nullptr, *b2 = nullptr;
+};
+struct ConfFF {
+  void *w1, *w2;
+  LnW ln;
+  const float *b1, *b2;
+};
 struct ConfBlock {
-  void *ff1_w1, *ff1_w2, *ff2_w1, *ff2_w2, *wqkv, *wout, *pw1, *pw2;
+  ConfFF ff[2];
+  void *wqkv, *wout, *pw1, *pw2;
   float *bn_scale, *bn_shift;
   void* rel_h;          // rel_pos_emb in operand type, rows padded to 64 (matrix-core attention)
   float* chain_prm[3];  // per fused chain: the per-column vectors packed into one 8-KB block (ConfChainArgs::params)
+  // what the per-op path and the fp32 VALU kernels read
+  LnW attn_ln, conv_ln, post_ln;
+  const float *bout, *bpw1, *bpw2;
+  const float* rel32;  // rel_pos_emb (1025, dh)
+  const float *dw_w, *dw_b;
 };
 
 struct Profiler;  // per-engine launch timing (below)
@@ -134,23 +165,22 @@ struct afx_engine {
   // overflow guard: device counters [0] rows of the trunk's final LayerNorm with non-finite statistics, [1] non-finite logits
   // (written by those kernels of every forward, read and cleared by afx_check_finite)
   int* nonfinite = nullptr;
-  // split precision: the scale each LayerNorm's output takes as a pair-form operand, keyed by the LayerNorm's gamma pointer and
-  // chosen at finalize from |y| <= sqrt(C) max|gamma| + max|beta|: the largest power of two <= kS3ScaleBounded that keeps the hi
-  // half inside fp16 -- a LayerNorm output cannot overflow whatever the checkpoint's gains are
-  std::unordered_map<const float*, float> ln_scale;
 
-  // trunk, packed operand-type weights
+  // trunk: packed operand-type weights, and the raw tensors resolve_weights found
   void* convw[7] = {nullptr};
   void* conv0pack = nullptr;  // layer 0 as the split-precision fp16 MFMA operand (layer_norm mode, half-precision engines)
   void* projw = nullptr;
   void* posw = nullptr;
   float* pos_norm = nullptr;
-  std::vector<void*> wqkv, wo, w1, w2;
-  std::vector<float*> bqkv;
+  ConvLayer conv[7];
+  LnW feat_ln, enc_ln;  // layer_norm, encoder.layer_norm
+  const float *proj_b = nullptr, *pos_b = nullptr;
+  std::vector<TrunkLayer> layers;
   // Conformer head
   int E = 0, Ep = 0, heads = 0, dh = 0, inner = 0, FF = 0, FFp = 0, C2 = 0, C2p = 0, ck = 0, nblk = 0;
   void* conf_ll = nullptr;
   float conf_bn_scale = 1.f, conf_bn_shift = 0.f;
+  const float *ll_b = nullptr, *class_token = nullptr, *fc5_w = nullptr, *fc5_b = nullptr;
   std::vector<ConfBlock> blk;
   // AASIST head
   AasistWeights aw;
@@ -217,11 +247,7 @@ extern "C" int afx_create(const afx_config* cfg, afx_handle* out) {
   e->hsz = dtype_size(e->dt);
   const int nl = head_only ? 0 : cfg->n_layers;
   e->cfg.n_layers = nl;
-  e->wqkv.assign(nl, nullptr);
-  e->wo.assign(nl, nullptr);
-  e->w1.assign(nl, nullptr);
-  e->w2.assign(nl, nullptr);
-  e->bqkv.assign(nl, nullptr);
+  e->layers.resize(nl);
   bool ok = true;
   ok &= (e->nonfinite = (int*)e->dalloc(16)) != nullptr && hipMemset(e->nonfinite, 0, 16) == hipSuccess;
   if (!head_only) {
@@ -231,11 +257,12 @@ extern "C" int afx_create(const afx_config* cfg, afx_handle* out) {
     ok &= (e->pos_norm = (float*)e->dalloc(kPosK * 4)) != nullptr;
   }
   for (int l = 0; l < nl && ok; ++l) {
-    ok &= (e->wqkv[l] = e->walloc(3 * kD, kD)) != nullptr;
-    ok &= (e->wo[l] = e->walloc(kD, kD)) != nullptr;
-    ok &= (e->w1[l] = e->walloc(kF, kD)) != nullptr;
-    ok &= (e->w2[l] = e->walloc(kD, kF)) != nullptr;
-    ok &= (e->bqkv[l] = (float*)e->dalloc((size_t)3 * kD * 4)) != nullptr;
+    TrunkLayer& t = e->layers[l];
+    ok &= (t.wqkv = e->walloc(3 * kD, kD)) != nullptr;
+    ok &= (t.wo = e->walloc(kD, kD)) != nullptr;
+    ok &= (t.w1 = e->walloc(kF, kD)) != nullptr;
+    ok &= (t.w2 = e->walloc(kD, kF)) != nullptr;
+    ok &= (t.bqkv = (float*)e->dalloc((size_t)3 * kD * 4)) != nullptr;
   }
   if (cfg->arch == AFX_ARCH_CONFORMER || head_only) {
     e->E = cfg->conf_emb;
@@ -258,10 +285,10 @@ extern "C" int afx_create(const afx_config* cfg, afx_handle* out) {
     e->blk.resize(e->nblk);
     for (int b = 0; b < e->nblk && ok; ++b) {
       ConfBlock& B = e->blk[b];
-      ok &= (B.ff1_w1 = e->walloc(e->FF, e->Ep)) != nullptr;
-      ok &= (B.ff1_w2 = e->walloc(e->E, e->FFp)) != nullptr;
-      ok &= (B.ff2_w1 = e->walloc(e->FF, e->Ep)) != nullptr;
-      ok &= (B.ff2_w2 = e->walloc(e->E, e->FFp)) != nullptr;
+      for (ConfFF& ff : B.ff) {
+        ok &= (ff.w1 = e->walloc(e->FF, e->Ep)) != nullptr;
+        ok &= (ff.w2 = e->walloc(e->E, e->FFp)) != nullptr;
+      }
       ok &= (B.wqkv = e->walloc(3 * e->inner, e->Ep)) != nullptr;
       ok &= (B.wout = e->walloc(e->E, e->Ep)) != nullptr;
       ok &= (B.pw1 = e->walloc(2 * e->C2, e->Ep)) != nullptr;
@@ -391,29 +418,29 @@ static int load_ssl(afx_engine* e, const std::string& k, const float* src, const
     for (int j = 0; j < 3; ++j) {
       if (t == std::string(proj[j]) + "weight") {
         if (expect_shape(k.c_str(), shape, ndim, {kD, kD})) return 1;
-        KOK(pack_linear(e, src, kD, kD, kD, (char*)e->wqkv[n] + (size_t)j * kD * kD * e->hsz,
-                        e->s3 ? e->wscale(e->wqkv[n], 3 * kD, kD) + j * kD : nullptr, s));
+        KOK(pack_linear(e, src, kD, kD, kD, (char*)e->layers[n].wqkv + (size_t)j * kD * kD * e->hsz,
+                        e->s3 ? e->wscale(e->layers[n].wqkv, 3 * kD, kD) + j * kD : nullptr, s));
         return 0;
       }
       if (t == std::string(proj[j]) + "bias") {
         if (expect_shape(k.c_str(), shape, ndim, {kD})) return 1;
-        HIP_OK(hipMemcpyAsync(e->bqkv[n] + j * kD, src, kD * 4, hipMemcpyDeviceToDevice, s));
+        HIP_OK(hipMemcpyAsync(e->layers[n].bqkv + j * kD, src, kD * 4, hipMemcpyDeviceToDevice, s));
         return 0;
       }
     }
     if (t == "self_attn.out_proj.weight") {
       if (expect_shape(k.c_str(), shape, ndim, {kD, kD})) return 1;
-      KOK(pack_linear(e, src, kD, kD, kD, e->wo[n], e->wscale(e->wo[n], kD, kD), s));
+      KOK(pack_linear(e, src, kD, kD, kD, e->layers[n].wo, e->wscale(e->layers[n].wo, kD, kD), s));
       return 0;
     }
     if (t == "fc1.weight") {
       if (expect_shape(k.c_str(), shape, ndim, {kF, kD})) return 1;
-      KOK(pack_linear(e, src, kF, kD, kD, e->w1[n], e->wscale(e->w1[n], kF, kD), s));
+      KOK(pack_linear(e, src, kF, kD, kD, e->layers[n].w1, e->wscale(e->layers[n].w1, kF, kD), s));
       return 0;
     }
     if (t == "fc2.weight") {
       if (expect_shape(k.c_str(), shape, ndim, {kD, kF})) return 1;
-      KOK(pack_linear(e, src, kD, kF, kF, e->w2[n], e->wscale(e->w2[n], kD, kF), s));
+      KOK(pack_linear(e, src, kD, kF, kF, e->layers[n].w2, e->wscale(e->layers[n].w2, kD, kF), s));
       return 0;
     }
     return store_raw(e, "ssl." + k, src, shape, ndim, s);
@@ -441,10 +468,10 @@ static int load_conformer(afx_engine* e, const std::string& k, const float* src,
     const std::string t = tail;
     float* qkv_sc = e->wscale(B.wqkv, 3 * e->inner, Ep);
     struct { const char* name; void* dst; int N, K, Kp; float* sc; } lin[] = {
-        {"ff1.fn.fn.net.0.weight", B.ff1_w1, e->FF, E, Ep, e->wscale(B.ff1_w1, e->FF, Ep)},
-        {"ff1.fn.fn.net.3.weight", B.ff1_w2, E, e->FF, e->FFp, e->wscale(B.ff1_w2, E, e->FFp)},
-        {"ff2.fn.fn.net.0.weight", B.ff2_w1, e->FF, E, Ep, e->wscale(B.ff2_w1, e->FF, Ep)},
-        {"ff2.fn.fn.net.3.weight", B.ff2_w2, E, e->FF, e->FFp, e->wscale(B.ff2_w2, E, e->FFp)},
+        {"ff1.fn.fn.net.0.weight", B.ff[0].w1, e->FF, E, Ep, e->wscale(B.ff[0].w1, e->FF, Ep)},
+        {"ff1.fn.fn.net.3.weight", B.ff[0].w2, E, e->FF, e->FFp, e->wscale(B.ff[0].w2, E, e->FFp)},
+        {"ff2.fn.fn.net.0.weight", B.ff[1].w1, e->FF, E, Ep, e->wscale(B.ff[1].w1, e->FF, Ep)},
+        {"ff2.fn.fn.net.3.weight", B.ff[1].w2, E, e->FF, e->FFp, e->wscale(B.ff[1].w2, E, e->FFp)},
         {"attn.fn.to_q.weight", B.wqkv, e->inner, E, Ep, qkv_sc},
         {"attn.fn.to_kv.weight", (char*)B.wqkv + (size_t)e->inner * Ep * e->hsz, 2 * e->inner, E, Ep, qkv_sc ? qkv_sc + e->inner : nullptr},
         {"attn.fn.to_out.weight", B.wout, E, e->inner, Ep, e->wscale(B.wout, E, Ep)},
@@ -485,8 +512,97 @@ extern "C" int afx_load_weight(afx_handle h, const char* name, const float* dev_
   return store_raw(h, k, dev_ptr, shape, ndim, s);
 }
 
-static int need(afx_engine* e, const std::string& k) {
-  if (!e->loaded.count(k)) return fail("afx_finalize: missing weight '%s'", k.c_str());
+// ---------------------------------------------------------------------------------
+// resolve_weights: THE list of the tensors the launch paths read.  Run by every afx_finalize (afx_load_weight may have replaced
+// any buffer since the last one), it checks each tensor for presence and for the element count the launches read, and stores
+// the pointer in the tables of afx_engine.  A tensor a launch is to read is declared here and nowhere else; a null field after
+// a successful finalize means "absent by mode" (set explicitly below), never a lookup that missed.
+// ---------------------------------------------------------------------------------
+struct LnRef { LnW* ln; int C; };
+struct Resolver {
+  afx_engine* e;
+  const char *ckpt, *key;  // the prefix of the checkpoint's own names (what errors quote), and the one `f` keeps them under
+  std::vector<LnRef>& lns;
+  int missing(const std::string& k) const { return fail("afx_finalize: missing weight '%s%s'", ckpt, k.c_str()); }
+  // a matrix packed into its operand form by afx_load_weight, which checked its shape
+  int packed(const std::string& k) const { return e->loaded.count(ckpt + k) ? 0 : missing(k); }
+  // a raw fp32 tensor of n elements (out null: only finalize itself reads it, by name)
+  int raw(const std::string& k, size_t n, const float** out = nullptr) const {
+    auto it = e->f.find(key + k);
+    if (it == e->f.end()) return missing(k);
+    if (it->second.n != n) return fail("afx_finalize: weight '%s%s' has %zu elements, expected %zu", ckpt, k.c_str(), it->second.n, n);
+    if (out) *out = it->second.p;
+    return 0;
+  }
+  int ln(const std::string& k, int C, LnW& w) const {
+    w = LnW();
+    if (raw(k + ".weight", C, &w.g) || raw(k + ".bias", C, &w.b)) return 1;
+    lns.push_back({&w, C});
+    return 0;
+  }
+};
+
+static int resolve_weights(afx_engine* e, std::vector<LnRef>& lns) {
+  const bool gn = e->cfg.extractor_mode == AFX_EXTRACTOR_GROUP_NORM;
+  const bool head_only = e->cfg.arch == AFX_ARCH_CONFORMER_HEAD;
+  if (!head_only) {
+    const Resolver r{e, "ssl_model.model.", "ssl.", lns};
+    for (int i = 0; i < 7; ++i) {
+      const std::string c = "feature_extractor.conv_layers." + std::to_string(i);
+      ConvLayer& L = e->conv[i] = ConvLayer();
+      if (i == 0 ? r.raw(c + ".0.weight", (size_t)kC * kConvK[0], &L.w0) : r.packed(c + ".0.weight")) return 1;
+      if (gn) {  // wav2vec2-base: bias-free convs, GroupNorm(512,512) on layer 0 only
+        if (i == 0 && (r.raw(c + ".2.weight", kC, &L.gn_g) || r.raw(c + ".2.bias", kC, &L.gn_b))) return 1;
+      } else if (r.raw(c + ".0.bias", kC, &L.bias) || r.ln(c + ".2.1", kC, L.ln)) {
+        return 1;
+      }
+    }
+    if (r.ln("layer_norm", kC, e->feat_ln) || r.packed("post_extract_proj.weight") || r.raw("post_extract_proj.bias", kD, &e->proj_b) ||
+        r.raw("encoder.pos_conv.0.bias", kD, &e->pos_b) || r.ln("encoder.layer_norm", kD, e->enc_ln))
+      return 1;
+    for (int l = 0; l < e->cfg.n_layers; ++l) {
+      const std::string P = "encoder.layers." + std::to_string(l) + ".";
+      TrunkLayer& L = e->layers[l];
+      for (const char* k : {"self_attn.q_proj.weight", "self_attn.q_proj.bias", "self_attn.k_proj.weight", "self_attn.k_proj.bias",
+                            "self_attn.v_proj.weight", "self_attn.v_proj.bias", "self_attn.out_proj.weight", "fc1.weight", "fc2.weight"})
+        if (r.packed(P + k)) return 1;
+      if (r.raw(P + "self_attn.out_proj.bias", kD, &L.bo) || r.ln(P + "self_attn_layer_norm", kD, L.ln1) ||
+          r.raw(P + "fc1.bias", kF, &L.b1) || r.raw(P + "fc2.bias", kD, &L.b2) || r.ln(P + "final_layer_norm", kD, L.ln2))
+        return 1;
+    }
+  }
+  if (e->cfg.arch == AFX_ARCH_CONFORMER || head_only) {
+    const Resolver r{e, "", "", lns};
+    const int E = e->E, C2 = e->C2;
+    e->ll_b = nullptr;  // head only: MyConformer starts from its tokens, no LL / first_bn in the handle
+    if (!head_only) {
+      if (r.packed("LL.weight") || r.raw("LL.bias", E, &e->ll_b)) return 1;
+      for (const char* k : {"first_bn.weight", "first_bn.bias", "first_bn.running_mean", "first_bn.running_var"})
+        if (r.raw(k, 1)) return 1;
+    }
+    if (r.raw("conformer.class_token", E, &e->class_token) || r.raw("conformer.fc5.weight", (size_t)2 * E, &e->fc5_w) ||
+        r.raw("conformer.fc5.bias", 2, &e->fc5_b))
+      return 1;
+    for (int b = 0; b < e->nblk; ++b) {
+      const std::string P = "conformer.encoder_blocks." + std::to_string(b) + ".";
+      ConfBlock& K = e->blk[b];
+      for (int i = 0; i < 2; ++i) {
+        const std::string ff = P + (i ? "ff2.fn." : "ff1.fn.");
+        if (r.ln(ff + "norm", E, K.ff[i].ln) || r.packed(ff + "fn.net.0.weight") || r.raw(ff + "fn.net.0.bias", e->FF, &K.ff[i].b1) ||
+            r.packed(ff + "fn.net.3.weight") || r.raw(ff + "fn.net.3.bias", E, &K.ff[i].b2))
+          return 1;
+      }
+      if (r.ln(P + "attn.norm", E, K.attn_ln) || r.packed(P + "attn.fn.to_q.weight") || r.packed(P + "attn.fn.to_kv.weight") ||
+          r.packed(P + "attn.fn.to_out.weight") || r.raw(P + "attn.fn.to_out.bias", E, &K.bout) ||
+          r.raw(P + "attn.fn.rel_pos_emb.weight", (size_t)1025 * e->dh, &K.rel32) || r.ln(P + "conv.net.0", E, K.conv_ln) ||
+          r.packed(P + "conv.net.2.weight") || r.raw(P + "conv.net.2.bias", (size_t)2 * C2, &K.bpw1) ||
+          r.raw(P + "conv.net.4.conv.weight", (size_t)C2 * e->ck, &K.dw_w) || r.raw(P + "conv.net.4.conv.bias", C2, &K.dw_b))
+        return 1;
+      for (const char* k : {"conv.net.5.weight", "conv.net.5.bias", "conv.net.5.running_mean", "conv.net.5.running_var"})
+        if (r.raw(P + k, C2)) return 1;  // (fold_bn)
+      if (r.packed(P + "conv.net.7.weight") || r.raw(P + "conv.net.7.bias", E, &K.bpw2) || r.ln(P + "post_norm", E, K.post_ln)) return 1;
+    }
+  }
   return 0;
 }
 
@@ -498,23 +614,14 @@ static int fold_bn(afx_engine* e, const std::string& p, int n, float* scale, flo
   return 0;
 }
 
-// split precision: one scale per LayerNorm (afx_engine::ln_scale) from the maxima of its gain and offset
-static int s3_layernorm_scales(afx_engine* h, hipStream_t s) {
-  h->ln_scale.clear();
-  if (!h->s3) return 0;
-  std::vector<std::pair<const FT*, const FT*>> lns;
-  for (const auto& kv : h->f) {
-    const std::string& k = kv.first;
-    if (kv.second.shape.size() != 1 || !ends_with(k, ".weight")) continue;
-    auto b = h->f.find(k.substr(0, k.size() - 6) + "bias");
-    if (b != h->f.end() && b->second.n == kv.second.n) lns.push_back({&kv.second, &b->second});
-  }
-  if (lns.empty()) return 0;
+// split precision: one scale per LayerNorm of the tables (LnW::scale) from the maxima of its gain and offset
+static int s3_layernorm_scales(afx_engine* h, const std::vector<LnRef>& lns, hipStream_t s) {
+  if (!h->s3 || lns.empty()) return 0;
   float* d = nullptr;
   HIP_OK(hipMalloc((void**)&d, lns.size() * 8));
   for (size_t i = 0; i < lns.size(); ++i) {
-    hipLaunchKernelGGL(absmax_kernel, dim3(1), dim3(256), 0, s, lns[i].first->p, (int)lns[i].first->n, d + 2 * i);
-    hipLaunchKernelGGL(absmax_kernel, dim3(1), dim3(256), 0, s, lns[i].second->p, (int)lns[i].second->n, d + 2 * i + 1);
+    hipLaunchKernelGGL(absmax_kernel, dim3(1), dim3(256), 0, s, lns[i].ln->g, lns[i].C, d + 2 * i);
+    hipLaunchKernelGGL(absmax_kernel, dim3(1), dim3(256), 0, s, lns[i].ln->b, lns[i].C, d + 2 * i + 1);
   }
   std::vector<float> m(2 * lns.size());
   hipError_t e = hipGetLastError();
@@ -523,10 +630,10 @@ static int s3_layernorm_scales(afx_engine* h, hipStream_t s) {
   (void)hipFree(d);
   if (e != hipSuccess) return fail("afx_finalize: %s", hipGetErrorString(e));
   for (size_t i = 0; i < lns.size(); ++i) {
-    const float bound = sqrtf((float)lns[i].first->n) * m[2 * i] + m[2 * i + 1];
+    const float bound = sqrtf((float)lns[i].C) * m[2 * i] + m[2 * i + 1];
     float sc = kS3ScaleBounded;
     while (sc * bound > 60000.f && sc > 1e-6f) sc *= 0.5f;  // (a non-finite gain stays non-finite: the overflow guard reports it)
-    h->ln_scale[lns[i].first->p] = sc;
+    lns[i].ln->scale = sc;
   }
   return 0;
 }
@@ -534,35 +641,14 @@ static int s3_layernorm_scales(afx_engine* h, hipStream_t s) {
 extern "C" int afx_finalize(afx_handle h, void* stream) {
   if (!h) return fail("afx_finalize: null handle");
   hipStream_t s = (hipStream_t)stream;
-  const std::string P = "ssl_model.model.";
   const bool gn = h->cfg.extractor_mode == AFX_EXTRACTOR_GROUP_NORM;
   const bool head_only = h->cfg.arch == AFX_ARCH_CONFORMER_HEAD;
+  std::vector<LnRef> lns;  // the LayerNorms of the tables
+  if (resolve_weights(h, lns)) return 1;
   if (!head_only) {
-    for (int i = 0; i < 7; ++i) {
-      const std::string c = P + "feature_extractor.conv_layers." + std::to_string(i);
-      if (need(h, c + ".0.weight")) return 1;
-      if (gn) {  // wav2vec2-base: bias-free convs, GroupNorm(512,512) on layer 0 only
-        if (i == 0 && (need(h, c + ".2.weight") || need(h, c + ".2.bias"))) return 1;
-      } else if (need(h, c + ".0.bias") || need(h, c + ".2.1.weight") || need(h, c + ".2.1.bias")) {
-        return 1;
-      }
-    }
-    for (const char* k : {"layer_norm.weight", "layer_norm.bias", "post_extract_proj.weight", "post_extract_proj.bias",
-                          "encoder.pos_conv.0.bias", "encoder.layer_norm.weight", "encoder.layer_norm.bias"})
-      if (need(h, P + k)) return 1;
-    for (int l = 0; l < h->cfg.n_layers; ++l) {
-      const std::string L = P + "encoder.layers." + std::to_string(l) + ".";
-      for (const char* k : {"self_attn.q_proj.weight", "self_attn.q_proj.bias", "self_attn.k_proj.weight",
-                            "self_attn.k_proj.bias", "self_attn.v_proj.weight", "self_attn.v_proj.bias",
-                            "self_attn.out_proj.weight", "self_attn.out_proj.bias", "self_attn_layer_norm.weight",
-                            "self_attn_layer_norm.bias", "fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias",
-                            "final_layer_norm.weight", "final_layer_norm.bias"})
-        if (need(h, L + k)) return 1;
-    }
     if (!gn && (h->dt != AFX_DT_FP32 || h->s3)) {  // conv layer 0 as the split-precision fp16 matrix-core operand
       if (!h->conv0pack && !(h->conv0pack = h->dalloc(conv0_pack_bytes()))) return fail("afx_finalize: device allocation failed");
-      KOK(launch_conv0_pack(h->F("ssl.feature_extractor.conv_layers.0.0.weight"), h->F("ssl.feature_extractor.conv_layers.0.0.bias"),
-                            h->conv0pack, s));
+      KOK(launch_conv0_pack(h->conv[0].w0, h->conv[0].bias, h->conv0pack, s));
     }
     // positional conv: weight-norm (dim=2) folded into the packed operand
     const float* pv = h->F("ssl.encoder.pos_conv.0.weight_v");
@@ -573,66 +659,46 @@ extern "C" int afx_finalize(afx_handle h, void* stream) {
     } else if (pw) {
       KOK(launch_pack_posconv(pw, nullptr, kD, kD / kPosG, kPosK, h->pos_norm, h->posw, h->dt, s));
     } else {
-      return fail("afx_finalize: missing weight '%sencoder.pos_conv.0.weight_g/weight_v'", P.c_str());
+      return fail("afx_finalize: missing weight 'ssl_model.model.encoder.pos_conv.0.weight_g/weight_v'");
     }
     if (h->s3) KOK(launch_split_weight_rows(h->posw, kD, (kD / kPosG) * kPosK, h->wscale(h->posw, kD, (size_t)(kD / kPosG) * kPosK), s));
   }
   if (h->cfg.arch == AFX_ARCH_CONFORMER || head_only) {
-    for (const char* k : {"LL.weight", "LL.bias", "first_bn.weight", "first_bn.bias", "first_bn.running_mean",
-                          "first_bn.running_var", "conformer.class_token", "conformer.fc5.weight", "conformer.fc5.bias"})
-      if (!(head_only && strncmp(k, "conformer.", 10)) && need(h, k)) return 1;
     for (int b = 0; b < h->nblk; ++b) {
-      const std::string B = "conformer.encoder_blocks." + std::to_string(b) + ".";
-      for (const char* k :
-           {"ff1.fn.norm.weight", "ff1.fn.norm.bias", "ff1.fn.fn.net.0.weight", "ff1.fn.fn.net.0.bias",
-            "ff1.fn.fn.net.3.weight", "ff1.fn.fn.net.3.bias", "ff2.fn.norm.weight", "ff2.fn.norm.bias",
-            "ff2.fn.fn.net.0.weight", "ff2.fn.fn.net.0.bias", "ff2.fn.fn.net.3.weight", "ff2.fn.fn.net.3.bias",
-            "attn.norm.weight", "attn.norm.bias", "attn.fn.to_q.weight", "attn.fn.to_kv.weight",
-            "attn.fn.to_out.weight", "attn.fn.to_out.bias", "attn.fn.rel_pos_emb.weight", "conv.net.0.weight",
-            "conv.net.0.bias", "conv.net.2.weight", "conv.net.2.bias", "conv.net.4.conv.weight",
-            "conv.net.4.conv.bias", "conv.net.5.weight", "conv.net.5.bias", "conv.net.5.running_mean",
-            "conv.net.5.running_var", "conv.net.7.weight", "conv.net.7.bias", "post_norm.weight", "post_norm.bias"})
-        if (need(h, B + k)) return 1;
-      if (fold_bn(h, B + "conv.net.5.", h->C2, h->blk[b].bn_scale, h->blk[b].bn_shift, s)) return 1;
-      const FT& dw = h->f[B + "conv.net.4.conv.weight"];
-      if (dw.n != (size_t)h->C2 * h->ck)
-        return fail("afx_finalize: depthwise kernel has %zu elements, expected %d x %d", dw.n, h->C2, h->ck);
-      const FT& rp = h->f[B + "attn.fn.rel_pos_emb.weight"];
-      if (rp.n != (size_t)1025 * h->dh) return fail("afx_finalize: rel_pos_emb must be (1025, %d)", h->dh);
-      KOK(launch_pack_linear(rp.p, 1025, h->dh, 64, h->blk[b].rel_h, h->dt, s));
+      ConfBlock& K = h->blk[b];
+      if (fold_bn(h, "conformer.encoder_blocks." + std::to_string(b) + ".conv.net.5.", h->C2, K.bn_scale, K.bn_shift, s)) return 1;
+      KOK(launch_pack_linear(K.rel32, 1025, h->dh, 64, K.rel_h, h->dt, s));
       if (h->E == 144) {  // parameter blocks of the fused chains (layout: ChainParamOffsets in afx_kernels.h)
-        auto put = [&](int st, int off, const std::string& name, int n) -> int {
-          HIP_OK(hipMemcpyAsync(h->blk[b].chain_prm[st] + off, h->F(B + name), (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+        auto put = [&](int st, int off, const float* v, int n) -> int {
+          HIP_OK(hipMemcpyAsync(K.chain_prm[st] + off, v, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
           return 0;
         };
-        for (int st = 0; st < 3; ++st) HIP_OK(hipMemsetAsync(h->blk[b].chain_prm[st], 0, (kChainParamFloats + kChainScaleFloats) * 4, s));
+        for (int st = 0; st < 3; ++st) HIP_OK(hipMemsetAsync(K.chain_prm[st], 0, (kChainParamFloats + kChainScaleFloats) * 4, s));
         for (int st = 0; st < 3; st += 2) {  // stages 0 and 2 carry a feed-forward module
-          const std::string ff = st == 0 ? "ff1" : "ff2";
-          if (put(st, CP_FF_G, ff + ".fn.norm.weight", 144) || put(st, CP_FF_B, ff + ".fn.norm.bias", 144) ||
-              put(st, CP_FF_B1, ff + ".fn.fn.net.0.bias", 576) || put(st, CP_FF_B2, ff + ".fn.fn.net.3.bias", 144))
+          const ConfFF& ff = K.ff[st / 2];
+          if (put(st, CP_FF_G, ff.ln.g, 144) || put(st, CP_FF_B, ff.ln.b, 144) || put(st, CP_FF_B1, ff.b1, 576) || put(st, CP_FF_B2, ff.b2, 144))
             return 1;
         }
-        if (put(0, CP_LN2_G, "attn.norm.weight", 144) || put(0, CP_LN2_B, "attn.norm.bias", 144) ||
-            put(1, CP_LN2_G, "conv.net.0.weight", 144) || put(1, CP_LN2_B, "conv.net.0.bias", 144) ||
-            put(1, CP_BA, "attn.fn.to_out.bias", 144) || put(1, CP_BB, "conv.net.2.bias", 576) ||
-            put(2, CP_LN2_G, "post_norm.weight", 144) || put(2, CP_LN2_B, "post_norm.bias", 144) ||
-            put(2, CP_BA, "conv.net.7.bias", 144))
+        if (put(0, CP_LN2_G, K.attn_ln.g, 144) || put(0, CP_LN2_B, K.attn_ln.b, 144) ||
+            put(1, CP_LN2_G, K.conv_ln.g, 144) || put(1, CP_LN2_B, K.conv_ln.b, 144) ||
+            put(1, CP_BA, K.bout, 144) || put(1, CP_BB, K.bpw1, 576) ||
+            put(2, CP_LN2_G, K.post_ln.g, 144) || put(2, CP_LN2_B, K.post_ln.b, 144) ||
+            put(2, CP_BA, K.bpw2, 144))
           return 1;
         if (h->s3) {  // the weight rows' scales, per output column, behind the parameter block (ChainScaleOffsets)
-          ConfBlock& K = h->blk[b];
           auto sc = [&](int st, int off, const void* w, int rows, int kp) -> int {
             HIP_OK(hipMemcpyAsync(K.chain_prm[st] + kChainParamFloats + off, h->wscale(w, rows, kp), (size_t)rows * 4, hipMemcpyDeviceToDevice, s));
             return 0;
           };
-          if (sc(0, CS_FF1, K.ff1_w1, h->FF, h->Ep) || sc(0, CS_FF2, K.ff1_w2, h->E, h->FFp) || sc(0, CS_A, K.wqkv, 3 * h->inner, h->Ep) ||
+          if (sc(0, CS_FF1, K.ff[0].w1, h->FF, h->Ep) || sc(0, CS_FF2, K.ff[0].w2, h->E, h->FFp) || sc(0, CS_A, K.wqkv, 3 * h->inner, h->Ep) ||
               sc(1, CS_A, K.wout, h->E, h->Ep) || sc(1, CS_B, K.pw1, 2 * h->C2, h->Ep) ||
-              sc(2, CS_A, K.pw2, h->E, h->C2p) || sc(2, CS_FF1, K.ff2_w1, h->FF, h->Ep) || sc(2, CS_FF2, K.ff2_w2, h->E, h->FFp))
+              sc(2, CS_A, K.pw2, h->E, h->C2p) || sc(2, CS_FF1, K.ff[1].w1, h->FF, h->Ep) || sc(2, CS_FF2, K.ff[1].w2, h->E, h->FFp))
             return 1;
         }
       }
     }
     if (head_only) {
-      if (int rc = s3_layernorm_scales(h, s)) return rc;
+      if (int rc = s3_layernorm_scales(h, lns, s)) return rc;
       h->finalized = true;
       return 0;
     }
@@ -651,7 +717,7 @@ extern "C" int afx_finalize(afx_handle h, void* stream) {
             h->aw, [&](const std::string& k) { return h->F(k); }, [&](size_t bytes) { return h->dalloc(bytes); }, s))
       return fail("afx_finalize: %s", m);
   }
-  if (int rc = s3_layernorm_scales(h, s)) return rc;
+  if (int rc = s3_layernorm_scales(h, lns, s)) return rc;
   h->finalized = true;
   return 0;
 }
@@ -844,8 +910,8 @@ static void prof_forget(afx_engine* e) {
 // by reference to whatever launches for it; nothing here is shared between calls, handles or threads, and nothing of it
 // outlives the call except the handle's `last_objective` read-back.  It holds the stream, the launch-shape objective (read
 // once from the handle's "concurrent" switch: fixed for the whole call), the handle's profiler, and -- split precision -- the
-// pair-form scratch of the workspace the call runs in with the registry below.  The engine's other switches ("gemm_small_deep",
-// the LayerNorm scales) are read from `e` where they are used.
+// pair-form scratch of the workspace the call runs in with the registry below.  The engine's other switches ("gemm_small_deep")
+// and its weight tables are read from `e` where they are used.
 // Pair-form registry: operand buffers whose ONLY readers are dense products may receive their producer's result directly as
 // the product's A operand (the PAIR FORM of the row -- afx_kernels.h -- in place of its fp32 values: same bytes, row by row) --
 // the LayerNorms, the GELU / LayerNorm epilogues of the products and the attention write the operand themselves and the
@@ -889,12 +955,6 @@ struct Call {
     for (const S3Reg& r : s3reg) if (r.p && r.p == p) return r.scale;
     return 0.f;
   }
-  // the scale a LayerNorm's output takes as a pair-form operand: what finalize chose for its gamma (afx_engine::ln_scale)
-  float ln_scale(const float* gamma) const {
-    auto it = e->ln_scale.find(gamma);
-    return it != e->ln_scale.end() ? it->second : kS3ScaleBounded;
-  }
-
   template <class F>
   const char* timed(int cls, double flops, F&& f) {
     if (!prof || !prof->on) return f();
@@ -907,7 +967,7 @@ struct Call {
     return m;
   }
   const char* gemm(const GemmArgs& g_in, int dt, int groups, bool rows = false);
-  const char* rownorm(const RowNormArgs& a_in, int dt);
+  const char* rownorm(const RowNormArgs& a_in, const LnW& ln, int dt);
 };
 // Split precision (Call::gemm): x.w ~ xh.wl + xl.wh + xh.wh on the fp16 matrix pipe.  Both operands go in PAIR FORM
 // (afx_kernels.h): the weight is stored that way with per-row scales behind it (pack_linear), the fp32 A operand is either
@@ -973,12 +1033,14 @@ const char* Call::gemm(const GemmArgs& g_in, int dt, int groups, bool rows) {
   return timed(dt == DT_FP32 ? PC_GEMM_F32 : cls_of(gemm_tile_of(g, groups)), fl,
                [&] { return rows ? launch_gemm_rows(g, dt, s) : launch_gemm(g, dt, groups, s); });
 }
-const char* Call::rownorm(const RowNormArgs& a_in, int dt) {
+// the rows of `a_in` (plain_norm) through the LayerNorm `ln` of the weight tables
+const char* Call::rownorm(const RowNormArgs& a_in, const LnW& ln, int dt) {
   RowNormArgs a = a_in;
+  a.gamma = ln.g; a.beta = ln.b;
   if (a.out_h && s3planes) {  // split precision: the LayerNorm writes the next product's A operand (pair-form rows) itself
     const bool pairs_out = dt == DT_FP32 && s3_ok(a.out_h) && (a.ldo_h & 31) == 0 && a.out_h != (const void*)a.x;
     a.oh_pairs = pairs_out ? 1 : 0;
-    a.oh_scale = ln_scale(a.gamma);  // |LayerNorm output| <= sqrt(C) max|gamma| + max|beta|: the scale finalize chose for this LayerNorm
+    a.oh_scale = ln.scale;  // |LayerNorm output| <= sqrt(C) max|gamma| + max|beta|: the scale finalize chose for this LayerNorm
     s3_set(a.out_h, pairs_out ? a.oh_scale : 0.f);
   }
   return timed(PC_ROWNORM, 0, [&] { return launch_rownorm(a, dt, s); });
@@ -1055,10 +1117,10 @@ static GemmArgs plain_gemm(const void* A, long lda, const void* W, long ldw, int
   return g;
 }
 
-static RowNormArgs plain_norm(const float* x, long ldx, int rows, int C, const float* g, const float* b) {
+static RowNormArgs plain_norm(const float* x, long ldx, int rows, int C) {  // (gamma, beta: Call::rownorm)
   RowNormArgs a;
   memset(&a, 0, sizeof a);
-  a.x = x; a.ldx = ldx; a.rows = rows; a.C = C; a.gamma = g; a.beta = b; a.eps = kLnEps; a.act = ACT_NONE;
+  a.x = x; a.ldx = ldx; a.rows = rows; a.C = C; a.eps = kLnEps; a.act = ACT_NONE;
   a.rpb = rows; a.o_batch_rows = rows;
   return a;
 }
@@ -1078,7 +1140,7 @@ static const char* posconv_product(Call& cx, const void* rows, long batch_rows, 
   g.rpb = T; g.a_batch = batch_rows * kD; g.a_row = kD;
   g.kchunk = cpg; g.kchunk_stride = kD;
   g.g_a = cpg; g.g_w = (long)cpg * cpg * kPosK; g.g_n = cpg;
-  g.bias = e->F("ssl.encoder.pos_conv.0.bias");
+  g.bias = e->pos_b;
   g.act = ACT_GELU;
   g.resid = x; g.ldr = kD;
   g.out_f = x; g.ldo_f = kD; g.o_batch_rows = T; g.oh_batch_rows = T;
@@ -1093,25 +1155,22 @@ static int run_trunk(Call& cx, const float* wave, int B, int L, Ws& w, const voi
   const int dt = e->dt;
   const int* T = w.T;
   if (T[6] < 1) return fail("afx_forward: %d samples are too few for one output frame (need >= 400)", L);
-  auto cf = [&](int i, const char* leaf) {
-    return e->F("ssl.feature_extractor.conv_layers." + std::to_string(i) + leaf);
-  };
+  const ConvLayer& c0 = e->conv[0];
   // layer 0: waveform -> (B,T0,512) operand type, normalisation + GELU fused
   const bool gn = e->cfg.extractor_mode == AFX_EXTRACTOR_GROUP_NORM;
   if (!l5)
     KOK(cx.timed(PC_CONV0, 2.0 * B * T[0] * kC * kConvK[0], [&] {
       if (gn)  // wav2vec2-base: GroupNorm over time per (utterance, channel), two passes over the cheap convolution
-        return launch_conv0_groupnorm(wave, B, L, T[0], cf(0, ".0.weight"), cf(0, ".2.weight"), cf(0, ".2.bias"), kLnEps,
+        return launch_conv0_groupnorm(wave, B, L, T[0], c0.w0, c0.gn_g, c0.gn_b, kLnEps,
                                       w.gn_stats, w.bufA, dt, s);
       if (e->s3) {  // split precision: the same matrix-core kernel as the fp16 engines; its rows leave as conv layer 1's pair-form operand
         // (LayerNorm + GELU output: bounded by the LayerNorm's gains -- the scale finalize chose for it)
-        const float sc = cx.s3_ok(w.bufA) ? cx.ln_scale(cf(0, ".2.1.weight")) : 0.f;
+        const float sc = cx.s3_ok(w.bufA) ? c0.ln.scale : 0.f;
         cx.s3_set(w.bufA, sc);
-        return launch_conv0(wave, B, L, T[0], cf(0, ".0.weight"), cf(0, ".0.bias"), cf(0, ".2.1.weight"), cf(0, ".2.1.bias"),
-                            e->cfg.pre_emphasis, e->cfg.pre_emphasis_coef, w.bufA, DT_FP16X3, s, e->conv0pack, sc);
+        return launch_conv0(wave, B, L, T[0], c0.w0, c0.bias, c0.ln.g, c0.ln.b, e->cfg.pre_emphasis, e->cfg.pre_emphasis_coef, w.bufA, DT_FP16X3, s, e->conv0pack, sc);
       }
-      return launch_conv0(wave, B, L, T[0], cf(0, ".0.weight"), cf(0, ".0.bias"), cf(0, ".2.1.weight"),
-                          cf(0, ".2.1.bias"), e->cfg.pre_emphasis, e->cfg.pre_emphasis_coef, w.bufA, dt, s, e->conv0pack);
+      return launch_conv0(wave, B, L, T[0], c0.w0, c0.bias, c0.ln.g, c0.ln.b, e->cfg.pre_emphasis, e->cfg.pre_emphasis_coef, w.bufA, dt, s,
+                          e->conv0pack);
     }));
   if (!l5) TAP("c0", w.bufA, (size_t)B * T[0] * kC, true, kC);
   // layers 1..6: conv-as-GEMM on a row-complete tile, LayerNorm(512) + GELU fused into the
@@ -1123,7 +1182,7 @@ static int run_trunk(Call& cx, const float* wave, int B, int L, Ws& w, const voi
     GemmArgs g = plain_gemm(in, 0, e->convw[i], K, M, kC, K);
     g.rpb = T[i]; g.a_batch = (l5 && i == 6 && l5_batch) ? l5_batch : (long)T[i - 1] * kC; g.a_row = (long)kConvS[i] * kC;
     g.o_batch_rows = T[i]; g.oh_batch_rows = T[i];
-    g.bias = gn ? nullptr : cf(i, ".0.bias");
+    g.bias = e->conv[i].bias;  // (group-norm mode: null)
     g.act = ACT_GELU;
     if (gn) {  // wav2vec2-base: conv -> GELU, nothing to normalise in layers 1-6 (plain product, GELU epilogue)
       if (i < 6) {
@@ -1136,7 +1195,7 @@ static int run_trunk(Call& cx, const float* wave, int B, int L, Ws& w, const voi
       // (split precision takes the two-kernel form below: measured, the row-complete tile with the pair-form walk and the fp32
       // erf-GELU in its epilogue is SLOWER than the 256-wide tile + a LayerNorm pass that writes the next layer's pair-form
       // operand -- student 12.9 against 12.3 ms per forward, teacher 9.0 / 8.75: profiles/r04_s3_knobs.txt)
-      g.ln_gamma = cf(i, ".2.1.weight"); g.ln_beta = cf(i, ".2.1.bias"); g.ln_eps = kLnEps;
+      g.ln_gamma = e->conv[i].ln.g; g.ln_beta = e->conv[i].ln.b; g.ln_eps = kLnEps;
       if (i < 6) {
         g.out_h = out; g.ldo_h = kC;
       } else {
@@ -1147,14 +1206,14 @@ static int run_trunk(Call& cx, const float* wave, int B, int L, Ws& w, const voi
       g.act = ACT_NONE;
       g.out_f = w.tmp32; g.ldo_f = kC;
       KOK(cx.gemm(g, dt, 1));
-      RowNormArgs n = plain_norm(w.tmp32, kC, M, kC, cf(i, ".2.1.weight"), cf(i, ".2.1.bias"));
+      RowNormArgs n = plain_norm(w.tmp32, kC, M, kC);
       n.act = ACT_GELU;
       if (i < 6) {
         n.out_h = out; n.ldo_h = kC;
       } else {
         n.out_f = w.tmp32; n.ldo_f = kC;  // in place: a row is register-resident before it is written
       }
-      KOK(cx.rownorm(n, dt));
+      KOK(cx.rownorm(n, e->conv[i].ln, dt));
     }
     if (i < 6) TAP("c" + std::to_string(i), out, (size_t)M * kC, true, kC);
     void* t = in; in = out; out = t;
@@ -1163,16 +1222,16 @@ static int run_trunk(Call& cx, const float* wave, int B, int L, Ws& w, const voi
   if (tap(cx, "conv", w.tmp32, (size_t)M * kC, false)) return 1;
   // feature LayerNorm(512) -> operand type
   {
-    RowNormArgs n = plain_norm(w.tmp32, kC, M, kC, e->F("ssl.layer_norm.weight"), e->F("ssl.layer_norm.bias"));
+    RowNormArgs n = plain_norm(w.tmp32, kC, M, kC);
     n.out_h = w.feats_h; n.ldo_h = kC;
-    KOK(cx.rownorm(n, dt));
+    KOK(cx.rownorm(n, e->feat_ln, dt));
   }
   TAP("feats", w.feats_h, (size_t)M * kC, true, kC);
   // post_extract_proj: fp32 residual stream x + operand copy into the time-padded buffer
   {
     GemmArgs g = plain_gemm(w.feats_h, kC, e->projw, kC, M, kD, kC);
     g.rpb = Tt; g.a_batch = (long)Tt * kC; g.a_row = kC;
-    g.bias = e->F("ssl.post_extract_proj.bias");
+    g.bias = e->proj_b;
     g.out_f = w.x; g.ldo_f = kD; g.o_batch_rows = Tt; g.o_row_off = 0;
     g.out_h = w.xpad; g.ldo_h = kD; g.oh_batch_rows = Tt + kPosK; g.oh_row_off = kPosPad;
     KOK(cx.gemm(g, dt, 1));
@@ -1186,7 +1245,7 @@ static int run_trunk(Call& cx, const float* wave, int B, int L, Ws& w, const voi
   if (e->posconv_sliding && dt != DT_FP32 && Tt <= 224) {  // (reads the zero-padded operand copy: ragged batches need nothing more)
     PosConvArgs pc;
     memset(&pc, 0, sizeof pc);
-    pc.xpad = w.xpad; pc.xpad_batch = (long)(Tt + kPosK) * kD; pc.W = e->posw; pc.bias = e->F("ssl.encoder.pos_conv.0.bias");
+    pc.xpad = w.xpad; pc.xpad_batch = (long)(Tt + kPosK) * kD; pc.W = e->posw; pc.bias = e->pos_b;
     pc.x = w.x; pc.B = B; pc.T = Tt;
     KOK(cx.timed(PC_POSCONV, 2.0 * M * kD * (kD / kPosG) * kPosK, [&] { return launch_posconv(pc, dt, s); }));
   } else {
@@ -1200,17 +1259,17 @@ static int run_trunk(Call& cx, const float* wave, int B, int L, Ws& w, const voi
     return cx.gemm(o, dt, 1);
   };
   for (int l = 0; l < e->cfg.n_layers; ++l) {
-    const std::string P = "ssl.encoder.layers." + std::to_string(l) + ".";
-    RowNormArgs n1 = plain_norm(w.x, kD, M, kD, e->F(P + "self_attn_layer_norm.weight"), e->F(P + "self_attn_layer_norm.bias"));
+    const TrunkLayer& L = e->layers[l];
+    RowNormArgs n1 = plain_norm(w.x, kD, M, kD);
     n1.out_h = w.hbuf; n1.ldo_h = kD;
-    KOK(cx.rownorm(n1, dt));
-    const std::string lp = "l" + std::to_string(l) + ".";
-    TAP(lp + "ln1", w.hbuf, (size_t)M * kD, true, kD);
-    GemmArgs q = plain_gemm(w.hbuf, kD, e->wqkv[l], kD, M, 3 * kD, kD);
-    q.bias = e->bqkv[l];
+    KOK(cx.rownorm(n1, L.ln1, dt));
+    auto lp = [l](const char* leaf) { return "l" + std::to_string(l) + "." + leaf; };  // (tap names: built only while taps are on)
+    TAP(lp("ln1"), w.hbuf, (size_t)M * kD, true, kD);
+    GemmArgs q = plain_gemm(w.hbuf, kD, L.wqkv, kD, M, 3 * kD, kD);
+    q.bias = L.bqkv;
     q.out_h = w.qkv; q.ldo_h = 3 * kD;
     KOK(cx.gemm(q, dt, 1));
-    TAP(lp + "qkv", w.qkv, (size_t)M * 3 * kD, true, 3 * kD);
+    TAP(lp("qkv"), w.qkv, (size_t)M * 3 * kD, true, 3 * kD);
     KOK(cx.timed(PC_MHSA, 4.0 * B * kH * (double)Tt * Tt * 64, [&] {
       if (e->s3 && Tt <= 224) {  // split precision: the matrix-core form; its output goes out as the output projection's A planes
         const bool pairs = cx.s3_ok(w.att);
@@ -1220,31 +1279,31 @@ static int run_trunk(Call& cx, const float* wave, int B, int L, Ws& w, const voi
       if (e->s3) cx.s3_set(w.att, 0.f);
       return launch_mhsa(w.qkv, w.att, B, Tt, kH, dt, s, w.lens);
     }));
-    TAP(lp + "att", w.att, (size_t)M * kD, true, kD);
-    KOK(resid_product(w.att, kD, e->wo[l], kD, e->F(P + "self_attn.out_proj.bias")));
-    TAP(lp + "mid", w.x, (size_t)M * kD, false, kD);
-    RowNormArgs n2 = plain_norm(w.x, kD, M, kD, e->F(P + "final_layer_norm.weight"), e->F(P + "final_layer_norm.bias"));
+    TAP(lp("att"), w.att, (size_t)M * kD, true, kD);
+    KOK(resid_product(w.att, kD, L.wo, kD, L.bo));
+    TAP(lp("mid"), w.x, (size_t)M * kD, false, kD);
+    RowNormArgs n2 = plain_norm(w.x, kD, M, kD);
     n2.out_h = w.hbuf; n2.ldo_h = kD;
-    KOK(cx.rownorm(n2, dt));
-    TAP(lp + "ln2", w.hbuf, (size_t)M * kD, true, kD);
-    GemmArgs f1 = plain_gemm(w.hbuf, kD, e->w1[l], kD, M, kF, kD);
-    f1.bias = e->F(P + "fc1.bias"); f1.act = ACT_GELU;
+    KOK(cx.rownorm(n2, L.ln2, dt));
+    TAP(lp("ln2"), w.hbuf, (size_t)M * kD, true, kD);
+    GemmArgs f1 = plain_gemm(w.hbuf, kD, L.w1, kD, M, kF, kD);
+    f1.bias = L.b1; f1.act = ACT_GELU;
     f1.out_h = w.ff; f1.ldo_h = kF;
     KOK(cx.gemm(f1, dt, 1));
-    TAP(lp + "ff", w.ff, (size_t)M * kF, true, kF);
-    KOK(resid_product(w.ff, kF, e->w2[l], kF, e->F(P + "fc2.bias")));
+    TAP(lp("ff"), w.ff, (size_t)M * kF, true, kF);
+    KOK(resid_product(w.ff, kF, L.w2, kF, L.b2));
     if (e->taps_on) {
       const std::string nm = "layer" + std::to_string(l);
       if (tap(cx, nm.c_str(), w.x, (size_t)M * kD, false)) return 1;
     }
   }
   // final encoder LayerNorm -> fp32 features (API output / AASIST input) + operand copy (LL GEMM)
-  RowNormArgs nf = plain_norm(w.x, kD, M, kD, e->F("ssl.encoder.layer_norm.weight"), e->F("ssl.encoder.layer_norm.bias"));
+  RowNormArgs nf = plain_norm(w.x, kD, M, kD);
   nf.out_f = w.ssl_f; nf.ldo_f = kD;
   nf.out_h = w.ssl_h; nf.ldo_h = kD;
   nf.nonfinite = e->nonfinite;  // overflow guard: an operand copy that left fp16's range anywhere in the trunk ends here as inf / NaN
   nf.nf_lens = w.lens; nf.nf_rpb = Tt;  // (ragged batch: only the rows of an utterance's own length are judged; the others hold stale workspace)
-  KOK(cx.rownorm(nf, dt));
+  KOK(cx.rownorm(nf, e->enc_ln, dt));
   if (tap(cx, "ssl", w.ssl_f, (size_t)M * kD, false)) return 1;
   TAP("ssl.op", w.ssl_h, (size_t)M * kD, true, kD);
   return 0;
@@ -1258,15 +1317,15 @@ static int run_conformer(Call& cx, int B, int T, Ws& w, float* logits, const flo
   const hipStream_t s = cx.s;
   const int dt = e->dt, E = e->E, Ep = e->Ep, N = T + 1, M = B * N;
   if (tokens) {  // class token + the rows as they are
-    KOK(cx.timed(PC_MISC, 0, [&] { return launch_conf_tokens(tokens, e->F("conformer.class_token"), 1.f, 0.f, B, T, E, w.xc, s, true); }));
+    KOK(cx.timed(PC_MISC, 0, [&] { return launch_conf_tokens(tokens, e->class_token, 1.f, 0.f, B, T, E, w.xc, s, true); }));
   } else {
     // LL -> BatchNorm2d(1) -> SELU -> class token
     GemmArgs ll = plain_gemm(w.ssl_h, kD, e->conf_ll, kD, B * T, E, kD);
-    ll.bias = e->F("LL.bias");
+    ll.bias = e->ll_b;
     ll.out_f = w.ll32; ll.ldo_f = E;
     KOK(cx.gemm(ll, dt, 1));
     KOK(cx.timed(PC_MISC, 0, [&] {
-      return launch_conf_tokens(w.ll32, e->F("conformer.class_token"), e->conf_bn_scale, e->conf_bn_shift, B, T, E, w.xc, s);
+      return launch_conf_tokens(w.ll32, e->class_token, e->conf_bn_scale, e->conf_bn_shift, B, T, E, w.xc, s);
     }));
   }
   if (tap(cx, "tokens", w.xc, (size_t)M * E, false)) return 1;
@@ -1284,22 +1343,21 @@ static int run_conformer(Call& cx, int B, int T, Ws& w, float* logits, const flo
   }
   for (int b = 0; fused && b < e->nblk; ++b) {
     // three register-resident row chains around the attention and the depthwise conv
-    const std::string P = "conformer.encoder_blocks." + std::to_string(b) + ".";
-    ConfBlock& K = e->blk[b];
+    const ConfBlock& K = e->blk[b];
     ConfChainArgs c;
     memset(&c, 0, sizeof c);
     c.M = M; c.E = E; c.Ep = Ep; c.FFp = e->FFp; c.objective = cx.objective;
     c.x_in = w.xc; c.x_out = w.xc;  // in place: a wave reads and writes only its own 16 rows
-    auto ff = [&](void* w1, void* w2) { c.ff_w1 = w1; c.ff_w2 = w2; };
+    auto ff = [&](const ConfFF& f) { c.ff_w1 = f.w1; c.ff_w2 = f.w2; };
     const double ff_fl = 2.0 * M * E * e->FF * 2;
-    ff(K.ff1_w1, K.ff1_w2);
+    ff(K.ff[0]);
     c.params = K.chain_prm[0];
     c.w_a = K.wqkv; c.ld_w_a = Ep;
     c.out2 = w.qkv32; c.ld_out2 = 3 * e->inner;
     KOK(cx.timed(PC_CONF_CHAIN, ff_fl + 2.0 * M * E * 3 * e->inner, [&] { return launch_conf_chain(c, 0, chain_dt, s); }));
-    const std::string bp = "b" + std::to_string(b) + ".";
-    TAP(bp + "xa", w.xc, (size_t)M * E, false, E);
-    TAP(bp + "qkv", w.qkv32, (size_t)M * 3 * e->inner, false, 3 * e->inner);
+    auto bp = [b](const std::string& leaf) { return "b" + std::to_string(b) + "." + leaf; };  // (tap names: only while taps are on)
+    TAP(bp("xa"), w.xc, (size_t)M * E, false, E);
+    TAP(bp("qkv"), w.qkv32, (size_t)M * 3 * e->inner, false, 3 * e->inner);
     KOK(cx.timed(PC_CONF_ATTN, 6.0 * B * e->heads * (double)N * N * e->dh, [&] {
       if (e->conf_attn_mfma && dt != DT_FP32 && e->dh == 36)
         return launch_conf_attn_mfma(w.qkv32, 3 * e->inner, w.qkv32 + e->inner, 3 * e->inner, K.rel_h, 512, B, N, e->heads,
@@ -1308,27 +1366,25 @@ static int run_conformer(Call& cx, int B, int T, Ws& w, float* logits, const flo
         return launch_conf_attn_split(w.qkv32, 3 * e->inner, w.qkv32 + e->inner, 3 * e->inner, (const float*)K.rel_h, 512, B, N,
                                       e->heads, e->dh, (float*)w.ao, Ep, s, w.lens, 1);
       return launch_conf_attn(w.qkv32, 3 * e->inner, w.qkv32 + e->inner, 3 * e->inner,
-                              e->F(P + "attn.fn.rel_pos_emb.weight"), 512, B, N, e->heads, e->dh, w.ao, Ep, dt, s, w.lens, 1);
+                              K.rel32, 512, B, N, e->heads, e->dh, w.ao, Ep, dt, s, w.lens, 1);
     }));
-    TAP(bp + "ao", w.ao, (size_t)M * Ep, true, Ep);
+    TAP(bp("ao"), w.ao, (size_t)M * Ep, true, Ep);
     c.in_h = w.ao; c.ld_in_h = Ep;
     c.params = K.chain_prm[1];
     c.w_a = K.wout;
     c.w_b = K.pw1;
     c.out2 = w.glu32; c.ld_out2 = 2 * e->C2;
     KOK(cx.timed(PC_CONF_CHAIN, 2.0 * M * E * (e->inner + 2 * e->C2), [&] { return launch_conf_chain(c, 1, chain_dt, s); }));
-    TAP(bp + "xb", w.xc, (size_t)M * E, false, E);
-    TAP(bp + "glu", w.glu32, (size_t)M * 2 * e->C2, false, 2 * e->C2);
+    TAP(bp("xb"), w.xc, (size_t)M * E, false, E);
+    TAP(bp("glu"), w.glu32, (size_t)M * 2 * e->C2, false, 2 * e->C2);
     KOK(cx.timed(PC_CONF_DWCONV, 2.0 * B * N * e->C2 * e->ck, [&] {
-      return launch_conf_dwconv(w.glu32, 2 * e->C2, e->F(P + "conv.net.4.conv.weight"),
-                                e->F(P + "conv.net.4.conv.bias"), K.bn_scale, K.bn_shift, B, N, e->C2, e->ck, w.u,
-                                e->C2p, dt, s, w.lens, 1);
+      return launch_conf_dwconv(w.glu32, 2 * e->C2, K.dw_w, K.dw_b, K.bn_scale, K.bn_shift, B, N, e->C2, e->ck, w.u, e->C2p, dt, s, w.lens, 1);
     }));
-    TAP(bp + "u", w.u, (size_t)M * e->C2p, true, e->C2p);
+    TAP(bp("u"), w.u, (size_t)M * e->C2p, true, e->C2p);
     c.in_h = w.u; c.ld_in_h = e->C2p;
     c.params = K.chain_prm[2];
     c.w_a = K.pw2; c.ld_w_a = e->C2p;
-    ff(K.ff2_w1, K.ff2_w2);
+    ff(K.ff[1]);
     c.w_b = nullptr; c.out2 = nullptr;
     KOK(cx.timed(PC_CONF_CHAIN, ff_fl + 2.0 * M * e->C2 * E, [&] { return launch_conf_chain(c, 2, chain_dt, s); }));
     if (e->taps_on) {
@@ -1337,40 +1393,39 @@ static int run_conformer(Call& cx, int B, int T, Ws& w, float* logits, const flo
     }
   }
   for (int b = 0; !fused && b < e->nblk; ++b) {
-    const std::string P = "conformer.encoder_blocks." + std::to_string(b) + ".";
-    ConfBlock& K = e->blk[b];
-    const std::string bp = "b" + std::to_string(b) + ".";
-    auto norm_to_h = [&](const char* nm) -> const char* {
-      RowNormArgs n = plain_norm(w.xc, E, M, E, e->F(P + nm + ".weight"), e->F(P + nm + ".bias"));
+    const ConfBlock& K = e->blk[b];
+    auto bp = [b](const std::string& leaf) { return "b" + std::to_string(b) + "." + leaf; };  // (tap names: only while taps are on)
+    auto norm_to_h = [&](const LnW& ln) -> const char* {
+      RowNormArgs n = plain_norm(w.xc, E, M, E);
       n.out_h = w.hc; n.ldo_h = Ep;
-      return cx.rownorm(n, dt);
+      return cx.rownorm(n, ln, dt);
     };
-    auto feed_forward = [&](const char* ff, void* w1, void* w2) -> int {
-      KOK(norm_to_h((std::string(ff) + ".fn.norm").c_str()));
-      TAP(bp + ff + ".hc", w.hc, (size_t)M * Ep, true, Ep);
-      GemmArgs a = plain_gemm(w.hc, Ep, w1, Ep, M, e->FF, Ep);
+    auto feed_forward = [&](const char* ff, const ConfFF& f) -> int {
+      KOK(norm_to_h(f.ln));
+      TAP(bp(std::string(ff) + ".hc"), w.hc, (size_t)M * Ep, true, Ep);
+      GemmArgs a = plain_gemm(w.hc, Ep, f.w1, Ep, M, e->FF, Ep);
       a.k_algo = E;
-      a.bias = e->F(P + ff + ".fn.fn.net.0.bias"); a.act = ACT_SWISH;
+      a.bias = f.b1; a.act = ACT_SWISH;
       a.out_h = w.hid; a.ldo_h = e->FFp;
       KOK(cx.gemm(a, dt, 1));
-      TAP(bp + ff + ".hid", w.hid, (size_t)M * e->FFp, true, e->FFp);
-      GemmArgs c = plain_gemm(w.hid, e->FFp, w2, e->FFp, M, E, e->FFp);
+      TAP(bp(std::string(ff) + ".hid"), w.hid, (size_t)M * e->FFp, true, e->FFp);
+      GemmArgs c = plain_gemm(w.hid, e->FFp, f.w2, e->FFp, M, E, e->FFp);
       c.k_algo = e->FF;
-      c.bias = e->F(P + ff + ".fn.fn.net.3.bias"); c.alpha = 0.5f;
+      c.bias = f.b2; c.alpha = 0.5f;
       c.resid = w.xc; c.ldr = E; c.out_f = w.xc; c.ldo_f = E;
       KOK(cx.gemm(c, dt, 1));
       return 0;
     };
-    if (feed_forward("ff1", K.ff1_w1, K.ff1_w2)) return 1;
-    TAP(bp + "xa", w.xc, (size_t)M * E, false, E);
+    if (feed_forward("ff1", K.ff[0])) return 1;
+    TAP(bp("xa"), w.xc, (size_t)M * E, false, E);
     // attention
-    KOK(norm_to_h("attn.norm"));
-    TAP(bp + "attn.hc", w.hc, (size_t)M * Ep, true, Ep);
+    KOK(norm_to_h(K.attn_ln));
+    TAP(bp("attn.hc"), w.hc, (size_t)M * Ep, true, Ep);
     GemmArgs q = plain_gemm(w.hc, Ep, K.wqkv, Ep, M, 3 * e->inner, Ep);
     q.k_algo = E;
     q.out_f = w.qkv32; q.ldo_f = 3 * e->inner;
     KOK(cx.gemm(q, dt, 1));
-    TAP(bp + "qkv", w.qkv32, (size_t)M * 3 * e->inner, false, 3 * e->inner);
+    TAP(bp("qkv"), w.qkv32, (size_t)M * 3 * e->inner, false, 3 * e->inner);
     KOK(cx.timed(PC_CONF_ATTN, 6.0 * B * e->heads * (double)N * N * e->dh, [&] {
       if (e->conf_attn_mfma && dt != DT_FP32 && e->dh == 36)
         return launch_conf_attn_mfma(w.qkv32, 3 * e->inner, w.qkv32 + e->inner, 3 * e->inner, K.rel_h, 512, B, N, e->heads,
@@ -1379,48 +1434,46 @@ static int run_conformer(Call& cx, int B, int T, Ws& w, float* logits, const flo
         return launch_conf_attn_split(w.qkv32, 3 * e->inner, w.qkv32 + e->inner, 3 * e->inner, (const float*)K.rel_h, 512, B, N,
                                       e->heads, e->dh, (float*)w.ao, Ep, s, w.lens, 1);
       return launch_conf_attn(w.qkv32, 3 * e->inner, w.qkv32 + e->inner, 3 * e->inner,
-                              e->F(P + "attn.fn.rel_pos_emb.weight"), 512, B, N, e->heads, e->dh, w.ao, Ep, dt, s, w.lens, 1);
+                              K.rel32, 512, B, N, e->heads, e->dh, w.ao, Ep, dt, s, w.lens, 1);
     }));
-    TAP(bp + "ao", w.ao, (size_t)M * Ep, true, Ep);
+    TAP(bp("ao"), w.ao, (size_t)M * Ep, true, Ep);
     GemmArgs o = plain_gemm(w.ao, Ep, K.wout, Ep, M, E, Ep);
     o.k_algo = e->inner;
-    o.bias = e->F(P + "attn.fn.to_out.bias");
+    o.bias = K.bout;
     o.resid = w.xc; o.ldr = E; o.out_f = w.xc; o.ldo_f = E;
     KOK(cx.gemm(o, dt, 1));
-    TAP(bp + "xb", w.xc, (size_t)M * E, false, E);
+    TAP(bp("xb"), w.xc, (size_t)M * E, false, E);
     // conv module
-    KOK(norm_to_h("conv.net.0"));
-    TAP(bp + "conv.hc", w.hc, (size_t)M * Ep, true, Ep);
+    KOK(norm_to_h(K.conv_ln));
+    TAP(bp("conv.hc"), w.hc, (size_t)M * Ep, true, Ep);
     GemmArgs p1 = plain_gemm(w.hc, Ep, K.pw1, Ep, M, 2 * e->C2, Ep);
     p1.k_algo = E;
-    p1.bias = e->F(P + "conv.net.2.bias");
+    p1.bias = K.bpw1;
     p1.out_f = w.glu32; p1.ldo_f = 2 * e->C2;
     KOK(cx.gemm(p1, dt, 1));
-    TAP(bp + "glu", w.glu32, (size_t)M * 2 * e->C2, false, 2 * e->C2);
+    TAP(bp("glu"), w.glu32, (size_t)M * 2 * e->C2, false, 2 * e->C2);
     KOK(cx.timed(PC_CONF_DWCONV, 2.0 * B * N * e->C2 * e->ck, [&] {
-      return launch_conf_dwconv(w.glu32, 2 * e->C2, e->F(P + "conv.net.4.conv.weight"),
-                                e->F(P + "conv.net.4.conv.bias"), K.bn_scale, K.bn_shift, B, N, e->C2, e->ck, w.u,
-                                e->C2p, dt, s, w.lens, 1);
+      return launch_conf_dwconv(w.glu32, 2 * e->C2, K.dw_w, K.dw_b, K.bn_scale, K.bn_shift, B, N, e->C2, e->ck, w.u, e->C2p, dt, s, w.lens, 1);
     }));
-    TAP(bp + "u", w.u, (size_t)M * e->C2p, true, e->C2p);
+    TAP(bp("u"), w.u, (size_t)M * e->C2p, true, e->C2p);
     GemmArgs p2 = plain_gemm(w.u, e->C2p, K.pw2, e->C2p, M, E, e->C2p);
     p2.k_algo = e->C2;
-    p2.bias = e->F(P + "conv.net.7.bias");
+    p2.bias = K.bpw2;
     p2.resid = w.xc; p2.ldr = E; p2.out_f = w.xc; p2.ldo_f = E;
     KOK(cx.gemm(p2, dt, 1));
-    TAP(bp + "xc", w.xc, (size_t)M * E, false, E);
-    if (feed_forward("ff2", K.ff2_w1, K.ff2_w2)) return 1;
-    TAP(bp + "xd", w.xc, (size_t)M * E, false, E);
-    RowNormArgs pn = plain_norm(w.xc, E, M, E, e->F(P + "post_norm.weight"), e->F(P + "post_norm.bias"));
+    TAP(bp("xc"), w.xc, (size_t)M * E, false, E);
+    if (feed_forward("ff2", K.ff[1])) return 1;
+    TAP(bp("xd"), w.xc, (size_t)M * E, false, E);
+    RowNormArgs pn = plain_norm(w.xc, E, M, E);
     pn.out_f = w.xc; pn.ldo_f = E;
-    KOK(cx.rownorm(pn, dt));
+    KOK(cx.rownorm(pn, K.post_ln, dt));
     if (e->taps_on) {
       const std::string nm = "block" + std::to_string(b);
       if (tap(cx, nm.c_str(), w.xc, (size_t)M * E, false)) return 1;
     }
   }
   KOK(cx.timed(PC_MISC, 0, [&] {
-    return launch_small_linear(w.xc, (long)N * E, B, E, e->F("conformer.fc5.weight"), e->F("conformer.fc5.bias"), 2,
+    return launch_small_linear(w.xc, (long)N * E, B, E, e->fc5_w, e->fc5_b, 2,
                                logits, s, e->nonfinite + 1);
   }));
   if (embedding)  // x[:, 0, :] (models/conformer_baseline.py:27)
@@ -1710,9 +1763,9 @@ static int kv_trunk(Call& cx, afx_kv* k, const KvForm& f, const float* feats6, i
   const size_t hs = e->hsz, xrow = (size_t)kD * hs, xpad_pitch = (size_t)(Tp + kPosK) * xrow;
   // feature LayerNorm -> operand type
   {
-    RowNormArgs a = plain_norm(feats6, kC, M, kC, e->F("ssl.layer_norm.weight"), e->F("ssl.layer_norm.bias"));
+    RowNormArgs a = plain_norm(feats6, kC, M, kC);
     a.out_h = w.feats_h; a.ldo_h = kC;
-    KOK(cx.rownorm(a, dt));
+    KOK(cx.rownorm(a, e->feat_ln, dt));
   }
   TAP("kv.feats", w.feats_h, (size_t)M * kC, true, kC);
   // positional conv operand: [64 zero rows | 64 cached projected frames | the chunk | 64 zero rows] per row block
@@ -1726,7 +1779,7 @@ static int kv_trunk(Call& cx, afx_kv* k, const KvForm& f, const float* feats6, i
   {
     GemmArgs g = plain_gemm(w.feats_h, kC, e->projw, kC, M, kD, kC);
     g.rpb = n; g.a_batch = (long)n * kC; g.a_row = kC;
-    g.bias = e->F("ssl.post_extract_proj.bias");
+    g.bias = e->proj_b;
     g.out_f = w.x; g.ldo_f = kD; g.o_batch_rows = n;  // the chunk's residual rows, dense (rows, n, 1024)
     g.out_h = w.xpad; g.ldo_h = kD; g.oh_batch_rows = Tp + kPosK; g.oh_row_off = kPosPad + kKvHist;
     KOK(cx.gemm(g, dt, 1));
@@ -1742,7 +1795,7 @@ static int kv_trunk(Call& cx, afx_kv* k, const KvForm& f, const float* feats6, i
   if (!e->s3) {
     PosConvArgs pc;
     memset(&pc, 0, sizeof pc);
-    pc.xpad = xchunk; pc.xpad_batch = (long)(Tp + kPosK) * kD; pc.W = e->posw; pc.bias = e->F("ssl.encoder.pos_conv.0.bias");
+    pc.xpad = xchunk; pc.xpad_batch = (long)(Tp + kPosK) * kD; pc.W = e->posw; pc.bias = e->pos_b;
     pc.x = w.x; pc.B = R; pc.T = n;
     KOK(cx.timed(PC_POSCONV, 2.0 * R * n * kD * (kD / kPosG) * kPosK, [&] { return launch_posconv(pc, dt, s); }));
   } else {  // split precision: the grouped product of run_trunk
@@ -1759,18 +1812,18 @@ static int kv_trunk(Call& cx, afx_kv* k, const KvForm& f, const float* feats6, i
     HIP_OK(hipMemcpy2DAsync(k->hist, kKvHist * xrow, (char*)w.xpad + (size_t)(kPosPad + n) * xrow, xpad_pitch, kKvHist * xrow, R, hipMemcpyDeviceToDevice, s));
   }
   for (int l = 0; l < e->cfg.n_layers; ++l) {
-    const std::string P = "ssl.encoder.layers." + std::to_string(l) + ".";
+    const TrunkLayer& L = e->layers[l];
     void* ring = (char*)k->rings + (size_t)l * k->S * kKvSlots * 3 * kD * hs;
     auto lp = [l](const char* leaf) { return "kv.l" + std::to_string(l) + "." + leaf; };  // (tap names: built only while taps are on)
-    RowNormArgs n1 = plain_norm(w.x, kD, M, kD, e->F(P + "self_attn_layer_norm.weight"), e->F(P + "self_attn_layer_norm.bias"));
+    RowNormArgs n1 = plain_norm(w.x, kD, M, kD);
     n1.out_h = w.hbuf; n1.ldo_h = kD;
-    KOK(cx.rownorm(n1, dt));
+    KOK(cx.rownorm(n1, L.ln1, dt));
     TAP(lp("ln1"), w.hbuf, (size_t)M * kD, true, kD);
     // q | k | v of the chunk go straight into its 16-slot group of the ring (row remap or row table of the epilogue): K / V are
     // cached by being written
-    GemmArgs q = plain_gemm(w.hbuf, kD, e->wqkv[l], kD, M, 3 * kD, kD);
+    GemmArgs q = plain_gemm(w.hbuf, kD, L.wqkv, kD, M, 3 * kD, kD);
     q.rpb = n; q.a_batch = (long)n * kD; q.a_row = kD;
-    q.bias = e->bqkv[l];
+    q.bias = L.bqkv;
     q.out_h = ring; q.ldo_h = 3 * kD;
     if (f.qkv_rows) {
       q.oh_rows = f.qkv_rows;
@@ -1788,25 +1841,25 @@ static int kv_trunk(Call& cx, afx_kv* k, const KvForm& f, const float* feats6, i
       return launch_mhsa_ring(ring, w.att, R, kH, f.ring, dt, s);
     }));
     TAP(lp("att"), w.att, (size_t)R * 16 * kD, true, kD);  // (a 16-row block per row block)
-    GemmArgs o = plain_gemm(w.att, kD, e->wo[l], kD, M, kD, kD);
+    GemmArgs o = plain_gemm(w.att, kD, L.wo, kD, M, kD, kD);
     o.rpb = n; o.a_batch = 16L * kD; o.a_row = kD; o.o_batch_rows = n;
-    o.bias = e->F(P + "self_attn.out_proj.bias"); o.resid = w.x; o.ldr = kD; o.out_f = w.x; o.ldo_f = kD;
+    o.bias = L.bo; o.resid = w.x; o.ldr = kD; o.out_f = w.x; o.ldo_f = kD;
     KOK(cx.gemm(o, dt, 1));
     TAP(lp("mid"), w.x, (size_t)M * kD, false, kD);
-    RowNormArgs n2 = plain_norm(w.x, kD, M, kD, e->F(P + "final_layer_norm.weight"), e->F(P + "final_layer_norm.bias"));
+    RowNormArgs n2 = plain_norm(w.x, kD, M, kD);
     n2.out_h = w.hbuf; n2.ldo_h = kD;
-    KOK(cx.rownorm(n2, dt));
+    KOK(cx.rownorm(n2, L.ln2, dt));
     TAP(lp("ln2"), w.hbuf, (size_t)M * kD, true, kD);
-    GemmArgs f1 = plain_gemm(w.hbuf, kD, e->w1[l], kD, M, kF, kD);
-    f1.bias = e->F(P + "fc1.bias"); f1.act = ACT_GELU; f1.out_h = w.ff; f1.ldo_h = kF;
+    GemmArgs f1 = plain_gemm(w.hbuf, kD, L.w1, kD, M, kF, kD);
+    f1.bias = L.b1; f1.act = ACT_GELU; f1.out_h = w.ff; f1.ldo_h = kF;
     KOK(cx.gemm(f1, dt, 1));
     TAP(lp("ff"), w.ff, (size_t)M * kF, true, kF);
-    GemmArgs f2 = plain_gemm(w.ff, kF, e->w2[l], kF, M, kD, kF);
-    f2.bias = e->F(P + "fc2.bias"); f2.resid = w.x; f2.ldr = kD; f2.out_f = w.x; f2.ldo_f = kD;
+    GemmArgs f2 = plain_gemm(w.ff, kF, L.w2, kF, M, kD, kF);
+    f2.bias = L.b2; f2.resid = w.x; f2.ldr = kD; f2.out_f = w.x; f2.ldo_f = kD;
     KOK(cx.gemm(f2, dt, 1));
     TAP("kv.layer" + std::to_string(l), w.x, (size_t)M * kD, false, kD);
   }
-  RowNormArgs nf = plain_norm(w.x, kD, M, kD, e->F("ssl.encoder.layer_norm.weight"), e->F("ssl.encoder.layer_norm.bias"));
+  RowNormArgs nf = plain_norm(w.x, kD, M, kD);
   if (f.win_next) {
     const size_t frow = (size_t)kD * 4, fpitch = (size_t)kKvFeat * frow;
     HIP_OK(hipMemcpy2DAsync(f.win_next, fpitch, (char*)k->feat[k->pp] + (size_t)n * frow, fpitch, (size_t)(kKvFeat - n) * frow, R, hipMemcpyDeviceToDevice, s));
@@ -1815,7 +1868,7 @@ static int kv_trunk(Call& cx, afx_kv* k, const KvForm& f, const float* feats6, i
     nf.out_f = w.fl; nf.ldo_f = kD;
   }
   nf.nonfinite = e->nonfinite;
-  KOK(cx.rownorm(nf, dt));
+  KOK(cx.rownorm(nf, e->enc_ln, dt));
   if (!f.win_next) TAP("kv.fl", w.fl, (size_t)M * kD, false, kD);  // (lock-step: the rows are the last n of every stream's "kv.win")
   return 0;
 }
@@ -2309,7 +2362,7 @@ extern "C" int afx_head_from_workspace(afx_handle h, int B, int L, float* logits
   Call cx(h, stream, w);
   // split precision: the Conformer head's LL reads the features' operand copy, which the trunk's final LayerNorm wrote as
   // pair-form rows (run_trunk: Call::rownorm).  That was afx_trunk_forward's call; this one starts from what the workspace holds
-  if (cx.s3_ok(w.ssl_h)) cx.s3_set(w.ssl_h, cx.ln_scale(h->F("ssl.encoder.layer_norm.weight")));
+  if (cx.s3_ok(w.ssl_h)) cx.s3_set(w.ssl_h, h->enc_ln.scale);
   return run_head(cx, B, w.T[6], w, logits);
 }
 
@@ -2809,8 +2862,8 @@ extern "C" int afx_k_tile_crop(const float* x, const long long* offs, const long
 extern "C" int afx_k_rownorm(int dtype, const float* x, long ldx, int rows, int C, const float* gamma,
                              const float* beta, float eps, int act, float* out_f, long ldo_f, void* out_h, long ldo_h,
                              void* stream) {
-  RowNormArgs a = plain_norm(x, ldx, rows, C, gamma, beta);
-  a.eps = eps; a.act = act; a.out_f = out_f; a.ldo_f = ldo_f; a.out_h = out_h; a.ldo_h = ldo_h;
+  RowNormArgs a = plain_norm(x, ldx, rows, C);
+  a.gamma = gamma; a.beta = beta; a.eps = eps; a.act = act; a.out_f = out_f; a.ldo_f = ldo_f; a.out_h = out_h; a.ldo_h = ldo_h;
   KRET(launch_rownorm(a, dtype, (hipStream_t)stream));
 }
 extern "C" int afx_k_mhsa(int dtype, const void* qkv, void* out, int B, int T, int H, void* stream) {

@@ -202,6 +202,42 @@ b2 = np.zeros(144, np.float32)
 ok(lib.afx_load_weight(h, b"LL.bias", ptr(b2), (C.c_int64 * 1)(144), 1, None), "raw store, new size")
 fails(lib.afx_finalize(h, None), "missing weight")
 lib.afx_destroy(h)
+
+
+def load_one(h, name, n):
+    a = np.zeros(n, np.float32)
+    ok(lib.afx_load_weight(h, name.encode(), ptr(a), (C.c_int64 * 1)(n), 1, None), "load " + name)
+
+
+# finalize's weight tables: a raw tensor of another length than the launches read is refused, one case per table family
+# (trunk single, transformer layer, Conformer block, Conformer single); the right length loaded over it is accepted again
+h = create(CONF, dtype=3)
+load(h, "conformer")
+for name, n in (("ssl_model.model.post_extract_proj.bias", 1024), ("ssl_model.model.encoder.layers.0.fc1.bias", 4096),
+                ("conformer.encoder_blocks.0.ff1.fn.norm.weight", 144), ("conformer.fc5.bias", 2)):
+    load_one(h, name, n - 1)
+    fails(lib.afx_finalize(h, None), f"weight '{name}' has {n - 1} elements, expected {n}")
+    fails(lib.afx_forward(h, ptr(wave), B, Ls, ptr(logits), ptr(ws_for(16)), 16, None), "not finalized")
+    load_one(h, name, n)
+    ok(lib.afx_finalize(h, None), "finalize after the right length")
+lib.afx_destroy(h)
+
+# reload: load, finalize, forward, then every tensor again from fresh arrays (the vectors loaded with another size in
+# between, so that the store frees and replaces their buffers), finalize, forward -- the tables follow the new buffers
+for arch, prefix in ((AAS, "xlsr_aasist"), (CONF, "conformer")):
+    for dtype in (1, 3):
+        h = create(arch, dtype=dtype)
+        for again in range(2):
+            if again:
+                for k in W.files:
+                    if k.startswith(prefix + "/") and W[k].ndim == 1 and W[k].size > 1 and ".bn1." not in k and "proj.bias" not in k:
+                        load_one(h, k[len(prefix) + 1:], W[k].size + 3)
+            load(h, prefix)
+            ok(lib.afx_finalize(h, None), "finalize")
+            n = lib.afx_workspace_bytes(h, B, Ls)
+            ok(lib.afx_forward(h, ptr(wave), B, Ls, ptr(logits), ptr(ws_for(n)), n, None), "forward")
+        lib.afx_destroy(h)
+
 bad = Config(CONF, 1, 0, 144, 4, 31, 4, 0, 0.97, 0)
 hh = P()
 assert lib.afx_create(C.cast(C.byref(bad), SIGNATURES["afx_create"][1][0]), C.byref(hh)) != 0 and b"at least 1" in lib.afx_last_error()

@@ -11,6 +11,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 SCORE_TOL = 1e-3
+S3_LOGIT_TOL = 1e-5  # split precision ("fp16x3") against fp32: max |delta logit|
 
 
 def rel_l2(a, b):
@@ -164,6 +165,14 @@ def test_errors_are_loud(afx_mod):
     bad = {k: v for k, v in sd.items() if "fc2.bias" not in k}
     with pytest.raises(AfxError, match="missing weight"):
         eng.load_state_dict(bad)
+    # a tensor shorter than what the launches read is refused at finalize, not read past its end
+    short = {k: (v[:4095] if k.endswith("layers.0.fc1.bias") else v) for k, v in sd.items()}
+    with pytest.raises(AfxError, match=r"afx_finalize: weight '.*fc1\.bias' has 4095 elements, expected 4096"):
+        eng.load_state_dict(short)
+    csd = synth.model_state_dict("ConformerModel", n_layers=1, n_encoders=1)
+    short = {k: (v[:143] if k.endswith("blocks.0.ff1.fn.norm.weight") else v) for k, v in csd.items()}
+    with pytest.raises(AfxError, match=r"afx_finalize: weight '.*ff1\.fn\.norm\.weight' has 143 elements, expected 144"):
+        engine.Engine("conformer", n_layers=1, conf_blocks=1).load_state_dict(short)
     eng.load_state_dict(sd)
     with pytest.raises(AfxError, match="too few"):
         eng.ssl(torch.zeros(1, 300, device="cuda"))
@@ -653,7 +662,7 @@ def test_ragged_batch_in_split_precision(afx_mod, arch):
     got = eng.forward_ragged([c.cuda() for c in clips]).cpu()
     for b, c in enumerate(clips):
         assert torch.equal(got[b], eng.forward(c[None].cuda()).cpu()[0]), b
-        assert (got[b] - ofwd(sd, c[None])[0]).abs().max().item() <= 1e-5
+        assert (got[b] - ofwd(sd, c[None])[0]).abs().max().item() <= S3_LOGIT_TOL
 
 
 def test_ragged_bit_identity_holds_across_tile_families(afx_mod):
@@ -780,3 +789,55 @@ def test_group_norm_extractor_mode(afx_mod, dtype, tol):
         eng.ssl_ragged([wave[0].cuda(), wave[1, :20000].cuda()])
     with pytest.raises(Exception, match="missing weight"):
         engine.Engine("ssl", n_layers=2, dtype=dtype, extractor_mode="group_norm").load_state_dict(synth.ssl_state_dict(2))
+
+
+def test_large_layernorm_gain_in_split_precision(afx_mod):
+    """A LayerNorm whose gain is 2048 times the usual: its output bound sqrt(1024) max|gamma| + max|beta| is ~9e4, so with
+    the default pair-form scale 16 the hi half would leave fp16 (65 504) and finalize has to pick 0.5 for this LayerNorm.
+    ``final_layer_norm`` x 2048 with ``fc1.weight`` / 2048 is the same function: the fp16x3 logits are finite and equal
+    the unscaled checkpoint's within the fp16x3-against-fp32 tolerance of this file."""
+    engine, synth = afx_mod
+    sd = synth.model_state_dict("ConformerModel", n_layers=1, n_encoders=1)
+    p = synth.SSL_PREFIX + "encoder.layers.0."
+    big = dict(sd)
+    for k in ("final_layer_norm.weight", "final_layer_norm.bias"):
+        big[p + k] = sd[p + k] * 2048.0
+    big[p + "fc1.weight"] = sd[p + "fc1.weight"] / 2048.0
+    wave = synth.waveforms(2, 16000, batch_idx=411).cuda()
+    out = []
+    for ckpt in (sd, big):
+        eng = engine.Engine("conformer", n_layers=1, dtype="fp16x3", conf_blocks=1)
+        eng.load_state_dict(ckpt)
+        out.append(eng.forward(wave).cpu())
+        eng.check_finite()
+    err = (out[1] - out[0]).abs().max().item()
+    print(f"LayerNorm gain x 2048, fp16x3: max |dlogit| against the unscaled checkpoint {err:.2e}")
+    assert err <= S3_LOGIT_TOL
+
+
+def _second_checkpoint(sd):
+    """Another valid checkpoint of the same shapes: every tensor's elements rotated by one."""
+    return {k: (torch.roll(v.reshape(-1), 1).reshape(v.shape) if v.dtype.is_floating_point else v) for k, v in sd.items()}
+
+
+@pytest.mark.parametrize("arch,dtype", [("conformer", "fp16"), ("conformer", "fp16x3"), ("xlsr_aasist", "fp16")])
+def test_reloaded_engine_equals_a_fresh_one(afx_mod, arch, dtype):
+    """load, finalize, forward; a second checkpoint loaded over the first, finalize, forward: every table finalize fills is
+    rebuilt, so the result is byte-equal to a fresh engine built from the second checkpoint."""
+    engine, synth = afx_mod
+    if arch == "conformer":
+        sd, kw = synth.model_state_dict("ConformerModel", n_layers=1, n_encoders=1), dict(conf_blocks=1)
+    else:
+        sd, kw = synth.model_state_dict("XLSR_AASIST", n_layers=1), {}
+    sd2 = _second_checkpoint(sd)
+    wave = synth.waveforms(2, 16000, batch_idx=412).cuda()
+    eng = engine.Engine(arch, n_layers=1, dtype=dtype, **kw)
+    eng.load_state_dict(sd)
+    first = eng.forward(wave).clone()
+    eng.load_state_dict(sd2)
+    again = eng.forward(wave).clone()
+    fresh = engine.Engine(arch, n_layers=1, dtype=dtype, **kw)
+    fresh.load_state_dict(sd2)
+    want = fresh.forward(wave)
+    assert not torch.equal(first, want)  # (the two checkpoints do differ)
+    assert torch.equal(again, want)
