@@ -853,6 +853,60 @@ int afx_k_evidence_copy(const float* x, const float* scores, int stride, const i
 int afx_k_quality(const float* x, long long stride, int A, int hop, const int* hdr, const float* scores, int sstride,
                   float clip, int clip_count, int flat_run, float e_quiet, float dc, int mask, int max_bad, int abstain,
                   unsigned char* ring, int W, int* state, int* totals, int S, int* meas, float* out, void* stream);
+/* Provenance (afx/provenance.py): which 16 kHz samples the jitter buffer made up, counted per frame and per hop on the
+ * device, and a score that is passed on or replaced by NaN while too much of the model's window is synthetic.
+ * Marks.  E is a slot's played-out stream (afx/jitter.py); C[i] = 1 where released index i was not received (loss-concealed
+ * in any mode, "zero" included, or comfort noise), else 0.  Output sample K of the slot's resampled stream, counted from the
+ * session's origin, has the mark c16[K] = C[floor(K * M / L)] (L / M the slot's up / down ratio; the identity: c16 = C): the
+ * newest input sample of K's filter support, so a release that moves the playout counter from N to N + n_in makes exactly
+ * the outputs whose source lies in [N, N + n_in), and a synthetic run [u, v) of it is the outputs [ceil(u L / M),
+ * ceil(v L / M)).  The mark leads the filter's centre by the resampler's delay (0.6 to 1.25 ms); a count does not care.
+ * Counts.  n[f] = the sum of c16 over the 16 kHz frame f (`frame` samples where a gate stands in the chain, else the whole
+ * hop); a hop's count c = the sum of n over its frames; behind a gate the gated stream's frame counts are the kept frames'
+ * counts, in order, exactly as the samples are compacted.
+ * afx_k_prov_spans: psyn (device, S x ring_len bytes, parallel to a front's pending ring).  rows (device, R x 4 int32) =
+ * slot, wpos, n, value: psyn[slot][(wpos + k) mod ring_len] = value for k < n.  The rows of a launch write disjoint
+ * ranges; max_n >= every n sizes the grid.  A row with a slot outside [0, S), wpos outside [0, ring_len), n outside
+ * [0, ring_len] or a value other than 0 / 1 is skipped whole.  Dword stores between a range's unaligned ends.
+ * afx_k_prov_frames: table (device, R x 2 int32) = slot, head: out[i][f] (device, R x hop / frame int32) = the number of
+ * non-zero bytes among psyn[slot][(head + f frame + k) mod ring_len], k < frame.  One wave per (row, frame), byte loads, a
+ * wave-64 shuffle reduction.  A row with a bad slot or head: its out row is all -1.
+ * afx_k_prov_compact: after a gate launch over A rows of F = n / frame frames (F <= 512).  counts (device, A x F int32, the
+ * frame counts of the rows' hops), mask (device, A x F bytes, the gate launch's mask: bit 0 = kept), hdr (device, A x 2
+ * int32) = slot, wpos (the gate launch's own header: the slot's write position in samples, a multiple of frame).  gsyn
+ * (device, S x ring_frames int32, parallel to the gate's pending ring): the counts of the kept frames, in order, to
+ * gsyn[slot][(wpos / frame + r) mod ring_frames], r = 0, 1, ...  One workgroup per row: an exclusive scan of bit 0, then a
+ * scatter.  A row with a bad slot or wpos, or with a count outside [0, frame], is skipped whole.
+ * afx_k_prov_take: table (device, R x 2 int32) = slot, head (the pop's own table: the ring head in samples, a multiple of
+ * frame): out[i] = the sum of gsyn[slot][(head / frame + k) mod ring_frames], k < per (saturating at 2^31 - 1); -1 for a row
+ * with a bad slot or head, or with a negative entry.  One wave per row.
+ * afx_k_provenance, the layer update.  1 <= W <= 1024 hops of window, 1 <= hop <= 2^24, 0 <= limit <= W * hop (the host's
+ * floor(float64(fp32(max_share)) * W * hop)), abstain 0 / 1.  State per slot: ring (S, W) int32, the count of hop j at
+ * (j - 1) mod W; state (S, 2) int32 = (total, valid), (0, 1) for a new stream; totals (S, 3) int32 saturating at 2^31 - 1 =
+ * hops, synthetic samples, hops that were not valid.  Rows i = 0..A-1, A <= 8192: slot b_i = hdr[i][0] (distinct), hop index
+ * k_i = hdr[i][1] >= 1 (hdr: device, A x 2 int32), c_i = counts[i] in [0, hop] (device, A int32), s_i = scores[i * sstride]
+ * (scores NULL: no scores, no out):
+ *     ring[b][(k - 1) mod W] = c
+ *     total    = the sum of ring[b][(j - 1) mod W] over j in [max(1, k - W + 1), k]   (never before the session's first hop)
+ *     valid    = total <= limit;   state[b] = (min(total, 2^31 - 1), valid)
+ *     totals[b] += (1, c, 1 - valid)
+ *     meas[i]  = (c, min(total, 2^31 - 1), valid)                                      3 int32
+ *     out[i]   = s_i, bit for bit, if valid or abstain == 0, else the quiet NaN 0x7fc00000
+ * A row with a slot outside [0, S), k < 1 or c outside [0, hop] is skipped whole: no state change, meas[i] all -1, out[i] =
+ * s_i.  One thread per row, the recount a loop over at most W entries.
+ * Every entry point: a NULL pointer (scores and its out excepted) or a scalar outside the ranges above (S < 1, rows outside
+ * 1..65535 -- take: 1..262140, provenance: 1..8192 --, a ring longer than 2^30, hop > ring_len, hop % frame != 0, per >
+ * ring_frames, F > ring_frames): non-zero, afx_last_error names `prov_spans` / `prov_frames` / `prov_compact` / `prov_take` /
+ * `provenance`, nothing launched. */
+int afx_k_prov_spans(unsigned char* psyn, int S, int ring_len, const int* rows, int R, int max_n, void* stream);
+int afx_k_prov_frames(const unsigned char* psyn, int S, int ring_len, const int* table, int R, int hop, int frame, int* out,
+                      void* stream);
+int afx_k_prov_compact(const int* counts, const unsigned char* mask, const int* hdr, int A, int F, int frame, int* gsyn, int S,
+                       int ring_frames, void* stream);
+int afx_k_prov_take(const int* gsyn, int S, int ring_frames, const int* table, int R, int per, int frame, int* out,
+                    void* stream);
+int afx_k_provenance(const int* hdr, const int* counts, const float* scores, int sstride, int A, int hop, long long limit,
+                     int abstain, int* ring, int W, int* state, int* totals, int S, int* meas, float* out, void* stream);
 /* Row LayerNorm (+ activation) of fp32 rows: 0 < C <= 1024, C % 4 == 0, any rows >= 1; out_f and / or out_h.  ldx, ldo_f,
  * ldo_h count elements (>= C).  A lane reads and writes 4 columns at a time, so rows must be aligned to that access: x,
  * gamma, beta, out_f 16-byte aligned with ldx % 4 == 0 and ldo_f % 4 == 0; out_h 8-byte aligned (16 for the fp32 operand

@@ -2,12 +2,12 @@
 and the argument checks of the per-slot state classes.
 
 The stack, innermost first (``ORDER``): a streaming scorer (``SlidingWindowScorer`` and its subclasses), the cascade, the
-quality layer, the verdict layer, the evidence layer, the speech gate, the fronts.  Every class carries its kind as
-``layer``.  The one rule: a layer goes around any kind that stands before it in ``ORDER`` -- except a kind named in
+quality layer, the provenance layer, the verdict layer, the evidence layer, the speech gate, the fronts.  Every class
+carries its kind as ``layer``.  The one rule: a layer goes around any kind that stands before it in ``ORDER`` -- except a kind named in
 ``EXACTLY``, which goes around that one kind only (the evidence layer reads the verdict layer's state).  The fronts take
 whatever presents the surface below.
 
-``Layer`` is the base of the five layers between a scorer and the fronts: the surface a layer above drives an inner scorer
+``Layer`` is the base of the six layers between a scorer and the fronts: the surface a layer above drives an inner scorer
 through (``S``, ``device``, ``hop``, ``window``, ``samples_seen``, ``_slot_list``, ``state_meta``), ``reset`` and the session
 moves.  A layer states its ``_meta()``, its state tensors ``_keys`` and the words ``_part`` for a state that lacks them, and
 four hooks: ``_export(idx, st)``, ``_check(state, n)``, ``_import(idx, rows)``, ``_reset(idx)``; and its ``push``.
@@ -20,11 +20,11 @@ import torch
 
 from ._lib import AfxError
 
-ORDER = ("scorer", "cascade", "quality", "verdict", "evidence", "gate", "front")
+ORDER = ("scorer", "cascade", "quality", "provenance", "verdict", "evidence", "gate", "front")
 EXACTLY = {"evidence": "verdict"}
 
 STATE_FORMAT = 1  # StreamState layout version: import_slots refuses any other
-MAX_ROWS = 8192   # rows of one launch of a per-slot state kernel (cascade select, quality, verdict, evidence)
+MAX_ROWS = 8192   # rows of one launch of a per-slot state kernel (cascade select, quality, provenance, verdict, evidence)
 N_MAX = (1 << 31) - 1
 _HOST_KEYS = ("kv_meta", "c6w")  # StreamState tensors that stay on the host whatever ``to`` is given
 
@@ -124,8 +124,9 @@ def sample_cols(seen, window, device):
 
 
 def export_pending(ring, idx, head, fill, width):
-    """-> (n, width) fp32: the pending samples of the slots ``idx`` of a pending ring ((S, ring_len) fp32; ring heads
-    ``head``, ``fill`` samples each: int64 arrays over idx), left-aligned, zeros after."""
+    """-> (n, width), the ring's dtype: the pending samples of the slots ``idx`` of a pending ring ((S, ring_len) fp32, or the
+    uint8 ring of their provenance marks; ring heads ``head``, ``fill`` samples each: int64 arrays over idx), left-aligned,
+    zeros after."""
     dev = ring.device
     with _on(dev):
         j = torch.arange(width)
@@ -228,6 +229,11 @@ class Layer:
     _part = ""          # how a refusal calls a state without them: "the state has no ..."
     _inner_seen = None  # the state tensor that holds the inner sessions' sample counts, where they are not the state's own
 
+    def _state_keys(self, state):
+        """The state tensors of this layer's part that ``state`` must have: ``_keys``, and for a layer with an optional part
+        also that part's keys where the state carries it (a part the layer cannot take is a ValueError here)."""
+        return self._keys
+
     def __init__(self, scorer):
         below, only = getattr(scorer, "layer", None), EXACTLY.get(self.layer)
         if not isinstance(below, str) or below not in ORDER or (
@@ -296,7 +302,7 @@ class Layer:
         same kind of scorer.  Anything else, a state without this layer's part, another number of sessions or rows that
         ``_check`` refuses is a ValueError before anything changes, here or below."""
         idx = self._slot_list(slots, ordered=True)
-        inner = peel(state, self._keys, self._meta(), self._part, seen=self._inner_seen)
+        inner = peel(state, self._state_keys(state), self._meta(), self._part, seen=self._inner_seen)
         if len(state) != len(idx):
             raise ValueError(f"the state holds {len(state)} sessions for {len(idx)} named slots")
         rows = self._check(state, len(state))

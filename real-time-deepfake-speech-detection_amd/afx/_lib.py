@@ -143,6 +143,11 @@ SIGNATURES = {
     "afx_k_evidence_mark": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P]),
     "afx_k_evidence_copy": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _P]),
     "afx_k_quality": (_I, [_P, C.c_longlong, _I, _I, _P, _P, _I, _F, _I, _I, _F, _F, _I, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P]),
+    "afx_k_prov_spans": (_I, [_P, _I, _I, _P, _I, _I, _P]),
+    "afx_k_prov_frames": (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _P]),
+    "afx_k_prov_compact": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _I, _P]),
+    "afx_k_prov_take": (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _P]),
+    "afx_k_provenance": (_I, [_P, _P, _P, _I, _I, _I, C.c_longlong, _I, _P, _I, _P, _P, _I, _P, _P, _P]),
     "afx_k_rownorm": (_I, [_I, _P, _L, _I, _I, _P, _P, _F, _I, _P, _L, _P, _L, _P]),
     "afx_k_mhsa": (_I, [_I, _P, _P, _I, _I, _I, _P]),
     "afx_k_conf_attn": (_I, [_I, _P, _L, _P, _L, _P, _I, _I, _I, _I, _I, _P, _L, _P]),

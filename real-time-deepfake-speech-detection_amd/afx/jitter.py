@@ -158,6 +158,14 @@ refused by a scorer without ``ComfortNoise`` or of another seed.  ``feed_rtp(...
 SSRC-checks datagrams of those payload types (RFC 4733 telephone-events) and drops them.  Out of scope: spectral shaping from
 the CN payload, inferring silence from the RTP marker bit, G.729 / AMR SID frames, per-slot seeds, noise in loss gaps,
 generating CN on a sending side.
+
+Provenance (``afx.provenance``): over a chain that holds a ``ProvenanceScorer``, the scorer keeps ``psyn``, (S, ring_len)
+bytes parallel to the pending ring: 1 where the 16 kHz sample was made up here (a loss part in any mode, or comfort noise).
+Per round the plan gains one ("spans", rows, longest row) op directly after the round's release (more than one where the
+round has more than 65 535 span rows), rows of (slot, wpos, n, value) that partition every release row's output range
+(``afx_k_prov_spans``), and every pop one ``afx_k_prov_frames`` launch
+whose counts are noted to what stands below.  ``export_slots`` adds ``jitter_syn`` (laid out as ``jitter_pending``, uint8).
+Over a chain without the layer nothing of this exists: plans, launches, state keys and bits are what they were.
 """
 import ctypes as C
 from itertools import repeat
@@ -169,6 +177,7 @@ from . import rtp
 from ._layer import StreamState, _on, check_pending, export_pending, import_pending, peel, rows_on, wrap
 from ._lib import JitterLags, JitterRate, call_on, check, lib, ptr
 from .codecs import CODECS
+from .provenance import discover
 from .ingest import (_MAX_SAMPLES, _SAMPLE, _UNIT, ENCODINGS, MAX_FORMATS, _at, _encoding, _format, device_encoding, expand_zone, layout,
                      with_expand)
 from .resample import FILTER_ID, Resampler
@@ -189,6 +198,7 @@ _NAMES = ENCODINGS + CODECS  # what a packet may come in, by the host's number: 
 _HOST_NUMBER = {e: i for i, e in enumerate(_NAMES)}
 _HOST_UNIT = np.array([_UNIT[e] for e in _NAMES], dtype=np.int64)  # bytes a packet is a whole number of, by host number
 NOISE_HDR, NOISE_RATES_HDR = 6, 7  # afx_k_jitter_noise / _noise_rates: slot, column, n, lo32(i0), hi32(i0), level [, rate index]
+SPANS_MAX_ROWS = 65535  # rows of one afx_k_prov_spans launch (include/afx.h): a round's span rows go in ops of at most this many
 CN_STATS = ("comfort", "marks", "marks_late")  # what stats() adds with a ComfortNoise
 _CN_KEYS = ("jitter_cn_marks", "jitter_cn_open", "jitter_cn_stats")  # what export_slots adds with a ComfortNoise
 _CN_COUNTERS = ("comfort", "nmarks", "marks_late")  # jitter_cn_stats columns (CN_STATS order)
@@ -347,7 +357,7 @@ def _merge(ivs, new):
 
 
 class Plan:
-    """What a call will do: ``ops`` (the launches, in order: ("place" | "noise" | "pitch" | "conceal" | "release", int32 rows, largest row) and
+    """What a call will do: ``ops`` (the launches, in order: ("place" | "noise" | "pitch" | "conceal" | "release" | "spans", int32 rows, largest row) and
     ("pop", (A, 2) table, slots)), ``counts`` (hops per named row) and ``book`` (the bookkeeping after it)."""
 
     def __init__(self, ops, slots, counts, book):
@@ -452,6 +462,11 @@ class JitterScorer(_Front):
         if self.Js >= _MAX_SAMPLES:
             raise ValueError("depth + period + fade: less than 2**30 samples")
         self._new_ring(max_pending)
+        # provenance (afx.provenance): with a provenance layer below, (whom the counts of a pop are noted to, the samples of a
+        # frame of those counts, whether that is an attached gate) and the marks of the pending ring's samples; else None
+        self._prov = discover(self)
+        if self._prov is not None:
+            self.psyn = torch.zeros(scorer.S, self.ring_len, dtype=torch.uint8, device=scorer.device)
         self.jring = torch.zeros(scorer.S, self.Js, dtype=torch.float32, device=scorer.device)
         if pitch:  # one gain table per rate, and the period of each slot's open gap (device state: written by the estimate)
             self._fades = [torch.from_numpy(gain_table(int(h), int(f)) if h + f else np.ones(1, np.float32)).to(scorer.device)
@@ -756,6 +771,8 @@ class JitterScorer(_Front):
                                        (head[k] + fill[k]) % R, rate[k] if self._rated else 0)):
                     rows[:, c] = v
                 ops.append(("release", rows, int(n_out.max())))
+                if self._prov is not None:
+                    ops.extend(self._span_rows(k, U[k], (head[k] + fill[k]) % R, cur[k], m[k], made[k], n_out, Lk, Mk, gaps, noise))
                 cur[k] += m[k]
                 fill[k] += n_out
                 progress = True
@@ -769,6 +786,54 @@ class JitterScorer(_Front):
         per_row = np.zeros(slot.size, dtype=np.int64)
         per_row[first] = counts  # a slot named twice: its hops are counted at its first row
         return Plan(ops, U.tolist(), per_row, b)
+
+    def _span_rows(self, k, slot, wpos, cur, m, made, n_out, L, M, gaps, noise):
+        """The ("spans", rows, longest row) ops of a round's release rows (``k``: their positions in U; the other arrays over
+        them; one op, or one per ``SPANS_MAX_ROWS`` rows: a slot's release may be cut into many runs): rows of (slot, wpos, n, value) that partition each release row's outputs [made, made + n_out), written from
+        ring position wpos on, into received runs (0) and synthetic runs (1).  A loss or noise part [u, v) of the released
+        range is the outputs [ceil(u L / M), ceil(v L / M)) (``afx.provenance``); a release with nothing synthetic is one row
+        of zeros."""
+        R = self.ring_len
+        marked = np.array([u in gaps or u in noise for u in k.tolist()], dtype=bool)
+        rows = np.stack([slot, wpos, n_out, np.zeros_like(n_out)], axis=1)[~marked].tolist()
+        for j in np.flatnonzero(marked).tolist():
+            u, c0, c1, l, mm = int(k[j]), int(cur[j]), int(cur[j] + m[j]), int(L[j]), int(M[j])
+            s, w, base, end = int(slot[j]), int(wpos[j]), int(made[j]), int(made[j] + n_out[j])
+            parts = [(g[1], g[2]) for g in gaps.get(u, ())] + [(z[0], z[1]) for z in noise.get(u, ())]
+            at, first = base, len(rows)
+            for lo, hi in sorted((max(lo, c0), min(hi, c1)) for lo, hi in parts):
+                if lo >= hi:
+                    continue
+                o0, o1 = -(-lo * l // mm), -(-hi * l // mm)  # base <= o0 <= o1 <= end
+                if o0 > at:
+                    rows.append((s, (w + at - base) % R, o0 - at, 0))
+                if o1 > o0:
+                    rows.append((s, (w + o0 - base) % R, o1 - o0, 1))
+                at = o1
+            if end > at or len(rows) == first:
+                rows.append((s, (w + at - base) % R, end - at, 0))
+        rows = np.array(rows, dtype=np.int64).reshape(-1, 4).astype(np.int32)
+        return [("spans", part, int(part[:, 2].max())) for part in (rows[i:i + SPANS_MAX_ROWS] for i in range(0, len(rows), SPANS_MAX_ROWS))]
+
+    def _span_launch(self):
+        """The launch of a "spans" op, for a scorer whose provenance lane is on."""
+        if self._prov is None:
+            return {}
+
+        def spans(d, off, op):
+            check(call_on(self.psyn, lib().afx_k_prov_spans, ptr(self.psyn), self.S, self.ring_len, _at(d, off), len(op[1]), op[2]))
+        return {"spans": spans}
+
+    def _note_pop(self, d, off, op):
+        """The popped hops' marks become frame counts (one ``afx_k_prov_frames`` launch over the pop's own table) and are noted
+        to the attached gate, or as one count per hop to the provenance layer."""
+        if self._prov is None:
+            return
+        target, frame, gated = self._prov
+        counts = torch.empty(len(op[2]), self.hop // frame, dtype=torch.int32, device=self.device)
+        check(call_on(self.psyn, lib().afx_k_prov_frames, ptr(self.psyn), self.S, self.ring_len, _at(d, off), len(op[2]), self.hop,
+                      frame, ptr(counts)))
+        target.note_synthetic(counts if gated else counts.view(-1), op[2])
 
     def _commit(self, book):
         self._b = book
@@ -1016,7 +1081,7 @@ class JitterScorer(_Front):
                           ptr(self._amp)))
 
         return self._execute(plan.ops, plan.slots, plan.counts, pay,
-                             {"place": place, "noise": noise, "pitch": pitch, "conceal": conceal, "release": release},
+                             {"place": place, "noise": noise, "pitch": pitch, "conceal": conceal, "release": release, **self._span_launch()},
                              lambda: self._commit(plan.book))
 
     # ---- sessions ----------------------------------------------------------------------------------------------------
@@ -1046,6 +1111,14 @@ class JitterScorer(_Front):
 
     def _cn_meta(self):
         return {} if self.cn is None else dict(jitter_cn=self.cn.seed)
+
+    def _syn_keys(self, state):
+        """What ``peel`` takes of ``state``'s provenance marks.  A state with them is refused by a chain without the layer; a
+        state without them imports with zeros."""
+        has = isinstance(state, StreamState) and "jitter_syn" in state.tensors
+        if has and self._prov is None:
+            raise ValueError("import_slots: the state carries provenance marks (jitter_syn) and this chain has no provenance layer")
+        return ("jitter_syn",) if has else ()
 
     def _cn_part(self, state, mine):
         """What ``peel`` takes of ``state``'s comfort-noise part -> (its state keys, ``mine`` as far as the state must match
@@ -1093,6 +1166,8 @@ class JitterScorer(_Front):
             cstats = np.stack([getattr(b, f)[idx] for f in _CN_COUNTERS], axis=1).reshape(len(idx), len(_CN_COUNTERS))
             more = dict(more, jitter_cn_marks=torch.from_numpy(mt), jitter_cn_open=torch.from_numpy(b.cn_open[idx]),
                         jitter_cn_stats=torch.from_numpy(cstats))
+        if self._prov is not None:
+            more = dict(more, jitter_syn=export_pending(self.psyn, idx, b.head[idx], b.fill[idx], self.max_pending * self.hop))
         return wrap(st, self._meta(), jitter_pending=export_pending(self.ring, idx, b.head[idx], b.fill[idx], self.max_pending * self.hop),
                     jitter_fill=torch.from_numpy(b.fill[idx]), jitter_ring=jr, jitter_book=torch.from_numpy(book),
                     jitter_stats=torch.from_numpy(stats), jitter_intervals=torch.from_numpy(table), **more)
@@ -1104,7 +1179,8 @@ class JitterScorer(_Front):
         with silence marks needs a ``ComfortNoise`` of its seed here; one without them imports with no marks."""
         idx = self.scorer._slot_list(slots, ordered=True)
         keys, mine = self._cn_part(state, self._meta())
-        inner = peel(state, _STATE_KEYS + keys + self._pitch_keys(), mine, "jitter-buffer part (it was not exported by a JitterScorer)")
+        inner = peel(state, _STATE_KEYS + keys + self._pitch_keys() + self._syn_keys(state), mine,
+                     "jitter-buffer part (it was not exported by a JitterScorer)")
         n = len(state)
         width = self.lookback + self.depth
         jr = state.tensors["jitter_ring"]
@@ -1169,12 +1245,19 @@ class JitterScorer(_Front):
             sounds = (gap >= 0) & (nxt - gap < self._rG[rate]) & (True if cn is None else cn[1] < 0)
             if ((pit < 0) | (pit > self._rPmax[rate]) | (sounds & (pit < self._rPmin[rate]))).any():
                 raise ValueError("import_slots: jitter_pitch holds a period outside its rate's lags for a gap younger than hold + fade")
-        return pend, state.tensors["jitter_ring"], fill, col, stats, lists, rate, cn, pit
+        syn = state.tensors.get("jitter_syn")
+        if syn is not None:  # the marks of the pending samples: laid out as jitter_pending, 0 / 1, zeros after the fill
+            if syn.dtype != torch.uint8 or tuple(syn.shape) != tuple(pend.shape):
+                raise ValueError(f"import_slots: jitter_syn {tuple(syn.shape)} {syn.dtype} is not {tuple(pend.shape)} uint8, as jitter_pending")
+            host = syn.cpu()
+            if bool((host > 1).any()) or bool((host * (torch.arange(host.shape[1])[None, :] >= torch.from_numpy(fill)[:, None])).any()):
+                raise ValueError("import_slots: jitter_syn marks a sample more than once, or beyond a session's pending samples")
+        return pend, state.tensors["jitter_ring"], fill, col, stats, lists, rate, cn, pit, syn
 
     def _install(self, idx, inner, checked):
         """The inner scorer imports ``inner`` (it refuses a foreign state before changing anything), then the named slots take
         the checked jitter part: ring columns [next - lookback, ...) at their places modulo each session's own J."""
-        pend, jr, fill, col, stats, lists, rate, cn, pit = checked
+        pend, jr, fill, col, stats, lists, rate, cn, pit, syn = checked
         self.scorer.import_slots(idx, inner)
         if not idx:
             return
@@ -1184,6 +1267,11 @@ class JitterScorer(_Front):
         _, _, J, _, _, depth, lookback = self._geometry(rate)
         own = lookback + depth  # each session's own columns of jitter_ring
         import_pending(self.ring, idx, pend)
+        if self._prov is not None:
+            with _on(dev):
+                self.psyn[rows_on(idx, dev)] = 0
+            if syn is not None:
+                import_pending(self.psyn, idx, syn)
         with _on(dev):
             rows = rows_on(idx, dev)
             self.jring[rows] = 0.0
@@ -1383,7 +1471,7 @@ class MixedJitterScorer(JitterScorer):
                           self.cn.seed, ptr(self._amp)))
 
         return self._execute(plan.ops, plan.slots, plan.counts, pay,
-                             {"place": place, "noise": noise, "pitch": pitch, "conceal": conceal, "release": release},
+                             {"place": place, "noise": noise, "pitch": pitch, "conceal": conceal, "release": release, **self._span_launch()},
                              lambda: self._commit(plan.book))
 
     # ---- sessions --------------------------------------------------------------------------------------------------------
@@ -1431,11 +1519,11 @@ class MixedJitterScorer(JitterScorer):
                         jitter_conceal=self.conceal, jitter_period=int(self._rP[r]), jitter_fade=int(self._rF[r]), **self._cn_meta(),
                         **self._pitch_meta(r))
             keys, mine = self._cn_part(state, mine)
-            inner = peel(state, _STATE_KEYS + keys + self._pitch_keys(), mine, what)
+            inner = peel(state, _STATE_KEYS + keys + self._pitch_keys() + self._syn_keys(state), mine, what)
             ri = np.full(n, r, dtype=np.int64)
         else:
             keys, mine = self._cn_part(state, self._meta())
-            inner = peel(state, _STATE_KEYS + ("jitter_rate", "jitter_params") + keys + self._pitch_keys(), mine, what)
+            inner = peel(state, _STATE_KEYS + ("jitter_rate", "jitter_params") + keys + self._pitch_keys() + self._syn_keys(state), mine, what)
             rates, params = state.tensors["jitter_rate"].cpu().reshape(-1), state.tensors["jitter_params"].cpu()
             width = 4 if self.conceal == "pitch_sync" else 3
             if rates.dtype != torch.int64 or rates.numel() != n or params.dtype != torch.int64 or tuple(params.shape) != (n, width):

@@ -1,0 +1,464 @@
+"""Provenance: the jitter buffer knows which samples it made up, and a stream's score is withheld while too much of the
+model's window is such audio.
+
+``afx.jitter`` writes audio that nobody spoke -- the last 10 ms or the last pitch period repeated, zeros, comfort noise --
+into the window of a model whose job is to flag synthetic speech.  What that does to the false-alarm rate is not measured
+(there is no corpus to measure it with); which samples are ours is known exactly.  This module carries a "made up here" mark,
+one per 16 kHz sample, on the device from the jitter buffer through its pending ring and a speech gate's compaction to a
+layer next to the quality layer: ``ProvenanceScorer(scorer, policy)`` hands on the inner score bit for bit, or the quiet NaN
+("cannot judge", as ``afx.quality`` does for a clipped microphone: the verdict layer raises nothing on it, the evidence layer
+records nothing).
+
+The function (also stated in include/afx.h).
+
+Marks.  E is a slot's played-out stream as ``afx.jitter`` defines it.  C[i] = 1 where released index i was not received: it
+was loss-concealed in any mode, "zero" included, or is comfort noise; else C[i] = 0 (``oracle.jitter.RefSlot.kinds``: C[i] = 1
+where ``kinds[i] != "r"``).
+
+At 16 kHz.  Output sample K of the slot's resampled stream, counted from the session's origin, has the mark
+c16[K] = C[floor(K * M / L)], L / M the slot's up / down ratio (the identity: c16 = C).  This is the newest input sample of
+K's filter support, on purpose: a release that moves the playout counter from N to N + n_in produces exactly the outputs whose
+source lies in [N, N + n_in), and a synthetic run [u, v) of that release is exactly the outputs [ceil(u L / M), ceil(v L / M)),
+so the host needs no history.  The mark LEADS the filter's centre by the resampler's delay, 0.6 to 1.25 ms (``Resampler.delay``
+16 kHz samples): a synthetic sample's energy is centred that much later than its mark.  That does not matter for a count over
+a window of seconds.  ``marks16(kinds, L, M)`` is the statement in numpy.
+
+Per frame, per hop.  n[f] is the sum of c16 over the 16 kHz frame f: ``gate.frame`` samples where a gate stands in the chain,
+otherwise the whole hop.  A hop's count c is the sum of n over its frames.  Behind a gate the gated stream's frame counts are
+the kept frames' counts, in order, exactly as the samples are compacted.
+
+The layer.  ``ProvenancePolicy(max_share=0.05, abstain=True)``; ``W = ceil(window / hop)``, 1 <= W <= 1024;
+``limit = int(floor(float64(fp32(max_share)) * W * hop))``.  Per slot the state is ``p_ring`` ((S, W) int32: the count of hop k
+at (k - 1) mod W), ``p_state`` ((S, 2) int32 = (total, valid); (0, 1) for a new stream) and ``p_totals`` ((S, 3) int32: hops,
+synthetic samples, hops that were not valid -- the scores withheld, or with ``abstain`` off the ones that would have been).
+All counters saturate at 2^31 - 1.  An update names rows (slot (distinct), k >= 1, c in 0..hop, score)::
+
+    p_ring[b, (k-1) mod W] = c
+    total   = the sum of the ring entries of hops max(1, k-W+1)..k          (never before the session's first hop)
+    valid   = total <= limit
+    p_state[b] = (total, valid);  p_totals[b] += (1, c, 1 - valid)
+    meas[i] = (c, total, valid), 3 int32
+    out[i]  = the score, bit for bit, when valid or abstain is off, else the quiet NaN 0x7fc00000
+
+A row with a slot outside [0, S), k < 1 or c outside 0..hop is skipped whole: the state is untouched, its ``meas`` row is -1
+and its score passes.  ``reset`` makes ``p_state`` (0, 1) and clears ``p_totals`` only: the bound k >= 1 keeps a new session
+from reading the ring entries of the one before it (the quality layer's rule, for the same reason).  It is all integer
+arithmetic; the kernel (``afx_k_provenance``, one thread per row) equals ``ProvenancePolicy.step_reference`` exactly.
+
+How the counts travel.  No ``push`` signature changes.  Directly before it pushes a round of hops, whatever stands above
+calls ``note_synthetic(counts, slots)`` on the next object below that takes notes (``note_target``): counts are int32 on
+the device.  The next ``push`` of exactly those slots consumes the note; any other ``push`` raises ValueError, and the note
+is gone.  A ``push`` with no note counts 0 for every row: ``PacketScorer`` and ``ResamplingScorer`` make nothing up and note
+nothing.  At construction a ``JitterScorer`` / ``MixedJitterScorer`` walks the ``.scorer`` links below it (``discover``); with
+a provenance layer there it turns its lane on: a byte ring ``psyn`` (S, ring_len) parallel to its pending ring, one
+("spans", rows) op per round directly after the round's release (rows of (slot, wpos, n, value) that partition every release
+row's output range into received and synthetic runs; ``afx_k_prov_spans``) and at each pop one ``afx_k_prov_frames`` launch
+that turns the popped hops of ``psyn`` into frame counts.  A ``GatedScorer`` with a plain ``SpeechGate`` or a ``ToneGate``
+on the way is attached: it asks its gate launch for the mask, keeps a count ring ``gsyn`` (S, ring_len / frame) int32 parallel
+to its sample ring (``afx_k_prov_compact`` after the gate launch, ``afx_k_prov_take`` at a pop) and notes the hop's sum to
+whatever takes notes below it; its one read-back stays the only one.  A ``LookaheadGate`` (its mask is delayed) or a
+``TurnScorer`` (its mask feeds turn buffers) on the way is refused.  With no provenance layer below, nothing of the front or
+the gate changes in any respect.
+
+Sessions: the layer's part of a ``StreamState`` is ``prov_ring`` ((n, W) int32), ``prov_state`` ((n, 2) int64) and
+``prov_totals`` ((n, 3) int64), meta ``provenance`` (format) and ``provenance_window`` (W and hop); a front whose lane is on
+adds ``jitter_syn`` (laid out as ``jitter_pending``, uint8), an attached gate ``gate_syn`` ((n, hop / frame) int64, -1 after
+the fill).  Rows that cannot be a session's are refused: a count above ``frame`` or ``hop``, a total that is not the ring's
+sum, a flag counted more often than hops.  A state without the front's or the gate's part imports with zeros; one with them
+is refused by a chain without the layer.  The ring holds counts, so ``max_share`` and ``abstain`` may differ where a session
+goes (``valid`` is set under the importing policy's limit, so a state whose new streams carry (0, 0) imports as well).
+
+Out of scope: ``LookaheadGate``; ``TurnScorer``, offline timelines and turns; per-sample marks into evidence clips; tuned
+thresholds (0.05 is an engineering default: there is no labelled corpus behind it); the filter-delay offset of the mark.
+"""
+import numpy as np
+import torch
+
+from ._layer import N_MAX, Layer, _on, fp32, hop_indices, need_gpu, slot_count, slots_of, upload_pairs
+from ._lib import call_on, check, lib, ptr
+from .quality import MAX_HOP, QNAN_BITS, window_hops
+
+PROVENANCE_FORMAT = 1  # layout of the provenance part of a StreamState: import_slots refuses any other
+MAX_FRAMES = 512       # frames of a hop behind an attached gate (one afx_k_prov_compact workgroup)
+
+
+def marks16(kinds, L, M):
+    """c16 of a played-out stream: ``kinds`` (``oracle.jitter.RefSlot.kinds``, or any sequence that is "r" where the index
+    was received) at the up / down ratio L / M -> (ceil(len * L / M),) uint8, c16[K] = C[floor(K * M / L)]."""
+    C = np.fromiter((k != "r" for k in kinds), dtype=np.uint8, count=len(kinds))
+    K = np.arange(-(-len(kinds) * L // M), dtype=np.int64)
+    return C[K * M // L]
+
+
+class ProvenanceState:
+    """Host mirrors of the whole provenance state of S slots: ``ring`` (S, W) int32, ``st`` (S, 2) int32 = (total, valid),
+    ``totals`` (S, 3) int32; a new stream everywhere."""
+
+    def __init__(self, S, W):
+        self.ring = np.zeros((S, W), dtype=np.int32)
+        self.st = np.zeros((S, 2), dtype=np.int32)
+        self.st[:, 1] = 1
+        self.totals = np.zeros((S, 3), dtype=np.int32)
+
+    def reset(self, slots):
+        """What ``Provenance.reset`` does: ``st`` = (0, 1) and ``totals`` cleared, the ring left alone."""
+        self.st[slots] = (0, 1)
+        self.totals[slots] = 0
+
+    def copy(self):
+        c = ProvenanceState(*self.ring.shape)
+        c.ring, c.st, c.totals = self.ring.copy(), self.st.copy(), self.totals.copy()
+        return c
+
+
+class ProvenancePolicy:
+    """When a stream's score is withheld: while more than ``max_share`` (0..1, rounded to fp32 once) of the samples of the
+    last ``W`` hops were made up by the jitter buffer.  abstain=False: count only, every score passes.  0.05 is an engineering
+    default, not a tuned one."""
+
+    def __init__(self, max_share=0.05, abstain=True):
+        self.share32 = fp32("max_share", max_share, False)
+        if self.share32 > 1:
+            raise ValueError(f"max_share {max_share!r}: 0 to 1")
+        if not isinstance(abstain, (bool, np.bool_)):
+            raise ValueError(f"abstain: True or False, got {abstain!r}")
+        self.max_share, self.abstain = float(self.share32), bool(abstain)
+
+    def params(self):
+        """What identifies this policy (a float and a bool)."""
+        return dict(max_share=self.max_share, abstain=self.abstain)
+
+    def limit(self, W, hop):
+        """The synthetic samples a window of W hops of ``hop`` samples may hold: floor(float64(fp32(max_share)) * W * hop)."""
+        return int(np.floor(np.float64(self.share32) * W * hop))
+
+    # ---- the numpy restatement -------------------------------------------------------------------------------------------
+    def step_reference(self, slots, counts, hop_index, scores, state, hop):
+        """One update in numpy.  slots (A,) distinct ints, counts (A,) ints, hop_index an int or (A,) ints, scores (A,) fp32
+        or None, hop the samples of a hop; ``state`` (a ``ProvenanceState`` of the whole scorer) is UPDATED IN PLACE -> ``(out,
+        meas)``: (A,) float32 or None, and (A, 3) int32.  A row with ``hop_index < 1`` or a count outside 0..hop is skipped
+        whole as the kernel skips it (its meas row is -1, its score passes)."""
+        if not isinstance(state, ProvenanceState):
+            raise ValueError("state: a ProvenanceState")
+        S, W = state.ring.shape
+        b = slots_of(slots, S)
+        A = b.size
+        c = np.asarray(counts)
+        if c.dtype == bool or (c.size and not np.issubdtype(c.dtype, np.integer)) or c.ndim != 1 or c.size != A:
+            raise ValueError("counts: one integer per named slot")
+        c = c.astype(np.int64)
+        if isinstance(hop, bool) or not isinstance(hop, (int, np.integer)) or not 1 <= hop <= MAX_HOP:
+            raise ValueError(f"hop {hop!r}: 1 to {MAX_HOP}")
+        k = hop_indices(hop_index, A).copy()
+        s_in = None if scores is None else np.asarray(scores, dtype=np.float32).reshape(-1).copy()
+        if s_in is not None and s_in.size != A:
+            raise ValueError("slots, counts, hop_index and scores name the same rows")
+        limit = self.limit(W, int(hop))
+        meas = np.full((A, 3), -1, dtype=np.int32)
+        out = None if s_in is None else s_in.copy()
+        live = np.flatnonzero((k >= 1) & (c >= 0) & (c <= hop))
+        if not live.size:
+            return out, meas
+        b, k, c = b[live], k[live], c[live]
+        state.ring[b, (k - 1) % W] = c.astype(np.int32)
+        i = np.arange(W, dtype=np.int64)[None, :]
+        inside = i < np.minimum(k, W)[:, None]                  # hops k, k-1, ..: never before the session's first
+        entries = state.ring[b[:, None], (k[:, None] - 1 - i) % W].astype(np.int64)
+        total = (entries * inside).sum(axis=1)
+        valid = total <= limit
+        state.st[b] = np.stack([np.minimum(total, N_MAX), valid], axis=1).astype(np.int32)
+        tot = state.totals[b].astype(np.int64)
+        tot += np.stack([np.ones_like(c), c, 1 - valid.astype(np.int64)], axis=1)
+        state.totals[b] = np.minimum(tot, N_MAX).astype(np.int32)
+        meas[live] = np.stack([c, np.minimum(total, N_MAX), valid], axis=1).astype(np.int32)
+        if out is not None and self.abstain:
+            out.view(np.int32)[live[~valid]] = QNAN_BITS
+        return out, meas
+
+    def run_reference(self, counts, hop, window):
+        """One fresh stream, hop by hop: counts (n,) ints, the synthetic samples of each hop -> ``(meas (n, 3) int32, valid
+        (n,) bool)``: the measurement of every hop and whether the stream's score passes after it (a skipped hop passes)."""
+        c = np.asarray(counts).reshape(-1)
+        st = ProvenanceState(1, window_hops(window, hop))
+        meas = np.zeros((c.size, 3), dtype=np.int32)
+        for j in range(c.size):
+            meas[j] = self.step_reference([0], c[j:j + 1], j + 1, None, st, hop)[1][0]
+        return meas, meas[:, 2] != 0
+
+
+class Provenance:
+    """The per-slot provenance state of ``S`` streams under ``policy`` for hops of ``hop`` samples and a window of ``window``
+    samples, on ``device``; see the module docstring.  ``update`` is one pinned upload of the header and one
+    ``afx_k_provenance`` launch, with no synchronisation; ``valid`` and ``synthetic`` are views of the state on the device;
+    ``stats()`` is the only read-back."""
+
+    def __init__(self, S, policy, hop, window, device="cuda"):
+        S = slot_count(S, policy, ProvenancePolicy)
+        self.W = window_hops(window, hop)
+        self.S, self.policy, self.hop, self.window = S, policy, int(hop), int(window)
+        self.limit = policy.limit(self.W, self.hop)
+        self.ring = torch.zeros(self.S, self.W, dtype=torch.int32, device=device)
+        self.device = self.ring.device  # (with its index: every launch of an update goes to THIS GPU)
+        self.st = torch.zeros(self.S, 2, dtype=torch.int32, device=self.device)
+        self.st[:, 1] = 1
+        self.totals = torch.zeros(self.S, 3, dtype=torch.int32, device=self.device)
+
+    @property
+    def synthetic(self):
+        """(S,) int32 on the device: the synthetic samples in each slot's window."""
+        return self.st[:, 0]
+
+    @property
+    def valid(self):
+        """(S,) bool on the device: which slots' scores pass (``total <= limit``; a new stream is valid)."""
+        return self.st[:, 1] != 0
+
+    def stats(self):
+        """Per slot, since its last ``reset``: (S,) int64 host tensors ``hops``, ``synthetic`` (samples) and ``withheld`` (the
+        hops that were not valid).  Reads ``p_totals`` back: the only read-back of this layer."""
+        t = self.totals.to("cpu", torch.int64)
+        return dict(hops=t[:, 0].clone(), synthetic=t[:, 1].clone(), withheld=t[:, 2].clone())
+
+    def update(self, counts, slots=None, *, hop_index, scores=None):
+        """counts: (A,) int32 on the device, row i the synthetic samples of the hop of slot slots[i] (None: every slot, in
+        order; the slots are distinct); hop_index: an int or (A,) ints on the host, 1 or more; scores: (A,) fp32 on the device
+        (any stride) or None -> ``(out, meas)`` on the device: (A,) fp32 or None, (A, 3) int32.  One pinned upload, one launch,
+        no synchronisation."""
+        b = slots_of(slots, self.S)
+        A = b.size
+        if (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or counts.shape != (A,)
+                or counts.device != self.device):
+            raise ValueError(f"counts: an int32 tensor of shape {(A,)} on {self.device}")
+        k = hop_indices(hop_index, A, 1)
+        if scores is not None and (not isinstance(scores, torch.Tensor) or scores.dtype != torch.float32 or scores.shape != (A,)
+                                   or scores.device != self.device):
+            raise ValueError(f"scores: an fp32 tensor of shape {(A,)} on {self.device}")
+        if not A:
+            empty = torch.empty(0, dtype=torch.float32, device=self.device)
+            return (None if scores is None else empty), torch.empty(0, 3, dtype=torch.int32, device=self.device)
+        return self._update(counts.contiguous(), b, k, scores)
+
+    def _update(self, counts, slots, hop_index, scores):
+        need_gpu(self.device, "hops are counted")
+        A = len(slots)
+        if scores is not None and A > 1 and scores.stride(0) < 1:
+            scores = scores.contiguous()
+        with torch.cuda.device(self.device):
+            d = upload_pairs(slots, hop_index, self.device)
+            meas = torch.empty(A, 3, dtype=torch.int32, device=self.device)
+            out = None if scores is None else torch.empty(A, dtype=torch.float32, device=self.device)
+            check(call_on(self.ring, lib().afx_k_provenance, ptr(d), ptr(counts), ptr(scores),
+                          1 if scores is None else max(scores.stride(0), 1), A, self.hop, self.limit, int(self.policy.abstain),
+                          ptr(self.ring), self.W, ptr(self.st), ptr(self.totals), self.S, ptr(meas), ptr(out)))
+        return out, meas
+
+    # ---- sessions ------------------------------------------------------------------------------------------------------------
+    def reset(self, slots):
+        """The named slots begin a new stream: ``p_state = (0, 1)`` and ``p_totals = 0``.  The ring is left alone: a new
+        session's window sum never reaches back before its first hop."""
+        b = slots_of(slots, self.S)
+        if b.size:
+            with _on(self.device):
+                rows = torch.from_numpy(b).to(self.device)
+                self.st[rows] = torch.tensor([0, 1], dtype=torch.int32, device=self.device)
+                self.totals[rows] = 0
+
+    def export_rows(self, slots):
+        """-> (prov_ring (n, W) int32 on the device, prov_state (n, 2) and prov_totals (n, 3) int64 on the host) of the named
+        slots."""
+        with _on(self.device):
+            rows = torch.from_numpy(slots_of(slots, self.S)).to(self.device)
+            return self.ring[rows].clone(), self.st[rows].to("cpu", torch.int64), self.totals[rows].to("cpu", torch.int64)
+
+    def check_rows(self, ring, st, totals, seen, n):
+        """Refuses (ValueError) what cannot be the state of n sessions of this window that have seen ``seen`` (n,) samples; ->
+        (ring, st, totals), ``valid`` set under THIS policy's limit."""
+        if not isinstance(ring, torch.Tensor) or ring.dtype != torch.int32 or tuple(ring.shape) != (n, self.W):
+            raise ValueError(f"import_slots: prov_ring is {(n, self.W)} int32")
+        if not isinstance(st, torch.Tensor) or st.dtype != torch.int64 or tuple(st.shape) != (n, 2):
+            raise ValueError("import_slots: prov_state is (n, 2) int64")
+        if not isinstance(totals, torch.Tensor) or totals.dtype != torch.int64 or tuple(totals.shape) != (n, 3):
+            raise ValueError("import_slots: prov_totals is (n, 3) int64")
+        st, totals, r = st.cpu().clone(), totals.cpu(), ring.cpu().to(torch.int64)
+        if bool(((r < 0) | (r > self.hop)).any()):
+            raise ValueError(f"import_slots: a hop counts more synthetic samples than its {self.hop} (or fewer than 0)")
+        k = torch.as_tensor(seen, dtype=torch.int64).reshape(-1) // self.hop
+        i = torch.arange(self.W)[None, :]
+        inside = i < k.clamp(max=self.W)[:, None]
+        total = (r.gather(1, (k[:, None] - 1 - i) % self.W) * inside).sum(dim=1)
+        if bool((st[:, 0] != total.clamp(max=N_MAX)).any()):
+            raise ValueError("import_slots: a session's synthetic total is not the sum of its window's ring entries")
+        if bool(((st[:, 1] != 0) & (st[:, 1] != 1)).any()):
+            raise ValueError("import_slots: a session's valid flag is 0 or 1")
+        if bool(((totals < 0) | (totals > N_MAX)).any()) or bool((totals[:, 2] > totals[:, 0]).any()):
+            raise ValueError("import_slots: a session's totals are negative, or hops were withheld more often than hops were seen")
+        st[:, 1] = (total <= self.limit).to(torch.int64)
+        return ring, st, totals
+
+    def import_rows(self, slots, ring, st, totals):
+        """The named slots take the (checked) state rows."""
+        b = slots_of(slots, self.S)
+        if b.size:
+            with _on(self.device):
+                rows = torch.from_numpy(b).to(self.device)
+                self.ring[rows] = ring.to(self.device)
+                self.st[rows] = st.to(self.device, torch.int32)
+                self.totals[rows] = totals.to(self.device, torch.int32)
+
+
+def note_target(scorer):
+    """The next object at or below ``scorer`` (along the ``.scorer`` links) that takes notes, or None."""
+    while scorer is not None and not callable(getattr(scorer, "note_synthetic", None)):
+        scorer = getattr(scorer, "scorer", None)
+    return scorer
+
+
+def discover(front):
+    """What a jitter front does at construction: walks the ``.scorer`` links below it; with no provenance layer there ->
+    None and nothing changes.  With one: a ``GatedScorer`` with a plain ``SpeechGate`` or a ``ToneGate`` on the way is
+    attached, a ``LookaheadGate`` or a ``TurnScorer`` (any other object of kind "gate") on the way is a ValueError -> (the
+    object the front notes its counts to, the samples of a frame of those counts, whether that object is an attached gate)."""
+    from .vad import GatedScorer, LookaheadGate
+    chain, s = [], getattr(front, "scorer", None)
+    while s is not None:
+        chain.append(s)
+        s = getattr(s, "scorer", None)
+    if not any(getattr(s, "layer", None) == "provenance" for s in chain):
+        return None
+    gated = None
+    for s in chain:
+        if getattr(s, "layer", None) == "provenance":
+            break
+        if getattr(s, "layer", None) == "gate":
+            if not isinstance(s, GatedScorer) or isinstance(s.gate, LookaheadGate):
+                what = "LookaheadGate (its mask is delayed)" if isinstance(s, GatedScorer) else f"{type(s).__name__} (its mask feeds turn buffers)"
+                raise ValueError(f"a jitter front over a provenance layer: a {what} on the way is out of scope")
+            if s.hop // s.gate.frame > MAX_FRAMES:
+                raise ValueError(f"a jitter front over a provenance layer: a hop of at most {MAX_FRAMES} gate frames")
+            gated = s
+    if gated is not None:
+        gated._attach_provenance()
+        return gated, gated.gate.frame, True
+    return note_target(front.scorer), front.scorer.hop, False
+
+
+class ProvenanceScorer(Layer):
+    """``scorer`` (a streaming scorer, a cascade or a quality layer) with the provenance layer behind it under ``policy``;
+    see the module docstring.  It goes where the quality layer goes, around it and inside the verdict layer:
+    ``JitterScorer(GatedScorer(VerdictScorer(ProvenanceScorer(QualityScorer(inner, qpolicy), ppolicy), vpolicy)), 8000,
+    "mulaw", depth)``.
+
+    ``push`` runs the inner ``push``, then one update with the counts of the note it holds (``note_synthetic``; none: zeros)
+    and ``hop_index = samples_seen // hop`` (one small upload, one launch, no synchronisation) and returns ``out``: the inner
+    scores, bit for bit, with the quiet NaN where the slot is not valid (a KV-cached ``None`` stays ``None``; the hop is counted
+    all the same).
+
+    Results, all on the device: ``last_meas`` ((A, 3) int32 = (c, total, valid), the rows of the newest push), ``valid`` ((S,)
+    bool), ``synthetic`` ((S,) int32, the window totals).  ``stats()`` is the only read-back.  Around a cascade ``verified``,
+    ``verified_at`` and ``take_events`` are the cascade's, and with ``abstain`` on ``last_verified()`` has NaN for the
+    verifier scores of the slots that are not valid."""
+
+    layer = "provenance"
+    _keys = ("prov_ring", "prov_state", "prov_totals")
+    _part = "provenance part (it was not exported by a ProvenanceScorer)"
+
+    def __init__(self, scorer, policy=None):
+        super().__init__(scorer)
+        self.policy = ProvenancePolicy() if policy is None else policy
+        self.provenance = Provenance(scorer.S, self.policy, scorer.hop, scorer.window, scorer.device)
+        self.last_meas = torch.empty(0, 3, dtype=torch.int32, device=self.provenance.device)
+        self._cascade = self._below("cascade") is not None  # (then what stands directly below hands the verifier scores on)
+        self._last = None  # (slots, verifier scores with the invalid slots' made NaN) of the newest push
+        self._note = None  # (slots, counts) for the next push
+
+    @property
+    def valid(self):
+        return self.provenance.valid
+
+    @property
+    def synthetic(self):
+        return self.provenance.synthetic
+
+    def stats(self):
+        """``Provenance.stats``."""
+        return self.provenance.stats()
+
+    # (around a cascade: its results, for the caller and for the verdict layer)
+    @property
+    def verified(self):
+        return self.scorer.verified
+
+    @property
+    def verified_at(self):
+        return self.scorer.verified_at
+
+    def take_events(self):
+        """``CascadeScorer.take_events`` (the verifier scores as the verifier gave them)."""
+        return self.scorer.take_events()
+
+    def last_verified(self):
+        """``CascadeScorer.last_verified`` of the newest push; with ``abstain`` on, the verifier scores of the slots that
+        are not valid are NaN."""
+        return self._last
+
+    def note_synthetic(self, counts, slots):
+        """counts: (A,) int32 on the scorer's device, the synthetic samples of the hop the next ``push`` brings for each of
+        ``slots`` (in its row order).  The next ``push`` must name exactly these slots; it consumes the note."""
+        idx = self._named(slots)
+        dev = self.provenance.device
+        if not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or counts.shape != (len(idx),) or counts.device != dev:
+            raise ValueError(f"counts: an int32 tensor of shape {(len(idx),)} on {dev}")
+        self._note = (idx, counts)
+
+    def push(self, chunk, slots=None):
+        """chunk and slots: the inner scorer's own rule (an fp32 chunk on the scorer's GPU) -> the inner scores with NaN
+        where the slot's score is withheld, ``None`` where the inner ``push`` returned ``None``."""
+        need_gpu(self.device, "hops are scored and counted")
+        inner, dev = self.scorer, self.provenance.device
+        idx = self._named(slots)
+        A = len(idx)
+        note, self._note = self._note, None
+        if note is not None and note[0] != idx:
+            raise ValueError(f"the note names the slots {note[0]}, this push {idx}: a note is for the next push of exactly its slots")
+        if not isinstance(chunk, torch.Tensor) or chunk.device != dev or chunk.dtype != torch.float32 or chunk.shape != (A, self.hop):
+            raise ValueError(f"expected a CUDA fp32 tensor of shape {(A, self.hop)} on {dev} (one hop per named slot)")
+        self._last = None
+        scores = inner.push(chunk, slots)
+        if not A:
+            return scores
+        if scores is not None and (scores.shape != (A,) or scores.device != dev):
+            raise RuntimeError(f"the inner scorer returned {tuple(scores.shape)} scores on {scores.device} for {A} rows")
+        if scores is not None and scores.dtype != torch.float32:
+            scores = scores.to(torch.float32)
+        with torch.cuda.device(dev):
+            counts = torch.zeros(A, dtype=torch.int32, device=dev) if note is None else note[1]
+        out, self.last_meas = self.provenance.update(counts, idx, hop_index=(inner.samples_seen[idx] // self.hop).numpy(), scores=scores)
+        # what stands directly below (the cascade, or a quality layer that has made its own invalid slots' NaN), then this
+        # layer's NaN on top: the verdict layer reads ``last_verified`` of what is directly below IT
+        last = inner.last_verified() if self._cascade else None
+        if last is not None and self.policy.abstain:
+            chosen, v = last
+            with torch.cuda.device(dev):
+                rows = torch.empty(chosen.numel(), dtype=torch.int64, pin_memory=True)
+                rows.copy_(chosen)
+                ok = self.provenance.valid.index_select(0, rows.to(dev, non_blocking=True))
+                last = (chosen, torch.where(ok, v, torch.full_like(v, float("nan"))))
+        self._last = last
+        return out
+
+    # ---- sessions (afx._layer.Layer) -----------------------------------------------------------------------------------------
+    def _meta(self):
+        return dict(provenance=PROVENANCE_FORMAT, provenance_window=dict(W=self.provenance.W, hop=self.hop))
+
+    def _reset(self, idx):
+        self.provenance.reset(idx)
+
+    def _export(self, idx, st):
+        ring, state, totals = self.provenance.export_rows(idx)
+        return dict(prov_ring=ring, prov_state=state, prov_totals=totals)
+
+    def _check(self, state, n):
+        return self.provenance.check_rows(*(state.tensors[k] for k in self._keys), state.seen, n)
+
+    def _import(self, idx, rows):
+        self.provenance.import_rows(idx, *rows)

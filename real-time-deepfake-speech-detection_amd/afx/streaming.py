@@ -211,6 +211,10 @@ class _Front:
             rounds += 1
         return rounds
 
+    def _note_pop(self, d, off, op):
+        """Issuing: what a front tells the objects below about the round of hops it is about to push (d: the uploaded buffer,
+        off: the byte offset of the pop's table in it).  Nothing, unless the front has something to say (``afx.provenance``)."""
+
     _SRC = {"ingest": 1, "place": 1}  # the int of a row that says at which byte of the buffer its samples are read
 
     @staticmethod
@@ -286,6 +290,7 @@ class _Front:
                 chunk = torch.empty(len(op[2]), self.hop, dtype=torch.float32, device=dev)
                 check(call_on(self.ring, lib().afx_k_ingest_pop, ptr(self.ring), self.S, self.ring_len, _at(d, off), len(op[2]),
                               self.hop, ptr(chunk)))
+                self._note_pop(d, off, op)
                 sc = self.scorer.push(chunk, op[2])
                 if sc is None:
                     raise RuntimeError("the inner scorer emitted no score for a hop")

@@ -576,7 +576,13 @@ class GatedScorer(Layer):
     ``last_tone_frames`` the (A,) int32 device tensor of the newest push's tone frames, in its row order (None with the
     other gates).  A session's part then gains ``gate_tone`` ((n, 3) int64: r, q, tones); a negative r, a q outside
     0..hold, ``r >= confirm`` with ``q != hold`` and a tones count that is negative or above the frames the session has seen
-    are refused.  A tone state and a plain or look-ahead state refuse each other (``gate_params``, ``gate_tone``)."""
+    are refused.  A tone state and a plain or look-ahead state refuse each other (``gate_params``, ``gate_tone``).
+
+    Provenance (``afx.provenance``): a jitter front over a provenance layer attaches a plain or a tone gate on its way.  An
+    attached gate takes the frame counts of the next push (``note_synthetic``), asks its gate launch for the mask (otherwise
+    NULL, as ever), compacts the kept frames' counts into ``gsyn`` ((S, ring_len / frame) int32, ``afx_k_prov_compact``), sums
+    a popped hop's entries (``afx_k_prov_take``) and notes them to what takes notes below; a session's part gains ``gate_syn``
+    ((n, hop / frame) int64, the pending frames' counts, -1 after the fill).  A gate that is not attached does none of this."""
 
     layer = "gate"
     _keys = ("gate_pending", "gate_fill", "gate_hang", "gate_inner_seen", "gate_nf")
@@ -608,6 +614,28 @@ class GatedScorer(Layer):
         self._extra = gate._new_extra(S, self.ring_len, dev)
         for name, t in self._extra.items():
             setattr(self, name, t)
+        self._syn = False  # (afx.provenance: a jitter front over a provenance layer attaches this gate)
+
+    # ---- provenance (afx.provenance) ---------------------------------------------------------------------------------------
+    def _attach_provenance(self):
+        """A jitter front found a provenance layer below this gate: from now on the gate launch writes its mask, and ``gsyn``
+        ((S, ring_len / frame) int32, parallel to the sample ring) holds the synthetic samples of every kept frame."""
+        if not self._syn:
+            from .provenance import note_target
+            self._syn, self._syn_note, self._syn_below = True, None, note_target(self.scorer)
+            self.gsyn = torch.zeros(self.S, self.ring_len // self.gate.frame, dtype=torch.int32, device=self.device)
+
+    def note_synthetic(self, counts, slots):
+        """counts: (A, hop / frame) int32 on the scorer's device, the synthetic samples of every frame of the hop the next
+        ``push`` brings for each of ``slots`` (in its row order).  The next ``push`` must name exactly these slots; it
+        consumes the note.  Only an attached gate takes notes."""
+        if not self._syn:
+            raise ValueError("this gate is not attached to a provenance layer (a jitter front over one attaches it)")
+        idx = self._named(slots)
+        shape = (len(idx), self.hop // self.gate.frame)
+        if not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or counts.shape != shape or counts.device != self.ring.device:
+            raise ValueError(f"counts: an int32 tensor of shape {shape} on {self.ring.device}")
+        self._syn_note = (idx, counts.contiguous())
 
     @property
     def samples_seen(self):
@@ -643,6 +671,11 @@ class GatedScorer(Layer):
         if not isinstance(chunk, torch.Tensor) or not chunk.is_cuda or chunk.dtype != torch.float32 or chunk.shape != (A, hop):
             raise ValueError(f"expected a CUDA fp32 tensor of shape {(A, hop)} (one hop per named slot)")
         la, frame = self._la, self.gate.frame
+        note = None
+        if self._syn:
+            note, self._syn_note = self._syn_note, None
+            if note is not None and note[0] != idx:
+                raise ValueError(f"the note names the slots {note[0]}, this push {idx}: a note is for the next push of exactly its slots")
         if not A:
             if la:
                 self.last_span = torch.empty(0, 2, dtype=torch.int64, device=dev)
@@ -656,7 +689,12 @@ class GatedScorer(Layer):
         with torch.cuda.device(dev):
             kept = torch.empty(A, dtype=torch.int32, device=dev)
             hdr = self.gate._header(slot, (head + fill) % self.ring_len, self._seen[slot], dev)
-            self.last_tone_frames = self.gate._launch(chunk.to(dev).contiguous(), hdr, self.nf, self.h, self.ring, kept, self._extra)
+            mask = torch.empty(A, hop // frame, dtype=torch.uint8, device=dev) if self._syn else None
+            self.last_tone_frames = self.gate._launch(chunk.to(dev).contiguous(), hdr, self.nf, self.h, self.ring, kept, self._extra, mask)
+            if self._syn:  # the kept frames' counts, in order, at the slot's write position in frames (hdr: the gate launch's own)
+                counts = torch.zeros(A, hop // frame, dtype=torch.int32, device=dev) if note is None else note[1]
+                check(call_on(self.gsyn, lib().afx_k_prov_compact, ptr(counts), ptr(mask), ptr(hdr), A, hop // frame, frame,
+                              ptr(self.gsyn), self.S, self.ring_len // frame))
             if la:
                 span = torch.full((A, 2), -1, dtype=torch.int64, device=dev)
             host = torch.empty(A, dtype=torch.int32, pin_memory=True)
@@ -681,6 +719,11 @@ class GatedScorer(Layer):
                 check(call_on(self.ring, lib().afx_k_ingest_pop, ptr(self.ring), self.S, self.ring_len, ptr(d), R, hop, ptr(ready)))
                 self._head[slot[rows]] = (head[rows] + hop) % self.ring_len
                 self._fill[slot[rows]] = fill[rows] - hop
+                if self._syn and self._syn_below is not None:  # the popped hops' sums, from the pop's own table
+                    took = torch.empty(R, dtype=torch.int32, device=dev)
+                    check(call_on(self.gsyn, lib().afx_k_prov_take, ptr(self.gsyn), self.S, self.ring_len // frame, ptr(d), R,
+                                  hop // frame, frame, ptr(took)))
+                    self._syn_below.note_synthetic(took, slot[rows].tolist())
                 sc = self.scorer.push(ready, slot[rows].tolist())
                 if sc is None:
                     raise RuntimeError("the inner scorer emitted no score for a hop")
@@ -729,7 +772,23 @@ class GatedScorer(Layer):
                 part.update(self._export_line(idx, rows))
             if self._tone:
                 part["gate_tone"] = self.tone_state[rows].to("cpu", torch.int64)
+            if self._syn:  # the pending frames' synthetic samples, oldest first, -1 after the fill
+                per = self.hop // self.gate.frame
+                j = np.arange(per)
+                ent = (self._head[idx][:, None] // self.gate.frame + j) % (self.ring_len // self.gate.frame)
+                syn = self.gsyn[rows[:, None], torch.from_numpy(ent).to(self.device)].to("cpu", torch.int64)
+                syn[torch.from_numpy(j[None, :] >= (self._fill[idx] // self.gate.frame)[:, None])] = -1
+                part["gate_syn"] = syn
             return part
+
+    def _state_keys(self, state):
+        """``_keys``, and ``gate_syn`` where the state carries it: a state with the synthetic counts of its pending frames is
+        refused by a gate that is not attached to a provenance layer, a state without them imports into an attached gate
+        with zeros."""
+        has = isinstance(state, StreamState) and "gate_syn" in state.tensors
+        if has and not self._syn:
+            raise ValueError("import_slots: the state carries provenance counts (gate_syn) and this chain has no provenance layer")
+        return self._keys + (("gate_syn",) if has else ())
 
     def _delayed(self, seen):
         """seen: (n,) samples per session -> (F frames seen, d = min(F, pre) frames delayed, the line block of the exported
@@ -769,7 +828,16 @@ class GatedScorer(Layer):
         if (inner_seen + fill > seen).any():
             raise ValueError("import_slots: a session kept more samples than it was pushed")
         check_hang_and_floor(self.gate, hang, nf)
-        return (pend, nf, hang, fill, seen) + (self._check_line(t, n, fill, seen) if self._la else ()) + (
+        syn = None  # (the pending frames' synthetic counts, where the state carries them: _state_keys)
+        if "gate_syn" in t and self._syn:
+            per, syn = hop // self.gate.frame, t["gate_syn"]
+            if syn.dtype != torch.int64 or tuple(syn.shape) != (n, per):
+                raise ValueError(f"import_slots: gate_syn is {(n, per)} int64")
+            so = syn.cpu().numpy()
+            pending = np.arange(per)[None, :] < (fill // self.gate.frame)[:, None]
+            if (so[~pending] != -1).any() or (((so < 0) | (so > self.gate.frame)) & pending).any():
+                raise ValueError(f"import_slots: gate_syn is 0..{self.gate.frame} for a session's pending frames and -1 after them")
+        return (pend, nf, hang, fill, seen, syn) + (self._check_line(t, n, fill, seen) if self._la else ()) + (
             self._check_tone(t, n, seen) if self._tone else ())
 
     def _check_tone(self, t, n, seen):
@@ -800,7 +868,7 @@ class GatedScorer(Layer):
         return line, dev_flags, block, sources
 
     def _import(self, idx, rows):
-        pend, nf, hang, fill, seen = rows[:5]
+        pend, nf, hang, fill, seen, syn = rows[:6]
         if idx:
             import_pending(self.ring, idx, pend)
             with _on(self.device):
@@ -808,7 +876,7 @@ class GatedScorer(Layer):
                 self.nf[dev_rows] = nf.to(self.device)
                 self.h[dev_rows] = torch.from_numpy(hang).to(self.device, torch.int32)
                 if self._la:
-                    line, dev_flags, block, sources = rows[5:]
+                    line, dev_flags, block, sources = rows[6:]
                     pre, frame, dev = self.gate.pre, self.gate.frame, self.device
                     self.line.view(self.S, pre, frame)[dev_rows[:, None], torch.from_numpy(block).to(dev)] = \
                         line.reshape(len(idx), pre, frame).to(dev)
@@ -816,7 +884,11 @@ class GatedScorer(Layer):
                     self.src[dev_rows] = -1
                     self.src[dev_rows, :sources.shape[1]] = sources.to(dev, torch.int32)
                 if self._tone:
-                    self.tone_state[dev_rows] = rows[5].to(self.device, torch.int32)
+                    self.tone_state[dev_rows] = rows[6].to(self.device, torch.int32)
+                if self._syn:
+                    self.gsyn[dev_rows] = 0
+                    if syn is not None:
+                        self.gsyn[dev_rows, :syn.shape[1]] = syn.clamp(min=0).to(self.device, torch.int32)
             self._head[idx] = 0
             self._fill[idx] = fill
             self._seen[idx] = seen

@@ -906,4 +906,107 @@ extern "C" int afx_k_turn_clips(const float* x, const long long* xoffs, int A, i
   return e == hipSuccess ? 0 : fail("%s", hipGetErrorString(e));
 }
 
+// ---------------------------------------------------------------------------------
+// Provenance counts behind a gate (afx/provenance.py; the functions are stated in include/afx.h afx_k_prov_compact /
+// afx_k_prov_take): gsyn, (S, ring_frames) int32 parallel to the gate's pending ring in frames, holds per kept frame how
+// many of its samples the jitter buffer made up.
+//   compact: one workgroup per row of a gate launch.  Thread t owns the frames 2 t and 2 t + 1 (F <= 512); an exclusive scan
+//            of bit 0 of their mask bytes -- inclusive over the wave by shuffle-up (w = 1 .. 32), the four waves' totals
+//            through LDS -- gives each kept frame its rank among the kept ones, and its count goes to
+//            gsyn[slot][(wpos / frame + rank) mod ring_frames]: the order in which gate_copy_kept compacts the samples;
+//   take:    one wave per ready row sums the hop's `per` entries from head / frame on (lane l: l, l + 64, ...; a shuffle-down tree).
+// ---------------------------------------------------------------------------------
+constexpr int PROV_MAX_RING_FRAMES = 1 << 30;
+
+__global__ __launch_bounds__(256) void prov_compact_kernel(const int* __restrict__ counts, const unsigned char* __restrict__ mask,
+                                                           const int* __restrict__ hdr, int F, int frame, int* __restrict__ gsyn,
+                                                           int S, int ring_frames) {
+  __shared__ int s_wave[4];
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int slot = hdr[2 * row], wpos = hdr[2 * row + 1], wposf = wpos / frame;  // (the gate launch's own header: samples)
+  if (!(slot >= 0 && slot < S && wpos >= 0 && wpos % frame == 0 && wposf < ring_frames)) return;  // (the whole workgroup: no barrier is passed by some)
+  int c[2], keep[2];
+  bool bad = false;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int f = 2 * tid + j;
+    const bool in = f < F;
+    c[j] = in ? counts[(long long)row * F + f] : 0;
+    keep[j] = in ? mask[(long long)row * F + f] & 1 : 0;
+    bad |= c[j] < 0 || c[j] > frame;
+  }
+  if (__syncthreads_or(bad)) return;  // a count that is no frame's: the row is skipped whole
+  const int mine = keep[0] + keep[1];
+  int incl = mine;
+  for (int w = 1; w < 64; w <<= 1) {
+    const int o = __shfl_up(incl, w);
+    if (lane >= w) incl += o;
+  }
+  if (lane == 63) s_wave[wave] = incl;
+  __syncthreads();
+  int rank = incl - mine;
+  for (int w = 0; w < wave; ++w) rank += s_wave[w];
+  int* dst = gsyn + (long long)slot * ring_frames;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    if (keep[j]) {
+      const int at = wposf + rank;  // rank < F <= ring_frames: one wrap
+      dst[at < ring_frames ? at : at - ring_frames] = c[j];
+      ++rank;
+    }
+  }
+}
+
+extern "C" int afx_k_prov_compact(const int* counts, const unsigned char* mask, const int* hdr, int A, int F, int frame, int* gsyn,
+                                  int S, int ring_frames, void* stream) {
+  if (!counts || !mask || !hdr || !gsyn) return fail("prov_compact: null argument");
+  if (A <= 0 || A > 65535) return fail("prov_compact: 1 to 65535 rows");
+  if (S <= 0) return fail("prov_compact: no slots");
+  if (F <= 0 || F > GATE_MAX_FRAMES) return fail("prov_compact: 1 to 512 frames a row");
+  if (frame <= 0) return fail("prov_compact: a frame of at least 1 sample");
+  if (ring_frames < F || ring_frames > PROV_MAX_RING_FRAMES) return fail("prov_compact: a ring of at least a row's frames, at most 2^30");
+  hipLaunchKernelGGL(prov_compact_kernel, dim3(A), dim3(256), 0, (hipStream_t)stream, counts, mask, hdr, F, frame, gsyn, S,
+                     ring_frames);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail("%s", hipGetErrorString(e));
+}
+
+__global__ __launch_bounds__(256) void prov_take_kernel(const int* __restrict__ gsyn, int S, int ring_frames,
+                                                        const int* __restrict__ table, int R, int per, int frame, int* __restrict__ out) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= R) return;  // (the same for the 64 lanes of a wave; the kernel passes no barrier)
+  const int slot = table[2 * row], head = table[2 * row + 1], headf = head / frame;  // (the pop's own table: samples)
+  if (!(slot >= 0 && slot < S && head >= 0 && head % frame == 0 && headf < ring_frames)) {
+    if (lane == 0) out[row] = -1;
+    return;
+  }
+  const int* src = gsyn + (long long)slot * ring_frames;
+  long long sum = 0;
+  int neg = 0;
+  for (int k = lane; k < per; k += 64) {
+    const int at = headf + k;  // per <= ring_frames: one wrap
+    const int v = src[at < ring_frames ? at : at - ring_frames];
+    neg |= v < 0;
+    sum += v;
+  }
+  for (int w = 32; w >= 1; w >>= 1) {
+    sum += __shfl_down(sum, w);
+    neg |= __shfl_down(neg, w);
+  }
+  if (lane == 0) out[row] = neg ? -1 : (int)min(sum, 0x7fffffffll);  // (a negative entry is no count: the row says so)
+}
+
+extern "C" int afx_k_prov_take(const int* gsyn, int S, int ring_frames, const int* table, int R, int per, int frame, int* out,
+                               void* stream) {
+  if (!gsyn || !table || !out) return fail("prov_take: null argument");
+  if (S <= 0) return fail("prov_take: no slots");
+  if (ring_frames <= 0 || ring_frames > PROV_MAX_RING_FRAMES) return fail("prov_take: a ring of 1 to 2^30 frames");
+  if (R <= 0 || R > 65535 * 4) return fail("prov_take: 1 to 262140 rows");
+  if (per <= 0 || per > ring_frames) return fail("prov_take: a hop's frames must fit the ring");
+  if (frame <= 0) return fail("prov_take: a frame of at least 1 sample");
+  hipLaunchKernelGGL(prov_take_kernel, dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream, gsyn, S, ring_frames, table, R, per, frame, out);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail("%s", hipGetErrorString(e));
+}
+
 }  // namespace afx

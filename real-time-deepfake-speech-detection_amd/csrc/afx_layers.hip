@@ -1,5 +1,5 @@
 // Per-slot state kernels of the streaming layers (afx/_layer.py) for gfx950 and their C entry points (include/afx.h):
-// cascade store / select / windows, verdict, evidence mark / copy, and input quality.
+// cascade store / select / windows, verdict, evidence mark / copy, input quality, and provenance.
 #include "../../include/afx.h"
 #include "afx_common.h"
 #include "afx_entry.h"
@@ -792,6 +792,76 @@ extern "C" int afx_k_quality(const float* x, long long stride, int A, int hop, c
   a.clip = clip; a.e_quiet = e_quiet; a.dc = dc;
   a.clip_count = clip_count; a.flat_run = flat_run; a.mask = mask; a.max_bad = max_bad; a.abstain = abstain;
   hipLaunchKernelGGL(quality_kernel, dim3(A), dim3(256), 0, (hipStream_t)stream, a);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail("%s", hipGetErrorString(e));
+}
+
+// ---------------------------------------------------------------------------------
+// Provenance (afx/provenance.py; the function is stated in include/afx.h afx_k_provenance): how many samples of each hop
+// the jitter buffer made up, a ring of the last W hops' counts per slot, their sum, and the score passed on or replaced by
+// NaN while the sum is above the limit.  All integers.  One thread per row, rows independent: the thread stores its hop's
+// ring entry, recounts the window over at most W entries, and writes state, totals, meas and out.
+// ---------------------------------------------------------------------------------
+constexpr int PROV_MAX_ROWS = 8192;
+constexpr int PROV_MAX_W = 1024;
+constexpr int PROV_MAX_HOP = 1 << 24;
+
+struct ProvArgs {
+  const int* hdr;      // (A, 2): slot, hop index k
+  const int* counts;   // (A,): the hop's synthetic samples
+  const int* scores;   // the bits of the inner scores at a stride of `sstride` words, or nullptr
+  int sstride;
+  int* ring;           // (S, W): the count of hop j at (j - 1) mod W
+  int* state;          // (S, 2): total, valid
+  int* totals;         // (S, 3): hops, synthetic samples, withheld hops
+  int* meas;           // (A, 3)
+  int* out;            // (A,) bits of the scores passed on, or nullptr
+  long long limit;
+  int A, hop, S, W, abstain;
+};
+
+__global__ __launch_bounds__(256) void provenance_kernel(ProvArgs a) {
+  const int row = blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= a.A) return;
+  const int slot = a.hdr[2 * row], k = a.hdr[2 * row + 1], c = a.counts[row];
+  const int sbits = a.scores ? a.scores[(long long)row * a.sstride] : 0;
+  int* m = a.meas + 3ll * row;
+  if (!(slot >= 0 && slot < a.S && k >= 1 && c >= 0 && c <= a.hop)) {
+    m[0] = m[1] = m[2] = -1;
+    if (a.out) a.out[row] = sbits;
+    return;
+  }
+  int* rg = a.ring + (long long)slot * a.W;
+  rg[(k - 1) % a.W] = c;
+  const int n = min(k, a.W);  // hops k, k - 1, .., k - n + 1: never before the session's first
+  long long sum = c;
+  for (int i = 1; i < n; ++i) sum += rg[(k - 1 - i) % a.W];
+  const int valid = sum <= a.limit, total = (int)min(sum, (long long)QUALITY_N_MAX);
+  a.state[2ll * slot] = total;
+  a.state[2ll * slot + 1] = valid;
+  int* tot = a.totals + 3ll * slot;
+  tot[0] = quality_sat_inc(tot[0], 1);
+  tot[1] = quality_sat_inc(tot[1], c);
+  tot[2] = quality_sat_inc(tot[2], 1 - valid);
+  m[0] = c, m[1] = total, m[2] = valid;
+  if (a.out) a.out[row] = valid || !a.abstain ? sbits : QUALITY_QNAN;
+}
+
+extern "C" int afx_k_provenance(const int* hdr, const int* counts, const float* scores, int sstride, int A, int hop, long long limit,
+                                int abstain, int* ring, int W, int* state, int* totals, int S, int* meas, float* out, void* stream) {
+  if (!hdr || !counts || !ring || !state || !totals || !meas) return fail("provenance: null argument");
+  if (scores && (!out || sstride < 1)) return fail("provenance: scores need an output and a stride of at least 1");
+  if (A <= 0 || A > PROV_MAX_ROWS) return fail("provenance: 1 to 8192 rows");
+  if (hop <= 0 || hop > PROV_MAX_HOP) return fail("provenance: a hop of 1 to 2^24 samples");
+  if (S <= 0) return fail("provenance: no slots");
+  if (W < 1 || W > PROV_MAX_W) return fail("provenance: a window of 1 to 1024 hops");
+  if (limit < 0 || limit > (long long)W * hop) return fail("provenance: a limit of 0 to W * hop samples");
+  if (abstain != 0 && abstain != 1) return fail("provenance: abstain is 0 or 1");
+  ProvArgs a{};
+  a.hdr = hdr; a.counts = counts; a.scores = reinterpret_cast<const int*>(scores); a.sstride = scores ? sstride : 0;
+  a.ring = ring; a.state = state; a.totals = totals; a.meas = meas; a.out = scores ? reinterpret_cast<int*>(out) : nullptr;
+  a.limit = limit; a.A = A; a.hop = hop; a.S = S; a.W = W; a.abstain = abstain;
+  hipLaunchKernelGGL(provenance_kernel, dim3((A + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : fail("%s", hipGetErrorString(e));
 }

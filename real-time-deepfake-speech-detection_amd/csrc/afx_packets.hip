@@ -1119,4 +1119,91 @@ extern "C" int afx_k_jitter_conceal_period_rates(float* jring, int S, int Js, co
                          n_rates, const_cast<int*>(period), (hipStream_t)stream));
 }
 
+// ---------------------------------------------------------------------------------
+// Provenance marks of a jitter front (afx/provenance.py; the functions are stated in include/afx.h afx_k_prov_spans /
+// afx_k_prov_frames): psyn, (S, ring_len) bytes parallel to the pending ring, holds 1 where the 16 kHz sample at that ring
+// position was made up by the jitter buffer (loss concealment or comfort noise) and 0 where it was received.
+//   spans:  rows of (slot, wpos, n, value) fill psyn[slot][(wpos + k) mod ring_len] = value, k < n; the host cuts every
+//           release's output range into such runs, so the rows of a launch write disjoint ranges.  A range is at most two
+//           linear pieces (before and after the wrap); each piece is written as its unaligned head and tail bytes and the
+//           aligned dwords between them, a grid of (tile, row) striding over both;
+//   frames: one wave per (row, frame) of the hops a pop takes: lane l counts the bytes l, l + 64, ... of the frame that are
+//           not 0 (byte loads, the wrap taken per byte), a shuffle-down tree folds the 64 partials (w = 32 .. 1), lane 0
+//           stores the count.  Integers: any order gives the same number.
+// ---------------------------------------------------------------------------------
+constexpr int PROV_MAX_RING = 1 << 30;  // bytes of a psyn row: positions and sums of two of them stay below 2^31
+
+// p[0 .. n) = v for the threads t0, t0 + step, ... of a row's grid
+__device__ __forceinline__ void prov_fill(unsigned char* p, int n, unsigned char v, int t0, int step) {
+  if (n <= 0) return;
+  const int head = min(n, (int)((4u - (unsigned)((unsigned long long)p & 3ull)) & 3u));
+  const int words = (n - head) >> 2, tail = n - head - 4 * words;
+  for (int i = t0; i < head; i += step) p[i] = v;
+  unsigned* w = reinterpret_cast<unsigned*>(p + head);
+  const unsigned vv = 0x01010101u * v;
+  for (int q = t0; q < words; q += step) w[q] = vv;
+  for (int i = t0; i < tail; i += step) p[head + 4 * words + i] = v;
+}
+
+__global__ __launch_bounds__(256) void prov_spans_kernel(unsigned char* __restrict__ psyn, int S, int ring_len,
+                                                         const int* __restrict__ rows) {
+  const int* r = rows + 4 * blockIdx.y;
+  const int slot = r[0], wpos = r[1], n = r[2], value = r[3];
+  if (!(slot >= 0 && slot < S && wpos >= 0 && wpos < ring_len && n >= 0 && n <= ring_len && (value == 0 || value == 1))) return;
+  unsigned char* row = psyn + (long long)slot * ring_len;
+  const int t0 = blockIdx.x * blockDim.x + threadIdx.x, step = gridDim.x * blockDim.x;
+  const int n1 = min(n, ring_len - wpos);  // up to the ring's end; the rest from column 0
+  prov_fill(row + wpos, n1, (unsigned char)value, t0, step);
+  prov_fill(row, n - n1, (unsigned char)value, t0, step);
+}
+
+extern "C" int afx_k_prov_spans(unsigned char* psyn, int S, int ring_len, const int* rows, int R, int max_n, void* stream) {
+  if (!psyn || !rows) return fail("prov_spans: null argument");
+  if (S <= 0) return fail("prov_spans: no slots");
+  if (ring_len <= 0 || ring_len > PROV_MAX_RING) return fail("prov_spans: a ring of 1 to 2^30 bytes");
+  if (R <= 0 || R > 65535) return fail("prov_spans: 1 to 65535 rows");
+  if (max_n < 0 || max_n > ring_len) return fail("prov_spans: the longest row is 0 to ring_len bytes");
+  hipLaunchKernelGGL(prov_spans_kernel, dim3(max(min((max_n + 1023) / 1024, 64), 1), R), dim3(256), 0, (hipStream_t)stream, psyn, S,
+                     ring_len, rows);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail("%s", hipGetErrorString(e));
+}
+
+__global__ __launch_bounds__(256) void prov_frames_kernel(const unsigned char* __restrict__ psyn, int S, int ring_len,
+                                                          const int* __restrict__ table, int hop, int frame, int* __restrict__ out) {
+  const int row = blockIdx.y, F = hop / frame;
+  const int f = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (f >= F) return;  // (the same for the 64 lanes of a wave; the kernel passes no barrier)
+  const int slot = table[2 * row], head = table[2 * row + 1];
+  int* o = out + (long long)row * F + f;
+  if (!(slot >= 0 && slot < S && head >= 0 && head < ring_len)) {
+    if (lane == 0) *o = -1;
+    return;
+  }
+  const unsigned char* src = psyn + (long long)slot * ring_len;
+  const long long at = (long long)head + (long long)f * frame;  // < 2 ring_len: hop <= ring_len
+  const int w0 = (int)(at < ring_len ? at : at - ring_len);
+  int c = 0;
+  for (int k = lane; k < frame; k += 64) {
+    const int w = w0 + k;  // frame <= ring_len: one wrap
+    c += src[w < ring_len ? w : w - ring_len] != 0;
+  }
+  for (int w = 32; w >= 1; w >>= 1) c += __shfl_down(c, w);
+  if (lane == 0) *o = c;
+}
+
+extern "C" int afx_k_prov_frames(const unsigned char* psyn, int S, int ring_len, const int* table, int R, int hop, int frame,
+                                 int* out, void* stream) {
+  if (!psyn || !table || !out) return fail("prov_frames: null argument");
+  if (S <= 0) return fail("prov_frames: no slots");
+  if (ring_len <= 0 || ring_len > PROV_MAX_RING) return fail("prov_frames: a ring of 1 to 2^30 bytes");
+  if (R <= 0 || R > 65535) return fail("prov_frames: 1 to 65535 rows");
+  if (hop <= 0 || hop > ring_len) return fail("prov_frames: a hop must fit the ring");
+  if (frame <= 0 || hop % frame != 0) return fail("prov_frames: a hop is a whole number of frames");
+  hipLaunchKernelGGL(prov_frames_kernel, dim3((hop / frame + 3) / 4, R), dim3(256), 0, (hipStream_t)stream, psyn, S, ring_len, table,
+                     hop, frame, out);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail("%s", hipGetErrorString(e));
+}
+
 }  // namespace afx
