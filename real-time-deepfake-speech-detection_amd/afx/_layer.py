@@ -11,7 +11,20 @@ whatever presents the surface below.
 through (``S``, ``device``, ``hop``, ``window``, ``samples_seen``, ``_slot_list``, ``state_meta``), ``reset`` and the session
 moves.  A layer states its ``_meta()``, its state tensors ``_keys`` and the words ``_part`` for a state that lacks them, and
 four hooks: ``_export(idx, st)``, ``_check(state, n)``, ``_import(idx, rows)``, ``_reset(idx)``; and its ``push``.
+
+A layer whose part is per-slot tensors writes none of the four hooks.  Its state class is a ``SlotTable``: it declares
+its tensors once, as ``Field`` rows in export order, and inherits their allocation, ``reset``, ``export_rows``,
+``import_rows`` and the dtype and shape refusals of ``check_rows``; the layer names the table with ``_own`` and ``Layer``
+derives ``_keys`` and the hooks from it (the quality, provenance, verdict and evidence layers; the cascade's part, with a
+tensor on the host and a ring exported in session order, and the gate's stay written out).  What such a layer still writes
+is its function: its policy and numpy reference, its ``update`` with the launch spelled out, and ``check_rows`` with the
+rules only it knows (``bad > W``, "the total is the ring's sum").  ``HopTable`` adds what an update with one row per named
+slot shares (the checks of ``hop_index`` and ``scores``, the header upload, the ``meas`` / ``out`` buffers), ``WindowState``
+is its numpy mirror, and ``WithholdingLayer`` is the base of the two layers that hand a score on or withhold it (quality,
+provenance): the whole ``push``, the verifier hand-on and the pass-throughs; a subclass states its policy, its state
+class, its words for ``need_gpu`` and ``_operand``, what its update takes of a push.
 """
+import collections
 import contextlib
 import math
 
@@ -112,6 +125,130 @@ def upload_pairs(first, second, device):
 
 def rows_on(idx, device):
     return torch.tensor(idx, dtype=torch.long, device=device)
+
+
+def returned_scores(scores, A, device, cast=False):
+    """What an inner ``push`` returned for A rows: None, or (A,) scores on ``device`` -- fp32, or with ``cast`` of any dtype and
+    made fp32 here; anything else is a RuntimeError."""
+    if scores is None:
+        return None
+    if scores.shape != (A,) or scores.device != device or not (cast or scores.dtype == torch.float32):
+        raise RuntimeError(f"the inner scorer returned {tuple(scores.shape)} {scores.dtype} scores on {scores.device} for {A} rows")
+    return scores if scores.dtype == torch.float32 else scores.to(torch.float32)
+
+
+# ---- per-slot state tables -------------------------------------------------------------------------------------------------
+class Field(collections.namedtuple("Field", "key name shape dtype host new", defaults=(False, None))):
+    """One per-slot tensor of a ``SlotTable``, (S, *shape) of ``dtype`` on the device: its ``StreamState`` key, its attribute
+    name, ``host=True``: exported to the host as int64 (the default: as a clone on the device, as it is), ``new``: the row of
+    a new stream, a number or a tuple (the default, None: zeros at first, and ``reset`` leaves it alone)."""
+
+
+class SlotTable:
+    """The per-slot tensors of a state class, declared once as ``Field`` rows in export order (``_allocate``): their
+    allocation, ``reset``, the session moves and the dtype and shape refusals.  A subclass adds its ``update`` and, in
+    ``check_rows``, the rules only it knows."""
+
+    def _allocate(self, S, device, *fields):
+        self.S, self._fields, self.keys, self._new = S, fields, tuple(f.key for f in fields), {}
+        for f in fields:
+            t = torch.zeros(S, *f.shape, dtype=f.dtype, device=device)
+            device = t.device
+            if f.new is not None:
+                self._new[f.name] = torch.tensor(f.new, dtype=f.dtype, device=device)
+                t[:] = self._new[f.name]
+            setattr(self, f.name, t)
+        self.device = device  # (the first tensor's, with its index: every launch of an update goes to THIS GPU)
+
+    def reset(self, slots):
+        """The named slots begin a new stream: every field with a new-stream row takes it, the others are left alone."""
+        b = slots_of(slots, self.S)
+        if b.size and self._new:
+            with _on(self.device):
+                rows = torch.from_numpy(b).to(self.device)
+                for name, new in self._new.items():
+                    getattr(self, name)[rows] = new
+
+    def export_rows(self, slots):
+        """-> the rows of the named slots, one tensor per field in the declared order: a clone on the device, or int64 on the
+        host."""
+        with _on(self.device):
+            rows = torch.from_numpy(slots_of(slots, self.S)).to(self.device)
+            return tuple(getattr(self, f.name)[rows].to("cpu", torch.int64) if f.host else getattr(self, f.name)[rows].clone()
+                         for f in self._fields)
+
+    def check_shapes(self, rows, n):
+        """Refuses (ValueError) a row set that is not one tensor per field as ``export_rows`` gives them for n sessions."""
+        for f, t in zip(self._fields, rows):
+            dtype = torch.int64 if f.host else f.dtype
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != (n, *f.shape):
+                raise ValueError(f"import_slots: {f.key} is {(n, *f.shape)} {str(dtype).split('.')[-1]}")
+
+    def check_rows(self, rows, n, seen):
+        """Refuses (ValueError) what cannot be the state of n sessions that have seen ``seen`` (n,) samples -> the rows
+        ``import_rows`` takes.  Here: the dtypes and shapes; a subclass checks them first (``check_shapes``), then its own
+        rules."""
+        self.check_shapes(rows, n)
+        return tuple(rows)
+
+    def import_rows(self, slots, *rows):
+        """The named slots take the (checked) state rows."""
+        b = slots_of(slots, self.S)
+        if b.size:
+            with _on(self.device):
+                at = torch.from_numpy(b).to(self.device)
+                for f, t in zip(self._fields, rows):
+                    getattr(self, f.name)[at] = t.to(self.device, f.dtype)
+
+
+class HopTable(SlotTable):
+    """A table that one launch per push advances, a row per named slot: what such updates share around the launch.
+    ``meas_cols``: the int32 columns of a row of ``meas``."""
+
+    meas_cols = 0
+
+    def _hop_rows(self, A, hop_index, scores):
+        """The checks of an update's ``hop_index`` (an int or A ints, 1 or more) and ``scores`` ((A,) fp32 on the device, or
+        None) -> (the hop indices, the scores with a stride the kernel can read: a column is read in place)."""
+        k = hop_indices(hop_index, A, 1)
+        if scores is not None and (not isinstance(scores, torch.Tensor) or scores.dtype != torch.float32 or scores.shape != (A,)
+                                   or scores.device != self.device):
+            raise ValueError(f"scores: an fp32 tensor of shape {(A,)} on {self.device}")
+        if scores is not None and A > 1 and scores.stride(0) < 1:
+            scores = scores.contiguous()
+        return k, scores
+
+    def _no_rows(self, scores):
+        """``(out, meas)`` of an update that names no slot."""
+        out = None if scores is None else torch.empty(0, dtype=torch.float32, device=self.device)
+        return out, torch.empty(0, self.meas_cols, dtype=torch.int32, device=self.device)
+
+    def _buffers(self, slots, hop_index, scores):
+        """-> (the (slot, hop_index) header on the device, ``meas``, ``out``) of a launch (the caller has made the device
+        current)."""
+        A = len(slots)
+        return (upload_pairs(slots, hop_index, self.device), torch.empty(A, self.meas_cols, dtype=torch.int32, device=self.device),
+                None if scores is None else torch.empty(A, dtype=torch.float32, device=self.device))
+
+
+class WindowState:
+    """Host mirrors of a ``HopTable`` of ``ring`` (S, W), ``st`` (S, k) int32 and ``totals`` (S, m) int32, a new stream
+    everywhere.  A subclass states ``ring_dtype``, ``new`` (the k values of a new stream's ``st``) and ``n_totals``."""
+
+    def __init__(self, S, W):
+        self.ring = np.zeros((S, W), dtype=self.ring_dtype)
+        self.st = np.tile(np.array(self.new, dtype=np.int32), (S, 1))
+        self.totals = np.zeros((S, self.n_totals), dtype=np.int32)
+
+    def reset(self, slots):
+        """What the table's ``reset`` does: ``st`` a new stream's and ``totals`` cleared, the ring left alone."""
+        self.st[slots] = self.new
+        self.totals[slots] = 0
+
+    def copy(self):
+        c = type(self)(*self.ring.shape)
+        c.ring, c.st, c.totals = self.ring.copy(), self.st.copy(), self.totals.copy()
+        return c
 
 
 # ---- rings ---------------------------------------------------------------------------------------------------------------------
@@ -228,6 +365,24 @@ class Layer:
     _keys = ()          # the state tensors of this layer's part
     _part = ""          # how a refusal calls a state without them: "the state has no ..."
     _inner_seen = None  # the state tensor that holds the inner sessions' sample counts, where they are not the state's own
+    _table = None       # the ``SlotTable`` that is this layer's whole part (``_own``): ``_keys`` and the four hooks are its
+
+    def _own(self, table):
+        """``table`` is this layer's part of a ``StreamState`` -> table."""
+        self._table, self._keys = table, table.keys
+        return table
+
+    def _reset(self, idx):
+        self._table.reset(idx)
+
+    def _export(self, idx, st):
+        return dict(zip(self._keys, self._table.export_rows(idx)))
+
+    def _check(self, state, n):
+        return self._table.check_rows([state.tensors[k] for k in self._keys], n, state.seen)
+
+    def _import(self, idx, rows):
+        self._table.import_rows(idx, *rows)
 
     def _state_keys(self, state):
         """The state tensors of this layer's part that ``state`` must have: ``_keys``, and for a layer with an optional part
@@ -308,3 +463,86 @@ class Layer:
         rows = self._check(state, len(state))
         self.scorer.import_slots(idx, inner)  # (refuses a foreign state before changing anything)
         self._import(idx, rows)
+
+
+class WithholdingLayer(Layer):
+    """The base of the layers that hand the inner score on bit for bit or withhold it (the quiet NaN): ``push`` runs the
+    inner ``push``, then one update of the layer's ``HopTable`` with ``hop_index = samples_seen // hop`` (one small upload,
+    one launch, no synchronisation) and returns its ``out`` (a KV-cached ``None`` stays ``None``; the hop is measured all the
+    same).  ``last_meas`` holds the ``meas`` rows of the newest push.  Around a cascade ``verified``, ``verified_at`` and
+    ``take_events`` are the cascade's, and with ``abstain`` on ``last_verified()`` has NaN for the verifier scores of the
+    slots that are not valid (on the device, no synchronisation).
+
+    A subclass states ``_does`` (the words for ``need_gpu``), builds its policy and names its state class (both to
+    ``__init__``) and writes ``_operand``."""
+
+    _does = ""
+
+    def __init__(self, scorer, policy, table_type):
+        super().__init__(scorer)
+        self.policy = policy
+        table = self._own(table_type(scorer.S, policy, scorer.hop, scorer.window, scorer.device))
+        self.last_meas = torch.empty(0, table.meas_cols, dtype=torch.int32, device=table.device)
+        # what stands directly below hands the verifier scores on: the cascade, or a layer of this kind that has made its own
+        # invalid slots' NaN; this layer's NaN go on top, and the verdict layer reads ``last_verified`` of what is directly below IT
+        self._cascade = self._below("cascade") is not None
+        self._last = None  # (slots, verifier scores with the invalid slots' made NaN) of the newest push
+
+    @property
+    def valid(self):
+        return self._table.valid
+
+    def stats(self):
+        """The state's ``stats``."""
+        return self._table.stats()
+
+    # (around a cascade: its results, for the caller and for the verdict layer)
+    @property
+    def verified(self):
+        return self.scorer.verified
+
+    @property
+    def verified_at(self):
+        return self.scorer.verified_at
+
+    def take_events(self):
+        """``CascadeScorer.take_events`` (the verifier scores as the verifier gave them)."""
+        return self.scorer.take_events()
+
+    def last_verified(self):
+        """``CascadeScorer.last_verified`` of the newest push; with ``abstain`` on, the verifier scores of the slots that
+        are not valid are NaN."""
+        return self._last
+
+    def _operand(self, chunk, idx):
+        """The first operand of the state's ``update`` for the push of ``chunk`` to the slots ``idx``; called before the
+        chunk is checked and the inner scorer pushed, so what it refuses changes nothing."""
+        raise NotImplementedError
+
+    def push(self, chunk, slots=None):
+        """chunk and slots: the inner scorer's own rule (an fp32 chunk on the scorer's GPU) -> the inner scores with NaN
+        where the slot's score is withheld, ``None`` where the inner ``push`` returned ``None``."""
+        need_gpu(self.device, self._does)
+        inner, table = self.scorer, self._table
+        dev = table.device
+        idx = self._named(slots)
+        A = len(idx)
+        operand = self._operand(chunk, idx)
+        if not isinstance(chunk, torch.Tensor) or chunk.device != dev or chunk.dtype != torch.float32 or chunk.shape != (A, self.hop):
+            raise ValueError(f"expected a CUDA fp32 tensor of shape {(A, self.hop)} on {dev} (one hop per named slot)")
+        self._last = None
+        scores = inner.push(chunk, slots)
+        if not A:
+            return scores
+        scores = returned_scores(scores, A, dev, cast=True)
+        out, self.last_meas = table.update(operand, idx, hop_index=(inner.samples_seen[idx] // self.hop).numpy(), scores=scores)
+        last = inner.last_verified() if self._cascade else None
+        if last is not None and self.policy.abstain:
+            chosen, v = last
+            with torch.cuda.device(dev):
+                rows = torch.empty(chosen.numel(), dtype=torch.int64, pin_memory=True)
+                rows.copy_(chosen)
+                ok = table.valid.index_select(0, rows.to(dev, non_blocking=True))
+                last = (chosen, torch.where(ok, v, torch.full_like(v, float("nan"))))
+        self._last = last
+        return out

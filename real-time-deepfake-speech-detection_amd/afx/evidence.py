@@ -52,7 +52,7 @@ import wave
 import numpy as np
 import torch
 
-from ._layer import N_MAX, Layer, _on, hop_indices, integer, need_gpu, slot_count, slots_of, upload_pairs
+from ._layer import N_MAX, Field, Layer, SlotTable, _on, hop_indices, integer, need_gpu, returned_scores, slot_count, slots_of, upload_pairs
 from ._lib import call_on, check, lib, ptr
 
 EVIDENCE_FORMAT = 1  # layout of the evidence part of a StreamState: import_slots refuses any other
@@ -249,21 +249,23 @@ class EvidencePolicy:
         return state
 
 
-class Evidence:
+class Evidence(SlotTable):
     """The pre-roll rings of ``S`` slots and the clip pool under ``policy`` on ``device``, for hops of ``hop`` samples; see
     the module docstring.  ``update`` is one pinned upload of the header and two launches, with no synchronisation;
     ``take_clips()`` is the only read-back of the layer (``stats()`` reads the counters when asked).  window: needed only
     for a policy with ``pre=None``."""
 
     def __init__(self, S, policy, hop, device="cuda", window=None):
-        self.S, self.policy = slot_count(S, policy, EvidencePolicy), policy
+        S, self.policy = slot_count(S, policy, EvidencePolicy), policy
         self.pre = policy.pre_for(hop, window)
         self.hop, self.post, self.clips = int(hop), policy.post, policy.clips
         self.P, self.L = self.pre + 1, self.pre + 1 + self.post
-        self.hist = torch.zeros(self.S, self.P * self.hop, dtype=torch.float32, device=device)
-        self.device = self.hist.device  # (with its index: every launch of an update goes to THIS GPU)
+        # the session state: the raw ring rows (a hop's position is a function of its hop number, so they move as they are;
+        # ``reset`` leaves them: ``first_hop >= 1`` keeps a new session from reading them).  ``rec``, ``left``, the pool
+        # and the counters belong to the scorer, not to a session
+        self._allocate(S, device, Field("evidence_hist", "hist", (self.P * self.hop,), torch.float32),
+                       Field("evidence_scores", "sring", (self.P,), torch.float32))
         dev = self.device
-        self.sring = torch.zeros(self.S, self.P, dtype=torch.float32, device=dev)
         self.rec = torch.full((self.S,), -1, dtype=torch.int32, device=dev)
         self.left = torch.zeros(self.S, dtype=torch.int32, device=dev)
         # (one header row more than the pool has entries: where ``reset`` sends the writes of slots that are not recording)
@@ -314,8 +316,7 @@ class Evidence:
     # ---- sessions ------------------------------------------------------------------------------------------------------------
     def reset(self, slots):
         """The named slots begin a new stream: a clip one of them is recording becomes TRUNCATED (kept with the hops it
-        has), ``rec = -1``, ``left = 0``.  The rings are left as they are: ``first_hop >= 1`` keeps a new session from
-        reading them.  No synchronisation."""
+        has), ``rec = -1``, ``left = 0``.  The rings are left as they are.  No synchronisation."""
         b = slots_of(slots, self.S)
         if b.size:
             with _on(self.device):
@@ -326,29 +327,10 @@ class Evidence:
                 self.rec[rows] = -1
                 self.left[rows] = 0
 
-    def export_rows(self, slots):
-        """-> (evidence_hist (n, P hop) fp32, evidence_scores (n, P) fp32) of the named slots, on the device: the raw ring
-        rows (a hop's position is a function of its hop number, so they move as they are)."""
-        with _on(self.device):
-            rows = torch.from_numpy(slots_of(slots, self.S)).to(self.device)
-            return self.hist[rows].clone(), self.sring[rows].clone()
-
-    def check_rows(self, hist, sring, n):
-        """Refuses (ValueError) what cannot be the ring rows of n sessions of this layout."""
-        if not isinstance(hist, torch.Tensor) or hist.dtype != torch.float32 or tuple(hist.shape) != (n, self.P * self.hop):
-            raise ValueError(f"import_slots: evidence_hist is {(n, self.P * self.hop)} float32 (pre {self.pre}, hop {self.hop})")
-        if not isinstance(sring, torch.Tensor) or sring.dtype != torch.float32 or tuple(sring.shape) != (n, self.P):
-            raise ValueError(f"import_slots: evidence_scores is {(n, self.P)} float32")
-
-    def import_rows(self, slots, hist, sring):
+    def import_rows(self, slots, *rows):
         """The named slots take the (checked) ring rows; what they were recording is TRUNCATED, as in ``reset``."""
-        b = slots_of(slots, self.S)
-        if b.size:
-            self.reset(b)
-            with _on(self.device):
-                rows = torch.from_numpy(b).to(self.device)
-                self.hist[rows] = hist.to(self.device)
-                self.sring[rows] = sring.to(self.device)
+        self.reset(slots)
+        super().import_rows(slots, *rows)
 
     # ---- the read-back -------------------------------------------------------------------------------------------------------
     def _to_host(self, *tensors):
@@ -410,13 +392,12 @@ class EvidenceScorer(Layer):
     counters belong to the scorer, not to a session."""
 
     layer = "evidence"
-    _keys = ("evidence_hist", "evidence_scores")
     _part = "evidence part (it was not exported by an EvidenceScorer)"
 
     def __init__(self, scorer, policy):
         super().__init__(scorer)
         self.policy = policy
-        self.evidence = Evidence(scorer.S, policy, scorer.hop, scorer.device, window=scorer.window)
+        self.evidence = self._own(Evidence(scorer.S, policy, scorer.hop, scorer.device, window=scorer.window))
 
     @property
     def alarm(self):
@@ -452,8 +433,7 @@ class EvidenceScorer(Layer):
         A = len(idx)
         if not A:
             return scores
-        if scores is not None and (scores.shape != (A,) or scores.device != self.device or scores.dtype != torch.float32):
-            raise RuntimeError(f"the inner scorer returned {tuple(scores.shape)} {scores.dtype} scores on {scores.device} for {A} rows")
+        returned_scores(scores, A, self.device)
         self.evidence.update(chunk.to(self.device, torch.float32), idx, hop_index=(inner.samples_seen[idx] // self.hop).numpy(),
                              scores=scores, verdict_state=inner.verdicts.st)
         return scores
@@ -461,18 +441,3 @@ class EvidenceScorer(Layer):
     # ---- sessions (afx._layer.Layer) -----------------------------------------------------------------------------------------
     def _meta(self):
         return dict(evidence=EVIDENCE_FORMAT, evidence_pre=self.evidence.pre)
-
-    def _reset(self, idx):
-        self.evidence.reset(idx)
-
-    def _export(self, idx, st):
-        hist, sring = self.evidence.export_rows(idx)
-        return dict(evidence_hist=hist, evidence_scores=sring)
-
-    def _check(self, state, n):
-        rows = state.tensors["evidence_hist"], state.tensors["evidence_scores"]
-        self.evidence.check_rows(*rows, n)
-        return rows
-
-    def _import(self, idx, rows):
-        self.evidence.import_rows(idx, *rows)

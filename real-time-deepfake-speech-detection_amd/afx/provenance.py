@@ -74,7 +74,7 @@ thresholds (0.05 is an engineering default: there is no labelled corpus behind i
 import numpy as np
 import torch
 
-from ._layer import N_MAX, Layer, _on, fp32, hop_indices, need_gpu, slot_count, slots_of, upload_pairs
+from ._layer import N_MAX, Field, HopTable, WindowState, WithholdingLayer, fp32, hop_indices, need_gpu, slot_count, slots_of
 from ._lib import call_on, check, lib, ptr
 from .quality import MAX_HOP, QNAN_BITS, window_hops
 
@@ -90,25 +90,11 @@ def marks16(kinds, L, M):
     return C[K * M // L]
 
 
-class ProvenanceState:
+class ProvenanceState(WindowState):
     """Host mirrors of the whole provenance state of S slots: ``ring`` (S, W) int32, ``st`` (S, 2) int32 = (total, valid),
     ``totals`` (S, 3) int32; a new stream everywhere."""
 
-    def __init__(self, S, W):
-        self.ring = np.zeros((S, W), dtype=np.int32)
-        self.st = np.zeros((S, 2), dtype=np.int32)
-        self.st[:, 1] = 1
-        self.totals = np.zeros((S, 3), dtype=np.int32)
-
-    def reset(self, slots):
-        """What ``Provenance.reset`` does: ``st`` = (0, 1) and ``totals`` cleared, the ring left alone."""
-        self.st[slots] = (0, 1)
-        self.totals[slots] = 0
-
-    def copy(self):
-        c = ProvenanceState(*self.ring.shape)
-        c.ring, c.st, c.totals = self.ring.copy(), self.st.copy(), self.totals.copy()
-        return c
+    ring_dtype, new, n_totals = np.int32, (0, 1), 3
 
 
 class ProvenancePolicy:
@@ -186,22 +172,23 @@ class ProvenancePolicy:
         return meas, meas[:, 2] != 0
 
 
-class Provenance:
+class Provenance(HopTable):
     """The per-slot provenance state of ``S`` streams under ``policy`` for hops of ``hop`` samples and a window of ``window``
     samples, on ``device``; see the module docstring.  ``update`` is one pinned upload of the header and one
     ``afx_k_provenance`` launch, with no synchronisation; ``valid`` and ``synthetic`` are views of the state on the device;
     ``stats()`` is the only read-back."""
 
+    meas_cols = 3
+
     def __init__(self, S, policy, hop, window, device="cuda"):
         S = slot_count(S, policy, ProvenancePolicy)
         self.W = window_hops(window, hop)
-        self.S, self.policy, self.hop, self.window = S, policy, int(hop), int(window)
+        self.policy, self.hop, self.window = policy, int(hop), int(window)
         self.limit = policy.limit(self.W, self.hop)
-        self.ring = torch.zeros(self.S, self.W, dtype=torch.int32, device=device)
-        self.device = self.ring.device  # (with its index: every launch of an update goes to THIS GPU)
-        self.st = torch.zeros(self.S, 2, dtype=torch.int32, device=self.device)
-        self.st[:, 1] = 1
-        self.totals = torch.zeros(self.S, 3, dtype=torch.int32, device=self.device)
+        # (``reset`` leaves the ring alone: a new session's window sum never reaches back before its first hop)
+        self._allocate(S, device, Field("prov_ring", "ring", (self.W,), torch.int32),
+                       Field("prov_state", "st", (2,), torch.int32, host=True, new=(0, 1)),
+                       Field("prov_totals", "totals", (3,), torch.int32, host=True, new=0))
 
     @property
     def synthetic(self):
@@ -229,57 +216,25 @@ class Provenance:
         if (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or counts.shape != (A,)
                 or counts.device != self.device):
             raise ValueError(f"counts: an int32 tensor of shape {(A,)} on {self.device}")
-        k = hop_indices(hop_index, A, 1)
-        if scores is not None and (not isinstance(scores, torch.Tensor) or scores.dtype != torch.float32 or scores.shape != (A,)
-                                   or scores.device != self.device):
-            raise ValueError(f"scores: an fp32 tensor of shape {(A,)} on {self.device}")
-        if not A:
-            empty = torch.empty(0, dtype=torch.float32, device=self.device)
-            return (None if scores is None else empty), torch.empty(0, 3, dtype=torch.int32, device=self.device)
-        return self._update(counts.contiguous(), b, k, scores)
+        k, scores = self._hop_rows(A, hop_index, scores)
+        return self._update(counts.contiguous(), b, k, scores) if A else self._no_rows(scores)
 
     def _update(self, counts, slots, hop_index, scores):
         need_gpu(self.device, "hops are counted")
-        A = len(slots)
-        if scores is not None and A > 1 and scores.stride(0) < 1:
-            scores = scores.contiguous()
         with torch.cuda.device(self.device):
-            d = upload_pairs(slots, hop_index, self.device)
-            meas = torch.empty(A, 3, dtype=torch.int32, device=self.device)
-            out = None if scores is None else torch.empty(A, dtype=torch.float32, device=self.device)
+            d, meas, out = self._buffers(slots, hop_index, scores)
             check(call_on(self.ring, lib().afx_k_provenance, ptr(d), ptr(counts), ptr(scores),
-                          1 if scores is None else max(scores.stride(0), 1), A, self.hop, self.limit, int(self.policy.abstain),
+                          1 if scores is None else max(scores.stride(0), 1), len(slots), self.hop, self.limit, int(self.policy.abstain),
                           ptr(self.ring), self.W, ptr(self.st), ptr(self.totals), self.S, ptr(meas), ptr(out)))
         return out, meas
 
     # ---- sessions ------------------------------------------------------------------------------------------------------------
-    def reset(self, slots):
-        """The named slots begin a new stream: ``p_state = (0, 1)`` and ``p_totals = 0``.  The ring is left alone: a new
-        session's window sum never reaches back before its first hop."""
-        b = slots_of(slots, self.S)
-        if b.size:
-            with _on(self.device):
-                rows = torch.from_numpy(b).to(self.device)
-                self.st[rows] = torch.tensor([0, 1], dtype=torch.int32, device=self.device)
-                self.totals[rows] = 0
-
-    def export_rows(self, slots):
-        """-> (prov_ring (n, W) int32 on the device, prov_state (n, 2) and prov_totals (n, 3) int64 on the host) of the named
-        slots."""
-        with _on(self.device):
-            rows = torch.from_numpy(slots_of(slots, self.S)).to(self.device)
-            return self.ring[rows].clone(), self.st[rows].to("cpu", torch.int64), self.totals[rows].to("cpu", torch.int64)
-
-    def check_rows(self, ring, st, totals, seen, n):
+    def check_rows(self, rows, n, seen):
         """Refuses (ValueError) what cannot be the state of n sessions of this window that have seen ``seen`` (n,) samples; ->
         (ring, st, totals), ``valid`` set under THIS policy's limit."""
-        if not isinstance(ring, torch.Tensor) or ring.dtype != torch.int32 or tuple(ring.shape) != (n, self.W):
-            raise ValueError(f"import_slots: prov_ring is {(n, self.W)} int32")
-        if not isinstance(st, torch.Tensor) or st.dtype != torch.int64 or tuple(st.shape) != (n, 2):
-            raise ValueError("import_slots: prov_state is (n, 2) int64")
-        if not isinstance(totals, torch.Tensor) or totals.dtype != torch.int64 or tuple(totals.shape) != (n, 3):
-            raise ValueError("import_slots: prov_totals is (n, 3) int64")
-        st, totals, r = st.cpu().clone(), totals.cpu(), ring.cpu().to(torch.int64)
+        self.check_shapes(rows, n)
+        ring, st, totals = rows[0], rows[1].cpu().clone(), rows[2].cpu()
+        r = ring.cpu().to(torch.int64)
         if bool(((r < 0) | (r > self.hop)).any()):
             raise ValueError(f"import_slots: a hop counts more synthetic samples than its {self.hop} (or fewer than 0)")
         k = torch.as_tensor(seen, dtype=torch.int64).reshape(-1) // self.hop
@@ -294,16 +249,6 @@ class Provenance:
             raise ValueError("import_slots: a session's totals are negative, or hops were withheld more often than hops were seen")
         st[:, 1] = (total <= self.limit).to(torch.int64)
         return ring, st, totals
-
-    def import_rows(self, slots, ring, st, totals):
-        """The named slots take the (checked) state rows."""
-        b = slots_of(slots, self.S)
-        if b.size:
-            with _on(self.device):
-                rows = torch.from_numpy(b).to(self.device)
-                self.ring[rows] = ring.to(self.device)
-                self.st[rows] = st.to(self.device, torch.int32)
-                self.totals[rows] = totals.to(self.device, torch.int32)
 
 
 def note_target(scorer):
@@ -342,7 +287,7 @@ def discover(front):
     return note_target(front.scorer), front.scorer.hop, False
 
 
-class ProvenanceScorer(Layer):
+class ProvenanceScorer(WithholdingLayer):
     """``scorer`` (a streaming scorer, a cascade or a quality layer) with the provenance layer behind it under ``policy``;
     see the module docstring.  It goes where the quality layer goes, around it and inside the verdict layer:
     ``JitterScorer(GatedScorer(VerdictScorer(ProvenanceScorer(QualityScorer(inner, qpolicy), ppolicy), vpolicy)), 8000,
@@ -359,47 +304,17 @@ class ProvenanceScorer(Layer):
     verifier scores of the slots that are not valid."""
 
     layer = "provenance"
-    _keys = ("prov_ring", "prov_state", "prov_totals")
     _part = "provenance part (it was not exported by a ProvenanceScorer)"
+    _does = "hops are scored and counted"
 
     def __init__(self, scorer, policy=None):
-        super().__init__(scorer)
-        self.policy = ProvenancePolicy() if policy is None else policy
-        self.provenance = Provenance(scorer.S, self.policy, scorer.hop, scorer.window, scorer.device)
-        self.last_meas = torch.empty(0, 3, dtype=torch.int32, device=self.provenance.device)
-        self._cascade = self._below("cascade") is not None  # (then what stands directly below hands the verifier scores on)
-        self._last = None  # (slots, verifier scores with the invalid slots' made NaN) of the newest push
+        super().__init__(scorer, ProvenancePolicy() if policy is None else policy, Provenance)
+        self.provenance = self._table
         self._note = None  # (slots, counts) for the next push
-
-    @property
-    def valid(self):
-        return self.provenance.valid
 
     @property
     def synthetic(self):
         return self.provenance.synthetic
-
-    def stats(self):
-        """``Provenance.stats``."""
-        return self.provenance.stats()
-
-    # (around a cascade: its results, for the caller and for the verdict layer)
-    @property
-    def verified(self):
-        return self.scorer.verified
-
-    @property
-    def verified_at(self):
-        return self.scorer.verified_at
-
-    def take_events(self):
-        """``CascadeScorer.take_events`` (the verifier scores as the verifier gave them)."""
-        return self.scorer.take_events()
-
-    def last_verified(self):
-        """``CascadeScorer.last_verified`` of the newest push; with ``abstain`` on, the verifier scores of the slots that
-        are not valid are NaN."""
-        return self._last
 
     def note_synthetic(self, counts, slots):
         """counts: (A,) int32 on the scorer's device, the synthetic samples of the hop the next ``push`` brings for each of
@@ -410,55 +325,15 @@ class ProvenanceScorer(Layer):
             raise ValueError(f"counts: an int32 tensor of shape {(len(idx),)} on {dev}")
         self._note = (idx, counts)
 
-    def push(self, chunk, slots=None):
-        """chunk and slots: the inner scorer's own rule (an fp32 chunk on the scorer's GPU) -> the inner scores with NaN
-        where the slot's score is withheld, ``None`` where the inner ``push`` returned ``None``."""
-        need_gpu(self.device, "hops are scored and counted")
-        inner, dev = self.scorer, self.provenance.device
-        idx = self._named(slots)
-        A = len(idx)
+    def _operand(self, chunk, idx):
+        """The counts of the note this push consumes, or zeros."""
         note, self._note = self._note, None
-        if note is not None and note[0] != idx:
+        if note is None:
+            return torch.zeros(len(idx), dtype=torch.int32, device=self.provenance.device)
+        if note[0] != idx:
             raise ValueError(f"the note names the slots {note[0]}, this push {idx}: a note is for the next push of exactly its slots")
-        if not isinstance(chunk, torch.Tensor) or chunk.device != dev or chunk.dtype != torch.float32 or chunk.shape != (A, self.hop):
-            raise ValueError(f"expected a CUDA fp32 tensor of shape {(A, self.hop)} on {dev} (one hop per named slot)")
-        self._last = None
-        scores = inner.push(chunk, slots)
-        if not A:
-            return scores
-        if scores is not None and (scores.shape != (A,) or scores.device != dev):
-            raise RuntimeError(f"the inner scorer returned {tuple(scores.shape)} scores on {scores.device} for {A} rows")
-        if scores is not None and scores.dtype != torch.float32:
-            scores = scores.to(torch.float32)
-        with torch.cuda.device(dev):
-            counts = torch.zeros(A, dtype=torch.int32, device=dev) if note is None else note[1]
-        out, self.last_meas = self.provenance.update(counts, idx, hop_index=(inner.samples_seen[idx] // self.hop).numpy(), scores=scores)
-        # what stands directly below (the cascade, or a quality layer that has made its own invalid slots' NaN), then this
-        # layer's NaN on top: the verdict layer reads ``last_verified`` of what is directly below IT
-        last = inner.last_verified() if self._cascade else None
-        if last is not None and self.policy.abstain:
-            chosen, v = last
-            with torch.cuda.device(dev):
-                rows = torch.empty(chosen.numel(), dtype=torch.int64, pin_memory=True)
-                rows.copy_(chosen)
-                ok = self.provenance.valid.index_select(0, rows.to(dev, non_blocking=True))
-                last = (chosen, torch.where(ok, v, torch.full_like(v, float("nan"))))
-        self._last = last
-        return out
+        return note[1]
 
     # ---- sessions (afx._layer.Layer) -----------------------------------------------------------------------------------------
     def _meta(self):
         return dict(provenance=PROVENANCE_FORMAT, provenance_window=dict(W=self.provenance.W, hop=self.hop))
-
-    def _reset(self, idx):
-        self.provenance.reset(idx)
-
-    def _export(self, idx, st):
-        ring, state, totals = self.provenance.export_rows(idx)
-        return dict(prov_ring=ring, prov_state=state, prov_totals=totals)
-
-    def _check(self, state, n):
-        return self.provenance.check_rows(*(state.tensors[k] for k in self._keys), state.seen, n)
-
-    def _import(self, idx, rows):
-        self.provenance.import_rows(idx, *rows)

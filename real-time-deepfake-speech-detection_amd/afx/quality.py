@@ -58,7 +58,7 @@ of 1e-7 (-70 dBFS); ``dc``: a mean of 5 % of full scale; ``max_bad=0``: one flag
 import numpy as np
 import torch
 
-from ._layer import N_MAX, Layer, _on, fp32, hop_indices, integer, need_gpu, slot_count, slots_of, upload_pairs
+from ._layer import N_MAX, Field, HopTable, WindowState, WithholdingLayer, _on, fp32, hop_indices, integer, need_gpu, slot_count, slots_of
 from ._lib import call_on, check, lib, ptr
 
 QUALITY_FORMAT = 1   # layout of the quality part of a StreamState: import_slots refuses any other
@@ -79,24 +79,11 @@ def window_hops(window, hop):
     return W
 
 
-class QualityState:
+class QualityState(WindowState):
     """Host mirrors of the whole quality state of S slots: ``ring`` (S, W) uint8, ``st`` (S, 3) int32 = (last, run, bad),
     ``totals`` (S, 6) int32; a new stream everywhere."""
 
-    def __init__(self, S, W):
-        self.ring = np.zeros((S, W), dtype=np.uint8)
-        self.st = np.zeros((S, 3), dtype=np.int32)
-        self.totals = np.zeros((S, 6), dtype=np.int32)
-
-    def reset(self, slots):
-        """What ``Quality.reset`` does: ``st`` and ``totals`` cleared, the ring left alone."""
-        self.st[slots] = 0
-        self.totals[slots] = 0
-
-    def copy(self):
-        c = QualityState(*self.ring.shape)
-        c.ring, c.st, c.totals = self.ring.copy(), self.st.copy(), self.totals.copy()
-        return c
+    ring_dtype, new, n_totals = np.uint8, (0, 0, 0), 6
 
 
 def hop_sums(x):
@@ -259,21 +246,23 @@ class QualityPolicy:
         return [all_meas[i, :hops[i]].copy() for i in range(n)]
 
 
-class Quality:
+class Quality(HopTable):
     """The per-slot quality state of ``S`` streams under ``policy`` for hops of ``hop`` samples and a window of ``window``
     samples, on ``device``; see the module docstring.  ``update`` is one pinned upload of the header and one
     ``afx_k_quality`` launch, with no synchronisation; ``valid`` and ``bad`` are views of the state on the device;
     ``stats()`` is the only read-back."""
 
+    meas_cols = 8
+
     def __init__(self, S, policy, hop, window, device="cuda"):
         S = slot_count(S, policy, QualityPolicy)
         self.W = window_hops(window, hop)
-        self.S, self.policy, self.hop, self.window = S, policy, int(hop), int(window)
+        self.policy, self.hop, self.window = policy, int(hop), int(window)
         self.e_quiet, self.d = (float(v) for v in policy.bounds(self.hop))
-        self.ring = torch.zeros(self.S, self.W, dtype=torch.uint8, device=device)
-        self.device = self.ring.device  # (with its index: every launch of an update goes to THIS GPU)
-        self.st = torch.zeros(self.S, 3, dtype=torch.int32, device=self.device)
-        self.totals = torch.zeros(self.S, 6, dtype=torch.int32, device=self.device)
+        # (``reset`` leaves the ring alone: a new session's window count never reaches back before its first hop)
+        self._allocate(S, device, Field("quality_ring", "ring", (self.W,), torch.uint8),
+                       Field("quality_state", "st", (3,), torch.int32, host=True, new=(0, 0, 0)),
+                       Field("quality_totals", "totals", (6,), torch.int32, host=True, new=0))
 
     # ---- views ---------------------------------------------------------------------------------------------------------------
     @property
@@ -315,26 +304,16 @@ class Quality:
         if (not isinstance(hops, torch.Tensor) or hops.dtype != torch.float32 or hops.shape != (A, self.hop)
                 or hops.device != self.device):
             raise ValueError(f"hops: an fp32 tensor of shape {(A, self.hop)} on {self.device}")
-        k = hop_indices(hop_index, A, 1)
-        if scores is not None and (not isinstance(scores, torch.Tensor) or scores.dtype != torch.float32 or scores.shape != (A,)
-                                   or scores.device != self.device):
-            raise ValueError(f"scores: an fp32 tensor of shape {(A,)} on {self.device}")
-        if not A:
-            empty = torch.empty(0, dtype=torch.float32, device=self.device)
-            return (None if scores is None else empty), torch.empty(0, 8, dtype=torch.int32, device=self.device)
-        return self._update(hops, b, k, scores)
+        k, scores = self._hop_rows(A, hop_index, scores)
+        return self._update(hops, b, k, scores) if A else self._no_rows(scores)
 
     def _update(self, hops, slots, hop_index, scores):
         need_gpu(self.device, "hops are measured")
         p, A = self.policy, len(slots)
         if hops.stride(1) != 1 or (A > 1 and hops.stride(0) < self.hop):  # (a transposed or expanded view)
             hops = hops.contiguous()
-        if scores is not None and A > 1 and scores.stride(0) < 1:
-            scores = scores.contiguous()
         with torch.cuda.device(self.device):
-            d = upload_pairs(slots, hop_index, self.device)
-            meas = torch.empty(A, 8, dtype=torch.int32, device=self.device)
-            out = None if scores is None else torch.empty(A, dtype=torch.float32, device=self.device)
+            d, meas, out = self._buffers(slots, hop_index, scores)
             check(call_on(self.ring, lib().afx_k_quality, ptr(hops), max(hops.stride(0), self.hop), A, self.hop, ptr(d), ptr(scores),
                           1 if scores is None else max(scores.stride(0), 1), p.clip, p.clip_count, p.flat_run, self.e_quiet, self.d,
                           p.mask, p.max_bad, int(p.abstain), ptr(self.ring), self.W, ptr(self.st), ptr(self.totals), self.S,
@@ -342,32 +321,10 @@ class Quality:
         return out, meas
 
     # ---- sessions ------------------------------------------------------------------------------------------------------------
-    def reset(self, slots):
-        """The named slots begin a new stream: ``q_state = (0, 0, 0)`` and ``q_totals = 0``.  The ring is left alone: a new
-        session's window count never reaches back before its first hop."""
-        b = slots_of(slots, self.S)
-        if b.size:
-            with _on(self.device):
-                rows = torch.from_numpy(b).to(self.device)
-                self.st[rows] = 0
-                self.totals[rows] = 0
-
-    def export_rows(self, slots):
-        """-> (quality_ring (n, W) uint8 on the device, quality_state (n, 3) and quality_totals (n, 6) int64 on the host) of
-        the named slots."""
-        with _on(self.device):
-            rows = torch.from_numpy(slots_of(slots, self.S)).to(self.device)
-            return self.ring[rows].clone(), self.st[rows].to("cpu", torch.int64), self.totals[rows].to("cpu", torch.int64)
-
-    def check_rows(self, ring, st, totals, n):
+    def check_rows(self, rows, n, seen):
         """Refuses (ValueError) what cannot be the state of n sessions of this window; -> (ring, st, totals)."""
-        if not isinstance(ring, torch.Tensor) or ring.dtype != torch.uint8 or tuple(ring.shape) != (n, self.W):
-            raise ValueError(f"import_slots: quality_ring is {(n, self.W)} uint8")
-        if not isinstance(st, torch.Tensor) or st.dtype != torch.int64 or tuple(st.shape) != (n, 3):
-            raise ValueError("import_slots: quality_state is (n, 3) int64")
-        if not isinstance(totals, torch.Tensor) or totals.dtype != torch.int64 or tuple(totals.shape) != (n, 6):
-            raise ValueError("import_slots: quality_totals is (n, 6) int64")
-        st, totals = st.cpu(), totals.cpu()
+        self.check_shapes(rows, n)
+        ring, st, totals = rows[0], rows[1].cpu(), rows[2].cpu()
         last, run, bad = st.unbind(1)
         if bool(((last < -(1 << 31)) | (last > N_MAX)).any()):
             raise ValueError("import_slots: a session's newest sample is not 32 bits")
@@ -381,18 +338,8 @@ class Quality:
             raise ValueError("import_slots: a ring entry has a bit that is no flag")
         return ring, st, totals
 
-    def import_rows(self, slots, ring, st, totals):
-        """The named slots take the (checked) state rows."""
-        b = slots_of(slots, self.S)
-        if b.size:
-            with _on(self.device):
-                rows = torch.from_numpy(b).to(self.device)
-                self.ring[rows] = ring.to(self.device)
-                self.st[rows] = st.to(self.device, torch.int32)
-                self.totals[rows] = totals.to(self.device, torch.int32)
 
-
-class QualityScorer(Layer):
+class QualityScorer(WithholdingLayer):
     """``scorer`` (whatever stands below the quality layer in the stack order of ``afx._layer``) with the quality layer
     behind it under ``policy``; see the module docstring.  It presents the surface the verdict layer, the gate and the
     fronts drive an inner scorer through and goes where the cascade goes, inside the verdict layer:
@@ -416,91 +363,21 @@ class QualityScorer(Layer):
     the slot's next hop)."""
 
     layer = "quality"
-    _keys = ("quality_ring", "quality_state", "quality_totals")
     _part = "quality part (it was not exported by a QualityScorer)"
+    _does = "hops are scored and measured"
 
     def __init__(self, scorer, policy=None):
-        super().__init__(scorer)
-        self.policy = QualityPolicy() if policy is None else policy
-        self.quality = Quality(scorer.S, self.policy, scorer.hop, scorer.window, scorer.device)
-        self.last_meas = torch.empty(0, 8, dtype=torch.int32, device=self.quality.device)
-        self._cascade = self._below("cascade")
-        self._last = None  # (slots, verifier scores with the invalid slots' made NaN) of the newest push
-
-    @property
-    def valid(self):
-        return self.quality.valid
+        super().__init__(scorer, QualityPolicy() if policy is None else policy, Quality)
+        self.quality = self._table
 
     @property
     def flags(self):
         """(S,) uint8 on the device: the flags of each slot's newest hop, 0 before its first."""
         return self.quality.flags_at((self.samples_seen // self.hop).numpy())
 
-    def stats(self):
-        """``Quality.stats``."""
-        return self.quality.stats()
-
-    # (around a cascade: its results, for the caller and for the verdict layer)
-    @property
-    def verified(self):
-        return self.scorer.verified
-
-    @property
-    def verified_at(self):
-        return self.scorer.verified_at
-
-    def take_events(self):
-        """``CascadeScorer.take_events`` (the verifier scores as the verifier gave them)."""
-        return self.scorer.take_events()
-
-    def last_verified(self):
-        """``CascadeScorer.last_verified`` of the newest push; with ``abstain`` on, the verifier scores of the slots that
-        are not valid are NaN."""
-        return self._last
-
-    def push(self, chunk, slots=None):
-        """chunk and slots: the inner scorer's own rule (an fp32 chunk on the scorer's GPU) -> the inner scores with NaN
-        where the slot's score is withheld, ``None`` where the inner ``push`` returned ``None``."""
-        need_gpu(self.device, "hops are scored and measured")
-        inner = self.scorer
-        idx = self._named(slots)
-        A = len(idx)
-        if (not isinstance(chunk, torch.Tensor) or chunk.device != self.quality.device or chunk.dtype != torch.float32
-                or chunk.shape != (A, self.hop)):
-            raise ValueError(f"expected a CUDA fp32 tensor of shape {(A, self.hop)} on {self.quality.device} (one hop per named slot)")
-        self._last = None
-        scores = inner.push(chunk, slots)
-        if not A:
-            return scores
-        if scores is not None and (scores.shape != (A,) or scores.device != self.quality.device):
-            raise RuntimeError(f"the inner scorer returned {tuple(scores.shape)} scores on {scores.device} for {A} rows")
-        if scores is not None and scores.dtype != torch.float32:
-            scores = scores.to(torch.float32)
-        out, self.last_meas = self.quality.update(chunk, idx, hop_index=(inner.samples_seen[idx] // self.hop).numpy(), scores=scores)
-        last = self._cascade.last_verified() if self._cascade is not None else None
-        if last is not None and self.policy.abstain:
-            chosen, v = last
-            with torch.cuda.device(self.device):
-                rows = torch.empty(chosen.numel(), dtype=torch.int64, pin_memory=True)
-                rows.copy_(chosen)
-                ok = self.quality.valid.index_select(0, rows.to(self.device, non_blocking=True))
-                last = (chosen, torch.where(ok, v, torch.full_like(v, float("nan"))))
-        self._last = last
-        return out
+    def _operand(self, chunk, idx):
+        return chunk  # (the hops the model saw are the hops measured)
 
     # ---- sessions (afx._layer.Layer) -----------------------------------------------------------------------------------------
     def _meta(self):
         return dict(quality=QUALITY_FORMAT, quality_window=dict(W=self.quality.W, hop=self.hop))
-
-    def _reset(self, idx):
-        self.quality.reset(idx)
-
-    def _export(self, idx, st):
-        ring, state, totals = self.quality.export_rows(idx)
-        return dict(quality_ring=ring, quality_state=state, quality_totals=totals)
-
-    def _check(self, state, n):
-        return self.quality.check_rows(*(state.tensors[k] for k in self._keys), n)
-
-    def _import(self, idx, rows):
-        self.quality.import_rows(idx, *rows)

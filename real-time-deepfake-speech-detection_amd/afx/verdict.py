@@ -47,7 +47,7 @@ engineering defaults, not tuned ones: there is no labelled speech behind them, a
 import numpy as np
 import torch
 
-from ._layer import N_MAX, Layer, _on, fp32, hop_indices, integer, need_gpu, slot_count, slots_of, upload_pairs
+from ._layer import N_MAX, Field, Layer, SlotTable, fp32, hop_indices, integer, need_gpu, returned_scores, slot_count, slots_of, upload_pairs
 from ._lib import call_on, check, lib, ptr
 
 VERDICT_FORMAT = 1  # layout of the verdict part of a StreamState: import_slots refuses any other
@@ -157,7 +157,7 @@ def new_state(S):
     return np.full(S, np.nan, dtype=np.float32), st
 
 
-class Verdicts:
+class Verdicts(SlotTable):
     """The per-slot verdict state of ``S`` streams under ``policy`` on ``device``, and the event log; see the module
     docstring.  ``update`` is one pinned upload of the header and one ``afx_k_verdict`` launch, with no synchronisation;
     ``alarm`` / ``smoothed`` / ``alarm_since`` are views of the state on the device; ``take_events()`` is the only
@@ -169,12 +169,10 @@ class Verdicts:
     every few pushes."""
 
     def __init__(self, S, policy, device="cuda"):
-        self.S, self.policy = slot_count(S, policy, VerdictPolicy), policy
+        self.policy = policy
+        self._allocate(slot_count(S, policy, VerdictPolicy), device, Field("verdict_m", "m", (), torch.float32, new=float("nan")),
+                       Field("verdict_state", "st", (4,), torch.int32, host=True, new=(0, 0, 0, -1)))
         self.cap = max(4 * self.S, 1024)
-        m, st = new_state(self.S)
-        self.m = torch.from_numpy(m).to(device)
-        self.device = self.m.device  # (with its index: every launch of an update goes to THIS GPU)
-        self.st = torch.from_numpy(st).to(self.device)
         self.log = torch.zeros(1 + 4 * self.cap, dtype=torch.int32, device=self.device)
         self._pending = 0  # upper bound on log[0]: the rows of the updates since the log was last cleared
         self._kept = []    # events the host took itself before an overflow, (n, 4) int32 arrays in log order
@@ -263,28 +261,11 @@ class Verdicts:
         return ev[:, 0].copy(), ev[:, 1].copy(), ev[:, 2].copy(), ev[:, 3].copy().view(np.float32)
 
     # ---- sessions ------------------------------------------------------------------------------------------------------------
-    def reset(self, slots):
-        """The named slots begin a new stream: ``m = NaN``, ``(n, run, on, since) = (0, 0, 0, -1)``.  The log is untouched."""
-        b = slots_of(slots, self.S)
-        if b.size:
-            with _on(self.device):
-                rows = torch.from_numpy(b).to(self.device)
-                self.m[rows] = float("nan")
-                self.st[rows] = torch.tensor([0, 0, 0, -1], dtype=torch.int32, device=self.device)
-
-    def export_rows(self, slots):
-        """-> (verdict_m (n,) fp32 on the device, verdict_state (n, 4) int64 on the host) of the named slots."""
-        with _on(self.device):
-            rows = torch.from_numpy(slots_of(slots, self.S)).to(self.device)
-            return self.m[rows].clone(), self.st[rows].to("cpu", torch.int64)
-
-    def check_rows(self, m, st, n):
+    # (``reset``: ``m = NaN``, ``(n, run, on, since) = (0, 0, 0, -1)``; the log is untouched)
+    def check_rows(self, rows, n, seen):
         """Refuses (ValueError) what cannot be the state of n sessions under this policy; -> (m, st) on the host."""
-        if not isinstance(m, torch.Tensor) or m.dtype != torch.float32 or tuple(m.shape) != (n,):
-            raise ValueError("import_slots: verdict_m is (n,) float32")
-        if not isinstance(st, torch.Tensor) or st.dtype != torch.int64 or tuple(st.shape) != (n, 4):
-            raise ValueError("import_slots: verdict_state is (n, 4) int64")
-        m, st = m.cpu(), st.cpu()
+        self.check_shapes(rows, n)
+        m, st = rows[0].cpu(), rows[1].cpu()
         cnt, run, on, since = st.unbind(1)
         p = self.policy
         if bool(((on != 0) & (on != 1)).any()):
@@ -299,15 +280,6 @@ class Verdicts:
         if bool((torch.isnan(m) != (cnt == 0)).any()):
             raise ValueError("import_slots: a session's smoothed score is NaN after a score, or a number before the first")
         return m, st
-
-    def import_rows(self, slots, m, st):
-        """The named slots take the (checked) state rows."""
-        b = slots_of(slots, self.S)
-        if b.size:
-            with _on(self.device):
-                rows = torch.from_numpy(b).to(self.device)
-                self.m[rows] = m.to(self.device)
-                self.st[rows] = st.to(self.device, torch.int32)
 
 
 class VerdictScorer(Layer):
@@ -330,13 +302,12 @@ class VerdictScorer(Layer):
     refused."""
 
     layer = "verdict"
-    _keys = ("verdict_m", "verdict_state")
     _part = "verdict part (it was not exported by a VerdictScorer)"
 
     def __init__(self, scorer, policy):
         super().__init__(scorer)
         self.policy = policy
-        self.verdicts = Verdicts(scorer.S, policy, scorer.device)
+        self.verdicts = self._own(Verdicts(scorer.S, policy, scorer.device))
         # (a quality layer in between hands the verifier scores on)
         self._verified = self._below("cascade") is not None and policy.verifier_enter is not None
 
@@ -368,8 +339,7 @@ class VerdictScorer(Layer):
         A = len(idx)
         if not A:
             return scores
-        if scores.shape != (A,) or scores.device != self.device or scores.dtype != torch.float32:
-            raise RuntimeError(f"the inner scorer returned {tuple(scores.shape)} {scores.dtype} scores on {scores.device} for {A} rows")
+        returned_scores(scores, A, self.device)
         verified = None
         last = inner.last_verified() if self._verified else None
         if last is not None:  # this push verified something: its scores, by row
@@ -386,16 +356,3 @@ class VerdictScorer(Layer):
     # ---- sessions (afx._layer.Layer) -----------------------------------------------------------------------------------------
     def _meta(self):
         return dict(verdict=VERDICT_FORMAT, verdict_policy=self.policy.params())
-
-    def _reset(self, idx):
-        self.verdicts.reset(idx)
-
-    def _export(self, idx, st):
-        m, state = self.verdicts.export_rows(idx)
-        return dict(verdict_m=m, verdict_state=state)
-
-    def _check(self, state, n):
-        return self.verdicts.check_rows(state.tensors["verdict_m"], state.tensors["verdict_state"], n)
-
-    def _import(self, idx, rows):
-        self.verdicts.import_rows(idx, *rows)

@@ -92,11 +92,12 @@ def _chain(S, front="packet", cooldown=0, confirm=1):
     from afx.evidence import EvidencePolicy, EvidenceScorer
     from afx.ingest import PacketScorer
     from afx.jitter import JitterScorer
+    from afx.provenance import ProvenancePolicy, ProvenanceScorer
     from afx.quality import QualityPolicy, QualityScorer
     from afx.vad import GatedScorer
     from afx.verdict import VerdictPolicy, VerdictScorer
-    g = GatedScorer(EvidenceScorer(VerdictScorer(QualityScorer(CascadeScorer(_bare(S), _Model(), CascadePolicy(0.0, 2, cooldown=cooldown)),
-                                                               QualityPolicy()),
+    quality = QualityScorer(CascadeScorer(_bare(S), _Model(), CascadePolicy(0.0, 2, cooldown=cooldown)), QualityPolicy())
+    g = GatedScorer(EvidenceScorer(VerdictScorer(ProvenanceScorer(quality, ProvenancePolicy()),
                                                  VerdictPolicy(0.0, 0.5, confirm=confirm, release=2, verifier_enter=-0.5)), EvidencePolicy()))
     return PacketScorer(g, 8000, "mulaw") if front == "packet" else JitterScorer(g, 8000, "mulaw", 4)
 
@@ -105,9 +106,11 @@ def _layers(front):
     gate = front.scorer
     evidence = gate.scorer
     verdict = evidence.scorer
-    quality = verdict.scorer
+    provenance = verdict.scorer
+    quality = provenance.scorer
     cascade = quality.scorer
-    return dict(front=front, gate=gate, evidence=evidence, verdict=verdict, quality=quality, cascade=cascade, base=cascade.screen)
+    return dict(front=front, gate=gate, evidence=evidence, verdict=verdict, provenance=provenance, quality=quality, cascade=cascade,
+                base=cascade.screen)
 
 
 def _bits(x):
@@ -138,6 +141,12 @@ def _dirty(front, seed, roll=0):
     q.ring[:] = torch.randint(0, 32, (S, 4), generator=g).to(torch.uint8)
     q.st[:] = torch.tensor(pick([[_bits(0.5), 1, 1], [0, 7000, 2], [0, 0, 0], [5, 3, 0]]), dtype=torch.int32)
     q.totals[:] = torch.tensor(pick([[2, 0, 1, 0, 0, 0], [5, 0, 0, 2, 3, 0], [0] * 6, [1, 0, 0, 0, 0, 1]]), dtype=torch.int32)
+    p = L["provenance"].provenance                        # (its own generator: the other layers' rows stay what they were)
+    p.ring[:] = torch.randint(0, 401, (S, 4), generator=torch.Generator().manual_seed(100 + seed), dtype=torch.int32)
+    hops, slot_of = torch.tensor(inner_hops)[:, None], torch.arange(1, 5)[None, :]  # ring position j holds hop j + 1, j + 5, ...
+    total = (p.ring * ((slot_of <= hops) | (hops >= 4))).sum(dim=1)  # the window's hops: all four once four were seen, else 1..k
+    p.st[:] = torch.stack([total, total <= p.limit], dim=1).to(torch.int32)
+    p.totals[:] = torch.tensor(pick([[2, 30, 1], [5, 900, 2], [0, 0, 0], [1, 0, 0]]), dtype=torch.int32)
     v = L["verdict"].verdicts
     v.m[:] = torch.tensor(pick([0.25, -0.3, NAN, 0.1]))
     v.st[:] = torch.tensor(pick([[5, 2, 0, -1], [7, 1, 1, 4], [0, 0, 0, -1], [1, 0, 0, -1]]), dtype=torch.int32)
@@ -167,7 +176,9 @@ def _dirty(front, seed, roll=0):
 def _snap(front):
     L = _layers(front)
     c, q, v, e, g, f = L["cascade"], L["quality"].quality, L["verdict"].verdicts, L["evidence"].evidence, L["gate"], L["front"]
-    parts = [L["base"].ring, L["base"]._seen, c.wait, c.verified, c.verified_at, q.ring, q.st, q.totals, v.m, v.st, v.log,
+    p = L["provenance"].provenance
+    parts = [L["base"].ring, L["base"]._seen, c.wait, c.verified, c.verified_at, q.ring, q.st, q.totals, p.ring, p.st, p.totals,
+             v.m, v.st, v.log,
              e.hist, e.sring, e.rec, e.left, e._pool, g.nf, g.h, g.ring, g._fill, g._head, g._seen, f.ring, f.hist, f._fill, f._head, f._in]
     return [torch.as_tensor(p).clone() for p in parts]
 
@@ -189,19 +200,20 @@ def _through_a_file(st):
 
 # ---- 2. the frozen layout ------------------------------------------------------------------------------------------------------
 META = ["arch", "build_id", "cascade", "cascade_policy", "cascade_verifier", "dtype", "evidence", "evidence_pre", "extractor_mode",
-        "fingerprint", "format", "gate", "gate_params", "head", "hop", "ingest", "input_rate", "kind", "n_layers", "quality",
-        "quality_window", "resampler", "verdict", "verdict_policy", "window"]
-f32, i64, u8 = torch.float32, torch.int64, torch.uint8
+        "fingerprint", "format", "gate", "gate_params", "head", "hop", "ingest", "input_rate", "kind", "n_layers", "provenance",
+        "provenance_window", "quality", "quality_window", "resampler", "verdict", "verdict_policy", "window"]
+f32, i64, i32, u8 = torch.float32, torch.int64, torch.int32, torch.uint8
 COMMON = {"cascade_verified": (f32, (2,)), "cascade_verified_at": (i64, (2,)), "cascade_wait": (i64, (2,)),
           "evidence_hist": (f32, (2, 16000)), "evidence_scores": (f32, (2, 4)), "gate_fill": (i64, (2,)), "gate_hang": (i64, (2,)),
-          "gate_inner_seen": (i64, (2,)), "gate_nf": (f32, (2,)), "gate_pending": (f32, (2, 4000)), "quality_ring": (u8, (2, 4)),
+          "gate_inner_seen": (i64, (2,)), "gate_nf": (f32, (2,)), "gate_pending": (f32, (2, 4000)), "prov_ring": (i32, (2, 4)),
+          "prov_state": (i64, (2, 2)), "prov_totals": (i64, (2, 3)), "quality_ring": (u8, (2, 4)),
           "quality_state": (i64, (2, 3)), "quality_totals": (i64, (2, 6)), "samples": (f32, (2, 16000)), "verdict_m": (f32, (2,)),
           "verdict_state": (i64, (2, 4))}
 LAYOUT = {
     "packet": (META, dict(COMMON, ingest_fill=(i64, (2,)), ingest_in=(i64, (2,)), ingest_pending=(f32, (2, 16000)),
                           resample_hist=(f32, (2, 20)))),
     "jitter": (sorted(set(META) - {"ingest"} | {"jitter", "jitter_conceal", "jitter_depth", "jitter_fade", "jitter_period"}),
-               dict(COMMON, jitter_book=(i64, (2, 8)), jitter_fill=(i64, (2,)), jitter_intervals=(i64, (2, 1, 2)),
+               dict(COMMON, gate_syn=(i64, (2, 25)), jitter_syn=(u8, (2, 16000)), jitter_book=(i64, (2, 8)), jitter_fill=(i64, (2,)), jitter_intervals=(i64, (2, 1, 2)),
                     jitter_pending=(f32, (2, 16000)), jitter_ring=(f32, (2, 324)), jitter_stats=(i64, (2, 5)))),
 }
 
@@ -213,6 +225,7 @@ def test_the_layout_of_a_full_chains_state_is_frozen_and_survives_a_file(built, 
     assert sorted(st.meta) == meta
     assert {k: (t.dtype, tuple(t.shape)) for k, t in st.tensors.items()} == tensors
     assert (st.meta["format"], st.meta["cascade"], st.meta["quality"], st.meta["verdict"], st.meta["evidence"], st.meta["gate"]) == (1,) * 6
+    assert st.meta["provenance"] == 1
     b = _chain(4, front)
     b.import_slots([1, 3], _through_a_file(st))
     back = b.export_slots([1, 3])
@@ -234,21 +247,26 @@ def test_a_refusal_at_any_depth_leaves_every_layer_unchanged(built):
     without = lambda k: StreamState(m, good.seen, {n: v for n, v in t.items() if n != k})  # noqa: E731
     bad_quality, bad_verdict = t["quality_state"].clone(), t["verdict_state"].clone()
     bad_quality[0, 2], bad_verdict[1, 2] = W + 1, 2
+    bad_prov = t["prov_state"].clone()
+    bad_prov[0, 0] += 1  # a total that is not the ring's sum
     spoiled = {
         "cascade_wait": with_t(cascade_wait=torch.tensor([COOLDOWN + 1, 0])),
         "quality_state": with_t(quality_state=bad_quality),
+        "prov_state": with_t(prov_state=bad_prov),
         "verdict_state": with_t(verdict_state=bad_verdict),
         "evidence_hist": with_t(evidence_hist=t["evidence_hist"][:, :-1]),
         "gate_fill": with_t(gate_fill=torch.tensor([H, 0])),
         "ingest_fill": with_t(ingest_fill=torch.tensor([-1, 100])),
         "meta cascade_policy": with_m(cascade_policy=dict(m["cascade_policy"], budget=1)),
         "meta quality_window": with_m(quality_window=dict(W=W + 1, hop=H)),
+        "meta provenance_window": with_m(provenance_window=dict(W=W + 1, hop=H)),
         "meta verdict_policy": with_m(verdict_policy=dict(m["verdict_policy"], release=3)),
         "meta evidence_pre": with_m(evidence_pre=m["evidence_pre"] - 1),
         "meta gate_params": with_m(gate_params=dict(m["gate_params"], hang=19)),
         "meta input_rate": with_m(input_rate=16000),
         "no cascade_verified": without("cascade_verified"),
         "no quality_totals": without("quality_totals"),
+        "no prov_totals": without("prov_totals"),
         "no verdict_m": without("verdict_m"),
         "no evidence_scores": without("evidence_scores"),
         "no gate_nf": without("gate_nf"),
@@ -275,6 +293,42 @@ def test_a_refusal_at_any_depth_leaves_every_layer_unchanged(built):
     L, A = _layers(b), _layers(a)
     assert L["cascade"].wait[[3, 1]].tolist() == A["cascade"].wait[[2, 0]].tolist()
     assert L["quality"].quality.st[[3, 1]].tolist() == A["quality"].quality.st[[2, 0]].tolist()
+    assert L["provenance"].provenance.st[[3, 1]].tolist() == A["provenance"].provenance.st[[2, 0]].tolist()
     assert L["verdict"].verdicts.st[[3, 1]].tolist() == A["verdict"].verdicts.st[[2, 0]].tolist()
     assert L["gate"]._seen[[3, 1]].tolist() == A["gate"]._seen[[2, 0]].tolist() and L["base"]._seen[[3, 1]].tolist() == A["base"]._seen[[2, 0]].tolist()
     assert L["front"]._fill[[3, 1]].tolist() == A["front"]._fill[[2, 0]].tolist() and L["front"]._head[[3, 1]].tolist() == [0, 0]
+
+
+# ---- 4. every tensor of the per-slot tables is held to its dtype and shape before anything changes ---------------------------
+TABLE_FIELDS = ["quality_ring", "quality_state", "quality_totals", "prov_ring", "prov_state", "prov_totals", "verdict_m", "verdict_state",
+                "evidence_hist", "evidence_scores"]  # (the cascade's part is checked by the cascade itself)
+
+
+@pytest.fixture(scope="module")
+def a_good_state(built):
+    """(a chain of 4 slots in use, its snapshot, a good state of two sessions of another chain): a refusal leaves the chain as
+    it was, so every case shares it."""
+    a, b = _chain(4, "packet", COOLDOWN, CONFIRM), _chain(4, "packet", COOLDOWN, CONFIRM)
+    _dirty(a, 3)
+    _dirty(b, 4, roll=1)
+    return b, _snap(b), _through_a_file(a.export_slots([2, 0]))
+
+
+def _spoil(t, how):
+    if how == "dtype":
+        return t.to({f32: torch.float64, i64: i32, i32: i64, u8: torch.int16}[t.dtype])
+    if how == "shape":
+        return t[:, :-1] if t.ndim > 1 else t[:, None]
+    return t[:1]  # one row for two sessions
+
+
+@pytest.mark.parametrize("how", ["dtype", "shape", "rows"])
+@pytest.mark.parametrize("key", TABLE_FIELDS)
+def test_a_table_tensor_of_another_dtype_shape_or_row_count_is_refused_and_changes_nothing(a_good_state, key, how):
+    from afx.streaming import StreamState
+    b, before, good = a_good_state
+    state = StreamState(good.meta, good.seen, good.tensors)
+    state.tensors[key] = _spoil(good.tensors[key], how)  # (behind the constructor's back: it counts the rows itself)
+    with pytest.raises(ValueError, match="tensor '" + key + "' has 1 rows" if how == "rows" else "import_slots: " + key + " "):
+        b.import_slots([3, 1], state)
+    assert all(_same(u, v) for u, v in zip(before, _snap(b)))

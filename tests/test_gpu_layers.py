@@ -1,5 +1,5 @@
 """The whole streaming stack on the GPU (afx/_layer.py): a live session of the longest chain,
-``PacketScorer(GatedScorer(EvidenceScorer(VerdictScorer(QualityScorer(CascadeScorer(...))))), 8000, "mulaw")``, moves between
+``PacketScorer(GatedScorer(EvidenceScorer(VerdictScorer(ProvenanceScorer(QualityScorer(CascadeScorer(...)))))), 8000, "mulaw")``, moves between
 scorers through host memory and a file and continues bit for bit in every layer.  Every comparison is exact.
 
 The audio is cut from the fixture stream of the per-layer tests: 0.1 s of noise (the gate sets its floor), the 2-s tone, noise,
@@ -90,6 +90,7 @@ def _chain(kind, S):
     from afx.cascade import CascadePolicy, CascadeScorer
     from afx.evidence import EvidencePolicy, EvidenceScorer
     from afx.ingest import PacketScorer
+    from afx.provenance import ProvenancePolicy, ProvenanceScorer
     from afx.quality import QualityPolicy, QualityScorer
     from afx.streaming import IncrementalScorer, KVCachedScorer
     from afx.vad import GatedScorer
@@ -97,7 +98,8 @@ def _chain(kind, S):
     (eng, sd), (teacher, tsd) = _student(), _teacher()
     screen = IncrementalScorer(eng, sd, S, window=16000, hop=H) if kind == "incremental" else KVCachedScorer(eng, sd, S, window=64000, hop=H)
     cascade = CascadeScorer(screen, teacher, CascadePolicy(threshold=1e30, budget=2, cooldown=1, min_samples=2 * H), state_dict=tsd)
-    verdict = VerdictScorer(QualityScorer(cascade, QualityPolicy()), VerdictPolicy(enter=1e30, confirm=2, min_scores=6))
+    verdict = VerdictScorer(ProvenanceScorer(QualityScorer(cascade, QualityPolicy()), ProvenancePolicy()),
+                            VerdictPolicy(enter=1e30, confirm=2, min_scores=6))
     return PacketScorer(GatedScorer(EvidenceScorer(verdict, EvidencePolicy(pre=2, post=2, clips=8))), 8000, "mulaw")
 
 
@@ -105,8 +107,10 @@ def _layers(front):
     gate = front.scorer
     evidence = gate.scorer
     verdict = evidence.scorer
-    quality = verdict.scorer
-    return dict(gate=gate, evidence=evidence.evidence, verdicts=verdict.verdicts, quality=quality.quality, cascade=quality.scorer,
+    provenance = verdict.scorer
+    quality = provenance.scorer
+    return dict(gate=gate, evidence=evidence.evidence, verdicts=verdict.verdicts, provenance=provenance.provenance, quality=quality.quality,
+                cascade=quality.scorer,
                 take_events=evidence.take_events, take_clips=evidence.take_clips)
 
 
@@ -149,14 +153,15 @@ def test_a_live_session_of_the_whole_stack_moves_bit_for_bit(kind):
     assert int(B["cascade"].stats()["verified"][[3, 1]].sum()) >= 1
 
     # every layer's state of the moved sessions, against the sessions that never moved
-    for name, fields in (("verdicts", ("m", "st")), ("quality", ("ring", "st", "totals")), ("cascade", ("verified", "wait", "verified_at")),
+    for name, fields in (("verdicts", ("m", "st")), ("quality", ("ring", "st", "totals")),
+                         ("provenance", ("ring", "st", "totals")), ("cascade", ("verified", "wait", "verified_at")),
                          ("gate", ("nf", "h")), ("evidence", ("hist", "sring"))):
         for f in fields:
             assert _same_bits(getattr(B[name], f)[[3, 1]], getattr(N[name], f)[[0, 2]]), (name, f)
     want, got = never.export_slots([0, 2]), b.export_slots([3, 1])
     assert torch.equal(want.seen, got.seen) and set(want.tensors) == set(got.tensors)
     for k in want.tensors:
-        if k.split("_")[0] in ("cascade", "quality", "verdict", "evidence", "gate", "ingest", "resample"):
+        if k.split("_")[0] in ("cascade", "quality", "prov", "verdict", "evidence", "gate", "ingest", "resample"):
             assert _same_bits(want.tensors[k], got.tensors[k]), k
 
     # events and clips after the move, up to the renaming of the slots
