@@ -907,6 +907,45 @@ int afx_k_prov_take(const int* gsyn, int S, int ring_frames, const int* table, i
                     void* stream);
 int afx_k_provenance(const int* hdr, const int* counts, const float* scores, int sstride, int A, int hop, long long limit,
                      int abstain, int* ring, int W, int* state, int* totals, int S, int* meas, float* out, void* stream);
+/* Provenance behind a look-ahead gate and through turns (afx/provenance.py, ProvenancePolicy(through="all")).  n[f] is the
+ * count of gate frame f of the stream the gate was pushed, 0 <= n[f] <= frame.  All integer arithmetic, exact.
+ * Behind afx_k_gate_la the gated stream is the emitted frames in order (keep'), so its frame counts are n[g] over the emitted
+ * g, in order.  State per slot: gline (device, S x pre int32), the count of delayed frame g at block g mod pre, parallel to
+ * `line`; a reset leaves it alone (nothing before the session's first frame is ever read).
+ * afx_k_prov_compact_la: directly after an afx_k_gate_la launch over A rows of n_frames frames, with that launch's own header
+ * and mask.  hdr (device, A x 4 int32) = slot, wpos (samples, on the frame grid), F (frames pushed before this row), 0;
+ * counts (device, A x n_frames int32): the counts of frames F .. F + n_frames - 1; mask (device, A x n_frames bytes): entry j =
+ * keep' of frame F - pre + j.  Per row, r = 0; for j = 0 .. n_frames - 1 with g = F - pre + j:
+ *     if g >= 0 and mask[j] & 1:
+ *         c = j < pre ? gline[slot][g mod pre] : counts[j - pre]
+ *         gsyn[slot][(wpos / frame + r) mod ring_frames] = c;   r += 1
+ * then for i = max(0, n_frames - pre) .. n_frames - 1:   gline[slot][(F + i) mod pre] = counts[i]
+ * (every read of gline precedes every write of the row: frame G enters the block frame G - pre leaves).  A row with a slot
+ * outside [0, S), wpos outside the ring or off the frame grid, F < 0, F + n_frames >= 2^31 or a count outside [0, frame] is
+ * skipped whole, nothing written.  One workgroup per row: an exclusive scan of mask bit 0 (the device function
+ * afx_k_prov_compact scans with), then a scatter.  afx_k_prov_take serves the pop unchanged.  A NULL pointer, A outside
+ * 1..65535, n_frames outside 1..512 or above ring_frames, pre outside 1..31, frame <= 0, S < 1 or a ring above 2^30:
+ * non-zero, afx_last_error names `prov_compact_la`, nothing launched.
+ * Through turns: afx_k_turn copies kept frame j of a row to bufs[slot][open][n]; bsyn (device, S x 2 x max_frames int32,
+ * parallel to bufs in frames) takes counts[j] at the same place (the turn mask is not delayed).  Entries beyond an open or
+ * completed turn's frames are undefined, as in bufs.
+ * afx_k_prov_turn: directly BEFORE afx_k_turn on the same stream, with the same mask (A x F) and header (A x 3 = slot, wpos,
+ * g0) and counts (device, A x F int32).  It reads state (open, n) and never writes it, replays afx_k_turn's recurrence for
+ * open and n only and stores the kept frames' counts where that recurrence stores the frames (those of a turn the row drops
+ * as short are not stored).  It skips the rows afx_k_turn skips (slot, g0, a state that is no turn state) plus any row with
+ * a count outside [0, frame]; it is not told the staging ring's length, so of wpos it checks wpos >= 0 only.  It refuses
+ * the scalars afx_k_turn refuses (the ring length excepted), by name (`prov_turn`).  One wave per row.
+ * afx_k_prov_turn_sum: beside afx_k_turn_collect, over the same table rows (device, R x 3 int32) = slot, buffer, frames m:
+ *     q = max_frames / m, rem = max_frames % m;   out[i] = q * sum(bsyn[slot][buffer][0..m)) + sum(bsyn[slot][buffer][0..rem))
+ * the count of the turn tiled to max_frames frames (saturating at 2^31 - 1; with entries <= frame it is at most the window).
+ * out[i] = -1 for a row afx_k_turn_collect would skip (slot outside [0, S), buffer not 0 / 1, m outside 1..max_frames) or with
+ * a negative entry among those it reads.  One wave per row, a wave-64 shuffle reduction of the two partial sums, no
+ * atomics.  A NULL pointer, S < 1, max_frames < 1 or R outside 1..262140: non-zero, `prov_turn_sum`, nothing launched. */
+int afx_k_prov_compact_la(const int* counts, const unsigned char* mask, const int* hdr, int A, int n_frames, int frame, int pre,
+                          int* gline, int* gsyn, int S, int ring_frames, void* stream);
+int afx_k_prov_turn(const int* counts, const unsigned char* mask, const int* hdr, int A, int F, int frame, int min_frames,
+                    int max_frames, const int* state, int* bsyn, int S, void* stream);
+int afx_k_prov_turn_sum(const int* bsyn, int S, int max_frames, const int* rows, int R, int* out, void* stream);
 /* Row LayerNorm (+ activation) of fp32 rows: 0 < C <= 1024, C % 4 == 0, any rows >= 1; out_f and / or out_h.  ldx, ldo_f,
  * ldo_h count elements (>= C).  A lane reads and writes 4 columns at a time, so rows must be aligned to that access: x,
  * gamma, beta, out_f 16-byte aligned with ldx % 4 == 0 and ldo_f % 4 == 0; out_h 8-byte aligned (16 for the fp32 operand

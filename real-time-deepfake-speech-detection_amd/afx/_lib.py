@@ -147,6 +147,9 @@ SIGNATURES = {
     "afx_k_prov_frames": (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _P]),
     "afx_k_prov_compact": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _I, _P]),
     "afx_k_prov_take": (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _P]),
+    "afx_k_prov_compact_la": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _P]),
+    "afx_k_prov_turn": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
+    "afx_k_prov_turn_sum": (_I, [_P, _I, _I, _P, _I, _P, _P]),
     "afx_k_provenance": (_I, [_P, _P, _P, _I, _I, _I, C.c_longlong, _I, _P, _I, _P, _P, _I, _P, _P, _P]),
     "afx_k_rownorm": (_I, [_I, _P, _L, _I, _I, _P, _P, _F, _I, _P, _L, _P, _L, _P]),
     "afx_k_mhsa": (_I, [_I, _P, _P, _I, _I, _I, _P]),

@@ -57,8 +57,29 @@ that turns the popped hops of ``psyn`` into frame counts.  A ``GatedScorer`` wit
 on the way is attached: it asks its gate launch for the mask, keeps a count ring ``gsyn`` (S, ring_len / frame) int32 parallel
 to its sample ring (``afx_k_prov_compact`` after the gate launch, ``afx_k_prov_take`` at a pop) and notes the hop's sum to
 whatever takes notes below it; its one read-back stays the only one.  A ``LookaheadGate`` (its mask is delayed) or a
-``TurnScorer`` (its mask feeds turn buffers) on the way is refused.  With no provenance layer below, nothing of the front or
-the gate changes in any respect.
+``TurnScorer`` (its mask feeds turn buffers) on the way is refused under the policy's default ``through="plain"``.  With no
+provenance layer below, nothing of the front or the gate changes in any respect.
+
+Through pre-roll and turns (``ProvenancePolicy(through="all")``; ``through`` is an attribute of the policy, no part of
+``params()`` and no part of a session).  Both layers move whole frames in a stated order, so the counts go the same way.
+
+Behind a ``LookaheadGate`` the gated stream is the emitted frames in order (``keep'``), and its frame counts are n[g] over
+the emitted g, in order: in numpy ``n[:decided][mask]`` with ``mask`` from ``LookaheadGate.gate_reference`` over the whole
+stream, then sums of ``hop / frame``.  The attached gate owns ``gline`` ((S, pre) int32: the count of delayed frame g at block
+g mod pre, parallel to ``line``; ``reset`` leaves it alone, nothing before a session's first frame is ever read) and its push
+calls ``afx_k_prov_compact_la`` in the place of ``afx_k_prov_compact``, over the gate launch's own header and mask: the
+count of an emitted frame comes out of ``gline`` where an earlier push brought the frame and out of the push's own counts
+otherwise, and the push's last ``pre`` counts enter ``gline`` after every read.  ``afx_k_prov_take`` serves the pop unchanged.
+
+Through a ``TurnScorer`` the turn recurrence copies kept frame j of a row to ``bufs[slot][open][n]``; ``bsyn`` ((S, 2,
+max_frames) int32, parallel to ``bufs``) takes ``counts[j]`` at the same place (``afx_k_prov_turn``, launched directly before
+``afx_k_turn`` with the same mask and header; it reads the turn state and never writes it).  The clip of a scored turn of m
+frames is the turn tiled to ``max_frames`` frames, so its count is ``clip_count(n[first:end], max_frames)`` =
+``np.resize(n[first:end], max_frames).sum()`` = ``q * sum(all m) + sum(the first rem)``, ``q, rem = divmod(max_frames, m)``
+(``afx_k_prov_turn_sum``, beside ``afx_k_turn_collect`` over the same table): made-up audio is repeated with the turn.  That
+count is noted to what takes notes below directly before the inner ``push``; the layer there stands around a scorer with
+``hop == window``, so ``W = 1`` and ``limit = floor(share * window)``.  ``flush`` goes through the same tail; the close step
+moves no frame and takes no note.  The limit of 512 frames per push holds for both chains.
 
 Sessions: the layer's part of a ``StreamState`` is ``prov_ring`` ((n, W) int32), ``prov_state`` ((n, 2) int64) and
 ``prov_totals`` ((n, 3) int64), meta ``provenance`` (format) and ``provenance_window`` (W and hop); a front whose lane is on
@@ -66,10 +87,16 @@ adds ``jitter_syn`` (laid out as ``jitter_pending``, uint8), an attached gate ``
 the fill).  Rows that cannot be a session's are refused: a count above ``frame`` or ``hop``, a total that is not the ring's
 sum, a flag counted more often than hops.  A state without the front's or the gate's part imports with zeros; one with them
 is refused by a chain without the layer.  The ring holds counts, so ``max_share`` and ``abstain`` may differ where a session
-goes (``valid`` is set under the importing policy's limit, so a state whose new streams carry (0, 0) imports as well).
+goes (``valid`` is set under the importing policy's limit, so a state whose new streams carry (0, 0) imports as well).  An
+attached look-ahead gate adds ``gate_syn_line`` ((n, pre) int64: the delayed frames' counts, oldest first, zeros in front
+where fewer than ``pre`` are delayed -- ``gate_line``'s layout; an entry outside 0..frame or a non-zero one in front of the
+delayed frames is refused), an attached ``TurnScorer`` ``turn_syn`` ((n, max_frames) int64: the open turn's counts, then -1;
+anything else after ``turn_frames`` or an entry outside 0..frame is refused; it lands in buffer 0 with ``turn_open``).  Both
+follow ``gate_syn``'s rule: refused by an object that is not attached, and a state without them imports with zeros.
 
-Out of scope: ``LookaheadGate``; ``TurnScorer``, offline timelines and turns; per-sample marks into evidence clips; tuned
-thresholds (0.05 is an engineering default: there is no labelled corpus behind it); the filter-delay offset of the mark.
+Out of scope: offline timelines and turns (no jitter buffer); counts or per-sample marks in evidence clips; a ``TurnScorer``
+with pre-roll (not built); tuned thresholds (0.05 is an engineering default: there is no labelled corpus behind it); the
+filter-delay offset of the mark.
 """
 import numpy as np
 import torch
@@ -102,16 +129,19 @@ class ProvenancePolicy:
     last ``W`` hops were made up by the jitter buffer.  abstain=False: count only, every score passes.  0.05 is an engineering
     default, not a tuned one."""
 
-    def __init__(self, max_share=0.05, abstain=True):
+    def __init__(self, max_share=0.05, abstain=True, through="plain"):
         self.share32 = fp32("max_share", max_share, False)
         if self.share32 > 1:
             raise ValueError(f"max_share {max_share!r}: 0 to 1")
         if not isinstance(abstain, (bool, np.bool_)):
             raise ValueError(f"abstain: True or False, got {abstain!r}")
-        self.max_share, self.abstain = float(self.share32), bool(abstain)
+        if not isinstance(through, str) or through not in ("plain", "all"):
+            raise ValueError(f'through: "plain" or "all", got {through!r}')
+        self.max_share, self.abstain, self.through = float(self.share32), bool(abstain), through
 
     def params(self):
-        """What identifies this policy (a float and a bool)."""
+        """What identifies this policy (a float and a bool; ``through`` says which chains a front may build over the layer
+        and is no part of a session)."""
         return dict(max_share=self.max_share, abstain=self.abstain)
 
     def limit(self, W, hop):
@@ -258,24 +288,43 @@ def note_target(scorer):
     return scorer
 
 
+def clip_count(frame_counts, max_frames):
+    """The count of a scored turn's clip: ``frame_counts`` (m,) ints, the counts of the turn's m frames (1 <= m <=
+    max_frames) -> the count of the turn tiled to ``max_frames`` frames, ``q * sum(all m) + sum(the first rem)`` with
+    ``q, rem = divmod(max_frames, m)``: ``np.resize(frame_counts, max_frames).sum()``, as ``afx_k_prov_turn_sum`` computes it."""
+    c = np.asarray(frame_counts).reshape(-1)
+    if c.dtype == bool or (c.size and not np.issubdtype(c.dtype, np.integer)):
+        raise ValueError("frame_counts: integers")
+    if isinstance(max_frames, bool) or not isinstance(max_frames, (int, np.integer)) or not 1 <= c.size <= max_frames:
+        raise ValueError(f"a turn of {c.size} frames: 1 to max_frames = {max_frames!r}")
+    c = c.astype(np.int64)
+    q, rem = divmod(int(max_frames), c.size)
+    return int(q * c.sum() + c[:rem].sum())
+
+
 def discover(front):
     """What a jitter front does at construction: walks the ``.scorer`` links below it; with no provenance layer there ->
     None and nothing changes.  With one: a ``GatedScorer`` with a plain ``SpeechGate`` or a ``ToneGate`` on the way is
-    attached, a ``LookaheadGate`` or a ``TurnScorer`` (any other object of kind "gate") on the way is a ValueError -> (the
-    object the front notes its counts to, the samples of a frame of those counts, whether that object is an attached gate)."""
+    attached; a ``GatedScorer`` with a ``LookaheadGate`` or a ``TurnScorer`` on the way is attached where the layer's policy
+    says ``through="all"`` and is a ValueError under ``through="plain"``, as is any other object of kind "gate" -> (the object
+    the front notes its counts to, the samples of a frame of those counts, whether that object is an attached gate)."""
+    from .turns import TurnScorer
     from .vad import GatedScorer, LookaheadGate
     chain, s = [], getattr(front, "scorer", None)
     while s is not None:
         chain.append(s)
         s = getattr(s, "scorer", None)
-    if not any(getattr(s, "layer", None) == "provenance" for s in chain):
+    layer = next((s for s in chain if getattr(s, "layer", None) == "provenance"), None)
+    if layer is None:
         return None
+    every = getattr(getattr(layer, "policy", None), "through", "plain") == "all"
     gated = None
     for s in chain:
         if getattr(s, "layer", None) == "provenance":
             break
         if getattr(s, "layer", None) == "gate":
-            if not isinstance(s, GatedScorer) or isinstance(s.gate, LookaheadGate):
+            plain = isinstance(s, GatedScorer) and not isinstance(s.gate, LookaheadGate)
+            if not plain and not (every and isinstance(s, (GatedScorer, TurnScorer))):
                 what = "LookaheadGate (its mask is delayed)" if isinstance(s, GatedScorer) else f"{type(s).__name__} (its mask feeds turn buffers)"
                 raise ValueError(f"a jitter front over a provenance layer: a {what} on the way is out of scope")
             if s.hop // s.gate.frame > MAX_FRAMES:

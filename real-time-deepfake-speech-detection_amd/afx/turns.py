@@ -233,7 +233,15 @@ class TurnScorer(Layer):
     zeros after), ``turn_frames`` and ``turn_first`` ((n,) int64; ``turn_first`` is -1 where ``turn_frames`` is 0) and
     ``turn_totals`` ((n, 4) int64); meta ``turn`` (format), ``turn_params`` = [hop, min_frames, max_frames], ``gate`` and
     ``gate_params``.  The state's ``seen`` is the layer's own sample count.  An imported open turn lands in buffer 0: which
-    buffer holds it is not part of a session.  A ``GatedScorer`` state and a turn state refuse each other."""
+    buffer holds it is not part of a session.  A ``GatedScorer`` state and a turn state refuse each other.
+
+    Provenance (``afx.provenance``): a jitter front over a provenance layer whose policy says ``through="all"`` attaches this
+    layer.  It then takes the frame counts of the next push (``note_synthetic``, (A, hop / frame) int32), keeps ``bsyn`` ((S,
+    2, max_frames) int32, parallel to ``bufs``: ``afx_k_prov_turn`` directly before ``afx_k_turn``), and the tail of ``push``
+    and ``flush`` sums each scored turn's tiled count (``afx_k_prov_turn_sum`` beside the collect) and notes it to what takes
+    notes below directly before the inner ``push``; ``done`` stays the one read-back.  A session's part gains ``turn_syn``
+    ((n, max_frames) int64: the open turn's counts, then -1; it lands in buffer 0 with ``turn_open``).  A layer that is not
+    attached does none of this."""
 
     layer = "gate"
     _keys = ("gate_nf", "gate_hang", "gate_inner_seen", "turn_open", "turn_frames", "turn_first", "turn_totals")
@@ -279,6 +287,28 @@ class TurnScorer(Layer):
         self._extra = gate._new_extra(S, hop, dev)  # the gate's own per-slot state, also as attributes (coef, tone_state)
         for name, t in self._extra.items():
             setattr(self, name, t)
+        self._syn = False  # (afx.provenance: a jitter front over a provenance layer with through="all" attaches this layer)
+
+    # ---- provenance (afx.provenance) ---------------------------------------------------------------------------------------
+    def _attach_provenance(self):
+        """A jitter front found a provenance layer below this layer: from now on ``bsyn`` ((S, 2, max_frames) int32, parallel
+        to ``bufs`` in frames) holds the synthetic samples of every frame of the open and the completed turns."""
+        if not self._syn:
+            from .provenance import note_target
+            self._syn, self._syn_note, self._syn_below = True, None, note_target(self.scorer)
+            self.bsyn = torch.zeros(self.S, 2, self.max_frames, dtype=torch.int32, device=self.device)
+
+    def note_synthetic(self, counts, slots):
+        """counts: (A, hop / frame) int32 on the scorer's device, the synthetic samples of every frame of the hop the next
+        ``push`` brings for each of ``slots`` (in its row order).  The next ``push`` must name exactly these slots; it
+        consumes the note (``flush`` neither takes nor consumes one).  Only an attached layer takes notes."""
+        if not self._syn:
+            raise ValueError("this layer is not attached to a provenance layer (a jitter front over one attaches it)")
+        idx = self._named(slots)
+        shape = (len(idx), self.F)
+        if not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or counts.shape != shape or counts.device != self.staging.device:
+            raise ValueError(f"counts: an int32 tensor of shape {shape} on {self.staging.device}")
+        self._syn_note = (idx, counts.contiguous())
 
     # ---- the surface ---------------------------------------------------------------------------------------------------------
     @property
@@ -322,6 +352,11 @@ class TurnScorer(Layer):
         need_gpu(dev, "turns are cut and scored")
         if not isinstance(chunk, torch.Tensor) or not chunk.is_cuda or chunk.dtype != torch.float32 or chunk.shape != (A, hop):
             raise ValueError(f"expected a CUDA fp32 tensor of shape {(A, hop)} (one hop per named slot)")
+        note = None
+        if self._syn:
+            note, self._syn_note = self._syn_note, None
+            if note is not None and note[0] != idx:
+                raise ValueError(f"the note names the slots {note[0]}, this push {idx}: a note is for the next push of exactly its slots")
         if not A:
             self.last_turn = torch.empty(0, 2, dtype=torch.int64, device=dev)
             if self._tone:
@@ -342,6 +377,10 @@ class TurnScorer(Layer):
             th = torch.empty(A, 3, dtype=torch.int32, pin_memory=True)
             th.numpy()[:] = np.stack([slot, zeros, g0], axis=1)
             th = th.to(dev, non_blocking=True)
+            if self._syn:  # the kept frames' counts go where afx_k_turn is about to put the frames (it reads the state: first)
+                counts = torch.zeros(A, self.F, dtype=torch.int32, device=dev) if note is None else note[1]
+                check(call_on(self.bsyn, lib().afx_k_prov_turn, ptr(counts), ptr(mask), ptr(th), A, self.F, frame, self.min_frames,
+                              self.max_frames, ptr(self.turn_state), ptr(self.bsyn), self.S))
             check(call_on(self.staging, lib().afx_k_turn, ptr(self.staging), self.S, hop, ptr(mask), ptr(th), A, self.F, frame,
                           self.min_frames, self.max_frames, ptr(self.bufs), ptr(self.turn_state), ptr(self._totals), ptr(done)))
             d = self._read_done(done, "afx_k_turn")
@@ -401,6 +440,10 @@ class TurnScorer(Layer):
             clips = torch.empty(R, self.window, dtype=torch.float32, device=dev)
             check(call_on(self.bufs, lib().afx_k_turn_collect, ptr(self.bufs), self.S, self.max_frames, self.gate.frame, ptr(t), R,
                           ptr(clips)))
+            if self._syn and self._syn_below is not None:  # the tiled turns' counts, over the collect's own table
+                c = torch.empty(R, dtype=torch.int32, device=dev)
+                check(call_on(self.bsyn, lib().afx_k_prov_turn_sum, ptr(self.bsyn), self.S, self.max_frames, ptr(t), R, ptr(c)))
+                self._syn_below.note_synthetic(c, slot[rows].tolist())
             sc = self.scorer.push(clips, slot[rows].tolist())
             if sc is None:
                 raise RuntimeError("the inner scorer emitted no score for a turn")
@@ -446,7 +489,20 @@ class TurnScorer(Layer):
                         turn_totals=self._totals[rows].to("cpu", torch.int64))
             if self._tone:
                 part["gate_tone"] = self.tone_state[rows].to("cpu", torch.int64)
+            if self._syn:  # the open turn's counts, -1 after its frames
+                syn = self.bsyn[rows, opn.to(self.device)].to("cpu", torch.int64)
+                syn[torch.arange(self.max_frames)[None, :] >= n[:, None]] = -1
+                part["turn_syn"] = syn
             return part
+
+    def _state_keys(self, state):
+        """``_keys``, and ``turn_syn`` where the state carries it: a state with the synthetic counts of its open turn is
+        refused by a layer that is not attached to a provenance layer, a state without them imports into an attached one
+        with zeros."""
+        has = isinstance(state, StreamState) and "turn_syn" in state.tensors
+        if has and not self._syn:
+            raise ValueError("import_slots: the state carries provenance counts (turn_syn) and this chain has no provenance layer")
+        return self._keys + (("turn_syn",) if has else ())
 
     def _check(self, state, n):
         t, frame, window = state.tensors, self.gate.frame, self.window
@@ -475,10 +531,19 @@ class TurnScorer(Layer):
         if ((tot < 0) | (tot > N_MAX)).any():
             raise ValueError("import_slots: a session's totals are negative (or 2^31 or more)")
         check_hang_and_floor(self.gate, hang, nf)
-        return (nf, hang, turn, frames, first, tot, seen) + (check_tone(self.gate, t, n, seen) if self._tone else ())
+        syn = None  # (the open turn's synthetic counts, where the state carries them: _state_keys)
+        if "turn_syn" in t and self._syn:
+            syn = t["turn_syn"]
+            if syn.dtype != torch.int64 or tuple(syn.shape) != (n, self.max_frames):
+                raise ValueError(f"import_slots: turn_syn is {(n, self.max_frames)} int64")
+            so = syn.cpu().numpy()
+            live = np.arange(self.max_frames)[None, :] < frames[:, None]
+            if (so[~live] != -1).any() or (((so < 0) | (so > frame)) & live).any():
+                raise ValueError(f"import_slots: turn_syn is 0..{frame} for the frames of a session's open turn and -1 after them")
+        return (nf, hang, turn, frames, first, tot, seen, syn) + (check_tone(self.gate, t, n, seen) if self._tone else ())
 
     def _import(self, idx, rows):
-        nf, hang, turn, frames, first, tot, seen = rows[:7]
+        nf, hang, turn, frames, first, tot, seen, syn = rows[:8]
         if idx:
             dev = self.device
             with _on(dev):
@@ -490,7 +555,11 @@ class TurnScorer(Layer):
                 self.turn_state[dev_rows] = torch.from_numpy(state).to(dev, torch.int32)
                 self._totals[dev_rows] = torch.from_numpy(tot).to(dev, torch.int32)
                 if self._tone:
-                    self.tone_state[dev_rows] = rows[7].to(dev, torch.int32)
+                    self.tone_state[dev_rows] = rows[8].to(dev, torch.int32)
+                if self._syn:
+                    self.bsyn[dev_rows] = 0
+                    if syn is not None:
+                        self.bsyn[dev_rows, 0] = syn.clamp(min=0).to(dev, torch.int32)
             self._seen[idx] = seen
 
 

@@ -582,7 +582,11 @@ class GatedScorer(Layer):
     attached gate takes the frame counts of the next push (``note_synthetic``), asks its gate launch for the mask (otherwise
     NULL, as ever), compacts the kept frames' counts into ``gsyn`` ((S, ring_len / frame) int32, ``afx_k_prov_compact``), sums
     a popped hop's entries (``afx_k_prov_take``) and notes them to what takes notes below; a session's part gains ``gate_syn``
-    ((n, hop / frame) int64, the pending frames' counts, -1 after the fill).  A gate that is not attached does none of this."""
+    ((n, hop / frame) int64, the pending frames' counts, -1 after the fill).  Over a layer whose policy says ``through="all"``
+    a look-ahead gate is attached too: it also owns ``gline`` ((S, pre) int32, the delayed frames' counts at block g mod pre,
+    parallel to ``line``; ``reset`` leaves it alone), its push calls ``afx_k_prov_compact_la`` in the place of
+    ``afx_k_prov_compact``, and a session's part also gains ``gate_syn_line`` ((n, pre) int64, laid out as ``gate_line``: the
+    delayed frames' counts, oldest first, zeros in front).  A gate that is not attached does none of this."""
 
     layer = "gate"
     _keys = ("gate_pending", "gate_fill", "gate_hang", "gate_inner_seen", "gate_nf")
@@ -624,6 +628,8 @@ class GatedScorer(Layer):
             from .provenance import note_target
             self._syn, self._syn_note, self._syn_below = True, None, note_target(self.scorer)
             self.gsyn = torch.zeros(self.S, self.ring_len // self.gate.frame, dtype=torch.int32, device=self.device)
+            if self._la:  # the delayed frames' counts: frame g at block g mod pre, parallel to ``line``
+                self.gline = torch.zeros(self.S, self.gate.pre, dtype=torch.int32, device=self.device)
 
     def note_synthetic(self, counts, slots):
         """counts: (A, hop / frame) int32 on the scorer's device, the synthetic samples of every frame of the hop the next
@@ -693,8 +699,12 @@ class GatedScorer(Layer):
             self.last_tone_frames = self.gate._launch(chunk.to(dev).contiguous(), hdr, self.nf, self.h, self.ring, kept, self._extra, mask)
             if self._syn:  # the kept frames' counts, in order, at the slot's write position in frames (hdr: the gate launch's own)
                 counts = torch.zeros(A, hop // frame, dtype=torch.int32, device=dev) if note is None else note[1]
-                check(call_on(self.gsyn, lib().afx_k_prov_compact, ptr(counts), ptr(mask), ptr(hdr), A, hop // frame, frame,
-                              ptr(self.gsyn), self.S, self.ring_len // frame))
+                if la:  # (the emitted frames' counts: out of gline, or the push's own, as the gate emits the samples)
+                    check(call_on(self.gsyn, lib().afx_k_prov_compact_la, ptr(counts), ptr(mask), ptr(hdr), A, hop // frame, frame,
+                                  self.gate.pre, ptr(self.gline), ptr(self.gsyn), self.S, self.ring_len // frame))
+                else:
+                    check(call_on(self.gsyn, lib().afx_k_prov_compact, ptr(counts), ptr(mask), ptr(hdr), A, hop // frame, frame,
+                                  ptr(self.gsyn), self.S, self.ring_len // frame))
             if la:
                 span = torch.full((A, 2), -1, dtype=torch.int64, device=dev)
             host = torch.empty(A, dtype=torch.int32, pin_memory=True)
@@ -779,16 +789,25 @@ class GatedScorer(Layer):
                 syn = self.gsyn[rows[:, None], torch.from_numpy(ent).to(self.device)].to("cpu", torch.int64)
                 syn[torch.from_numpy(j[None, :] >= (self._fill[idx] // self.gate.frame)[:, None])] = -1
                 part["gate_syn"] = syn
+                if self._la:  # the delayed frames' counts, oldest first, zeros in front: gate_line's layout
+                    pre = self.gate.pre
+                    _, d, block = self._delayed(self._seen[idx])
+                    ln = self.gline[rows[:, None], torch.from_numpy(block).to(self.device)].to("cpu", torch.int64)
+                    ln[torch.from_numpy(np.arange(pre)[None, :] < (pre - d)[:, None])] = 0
+                    part["gate_syn_line"] = ln
             return part
 
     def _state_keys(self, state):
-        """``_keys``, and ``gate_syn`` where the state carries it: a state with the synthetic counts of its pending frames is
-        refused by a gate that is not attached to a provenance layer, a state without them imports into an attached gate
-        with zeros."""
-        has = isinstance(state, StreamState) and "gate_syn" in state.tensors
+        """``_keys``, and ``gate_syn`` (a look-ahead gate: and ``gate_syn_line``) where the state carries it: a state with
+        the synthetic counts of its pending or delayed frames is refused by a gate that is not attached to a provenance
+        layer, a state without them imports into an attached gate with zeros."""
+        own = isinstance(state, StreamState)
+        has, line = own and "gate_syn" in state.tensors, own and "gate_syn_line" in state.tensors
         if has and not self._syn:
             raise ValueError("import_slots: the state carries provenance counts (gate_syn) and this chain has no provenance layer")
-        return self._keys + (("gate_syn",) if has else ())
+        if line and not self._syn:
+            raise ValueError("import_slots: the state carries provenance counts (gate_syn_line) and this chain has no provenance layer")
+        return self._keys + (("gate_syn",) if has else ()) + (("gate_syn_line",) if line and self._la else ())
 
     def _delayed(self, seen):
         """seen: (n,) samples per session -> (F frames seen, d = min(F, pre) frames delayed, the line block of the exported
@@ -837,8 +856,22 @@ class GatedScorer(Layer):
             pending = np.arange(per)[None, :] < (fill // self.gate.frame)[:, None]
             if (so[~pending] != -1).any() or (((so < 0) | (so > self.gate.frame)) & pending).any():
                 raise ValueError(f"import_slots: gate_syn is 0..{self.gate.frame} for a session's pending frames and -1 after them")
-        return (pend, nf, hang, fill, seen, syn) + (self._check_line(t, n, fill, seen) if self._la else ()) + (
-            self._check_tone(t, n, seen) if self._tone else ())
+        return (pend, nf, hang, fill, seen, syn) + (self._check_line(t, n, fill, seen) + (self._check_syn_line(t, n, seen),)
+                                                    if self._la else ()) + (self._check_tone(t, n, seen) if self._tone else ())
+
+    def _check_syn_line(self, t, n, seen):
+        """``gate_syn_line`` where the state carries it and this gate is attached -> the tensor, else None."""
+        if "gate_syn_line" not in t or not self._syn:
+            return None
+        pre, ln = self.gate.pre, t["gate_syn_line"]
+        if ln.dtype != torch.int64 or tuple(ln.shape) != (n, pre):
+            raise ValueError(f"import_slots: gate_syn_line is {(n, pre)} int64")
+        lo = ln.cpu().numpy()
+        _, d, _ = self._delayed(seen)
+        delayed = np.arange(pre)[None, :] >= (pre - d)[:, None]
+        if (lo[~delayed] != 0).any() or (((lo < 0) | (lo > self.gate.frame)) & delayed).any():
+            raise ValueError(f"import_slots: gate_syn_line is 0..{self.gate.frame} for a session's delayed frames and 0 in front of them")
+        return ln
 
     def _check_tone(self, t, n, seen):
         return check_tone(self.gate, t, n, seen)
@@ -876,10 +909,14 @@ class GatedScorer(Layer):
                 self.nf[dev_rows] = nf.to(self.device)
                 self.h[dev_rows] = torch.from_numpy(hang).to(self.device, torch.int32)
                 if self._la:
-                    line, dev_flags, block, sources = rows[6:]
+                    line, dev_flags, block, sources, syn_line = rows[6:]
                     pre, frame, dev = self.gate.pre, self.gate.frame, self.device
                     self.line.view(self.S, pre, frame)[dev_rows[:, None], torch.from_numpy(block).to(dev)] = \
                         line.reshape(len(idx), pre, frame).to(dev)
+                    if self._syn:
+                        self.gline[dev_rows] = 0
+                        if syn_line is not None:
+                            self.gline[dev_rows[:, None], torch.from_numpy(block).to(dev)] = syn_line.to(dev, torch.int32)
                     self.flags[dev_rows] = torch.from_numpy(dev_flags).to(dev)
                     self.src[dev_rows] = -1
                     self.src[dev_rows, :sources.shape[1]] = sources.to(dev, torch.int32)

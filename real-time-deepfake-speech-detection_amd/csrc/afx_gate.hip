@@ -918,6 +918,22 @@ extern "C" int afx_k_turn_clips(const float* x, const long long* xoffs, int A, i
 // ---------------------------------------------------------------------------------
 constexpr int PROV_MAX_RING_FRAMES = 1 << 30;
 
+// The exclusive scan of a workgroup of 256 threads: `mine` kept frames per thread -> the kept frames before this thread's.
+// Inclusive over the wave by shuffle-up, the four waves' totals through s_wave (4 ints of LDS); every thread of the
+// workgroup calls it (it passes one barrier).
+__device__ __forceinline__ int prov_rank(int mine, int lane, int wave, int* s_wave) {
+  int incl = mine;
+  for (int w = 1; w < 64; w <<= 1) {
+    const int o = __shfl_up(incl, w);
+    if (lane >= w) incl += o;
+  }
+  if (lane == 63) s_wave[wave] = incl;
+  __syncthreads();
+  int rank = incl - mine;
+  for (int w = 0; w < wave; ++w) rank += s_wave[w];
+  return rank;
+}
+
 __global__ __launch_bounds__(256) void prov_compact_kernel(const int* __restrict__ counts, const unsigned char* __restrict__ mask,
                                                            const int* __restrict__ hdr, int F, int frame, int* __restrict__ gsyn,
                                                            int S, int ring_frames) {
@@ -936,16 +952,7 @@ __global__ __launch_bounds__(256) void prov_compact_kernel(const int* __restrict
     bad |= c[j] < 0 || c[j] > frame;
   }
   if (__syncthreads_or(bad)) return;  // a count that is no frame's: the row is skipped whole
-  const int mine = keep[0] + keep[1];
-  int incl = mine;
-  for (int w = 1; w < 64; w <<= 1) {
-    const int o = __shfl_up(incl, w);
-    if (lane >= w) incl += o;
-  }
-  if (lane == 63) s_wave[wave] = incl;
-  __syncthreads();
-  int rank = incl - mine;
-  for (int w = 0; w < wave; ++w) rank += s_wave[w];
+  int rank = prov_rank(keep[0] + keep[1], lane, wave, s_wave);
   int* dst = gsyn + (long long)slot * ring_frames;
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
@@ -1005,6 +1012,177 @@ extern "C" int afx_k_prov_take(const int* gsyn, int S, int ring_frames, const in
   if (per <= 0 || per > ring_frames) return fail("prov_take: a hop's frames must fit the ring");
   if (frame <= 0) return fail("prov_take: a frame of at least 1 sample");
   hipLaunchKernelGGL(prov_take_kernel, dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream, gsyn, S, ring_frames, table, R, per, frame, out);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail("%s", hipGetErrorString(e));
+}
+
+// ---------------------------------------------------------------------------------
+// Provenance counts behind a look-ahead gate and through turns (afx/provenance.py; the functions are stated in
+// include/afx.h afx_k_prov_compact_la / afx_k_prov_turn / afx_k_prov_turn_sum).  Integer copies and sums, beside the
+// kernels they mirror:
+//   compact_la: gate_la_kernel's emission for counts.  Mask entry j of a row is keep' of frame g = F - pre + j; the count of
+//               an emitted frame comes out of gline (S, pre: delayed frame g at block g mod pre, parallel to `line`) for
+//               j < pre and out of this row's counts[j - pre] otherwise.  One workgroup per row, thread t owns the entries
+//               2 t and 2 t + 1; every gline read stands before prov_rank's barrier and every gline write (the row's last
+//               min(pre, n_frames) counts: frame G enters the block frame G - pre leaves) behind it;
+//   turn:       turn_kernel's plan for counts.  One wave per row: lane 0 replays the recurrence for open and n from the
+//               slot's state (which it only reads: turn_kernel, launched next on the stream, moves it) and writes each kept
+//               frame's destination among the slot's 2 x max_frames entries to LDS, the frames of a turn the row drops as
+//               short taken out again (the next turn starts at the same place); then the lanes copy counts to bsyn;
+//   turn_sum:   the count of a turn tiled to max_frames frames, q * sum(first m) + sum(first max_frames mod m); one wave per
+//               row, the two partial sums through one shuffle-down tree.
+// ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void prov_compact_la_kernel(const int* __restrict__ counts, const unsigned char* __restrict__ mask,
+                                                              const int* __restrict__ hdr, int n, int frame, int pre, int* gline,
+                                                              int* __restrict__ gsyn, int S, int ring_frames) {
+  __shared__ int s_wave[4];
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int slot = hdr[4 * row], wpos = hdr[4 * row + 1], F = hdr[4 * row + 2], wposf = wpos / frame;  // (afx_k_gate_la's header)
+  if (!(slot >= 0 && slot < S && wpos >= 0 && wpos % frame == 0 && wposf < ring_frames && F >= 0 && F <= 0x7fffffff - n))
+    return;  // (the whole workgroup: no barrier is passed by some)
+  const int* cr = counts + (long long)row * n;
+  int* gl = gline + (long long)slot * pre;
+  int c[2], keep[2];
+  bool bad = false;
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int j = 2 * tid + k;
+    const bool in = j < n;
+    c[k] = in ? cr[j] : 0;
+    bad |= c[k] < 0 || c[k] > frame;
+  }
+  if (__syncthreads_or(bad)) return;  // a count that is no frame's: the row is skipped whole
+  int v[2];
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int j = 2 * tid + k;
+    const long long g = (long long)F - pre + j;  // the frame that leaves at step j
+    keep[k] = j < n && g >= 0 && (mask[(long long)row * n + j] & 1);
+    v[k] = !keep[k] ? 0 : j < pre ? gl[g % pre] : cr[j - pre];
+  }
+  int rank = prov_rank(keep[0] + keep[1], lane, wave, s_wave);  // (its barrier: every read of gline is done)
+  int* dst = gsyn + (long long)slot * ring_frames;
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int j = 2 * tid + k;
+    if (keep[k]) {
+      const int at = wposf + rank;  // rank < n <= ring_frames: one wrap
+      dst[at < ring_frames ? at : at - ring_frames] = v[k];
+      ++rank;
+    }
+    if (j < n && j >= n - pre) gl[(F + j) % pre] = c[k];  // (F + j < 2^31; the last min(pre, n) frames: distinct blocks)
+  }
+}
+
+extern "C" int afx_k_prov_compact_la(const int* counts, const unsigned char* mask, const int* hdr, int A, int n_frames, int frame,
+                                     int pre, int* gline, int* gsyn, int S, int ring_frames, void* stream) {
+  if (!counts || !mask || !hdr || !gline || !gsyn) return fail("prov_compact_la: null argument");
+  if (A <= 0 || A > 65535) return fail("prov_compact_la: 1 to 65535 rows");
+  if (S <= 0) return fail("prov_compact_la: no slots");
+  if (n_frames <= 0 || n_frames > GATE_MAX_FRAMES) return fail("prov_compact_la: 1 to 512 frames a row");
+  if (frame <= 0) return fail("prov_compact_la: a frame of at least 1 sample");
+  if (pre < 1 || pre > 31) return fail("prov_compact_la: 1 to 31 frames of pre-roll");
+  if (ring_frames < n_frames || ring_frames > PROV_MAX_RING_FRAMES)
+    return fail("prov_compact_la: a ring of at least a row's frames, at most 2^30");
+  hipLaunchKernelGGL(prov_compact_la_kernel, dim3(A), dim3(256), 0, (hipStream_t)stream, counts, mask, hdr, n_frames, frame, pre,
+                     gline, gsyn, S, ring_frames);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail("%s", hipGetErrorString(e));
+}
+
+__global__ __launch_bounds__(64) void prov_turn_kernel(const int* __restrict__ counts, const unsigned char* __restrict__ mask,
+                                                       const int* __restrict__ hdr, int F, int frame, int min_frames, int max_frames,
+                                                       const int* __restrict__ state, int* __restrict__ bsyn, int S) {
+  __shared__ int s_plan[TURN_MAX_FRAMES];  // open * max_frames + n of a kept frame, -1: nothing to store
+  const int row = blockIdx.x, lane = threadIdx.x;
+  const int slot = hdr[3 * row], wpos = hdr[3 * row + 1], g0 = hdr[3 * row + 2];
+  bool ok = slot >= 0 && slot < S && wpos >= 0 && g0 >= 0 && g0 <= 0x7fffffff - F;
+  int open = 0, n = 0;
+  if (ok) {
+    open = state[3 * slot];
+    n = state[3 * slot + 1];
+    ok = (open == 0 || open == 1) && n >= 0 && n < max_frames;
+  }
+  if (!ok) return;  // (the whole wave)
+  const int* cr = counts + (long long)row * F;
+  bool bad = false;
+  for (int j = lane; j < F; j += 64) bad |= cr[j] < 0 || cr[j] > frame;
+  if (__syncthreads_or(bad)) return;  // a count that is no frame's: the row is skipped whole
+  if (lane == 0) {
+    const unsigned char* m = mask + (long long)row * F;
+    int j0 = 0;  // the open turn's first frame in this row
+    for (int j = 0; j < F; ++j) {
+      if (m[j] & 1) {
+        if (n == 0) j0 = j;
+        s_plan[j] = open * max_frames + n;
+        if (++n == max_frames) { open ^= 1; n = 0; }
+      } else {
+        s_plan[j] = -1;
+        if (n > 0) {
+          if (n >= min_frames) open ^= 1;
+          else for (int k = j0; k < j; ++k) s_plan[k] = -1;
+          n = 0;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  int* dst = bsyn + (long long)slot * 2 * max_frames;
+  for (int j = lane; j < F; j += 64) {
+    const int p = s_plan[j];
+    if (p >= 0) dst[p] = cr[j];
+  }
+}
+
+extern "C" int afx_k_prov_turn(const int* counts, const unsigned char* mask, const int* hdr, int A, int F, int frame, int min_frames,
+                               int max_frames, const int* state, int* bsyn, int S, void* stream) {
+  if (!counts || !mask || !hdr || !state || !bsyn) return fail("prov_turn: null argument");
+  if (A <= 0 || A > 65535) return fail("prov_turn: 1 to 65535 rows");
+  if (F < 1 || F > TURN_MAX_FRAMES) return fail("prov_turn: 1 to 512 frames in a row");
+  if (frame <= 0) return fail("prov_turn: a frame is a positive number of samples");
+  if (min_frames < F) return fail("prov_turn: min_frames is at least the frames of a row (else a row could complete two turns)");
+  if (min_frames > max_frames) return fail("prov_turn: min_frames is at most max_frames");
+  if (S <= 0) return fail("prov_turn: no slots");
+  if ((long long)max_frames * frame > 0x3fffffff) return fail("prov_turn: a turn of more than 2^30 samples");
+  hipLaunchKernelGGL(prov_turn_kernel, dim3(A), dim3(64), 0, (hipStream_t)stream, counts, mask, hdr, F, frame, min_frames, max_frames,
+                     state, bsyn, S);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail("%s", hipGetErrorString(e));
+}
+
+__global__ __launch_bounds__(256) void prov_turn_sum_kernel(const int* __restrict__ bsyn, int S, int max_frames,
+                                                            const int* __restrict__ rows, int R, int* __restrict__ out) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= R) return;  // (the same for the 64 lanes of a wave; the kernel passes no barrier)
+  const int slot = rows[3 * row], buf = rows[3 * row + 1], m = rows[3 * row + 2];
+  if (slot < 0 || slot >= S || buf < 0 || buf > 1 || m < 1 || m > max_frames) {  // (turn_collect_kernel's guard)
+    if (lane == 0) out[row] = -1;
+    return;
+  }
+  const int* src = bsyn + ((long long)slot * 2 + buf) * max_frames;
+  const int q = max_frames / m, rem = max_frames % m;
+  long long whole = 0, part = 0;
+  int neg = 0;
+  for (int k = lane; k < m; k += 64) {
+    const int v = src[k];
+    neg |= v < 0;
+    whole += v;
+    if (k < rem) part += v;
+  }
+  for (int w = 32; w >= 1; w >>= 1) {
+    whole += __shfl_down(whole, w);
+    part += __shfl_down(part, w);
+    neg |= __shfl_down(neg, w);
+  }
+  if (lane == 0) out[row] = neg ? -1 : (int)min(q * whole + part, 0x7fffffffll);  // (entries <= frame: at most the window)
+}
+
+extern "C" int afx_k_prov_turn_sum(const int* bsyn, int S, int max_frames, const int* rows, int R, int* out, void* stream) {
+  if (!bsyn || !rows || !out) return fail("prov_turn_sum: null argument");
+  if (S <= 0) return fail("prov_turn_sum: no slots");
+  if (max_frames <= 0) return fail("prov_turn_sum: a window of at least 1 frame");
+  if (R <= 0 || R > 65535 * 4) return fail("prov_turn_sum: 1 to 262140 rows");
+  hipLaunchKernelGGL(prov_turn_sum_kernel, dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream, bsyn, S, max_frames, rows, R, out);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : fail("%s", hipGetErrorString(e));
 }

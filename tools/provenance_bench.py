@@ -8,7 +8,13 @@ of this build in one process, on the same arrivals:
   provenance  JitterScorer(ProvenanceScorer(SlidingWindowScorer(stand-in))): the byte ring, one "spans" op per round, one
               afx_k_prov_frames launch per pop, one afx_k_provenance launch per push;
   --gate      both chains with a GatedScorer (plain SpeechGate) under the front: then also the mask, afx_k_prov_compact per
-              gate launch and afx_k_prov_take per pop.
+              gate launch and afx_k_prov_take per pop;
+  --chain lookahead   both chains with a GatedScorer(LookaheadGate()) under the front, the layer's policy through="all": the
+              mask, afx_k_prov_compact_la per gate launch (the delayed frames' counts in gline), afx_k_prov_take per pop;
+  --chain turns       both chains with a TurnScorer (default gate and policy, pushes of one hop, a 4-s window) under the
+              front, the layer around a scorer with hop == window, through="all": afx_k_prov_turn before every afx_k_turn, and
+              per push that scores a turn afx_k_prov_turn_sum beside the collect.  The stand-in traffic is loud throughout, so
+              every turn is a cut one of 400 frames: one scored turn per slot every 16 hops.
 
 Every tick one ``feed(packets, slots, timestamps, score=False)`` with whatever arrived, one ``drain()`` per hop.  Both chains are
 warmed up, then the timed passes alternate between them.  Reported per 250 ms of audio: wall clock around a pass that ends in
@@ -21,11 +27,12 @@ spent in the planner (``_plan``: where the spans rows are made).
               alternating, and the tool's "jitter" line of every run is reported with the build it measured.  The path is
               untouched by the lane, so this tree's figures should sit inside the parent's own run-to-run spread.
 
-On an MI355X every invocation APPENDS its report, with its command line, to profiles/provenance_stream.txt, stamped with
-afx_build_id() (delete the file for a fresh one; what follows a "Reading" heading there is written by hand).  Nothing
+On an MI355X every invocation APPENDS its report, with its command line, to profiles/provenance_stream.txt (--chain turns
+and --chain lookahead: to profiles/provenance_turns.txt), stamped with afx_build_id() (delete the file for a fresh one; what follows a "Reading" heading there is written by hand).  Nothing
 asserts a time.
 
     python tools/provenance_bench.py [--streams 2048] [--packet-ms 20] [--loss 0.02] [--reorder 0.1] [--hops 8] [--reps 5] [--gate]
+    python tools/provenance_bench.py --chain turns | --chain lookahead [the same options]
     python tools/provenance_bench.py --parent DIR [--parent-runs 2]
 """
 import argparse
@@ -44,7 +51,8 @@ from afx._lib import lib  # noqa: E402
 from afx.jitter import JitterScorer  # noqa: E402
 from afx.provenance import ProvenancePolicy, ProvenanceScorer  # noqa: E402
 from afx.streaming import SlidingWindowScorer  # noqa: E402
-from afx.vad import GatedScorer  # noqa: E402
+from afx.turns import TurnScorer  # noqa: E402
+from afx.vad import GatedScorer, LookaheadGate  # noqa: E402
 
 W, H = 64000, 4000
 
@@ -63,14 +71,20 @@ HEADER = ("tools/provenance_bench.py on one MI355X: a jitter front over a summin
           "command line; the kernels were not profiled separately; nothing here is a gate.\n")
 
 
-def record(report):
-    """Print the report; on an MI355X append it, with the command line, to profiles/provenance_stream.txt."""
+HEADER_TURNS = ("tools/provenance_bench.py --chain turns / --chain lookahead on one MI355X: a jitter front over a TurnScorer / a "
+                "look-ahead gate and a summing stand-in scorer, with and without the provenance layer (through=\"all\") below it, "
+                "alternating pass by pass in one process, on the same arrivals.  Every section is one invocation, appended by the tool "
+                "with its command line; nothing here is a gate.\n")
+
+
+def record(report, name="provenance_stream.txt", header=HEADER):
+    """Print the report; on an MI355X append it, with the command line, to profiles/<name>."""
     print("\n".join(report), flush=True)
     if torch.cuda.get_device_properties(0).gcnArchName.startswith("gfx950"):
-        path = os.path.join(ROOT, "profiles", "provenance_stream.txt")
+        path = os.path.join(ROOT, "profiles", name)
         fresh = not os.path.exists(path)
         with open(path, "a") as f:
-            f.write((HEADER if fresh else "") + f"\n(tools/provenance_bench.py {' '.join(sys.argv[1:])})\n" + "\n".join(report) + "\n")
+            f.write((header if fresh else "") + f"\n(tools/provenance_bench.py {' '.join(sys.argv[1:])})\n" + "\n".join(report) + "\n")
         print(f"  appended to {path}", flush=True)
 
 
@@ -106,6 +120,8 @@ def main():
     ap.add_argument("--hops", type=int, default=8, help="hops of audio per timed pass")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--gate", action="store_true", help="a GatedScorer under the front in both chains")
+    ap.add_argument("--chain", choices=["default", "turns", "lookahead"], default="default",
+                    help="turns: a TurnScorer under the front; lookahead: a GatedScorer(LookaheadGate()); the layer's policy is then through=\"all\"")
     ap.add_argument("--parent", default=None, help="a checkout of the parent commit with its library built: measure "
                     "tools/jitter_bench.py of both trees instead")
     ap.add_argument("--parent-runs", type=int, default=2)
@@ -137,10 +153,20 @@ def main():
         return ([audio[s][k * pk:(k + 1) * pk].tobytes() for s, k in rows], [s for s, _ in rows],
                 np.array([(int(origin[s]) + k * pk) % (1 << 32) for s, k in rows], dtype=np.int64))
 
+    if args.gate and args.chain != "default":
+        raise SystemExit("--gate goes with the default chain")
+
     def chain(layer):
-        s = SlidingWindowScorer(Summing(), S, W, H)
-        s = ProvenanceScorer(s, ProvenancePolicy()) if layer else s
+        s = SlidingWindowScorer(Summing(), S, W, W if args.chain == "turns" else H)
+        s = ProvenanceScorer(s, ProvenancePolicy(through="plain" if args.chain == "default" else "all")) if layer else s
+        if args.chain == "turns":
+            s = TurnScorer(s, hop=H)
+        elif args.chain == "lookahead":
+            s = GatedScorer(s, LookaheadGate())
         return JitterScorer(GatedScorer(s) if args.gate else s, rate, "mulaw", depth)
+
+    under = {"default": ", a plain SpeechGate under the front" if args.gate else "", "turns": ", a TurnScorer (pushes of one hop) under the front",
+             "lookahead": ", a GatedScorer(LookaheadGate()) under the front"}[args.chain]
 
     names = ["plain", "provenance"]
     fronts = {"plain": chain(False), "provenance": chain(True)}
@@ -185,7 +211,7 @@ def main():
                     lst.append(v / args.hops)
     report = [f"provenance_bench: build {lib().afx_build_id().decode()}; {torch.cuda.get_device_properties(0).name}; {S} streams, {rate} Hz "
               f"mulaw, {args.packet_ms}-ms packets, depth {args.depth_ms} ms, loss {args.loss:.3f}, reordered {args.reorder:.3f}; a summing "
-              f"stand-in for the model, window {W}, hop {H}{', a plain SpeechGate under the front' if args.gate else ''}; {args.hops} hops "
+              f"stand-in for the model, window {W}, hop {H}{under}; {args.hops} hops "
               f"({ticks} ticks) per pass, the median of {args.reps} timed passes per chain (alternating) after a warm-up pass"]
     med = {}
     for name in names:
@@ -195,13 +221,16 @@ def main():
                       f"{(wall[-1] - wall[0]) / med[name][0] * 100:.1f} % of the median); host time inside feed / drain calls "
                       f"{med[name][1] * 1e3:.2f} ms, of it in the planner {med[name][2] * 1e3:.2f} ms (min {plan[0] * 1e3:.2f}, max {plan[-1] * 1e3:.2f})")
     st = fronts["provenance"].stats()
-    layer = fronts["provenance"].scorer.scorer if args.gate else fronts["provenance"].scorer
+    layer = fronts["provenance"].scorer.scorer if args.gate or args.chain != "default" else fronts["provenance"].scorer
     ps = layer.stats()
     report.append(f"  provenance / plain {med['provenance'][0] / med['plain'][0]:.3f}x wall, planner +{(med['provenance'][2] - med['plain'][2]) * 1e3:.2f} ms "
                   f"per 250 ms of audio; all passes planned {spans[0]} spans ops with {spans[1]} rows")
     report.append(f"  over all streams: {int(st['concealed'].sum())} concealed input samples; the layer saw {int(ps['hops'].sum())} hops, "
                   f"{int(ps['synthetic'].sum())} synthetic 16 kHz samples, withheld {int(ps['withheld'].sum())} scores")
-    record(report)
+    if args.chain == "default":
+        record(report)
+    else:
+        record(report, "provenance_turns.txt", HEADER_TURNS)
 
 
 if __name__ == "__main__":
